@@ -44,6 +44,8 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 VALU_PEAK_LANEOPS = 256 * 4 * 32 * 2.4e9   # 256 CUs x 4 SIMD-32 x 2.4 GHz: a wave64 instruction issues in 2 cycles (MI355X_MICROARCH.md)
 CACHE_VERSION = "v3"          # bump when synth.make_genome_device or the index layout changes
 PROFILE_TAG = "r06"          # profiles/<tag>_pmc*.json: counters collected by scripts/profile_round.sh with this same command (one file per workload)
+DUMP_READS = 1 << 17         # --dump-outputs: reads whose regions are written (a fixed, seeded sample when the batch has more)
+DUMP_BYTES = 64 << 20        # --dump-outputs: at most this much in all
 
 
 def profile_counters(workload_key: str, lib_sha: str):
@@ -136,6 +138,28 @@ def cpu_baseline(g, pac_h, hidx, reads, contigs, n_all: int, n_one: int, n_threa
     return out
 
 
+def dump_outputs(out_dir, regs, n_regs, n_reads):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step -- the batch's alignment regions, records of
+    8 int32 {read, score, qb, qe, rb lo, rb hi, re lo, re hi} in read order -- as float64 rows {read, score, qb, qe, rb, re} in
+    regions.npy, for the reads of regions_reads.npy (all of them, or a fixed seeded sample of DUMP_READS), and the number of regions of
+    every read of the batch in regions_per_read.npy.  Same arguments, same reads: two builds compare file by file."""
+    r = regs[:n_regs].cpu().numpy().astype(np.int64)
+    rb = (r[:, 5] << 32) | (r[:, 4] & 0xFFFFFFFF)
+    re_ = (r[:, 7] << 32) | (r[:, 6] & 0xFFFFFFFF)
+    rows = np.stack([r[:, 0], r[:, 1], r[:, 2], r[:, 3], rb, re_], axis=1)
+    reads = np.arange(n_reads) if n_reads <= DUMP_READS else np.sort(np.random.default_rng(20261015).choice(n_reads, DUMP_READS, replace=False))
+    per_read = np.bincount(r[:, 0], minlength=n_reads)[:n_reads].astype(np.float32)
+    rows = rows[np.isin(r[:, 0], reads)].astype(np.float64)
+    room = (DUMP_BYTES - per_read.nbytes - 8 * len(reads)) // (8 * rows.shape[1])
+    if len(rows) > room:
+        print(f"bench.py: --dump-outputs keeps the first {room} of {len(rows)} sampled regions (at most {DUMP_BYTES >> 20} MB)", file=sys.stderr)
+        rows = rows[:room]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "regions.npy"), rows)
+    np.save(os.path.join(out_dir, "regions_reads.npy"), reads.astype(np.float64))
+    np.save(os.path.join(out_dir, "regions_per_read.npy"), per_read)
+
+
 def verify_against_oracle(check, gpu_seeds, gpu_regs):
     """The GPU's seeds and alignment regions of the first check['n'] reads of a batch against the CPU checker's (oracle seeding ->
     bmh_build_jobs -> oracle ksw_extend2 -> bmh_merge_regs, i.e. what the reference's host code holds at src/bwamem.c:2297-2303).
@@ -175,6 +199,8 @@ def main():
     ap.add_argument("--cpu-sample-1t", type=int, default=int(os.environ.get("BENCH_CPU_SAMPLE_1T", "3000")), help="reads of the one-thread CPU legs")
     ap.add_argument("--verify-sample", type=int, default=int(os.environ.get("BENCH_VERIFY_SAMPLE", "-1")), help="reads of the last timed batch whose GPU seeds and regions are "
                     "compared with the oracle after the timed loops (-1: the CPU sample at N = 1, 10000 per rank at N > 1; 0: off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps write the regions of the last timed step as DIR/*.npy "
+                    "(rank 0; float64, a fixed seeded sample of the reads, at most 64 MB)")
     ap.add_argument("--print-cache-dir", action="store_true", help="print the --index-cache directory this command would use and exit (for the profile scripts)")
     ap.add_argument("--distinct-batches", type=int, default=int(os.environ.get("BENCH_DISTINCT_BATCHES", "4")), help="different read batches the steps take in turn "
                     "(step i works on batch i mod N; 10 puts configs[2]'s 10 M distinct reads through one GPU in 10 steps); at least 2")
@@ -505,6 +531,10 @@ def main():
             stage_ms[kk] = stage_ms.get(kk, 0.0) + v
     stage_ms = {k: v / a.steps for k, v in stage_ms.items()}
     regs_out = [lanes[0].regs, lanes[-1].regs]
+    if a.dump_outputs and rank == 0 and a.steps > 0:
+        # the lane that ran the last timed step (step a.steps - 1), before the PCIe loop below reuses its region buffer
+        last = lanes[(a.steps - 1) % n_lanes]
+        dump_outputs(a.dump_outputs, last.last_regs, last.n_regs, n_reads)
 
     # ---------------- the same steps fed over PCIe: pinned host reads -> H2D -> path -> D2H of the regions, every lane on its own stream
     # (the copies of one lane overlap the kernels of the others)

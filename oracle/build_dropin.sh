@@ -3,12 +3,12 @@
 # Compiles the REFERENCE's own host sources from where they lie -- unchanged -- against this
 # repository's two boundary headers (include/seed_gen.h, include/gasal2_root/GASAL2/include/*.h)
 # and links them with libbwamem_hip.so instead of libseed.a + libgasal.a + CUDA:
-#     build/dropin/bwa-gasal2     (git-ignored; travels to the GPU box with the snapshot)
+#     oracle/_ref/dropin/bwa-gasal2     (git-ignored; travels to the GPU box with the snapshot)
 # Same flags as the reference Makefile (:14,:18), no CUDA, no GASAL2 submodule.
 set -euo pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 REF=${REF:-/root/reference}
-OUT=$ROOT/build/dropin
+OUT=$ROOT/oracle/_ref/dropin
 mkdir -p "$OUT/obj"
 make -s -C "$ROOT/bwa-mem_gpu_amd/csrc"
 CFLAGS="-Wall -Wno-unused-function -O3 -msse4.2 -std=c++11 -fpermissive -w -DHAVE_PTHREAD -DUSE_MALLOC_WRAPPERS"
@@ -20,7 +20,7 @@ pids=()
 for o in $LOBJS $AOBJS; do g++ -c $CFLAGS $INC "$REF/src/$o.c" -o "$OUT/obj/$o.o" & pids+=($!); done
 for o in $SHD; do g++ -c $CFLAGS $INC "$REF/src/$o.cpp" -o "$OUT/obj/$o.o" & pids+=($!); done
 for p in "${pids[@]}"; do wait "$p"; done
-g++ $CFLAGS "$OUT"/obj/*.o -o "$OUT/bwa-gasal2" -L"$ROOT/bwa-mem_gpu_amd" -lbwamem_hip -Wl,-rpath,'$ORIGIN/../../bwa-mem_gpu_amd' \
+g++ $CFLAGS "$OUT"/obj/*.o -o "$OUT/bwa-gasal2" -L"$ROOT/bwa-mem_gpu_amd" -lbwamem_hip -Wl,-rpath,'$ORIGIN/../../../bwa-mem_gpu_amd' \
     -Wl,--unresolved-symbols=ignore-all -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lm -lz -ldl -lpthread -lrt
 echo "built $OUT/bwa-gasal2"
 # Second binary for the root-cause demonstration of INTEGRATION.md section 2 (-t >= 4): identical, except that the four places of
@@ -33,7 +33,7 @@ sed -n '2295p;2313p' "$REF/src/bwamem.c" | grep -c 'seq\[j\]\.' | grep -qx 2 || 
 sed -e '2228s/seq\[r\]/seq[r + batch_start_idx]/' -e '2251s/seq\[r\]/seq[r + batch_start_idx]/' \
     -e '2295s/seq\[j\]/seq[j + batch_start_idx]/' -e '2313s/seq\[j\]/seq[j + batch_start_idx]/' "$REF/src/bwamem.c" > "$TMPD/bwamem.c"
 g++ -c $CFLAGS $INC -I"$REF/src" "$TMPD/bwamem.c" -o "$OUT/obj/bwamem.o"
-g++ $CFLAGS "$OUT"/obj/*.o -o "$OUT/bwa-gasal2-seqidx" -L"$ROOT/bwa-mem_gpu_amd" -lbwamem_hip -Wl,-rpath,'$ORIGIN/../../bwa-mem_gpu_amd' \
+g++ $CFLAGS "$OUT"/obj/*.o -o "$OUT/bwa-gasal2-seqidx" -L"$ROOT/bwa-mem_gpu_amd" -lbwamem_hip -Wl,-rpath,'$ORIGIN/../../../bwa-mem_gpu_amd' \
     -Wl,--unresolved-symbols=ignore-all -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lm -lz -ldl -lpthread -lrt
 rm -rf "$TMPD" "$OUT/obj"
 echo "built $OUT/bwa-gasal2-seqidx"

@@ -1,6 +1,6 @@
 """Parity of the host job builder (bmh_build_jobs) with the REFERENCE's own host code.
 
-Runs build/dropin/bwa-gasal2 (the reference's src/*.c, unchanged, on our library) with BMH_GASAL_DUMP
+Runs oracle/_ref/dropin/bwa-gasal2 (the reference's src/*.c, unchanged, on our library) with BMH_GASAL_DUMP
 so every extension job its mem_chain/mem_chain_flt/mem_chain2aln submit is recorded, then builds the
 jobs for the same reads with bmh_build_jobs from our seeds and compares the two job multisets
 (h0, query bases, target bases) exactly.  Also checks the best region score of every read against
@@ -14,7 +14,7 @@ import bwamem_hip as B
 from bwamem_hip import fmindex, synth
 from bwamem_hip.lib import HostJobs
 
-exe = os.path.join(ROOT, "build", "dropin", "bwa-gasal2")
+exe = os.path.join(ROOT, "oracle", "_ref", "dropin", "bwa-gasal2")
 work = sys.argv[1] if len(sys.argv) > 1 else "/tmp/jobs_vs_ref"
 n_genome = int(float(sys.argv[2])) if len(sys.argv) > 2 else 2_000_000
 n_reads = int(float(sys.argv[3])) if len(sys.argv) > 3 else 5000

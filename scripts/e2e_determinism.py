@@ -1,7 +1,7 @@
 import sys, os, subprocess, io
 sys.path.insert(0, "bwa-mem_gpu_amd")
 work = sys.argv[1]; threads = sys.argv[2]
-exe = os.path.abspath("build/dropin/bwa-gasal2")
+exe = os.path.abspath("oracle/_ref/dropin/bwa-gasal2")
 prefix = os.path.join(work, "g.fa"); fq = os.path.join(work, "reads.fa")
 def ref(t):
     r = subprocess.run([exe, "gase_aln", "-t", t, "-l", "150", "-p", prefix, fq], stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=work)

@@ -1,5 +1,5 @@
 """End-to-end drop-in run: the REFERENCE's own `bwa-gasal2 gase_aln` host code (compiled unchanged by
-scripts/build_dropin.sh, linked against libbwamem_hip.so) on BASELINE.json configs[0]'s shape:
+oracle/build_dropin.sh, linked against libbwamem_hip.so) on BASELINE.json configs[0]'s shape:
 10k synthetic 150 bp single-end reads vs an E. coli-size (4.64 Mbp) seeded genome.  Checks the SAM
 against the simulation truth (position/strand of every read).
 -K keeps the whole file in one batch whatever -t is (insert-size statistics are per batch).  NOTE: with -t >= 4 the
@@ -15,9 +15,9 @@ import numpy as np
 import torch
 from bwamem_hip import fmindex, synth
 
-exe = os.path.join(ROOT, "build", "dropin", os.environ.get("E2E_EXE", "bwa-gasal2"))      # E2E_EXE=bwa-gasal2-seqidx: the build with the reference's four batch-relative seq[] indices corrected (scripts/build_dropin.sh)
+exe = os.path.join(ROOT, "oracle", "_ref", "dropin", os.environ.get("E2E_EXE", "bwa-gasal2"))      # E2E_EXE=bwa-gasal2-seqidx: the build with the reference's four batch-relative seq[] indices corrected (oracle/build_dropin.sh)
 if not os.path.exists(exe):
-    sys.exit("build/dropin/bwa-gasal2 missing: run scripts/build_dropin.sh in the build container")
+    sys.exit("oracle/_ref/dropin/bwa-gasal2 missing: run oracle/build_dropin.sh in the build container")
 work = sys.argv[1] if len(sys.argv) > 1 else "/tmp/e2e_dropin"
 n_genome = int(float(sys.argv[2])) if len(sys.argv) > 2 else 4_640_000
 n_reads = int(float(sys.argv[3])) if len(sys.argv) > 3 else 10_000

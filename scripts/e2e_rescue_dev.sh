@@ -1,5 +1,5 @@
 #!/bin/bash
-# Live comparisons of paired read sets (the reference's own host code in build/dropin/bwa-gasal2 against the device-resident path) with the mate rescue's
+# Live comparisons of paired read sets (the reference's own host code in oracle/_ref/dropin/bwa-gasal2 against the device-resident path) with the mate rescue's
 # windows found on the device (BMH_ALIGNER_RESCUE_DEV=1, the host's walk beside it: BMH_RESCUE_CHECK=1) -> gpurun_out/r06_e2e_rescue_dev.txt
 cd ${GRAFT_REPO_ROOT:-$(dirname $0)/..}
 export BMH_ALIGNER_RESCUE_DEV=1 BMH_RESCUE_CHECK=1

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Root cause of the reference's garbage records at -t >= 4, shown on the GPU box:
-#   stock build of the reference host code (build/dropin/bwa-gasal2) vs the build with the four batch-relative seq[] indices of
-#   mem_align1_core made absolute (bwa-gasal2-seqidx, scripts/build_dropin.sh), run three times each at -t 8 WITHOUT -K (several
+#   stock build of the reference host code (oracle/_ref/dropin/bwa-gasal2) vs the build with the four batch-relative seq[] indices of
+#   mem_align1_core made absolute (bwa-gasal2-seqidx, oracle/build_dropin.sh), run three times each at -t 8 WITHOUT -K (several
 #   chunks, work stealing) on a hard single-end set: run-to-run differences and records with an impossible AS.
 # usage: bash scripts/e2e_seqidx_probe.sh [reads=200000]
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; cd $R

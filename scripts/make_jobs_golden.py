@@ -1,5 +1,5 @@
 """Golden vector for the host job builder, produced on the GPU box by the REFERENCE's own host code:
-runs build/dropin/bwa-gasal2 with BMH_GASAL_DUMP on a small seeded read set and stores, next to the inputs of
+runs oracle/_ref/dropin/bwa-gasal2 with BMH_GASAL_DUMP on a small seeded read set and stores, next to the inputs of
 bmh_build_jobs (genome seed/size, reads, seeds), the multiset of extension jobs the reference submitted
 (as sorted SHA-1 digests of h0|query|target) and the AS tag of every read.  Output: gpurun_out/jobs_golden.npz,
 to be committed as tests/golden/jobs_golden.npz."""
@@ -146,7 +146,7 @@ dump = os.path.join(work, "jobs.bin")
 if os.path.exists(dump): os.remove(dump)
 sam = os.path.join(work, "o.sam")
 with open(sam, "w") as f:
-    subprocess.check_call([os.path.join(ROOT, "build", "dropin", "bwa-gasal2"), "gase_aln", "-t", "1", "-l", str(L)] + EXTRA + [prefix, fq], stdout=f,
+    subprocess.check_call([os.path.join(ROOT, "oracle", "_ref", "dropin", "bwa-gasal2"), "gase_aln", "-t", "1", "-l", str(L)] + EXTRA + [prefix, fq], stdout=f,
                           stderr=subprocess.DEVNULL, cwd=work, env=dict(os.environ, BMH_GASAL_DUMP=dump))
 raw = np.fromfile(dump, dtype=np.uint8); p = 0; digs = []
 while p < raw.size:
@@ -178,7 +178,7 @@ def sam_lines(path):
     return rows
 sam_a = os.path.join(work, "o_all.sam")
 with open(sam_a, "w") as f:
-    subprocess.check_call([os.path.join(ROOT, "build", "dropin", "bwa-gasal2"), "gase_aln", "-a", "-t", "1", "-l", str(L)] + EXTRA + [prefix, fq], stdout=f,
+    subprocess.check_call([os.path.join(ROOT, "oracle", "_ref", "dropin", "bwa-gasal2"), "gase_aln", "-a", "-t", "1", "-l", str(L)] + EXTRA + [prefix, fq], stdout=f,
                           stderr=subprocess.DEVNULL, cwd=work)
 def pack(rows):
     return dict(read=np.array([r[0] for r in rows], np.int32), flag=np.array([r[1] for r in rows], np.int32), pos=np.array([r[2] for r in rows], np.int64),

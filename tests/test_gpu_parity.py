@@ -397,13 +397,13 @@ def test_gasal_shim_matches_oracle(hip, oracle, tmp_path):
 
 
 def test_reference_gase_aln_end_to_end(hip, tmp_path):
-    """BASELINE configs[0] shape through the REFERENCE's own host code: build/dropin/bwa-gasal2 is the
+    """BASELINE configs[0] shape through the REFERENCE's own host code: oracle/_ref/dropin/bwa-gasal2 is the
     reference's src/*.c compiled unchanged against include/seed_gen.h + include/gasal2_root and linked
-    with libbwamem_hip.so (scripts/build_dropin.sh, build container only)."""
+    with libbwamem_hip.so (oracle/build_dropin.sh, build container only)."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.exists(os.path.join(root, "build", "dropin", "bwa-gasal2")):
-        pytest.skip("build/dropin/bwa-gasal2 not built (needs /root/reference at build time)")
+    if not os.path.exists(os.path.join(root, "oracle", "_ref", "dropin", "bwa-gasal2")):
+        pytest.skip("oracle/_ref/dropin/bwa-gasal2 not built (needs the reference sources at build time)")
     # single-end (configs[0] shape), interleaved paired-end with -p (configs[3] shape), and hard pairs (diverged / relocated /
     # random / chimeric mates) under a non-default option set given to both sides
     # (the first run is configs[0] at its stated size: 10 000 reads vs a 4.64 Mbp genome, -t 1)
@@ -421,9 +421,9 @@ def test_reference_gase_aln_end_to_end(hip, tmp_path):
     assert r.returncode == 0 and "SAM IDENTICAL" in out, out[-3000:]
     # ... and on a hard set (4 % substitutions, indels, chimeric reads, every 7th read across a 12-60 bp deletion) it does so once the four
     # batch-relative seq[] indices of mem_align1_core (src/bwamem.c:2228, 2251, 2295, 2313) are made absolute -- the build
-    # bwa-gasal2-seqidx of scripts/build_dropin.sh; as shipped, :2313 hands mem_sort_dedup_patch ANOTHER read's bases, which a second
+    # bwa-gasal2-seqidx of oracle/build_dropin.sh; as shipped, :2313 hands mem_sort_dedup_patch ANOTHER read's bases, which a second
     # worker may be converting in place at that moment (:2052-2053): the garbage scores of INTEGRATION.md section 2
-    if os.path.exists(os.path.join(root, "build", "dropin", "bwa-gasal2-seqidx")):
+    if os.path.exists(os.path.join(root, "oracle", "_ref", "dropin", "bwa-gasal2-seqidx")):
         env = dict(os.environ, E2E_EXE="bwa-gasal2-seqidx", E2E_LONGDEL="7", E2E_TAG="seqidx_t8")
         r = subprocess.run([sys.executable, os.path.join(root, "scripts", "e2e_dropin.py"), str(tmp_path), "2000000", "30000", "8", "se_hard"],
                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env)
@@ -437,8 +437,8 @@ def test_dropin_with_several_device_workers(hip, tmp_path):
     its device differs) -- and the gasal storages are spread over the devices.  The reference binary must write the same SAM."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.exists(os.path.join(root, "build", "dropin", "bwa-gasal2")):
-        pytest.skip("build/dropin/bwa-gasal2 not built (needs /root/reference at build time)")
+    if not os.path.exists(os.path.join(root, "oracle", "_ref", "dropin", "bwa-gasal2")):
+        pytest.skip("oracle/_ref/dropin/bwa-gasal2 not built (needs the reference sources at build time)")
     env = dict(os.environ, BMH_DEVICES="2", BMH_SEED_BATCH_READS="700")
     r = subprocess.run([sys.executable, os.path.join(root, "scripts", "e2e_dropin.py"), str(tmp_path), "2000000", "4000", "2"],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env)
@@ -476,11 +476,11 @@ def test_index_replicate_and_shard_range(hip, oracle):
 
 def test_host_job_builder_matches_reference_host_code(hip, tmp_path):
     """bmh_build_jobs (chain -> chain_flt -> chain2aln restatement) vs the job stream the REFERENCE's own host
-    code submits (build/dropin/bwa-gasal2 with BMH_GASAL_DUMP), and best region score vs the SAM AS tag."""
+    code submits (oracle/_ref/dropin/bwa-gasal2 with BMH_GASAL_DUMP), and best region score vs the SAM AS tag."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.exists(os.path.join(root, "build", "dropin", "bwa-gasal2")):
-        pytest.skip("build/dropin/bwa-gasal2 not built (needs /root/reference at build time)")
+    if not os.path.exists(os.path.join(root, "oracle", "_ref", "dropin", "bwa-gasal2")):
+        pytest.skip("oracle/_ref/dropin/bwa-gasal2 not built (needs the reference sources at build time)")
     # (the -W 5 and the 800 bp runs go through the reference's seed filter mem_flt_chained_seeds / mem_seed_sw, src/bwamem.c:970-991)
     for args in (["1500000", "3000", "150"], ["1500000", "1500", "300"], ["1500000", "2000", "150", "-W", "5"], ["1500000", "300", "740"]):
         r = subprocess.run([sys.executable, os.path.join(root, "scripts", "check_jobs_vs_reference.py"), str(tmp_path)] + args,

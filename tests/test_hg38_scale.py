@@ -181,15 +181,15 @@ def test_baseline_configs_1_3_and_4_at_full_size(variant):
 @pytest.mark.parametrize("shape", ["pairs_150bp", "single_300bp"])
 def test_reference_host_code_at_hg38_scale(hip, tmp_path, shape):
     """The REFERENCE's own host code against the device-resident path on the 3.1 Gbp genome (24 sequences, seq_len 6.2e9 > 2^32; index built by
-    bmh_index_build and written in the reference's file layout for both sides to load): build/dropin/bwa-gasal2 -- the reference's src/*.c compiled
+    bmh_index_build and written in the reference's file layout for both sides to load): oracle/_ref/dropin/bwa-gasal2 -- the reference's src/*.c compiled
     unchanged against include/seed_gen.h + include/gasal2_root, linked with libbwamem_hip.so -- at -t 1 beside bwamem_hip.aligner on 100 000 hard
     pairs of 150 bp (configs[3]'s shape: diverged / relocated / random / chimeric mates) and on 50 000 hard single-end reads of 300 bp (configs[4]'s):
     every SAM record identical.  This is the comparison of the host-side record logic (positions, TLEN, pairing windows, the mate rescue's windows,
     CIGARs) with the reference's own code at coordinates that do not fit 32 bits (scripts/e2e_hg.sh baseline, now inside the driver-run suite)."""
     import subprocess
     import sys
-    if not os.path.exists(os.path.join(ROOT, "build", "dropin", "bwa-gasal2")):
-        pytest.skip("build/dropin/bwa-gasal2 not built (needs /root/reference at build time)")
+    if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "dropin", "bwa-gasal2")):
+        pytest.skip("oracle/_ref/dropin/bwa-gasal2 not built (needs the reference sources at build time)")
     n, mode, rl = ("200000", "pe_hard", "150") if shape == "pairs_150bp" else ("50000", "se_hard", "300")
     env = dict(os.environ, E2E_CONTIGS="24", E2E_NATIVE_BUILD="1", E2E_READLEN=rl, E2E_TAG="gputest_" + shape,
                E2E_GENOME_KW="{'repeat_frac': 0.3, 'repeat_copies': (10, 3000), 'repeat_len': (300, 3000), 'repeat_div': 0.03}")
