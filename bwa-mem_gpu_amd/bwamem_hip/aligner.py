@@ -151,7 +151,11 @@ def read_fasta_reads_numpy(path: str) -> ReadSet:
 
 
 class Aligner:
-    def __init__(self, prefix: str | None, device: str = "cuda:0", n_threads: int = 0, _mem=None, sa_intv: int | None = 1):
+    def __init__(self, prefix: str | None, device: str = "cuda:0", n_threads: int = 0, _mem=None, sa_intv: int | None = 1,
+                 long_reads: bool = False):
+        # long_reads: extension flanks of 769 .. EXT_LONG_MAX bases go to the long-query kernel (bmh_extend_batch_long) instead of
+        # raising; batches without a read beyond 700 bp take the same path either way
+        self.long_reads = bool(long_reads)
         self.L = load_library()
         self.dev = torch.device(device)
         if _mem is not None:                                  # (index, contigs, packed reference) already in memory: from_memory()
@@ -297,7 +301,7 @@ class Aligner:
         ext_p = ExtParams(e.a, e.b, e.o_del, e.e_del, e.o_del, e.e_del, e.zdrop, e.end_bonus)
         cw = None
         if host_jobs:
-            from .lib import HostJobs, seeds_to_host, extend_batch
+            from .lib import EXT_LONG_MAX, HostJobs, seeds_to_host, extend_batch
             hj = HostJobs(self.l_pac, codes, offs, lens, seeds_to_host(s, n), n_threads=self.n_threads, opt=self.copt,
                           contigs=self.contigs if len(self.contigs) > 1 else None, pac=self.pac)
             nr, nj = hj.n_regs, hj.n_jobs
@@ -305,10 +309,14 @@ class Aligner:
             out3 = torch.zeros(max(nj, 1), 3, dtype=torch.int32, device=dev)
             if nj:
                 d = [torch.from_numpy(np.ascontiguousarray(x).view(np.int32) if x.dtype == np.uint32 else np.ascontiguousarray(x)).to(dev) for x in hj.jobs()]
-                extend_batch(*d, out3, params=ext_p)
-                # a flank longer than the DP kernels take (768 query bases: a read beyond ~790 bp seeded near one end) comes back as
-                # INT32_MIN and must never reach the merge; the device builder refuses such reads itself
+                extend_batch(*d, out3, params=ext_p, long_queries=self.long_reads)
+                # a flank longer than the DP kernels take (768 query bases: a read beyond ~790 bp seeded near one end; with long_reads
+                # EXT_LONG_MAX) comes back as INT32_MIN and must never reach the merge; the device builder refuses such reads itself
                 n_bad = int(L.bmh_extend_last_unsupported())
+                if n_bad and self.long_reads:
+                    hj.free()
+                    raise NotImplementedError(f"{n_bad} extension job(s) of this batch have a query side longer than {EXT_LONG_MAX} bases, "
+                                              "the cap of the long-query extension kernel")
                 if n_bad:
                     hj.free()
                     raise NotImplementedError(f"{n_bad} extension job(s) of this batch have a query side longer than 768 bases: reads this long are beyond the "
@@ -402,6 +410,23 @@ class Aligner:
             cg2, aln2, md2 = cigar_batch(self.index, r, o, l, fin_t, len(over), sel_t=torch.from_numpy(sel[over].copy()).to(dev), params=self.ep,
                                          opt_w=self.copt.w, max_cigar=max_cigar, md_cap=md_cap)
             aln_h[over] = aln2.cpu().numpy(); cg_h[over] = cg2.cpu().numpy().view(np.uint32); md_h[over] = md2.cpu().numpy()
+            over2 = np.flatnonzero(aln_h[:, 7] & 9)
+            if over2.size and self.long_reads:
+                # long regions: buffers sized from the regions themselves -- every CIGAR op takes a base of one side (at most
+                # qlen + rlen ops, plus two clips), and MD holds at most a number and a base (or '^' and bases) per reference base
+                rg = fin[sel[over2]]
+                ql = int((rg[:, 3] - rg[:, 2]).max())
+                rl = int(((rg[:, 6].astype(np.int64) & 0xFFFFFFFF | rg[:, 7].astype(np.int64) << 32)
+                          - (rg[:, 4].astype(np.int64) & 0xFFFFFFFF | rg[:, 5].astype(np.int64) << 32)).max())
+                mc, mdc = ql + rl + 8, 9 * rl + 16
+                cg3, aln3, md3 = cigar_batch(self.index, r, o, l, fin_t, len(over2), sel_t=torch.from_numpy(sel[over2].copy()).to(dev), params=self.ep,
+                                             opt_w=self.copt.w, max_cigar=mc, md_cap=mdc)
+                aln3 = aln3.cpu().numpy(); cg3 = cg3.cpu().numpy().view(np.uint32); md3 = md3.cpu().numpy()
+                if mc > cg_h.shape[1]:
+                    cg_h = np.concatenate([cg_h, np.zeros((len(sel), mc - cg_h.shape[1]), np.uint32)], 1)
+                if mdc > md_h.shape[1]:
+                    md_h = np.concatenate([md_h, np.zeros((len(sel), mdc - md_h.shape[1]), np.uint8)], 1)
+                aln_h[over2] = aln3; cg_h[over2] = 0; cg_h[over2, :mc] = cg3; md_h[over2] = 0; md_h[over2, :mdc] = md3
         if (aln_h[:, 7] & ~2).any():
             raise RuntimeError("bmh_cigar_batch flagged an alignment (CIGAR or MD longer than the buffers)")
         return aln_h, cg_h, md_h

@@ -54,7 +54,11 @@ struct cigar_args_t {
 	unsigned long long *z_total;    // bytes of direction matrices of the fast jobs (running sum while classifying)
 	uint8_t *z; uint32_t *rev;      // direction matrices; reversed CIGAR scratch [n][max_cigar]
 	int use_list;                   // wave-per-region kernel: 0 = all jobs, 1 = list[CG_SLOW]
+	// regions beyond CG_LDS_MAX bases (either side): cigar_kernel<1, 0, true> takes them, the LDS forms skip them
+	int long_split;
+	uint8_t *lws; unsigned long long lws_stride;   // per-workgroup HBM scratch of the long form: bases, two H rows, E
 };
+#define CG_LDS_MAX 704
 
 enum { CG_REJECT = 0, CG_TRIVIAL = 1, CG_F2 = 2, CG_F3 = 3, CG_F5 = 4, CG_F10 = 5, CG_F16 = 6, CG_SLOW = 7, CG_NKIND = 8 };
 struct cg_job_t { int32_t w, n_col, score, kind; unsigned long long zoff; };
@@ -137,6 +141,50 @@ __device__ int g_fill(const cigar_args_t &A, const uint8_t *qs, const uint8_t *t
 	return __builtin_amdgcn_readlane(src, jl / C);
 }
 
+// g_fill for regions beyond CG_LDS_MAX: the same cells, 64 columns at a time along the row's band [beg,end) (the F scan
+// carried from chunk to chunk), H of the previous / current row and E in HBM rows (absolute columns).  An in-band cell
+// only ever reads in-band cells of the previous row (its diagonal j-1 >= beg(i-1), < end(i-1)) or the first-column
+// value, so the cells outside the band that g_fill carries along are never needed here.
+__device__ int g_fill_long(const cigar_args_t &A, const uint8_t *qs, const uint8_t *ts, int qlen, int rlen, int w, uint8_t *z, int n_col, int lane,
+                           int *hp, int *hc, int *ev)
+{
+	const int oe_del = A.o_del + A.e_del, oe_ins = A.o_ins + A.e_ins;
+	for (int j = lane; j < qlen; j += 64) { hp[j] = (j + 1 <= w) ? -(A.o_ins + A.e_ins * (j + 1)) : G_NEG; ev[j] = G_NEG; }      // H(-1, j)
+	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_s_waitcnt(0);
+	for (int i = 0; i < rlen; ++i) {
+		const int ti = (int)ts[i];
+		const int beg = i > w ? i - w : 0, end = i + w + 1 < qlen ? i + w + 1 : qlen;
+		const int fill0 = i == 0 ? 0 : (i - 1 > w ? G_NEG : -(A.o_del + A.e_del * i));           // H(i-1, -1)
+		int carry = G_NEG + A.e_ins * (beg - 1);                                                 // the seed f(beg) = MINUS_INF
+		uint8_t *zr = z + (size_t)i * n_col - beg;
+		for (int s = beg; s < end; s += 64) {
+			const int j = s + lane;
+			const bool act = j < end;
+			const int hd = !act ? 0 : j == 0 ? fill0 : hp[j - 1];
+			const int m = hd + g_sc(A, ti, act ? (int)qs[j] : 4);
+			const int g = act ? m - oe_ins + A.e_ins * j : G_SENT;
+			const int incl = g_wave_scan_max(g);
+			const int run = max(g_wave_shr1(incl, G_SENT), carry);
+			carry = max(carry, __builtin_amdgcn_readlane(incl, 63));
+			const int f = run - A.e_ins * (j - 1);
+			const int e = act ? ev[j] : G_NEG;
+			int d = m >= e ? 0 : 1;
+			int h = max(m, e);
+			d = h >= f ? d : 2;
+			h = max(h, f);
+			int t = m - oe_del, e2 = e - A.e_del;
+			d |= e2 > t ? 1 << 2 : 0;
+			e2 = max(e2, t);
+			t = m - oe_ins;
+			d |= (f - A.e_ins) > t ? 2 << 4 : 0;
+			if (act) { ev[j] = e2; zr[j] = (uint8_t)d; hc[j] = h; }
+		}
+		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_s_waitcnt(0);
+		int *tmp = hp; hp = hc; hc = tmp;
+	}
+	return hp[qlen - 1];
+}
+
 struct md_out_t { char *p; int len, cap; };
 __device__ __forceinline__ void md_putc(md_out_t &m, char c, int lane) { if (m.len + 1 < m.cap && lane == 0) m.p[m.len] = c; ++m.len; }
 __device__ __forceinline__ void md_putw(md_out_t &m, int v, int lane)
@@ -153,14 +201,17 @@ __device__ __forceinline__ void md_putw(md_out_t &m, int v, int lane)
 	}
 }
 
-template <int C, int CLO>       // handles jobs with CLO < ceil(qlen / 64) <= C
+// LONG: the form for regions beyond CG_LDS_MAX bases (bases, H / E rows and the direction matrix in HBM; g_fill_long)
+template <int C, int CLO, bool LONG = false>       // handles jobs with CLO < ceil(qlen / 64) <= C (LONG: every job beyond CG_LDS_MAX)
 __global__ void __launch_bounds__(64) cigar_kernel(cigar_args_t A)
 {
 	extern __shared__ __align__(16) uint8_t g_lds[];
 	const int lane = threadIdx.x;
-	uint8_t *qs = g_lds, *ts = g_lds + A.max_len;
-	uint32_t *rev = (uint32_t *)(g_lds + 2 * (size_t)A.max_len);
-	uint8_t *z_l = g_lds + 2 * (size_t)A.max_len + 4 * (size_t)A.max_cigar;
+	uint8_t *lw = LONG ? A.lws + (size_t)blockIdx.x * A.lws_stride : nullptr;
+	int *l_h0 = LONG ? (int *)(lw + 2 * (size_t)A.max_len) : nullptr, *l_h1 = l_h0 + A.max_len, *l_e = l_h1 + A.max_len;
+	uint8_t *qs = LONG ? lw : g_lds, *ts = LONG ? lw + A.max_len : g_lds + A.max_len;
+	uint32_t *rev = (uint32_t *)(g_lds + (LONG ? 0 : 2 * (size_t)A.max_len));
+	uint8_t *z_l = g_lds + (LONG ? 0 : 2 * (size_t)A.max_len) + 4 * (size_t)A.max_cigar;
 	uint8_t *z_g = A.z_slab + (size_t)blockIdx.x * A.z_slab_stride;
 	const uint32_t n_iter = A.use_list ? A.list_n[CG_SLOW] : A.n;
 	for (uint32_t it_ = blockIdx.x; it_ < n_iter; it_ += gridDim.x) {
@@ -172,7 +223,12 @@ __global__ void __launch_bounds__(64) cigar_kernel(cigar_args_t A)
 		const long long rb = (long long)(uint32_t)R[4] | (long long)R[5] << 32, re = (long long)(uint32_t)R[6] | (long long)R[7] << 32;
 		const int qlen = qe - qb, l_query = (int)A.lens[read];
 		const int need = (qlen + 63) >> 6;
-		if (need <= CLO || need > C) { if (!(CLO == 0 && need <= 0)) continue; }
+		const bool is_long = qlen > CG_LDS_MAX || (long long)(re - rb) > CG_LDS_MAX;
+		if (LONG) { if (!is_long) continue; }
+		else {
+			if (need <= CLO || need > C) { if (!(CLO == 0 && need <= 0)) continue; }
+			if (A.long_split && is_long && qlen > 0 && rb < re && !(rb < A.l_pac && re > A.l_pac)) continue;      // the long form's
+		}
 		int32_t *out = A.aln + 8 * (size_t)job;
 		uint32_t *cg = A.cigar + (size_t)job * A.max_cigar;
 		md_out_t md; md.p = A.md ? A.md + (size_t)job * A.md_cap : nullptr; md.len = 0; md.cap = A.md ? A.md_cap : 0;
@@ -218,7 +274,8 @@ __global__ void __launch_bounds__(64) cigar_kernel(cigar_args_t A)
 				lds_z = (size_t)n_col * rlen <= A.z_lds_bytes;
 				uint8_t *z = lds_z ? z_l : z_g;
 				if (!lds_z && (unsigned long long)n_col * rlen > A.z_slab_stride) { flags |= 4; break; }
-				score = g_fill<C>(A, qs, ts, qlen, rlen, w, z, n_col, lane);
+				if constexpr (LONG) score = g_fill_long(A, qs, ts, qlen, rlen, w, z, n_col, lane, l_h0, l_h1, l_e);
+				else score = g_fill<C>(A, qs, ts, qlen, rlen, w, z, n_col, lane);
 				__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_s_waitcnt(0);
 				// traceback (ksw.c:1213-1235): state 0 = H (bits 0-1), 1 = E (bits 2-3), 2 = F (bits 4-5); ops come out reversed
 				int i = rlen - 1, k = (i + w + 1 < qlen ? i + w + 1 : qlen) - 1, state = 0, cur_op = -1, cur_len = 0;
@@ -681,13 +738,14 @@ __global__ void __launch_bounds__(256) cigar_size_kernel(const int32_t *regs, in
 struct cigar_scratch_t {
 	unsigned long long *d_sizes = nullptr;       // [0] largest rectangle [1] longest sequence [2] fast-path matrix bytes; then CG_NKIND list counts (u32)
 	uint8_t *slab = nullptr; size_t slab_bytes = 0;
+	uint8_t *lslab = nullptr; size_t lslab_bytes = 0;            // the long form's direction matrices + bases / H / E rows
 	cg_job_t *jobs = nullptr; uint32_t *lists = nullptr, *rev = nullptr; size_t cap_n = 0, cap_rev = 0; uint8_t *z = nullptr; size_t z_bytes = 0;
 	void drop()
 	{
-		void *ps[] = {d_sizes, slab, jobs, lists, rev, z};
+		void *ps[] = {d_sizes, slab, jobs, lists, rev, z, lslab};
 		for (void *q : ps) if (q) (void)hipFree(q);
-		d_sizes = nullptr; slab = nullptr; jobs = nullptr; lists = rev = nullptr; z = nullptr;
-		slab_bytes = cap_n = cap_rev = z_bytes = 0;
+		d_sizes = nullptr; slab = nullptr; jobs = nullptr; lists = rev = nullptr; z = nullptr; lslab = nullptr;
+		slab_bytes = cap_n = cap_rev = z_bytes = lslab_bytes = 0;
 	}
 };
 static std::mutex g_cs_mu;
@@ -770,9 +828,12 @@ extern "C" int bmh_cigar_batch(const bmh_index_t *idx, const uint8_t *d_reads, c
 	if (!slow_only && getenv("BMH_CIGAR_STATS"))
 		fprintf(stderr, "[cigar] %u regions: band<=32 %u, <=48 %u, <=80 %u, <=160 %u, <=256 %u, wide/other %u; direction matrices %.1f MB\n", n, h_list_n[CG_F2], h_list_n[CG_F3], h_list_n[CG_F5], h_list_n[CG_F10],
 		        h_list_n[CG_F16], h_list_n[CG_SLOW], (double)h[2] / 1e6);
-	const uint32_t max_len = (uint32_t)((h[1] + 15) & ~15ull);
-	if (max_len > 704) { bmh_set_error("bmh_cigar_batch: a region spans %llu bases (limit 704)", h[1]); return BMH_ECAPACITY; }
+	// regions beyond CG_LDS_MAX bases: the LDS forms below are launched as for a batch of at most CG_LDS_MAX and skip them; the long
+	// form takes them after the others
+	const uint32_t long_len = (uint32_t)((h[1] + 15) & ~15ull);
+	const uint32_t max_len = long_len > CG_LDS_MAX ? CG_LDS_MAX : long_len;
 	a.max_len = max_len;
+	a.long_split = long_len > CG_LDS_MAX;
 	if (!slow_only) {
 		// fast path: direction matrices of all single-band jobs at once (HBM is large), then one lane per region
 		if (g_cs.z_bytes < h[2] + 256) { const size_t c = (size_t)h[2] + (size_t)h[2] / 4 + 4096; if (cg_grow(g_cs.z, c) != BMH_OK) return BMH_ENOMEM; g_cs.z_bytes = c; }
@@ -797,6 +858,7 @@ extern "C" int bmh_cigar_batch(const bmh_index_t *idx, const uint8_t *d_reads, c
 	if (grid > 256u * 16) grid = 256u * 16;
 	if (grid > n) grid = n;
 	a.z_slab_stride = (h[0] + 255) & ~255ull;
+	if (a.long_split) a.z_slab_stride = (unsigned long long)max_len * max_len;      // (the LDS forms' largest rectangle)
 	const size_t slab = (size_t)a.z_slab_stride * grid;
 	if (g_cs.slab_bytes < slab) {
 		if (g_cs.slab) (void)hipFree(g_cs.slab);
@@ -813,6 +875,32 @@ extern "C" int bmh_cigar_batch(const bmh_index_t *idx, const uint8_t *d_reads, c
 	if (rc == BMH_OK && max_len > 320) rc = launch_cigar<8, 5>(a, grid, lds, st);
 	if (rc == BMH_OK && max_len > 512) rc = launch_cigar<11, 8>(a, grid, lds, st);
 	if (rc != BMH_OK) return rc;
+	if (a.long_split) {
+		// one wave per long region; its direction matrix holds at most min(length, 2 (opt_w << 2) + 1) columns of every row (a
+		// band that does not fit is flagged 4), the bases and the H / E rows of absolute columns sit beside it
+		cigar_args_t b = a;
+		b.max_len = long_len;
+		b.z_lds_bytes = 0;
+		const unsigned long long band = 2ull * ((unsigned long long)opt_w << 2) + 1;
+		b.z_slab_stride = ((band < long_len ? band : long_len) * long_len + 255) & ~255ull;
+		b.lws_stride = (2ull * long_len + 3ull * 4 * long_len + 255) & ~255ull;
+		const unsigned long long per = b.z_slab_stride + b.lws_stride;
+		unsigned long long g = (1ull << 31) / per;                   // at most 2 GiB of scratch
+		if (g > 1024) g = 1024;
+		if (g < 1) g = 1;
+		if (g > n) g = n;
+		const size_t need = (size_t)(per * g);
+		if (g_cs.lslab_bytes < need) {
+			if (g_cs.lslab) (void)hipFree(g_cs.lslab);
+			g_cs.lslab = nullptr; g_cs.lslab_bytes = 0;
+			if (hipMalloc((void **)&g_cs.lslab, need) != hipSuccess) { bmh_set_error("bmh_cigar_batch: hipMalloc of %zu bytes failed", need); return BMH_ENOMEM; }
+			g_cs.lslab_bytes = need;
+		}
+		b.z_slab = g_cs.lslab; b.lws = g_cs.lslab + (size_t)(b.z_slab_stride * g);
+		const size_t llds = 4 * (size_t)max_cigar;
+		HIPCK(hipFuncSetAttribute((const void *)cigar_kernel<1, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)llds));
+		cigar_kernel<1, 0, true><<<(unsigned)g, 64, llds, st>>>(b);
+	}
 	HIPCK(hipGetLastError());
 	return BMH_OK;
 }

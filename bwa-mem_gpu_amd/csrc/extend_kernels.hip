@@ -80,6 +80,7 @@ struct ext_args_t {
 	int32_t *out, *raw;
 	int a, b, o_del, e_del, o_ins, e_ins, zdrop, end_bonus;
 	unsigned long long *stats;    // debug (BMH_EXT_STATS): [0] rows executed, [1] sum of tlen, [2] alignments, [3] wave-rows
+	uint32_t long_cap;            // queries of 769 .. long_cap columns go to the long classes (bmh_extend_batch_long); 0: none
 };
 
 // where the bases of one job come from
@@ -647,10 +648,190 @@ __global__ void __launch_bounds__(256, EXT_MIN_WAVES) extend16_kernel(ext_args_t
 }
 
 
-// classes: 0 = unsupported length (query longer than 768 bases: all three outputs INT32_MIN, counted, see
-// bmh_extend_last_unsupported); 1..18 = extend16_kernel<C>; 19..26 = extend_wide_kernel<5..12>
+// ------------------------------------------------------------------ long queries (769 .. EXT_LONG_CAP columns)
+//
+// One workgroup per alignment, NW waves, wave w owns the contiguous strip of 64 * C columns from w * 64 * C; a lane's C
+// columns, their row state and the row algebra are those of extend_wide_kernel<C>.  What crosses strips goes through
+// LDS, twice per row (every wave reaches both barriers of every row; all control below is workgroup-uniform):
+//   barrier 1: the wave totals of the F scan.  g(j) = max(M - oe_ins, 0) + e_ins * j carries its decay in the column
+//              index, so the carry into strip k is the plain maximum of the totals of strips 0..k-1;
+//   barrier 2: per strip the row maximum and its last column, the first / last index of the next row's [beg,end), the
+//              H of its last column (the left neighbour of the next strip's first column in the next row) and, from the
+//              strip holding column qlen-1, H(i, qlen-1) for gscore.  Every wave reduces the NW entries itself, in the
+//              same order, so the break / z-drop decision and the new [beg,end) are identical in all of them.
+// The slots are double-buffered by row parity: a slot of row i is written again in row i+2, after a barrier that every
+// reader of row i has passed.  A wave whose strip lies wholly outside [beg,end) does no cell work: its cells are zero.
+#define EXT_LONG_CAP 16384
+#define EXT_LONG_BASE 49      // classes 49..53: extend_long_kernel<2,8> (up to 1024 columns), <4,8> (2048), <8,8> (4096), <16,8> (8192), <16,16> (16384)
+#define EXT_LONG_NCLS 5
+__device__ __forceinline__ int ext_long_class(uint32_t ql)
+{
+	return EXT_LONG_BASE + (ql <= 1024 ? 0 : ql <= 2048 ? 1 : ql <= 4096 ? 2 : ql <= 8192 ? 3 : 4);
+}
+
+constexpr int ext_long_cls_of(int NW, int C) { return EXT_LONG_BASE + (C == 16 ? 4 : NW == 2 ? 0 : NW == 4 ? 1 : NW == 8 ? 2 : 3); }
+
+struct ext_long_slot_t { int tot, m, mj, fidx, lidx, edge; };
+
+template <int NW, int C>
+__global__ void __launch_bounds__(64 * NW) extend_long_kernel(ext_args_t A)
+{
+	const int lane = threadIdx.x & 63;
+	const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const int J0 = wv * 64 * C, J1 = J0 + 64 * C;              // this wave's strip [J0, J1)
+	const uint32_t n = A.count[0];
+	const uint32_t *ids = A.ids + A.count[1];
+	const int oe_del = A.o_del + A.e_del, oe_ins = A.o_ins + A.e_ins;
+	__shared__ ext_long_slot_t sl[2][NW];
+	__shared__ int sh1[2];
+	for (uint32_t w = blockIdx.x; w < n; w += gridDim.x) {
+		const uint32_t id = ids[w];
+		const int qlen = (int)A.qlen[id], tlen = (int)A.tlen[id], h0 = (int)A.h0[id];
+		const job_src_t src = ext_job_src(A, id, true, qlen, tlen);
+		int H[C], E[C];
+		uint32_t qw[C / 4];                                          // query codes, four to a register (byte c & 3 of qw[c >> 2])
+#pragma unroll
+		for (int c = 0; c < C / 4; ++c) qw[c] = 0;
+#pragma unroll
+		for (int c = 0; c < C; ++c) {
+			const int j = J0 + lane * C + c;
+			qw[c >> 2] |= (uint32_t)(j < qlen ? min(ext_q_at(A, src, j), 4) : 4) << (8 * (c & 3));
+			const int v = h0 - oe_ins - j * A.e_ins;               // H(-1,j), ksw.c:880-883
+			H[c] = (j < qlen && v > 0) ? v : 0;
+			E[c] = 0;
+		}
+		const int jl = qlen - 1, jl_w = jl / (64 * C);
+		// left neighbour of this strip's first column in row -1: H(-1, J0-1) of the previous strip
+		int edge_in = 0;
+		if (wv > 0) { const int v = h0 - oe_ins - (J0 - 1) * A.e_ins; edge_in = (J0 - 1 < qlen && v > 0) ? v : 0; }
+		int beg = 0, end = qlen, mx = h0, max_i = -1, max_j = -1, max_ie = -1, gscore = -1, max_off = 0;
+		int tchunk = 0;
+		for (int i = 0; i < tlen; ++i) {
+			const int p = i & 1;
+			if ((i & 63) == 0) tchunk = (i + lane < tlen) ? ext_t_at(A, src, i + lane) : 4;
+			const int ti = __builtin_amdgcn_readlane(tchunk, i & 63);
+			const bool work = J1 > beg && J0 < end;                  // wave-uniform
+			const int hm1 = i == 0 ? h0 : max(0, h0 - (A.o_del + A.e_del * i));      // H(i-1,-1) (ksw.c:909-914, :880)
+			int M[C];
+			int agg = NEG_INF, incl = NEG_INF;
+			if (work) {
+				const int left = wave_shr1(H[C - 1], wv == 0 ? (beg == 0 ? hm1 : 0) : edge_in);
+#pragma unroll
+				for (int c = 0; c < C; ++c) {
+					const int j = J0 + lane * C + c;
+					const bool act = j >= beg && j < end;
+					const int hd = c == 0 ? left : H[c - 1];
+					const int qb = (int)((qw[c >> 2] >> (8 * (c & 3))) & 0xFFu);
+					const int sc = (ti > 3 || qb > 3) ? -1 : (ti == qb ? A.a : -A.b);
+					const int m = (act && hd) ? hd + sc : 0;
+					M[c] = m;
+					agg = max(agg, act ? max(m - oe_ins, 0) + A.e_ins * j : NEG_INF);
+				}
+				incl = wave_scan_max(agg);
+			}
+			if (lane == 63) sl[p][wv].tot = incl;
+			__syncthreads();                                         // barrier 1: strip totals of the F scan
+			int carry = NEG_INF;
+#pragma unroll 1
+			for (int k = 0; k < wv; ++k) carry = max(carry, sl[p][k].tot);
+			int lm = 0, lmj = -1;                                    // lane-local row maximum and its last column (ksw.c:900)
+			int firstH = 1 << 20, lastH = -1, firstE = 1 << 20, lastE = -1;
+			if (work) {
+				int run = max(wave_shr1(incl, NEG_INF), carry);      // max of g over all columns left of this lane
+#pragma unroll
+				for (int c = 0; c < C; ++c) {
+					const int j = J0 + lane * C + c;
+					const bool act = j >= beg && j < end;
+					const int f = max(0, run - A.e_ins * (j - 1));
+					run = max(run, act ? max(M[c] - oe_ins, 0) + A.e_ins * j : NEG_INF);
+					int h = max(max(M[c], E[c]), f);
+					int e = max(E[c] - A.e_del, max(M[c] - oe_del, 0));
+					h = act ? h : 0;
+					e = act ? e : 0;
+					H[c] = h; E[c] = e;
+					if (act && h >= lm) { lm = h; lmj = j; }
+					if (h) { firstH = min(firstH, j); lastH = j; }
+					if (e) { firstE = min(firstE, j); lastE = j; }
+				}
+			} else {
+#pragma unroll
+				for (int c = 0; c < C; ++c) { H[c] = 0; E[c] = 0; }
+			}
+			// this strip's share of the row maximum (last column on ties) and of the next row's [beg,end) (ksw.c:928-929, :963-970)
+			const int wm = __builtin_amdgcn_readlane(wave_scan_max(lm), 63);
+			const unsigned long long em = __ballot(lm == wm);
+			const int wmj = __builtin_amdgcn_readlane(lmj, 63 - __builtin_clzll(em));
+			const unsigned long long bh = __ballot(lastH >= 0), be = __ballot(lastE >= 0);
+			int fidx = 1 << 20, lidx = -1;
+			if (bh) {
+				fidx = min(fidx, __builtin_amdgcn_readlane(firstH, __builtin_ctzll(bh)) + 1);
+				lidx = max(lidx, __builtin_amdgcn_readlane(lastH, 63 - __builtin_clzll(bh)) + 1);
+			}
+			if (be) {
+				fidx = min(fidx, __builtin_amdgcn_readlane(firstE, __builtin_ctzll(be)));
+				lidx = max(lidx, __builtin_amdgcn_readlane(lastE, 63 - __builtin_clzll(be)));
+			}
+			int hjl = 0;
+			if (wv == jl_w) {
+				int s = 0;
+#pragma unroll
+				for (int c = 0; c < C; ++c) if (jl % C == c) s = H[c];
+				hjl = __builtin_amdgcn_readlane(s, (jl - J0) / C);
+			}
+			if (lane == 63) { ext_long_slot_t &S = sl[p][wv]; S.m = wm; S.mj = wmj; S.fidx = fidx; S.lidx = lidx; S.edge = H[C - 1]; }
+			if (lane == 0 && wv == jl_w) sh1[p] = hjl;
+			__syncthreads();                                         // barrier 2: the row's reductions
+			edge_in = wv > 0 ? sl[p][wv - 1].edge : 0;
+			int m = 0, mj = -1;
+			fidx = 1 << 20; lidx = -1;
+#pragma unroll 1
+			for (int k = 0; k < NW; ++k) {
+				const ext_long_slot_t S = sl[p][k];
+				if (S.m >= m && S.mj >= 0) { m = S.m; mj = S.mj; }
+				fidx = min(fidx, S.fidx); lidx = max(lidx, S.lidx);
+			}
+			if (end == qlen) {                                       // ksw.c:942-945
+				const int h1 = jl >= beg ? sh1[p] : 0;
+				if (!(gscore > h1)) max_ie = i;
+				gscore = max(gscore, h1);
+			}
+			if (m == 0) break;                                       // ksw.c:946
+			if (m > mx) {
+				mx = m; max_i = i; max_j = mj;
+				max_off = max(max_off, abs(mj - i));
+			} else if (A.zdrop > 0) {                                // ksw.c:951-959
+				if (i - max_i > mj - max_j) {
+					if (mx - m - ((i - max_i) - (mj - max_j)) * A.e_del > A.zdrop) break;
+				} else {
+					if (mx - m - ((mj - max_j) - (i - max_i)) * A.e_ins > A.zdrop) break;
+				}
+			}
+			const int h1i = beg == 0 ? max(0, h0 - (A.o_del + A.e_del * (i + 1))) : 0;
+			if (h1i) { fidx = min(fidx, beg); lidx = max(lidx, beg); }
+			const int nbeg = min(fidx, end);
+			const int nend = min(qlen, max(lidx, nbeg - 1) + 2);
+			beg = nbeg; end = nend;
+		}
+		if (threadIdx.x == 0) {
+			const int qle = max_j + 1, tle = max_i + 1, gtle = max_ie + 1;
+			int32_t *o = A.out + 3 * (size_t)id;
+			if (gscore <= 0 || gscore <= mx - A.end_bonus) { o[0] = mx; o[1] = qle; o[2] = tle; }
+			else { o[0] = gscore; o[1] = qlen; o[2] = gtle; }
+			if (A.raw) {
+				int32_t *r = A.raw + 6 * (size_t)id;
+				r[0] = mx; r[1] = qle; r[2] = tle; r[3] = gtle; r[4] = gscore; r[5] = max_off;
+			}
+		}
+		__syncthreads();                                             // the next job's rows reuse the slots
+	}
+}
+
+
+// classes: 0 = unsupported length (query longer than 768 bases, or than the cap of bmh_extend_batch_long: all three outputs
+// INT32_MIN, counted, see bmh_extend_last_unsupported); 1..18 = extend16_kernel<C>; 19..26 = extend_wide_kernel<5..12>;
+// 49..53 = extend_long_kernel (bmh_extend_batch_long only)
 #define EXT_WIDE_MAX_C 12
-#define EXT_N_CLS 49
+#define EXT_N_CLS 54
 #define EXT_DONE_CLS 27     // decided by the closed-form prefilter: no DP
 #define EXT16_MAX_C 18
 // 28..34 = extpk_kernel<4, P>, P = 4, 6, .. 16 (queries up to 8 P columns); 35..36 = extpk_kernel<8, P>, P = 9, 10 (up to 16 P); 37..39 = extpk_kernel<4, P>, P = 24, 28, 32
@@ -894,7 +1075,8 @@ __global__ void __launch_bounds__(256) ext_closed_form_kernel(ext_args_t A, uint
 		if (A.zdrop > 0 && two) ok = ok && (max(V1, V2) - V2 + A.b <= A.zdrop);
 		if (have && l8 == 0) {
 			{   // the job's bin: decided here (no DP), or its DP class by query / target length and score range
-				const int cls = ok ? EXT_DONE_CLS : ext_route((uint32_t)qlen, (uint32_t)tlen, (uint32_t)h0, pk_a, (uint32_t)g2);
+				int cls = ok ? EXT_DONE_CLS : ext_route((uint32_t)qlen, (uint32_t)tlen, (uint32_t)h0, pk_a, (uint32_t)g2);
+				if (cls == 0 && (uint32_t)qlen <= A.long_cap) cls = ext_long_class((uint32_t)qlen);
 				if (cls == 0) A.out[3 * (size_t)id] = A.out[3 * (size_t)id + 1] = A.out[3 * (size_t)id + 2] = INT32_MIN;
 				const uint32_t tb = (uint32_t)tlen >> 5;
 				const uint32_t bin = (uint32_t)cls * EXT_TL_BINS + (tb < EXT_TL_BINS - 1 ? tb : EXT_TL_BINS - 1);
@@ -1110,9 +1292,18 @@ static void launch_wide(const ext_args_t &base, hipStream_t st, unsigned grid)
 	extend_wide_kernel<C><<<grid, 256, 0, st>>>(a);
 }
 
+template <int NW, int C>
+static void launch_long(const ext_args_t &base, hipStream_t st, uint32_t n)
+{
+	ext_args_t a = base;
+	a.count = base.count + 2 * ext_long_cls_of(NW, C);
+	const unsigned g = n < 8192u / NW ? n : 8192u / NW;
+	extend_long_kernel<NW, C><<<g, 64 * NW, 0, st>>>(a);
+}
+
 static int extend_launch(const uint8_t *d_q, const uint32_t *d_qoff, const uint32_t *d_qlen, const uint8_t *d_t,
                          const uint32_t *d_toff, const uint32_t *d_tlen, const uint32_t *d_h0, uint32_t n,
-                         const bmh_ext_params_t *p, int32_t *d_out, int32_t *d_raw, void *stream_, const bmh_ext_desc_t *desc);
+                         const bmh_ext_params_t *p, int32_t *d_out, int32_t *d_raw, void *stream_, const bmh_ext_desc_t *desc, uint32_t long_cap = 0);
 
 extern "C" int bmh_extend_batch(const uint8_t *d_q, const uint32_t *d_qoff, const uint32_t *d_qlen, const uint8_t *d_t,
                                 const uint32_t *d_toff, const uint32_t *d_tlen, const uint32_t *d_h0, uint32_t n,
@@ -1122,6 +1313,19 @@ extern "C" int bmh_extend_batch(const uint8_t *d_q, const uint32_t *d_qoff, cons
 		bmh_set_error("bmh_extend_batch: null argument"); return BMH_EINVAL;
 	}
 	return extend_launch(d_q, d_qoff, d_qlen, d_t, d_toff, d_tlen, d_h0, n, p, d_out, d_raw, stream_, nullptr);
+}
+
+// bmh_extend_batch with the long classes: queries of 769 .. min(max_qlen, EXT_LONG_CAP) columns (max_qlen 0: the cap) run on
+// extend_long_kernel; shorter ones take exactly the classes of bmh_extend_batch, longer ones get INT32_MIN and are counted
+extern "C" int bmh_extend_batch_long(const uint8_t *d_q, const uint32_t *d_qoff, const uint32_t *d_qlen, const uint8_t *d_t,
+                                     const uint32_t *d_toff, const uint32_t *d_tlen, const uint32_t *d_h0, uint32_t n,
+                                     const bmh_ext_params_t *p, uint32_t max_qlen, int32_t *d_out, int32_t *d_raw, void *stream_)
+{
+	if (!p || (n && (!d_q || !d_t || !d_qoff || !d_qlen || !d_toff || !d_tlen || !d_h0 || !d_out))) {
+		bmh_set_error("bmh_extend_batch_long: null argument"); return BMH_EINVAL;
+	}
+	const uint32_t cap = max_qlen == 0 || max_qlen > EXT_LONG_CAP ? EXT_LONG_CAP : max_qlen;
+	return extend_launch(d_q, d_qoff, d_qlen, d_t, d_toff, d_tlen, d_h0, n, p, d_out, d_raw, stream_, nullptr, cap);
 }
 
 // descriptor form, used by bmh_chain_extend (chain_kernels.hip)
@@ -1136,7 +1340,7 @@ int bmh_extend_batch_desc(const bmh_ext_desc_t *desc, const uint32_t *d_qlen, co
 
 static int extend_launch(const uint8_t *d_q, const uint32_t *d_qoff, const uint32_t *d_qlen, const uint8_t *d_t,
                          const uint32_t *d_toff, const uint32_t *d_tlen, const uint32_t *d_h0, uint32_t n,
-                         const bmh_ext_params_t *p, int32_t *d_out, int32_t *d_raw, void *stream_, const bmh_ext_desc_t *desc)
+                         const bmh_ext_params_t *p, int32_t *d_out, int32_t *d_raw, void *stream_, const bmh_ext_desc_t *desc, uint32_t long_cap)
 {
 	if (p->e_del < 0 || p->e_ins < 0 || p->o_del < 0 || p->o_ins < 0) { bmh_set_error("bmh_extend_batch: negative gap penalty"); return BMH_EINVAL; }
 	if (n == 0) return BMH_OK;
@@ -1164,6 +1368,7 @@ static int extend_launch(const uint8_t *d_q, const uint32_t *d_qoff, const uint3
 	a.a = p->a; a.b = p->b; a.o_del = p->o_del; a.e_del = p->e_del; a.o_ins = p->o_ins; a.e_ins = p->e_ins;
 	a.zdrop = p->zdrop; a.end_bonus = p->end_bonus;
 	a.stats = nullptr;
+	a.long_cap = long_cap > 64u * EXT_WIDE_MAX_C ? long_cap : 0;
 	static const bool want_stats = getenv("BMH_EXT_STATS") != nullptr;
 	static unsigned long long *d_stats = nullptr;
 	if (want_stats) {
@@ -1278,6 +1483,15 @@ static int extend_launch(const uint8_t *d_q, const uint32_t *d_qoff, const uint3
 	if (mq > 576) launch_wide<10>(a, S[1], gw);
 	if (mq > 640) launch_wide<11>(a, S[2], gw);
 	if (mq > 704) launch_wide<12>(a, S[3], gw);
+	if (a.long_cap) {
+		// one workgroup per alignment; grids of at most one full chip of waves (256 CUs x 32), the blocks stride over the class
+		const unsigned lc = a.long_cap;
+		launch_long<2, 8>(a, S[0], n);
+		if (lc > 1024) launch_long<4, 8>(a, S[1], n);
+		if (lc > 2048) launch_long<8, 8>(a, S[2], n);
+		if (lc > 4096) launch_long<16, 8>(a, S[3], n);
+		if (lc > 8192) launch_long<16, 16>(a, S[0], n);
+	}
 	for (int i = 0; i < 4; ++i) { HIPCK(hipEventRecord(g_scr.join[i], g_scr.side[i])); HIPCK(hipStreamWaitEvent(st, g_scr.join[i], 0)); }
 	HIPCK(hipEventRecord(g_scr.ev1, st));
 	HIPCK(hipGetLastError());

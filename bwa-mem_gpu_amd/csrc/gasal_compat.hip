@@ -215,9 +215,16 @@ void gasal_aln_async(gasal_gpu_storage_t *s, const uint32_t qb, const uint32_t t
 	if (n > s->host_max_n_alns) FATAL("gasal_aln_async: %u alignments > host_max_n_alns %u", n, s->host_max_n_alns);
 	if (qb > s->extensible_host_unpacked_query_batch->data_size || tb > s->extensible_host_unpacked_target_batch->data_size)
 		FATAL("gasal_aln_async: batch bytes beyond what was filled");
-	// the DP kernels take queries of up to 768 bases (GASAL2 has a compile-time MAX_SEQ_LEN as well, README.md:38): refuse loudly
+	// the DP kernels take queries of up to 768 bases (GASAL2 has a compile-time MAX_SEQ_LEN as well, README.md:38): refuse loudly.
+	// BMH_GASAL_MAX_SEQ_LEN (read once; 769 .. BMH_EXT_LONG_MAX) stands in for that build-time limit, which the reference's host code
+	// cannot pass as an option: longer queries up to it go through bmh_extend_batch_long
+	static const uint32_t max_seq = [] {
+		const char *e = getenv("BMH_GASAL_MAX_SEQ_LEN");
+		const long v = e ? atol(e) : 768;
+		return (uint32_t)(v < 768 ? 768 : v > BMH_EXT_LONG_MAX ? BMH_EXT_LONG_MAX : v);
+	}();
 	for (uint32_t i = 0; i < n; ++i)
-		if (s->host_query_batch_lens[i] > 768u) FATAL("gasal_aln_async: alignment %u has a query of %u bases; this library supports up to 768", i, s->host_query_batch_lens[i]);
+		if (s->host_query_batch_lens[i] > max_seq) FATAL("gasal_aln_async: alignment %u has a query of %u bases; this library supports up to %u (BMH_GASAL_MAX_SEQ_LEN, at most %d)", i, s->host_query_batch_lens[i], max_seq, BMH_EXT_LONG_MAX);
 	// BMH_GASAL_DUMP=<file>: append every submitted job (qlen, tlen, h0, bases) -- lets tests compare the job
 	// stream of the reference's own host code with bmh_build_jobs
 	static const char *dump = getenv("BMH_GASAL_DUMP");
@@ -250,7 +257,9 @@ void gasal_aln_async(gasal_gpu_storage_t *s, const uint32_t qb, const uint32_t t
 	HIPX(hipMemcpyAsync(m->d_qlen, s->host_query_batch_lens, (size_t)n * 4, hipMemcpyHostToDevice, st));
 	HIPX(hipMemcpyAsync(m->d_tlen, s->host_target_batch_lens, (size_t)n * 4, hipMemcpyHostToDevice, st));
 	HIPX(hipMemcpyAsync(m->d_h0, s->host_seed_scores, (size_t)n * 4, hipMemcpyHostToDevice, st));
-	if (bmh_extend_batch(m->d_q, m->d_qoff, m->d_qlen, m->d_t, m->d_toff, m->d_tlen, m->d_h0, n, &g_params, m->d_out, nullptr, st) != BMH_OK)
+	const int rc = max_seq > 768 ? bmh_extend_batch_long(m->d_q, m->d_qoff, m->d_qlen, m->d_t, m->d_toff, m->d_tlen, m->d_h0, n, &g_params, max_seq, m->d_out, nullptr, st)
+	                             : bmh_extend_batch(m->d_q, m->d_qoff, m->d_qlen, m->d_t, m->d_toff, m->d_tlen, m->d_h0, n, &g_params, m->d_out, nullptr, st);
+	if (rc != BMH_OK)
 		FATAL("gasal_aln_async: %s", bmh_last_error());
 	HIPX(hipMemcpyAsync(m->h_out, m->d_out, (size_t)n * 12, hipMemcpyDeviceToHost, st));
 	if (serial) HIPX(hipStreamSynchronize(st));

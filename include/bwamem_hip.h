@@ -215,6 +215,16 @@ int bmh_extend_batch(const uint8_t *d_q, const uint32_t *d_qoff, const uint32_t 
  * refuses such a batch up front; bmh_chain_batch only admits reads up to 700 bases, whose flanks always fit. */
 int64_t bmh_extend_last_unsupported(void);
 
+/* Long queries, opt-in: bmh_extend_batch, except that jobs whose query has 769 .. min(max_qlen, BMH_EXT_LONG_MAX) bases (max_qlen 0:
+ * BMH_EXT_LONG_MAX) run on the long-query kernel (one workgroup per alignment; same contract, results bit-identical to ksw_extend2
+ * without a band).  Jobs of at most 768 bases take exactly the kernels of bmh_extend_batch; longer ones than the cap get INT32_MIN
+ * and are counted by bmh_extend_last_unsupported. */
+#define BMH_EXT_LONG_MAX 16384
+int bmh_extend_batch_long(const uint8_t *d_q, const uint32_t *d_qoff, const uint32_t *d_qlen,
+                          const uint8_t *d_t, const uint32_t *d_toff, const uint32_t *d_tlen,
+                          const uint32_t *d_h0, uint32_t n, const bmh_ext_params_t *p, uint32_t max_qlen,
+                          int32_t *d_out, int32_t *d_raw, void *stream);
+
 /* Jobs whose scores fit 16 bits (h0 + qlen*a < 4096; scoring with 1 <= b, a + b <= 255) and whose sides fit a packed class -- qlen <= 128
  * with tlen <= 384 (4 lanes per job, 16 jobs per wave; qlen 129..136 too while h0 + qlen*a < 2048: the 17-pair class), qlen <= 256
  * with tlen <= 512 (8 lanes, 8 jobs per wave), qlen <= 288 with tlen <= 640 (16 lanes, 4 jobs per wave) -- run on the packed 16-bit

@@ -115,12 +115,16 @@ else:
     else:
         synth.write_fasta_reads(fq, reads)
 sam = os.path.join(work, "out.sam")
+LONG = bool(os.environ.get("E2E_LONG"))
 t = time.time()
 with open(sam, "w") as f:
     # E2E_DEFAULT_K=1: no -K -- the reference cuts its batches itself (10 Mbases per thread, src/fastmap.c:527; the insert-size statistics are per batch) and the aligner
     # below cuts the same way (align_file's default); only meaningful with E2E_EXE=bwa-gasal2-seqidx: the stock build indexes seq[] batch-relative (see the docstring)
     kopt = [] if os.environ.get("E2E_DEFAULT_K") else ["-K", "2000000000"]
-    r = subprocess.run([exe, "gase_aln", "-t", threads] + kopt + ["-l", os.environ.get("E2E_READLEN", "150")] + opts + (["-p"] if paired else []) + [prefix, fq], stdout=f, stderr=subprocess.PIPE, cwd=work)
+    # E2E_LONG=1: reads beyond ~790 bp -- the reference binary's GASAL2 layer takes queries up to BMH_GASAL_MAX_SEQ_LEN, the aligner below is built with
+    # long_reads=True
+    env = dict(os.environ, BMH_GASAL_MAX_SEQ_LEN="16384") if LONG else None
+    r = subprocess.run([exe, "gase_aln", "-t", threads] + kopt + ["-l", os.environ.get("E2E_READLEN", "150")] + opts + (["-p"] if paired else []) + [prefix, fq], stdout=f, stderr=subprocess.PIPE, cwd=work, env=env)
 dt = time.time() - t
 print("gase_aln rc=%d in %.2fs" % (r.returncode, dt))
 print(r.stderr.decode()[-1500:])
@@ -149,7 +153,7 @@ if paired:
     # the same job through the device-resident path: one batch like the reference's (its insert-size statistics are per batch)
     from bwamem_hip.aligner import Aligner
     import io
-    al = Aligner(prefix); al.set_options(opts + (["-t", threads] if os.environ.get("E2E_DEFAULT_K") else []))       # (-t: the reference's batches hold 10 Mbases per thread)
+    al = Aligner(prefix, long_reads=LONG); al.set_options(opts + (["-t", threads] if os.environ.get("E2E_DEFAULT_K") else []))       # (-t: the reference's batches hold 10 Mbases per thread)
     buf = io.StringIO()
     al.align_file(fq, buf, batch_reads=0 if os.environ.get("E2E_DEFAULT_K") else 1 << 30, paired=True)
     ours = [l for l in buf.getvalue().split("\n") if l and l[0] != "@"]
@@ -206,7 +210,7 @@ assert n == n_reads and (hard or ok / n > 0.97), "end-to-end accuracy too low"
 from bwamem_hip.aligner import Aligner
 import io
 t = time.time()
-al = Aligner(prefix); al.set_options(opts)
+al = Aligner(prefix, long_reads=LONG); al.set_options(opts)
 buf = io.StringIO()
 al.align_file(fq, buf, batch_reads=4096)                  # several batches: the tie-break hash depends on the global read index
 dt2 = time.time() - t
