@@ -1,4 +1,4 @@
-"""Single-end `gase_aln` on the device-resident path: index files + FASTA reads -> SAM.
+"""Single-end `gase_aln` on the device-resident path: index files + FASTA or FASTQ reads -> SAM.
 
 The reference's CLI keeps working on this library through the drop-in headers (INTEGRATION.md sections 1-2); this module
 is the same job done through the device-level C ABI instead -- seeding, chaining / job construction, extension and the
@@ -7,7 +7,9 @@ threads as in the reference (bmh_finalize_regs), CIGAR / NM / MD on the GPU (bmh
 (bmh_format_sam).  It writes the records the reference writes, byte for byte (tests/test_gpu_parity.py).  torch is used
 for device memory only.  Interleaved pairs (gase_aln -p) go through bmh_finalize_pairs / bmh_format_sam_pe; their
 insert-size statistics are per batch as in the reference, so identical output needs the reference's batching (one batch
-here = batch_reads reads).  ALT contigs come from <prefix>.alt as in the reference; read groups and FASTQ qualities are not handled.
+here = batch_reads reads).  ALT contigs come from <prefix>.alt as in the reference; read groups come from -R.  FASTQ files (four-line
+records) give QUAL as the reference writes it (src/bwamem.c:1575-1612), and -C appends every read's header comment (src/bwamem.c:1670-1673);
+a FASTA file still gives QUAL '*'.
 """
 from __future__ import annotations
 
@@ -63,11 +65,14 @@ def read_alt(prefix: str, contigs) -> np.ndarray:
 
 
 class ReadSet:
-    """reads of a FASTA file as flat arrays: ascii bases back to back + offsets / lengths, names as a NUL-separated blob"""
+    """reads of a FASTA or FASTQ file as flat arrays: ascii bases back to back + offsets / lengths, names as a NUL-separated blob;
+    qual: the qualities at the letters' offsets (FASTQ) or None; comments: (blob, offsets) of the header comments, NUL-separated like
+    the names, or None (not kept)"""
 
-    def __init__(self, ascii_, offs, lens, name_blob, name_off, codes=None):
+    def __init__(self, ascii_, offs, lens, name_blob, name_off, codes=None, qual=None, comments=None):
         self.ascii, self.offs, self.lens, self.name_blob, self.name_off = ascii_, offs, lens, name_blob, name_off
         self.codes = codes                      # nt4 codes of the letters when the loader made them (bmh_reads_load_fasta), else None
+        self.qual, self.comments = qual, comments
 
     def __len__(self):
         return len(self.lens)
@@ -76,11 +81,17 @@ class ReadSet:
         b1 = min(b1, len(self))
         a0 = int(self.offs[b0]); a1 = int(self.offs[b1 - 1] + self.lens[b1 - 1])
         n0 = int(self.name_off[b0]); n1 = int(self.name_off[b1]) if b1 < len(self) else len(self.name_blob)
+        cm = None
+        if self.comments is not None:
+            cb, co = self.comments
+            c0 = int(co[b0]); c1 = int(co[b1]) if b1 < len(self) else len(cb)
+            cm = (cb[c0:c1], co[b0:b1] - np.uint64(c0))
         return ReadSet(self.ascii[a0:a1], self.offs[b0:b1] - np.uint64(a0), self.lens[b0:b1], self.name_blob[n0:n1], self.name_off[b0:b1] - np.uint64(n0),
-                       codes=None if self.codes is None else self.codes[a0:a1])
+                       codes=None if self.codes is None else self.codes[a0:a1], qual=None if self.qual is None else self.qual[a0:a1], comments=cm)
 
     @classmethod
-    def from_lists(cls, names, seqs) -> "ReadSet":
+    def from_lists(cls, names, seqs, quals=None, comments=None) -> "ReadSet":
+        """quals: one quality string (str / bytes / uint8 array) per read, of its length; comments: one str per read ("" = none)"""
         seqs = [np.frombuffer(s.encode(), dtype=np.uint8) if isinstance(s, str) else np.asarray(s, dtype=np.uint8) for s in seqs]
         lens = np.array([len(s) for s in seqs], np.uint32)
         offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if len(seqs) else np.zeros(0, np.uint64)
@@ -88,7 +99,20 @@ class ReadSet:
         enc = [n.encode() + b"\0" for n in names]
         blob = np.frombuffer(b"".join(enc), dtype=np.uint8) if enc else np.zeros(1, np.uint8)
         noff = np.concatenate([[0], np.cumsum([len(e) for e in enc])[:-1]]).astype(np.uint64) if enc else np.zeros(0, np.uint64)
-        return cls(ascii_, offs, lens, blob, noff)
+        qual = None
+        if quals is not None:
+            qs = [np.frombuffer(q.encode() if isinstance(q, str) else bytes(q), dtype=np.uint8) for q in quals]
+            if len(qs) != len(seqs) or any(len(q) != len(x) for q, x in zip(qs, seqs)):
+                raise ValueError("quals: one quality string of its read's length per read")
+            qual = np.concatenate(qs) if len(qs) and lens.sum() else np.zeros(1, np.uint8)
+        cm = None
+        if comments is not None:
+            ce = [c.encode() + b"\0" for c in comments]
+            if len(ce) != len(seqs):
+                raise ValueError("comments: one per read")
+            cm = (np.frombuffer(b"".join(ce), dtype=np.uint8) if ce else np.zeros(1, np.uint8),
+                  np.concatenate([[0], np.cumsum([len(e) for e in ce])[:-1]]).astype(np.uint64) if ce else np.zeros(0, np.uint64))
+        return cls(ascii_, offs, lens, blob, noff, qual=qual, comments=cm)
 
 
 def read_fasta_reads(path: str) -> ReadSet:
@@ -99,6 +123,17 @@ def read_fasta_reads(path: str) -> ReadSet:
     if len(d["lens"]) == 0:
         return ReadSet.from_lists([], [])
     return ReadSet(d["ascii"], d["offs"], d["lens"], d["names"], d["name_offs"], codes=d["codes"])
+
+
+def read_reads(path: str, comments: bool = False) -> ReadSet:
+    """a FASTA or FASTQ file (the first non-blank byte decides) through the library's loader (bmh_reads_load): read_fasta_reads plus the
+    qualities of a FASTQ file and, with comments=True, the header comments (what -C writes).  A malformed file raises ValueError."""
+    from .lib import load_reads
+    d = load_reads(path, comments=comments)
+    if len(d["lens"]) == 0:
+        return ReadSet.from_lists([], [], comments=[] if comments else None)
+    cm = (d["comments"], d["comment_offs"]) if d["comments"] is not None else None
+    return ReadSet(d["ascii"], d["offs"], d["lens"], d["names"], d["name_offs"], codes=d["codes"], qual=d["quals"], comments=cm)
 
 
 def read_fasta_reads_numpy(path: str) -> ReadSet:
@@ -200,8 +235,8 @@ class Aligner:
         kinds, as the reference's GPU extension does (src/fastmap.c:417-424); -O/-E given as "del,ins" keep the pair for
         the host stages.  Unlike the reference (update_a, src/fastmap.c), nothing is rescaled by -A: pass every value you want
         changed (-B -O -E -T -U).
-        -d and -L are accepted and ignored (they do not reach the reference's GPU extension either).  Not modelled: -x -r -s
-        -y (seeding variants the GPU seeding of the reference ignores too), -I -H -C -V."""
+        -d and -L are accepted and ignored (they do not reach the reference's GPU extension either).  -C appends every read's header
+        comment to its records.  Not modelled: -x -r -s -y (seeding variants the GPU seeding of the reference ignores too), -I -H -V."""
         import math
         co, ep, po, pe = self.copt, self.ep, self.po, self.pe
         i = 0
@@ -210,7 +245,7 @@ class Aligner:
             return int(a), int(b) if b else int(a)
         while i < len(argv):
             f = argv[i]
-            if f in ("-a", "-M", "-Y", "-S", "-P", "-j"):
+            if f in ("-a", "-M", "-Y", "-S", "-P", "-j", "-C"):
                 if f == "-j":                             # the .alt file is ignored (src/fastmap.c:186,390-392): every sequence belongs to the primary assembly
                     self.alt[:] = 0; self.has_alt = False; co.contig_is_alt = None; po.contig_is_alt = None
                     if getattr(self, "_native", None) is not None: self._native.free(); self._native = None
@@ -219,6 +254,7 @@ class Aligner:
                 elif f == "-a": po.flag_all = 1
                 elif f == "-M": po.no_multi = 1
                 elif f == "-Y": po.softclip = 1
+                elif f == "-C": po.copy_comment = 1
                 elif f == "-S": pe.no_rescue = 1
                 else: pe.no_pairing = 1
                 i += 1; continue
@@ -265,10 +301,12 @@ class Aligner:
     def header(self) -> str:
         return "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in self.contigs) + (getattr(self, "rg_line", "") + "\n" if getattr(self, "rg_line", "") else "")
 
-    def align_batch(self, names, seqs=None, id0: int = 0, paired: bool = False, as_bytes: bool = False):
-        """SAM records of one batch of reads: a ReadSet, or (names, seqs) lists of str / ASCII uint8 arrays; id0 = index of
-        its first read in the run.  paired: interleaved pairs (gase_aln -p); the insert-size statistics are the batch's."""
-        rs = names if isinstance(names, ReadSet) else ReadSet.from_lists(names, seqs)
+    def align_batch(self, names, seqs=None, id0: int = 0, paired: bool = False, as_bytes: bool = False, quals=None, comments=None):
+        """SAM records of one batch of reads: a ReadSet, or (names, seqs) lists of str / ASCII uint8 arrays (quals, comments: lists as
+        ReadSet.from_lists takes them); id0 = index of its first read in the run.  paired: interleaved pairs (gase_aln -p); the insert-size
+        statistics are the batch's.  QUAL comes from the reads' qualities, '*' without; with -C the comments end the records."""
+        rs = names if isinstance(names, ReadSet) else ReadSet.from_lists(names, seqs, quals=quals, comments=comments)
+        self._qc = (rs.qual, rs.comments if self.po.copy_comment else None)
         L, dev, n = self.L, self.dev, len(rs)
         self._as_bytes = as_bytes
         if n == 0:
@@ -382,7 +420,7 @@ class Aligner:
         aln_h, cg_h, md_h = self._cigars(r, o, l, fin, sel, fin_t=fin_t)
         _lap("cigar + D2H")
         txt = format_sam(po, names, codes, offs, lens, self.contigs, fin if m else np.zeros((1, 16), np.int32), opr, slot, aln_h, cg_h, md_h,
-                         as_bytes=as_bytes)
+                         as_bytes=as_bytes, quals=self._qc[0], comments=self._qc[1])
         _lap("format (host)")
         if self.profile:
             import sys
@@ -445,7 +483,7 @@ class Aligner:
         slot = np.full(max(m, 1), -1, np.int64); slot[sel] = np.arange(len(sel))
         aln_h, cg_h, md_h = self._cigars(r, o, l, fin, sel)
         txt = format_sam(po, names, codes, offs, lens, self.contigs, fin if m else np.zeros((1, 16), np.int32), opr, slot, aln_h, cg_h, md_h,
-                         h_rec=h_rec, unflag=unflag, as_bytes=self._as_bytes)
+                         h_rec=h_rec, unflag=unflag, as_bytes=self._as_bytes, quals=self._qc[0], comments=self._qc[1])
         return txt
 
     def _native_aligner(self):
@@ -466,12 +504,12 @@ class Aligner:
         cut decides flags and MAPQ of borderline pairs.  chunk_bases 0: 10 000 000 x the thread count given with -t (1).
         batch_reads > 0 cuts by read count instead (the earlier behaviour)."""
         binary = "b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")
-        # The file batch by batch through bmh_aligner_run_fasta (a loader thread cuts and fills batch k+1 .. while the lanes are on batch k: nothing of the file is
-        # held beyond the batches in flight), when every read fits the device job builder (bmh_fasta_scan: one counting pass); BMH_ALIGNER_STREAM=0: load the
-        # whole file first (below).
+        # The file (FASTA or FASTQ) batch by batch through bmh_aligner_run_file (a loader thread cuts and fills batch k+1 .. while the lanes are on batch k:
+        # nothing of the file is held beyond the batches in flight), when every read fits the device job builder (bmh_reads_scan: one counting pass);
+        # BMH_ALIGNER_STREAM=0: load the whole file first (below).
         if os.environ.get("BMH_ALIGNER_NATIVE", "1") != "0" and os.environ.get("BMH_ALIGNER_STREAM", "1") != "0" and not self.profile:
-            from .lib import NativeAligner, fasta_scan
-            info = fasta_scan(reads_fa)
+            from .lib import reads_scan
+            info = reads_scan(reads_fa)
             if info["n_reads"] and info["max_len"] <= 700:
                 out.write(self.header().encode() if binary else self.header())
                 cb = 0
@@ -481,11 +519,11 @@ class Aligner:
                         cb = max(cb, 150_000_000)             # (single-end records do not depend on the cuts: see below)
                     cb = min(cb, (1 << 31) - 1024)
                 nat = self._native_aligner()
-                self.last_stats = nat.run_fasta(reads_fa, paired, (lambda mv: out.write(mv)) if binary else (lambda mv: out.write(bytes(mv).decode())),
+                self.last_stats = nat.run_file(reads_fa, paired, (lambda mv: out.write(mv)) if binary else (lambda mv: out.write(bytes(mv).decode())),
                                                 batch_bases=cb, batch_reads=max(batch_reads, 0),
                                                 n_lanes=int(os.environ.get("BMH_ALIGNER_LANES", "3" if paired else "2")), n_threads=self.n_threads)
                 return info["n_reads"]
-        rs = read_fasta_reads(reads_fa)
+        rs = read_reads(reads_fa, comments=bool(self.po.copy_comment))
         out.write(self.header().encode() if binary else self.header())
         n = len(rs)
         if batch_reads > 0:

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "bwt_destroy_gpu", "bwt_restore_sa_gpu", "bwt_restore_bwt_gpu", "gpu_cpy_wrapper",
     "pre_calc_seed_intervals_wrapper", "free_gpuseed_data", "seed_gpu", "seed_gpu_last_n_reads",
     "bmh_reads_load_fasta", "bmh_reads_free", "bmh_fasta_scan",
+    "bmh_reads_load", "bmh_reads_scan", "bmh_format_sam_ex", "bmh_format_sam_pe_ex", "bmh_aligner_run_file",
 ]
 
 
@@ -41,13 +42,14 @@ class SamDev(C.Structure):
     _fields_ = [("n_reads", C.c_uint32), ("d_names", C.c_void_p), ("d_name_off", C.c_void_p), ("d_reads", C.c_void_p), ("d_offs", C.c_void_p), ("d_lens", C.c_void_p),
                 ("n_contigs", C.c_int), ("d_contig_names", C.c_void_p), ("d_contig_name_off", C.c_void_p), ("d_contig_offset", C.c_void_p),
                 ("d_fin", C.c_void_p), ("d_fin_per_read", C.c_void_p), ("d_slot", C.c_void_p), ("d_aln", C.c_void_p), ("d_cig_off", C.c_void_p), ("d_packed", C.c_void_p),
-                ("d_h_rec", C.c_void_p), ("d_unflag", C.c_void_p)]
+                ("d_h_rec", C.c_void_p), ("d_unflag", C.c_void_p), ("d_quals", C.c_void_p), ("d_comments", C.c_void_p), ("d_comment_off", C.c_void_p)]
 
 
 class ReadSetT(C.Structure):
     """bmh_read_set_t"""
     _fields_ = [("n_reads", C.c_uint64), ("n_bases", C.c_uint64), ("n_name_bytes", C.c_uint64), ("ascii", C.c_void_p), ("codes", C.c_void_p),
-                ("offs", C.c_void_p), ("lens", C.c_void_p), ("names", C.c_void_p), ("name_offs", C.c_void_p)]
+                ("offs", C.c_void_p), ("lens", C.c_void_p), ("names", C.c_void_p), ("name_offs", C.c_void_p),
+                ("quals", C.c_void_p), ("comments", C.c_void_p), ("comment_offs", C.c_void_p), ("n_comment_bytes", C.c_uint64)]
 
 
 class _ReadSetOwner:
@@ -97,6 +99,52 @@ def load_fasta_reads(path: str, n_threads: int = 0) -> dict:
                 lens=arr(rs.lens, rs.n_reads, np.uint32), names=arr(rs.names, rs.n_name_bytes, np.uint8), name_offs=arr(rs.name_offs, rs.n_reads, np.uint64))
 
 
+READS_COMMENTS = 1          # BMH_READS_COMMENTS
+
+
+class ReadFileError(ValueError, RuntimeError):
+    """a malformed read file (bmh_reads_load, bmh_reads_scan, bmh_aligner_run_file): a ValueError whose message names the problem, and a
+    RuntimeError as the FASTA-only entry points' refusals were"""
+
+
+def reads_scan(path: str, n_threads: int = 0) -> dict:
+    """bmh_reads_scan: fasta_scan for a FASTA or FASTQ file"""
+    L = load_library()
+    L.bmh_reads_scan.restype = C.c_int
+    L.bmh_reads_scan.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    if L.bmh_reads_scan(path.encode(), n_threads, out) != 0:
+        msg = _err(L)
+        raise ReadFileError(msg) if msg.startswith(("FASTQ:", "reads file:")) else RuntimeError("bmh_reads_scan: " + msg)
+    return dict(n_reads=int(out[0]), n_bases=int(out[1]), n_name_bytes=int(out[2]), max_len=int(out[3]))
+
+
+def load_reads(path: str, comments: bool = False, n_threads: int = 0) -> dict:
+    """bmh_reads_load: a FASTA or FASTQ file as load_fasta_reads gives it, plus quals (FASTQ; None for FASTA) and, with comments=True, the header
+    comments (comments / comment_offs: NUL-terminated back to back like the names).  A malformed file raises ValueError naming the problem."""
+    L = load_library()
+    rs = ReadSetT()
+    L.bmh_reads_load.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(ReadSetT)]
+    L.bmh_reads_free.argtypes = [C.POINTER(ReadSetT)]
+    if L.bmh_reads_load(path.encode(), n_threads, READS_COMMENTS if comments else 0, C.byref(rs)) != 0:
+        msg = _err(L)
+        raise ReadFileError(msg) if msg.startswith(("FASTQ:", "reads file:")) else RuntimeError("bmh_reads_load: " + msg)
+    owner = _ReadSetOwner(L, rs)
+
+    def arr(ptr, n, dt):
+        n = int(n)
+        if n == 0 or not ptr:
+            return np.zeros(0, dt)
+        buf = (C.c_uint8 * (n * np.dtype(dt).itemsize)).from_address(ptr)
+        buf._owner = owner
+        return np.frombuffer(buf, dtype=dt)
+    return dict(ascii=arr(rs.ascii, rs.n_bases, np.uint8), codes=arr(rs.codes, rs.n_bases, np.uint8), offs=arr(rs.offs, rs.n_reads, np.uint64),
+                lens=arr(rs.lens, rs.n_reads, np.uint32), names=arr(rs.names, rs.n_name_bytes, np.uint8), name_offs=arr(rs.name_offs, rs.n_reads, np.uint64),
+                quals=arr(rs.quals, rs.n_bases, np.uint8) if rs.quals else None,
+                comments=arr(rs.comments, rs.n_comment_bytes, np.uint8) if rs.comments else None,
+                comment_offs=arr(rs.comment_offs, rs.n_reads, np.uint64) if rs.comments else None)
+
+
 class AlignStats(C.Structure):
     """bmh_align_stats_t"""
     _fields_ = [("n_reads", C.c_uint64), ("n_bytes", C.c_uint64), ("n_batches", C.c_uint32), ("n_lanes", C.c_int)] + \
@@ -138,6 +186,11 @@ class NativeAligner:
         c = ReadSetT()
         c.n_reads = len(keep[3]); c.n_bases = int(keep[2][-1] + keep[3][-1]) if len(keep[3]) else 0; c.n_name_bytes = len(keep[4])
         c.ascii, c.codes, c.offs, c.lens, c.names, c.name_offs = (k.ctypes.data for k in keep)
+        if getattr(rs, "qual", None) is not None:               # FASTQ: QUAL from these (same offsets as the letters)
+            keep.append(np.ascontiguousarray(rs.qual, dtype=np.uint8)); c.quals = keep[-1].ctypes.data
+        if getattr(rs, "comments", None) is not None:           # (blob, offsets): written with -C
+            keep.append(np.ascontiguousarray(rs.comments[0], dtype=np.uint8)); c.comments = keep[-1].ctypes.data; c.n_comment_bytes = len(keep[-1])
+            keep.append(np.ascontiguousarray(rs.comments[1], dtype=np.uint64)); c.comment_offs = keep[-1].ctypes.data
         cu = np.ascontiguousarray(cuts, dtype=np.uint64)
         err = []
 
@@ -181,6 +234,32 @@ class NativeAligner:
             raise (CapacityError if rc == -3 else RuntimeError)(f"bmh_aligner_run_fasta rc={rc}: " + _err(L))
         return st
 
+    def run_file(self, path: str, paired: bool, write, batch_bases: int = 0, batch_reads: int = 0, n_lanes: int = 2, n_threads: int = 0) -> "AlignStats":
+        """bmh_aligner_run_file: run_fasta for a FASTA or FASTQ file (QUAL from the qualities; the comments with -C)"""
+        L = load_library()
+        L.bmh_aligner_run_file.restype = C.c_int
+        L.bmh_aligner_run_file.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, SAM_SINK, C.c_void_p, C.POINTER(AlignStats)]
+        err = []
+
+        def sink(_user, ptr, n):
+            try:
+                write(memoryview((C.c_char * n).from_address(ptr)))
+                return 0
+            except BaseException as e:                      # noqa: BLE001 -- reported after the run (an exception must not cross the C frames)
+                err.append(e)
+                return 1
+        cb = SAM_SINK(sink)
+        st = AlignStats()
+        rc = L.bmh_aligner_run_file(self.handle, path.encode(), int(batch_bases), int(batch_reads), 1 if paired else 0, int(n_lanes), int(n_threads), cb, None, C.byref(st))
+        if err:
+            raise err[0]
+        if rc != 0:
+            msg = _err(L)
+            if "FASTQ:" in msg or "reads file:" in msg:
+                raise ReadFileError(msg)
+            raise (CapacityError if rc == -3 else RuntimeError)(f"bmh_aligner_run_file rc={rc}: " + msg)
+        return st
+
     def free(self):
         if self.handle:
             load_library().bmh_aligner_free(self.handle)
@@ -212,7 +291,8 @@ class PostOpt(C.Structure):
     """bmh_post_opt_t"""
     _fields_ = [("T", C.c_int), ("mask_level_redun", C.c_float), ("mapQ_coef_len", C.c_float), ("mapQ_coef_fac", C.c_int),
                 ("flag_all", C.c_int), ("id0", C.c_int64), ("XA_drop_ratio", C.c_float), ("max_XA_hits", C.c_int),
-                ("no_multi", C.c_int), ("softclip", C.c_int), ("max_XA_hits_alt", C.c_int), ("contig_is_alt", C.c_void_p), ("rg_id", C.c_char_p)]
+                ("no_multi", C.c_int), ("softclip", C.c_int), ("max_XA_hits_alt", C.c_int), ("contig_is_alt", C.c_void_p), ("rg_id", C.c_char_p),
+                ("copy_comment", C.c_int)]
 
 
 class PeOpt(C.Structure):
@@ -376,6 +456,13 @@ def load_library() -> C.CDLL:
     L.bmh_format_sam_pe.restype = C.c_void_p
     L.bmh_format_sam_pe.argtypes = [C.POINTER(PostOpt), C.c_uint32, C.c_void_p, _u64p, _u8p, _u64p, _u32p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p,
                                     _i32p, _u32p, _i32p, _i32p, C.c_void_p, _i32p, _u32p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
+    L.bmh_format_sam_ex.restype = C.c_void_p
+    L.bmh_format_sam_ex.argtypes = [C.POINTER(PostOpt), C.c_uint32, C.c_void_p, _u64p, _u8p, _u64p, _u32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.POINTER(C.c_char_p), C.c_void_p, _i32p, _u32p, C.c_void_p, _i32p, _u32p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
+    L.bmh_format_sam_pe_ex.restype = C.c_void_p
+    L.bmh_format_sam_pe_ex.argtypes = [C.POINTER(PostOpt), C.c_uint32, C.c_void_p, _u64p, _u8p, _u64p, _u32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.POINTER(C.c_char_p), C.c_void_p, _i32p, _u32p, _i32p, _i32p, C.c_void_p, _i32p, _u32p, C.c_int, C.c_void_p, C.c_int,
+                                       C.POINTER(C.c_size_t)]
     L.bmh_merge_regs.restype = C.c_int
     L.bmh_merge_regs.argtypes = [C.c_void_p, _i32p, _i32p]
     L.bmh_chain_ws_create.restype = C.c_void_p
@@ -676,10 +763,10 @@ def cigar_pack(aln_t, cigar_t, md_t=None, stream: int = 0):
 
 
 def sam_text_device(po: "PostOpt", names, reads_t, offs_t, lens_t, contigs, fin_t, fin_per_read_t, slot_t, aln_t, cig_off_t, packed_t, h_rec_t=None, unflag_t=None,
-                    stream: int = 0) -> bytes:
+                    stream: int = 0, quals_t=None, comments=None) -> bytes:
     """bmh_sam_text_sizes + bmh_sam_text_write on torch CUDA tensors: the SAM text of a batch written on the device.  names: list of str;
     contigs: list of (name, length); reads_t / offs_t / lens_t: the batch's ASCII reads; the rest as sam_select_device / cigar_batch / cigar_pack
-    left them.  Returns the text as bytes."""
+    left them.  quals_t: the qualities at offs_t (QUAL); comments: list of str (written with po.copy_comment).  Returns the text as bytes."""
     import torch
     L = load_library()
     dev = fin_t.device
@@ -694,6 +781,13 @@ def sam_text_device(po: "PostOpt", names, reads_t, offs_t, lens_t, contigs, fin_
     d = SamDev(n, nblob.data_ptr(), noff.data_ptr(), reads_t.data_ptr(), offs_t.data_ptr(), lens_t.data_ptr(), len(contigs), cblob.data_ptr(), cnoff.data_ptr(), coff.data_ptr(),
                fin_t.data_ptr(), fin_per_read_t.data_ptr(), slot_t.data_ptr(), aln_t.data_ptr(), cig_off_t.data_ptr(), packed_t.data_ptr(),
                h_rec_t.data_ptr() if h_rec_t is not None else None, unflag_t.data_ptr() if unflag_t is not None else None)
+    if quals_t is not None:
+        d.d_quals = quals_t.data_ptr()
+    if comments is not None:
+        cm = [x.encode() + b"\0" for x in comments]
+        cmblob = torch.from_numpy(np.frombuffer(b"".join(cm) or b"\0", dtype=np.uint8).copy()).to(dev)
+        cmoff = torch.from_numpy(np.concatenate([[0], np.cumsum([len(e) for e in cm])]).astype(np.int64)).to(dev)
+        d.d_comments, d.d_comment_off = cmblob.data_ptr(), cmoff.data_ptr()
     wb = int(L.bmh_sam_text_work(n))
     work = torch.empty(wb, dtype=torch.uint8, device=dev)
     toff = torch.empty(n + 2, dtype=torch.int64, device=dev)
@@ -777,10 +871,11 @@ def finalize_pairs(copt, ep, po, genome_len: int, pac: np.ndarray, reads_flat: n
 
 def format_sam(po: "PostOpt", names, reads_flat: np.ndarray, read_offs: np.ndarray, read_lens: np.ndarray, contigs, fin: np.ndarray,
                fin_per_read: np.ndarray, slot: np.ndarray, aln: np.ndarray, cigar: np.ndarray, md: np.ndarray, h_rec=None, unflag=None,
-               as_bytes: bool = False):
+               as_bytes: bool = False, quals=None, comments=None):
     """bmh_format_sam (or bmh_format_sam_pe when h_rec / unflag are given) on numpy arrays; contigs = list of (name, length).
     names: list of str, or (blob uint8 array of NUL-terminated names, uint64 offsets).  Returns the text as bytes if
-    as_bytes, as a uint8 array over the library's own buffer if as_bytes == "view", else as str."""
+    as_bytes, as a uint8 array over the library's own buffer if as_bytes == "view", else as str.  quals: the qualities at read_offs (QUAL; None:
+    '*'); comments: (blob, offsets) as names, or None -- written with po.copy_comment (bmh_format_sam_ex / bmh_format_sam_pe_ex)."""
     L = load_library()
     if isinstance(names, tuple):
         nblob, noff = np.ascontiguousarray(names[0], dtype=np.uint8), np.ascontiguousarray(names[1], dtype=np.uint64)
@@ -795,7 +890,21 @@ def format_sam(po: "PostOpt", names, reads_flat: np.ndarray, read_offs: np.ndarr
     keep = [a(reads_flat, np.uint8), a(read_offs, np.uint64), a(read_lens, np.uint32), a(fin, np.int32), a(fin_per_read, np.uint32), a(slot, np.int64),
             a(aln, np.int32), a(cigar, np.uint32), a(md, np.uint8)]
     ln = C.c_size_t()
-    if h_rec is not None:
+    if quals is not None or comments is not None:
+        qq = a(quals, np.uint8) if quals is not None else None
+        cb, co = (a(comments[0], np.uint8), a(comments[1], np.uint64)) if comments is not None else (None, None)
+        ex = (qq.ctypes.data_as(C.c_void_p) if qq is not None else None, cb.ctypes.data_as(C.c_void_p) if cb is not None else None,
+              co.ctypes.data_as(C.c_void_p) if co is not None else None)
+        head = (C.byref(po), len(read_lens), nblob.ctypes.data_as(C.c_void_p), _np_ptr(noff, _u64p), _np_ptr(keep[0], _u8p), _np_ptr(keep[1], _u64p), _np_ptr(keep[2], _u32p)) + ex + \
+               (len(contigs), cn, off.ctypes.data_as(C.c_void_p), _np_ptr(keep[3], _i32p), _np_ptr(keep[4], _u32p))
+        tail = (keep[5].ctypes.data_as(C.c_void_p), _np_ptr(keep[6], _i32p), _np_ptr(keep[7], _u32p), int(keep[7].shape[1]), keep[8].ctypes.data_as(C.c_void_p),
+                int(keep[8].shape[1]), C.byref(ln))
+        if h_rec is not None:
+            hh, uu = a(h_rec, np.int32), a(unflag, np.int32)
+            p = L.bmh_format_sam_pe_ex(*head, _np_ptr(hh, _i32p), _np_ptr(uu, _i32p), *tail)
+        else:
+            p = L.bmh_format_sam_ex(*head, *tail)
+    elif h_rec is not None:
         hh, uu = a(h_rec, np.int32), a(unflag, np.int32)
         p = L.bmh_format_sam_pe(C.byref(po), len(read_lens), nblob.ctypes.data_as(C.c_void_p), _np_ptr(noff, _u64p), _np_ptr(keep[0], _u8p), _np_ptr(keep[1], _u64p), _np_ptr(keep[2], _u32p), len(contigs), cn,
                                 off.ctypes.data_as(C.c_void_p), _np_ptr(keep[3], _i32p), _np_ptr(keep[4], _u32p), _np_ptr(hh, _i32p), _np_ptr(uu, _i32p),

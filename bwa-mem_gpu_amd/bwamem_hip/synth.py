@@ -135,6 +135,40 @@ def write_fasta_reads(path: str, reads: np.ndarray, prefix: str = "r") -> None:
             f.write(b"\n")
 
 
+def random_quals(lens, seed: int = 0) -> list:
+    """Phred+33 qualities ('!' .. 'J') for reads of the given lengths.  On purpose, some quality lines begin with '@' (every third read) and
+    some with '+' (every fifth): the two characters a FASTQ parser can mistake for a record's header or separator line."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i, n in enumerate(lens):
+        q = rng.integers(33, 75, size=int(n)).astype(np.uint8)
+        if n and i % 3 == 0:
+            q[0] = ord("@")
+        elif n and i % 5 == 0:
+            q[0] = ord("+")
+        out.append(q)
+    return out
+
+
+def write_fastq_reads(path: str, reads, quals=None, comments=None, prefix: str = "r", seed: int = 0) -> list:
+    """Four-line FASTQ: '@<prefix><i>[ <comment>]', the read, '+', its qualities.  reads: nt4 codes, [n, L] or a list of arrays;
+    quals: one Phred+33 array / bytes per read, or None (random_quals); comments: one str per read ("" = none) or None.
+    Returns the qualities written."""
+    rows = [np.asarray(r) for r in reads]
+    if quals is None:
+        quals = random_quals([len(r) for r in rows], seed=seed)
+    with open(path, "wb") as f:
+        for i, r in enumerate(rows):
+            c = comments[i] if comments is not None else ""
+            f.write(b"@%s%d%s\n" % (prefix.encode(), i, (b" " + c.encode()) if c else b""))
+            f.write(codes_to_ascii(r).tobytes())
+            f.write(b"\n+\n")
+            q = quals[i]
+            f.write(bytes(q) if isinstance(q, (bytes, bytearray)) else np.asarray(q, dtype=np.uint8).tobytes())
+            f.write(b"\n")
+    return quals
+
+
 def write_fasta_genome(path: str, genome: np.ndarray, name: str = "chrS", width: int = 60) -> None:
     asc = codes_to_ascii(genome)
     with open(path, "wb") as f:

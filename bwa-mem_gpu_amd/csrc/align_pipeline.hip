@@ -133,6 +133,9 @@ struct lane_t {
 	dbuf_t<uint32_t> d_cg2; dbuf_t<int32_t> d_aln2; dbuf_t<char> d_md2; uint32_t max_read_len = 0;      // the redo of the alignments that overflow the fixed slots
 	dbuf_t<char> d_names, d_text, d_ctg_names; dbuf_t<uint64_t> d_name_off, d_text_off; dbuf_t<uint32_t> d_ctg_name_off; dbuf_t<int64_t> d_ctg_off; bool ctg_up = false;
 	hbuf_t<uint32_t> h_offs, h_sel, h_rpr; hbuf_t<int32_t> h_regs; hbuf_t<float> h_fr; hbuf_t<uint8_t> h_need, h_reads; hbuf_t<char> h_names; hbuf_t<uint64_t> h_name_off;
+	// a FASTQ batch: its qualities (at the letters' offsets) and, with -C, its comments -- staged and sent only when the read set carries them
+	dbuf_t<uint8_t> d_quals; dbuf_t<char> d_comments; dbuf_t<uint64_t> d_comment_off; hbuf_t<uint8_t> h_quals; hbuf_t<char> h_comments; hbuf_t<uint64_t> h_comment_off;
+	bool has_quals = false, has_comments = false;
 	double t[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // h2d, seed, chain+extend+merge, tail, select, cigar + d2h, wait at the gate
 	// the copies themselves, timed by events on the lane's stream (what t[0] and t[5] are NOT: those are host clocks around the whole stage -- the staging of the
 	// letters, offsets and names on host threads / the CIGAR and text kernels the host waits for): [0] reads, offsets, names H2D  [1] SAM text D2H
@@ -232,6 +235,8 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 	d.n_contigs = A.n_contigs; d.d_contig_names = Ln.d_ctg_names.p; d.d_contig_name_off = Ln.d_ctg_name_off.p; d.d_contig_offset = Ln.d_ctg_off.p;
 	d.d_fin = d_fin; d.d_fin_per_read = Ln.d_opr.p; d.d_slot = Ln.d_slot.p; d.d_aln = Ln.d_aln.p; d.d_cig_off = Ln.d_off.p; d.d_packed = Ln.d_packed.p;
 	d.d_h_rec = paired ? Ln.d_hrec.p : nullptr; d.d_unflag = paired ? Ln.d_unflag.p : nullptr;
+	if (Ln.has_quals) d.d_quals = Ln.d_quals.p;
+	if (Ln.has_comments) { d.d_comments = Ln.d_comments.p; d.d_comment_off = Ln.d_comment_off.p; }
 	const size_t wb = bmh_sam_text_work(n);
 	RCK(Ln.d_work.need(wb)); RCK(Ln.d_text_off.need((size_t)n + 2));
 	const int64_t total = bmh_sam_text_sizes(&po, &d, Ln.d_text_off.p, Ln.d_work.p, Ln.d_work.cap, Ln.st);
@@ -487,6 +492,29 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 		LCK(hipMemcpyAsync(Ln.d_name_off.p, Ln.h_name_off.p, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, Ln.st));
 		h2d_bytes += (n1 - n0) + 8 * ((uint64_t)n + 1);
 	}
+	// FASTQ: the qualities go beside the letters (same offsets); -C: the comments beside the names.  A read set without them takes none of this
+	Ln.has_quals = text_dev && rs.quals != nullptr;
+	Ln.has_comments = text_dev && A.po.copy_comment && rs.comments != nullptr && rs.comment_offs != nullptr;
+	if (Ln.has_quals) {
+		RCK(Ln.d_quals.need(nb + 16));
+		if (src_pinned) LCK(hipMemcpyAsync(Ln.d_quals.p, rs.quals + a0, nb, hipMemcpyHostToDevice, Ln.st));
+		else {
+			RCK(Ln.h_quals.need(nb + 16));
+			par_memcpy(Ln.h_quals.p, rs.quals + a0, nb, n_threads);
+			LCK(hipMemcpyAsync(Ln.d_quals.p, Ln.h_quals.p, nb, hipMemcpyHostToDevice, Ln.st));
+		}
+		h2d_bytes += nb;
+	}
+	if (Ln.has_comments) {
+		const uint64_t c0 = rs.comment_offs[b0], c1 = b1 < rs.n_reads ? rs.comment_offs[b1] : rs.n_comment_bytes;
+		RCK(Ln.h_comments.need(c1 - c0 + 1)); RCK(Ln.h_comment_off.need(n + 2)); RCK(Ln.d_comments.need(c1 - c0 + 1)); RCK(Ln.d_comment_off.need(n + 2));
+		memcpy(Ln.h_comments.p, rs.comments + c0, c1 - c0);
+		for (uint32_t r = 0; r < n; ++r) Ln.h_comment_off.p[r] = rs.comment_offs[b0 + r] - c0;
+		Ln.h_comment_off.p[n] = c1 - c0;
+		LCK(hipMemcpyAsync(Ln.d_comments.p, Ln.h_comments.p, c1 - c0, hipMemcpyHostToDevice, Ln.st));
+		LCK(hipMemcpyAsync(Ln.d_comment_off.p, Ln.h_comment_off.p, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, Ln.st));
+		h2d_bytes += (c1 - c0) + 8 * ((uint64_t)n + 1);
+	}
 	LCK(hipEventRecord(Ln.ev_c[1], Ln.st));
 	Ln.copy_bytes[0] += h2d_bytes;
 	// ---- seeding
@@ -703,6 +731,7 @@ extern "C" {
 namespace {
 struct fbatch_t {
 	hbuf_t<uint8_t> ascii, codes, names; hbuf_t<uint64_t> offs, name_offs; hbuf_t<uint32_t> lens;
+	hbuf_t<uint8_t> quals, comments; hbuf_t<uint64_t> comment_offs;        // a FASTQ file's qualities; -C: the comments
 	bmh_read_set_t rs; uint32_t index = 0; int64_t id0 = 0;
 };
 }
@@ -855,12 +884,17 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 				std::vector<uint64_t> offs64(R->n), noff(R->n);
 				const uint64_t n0 = rs->name_offs[R->b0];
 				for (uint32_t r = 0; r < R->n; ++r) { offs64[r] = rs->offs[R->b0 + r] - a0; noff[r] = rs->name_offs[R->b0 + r] - n0; }
+				const bool cm = A.po.copy_comment && rs->comments && rs->comment_offs;
+				std::vector<uint64_t> coff(cm ? R->n : 0);
+				const uint64_t c0 = cm ? rs->comment_offs[R->b0] : 0;
+				for (uint32_t r = 0; cm && r < R->n; ++r) coff[r] = rs->comment_offs[R->b0 + r] - c0;
 				bmh_cigar_src_t cs;
 				if (R->slot.empty()) cs.slot32 = R->slot32.p; else cs.slot64 = R->slot.data();
 				cs.aln = R->aln.p; cs.packed = R->packed.p; cs.off = R->off.p;
 				const bool ok = bmh_format_sam_parts(&po, R->n, (const char *)rs->names + n0, noff.data(), rs->codes + a0, offs64.data(), rs->lens + R->b0, A.n_contigs,
 				                                     A.name_ptr.data(), A.off.data(), R->fin.p, R->opr.p, cs,
-				                                     paired ? R->h_rec.data() : nullptr, paired ? R->unflag.data() : nullptr, parts);
+				                                     paired ? R->h_rec.data() : nullptr, paired ? R->unflag.data() : nullptr, parts,
+				                                     rs->quals ? rs->quals + a0 : nullptr, cm ? (const char *)rs->comments + c0 : nullptr, cm ? coff.data() : nullptr);
 				if (!ok) { fail(BMH_EINVAL, bmh_last_error()); return; }
 				t_format += now_s() - t0;
 				const double ts0 = now_s();
@@ -958,30 +992,35 @@ int bmh_aligner_run(bmh_aligner_t *h, const bmh_read_set_t *rs, const uint64_t *
 // batch into pinned host memory (csrc/reads_io.cpp: bmh_fasta_cut / bmh_fasta_fill, on host threads) while the lanes are on the batches before it: the letters go to
 // the device straight from there, nothing of the file is held beyond the batches in flight (n_lanes + 3 of them).
 
-int bmh_aligner_run_fasta(bmh_aligner_t *h, const char *path, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
-                          bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats)
+// either: FASTA or FASTQ (bmh_aligner_run_file), else FASTA only (bmh_aligner_run_fasta); fn: the entry point's name in messages
+static int run_file(bmh_aligner_t *h, const char *path, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
+                    bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats, bool either, const char *fn)
 {
-	if (!h || !path || !sink) { bmh_set_error("bmh_aligner_run_fasta: null argument"); return BMH_EINVAL; }
+	if (!h || !path || !sink) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	if (stats) memset(stats, 0, sizeof(*stats));
-	if (batch_bases == 0 && batch_reads == 0) { bmh_set_error("bmh_aligner_run_fasta: batch_bases or batch_reads must be given"); return BMH_EINVAL; }
+	if (batch_bases == 0 && batch_reads == 0) { bmh_set_error("%s: batch_bases or batch_reads must be given", fn); return BMH_EINVAL; }
 	if (batch_bases >= (1ull << 31) - 4096) batch_bases = (1ull << 31) - 4096;      // offsets inside a batch are 32-bit
 	if (paired && (batch_reads & 1)) --batch_reads;
 	if (n_lanes < 1) n_lanes = 1;
 	if (n_threads < 1) n_threads = bmh_effective_cpus();
 	const int fd = open(path, O_RDONLY);
-	if (fd < 0) { bmh_set_error("bmh_aligner_run_fasta: cannot open %s", path); return BMH_EINVAL; }
+	if (fd < 0) { bmh_set_error("%s: cannot open %s", fn, path); return BMH_EINVAL; }
 	struct stat sb;
-	if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { close(fd); bmh_set_error("bmh_aligner_run_fasta: %s is not a regular, seekable file", path); return BMH_EINVAL; }
+	if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { close(fd); bmh_set_error("%s: %s is not a regular, seekable file", fn, path); return BMH_EINVAL; }
 	const size_t sz = (size_t)sb.st_size;
 	if (sz == 0) { close(fd); return BMH_OK; }
 	void *m = mmap(nullptr, sz, PROT_READ, MAP_PRIVATE, fd, 0);
 	close(fd);
-	if (m == MAP_FAILED) { bmh_set_error("bmh_aligner_run_fasta: cannot map %s (%zu bytes)", path, sz); return BMH_ENOMEM; }
+	if (m == MAP_FAILED) { bmh_set_error("%s: cannot map %s (%zu bytes)", fn, path, sz); return BMH_ENOMEM; }
 	(void)madvise(m, sz, MADV_SEQUENTIAL);
 	const uint8_t *buf = (const uint8_t *)m;
+	bmh_reads_fmt_t fmt;
+	fmt.either = either;
+	fmt.fq = either && bmh_reads_detect(buf, sz);
+	fmt.comments = either && h->a.po.copy_comment;        // (the comments are read only when the records carry them)
 	const bool need_codes = true;        // nt4 codes: every host form reads them (pairs' walks, ALT reads, a batch the device tail refuses, the host formatter)
 	int dev = 0;
-	if (hipGetDevice(&dev) != hipSuccess) { (void)munmap(m, sz); bmh_set_error("bmh_aligner_run_fasta: no HIP device"); return BMH_ENODEV; }
+	if (hipGetDevice(&dev) != hipSuccess) { (void)munmap(m, sz); bmh_set_error("%s: no HIP device", fn); return BMH_ENODEV; }
 	// the loader: batches in file order into `ready`; at most n_lanes + 3 batch buffers exist
 	std::mutex qm; std::condition_variable qcv;
 	std::vector<std::unique_ptr<fbatch_t>> &all = h->fbatches; std::vector<fbatch_t *> free_list; std::map<uint32_t, fbatch_t *> ready;
@@ -1002,18 +1041,24 @@ int bmh_aligner_run_fasta(bmh_aligner_t *h, const char *path, uint64_t batch_bas
 				else { all.emplace_back(new fbatch_t()); fb = all.back().get(); }
 			}
 			size_t end = sz; uint64_t nr = 0, nb = 0, nn = 0;
-			int rc = bmh_fasta_cut(buf, sz, p, batch_bases, batch_reads, /* even counts, as bseq_read ends its batches */ batch_reads == 0, load_threads, est, &end, &nr, &nb, &nn);
-			if (rc == BMH_OK && paired && (nr & 1)) { bmh_set_error("bmh_aligner_run_fasta: an odd number of reads in a paired file"); rc = BMH_EINVAL; }
-			if (rc == BMH_OK && (nb >> 31)) { bmh_set_error("bmh_aligner_run_fasta: a batch holds 2^31 bases or more"); rc = BMH_EINVAL; }
+			uint64_t ncm = 0;
+			int rc = bmh_fasta_cut(buf, sz, p, batch_bases, batch_reads, /* even counts, as bseq_read ends its batches */ batch_reads == 0, load_threads, est, &end, &nr, &nb, &nn,
+			                       fmt, &ncm);
+			if (rc == BMH_OK && paired && (nr & 1)) { bmh_set_error("%s: an odd number of reads in a paired file", fn); rc = BMH_EINVAL; }
+			if (rc == BMH_OK && (nb >> 31)) { bmh_set_error("%s: a batch holds 2^31 bases or more", fn); rc = BMH_EINVAL; }
 			if (rc == BMH_OK && nr) {
 				if (fb->ascii.need(nb + 16) != BMH_OK || (need_codes && fb->codes.need(nb + 16) != BMH_OK) || fb->names.need(nn + 16) != BMH_OK || fb->offs.need(nr + 2) != BMH_OK ||
 				    fb->name_offs.need(nr + 2) != BMH_OK || fb->lens.need(nr + 2) != BMH_OK) rc = BMH_ENOMEM;
+				if (fmt.fq && fb->quals.need(nb + 16) != BMH_OK) rc = BMH_ENOMEM;
+				if (fmt.comments && (fb->comments.need(ncm + 16) != BMH_OK || fb->comment_offs.need(nr + 2) != BMH_OK)) rc = BMH_ENOMEM;
 			}
 			if (rc == BMH_OK && nr) {
 				memset(&fb->rs, 0, sizeof(fb->rs));
 				fb->rs.ascii = fb->ascii.p; fb->rs.codes = need_codes ? fb->codes.p : nullptr; fb->rs.names = fb->names.p; fb->rs.offs = fb->offs.p; fb->rs.name_offs = fb->name_offs.p; fb->rs.lens = fb->lens.p;
-				rc = bmh_fasta_fill(buf, p, end, nr, nb, nn, load_threads, &fb->rs);
-				if (rc == BMH_OK) for (uint64_t r = 0; r < nr; ++r) if (fb->lens.p[r] > 700) { bmh_set_error("bmh_aligner_run_fasta: read %lld has %u bases: reads beyond 700 go through the host job builder (bmh_build_jobs)", (long long)(id0 + (int64_t)r), fb->lens.p[r]); rc = BMH_EINVAL; break; }
+				if (fmt.fq) fb->rs.quals = fb->quals.p;
+				if (fmt.comments) { fb->rs.comments = fb->comments.p; fb->rs.comment_offs = fb->comment_offs.p; }
+				rc = bmh_fasta_fill(buf, p, end, nr, nb, nn, load_threads, &fb->rs, fmt, ncm);
+				if (rc == BMH_OK) for (uint64_t r = 0; r < nr; ++r) if (fb->lens.p[r] > 700) { bmh_set_error("%s: read %lld has %u bases: reads beyond 700 go through the host job builder (bmh_build_jobs)", fn, (long long)(id0 + (int64_t)r), fb->lens.p[r]); rc = BMH_EINVAL; break; }
 			}
 			std::lock_guard<std::mutex> lk(qm);
 			if (rc != BMH_OK) { load_rc = rc; load_err = bmh_last_error(); free_list.push_back(fb); break; }
@@ -1040,11 +1085,23 @@ int bmh_aligner_run_fasta(bmh_aligner_t *h, const char *path, uint64_t batch_bas
 	src.release = [&](void *tok) { if (!tok) return; std::lock_guard<std::mutex> lk(qm); free_list.push_back((fbatch_t *)tok); qcv.notify_all(); };
 	src.stop = [&]() { std::lock_guard<std::mutex> lk(qm); stopped = true; qcv.notify_all(); };
 	std::thread lt(loader);
-	const int rc = run_core(h, src, "bmh_aligner_run_fasta", paired, n_lanes, n_threads, sink, user, stats);
+	const int rc = run_core(h, src, fn, paired, n_lanes, n_threads, sink, user, stats);
 	src.stop();
 	lt.join();
 	(void)munmap(m, sz);
 	return rc;
 }
 
+}
+
+int bmh_aligner_run_fasta(bmh_aligner_t *h, const char *path, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
+                          bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats)
+{
+	return run_file(h, path, batch_bases, batch_reads, paired, n_lanes, n_threads, sink, user, stats, false, "bmh_aligner_run_fasta");
+}
+
+int bmh_aligner_run_file(bmh_aligner_t *h, const char *path, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
+                         bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats)
+{
+	return run_file(h, path, batch_bases, batch_reads, paired, n_lanes, n_threads, sink, user, stats, true, "bmh_aligner_run_file");
 }   // extern "C"

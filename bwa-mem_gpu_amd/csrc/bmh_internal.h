@@ -43,7 +43,8 @@ struct bmh_cigar_src_t {
 bool bmh_format_sam_parts(const bmh_post_opt_t *po, uint32_t n_reads, const char *names, const uint64_t *name_off, const uint8_t *reads,
                           const uint64_t *read_offs, const uint32_t *read_lens, int n_contigs, const char *const *contig_names,
                           const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read, const bmh_cigar_src_t &cs,
-                          const int32_t *h_rec, const int32_t *unflag, std::vector<std::string> &parts);
+                          const int32_t *h_rec, const int32_t *unflag, std::vector<std::string> &parts,
+                          const uint8_t *quals = nullptr, const char *comments = nullptr, const uint64_t *comment_off = nullptr);
 // csrc/sam_kernels.hip, for csrc/align_pipeline.hip: the alignments whose fixed slots overflowed (flags 1, 8) found and, once redone with large
 // slots, put in place on the device (see the definitions)
 int64_t bmh_cigar_overflowed(const int32_t *d_aln, uint32_t n, const uint32_t *d_sel, uint32_t *d_over, uint32_t *d_sel2, uint32_t *d_counter, void *stream);
@@ -60,10 +61,17 @@ int64_t bmh_finalize_regs_device_ex(const bmh_index_t *idx, const bmh_chain_opt_
 // csrc/sam_kernels.hip: the device tail's records as ALT-mode records ([11] = [12]), then the records of the ns reads the host redid with the ALT table (d_ids, their
 // records d_sub at d_sub_off [ns + 1]) in their places (d_rec_off: first record of every read)
 int bmh_alt_records_device(int32_t *d_fin, uint64_t m, const uint32_t *d_rec_off, const uint32_t *d_ids, const uint32_t *d_sub_off, const int32_t *d_sub, uint32_t ns, void *stream);
-// csrc/reads_io.cpp: a mapped read file cut and filled batch by batch (bmh_aligner_run_fasta)
+// csrc/reads_io.cpp: a mapped read file cut and filled batch by batch (bmh_aligner_run_fasta, bmh_aligner_run_file).  fmt.fq: FASTQ records (4 lines;
+// a record starts at a '@' line whose line two below starts with '+'), else FASTA; fmt.comments: count (cut) and fill the header comments too -- the fill
+// writes o->quals (FASTQ) and o->comments / o->comment_offs when they are not NULL; fmt.either: the caller takes either layout (its messages name the FASTQ
+// problems; a FASTA-only caller keeps its one message).  bmh_reads_detect: 1 when the first non-blank byte is '@'
+struct bmh_reads_fmt_t { bool fq = false; bool comments = false; bool either = false; };
+int bmh_reads_detect(const uint8_t *buf, size_t sz);
 int bmh_fasta_cut(const uint8_t *buf, size_t sz, size_t p, uint64_t want_bases, uint64_t want_reads, bool even, int n_threads, size_t est_bytes,
-                  size_t *end, uint64_t *n_reads, uint64_t *n_bases, uint64_t *n_name_bytes);
-int bmh_fasta_fill(const uint8_t *buf, size_t p, size_t end, uint64_t n_reads, uint64_t n_bases, uint64_t n_name_bytes, int n_threads, bmh_read_set_t *o);
+                  size_t *end, uint64_t *n_reads, uint64_t *n_bases, uint64_t *n_name_bytes, const bmh_reads_fmt_t &fmt = bmh_reads_fmt_t(),
+                  uint64_t *n_comment_bytes = nullptr);
+int bmh_fasta_fill(const uint8_t *buf, size_t p, size_t end, uint64_t n_reads, uint64_t n_bases, uint64_t n_name_bytes, int n_threads, bmh_read_set_t *o,
+                   const bmh_reads_fmt_t &fmt = bmh_reads_fmt_t(), uint64_t n_comment_bytes = 0);
 // ---- interleaved pairs with mem_pair / mem_sam_pe's choices on the device (csrc/pair_dev.hip) for the pairs the mate rescue does not touch
 // The host call (csrc/pair_post.cpp: bmh_finalize_pairs_split = bmh_finalize_pairs_deduped on a subset) tells the caller the insert-size statistics as
 // soon as it has them (after_pestat: the caller starts the device's pair kernel), asks before its own final walk which pairs the device handed back

@@ -3,6 +3,9 @@
 // into the flat arrays the device path takes: letters back to back (what goes to HBM), nt4 codes (nst_nt4_table: what the host
 // tail and the SAM text use), offsets, lengths, names (the header up to the first blank, NUL-terminated, back to back).
 // Two passes over the file in memory, both on host threads: count per chunk, then fill at the chunk's offsets.
+// FASTQ (bmh_reads_load, bmh_reads_scan, bmh_aligner_run_file): four-line records -- '@' header, one sequence line, a '+' line, one quality line
+// of the same length (kseq_read, src/kseq.h:180-220, reads the same files); the qualities land at the letters' offsets.  Comments: the header
+// behind the first blank, as kseq cuts it (src/kseq.h:187, its trailing CR dropped at :140 when the comment is longer than that CR).
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -30,7 +33,37 @@ inline size_t name_len(const uint8_t *buf, size_t s, size_t le)
 	return n;
 }
 
-struct counts_t { uint64_t reads = 0, bases = 0, name_bytes = 0, max_len = 0; int bad = 0; };
+// bad: 1 headers and sequence lines do not alternate, 2 a line of 2^32 bases, 3 .. 8 FASTQ (bad_msg)
+struct counts_t { uint64_t reads = 0, bases = 0, name_bytes = 0, max_len = 0, comment_bytes = 0; int bad = 0; };
+
+const char *bad_msg(int bad)
+{
+	switch (bad) {
+	case 2: return "reads file: a sequence line of 2^32 bases or more";
+	case 3: return "FASTQ: a quality line whose length differs from its sequence line";
+	case 4: return "FASTQ: a record without its '+' line";
+	case 5: return "FASTQ: the last record is truncated";
+	case 6: return "FASTQ: a multi-line record (a sequence or quality over several lines)";
+	case 7: return "reads file: FASTA and FASTQ records mixed in one file";
+	case 8: return "FASTQ: a record with an empty sequence line";
+	default: return "reads file: expected alternating '>' header and sequence lines";
+	}
+}
+// (the FASTA-only entry points keep their one message: a '@' line where a '>' header belongs is a line out of place there)
+inline const char *bad_msg_fasta(int bad) { return bad == 2 ? bad_msg(2) : bad_msg(1); }
+
+// the comment of the header line [s, raw_le) (s behind the '>' / '@', raw_le at the '\n' or the end; le: raw_le without a trailing CR): kseq's -- the
+// rest of the line behind the first blank, its trailing CR dropped only when the comment is longer than it; empty = none
+inline void comment_span(const uint8_t *buf, size_t s, size_t le, size_t raw_le, size_t *cb, size_t *cl)
+{
+	size_t q = s;
+	while (q < le && buf[q] != ' ' && buf[q] != '\t') ++q;
+	*cb = q + 1; *cl = 0;
+	if (q >= le) return;
+	size_t l = raw_le - (q + 1);
+	if (l > 1 && buf[raw_le - 1] == '\r') --l;
+	*cl = l;
+}
 
 // nst_nt4_table (src/bntseq.c): A/a 0, C/c 1, G/g 2, T/t 3, everything else 4
 struct nt4_table_t {
@@ -40,24 +73,31 @@ struct nt4_table_t {
 const nt4_table_t NT4;
 
 // walks the lines of buf[b, e): headers and sequence lines must alternate (blank lines, also "\r" alone, are skipped); FILL writes
+// cm: the comments too (c.comment_bytes; FILL: o->comments / o->comment_offs from m0)
 template <bool FILL, bool CODES = true>
-void walk(const uint8_t *buf, size_t b, size_t e, counts_t &c, bmh_read_set_t *o, uint64_t r0, uint64_t b0, uint64_t n0)
+void walk(const uint8_t *buf, size_t b, size_t e, counts_t &c, bmh_read_set_t *o, uint64_t r0, uint64_t b0, uint64_t n0, bool cm = false, uint64_t m0 = 0)
 {
 	bool want_hdr = true;
-	uint64_t r = r0, nb = b0, nn = n0;
+	uint64_t r = r0, nb = b0, nn = n0, nm = m0;
 	size_t p = b;
 	while (p < e) {
 		const uint8_t *nl = (const uint8_t *)memchr(buf + p, '\n', e - p);
 		size_t le = nl ? (size_t)(nl - buf) : e;
+		const size_t raw_le = le;
 		const size_t next = nl ? le + 1 : e;
 		if (le > p && buf[le - 1] == '\r') --le;
 		if (le > p) {
 			const bool hdr = buf[p] == '>';
-			if (hdr != want_hdr) { c.bad = 1; return; }
+			if (hdr != want_hdr) { c.bad = want_hdr && buf[p] == '@' ? 7 : 1; return; }
 			if (hdr) {
 				const size_t nl_ = name_len(buf, p + 1, le);
 				if (FILL) { memcpy(o->names + nn, buf + p + 1, nl_); o->names[nn + nl_] = 0; o->name_offs[r] = nn; }
 				nn += nl_ + 1;
+				if (cm) {
+					size_t cb, cl; comment_span(buf, p + 1, le, raw_le, &cb, &cl);
+					if (FILL) { memcpy(o->comments + nm, buf + cb, cl); o->comments[nm + cl] = 0; o->comment_offs[r] = nm; }
+					nm += cl + 1;
+				}
 			} else {
 				const size_t L = le - p;
 				if (L >> 32) { c.bad = 2; return; }
@@ -74,14 +114,113 @@ void walk(const uint8_t *buf, size_t b, size_t e, counts_t &c, bmh_read_set_t *o
 		p = next;
 	}
 	if (!want_hdr) { c.bad = 1; return; }                  // a header without its sequence line
-	c.reads = r - r0; c.bases = nb - b0; c.name_bytes = nn - n0;
+	c.reads = r - r0; c.bases = nb - b0; c.name_bytes = nn - n0; c.comment_bytes = nm - m0;
+}
+
+// FASTQ: '@' header, sequence, '+' line, quality line of the sequence's length; blank lines (also "\r" alone) between records are skipped.  FILL writes
+// the qualities at the letters' offsets (o->quals, if not NULL)
+template <bool FILL, bool CODES = true>
+void walk_fq(const uint8_t *buf, size_t b, size_t e, counts_t &c, bmh_read_set_t *o, uint64_t r0, uint64_t b0, uint64_t n0, bool cm = false, uint64_t m0 = 0)
+{
+	int st = 0;                                            // the line the record wants next: 0 header, 1 sequence, 2 '+', 3 quality
+	uint64_t r = r0, nb = b0, nn = n0, nm = m0;
+	size_t s_beg = 0, s_len = 0;
+	size_t p = b;
+	while (p < e) {
+		const uint8_t *nl = (const uint8_t *)memchr(buf + p, '\n', e - p);
+		size_t le = nl ? (size_t)(nl - buf) : e;
+		const size_t raw_le = le;
+		const size_t next = nl ? le + 1 : e;
+		if (le > p && buf[le - 1] == '\r') --le;
+		if (st == 0) {
+			if (le == p) { p = next; continue; }
+			if (buf[p] != '@') { c.bad = buf[p] == '>' ? 7 : 6; return; }
+			const size_t nl_ = name_len(buf, p + 1, le);
+			if (FILL) { memcpy(o->names + nn, buf + p + 1, nl_); o->names[nn + nl_] = 0; o->name_offs[r] = nn; }
+			nn += nl_ + 1;
+			if (cm) {
+				size_t cb, cl; comment_span(buf, p + 1, le, raw_le, &cb, &cl);
+				if (FILL) { memcpy(o->comments + nm, buf + cb, cl); o->comments[nm + cl] = 0; o->comment_offs[r] = nm; }
+				nm += cl + 1;
+			}
+			st = 1;
+		} else if (st == 1) {
+			if (le == p || buf[p] == '+') { c.bad = 8; return; }
+			s_beg = p; s_len = le - p;
+			if (s_len >> 32) { c.bad = 2; return; }
+			st = 2;
+		} else if (st == 2) {
+			if (le == p || buf[p] != '+') { c.bad = (le == p || buf[p] == '@' || buf[p] == '>') ? 4 : 6; return; }
+			st = 3;
+		} else {
+			if (le - p != s_len) { c.bad = 3; return; }
+			if (FILL) {
+				memcpy(o->ascii + nb, buf + s_beg, s_len);
+				if (CODES) { const uint8_t *src = buf + s_beg; uint8_t *dst = o->codes + nb; for (size_t i = 0; i < s_len; ++i) dst[i] = NT4.v[src[i]]; }
+				if (o->quals) memcpy(o->quals + nb, buf + p, s_len);
+				o->offs[r] = nb; o->lens[r] = (uint32_t)s_len;
+			}
+			nb += s_len; ++r;
+			if (!FILL && s_len > c.max_len) c.max_len = s_len;
+			st = 0;
+		}
+		p = next;
+	}
+	if (st != 0) { c.bad = 5; return; }
+	c.reads = r - r0; c.bases = nb - b0; c.name_bytes = nn - n0; c.comment_bytes = nm - m0;
+}
+
+// either layout
+template <bool FILL, bool CODES = true>
+inline void walk_any(bool fq, const uint8_t *buf, size_t b, size_t e, counts_t &c, bmh_read_set_t *o, uint64_t r0, uint64_t b0, uint64_t n0, bool cm, uint64_t m0)
+{
+	if (fq) walk_fq<FILL, CODES>(buf, b, e, c, o, r0, b0, n0, cm, m0);
+	else walk<FILL, CODES>(buf, b, e, c, o, r0, b0, n0, cm, m0);
+}
+
+// a FASTQ record starts at p: a '@' line whose line two below starts with '+' (a quality line that starts with '@' has a header and a sequence line below it)
+inline bool fq_record_at(const uint8_t *buf, size_t p, size_t sz)
+{
+	if (p >= sz || buf[p] != '@') return false;
+	const uint8_t *a = (const uint8_t *)memchr(buf + p, '\n', sz - p);
+	if (!a) return false;
+	size_t q = (size_t)(a - buf) + 1;
+	if (q >= sz) return false;
+	const uint8_t *b = (const uint8_t *)memchr(buf + q, '\n', sz - q);
+	if (!b) return false;
+	q = (size_t)(b - buf) + 1;
+	return q < sz && buf[q] == '+';
+}
+
+// first record start at or behind p (FASTA: a '>' at the beginning of a line)
+size_t next_record(const uint8_t *buf, size_t p, size_t sz, bool fq = false)
+{
+	if (p == 0) return 0;
+	if (p >= sz) return sz;
+	auto at = [&](size_t q) { return fq ? fq_record_at(buf, q, sz) : buf[q] == '>'; };
+	if (buf[p - 1] == '\n' && at(p)) return p;
+	while (p < sz) {
+		const uint8_t *nl = (const uint8_t *)memchr(buf + p, '\n', sz - p);
+		if (!nl) return sz;
+		p = (size_t)(nl - buf) + 1;
+		if (p < sz && at(p)) return p;
+	}
+	return sz;
 }
 
 } // namespace
 
-extern "C" int bmh_reads_load_fasta(const char *path, int n_threads, bmh_read_set_t *out)
+int bmh_reads_detect(const uint8_t *buf, size_t sz)
 {
-	if (!path || !out) { bmh_set_error("bmh_reads_load_fasta: null argument"); return BMH_EINVAL; }
+	size_t p = 0;
+	while (p < sz && (buf[p] == '\n' || buf[p] == '\r' || buf[p] == ' ' || buf[p] == '\t')) ++p;
+	return p < sz && buf[p] == '@' ? 1 : 0;
+}
+
+// the whole file: fq_ok = FASTQ allowed (the first non-blank byte decides), cm = keep the comments; fn: the entry point's name in messages
+static int load_reads(const char *fn, const char *path, int n_threads, bool fq_ok, bool cm, bmh_read_set_t *out)
+{
+	if (!path || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	memset(out, 0, sizeof(*out));
 	const bool prof = getenv("BMH_IO_PROFILE") != nullptr;
 	auto now = [] { return std::chrono::steady_clock::now(); };
@@ -90,21 +229,22 @@ extern "C" int bmh_reads_load_fasta(const char *path, int n_threads, bmh_read_se
 	// the file is mapped, not copied (its pages come straight from the page cache; the two passes below read it on host threads); it has to be
 	// a regular file (a FIFO or a process substitution cannot be mapped or cut at headers)
 	const int fd = open(path, O_RDONLY);
-	if (fd < 0) { bmh_set_error("bmh_reads_load_fasta: cannot open %s", path); return BMH_EINVAL; }
+	if (fd < 0) { bmh_set_error("%s: cannot open %s", fn, path); return BMH_EINVAL; }
 	struct stat sb;
-	if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { close(fd); bmh_set_error("bmh_reads_load_fasta: %s is not a regular, seekable file", path); return BMH_EINVAL; }
+	if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { close(fd); bmh_set_error("%s: %s is not a regular, seekable file", fn, path); return BMH_EINVAL; }
 	const size_t sz = (size_t)sb.st_size;
 	const uint8_t *buf = (const uint8_t *)"";
 	if (sz) {
 		void *m = mmap(nullptr, sz, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fd, 0);
-		if (m == MAP_FAILED) { close(fd); bmh_set_error("bmh_reads_load_fasta: cannot map %s (%zu bytes)", path, sz); return BMH_ENOMEM; }
+		if (m == MAP_FAILED) { close(fd); bmh_set_error("%s: cannot map %s (%zu bytes)", fn, path, sz); return BMH_ENOMEM; }
 		(void)madvise(m, sz, MADV_SEQUENTIAL);
 		buf = (const uint8_t *)m;
 	}
 	close(fd);
 	auto unmap = [&]() { if (sz) (void)munmap((void *)buf, sz); };
 	lap("read", tp);
-	// chunks that begin at a header: the first '>' that follows a newline at or behind the nominal cut
+	const bool fq = fq_ok && bmh_reads_detect(buf, sz);
+	// chunks that begin at a record: the first one that starts a line at or behind the nominal cut
 	unsigned T = n_threads > 0 ? (unsigned)n_threads : (unsigned)bmh_effective_cpus();      // (the CPUs the process is granted, not the ones the machine shows)
 	if (T == 0) T = 1;
 	if (T > 32) T = 32;                                    // (memory-bound beyond a few threads; the host may show hundreds of hardware threads)
@@ -114,34 +254,32 @@ extern "C" int bmh_reads_load_fasta(const char *path, int n_threads, bmh_read_se
 	for (unsigned t = 1; t < T; ++t) {
 		size_t p = sz / T * t;
 		if (p < cut[t - 1]) p = cut[t - 1];
+		// (the first line start behind p, not p itself: what the loader always did)
 		size_t c = sz;
-		while (p < sz) {
-			const uint8_t *nl = (const uint8_t *)memchr(buf + p, '\n', sz - p);
-			if (!nl) break;
-			p = (size_t)(nl - buf) + 1;
-			if (p < sz && buf[p] == '>') { c = p; break; }
-		}
+		const uint8_t *nl = p < sz ? (const uint8_t *)memchr(buf + p, '\n', sz - p) : nullptr;
+		if (nl) c = next_record(buf, (size_t)(nl - buf) + 1, sz, fq);
 		cut[t] = c;
 	}
 	std::vector<counts_t> cnt(T);
-	auto run = [&](auto fn) {
-		if (T == 1) { fn(0u); return; }
+	auto run = [&](auto fn_) {
+		if (T == 1) { fn_(0u); return; }
 		std::vector<std::thread> th;
-		for (unsigned t = 0; t < T; ++t) th.emplace_back(fn, t);
+		for (unsigned t = 0; t < T; ++t) th.emplace_back(fn_, t);
 		for (auto &x : th) x.join();
 	};
-	run([&](unsigned t) { walk<false>(buf, cut[t], cut[t + 1], cnt[t], nullptr, 0, 0, 0); });
+	run([&](unsigned t) { walk_any<false>(fq, buf, cut[t], cut[t + 1], cnt[t], nullptr, 0, 0, 0, cm, 0); });
 	lap("count", tp);
-	uint64_t nr = 0, nb = 0, nn = 0;
-	std::vector<uint64_t> r0(T), b0(T), n0(T);
+	uint64_t nr = 0, nb = 0, nn = 0, nm = 0;
+	std::vector<uint64_t> r0(T), b0(T), n0(T), m0(T);
 	for (unsigned t = 0; t < T; ++t) {
 		if (cnt[t].bad) {
 			unmap();
-			bmh_set_error(cnt[t].bad == 2 ? "bmh_reads_load_fasta: a sequence line of 2^32 bases or more" : "reads file: expected alternating '>' header and sequence lines");
+			if (!fq_ok && cnt[t].bad == 2) bmh_set_error("%s: a sequence line of 2^32 bases or more", fn);
+			else bmh_set_error("%s", fq_ok ? bad_msg(cnt[t].bad) : bad_msg_fasta(cnt[t].bad));
 			return BMH_EINVAL;
 		}
-		r0[t] = nr; b0[t] = nb; n0[t] = nn;
-		nr += cnt[t].reads; nb += cnt[t].bases; nn += cnt[t].name_bytes;
+		r0[t] = nr; b0[t] = nb; n0[t] = nn; m0[t] = nm;
+		nr += cnt[t].reads; nb += cnt[t].bases; nn += cnt[t].name_bytes; nm += cnt[t].comment_bytes;
 	}
 	out->n_reads = nr; out->n_bases = nb; out->n_name_bytes = nn;
 	// (no MADV_HUGEPAGE on the two large arrays: with the kernel's defrag = madvise the fill pass sometimes stalled for a second in
@@ -149,22 +287,38 @@ extern "C" int bmh_reads_load_fasta(const char *path, int n_threads, bmh_read_se
 	out->ascii = (uint8_t *)malloc(nb + 1); out->codes = (uint8_t *)malloc(nb + 1);
 	out->offs = (uint64_t *)malloc(8 * (nr + 1)); out->lens = (uint32_t *)malloc(4 * (nr + 1));
 	out->names = (uint8_t *)malloc(nn + 1); out->name_offs = (uint64_t *)malloc(8 * (nr + 1));
-	if (!out->ascii || !out->codes || !out->offs || !out->lens || !out->names || !out->name_offs) {
+	bool ok = out->ascii && out->codes && out->offs && out->lens && out->names && out->name_offs;
+	if (fq) { out->quals = (uint8_t *)malloc(nb + 1); ok = ok && out->quals; }
+	if (cm) { out->n_comment_bytes = nm; out->comments = (uint8_t *)malloc(nm + 1); out->comment_offs = (uint64_t *)malloc(8 * (nr + 1)); ok = ok && out->comments && out->comment_offs; }
+	if (!ok) {
 		unmap(); bmh_reads_free(out);
-		bmh_set_error("bmh_reads_load_fasta: out of memory"); return BMH_ENOMEM;
+		bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM;
 	}
 	out->ascii[nb] = out->codes[nb] = 0; out->names[nn] = 0;
+	if (fq) out->quals[nb] = 0;
+	if (cm) out->comments[nm] = 0;
 	lap("alloc", tp);
-	run([&](unsigned t) { counts_t c; walk<true>(buf, cut[t], cut[t + 1], c, out, r0[t], b0[t], n0[t]); });
+	run([&](unsigned t) { counts_t c; walk_any<true>(fq, buf, cut[t], cut[t + 1], c, out, r0[t], b0[t], n0[t], cm, m0[t]); });
 	lap("fill", tp);
 	unmap();
 	return BMH_OK;
+}
+
+extern "C" int bmh_reads_load_fasta(const char *path, int n_threads, bmh_read_set_t *out)
+{
+	return load_reads("bmh_reads_load_fasta", path, n_threads, false, false, out);
+}
+
+extern "C" int bmh_reads_load(const char *path, int n_threads, int flags, bmh_read_set_t *out)
+{
+	return load_reads("bmh_reads_load", path, n_threads, true, (flags & BMH_READS_COMMENTS) != 0, out);
 }
 
 extern "C" void bmh_reads_free(bmh_read_set_t *r)
 {
 	if (!r) return;
 	free(r->ascii); free(r->codes); free(r->offs); free(r->lens); free(r->names); free(r->name_offs);
+	free(r->quals); free(r->comments); free(r->comment_offs);
 	memset(r, 0, sizeof(*r));
 }
 
@@ -174,49 +328,50 @@ extern "C" void bmh_reads_free(bmh_read_set_t *r)
 // chunk in which the count is reached -- and a batch is then filled into the caller's arrays (pinned memory: the letters go to the device from there).
 namespace {
 
-// first record start (a '>' at the beginning of a line) at or behind p
-size_t next_record(const uint8_t *buf, size_t p, size_t sz)
-{
-	if (p == 0) return 0;
-	if (p >= sz) return sz;
-	if (buf[p - 1] == '\n' && buf[p] == '>') return p;
-	while (p < sz) {
-		const uint8_t *nl = (const uint8_t *)memchr(buf + p, '\n', sz - p);
-		if (!nl) return sz;
-		p = (size_t)(nl - buf) + 1;
-		if (p < sz && buf[p] == '>') return p;
-	}
-	return sz;
-}
-
 // walks records from b until the batch is complete (bases >= want_bases, or reads == want_reads when that is not 0; an even count when `even`) or e is reached;
 // reads0 / bases0: what the batch holds before b.  Returns the offset behind the last record taken; bad: the lines do not alternate
-size_t walk_until(const uint8_t *buf, size_t b, size_t e, uint64_t reads0, uint64_t bases0, uint64_t want_bases, uint64_t want_reads, bool even, counts_t &c, bool *complete)
+size_t walk_until(const uint8_t *buf, size_t b, size_t e, uint64_t reads0, uint64_t bases0, uint64_t want_bases, uint64_t want_reads, bool even, counts_t &c, bool *complete,
+                  bool fq = false, bool cm = false)
 {
 	bool want_hdr = true;
-	uint64_t r = reads0, nb = bases0, nn = 0;
+	uint64_t r = reads0, nb = bases0, nn = 0, nm = 0;
 	size_t p = b, last = b;
 	*complete = false;
 	while (p < e) {
 		const uint8_t *nl = (const uint8_t *)memchr(buf + p, '\n', e - p);
 		size_t le = nl ? (size_t)(nl - buf) : e;
+		const size_t raw_le = le;
 		const size_t next = nl ? le + 1 : e;
 		if (le > p && buf[le - 1] == '\r') --le;
+		if (le > p && fq) {                                 // a FASTQ record: its four lines, counted by walk_fq
+			size_t q = p;
+			for (int k = 0; k < 4 && q < e; ++k) { const uint8_t *x = (const uint8_t *)memchr(buf + q, '\n', e - q); q = x ? (size_t)(x - buf) + 1 : e; }
+			counts_t one;
+			walk_fq<false>(buf, p, q, one, nullptr, 0, 0, 0, cm, 0);
+			if (one.bad) { c.bad = one.bad; return last; }
+			nn += one.name_bytes; nm += one.comment_bytes; nb += one.bases; ++r; last = q;
+			const bool full = want_reads ? r >= want_reads : nb >= want_bases;
+			if (full && (!even || !(r & 1))) { *complete = true; c.reads = r - reads0; c.bases = nb - bases0; c.name_bytes = nn; c.comment_bytes = nm; return last; }
+			p = q;
+			continue;
+		}
 		if (le > p) {
 			const bool hdr = buf[p] == '>';
-			if (hdr != want_hdr) { c.bad = 1; return last; }
-			if (hdr) nn += name_len(buf, p + 1, le) + 1;
-			else {
+			if (hdr != want_hdr) { c.bad = want_hdr && buf[p] == '@' ? 7 : 1; return last; }
+			if (hdr) {
+				nn += name_len(buf, p + 1, le) + 1;
+				if (cm) { size_t cb, cl; comment_span(buf, p + 1, le, raw_le, &cb, &cl); nm += cl + 1; }
+			} else {
 				nb += le - p; ++r; last = next;
 				const bool full = want_reads ? r >= want_reads : nb >= want_bases;
-				if (full && (!even || !(r & 1))) { *complete = true; c.reads = r - reads0; c.bases = nb - bases0; c.name_bytes = nn; return last; }
+				if (full && (!even || !(r & 1))) { *complete = true; c.reads = r - reads0; c.bases = nb - bases0; c.name_bytes = nn; c.comment_bytes = nm; return last; }
 			}
 			want_hdr = !hdr;
 		}
 		p = next;
 	}
 	if (!want_hdr) { c.bad = 1; return last; }
-	c.reads = r - reads0; c.bases = nb - bases0; c.name_bytes = nn;
+	c.reads = r - reads0; c.bases = nb - bases0; c.name_bytes = nn; c.comment_bytes = nm;
 	return e;
 }
 
@@ -225,93 +380,112 @@ size_t walk_until(const uint8_t *buf, size_t b, size_t e, uint64_t reads0, uint6
 // The end of the batch that starts at offset p of the mapped file (p at a record start): *end, and what it holds.  est_bytes: the caller's guess of its size in
 // the file (0: none).  BMH_OK, or BMH_EINVAL (lines that do not alternate).  A batch that ends with the file may be short (and odd).
 int bmh_fasta_cut(const uint8_t *buf, size_t sz, size_t p, uint64_t want_bases, uint64_t want_reads, bool even, int n_threads, size_t est_bytes,
-                  size_t *end, uint64_t *n_reads, uint64_t *n_bases, uint64_t *n_name_bytes)
+                  size_t *end, uint64_t *n_reads, uint64_t *n_bases, uint64_t *n_name_bytes, const bmh_reads_fmt_t &fmt, uint64_t *n_comment_bytes)
 {
 	unsigned T = n_threads > 0 ? (unsigned)n_threads : 1u;
 	if (T > 16) T = 16;
-	size_t window = est_bytes ? est_bytes + est_bytes / 16 + (1u << 16) : (size_t)(want_reads ? want_reads * 200 : want_bases + want_bases / 4) + (1u << 16);
+	const bool fq = fmt.fq, cm = fmt.comments;
+	uint64_t ncm_dummy = 0;
+	uint64_t *ncm = n_comment_bytes ? n_comment_bytes : &ncm_dummy;
+	size_t window = est_bytes ? est_bytes + est_bytes / 16 + (1u << 16) : (size_t)(want_reads ? want_reads * (fq ? 400 : 200) : (want_bases + want_bases / 4) * (fq ? 2 : 1)) + (1u << 16);
 	for (;;) {
-		const size_t q = p + window >= sz ? sz : next_record(buf, p + window, sz);
+		const size_t q = p + window >= sz ? sz : next_record(buf, p + window, sz, fq);
 		const unsigned Tw = (q - p) < (1u << 20) ? 1u : T;
 		std::vector<size_t> cut(Tw + 1, q);
 		cut[0] = p;
-		for (unsigned t = 1; t < Tw; ++t) { size_t c = next_record(buf, p + (q - p) / Tw * t, q); if (c < cut[t - 1]) c = cut[t - 1]; cut[t] = c > q ? q : c; }
+		for (unsigned t = 1; t < Tw; ++t) { size_t c = next_record(buf, p + (q - p) / Tw * t, q, fq); if (c < cut[t - 1]) c = cut[t - 1]; cut[t] = c > q ? q : c; }
 		std::vector<counts_t> cnt(Tw);
-		if (Tw == 1) walk<false>(buf, cut[0], cut[1], cnt[0], nullptr, 0, 0, 0);
-		else { std::vector<std::thread> th; for (unsigned t = 0; t < Tw; ++t) th.emplace_back([&, t] { walk<false>(buf, cut[t], cut[t + 1], cnt[t], nullptr, 0, 0, 0); }); for (auto &x : th) x.join(); }
-		uint64_t r = 0, b = 0, nn = 0;
+		if (Tw == 1) walk_any<false>(fq, buf, cut[0], cut[1], cnt[0], nullptr, 0, 0, 0, cm, 0);
+		else { std::vector<std::thread> th; for (unsigned t = 0; t < Tw; ++t) th.emplace_back([&, t] { walk_any<false>(fq, buf, cut[t], cut[t + 1], cnt[t], nullptr, 0, 0, 0, cm, 0); }); for (auto &x : th) x.join(); }
+		uint64_t r = 0, b = 0, nn = 0, nm = 0;
 		for (unsigned t = 0; t < Tw; ++t) {
-			if (cnt[t].bad) { bmh_set_error(cnt[t].bad == 2 ? "reads file: a sequence line of 2^32 bases or more" : "reads file: expected alternating '>' header and sequence lines"); return BMH_EINVAL; }
+			if (cnt[t].bad) { bmh_set_error("%s", fmt.either ? bad_msg(cnt[t].bad) : bad_msg_fasta(cnt[t].bad)); return BMH_EINVAL; }
 			const bool reached = want_reads ? r + cnt[t].reads >= want_reads : b + cnt[t].bases >= want_bases;
 			if (reached) {                                          // the batch ends inside this chunk (or, for an even count, a record into the next ones)
 				counts_t c; bool complete = false;
-				const size_t e = walk_until(buf, cut[t], q, r, b, want_bases, want_reads, even, c, &complete);
-				if (c.bad) { bmh_set_error("reads file: expected alternating '>' header and sequence lines"); return BMH_EINVAL; }
-				if (complete || q == sz) { *end = complete ? e : sz; *n_reads = r + c.reads; *n_bases = b + c.bases; *n_name_bytes = nn + c.name_bytes; return BMH_OK; }
+				const size_t e = walk_until(buf, cut[t], q, r, b, want_bases, want_reads, even, c, &complete, fq, cm);
+				if (c.bad) { bmh_set_error("%s", fmt.either ? bad_msg(c.bad) : bad_msg_fasta(c.bad)); return BMH_EINVAL; }
+				if (complete || q == sz) {
+					*end = complete ? e : sz; *n_reads = r + c.reads; *n_bases = b + c.bases; *n_name_bytes = nn + c.name_bytes; *ncm = nm + c.comment_bytes;
+					return BMH_OK;
+				}
 				break;                                               // (ran out of window behind the threshold: a larger window)
 			}
-			r += cnt[t].reads; b += cnt[t].bases; nn += cnt[t].name_bytes;
+			r += cnt[t].reads; b += cnt[t].bases; nn += cnt[t].name_bytes; nm += cnt[t].comment_bytes;
 		}
-		if (q == sz) { *end = sz; *n_reads = r; *n_bases = b; *n_name_bytes = nn; return BMH_OK; }
+		if (q == sz) { *end = sz; *n_reads = r; *n_bases = b; *n_name_bytes = nn; *ncm = nm; return BMH_OK; }
 		window *= 2;
 	}
 }
 
-// fills the batch [p, end) (bmh_fasta_cut's numbers) into o's arrays -- the caller's, large enough: ascii / codes n_bases + 1, offs / lens / name_offs n_reads + 1,
-// names n_name_bytes + 1 -- on n_threads host threads; o->codes may be NULL (no nt4 codes wanted)
-int bmh_fasta_fill(const uint8_t *buf, size_t p, size_t end, uint64_t n_reads, uint64_t n_bases, uint64_t n_name_bytes, int n_threads, bmh_read_set_t *o)
+// fills the batch [p, end) (bmh_fasta_cut's numbers) into o's arrays -- the caller's, large enough: ascii / codes / quals n_bases + 1, offs / lens / name_offs /
+// comment_offs n_reads + 1, names n_name_bytes + 1, comments n_comment_bytes + 1 -- on n_threads host threads; o->codes may be NULL (no nt4 codes wanted),
+// o->quals / o->comments too (not kept)
+int bmh_fasta_fill(const uint8_t *buf, size_t p, size_t end, uint64_t n_reads, uint64_t n_bases, uint64_t n_name_bytes, int n_threads, bmh_read_set_t *o,
+                   const bmh_reads_fmt_t &fmt, uint64_t n_comment_bytes)
 {
 	unsigned T = n_threads > 0 ? (unsigned)n_threads : 1u;
 	if (T > 16) T = 16;
 	if (end - p < (1u << 20)) T = 1;
+	const bool fq = fmt.fq, cm = fmt.comments;
 	std::vector<size_t> cut(T + 1, end);
 	cut[0] = p;
-	for (unsigned t = 1; t < T; ++t) { size_t c = next_record(buf, p + (end - p) / T * t, end); if (c < cut[t - 1]) c = cut[t - 1]; cut[t] = c > end ? end : c; }
+	for (unsigned t = 1; t < T; ++t) { size_t c = next_record(buf, p + (end - p) / T * t, end, fq); if (c < cut[t - 1]) c = cut[t - 1]; cut[t] = c > end ? end : c; }
 	std::vector<counts_t> cnt(T);
 	auto run = [&](auto fn) { if (T == 1) { fn(0u); return; } std::vector<std::thread> th; for (unsigned t = 0; t < T; ++t) th.emplace_back(fn, t); for (auto &x : th) x.join(); };
-	run([&](unsigned t) { walk<false>(buf, cut[t], cut[t + 1], cnt[t], nullptr, 0, 0, 0); });
-	std::vector<uint64_t> r0(T), b0(T), n0(T);
-	uint64_t nr = 0, nb = 0, nn = 0;
-	for (unsigned t = 0; t < T; ++t) { if (cnt[t].bad) { bmh_set_error("reads file: expected alternating '>' header and sequence lines"); return BMH_EINVAL; } r0[t] = nr; b0[t] = nb; n0[t] = nn; nr += cnt[t].reads; nb += cnt[t].bases; nn += cnt[t].name_bytes; }
-	if (nr != n_reads || nb != n_bases || nn != n_name_bytes) { bmh_set_error("reads file: internal error: a batch counted twice gave different sizes"); return BMH_EINVAL; }
-	o->n_reads = nr; o->n_bases = nb; o->n_name_bytes = nn;
+	run([&](unsigned t) { walk_any<false>(fq, buf, cut[t], cut[t + 1], cnt[t], nullptr, 0, 0, 0, cm, 0); });
+	std::vector<uint64_t> r0(T), b0(T), n0(T), m0(T);
+	uint64_t nr = 0, nb = 0, nn = 0, nm = 0;
+	for (unsigned t = 0; t < T; ++t) {
+		if (cnt[t].bad) { bmh_set_error("%s", fmt.either ? bad_msg(cnt[t].bad) : bad_msg_fasta(cnt[t].bad)); return BMH_EINVAL; }
+		r0[t] = nr; b0[t] = nb; n0[t] = nn; m0[t] = nm; nr += cnt[t].reads; nb += cnt[t].bases; nn += cnt[t].name_bytes; nm += cnt[t].comment_bytes;
+	}
+	if (nr != n_reads || nb != n_bases || nn != n_name_bytes || (cm && nm != n_comment_bytes)) { bmh_set_error("reads file: internal error: a batch counted twice gave different sizes"); return BMH_EINVAL; }
+	o->n_reads = nr; o->n_bases = nb; o->n_name_bytes = nn; o->n_comment_bytes = cm ? nm : 0;
 	uint8_t *codes = o->codes;
 	bmh_read_set_t w = *o;
-	run([&](unsigned t) { counts_t c; if (codes) walk<true, true>(buf, cut[t], cut[t + 1], c, &w, r0[t], b0[t], n0[t]); else walk<true, false>(buf, cut[t], cut[t + 1], c, &w, r0[t], b0[t], n0[t]); });
+	const bool wcm = cm && o->comments && o->comment_offs;
+	if (!wcm) { w.comments = nullptr; w.comment_offs = nullptr; o->comments = nullptr; o->comment_offs = nullptr; o->n_comment_bytes = 0; }
+	if (!fq) { w.quals = nullptr; o->quals = nullptr; }
+	run([&](unsigned t) { counts_t c; if (codes) walk_any<true, true>(fq, buf, cut[t], cut[t + 1], c, &w, r0[t], b0[t], n0[t], wcm, m0[t]); else walk_any<true, false>(fq, buf, cut[t], cut[t + 1], c, &w, r0[t], b0[t], n0[t], wcm, m0[t]); });
 	return BMH_OK;
 }
 
 // reads, bases, name bytes and the longest read of a read file, without loading it (one counting pass of the mapped file on host threads): out[4]
-extern "C" int bmh_fasta_scan(const char *path, int n_threads, uint64_t *out)
+static int scan_reads(const char *fn, const char *path, int n_threads, bool fq_ok, uint64_t *out)
 {
-	if (!path || !out) { bmh_set_error("bmh_fasta_scan: null argument"); return BMH_EINVAL; }
+	if (!path || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	out[0] = out[1] = out[2] = out[3] = 0;
 	const int fd = open(path, O_RDONLY);
-	if (fd < 0) { bmh_set_error("bmh_fasta_scan: cannot open %s", path); return BMH_EINVAL; }
+	if (fd < 0) { bmh_set_error("%s: cannot open %s", fn, path); return BMH_EINVAL; }
 	struct stat sb;
-	if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { close(fd); bmh_set_error("bmh_fasta_scan: %s is not a regular, seekable file", path); return BMH_EINVAL; }
+	if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { close(fd); bmh_set_error("%s: %s is not a regular, seekable file", fn, path); return BMH_EINVAL; }
 	const size_t sz = (size_t)sb.st_size;
 	if (sz == 0) { close(fd); return BMH_OK; }
 	void *m = mmap(nullptr, sz, PROT_READ, MAP_PRIVATE, fd, 0);
 	close(fd);
-	if (m == MAP_FAILED) { bmh_set_error("bmh_fasta_scan: cannot map %s (%zu bytes)", path, sz); return BMH_ENOMEM; }
+	if (m == MAP_FAILED) { bmh_set_error("%s: cannot map %s (%zu bytes)", fn, path, sz); return BMH_ENOMEM; }
 	(void)madvise(m, sz, MADV_SEQUENTIAL);
 	const uint8_t *buf = (const uint8_t *)m;
+	const bool fq = fq_ok && bmh_reads_detect(buf, sz);
 	unsigned T = n_threads > 0 ? (unsigned)n_threads : (unsigned)bmh_effective_cpus();
 	if (T == 0) T = 1;
 	if (T > 32) T = 32;
 	if (sz < (1u << 20)) T = 1;
 	std::vector<size_t> cut(T + 1, sz);
 	cut[0] = 0;
-	for (unsigned t = 1; t < T; ++t) { size_t c = next_record(buf, sz / T * t, sz); if (c < cut[t - 1]) c = cut[t - 1]; cut[t] = c; }
+	for (unsigned t = 1; t < T; ++t) { size_t c = next_record(buf, sz / T * t, sz, fq); if (c < cut[t - 1]) c = cut[t - 1]; cut[t] = c; }
 	std::vector<counts_t> cnt(T);
-	if (T == 1) walk<false>(buf, cut[0], cut[1], cnt[0], nullptr, 0, 0, 0);
-	else { std::vector<std::thread> th; for (unsigned t = 0; t < T; ++t) th.emplace_back([&, t] { walk<false>(buf, cut[t], cut[t + 1], cnt[t], nullptr, 0, 0, 0); }); for (auto &x : th) x.join(); }
+	if (T == 1) walk_any<false>(fq, buf, cut[0], cut[1], cnt[0], nullptr, 0, 0, 0, false, 0);
+	else { std::vector<std::thread> th; for (unsigned t = 0; t < T; ++t) th.emplace_back([&, t] { walk_any<false>(fq, buf, cut[t], cut[t + 1], cnt[t], nullptr, 0, 0, 0, false, 0); }); for (auto &x : th) x.join(); }
 	int rc = BMH_OK;
 	for (unsigned t = 0; t < T; ++t) {
-		if (cnt[t].bad) { bmh_set_error(cnt[t].bad == 2 ? "reads file: a sequence line of 2^32 bases or more" : "reads file: expected alternating '>' header and sequence lines"); rc = BMH_EINVAL; break; }
+		if (cnt[t].bad) { bmh_set_error("%s", fq_ok ? bad_msg(cnt[t].bad) : bad_msg_fasta(cnt[t].bad)); rc = BMH_EINVAL; break; }
 		out[0] += cnt[t].reads; out[1] += cnt[t].bases; out[2] += cnt[t].name_bytes; if (cnt[t].max_len > out[3]) out[3] = cnt[t].max_len;
 	}
 	(void)munmap(m, sz);
 	return rc;
 }
+
+extern "C" int bmh_fasta_scan(const char *path, int n_threads, uint64_t *out) { return scan_reads("bmh_fasta_scan", path, n_threads, false, out); }
+extern "C" int bmh_reads_scan(const char *path, int n_threads, uint64_t *out) { return scan_reads("bmh_reads_scan", path, n_threads, true, out); }

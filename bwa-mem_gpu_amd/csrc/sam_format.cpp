@@ -4,8 +4,9 @@
 //   mem_gen_alt   src/bwamem_extra.c:97-150                the XA tag: secondary hits within XA_drop_ratio of their primary,
 //                                                          listed when there are at most max_XA_hits of them
 //   mem_reg2sam   src/bwamem.c:1721-1770                   the unmapped record when nothing is reported
-// Host code, like the reference's.  Pairing (bwamem_pair.c) and ALT contigs are not modelled; reads come without qualities
-// (the seeding library reads FASTA only, src/GPUSeed/seed_gen.cu:1698-1728).
+//   QUAL and -C                                            src/bwamem.c:1575-1612, 1670-1673 (bmh_format_sam_ex: qualities of a FASTQ file,
+//                                                          the header comments)
+// Host code, like the reference's.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -38,6 +39,17 @@ inline void put_seq(std::string &s, const uint8_t *seq, int qb, int qe, bool rev
 	char *d = &s[at];
 	if (!rev) for (int k = qb; k < qe; ++k) *d++ = "ACGTN"[seq[k] > 4 ? 4 : seq[k]];
 	else for (int k = qe - 1; k >= qb; --k) *d++ = "TGCAN"[seq[k] > 4 ? 4 : seq[k]];
+}
+
+// QUAL: the qualities of [qb, qe), reversed (not complemented) for the reverse strand
+inline void put_qual(std::string &s, const uint8_t *q, int qb, int qe, bool rev)
+{
+	if (qe <= qb) return;
+	const size_t at = s.size();
+	s.resize(at + (size_t)(qe - qb));
+	char *d = &s[at];
+	if (!rev) for (int k = qb; k < qe; ++k) *d++ = (char)q[k];
+	else for (int k = qe - 1; k >= qb; --k) *d++ = (char)q[k];
 }
 
 struct Rec { const int32_t *fin; const int32_t *aln; const uint32_t *cigar; const char *md; };
@@ -112,12 +124,14 @@ extern "C" int64_t bmh_sam_need_cigar(const bmh_post_opt_t *po, const int32_t *f
 bool bmh_format_sam_parts(const bmh_post_opt_t *po, uint32_t n_reads, const char *names, const uint64_t *name_off, const uint8_t *reads,
                           const uint64_t *read_offs, const uint32_t *read_lens, int n_contigs, const char *const *contig_names,
                           const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read, const bmh_cigar_src_t &cs,
-                          const int32_t *h_rec, const int32_t *unflag, std::vector<std::string> &parts)
+                          const int32_t *h_rec, const int32_t *unflag, std::vector<std::string> &parts,
+                          const uint8_t *quals, const char *comments, const uint64_t *comment_off)
 {
 	std::vector<uint64_t> bases((size_t)n_reads + 1, 0);
 	for (uint32_t r = 0; r < n_reads; ++r) bases[r + 1] = bases[r] + fin_per_read[r];
 	const bool pe = h_rec != nullptr;
 	const char *rg = po->rg_id && po->rg_id[0] ? po->rg_id : nullptr;      // read group: RG:Z:<id> on every record
+	const bool cm = po->copy_comment && comments && comment_off;           // -C: the header comment behind every record
 	auto rec_at = [&](uint64_t base, const int32_t *a, int i) {
 		Rec x; x.fin = a + 16 * i;
 		const int64_t s = cs.slot32 ? (int64_t)cs.slot32[base + i] : cs.slot64[base + i];
@@ -183,6 +197,8 @@ bool bmh_format_sam_parts(const bmh_post_opt_t *po, uint32_t n_reads, const char
 		list.clear();
 		for (int i = 0; i < n; ++i) if (a[16 * i + 15] & 1) list.push_back(i);
 		const uint8_t *seq = reads + read_offs[r];
+		const uint8_t *qual = quals ? quals + read_offs[r] : nullptr;
+		const char *cmt = cm && comments[comment_off[r]] ? comments + comment_off[r] : nullptr;
 		const int l_seq = (int)read_lens[r];
 		auto mate_fields = [&](int p_rid, long long p_pos, int p_rev, int p_ncig, const uint32_t *p_cig, bool mate_mapped, int m_rid, long long m_pos, int m_rev,
 		                       int m_ncig, const uint32_t *m_cig) {
@@ -209,8 +225,11 @@ bool bmh_format_sam_parts(const bmh_post_opt_t *po, uint32_t n_reads, const char
 			else out += "*\t0\t0\t*\t";
 			mate_fields(mm ? m.rid : -1, m.pos, p_rev, 0, nullptr, mm, m.rid, m.pos, m.is_rev, m.n_cigar, m.cigar);
 			put_seq(out, seq, 0, l_seq, p_rev != 0);
-			out += "\t*\tAS:i:0\tXS:i:0";
+			out += '\t';
+			if (qual) put_qual(out, qual, 0, l_seq, p_rev != 0); else out += '*';
+			out += "\tAS:i:0\tXS:i:0";
 			if (rg) { out += "\tRG:Z:"; out += rg; }
+			if (cmt) { out += '\t'; out += cmt; }
 			out += '\n';
 			continue;
 		}
@@ -242,7 +261,8 @@ bool bmh_format_sam_parts(const bmh_post_opt_t *po, uint32_t n_reads, const char
 					else { if (c0 == 3 || c0 == 4) qe -= x.cigar[0] >> 4; if (c1 == 3 || c1 == 4) qb += x.cigar[nc - 1] >> 4; }
 				}
 				put_seq(out, seq, qb, qe, x.aln[2] != 0);
-				out += "\t*";
+				out += '\t';
+				if (qual) put_qual(out, qual, qb, qe, x.aln[2] != 0); else out += '*';
 			}
 			if (x.aln[3]) { out += "\tNM:i:"; put_int(out, x.aln[4]); out += "\tMD:Z:"; out += x.md; }
 			if (x.fin[1] >= 0) { out += "\tAS:i:"; put_int(out, x.fin[1]); }
@@ -269,6 +289,7 @@ bool bmh_format_sam_parts(const bmh_post_opt_t *po, uint32_t n_reads, const char
 				char buf[48]; snprintf(buf, sizeof(buf), "\tpa:f:%.3f", (double)x.fin[1] / (double)(x.fin[15] >> 2)); out += buf;
 			}
 			if (!xa[i].empty()) { out += "\tXA:Z:"; out += xa[i]; }
+			if (cmt) { out += '\t'; out += cmt; }                   // src/bwamem.c:1670-1673
 			out += '\n';
 		}
 	}
@@ -284,12 +305,13 @@ static char *format_sam(const bmh_post_opt_t *po, uint32_t n_reads, const char *
                         const uint64_t *read_offs, const uint32_t *read_lens, int n_contigs, const char *const *contig_names,
                         const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read, const int64_t *slot,
                         const int32_t *aln, const uint32_t *cigar, int max_cigar, const char *md, int md_cap,
-                        const int32_t *h_rec, const int32_t *unflag, size_t *len_out)
+                        const int32_t *h_rec, const int32_t *unflag, const uint8_t *quals, const char *comments, const uint64_t *comment_off, size_t *len_out)
 {
 	std::vector<std::string> parts;
 	bmh_cigar_src_t cs;
 	cs.slot64 = slot; cs.aln = aln; cs.cigar = cigar; cs.max_cigar = max_cigar; cs.md = md; cs.md_cap = md_cap;
-	if (!bmh_format_sam_parts(po, n_reads, names, name_off, reads, read_offs, read_lens, n_contigs, contig_names, contig_offset, fin, fin_per_read, cs, h_rec, unflag, parts)) return nullptr;
+	if (!bmh_format_sam_parts(po, n_reads, names, name_off, reads, read_offs, read_lens, n_contigs, contig_names, contig_offset, fin, fin_per_read, cs, h_rec, unflag, parts,
+	                          quals, comments, comment_off)) return nullptr;
 	const unsigned n_thr = (unsigned)parts.size();
 	size_t total = 0;
 	for (const std::string &p : parts) total += p.size();
@@ -307,30 +329,50 @@ static char *format_sam(const bmh_post_opt_t *po, uint32_t n_reads, const char *
 	return res;
 }
 
+extern "C" char *bmh_format_sam_ex(const bmh_post_opt_t *po, uint32_t n_reads, const char *names, const uint64_t *name_off, const uint8_t *reads,
+                                   const uint64_t *read_offs, const uint32_t *read_lens, const uint8_t *quals, const char *comments, const uint64_t *comment_off,
+                                   int n_contigs, const char *const *contig_names, const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read,
+                                   const int64_t *slot, const int32_t *aln, const uint32_t *cigar, int max_cigar, const char *md, int md_cap, size_t *len_out)
+{
+	if (!po || !names || !name_off || !reads || !read_offs || !read_lens || !contig_names || !fin_per_read || !len_out || (n_contigs > 1 && !contig_offset) ||
+	    (!comments) != (!comment_off)) {
+		bmh_set_error("bmh_format_sam: null argument"); return nullptr;
+	}
+	return format_sam(po, n_reads, names, name_off, reads, read_offs, read_lens, n_contigs, contig_names, contig_offset, fin, fin_per_read, slot, aln, cigar, max_cigar,
+	                  md, md_cap, nullptr, nullptr, quals, comments, comment_off, len_out);
+}
+
 extern "C" char *bmh_format_sam(const bmh_post_opt_t *po, uint32_t n_reads, const char *names, const uint64_t *name_off, const uint8_t *reads,
                                 const uint64_t *read_offs, const uint32_t *read_lens, int n_contigs, const char *const *contig_names,
                                 const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read, const int64_t *slot,
                                 const int32_t *aln, const uint32_t *cigar, int max_cigar, const char *md, int md_cap, size_t *len_out)
 {
-	if (!po || !names || !name_off || !reads || !read_offs || !read_lens || !contig_names || !fin_per_read || !len_out || (n_contigs > 1 && !contig_offset)) {
-		bmh_set_error("bmh_format_sam: null argument"); return nullptr;
-	}
-	return format_sam(po, n_reads, names, name_off, reads, read_offs, read_lens, n_contigs, contig_names, contig_offset, fin, fin_per_read, slot, aln, cigar, max_cigar,
-	                  md, md_cap, nullptr, nullptr, len_out);
+	return bmh_format_sam_ex(po, n_reads, names, name_off, reads, read_offs, read_lens, nullptr, nullptr, nullptr, n_contigs, contig_names, contig_offset, fin,
+	                         fin_per_read, slot, aln, cigar, max_cigar, md, md_cap, len_out);
 }
 
 // interleaved pairs: fin / fin_per_read / h_rec / unflag from bmh_finalize_pairs (mem_aln2sam with the mate: flags 0x8 0x20,
 // RNEXT, PNEXT, TLEN; an unmapped read takes its mate's coordinate and strand)
+extern "C" char *bmh_format_sam_pe_ex(const bmh_post_opt_t *po, uint32_t n_reads, const char *names, const uint64_t *name_off, const uint8_t *reads,
+                                      const uint64_t *read_offs, const uint32_t *read_lens, const uint8_t *quals, const char *comments, const uint64_t *comment_off,
+                                      int n_contigs, const char *const *contig_names, const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read,
+                                      const int32_t *h_rec, const int32_t *unflag, const int64_t *slot, const int32_t *aln, const uint32_t *cigar, int max_cigar,
+                                      const char *md, int md_cap, size_t *len_out)
+{
+	if (!po || !names || !name_off || !reads || !read_offs || !read_lens || !contig_names || !fin_per_read || !h_rec || !unflag || !len_out || (n_reads & 1) ||
+	    (n_contigs > 1 && !contig_offset) || (!comments) != (!comment_off)) { bmh_set_error("bmh_format_sam_pe: bad argument"); return nullptr; }
+	return format_sam(po, n_reads, names, name_off, reads, read_offs, read_lens, n_contigs, contig_names, contig_offset, fin, fin_per_read, slot, aln, cigar, max_cigar,
+	                  md, md_cap, h_rec, unflag, quals, comments, comment_off, len_out);
+}
+
 extern "C" char *bmh_format_sam_pe(const bmh_post_opt_t *po, uint32_t n_reads, const char *names, const uint64_t *name_off, const uint8_t *reads,
                                    const uint64_t *read_offs, const uint32_t *read_lens, int n_contigs, const char *const *contig_names,
                                    const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read, const int32_t *h_rec,
                                    const int32_t *unflag, const int64_t *slot, const int32_t *aln, const uint32_t *cigar, int max_cigar,
                                    const char *md, int md_cap, size_t *len_out)
 {
-	if (!po || !names || !name_off || !reads || !read_offs || !read_lens || !contig_names || !fin_per_read || !h_rec || !unflag || !len_out || (n_reads & 1) ||
-	    (n_contigs > 1 && !contig_offset)) { bmh_set_error("bmh_format_sam_pe: bad argument"); return nullptr; }
-	return format_sam(po, n_reads, names, name_off, reads, read_offs, read_lens, n_contigs, contig_names, contig_offset, fin, fin_per_read, slot, aln, cigar, max_cigar,
-	                  md, md_cap, h_rec, unflag, len_out);
+	return bmh_format_sam_pe_ex(po, n_reads, names, name_off, reads, read_offs, read_lens, nullptr, nullptr, nullptr, n_contigs, contig_names, contig_offset, fin,
+	                            fin_per_read, h_rec, unflag, slot, aln, cigar, max_cigar, md, md_cap, len_out);
 }
 
 // bmh_sam_need_cigar for pairs: additionally the own-alignment record of every read (the mate fields come from it)

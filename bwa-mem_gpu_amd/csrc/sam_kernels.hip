@@ -198,6 +198,7 @@ struct sam_args_t {
 	int flag_all, max_XA_hits, max_XA_hits_alt, no_multi, softclip; double drop;
 	int sa;                        // field of a record that holds the XA tag's key: [12] secondary, with ALT contigs [11] secondary_all (bmh_post_opt_t)
 	int rg_len; char rg[256];      // read group id (bmh_post_opt_t::rg_id), 0 = none
+	int copy_comment;              // -C with comments given (d.d_comments): every record ends with its read's comment
 };
 
 // where the text goes: W = 0 counts the bytes, 1 writes them to global memory, 2 into the wave's image in LDS (copied out in dwords afterwards:
@@ -313,6 +314,15 @@ template <int W> __device__ void sam_seq(sam_out_t<W> &o, const uint8_t *seq, in
 	else for (int k = qe - 1; k >= qb; --k) *o.p++ = sam_letter(seq[k], true);
 }
 
+// QUAL: the qualities of [qb, qe) as they are, reversed (not complemented) on the reverse strand -- a byte store per lane, like SEQ
+template <int W> __device__ void sam_qual(sam_out_t<W> &o, const uint8_t *q, int qb, int qe, bool rev)
+{
+	if (qe <= qb) return;
+	if (!W) { o.n += (uint32_t)(qe - qb); return; }
+	if (!rev) for (int k = qb; k < qe; ++k) *o.p++ = (char)q[k];
+	else for (int k = qe - 1; k >= qb; --k) *o.p++ = (char)q[k];
+}
+
 struct sam_mate_t { int rid; long long pos; int is_rev, n_cigar; const uint32_t *cigar; };
 
 template <int W> __device__ void sam_mate_fields(const sam_args_t &A, sam_out_t<W> &o, bool pe, int p_rid, long long p_pos, int p_rev, int p_ncig, const uint32_t *p_cig,
@@ -350,6 +360,9 @@ template <int W> __device__ bool sam_read(const sam_args_t &A, uint32_t r, sam_o
 	const char *name = A.d.d_names + A.d.d_name_off[r];
 	const int name_len = (int)(A.d.d_name_off[r + 1] - A.d.d_name_off[r]) - 1;     // (names are NUL-terminated back to back: no strlen)
 	const uint8_t *seq = A.d.d_reads + A.d.d_offs[r];
+	const uint8_t *qual = A.d.d_quals ? A.d.d_quals + A.d.d_offs[r] : nullptr;       // (FASTQ: the qualities at the letters' offsets)
+	const char *cmt = nullptr; int cmt_len = 0;                                       // (-C: the read's comment, NUL-terminated back to back like the names)
+	if (A.copy_comment) { cmt = A.d.d_comments + A.d.d_comment_off[r]; cmt_len = (int)(A.d.d_comment_off[r + 1] - A.d.d_comment_off[r]) - 1; }
 	const int l_seq = (int)A.d.d_lens[r];
 	int n_rep = 0;
 	for (int i = 0; i < n; ++i) n_rep += a[16 * i + 15] & 1;
@@ -365,8 +378,11 @@ template <int W> __device__ bool sam_read(const sam_args_t &A, uint32_t r, sam_o
 		else out.lit("*\t0\t0\t*\t");
 		sam_mate_fields<W>(A, out, pe, mm ? m.rid : -1, m.pos, p_rev, 0, nullptr, mm, m.rid, m.pos, m.is_rev, m.n_cigar, m.cigar);
 		sam_seq<W>(out, seq, 0, l_seq, p_rev != 0);
-		out.lit("\t*\tAS:i:0\tXS:i:0");
+		out.ch('\t');
+		if (qual) sam_qual<W>(out, qual, 0, l_seq, p_rev != 0); else out.ch('*');
+		out.lit("\tAS:i:0\tXS:i:0");
 		if (A.rg_len) { out.lit("\tRG:Z:"); out.str(A.rg, A.rg_len); }
+		if (cmt_len > 0) { out.ch('\t'); out.str(cmt, cmt_len); }
 		out.ch('\n');
 		return true;
 	}
@@ -399,7 +415,8 @@ template <int W> __device__ bool sam_read(const sam_args_t &A, uint32_t r, sam_o
 				else { if (c0 == 3 || c0 == 4) qe -= x.cigar[0] >> 4; if (c1 == 3 || c1 == 4) qb += x.cigar[nc - 1] >> 4; }
 			}
 			sam_seq<W>(out, seq, qb, qe, x.aln[2] != 0);
-			out.lit("\t*");
+			out.ch('\t');
+			if (qual) sam_qual<W>(out, qual, qb, qe, x.aln[2] != 0); else out.ch('*');
 		}
 		if (x.aln[3]) { out.lit("\tNM:i:"); out.num(x.aln[4]); out.lit("\tMD:Z:"); out.str(x.md, x.aln[6]); }
 		if (x.fin[1] >= 0) { out.lit("\tAS:i:"); out.num(x.fin[1]); }
@@ -441,6 +458,7 @@ template <int W> __device__ bool sam_read(const sam_args_t &A, uint32_t r, sam_o
 				}
 			}
 		}
+		if (cmt_len > 0) { out.ch('\t'); out.str(cmt, cmt_len); }              // src/bwamem.c:1670-1673
 		out.ch('\n');
 		++which;
 	}
@@ -530,7 +548,8 @@ int sam_args(const bmh_post_opt_t *popt, const bmh_sam_dev_t *d, const char *fn,
 {
 	if (!popt || !d) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	if (d->n_reads && (!d->d_names || !d->d_name_off || !d->d_reads || !d->d_offs || !d->d_lens || !d->d_contig_names || !d->d_contig_name_off || !d->d_fin_per_read ||
-	                   !d->d_slot || !d->d_aln || !d->d_cig_off || !d->d_packed || (d->n_contigs > 1 && !d->d_contig_offset) || (d->d_h_rec && (!d->d_unflag || (d->n_reads & 1))))) {
+	                   !d->d_slot || !d->d_aln || !d->d_cig_off || !d->d_packed || (d->n_contigs > 1 && !d->d_contig_offset) || (d->d_h_rec && (!d->d_unflag || (d->n_reads & 1))) ||
+	                   (!d->d_comments) != (!d->d_comment_off))) {
 		bmh_set_error("%s: null argument", fn); return BMH_EINVAL;
 	}
 	memset(&A, 0, sizeof(A));
@@ -538,6 +557,7 @@ int sam_args(const bmh_post_opt_t *popt, const bmh_sam_dev_t *d, const char *fn,
 	A.flag_all = popt->flag_all; A.max_XA_hits = popt->max_XA_hits; A.max_XA_hits_alt = popt->max_XA_hits_alt; A.no_multi = popt->no_multi; A.softclip = popt->softclip;
 	A.drop = (double)popt->XA_drop_ratio;
 	A.sa = popt->contig_is_alt ? 11 : 12;
+	A.copy_comment = popt->copy_comment && d->d_comments ? 1 : 0;
 	if (popt->rg_id && popt->rg_id[0]) {
 		const size_t l = strlen(popt->rg_id);
 		if (l > 255) { bmh_set_error("%s: the read group id is longer than 255 characters", fn); return BMH_EINVAL; }

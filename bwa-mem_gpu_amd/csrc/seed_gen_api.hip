@@ -162,6 +162,18 @@ extern "C" mem_seed_v_gpu *seed_gpu(gpuseed_storage_vector *d)
 	uint64_t file_bytes = 0;
 	bool rd_eof = false;
 	char *rd_line = nullptr; size_t rd_cap = 0;
+	// FASTA, or FASTQ when the first non-blank byte is '@' (the reference's own seeding library parses FASTA only, seed_gen.cu:1698-1728; its host reads
+	// either through kseq): four-line records whose second line is the read -- the same seeds as the same reads in FASTA
+	bool fq = false;
+	{
+		const long at = ftell(fp);
+		int c;
+		while ((c = fgetc(fp)) != EOF && (c == '\n' || c == '\r' || c == ' ' || c == '\t')) {}
+		fq = c == '@';
+		fseek(fp, at, SEEK_SET);
+	}
+	int fq_line = 0;               // FASTQ: which line of its record the next non-blank line is (0 header, 1 sequence, 2 '+', 3 quality)
+	uint64_t fq_rec_bytes = 0;     // FASTQ: the bytes of the header in front of the sequence line (pushed back with it when a batch is full)
 	// next batch of the file into (bases, offs, lens); returns its index, or -1 at the end of the file
 	auto read_batch = [&](uint8_t *bases, uint32_t *offs, uint32_t *lens, uint32_t *n_reads, uint64_t *n_bases) -> long {
 		std::lock_guard<std::mutex> lk(rd_mu);
@@ -171,13 +183,21 @@ extern "C" mem_seed_v_gpu *seed_gpu(gpuseed_storage_vector *d)
 			if (n < 0) { rd_eof = true; break; }
 			const size_t raw = (size_t)n;
 			file_bytes += raw;
-			if (rd_line[0] == '>') continue;
+			if (!fq && rd_line[0] == '>') continue;
 			while (n > 0 && (rd_line[n - 1] == '\n' || rd_line[n - 1] == '\r')) --n;
-			if (n == 0) continue;                     // blank line (kseq skips it too)
-			if (nb + (uint64_t)n > BATCH_BASES) {  // batch full: push the line back
-				fseek(fp, -(long)raw, SEEK_CUR); file_bytes -= raw;
+			if (fq && fq_line != 1) {                  // header, '+' and quality lines; blank lines between records
+				if (fq_line == 0) { if (n == 0) continue; fq_rec_bytes = raw; }
+				fq_line = (fq_line + 1) & 3;
+				continue;
+			}
+			if (n == 0) { if (fq) fq_line = 2; continue; }      // blank line (kseq skips it too)
+			if (nb + (uint64_t)n > BATCH_BASES) {  // batch full: push the line back (FASTQ: with its header)
+				const uint64_t back = raw + (fq ? fq_rec_bytes : 0);
+				fseek(fp, -(long)back, SEEK_CUR); file_bytes -= back;
+				if (fq) fq_line = 0;
 				break;
 			}
+			if (fq) fq_line = 2;
 			memcpy(bases + nb, rd_line, (size_t)n);
 			offs[nr] = (uint32_t)nb; lens[nr] = (uint32_t)n; ++nr;
 			nb += (uint64_t)n;

@@ -326,6 +326,9 @@ typedef struct {
 	/* read group (-R: bwa_set_rg, src/bwa.c:425-452): the ID of the @RG line, NUL-terminated, in HOST memory, at most 255 characters; NULL or empty = none.  Every
 	 * record -- the unmapped ones too -- gets RG:Z:<id> behind AS / XS and in front of SA (mem_aln2sam, src/bwamem.c:1631-1634); the caller writes the @RG header line. */
 	const char *rg_id;
+	/* -C: the read's header comment, a tab in front, at the end of every record -- the unmapped ones too (mem_aln2sam, src/bwamem.c:1670-1673).
+	 * 0 (the default): none.  The writers take the comments from their own arguments (bmh_format_sam_ex, bmh_sam_dev_t, bmh_read_set_t). */
+	int copy_comment;
 } bmh_post_opt_t;
 void bmh_post_opt_default(bmh_post_opt_t *o);
 
@@ -361,14 +364,22 @@ float bmh_finalize_regs_device_last_ms(void);       /* device time of the thread
  * the reported ones and the XA candidates -- and returns their number.  bmh_format_sam then takes, per record, its slot
  * in the bmh_cigar_batch outputs (slot[i], -1 = none) and returns the text (malloc'd; free with bmh_free), one line per
  * record in the reference's order, an unmapped record for reads without a reported alignment.  names: the read names,
- * NUL-terminated, back to back, name_off[r] the start of read r's.  Formats ranges of reads on host threads.  reads: nt4 codes (the
- * path reads FASTA: QUAL is '*').  ALT contigs: po->contig_is_alt (soft clips on ALT hits, the pa:f tag, the XA limits); pairs: bmh_format_sam_pe. */
+ * NUL-terminated, back to back, name_off[r] the start of read r's.  Formats ranges of reads on host threads.  reads: nt4 codes (QUAL is '*':
+ * bmh_format_sam_ex takes the qualities).  ALT contigs: po->contig_is_alt (soft clips on ALT hits, the pa:f tag, the XA limits); pairs: bmh_format_sam_pe. */
 int64_t bmh_sam_need_cigar(const bmh_post_opt_t *po, const int32_t *fin, const uint32_t *fin_per_read, uint32_t n_reads, uint8_t *need);
 char *bmh_format_sam(const bmh_post_opt_t *po, uint32_t n_reads, const char *names, const uint64_t *name_off, const uint8_t *reads,
                      const uint64_t *read_offs, const uint32_t *read_lens, int n_contigs, const char *const *contig_names,
                      const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read, const int64_t *slot,
                      const int32_t *aln, const uint32_t *cigar, int max_cigar, const char *md, int md_cap, size_t *len_out);
 void bmh_free(void *p);
+/* bmh_format_sam with the read file's qualities and comments (FASTQ, -C): quals [.. same offsets as reads] Phred+33 or NULL (QUAL '*'); comments / comment_off
+ * as names / name_off, or NULL (no comments).  QUAL covers SEQ's bases -- the hard clips of later records trimmed, reversed (not complemented) on the reverse
+ * strand, '*' on 0x100 records (src/bwamem.c:1575-1612); with po->copy_comment a non-empty comment goes behind every record's tags (src/bwamem.c:1670-1673).
+ * bmh_format_sam = bmh_format_sam_ex with NULLs; the same for pairs: bmh_format_sam_pe_ex. */
+char *bmh_format_sam_ex(const bmh_post_opt_t *po, uint32_t n_reads, const char *names, const uint64_t *name_off, const uint8_t *reads,
+                        const uint64_t *read_offs, const uint32_t *read_lens, const uint8_t *quals, const char *comments, const uint64_t *comment_off,
+                        int n_contigs, const char *const *contig_names, const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read,
+                        const int64_t *slot, const int32_t *aln, const uint32_t *cigar, int max_cigar, const char *md, int md_cap, size_t *len_out);
 
 /* ---- the read file: one '>' header line and one sequence line per read, the only layout the reference's seeding library parses
  * (src/GPUSeed/seed_gen.cu:1698-1728; the host takes the same file through kseq, bseq_read src/bwa.c:48-66).  Loads it into the flat
@@ -376,9 +387,17 @@ void bmh_free(void *p);
  * src/bntseq.c: what the host tail and bmh_format_sam read), offsets, lengths, and the names (the header up to the first blank,
  * NUL-terminated, back to back: bmh_format_sam's names / name_off).  Blank lines are skipped, CR LF line ends accepted; headers and
  * sequence lines that do not alternate: BMH_EINVAL.  n_threads <= 0: all host threads.  Arrays are malloc'd: bmh_reads_free. */
+/* FASTA or FASTQ (bmh_reads_load / bmh_reads_scan; the first non-blank byte decides, '>' or '@'): FASTQ records are four lines -- '@' header, ONE sequence
+ * line, a '+' line, ONE quality line of the sequence's length --, blank lines between records and CR LF line ends accepted.  A quality line of another
+ * length, a missing '+' line, a truncated last record, a record over more lines, FASTA and FASTQ records in one file: BMH_EINVAL with a message that
+ * names it.  out->quals (FASTQ; NULL for FASTA): the qualities at the letters' offsets.  flags & BMH_READS_COMMENTS: out->comments / comment_offs /
+ * n_comment_bytes hold every read's header comment (the text behind the first blank, as kseq cuts it: src/kseq.h:187, a trailing CR dropped at :140),
+ * NUL-terminated back to back like the names ("" = none); else NULL / 0.  bmh_reads_load_fasta and bmh_fasta_scan take FASTA only, as before. */
+#define BMH_READS_COMMENTS 1
 /* bmh_fasta_scan: reads, bases, name bytes and the longest read of such a file -- out[4] -- from one counting pass of the mapped file, without loading it
  * (what a driver looks at before it chooses between bmh_aligner_run_fasta and the paths that take longer reads). */
 int bmh_fasta_scan(const char *path, int n_threads, uint64_t *out);
+int bmh_reads_scan(const char *path, int n_threads, uint64_t *out);
 typedef struct {
 	uint64_t n_reads, n_bases, n_name_bytes;
 	uint8_t *ascii, *codes;        /* [n_bases] */
@@ -386,8 +405,13 @@ typedef struct {
 	uint32_t *lens;                /* [n_reads] */
 	uint8_t *names;                /* [n_name_bytes] */
 	uint64_t *name_offs;           /* [n_reads] */
+	uint8_t *quals;                /* [n_bases] Phred+33 at the offsets of ascii, or NULL (no qualities: QUAL '*') */
+	uint8_t *comments;             /* [n_comment_bytes] as names, or NULL (none) */
+	uint64_t *comment_offs;        /* [n_reads] */
+	uint64_t n_comment_bytes;
 } bmh_read_set_t;
 int bmh_reads_load_fasta(const char *path, int n_threads, bmh_read_set_t *out);
+int bmh_reads_load(const char *path, int n_threads, int flags, bmh_read_set_t *out);
 void bmh_reads_free(bmh_read_set_t *r);
 
 /* ---- interleaved pairs (read 2i, 2i+1): mem_pestat, mem_matesw (mate rescue, host local alignment), mem_pair, mem_sam_pe
@@ -445,6 +469,11 @@ char *bmh_format_sam_pe(const bmh_post_opt_t *po, uint32_t n_reads, const char *
                         const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read, const int32_t *h_rec,
                         const int32_t *unflag, const int64_t *slot, const int32_t *aln, const uint32_t *cigar, int max_cigar,
                         const char *md, int md_cap, size_t *len_out);
+char *bmh_format_sam_pe_ex(const bmh_post_opt_t *po, uint32_t n_reads, const char *names, const uint64_t *name_off, const uint8_t *reads,
+                           const uint64_t *read_offs, const uint32_t *read_lens, const uint8_t *quals, const char *comments, const uint64_t *comment_off,
+                           int n_contigs, const char *const *contig_names, const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read,
+                           const int32_t *h_rec, const int32_t *unflag, const int64_t *slot, const int32_t *aln, const uint32_t *cigar, int max_cigar,
+                           const char *md, int md_cap, size_t *len_out);
 
 /* ------------------------------------------------- device job builder (SURVEY 8f ranks 1-2 on the GPU) */
 
@@ -557,6 +586,7 @@ int bmh_cigar_pack(const int32_t *d_aln, const uint32_t *d_cigar, int max_cigar,
  * text follows (soft clips on ALT hits, the larger XA limit, pa:f written as printf's %.3f).
  * bmh_sam_text_sizes: first pass, d_text_off [n_reads + 1] = start of every read's records in the text; returns the text's length
  * (waits for the stream).  bmh_sam_text_write: second pass into d_text (asynchronous; the same d_work, untouched in between);
+ * d_quals / d_comments + d_comment_off: as bmh_format_sam_ex's quals / comments / comment_off (d_comment_off [n_reads + 1]), NULL = none;
  * bmh_sam_text_check afterwards waits for the stream and reports an inconsistency between the passes.  d_work: bmh_sam_text_work bytes. */
 typedef struct {
 	uint32_t n_reads;
@@ -567,6 +597,8 @@ typedef struct {
 	const int32_t *d_slot;                                     /* [m] record -> alignment (bmh_sam_select_device) */
 	const int32_t *d_aln; const uint32_t *d_cig_off, *d_packed; /* bmh_cigar_batch's d_aln; bmh_cigar_pack's d_off / d_packed (with MD) */
 	const int32_t *d_h_rec, *d_unflag;                         /* interleaved pairs (bmh_finalize_pairs' out_h / out_unflag) or NULL */
+	const uint8_t *d_quals;                                    /* Phred+33 at d_offs, or NULL (QUAL '*') */
+	const char *d_comments; const uint64_t *d_comment_off;     /* as d_names / d_name_off, or NULL (written only with popt->copy_comment) */
 } bmh_sam_dev_t;
 size_t bmh_sam_text_work(uint32_t n_reads);
 int64_t bmh_sam_text_sizes(const bmh_post_opt_t *popt, const bmh_sam_dev_t *d, uint64_t *d_text_off, void *d_work, size_t work_bytes, void *stream);
@@ -584,7 +616,8 @@ int bmh_sam_text_check(const void *d_work, uint32_t n_reads, void *stream);
  * the device too; the insert-size statistics, the rescue's bookkeeping and the pairs it touches on n_threads host threads in the
  * middle of the batch.  An index with ALT contigs: the same (the device tail and the pairing kernel know the ALT rules).  A batch the device tail refuses (BMH_ECAPACITY)
  * takes the host tail.  The text is what
- * bmh_format_sam / bmh_format_sam_pe write, byte for byte (records only: the caller writes the @SQ header).
+ * bmh_format_sam / bmh_format_sam_pe write, byte for byte (records only: the caller writes the @SQ header).  A read set with quals (FASTQ) gets QUAL,
+ * one with comments and popt->copy_comment the comments (bmh_format_sam_ex): they go to the device beside the letters and names; without them nothing more is sent.
  * cuts: n_batches + 1 read indices, cuts[0] = 0, cuts[n_batches] = n_reads, even batch sizes when paired (the reference cuts its
  * batches by bases, bseq_read src/bwa.c:48-66, and the insert-size statistics are those of a batch).  popt->id0 is ignored (a batch's
  * id0 is its first read).  Reads longer than 700 bases: BMH_EINVAL (the device job builder's limit; such a set goes through
@@ -619,6 +652,10 @@ int bmh_aligner_run(bmh_aligner_t *a, const bmh_read_set_t *reads, const uint64_
  * bmh_reads_load_fasta + bmh_aligner_run with the same cuts. */
 int bmh_aligner_run_fasta(bmh_aligner_t *a, const char *reads_fa, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
                           bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats);
+/* bmh_aligner_run_fasta for a FASTA or FASTQ file (as bmh_reads_load takes it): the loader's pinned batches carry the qualities (QUAL) and, with
+ * popt->copy_comment, the comments.  Same text as bmh_reads_load + bmh_aligner_run with the same cuts. */
+int bmh_aligner_run_file(bmh_aligner_t *a, const char *path, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
+                         bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats);
 
 #ifdef __cplusplus
 }
