@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import fmindex
-from .lib import (ChainOpt, ChainWorkspace, ExtParams, Index, PeOpt, PostOpt, SeedWorkspace, _memcpy_d2d, _np_ptr, _i32p, _u32p, _u64p, _u8p,
+from .lib import (EXT_LONG_MAX, ChainOpt, ChainWorkspace, ExtParams, Index, PeOpt, PostOpt, SeedWorkspace, _memcpy_d2d, _np_ptr, _i32p, _u32p, _u64p, _u8p,
                   cigar_batch, finalize_pairs, format_sam, load_library)
 
 _NT4 = np.full(256, 4, np.uint8)
@@ -185,11 +185,19 @@ def read_fasta_reads_numpy(path: str) -> ReadSet:
     return ReadSet(ascii_ if ascii_.size else np.zeros(1, np.uint8), offs, lens, blob, noff)
 
 
+def _raise_beyond_cap(e: Exception) -> None:
+    """a batch refused because a query side exceeds the extension cap (768 bases by default; EXT_LONG_MAX with long_reads) -> NotImplementedError"""
+    msg = str(e)
+    if "extension cap" in msg:
+        raise NotImplementedError(msg + ": reads this long are beyond the extension kernels of this aligner (Aligner(long_reads=True) takes "
+                                  "flanks of up to EXT_LONG_MAX bases; the reference's own GASAL2 build is sized by MAX_SEQ_LEN, README.md:38)") from e
+
+
 class Aligner:
     def __init__(self, prefix: str | None, device: str = "cuda:0", n_threads: int = 0, _mem=None, sa_intv: int | None = 1,
                  long_reads: bool = False):
-        # long_reads: extension flanks of 769 .. EXT_LONG_MAX bases go to the long-query kernel (bmh_extend_batch_long) instead of
-        # raising; batches without a read beyond 700 bp take the same path either way
+        # long_reads: the extension cap of the chain workspace and of the native aligner is EXT_LONG_MAX -- extension flanks of
+        # 769 .. EXT_LONG_MAX bases go to the long-query kernel instead of raising; batches without such a flank take the same path either way
         self.long_reads = bool(long_reads)
         self.L = load_library()
         self.dev = torch.device(device)
@@ -318,10 +326,6 @@ class Aligner:
             if self.profile:
                 torch.cuda.synchronize(); _t.append(time.perf_counter()); _nm.append(name)
         lens, offs, ascii_ = rs.lens, np.ascontiguousarray(rs.offs), rs.ascii
-        # the device job builder takes reads of up to 700 bases (CH_MAX_READ_LEN, csrc/chain_core.h: the extension kernels' classes end at
-        # 768 columns), the reference's seed filter mem_flt_chained_seeds (src/bwamem.c:970-991) included when a small -W makes it apply;
-        # a batch with a longer read (where the filter applies without -W, beyond ~730 bp) goes through bmh_build_jobs
-        host_jobs = bool((lens > 700).any())
         if int(lens.sum()) >= 1 << 31:
             raise ValueError("a batch holds 2^31 bases or more: offsets inside a batch are 32-bit (use a smaller batch_reads)")
         codes = rs.codes if getattr(rs, "codes", None) is not None else _NT4[ascii_]
@@ -337,65 +341,44 @@ class Aligner:
         _lap("seeding")
         e = self.ep                                             # the reference's GPU extension: deletion penalties for both gap kinds
         ext_p = ExtParams(e.a, e.b, e.o_del, e.e_del, e.o_del, e.e_del, e.zdrop, e.end_bonus)
-        cw = None
-        if host_jobs:
-            from .lib import EXT_LONG_MAX, HostJobs, seeds_to_host, extend_batch
-            hj = HostJobs(self.l_pac, codes, offs, lens, seeds_to_host(s, n), n_threads=self.n_threads, opt=self.copt,
-                          contigs=self.contigs if len(self.contigs) > 1 else None, pac=self.pac)
-            nr, nj = hj.n_regs, hj.n_jobs
-            _lap("chain (host builder: a read beyond 700 bp)")
-            out3 = torch.zeros(max(nj, 1), 3, dtype=torch.int32, device=dev)
-            if nj:
-                d = [torch.from_numpy(np.ascontiguousarray(x).view(np.int32) if x.dtype == np.uint32 else np.ascontiguousarray(x)).to(dev) for x in hj.jobs()]
-                extend_batch(*d, out3, params=ext_p, long_queries=self.long_reads)
-                # a flank longer than the DP kernels take (768 query bases: a read beyond ~790 bp seeded near one end; with long_reads
-                # EXT_LONG_MAX) comes back as INT32_MIN and must never reach the merge; the device builder refuses such reads itself
-                n_bad = int(L.bmh_extend_last_unsupported())
-                if n_bad and self.long_reads:
-                    hj.free()
-                    raise NotImplementedError(f"{n_bad} extension job(s) of this batch have a query side longer than {EXT_LONG_MAX} bases, "
-                                              "the cap of the long-query extension kernel")
-                if n_bad:
-                    hj.free()
-                    raise NotImplementedError(f"{n_bad} extension job(s) of this batch have a query side longer than 768 bases: reads this long are beyond the "
-                                              "extension kernels (the reference's own GASAL2 build is sized by MAX_SEQ_LEN, README.md:38)")
-            regs_h = np.ascontiguousarray(hj.merge(out3[:nj].cpu().numpy())) if nr else np.zeros((0, 8), np.int32)
-            rpr_h = np.ascontiguousarray(hj.regs_per_read.copy()); fr_h = np.ascontiguousarray(hj.frac_rep(), dtype=np.float32)
-            hj.free()
-            _lap("extend+merge")
-        else:
-            cw = self._chain_ws(n, max(int(s.n_seeds), 1))
-            dj = cw.chain_batch(self.index, r, o, l, s)
-            nr, nj = int(dj.n_regs), int(dj.n_jobs)
-            out3 = torch.zeros(max(nj, 1), 3, dtype=torch.int32, device=dev)
-            regs = torch.zeros(max(nr, 1), 8, dtype=torch.int32, device=dev)
-            _lap("chain")
+        # the device job builder for every batch: reads beyond 700 bases are chained in wide records (chain_long_kernel), their flanks
+        # extended up to the workspace's cap (768, or EXT_LONG_MAX with long_reads); HostJobs / bmh_build_jobs are the cross-check
+        cw = self._chain_ws(n, max(int(s.n_seeds), 1))
+        dj = cw.chain_batch(self.index, r, o, l, s)
+        nr, nj = int(dj.n_regs), int(dj.n_jobs)
+        out3 = torch.zeros(max(nj, 1), 3, dtype=torch.int32, device=dev)
+        regs = torch.zeros(max(nr, 1), 8, dtype=torch.int32, device=dev)
+        _lap("chain")
+        try:
             cw.extend(out3, params=ext_p)
-            cw.merge(out3, regs)
-            _lap("extend+merge")
-            if not paired and not self.has_alt:
-                # single-end: the region tail runs on the device too (bmh_finalize_regs_device); what comes back over PCIe are the records
-                po = PostOpt.from_buffer_copy(self.po); po.id0 = id0
-                from .lib import CapacityError, finalize_regs_device
-                try:
-                    d_fin, d_opr = finalize_regs_device(self.index, self.copt, self.ep, po, r, o, regs, nr, dj.d_regs_per_read, dj.d_frac_rep, n,
-                                                        contigs=self.contigs if len(self.contigs) > 1 else None)
-                except CapacityError:
-                    # a read beyond the device tail's fixed limits (65 535 near-equal regions, a patch alignment of more than 1 022
-                    # bases): this batch takes the host form below, which has none of them -- same records
-                    d_fin = None
-                    self.host_tail_batches = getattr(self, "host_tail_batches", 0) + 1
-                if d_fin is not None:
-                    _lap("finalize (device)")
-                    fin = self._d2h("fin", d_fin); opr = np.ascontiguousarray(d_opr.cpu().numpy().view(np.uint32)[:n]); m = len(fin)
-                    _lap("D2H records")
-                    self._lap = _lap; self._prof = (_t, _nm)
-                    return self._finish_single(names, codes, offs, lens, r, o, l, fin, opr, m, po, cw, ws, _lap, _t, _nm, as_bytes, fin_t=d_fin)
-            rpr = torch.empty(n, dtype=torch.int32, device=dev); fr = torch.empty(n, dtype=torch.float32, device=dev)
-            _memcpy_d2d(rpr.data_ptr(), dj.d_regs_per_read, 4 * n); _memcpy_d2d(fr.data_ptr(), dj.d_frac_rep, 4 * n)
-            regs_h = np.ascontiguousarray(regs[:nr].cpu().numpy())
-            rpr_h = np.ascontiguousarray(rpr.cpu().numpy().view(np.uint32)); fr_h = np.ascontiguousarray(fr.cpu().numpy())
-            _lap("D2H regions")
+        except RuntimeError as err:
+            _raise_beyond_cap(err)
+            raise
+        cw.merge(out3, regs)
+        _lap("extend+merge")
+        if not paired and not self.has_alt:
+            # single-end: the region tail runs on the device too (bmh_finalize_regs_device); what comes back over PCIe are the records
+            po = PostOpt.from_buffer_copy(self.po); po.id0 = id0
+            from .lib import CapacityError, finalize_regs_device
+            try:
+                d_fin, d_opr = finalize_regs_device(self.index, self.copt, self.ep, po, r, o, regs, nr, dj.d_regs_per_read, dj.d_frac_rep, n,
+                                                    contigs=self.contigs if len(self.contigs) > 1 else None)
+            except CapacityError:
+                # a read beyond the device tail's fixed limits (65 535 near-equal regions, a patch alignment of more than 1 022
+                # bases): this batch takes the host form below, which has none of them -- same records
+                d_fin = None
+                self.host_tail_batches = getattr(self, "host_tail_batches", 0) + 1
+            if d_fin is not None:
+                _lap("finalize (device)")
+                fin = self._d2h("fin", d_fin); opr = np.ascontiguousarray(d_opr.cpu().numpy().view(np.uint32)[:n]); m = len(fin)
+                _lap("D2H records")
+                self._lap = _lap; self._prof = (_t, _nm)
+                return self._finish_single(names, codes, offs, lens, r, o, l, fin, opr, m, po, cw, ws, _lap, _t, _nm, as_bytes, fin_t=d_fin)
+        rpr = torch.empty(n, dtype=torch.int32, device=dev); fr = torch.empty(n, dtype=torch.float32, device=dev)
+        _memcpy_d2d(rpr.data_ptr(), dj.d_regs_per_read, 4 * n); _memcpy_d2d(fr.data_ptr(), dj.d_frac_rep, 4 * n)
+        regs_h = np.ascontiguousarray(regs[:nr].cpu().numpy())
+        rpr_h = np.ascontiguousarray(rpr.cpu().numpy().view(np.uint32)); fr_h = np.ascontiguousarray(fr.cpu().numpy())
+        _lap("D2H regions")
         po = PostOpt.from_buffer_copy(self.po); po.id0 = id0
         self._lap = _lap; self._prof = (_t, _nm)
         if paired:
@@ -495,6 +478,8 @@ class Aligner:
             nat.free(); nat = None
         if nat is None:
             nat = self._native = NativeAligner(self.index, self.pac, self.l_pac, self.contigs, self.alt if self.has_alt else None, self.copt, self.ep, self.po, self.pe)
+            if self.long_reads:
+                nat.set_max_qlen(EXT_LONG_MAX)
         return nat
 
     def align_file(self, reads_fa: str, out, batch_reads: int = 0, paired: bool = False, chunk_bases: int = 0) -> int:
@@ -510,7 +495,7 @@ class Aligner:
         if os.environ.get("BMH_ALIGNER_NATIVE", "1") != "0" and os.environ.get("BMH_ALIGNER_STREAM", "1") != "0" and not self.profile:
             from .lib import reads_scan
             info = reads_scan(reads_fa)
-            if info["n_reads"] and info["max_len"] <= 700:
+            if info["n_reads"]:
                 out.write(self.header().encode() if binary else self.header())
                 cb = 0
                 if batch_reads <= 0:
@@ -519,9 +504,14 @@ class Aligner:
                         cb = max(cb, 150_000_000)             # (single-end records do not depend on the cuts: see below)
                     cb = min(cb, (1 << 31) - 1024)
                 nat = self._native_aligner()
-                self.last_stats = nat.run_file(reads_fa, paired, (lambda mv: out.write(mv)) if binary else (lambda mv: out.write(bytes(mv).decode())),
-                                                batch_bases=cb, batch_reads=max(batch_reads, 0),
-                                                n_lanes=int(os.environ.get("BMH_ALIGNER_LANES", "3" if paired else "2")), n_threads=self.n_threads)
+                try:
+                    self.last_stats = nat.run_file(reads_fa, paired, (lambda mv: out.write(mv)) if binary else (lambda mv: out.write(bytes(mv).decode())),
+                                                    batch_bases=cb, batch_reads=max(batch_reads, 0),
+                                                    n_lanes=int(os.environ.get("BMH_ALIGNER_LANES", "3" if paired else "2")), n_threads=self.n_threads)
+                except RuntimeError as e:
+                    _raise_beyond_cap(e)
+                    raise
+                self.host_tail_batches = nat.host_tail_batches()
                 return info["n_reads"]
         rs = read_reads(reads_fa, comments=bool(self.po.copy_comment))
         out.write(self.header().encode() if binary else self.header())
@@ -548,10 +538,15 @@ class Aligner:
         # The native pipeline (csrc/align_pipeline.hip: batches driven by C threads, the text of batch k formatted while batches
         # k+1, k+2 are on the device) takes every read set whose reads fit the device job builder; BMH_ALIGNER_NATIVE=0 keeps the
         # batch-after-batch Python loop below (the same stages through the same entry points: the cross-check of the native one).
-        if n and os.environ.get("BMH_ALIGNER_NATIVE", "1") != "0" and rs.codes is not None and int(rs.lens.max()) <= 700 and not self.profile:
+        if n and os.environ.get("BMH_ALIGNER_NATIVE", "1") != "0" and rs.codes is not None and not self.profile:
             nat = self._native_aligner()
-            self.last_stats = nat.run(rs, cuts, paired, (lambda mv: out.write(mv)) if binary else (lambda mv: out.write(bytes(mv).decode())),
-                                      n_lanes=int(os.environ.get("BMH_ALIGNER_LANES", "3" if paired else "2")), n_threads=self.n_threads)   # (pairs: a lane waits for host walks in the middle of its batch)
+            try:
+                self.last_stats = nat.run(rs, cuts, paired, (lambda mv: out.write(mv)) if binary else (lambda mv: out.write(bytes(mv).decode())),
+                                          n_lanes=int(os.environ.get("BMH_ALIGNER_LANES", "3" if paired else "2")), n_threads=self.n_threads)   # (pairs: a lane waits for host walks in the middle of its batch)
+            except RuntimeError as e:
+                _raise_beyond_cap(e)
+                raise
+            self.host_tail_batches = nat.host_tail_batches()
             return n
         for b, e in zip(cuts[:-1], cuts[1:]):
             if e > b:
@@ -598,6 +593,8 @@ class Aligner:
         cn, cs = (n, n_seeds + n_seeds // 8) if c is None else (n + n // 4, n_seeds + n_seeds // 4)
         cw = ChainWorkspace(cn, cs, opt=self.copt)
         cw.set_materialize(False)
+        if self.long_reads:
+            cw.set_max_qlen(EXT_LONG_MAX)
         if len(self.contigs) > 1:
             cw.set_contigs(self.contigs)
             if self.has_alt:

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "pre_calc_seed_intervals_wrapper", "free_gpuseed_data", "seed_gpu", "seed_gpu_last_n_reads",
     "bmh_reads_load_fasta", "bmh_reads_free", "bmh_fasta_scan",
     "bmh_reads_load", "bmh_reads_scan", "bmh_format_sam_ex", "bmh_format_sam_pe_ex", "bmh_aligner_run_file",
+    "bmh_chain_ws_set_max_qlen", "bmh_aligner_set_max_qlen", "bmh_aligner_host_tail_batches",
 ]
 
 
@@ -176,6 +177,20 @@ class NativeAligner:
                                            C.byref(copt), C.byref(ep), C.byref(po), C.byref(pe))
         if not self.handle:
             raise RuntimeError("bmh_aligner_create: " + _err(L))
+
+    def set_max_qlen(self, cap: int) -> None:
+        """bmh_aligner_set_max_qlen: the extension cap of the runs that follow (768 by default, EXT_LONG_MAX for reads of any length)"""
+        L = load_library()
+        L.bmh_aligner_set_max_qlen.argtypes = [C.c_void_p, C.c_uint32]
+        if L.bmh_aligner_set_max_qlen(self.handle, int(cap)) != 0:
+            raise ValueError("bmh_aligner_set_max_qlen: " + _err(L))
+
+    def host_tail_batches(self) -> int:
+        """batches of the last run whose region tail the device refused (the host forms took them)"""
+        L = load_library()
+        L.bmh_aligner_host_tail_batches.restype = C.c_uint64
+        L.bmh_aligner_host_tail_batches.argtypes = [C.c_void_p]
+        return int(L.bmh_aligner_host_tail_batches(self.handle))
 
     def run(self, rs, cuts, paired: bool, write, n_lanes: int = 2, n_threads: int = 0) -> "AlignStats":
         """the batches [cuts[b], cuts[b+1]) of the read set `rs` (an aligner.ReadSet; codes required); write(memoryview) receives every
@@ -662,6 +677,14 @@ class ChainWorkspace:
 
     def set_materialize(self, on: bool) -> None:
         load_library().bmh_chain_set_materialize(self.handle, 1 if on else 0)
+
+    def set_max_qlen(self, cap: int) -> None:
+        """bmh_chain_ws_set_max_qlen: extend / extend_merge send query sides of 769 .. cap bases to the long-query classes (default 768: none);
+        a batch with a longer one raises, naming the cap"""
+        L = load_library()
+        L.bmh_chain_ws_set_max_qlen.argtypes = [C.c_void_p, C.c_uint32]
+        if L.bmh_chain_ws_set_max_qlen(self.handle, int(cap)) != 0:
+            raise ValueError("bmh_chain_ws_set_max_qlen: " + _err(L))
 
     def extend(self, out3_t, params: "ExtParams | None" = None, raw_t=None, stream: int = 0) -> None:
         """bmh_chain_extend: extension of the last chain_batch's jobs straight from their descriptors."""

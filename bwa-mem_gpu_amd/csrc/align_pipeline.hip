@@ -9,7 +9,8 @@
 //     caller's sink while the workers are on the next batches.
 // Single-end batches finish their region tail on the device (bmh_finalize_regs_device); a batch it refuses (BMH_ECAPACITY), an index
 // with ALT contigs and interleaved pairs (bmh_finalize_pairs_dev) take the host forms -- the same choices bwamem_hip/aligner.py makes,
-// the same text.  Reads longer than 700 bases (the device job builder's limit) are refused: the caller takes the slower path.
+// the same text.  Reads of up to BMH_EXT_LONG_MAX bases: the device job builder chains those beyond 700 bases in wide records, and the
+// extension takes query sides up to the aligner's cap (bmh_aligner_set_max_qlen, 768 by default; a batch with a longer one fails the run).
 #include <hip/hip_runtime.h>
 #include <sched.h>
 #include <atomic>
@@ -42,6 +43,7 @@ struct aligner_t {
 	std::vector<int64_t> off; std::vector<int32_t> len; std::vector<uint8_t> alt; bool has_alt;
 	bmh_chain_opt_t co; bmh_ext_params_t ep; bmh_post_opt_t po; bmh_pe_opt_t pe;
 	std::string rg_id;             // the aligner's own copy of popt->rg_id (po.rg_id points into it): the caller's string need not outlive the call that created the aligner
+	uint32_t max_qlen = 768;       // the extension cap of the chain workspaces (bmh_aligner_set_max_qlen)
 };
 
 }   // namespace
@@ -140,6 +142,7 @@ struct lane_t {
 	// the copies themselves, timed by events on the lane's stream (what t[0] and t[5] are NOT: those are host clocks around the whole stage -- the staging of the
 	// letters, offsets and names on host threads / the CIGAR and text kernels the host waits for): [0] reads, offsets, names H2D  [1] SAM text D2H
 	hipEvent_t ev_c[4] = {nullptr, nullptr, nullptr, nullptr}; double copy_ms[2] = {0, 0}; uint64_t copy_bytes[2] = {0, 0}; bool d2h_marked = false;
+	uint32_t host_tail = 0;                      // batches of the run whose region tail the device refused (BMH_ECAPACITY): the host forms took them
 	~lane_t()
 	{
 		for (hipEvent_t e : ev_c) if (e) (void)hipEventDestroy(e);
@@ -521,7 +524,9 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 	if (!Ln.sws || n > Ln.sws_reads || nb > Ln.sws_bases) {
 		if (Ln.sws) bmh_seed_ws_free(Ln.sws);
 		Ln.sws_reads = n + n / 4; Ln.sws_bases = nb + nb / 4;
-		const uint64_t occ = 64ull * Ln.sws_reads > (1ull << 16) ? 64ull * Ln.sws_reads : (1ull << 16);
+		// (64 occurrences per read of 150 bases: a batch of long reads gets that per 150 of its bases)
+		const uint64_t per = std::max<uint64_t>(Ln.sws_reads, Ln.sws_bases / 150);
+		const uint64_t occ = 64ull * per > (1ull << 16) ? 64ull * per : (1ull << 16);
 		Ln.sws = bmh_seed_ws_create(Ln.sws_reads, Ln.sws_bases, Ln.sws_bases, occ);          // one candidate per base is the hard upper bound
 		if (!Ln.sws) return BMH_ENOMEM;
 	}
@@ -544,6 +549,7 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 			if (A.has_alt) RCK(bmh_chain_set_alt(Ln.cws, A.n_contigs, A.alt.data()));
 		}
 	}
+	RCK(bmh_chain_ws_set_max_qlen(Ln.cws, A.max_qlen));
 	bmh_dev_jobs_t dj;
 	// the reference's GPU extension takes the deletion penalties for both gap kinds (src/fastmap.c:417-424)
 	bmh_ext_params_t xp = A.ep; xp.o_ins = A.ep.o_del; xp.e_ins = A.ep.e_del;
@@ -610,6 +616,7 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 			}
 		}
 		if (m < 0) {                                                // the host tail: a read beyond the device tail's fixed limits
+			++Ln.host_tail;
 			RCK(Ln.h_regs.need(8 * (nr + 1))); RCK(Ln.h_rpr.need(n + 1)); RCK(Ln.h_fr.need(n + 1));
 			if (nr) LCK(hipMemcpyAsync(Ln.h_regs.p, Ln.d_regs.p, 32 * (size_t)nr, hipMemcpyDeviceToHost, Ln.st));
 			LCK(hipMemcpyAsync(Ln.h_rpr.p, dj.d_regs_per_read, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
@@ -633,6 +640,7 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 			else if (rc_pd != BMH_ECAPACITY) return rc_pd;              // (BMH_ECAPACITY: a read beyond the device tail's fixed limits: the host forms below)
 		}
 		if (!pe_done) {
+			++Ln.host_tail;
 		// mem_sort_dedup_patch of every read on the device (the first step of the single-end tail: bmh_dedup_regs_device), the rest of mem_sam_pe on host
 		// threads from its records; a batch the device refuses (a read beyond its fixed limits), or BMH_ALIGNER_PE_HOST_DEDUP, takes the regions themselves
 		int64_t md = BMH_ECAPACITY;
@@ -743,6 +751,7 @@ struct bmh_aligner {
 	std::vector<std::unique_ptr<result_t>> pool; int n_results = 0;
 	std::vector<std::string> parts;
 	int dev = -1;
+	uint64_t host_tail_batches = 0;                      // of the last run (bmh_aligner_host_tail_batches)
 };
 
 bmh_aligner_t *bmh_aligner_create(const bmh_index_t *idx, const uint8_t *pac, int64_t l_pac, int n_contigs, const char *const *contig_names,
@@ -765,6 +774,19 @@ bmh_aligner_t *bmh_aligner_create(const bmh_index_t *idx, const uint8_t *pac, in
 	if (pe) A.pe = *pe; else bmh_pe_opt_default(&A.pe);
 	A.co.contig_is_alt = A.has_alt ? A.alt.data() : nullptr; A.po.contig_is_alt = A.has_alt ? A.alt.data() : nullptr;
 	return h;
+}
+
+int bmh_aligner_set_max_qlen(bmh_aligner_t *h, uint32_t cap)
+{
+	if (!h) { bmh_set_error("bmh_aligner_set_max_qlen: null aligner"); return BMH_EINVAL; }
+	if (cap > BMH_EXT_LONG_MAX) { bmh_set_error("bmh_aligner_set_max_qlen: %u bases > BMH_EXT_LONG_MAX (%d)", cap, BMH_EXT_LONG_MAX); return BMH_EINVAL; }
+	h->a.max_qlen = cap > 768 ? cap : 768;
+	return BMH_OK;
+}
+
+uint64_t bmh_aligner_host_tail_batches(const bmh_aligner_t *h)
+{
+	return h ? h->host_tail_batches : 0;
 }
 
 void bmh_aligner_free(bmh_aligner_t *h)
@@ -823,7 +845,8 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 		}
 		h->lanes.push_back(std::move(ln));
 	}
-	for (auto &ln : h->lanes) { for (double &v : ln->t) v = 0.0; ln->copy_ms[0] = ln->copy_ms[1] = 0.0; ln->copy_bytes[0] = ln->copy_bytes[1] = 0; }
+	for (auto &ln : h->lanes) { for (double &v : ln->t) v = 0.0; ln->copy_ms[0] = ln->copy_ms[1] = 0.0; ln->copy_bytes[0] = ln->copy_bytes[1] = 0; ln->host_tail = 0; }
+	h->host_tail_batches = 0;
 	auto worker = [&](int lane_index) {
 		if (hipSetDevice(dev) != hipSuccess) { fail(BMH_ENODEV, "hipSetDevice failed in a worker thread"); return; }
 		lane_t &Ln = *h->lanes[(size_t)lane_index];
@@ -922,6 +945,7 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 	}
 	if (src.release) for (auto &kv : done) if (kv.second) src.release(kv.second->token);       // (a failed run: what was waiting for the writer)
 	n_results = (int)pool.size();                                   // (after a failed run the results that were in flight are gone)
+	for (auto &ln : h->lanes) h->host_tail_batches += ln->host_tail;
 	if (first_rc != BMH_OK) { bmh_set_error("%s", first_err.c_str()); return first_rc; }
 	if (stats) {
 		stats->n_reads = n_reads_total; stats->n_bytes = n_bytes; stats->n_batches = n_written; stats->n_lanes = n_lanes;
@@ -962,7 +986,7 @@ int bmh_aligner_run(bmh_aligner_t *h, const bmh_read_set_t *rs, const uint64_t *
 	for (uint32_t b = 0; b < n_batches; ++b)
 		if (cuts[b + 1] < cuts[b] || (paired && ((cuts[b + 1] - cuts[b]) & 1)) || cuts[b + 1] - cuts[b] > 0xFFFFFFF0ull) { bmh_set_error("bmh_aligner_run: bad batch cuts"); return BMH_EINVAL; }
 	for (uint64_t r = 0; r < rs->n_reads; ++r)
-		if (rs->lens[r] > 700) { bmh_set_error("bmh_aligner_run: read %llu has %u bases: reads beyond 700 go through the host job builder (bmh_build_jobs)", (unsigned long long)r, rs->lens[r]); return BMH_EINVAL; }
+		if (rs->lens[r] > BMH_EXT_LONG_MAX) { bmh_set_error("bmh_aligner_run: read %llu has %u bases: the longest read the aligner takes has %d (BMH_EXT_LONG_MAX)", (unsigned long long)r, rs->lens[r], BMH_EXT_LONG_MAX); return BMH_EINVAL; }
 	if ((uint32_t)n_lanes > n_batches) n_lanes = (int)n_batches;
 	// the letters in pinned or registered host memory (hipHostMalloc, hipHostRegister / bmh_host_pin): the batches go to the device straight from there --
 	// no staging copy into the lane's pinned buffer on host threads
@@ -1058,7 +1082,7 @@ static int run_file(bmh_aligner_t *h, const char *path, uint64_t batch_bases, ui
 				if (fmt.fq) fb->rs.quals = fb->quals.p;
 				if (fmt.comments) { fb->rs.comments = fb->comments.p; fb->rs.comment_offs = fb->comment_offs.p; }
 				rc = bmh_fasta_fill(buf, p, end, nr, nb, nn, load_threads, &fb->rs, fmt, ncm);
-				if (rc == BMH_OK) for (uint64_t r = 0; r < nr; ++r) if (fb->lens.p[r] > 700) { bmh_set_error("%s: read %lld has %u bases: reads beyond 700 go through the host job builder (bmh_build_jobs)", fn, (long long)(id0 + (int64_t)r), fb->lens.p[r]); rc = BMH_EINVAL; break; }
+				if (rc == BMH_OK) for (uint64_t r = 0; r < nr; ++r) if (fb->lens.p[r] > BMH_EXT_LONG_MAX) { bmh_set_error("%s: read %lld has %u bases: the longest read the aligner takes has %d (BMH_EXT_LONG_MAX)", fn, (long long)(id0 + (int64_t)r), fb->lens.p[r], BMH_EXT_LONG_MAX); rc = BMH_EINVAL; break; }
 			}
 			std::lock_guard<std::mutex> lk(qm);
 			if (rc != BMH_OK) { load_rc = rc; load_err = bmh_last_error(); free_list.push_back(fb); break; }

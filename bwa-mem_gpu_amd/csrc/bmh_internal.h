@@ -20,6 +20,7 @@ struct bmh_ext_desc_t {
 	uint32_t max_qlen;           // 0, or an upper bound of every query length of the batch (the longest read): classes no job can reach are not launched
 	const int64_t *jt0;          // [n] first text position of the target window; a window lies on ONE strand of fwd . revcomp(fwd)
 	                             // (mem_chain2aln clips it at l_pac, src/bwamem.c:1261-1264): the kernels decode eight rows at a time on that premise
+	uint32_t long_cap;           // 0, or the cap of bmh_extend_batch_long: query sides of 769 .. long_cap bases run on the long-query classes
 };
 int bmh_extend_batch_desc(const bmh_ext_desc_t *desc, const uint32_t *d_qlen, const uint32_t *d_tlen, const uint32_t *d_h0, uint32_t n,
                           const bmh_ext_params_t *p, int32_t *d_out, int32_t *d_raw, void *stream);

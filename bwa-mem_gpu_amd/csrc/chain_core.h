@@ -68,11 +68,15 @@ struct ch_ctx_t {
 	ch_reg_t *regs;               // output slots, prefix[read] + i in creation order
 	uint32_t *regs_per_read, *jobs_per_read;
 	float *frac_rep;              // per read: part of the read covered by SMEMs with more than max_occ occurrences (mem_chain :415-459)
-	int *err;                     // 1: a read longer than CH_MAX_READ_LEN, or one the reference's seed filter applies to in a form compiled without it
+	int *err;                     // 1: a read longer than CH_LONG_READ_MAX, or one the reference's seed filter applies to in a form compiled without it;
+	                              // 4: a read longer than CH_MAX_READ_LEN in a form with compact records (the classifier sends none there)
 	long long *prof; uint32_t prof_read;
 };
 
+// Reads of at most CH_MAX_READ_LEN bases may take every form; longer ones (up to CH_LONG_READ_MAX, the long-query extension's cap) only the forms with
+// wide records -- chain_kernels.hip sends them to chain_long_kernel -- since read coordinates and list links of the compact records are 16 bits
 #define CH_MAX_READ_LEN 700
+#define CH_LONG_READ_MAX BMH_EXT_LONG_MAX
 // tmp.is_alt of mem_chain (src/bwamem.c:446): a function of the chain's sequence
 CH_HD inline uint32_t chain_is_alt(const ch_ctx_t &x, int rid) { return (x.ctg_alt && rid >= 0 && x.ctg_alt[rid]) ? 1u : 0u; }
 
@@ -765,10 +769,11 @@ template <bool COOP, bool LDSX = false, bool FLT = false, int W = 64, bool STG =
 	if (n == 0 || l_query < o.min_seed_len) return;
 	// the reference's seed filter (mem_flt_chained_seeds, src/bwamem.c:970-991) applies to a read with (W ? 1.1f W : 5.5 ln l) <= 0.05f l,
 	// i.e. a small -W or more than ~730 bp: the FLT forms run it (below, between mem_chain_flt and mem_chain2aln), the others refuse
-	// the read, and so does every form a read longer than the extension kernels' classes reach
+	// the read, and so does every form a read longer than the long-query extension's cap; the compact records end at CH_MAX_READ_LEN
 	int min_HSP_score = 0;
 	const bool flt_on = seed_filter_applies(o, l_query, &min_HSP_score);
-	if (l_query > CH_MAX_READ_LEN || (flt_on && !FLT)) { *x.err = 1; return; }
+	if (l_query > CH_LONG_READ_MAX || (flt_on && !FLT)) { *x.err = 1; return; }
+	if (sizeof(idx_t) < 4 && l_query > CH_MAX_READ_LEN) { *x.err = 4; return; }
 	const uint64_t *g_rbeg; const int32_t *g_qbeg; const uint32_t *g_score;
 #if defined(__HIP_DEVICE_COMPILE__)
 	if constexpr (STG) {

@@ -29,6 +29,7 @@ struct chain_args_t {
 	uint32_t *need;               // [n_reads] seed occurrences the chaining core will sample
 	uint32_t *light_list, *light_n;   // the reads of the lane kernel by need bin: [CH_N_BINS][n_reads], [CH_N_BINS]
 	unsigned long long *need_sum;     // sum of need over the reads beyond heavy_thresh
+	uint32_t *long_list, *long_n;     // the reads longer than CH_MAX_READ_LEN (chain_long_kernel) and how many
 };
 
 // What a read costs the chaining core is the number of seed occurrences mem_chain SAMPLES (at most max_occ per SMEM,
@@ -97,15 +98,21 @@ __global__ void __launch_bounds__(256) chain_classify_kernel(chain_args_t A)
 				i += cnt;
 			}
 		}
-		A.need[r] = need;
-		if (need > A.heavy_thresh) {
+		const uint32_t len = A.x.read_lens[r];
+		if (len > CH_MAX_READ_LEN) {
+			// A long read takes the wide records of chain_long_kernel.  It counts as a read of the wave kernels (need beyond the threshold): the
+			// second pass of bmh_chain_extend_merge, which waits for every side stream, emits its jobs -- the first one only waits for the lane kernel.
+			if (need <= A.heavy_thresh) need = A.heavy_thresh + 1;
+			A.long_list[atomicAdd(A.long_n, 1u)] = r;          // (rare: one atomic each)
+		} else if (need > A.heavy_thresh) {
 			// (the four-per-wave classes stage a read's LOCATED seeds in its scratch: a read that samples few of many -- a small -c -- goes by that count,
 			// to a wave class if need be)
 			int c = ch_class_of(need);
 			if (c < CH_N_SUB && n > need) { const int c2 = ch_class_of(n); c = c2 < CH_N_SUB ? c2 : CH_N_SUB; }
 			bin = CH_N_BINS + c;
 		} else bin = ch_bin_of(need);
-		my = atomicAdd(&l_cnt[bin], 1u);
+		A.need[r] = need;
+		if (bin >= 0) my = atomicAdd(&l_cnt[bin], 1u);
 		if (need > A.heavy_thresh) atomicAdd(&l_need, need);
 		atomicMax(&l_maxlen, A.x.read_lens[r]);
 	}
@@ -284,6 +291,26 @@ __global__ void __launch_bounds__(64) CH_WAVE_ATTR chain_wave_kernel(chain_args_
 	}
 }
 
+// Reads longer than CH_MAX_READ_LEN (up to CH_LONG_READ_MAX bases): one wave per read, the cooperative core over the read's slice of the global scratch in
+// WIDE records -- read coordinates and list links of the compact ones are 16 bits -- and with the reference's seed filter compiled in, since without -W it
+// applies to every read beyond ~730 bp.  The form of the last class (class 10), for any number of entries; a read's seed list is what sizes its slice.
+// (Why not an LDS class: a 1-10 kbp read samples 40-400 occurrences at 124 bytes an entry in wide records -- 5-50 KB, one to a dozen waves per CU --,
+// and long reads are few per batch: DESIGN.md section 4.4.)
+#ifndef CH_LONG_GRID
+#define CH_LONG_GRID 1024u         // blocks of one wave; they stride over the list (an empty list: every block leaves at once)
+#endif
+__global__ void __launch_bounds__(64) chain_long_kernel(chain_args_t A)
+{
+	wtrace_scope_t wt_(WT_CHAIN_WAVE, CH_N_CLASSES);
+	const uint32_t nl = *A.long_n;
+	for (uint32_t i = blockIdx.x; i < nl; i += gridDim.x) {
+		const uint32_t r = A.long_list[i];
+		chain_core::chain_read<true, false, true>(A.x, r, chain_core::global_scratch(A.x, r));
+		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+		__builtin_amdgcn_s_waitcnt(0);                           // the read's output stores before the next read
+	}
+}
+
 // FOUR reads per wave, one per 16-lane row, for the classes of at most 64 entries: the cooperative core with W = 16 (chain_core.h: ch_grp<16>) -- every
 // ballot, broadcast and scan stays inside the row, the rows of a wave diverge freely --, each row's scratch in its own slice of the block's LDS (cap entries of
 // CH_LDS_BYTES_PER_ENTRY bytes), global memory only for the read's seeds and its regions.  These reads used to take a lane each with their scratch in global memory
@@ -325,6 +352,7 @@ struct emit_args_t {
 	const uint32_t *need; uint32_t thresh; int pass;      // need != nullptr: only the reads of one pass count (pass 1: need > thresh, pass 0: the others)
 	ch_outreg_t *outregs;
 	uint32_t *qlen, *tlen, *h0, *job_read, *job_reg, *job_side, *jq_src; int64_t *jt0;
+	uint32_t qcap; uint32_t *over;    // the longest query side beyond qcap (the extension cap of the workspace) goes to *over: the batch is refused
 };
 
 // (reads with more regions than this are emitted by a wave each, emit_wave_kernel: a repetitive read has up to max_occ regions per
@@ -354,21 +382,26 @@ __global__ void __launch_bounds__(256) emit_kernel(emit_args_t A)
 			A.job_read[j] = r; A.job_reg[j] = g; A.job_side[j] = 1; A.jq_src[j] = roff + (uint32_t)(a.seed_qbeg + a.seedlen0);
 			A.jt0[j] = a.seed_rbeg + a.seedlen0; ++j;
 		}
+		const uint32_t qm = (uint32_t)(a.seed_qbeg > a.rq ? a.seed_qbeg : a.rq);
+		if (qm > A.qcap) atomicMax(A.over, qm);
 		A.outregs[g] = o;
 	}
 }
 
 // the same for the reads of the wave classes' lists that have more than CH_EMIT_LANE_MAX regions (fewer sampled seeds than that
 // cannot make that many): one wave per read, one region per lane, the jobs' places by ballot counts
-__global__ void __launch_bounds__(256) emit_wave_kernel(emit_args_t A, const uint32_t *__restrict__ lists, const uint32_t *__restrict__ list_n, int cls_lo, int cls_hi)
+// (the list of the long reads, chain_long_kernel's, after the classes cls_lo .. cls_hi)
+__global__ void __launch_bounds__(256) emit_wave_kernel(emit_args_t A, const uint32_t *__restrict__ lists, const uint32_t *__restrict__ list_n, int cls_lo, int cls_hi,
+                                                        const uint32_t *__restrict__ long_list, const uint32_t *__restrict__ long_n)
 {
 	wtrace_scope_t wt_(WT_CHAIN_EMIT, 1);
 	const int lane = threadIdx.x & 63;
 	const uint32_t gw = (blockIdx.x * 256u + threadIdx.x) >> 6, n_waves = (gridDim.x * 256u) >> 6;
 	const unsigned long long lt = (1ull << lane) - 1ull;
-	for (int cls = cls_lo; cls <= cls_hi; ++cls) {
-		const uint32_t nh = list_n[cls];
-		const uint32_t *list = lists + (size_t)cls * A.n_reads;
+	for (int cls = cls_lo; cls <= cls_hi + 1; ++cls) {
+		const bool lng = cls > cls_hi;
+		const uint32_t nh = lng ? *long_n : list_n[cls];
+		const uint32_t *list = lng ? long_list : lists + (size_t)cls * A.n_reads;
 		for (uint32_t k = gw; k < nh; k += n_waves) {
 			const uint32_t r = list[k];
 			const uint32_t nr = (A.need && (A.need[r] > A.thresh) != (A.pass == 1)) ? 0u : A.regs_per_read[r];
@@ -398,6 +431,8 @@ __global__ void __launch_bounds__(256) emit_wave_kernel(emit_args_t A, const uin
 						A.job_read[j] = r; A.job_reg[j] = g; A.job_side[j] = 1; A.jq_src[j] = roff + (uint32_t)(a.seed_qbeg + a.seedlen0);
 						A.jt0[j] = a.seed_rbeg + a.seedlen0;
 					}
+					const uint32_t qm = (uint32_t)(has0 && a.seed_qbeg > a.rq ? a.seed_qbeg : has1 ? a.rq : 0);
+					if (qm > A.qcap) atomicMax(A.over, qm);
 					A.outregs[g] = o;
 				}
 				j0 += (uint32_t)__builtin_popcountll(m0) + (uint32_t)__builtin_popcountll(m1);
@@ -472,6 +507,7 @@ __global__ void __launch_bounds__(256) merge_kernel(const ch_outreg_t *__restric
 
 // ------------------------------------------------------------------------------------------------ workspace / API
 
+#define CH_EXT_QMAX 768u           // the longest query side of the extension's classes below the long-query ones (extend_kernels.hip: 64 x EXT_WIDE_MAX_C)
 struct bmh_chain_ws {
 	uint32_t max_reads; uint64_t max_seeds;
 	// per-seed scratch
@@ -479,6 +515,7 @@ struct bmh_chain_ws {
 	// per read
 	uint32_t *regs_per_read, *jobs_per_read, *reg_off, *job_off, *heavy_list, *need; float *frac_rep;
 	uint32_t *counters;            // [0..CH_N_CLASSES) heavy_n per size class  [CH_N_CLASSES] err  [12..32) profile stamps  [32..36) reads per need bin of the lane kernel  [36] longest read
+	                               // [37] reads of chain_long_kernel  [38] the longest query side beyond max_qlen (0: none)
 	// contigs
 	int n_contigs; int64_t *ctg_off; int32_t *ctg_len; uint8_t *ctg_alt;
 	// outputs, grown on demand
@@ -502,6 +539,8 @@ struct bmh_chain_ws {
 	uint64_t n_regs_a, n_jobs_a;                 // kernel times of the last batch (bmh_chain_last_timing)
 	int materialize;               // 1: bmh_chain_batch also writes the base arrays q/t (+ qoff/toff)
 	const uint8_t *last_reads, *last_pac; uint64_t last_l_pac;   // sources of the last batch, for bmh_chain_extend
+	uint32_t max_qlen;             // the extension cap: query sides of 769 .. max_qlen bases go to the long-query classes (bmh_chain_ws_set_max_qlen; 768: none)
+	uint32_t over_qlen;            // bmh_chain_batch: the longest query side of the batch beyond max_qlen (0: none) -- bmh_chain_extend refuses the batch
 };
 
 extern "C" void bmh_chain_ws_free(bmh_chain_ws_t *w)
@@ -540,7 +579,7 @@ extern "C" bmh_chain_ws_t *bmh_chain_ws_create(uint32_t max_reads, uint64_t max_
 	A(w->seeds, sizeof(ch_seed_t) * S); A(w->chains, sizeof(ch_chain_t) * S); A(w->order, 4 * S); A(w->opos, 8 * S); A(w->klist, 4 * S);
 	A(w->srt, 8 * S); A(w->cidx, 4 * S); A(w->regs, sizeof(ch_reg_t) * S); A(w->est, sizeof(ch_est_t) * S);
 	const size_t Rn = (size_t)max_reads + 1;
-	A(w->regs_per_read, 4 * Rn); A(w->jobs_per_read, 4 * Rn); A(w->reg_off, 4 * Rn); A(w->job_off, 4 * Rn); A(w->heavy_list, (CH_N_CLASSES + CH_N_BINS) * 4 * Rn); A(w->need, 4 * Rn); A(w->frac_rep, 4 * Rn);
+	A(w->regs_per_read, 4 * Rn); A(w->jobs_per_read, 4 * Rn); A(w->reg_off, 4 * Rn); A(w->job_off, 4 * Rn); A(w->heavy_list, (CH_N_CLASSES + CH_N_BINS + 1) * 4 * Rn); A(w->need, 4 * Rn); A(w->frac_rep, 4 * Rn);
 	A(w->counters, 256);
 	for (int i = 0; i < 4; ++i) A(w->off2[i], 4 * Rn);
 	A(w->need_sum, 16);
@@ -581,7 +620,16 @@ extern "C" bmh_chain_ws_t *bmh_chain_ws_create(uint32_t max_reads, uint64_t max_
 	if (!ok) { bmh_set_error("bmh_chain_ws_create: hipMalloc failed (%s)", hipGetErrorString(hipGetLastError())); bmh_chain_ws_free(w); return nullptr; }
 	w->n_contigs = 1;
 	w->materialize = 1;
+	w->max_qlen = CH_EXT_QMAX;
 	return w;
+}
+
+extern "C" int bmh_chain_ws_set_max_qlen(bmh_chain_ws_t *w, uint32_t cap)
+{
+	if (!w) { bmh_set_error("bmh_chain_ws_set_max_qlen: null workspace"); return BMH_EINVAL; }
+	if (cap > BMH_EXT_LONG_MAX) { bmh_set_error("bmh_chain_ws_set_max_qlen: %u bases > BMH_EXT_LONG_MAX (%d)", cap, BMH_EXT_LONG_MAX); return BMH_EINVAL; }
+	w->max_qlen = cap > CH_EXT_QMAX ? cap : CH_EXT_QMAX;
+	return BMH_OK;
 }
 
 extern "C" void bmh_chain_last_timing(const bmh_chain_ws_t *w, float ms[8])
@@ -659,6 +707,7 @@ static void chain_fill_args(bmh_chain_ws *w, chain_args_t &A, const bmh_chain_op
 	A.heavy_list = w->heavy_list; A.heavy_n = w->counters; A.need = w->need;
 	A.light_list = w->heavy_list + (size_t)CH_N_CLASSES * w->max_reads; A.light_n = w->counters + 32;
 	A.need_sum = (unsigned long long *)w->need_sum;
+	A.long_list = w->heavy_list + (size_t)(CH_N_CLASSES + CH_N_BINS) * w->max_reads; A.long_n = w->counters + 37;
 #ifdef CH_PROFILE
 	{
 		const char *pr = getenv("BMH_CHAIN_PROF_READ");
@@ -768,9 +817,18 @@ static int chain_launch_t(bmh_chain_ws *w, const chain_args_t &A, hipStream_t st
 	return BMH_OK;
 }
 
-// The forms with the reference's seed filter (mem_flt_chained_seeds) are launched only when the options let it apply to a read the
-// device path takes at all (a -W small enough for some read of at most CH_MAX_READ_LEN bases; without -W it starts beyond ~730 bp):
-// they carry the local alignment's rows in private memory.
+// The forms with the reference's seed filter (mem_flt_chained_seeds) are launched only when the options let it apply to a read of at
+// most CH_MAX_READ_LEN bases (a -W small enough; without -W it starts beyond ~730 bp): they carry the local alignment's rows in private
+// memory.  The longer reads of a batch -- the only ones the filter reaches without -W -- take chain_long_kernel, which always has it.
+// The reads beyond CH_MAX_READ_LEN: launched by the host once it has seen that the batch has one (the longest read, counted by the classification --
+// a launch for every batch, its blocks finding the list empty, cost the 150 bp bench about 1-2 %: the kernel carries the seed filter's private arrays)
+static int chain_launch_long(const chain_args_t &A, hipStream_t st)
+{
+	chain_long_kernel<<<A.n_reads < CH_LONG_GRID ? A.n_reads : CH_LONG_GRID, 64, 0, st>>>(A);
+	HIPCK(hipGetLastError());
+	return BMH_OK;
+}
+
 static bool chain_filter_possible(const bmh_chain_opt_t &o) { return o.min_chain_weight > 0 && chain_core::seed_filter_applies(o, CH_MAX_READ_LEN, nullptr); }
 static int chain_launch(bmh_chain_ws *w, const chain_args_t &A, hipStream_t st, bool join)
 {
@@ -805,27 +863,34 @@ extern "C" int bmh_chain_batch(bmh_chain_ws_t *w, const bmh_chain_opt_t *opt, co
 	memset(out, 0, sizeof(*out));
 	{ const int rc = chain_check_args("bmh_chain_batch", w, opt, idx, n_reads, seeds); if (rc != BMH_OK) return rc; }
 	hipStream_t st = (hipStream_t)stream_;
-	w->n_regs = w->n_jobs = 0;
+	w->n_regs = w->n_jobs = 0; w->over_qlen = 0;
 	w->last_reads = d_reads; w->last_pac = idx->dev.pac; w->last_l_pac = idx->dev.l_pac;
 	if (n_reads == 0) return BMH_OK;
 	chain_args_t A;
 	chain_fill_args(w, A, opt, idx, d_reads, d_offs, d_lens, n_reads, seeds);
 	{ const int rc = chain_launch(w, A, st, true); if (rc != BMH_OK) return rc; }
-	size_t tb = w->scan_tmp_bytes;
-	HIPCK(rocprim::exclusive_scan(w->scan_tmp, tb, w->regs_per_read, w->reg_off, 0u, (size_t)n_reads + 1, rocprim::plus<uint32_t>(), st));
-	tb = w->scan_tmp_bytes;
-	HIPCK(rocprim::exclusive_scan(w->scan_tmp, tb, w->jobs_per_read, w->job_off, 0u, (size_t)n_reads + 1, rocprim::plus<uint32_t>(), st));
-	HIPCK(hipMemcpyAsync(w->h_pin + 0, w->reg_off + n_reads, 4, hipMemcpyDeviceToHost, st));
-	HIPCK(hipMemcpyAsync(w->h_pin + 1, w->job_off + n_reads, 4, hipMemcpyDeviceToHost, st));
-	HIPCK(hipMemcpyAsync(w->h_pin + 2, w->counters, 4 * (CH_N_CLASSES + 1), hipMemcpyDeviceToHost, st));
-	HIPCK(hipEventRecord(w->ev_t[5], st));
-	HIPCK(hipStreamSynchronize(st));
+	size_t tb = 0;
+	for (int round = 0; round < 2; ++round) {
+		tb = w->scan_tmp_bytes;
+		HIPCK(rocprim::exclusive_scan(w->scan_tmp, tb, w->regs_per_read, w->reg_off, 0u, (size_t)n_reads + 1, rocprim::plus<uint32_t>(), st));
+		tb = w->scan_tmp_bytes;
+		HIPCK(rocprim::exclusive_scan(w->scan_tmp, tb, w->jobs_per_read, w->job_off, 0u, (size_t)n_reads + 1, rocprim::plus<uint32_t>(), st));
+		HIPCK(hipMemcpyAsync(w->h_pin + 0, w->reg_off + n_reads, 4, hipMemcpyDeviceToHost, st));
+		HIPCK(hipMemcpyAsync(w->h_pin + 1, w->job_off + n_reads, 4, hipMemcpyDeviceToHost, st));
+		HIPCK(hipMemcpyAsync(w->h_pin + 2, w->counters, 4 * (CH_N_CLASSES + 1), hipMemcpyDeviceToHost, st));
+		HIPCK(hipMemcpyAsync(w->h_pin + 40, w->counters + 32 + CH_N_BINS, 4, hipMemcpyDeviceToHost, st));
+		HIPCK(hipEventRecord(w->ev_t[5], st));
+		HIPCK(hipStreamSynchronize(st));
+		// a read beyond CH_MAX_READ_LEN: chain_long_kernel, then the counts again
+		if (round > 0 || w->h_pin[40] <= CH_MAX_READ_LEN) break;
+		{ const int rc = chain_launch_long(A, st); if (rc != BMH_OK) return rc; }
+	}
 	HIPCK(hipGetLastError());
 	(void)hipEventElapsedTime(&w->ms[0], w->ev_t[0], w->ev_t[1]); (void)hipEventElapsedTime(&w->ms[1], w->ev_t[1], w->ev_t[2]);
 	(void)hipEventElapsedTime(&w->ms[2], w->ev_t[3], w->ev_t[4]); (void)hipEventElapsedTime(&w->ms[3], w->ev_t[0], w->ev_t[5]);
 	for (int c = 0; c < CH_N_CLASSES; ++c) w->heavy_per_class[c] = w->h_pin[2 + c];
 	if (getenv("BMH_CHAIN_STATS")) chain_print_stats(w);
-	if (w->h_pin[2 + CH_N_CLASSES] == 1) { bmh_set_error("bmh_chain_batch: a read is longer than %d bp (the extension kernels' classes end at 768 columns): use bmh_build_jobs for this batch", CH_MAX_READ_LEN); return BMH_EINVAL; }
+	if (w->h_pin[2 + CH_N_CLASSES] == 1) { bmh_set_error("bmh_chain_batch: a read is longer than %d bases (BMH_EXT_LONG_MAX, the cap of the long-query extension)", CH_LONG_READ_MAX); return BMH_EINVAL; }
 	if (w->h_pin[2 + CH_N_CLASSES] != 0) { bmh_set_error("bmh_chain_batch: internal error %u in the chaining kernel", w->h_pin[2 + CH_N_CLASSES]); return BMH_ENODEV; }
 #ifdef CH_PROFILE
 	if (A.x.prof) {
@@ -858,8 +923,14 @@ extern "C" int bmh_chain_batch(bmh_chain_ws_t *w, const bmh_chain_opt_t *opt, co
 	E.regs = w->regs; E.prefix = seeds->d_prefix; E.regs_per_read = w->regs_per_read; E.reg_off = w->reg_off; E.job_off = w->job_off; E.need = nullptr; E.thresh = 0; E.pass = 0;
 	E.read_offs = d_offs; E.read_lens = d_lens; E.n_reads = n_reads; E.outregs = w->outregs; E.reg_base = E.job_base = 0;
 	E.qlen = w->qlen; E.tlen = w->tlen; E.h0 = w->h0; E.job_read = w->job_read; E.job_reg = w->job_reg; E.job_side = w->job_side; E.jq_src = w->jq_src; E.jt0 = w->jt0;
+	E.qcap = w->max_qlen; E.over = w->counters + 38;
 	emit_kernel<<<nblk(n_reads, 256), 256, 0, st>>>(E);
-	emit_wave_kernel<<<1024, 256, 0, st>>>(E, w->heavy_list, w->counters, 0, CH_N_CLASSES - 1);
+	emit_wave_kernel<<<1024, 256, 0, st>>>(E, w->heavy_list, w->counters, 0, CH_N_CLASSES - 1, A.long_list, A.long_n);
+	if (w->h_pin[40] > w->max_qlen) {                       // (only a read longer than the cap can have a query side beyond it)
+		HIPCK(hipMemcpyAsync(w->h_pin + 41, w->counters + 38, 4, hipMemcpyDeviceToHost, st));
+		HIPCK(hipStreamSynchronize(st));
+		w->over_qlen = w->h_pin[41];
+	}
 	out->d_qlen = w->qlen; out->d_tlen = w->tlen; out->d_h0 = w->h0; out->d_job_read = w->job_read; out->d_job_reg = w->job_reg; out->d_job_side = w->job_side;
 	out->d_qoff = w->qoff; out->d_toff = w->toff;
 	if (n_jobs == 0 || !w->materialize) { out->d_qoff = out->d_toff = nullptr; HIPCK(hipGetLastError()); return BMH_OK; }
@@ -891,9 +962,16 @@ extern "C" int bmh_chain_batch(bmh_chain_ws_t *w, const bmh_chain_opt_t *opt, co
 extern "C" int bmh_chain_extend(bmh_chain_ws_t *w, const bmh_ext_params_t *p, int32_t *d_out3, int32_t *d_raw, void *stream_)
 {
 	if (!w || !p) { bmh_set_error("bmh_chain_extend: null argument"); return BMH_EINVAL; }
+	if (w->over_qlen) {
+		bmh_set_error("bmh_chain_extend: a query side of %u bases is longer than the extension cap of %u bases (bmh_chain_ws_set_max_qlen, at most BMH_EXT_LONG_MAX = %d)",
+		              w->over_qlen, w->max_qlen, BMH_EXT_LONG_MAX);
+		w->n_regs = w->n_jobs = 0;                          // (no region of the batch comes back: bmh_chain_merge writes none)
+		return BMH_EINVAL;
+	}
 	if (w->n_jobs == 0) return BMH_OK;
 	bmh_ext_desc_t d;
 	d.reads = w->last_reads; d.pac = w->last_pac; d.l_pac = (long long)w->last_l_pac; d.jq_src = w->jq_src; d.job_side = w->job_side; d.jt0 = w->jt0; d.max_qlen = 0;
+	d.long_cap = w->max_qlen > CH_EXT_QMAX ? w->max_qlen : 0;
 	return bmh_extend_batch_desc(&d, w->qlen, w->tlen, w->h0, (uint32_t)w->n_jobs, p, d_out3, d_raw, stream_);
 }
 
@@ -1019,6 +1097,8 @@ extern "C" int bmh_chain_extend_merge(bmh_chain_ws_t *w, const bmh_chain_opt_t *
 	bmh_ext_desc_t d;
 	d.reads = d_reads; d.pac = idx->dev.pac; d.l_pac = (long long)idx->dev.l_pac;
 	d.max_qlen = w->h_pin[40];                                  // (the longest read: the extension skips the classes beyond it)
+	d.long_cap = w->max_qlen > CH_EXT_QMAX ? w->max_qlen : 0;
+	E.qcap = w->max_qlen; E.over = w->counters + 38;
 	HIPCK(hipEventRecord(w->ev_x[0], st));
 	if (n_regs_a) {
 		E.regs_per_read = w->regs_per_read; E.need = w->need; E.thresh = A.heavy_thresh; E.pass = 0; E.reg_off = w->off2[0]; E.job_off = w->off2[1]; E.reg_base = E.job_base = 0;
@@ -1031,6 +1111,8 @@ extern "C" int bmh_chain_extend_merge(bmh_chain_ws_t *w, const bmh_chain_opt_t *
 	}
 	HIPCK(hipEventRecord(w->ev_x[1], st));
 	// ---- pass B: the reads of the wave kernels, counted on a second stream so that the host does not wait for pass A's extension
+	// (the reads beyond CH_MAX_READ_LEN -- pass B's too -- are chained on that stream first: the classification is through, the host has seen it)
+	if (w->h_pin[40] > CH_MAX_READ_LEN) { const int rc = chain_launch_long(A, w->side2); if (rc != BMH_OK) return rc; }
 	HIPCK(hipStreamWaitEvent(w->side2, w->ev_join, 0));
 	// (its own scan scratch: pass A's extension may still be using nothing of ours, but the scans above share scan_tmp with nothing in flight on st)
 	tb = w->scan_tmp_bytes;
@@ -1046,7 +1128,7 @@ extern "C" int bmh_chain_extend_merge(bmh_chain_ws_t *w, const bmh_chain_opt_t *
 	(void)hipEventElapsedTime(&w->ms[2], w->ev_t[3], w->ev_t[4]); (void)hipEventElapsedTime(&w->ms[3], w->ev_t[0], w->ev_t[5]);
 	for (int c = 0; c < CH_N_CLASSES; ++c) w->heavy_per_class[c] = w->h_pin[2 + c];
 	if (getenv("BMH_CHAIN_STATS")) chain_print_stats(w);
-	if (w->h_pin[2 + CH_N_CLASSES] == 1) { bmh_set_error("bmh_chain_extend_merge: a read is longer than %d bp (the extension kernels' classes end at 768 columns): use bmh_build_jobs for this batch", CH_MAX_READ_LEN); return BMH_EINVAL; }
+	if (w->h_pin[2 + CH_N_CLASSES] == 1) { bmh_set_error("bmh_chain_extend_merge: a read is longer than %d bases (BMH_EXT_LONG_MAX, the cap of the long-query extension)", CH_LONG_READ_MAX); return BMH_EINVAL; }
 	if (w->h_pin[2 + CH_N_CLASSES] != 0) { bmh_set_error("bmh_chain_extend_merge: internal error %u in the chaining kernel", w->h_pin[2 + CH_N_CLASSES]); return BMH_ENODEV; }
 	const uint64_t n_regs_b = w->h_pin[32], n_jobs_b = w->h_pin[33];
 	const uint64_t n_regs = n_regs_a + n_regs_b, n_jobs = n_jobs_a + n_jobs_b;
@@ -1061,7 +1143,19 @@ extern "C" int bmh_chain_extend_merge(bmh_chain_ws_t *w, const bmh_chain_opt_t *
 	if (n_regs_b) {
 		E.regs_per_read = w->regs_per_read; E.need = w->need; E.thresh = A.heavy_thresh; E.pass = 1; E.reg_off = w->off2[2]; E.job_off = w->off2[3]; E.reg_base = (uint32_t)n_regs_a; E.job_base = (uint32_t)n_jobs_a;
 		emit_kernel<<<nblk(n_reads, 256), 256, 0, sb>>>(E);
-		emit_wave_kernel<<<1024, 256, 0, sb>>>(E, w->heavy_list, w->counters, 0, CH_N_CLASSES - 1);
+		emit_wave_kernel<<<1024, 256, 0, sb>>>(E, w->heavy_list, w->counters, 0, CH_N_CLASSES - 1, A.long_list, A.long_n);
+		if (w->h_pin[40] > w->max_qlen) {
+			// a read longer than the cap (only those are in this pass) may have a query side beyond it: such a batch is refused before its extension --
+			// the kernels would leave INT32_MIN placeholders, and no region may be built from them
+			HIPCK(hipMemcpyAsync(w->h_pin + 41, w->counters + 38, 4, hipMemcpyDeviceToHost, sb));
+			HIPCK(hipStreamSynchronize(sb));
+			if (w->h_pin[41]) {
+				HIPCK(hipStreamSynchronize(st));                      // (pass A's extension: nothing of the batch is left in flight)
+				bmh_set_error("bmh_chain_extend_merge: a query side of %u bases is longer than the extension cap of %u bases (bmh_chain_ws_set_max_qlen, at most BMH_EXT_LONG_MAX = %d)",
+				              w->h_pin[41], w->max_qlen, BMH_EXT_LONG_MAX);
+				return BMH_EINVAL;
+			}
+		}
 		if (n_jobs_b) {
 			d.jq_src = w->jq_src + n_jobs_a; d.job_side = w->job_side + n_jobs_a; d.jt0 = w->jt0 + n_jobs_a;
 			if (b_side) { const int rc = bmh_extend_reserve((void *)sb, 2 * need_b); if (rc != BMH_OK) return rc; }

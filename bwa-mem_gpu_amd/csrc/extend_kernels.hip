@@ -1335,7 +1335,10 @@ int bmh_extend_batch_desc(const bmh_ext_desc_t *desc, const uint32_t *d_qlen, co
 	if (!p || !desc || (n && (!d_qlen || !d_tlen || !d_h0 || !d_out || !desc->reads || !desc->pac || !desc->jq_src || !desc->job_side || !desc->jt0))) {
 		bmh_set_error("bmh_extend_batch_desc: null argument"); return BMH_EINVAL;
 	}
-	return extend_launch(nullptr, nullptr, d_qlen, nullptr, nullptr, d_tlen, d_h0, n, p, d_out, d_raw, stream_, desc);
+	// (long classes: up to the cap, and no further than the longest query of the batch when the caller knows it)
+	uint32_t cap = desc->long_cap > EXT_LONG_CAP ? EXT_LONG_CAP : desc->long_cap;
+	if (desc->max_qlen && cap > desc->max_qlen) cap = desc->max_qlen;
+	return extend_launch(nullptr, nullptr, d_qlen, nullptr, nullptr, d_tlen, d_h0, n, p, d_out, d_raw, stream_, desc, cap);
 }
 
 static int extend_launch(const uint8_t *d_q, const uint32_t *d_qoff, const uint32_t *d_qlen, const uint8_t *d_t,

@@ -490,6 +490,12 @@ void bmh_chain_ws_free(bmh_chain_ws_t *ws);
 int bmh_chain_set_contigs(bmh_chain_ws_t *ws, int n_contigs, const int64_t *contig_offset, const int32_t *contig_len);
 /* which of them are ALT contigs (is_alt[n_contigs], host memory; NULL or all zero: none) -- call after bmh_chain_set_contigs */
 int bmh_chain_set_alt(bmh_chain_ws_t *ws, int n_contigs, const uint8_t *is_alt);
+/* The extension cap of the workspace: bmh_chain_extend and bmh_chain_extend_merge send query sides of 769 .. cap bases to the long-query
+ * classes of bmh_extend_batch_long.  Default (and any cap up to 768): the classes of bmh_extend_batch alone.  A batch with a longer query
+ * side makes either call return BMH_EINVAL with a message that names the cap, and no region of it comes back.  Reads of up to
+ * BMH_EXT_LONG_MAX bases are chained (those beyond 700 one wave per read, in wide records); a longer read makes the chaining call
+ * return BMH_EINVAL.  cap > BMH_EXT_LONG_MAX: BMH_EINVAL. */
+int bmh_chain_ws_set_max_qlen(bmh_chain_ws_t *ws, uint32_t cap);
 
 typedef struct {
 	uint64_t n_jobs, n_regs, q_bytes, t_bytes;
@@ -620,8 +626,8 @@ int bmh_sam_text_check(const void *d_work, uint32_t n_reads, void *stream);
  * one with comments and popt->copy_comment the comments (bmh_format_sam_ex): they go to the device beside the letters and names; without them nothing more is sent.
  * cuts: n_batches + 1 read indices, cuts[0] = 0, cuts[n_batches] = n_reads, even batch sizes when paired (the reference cuts its
  * batches by bases, bseq_read src/bwa.c:48-66, and the insert-size statistics are those of a batch).  popt->id0 is ignored (a batch's
- * id0 is its first read).  Reads longer than 700 bases: BMH_EINVAL (the device job builder's limit; such a set goes through
- * bmh_build_jobs).  n_threads: host threads of the host forms (<= 0: all).  The aligner borrows idx and pac: both outlive it; popt->rg_id is copied. */
+ * id0 is its first read).  Reads of up to BMH_EXT_LONG_MAX bases; a longer one: BMH_EINVAL.  A batch with a query side beyond the aligner's
+ * extension cap (bmh_aligner_set_max_qlen; 768 by default) fails the run with BMH_EINVAL naming the cap.  n_threads: host threads of the host forms (<= 0: all).  The aligner borrows idx and pac: both outlive it; popt->rg_id is copied. */
 int bmh_effective_cpus(void);      /* CPUs this process may use: affinity mask capped by the cgroup quota (what n_threads <= 0 resolves to) */
 typedef struct bmh_aligner bmh_aligner_t;
 typedef int (*bmh_sam_sink_t)(void *user, const char *text, size_t len);
@@ -643,6 +649,12 @@ bmh_aligner_t *bmh_aligner_create(const bmh_index_t *idx, const uint8_t *pac, in
                                   const int32_t *contig_len, const uint8_t *contig_is_alt, const bmh_chain_opt_t *copt, const bmh_ext_params_t *ep,
                                   const bmh_post_opt_t *popt, const bmh_pe_opt_t *pe);
 void bmh_aligner_free(bmh_aligner_t *a);
+/* The extension cap of the aligner's chain workspaces (bmh_chain_ws_set_max_qlen): 768 by default, BMH_EXT_LONG_MAX for reads of any length
+ * the aligner takes.  Applies to the runs that follow. */
+int bmh_aligner_set_max_qlen(bmh_aligner_t *a, uint32_t cap);
+/* Batches of the last run whose region tail the device refused (BMH_ECAPACITY: a patch alignment with a query side beyond 1 022 bases, more than
+ * 65 535 near-equal regions; pairs: a read beyond the pairing kernels' limits): the host forms took them, same text. */
+uint64_t bmh_aligner_host_tail_batches(const bmh_aligner_t *a);
 int bmh_aligner_run(bmh_aligner_t *a, const bmh_read_set_t *reads, const uint64_t *cuts, uint32_t n_batches, int paired, int n_lanes, int n_threads,
                     bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats);
 /* The same from a read FILE (one '>' header line and one sequence line per read, as bmh_reads_load_fasta takes), batch by batch: a loader thread cuts the
