@@ -717,19 +717,26 @@ __global__ void __launch_bounds__(256) cigar_finish_kernel(cigar_args_t A)
 	out[4] = n_mm + n_gap; out[5] = score; out[6] = md_len; out[7] = flags;
 }
 
-// largest direction matrix (the whole rectangle bounds every retry) and longest sequence of the batch
+// largest direction matrix (the whole rectangle bounds every retry) and longest sequence of the batch; out[7]: largest |rlen - qlen|
+// of the regions beyond CG_LDS_MAX (the long form's band is at least that + 3 wide, ksw_global2's w >= |tlen - qlen| + 3)
 __global__ void __launch_bounds__(256) cigar_size_kernel(const int32_t *regs, int stride, const uint32_t *sel, uint32_t n, unsigned long long *out)
 {
 	const uint32_t job = blockIdx.x * 256u + threadIdx.x;
-	unsigned long long zb = 0, ml = 0;
+	unsigned long long zb = 0, ml = 0, dl = 0;
 	if (job < n) {
 		const int32_t *R = regs + (size_t)stride * (sel ? sel[job] : job);
 		const long long rb = (long long)(uint32_t)R[4] | (long long)R[5] << 32, re = (long long)(uint32_t)R[6] | (long long)R[7] << 32;
 		const long long ql = (long long)R[3] - R[2], rl = re - rb;
-		if (ql > 0 && rl > 0 && ql < (1 << 20) && rl < (1 << 20)) { zb = (unsigned long long)(ql * rl); ml = (unsigned long long)(ql > rl ? ql : rl); }
+		if (ql > 0 && rl > 0 && ql < (1 << 20) && rl < (1 << 20)) {
+			zb = (unsigned long long)(ql * rl); ml = (unsigned long long)(ql > rl ? ql : rl);
+			if (ml > CG_LDS_MAX) dl = (unsigned long long)(ql > rl ? ql - rl : rl - ql);
+		}
 	}
-	for (int o = 32; o; o >>= 1) { zb = max(zb, (unsigned long long)__shfl_xor((long long)zb, o)); ml = max(ml, (unsigned long long)__shfl_xor((long long)ml, o)); }
-	if ((threadIdx.x & 63) == 0) { atomicMax(out, zb); atomicMax(out + 1, ml); }
+	for (int o = 32; o; o >>= 1) {
+		zb = max(zb, (unsigned long long)__shfl_xor((long long)zb, o)); ml = max(ml, (unsigned long long)__shfl_xor((long long)ml, o));
+		dl = max(dl, (unsigned long long)__shfl_xor((long long)dl, o));
+	}
+	if ((threadIdx.x & 63) == 0) { atomicMax(out, zb); atomicMax(out + 1, ml); atomicMax(out + 7, dl); }
 }
 
 // the scratch of bmh_cigar_batch per (device, stream), like the other stages': kept between calls (the direction matrices of a million 300 bp alignments are
@@ -876,12 +883,17 @@ extern "C" int bmh_cigar_batch(const bmh_index_t *idx, const uint8_t *d_reads, c
 	if (rc == BMH_OK && max_len > 512) rc = launch_cigar<11, 8>(a, grid, lds, st);
 	if (rc != BMH_OK) return rc;
 	if (a.long_split) {
-		// one wave per long region; its direction matrix holds at most min(length, 2 (opt_w << 2) + 1) columns of every row (a
-		// band that does not fit is flagged 4), the bases and the H / E rows of absolute columns sit beside it
+		// one wave per long region; its direction matrix holds at most min(length, 2 w + 1) columns of every row, where the band w is
+		// at most max(opt_w << 2, |rlen - qlen| + 3) (the retries stop at opt_w << 2; a length difference widens it beyond), the bases
+		// and the H / E rows of absolute columns sit beside it
 		cigar_args_t b = a;
 		b.max_len = long_len;
 		b.z_lds_bytes = 0;
-		const unsigned long long band = 2ull * ((unsigned long long)opt_w << 2) + 1;
+		const unsigned long long wmax = (unsigned long long)opt_w << 2 > h[7] + 3 ? (unsigned long long)opt_w << 2 : h[7] + 3;
+		const unsigned long long band0 = 2ull * ((unsigned long long)opt_w << 2) + 1;
+		unsigned long long band = 2ull * wmax + 1;
+		// (a slab of at most 1 GiB for the widening: never binding for sides up to 32 768 bases; a region whose band still does not fit is flagged 4)
+		if (band > band0 && (band < long_len ? band : long_len) * long_len > (1ull << 30)) band = band0 > (1ull << 30) / long_len ? band0 : (1ull << 30) / long_len;
 		b.z_slab_stride = ((band < long_len ? band : long_len) * long_len + 255) & ~255ull;
 		b.lws_stride = (2ull * long_len + 3ull * 4 * long_len + 255) & ~255ull;
 		const unsigned long long per = b.z_slab_stride + b.lws_stride;

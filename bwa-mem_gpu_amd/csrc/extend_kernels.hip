@@ -1016,7 +1016,8 @@ __global__ void __launch_bounds__(256) ext_closed_form_kernel(ext_args_t A, uint
 		const bool have = id < n;
 		const int qlen = have ? (int)A.qlen[id] : 0, tlen = have ? (int)A.tlen[id] : 0, h0 = have ? (int)A.h0[id] : 1;
 		const job_src_t src = ext_job_src(A, id, have, qlen, tlen);
-		const bool elig = have && qlen > 0 && qlen <= 512 && tlen >= qlen && params_ok;     // (512: the LDS rows; longer queries have no DP class either)
+		// (512: the LDS rows; longer queries have no DP class either.  h0 = 0: no cell is ever non-zero, which the forms below do not model)
+		const bool elig = have && qlen > 0 && qlen <= 512 && tlen >= qlen && h0 > 0 && params_ok;
 		int hi = -1, lo = -0x7000, cnt = 0;   // largest / (negated) smallest mismatching column, mismatch count of this lane
 		for (int j0 = 8 * l8; __any(elig && j0 < qlen); j0 += 64) {
 			if (elig && j0 < qlen) {
@@ -1247,6 +1248,18 @@ extern "C" int64_t bmh_extend_last_unsupported(void)
 	if (hipEventSynchronize(g_last->ev1) != hipSuccess) return -1;
 	if (hipMemcpy(&n0, g_last->counts, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
 	return (int64_t)n0;
+}
+
+// jobs per class of the thread's last bmh_extend_batch (tests: which kernels the router chose).  Waits for the batch.
+extern "C" int bmh_extend_last_class_sizes(uint32_t *sizes, int cap)
+{
+	if (!sizes || cap < 0) { bmh_set_error("bmh_extend_last_class_sizes: bad argument"); return BMH_EINVAL; }
+	if (!g_last || !g_last->have_ev) return 0;
+	uint32_t c[2 * EXT_N_CLS];
+	HIPCK(hipEventSynchronize(g_last->ev1));
+	HIPCK(hipMemcpy(c, g_last->counts, sizeof(c), hipMemcpyDeviceToHost));
+	for (int k = 0; k < cap && k < EXT_N_CLS; ++k) sizes[k] = c[2 * k];
+	return EXT_N_CLS;
 }
 
 // Occupancy cap for co-scheduling: a block that reserves `g_ext_lds` bytes of (unused) dynamic LDS limits the DP

@@ -215,6 +215,11 @@ int bmh_extend_batch(const uint8_t *d_q, const uint32_t *d_qoff, const uint32_t 
  * refuses such a batch up front; bmh_chain_batch only admits reads up to 700 bases, whose flanks always fit. */
 int64_t bmh_extend_last_unsupported(void);
 
+/* Jobs per kernel class of the calling thread's last bmh_extend_batch[_long] (waits for it): sizes[c] for c < min(cap, number of
+ * classes); returns the number of classes (0 before any batch).  Class 0 = unsupported, 1..18 = 16-lane rows, 19..26 = wide
+ * kernel, 27 = decided without DP (closed form), 28..48 = packed 16-bit kernels, 49..53 = long-query kernel.  For tests. */
+int bmh_extend_last_class_sizes(uint32_t *sizes, int cap);
+
 /* Long queries, opt-in: bmh_extend_batch, except that jobs whose query has 769 .. min(max_qlen, BMH_EXT_LONG_MAX) bases (max_qlen 0:
  * BMH_EXT_LONG_MAX) run on the long-query kernel (one workgroup per alignment; same contract, results bit-identical to ksw_extend2
  * without a band).  Jobs of at most 768 bases take exactly the kernels of bmh_extend_batch; longer ones than the cap get INT32_MIN
@@ -557,7 +562,9 @@ int bmh_chain_extend_merge_timing(const bmh_chain_ws_t *ws, float ms[3], uint64_
  * first n regions.  opt_w = mem_opt_t.w (300).
  * Out, per job: d_cigar[max_cigar] (len << 4 | op, op 0 M, 1 I, 2 D, 3 S), d_aln[8] = {pos_lo, pos_hi (0-based,
  * forward strand of the concatenated reference), is_rev, n_cigar, NM, global score, MD length, flags (1 = more than
- * max_cigar-2 ops, 2 = interval rejected by bwa_gen_cigar2, 4 = too large, 8 = MD longer than md_cap)}, d_md[md_cap]
+ * max_cigar-2 ops, 2 = interval rejected by bwa_gen_cigar2, 4 = too large: a side of 2^20 bases or more, or a region beyond 704
+ * bases whose band -- max(4 opt_w, |rlen - qlen| + 3) -- needs a direction matrix (min(qlen, 2 band + 1) x rlen bytes) over 1 GiB, never
+ * the case for sides up to 32 768 bases; 8 = MD longer than md_cap)}, d_md[md_cap]
  * (NUL-terminated; d_md may be NULL).  The index must carry its pac.  Synchronises the stream once (sizes). */
 int bmh_cigar_batch(const bmh_index_t *idx, const uint8_t *d_reads, const uint32_t *d_offs, const uint32_t *d_lens,
                     const int32_t *d_regs, int reg_stride, const uint32_t *d_sel, uint32_t n, const bmh_ext_params_t *p, int opt_w,

@@ -170,13 +170,13 @@ def test_seeding_unique_interval_shortcut(hip, oracle, case):
         common.assert_seeds_equal(got, want, "phases " + phases + ": ")
 
 
-def gpu_extend(B, jobs, zdrop=0, want_raw=True, scoring=None, packed=None):
+def gpu_extend(B, jobs, zdrop=0, want_raw=True, scoring=None, packed=None, end_bonus=5):
     """packed: None = the library's default routing (packed 16-bit kernels for the jobs that qualify), 0 = 32-bit kernels only"""
     import torch
     if packed is not None:
         was = B.load_library().bmh_extend_set_packed(int(packed))
         try:
-            return gpu_extend(B, jobs, zdrop, want_raw, scoring)
+            return gpu_extend(B, jobs, zdrop, want_raw, scoring, end_bonus=end_bonus)
         finally:
             B.load_library().bmh_extend_set_packed(was)
     q, qoff, qlen, t, toff, tlen, h0 = jobs
@@ -186,13 +186,14 @@ def gpu_extend(B, jobs, zdrop=0, want_raw=True, scoring=None, packed=None):
     out = torch.zeros(n, 3, dtype=torch.int32, device="cuda")
     raw = torch.zeros(n, 6, dtype=torch.int32, device="cuda") if want_raw else None
     prm = B.ExtParams.default(zdrop=zdrop)
+    prm.end_bonus = end_bonus
     if scoring is not None:
         if len(scoring) == 6:
             a_, b_, od_, ed_, oi_, ei_ = scoring
-            prm = B.ExtParams(a_, b_, od_, ed_, oi_, ei_, zdrop, 5)
+            prm = B.ExtParams(a_, b_, od_, ed_, oi_, ei_, zdrop, end_bonus)
         else:
             a_, b_, o_, e_ = scoring
-            prm = B.ExtParams(a_, b_, o_, e_, o_, e_, zdrop, 5)
+            prm = B.ExtParams(a_, b_, o_, e_, o_, e_, zdrop, end_bonus)
     B.extend_batch(*d, out, params=prm, raw_t=raw)
     torch.cuda.synchronize()
     # both launch forms of the packed kernels -- one kernel per class, and the persistent kernel that works all classes off

@@ -69,7 +69,8 @@ def _very_long_jobs(rng):
     return _pack(qs, ts, h0)
 
 
-def gpu_extend_long(B, jobs, zdrop=0, end_bonus=5, long_queries=True, raw=True, max_qlen=0):
+def gpu_extend_long(B, jobs, zdrop=0, end_bonus=5, long_queries=True, raw=True, max_qlen=0, scoring=(1, 4, 6, 1, 6, 1)):
+    """scoring: (a, b, o_del, e_del, o_ins, e_ins)"""
     import torch
     q, qoff, qlen, t, toff, tlen, h0 = jobs
     n = len(qlen)
@@ -77,7 +78,7 @@ def gpu_extend_long(B, jobs, zdrop=0, end_bonus=5, long_queries=True, raw=True, 
          for x in (q, qoff, qlen, t, toff, tlen, h0)]
     out = torch.zeros(n, 3, dtype=torch.int32, device="cuda")
     r6 = torch.zeros(n, 6, dtype=torch.int32, device="cuda") if raw else None
-    prm = B.ExtParams(1, 4, 6, 1, 6, 1, zdrop, end_bonus)
+    prm = B.ExtParams(*scoring, zdrop, end_bonus)
     B.extend_batch(*d, out, params=prm, raw_t=r6, long_queries=long_queries, max_qlen=max_qlen)
     torch.cuda.synchronize()
     n_bad = int(B.load_library().bmh_extend_last_unsupported())
@@ -256,16 +257,22 @@ def test_aligner_long_reads(hip, tmp_path):
     al0.close()
 
 
-@pytest.mark.parametrize("readlen,n_reads,mode", [(1000, 1500, "se_hard"), (2500, 600, "se_hard"), (1000, 1500, "pe")])
-def test_reference_gase_aln_long_reads(hip, tmp_path, readlen, n_reads, mode):
+SCORING_OPTS = "-A 2 -B 8 -O 12,14 -E 2,3 -T 60 -w 60"      # given in full: the Aligner does not rescale the penalties by -A
+
+
+@pytest.mark.parametrize("readlen,n_reads,mode,opts", [(1000, 1500, "se_hard", ""), (2500, 600, "se_hard", ""), (1000, 1500, "pe", ""),
+                                                        (1000, 1500, "se_hard", SCORING_OPTS), (1000, 1500, "pe", SCORING_OPTS)],
+                         ids=["1000-1500-se_hard", "2500-600-se_hard", "1000-1500-pe", "1000-1500-se_hard-scoring", "1000-1500-pe-scoring"])
+def test_reference_gase_aln_long_reads(hip, tmp_path, readlen, n_reads, mode, opts):
     """The reference's own host code (oracle/_ref/dropin/bwa-gasal2, linked on this library) with BMH_GASAL_MAX_SEQ_LEN against
-    Aligner(long_reads=True) on the same reads (one length per file: the reference's host code aborts on mixed lengths)."""
+    Aligner(long_reads=True) on the same reads (one length per file: the reference's host code aborts on mixed lengths), at the
+    default scoring and at another one with asymmetric gap penalties (both sides get the same options)."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     if not os.path.exists(os.path.join(root, "oracle", "_ref", "dropin", "bwa-gasal2")):
         pytest.skip("oracle/_ref/dropin/bwa-gasal2 not built (needs the reference sources at build time)")
-    env = dict(os.environ, E2E_LONG="1", E2E_READLEN=str(readlen), E2E_TAG=f"long{readlen}_{mode}")
-    r = subprocess.run([sys.executable, os.path.join(root, "scripts", "e2e_dropin.py"), str(tmp_path), "2000000", str(n_reads), "1", mode],
+    env = dict(os.environ, E2E_LONG="1", E2E_READLEN=str(readlen), E2E_TAG=f"long{readlen}_{mode}" + ("_scoring" if opts else ""))
+    r = subprocess.run([sys.executable, os.path.join(root, "scripts", "e2e_dropin.py"), str(tmp_path), "2000000", str(n_reads), "1", mode] + ([opts] if opts else []),
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env)
     out = r.stdout.decode()
     assert r.returncode == 0 and "SAM IDENTICAL" in out, out[-3000:]
