@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
-"""bench.py -- seed-and-extend hot path on MI355X: Mreads/s, roofline and CPU baseline.
+"""bench.py -- seed-and-extend hot path on MI355X: Mreads/s; with --full also roofline, CPU baseline and self-check.
 
 Contract (driver): python bench.py --gpus N --steps K --warmup W ; for N > 1 launched by
 torch.distributed.run, one rank per GPU.  Rank 0 prints ONE JSON line.
+A plain run does what the headline needs: setup, W warm-up steps, K timed steps, --dump-outputs, the line.
+--full adds the rest after the timed steps (the same steps fed over PCIe, isolated stage times, the CPU baseline and the
+oracle's check of the timed batch, the VALU calibration, the rooflines, the rows after the hot path) and the complete
+check of the suffix array in setup.
 
 Workload (BASELINE.json configs[1], the configuration the metric is quoted on):
   1 M synthetic 150 bp single-end reads per GPU against an hg38-SCALE index: a seeded synthetic 3.1 Gbp genome
@@ -185,6 +189,9 @@ def main():
     ap.add_argument("--sa-intv", type=int, default=1, help="suffix-array samples resident in HBM: every N-th row (1 = the whole suffix array: "
                     "locating a seed is one gather; 16 = what the reference's `bwa index` writes for its GPU index, src/bwtindex.c:324)")
     ap.add_argument("--paired", action="store_true", help="interleaved 2 x read-len pairs (configs[3]); reads-per-gpu counts reads, shards stay on pair boundaries")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: the complete check of the suffix array, "
+                    "the steps fed over PCIe, isolated stage times, the CPU baseline and the self-check against the oracle, the VALU calibration, "
+                    "the rooflines and the rows after the hot path (without it a run sets up, warms up, times the steps, dumps and prints the line)")
     ap.add_argument("--no-verify-index", dest="verify", action="store_false", help="skip the complete check of the suffix array after the build")
     ap.add_argument("--index-cache", default=os.environ.get("BENCH_INDEX_CACHE", ""), help="directory: save the built genome + index there / load them from there "
                     "(setup only; used by scripts/profile_round.sh so that the rocprofv3 passes do not rebuild it)")
@@ -195,16 +202,29 @@ def main():
                     "(one extension over all jobs of the batch, after all of its chaining: pays with batches in flight, whose work fills the wait)")
     ap.add_argument("--no-pcie", dest="pcie", action="store_false", help="skip the second timed loop (steps fed from pinned host memory)")
     ap.add_argument("--no-next-rows", dest="next_rows", action="store_false")
-    ap.add_argument("--cpu-sample", type=int, default=int(os.environ.get("BENCH_CPU_SAMPLE", "100000")), help="reads of the all-cores CPU leg (0 = no CPU baseline)")
-    ap.add_argument("--cpu-sample-1t", type=int, default=int(os.environ.get("BENCH_CPU_SAMPLE_1T", "3000")), help="reads of the one-thread CPU legs")
-    ap.add_argument("--verify-sample", type=int, default=int(os.environ.get("BENCH_VERIFY_SAMPLE", "-1")), help="reads of the last timed batch whose GPU seeds and regions are "
-                    "compared with the oracle after the timed loops (-1: the CPU sample at N = 1, 10000 per rank at N > 1; 0: off)")
+    # (the three samples default to None so that a plain run can tell an explicit request, which needs --full, from the default)
+    ap.add_argument("--cpu-sample", type=int, default=None, help="reads of the all-cores CPU leg (0 = no CPU baseline; default BENCH_CPU_SAMPLE or 100000)")
+    ap.add_argument("--cpu-sample-1t", type=int, default=None, help="reads of the one-thread CPU legs (default BENCH_CPU_SAMPLE_1T or 3000)")
+    ap.add_argument("--verify-sample", type=int, default=None, help="reads of the last timed batch whose GPU seeds and regions are "
+                    "compared with the oracle after the timed loops (-1: the CPU sample at N = 1, 10000 per rank at N > 1; 0: off; default BENCH_VERIFY_SAMPLE or -1)")
     ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps write the regions of the last timed step as DIR/*.npy "
                     "(rank 0; float64, a fixed seeded sample of the reads, at most 64 MB)")
     ap.add_argument("--print-cache-dir", action="store_true", help="print the --index-cache directory this command would use and exit (for the profile scripts)")
     ap.add_argument("--distinct-batches", type=int, default=int(os.environ.get("BENCH_DISTINCT_BATCHES", "4")), help="different read batches the steps take in turn "
                     "(step i works on batch i mod N; 10 puts configs[2]'s 10 M distinct reads through one GPU in 10 steps); at least 2")
     a = ap.parse_args()
+    samples = (("cpu_sample", "BENCH_CPU_SAMPLE", "100000"), ("cpu_sample_1t", "BENCH_CPU_SAMPLE_1T", "3000"), ("verify_sample", "BENCH_VERIFY_SAMPLE", "-1"))
+    if a.full:
+        for k, var, dflt in samples:
+            if getattr(a, k) is None:
+                setattr(a, k, int(os.environ.get(var, dflt)))
+    else:
+        asked = ["--" + k.replace("_", "-") for k, _, _ in samples if getattr(a, k)]
+        if asked:
+            ap.error(" / ".join(asked) + ": the CPU baseline and the self-check run with --full only")
+        # a plain run: only what the headline needs (the extras below all key on these)
+        a.verify = a.pcie = a.next_rows = False
+        a.cpu_sample = a.cpu_sample_1t = a.verify_sample = 0
     n_batches = max(2, a.distinct_batches)
     CB = 1                        # the batch the isolated passes, the CPU baseline and the self-check work on
     if a.print_cache_dir:
@@ -558,13 +578,14 @@ def main():
         L.bmh_tune_set(b"CHAIN_REPLAY_HEAVY", 0, 1)
     # ---------------- the regions of the LAST TIMED step of the last lane, as they left the timed loop (over PCIe when that loop ran):
     # what the self-check below compares with the oracle.  The check is made on batch CB; a lane whose last step was another batch runs
-    # one more (untimed) step of the same code path on batch CB.
+    # one more (untimed) step of the same code path on batch CB.  (--full only, like everything else between here and the result line)
     vlane = lanes[-1]
-    if getattr(vlane, "last_batch", -1) != CB or chain_replay:
-        vlane.k_end = 0
-        vlane.step(CB, host_in if a.pcie else None)
-    torch.cuda.synchronize()
-    last_regs_h = vlane.host_out[: vlane.n_regs].numpy().copy() if vlane.last_pcie else vlane.last_regs[: vlane.n_regs].cpu().numpy()
+    if a.full:
+        if getattr(vlane, "last_batch", -1) != CB or chain_replay:
+            vlane.k_end = 0
+            vlane.step(CB, host_in if a.pcie else None)
+        torch.cuda.synchronize()
+        last_regs_h = vlane.host_out[: vlane.n_regs].numpy().copy() if vlane.last_pcie else vlane.last_regs[: vlane.n_regs].cpu().numpy()
 
     if distributed:
         tt = torch.tensor([dt, dt_pcie or 0.0], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
@@ -588,7 +609,7 @@ def main():
     # per-kernel durations of one more pass on the last batch (HIP events on the launch stream), for the roofline
     iso_ms = {}
     dr = batches[CB][1]
-    for _ in range(3):
+    for _ in range(3 if a.full else 0):
         sd = ws.seed_batch(dindex, dr.ascii, dr.offs, dr.lens, 19, stream=h_main)
         tm = ws.timing()
         torch.cuda.synchronize()
@@ -636,14 +657,14 @@ def main():
     if rank == 0:
         ms_per_step = dt / a.steps * 1e3
         value = total_reads * a.steps / dt / 1e6
-        # VALU calibration of THIS device in THIS run (bmh_calib_valu: the DP kernels' instruction kinds without their data, 8 waves per SIMD), with
+        # VALU calibration of THIS device in THIS run (--full; bmh_calib_valu: the DP kernels' instruction kinds without their data, 8 waves per SIMD), with
         # the shader clock read inside the kernel (s_memtime over s_memrealtime around a VALU-dense loop): the extension is VALU-bound, MI355X boards
         # differ by up to 12 % in sustained clock (MI355X_MICROARCH.md), so two bench lines can be split into clock and code
         cal, clock = {}, {}
         L.bmh_calib_valu.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]
         L.bmh_calib_last_clock.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
         ms_c = C.c_float(0); ops_c = C.c_double(0); mhz_c = C.c_double(0); cpi_c = C.c_double(0)
-        for mode, nm in ((0, "independent_v_max_add"), (1, "dependent_chain"), (2, "dpp_row_shr_max"), (4, "packed_u16_add_max")):
+        for mode, nm in ((0, "independent_v_max_add"), (1, "dependent_chain"), (2, "dpp_row_shr_max"), (4, "packed_u16_add_max")) if a.full else ():
             if L.bmh_calib_valu(mode, 8, 20000, None, C.byref(ms_c), C.byref(ops_c)) == 0:
                 cal[nm] = round(ops_c.value / (ms_c.value * 1e-3) / VALU_PEAK_LANEOPS, 3)
                 if mode == 0 and L.bmh_calib_last_clock(C.byref(mhz_c), C.byref(cpi_c)) == 0:
@@ -652,7 +673,8 @@ def main():
                                     "on every SIMD (the SIMD issues its oldest ready wave first: that wave runs at the SIMD's rate, one instruction per ~4.4 cycles)"}
         st = stats[CB]
         index_how = ("loaded from --index-cache (built on the device by an earlier run of this command)" if build_stats.get("loaded_from_cache") else
-                     "built on the device in setup" + (" and verified completely (every adjacent pair of suffix-array rows)" if build_stats.get("verified") else ", not verified (--no-verify-index)"))
+                     "built on the device in setup" + (" and verified completely (every adjacent pair of suffix-array rows)" if build_stats.get("verified") else
+                                                       ", not verified (--no-verify-index)" if a.full else ", not verified (--full verifies it)"))
         from bwamem_hip.lib import sources_sha16
         lib_sha = sources_sha16()
         workload_key = f"g{a.genome_mbp:g}_r{n_reads}_l{a.read_len}_{'pe' if a.paired else 'se'}_sa{a.sa_intv}"

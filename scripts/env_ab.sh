@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; cd $R
 rounds=$1; shift
 export BENCH_INDEX_CACHE=${BENCH_INDEX_CACHE:-/tmp/bmh_cache}
-ARGS=${AB_ARGS:---no-pcie --cpu-sample 0 --no-next-rows --steps 10 --warmup 2}
+ARGS=${AB_ARGS:---full --no-pcie --cpu-sample 0 --no-next-rows --steps 10 --warmup 2}
 for r in $(seq 1 $rounds); do
   for c in "$@"; do
     ( if [ "$c" != "-" ]; then for kv in ${c//;/ }; do export "$kv"; done; fi

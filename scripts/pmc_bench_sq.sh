@@ -3,7 +3,7 @@
 TAG=$1; shift
 R=$GRAFT_REPO_ROOT; cd $R
 export BENCH_INDEX_CACHE=${BENCH_INDEX_CACHE:-/tmp/bmh_cache}
-A="--cpu-sample 0 --no-next-rows --no-pcie $*"
+A="--full --cpu-sample 0 --no-next-rows --no-pcie $*"
 # (the exact cache directory of THIS command: genome size, sample interval and generator version are in its name)
 [ -f "$(python bench.py $A --print-cache-dir)/meta.json" ] || python bench.py $A --steps 1 --warmup 0 > /dev/null 2>&1
 D=$R/gpurun_out/pmcsq_$TAG; rm -rf $D; mkdir -p $D

@@ -166,7 +166,7 @@ def test_baseline_configs_1_3_and_4_at_full_size(variant):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     # (configs[3] is 1 M PAIRS: two million interleaved reads per batch)
     extra = {"single": [], "paired": ["--paired", "--reads-per-gpu", "2000000"], "300bp": ["--read-len", "300"]}[variant] + ["--distinct-batches", "2"]
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--verify-sample", "100000", "--no-next-rows", "--cpu-sample", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--verify-sample", "100000", "--no-next-rows", "--cpu-sample", "0",
                         "--no-pcie"] + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     res = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])

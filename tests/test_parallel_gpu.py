@@ -71,7 +71,7 @@ def test_bench_spawns_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher and no WORLD_SIZE: two fresh ranks, one JSON line with n_gpus 2, the timed batch
     of every rank verified against the oracle (small workload: 40 Mbp genome, 20 k reads per rank)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--genome-mbp", "40", "--reads-per-gpu", "20000",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--genome-mbp", "40", "--reads-per-gpu", "20000",
                         "--verify-sample", "2000", "--no-next-rows"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -88,7 +88,7 @@ def test_bench_with_four_ranks_on_a_300_mbp_index(tmp_path):
     their shards' reads, then the broadcast, every rank's timed batch checked against the oracle, max-over-ranks timing.  (VERDICT r05 asked
     for eight ranks; the GPU pool's process guard ends a run with more than six processes on the card, and the test runner is one of them.)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "4", "--warmup", "2", "--genome-mbp", "300", "--reads-per-gpu", "50000",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--steps", "4", "--warmup", "2", "--genome-mbp", "300", "--reads-per-gpu", "50000",
                         "--verify-sample", "2000", "--no-next-rows", "--distinct-batches", "2"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -151,7 +151,7 @@ def test_bench_under_torchrun_takes_the_rccl_branch():
     of the timing and of the verdict) executes on the device -- with one rank, the most this box can hold."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "HIP_VISIBLE_DEVICES")}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-                        os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--genome-mbp", "40", "--reads-per-gpu", "20000",
+                        os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--genome-mbp", "40", "--reads-per-gpu", "20000",
                         "--verify-sample", "2000", "--no-next-rows", "--cpu-sample", "0", "--no-pcie"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     res = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])
