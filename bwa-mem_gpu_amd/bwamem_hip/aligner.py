@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import fmindex
-from .lib import (EXT_LONG_MAX, ChainOpt, ChainWorkspace, ExtParams, Index, PeOpt, PostOpt, SeedWorkspace, _memcpy_d2d, _np_ptr, _i32p, _u32p, _u64p, _u8p,
+from .lib import (EXT_LONG_MAX, ChainOpt, ChainWorkspace, ExtParams, Index, PeOpt, PostOpt, ReseedOpt, SeedWorkspace, _memcpy_d2d, _np_ptr, _i32p, _u32p, _u64p, _u8p,
                   cigar_batch, finalize_pairs, format_sam, load_library)
 
 _NT4 = np.full(256, 4, np.uint8)
@@ -219,6 +219,7 @@ class Aligner:
         self.ep = ExtParams.default()
         self.po = PostOpt(); self.L.bmh_post_opt_default(C.byref(self.po))
         self.pe = PeOpt(); self.L.bmh_pe_opt_default(C.byref(self.pe))
+        self.reseed = ReseedOpt.default()                        # BWA-MEM's second and third seeding rounds: off until -g
         # ALT contigs (<prefix>.alt): the chain filter, the marking of primary hits, MAPQ, the XA / pa tags and the clipping depend on them
         # (src/bwamem.c:446,518,571-574,702,714-760,1540,1663,1742,1755); the region tail of such an index runs on the host
         self.has_alt = bool(self.alt.any())
@@ -237,14 +238,16 @@ class Aligner:
         pac = np.ascontiguousarray(np.concatenate([pac, np.zeros(2, np.uint8)]))
         return cls(None, _mem=(idx, contigs or [("chrS", int(len(genome_fwd)))], pac), **kw)
 
-    def set_options(self, argv) -> None:
+    def set_options(self, argv, *, split_factor: float | None = None, split_width: int | None = None, max_mem_intv: int | None = None) -> None:
         """gase_aln's command-line options (src/fastmap.c:166-262) that reach this path, as a list of strings, e.g.
         ["-k", "23", "-A", "2", "-a"].  The device extension takes -A -B and the DELETION penalties -O -E for both gap
         kinds, as the reference's GPU extension does (src/fastmap.c:417-424); -O/-E given as "del,ins" keep the pair for
         the host stages.  Unlike the reference (update_a, src/fastmap.c), nothing is rescaled by -A: pass every value you want
         changed (-B -O -E -T -U).
         -d and -L are accepted and ignored (they do not reach the reference's GPU extension either).  -C appends every read's header
-        comment to its records.  Not modelled: -x -r -s -y (seeding variants the GPU seeding of the reference ignores too), -I -H -V."""
+        comment to its records.  -g turns on BWA-MEM's re-seeding (the second and third seeding rounds of mem_collect_intv); its parameters
+        are the keyword arguments split_factor (-r, 1.5), split_width (-s, 10) and max_mem_intv (-y, 20; 0 leaves out the third round).
+        Not modelled: -x -r -s -y on the option list (seeding variants the GPU seeding of the reference ignores too), -I -H -V."""
         import math
         co, ep, po, pe = self.copt, self.ep, self.po, self.pe
         i = 0
@@ -253,7 +256,7 @@ class Aligner:
             return int(a), int(b) if b else int(a)
         while i < len(argv):
             f = argv[i]
-            if f in ("-a", "-M", "-Y", "-S", "-P", "-j", "-C"):
+            if f in ("-a", "-M", "-Y", "-S", "-P", "-j", "-C", "-g"):
                 if f == "-j":                             # the .alt file is ignored (src/fastmap.c:186,390-392): every sequence belongs to the primary assembly
                     self.alt[:] = 0; self.has_alt = False; co.contig_is_alt = None; po.contig_is_alt = None
                     if getattr(self, "_native", None) is not None: self._native.free(); self._native = None
@@ -263,6 +266,7 @@ class Aligner:
                 elif f == "-M": po.no_multi = 1
                 elif f == "-Y": po.softclip = 1
                 elif f == "-C": po.copy_comment = 1
+                elif f == "-g": self.reseed.enable = 1              # takes no value (src/fastmap.c:202)
                 elif f == "-S": pe.no_rescue = 1
                 else: pe.no_pairing = 1
                 i += 1; continue
@@ -305,6 +309,9 @@ class Aligner:
             elif f in ("-l", "-v", "-f", "-d", "-L"): pass              # bookkeeping; -d -L: no effect on the GPU extension
             else:
                 raise ValueError(f"option {f} is not modelled")
+        if split_factor is not None: self.reseed.split_factor = float(split_factor)
+        if split_width is not None: self.reseed.split_width = int(split_width)
+        if max_mem_intv is not None: self.reseed.max_mem_intv = int(max_mem_intv)
 
     def header(self) -> str:
         return "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in self.contigs) + (getattr(self, "rg_line", "") + "\n" if getattr(self, "rg_line", "") else "")
@@ -337,7 +344,7 @@ class Aligner:
         nb = max(int(lens.sum()), 1)
         ws = self._seed_ws(n, nb)
         _lap("seed workspace")
-        s = ws.seed_batch(self.index, r, o, l, self.copt.min_seed_len)
+        s = ws.seed_batch(self.index, r, o, l, self.copt.min_seed_len, reseed=self.reseed if self.reseed.enable else None)
         _lap("seeding")
         e = self.ep                                             # the reference's GPU extension: deletion penalties for both gap kinds
         ext_p = ExtParams(e.a, e.b, e.o_del, e.e_del, e.o_del, e.e_del, e.zdrop, e.end_bonus)
@@ -480,6 +487,7 @@ class Aligner:
             nat = self._native = NativeAligner(self.index, self.pac, self.l_pac, self.contigs, self.alt if self.has_alt else None, self.copt, self.ep, self.po, self.pe)
             if self.long_reads:
                 nat.set_max_qlen(EXT_LONG_MAX)
+        nat.set_reseed(self.reseed if self.reseed.enable else None)
         return nat
 
     def align_file(self, reads_fa: str, out, batch_reads: int = 0, paired: bool = False, chunk_bases: int = 0) -> int:

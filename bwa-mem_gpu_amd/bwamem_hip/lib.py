@@ -22,7 +22,7 @@ def lib_path() -> str:
 # every symbol include/bwamem_hip.h and include/seed_gen.h declare
 EXPORTED_SYMBOLS = [
     "bmh_last_error", "bmh_device_count", "bmh_set_device", "bmh_index_upload", "bmh_index_from_device",
-    "bmh_index_free", "bmh_index_probe", "bmh_index_replicate", "bmh_rccl_where", "bmh_rccl_unique_id", "bmh_rccl_comm_init_rank", "bmh_rccl_comm_destroy", "bmh_index_broadcast_rccl", "bmh_index_replicate_all", "bmh_shard_range", "bmh_index_densify_sa", "bmh_index_build", "bmh_seed_ws_create", "bmh_seed_ws_free", "bmh_seed_batch", "bmh_seed_last_timing",
+    "bmh_index_free", "bmh_index_probe", "bmh_index_replicate", "bmh_rccl_where", "bmh_rccl_unique_id", "bmh_rccl_comm_init_rank", "bmh_rccl_comm_destroy", "bmh_index_broadcast_rccl", "bmh_index_replicate_all", "bmh_shard_range", "bmh_index_densify_sa", "bmh_index_build", "bmh_seed_ws_create", "bmh_seed_ws_free", "bmh_seed_batch", "bmh_seed_last_timing", "bmh_reseed_opt_default", "bmh_seed_batch_reseed", "bmh_aligner_set_reseed",
     "bmh_host_pin", "bmh_host_unpin", "bmh_extend_batch", "bmh_extend_batch_long", "bmh_extend_last_ms", "bmh_extend_last_unsupported", "bmh_extend_last_class_sizes", "bmh_extend_set_packed", "bmh_tune_set", "bmh_wtrace_start", "bmh_wtrace_stop", "bmh_wtrace_kept", "bmh_extend_release", "bmh_finalize_release", "bmh_matesw_release", "bmh_calib_gather", "bmh_calib_valu", "bmh_calib_valu_placed", "bmh_calib_last_clock",
     "bmh_jobs_frac_rep", "bmh_post_opt_default", "bmh_finalize_regs", "bmh_finalize_regs_device", "bmh_finalize_regs_device_last_ms", "bmh_sam_need_cigar", "bmh_format_sam", "bmh_free",
     "bmh_pe_opt_default", "bmh_finalize_pairs", "bmh_finalize_pairs_dev", "bmh_dedup_regs_device", "bmh_finalize_pairs_deduped", "bmh_rescue_check_counts", "bmh_sam_need_cigar_pe", "bmh_format_sam_pe",
@@ -185,6 +185,12 @@ class NativeAligner:
         if L.bmh_aligner_set_max_qlen(self.handle, int(cap)) != 0:
             raise ValueError("bmh_aligner_set_max_qlen: " + _err(L))
 
+    def set_reseed(self, opt: "ReseedOpt | None") -> None:
+        """bmh_aligner_set_reseed: the seeding rounds of the runs that follow (None: re-seeding off)"""
+        L = load_library()
+        if L.bmh_aligner_set_reseed(self.handle, C.byref(opt) if opt is not None else None) != 0:
+            raise ValueError("bmh_aligner_set_reseed: " + _err(L))
+
     def host_tail_batches(self) -> int:
         """batches of the last run whose region tail the device refused (the host forms took them)"""
         L = load_library()
@@ -279,6 +285,22 @@ class NativeAligner:
         if self.handle:
             load_library().bmh_aligner_free(self.handle)
             self.handle = None
+
+
+class ReseedOpt(C.Structure):
+    """bmh_reseed_opt_t: BWA-MEM's second and third seeding rounds (gase_aln -g)"""
+    _fields_ = [("enable", C.c_int), ("split_factor", C.c_float), ("split_width", C.c_int), ("max_mem_intv", C.c_int)]
+
+    @classmethod
+    def default(cls, **kw) -> "ReseedOpt":
+        """mem_opt_init's values (re-seeding off, 1.5, 10, 20), then the keyword arguments (enable, split_factor, split_width, max_mem_intv)"""
+        o = cls()
+        load_library().bmh_reseed_opt_default(C.byref(o))
+        for k, v in kw.items():
+            if k not in ("enable", "split_factor", "split_width", "max_mem_intv"):
+                raise TypeError(f"ReseedOpt: unknown field {k}")
+            setattr(o, k, v)
+        return o
 
 
 class SeedsT(C.Structure):
@@ -417,6 +439,12 @@ def load_library() -> C.CDLL:
     L.bmh_seed_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
                                  C.c_void_p, C.POINTER(SeedsT)]
     L.bmh_seed_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.bmh_reseed_opt_default.argtypes = [C.POINTER(ReseedOpt)]
+    L.bmh_seed_batch_reseed.restype = C.c_int
+    L.bmh_seed_batch_reseed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
+                                        C.POINTER(ReseedOpt), C.c_void_p, C.POINTER(SeedsT)]
+    L.bmh_aligner_set_reseed.restype = C.c_int
+    L.bmh_aligner_set_reseed.argtypes = [C.c_void_p, C.POINTER(ReseedOpt)]
     L.bmh_extend_batch.restype = C.c_int
     L.bmh_extend_batch.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.POINTER(ExtParams), C.c_void_p, C.c_void_p, C.c_void_p]
     L.bmh_extend_batch_long.restype = C.c_int
@@ -616,12 +644,17 @@ class SeedWorkspace:
         if not self.handle:
             raise RuntimeError("bmh_seed_ws_create: " + _err(L))
 
-    def seed_batch(self, index: Index, reads_t, offs_t, lens_t, min_seed_len: int = 19, stream: int = 0) -> SeedsT:
-        """reads_t/offs_t/lens_t: torch CUDA tensors (uint8 ASCII, int32/uint32 offsets and lengths)."""
+    def seed_batch(self, index: Index, reads_t, offs_t, lens_t, min_seed_len: int = 19, stream: int = 0, reseed: "ReseedOpt | None" = None) -> SeedsT:
+        """reads_t/offs_t/lens_t: torch CUDA tensors (uint8 ASCII, int32/uint32 offsets and lengths).  reseed: a ReseedOpt with enable = 1 adds
+        BWA-MEM's second and third seeding rounds (bmh_seed_batch_reseed); None or enable = 0: bmh_seed_batch."""
         L = load_library()
         out = SeedsT()
-        rc = L.bmh_seed_batch(self.handle, index.handle, reads_t.data_ptr(), offs_t.data_ptr(), lens_t.data_ptr(),
-                              lens_t.numel(), min_seed_len, stream, C.byref(out))
+        if reseed is not None and reseed.enable:
+            rc = L.bmh_seed_batch_reseed(self.handle, index.handle, reads_t.data_ptr(), offs_t.data_ptr(), lens_t.data_ptr(),
+                                         lens_t.numel(), min_seed_len, C.byref(reseed), stream, C.byref(out))
+        else:
+            rc = L.bmh_seed_batch(self.handle, index.handle, reads_t.data_ptr(), offs_t.data_ptr(), lens_t.data_ptr(),
+                                  lens_t.numel(), min_seed_len, stream, C.byref(out))
         if rc != 0:
             raise RuntimeError(f"bmh_seed_batch rc={rc}: " + _err(L))
         return out

@@ -44,6 +44,7 @@ struct aligner_t {
 	bmh_chain_opt_t co; bmh_ext_params_t ep; bmh_post_opt_t po; bmh_pe_opt_t pe;
 	std::string rg_id;             // the aligner's own copy of popt->rg_id (po.rg_id points into it): the caller's string need not outlive the call that created the aligner
 	uint32_t max_qlen = 768;       // the extension cap of the chain workspaces (bmh_aligner_set_max_qlen)
+	bmh_reseed_opt_t rs = {0, 1.5f, 10, 20};   // the seeding rounds (bmh_aligner_set_reseed; enable 0: the first round only)
 };
 
 }   // namespace
@@ -534,7 +535,7 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 	gate_hold_t gate(gpu_gate);
 	double t1 = now_s(); Ln.t[6] += t1 - tg;                     // (the wait at the gate is its own entry, not part of the upload)
 	bmh_seeds_t seeds;
-	RCK(bmh_seed_batch(Ln.sws, A.idx, Ln.d_reads.p, Ln.d_offs.p, Ln.d_lens.p, n, A.co.min_seed_len, Ln.st, &seeds));
+	RCK(bmh_seed_batch_reseed(Ln.sws, A.idx, Ln.d_reads.p, Ln.d_offs.p, Ln.d_lens.p, n, A.co.min_seed_len, &A.rs, Ln.st, &seeds));
 	double t2 = now_s(); Ln.t[1] += t2 - t1;
 	// ---- chains, jobs, extension, regions
 	const uint64_t ns = seeds.n_seeds ? seeds.n_seeds : 1;
@@ -781,6 +782,14 @@ int bmh_aligner_set_max_qlen(bmh_aligner_t *h, uint32_t cap)
 	if (!h) { bmh_set_error("bmh_aligner_set_max_qlen: null aligner"); return BMH_EINVAL; }
 	if (cap > BMH_EXT_LONG_MAX) { bmh_set_error("bmh_aligner_set_max_qlen: %u bases > BMH_EXT_LONG_MAX (%d)", cap, BMH_EXT_LONG_MAX); return BMH_EINVAL; }
 	h->a.max_qlen = cap > 768 ? cap : 768;
+	return BMH_OK;
+}
+
+int bmh_aligner_set_reseed(bmh_aligner_t *h, const bmh_reseed_opt_t *opt)
+{
+	if (!h) { bmh_set_error("bmh_aligner_set_reseed: null aligner"); return BMH_EINVAL; }
+	if (opt) h->a.rs = *opt;
+	else { bmh_reseed_opt_default(&h->a.rs); h->a.rs.enable = 0; }
 	return BMH_OK;
 }
 

@@ -40,21 +40,9 @@
 #include "bmh_internal.h"
 #include "wtrace.h"
 #include "fmd_dev.h"
+#include "seed_dev.h"
 
-// ---------------------------------------------------------------- read access
-
-struct read_view_t {
-	const uint32_t *pk;   // [word][read] 2-bit, base i at bits 2*(i&15)
-	const uint32_t *nm;   // [word32][read] N mask, base i at bit i&31
-	uint32_t n_reads;
-};
-
-__device__ __forceinline__ int read_base(const read_view_t &v, uint32_t r, int i)
-{
-	uint32_t w = v.pk[(size_t)(i >> 4) * v.n_reads + r];
-	uint32_t m = v.nm[(size_t)(i >> 5) * v.n_reads + r];
-	return ((m >> (i & 31)) & 1) ? 4 : (int)((w >> ((i & 15) << 1)) & 3);
-}
+// ---------------------------------------------------------------- read access (read_view_t, read_base: seed_dev.h)
 
 __device__ __forceinline__ int ascii_code(uint8_t ch)
 {
@@ -269,8 +257,6 @@ __global__ void __launch_bounds__(256) smem_forward_kernel(fmd_dev_t f, read_vie
 
 // ---------------------------------------------------------------- backward
 
-struct res_t { uint32_t read, be, s, pad; };   // be = begin<<16 | end; s == 0: dropped
-
 // list order -> (read, ordinal) order: slot cand_base[read] + ordinal receives the list index of its candidate (4 bytes
 // scattered instead of the 24-byte candidate; the backward kernel fetches the candidate through it).  In that order the
 // candidates of one forward pass (same read, same start) sit in adjacent slots, shortest first.
@@ -452,8 +438,7 @@ __global__ void __launch_bounds__(256) smem_filter_kernel(const res_t *__restric
 
 // The scan over the occurrence counts carries the number of kept results in its high bits (one pass instead of a second array and
 // a reduction): element t contributes occ[t] | (occ[t] != 0) << 36; totals stay below 2^32 occurrences (checked) / 2^28 results.
-#define OCC_OFF_SHIFT 36
-#define OCC_OFF_MASK ((1ull << OCC_OFF_SHIFT) - 1ull)
+// (OCC_OFF_SHIFT / OCC_OFF_MASK: seed_dev.h)
 struct occ_keep_in {
 	const uint32_t *occ;
 	__device__ uint64_t operator()(uint64_t t) const { const uint32_t v = occ[t]; return (uint64_t)v | ((uint64_t)(v != 0u) << OCC_OFF_SHIFT); }
@@ -783,6 +768,7 @@ struct bmh_seed_ws {
 	// the seeding kernels run on a stream of the highest priority (ordered behind and before the caller's by two events): their waves wait on HBM most of the
 	// time, and beside another batch's extension -- whose waves fill the register files -- they are the ones that should get the slots that become free
 	hipStream_t st_hi; hipEvent_t ev_in, ev_out;
+	reseed_state_t *rs;                                  // the re-seeding rounds' buffers (bmh_seed_batch_reseed; allocated on first use)
 };
 
 extern "C" bmh_seed_ws_t *bmh_seed_ws_create(uint32_t max_reads, uint64_t max_bases, uint64_t max_cands, uint64_t max_occ)
@@ -851,6 +837,7 @@ extern "C" void bmh_seed_ws_free(bmh_seed_ws_t *w)
 	if (w->st_hi) (void)hipStreamDestroy(w->st_hi);
 	if (w->ev_in) (void)hipEventDestroy(w->ev_in);
 	if (w->ev_out) (void)hipEventDestroy(w->ev_out);
+	reseed_state_free(w->rs);
 	free(w);
 }
 
@@ -889,24 +876,42 @@ static int grow_occ(bmh_seed_ws *w, uint64_t need, bmh_seeds_t *out)
 }
 
 static int seed_batch_on(bmh_seed_ws_t *w, const bmh_index_t *idx, const uint8_t *d_reads, const uint32_t *d_offs,
-                         const uint32_t *d_lens, uint32_t n_reads, int min_seed_len, void *stream_, bmh_seeds_t *out);
+                         const uint32_t *d_lens, uint32_t n_reads, int min_seed_len, void *stream_, bmh_seeds_t *out, const bmh_reseed_opt_t *ro = nullptr);
+static int seed_batch_impl(bmh_seed_ws_t *w, const bmh_index_t *idx, const uint8_t *d_reads, const uint32_t *d_offs,
+                           const uint32_t *d_lens, uint32_t n_reads, int min_seed_len, const bmh_reseed_opt_t *ro, void *stream_, bmh_seeds_t *out);
 extern "C" int bmh_seed_batch(bmh_seed_ws_t *w, const bmh_index_t *idx, const uint8_t *d_reads, const uint32_t *d_offs,
                               const uint32_t *d_lens, uint32_t n_reads, int min_seed_len, void *stream_, bmh_seeds_t *out)
 {
+	return seed_batch_impl(w, idx, d_reads, d_offs, d_lens, n_reads, min_seed_len, nullptr, stream_, out);
+}
+extern "C" void bmh_reseed_opt_default(bmh_reseed_opt_t *o)
+{
+	if (!o) return;
+	o->enable = 0; o->split_factor = 1.5f; o->split_width = 10; o->max_mem_intv = 20;      // mem_opt_init, src/bwamem.c:115-125
+}
+// the second and third seeding rounds run behind the first one's filter (reseed_kernels.hip); off: bmh_seed_batch itself
+extern "C" int bmh_seed_batch_reseed(bmh_seed_ws_t *w, const bmh_index_t *idx, const uint8_t *d_reads, const uint32_t *d_offs,
+                                     const uint32_t *d_lens, uint32_t n_reads, int min_seed_len, const bmh_reseed_opt_t *opt, void *stream_, bmh_seeds_t *out)
+{
+	return seed_batch_impl(w, idx, d_reads, d_offs, d_lens, n_reads, min_seed_len, (opt && opt->enable) ? opt : nullptr, stream_, out);
+}
+static int seed_batch_impl(bmh_seed_ws_t *w, const bmh_index_t *idx, const uint8_t *d_reads, const uint32_t *d_offs,
+                           const uint32_t *d_lens, uint32_t n_reads, int min_seed_len, const bmh_reseed_opt_t *ro, void *stream_, bmh_seeds_t *out)
+{
 	if (!w || !idx || !out) { bmh_set_error("bmh_seed_batch: null argument"); return BMH_EINVAL; }
-	if (!w->st_hi) return seed_batch_on(w, idx, d_reads, d_offs, d_lens, n_reads, min_seed_len, stream_, out);
+	if (!w->st_hi) return seed_batch_on(w, idx, d_reads, d_offs, d_lens, n_reads, min_seed_len, stream_, out, ro);
 	// behind what the caller's stream holds -- the HOST waits for it (the call waits for the stream several times anyway): a barrier packet that waits in the
 	// high-priority queue was measured to cost what the priority gains (34.1 against 35.3 Mreads/s) --, on the workspace's own stream, and the caller's
 	// stream behind it again (whatever the outcome)
 	hipStream_t su = (hipStream_t)stream_;
 	HIPCK(hipStreamSynchronize(su));
-	const int rc = seed_batch_on(w, idx, d_reads, d_offs, d_lens, n_reads, min_seed_len, (void *)w->st_hi, out);
+	const int rc = seed_batch_on(w, idx, d_reads, d_offs, d_lens, n_reads, min_seed_len, (void *)w->st_hi, out, ro);
 	HIPCK(hipEventRecord(w->ev_out, w->st_hi));
 	HIPCK(hipStreamWaitEvent(su, w->ev_out, 0));
 	return rc;
 }
 static int seed_batch_on(bmh_seed_ws_t *w, const bmh_index_t *idx, const uint8_t *d_reads, const uint32_t *d_offs,
-                         const uint32_t *d_lens, uint32_t n_reads, int min_seed_len, void *stream_, bmh_seeds_t *out)
+                         const uint32_t *d_lens, uint32_t n_reads, int min_seed_len, void *stream_, bmh_seeds_t *out, const bmh_reseed_opt_t *ro)
 {
 	memset(out, 0, sizeof(*out));
 	if (n_reads > w->max_reads) { bmh_set_error("bmh_seed_batch: %u reads > workspace capacity %u", n_reads, w->max_reads); return BMH_ECAPACITY; }
@@ -952,7 +957,7 @@ static int seed_batch_on(bmh_seed_ws_t *w, const bmh_index_t *idx, const uint8_t
 	// The fused form moves ~15x fewer bytes between kernels but keeps fewer gathers in flight per CU; on MI355X
 	// both are bound by the random 32-byte gather rate and the split form is currently faster.
 	static const bool use_fused = getenv("BMH_SEED_FUSED") != nullptr;
-	if (use_fused) {
+	if (use_fused && !ro) {          // (re-seeding starts from the split form's filtered results: it always takes that form)
 		// ---- fused pipeline: pack | fused forward+backward | sort SMEMs by (read, end) | scans | expand | locate
 		const uint32_t depth = max_len >= (uint32_t)min_seed_len ? max_len - (uint32_t)min_seed_len + 1 : 1;
 		// persistent grid: as many 256-thread blocks as the chip keeps resident, never more than the reads need
@@ -1121,6 +1126,28 @@ static int seed_batch_on(bmh_seed_ws_t *w, const bmh_index_t *idx, const uint8_t
 	HIPCK(hipStreamSynchronize(st));
 	tot[1] = tot[0] >> OCC_OFF_SHIFT; tot[0] &= OCC_OFF_MASK;
 	if (n_cands >> 28) { bmh_set_error("bmh_seed_batch: more than 2^28 candidates in one batch"); return BMH_ECAPACITY; }
+	if (ro) {
+		// rounds 2 and 3 from the kept SMEMs, merged with them per read by (begin, end); expand and locate as below, on the merged groups
+		reseed_in_t ri = {f, rv, d_lens, n_reads, max_len, min_seed_len, w->res_a, w->res_k, w->occ, w->occ_off, n_cands, tot[1], *ro, w->n_ref_pos, w->prefix};
+		reseed_out_t mo;
+		const int rc = reseed_merge(&w->rs, ri, st, &mo);
+		if (rc != BMH_OK) return rc;
+		out->n_seeds = mo.n_occ; out->n_smems = mo.n;
+		if (grow_occ(w, mo.n_occ, out) != BMH_OK) return BMH_ECAPACITY;
+		if (mo.n_occ >> 32) { bmh_set_error("bmh_seed_batch_reseed: more than 2^32 occurrences in one batch"); return BMH_ECAPACITY; }
+		HIPCK(hipEventRecord(w->ev[4], st));
+		if (mo.n)
+			expand_kernel<<<nblk(mo.n, 256), 256, 0, st>>>(mo.res_a, mo.res_k, mo.occ, mo.occ_off, mo.n, w->rows, w->qbeg, w->score);
+		HIPCK(hipEventRecord(w->ev[5], st));
+		if (mo.n_occ)
+			locate_kernel<<<nblk(nblk(mo.n_occ, LOCATE_PER_WAVE) * 64ull, 256), 256, lds_pad, st>>>(f, w->rows, mo.n_occ);
+		HIPCK(hipEventRecord(w->ev[6], st));
+		HIPCK(hipStreamSynchronize(st));
+		HIPCK(hipGetLastError());
+		for (int i = 0; i < 6; ++i) (void)hipEventElapsedTime(&w->ms[i], w->ev[i], w->ev[i + 1]);
+		(void)hipEventElapsedTime(&w->ms[6], w->ev[0], w->ev[6]);
+		return BMH_OK;
+	}
 	out->n_seeds = tot[0]; out->n_smems = tot[1];
 	if (grow_occ(w, tot[0], out) != BMH_OK) return BMH_ECAPACITY;
 	if (tot[0] >> 32) { bmh_set_error("bmh_seed_batch: more than 2^32 occurrences in one batch"); return BMH_ECAPACITY; }

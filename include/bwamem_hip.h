@@ -161,6 +161,18 @@ int bmh_seed_batch(bmh_seed_ws_t *ws, const bmh_index_t *idx, const uint8_t *d_r
                    const uint32_t *d_offs, const uint32_t *d_lens, uint32_t n_reads,
                    int min_seed_len, void *stream, bmh_seeds_t *out);
 
+/* BWA-MEM's second and third seeding rounds (mem_collect_intv with re_seed, src/bwamem.c:266-297; gase_aln -g).
+ * Round 2 re-seeds from the middle of every SMEM of at least (int)(min_seed_len * split_factor + .499) bases with at most split_width
+ * occurrences (bwt_smem1 with min_intv = occurrences + 1); round 3 (max_mem_intv > 0) scans the read for the shortest seeds of more
+ * than min_seed_len bases with fewer than max_mem_intv occurrences (bwt_seed_strategy1).  The groups of all three rounds are merged
+ * per read by (begin, end), duplicates kept, in the layout of bmh_seeds_t. */
+typedef struct { int enable; float split_factor; int split_width; int max_mem_intv; } bmh_reseed_opt_t;
+void bmh_reseed_opt_default(bmh_reseed_opt_t *o);      /* 0 / 1.5 / 10 / 20, as mem_opt_init (src/bwamem.c:115-125) */
+/* bmh_seed_batch with the re-seeding rounds; opt NULL or opt->enable == 0: exactly bmh_seed_batch. */
+int bmh_seed_batch_reseed(bmh_seed_ws_t *ws, const bmh_index_t *idx, const uint8_t *d_reads,
+                          const uint32_t *d_offs, const uint32_t *d_lens, uint32_t n_reads,
+                          int min_seed_len, const bmh_reseed_opt_t *opt, void *stream, bmh_seeds_t *out);
+
 /* per-kernel time of the last bmh_seed_batch, in ms (HIP events on the launch stream):
  * [0]=pack [1]=forward [2]=scatter+backward [3]=filter+scans [4]=expand [5]=locate [6]=total
  * (with BMH_SEED_FUSED=1: [1]=fused forward+backward [2]=sort of the SMEMs [3]=gather+scans) */
@@ -659,6 +671,8 @@ void bmh_aligner_free(bmh_aligner_t *a);
 /* The extension cap of the aligner's chain workspaces (bmh_chain_ws_set_max_qlen): 768 by default, BMH_EXT_LONG_MAX for reads of any length
  * the aligner takes.  Applies to the runs that follow. */
 int bmh_aligner_set_max_qlen(bmh_aligner_t *a, uint32_t cap);
+/* The seeding rounds of the aligner's lanes (bmh_seed_batch_reseed); NULL = re-seeding off.  Applies to the runs that follow. */
+int bmh_aligner_set_reseed(bmh_aligner_t *a, const bmh_reseed_opt_t *opt);
 /* Batches of the last run whose region tail the device refused (BMH_ECAPACITY: a patch alignment with a query side beyond 1 022 bases, more than
  * 65 535 near-equal regions; pairs: a read beyond the pairing kernels' limits): the host forms took them, same text. */
 uint64_t bmh_aligner_host_tail_batches(const bmh_aligner_t *a);
