@@ -8,5 +8,6 @@ the hot path in here: if the shared library or a HIP device is missing, calls
 raise.
 """
 from . import fmindex, synth  # noqa: F401
+from .index import fasta_pack, index_fasta  # noqa: F401
 from .lib import (ExtParams, HipLibraryMissing, Index, SeedWorkspace, extend_batch, lib_path,  # noqa: F401
                   load_library, seed_file)

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "bmh_reads_load_fasta", "bmh_reads_free", "bmh_fasta_scan",
     "bmh_reads_load", "bmh_reads_scan", "bmh_format_sam_ex", "bmh_format_sam_pe_ex", "bmh_aligner_run_file",
     "bmh_chain_ws_set_max_qlen", "bmh_aligner_set_max_qlen", "bmh_aligner_host_tail_batches",
+    "bmh_index_fasta", "bmh_fasta_pack", "bmh_fasta_packed_free",
 ]
 
 

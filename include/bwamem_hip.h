@@ -124,6 +124,33 @@ typedef struct {
 int bmh_index_build(const uint8_t *d_pac, uint64_t l_pac, int sa_intv, uint32_t *d_bwt_words, uint32_t *d_sa, uint32_t *d_sa_bits,
                     uint64_t *primary_out, uint64_t L2_out[5], int flags, bmh_build_stats_t *stats);
 
+/* `bwa index` on the device (csrc/fasta_pack.hip): a FASTA file, plain or gzip (by its magic bytes; zlib is loaded with
+ * dlopen("libz.so.1")), in; prefix.{bwt,sa,pac,ann,amb} out, byte for byte what the reference's two-pass build writes
+ * (bwa_index/bntseq.c bns_fasta2bntseq over kseq_read, then bmh_index_build).  The file is streamed in chunks of chunk_bytes
+ * (0: 256 MiB; 64 .. 2^31) through pinned double buffers and packed into the 2-bit forward strand on the device; the
+ * packer's buffers (about 66 bytes of HBM per chunk byte) are freed before the builder runs.  sa_intv: a power of two (the
+ * builder's; `bwa index -r` takes any value).  flags: BMH_BUILD_VERIFY.  Refused with BMH_EINVAL and nothing written under
+ * the final names: a file with no record, with only empty records, with a line that starts with '+' (FASTQ), or with a
+ * sequence byte 0 or >= 128; an unreadable file; a .gz without zlib.  More than 2^32 - 1 bases: BMH_ECAPACITY.  The files
+ * are written under temporary names and renamed at the end.  stats (optional) reports what happened. */
+typedef struct {
+	uint64_t n_contigs, n_holes, l_pac, n_ambig, file_bytes;
+	double read_seconds;     /* reading / inflating the file (the part not hidden behind the device's work) */
+	double h2d_seconds, pack_seconds, build_seconds, write_seconds, total_seconds;
+	int verified;
+} bmh_index_fasta_stats_t;
+int bmh_index_fasta(const char *fa_path, const char *prefix, int sa_intv, int flags, size_t chunk_bytes, bmh_index_fasta_stats_t *stats);
+/* The packing step alone: d_pac (device, pac_bytes >= (l_pac+3)/4 + 64, zero beyond the text) and the host tables of the
+ * .ann / .amb -- per contig its name and comment (NUL-terminated at name_off / comment_off; an empty comment is written
+ * "(null)"), offset, length and holes; per hole its offset, length and byte.  Free with bmh_fasta_packed_free. */
+typedef struct {
+	uint8_t *d_pac; uint64_t pac_bytes, l_pac, n_ambig;
+	int32_t n_contigs; char *names, *comments; uint64_t *name_off, *comment_off; int64_t *offsets, *lens; int32_t *n_ambs;
+	int64_t n_holes; int64_t *hole_off, *hole_len; uint8_t *hole_char;
+} bmh_fasta_packed_t;
+int bmh_fasta_pack(const char *fa_path, size_t chunk_bytes, bmh_fasta_packed_t *out, bmh_index_fasta_stats_t *stats);
+void bmh_fasta_packed_free(bmh_fasta_packed_t *p);
+
 /* ---------------------------------------------------------------- seeding */
 
 /* Workspace for batches of up to max_reads reads / max_bases bases.
