@@ -136,6 +136,26 @@ def read_reads(path: str, comments: bool = False) -> ReadSet:
     return ReadSet(d["ascii"], d["offs"], d["lens"], d["names"], d["name_offs"], codes=d["codes"], qual=d["quals"], comments=cm)
 
 
+def read_reads_files(path1: str, path2: str | None = None, comments: bool = False, host: bool = False) -> ReadSet:
+    """one or two read files of any shape the reference takes (bmh_reads_load_files): FASTA or FASTQ with records over any number of lines, plain, gzip or
+    BGZF, regular files or pipes; path2: the mates (read i of each file -> reads 2i, 2i+1).  The records are cut on the device; host=True: by the host
+    walker alone (no device needed).  A refused file raises ValueError (lib.ReadFileError); when one file ends before the other, its `partial` attribute
+    is the ReadSet of the complete pairs."""
+    from .lib import ReadFileError, load_reads_files
+
+    def wrap(d):
+        if len(d["lens"]) == 0:
+            return ReadSet.from_lists([], [], comments=[] if comments else None)
+        cm = (d["comments"], d["comment_offs"]) if d["comments"] is not None else None
+        return ReadSet(d["ascii"], d["offs"], d["lens"], d["names"], d["name_offs"], codes=d["codes"], qual=d["quals"], comments=cm)
+    try:
+        return wrap(load_reads_files(path1, path2, comments=comments, host=host))
+    except ReadFileError as e:
+        if getattr(e, "partial", None) is not None:
+            e.partial = wrap(e.partial)
+        raise
+
+
 def read_fasta_reads_numpy(path: str) -> ReadSet:
     """the same parse with numpy array operations (what read_fasta_reads was before the library had a loader; kept as its cross-check)"""
     buf = np.fromfile(path, dtype=np.uint8)
@@ -560,6 +580,32 @@ class Aligner:
             if e > b:
                 out.write(self.align_batch(rs.slice(b, e), id0=b, paired=paired, as_bytes="view" if binary else False))   # (binary: the library's buffer, uncopied)
         return n
+
+    def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0) -> int:
+        """align_file for the files users have (bmh_aligner_run_files): `reads` (and `mates`: the second file of a pair, which implies paired) may be
+        multi-line FASTA or FASTQ, plain, gzip or BGZF, a regular file or a pipe.  Batches are cut by align_file's rules (-t, -K, the 150 Mbase floor for
+        single-end runs), so the text equals align_file's on the single-line interleaved file of the same reads.  Returns the number of reads."""
+        if out is None:
+            raise ValueError("align_files: out (a text or binary file object) is required")
+        binary = "b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")
+        paired = bool(paired or mates is not None)
+        cb = 0
+        if batch_reads <= 0:
+            cb = chunk_bases or int(getattr(self, "ref_chunk_bases", 0)) or 10_000_000 * max(1, int(getattr(self, "ref_threads", 1)))
+            if not paired and not chunk_bases:
+                cb = max(cb, 150_000_000)                 # (single-end records do not depend on the cuts: align_file)
+            cb = min(cb, (1 << 31) - 1024)
+        out.write(self.header().encode() if binary else self.header())
+        nat = self._native_aligner()
+        try:
+            self.last_stats = nat.run_files(reads, mates, paired, (lambda mv: out.write(mv)) if binary else (lambda mv: out.write(bytes(mv).decode())),
+                                             batch_bases=cb, batch_reads=max(batch_reads, 0),
+                                             n_lanes=int(os.environ.get("BMH_ALIGNER_LANES", "3" if paired else "2")), n_threads=self.n_threads)
+        except RuntimeError as e:
+            _raise_beyond_cap(e)
+            raise
+        self.host_tail_batches = nat.host_tail_batches()
+        return int(self.last_stats.n_reads)
 
     # The seeding and chaining workspaces are kept between batches (allocating and freeing a few GB of HBM per batch cost more than
     # the kernels of an easy batch); a batch that needs more gets a new one, a quarter larger than it asked for.

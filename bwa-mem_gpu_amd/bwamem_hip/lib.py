@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "bmh_reads_load", "bmh_reads_scan", "bmh_format_sam_ex", "bmh_format_sam_pe_ex", "bmh_aligner_run_file",
     "bmh_chain_ws_set_max_qlen", "bmh_aligner_set_max_qlen", "bmh_aligner_host_tail_batches",
     "bmh_index_fasta", "bmh_fasta_pack", "bmh_fasta_packed_free",
+    "bmh_reads_load_files", "bmh_aligner_run_files",
 ]
 
 
@@ -145,6 +146,53 @@ def load_reads(path: str, comments: bool = False, n_threads: int = 0) -> dict:
                 quals=arr(rs.quals, rs.n_bases, np.uint8) if rs.quals else None,
                 comments=arr(rs.comments, rs.n_comment_bytes, np.uint8) if rs.comments else None,
                 comment_offs=arr(rs.comment_offs, rs.n_reads, np.uint64) if rs.comments else None)
+
+
+READS_HOST = 2              # BMH_READS_HOST
+
+
+def reads_last_counts() -> dict:
+    """bmh_reads_last_counts: how the last load_reads_files / run_files call of the process cut its text -- windows on the device, windows the host walked
+    (the fallback), text bytes, records"""
+    L = load_library()
+    L.bmh_reads_last_counts.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    L.bmh_reads_last_counts(out)
+    return dict(device_windows=int(out[0]), host_windows=int(out[1]), text_bytes=int(out[2]), records=int(out[3]))
+
+
+def load_reads_files(path1: str, path2: str | None = None, comments: bool = False, host: bool = False, n_threads: int = 0) -> dict:
+    """bmh_reads_load_files: one or two read files of any shape (multi-line records, gzip / BGZF, pipes) as load_reads gives them; path2: the mates (reads 2i
+    and 2i+1).  host=True: the host walker alone (no device).  A refused file raises ReadFileError; when one file ends before the other its `partial`
+    attribute holds the complete pairs before the end."""
+    L = load_library()
+    rs = ReadSetT()
+    L.bmh_reads_load_files.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(ReadSetT)]
+    L.bmh_reads_free.argtypes = [C.POINTER(ReadSetT)]
+    rc = L.bmh_reads_load_files(os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, n_threads,
+                                (READS_COMMENTS if comments else 0) | (READS_HOST if host else 0), C.byref(rs))
+    msg = _err(L) if rc != 0 else ""
+    if rc != 0 and not rs.ascii:
+        raise ReadFileError(msg) if msg.startswith(("FASTQ:", "reads file", "reads files")) else RuntimeError("bmh_reads_load_files: " + msg)
+    owner = _ReadSetOwner(L, rs)
+
+    def arr(ptr, n, dt):
+        n = int(n)
+        if n == 0 or not ptr:
+            return np.zeros(0, dt)
+        buf = (C.c_uint8 * (n * np.dtype(dt).itemsize)).from_address(ptr)
+        buf._owner = owner
+        return np.frombuffer(buf, dtype=dt)
+    d = dict(ascii=arr(rs.ascii, rs.n_bases, np.uint8), codes=arr(rs.codes, rs.n_bases, np.uint8), offs=arr(rs.offs, rs.n_reads, np.uint64),
+             lens=arr(rs.lens, rs.n_reads, np.uint32), names=arr(rs.names, rs.n_name_bytes, np.uint8), name_offs=arr(rs.name_offs, rs.n_reads, np.uint64),
+             quals=arr(rs.quals, rs.n_bases, np.uint8) if rs.quals else None,
+             comments=arr(rs.comments, rs.n_comment_bytes, np.uint8) if rs.comments else None,
+             comment_offs=arr(rs.comment_offs, rs.n_reads, np.uint64) if rs.comments else None)
+    if rc != 0:
+        e = ReadFileError(msg)
+        e.partial = d
+        raise e
+    return d
 
 
 class AlignStats(C.Structure):
@@ -280,6 +328,33 @@ class NativeAligner:
             if "FASTQ:" in msg or "reads file:" in msg:
                 raise ReadFileError(msg)
             raise (CapacityError if rc == -3 else RuntimeError)(f"bmh_aligner_run_file rc={rc}: " + msg)
+        return st
+
+    def run_files(self, path1: str, path2: str | None, paired: bool, write, batch_bases: int = 0, batch_reads: int = 0, n_lanes: int = 2, n_threads: int = 0) -> "AlignStats":
+        """bmh_aligner_run_files: run_file for one or two read files of any shape (multi-line records, gzip / BGZF, pipes; path2: the mates)"""
+        L = load_library()
+        L.bmh_aligner_run_files.restype = C.c_int
+        L.bmh_aligner_run_files.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, SAM_SINK, C.c_void_p, C.POINTER(AlignStats)]
+        err = []
+
+        def sink(_user, ptr, n):
+            try:
+                write(memoryview((C.c_char * n).from_address(ptr)))
+                return 0
+            except BaseException as e:                      # noqa: BLE001 -- reported after the run (an exception must not cross the C frames)
+                err.append(e)
+                return 1
+        cb = SAM_SINK(sink)
+        st = AlignStats()
+        rc = L.bmh_aligner_run_files(self.handle, os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, int(batch_bases), int(batch_reads),
+                                     1 if paired else 0, int(n_lanes), int(n_threads), cb, None, C.byref(st))
+        if err:
+            raise err[0]
+        if rc != 0:
+            msg = _err(L)
+            if "FASTQ:" in msg or "reads file" in msg:
+                raise ReadFileError(msg)
+            raise (CapacityError if rc == -3 else RuntimeError)(f"bmh_aligner_run_files rc={rc}: " + msg)
         return st
 
     def free(self):

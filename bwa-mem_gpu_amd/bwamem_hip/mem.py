@@ -1,0 +1,102 @@
+"""`bwa mem` on the device: reads (FASTA or FASTQ, multi-line or not, plain, gzip or BGZF, one file or an R1 / R2 pair) -> SAM.
+
+    python -m bwamem_hip.mem [options] PREFIX reads [mates] [-o out.sam]
+
+PREFIX is what `python -m bwamem_hip.index` (or `bwa index`) wrote.  Options are Aligner.set_options' list (-k -w -c -D -G -N -W -X -A -B
+-O -E -T -h -Q -U -m -R -a -M -Y -S -P -j -C -g -t -K ...) plus -p (the one file holds interleaved pairs), -o (the output file; default
+stdout), --long-reads (reads of up to 16 384 bases) and --device (the torch device, cuda:0).  An option that is not on that list is
+refused by name.  Two input files imply pairs.  One plain, regular file is offered to Aligner.align_file first, which takes it when every
+record has one sequence line (its own counting pass decides, before anything is written); every other input goes through
+Aligner.align_files; the text is the same.  A refused file ends the command with status 1 and the library's message on stderr.
+"""
+from __future__ import annotations
+
+import os
+import stat
+import sys
+
+FLAGS = ("-a", "-M", "-Y", "-S", "-P", "-j", "-C", "-g")
+VALUED = ("-k", "-w", "-c", "-D", "-G", "-N", "-W", "-X", "-A", "-B", "-O", "-E", "-T", "-h", "-Q", "-U", "-m", "-R", "-t", "-K", "-l", "-v", "-f", "-d", "-L")
+
+
+def _plain_regular(path: str) -> bool:
+    """a regular, uncompressed file: what align_file's mapped loader can take (whether its records are single-line is align_file's to say)"""
+    try:
+        if not stat.S_ISREG(os.stat(path).st_mode):
+            return False
+        with open(path, "rb") as f:
+            return f.read(2) != b"\x1f\x8b"
+    except OSError:
+        return False
+
+
+def main(argv=None) -> int:
+    argv = list(sys.argv[1:] if argv is None else argv)
+    opts, pos, out_path, interleaved, long_reads, device = [], [], None, False, False, "cuda:0"
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a == "-p":
+            interleaved = True
+        elif a == "--long-reads":
+            long_reads = True
+        elif a in ("-o", "--device"):
+            if i + 1 >= len(argv):
+                print(f"[bwamem_hip.mem] option {a} needs a value", file=sys.stderr)
+                return 2
+            if a == "-o":
+                out_path = argv[i + 1]
+            else:
+                device = argv[i + 1]
+            i += 1
+        elif a in FLAGS:
+            opts.append(a)
+        elif a.startswith("-") and len(a) > 1:
+            if a not in VALUED:
+                print(f"[bwamem_hip.mem] option {a} is not taken", file=sys.stderr)
+                return 2
+            if i + 1 >= len(argv):
+                print(f"[bwamem_hip.mem] option {a} needs a value", file=sys.stderr)
+                return 2
+            opts += [a, argv[i + 1]]
+            i += 1
+        else:
+            pos.append(a)
+        i += 1
+    if len(pos) not in (2, 3):
+        print(__doc__, file=sys.stderr)
+        return 2
+    prefix, reads, mates = pos[0], pos[1], pos[2] if len(pos) == 3 else None
+    from .aligner import Aligner
+    try:
+        al = Aligner(prefix, device=device, long_reads=long_reads)
+        al.set_options(opts)
+    except (OSError, ValueError) as e:
+        print(f"[bwamem_hip.mem] {e}", file=sys.stderr)
+        return 1
+    out = open(out_path, "wb") if out_path is not None else sys.stdout.buffer
+    try:
+        paired = interleaved or mates is not None
+        done = False
+        if mates is None and _plain_regular(reads):
+            from .lib import ReadFileError
+            try:
+                al.align_file(reads, out, paired=paired)
+                done = True
+            except ReadFileError:                                    # (its counting pass refused the layout: nothing has been written)
+                pass
+        if not done:
+            al.align_files(reads, mates, out=out, paired=paired)
+        out.flush()
+    except (ValueError, NotImplementedError) as e:
+        print(f"[bwamem_hip.mem] {e}", file=sys.stderr)
+        return 1
+    finally:
+        if out_path is not None:
+            out.close()
+        al.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1127,6 +1127,98 @@ static int run_file(bmh_aligner_t *h, const char *path, uint64_t batch_bases, ui
 
 }
 
+// ---- the same from one or two read files of any shape (multi-line, gzip / BGZF, R1 + R2): the loader thread drives the pump of csrc/reads_parse.hip -- text
+// windows in pinned memory, records cut on the device (or walked by the host where the device hands a window back) -- and every batch lands in an fbatch_t
+// as run_file's batches do, so the lanes take them exactly as they take those
+int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
+                          bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats)
+{
+	const char *fn = "bmh_aligner_run_files";
+	if (!h || !path1 || !sink) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (stats) memset(stats, 0, sizeof(*stats));
+	if (batch_bases == 0 && batch_reads == 0) { bmh_set_error("%s: batch_bases or batch_reads must be given", fn); return BMH_EINVAL; }
+	if (batch_bases >= (1ull << 31) - 4096) batch_bases = (1ull << 31) - 4096;      // offsets inside a batch are 32-bit
+	if (path2) paired = 1;
+	if (paired && (batch_reads & 1)) --batch_reads;
+	if (n_lanes < 1) n_lanes = 1;
+	if (n_threads < 1) n_threads = bmh_effective_cpus();
+	int dev = 0;
+	if (hipGetDevice(&dev) != hipSuccess) { bmh_set_error("%s: no HIP device", fn); return BMH_ENODEV; }
+	const bool cm = h->a.po.copy_comment != 0;
+	bmh_reads_pump_t *P = bmh_pump_open(path1, path2, n_threads, cm, false, 0);
+	if (!P) return BMH_EINVAL;
+	std::mutex qm; std::condition_variable qcv;
+	std::vector<std::unique_ptr<fbatch_t>> &all = h->fbatches; std::vector<fbatch_t *> free_list; std::map<uint32_t, fbatch_t *> ready;
+	for (auto &fb : all) free_list.push_back(fb.get());
+	uint32_t next_out = 0; bool eof = false, stopped = false; int load_rc = BMH_OK; std::string load_err;
+	int outstanding = 0;                                  // batches handed to the lanes whose text has not been written yet
+	const int max_batches = n_lanes + 3;
+	auto loader = [&]() {
+		if (hipSetDevice(dev) != hipSuccess) { std::lock_guard<std::mutex> lk(qm); load_rc = BMH_ENODEV; load_err = "hipSetDevice failed in the loader thread"; eof = true; qcv.notify_all(); return; }
+		uint32_t index = 0; int64_t id0 = 0;
+		for (;;) {
+			fbatch_t *fb = nullptr;
+			{
+				std::unique_lock<std::mutex> lk(qm);
+				qcv.wait(lk, [&] { return stopped || !free_list.empty() || (int)all.size() < max_batches; });
+				if (stopped) break;
+				if (!free_list.empty()) { fb = free_list.back(); free_list.pop_back(); }
+				else { all.emplace_back(new fbatch_t()); fb = all.back().get(); }
+			}
+			bmh_batch_alloc_t alloc = [&](uint64_t nr, uint64_t nb, uint64_t nn, uint64_t ncm, bool fq, bmh_read_set_t *rs) {
+				if (nb >> 31) { bmh_set_error("%s: a batch holds 2^31 bases or more", fn); return (int)BMH_EINVAL; }
+				if (fb->ascii.need(nb + 16) != BMH_OK || fb->codes.need(nb + 16) != BMH_OK || fb->names.need(nn + 16) != BMH_OK || fb->offs.need(nr + 2) != BMH_OK ||
+				    fb->name_offs.need(nr + 2) != BMH_OK || fb->lens.need(nr + 2) != BMH_OK) return (int)BMH_ENOMEM;
+				if (fq && fb->quals.need(nb + 16) != BMH_OK) return (int)BMH_ENOMEM;
+				if (cm && (fb->comments.need(ncm + 16) != BMH_OK || fb->comment_offs.need(nr + 2) != BMH_OK)) return (int)BMH_ENOMEM;
+				rs->ascii = fb->ascii.p; rs->codes = fb->codes.p; rs->names = fb->names.p; rs->offs = fb->offs.p; rs->name_offs = fb->name_offs.p; rs->lens = fb->lens.p;
+				if (fq) rs->quals = fb->quals.p;
+				if (cm) { rs->comments = fb->comments.p; rs->comment_offs = fb->comment_offs.p; }
+				return (int)BMH_OK;
+			};
+			int rc = bmh_pump_next(P, batch_bases, batch_reads, /* even counts, as bseq_read ends its batches */ batch_reads == 0, false, alloc, &fb->rs);
+			const uint64_t nr = rc == 1 ? fb->rs.n_reads : 0;
+			if (rc == 1 && paired && (nr & 1)) { bmh_set_error("%s: an odd number of reads in a paired file", fn); rc = BMH_EINVAL; }
+			if (rc == 1) for (uint64_t r = 0; r < nr; ++r) if (fb->lens.p[r] > BMH_EXT_LONG_MAX) { bmh_set_error("%s: read %lld has %u bases: the longest read the aligner takes has %d (BMH_EXT_LONG_MAX)", fn, (long long)(id0 + (int64_t)r), fb->lens.p[r], BMH_EXT_LONG_MAX); rc = BMH_EINVAL; break; }
+			std::lock_guard<std::mutex> lk(qm);
+			if (rc < 0) { load_rc = rc; load_err = bmh_last_error(); free_list.push_back(fb); break; }
+			if (rc == 0) { free_list.push_back(fb); break; }
+			fb->index = index++; fb->id0 = id0; id0 += (int64_t)nr;
+			ready[fb->index] = fb;
+			qcv.notify_all();
+		}
+		std::lock_guard<std::mutex> lk(qm);
+		eof = true;
+		qcv.notify_all();
+	};
+	batch_src_t src;
+	src.next = [&](batch_t &bt) {
+		std::unique_lock<std::mutex> lk(qm);
+		qcv.wait(lk, [&] { return stopped || ready.count(next_out) || eof; });
+		if (stopped) return 0;
+		if (!ready.count(next_out)) {
+			if (load_rc == BMH_OK) return 0;
+			// a refused file fails the run only when the batches before the refusal have been written (a file that ends before its mate file: the complete pairs first)
+			qcv.wait(lk, [&] { return stopped || outstanding == 0; });
+			if (stopped) return 0;
+			bmh_set_error("%s", load_err.c_str()); return load_rc;
+		}
+		fbatch_t *fb = ready[next_out]; ready.erase(next_out); ++next_out;
+		bt.index = fb->index; bt.rs = &fb->rs; bt.b0 = 0; bt.b1 = (uint32_t)fb->rs.n_reads; bt.id0 = fb->id0; bt.pinned = true; bt.token = fb;
+		++outstanding;
+		return 1;
+	};
+	src.release = [&](void *tok) { if (!tok) return; std::lock_guard<std::mutex> lk(qm); free_list.push_back((fbatch_t *)tok); --outstanding; qcv.notify_all(); };
+	src.stop = [&]() { std::lock_guard<std::mutex> lk(qm); stopped = true; qcv.notify_all(); };
+	std::thread lt(loader);
+	const int rc = run_core(h, src, fn, paired, n_lanes, n_threads, sink, user, stats);
+	src.stop();
+	lt.join();
+	uint64_t cnt[4]; bmh_pump_counts(P, cnt); bmh_reads_note_counts(cnt);
+	bmh_pump_close(P);
+	return rc;
+}
+
 int bmh_aligner_run_fasta(bmh_aligner_t *h, const char *path, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
                           bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats)
 {

@@ -28,6 +28,7 @@ int bmh_extend_batch_desc(const bmh_ext_desc_t *desc, const uint32_t *d_qlen, co
 int bmh_extend_reserve(void *stream, uint64_t n);
 
 #ifdef __cplusplus
+#include <functional>
 #include <string>
 #include <vector>
 // where the formatter finds a record's alignment: slot (64- or 32-bit, -1 = none) -> aln[8], and the operations / MD string either in the
@@ -73,6 +74,34 @@ int bmh_fasta_cut(const uint8_t *buf, size_t sz, size_t p, uint64_t want_bases, 
                   uint64_t *n_comment_bytes = nullptr);
 int bmh_fasta_fill(const uint8_t *buf, size_t p, size_t end, uint64_t n_reads, uint64_t n_bases, uint64_t n_name_bytes, int n_threads, bmh_read_set_t *o,
                    const bmh_reads_fmt_t &fmt = bmh_reads_fmt_t(), uint64_t n_comment_bytes = 0);
+// ---- read files of any shape (bmh_reads_load_files, bmh_aligner_run_files): multi-line records, gzip / BGZF, two files
+// csrc/reads_src.cpp: the text of a plain, gzip or BGZF file (or pipe) in order; n_threads: host threads of the BGZF inflate (<= 0: bmh_effective_cpus)
+struct bmh_text_src_t;
+bmh_text_src_t *bmh_text_open(const char *path, int n_threads);          // NULL: the message is set
+int64_t bmh_text_read(bmh_text_src_t *s, uint8_t *dst, size_t n);         // bytes written: fewer than n at the end of the text only; -1: error (message set)
+int bmh_text_kind(const bmh_text_src_t *s);                              // 0 plain, 1 gzip, 2 BGZF
+void bmh_text_close(bmh_text_src_t *s);
+// csrc/reads_io.cpp: the host walker (kseq_read restated) appends a record to growing arrays; nlen / clen: bytes of its name / comment with their NUL
+struct bmh_hbatch_t {
+	std::vector<uint8_t> ascii, quals, names, comments; std::vector<uint32_t> lens, nlen, clen;
+	void clear() { ascii.clear(); quals.clear(); names.clear(); comments.clear(); lens.clear(); nlen.clear(); clen.clear(); }
+};
+int bmh_walk_record(const uint8_t *b, size_t n, bool eof, size_t *p, bmh_hbatch_t &o, bool comments, int *kind);
+void bmh_nt4_codes(const uint8_t *src, uint8_t *dst, size_t n);
+// csrc/reads_parse.hip: one or two read files batch by batch -- text windows in (pinned) host memory, cut into records by the device parser or, for what it
+// hands back (and with host_only), by the host walker.  next: 1 = a batch in the arrays `alloc` provided (it is told the sizes and sets rs's pointers; offsets
+// start at 0), 0 = the end, < 0 = refused.  The batch ends as bseq_read ends its batches (bases >= want_bases -- or reads == want_reads if not 0 -- and an
+// even count when `even`; pairs stay together with two files); take_all: every complete record of the window instead.
+struct bmh_reads_pump_t;
+typedef std::function<int(uint64_t n_reads, uint64_t n_bases, uint64_t n_name_bytes, uint64_t n_comment_bytes, bool fq, bmh_read_set_t *rs)> bmh_batch_alloc_t;
+bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_threads, bool comments, bool host_only, size_t chunk_bytes);
+int bmh_pump_next(bmh_reads_pump_t *p, uint64_t want_bases, uint64_t want_reads, bool even, bool take_all, const bmh_batch_alloc_t &alloc, bmh_read_set_t *rs);
+void bmh_pump_counts(const bmh_reads_pump_t *p, uint64_t out[4]);        // windows parsed on the device, windows walked on the host, text bytes, records
+void bmh_pump_close(bmh_reads_pump_t *p);
+// for the tests and scripts/reads_input_rate.py, not part of the public interface: out[4] of the process's last bmh_reads_load_files / bmh_aligner_run_files call --
+// windows cut on the device, windows walked by the host, text bytes, records
+void bmh_reads_note_counts(const uint64_t *c);
+extern "C" int bmh_reads_last_counts(uint64_t *out);
 // ---- interleaved pairs with mem_pair / mem_sam_pe's choices on the device (csrc/pair_dev.hip) for the pairs the mate rescue does not touch
 // The host call (csrc/pair_post.cpp: bmh_finalize_pairs_split = bmh_finalize_pairs_deduped on a subset) tells the caller the insert-size statistics as
 // soon as it has them (after_pestat: the caller starts the device's pair kernel), asks before its own final walk which pairs the device handed back

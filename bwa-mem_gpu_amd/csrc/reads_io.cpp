@@ -489,3 +489,81 @@ static int scan_reads(const char *fn, const char *path, int n_threads, bool fq_o
 
 extern "C" int bmh_fasta_scan(const char *path, int n_threads, uint64_t *out) { return scan_reads("bmh_fasta_scan", path, n_threads, false, out); }
 extern "C" int bmh_reads_scan(const char *path, int n_threads, uint64_t *out) { return scan_reads("bmh_reads_scan", path, n_threads, true, out); }
+
+// ---- the host walker of bmh_reads_load_files / bmh_aligner_run_files: kseq_read (src/kseq.h:175-215) restated over a window of the text.  A record starts at
+// the next '>' or '@' byte; its name runs to the first isspace byte, the comment is the rest of that line (a trailing CR dropped when the comment is longer
+// than it); the sequence is every following line until one that starts with '>', '@' or '+' (empty lines skipped; a trailing CR dropped unless it is the
+// record's first sequence byte or a one-byte last line of the file); behind a '+' line the qualities are lines until their total length reaches the
+// sequence's.  It is what the device parser (csrc/reads_parse.hip) must equal, its fallback, and the form that runs without a device.  Where kseq_read
+// gives up silently (-2: bseq_read ends the run there) this refuses with a message, and so for an empty sequence and for FASTA and FASTQ records in one file.
+void bmh_nt4_codes(const uint8_t *src, uint8_t *dst, size_t n) { for (size_t i = 0; i < n; ++i) dst[i] = NT4.v[src[i]]; }
+
+static inline bool c_isspace(uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
+
+// One record from b[*p, n) appended to o.  1: done, *p behind it; 0: none -- *p = n when the window ends the file (eof), else *p is where the unfinished
+// record starts (more text is needed); < 0: refused (message set).  *kind: 0 at first, then 1 (FASTA) or 2 (FASTQ): what the file's records are
+int bmh_walk_record(const uint8_t *b, size_t n, bool eof, size_t *pp, bmh_hbatch_t &o, bool comments, int *kind)
+{
+	size_t p = *pp;
+	while (p < n && b[p] != '>' && b[p] != '@') ++p;
+	*pp = p;
+	if (p >= n) return 0;
+	const size_t a0 = o.ascii.size(), q0 = o.quals.size(), n0 = o.names.size(), c0 = o.comments.size();
+	auto more = [&]() { o.ascii.resize(a0); o.quals.resize(q0); o.names.resize(n0); o.comments.resize(c0); return 0; };
+	auto line_end = [&](size_t q) { const uint8_t *x = q < n ? (const uint8_t *)memchr(b + q, '\n', n - q) : nullptr; return x ? (size_t)(x - b) : n; };
+	size_t q = p + 1;
+	while (q < n && !c_isspace(b[q])) ++q;
+	if (q >= n) {
+		if (!eof) return more();
+		if (q == p + 1) { *pp = n; return 0; }                  // (a header byte that ends the file makes no record)
+	}
+	size_t nl_ = q - (p + 1);
+	size_t cb = q, cl = 0;
+	if (q < n && b[q] != '\n') {
+		const size_t le = line_end(q + 1);
+		if (le >= n && !eof) return more();
+		cb = q + 1; cl = le - cb;
+		if (cl > 1 && b[cb + cl - 1] == '\r') --cl;
+		q = le < n ? le + 1 : n;
+	} else if (q < n) ++q;
+	int c = -1;
+	for (;;) {
+		if (q >= n) { if (!eof) return more(); c = -1; break; }
+		c = b[q];
+		if (c == '>' || c == '@' || c == '+') break;
+		if (c == '\n') { ++q; continue; }
+		const size_t le = line_end(q);
+		if (le >= n && !eof) return more();
+		o.ascii.insert(o.ascii.end(), b + q, b + le);
+		const bool lone_last = le >= n && le - q == 1;           // (kseq: the rest of the line is empty and the file ends -- nothing is trimmed)
+		if (!lone_last && o.ascii.size() - a0 > 1 && o.ascii.back() == '\r') o.ascii.pop_back();
+		q = le < n ? le + 1 : n;
+	}
+	const size_t L = o.ascii.size() - a0;
+	const int k = c == '+' ? 2 : 1;
+	if (c == '+') {
+		size_t le = line_end(q);
+		if (le >= n) { if (!eof) return more(); bmh_set_error("%s", bad_msg(5)); return BMH_EINVAL; }
+		q = le + 1;
+		bool ended = false;
+		do {
+			if (q >= n) { if (!eof) return more(); ended = true; break; }
+			le = line_end(q);
+			if (le >= n && !eof) return more();
+			o.quals.insert(o.quals.end(), b + q, b + le);
+			if (o.quals.size() - q0 > 1 && o.quals.back() == '\r') o.quals.pop_back();
+			q = le < n ? le + 1 : n;
+		} while (o.quals.size() - q0 < L);
+		if (o.quals.size() - q0 != L) { bmh_set_error("%s", bad_msg(ended ? 5 : 3)); return BMH_EINVAL; }
+	}
+	if (*kind && *kind != k) { bmh_set_error("%s", bad_msg(7)); return BMH_EINVAL; }
+	*kind = k;
+	if (L == 0) { bmh_set_error("%s", k == 2 ? bad_msg(8) : "reads file: a record with an empty sequence"); return BMH_EINVAL; }
+	if (L > 0x7fffffffu) { bmh_set_error("%s", bad_msg(2)); return BMH_EINVAL; }
+	if (nl_ > 2 && b[p + nl_ - 1] == '/' && b[p + nl_] >= '0' && b[p + nl_] <= '9') nl_ -= 2;         // trim_readno (src/bwa.c:27-31)
+	o.names.insert(o.names.end(), b + p + 1, b + p + 1 + nl_); o.names.push_back(0);
+	if (comments) { o.comments.insert(o.comments.end(), b + cb, b + cb + cl); o.comments.push_back(0); o.clen.push_back((uint32_t)cl + 1); }
+	o.lens.push_back((uint32_t)L); o.nlen.push_back((uint32_t)nl_ + 1);
+	*pp = q;
+	return 1;
+}

@@ -457,6 +457,18 @@ typedef struct {
 int bmh_reads_load_fasta(const char *path, int n_threads, bmh_read_set_t *out);
 int bmh_reads_load(const char *path, int n_threads, int flags, bmh_read_set_t *out);
 void bmh_reads_free(bmh_read_set_t *r);
+/* One or two read files of any shape the reference takes (kseq_read / bseq_read, src/kseq.h:175-215, src/bwa.c:42-75): FASTA with sequences over any number
+ * of lines, FASTQ (four-line, or with sequence and qualities over several lines), CR LF line ends, empty lines; plain, gzip (by the magic bytes; concatenated
+ * members are one stream) or BGZF (inflated on n_threads host threads); regular files, pipes, process substitutions.  zlib is loaded at run time
+ * (libz.so.1); without it a gzip file is refused with a message.  path2 (or NULL): the mates -- read i of path1 and read i of path2 become reads 2i and
+ * 2i+1, both names without a trailing "/<digit>"; the two files hold the same kind of records.  The records are cut on the device (csrc/reads_parse.hip);
+ * text it cannot decide (multi-line FASTQ, stray '+' / '@' lines, text before the first header) is walked by the host.  flags: BMH_READS_COMMENTS as above;
+ * BMH_READS_HOST: the host walker alone (no device needed).  Refused with a message (BMH_EINVAL): a truncated or damaged gzip stream, qualities of another
+ * length than the sequence, a truncated last record, an empty sequence, FASTA and FASTQ records mixed (in one file or between the two), a pair whose two
+ * names differ, a file that ends before the other -- in that last case *out holds the complete pairs before the end (free it as usual).
+ */
+#define BMH_READS_HOST 2
+int bmh_reads_load_files(const char *path1, const char *path2, int n_threads, int flags, bmh_read_set_t *out);
 
 /* ---- interleaved pairs (read 2i, 2i+1): mem_pestat, mem_matesw (mate rescue, host local alignment), mem_pair, mem_sam_pe
  * (src/bwamem_pair.c).  Same inputs as bmh_finalize_regs plus read_lens and contig_len; out has room for `cap` records
@@ -716,6 +728,13 @@ int bmh_aligner_run_fasta(bmh_aligner_t *a, const char *reads_fa, uint64_t batch
  * popt->copy_comment, the comments.  Same text as bmh_reads_load + bmh_aligner_run with the same cuts. */
 int bmh_aligner_run_file(bmh_aligner_t *a, const char *path, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
                          bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats);
+
+/* bmh_aligner_run_file for the files bmh_reads_load_files takes (path2: the mates, or NULL; two files imply pairs): a loader thread reads (and inflates) the
+ * text into pinned windows, the device cuts them into records, and every batch -- ended as bseq_read ends it -- lands in pinned host memory while the lanes
+ * are on the batches before it; at most n_lanes + 3 batches are alive.  Same text as bmh_aligner_run_file on the single-line interleaved file of the same
+ * reads.  A file that ends before its mate file: the complete pairs before it are written, then BMH_EINVAL naming the shorter file. */
+int bmh_aligner_run_files(bmh_aligner_t *a, const char *path1, const char *path2, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
+                          bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,207 @@
+"""What the read-input path costs in file -> SAM text: FASTQ files of 150 bp reads on the bench's hg38-scale synthetic genome and index
+(scripts/fastq_cost.py's setup), single-end and paired, through
+  * bmh_aligner_run_file on the plain interleaved file (the yardstick: the path that exists without csrc/reads_parse.hip) -- in this tree
+    and, with --parent DIR, in a built tree of the parent commit (a child process with that tree's package and library, the same files),
+  * bmh_aligner_run_files on the same plain file, on two plain files (paired), on BGZF and on single-member gzip.
+Every configuration runs once to warm the lanes, then --runs times; each row lists every run, the median, the spread, the host CPU
+seconds of the process per million reads, and how many windows the device parser cut and how many the host walker took.
+
+--parser-only times nothing else than the parser: it loads a FASTQ file of --reads reads through bmh_reads_load_files (64 MiB windows), for a
+kernel trace in a run of its own (rocprofv3 --kernel-trace --stats -- python scripts/reads_input_rate.py --parser-only).
+
+    python scripts/reads_input_rate.py [--genome-mbp 3100] [--reads 1000000] [--runs 3] [--modes se,pe] [--parent DIR] [--out profiles/reads_input.json]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import struct
+import sys
+import tempfile
+import time
+import zlib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(os.environ.get("BMH_RATE_TREE") or ROOT, "bwa-mem_gpu_amd"))      # (--parent's child: the parent tree's package and library)
+import numpy as np
+import torch
+
+import bwamem_hip as B
+from bwamem_hip import fmindex as F
+from bwamem_hip.lib import ChainOpt, ExtParams, NativeAligner, PeOpt, PostOpt
+
+
+def _deflate_raw(data: bytes, level: int = 1) -> bytes:
+    c = zlib.compressobj(level, zlib.DEFLATED, -15)
+    return c.compress(data) + c.flush()
+
+
+def write_gzip(path: str, data: bytes) -> None:
+    with open(path, "wb") as f:
+        f.write(b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\xff" + _deflate_raw(data) + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data) & 0xFFFFFFFF))
+
+
+def write_bgzf(path: str, data: bytes, block: int = 65280) -> None:
+    with open(path, "wb") as f:
+        for i in list(range(0, len(data), block)) + [None]:
+            d = b"" if i is None else data[i:i + block]
+            z = _deflate_raw(d)
+            f.write(b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", len(z) + 25) + z + struct.pack("<II", zlib.crc32(d) & 0xFFFFFFFF, len(d)))
+
+
+def fastq_records(names: np.ndarray, w: int, asc: np.ndarray, qual: np.ndarray, rl: int) -> np.ndarray:
+    n = asc.size // rl
+    nm = np.frombuffer("".join(names.tolist()).encode(), np.uint8).reshape(n, w + 1)
+    recs = np.empty((n, w + 3 + rl + 3 + rl + 1), np.uint8)
+    recs[:, 0] = ord("@"); recs[:, 1:w + 2] = nm; recs[:, w + 2] = 10; recs[:, w + 3:w + 3 + rl] = asc.reshape(n, rl)
+    recs[:, w + 3 + rl] = 10; recs[:, w + 4 + rl] = ord("+"); recs[:, w + 5 + rl] = 10; recs[:, w + 6 + rl:w + 6 + 2 * rl] = qual.reshape(n, rl); recs[:, -1] = 10
+    return recs
+
+
+def measure(fn, runs: int, n4: int) -> dict:
+    """fn once to warm, then `runs` times: median rate, every run, spread, host CPU seconds (user + system of the process) per million reads"""
+    secs, cpus = [], []
+    for it in range(runs + 1):
+        c0 = os.times(); t1 = time.perf_counter()
+        fn()
+        dt = time.perf_counter() - t1; c1 = os.times()
+        if it:
+            secs.append(dt); cpus.append((c1.user - c0.user) + (c1.system - c0.system))
+    med = sorted(secs)[len(secs) // 2]
+    return {"Mreads_per_s": round(n4 / med / 1e6, 2), "runs_Mreads_per_s": [round(n4 / s / 1e6, 2) for s in secs],
+            "spread_pct": round(100 * (max(secs) - min(secs)) / med, 1), "host_cpu_s_per_Mreads": round(sorted(cpus)[len(cpus) // 2] / (n4 / 1e6), 3)}
+
+
+def parser_only(a):
+    from bwamem_hip.aligner import read_reads_files
+    from bwamem_hip.lib import reads_last_counts
+    B.load_library()
+    n, rl = a.reads, 150
+    rng = np.random.default_rng(1)
+    asc = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, n * rl)]
+    qual = rng.integers(33, 75, size=n * rl).astype(np.uint8)
+    w = len(str(n))
+    names = np.char.add("r", np.char.zfill(np.arange(n).astype(str), w))
+    path = os.path.join(tempfile.gettempdir(), "bmh_parser_only_%d.fq" % os.getpid())
+    fastq_records(names, w, asc, qual, rl).tofile(path)
+    for it in range(3):
+        t0 = time.perf_counter()
+        rs = read_reads_files(path, comments=True)
+        dt = time.perf_counter() - t0
+        print(json.dumps({"reads": len(rs), "text_bytes": os.path.getsize(path), "load_s": round(dt, 3), "counts": reads_last_counts()}), flush=True)
+    os.remove(path)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--genome-mbp", type=float, default=3100)
+    ap.add_argument("--reads", type=int, default=1_000_000, help="reads per distinct batch; a run takes four times as many")
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--modes", default="se,pe")
+    ap.add_argument("--out", default="")
+    ap.add_argument("--parent", default="", help="a built tree of the parent commit: its align_file on the same plain file, in a child process")
+    ap.add_argument("--parser-only", action="store_true")
+    ap.add_argument("--child", default="", help=argparse.SUPPRESS)          # the plain file the --parent child aligns (mode and sizes from the other options)
+    a = ap.parse_args()
+    if a.parser_only:
+        return parser_only(a)
+    dev = torch.device("cuda:0")
+    L = B.load_library()
+    n_genome = int(a.genome_mbp * 1e6)
+    t0 = time.time()
+    g_t, meta = B.synth.make_genome_device(n_genome, dev, seed=42, return_meta=True)
+    pac_t = F.pack_pac_device(g_t)
+    del g_t
+    torch.cuda.empty_cache()
+    d = F.build_fmd_index_device(pac_t, n_genome, sa_intv=1, verify=False)
+    dindex = B.Index.from_device(d.primary, d.L2.astype(np.uint64), d.seq_len, d.bwt_t, d.sa_intv, d.sa_t, d.bits_t, pac_t=pac_t, l_pac=n_genome)
+    g = F.unpack_pac_device(pac_t, n_genome).cpu().numpy()
+    pac_h = pac_t.cpu().numpy()
+    contigs, holes = meta["contigs"], meta["holes"]
+    nth = int(L.bmh_effective_cpus())
+    co = ChainOpt(); L.bmh_chain_opt_default(C.byref(co))
+    po = PostOpt(); L.bmh_post_opt_default(C.byref(po))
+    pe_o = PeOpt(); L.bmh_pe_opt_default(C.byref(pe_o))
+    params = ExtParams.default()
+    rl = 150
+    result = {"genome_mbp": a.genome_mbp, "setup_s": round(time.time() - t0, 1), "runs": a.runs, "host_threads": nth, "rows": {}}
+    tmp = tempfile.mkdtemp(prefix="bmh_reads_input_")
+    if a.child:                                                # the --parent child: the yardstick alone, on the file the parent process wrote
+        paired = a.modes == "pe"
+        n4 = 4 * a.reads
+        lanes, nb4 = (4, 8) if paired else (2, 4)
+        nat = NativeAligner(dindex, pac_h, n_genome, contigs, None, co, params, po, pe_o)
+        os.rmdir(tmp)
+        print("CHILD " + json.dumps(measure(lambda: nat.run_file(a.child, paired, lambda mv: None, batch_reads=(n4 // nb4) & ~1, n_lanes=lanes, n_threads=nth), a.runs, n4)), flush=True)
+        return
+    from bwamem_hip.lib import reads_last_counts
+    for mode in a.modes.split(","):
+        paired = mode == "pe"
+        n = a.reads
+        if paired:
+            r1 = B.synth.make_pairs(g, n // 2, rl, seed=7, holes=holes)[0]; r2 = B.synth.make_pairs(g, n // 2, rl, seed=1007, holes=holes)[0]
+        else:
+            r1 = B.synth.make_reads(g, n, rl, seed=7, holes=holes)[0]; r2 = B.synth.make_reads(g, n, rl, seed=1007, holes=holes)[0]
+        flat4 = np.concatenate([r1.reshape(-1), r2.reshape(-1), r1.reshape(-1), r2.reshape(-1)])
+        n4 = 4 * n
+        asc = B.synth.codes_to_ascii(flat4)
+        qual = np.random.default_rng(3).integers(33, 75, size=asc.size).astype(np.uint8)
+        w = len(str(n4))
+        names = np.char.add("r", np.char.zfill((np.arange(n4) // (2 if paired else 1)).astype(str), w))
+        recs = fastq_records(names, w, asc, qual, rl)
+        p = lambda s: os.path.join(tmp, mode + "." + s)  # noqa: E731
+        recs.tofile(p("fq"))
+        write_bgzf(p("fq.bgzf"), recs.tobytes()); write_gzip(p("fq.gz"), recs.tobytes())
+        if paired:
+            recs[0::2].tofile(p("r1.fq")); recs[1::2].tofile(p("r2.fq"))
+            write_bgzf(p("r1.bgzf"), recs[0::2].tobytes()); write_bgzf(p("r2.bgzf"), recs[1::2].tobytes())
+            write_gzip(p("r1.gz"), recs[0::2].tobytes()); write_gzip(p("r2.gz"), recs[1::2].tobytes())
+        del recs
+        lanes, nb4 = (4, 8) if paired else (2, 4)
+        br = (n4 // nb4) & ~1
+        nat = NativeAligner(dindex, pac_h, n_genome, contigs, None, co, params, po, pe_o)
+        bytes_out = [0]
+
+        def sink(mv):
+            bytes_out[0] += len(mv)
+        kw = dict(batch_reads=br, n_lanes=lanes, n_threads=nth)
+        configs = {"align_file_plain": lambda: nat.run_file(p("fq"), paired, sink, **kw),
+                   "align_files_plain": lambda: nat.run_files(p("fq"), None, paired, sink, **kw),
+                   "align_files_bgzf": lambda: nat.run_files(p("fq.bgzf"), None, paired, sink, **kw),
+                   "align_files_gzip": lambda: nat.run_files(p("fq.gz"), None, paired, sink, **kw)}
+        if paired:
+            configs.update({"align_files_two_plain": lambda: nat.run_files(p("r1.fq"), p("r2.fq"), True, sink, **kw),
+                            "align_files_two_bgzf": lambda: nat.run_files(p("r1.bgzf"), p("r2.bgzf"), True, sink, **kw),
+                            "align_files_two_gzip": lambda: nat.run_files(p("r1.gz"), p("r2.gz"), True, sink, **kw)})
+        rows, sizes = {}, set()
+        if a.parent:
+            import subprocess
+            env = dict(os.environ, BMH_RATE_TREE=a.parent, BMH_LIB=os.path.join(a.parent, "bwa-mem_gpu_amd", "libbwamem_hip.so"))
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", p("fq"), "--modes", mode, "--reads", str(a.reads), "--runs", str(a.runs),
+                                "--genome-mbp", str(a.genome_mbp)], env=env, stdout=subprocess.PIPE, timeout=900)
+            line = [l for l in r.stdout.decode().splitlines() if l.startswith("CHILD ")]
+            if r.returncode != 0 or not line:
+                raise RuntimeError("the --parent child failed")
+            rows["parent_align_file_plain"] = json.loads(line[0][6:])
+            print(mode, "parent_align_file_plain", json.dumps(rows["parent_align_file_plain"]), flush=True)
+        for key, fn in configs.items():
+            rows[key] = measure(lambda: (bytes_out.__setitem__(0, 0), fn()), a.runs, n4)
+            rows[key]["sam_bytes"] = int(bytes_out[0]); sizes.add(bytes_out[0])
+            if key != "align_file_plain":
+                rows[key]["parser"] = reads_last_counts()
+            print(mode, key, json.dumps(rows[key]), flush=True)
+        assert len(sizes) == 1, ("the configurations wrote different amounts of text", sizes)
+        nat.free()
+        for f in os.listdir(tmp):
+            os.remove(os.path.join(tmp, f))
+        result["rows"][mode] = dict(rows, reads=n4, lanes=lanes, batches=nb4)
+    os.rmdir(tmp)
+    line = json.dumps(result)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
