@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "bmh_chain_ws_set_max_qlen", "bmh_aligner_set_max_qlen", "bmh_aligner_host_tail_batches",
     "bmh_index_fasta", "bmh_fasta_pack", "bmh_fasta_packed_free",
     "bmh_reads_load_files", "bmh_aligner_run_files",
+    "bmh_bgzf_scan", "bmh_inflate_members_device", "bmh_inflate_members_host", "bmh_inflate_status_name", "bmh_bgzf_inflate",
 ]
 
 
@@ -158,7 +159,77 @@ def reads_last_counts() -> dict:
     L.bmh_reads_last_counts.argtypes = [C.POINTER(C.c_uint64)]
     out = (C.c_uint64 * 4)()
     L.bmh_reads_last_counts(out)
-    return dict(device_windows=int(out[0]), host_windows=int(out[1]), text_bytes=int(out[2]), records=int(out[3]))
+    L.bmh_reads_last_inflate_counts.argtypes = [C.POINTER(C.c_uint64)]
+    inf = (C.c_uint64 * 2)()
+    L.bmh_reads_last_inflate_counts(inf)
+    return dict(device_windows=int(out[0]), host_windows=int(out[1]), text_bytes=int(out[2]), records=int(out[3]),
+                device_inflate_members=int(inf[0]), host_inflate_members=int(inf[1]))
+
+
+# ---- BGZF members inflated on the device (csrc/inflate_kernels.hip) or by the same decoder on the host
+INFLATE_HOST = 1            # BMH_INFLATE_HOST
+INFLATE_MEMBER = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("in_len", "<u4"), ("isize", "<u4"), ("crc32", "<u4"), ("reserved", "<u4")])     # bmh_inflate_member_t
+INFLATE_STATUS = ("ok", "block_type", "stored_len", "code_lengths", "symbol", "distance", "truncated", "size", "crc", "table")
+
+
+def bgzf_scan(data: bytes) -> tuple:
+    """bmh_bgzf_scan: (member table as an INFLATE_MEMBER array, bytes the whole members cover, bytes of text).  Bytes that begin no BGZF member raise ValueError;
+    a cut last member is left out (used < len(data))."""
+    L = load_library()
+    L.bmh_bgzf_scan.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p, _u64p, _u64p]
+    nm, used, text = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    if L.bmh_bgzf_scan(data, len(data), None, 0, C.byref(nm), C.byref(used), C.byref(text)) != 0:
+        raise ValueError(_err(L))
+    tab = np.zeros(int(nm.value), INFLATE_MEMBER)
+    if L.bmh_bgzf_scan(data, len(data), tab.ctypes.data if len(tab) else None, len(tab), C.byref(nm), C.byref(used), C.byref(text)) != 0:
+        raise ValueError(_err(L))
+    return tab, int(used.value), int(text.value)
+
+
+def inflate_members(data: bytes, tab: np.ndarray, out_bytes: int, host: bool = False, per_launch: int = 0) -> tuple:
+    """bmh_inflate_members_device (or _host): the members of `tab` (INFLATE_MEMBER, offsets into data and into the text) -> (text as a uint8 array, status per
+    member); per_launch > 0: that many members per kernel launch"""
+    L = load_library()
+    tab = np.ascontiguousarray(tab, INFLATE_MEMBER)
+    n = len(tab)
+    if host:
+        out, st = np.zeros(out_bytes + 1, np.uint8), np.zeros(n, np.uint32)
+        L.bmh_inflate_members_host.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
+        if L.bmh_inflate_members_host(data, len(data), tab.ctypes.data, n, out.ctypes.data, out_bytes, st.ctypes.data, 0) != 0:
+            raise RuntimeError("bmh_inflate_members_host: " + _err(L))
+        return out[:out_bytes], st
+    import torch
+    d_in = torch.from_numpy(np.frombuffer(data + b"\0", np.uint8).copy()).cuda()
+    d_tab = torch.from_numpy(tab.view(np.uint8).reshape(-1).copy() if n else np.zeros(1, np.uint8)).cuda()
+    d_out = torch.zeros(out_bytes + 1, dtype=torch.uint8, device="cuda")
+    d_st = torch.full((max(n, 1),), 0x7fffffff, dtype=torch.int32, device="cuda")
+    L.bmh_inflate_members_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    step = per_launch if per_launch > 0 else max(n, 1)
+    stream = torch.cuda.current_stream().cuda_stream
+    for a in range(0, n, step):
+        k = min(step, n - a)
+        if L.bmh_inflate_members_device(d_in.data_ptr(), len(data), d_tab.data_ptr() + a * INFLATE_MEMBER.itemsize, k, d_out.data_ptr(), out_bytes,
+                                        d_st.data_ptr() + 4 * a, stream) != 0:
+            raise RuntimeError("bmh_inflate_members_device: " + _err(L))
+    torch.cuda.synchronize()
+    return d_out.cpu().numpy()[:out_bytes], d_st.cpu().numpy()[:n].astype(np.uint32)
+
+
+def inflate_bgzf(data: bytes, host: bool = False) -> bytes:
+    """bmh_bgzf_inflate: the text of a BGZF file held in memory, inflated on the device -- host=True: by the same decoder as plain C++, no device needed.
+    A cut file, bytes that are no BGZF member or a damaged member (inflate, length or CRC32) raise ValueError."""
+    L = load_library()
+    L.bmh_bgzf_inflate.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p), _u64p]
+    L.bmh_free.argtypes = [C.c_void_p]
+    text, n = C.c_void_p(), C.c_uint64()
+    rc = L.bmh_bgzf_inflate(data, len(data), INFLATE_HOST if host else 0, C.byref(text), C.byref(n))
+    if rc != 0:
+        msg = _err(L)
+        raise ValueError(msg) if rc == -2 else RuntimeError("bmh_bgzf_inflate: " + msg)
+    try:
+        return C.string_at(text.value, n.value)
+    finally:
+        L.bmh_free(text)
 
 
 def load_reads_files(path1: str, path2: str | None = None, comments: bool = False, host: bool = False, n_threads: int = 0) -> dict:

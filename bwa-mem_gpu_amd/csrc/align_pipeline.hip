@@ -1215,6 +1215,7 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 	src.stop();
 	lt.join();
 	uint64_t cnt[4]; bmh_pump_counts(P, cnt); bmh_reads_note_counts(cnt);
+	uint64_t icnt[2]; bmh_pump_inflate_counts(P, icnt); bmh_reads_note_inflate_counts(icnt);
 	bmh_pump_close(P);
 	return rc;
 }

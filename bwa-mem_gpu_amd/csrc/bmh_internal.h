@@ -81,6 +81,11 @@ bmh_text_src_t *bmh_text_open(const char *path, int n_threads);          // NULL
 int64_t bmh_text_read(bmh_text_src_t *s, uint8_t *dst, size_t n);         // bytes written: fewer than n at the end of the text only; -1: error (message set)
 int bmh_text_kind(const bmh_text_src_t *s);                              // 0 plain, 1 gzip, 2 BGZF
 void bmh_text_close(bmh_text_src_t *s);
+// a BGZF source for the device inflate (csrc/inflate_kernels.hip): whole compressed members into dst [cap >= bmh_text_pending + 1 MiB] until they hold want_text bytes of
+// text, the file ends or dst is full; tab: one entry per member (offsets into dst / into their text); returns the bytes they cover, -1: refused; *end: nothing is left
+size_t bmh_text_pending(const bmh_text_src_t *s);
+int64_t bmh_text_members(bmh_text_src_t *s, uint8_t *dst, size_t cap, size_t want_text, std::vector<bmh_inflate_member_t> &tab, uint64_t *text_bytes, bool *end);
+uint64_t bmh_text_host_members(const bmh_text_src_t *s);                // BGZF members inflated by the host threads so far
 // csrc/reads_io.cpp: the host walker (kseq_read restated) appends a record to growing arrays; nlen / clen: bytes of its name / comment with their NUL
 struct bmh_hbatch_t {
 	std::vector<uint8_t> ascii, quals, names, comments; std::vector<uint32_t> lens, nlen, clen;
@@ -102,6 +107,10 @@ void bmh_pump_close(bmh_reads_pump_t *p);
 // windows cut on the device, windows walked by the host, text bytes, records
 void bmh_reads_note_counts(const uint64_t *c);
 extern "C" int bmh_reads_last_counts(uint64_t *out);
+// beside it: out[2] of the same call -- BGZF members inflated on the device, BGZF members inflated by the host threads
+void bmh_pump_inflate_counts(const bmh_reads_pump_t *p, uint64_t out[2]);
+void bmh_reads_note_inflate_counts(const uint64_t *c);
+extern "C" int bmh_reads_last_inflate_counts(uint64_t *out);
 // ---- interleaved pairs with mem_pair / mem_sam_pe's choices on the device (csrc/pair_dev.hip) for the pairs the mate rescue does not touch
 // The host call (csrc/pair_post.cpp: bmh_finalize_pairs_split = bmh_finalize_pairs_deduped on a subset) tells the caller the insert-size statistics as
 // soon as it has them (after_pestat: the caller starts the device's pair kernel), asks before its own final walk which pairs the device handed back

@@ -246,12 +246,91 @@ struct pbuf_t {         // pinned host memory
 	template <class T> T *as() const { return (T *)p; }
 };
 
+#define RCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("reads parser: %s: %s", #x, hipGetErrorString(e_)); (void)hipGetLastError(); return BMH_ENODEV; } } while (0)
+
 // one file: its source and the window of its text
 struct stream_t {
 	std::string path; bmh_text_src_t *src = nullptr;
 	uint8_t *buf = nullptr; size_t cap = 0, have = 0; bool eof = false, pinned = false; int kind = 0; uint64_t bytes = 0;
+	// a BGZF file inflated on the device (csrc/inflate_kernels.hip): the window's text is dtext[cur][0 .. have) in HBM and never was on the host; whole compressed
+	// members go up from hcomp, the statuses come back in hstat with the parser's first wait (check_status), and buf is the host's copy for the walker (mirror)
+	bool on_dev = false, comp_busy = false; int cur = 0; uint32_t n_stat = 0; uint64_t n_dev_members = 0, comp_seen = 0, text_seen = 0;
+	dbuf_t dtext[2], dcomp, dtab, dstat; pbuf_t hcomp, htab, hstat; std::vector<bmh_inflate_member_t> tab;
+	uint8_t *text_dev() const { return dtext[cur].as<uint8_t>(); }
+	int check_status()
+	{
+		comp_busy = false;
+		const uint32_t *h = hstat.as<uint32_t>();
+		for (uint32_t i = 0; i < n_stat; ++i) if (h[i]) { n_stat = 0; bmh_set_error("reads file: %s: damaged BGZF member (inflate, length or CRC)", path.c_str()); return BMH_EINVAL; }
+		n_stat = 0;
+		return BMH_OK;
+	}
+	// room for `bytes` of text, the text held kept
+	int grow_text(size_t bytes, hipStream_t st)
+	{
+		if (dtext[cur].cap >= bytes) return BMH_OK;
+		dbuf_t &o = dtext[1 - cur];
+		if (o.need(bytes) != BMH_OK) return BMH_ENOMEM;
+		if (have) { RCK(hipMemcpyAsync(o.p, dtext[cur].p, have, hipMemcpyDeviceToDevice, st)); RCK(hipStreamSynchronize(st)); }
+		cur = 1 - cur;
+		return BMH_OK;
+	}
+	int fill_dev(size_t target, hipStream_t st)
+	{
+		while (!eof && have < target) {
+			if (comp_busy) { RCK(hipStreamSynchronize(st)); const int rc = check_status(); if (rc != BMH_OK) return rc; }     // (a second round of one window: poorly compressed members)
+			const size_t want = target - have;
+			// room for the compressed bytes of the text wanted, by the ratio this file has shown so far (half the text before any is known; at most all of it plus the
+			// members' headers), so that a poorly compressed file does not take two rounds, and a fourth host wait, per window
+			const double ratio = text_seen ? std::min(1.05, 1.25 * (double)comp_seen / (double)text_seen) : 0.5;
+			if (hcomp.need(bmh_text_pending(src) + std::max<size_t>((size_t)1 << 20, (size_t)((double)want * ratio) + (256u << 10))) != BMH_OK) return BMH_ENOMEM;
+			uint64_t text = 0; bool end = false;
+			const int64_t r = bmh_text_members(src, hcomp.as<uint8_t>(), hcomp.cap, want, tab, &text, &end);
+			if (r < 0) return BMH_EINVAL;
+			if (end) eof = true;
+			if (tab.empty()) { if (eof) break; bmh_set_error("reads file: %s: no whole BGZF member in %zu bytes", path.c_str(), hcomp.cap); return BMH_EINVAL; }
+			const size_t nm = tab.size(), tb = nm * sizeof(bmh_inflate_member_t);
+			if (nm >= 0xFFFFFFF0ull) { bmh_set_error("reads file: %s: 2^32 BGZF members in one window", path.c_str()); return BMH_EINVAL; }
+			const int grc = grow_text(have + text + 16, st);
+			if (grc != BMH_OK) return grc;
+			if (dcomp.need((size_t)r + 16) != BMH_OK || dtab.need(tb) != BMH_OK || dstat.need(nm * 4) != BMH_OK || htab.need(tb) != BMH_OK || hstat.need(nm * 4) != BMH_OK) return BMH_ENOMEM;
+			memcpy(htab.p, tab.data(), tb);
+			RCK(hipMemcpyAsync(dcomp.p, hcomp.p, (size_t)r, hipMemcpyHostToDevice, st));
+			RCK(hipMemcpyAsync(dtab.p, htab.p, tb, hipMemcpyHostToDevice, st));
+			const int irc = bmh_inflate_members_device(dcomp.as<uint8_t>(), (uint64_t)r, dtab.as<bmh_inflate_member_t>(), (uint32_t)nm, text_dev() + have, text, dstat.as<uint32_t>(), st);
+			if (irc != BMH_OK) return irc;
+			RCK(hipMemcpyAsync(hstat.p, dstat.p, nm * 4, hipMemcpyDeviceToHost, st));
+			comp_busy = true; n_stat = (uint32_t)nm; n_dev_members += nm; comp_seen += (uint64_t)r; text_seen += text;
+			have += (size_t)text; bytes += text;
+		}
+		return BMH_OK;
+	}
+	// the text behind the first k bytes moves to the front: into the other buffer, in stream order
+	int consume_dev(size_t k, hipStream_t st)
+	{
+		if (k >= have) { have = 0; return BMH_OK; }
+		if (k == 0) return BMH_OK;
+		const size_t rest = have - k;
+		dbuf_t &o = dtext[1 - cur];
+		if (o.need(rest + 16) != BMH_OK) return BMH_ENOMEM;
+		RCK(hipMemcpyAsync(o.p, text_dev() + k, rest, hipMemcpyDeviceToDevice, st));
+		cur = 1 - cur; have = rest;
+		return BMH_OK;
+	}
+	// the window for the host walker: the rare path
+	int mirror(hipStream_t st)
+	{
+		if (cap < have + 16) {
+			uint8_t *nb = (uint8_t *)malloc(have + 16);
+			if (!nb) { bmh_set_error("reads file: out of memory (%zu bytes of text)", have + 16); return BMH_ENOMEM; }
+			free(buf); buf = nb; cap = have + 16;
+		}
+		if (comp_busy) { RCK(hipStreamSynchronize(st)); const int rc = check_status(); if (rc != BMH_OK) return rc; }
+		if (have) { RCK(hipMemcpyAsync(buf, text_dev(), have, hipMemcpyDeviceToHost, st)); RCK(hipStreamSynchronize(st)); }
+		return BMH_OK;
+	}
 	~stream_t() { if (src) bmh_text_close(src); release(buf); }
-	void release(uint8_t *p) { if (!p) return; if (pinned) (void)hipHostFree(p); else free(p); }
+	void release(uint8_t *p) { if (!p) return; if (pinned && !on_dev) (void)hipHostFree(p); else free(p); }
 	int fill(size_t target)
 	{
 		if (eof || have >= target) return BMH_OK;
@@ -290,10 +369,10 @@ uint64_t cut_batch(const uint32_t *lens, uint64_t n, int step, uint64_t want_bas
 	return n;
 }
 
-#define RCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("reads parser: %s: %s", #x, hipGetErrorString(e_)); (void)hipGetLastError(); return BMH_ENODEV; } } while (0)
-
 struct dev_parser_t {
 	hipStream_t st = nullptr;
+	static constexpr uint32_t PEEK = 64;
+	int stream(hipStream_t *out) { if (!st) RCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); *out = st; return BMH_OK; }
 	struct per_file_t { dbuf_t b, lid, L, kind, klen, flag, fs, role, rec, seqk, sloff, hdr_line, seq_line, qual_line, rend, rsl, ctl; } D[2];
 	dbuf_t tmp, lens, nlen, clen, nstart, cstart, offs, noffs, coffs, ascii, codes, quals, names, cm;
 	pbuf_t h_small, h_lens, h_offs, h_noffs, h_coffs, h_rend[2];
@@ -305,7 +384,7 @@ struct dev_parser_t {
 	{
 		if (!st) RCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
 		rp_file_t F[2]; memset(F, 0, sizeof(F));
-		if (h_small.need(64 * sizeof(uint32_t)) != BMH_OK) return BMH_ENOMEM;
+		if (h_small.need(128 * sizeof(uint32_t)) != BMH_OK) return BMH_ENOMEM;
 		uint32_t *hs = h_small.as<uint32_t>();
 		uint64_t text = 0;
 		for (int f = 0; f < nf; ++f) {
@@ -314,22 +393,42 @@ struct dev_parser_t {
 			F[f].n = n; F[f].eof = S[f].eof; F[f].m = 0;
 			text += n;
 			if (n == 0) continue;
-			size_t p = 0;
-			while (p < n && (S[f].buf[p] == '\n' || S[f].buf[p] == '\r')) ++p;
-			if (p < n && S[f].buf[p] != '>' && S[f].buf[p] != '@') return 2;
-			F[f].fq = p < n && S[f].buf[p] == '@';
-			if (P.b.need(n + 16) != BMH_OK || P.lid.need((size_t)n * 4) != BMH_OK || P.ctl.need(sizeof(rp_ctl_t)) != BMH_OK) return BMH_ENOMEM;
-			RCK(hipMemcpyAsync(P.b.p, S[f].buf, n, hipMemcpyHostToDevice, st));
+			if (S[f].on_dev) {
+				// the text is in HBM already (inflated there): its first bytes come back with the line count
+				if (P.lid.need((size_t)n * 4) != BMH_OK || P.ctl.need(sizeof(rp_ctl_t)) != BMH_OK) return BMH_ENOMEM;
+				F[f].b = S[f].text_dev();
+				RCK(hipMemcpyAsync(hs + 64 + 16 * f, F[f].b, std::min<uint32_t>(n, PEEK), hipMemcpyDeviceToHost, st));
+			} else {
+				size_t p = 0;
+				while (p < n && (S[f].buf[p] == '\n' || S[f].buf[p] == '\r')) ++p;
+				if (p < n && S[f].buf[p] != '>' && S[f].buf[p] != '@') return 2;
+				F[f].fq = p < n && S[f].buf[p] == '@';
+				if (P.b.need(n + 16) != BMH_OK || P.lid.need((size_t)n * 4) != BMH_OK || P.ctl.need(sizeof(rp_ctl_t)) != BMH_OK) return BMH_ENOMEM;
+				RCK(hipMemcpyAsync(P.b.p, S[f].buf, n, hipMemcpyHostToDevice, st));
+				F[f].b = P.b.as<uint8_t>();
+			}
 			RCK(hipMemsetAsync(P.ctl.p, 0, sizeof(rp_ctl_t), st));
 			size_t tb = 0;
-			auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), rp_ls_flag{P.b.as<uint8_t>()});
+			auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), rp_ls_flag{F[f].b});
 			RCK(rocprim::inclusive_scan(nullptr, tb, in, P.lid.as<uint32_t>(), (size_t)n, rocprim::plus<uint32_t>(), st));
 			if (tb > tmp.cap) { RCK(hipStreamSynchronize(st)); if (tmp.need(tb) != BMH_OK) return BMH_ENOMEM; }
 			RCK(rocprim::inclusive_scan(tmp.p, tb, in, P.lid.as<uint32_t>(), (size_t)n, rocprim::plus<uint32_t>(), st));
 			RCK(hipMemcpyAsync(hs + f, P.lid.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, st));
-			F[f].b = P.b.as<uint8_t>(); F[f].lid = P.lid.as<uint32_t>();
+			F[f].lid = P.lid.as<uint32_t>();
 		}
 		RCK(hipStreamSynchronize(st));
+		for (int f = 0; f < nf; ++f) {
+			if (!S[f].on_dev) continue;
+			const int src_rc = S[f].check_status();                    // every member of the window inflated to its size and CRC, or the file is refused
+			if (src_rc != BMH_OK) return src_rc;
+			if (F[f].n == 0) continue;
+			const uint8_t *pk = (const uint8_t *)(hs + 64 + 16 * f);
+			const uint32_t np = std::min<uint32_t>(F[f].n, PEEK);
+			uint32_t p = 0;
+			while (p < np && (pk[p] == '\n' || pk[p] == '\r')) ++p;
+			if (p == np ? np < F[f].n : (pk[p] != '>' && pk[p] != '@')) return 2;       // (more blank bytes than the peek holds: the host looks)
+			F[f].fq = p < np && pk[p] == '@';
+		}
 		for (int f = 0; f < nf; ++f) {
 			if (F[f].n == 0) continue;
 			per_file_t &P = D[f];
@@ -542,6 +641,9 @@ bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_thre
 		P->S[f].path = paths[f]; P->S[f].pinned = !host_only;
 		P->S[f].src = bmh_text_open(paths[f], n_threads);
 		if (!P->S[f].src) { delete P; return nullptr; }
+		// BGZF is inflated on the device when asked for (BMH_INFLATE_DEVICE=1: opt-in until its end-to-end rate against the host inflate is on record, DESIGN.md
+		// section 4.8); BMH_INFLATE_HOST=1 overrides it (the A/B switch); a plain gzip stream stays with the host
+		P->S[f].on_dev = !host_only && bmh_text_kind(P->S[f].src) == 2 && bmh_tune("INFLATE_DEVICE", 0) != 0 && bmh_tune("INFLATE_HOST", 0) == 0;
 	}
 	if (!host_only) P->dev = new dev_parser_t();
 	return P;
@@ -550,6 +652,12 @@ bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_thre
 void bmh_pump_counts(const bmh_reads_pump_t *p, uint64_t out[4])
 {
 	out[0] = p->n_dev; out[1] = p->n_host; out[2] = p->S[0].bytes + p->S[1].bytes; out[3] = p->n_records;
+}
+
+void bmh_pump_inflate_counts(const bmh_reads_pump_t *p, uint64_t out[2])
+{
+	out[0] = out[1] = 0;
+	for (int f = 0; f < p->nf; ++f) { out[0] += p->S[f].n_dev_members; if (p->S[f].src) out[1] += bmh_text_host_members(p->S[f].src); }
 }
 
 void bmh_pump_close(bmh_reads_pump_t *p) { delete p; }
@@ -565,13 +673,22 @@ int bmh_pump_next(bmh_reads_pump_t *P, uint64_t want_bases, uint64_t want_reads,
 		else P->target = (size_t)std::min<uint64_t>(MAX_WINDOW, (want_reads ? want_reads * 400 : want_bases * 5 / 2) / (uint64_t)nf + (1u << 20));
 	}
 	for (;;) {
-		for (int f = 0; f < nf; ++f) { const int rc = P->S[f].fill(P->target); if (rc != BMH_OK) return rc; }
+		hipStream_t st = nullptr;
+		if (P->dev) { const int src = P->dev->stream(&st); if (src != BMH_OK) return src; }
+		for (int f = 0; f < nf; ++f) { const int rc = P->S[f].on_dev ? P->S[f].fill_dev(std::min(P->target, MAX_WINDOW - 65536) /* (it ends on a whole member: up to 64 KiB beyond) */, st) : P->S[f].fill(P->target); if (rc != BMH_OK) return rc; }
 		bool all_eof = true, any_eof = false, none_left = true;
 		for (int f = 0; f < nf; ++f) { all_eof = all_eof && P->S[f].eof; any_eof = any_eof || P->S[f].eof; none_left = none_left && P->S[f].have == 0; }
-		if (all_eof && none_left) return 0;
+		if (all_eof && none_left) {
+			for (int f = 0; f < nf; ++f) if (P->S[f].comp_busy) {          // (members without text, the end-of-file marker among them, are checked as well)
+				if (hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); bmh_set_error("reads parser: hipStreamSynchronize failed"); return BMH_ENODEV; }
+				const int src = P->S[f].check_status(); if (src != BMH_OK) return src;
+			}
+			return 0;
+		}
 		result_t R;
 		int rc = 2;
 		if (!P->host_only) rc = P->dev->run(P->S, nf, P->comments, want_bases, want_reads, even, take_all, alloc, rs, R);
+		if (rc == 2) for (int f = 0; f < nf; ++f) if (P->S[f].on_dev) { const int mrc = P->S[f].mirror(st); if (mrc != BMH_OK) return mrc; }
 		if (rc == 2) { rc = host_run(P->S, nf, P->comments, want_bases, want_reads, even, take_all, alloc, rs, R, P->hb); if (rc >= 0) ++P->n_host; }
 		else if (rc >= 0) ++P->n_dev;
 		if (rc < 0) return rc;
@@ -599,7 +716,10 @@ int bmh_pump_next(bmh_reads_pump_t *P, uint64_t want_bases, uint64_t want_reads,
 					}
 				}
 			}
-			for (int f = 0; f < nf; ++f) P->S[f].consume(R.consumed[f]);
+			for (int f = 0; f < nf; ++f) {
+				if (!P->S[f].on_dev) P->S[f].consume(R.consumed[f]);
+				else { const int crc = P->S[f].consume_dev(R.consumed[f], st); if (crc != BMH_OK) return crc; }
+			}
 			P->n_records += R.n_reads;
 			if (R.n_reads > 0) {
 				if (!take_all && !P->chunk) { size_t c = std::max(R.consumed[0], R.consumed[1]); P->target = std::min(MAX_WINDOW, c + c / 16 + (1u << 16)); }
@@ -608,7 +728,7 @@ int bmh_pump_next(bmh_reads_pump_t *P, uint64_t want_bases, uint64_t want_reads,
 			if (!P->pending.empty()) { bmh_set_error("%s", P->pending.c_str()); return BMH_EINVAL; }
 			if (all_eof) return 0;
 			bool progress = false;
-			for (int f = 0; f < nf; ++f) progress = progress || R.consumed[f] > 0 || (!P->S[f].eof && P->S[f].have < P->target);
+			for (int f = 0; f < nf; ++f) progress = progress || R.consumed[f] > 0 || (!P->S[f].eof && P->S[f].have < (P->S[f].on_dev ? std::min(P->target, MAX_WINDOW - 65536) : P->target));
 			if (progress) continue;
 		}
 		// the window holds no complete batch: a larger one
@@ -618,7 +738,10 @@ int bmh_pump_next(bmh_reads_pump_t *P, uint64_t want_bases, uint64_t want_reads,
 }
 
 // ---- the whole of one or two files as a read set
-namespace { uint64_t g_last_counts[4] = {0, 0, 0, 0}; std::mutex g_counts_mu; }
+namespace { uint64_t g_last_counts[4] = {0, 0, 0, 0}, g_last_inflate[2] = {0, 0}; std::mutex g_counts_mu; }
+
+extern "C" int bmh_reads_last_inflate_counts(uint64_t *out) { if (!out) return BMH_EINVAL; std::lock_guard<std::mutex> lk(g_counts_mu); memcpy(out, g_last_inflate, sizeof(g_last_inflate)); return BMH_OK; }
+void bmh_reads_note_inflate_counts(const uint64_t *c) { std::lock_guard<std::mutex> lk(g_counts_mu); memcpy(g_last_inflate, c, sizeof(g_last_inflate)); }
 
 extern "C" int bmh_reads_last_counts(uint64_t *out) { if (!out) return BMH_EINVAL; std::lock_guard<std::mutex> lk(g_counts_mu); memcpy(out, g_last_counts, sizeof(g_last_counts)); return BMH_OK; }
 void bmh_reads_note_counts(const uint64_t *c) { std::lock_guard<std::mutex> lk(g_counts_mu); memcpy(g_last_counts, c, sizeof(g_last_counts)); }
@@ -652,6 +775,7 @@ extern "C" int bmh_reads_load_files(const char *path1, const char *path2, int n_
 		for (uint64_t r = r0; r < lens.size(); ++r) { offs[r] += b0; noffs[r] += n0; if (cm) coffs[r] += c0; }
 	}
 	uint64_t cnt[4]; bmh_pump_counts(P, cnt); bmh_reads_note_counts(cnt);
+	uint64_t icnt[2]; bmh_pump_inflate_counts(P, icnt); bmh_reads_note_inflate_counts(icnt);
 	const bool partial = rc < 0 && strstr(bmh_last_error(), " ends before ") != nullptr;       // the complete pairs come back with the refusal
 	bmh_pump_close(P);
 	if (rc < 0 && !partial) return rc;

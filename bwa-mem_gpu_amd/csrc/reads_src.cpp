@@ -78,6 +78,7 @@ struct bmh_text_src_t {
 	zlib_t z; zs_t zs; bool zs_live = false, member_done = false, tail_ignored = false;
 	// BGZF: the members inflated last, served in order
 	std::vector<uint8_t> slots; std::vector<uint32_t> slot_len; size_t slot_cur = 0, slot_pos = 0;
+	uint64_t n_host_members = 0;
 	~bmh_text_src_t() { if (zs_live) z.end(&zs); if (fd >= 0) close(fd); }
 
 	// more compressed bytes behind the ones not yet used (moved to the front); false at the end of the file
@@ -182,7 +183,54 @@ struct bmh_text_src_t {
 		else { std::vector<std::thread> th; for (unsigned t = 0; t < T; ++t) th.emplace_back(work, t); for (auto &x : th) x.join(); }
 		for (int b : bad) if (b) { bmh_set_error("reads file: %s: damaged BGZF member (inflate, length or CRC)", path.c_str()); return false; }
 		in_pos = blk.back().off + blk.back().size;
+		n_host_members += blk.size();
 		return true;
+	}
+
+	// for the device inflate: the bytes not yet used and then the file's next bytes go to dst [cap] until the whole members at its front hold want_text bytes of
+	// text (or the file ends, or dst is full); tab: those members, offsets into dst and into their text; returns the bytes they cover (the rest waits in `in` for
+	// the next call: a member cut at the end of dst, or one more member than wanted), -1: refused.  cap >= the unused bytes + 1 MiB.
+	int64_t members(uint8_t *dst, size_t cap, size_t want_text, std::vector<bmh_inflate_member_t> &tab, uint64_t *text, bool *end)
+	{
+		tab.clear(); *text = 0; *end = false;
+		size_t n = in_len - in_pos, p = 0;
+		if (n + (1u << 20) > cap) { bmh_set_error("reads file: %s: the buffer of compressed bytes is too small (%zu for %zu held)", path.c_str(), cap, n); return -1; }
+		memcpy(dst, in.data() + in_pos, n); in_pos = in_len = 0;
+		for (;;) {
+			bool foreign = false;
+			while (*text < want_text) {
+				size_t data = 0;
+				const size_t bs = bgzf_size(dst + p, n - p, &data);
+				if (bs == (size_t)-1) break;                               // (its header is cut)
+				if (bs == 0 || bs < data + 8) {
+					if (!tab.empty() || p > 0) { foreign = true; break; }    // (refused by the next call: what lies before it is delivered first)
+					bmh_set_error("reads file: %s: a gzip member without the BGZF size field behind BGZF members", path.c_str()); return -1;
+				}
+				if (n - p < bs) break;
+				const uint8_t *tr = dst + p + bs - 8;
+				bmh_inflate_member_t e;
+				e.in_off = p + data; e.out_off = *text; e.in_len = (uint32_t)(bs - data - 8); e.reserved = 0;
+				e.crc32 = tr[0] | (tr[1] << 8) | (tr[2] << 16) | ((uint32_t)tr[3] << 24); e.isize = tr[4] | (tr[5] << 8) | (tr[6] << 16) | ((uint32_t)tr[7] << 24);
+				tab.push_back(e); *text += e.isize; p += bs;
+			}
+			if (foreign || *text >= want_text || n == cap) break;
+			if (in_eof) {
+				if (p < n && tab.empty()) { bmh_set_error("reads file: %s: the gzip stream is truncated", path.c_str()); return -1; }
+				break;
+			}
+			// as many bytes as the text still wanted is likely to take, by the ratio seen so far
+			const double ratio = *text ? (double)p / (double)*text : 0.3;
+			const size_t guess = (size_t)((double)(want_text - *text) * ratio * 1.05) + (128u << 10);
+			const size_t want = std::min(cap - n, guess > n - p ? guess - (n - p) : (size_t)65536);
+			const ssize_t r = ::read(fd, dst + n, want);
+			if (r < 0) { if (errno == EINTR) continue; bmh_set_error("reads file: read error in %s: %s", path.c_str(), strerror(errno)); return -1; }
+			if (r == 0) in_eof = true; else n += (size_t)r;
+		}
+		if (p == 0 && n > 0 && !in_eof && n == cap) { bmh_set_error("reads file: %s: a BGZF member larger than the buffer of compressed bytes", path.c_str()); return -1; }
+		if (n - p > in.size()) in.resize(n - p);
+		memcpy(in.data(), dst + p, n - p); in_len = n - p;
+		*end = in_eof && in_len == 0;
+		return (int64_t)p;
 	}
 
 	int64_t read_bgzf(uint8_t *dst, size_t n)
@@ -237,4 +285,33 @@ int64_t bmh_text_read(bmh_text_src_t *s, uint8_t *dst, size_t n)
 }
 
 int bmh_text_kind(const bmh_text_src_t *s) { return s->kind; }
+size_t bmh_text_pending(const bmh_text_src_t *s) { return s->in_len - s->in_pos; }
+uint64_t bmh_text_host_members(const bmh_text_src_t *s) { return s->n_host_members; }
+int64_t bmh_text_members(bmh_text_src_t *s, uint8_t *dst, size_t cap, size_t want_text, std::vector<bmh_inflate_member_t> &tab, uint64_t *text_bytes, bool *end)
+{
+	return s->members(dst, cap, want_text, tab, text_bytes, end);
+}
+
+extern "C" int bmh_bgzf_scan(const uint8_t *data, uint64_t n_bytes, bmh_inflate_member_t *tab, uint64_t tab_cap, uint64_t *n_members, uint64_t *used, uint64_t *text_bytes)
+{
+	if ((!data && n_bytes) || !n_members || !used || !text_bytes) { bmh_set_error("bmh_bgzf_scan: null argument"); return BMH_EINVAL; }
+	uint64_t nm = 0, p = 0, text = 0;
+	while (p < n_bytes && (!tab || nm < tab_cap)) {
+		size_t data_off = 0;
+		const size_t bs = bgzf_size(data + p, (size_t)(n_bytes - p), &data_off);
+		if (bs == (size_t)-1) break;
+		if (bs == 0 || bs < data_off + 8) { bmh_set_error("bmh_bgzf_scan: the bytes at %llu begin no BGZF member (a gzip member with the size field BC)", (unsigned long long)p); return BMH_EINVAL; }
+		if (n_bytes - p < bs) break;
+		const uint8_t *tr = data + p + bs - 8;
+		const uint32_t isize = tr[4] | (tr[5] << 8) | (tr[6] << 16) | ((uint32_t)tr[7] << 24);
+		if (tab) {
+			bmh_inflate_member_t &e = tab[nm];
+			e.in_off = p + data_off; e.out_off = text; e.in_len = (uint32_t)(bs - data_off - 8); e.isize = isize; e.reserved = 0;
+			e.crc32 = tr[0] | (tr[1] << 8) | (tr[2] << 16) | ((uint32_t)tr[3] << 24);
+		}
+		++nm; text += isize; p += bs;
+	}
+	*n_members = nm; *used = p; *text_bytes = text;
+	return BMH_OK;
+}
 void bmh_text_close(bmh_text_src_t *s) { delete s; }

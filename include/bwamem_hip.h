@@ -470,6 +470,35 @@ void bmh_reads_free(bmh_read_set_t *r);
 #define BMH_READS_HOST 2
 int bmh_reads_load_files(const char *path1, const char *path2, int n_threads, int flags, bmh_read_set_t *out);
 
+/* ---- BGZF members inflated on the device (csrc/inflate_core.h, csrc/inflate_kernels.hip): all of RFC 1951, one lane per member, the CRC32 of the text
+ * computed and compared there too.  BGZF (what bgzip writes) is a series of gzip members of at most 64 KiB of text, each naming its own size in the extra
+ * field "BC" and its text's size and CRC32 in its trailer; a plain gzip stream is one dependent bit stream and is not taken here.
+ * bmh_bgzf_scan (host only): the whole members at the front of data[0 .. n_bytes) as table entries -- tab may be NULL to count; at most tab_cap are
+ * written.  *used: the bytes they cover (less than n_bytes: the next member's header or body is cut, or tab_cap was reached); *text_bytes: the sum of
+ * their ISIZE; out_off is the prefix sum of ISIZE, so every member's text lands at its final place.  BMH_EINVAL: bytes that begin no BGZF member.
+ * bmh_inflate_members_device: n members on `stream` -- d_in [in_bytes] the compressed bytes, d_tab [n], d_out [out_bytes] the text, d_status [n] one
+ * word per member: 0, or the check that failed (bmh_inflate_status_name says which: block type 3, LEN / NLEN, a bad code-length set, no such symbol,
+ * a distance beyond the text, data that end early, a size other than ISIZE, the CRC32, a table entry outside the buffers).  A damaged member cannot
+ * make the kernel read or write outside the member's own bytes and text.  bmh_inflate_members_host: the same decoder as plain C++ on host threads.
+ * bmh_bgzf_inflate: the text of a whole BGZF file held in host memory (malloc'd, NUL behind it; free with bmh_free); flags: BMH_INFLATE_HOST runs
+ * the host decoder (no device needed).  Refused with a message: a cut file, bytes that are no BGZF member, a damaged member (named by its index). */
+typedef struct {
+	uint64_t in_off;       /* where the member's deflate data begin in the compressed buffer */
+	uint64_t out_off;      /* where its text goes in the output */
+	uint32_t in_len;       /* bytes of deflate data */
+	uint32_t isize;        /* bytes of text (the trailer's ISIZE; at most 65536) */
+	uint32_t crc32;        /* of the text (the trailer's) */
+	uint32_t reserved;
+} bmh_inflate_member_t;
+#define BMH_INFLATE_HOST 1
+int bmh_bgzf_scan(const uint8_t *data, uint64_t n_bytes, bmh_inflate_member_t *tab, uint64_t tab_cap, uint64_t *n_members, uint64_t *used, uint64_t *text_bytes);
+int bmh_inflate_members_device(const uint8_t *d_in, uint64_t in_bytes, const bmh_inflate_member_t *d_tab, uint32_t n, uint8_t *d_out, uint64_t out_bytes,
+                               uint32_t *d_status, void *stream);
+int bmh_inflate_members_host(const uint8_t *in, uint64_t in_bytes, const bmh_inflate_member_t *tab, uint32_t n, uint8_t *out, uint64_t out_bytes,
+                             uint32_t *status, int n_threads);
+const char *bmh_inflate_status_name(uint32_t status);
+int bmh_bgzf_inflate(const uint8_t *data, uint64_t n_bytes, int flags, uint8_t **text, uint64_t *text_bytes);
+
 /* ---- interleaved pairs (read 2i, 2i+1): mem_pestat, mem_matesw (mate rescue, host local alignment), mem_pair, mem_sam_pe
  * (src/bwamem_pair.c).  Same inputs as bmh_finalize_regs plus read_lens and contig_len; out has room for `cap` records
  * (mate rescue adds regions: regions_in + 16 per read is ample).  out_h[r]: the record of read r's own alignment within

@@ -9,6 +9,10 @@ seconds of the process per million reads, and how many windows the device parser
 --parser-only times nothing else than the parser: it loads a FASTQ file of --reads reads through bmh_reads_load_files (64 MiB windows), for a
 kernel trace in a run of its own (rocprofv3 --kernel-trace --stats -- python scripts/reads_input_rate.py --parser-only).
 
+--inflate-only times nothing else than the device inflate (csrc/inflate_kernels.hip): the BGZF members of a FASTQ text of --reads reads go up once, then the
+kernel alone runs on the first 1024, 4096, 16384 ... and on all of them, several launches each (rocprofv3 --kernel-trace --stats -- python
+scripts/reads_input_rate.py --inflate-only); beside it zlib on the same members on the host's threads, the yardstick, and the library's own host decoder.
+
     python scripts/reads_input_rate.py [--genome-mbp 3100] [--reads 1000000] [--runs 3] [--modes se,pe] [--parent DIR] [--out profiles/reads_input.json]
 """
 import argparse
@@ -92,6 +96,75 @@ def parser_only(a):
     os.remove(path)
 
 
+def inflate_only(a):
+    from concurrent.futures import ThreadPoolExecutor
+    from bwamem_hip.lib import INFLATE_MEMBER, bgzf_scan, inflate_members
+    L = B.load_library()
+    nth = int(L.bmh_effective_cpus())
+    n, rl = a.reads, 150
+    rng = np.random.default_rng(1)
+    asc = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, n * rl)]
+    qual = rng.integers(33, 75, size=n * rl).astype(np.uint8)
+    w = len(str(n))
+    names = np.char.add("r", np.char.zfill(np.arange(n).astype(str), w))
+    text = fastq_records(names, w, asc, qual, rl).tobytes()
+    block = 65280
+
+    def member(i):
+        d = text[i:i + block]
+        z = _deflate_raw(d)
+        return b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", len(z) + 25) + z + struct.pack("<II", zlib.crc32(d) & 0xFFFFFFFF, len(d))
+    with ThreadPoolExecutor(nth) as ex:
+        data = b"".join(ex.map(member, range(0, len(text), block)))
+    tab, used, nbytes = bgzf_scan(data)
+    assert used == len(data) and nbytes == len(text)
+    res = {"reads": n, "text_bytes": nbytes, "compressed_bytes": len(data), "members": len(tab), "host_threads": nth, "launches": []}
+    # the yardstick: zlib (inflate and crc32, what the host path runs per member) on the host's threads
+    raws = [data[int(e["in_off"]):int(e["in_off"]) + int(e["in_len"])] for e in tab]
+
+    def z_one(k):
+        t = zlib.decompress(raws[k], -15)
+        return zlib.crc32(t) == int(tab["crc32"][k])
+    secs = []
+    with ThreadPoolExecutor(nth) as ex:
+        for _ in range(3):
+            t0 = time.perf_counter(); ok = all(ex.map(z_one, range(len(tab)), chunksize=16)); secs.append(time.perf_counter() - t0)
+            assert ok
+    res["zlib_host_GBps"] = round(nbytes / sorted(secs)[1] / 1e9, 2)
+    t0 = time.perf_counter(); out, st = inflate_members(data, tab, nbytes, host=True); dt = time.perf_counter() - t0
+    assert not st.any() and out.tobytes() == text
+    res["own_decoder_host_GBps"] = round(nbytes / dt / 1e9, 2)
+    d_in = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).cuda()
+    d_tab = torch.from_numpy(tab.view(np.uint8).reshape(-1).copy()).cuda()
+    d_out = torch.zeros(nbytes + 16, dtype=torch.uint8, device="cuda")
+    d_st = torch.zeros(len(tab), dtype=torch.int32, device="cuda")
+    L.bmh_inflate_members_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    stream = torch.cuda.current_stream().cuda_stream
+    sizes = sorted({min(k, len(tab)) for k in (1024, 4096, 8192, 16384, 32768, len(tab))})
+    for k in sizes:
+        tb = int(tab["isize"][:k].sum())
+        ms = []
+        for it in range(a.runs + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            rc = L.bmh_inflate_members_device(d_in.data_ptr(), len(data), d_tab.data_ptr(), k, d_out.data_ptr(), nbytes, d_st.data_ptr(), stream)
+            e1.record(); torch.cuda.synchronize()
+            assert rc == 0
+            if it:
+                ms.append(e0.elapsed_time(e1))
+        assert not d_st[:k].any().item()
+        med = sorted(ms)[len(ms) // 2]
+        res["launches"].append({"members": k, "text_bytes": tb, "ms": [round(x, 3) for x in ms], "text_GBps": round(tb / med / 1e6, 2)})
+        print(json.dumps(res["launches"][-1]), flush=True)
+    assert d_out[:nbytes].cpu().numpy().tobytes() == text
+    res["device_over_zlib_host"] = round(res["launches"][-1]["text_GBps"] / res["zlib_host_GBps"], 2)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mbp", type=float, default=3100)
@@ -101,10 +174,13 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--parent", default="", help="a built tree of the parent commit: its align_file on the same plain file, in a child process")
     ap.add_argument("--parser-only", action="store_true")
+    ap.add_argument("--inflate-only", action="store_true")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)          # the plain file the --parent child aligns (mode and sizes from the other options)
     a = ap.parse_args()
     if a.parser_only:
         return parser_only(a)
+    if a.inflate_only:
+        return inflate_only(a)
     dev = torch.device("cuda:0")
     L = B.load_library()
     n_genome = int(a.genome_mbp * 1e6)
@@ -165,13 +241,23 @@ def main():
         def sink(mv):
             bytes_out[0] += len(mv)
         kw = dict(batch_reads=br, n_lanes=lanes, n_threads=nth)
+
+        def device_inflate(fn):                # BMH_INFLATE_DEVICE=1 for one call; without it BGZF is inflated on the host, the parent commit's path
+            L.bmh_tune_set.argtypes = [C.c_char_p, C.c_int, C.c_int]
+            L.bmh_tune_set(b"INFLATE_DEVICE", 1, 0)
+            try:
+                return fn()
+            finally:
+                L.bmh_tune_set(b"INFLATE_DEVICE", 0, 1)
         configs = {"align_file_plain": lambda: nat.run_file(p("fq"), paired, sink, **kw),
                    "align_files_plain": lambda: nat.run_files(p("fq"), None, paired, sink, **kw),
                    "align_files_bgzf": lambda: nat.run_files(p("fq.bgzf"), None, paired, sink, **kw),
+                   "align_files_bgzf_device_inflate": lambda: device_inflate(lambda: nat.run_files(p("fq.bgzf"), None, paired, sink, **kw)),
                    "align_files_gzip": lambda: nat.run_files(p("fq.gz"), None, paired, sink, **kw)}
         if paired:
             configs.update({"align_files_two_plain": lambda: nat.run_files(p("r1.fq"), p("r2.fq"), True, sink, **kw),
                             "align_files_two_bgzf": lambda: nat.run_files(p("r1.bgzf"), p("r2.bgzf"), True, sink, **kw),
+                            "align_files_two_bgzf_device_inflate": lambda: device_inflate(lambda: nat.run_files(p("r1.bgzf"), p("r2.bgzf"), True, sink, **kw)),
                             "align_files_two_gzip": lambda: nat.run_files(p("r1.gz"), p("r2.gz"), True, sink, **kw)})
         rows, sizes = {}, set()
         if a.parent:
