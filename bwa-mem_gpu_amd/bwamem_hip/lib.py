@@ -22,7 +22,7 @@ def lib_path() -> str:
 # every symbol include/bwamem_hip.h and include/seed_gen.h declare
 EXPORTED_SYMBOLS = [
     "bmh_last_error", "bmh_device_count", "bmh_set_device", "bmh_index_upload", "bmh_index_from_device",
-    "bmh_index_free", "bmh_index_probe", "bmh_index_replicate", "bmh_rccl_where", "bmh_rccl_unique_id", "bmh_rccl_comm_init_rank", "bmh_rccl_comm_destroy", "bmh_index_broadcast_rccl", "bmh_index_replicate_all", "bmh_shard_range", "bmh_index_densify_sa", "bmh_index_build", "bmh_seed_ws_create", "bmh_seed_ws_free", "bmh_seed_batch", "bmh_seed_last_timing", "bmh_reseed_opt_default", "bmh_seed_batch_reseed", "bmh_aligner_set_reseed",
+    "bmh_index_free", "bmh_index_kbits_info", "bmh_index_probe", "bmh_index_replicate", "bmh_rccl_where", "bmh_rccl_unique_id", "bmh_rccl_comm_init_rank", "bmh_rccl_comm_destroy", "bmh_index_broadcast_rccl", "bmh_index_replicate_all", "bmh_shard_range", "bmh_index_densify_sa", "bmh_index_build", "bmh_seed_ws_create", "bmh_seed_ws_free", "bmh_seed_batch", "bmh_seed_last_timing", "bmh_reseed_opt_default", "bmh_seed_batch_reseed", "bmh_aligner_set_reseed",
     "bmh_host_pin", "bmh_host_unpin", "bmh_extend_batch", "bmh_extend_batch_long", "bmh_extend_last_ms", "bmh_extend_last_unsupported", "bmh_extend_last_class_sizes", "bmh_extend_set_packed", "bmh_tune_set", "bmh_wtrace_start", "bmh_wtrace_stop", "bmh_wtrace_kept", "bmh_extend_release", "bmh_finalize_release", "bmh_matesw_release", "bmh_calib_gather", "bmh_calib_valu", "bmh_calib_valu_placed", "bmh_calib_last_clock",
     "bmh_jobs_frac_rep", "bmh_post_opt_default", "bmh_finalize_regs", "bmh_finalize_regs_device", "bmh_finalize_regs_device_last_ms", "bmh_sam_need_cigar", "bmh_format_sam", "bmh_free",
     "bmh_pe_opt_default", "bmh_finalize_pairs", "bmh_finalize_pairs_dev", "bmh_dedup_regs_device", "bmh_finalize_pairs_deduped", "bmh_rescue_check_counts", "bmh_sam_need_cigar_pe", "bmh_format_sam_pe",
@@ -556,6 +556,8 @@ def load_library() -> C.CDLL:
     L.bmh_index_from_device.argtypes = [C.c_uint64, _u64p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
                                         C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
     L.bmh_index_free.argtypes = [C.c_void_p]
+    L.bmh_index_kbits_info.restype = C.c_int
+    L.bmh_index_kbits_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), _u64p]
     L.bmh_tune_set.restype = C.c_int
     L.bmh_wtrace_start.restype = C.c_int
     L.bmh_wtrace_start.argtypes = [C.c_uint32]
@@ -777,6 +779,25 @@ class Index:
         torch.cuda.synchronize()
         o = out.cpu().numpy().view(np.uint64)
         return o.reshape(-1, 4) if code == 0 else o
+
+    def kbits_info(self) -> tuple:
+        """bmh_index_kbits_info: (K, device pointer, 32-bit words) of the handle's K-mer bitmap; (0, 0, 0) when it has none"""
+        L = load_library()
+        k, p, n = C.c_int(0), C.c_void_p(None), C.c_uint64(0)
+        rc = L.bmh_index_kbits_info(self.handle, C.byref(k), C.byref(p), C.byref(n))
+        if rc != 0:
+            raise RuntimeError(f"bmh_index_kbits_info rc={rc}: " + _err(L))
+        return int(k.value), int(p.value or 0), int(n.value)
+
+    def kbits_to_host(self) -> np.ndarray:
+        """the K-mer bitmap's 32-bit words (test helper; uses torch only to read HBM); empty when the handle has none"""
+        import torch
+        _, p, n = self.kbits_info()
+        if not n:
+            return np.zeros(0, np.uint32)
+        buf = torch.empty(n, dtype=torch.int32, device="cuda")
+        _memcpy_d2d(buf.data_ptr(), p, n * 4)
+        return buf.cpu().numpy().view(np.uint32)
 
     def free(self):
         if self.handle:

@@ -10,6 +10,10 @@ struct bmh_index {
 	bool owns_blocks;      // dev.blocks is the handle's own native re-encoding of a caller's buffer (bmh_index_from_device)
 	uint64_t n_words;
 };
+// csrc/kmer_bits.hip: the handle's K-mer bitmap (dev.kbits), built on the current device -- every function that gives a handle a text
+// calls attach once the text is in place (a handle copied from another must not keep the other's pointer); free with the handle
+void bmh_kbits_attach(bmh_index *ix);
+void bmh_kbits_free(bmh_index *ix);
 
 // extension jobs described by where their bases live instead of materialised base arrays (device job builder)
 struct bmh_ext_desc_t {

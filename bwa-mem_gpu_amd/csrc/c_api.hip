@@ -199,6 +199,7 @@ extern "C" bmh_index_t *bmh_index_upload(uint64_t primary, const uint64_t L2[5],
 		return nullptr;
 	}
 	ix->dev.blocks = (const uint4 *)d_bwt; ix->dev.sa = d_sa; ix->dev.sa_bits = d_bits; ix->dev.pac = d_pac;
+	bmh_kbits_attach(ix);
 	return ix;
 }
 
@@ -224,6 +225,7 @@ extern "C" bmh_index_t *bmh_index_from_device(uint64_t primary, const uint64_t L
 	ix->owns = false; ix->owns_blocks = true; ix->n_words = n_words;
 	fill_dev(ix, primary, L2, seq_len, sa_intv, n_sa, d_pac ? l_pac : 0);
 	ix->dev.blocks = (const uint4 *)d_native; ix->dev.sa = d_sa; ix->dev.sa_bits = d_sa_bits; ix->dev.pac = d_pac;
+	bmh_kbits_attach(ix);
 	return ix;
 }
 
@@ -260,6 +262,7 @@ extern "C" int bmh_index_replicate(const bmh_index_t *src, int src_device, int d
 		return BMH_ENOMEM;
 	}
 	ix->dev.blocks = (const uint4 *)d_bwt; ix->dev.sa = (const uint32_t *)d_sa; ix->dev.sa_bits = (const uint32_t *)d_bits; ix->dev.pac = (const uint8_t *)d_pac;
+	bmh_kbits_attach(ix);                            // dst_device is current: the copy's own bitmap, not the source's pointer
 	(void)hipSetDevice(prev);
 	*out = ix;
 	return BMH_OK;
@@ -324,6 +327,7 @@ extern "C" void bmh_index_free(bmh_index_t *ix)
 	if (ix->owns || ix->owns_blocks) (void)hipFree((void *)ix->dev.blocks);
 	if (ix->owns && ix->dev.pac) (void)hipFree((void *)ix->dev.pac);
 	if (ix->owns || ix->owns_sa) { (void)hipFree((void *)ix->dev.sa); (void)hipFree((void *)ix->dev.sa_bits); }
+	bmh_kbits_free(ix);
 	free(ix);
 }
 

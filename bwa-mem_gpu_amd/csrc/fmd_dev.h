@@ -33,7 +33,25 @@ struct fmd_dev_t {
 	const uint8_t *pac;
 	uint64_t l_pac;
 	int wave_prio;            // measurement knob SEED_SETPRIO (0 = off): s_setprio level of the seeding kernels' waves
+	// optional bitmap of the kbits_k-mers that occur in the indexed text (csrc/kmer_bits.hip): the forward search does not emit a
+	// candidate shorter than kbits_k whose last kbits_k read bases are no substring of the text; 0 when absent
+	const uint32_t *kbits;
+	int kbits_k;
 };
+
+// ---- K-mer bitmap (csrc/kmer_bits.hip builds it, smem_forward_kernel looks it up).  The key of K symbols holds symbol j of the
+// window (j = 0 the first, i.e. leftmost) at bits 2j+1:2j -- the order of the packed read words and of fmd_text16, so K symbols
+// cut out of either are a key as they are.  Bit (key & 31) of word (key >> 5) says whether the K-mer occurs in the text.
+__host__ __device__ __forceinline__ uint64_t kbits_mask(int K) { return (1ull << (2 * K)) - 1ull; }
+__host__ __device__ __forceinline__ uint64_t kbits_n_words(int K) { return K >= 3 ? 1ull << (2 * K - 5) : 1ull; }
+// THE encoding: where the bit of a key lives (builder and lookup both come through here)
+__host__ __device__ __forceinline__ void kbits_slot(uint64_t key, uint64_t &word, uint32_t &bit) { word = key >> 5; bit = 1u << (uint32_t)(key & 31); }
+// the window moved on by n symbols (0 <= n <= 16) given as packed 2-bit codes in the low 2n bits of `syms`
+__device__ __forceinline__ uint64_t kbits_push(uint64_t win, uint32_t syms, int n, int K)
+{
+	const uint64_t v = (uint64_t)syms & ((1ull << (2 * n)) - 1ull);
+	return n >= K ? v >> (2 * (n - K)) : (win >> (2 * n)) | (v << (2 * (K - n)));
+}
 
 // the wave's issue priority (the SIMD arbitrates by priority, then age): the gather-bound kernels run short bursts between loads
 __device__ __forceinline__ void fmd_wave_prio(const int p)

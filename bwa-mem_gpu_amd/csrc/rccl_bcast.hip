@@ -234,6 +234,7 @@ extern "C" int bmh_index_broadcast_rccl(void *comm_, int root, const bmh_index_t
 		ix->dev = f; ix->owns = true; ix->n_words = h.n_words;
 		ix->dev.blocks = (const uint4 *)d[0]; ix->dev.sa = (const uint32_t *)d[1]; ix->dev.sa_bits = (const uint32_t *)d[2]; ix->dev.pac = (const uint8_t *)d[3];
 		if (!h.has_pac) ix->dev.l_pac = 0;
+		bmh_kbits_attach(ix);                        // every rank builds its own bitmap from the text it received
 		*out = ix;
 	}
 	return BMH_OK;
@@ -292,6 +293,8 @@ extern "C" int bmh_index_replicate_all(const bmh_index_t *src, int src_device, c
 					bmh_index *ix = (bmh_index *)calloc(1, sizeof(bmh_index));
 					*ix = *src; ix->owns = true; ix->owns_sa = false; ix->owns_blocks = false;
 					ix->dev.blocks = (const uint4 *)d[i][0]; ix->dev.sa = (const uint32_t *)d[i][1]; ix->dev.sa_bits = (const uint32_t *)d[i][2]; ix->dev.pac = (const uint8_t *)d[i][3];
+					(void)hipSetDevice(devs[i]);
+					bmh_kbits_attach(ix);                // the copy's own bitmap, built where the copy lives
 					per_dev[i] = ix;
 				}
 				done = true;

@@ -16,7 +16,9 @@
 //   forward   one lane per read: bidirectional forward extension; at every
 //             interval-size change with end >= min_seed_len append a candidate
 //             {read, ordinal, start, end, k, s} to a global list (one
-//             wave-aggregated atomic per append round)
+//             wave-aggregated atomic per append round) -- unless the candidate is
+//             shorter than the index's K-mer bitmap's K and its last K bases do
+//             not occur in the text: it could never reach min_seed_len (kmer_bits.hip)
 //   backward  one lane per candidate: unidirectional backward search from
 //             start-1 to the maximal begin; result written at
 //             cand_base[read]+ordinal, i.e. already sorted by (read, end)
@@ -164,6 +166,14 @@ __global__ void __launch_bounds__(256) smem_forward_kernel(fmd_dev_t f, read_vie
 	enum { ST_START, ST_EXT, ST_DONE, ST_TAIL, ST_UNIQ };
 	uint64_t tp = 0;                 // ST_UNIQ: text index that pairs with read position i
 	int st = live && len > 0 ? ST_START : ST_DONE;
+	// K-mer bitmap (kmer_bits.hip): win = read[i-K .. i) as a key, clean = bases since the last N (saturating); both follow i through
+	// every state.  A candidate [x, e) with e - x < K is appended only if read[e-K .. e) is N-free and a K-mer of the text: it is kept
+	// only if its walk reaches a begin b with e - b >= min_seed_len >= K, and then the text holds that window.  Longer candidates
+	// contain their window.  (The candidates of a pass that the walk drops in lockstep with a longer mate end at that mate's begin: a
+	// mate that cannot reach min_seed_len takes no shorter one with it that could.)
+	const int kK = (f.kbits && min_seed_len >= f.kbits_k) ? f.kbits_k : 0;      // 0: no test, the kernel as it was
+	uint64_t win = 0;
+	int clean = 0;
 	cand_cursor_t cc = {0, 0};
 	unsigned it_wave = 0, it_mine = 0;                   // (BMH_SEED_STATS: iterations of the wave / in which this lane's read was still at work)
 	while (__any(st != ST_DONE)) {
@@ -171,15 +181,26 @@ __global__ void __launch_bounds__(256) smem_forward_kernel(fmd_dev_t f, read_vie
 		bool want = false;
 		cand_t c = {r, 0, 0, 0};
 		uint64_t ck = 0;
+		// a candidate pushed by ST_EXT / ST_TAIL ends at this iteration's i: its window is known now, and its bitmap word is fetched
+		// beside the iteration's rank gathers, not behind them
+		const bool kprobe = kK && (st == ST_EXT || st == ST_TAIL) && i >= min_seed_len && i - x < kK;
+		uint32_t kw = 0, kb = 0;
+		if (kprobe && clean >= kK) { uint64_t wd; kbits_slot(win, wd, kb); kw = f.kbits[wd]; }
+		const bool kdead = kprobe && !(kw & kb);          // (an N inside the window: nothing fetched, dead)
 		if (st == ST_START) {
 			// skip ambiguous bases, open a pass at the first A/C/G/T
 			int b = read_base(rv, r, i);
 			++i;
+			win = kbits_push(win, (uint32_t)b & 3u, 1, kK); clean = b < 4 ? min(clean + 1, 255) : 0;
 			if (b < 4) {
 				x = i - 1;
 				k = fmd_L2(f, b) + 1; s = fmd_L2(f, b + 1) - fmd_L2(f, b); l = fmd_L2(f, 3 - b) + 1;
 				if (i == len) {           // pass that starts on the last base
 					want = i >= min_seed_len;
+					if (want && kK > 1) {  // (one base long: its window ends with the base just read)
+						uint64_t wd; uint32_t bt; kbits_slot(win, wd, bt);
+						want = clean >= kK && (f.kbits[wd] & bt);
+					}
 					c.xe = ((uint32_t)x << 16) | (uint32_t)i; c.j = j; c.s = (uint32_t)s; ck = k;
 					st = ST_DONE;
 				} else st = ST_EXT;
@@ -194,12 +215,13 @@ __global__ void __launch_bounds__(256) smem_forward_kernel(fmd_dev_t f, read_vie
 				const uint64_t nk = cb == 0 ? ak[0] : cb == 1 ? ak[1] : cb == 2 ? ak[2] : ak[3];
 				const uint64_t nl = cb == 0 ? al[0] : cb == 1 ? al[1] : cb == 2 ? al[2] : al[3];
 				if (ns != s) {
-					want = i >= min_seed_len;
+					want = i >= min_seed_len && !kdead;
 					c.xe = ((uint32_t)x << 16) | (uint32_t)i; c.j = j; c.s = (uint32_t)s; ck = k;
 				}
 				if (ns == 0) st = ST_START;            // next pass starts at i (src/bwt.c:519 ret)
 				else {
 					k = nk; l = nl; s = ns; ++i;
+					win = kbits_push(win, (uint32_t)b, 1, kK); clean = min(clean + 1, 255);
 					if (i == len) {                       // reached the end: push the last interval
 						// the interval just computed is itself a candidate; it is appended on the
 						// next iteration through ST_TAIL below
@@ -210,12 +232,12 @@ __global__ void __launch_bounds__(256) smem_forward_kernel(fmd_dev_t f, read_vie
 					}
 				}
 			} else {                                      // ambiguous base ends the pass
-				want = i >= min_seed_len;
+				want = i >= min_seed_len && !kdead;
 				c.xe = ((uint32_t)x << 16) | (uint32_t)i; c.j = j; c.s = (uint32_t)s; ck = k;
 				st = ST_START;
 			}
 		} else if (st == ST_TAIL) {
-			want = i >= min_seed_len;
+			want = i >= min_seed_len && !kdead;
 			c.xe = ((uint32_t)x << 16) | (uint32_t)i; c.j = j; c.s = (uint32_t)s; ck = k;
 			st = ST_DONE;
 		} else if (st == ST_UNIQ) {
@@ -236,9 +258,14 @@ __global__ void __launch_bounds__(256) smem_forward_kernel(fmd_dev_t f, read_vie
 				const int m = min(min(fd, fn), n_av);
 				stop = m < n_av || n_av == 0;                     // mismatch, N, or nothing left of the text: the pass ends at i
 				i += m; tp += (uint64_t)m;
+				win = kbits_push(win, rw, m, kK); clean = min(clean + m, 255);       // the m bases taken matched the text: none is an N
 			}
 			if (stop) {
 				want = i >= min_seed_len;
+				if (want && i - x < kK) {      // (the window moved with the jump: this one fetch comes behind the text's)
+					uint64_t wd; uint32_t bt; kbits_slot(win, wd, bt);
+					want = clean >= kK && (f.kbits[wd] & bt);
+				}
 				c.xe = ((uint32_t)x << 16) | (uint32_t)i; c.j = j; c.s = 1u; ck = k;
 				st = ST_START;
 			} else if (i == len) st = ST_TAIL;
@@ -369,6 +396,8 @@ __global__ void __launch_bounds__(256) smem_backward_kernel(fmd_dev_t f, read_vi
 		if (live && !RESUME) atomicAdd(stats + 8 + (st_mine < 39u ? st_mine : 39u), 1ull);      // histogram of rank steps per candidate (0 .. 38, 39+)
 		atomicAdd(stats + 1, (unsigned long long)st_steps); atomicAdd(stats + 4, (unsigned long long)st_uniq); atomicAdd(stats + 5, (unsigned long long)st_u0); atomicAdd(stats + 6, (unsigned long long)st_x0); { const bool nowalk = !__any(live && !st_x0); if (!RESUME && lane == 0 && nowalk) atomicAdd(stats + 7, 1ull); }
 		if (lane == 0) { atomicAdd(stats, (unsigned long long)st_iter); atomicAdd(stats + 2, 1ull); atomicMax(stats + 3, (unsigned long long)st_iter); }
+		// walks for nothing: lane-steps (this launch's) and number of the candidates that end shorter than min_seed_len
+		if (live && !act && end - beg < min_seed_len) { atomicAdd(stats + 48, (unsigned long long)st_mine); atomicAdd(stats + 49, 1ull); if (!dropped) { atomicAdd(stats + 50, (unsigned long long)st_mine); atomicAdd(stats + 51, 1ull); } }
 	}
 	// still searching when the phase ends: parked for the next launch, in lane order
 	const unsigned long long sm = __ballot(act);
@@ -1076,7 +1105,7 @@ static int seed_batch_on(bmh_seed_ws_t *w, const bmh_index_t *idx, const uint8_t
 	{
 		static const bool want_stats = getenv("BMH_SEED_STATS") != nullptr;
 		unsigned long long *d_st = want_stats ? (unsigned long long *)w->counter + 8 : nullptr;
-		if (want_stats) HIPCK(hipMemsetAsync(d_st, 0, 64 + 40 * 8, st));
+		if (want_stats) HIPCK(hipMemsetAsync(d_st, 0, 52 * 8, st));
 		if (n_cands) {
 			// phases of the walk (BMH_SEED_BWD_PHASES="k1,k2,..": steps per phase, the last phase runs to the end).  Default: one launch --
 			// measured on the bench workload, "6,12,24,48" takes the wave-iterations from 14.7 M to 9.2 M (lane utilisation 38.5 -> 61.7 %)
@@ -1101,9 +1130,9 @@ static int seed_batch_on(bmh_seed_ws_t *w, const bmh_index_t *idx, const uint8_t
 				                                                                       ph < np ? cnt + (size_t)ph * BWD_NSUB : nullptr, sub_cap, ph < np ? phases[ph] : big);
 		}
 		if (want_stats) {
-			unsigned long long h[48];
+			unsigned long long h[52];
 			HIPCK(hipStreamSynchronize(st));
-			HIPCK(hipMemcpy(h, d_st, 64 + 40 * 8, hipMemcpyDeviceToHost));
+			HIPCK(hipMemcpy(h, d_st, sizeof(h), hipMemcpyDeviceToHost));
 			fprintf(stderr, "[backward] rank steps per candidate (0, 1, .. 38, 39+):");
 			for (int q = 0; q < 40; ++q) fprintf(stderr, " %llu", h[8 + q]);
 			fprintf(stderr, "\n");
@@ -1111,6 +1140,9 @@ static int seed_batch_on(bmh_seed_ws_t *w, const bmh_index_t *idx, const uint8_t
 			fprintf(stderr, "[backward] candidates of a pass that starts at read position 0 (no walk) %llu (%.1f%%); waves made of such only %llu\n", h[6], 100.0 * h[6] / (n_cands ? n_cands : 1), h[7]);
 			fprintf(stderr, "[backward] candidates %llu, waves %llu (all phases), wave-iterations %llu (%.1f per wave, max %llu), lane-steps %llu (%.1f per candidate): lane utilisation %.1f%%\n",
 			        (unsigned long long)n_cands, h[2], h[0], (double)h[0] / (h[2] ? h[2] : 1), h[3], h[1], (double)h[1] / (n_cands ? n_cands : 1), 100.0 * h[1] / (64.0 * (h[0] ? h[0] : 1)));
+			fprintf(stderr, "[backward] candidates that end shorter than min_seed_len %llu (%.1f%%) with %llu lane-steps (%.1f%% of all); of these not dropped in lockstep %llu with %llu lane-steps (%.1f%%); K-mer bitmap %s (%.1f candidates per read)\n",
+			        h[49], 100.0 * h[49] / (n_cands ? n_cands : 1), h[48], 100.0 * h[48] / (h[1] ? h[1] : 1), h[51], h[50], 100.0 * h[50] / (h[1] ? h[1] : 1),
+			        (f.kbits && min_seed_len >= f.kbits_k) ? "on" : "off", (double)n_cands / n_reads);
 		}
 	}
 	HIPCK(hipEventRecord(w->ev[3], st));

@@ -61,6 +61,14 @@ bmh_index_t *bmh_index_from_device(uint64_t primary, const uint64_t L2[5], uint6
                                    const uint32_t *d_sa, uint64_t n_sa, const uint32_t *d_sa_bits,
                                    const uint8_t *d_pac, uint64_t l_pac);
 void bmh_index_free(bmh_index_t *idx);
+/* A handle with the 2-bit text also holds a bitmap of the K-mers that occur in the indexed text fwd . revcomp(fwd)
+ * (csrc/kmer_bits.hip): K is the smallest with 4^K >= 8 seq_len, at most 18 (8 GiB at hg38 scale); key of a K-mer = its
+ * symbol j at bits 2j+1:2j, bit (key & 31) of word (key >> 5).  It is built on the device when the handle is made -- by
+ * every function that makes one, on the handle's own device -- and freed with it.  With min_seed_len >= K the forward
+ * search of bmh_seed_batch skips candidates that cannot reach min_seed_len; seeds are the same with and without it.
+ * No text, BMH_SEED_KBITS=0 in the environment when the handle is made, or no memory for it: the handle has none.
+ * bmh_index_kbits_info: *k = K (0: none), *d_bits = the bitmap in HBM (NULL: none), *n_words = its 32-bit words. */
+int bmh_index_kbits_info(const bmh_index_t *idx, int *k, const uint32_t **d_bits, uint64_t *n_words);
 /* Rank primitives at n given rows (d_rows, d_out: device memory), asynchronous on `stream`:
  *   what = 0: d_out[4 i + c] = Occ(rows[i], c), c = A,C,G,T  (bwt_occ4, src/bwt.c:309-330; rows -1 and seq_len allowed)
  *   what = 1: d_out[i] = LF(rows[i])                         (bwt_invPsi, src/bwt.c:64-70)
