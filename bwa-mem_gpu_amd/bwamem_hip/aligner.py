@@ -336,10 +336,38 @@ class Aligner:
     def header(self) -> str:
         return "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in self.contigs) + (getattr(self, "rg_line", "") + "\n" if getattr(self, "rg_line", "") else "")
 
-    def align_batch(self, names, seqs=None, id0: int = 0, paired: bool = False, as_bytes: bool = False, quals=None, comments=None):
+    def _bam_open(self, out, fmt: str, level: int) -> bool:
+        """fmt="bam": checks `out` and writes the header members (bmh_bam_header of header(), compressed by the host core); True for BAM"""
+        if fmt not in ("sam", "bam"):
+            raise ValueError(f"fmt {fmt!r}: sam or bam")
+        if fmt == "sam":
+            return False
+        if level not in (0, 1):
+            raise ValueError(f"level {level}: 0 or 1")
+        if not ("b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")):
+            raise ValueError('fmt="bam" needs a binary file object')
+        from .lib import bam_header, bgzf_compress
+        out.write(bgzf_compress(bam_header(self.header(), self.contigs), level, host=True))
+        return True
+
+    def _bam_members(self, text: bytes, level: int) -> bytes:
+        """SAM record lines -> the BGZF members of their BAM records (the device entry points); a refused record raises BamRefusal naming the read"""
+        from .lib import BamRefusal, bam_status_name, bgzf_compress, sam_to_bam
+        bam, st = sam_to_bam(text, self.contigs)
+        bad = np.flatnonzero(st)
+        if bad.size:
+            line = bytes(text).split(b"\n")[int(bad[0])]
+            raise BamRefusal(f"BAM output: read '{line.split(chr(9).encode())[0].decode(errors='replace')}': its SAM record cannot be written as BAM: {bam_status_name(int(st[bad[0]]))}")
+        return bgzf_compress(bam, level)
+
+    def align_batch(self, names, seqs=None, id0: int = 0, paired: bool = False, as_bytes: bool = False, quals=None, comments=None, fmt: str = "sam", level: int = 1):
         """SAM records of one batch of reads: a ReadSet, or (names, seqs) lists of str / ASCII uint8 arrays (quals, comments: lists as
         ReadSet.from_lists takes them); id0 = index of its first read in the run.  paired: interleaved pairs (gase_aln -p); the insert-size
         statistics are the batch's.  QUAL comes from the reads' qualities, '*' without; with -C the comments end the records."""
+        if fmt != "sam":                                          # fmt="bam": the batch's records as BGZF members (bytes; no header, no end-of-file member)
+            if fmt != "bam" or level not in (0, 1):
+                raise ValueError(f"fmt {fmt!r}, level {level}: sam or bam, 0 or 1")
+            return self._bam_members(self.align_batch(names, seqs, id0=id0, paired=paired, as_bytes=True, quals=quals, comments=comments), level)
         rs = names if isinstance(names, ReadSet) else ReadSet.from_lists(names, seqs, quals=quals, comments=comments)
         self._qc = (rs.qual, rs.comments if self.po.copy_comment else None)
         L, dev, n = self.L, self.dev, len(rs)
@@ -508,9 +536,12 @@ class Aligner:
             if self.long_reads:
                 nat.set_max_qlen(EXT_LONG_MAX)
         nat.set_reseed(self.reseed if self.reseed.enable else None)
+        nat.set_output(*getattr(self, "_out_fmt", ("sam", 1)))
         return nat
 
-    def align_file(self, reads_fa: str, out, batch_reads: int = 0, paired: bool = False, chunk_bases: int = 0) -> int:
+    def align_file(self, reads_fa: str, out, batch_reads: int = 0, paired: bool = False, chunk_bases: int = 0, fmt: str = "sam", level: int = 1) -> int:
+        if fmt != "sam":
+            return self._align_bam(lambda o: self.align_file(reads_fa, o, batch_reads=batch_reads, paired=paired, chunk_bases=chunk_bases), out, fmt, level)
         """out: a text or binary file object.  Batches are cut the way the reference's bseq_read cuts them (src/bwa.c, called with
         chunk_size * n_threads = 10 Mbases per thread, or -K, src/fastmap.c:527): reads are added until the batch holds at least
         chunk_bases bases and an even number of reads -- in paired mode the insert-size statistics are those of the batch, so the
@@ -578,15 +609,56 @@ class Aligner:
             return n
         for b, e in zip(cuts[:-1], cuts[1:]):
             if e > b:
+                if getattr(self, "_out_fmt", ("sam", 1))[0] == "bam":
+                    out.write(self.align_batch(rs.slice(b, e), id0=b, paired=paired, fmt="bam", level=self._out_fmt[1]))
+                    continue
                 out.write(self.align_batch(rs.slice(b, e), id0=b, paired=paired, as_bytes="view" if binary else False))   # (binary: the library's buffer, uncopied)
         return n
 
-    def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0) -> int:
+    def _align_bam(self, run, out, fmt: str, level: int) -> int:
+        """fmt="bam" of align_file / align_files: the header members, the batches' members (`run` with the native aligner's output switched; the Python
+        loop's batches converted here), the end-of-file member.  The file is written through a shim that drops the SAM header `run` writes first."""
+        from .lib import bgzf_eof
+        if fmt != "bam":
+            raise ValueError(f"fmt {fmt!r}: sam or bam")
+        if level not in (0, 1):
+            raise ValueError(f"level {level}: 0 or 1")
+        if not ("b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")):
+            raise ValueError('fmt="bam" needs a binary file object')
+        al = self
+
+        class _Shim:
+            mode = "wb"
+            first = True
+
+            def write(self, b):
+                if self.first:                                    # the SAM header text: the BAM header goes in its place
+                    self.first = False
+                    al._bam_open(out, "bam", level)
+                    return
+                out.write(b)
+        shim = _Shim()
+        self._out_fmt = ("bam", level)
+        try:
+            n = run(shim)
+        finally:
+            self._out_fmt = ("sam", 1)
+            nat = getattr(self, "_native", None)
+            if nat is not None:
+                nat.set_output("sam", 1)
+        if shim.first:                                            # (no reads: nothing was written)
+            self._bam_open(out, "bam", level)
+        out.write(bgzf_eof())
+        return n
+
+    def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1) -> int:
         """align_file for the files users have (bmh_aligner_run_files): `reads` (and `mates`: the second file of a pair, which implies paired) may be
         multi-line FASTA or FASTQ, plain, gzip or BGZF, a regular file or a pipe.  Batches are cut by align_file's rules (-t, -K, the 150 Mbase floor for
         single-end runs), so the text equals align_file's on the single-line interleaved file of the same reads.  Returns the number of reads."""
         if out is None:
             raise ValueError("align_files: out (a text or binary file object) is required")
+        if fmt != "sam":
+            return self._align_bam(lambda o: self.align_files(reads, mates, out=o, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads), out, fmt, level)
         binary = "b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")
         paired = bool(paired or mates is not None)
         cb = 0

@@ -38,6 +38,8 @@ EXPORTED_SYMBOLS = [
     "bmh_index_fasta", "bmh_fasta_pack", "bmh_fasta_packed_free",
     "bmh_reads_load_files", "bmh_aligner_run_files",
     "bmh_bgzf_scan", "bmh_inflate_members_device", "bmh_inflate_members_host", "bmh_inflate_status_name", "bmh_bgzf_inflate",
+    "bmh_bam_ws_create", "bmh_bam_ws_free", "bmh_sam_to_bam_device", "bmh_sam_to_bam_host", "bmh_bam_status_name", "bmh_bgzf_deflate_device", "bmh_bgzf_deflate_host",
+    "bmh_deflate_blocks_host", "bmh_bam_header", "bmh_aligner_set_output",
 ]
 
 
@@ -232,6 +234,131 @@ def inflate_bgzf(data: bytes, host: bool = False) -> bytes:
         L.bmh_free(text)
 
 
+# ---- BAM output: SAM record lines -> BAM records -> BGZF members (csrc/bam_kernels.hip, csrc/deflate_kernels.hip), or the same cores on the host
+OUT_SAM, OUT_BAM = 0, 1     # BMH_OUT_SAM, BMH_OUT_BAM
+BAM_STATUS = ("ok", "fields", "name", "cigar", "tag", "seq_qual", "no_eol", "rname", "number", "int_tag", "float_tag", "b_array", "size")
+
+
+class BamOut(C.Structure):
+    """bmh_bam_out_t"""
+    _fields_ = [("d_bam", C.c_void_p), ("bam_bytes", C.c_uint64), ("d_status", C.c_void_p), ("n_records", C.c_uint32),
+                ("n_refused", C.c_uint32), ("first_refused", C.c_uint32), ("first_status", C.c_uint32)]
+
+
+class BamRefusal(ValueError):
+    """a SAM record that cannot be written as BAM (the message names the read and the check)"""
+
+
+def _contig_table(contigs) -> tuple:
+    """names NUL-terminated back to back, offsets [n + 1]; contigs: names, or (name, length) pairs"""
+    names = [(c if isinstance(c, (str, bytes)) else c[0]) for c in contigs]
+    names = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    off = np.zeros(len(names) + 1, np.uint32)
+    off[1:] = np.cumsum([len(n) + 1 for n in names], dtype=np.int64)
+    return np.frombuffer(b"".join(n + b"\0" for n in names) + b"\0", np.uint8).copy(), off
+
+
+def bgzf_eof() -> bytes:
+    """bmh_bgzf_eof: the 28-byte end-of-file member"""
+    return bytes((C.c_uint8 * 28).in_dll(load_library(), "bmh_bgzf_eof"))
+
+
+def bam_status_name(status: int) -> str:
+    L = load_library()
+    L.bmh_bam_status_name.restype = C.c_char_p
+    L.bmh_bam_status_name.argtypes = [C.c_uint32]
+    return L.bmh_bam_status_name(int(status)).decode()
+
+
+def sam_to_bam(text: bytes, contigs, host: bool = False) -> tuple:
+    """bmh_sam_to_bam_device (host=True: bmh_sam_to_bam_host, no device needed): SAM record lines -> (the BAM records back to back as bytes, status per
+    line as a uint32 array: 0, or the index into BAM_STATUS of the check that refused the line, which then left no bytes)"""
+    L = load_library()
+    text = bytes(text)
+    blob, off = _contig_table(contigs)
+    nc = len(off) - 1
+    if host:
+        L.bmh_sam_to_bam_host.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u32p]
+        L.bmh_free.argtypes = [C.c_void_p]
+        bam, st, nb, nr = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint32()
+        if L.bmh_sam_to_bam_host(text, len(text), nc, blob.ctypes.data, off.ctypes.data, 0, C.byref(bam), C.byref(nb), C.byref(st), C.byref(nr)) != 0:
+            raise RuntimeError("bmh_sam_to_bam_host: " + _err(L))
+        try:
+            return C.string_at(bam.value, nb.value) if nb.value else b"", np.frombuffer(C.string_at(st.value, 4 * nr.value), np.uint32).copy()
+        finally:
+            L.bmh_free(bam); L.bmh_free(st)
+    import torch
+    L.bmh_bam_ws_create.restype = C.c_void_p
+    L.bmh_bam_ws_free.argtypes = [C.c_void_p]
+    L.bmh_sam_to_bam_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BamOut)]
+    d_text = torch.from_numpy(np.frombuffer(text + b"\0", np.uint8).copy()).cuda()
+    d_blob, d_off = torch.from_numpy(blob).cuda(), torch.from_numpy(off.view(np.int32).copy()).cuda()
+    ws = L.bmh_bam_ws_create()
+    try:
+        o = BamOut()
+        if L.bmh_sam_to_bam_device(ws, d_text.data_ptr(), len(text), nc, d_blob.data_ptr(), d_off.data_ptr(), torch.cuda.current_stream().cuda_stream, C.byref(o)) != 0:
+            raise RuntimeError("bmh_sam_to_bam_device: " + _err(L))
+        bam = torch.empty(max(int(o.bam_bytes), 1), dtype=torch.uint8, device="cuda"); st = torch.empty(max(int(o.n_records), 1), dtype=torch.int32, device="cuda")
+        if o.bam_bytes: _memcpy_d2d(bam.data_ptr(), o.d_bam, int(o.bam_bytes))
+        if o.n_records: _memcpy_d2d(st.data_ptr(), o.d_status, 4 * int(o.n_records))
+        torch.cuda.synchronize()
+        return bam.cpu().numpy()[:int(o.bam_bytes)].tobytes(), st.cpu().numpy()[:int(o.n_records)].view(np.uint32).copy()
+    finally:
+        L.bmh_bam_ws_free(ws)
+
+
+def bgzf_compress(data: bytes, level: int = 1, host: bool = False) -> bytes:
+    """bmh_bgzf_deflate_device (host=True: bmh_bgzf_deflate_host): the bytes as BGZF members of at most 0xff00 bytes of data each (level 0: stored, 1: LZ77 +
+    dynamic Huffman codes); no bytes give no members.  Both forms give the same bytes.  The caller appends bgzf_eof() to end a file."""
+    L = load_library()
+    data = bytes(data)
+    if host:
+        L.bmh_bgzf_deflate_host.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_void_p), _u64p]
+        L.bmh_free.argtypes = [C.c_void_p]
+        out, n = C.c_void_p(), C.c_uint64()
+        if L.bmh_bgzf_deflate_host(data, len(data), int(level), 0, C.byref(out), C.byref(n)) != 0:
+            raise ValueError("bmh_bgzf_deflate_host: " + _err(L))
+        try:
+            return C.string_at(out.value, n.value) if n.value else b""
+        finally:
+            L.bmh_free(out)
+    import torch
+    L.bmh_bam_ws_create.restype = C.c_void_p
+    L.bmh_bam_ws_free.argtypes = [C.c_void_p]
+    L.bmh_bgzf_deflate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), _u64p]
+    d_in = torch.from_numpy(np.frombuffer(data + b"\0", np.uint8).copy()).cuda()
+    ws = L.bmh_bam_ws_create()
+    try:
+        out, n = C.c_void_p(), C.c_uint64()
+        if L.bmh_bgzf_deflate_device(ws, d_in.data_ptr(), len(data), int(level), torch.cuda.current_stream().cuda_stream, C.byref(out), C.byref(n)) != 0:
+            raise ValueError("bmh_bgzf_deflate_device: " + _err(L))
+        if not n.value:
+            return b""
+        t = torch.empty(int(n.value), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        _memcpy_d2d(t.data_ptr(), out.value, int(n.value))
+        torch.cuda.synchronize()
+        return t.cpu().numpy().tobytes()
+    finally:
+        L.bmh_bam_ws_free(ws)
+
+
+def bam_header(header_text: str, contigs) -> bytes:
+    """bmh_bam_header: magic, l_text, text, n_ref and the references of (name, length) pairs -- uncompressed"""
+    L = load_library()
+    L.bmh_bam_header.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(C.c_void_p), _u64p]
+    L.bmh_free.argtypes = [C.c_void_p]
+    names = (C.c_char_p * max(len(contigs), 1))(*[c[0].encode() for c in contigs])
+    lens = np.ascontiguousarray([c[1] for c in contigs] or [0], dtype=np.int32)
+    out, n = C.c_void_p(), C.c_uint64()
+    if L.bmh_bam_header(header_text.encode(), len(contigs), names, lens.ctypes.data, C.byref(out), C.byref(n)) != 0:
+        raise ValueError("bmh_bam_header: " + _err(L))
+    try:
+        return C.string_at(out.value, n.value)
+    finally:
+        L.bmh_free(out)
+
+
 def load_reads_files(path1: str, path2: str | None = None, comments: bool = False, host: bool = False, n_threads: int = 0) -> dict:
     """bmh_reads_load_files: one or two read files of any shape (multi-line records, gzip / BGZF, pipes) as load_reads gives them; path2: the mates (reads 2i
     and 2i+1).  host=True: the host walker alone (no device).  A refused file raises ReadFileError; when one file ends before the other its `partial`
@@ -311,6 +438,13 @@ class NativeAligner:
         if L.bmh_aligner_set_reseed(self.handle, C.byref(opt) if opt is not None else None) != 0:
             raise ValueError("bmh_aligner_set_reseed: " + _err(L))
 
+    def set_output(self, fmt: str = "sam", level: int = 1) -> None:
+        """bmh_aligner_set_output: what the runs that follow hand to `write` -- "sam": the records' text; "bam": BGZF members of BAM records"""
+        L = load_library()
+        L.bmh_aligner_set_output.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        if fmt not in ("sam", "bam") or L.bmh_aligner_set_output(self.handle, OUT_BAM if fmt == "bam" else OUT_SAM, int(level)) != 0:
+            raise ValueError("bmh_aligner_set_output: " + (_err(L) if fmt in ("sam", "bam") else f"format {fmt!r} (sam or bam)"))
+
     def host_tail_batches(self) -> int:
         """batches of the last run whose region tail the device refused (the host forms took them)"""
         L = load_library()
@@ -348,6 +482,8 @@ class NativeAligner:
         if err:
             raise err[0]
         if rc != 0:
+            if _err(L).startswith("BAM output:"):
+                raise BamRefusal(_err(L))
             raise (CapacityError if rc == -3 else RuntimeError)(f"bmh_aligner_run rc={rc}: " + _err(L))
         return st
 
@@ -396,6 +532,8 @@ class NativeAligner:
             raise err[0]
         if rc != 0:
             msg = _err(L)
+            if msg.startswith("BAM output:"):
+                raise BamRefusal(msg)
             if "FASTQ:" in msg or "reads file:" in msg:
                 raise ReadFileError(msg)
             raise (CapacityError if rc == -3 else RuntimeError)(f"bmh_aligner_run_file rc={rc}: " + msg)
@@ -423,6 +561,8 @@ class NativeAligner:
             raise err[0]
         if rc != 0:
             msg = _err(L)
+            if msg.startswith("BAM output:"):
+                raise BamRefusal(msg)
             if "FASTQ:" in msg or "reads file" in msg:
                 raise ReadFileError(msg)
             raise (CapacityError if rc == -3 else RuntimeError)(f"bmh_aligner_run_files rc={rc}: " + msg)

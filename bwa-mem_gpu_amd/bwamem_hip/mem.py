@@ -4,7 +4,8 @@
 
 PREFIX is what `python -m bwamem_hip.index` (or `bwa index`) wrote.  Options are Aligner.set_options' list (-k -w -c -D -G -N -W -X -A -B
 -O -E -T -h -Q -U -m -R -a -M -Y -S -P -j -C -g -t -K ...) plus -p (the one file holds interleaved pairs), -o (the output file; default
-stdout), --long-reads (reads of up to 16 384 bases) and --device (the torch device, cuda:0).  An option that is not on that list is
+stdout), --long-reads (reads of up to 16 384 bases), --device (the torch device, cuda:0), --bam (the output is BAM: records converted and BGZF-
+compressed on the device; -o is unchanged, a name ending in .bam does not switch formats) and --bam-level 0|1 (stored, or LZ77 + dynamic Huffman; 1).  An option that is not on that list is
 refused by name.  Two input files imply pairs.  One plain, regular file is offered to Aligner.align_file first, which takes it when every
 record has one sequence line (its own counting pass decides, before anything is written); every other input goes through
 Aligner.align_files; the text is the same.  A refused file ends the command with status 1 and the library's message on stderr.
@@ -33,6 +34,7 @@ def _plain_regular(path: str) -> bool:
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     opts, pos, out_path, interleaved, long_reads, device = [], [], None, False, False, "cuda:0"
+    bam, bam_level = False, 1
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -40,6 +42,14 @@ def main(argv=None) -> int:
             interleaved = True
         elif a == "--long-reads":
             long_reads = True
+        elif a == "--bam":
+            bam = True
+        elif a == "--bam-level":
+            if i + 1 >= len(argv) or argv[i + 1] not in ("0", "1"):
+                print("[bwamem_hip.mem] option --bam-level needs 0 or 1", file=sys.stderr)
+                return 2
+            bam_level = int(argv[i + 1])
+            i += 1
         elif a in ("-o", "--device"):
             if i + 1 >= len(argv):
                 print(f"[bwamem_hip.mem] option {a} needs a value", file=sys.stderr)
@@ -77,16 +87,17 @@ def main(argv=None) -> int:
     out = open(out_path, "wb") if out_path is not None else sys.stdout.buffer
     try:
         paired = interleaved or mates is not None
+        fmt_kw = dict(fmt="bam", level=bam_level) if bam else {}
         done = False
         if mates is None and _plain_regular(reads):
             from .lib import ReadFileError
             try:
-                al.align_file(reads, out, paired=paired)
+                al.align_file(reads, out, paired=paired, **fmt_kw)
                 done = True
             except ReadFileError:                                    # (its counting pass refused the layout: nothing has been written)
                 pass
         if not done:
-            al.align_files(reads, mates, out=out, paired=paired)
+            al.align_files(reads, mates, out=out, paired=paired, **fmt_kw)
         out.flush()
     except (ValueError, NotImplementedError) as e:
         print(f"[bwamem_hip.mem] {e}", file=sys.stderr)

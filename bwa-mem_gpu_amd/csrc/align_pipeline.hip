@@ -32,6 +32,7 @@
 #include <vector>
 #include "bmh_internal.h"
 #include "pair_kernels.h"
+#include "bam_ws.h"
 
 namespace {
 
@@ -45,6 +46,8 @@ struct aligner_t {
 	std::string rg_id;             // the aligner's own copy of popt->rg_id (po.rg_id points into it): the caller's string need not outlive the call that created the aligner
 	uint32_t max_qlen = 768;       // the extension cap of the chain workspaces (bmh_aligner_set_max_qlen)
 	bmh_reseed_opt_t rs = {0, 1.5f, 10, 20};   // the seeding rounds (bmh_aligner_set_reseed; enable 0: the first round only)
+	int out_fmt = BMH_OUT_SAM, out_level = 1;  // what the sink receives (bmh_aligner_set_output): the records' text, or BGZF members of BAM records
+	std::vector<char> ctg_blob; std::vector<uint32_t> ctg_noff;      // the contig table as the BAM converter takes it
 };
 
 }   // namespace
@@ -144,8 +147,10 @@ struct lane_t {
 	// letters, offsets and names on host threads / the CIGAR and text kernels the host waits for): [0] reads, offsets, names H2D  [1] SAM text D2H
 	hipEvent_t ev_c[4] = {nullptr, nullptr, nullptr, nullptr}; double copy_ms[2] = {0, 0}; uint64_t copy_bytes[2] = {0, 0}; bool d2h_marked = false;
 	uint32_t host_tail = 0;                      // batches of the run whose region tail the device refused (BMH_ECAPACITY): the host forms took them
+	bmh_bam_ws_t *bam = nullptr;                 // BAM output: the converter's and the compressor's buffers
 	~lane_t()
 	{
+		if (bam) bmh_bam_ws_free(bam);
 		for (hipEvent_t e : ev_c) if (e) (void)hipEventDestroy(e);
 		if (sws) bmh_seed_ws_free(sws);
 		if (cws) bmh_chain_ws_free(cws);
@@ -247,6 +252,33 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 	if (total < 0) return (int)total;
 	RCK(Ln.d_text.need((size_t)total + 1)); RCK(R.text.need((size_t)total + 1));
 	RCK(bmh_sam_text_write(&po, &d, Ln.d_text_off.p, Ln.d_text.p, Ln.d_work.p, Ln.d_work.cap, Ln.st));
+	if (A.out_fmt == BMH_OUT_BAM) {
+		// BAM output: the text stays on the device -- text -> records -> members on the lane's stream; only the members cross to the host.  The batch's
+		// last member is short, so the batches stay independent and the file is their concatenation
+		RCK(bmh_sam_text_check(Ln.d_work.p, n, Ln.st));
+		R.text_len = 0; R.has_text = true;
+		if (!total) return BMH_OK;
+		if (!Ln.bam && !(Ln.bam = bmh_bam_ws_create())) return BMH_ENOMEM;
+		bmh_bam_out_t bo;
+		RCK(bmh_sam_to_bam_device(Ln.bam, Ln.d_text.p, (uint64_t)total, A.n_contigs, Ln.d_ctg_names.p, Ln.d_ctg_name_off.p, Ln.st, &bo));
+		if (bo.n_refused) {
+			const std::string nm = bmh_bam_record_name_device(Ln.bam, Ln.d_text.p, (uint64_t)total, bo.first_refused);
+			bmh_set_error("BAM output: read '%s': its SAM record cannot be written as BAM: %s", nm.c_str(), bmh_bam_status_name(bo.first_status));
+			return BMH_EINVAL;
+		}
+		const uint8_t *d_members = nullptr; uint64_t mb = 0;
+		RCK(bmh_bgzf_deflate_device(Ln.bam, bo.d_bam, bo.bam_bytes, A.out_level, Ln.st, &d_members, &mb));
+		RCK(R.text.need((size_t)mb + 1));
+		if (mb) {
+			LCK(hipEventRecord(Ln.ev_c[2], Ln.st));
+			LCK(hipMemcpyAsync(R.text.p, d_members, (size_t)mb, hipMemcpyDeviceToHost, Ln.st));
+			LCK(hipEventRecord(Ln.ev_c[3], Ln.st));
+			Ln.copy_bytes[1] += mb; Ln.d2h_marked = true;
+		}
+		LCK(hipStreamSynchronize(Ln.st));
+		R.text_len = mb;
+		return BMH_OK;
+	}
 	if (total) {
 		LCK(hipEventRecord(Ln.ev_c[2], Ln.st));
 		LCK(hipMemcpyAsync(R.text.p, Ln.d_text.p, (size_t)total, hipMemcpyDeviceToHost, Ln.st));
@@ -774,7 +806,18 @@ bmh_aligner_t *bmh_aligner_create(const bmh_index_t *idx, const uint8_t *pac, in
 	if (popt->rg_id) { A.rg_id = popt->rg_id; A.po.rg_id = A.rg_id.c_str(); }
 	if (pe) A.pe = *pe; else bmh_pe_opt_default(&A.pe);
 	A.co.contig_is_alt = A.has_alt ? A.alt.data() : nullptr; A.po.contig_is_alt = A.has_alt ? A.alt.data() : nullptr;
+	for (const std::string &s : A.names) { A.ctg_noff.push_back((uint32_t)A.ctg_blob.size()); A.ctg_blob.insert(A.ctg_blob.end(), s.begin(), s.end()); A.ctg_blob.push_back(0); }
+	A.ctg_noff.push_back((uint32_t)A.ctg_blob.size());
 	return h;
+}
+
+int bmh_aligner_set_output(bmh_aligner_t *h, int format, int level)
+{
+	if (!h) { bmh_set_error("bmh_aligner_set_output: null aligner"); return BMH_EINVAL; }
+	if (format != BMH_OUT_SAM && format != BMH_OUT_BAM) { bmh_set_error("bmh_aligner_set_output: format %d (BMH_OUT_SAM or BMH_OUT_BAM)", format); return BMH_EINVAL; }
+	if (format == BMH_OUT_BAM && level != 0 && level != 1) { bmh_set_error("bmh_aligner_set_output: level %d (0 or 1)", level); return BMH_EINVAL; }
+	h->a.out_fmt = format; h->a.out_level = level;
+	return BMH_OK;
 }
 
 int bmh_aligner_set_max_qlen(bmh_aligner_t *h, uint32_t cap)
@@ -930,6 +973,27 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 				if (!ok) { fail(BMH_EINVAL, bmh_last_error()); return; }
 				t_format += now_s() - t0;
 				const double ts0 = now_s();
+				if (A.out_fmt == BMH_OUT_BAM) {                         // the host formatter's text through the two host cores: the same members as the device's
+					std::string all;
+					for (const std::string &part : parts) all += part;
+					uint8_t *bam = nullptr, *mem = nullptr; uint64_t bb = 0, mb = 0; uint32_t *st = nullptr, nrec = 0;
+					int rc = bmh_sam_to_bam_host(all.data(), all.size(), A.n_contigs, A.ctg_blob.data(), A.ctg_noff.data(), n_threads, &bam, &bb, &st, &nrec);
+					if (rc == BMH_OK) for (uint32_t r = 0; r < nrec; ++r) if (st[r]) {
+						size_t a = 0;
+						for (uint32_t k = 0; k < r; ++k) a = all.find('\n', a) + 1;
+						size_t e = a;
+						while (e < all.size() && e - a < 254 && all[e] != '\t' && all[e] != '\n') ++e;
+						bmh_set_error("BAM output: read '%s': its SAM record cannot be written as BAM: %s", all.substr(a, e - a).c_str(), bmh_bam_status_name(st[r]));
+						rc = BMH_EINVAL; break;
+					}
+					if (rc == BMH_OK) rc = bmh_bgzf_deflate_host(bam, bb, A.out_level, n_threads, &mem, &mb);
+					bmh_free(bam); bmh_free(st);
+					if (rc != BMH_OK) { bmh_free(mem); fail(rc, bmh_last_error()); return; }
+					const int refused = mb ? sink(user, (const char *)mem, (size_t)mb) : 0;
+					bmh_free(mem);
+					if (refused) { fail(BMH_EINVAL, "the sink refused the text"); return; }
+					n_bytes += mb;
+				} else
 				for (const std::string &part : parts) {
 					if (part.empty()) continue;
 					if (sink(user, part.data(), part.size()) != 0) { fail(BMH_EINVAL, "the sink refused the text"); return; }

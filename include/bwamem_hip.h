@@ -773,6 +773,45 @@ int bmh_aligner_run_file(bmh_aligner_t *a, const char *path, uint64_t batch_base
 int bmh_aligner_run_files(bmh_aligner_t *a, const char *path1, const char *path2, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
                           bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats);
 
+/* ---- BAM output: SAM record lines -> BAM records -> BGZF members, on the device (csrc/bam_core.h, csrc/bam_kernels.hip, csrc/deflate_core.h,
+ * csrc/deflate_kernels.hip) or by the same two cores as plain C++ on host threads (no device needed).
+ *
+ * The contig table of both forms: the names NUL-terminated back to back, ctg_name_off [n_contigs + 1] (off[c + 1] - off[c] - 1 = the length of name c).
+ * bmh_sam_to_bam_device: the record lines d_text [text_bytes] (every line ends with '\n'; no header lines) on `stream`, which it waits for.  out->d_bam
+ * [bam_bytes]: the records back to back in line order; out->d_status [n_records]: 0, or the check that refused the line (bmh_bam_status_name says which:
+ * fewer than 11 fields, a name beyond 254 bytes, a bad CIGAR or more than 65 535 operations, a tag that is not XX:T:value with T of A i f Z H, SEQ and QUAL
+ * of different lengths, a last line without '\n', an unknown contig, a number outside its range, an integer tag outside [-2^31, 2^32), a float tag that is
+ * not [-+]?digits[.digits] of at most 15 digits, a B tag).  A refused line leaves no bytes in d_bam.  The arrays live in the work space until its next call.
+ * bmh_sam_to_bam_host: the same from host memory; *bam, *status are malloc'd (bmh_free).
+ * bmh_bgzf_deflate_device / _host: the bytes cut into pieces of at most 0xff00, every piece one BGZF member (level 0: a stored block; level 1: LZ77 and
+ * dynamic Huffman codes, or the stored block when that is not smaller), back to back; no bytes give no members.  The device and the host form give the
+ * same bytes.  bmh_deflate_blocks_host: the members in zeroed slots of 65 536 bytes each, sizes [n_members].  bmh_bgzf_eof: the 28-byte end-of-file member.
+ * bmh_bam_header: magic, l_text, the header text, n_ref and the references (malloc'd; bmh_free) -- uncompressed, on the host.
+ * bmh_aligner_set_output: what the runs that follow hand to the sink -- BMH_OUT_SAM (the default): the records' text; BMH_OUT_BAM: every batch's records
+ * as BGZF members of `level` (0 or 1), the last member of a batch short, so that header members + the batches in order + bmh_bgzf_eof are a BAM file.
+ * A record the converter refuses fails the run with a message naming the read. */
+typedef struct bmh_bam_ws bmh_bam_ws_t;
+typedef struct {
+	const uint8_t *d_bam; uint64_t bam_bytes;
+	const uint32_t *d_status; uint32_t n_records;
+	uint32_t n_refused, first_refused, first_status;       /* how many lines were refused; the first of them and its status */
+} bmh_bam_out_t;
+#define BMH_OUT_SAM 0
+#define BMH_OUT_BAM 1
+extern const uint8_t bmh_bgzf_eof[28];
+bmh_bam_ws_t *bmh_bam_ws_create(void);
+void bmh_bam_ws_free(bmh_bam_ws_t *ws);
+int bmh_sam_to_bam_device(bmh_bam_ws_t *ws, const char *d_text, uint64_t text_bytes, int n_contigs, const char *d_ctg_names, const uint32_t *d_ctg_name_off,
+                          void *stream, bmh_bam_out_t *out);
+int bmh_sam_to_bam_host(const char *text, uint64_t text_bytes, int n_contigs, const char *ctg_names, const uint32_t *ctg_name_off, int n_threads,
+                        uint8_t **bam, uint64_t *bam_bytes, uint32_t **status, uint32_t *n_records);
+const char *bmh_bam_status_name(uint32_t status);
+int bmh_bgzf_deflate_device(bmh_bam_ws_t *ws, const uint8_t *d_in, uint64_t n_bytes, int level, void *stream, const uint8_t **d_out, uint64_t *out_bytes);
+int bmh_bgzf_deflate_host(const uint8_t *in, uint64_t n_bytes, int level, int n_threads, uint8_t **out, uint64_t *out_bytes);
+int bmh_deflate_blocks_host(const uint8_t *in, uint64_t n_bytes, int level, uint8_t *slots, uint32_t *sizes, int n_threads);
+int bmh_bam_header(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, uint8_t **out, uint64_t *out_bytes);
+int bmh_aligner_set_output(bmh_aligner_t *a, int format, int level);
+
 #ifdef __cplusplus
 }
 #endif
