@@ -336,7 +336,7 @@ class Aligner:
     def header(self) -> str:
         return "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in self.contigs) + (getattr(self, "rg_line", "") + "\n" if getattr(self, "rg_line", "") else "")
 
-    def _bam_open(self, out, fmt: str, level: int) -> bool:
+    def _bam_open(self, out, fmt: str, level: int, sort: bool = False) -> bool:
         """fmt="bam": checks `out` and writes the header members (bmh_bam_header of header(), compressed by the host core); True for BAM"""
         if fmt not in ("sam", "bam"):
             raise ValueError(f"fmt {fmt!r}: sam or bam")
@@ -347,7 +347,10 @@ class Aligner:
         if not ("b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")):
             raise ValueError('fmt="bam" needs a binary file object')
         from .lib import bam_header, bgzf_compress
-        out.write(bgzf_compress(bam_header(self.header(), self.contigs), level, host=True))
+        # (sorted output says so in its header: the @HD line goes in front of header()'s text, here only)
+        hdr = bgzf_compress(bam_header(("@HD\tVN:1.6\tSO:coordinate\n" if sort else "") + self.header(), self.contigs), level, host=True)
+        self._bam_header_bytes = len(hdr)
+        out.write(hdr)
         return True
 
     def _bam_members(self, text: bytes, level: int) -> bytes:
@@ -360,10 +363,12 @@ class Aligner:
             raise BamRefusal(f"BAM output: read '{line.split(chr(9).encode())[0].decode(errors='replace')}': its SAM record cannot be written as BAM: {bam_status_name(int(st[bad[0]]))}")
         return bgzf_compress(bam, level)
 
-    def align_batch(self, names, seqs=None, id0: int = 0, paired: bool = False, as_bytes: bool = False, quals=None, comments=None, fmt: str = "sam", level: int = 1):
+    def align_batch(self, names, seqs=None, id0: int = 0, paired: bool = False, as_bytes: bool = False, quals=None, comments=None, fmt: str = "sam", level: int = 1, sort: bool = False):
         """SAM records of one batch of reads: a ReadSet, or (names, seqs) lists of str / ASCII uint8 arrays (quals, comments: lists as
         ReadSet.from_lists takes them); id0 = index of its first read in the run.  paired: interleaved pairs (gase_aln -p); the insert-size
         statistics are the batch's.  QUAL comes from the reads' qualities, '*' without; with -C the comments end the records."""
+        if sort:
+            raise ValueError("align_batch: sort=True sorts a file's records, and one batch is not a file (align_file / align_files)")
         if fmt != "sam":                                          # fmt="bam": the batch's records as BGZF members (bytes; no header, no end-of-file member)
             if fmt != "bam" or level not in (0, 1):
                 raise ValueError(f"fmt {fmt!r}, level {level}: sam or bam, 0 or 1")
@@ -537,11 +542,15 @@ class Aligner:
                 nat.set_max_qlen(EXT_LONG_MAX)
         nat.set_reseed(self.reseed if self.reseed.enable else None)
         nat.set_output(*getattr(self, "_out_fmt", ("sam", 1)))
+        if getattr(self, "_out_fmt", ("sam", 1))[0] == "bam_sorted":
+            nat.set_sort(*self._sort_knobs)
         return nat
 
-    def align_file(self, reads_fa: str, out, batch_reads: int = 0, paired: bool = False, chunk_bases: int = 0, fmt: str = "sam", level: int = 1) -> int:
-        if fmt != "sam":
-            return self._align_bam(lambda o: self.align_file(reads_fa, o, batch_reads=batch_reads, paired=paired, chunk_bases=chunk_bases), out, fmt, level)
+    def align_file(self, reads_fa: str, out, batch_reads: int = 0, paired: bool = False, chunk_bases: int = 0, fmt: str = "sam", level: int = 1,
+                   sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None) -> int:
+        if fmt != "sam" or sort or index is not None:
+            return self._align_bam(lambda o: self.align_file(reads_fa, o, batch_reads=batch_reads, paired=paired, chunk_bases=chunk_bases), out, fmt, level,
+                                   sort, index, sort_mem, sort_tmp, sort_window)
         """out: a text or binary file object.  Batches are cut the way the reference's bseq_read cuts them (src/bwa.c, called with
         chunk_size * n_threads = 10 Mbases per thread, or -K, src/fastmap.c:527): reads are added until the batch holds at least
         chunk_bases bases and an even number of reads -- in paired mode the insert-size statistics are those of the batch, so the
@@ -609,16 +618,24 @@ class Aligner:
             return n
         for b, e in zip(cuts[:-1], cuts[1:]):
             if e > b:
+                if getattr(self, "_out_fmt", ("sam", 1))[0] == "bam_sorted":
+                    raise NotImplementedError("sort=True needs the native pipeline (BMH_ALIGNER_NATIVE=0 and profile runs write batch after batch)")
                 if getattr(self, "_out_fmt", ("sam", 1))[0] == "bam":
                     out.write(self.align_batch(rs.slice(b, e), id0=b, paired=paired, fmt="bam", level=self._out_fmt[1]))
                     continue
                 out.write(self.align_batch(rs.slice(b, e), id0=b, paired=paired, as_bytes="view" if binary else False))   # (binary: the library's buffer, uncopied)
         return n
 
-    def _align_bam(self, run, out, fmt: str, level: int) -> int:
+    def _align_bam(self, run, out, fmt: str, level: int, sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None) -> int:
         """fmt="bam" of align_file / align_files: the header members, the batches' members (`run` with the native aligner's output switched; the Python
-        loop's batches converted here), the end-of-file member.  The file is written through a shim that drops the SAM header `run` writes first."""
+        loop's batches converted here), the end-of-file member.  The file is written through a shim that drops the SAM header `run` writes first.
+        sort=True: the batches become sorted runs and the members are those of the coordinate-sorted file, written at the end of the input; `index` (a path or
+        a binary file object) receives its .bai."""
         from .lib import bgzf_eof
+        if sort and fmt != "bam":
+            raise ValueError(f'sort=True needs fmt="bam" (fmt {fmt!r})')
+        if index is not None and not sort:
+            raise ValueError("index needs sort=True: only a coordinate-sorted file has a .bai")
         if fmt != "bam":
             raise ValueError(f"fmt {fmt!r}: sam or bam")
         if level not in (0, 1):
@@ -634,11 +651,15 @@ class Aligner:
             def write(self, b):
                 if self.first:                                    # the SAM header text: the BAM header goes in its place
                     self.first = False
-                    al._bam_open(out, "bam", level)
+                    al._bam_open(out, "bam", level, sort)
                     return
                 out.write(b)
         shim = _Shim()
-        self._out_fmt = ("bam", level)
+        if sort:
+            if os.environ.get("BMH_ALIGNER_NATIVE", "1") == "0" or self.profile:   # (before anything is switched: a refused call leaves the aligner as it was)
+                raise NotImplementedError("sort=True needs the native pipeline (BMH_ALIGNER_NATIVE=0 and profile runs write batch after batch)")
+            self._sort_knobs = (int(sort_mem or 0), sort_tmp, int(sort_window or 0))
+        self._out_fmt = ("bam_sorted" if sort else "bam", level)
         try:
             n = run(shim)
         finally:
@@ -647,18 +668,30 @@ class Aligner:
             if nat is not None:
                 nat.set_output("sam", 1)
         if shim.first:                                            # (no reads: nothing was written)
-            self._bam_open(out, "bam", level)
+            self._bam_open(out, "bam", level, sort)
         out.write(bgzf_eof())
+        if index is not None:
+            nat = self._native_aligner() if n == 0 else self._native
+            if n == 0:                                            # (no run was made: the index of a file without records)
+                nat.set_output("bam_sorted", level); nat.set_output("sam", 1)
+            bai = nat.sort_index(self._bam_header_bytes)
+            if hasattr(index, "write"):
+                index.write(bai)
+            else:
+                with open(index, "wb") as f:
+                    f.write(bai)
         return n
 
-    def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1) -> int:
+    def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
+                    sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None) -> int:
         """align_file for the files users have (bmh_aligner_run_files): `reads` (and `mates`: the second file of a pair, which implies paired) may be
         multi-line FASTA or FASTQ, plain, gzip or BGZF, a regular file or a pipe.  Batches are cut by align_file's rules (-t, -K, the 150 Mbase floor for
         single-end runs), so the text equals align_file's on the single-line interleaved file of the same reads.  Returns the number of reads."""
         if out is None:
             raise ValueError("align_files: out (a text or binary file object) is required")
-        if fmt != "sam":
-            return self._align_bam(lambda o: self.align_files(reads, mates, out=o, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads), out, fmt, level)
+        if fmt != "sam" or sort or index is not None:
+            return self._align_bam(lambda o: self.align_files(reads, mates, out=o, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads), out, fmt, level,
+                                   sort, index, sort_mem, sort_tmp, sort_window)
         binary = "b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")
         paired = bool(paired or mates is not None)
         cb = 0

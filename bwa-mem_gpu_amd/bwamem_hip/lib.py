@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = [
     "bmh_bgzf_scan", "bmh_inflate_members_device", "bmh_inflate_members_host", "bmh_inflate_status_name", "bmh_bgzf_inflate",
     "bmh_bam_ws_create", "bmh_bam_ws_free", "bmh_sam_to_bam_device", "bmh_sam_to_bam_host", "bmh_bam_status_name", "bmh_bgzf_deflate_device", "bmh_bgzf_deflate_host",
     "bmh_deflate_blocks_host", "bmh_bam_header", "bmh_aligner_set_output",
+    "bmh_bam_sort_device", "bmh_bam_sort_host", "bmh_bam_sorted_file_device", "bmh_bam_sorted_file_host", "bmh_aligner_set_sort", "bmh_aligner_sort_index",
 ]
 
 
@@ -359,6 +360,63 @@ def bam_header(header_text: str, contigs) -> bytes:
         L.bmh_free(out)
 
 
+# ---- coordinate-sorted BAM and its BAI index (csrc/bam_sort_core.h, csrc/bam_sort_kernels.hip, csrc/bam_sort_host.cpp)
+OUT_BAM_SORTED = 2          # BMH_OUT_BAM_SORTED
+
+
+def bam_sort(records: bytes, host: bool = False) -> bytes:
+    """bmh_bam_sort_device (host=True: bmh_bam_sort_host, std::stable_sort, no device needed): a stream of BAM records in coordinate order -- `samtools sort`'s
+    key, equal keys in the order they came in.  A stream that is not a whole number of records raises ValueError."""
+    L = load_library()
+    records = bytes(records)
+    L.bmh_free.argtypes = [C.c_void_p]
+    out = C.c_void_p()
+    if host:
+        L.bmh_bam_sort_host.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]
+        rc = L.bmh_bam_sort_host(records, len(records), C.byref(out))
+    else:
+        import torch
+        L.bmh_bam_sort_device.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]
+        rc = L.bmh_bam_sort_device(records, len(records), torch.cuda.current_stream().cuda_stream, C.byref(out))
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_sort: " + _err(L))
+    try:
+        return C.string_at(out.value, len(records)) if records else b""
+    finally:
+        L.bmh_free(out)
+
+
+def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False) -> tuple:
+    """bmh_bam_sorted_file_device (host=True: _host): (the complete sorted BAM file -- header members, the records in coordinate order in windows of `window`
+    records (0: about 64 MiB), the end-of-file member --, its .bai index).  contigs: (name, length) pairs; both forms give the same bytes."""
+    L = load_library()
+    records = bytes(records)
+    L.bmh_free.argtypes = [C.c_void_p]
+    names = (C.c_char_p * max(len(contigs), 1))(*[c[0].encode() for c in contigs])
+    lens = np.ascontiguousarray([c[1] for c in contigs] or [0], dtype=np.int64)
+    if ((lens < 0) | (lens >= 1 << 29)).any():
+        raise ValueError("bam_sorted_file: a BAI index holds contigs below 2^29 bases (CSI is not written)")
+    lens = lens.astype(np.int32)
+    bam, bai, nb, ni = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+    head = [header_text.encode(), len(contigs), names, lens.ctypes.data, records, len(records), int(level), int(window)]
+    tail = [C.byref(bam), C.byref(nb), C.byref(bai), C.byref(ni)]
+    sig = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_uint32]
+    out = [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p]
+    if host:
+        L.bmh_bam_sorted_file_host.argtypes = sig + out
+        rc = L.bmh_bam_sorted_file_host(*head, *tail)
+    else:
+        import torch
+        L.bmh_bam_sorted_file_device.argtypes = sig + [C.c_void_p] + out
+        rc = L.bmh_bam_sorted_file_device(*head, torch.cuda.current_stream().cuda_stream, *tail)
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_sorted_file: " + _err(L))
+    try:
+        return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)
+    finally:
+        L.bmh_free(bam); L.bmh_free(bai)
+
+
 def load_reads_files(path1: str, path2: str | None = None, comments: bool = False, host: bool = False, n_threads: int = 0) -> dict:
     """bmh_reads_load_files: one or two read files of any shape (multi-line records, gzip / BGZF, pipes) as load_reads gives them; path2: the mates (reads 2i
     and 2i+1).  host=True: the host walker alone (no device).  A refused file raises ReadFileError; when one file ends before the other its `partial`
@@ -442,8 +500,29 @@ class NativeAligner:
         """bmh_aligner_set_output: what the runs that follow hand to `write` -- "sam": the records' text; "bam": BGZF members of BAM records"""
         L = load_library()
         L.bmh_aligner_set_output.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        if fmt not in ("sam", "bam") or L.bmh_aligner_set_output(self.handle, OUT_BAM if fmt == "bam" else OUT_SAM, int(level)) != 0:
-            raise ValueError("bmh_aligner_set_output: " + (_err(L) if fmt in ("sam", "bam") else f"format {fmt!r} (sam or bam)"))
+        codes = {"sam": OUT_SAM, "bam": OUT_BAM, "bam_sorted": OUT_BAM_SORTED}      # ("bam_sorted": sorted runs, merged at the end of the input)
+        if fmt not in codes or L.bmh_aligner_set_output(self.handle, codes[fmt], int(level)) != 0:
+            raise ValueError("bmh_aligner_set_output: " + (_err(L) if fmt in codes else f"format {fmt!r} (sam or bam)"))
+
+    def set_sort(self, mem_bytes: int = 0, tmp_dir: "str | None" = None, window_records: int = 0) -> None:
+        """bmh_aligner_set_sort: the sorted output's run store budget (0: 4 GiB), its directory (None: $TMPDIR, else /tmp) and window (0: about 64 MiB)"""
+        L = load_library()
+        L.bmh_aligner_set_sort.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint32]
+        if L.bmh_aligner_set_sort(self.handle, int(mem_bytes), os.fsencode(tmp_dir) if tmp_dir is not None else None, int(window_records)) != 0:
+            raise ValueError("bmh_aligner_set_sort: " + _err(L))
+
+    def sort_index(self, base_offset: int) -> bytes:
+        """bmh_aligner_sort_index: the .bai bytes of the last sorted run; base_offset: the bytes written before the sink's first (the header members)"""
+        L = load_library()
+        L.bmh_aligner_sort_index.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), _u64p]
+        L.bmh_free.argtypes = [C.c_void_p]
+        out, n = C.c_void_p(), C.c_uint64()
+        if L.bmh_aligner_sort_index(self.handle, int(base_offset), C.byref(out), C.byref(n)) != 0:
+            raise ValueError("bmh_aligner_sort_index: " + _err(L))
+        try:
+            return C.string_at(out.value, n.value)
+        finally:
+            L.bmh_free(out)
 
     def host_tail_batches(self) -> int:
         """batches of the last run whose region tail the device refused (the host forms took them)"""

@@ -5,7 +5,10 @@
 PREFIX is what `python -m bwamem_hip.index` (or `bwa index`) wrote.  Options are Aligner.set_options' list (-k -w -c -D -G -N -W -X -A -B
 -O -E -T -h -Q -U -m -R -a -M -Y -S -P -j -C -g -t -K ...) plus -p (the one file holds interleaved pairs), -o (the output file; default
 stdout), --long-reads (reads of up to 16 384 bases), --device (the torch device, cuda:0), --bam (the output is BAM: records converted and BGZF-
-compressed on the device; -o is unchanged, a name ending in .bam does not switch formats) and --bam-level 0|1 (stored, or LZ77 + dynamic Huffman; 1).  An option that is not on that list is
+compressed on the device; -o is unchanged, a name ending in .bam does not switch formats), --bam-level 0|1 (stored, or LZ77 + dynamic Huffman; 1),
+--sort (implies --bam: the records in coordinate order, `samtools sort`'s, sorted on the device; with -o PATH the BAI index goes to PATH.bai, --index PATH
+names it otherwise, and on stdout without --index none is written), --sort-mem BYTES (records kept in host memory before the sorted runs spill to a temporary
+file; 4 GiB) and --sort-tmp DIR (where that file lives; $TMPDIR, else /tmp).  An option that is not on that list is
 refused by name.  Two input files imply pairs.  One plain, regular file is offered to Aligner.align_file first, which takes it when every
 record has one sequence line (its own counting pass decides, before anything is written); every other input goes through
 Aligner.align_files; the text is the same.  A refused file ends the command with status 1 and the library's message on stderr.
@@ -35,6 +38,7 @@ def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     opts, pos, out_path, interleaved, long_reads, device = [], [], None, False, False, "cuda:0"
     bam, bam_level = False, 1
+    sort, index_path, sort_mem, sort_tmp = False, None, None, None
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -50,12 +54,23 @@ def main(argv=None) -> int:
                 return 2
             bam_level = int(argv[i + 1])
             i += 1
-        elif a in ("-o", "--device"):
+        elif a == "--sort":
+            sort = bam = True
+        elif a in ("-o", "--device", "--index", "--sort-mem", "--sort-tmp"):
             if i + 1 >= len(argv):
                 print(f"[bwamem_hip.mem] option {a} needs a value", file=sys.stderr)
                 return 2
             if a == "-o":
                 out_path = argv[i + 1]
+            elif a == "--index":
+                index_path = argv[i + 1]
+            elif a == "--sort-tmp":
+                sort_tmp = argv[i + 1]
+            elif a == "--sort-mem":
+                if not argv[i + 1].isdigit() or int(argv[i + 1]) < 1:
+                    print("[bwamem_hip.mem] option --sort-mem needs a number of bytes", file=sys.stderr)
+                    return 2
+                sort_mem = int(argv[i + 1])
             else:
                 device = argv[i + 1]
             i += 1
@@ -77,6 +92,11 @@ def main(argv=None) -> int:
         print(__doc__, file=sys.stderr)
         return 2
     prefix, reads, mates = pos[0], pos[1], pos[2] if len(pos) == 3 else None
+    if not sort and (index_path is not None or sort_mem is not None or sort_tmp is not None):
+        print("[bwamem_hip.mem] --index, --sort-mem and --sort-tmp need --sort", file=sys.stderr)
+        return 2
+    if sort and index_path is None and out_path is not None:
+        index_path = out_path + ".bai"
     from .aligner import Aligner
     try:
         al = Aligner(prefix, device=device, long_reads=long_reads)
@@ -88,6 +108,8 @@ def main(argv=None) -> int:
     try:
         paired = interleaved or mates is not None
         fmt_kw = dict(fmt="bam", level=bam_level) if bam else {}
+        if sort:
+            fmt_kw.update(sort=True, index=index_path, sort_mem=sort_mem, sort_tmp=sort_tmp)
         done = False
         if mates is None and _plain_regular(reads):
             from .lib import ReadFileError

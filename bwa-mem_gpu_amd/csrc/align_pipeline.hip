@@ -33,6 +33,7 @@
 #include "bmh_internal.h"
 #include "pair_kernels.h"
 #include "bam_ws.h"
+#include "bam_sort.h"
 
 namespace {
 
@@ -122,6 +123,7 @@ struct result_t {
 	const bmh_read_set_t *rs = nullptr; int64_t id0 = 0; void *token = nullptr;      // the read set the batch [b0, b0 + n) lies in, the index of its first read in the run, the source's handle
 	hbuf_t<int32_t> fin, aln, slot32; hbuf_t<uint32_t> opr, off, packed;
 	hbuf_t<char> text; uint64_t text_len = 0; bool has_text = false;     // the text written on the device (no formatting on the host)
+	hbuf_t<uint64_t> skeys, soff; uint32_t n_rec = 0;                   // sorted BAM: text holds the batch's records in order; their keys and offsets [n_rec + 1]
 	std::vector<int64_t> slot;                   // (host selection only; empty: slot32)
 	std::vector<int32_t> h_rec, unflag;          // pairs
 	std::vector<uint32_t> dev_index;             // record -> its place in the lane's d_fin when that is not the record's own index (ALT indexes); empty: identity
@@ -148,9 +150,11 @@ struct lane_t {
 	hipEvent_t ev_c[4] = {nullptr, nullptr, nullptr, nullptr}; double copy_ms[2] = {0, 0}; uint64_t copy_bytes[2] = {0, 0}; bool d2h_marked = false;
 	uint32_t host_tail = 0;                      // batches of the run whose region tail the device refused (BMH_ECAPACITY): the host forms took them
 	bmh_bam_ws_t *bam = nullptr;                 // BAM output: the converter's and the compressor's buffers
+	bsr_dev_t *bsr = nullptr;                    // sorted BAM output: the sort's, the gather's and the index pass's buffers
 	~lane_t()
 	{
 		if (bam) bmh_bam_ws_free(bam);
+		if (bsr) bsr_dev_free(bsr);
 		for (hipEvent_t e : ev_c) if (e) (void)hipEventDestroy(e);
 		if (sws) bmh_seed_ws_free(sws);
 		if (cws) bmh_chain_ws_free(cws);
@@ -252,11 +256,11 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 	if (total < 0) return (int)total;
 	RCK(Ln.d_text.need((size_t)total + 1)); RCK(R.text.need((size_t)total + 1));
 	RCK(bmh_sam_text_write(&po, &d, Ln.d_text_off.p, Ln.d_text.p, Ln.d_work.p, Ln.d_work.cap, Ln.st));
-	if (A.out_fmt == BMH_OUT_BAM) {
+	if (A.out_fmt == BMH_OUT_BAM || A.out_fmt == BMH_OUT_BAM_SORTED) {
 		// BAM output: the text stays on the device -- text -> records -> members on the lane's stream; only the members cross to the host.  The batch's
 		// last member is short, so the batches stay independent and the file is their concatenation
 		RCK(bmh_sam_text_check(Ln.d_work.p, n, Ln.st));
-		R.text_len = 0; R.has_text = true;
+		R.text_len = 0; R.has_text = true; R.n_rec = 0;
 		if (!total) return BMH_OK;
 		if (!Ln.bam && !(Ln.bam = bmh_bam_ws_create())) return BMH_ENOMEM;
 		bmh_bam_out_t bo;
@@ -265,6 +269,27 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 			const std::string nm = bmh_bam_record_name_device(Ln.bam, Ln.d_text.p, (uint64_t)total, bo.first_refused);
 			bmh_set_error("BAM output: read '%s': its SAM record cannot be written as BAM: %s", nm.c_str(), bmh_bam_status_name(bo.first_status));
 			return BMH_EINVAL;
+		}
+		if (A.out_fmt == BMH_OUT_BAM_SORTED) {
+			// sorted output: records -> keys -> sort -> gather on the lane's stream; the run (records, keys, offsets) crosses uncompressed, the writer stores it
+			if (!Ln.bsr && !(Ln.bsr = bsr_dev_create())) return BMH_ENOMEM;
+			const uint8_t *ds = nullptr; const uint64_t *dk = nullptr, *dso = nullptr;
+			const uint32_t nrec = bo.n_records;
+			RCK(bsr_sort_run_device(Ln.bsr, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &ds, &dk, &dso));
+			RCK(R.text.need((size_t)bo.bam_bytes + 1)); RCK(R.skeys.need((size_t)nrec + 1)); RCK(R.soff.need((size_t)nrec + 2));
+			LCK(hipEventRecord(Ln.ev_c[2], Ln.st));
+			if (bo.bam_bytes) LCK(hipMemcpyAsync(R.text.p, ds, (size_t)bo.bam_bytes, hipMemcpyDeviceToHost, Ln.st));
+			if (nrec) LCK(hipMemcpyAsync(R.skeys.p, dk, 8 * (size_t)nrec, hipMemcpyDeviceToHost, Ln.st));
+			LCK(hipMemcpyAsync(R.soff.p, dso, 8 * ((size_t)nrec + 1), hipMemcpyDeviceToHost, Ln.st));
+			LCK(hipEventRecord(Ln.ev_c[3], Ln.st));
+			Ln.copy_bytes[1] += bo.bam_bytes + 16ull * nrec; Ln.d2h_marked = true;
+			LCK(hipStreamSynchronize(Ln.st));
+			if (R.soff.p[nrec] != bo.bam_bytes) {                 // (the gather skips a record whose offsets lie outside the buffers: the scan of the sizes shows it)
+				bmh_set_error("sorted BAM: internal error: the sorted run holds %llu bytes, the batch's records %llu", (unsigned long long)R.soff.p[nrec], (unsigned long long)bo.bam_bytes);
+				return BMH_EINVAL;
+			}
+			R.text_len = bo.bam_bytes; R.n_rec = nrec;
+			return BMH_OK;
 		}
 		const uint8_t *d_members = nullptr; uint64_t mb = 0;
 		RCK(bmh_bgzf_deflate_device(Ln.bam, bo.d_bam, bo.bam_bytes, A.out_level, Ln.st, &d_members, &mb));
@@ -785,6 +810,7 @@ struct bmh_aligner {
 	std::vector<std::string> parts;
 	int dev = -1;
 	uint64_t host_tail_batches = 0;                      // of the last run (bmh_aligner_host_tail_batches)
+	bsr_store_t store; bsr_index_t sort_ix; uint32_t sort_window = 0;      // sorted BAM output: the runs of the run in progress, the index of the last one, the window
 };
 
 bmh_aligner_t *bmh_aligner_create(const bmh_index_t *idx, const uint8_t *pac, int64_t l_pac, int n_contigs, const char *const *contig_names,
@@ -814,8 +840,9 @@ bmh_aligner_t *bmh_aligner_create(const bmh_index_t *idx, const uint8_t *pac, in
 int bmh_aligner_set_output(bmh_aligner_t *h, int format, int level)
 {
 	if (!h) { bmh_set_error("bmh_aligner_set_output: null aligner"); return BMH_EINVAL; }
-	if (format != BMH_OUT_SAM && format != BMH_OUT_BAM) { bmh_set_error("bmh_aligner_set_output: format %d (BMH_OUT_SAM or BMH_OUT_BAM)", format); return BMH_EINVAL; }
-	if (format == BMH_OUT_BAM && level != 0 && level != 1) { bmh_set_error("bmh_aligner_set_output: level %d (0 or 1)", level); return BMH_EINVAL; }
+	if (format != BMH_OUT_SAM && format != BMH_OUT_BAM && format != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_output: format %d (BMH_OUT_SAM, BMH_OUT_BAM or BMH_OUT_BAM_SORTED)", format); return BMH_EINVAL; }
+	if (format != BMH_OUT_SAM && level != 0 && level != 1) { bmh_set_error("bmh_aligner_set_output: level %d (0 or 1)", level); return BMH_EINVAL; }
+	if (format == BMH_OUT_BAM_SORTED) { h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), "sorted BAM output")); }
 	h->a.out_fmt = format; h->a.out_level = level;
 	return BMH_OK;
 }
@@ -833,6 +860,27 @@ int bmh_aligner_set_reseed(bmh_aligner_t *h, const bmh_reseed_opt_t *opt)
 	if (!h) { bmh_set_error("bmh_aligner_set_reseed: null aligner"); return BMH_EINVAL; }
 	if (opt) h->a.rs = *opt;
 	else { bmh_reseed_opt_default(&h->a.rs); h->a.rs.enable = 0; }
+	return BMH_OK;
+}
+
+int bmh_aligner_set_sort(bmh_aligner_t *h, uint64_t mem_bytes, const char *tmp_dir, uint32_t window_records)
+{
+	if (!h) { bmh_set_error("bmh_aligner_set_sort: null aligner"); return BMH_EINVAL; }
+	h->store.mem_bytes = mem_bytes ? mem_bytes : 4ull << 30; h->store.tmp_dir = tmp_dir ? tmp_dir : ""; h->sort_window = window_records;
+	return BMH_OK;
+}
+
+int bmh_aligner_sort_index(bmh_aligner_t *h, uint64_t base_offset, uint8_t **bai, uint64_t *bai_bytes)
+{
+	if (!h || !bai || !bai_bytes) { bmh_set_error("bmh_aligner_sort_index: null argument"); return BMH_EINVAL; }
+	*bai = nullptr; *bai_bytes = 0;
+	if (h->sort_ix.lin.empty()) { bmh_set_error("bmh_aligner_sort_index: no sorted run has been made (bmh_aligner_set_output with BMH_OUT_BAM_SORTED comes first)"); return BMH_EINVAL; }
+	if (!h->sort_ix.valid) { bmh_set_error("bmh_aligner_sort_index: the last sorted run failed before its file was complete: there is no index of it"); return BMH_EINVAL; }
+	std::string s; h->sort_ix.bai(base_offset, s);
+	uint8_t *o = (uint8_t *)malloc(s.size() + 1);
+	if (!o) { bmh_set_error("bmh_aligner_sort_index: out of memory"); return BMH_ENOMEM; }
+	memcpy(o, s.data(), s.size());
+	*bai = o; *bai_bytes = s.size();
 	return BMH_OK;
 }
 
@@ -899,6 +947,8 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 	}
 	for (auto &ln : h->lanes) { for (double &v : ln->t) v = 0.0; ln->copy_ms[0] = ln->copy_ms[1] = 0.0; ln->copy_bytes[0] = ln->copy_bytes[1] = 0; ln->host_tail = 0; }
 	h->host_tail_batches = 0;
+	const bool sorted = A.out_fmt == BMH_OUT_BAM_SORTED;
+	if (sorted) { h->store.clear(); RCK(h->sort_ix.init(A.n_contigs, A.len.data(), fn)); h->sort_ix.valid = false; }      // (valid again once the merge has written the whole file)
 	auto worker = [&](int lane_index) {
 		if (hipSetDevice(dev) != hipSuccess) { fail(BMH_ENODEV, "hipSetDevice failed in a worker thread"); return; }
 		lane_t &Ln = *h->lanes[(size_t)lane_index];
@@ -950,6 +1000,9 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 			const bmh_read_set_t *rs = R->rs;
 			if (R->n && R->has_text) {                               // written on the device: nothing to format
 				const double ts0 = now_s();
+				if (sorted) {                                          // a sorted run: kept until the end of the input
+					if (R->n_rec) { const int rc = h->store.append((const uint8_t *)R->text.p, R->text_len, R->skeys.p, R->soff.p, R->n_rec); if (rc != BMH_OK) { fail(rc, bmh_last_error()); return; } }
+				} else
 				if (R->text_len) { if (sink(user, R->text.p, (size_t)R->text_len) != 0) { fail(BMH_EINVAL, "the sink refused the text"); return; } n_bytes += R->text_len; }
 				if (trace) fprintf(stderr, "[aligner] writer batch %u: text of the device, sink %.1f .. %.1f ms\n", b, (ts0 - t_start) * 1e3, (now_s() - t_start) * 1e3);
 			} else if (R->n) {
@@ -973,7 +1026,7 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 				if (!ok) { fail(BMH_EINVAL, bmh_last_error()); return; }
 				t_format += now_s() - t0;
 				const double ts0 = now_s();
-				if (A.out_fmt == BMH_OUT_BAM) {                         // the host formatter's text through the two host cores: the same members as the device's
+				if (A.out_fmt == BMH_OUT_BAM || sorted) {               // the host formatter's text through the two host cores: the same members as the device's
 					std::string all;
 					for (const std::string &part : parts) all += part;
 					uint8_t *bam = nullptr, *mem = nullptr; uint64_t bb = 0, mb = 0; uint32_t *st = nullptr, nrec = 0;
@@ -986,6 +1039,16 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 						bmh_set_error("BAM output: read '%s': its SAM record cannot be written as BAM: %s", all.substr(a, e - a).c_str(), bmh_bam_status_name(st[r]));
 						rc = BMH_EINVAL; break;
 					}
+					if (rc == BMH_OK && sorted) {                        // the host form of the sort: the same run as the device's
+						std::vector<uint64_t> off, keys, soff(1, 0); std::vector<uint32_t> ord; std::vector<uint8_t> srt;
+						rc = bsr_walk(bam, bb, A.n_contigs, off, fn);
+						if (rc == BMH_OK) {
+							bsr_sort_host(bam, off, keys, ord);
+							srt.reserve((size_t)bb + 1);
+							for (uint32_t i : ord) { srt.insert(srt.end(), bam + off[i], bam + off[i + 1]); soff.push_back(srt.size()); }
+							if (!ord.empty()) rc = h->store.append(srt.data(), bb, keys.data(), soff.data(), ord.size());
+						}
+					} else
 					if (rc == BMH_OK) rc = bmh_bgzf_deflate_host(bam, bb, A.out_level, n_threads, &mem, &mb);
 					bmh_free(bam); bmh_free(st);
 					if (rc != BMH_OK) { bmh_free(mem); fail(rc, bmh_last_error()); return; }
@@ -1019,7 +1082,24 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 	if (src.release) for (auto &kv : done) if (kv.second) src.release(kv.second->token);       // (a failed run: what was waiting for the writer)
 	n_results = (int)pool.size();                                   // (after a failed run the results that were in flight are gone)
 	for (auto &ln : h->lanes) h->host_tail_batches += ln->host_tail;
-	if (first_rc != BMH_OK) { bmh_set_error("%s", first_err.c_str()); return first_rc; }
+	if (first_rc != BMH_OK) { h->store.clear(); bmh_set_error("%s", first_err.c_str()); return first_rc; }
+	if (sorted) {
+		// the end of the input: every run's keys sorted once more, the file written window by window (csrc/bam_sort_kernels.hip), on the first lane's stream
+		struct out_t { bmh_sam_sink_t sink; void *user; uint64_t n; } o = {sink, user, 0};
+		auto fwd = [](void *u, const char *b, size_t n) { out_t *p = (out_t *)u; p->n += n; return p->sink(p->user, b, n); };
+		lane_t &L0 = *h->lanes[0];
+		int rc = BMH_OK;
+		if (!L0.bam && !(L0.bam = bmh_bam_ws_create())) rc = BMH_ENOMEM;
+		if (rc == BMH_OK && !L0.bsr && !(L0.bsr = bsr_dev_create())) rc = BMH_ENOMEM;
+		const double tm0 = now_s();
+		if (rc == BMH_OK) rc = bsr_merge_device(L0.bsr, L0.bam, h->store, h->sort_window, A.out_level, L0.st, h->sort_ix, fwd, &o);
+		if (trace) fprintf(stderr, "[aligner] sorted output: %zu runs (%llu spilled) merged in %.1f ms\n", h->store.runs.size(), (unsigned long long)h->store.spilled, (now_s() - tm0) * 1e3);
+		t_format += now_s() - tm0;
+		h->store.clear();
+		if (rc != BMH_OK) return rc;
+		h->sort_ix.valid = true;
+		n_bytes += o.n;
+	}
 	if (stats) {
 		stats->n_reads = n_reads_total; stats->n_bytes = n_bytes; stats->n_batches = n_written; stats->n_lanes = n_lanes;
 		stats->seconds = now_s() - t_start; stats->format_seconds = t_format;

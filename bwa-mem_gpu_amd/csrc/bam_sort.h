@@ -1,0 +1,63 @@
+// Sorted BAM output, internal: the index being built over a file's windows, the run store, and what csrc/bam_sort_kernels.hip offers csrc/align_pipeline.hip.
+#pragma once
+#include <stdint.h>
+#include <string>
+#include <vector>
+#include "bmh_internal.h"
+#include "bam_sort_core.h"
+
+typedef int (*bsr_sink_t)(void *user, const char *bytes, size_t n);
+
+// a chunk's first record: its reference (-1: the group without one), bin and virtual offset (relative to the sink's first byte)
+struct bsr_head_t { int32_t ref; uint32_t bin; uint64_t beg; };
+
+// The index of one file, filled window after window (heads in file order; lin, counts: on the host form directly, on the device form copied back at the end)
+struct bsr_index_t {
+	int n_ref = 0;
+	std::vector<uint32_t> n_win; std::vector<uint64_t> lin_off;    // windows of every reference, their places in lin [n_ref + 1]
+	std::vector<uint64_t> lin;                                     // smallest begin offset per window, ~0: none
+	std::vector<uint64_t> counts;                                  // [2 r]: mapped, [2 r + 1]: unmapped records of reference r; [2 n_ref]: records without one
+	std::vector<bsr_head_t> heads;
+	uint64_t file_pos = 0;                                         // bytes handed to the sink so far
+	bool valid = false;                                            // the index of a whole file (init: of one without records); false while a run builds it and after it failed
+	int init(int n_contigs, const int32_t *contig_len, const char *fn);
+	// one window on the host: its n records recs [soff[n]], its members' offsets moff [n_members + 1]
+	void window_host(const uint8_t *recs, const uint64_t *soff, uint32_t n, const uint64_t *moff);
+	// the .bai bytes; base_offset: bytes in the file before the sink's first
+	void bai(uint64_t base_offset, std::string &out) const;
+};
+
+// Sorted runs kept until the end of the input: the records in host memory up to mem_bytes, beyond that in one unnamed temporary file; keys and offsets
+// (16 bytes per record) always in memory
+struct bsr_run_t { uint64_t n = 0, bytes = 0; std::vector<uint64_t> keys, off; uint8_t *mem = nullptr; int64_t file_at = -1; };
+struct bsr_store_t {
+	uint64_t mem_bytes = 4ull << 30, used = 0, spilled = 0; std::string tmp_dir; int fd = -1; uint64_t file_bytes = 0;
+	std::vector<bsr_run_t> runs;
+	~bsr_store_t() { clear(); }
+	void clear();
+	int append(const uint8_t *recs, uint64_t bytes, const uint64_t *keys, const uint64_t *off, uint64_t n);
+	int read(const bsr_run_t &r, uint64_t a, uint64_t b, uint8_t *dst) const;       // bytes [a, b) of the run's records
+};
+
+// csrc/bam_sort_host.cpp: records (walked, checked) -> sorted order on the host
+int bsr_walk(const uint8_t *recs, uint64_t n_bytes, int n_ref, std::vector<uint64_t> &off, const char *fn);
+void bsr_sort_host(const uint8_t *recs, const std::vector<uint64_t> &off, std::vector<uint64_t> &keys, std::vector<uint32_t> &ord);
+
+// csrc/bam_sort_kernels.hip
+struct bsr_dev_t;                                                  // device buffers of the sort, the gather and the index pass; kept between calls
+bsr_dev_t *bsr_dev_create(void);
+void bsr_dev_free(bsr_dev_t *d);
+// a batch's records d_recs with offsets d_off [n + 1] (device) -> the sorted run: *d_sorted (total bytes), *d_keys [n], *d_soff [n + 1], all in d until its next call
+int bsr_sort_run_device(bsr_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream,
+                        const uint8_t **d_sorted, const uint64_t **d_keys, const uint64_t **d_soff);
+// every run's keys (host) -> ord [n]: the records' global ordinals (run after run) in sorted order
+int bsr_sort_keys_device(bsr_dev_t *d, const uint64_t *keys, uint64_t n, void *stream, uint32_t *ord);
+// one window of the final file.  src (host, pinned or not) [src_bytes]: the records of the window as the runs hold them; src_off / size [n] (host): record j of the
+// window in src.  The records are gathered into order, compressed (ws), indexed (ix: heads appended; lin and counts stay on the device until bsr_index_finish) and
+// the members handed to the sink
+int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64_t src_bytes, const uint64_t *src_off, const uint32_t *size, uint32_t n, int level,
+                      void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user);
+// every run of the store -> the record members of the sorted file (to the sink, in windows of `window` records; 0: about 64 MiB of records) and its index
+int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user);
+int bsr_index_begin(bsr_dev_t *d, const bsr_index_t &ix, void *stream);
+int bsr_index_finish(bsr_dev_t *d, bsr_index_t &ix, void *stream);

@@ -1,0 +1,234 @@
+// Sorted BAM output on the host: the walk over a record stream, the host form of the sort (std::stable_sort), the index pass over a window and the .bai bytes
+// (csrc/bam_sort_core.h's rules), the run store of csrc/align_pipeline.hip, and bmh_bam_sort_host / bmh_bam_sorted_file_host.
+#include <errno.h>
+#include <fcntl.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
+#include <algorithm>
+#include <map>
+#include <numeric>
+#include "bam_sort.h"
+
+#ifndef O_TMPFILE
+#define O_TMPFILE 0
+#endif
+
+int bsr_walk(const uint8_t *recs, uint64_t n_bytes, int n_ref, std::vector<uint64_t> &off, const char *fn)
+{
+	off.clear(); off.push_back(0);
+	for (uint64_t p = 0; p < n_bytes;) {
+		const uint64_t sz = bsr_record_bytes(recs + p, n_bytes - p);
+		if (!sz) { bmh_set_error("%s: the bytes at %llu begin no whole BAM record (the stream is cut, or is no record stream)", fn, (unsigned long long)p); return BMH_EINVAL; }
+		const int32_t r = bsr_ref(recs + p);
+		if (r < -1 || (n_ref >= 0 && r >= n_ref)) { bmh_set_error("%s: record %zu names reference %d of %d", fn, off.size() - 1, r, n_ref); return BMH_EINVAL; }
+		p += sz; off.push_back(p);
+		if (off.size() > 0xfffffff0ull) { bmh_set_error("%s: 2^32 records", fn); return BMH_EINVAL; }
+	}
+	return BMH_OK;
+}
+
+void bsr_sort_host(const uint8_t *recs, const std::vector<uint64_t> &off, std::vector<uint64_t> &keys, std::vector<uint32_t> &ord)
+{
+	const size_t n = off.size() - 1;
+	std::vector<uint64_t> k(n);
+	for (size_t i = 0; i < n; ++i) k[i] = bsr_key(recs + off[i]);
+	ord.resize(n); std::iota(ord.begin(), ord.end(), 0u);
+	std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return k[a] < k[b]; });
+	keys.resize(n);
+	for (size_t j = 0; j < n; ++j) keys[j] = k[ord[j]];
+}
+
+int bsr_index_t::init(int n_contigs, const int32_t *contig_len, const char *fn)
+{
+	n_ref = n_contigs; n_win.clear(); lin_off.assign(1, 0); heads.clear(); file_pos = 0; valid = false;
+	for (int c = 0; c < n_contigs; ++c) {
+		if (contig_len[c] < 0 || contig_len[c] >= BSR_MAX_CONTIG) {
+			bmh_set_error("%s: contig %d has %lld bases: a BAI index holds contigs below 2^29 bases (CSI is not written)", fn, c, (long long)(uint32_t)contig_len[c]); return BMH_EINVAL;
+		}
+		n_win.push_back(bsr_n_windows(contig_len[c])); lin_off.push_back(lin_off.back() + n_win.back());
+	}
+	lin.assign(lin_off.back() + 1, ~0ull); counts.assign(2 * (size_t)n_ref + 1, 0);
+	valid = true;
+	return BMH_OK;
+}
+
+void bsr_index_t::window_host(const uint8_t *recs, const uint64_t *soff, uint32_t n, const uint64_t *moff)
+{
+	const uint64_t total = soff[n];
+	for (uint32_t j = 0; j < n; ++j) {
+		const uint8_t *rec = recs + soff[j], *prev = j ? recs + soff[j - 1] : nullptr;
+		const uint64_t v = bsr_voff(file_pos, moff, total, soff[j]);
+		const int32_t r = bsr_ref(rec);
+		if (bsr_chunk_head(rec, prev)) heads.push_back({r < 0 ? -1 : r, bsr_bin(rec), v});
+		if (r < 0 || r >= n_ref) { ++counts[2 * (size_t)n_ref]; continue; }
+		++counts[2 * (size_t)r + ((bsr_flag(rec) & 4u) ? 1 : 0)];
+		uint32_t lo, hi;
+		bsr_windows(rec, n_win[r], &lo, &hi);
+		for (uint32_t w = lo; w <= hi; ++w) { uint64_t &s = lin[lin_off[r] + w]; if (v < s) s = v; }
+	}
+	file_pos += moff[(total + BSR_PIECE - 1) / BSR_PIECE];
+}
+
+void bsr_index_t::bai(uint64_t base_offset, std::string &out) const
+{
+	const uint64_t sh = base_offset << 16;
+	auto u32 = [&](uint32_t v) { for (int k = 0; k < 4; ++k) out.push_back((char)(v >> (8 * k))); };
+	auto u64 = [&](uint64_t v) { for (int k = 0; k < 8; ++k) out.push_back((char)(v >> (8 * k))); };
+	// chunks: heads that continue the chunk before them (a window's first record) are dropped; a chunk ends where the next begins
+	struct ref_t { std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins; uint64_t beg = 0, end = 0; bool any = false; };
+	std::vector<ref_t> refs((size_t)n_ref);
+	std::vector<bsr_head_t> hs;
+	for (const bsr_head_t &h : heads)
+		if (hs.empty() || hs.back().ref != h.ref || (h.ref >= 0 && hs.back().bin != h.bin)) hs.push_back(h);
+	for (size_t i = 0; i < hs.size(); ++i) {
+		if (hs[i].ref < 0 || hs[i].ref >= n_ref) continue;
+		const uint64_t b = hs[i].beg + sh, e = (i + 1 < hs.size() ? hs[i + 1].beg : file_pos << 16) + sh;
+		ref_t &R = refs[(size_t)hs[i].ref];
+		R.bins[hs[i].bin].push_back({b, e});
+		if (!R.any) { R.any = true; R.beg = b; }
+		R.end = e;
+	}
+	out.clear();
+	out += "BAI\1"; u32((uint32_t)n_ref);
+	for (int r = 0; r < n_ref; ++r) {
+		const ref_t &R = refs[(size_t)r];
+		if (!R.any) { u32(0); u32(0); continue; }
+		u32((uint32_t)R.bins.size() + 1);
+		for (const auto &kv : R.bins) {
+			u32(kv.first); u32((uint32_t)kv.second.size());
+			for (const auto &c : kv.second) { u64(c.first); u64(c.second); }
+		}
+		u32(BSR_META_BIN); u32(2); u64(R.beg); u64(R.end); u64(counts[2 * (size_t)r]); u64(counts[2 * (size_t)r + 1]);
+		uint32_t n_intv = 0;
+		for (uint32_t w = 0; w < n_win[r]; ++w) if (lin[lin_off[r] + w] != ~0ull) n_intv = w + 1;
+		u32(n_intv);
+		uint64_t last = 0;
+		for (uint32_t w = 0; w < n_intv; ++w) { const uint64_t v = lin[lin_off[r] + w]; if (v != ~0ull) last = v + sh; u64(last); }
+	}
+	u64(counts[2 * (size_t)n_ref]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the run store
+
+void bsr_store_t::clear()
+{
+	for (bsr_run_t &r : runs) free(r.mem);
+	runs.clear(); used = 0; spilled = 0; file_bytes = 0;
+	if (fd >= 0) close(fd);
+	fd = -1;
+}
+
+int bsr_store_t::append(const uint8_t *recs, uint64_t bytes, const uint64_t *keys, const uint64_t *off, uint64_t n)
+{
+	bsr_run_t r;
+	r.n = n; r.bytes = bytes; r.keys.assign(keys, keys + n); r.off.assign(off, off + n + 1);
+	if (bytes <= mem_bytes - std::min(used, mem_bytes)) {
+		r.mem = (uint8_t *)malloc(bytes + 1);
+		if (!r.mem) { bmh_set_error("sorted BAM: out of memory for a run of %llu bytes", (unsigned long long)bytes); return BMH_ENOMEM; }
+		memcpy(r.mem, recs, bytes); used += bytes;
+	} else {
+		if (fd < 0) {                                     // an unnamed file: nothing to remove, whatever ends the run
+			const char *env = getenv("TMPDIR");
+			const std::string dir = !tmp_dir.empty() ? tmp_dir : (env && env[0] ? env : "/tmp");
+			if (O_TMPFILE) fd = open(dir.c_str(), O_TMPFILE | O_RDWR | O_CLOEXEC, 0600);
+			if (fd < 0) {
+				std::string t = dir + "/bmh_sort_XXXXXX";
+				fd = mkstemp(&t[0]);
+				if (fd >= 0) (void)unlink(t.c_str());
+			}
+			if (fd < 0) { bmh_set_error("sorted BAM: cannot create a temporary file in %s: %s", dir.c_str(), strerror(errno)); return BMH_EINVAL; }
+		}
+		for (uint64_t p = 0; p < bytes;) {
+			const ssize_t w = pwrite(fd, recs + p, (size_t)std::min<uint64_t>(bytes - p, 1u << 30), (off_t)(file_bytes + p));
+			if (w <= 0) {
+				if (w < 0 && errno == EINTR) continue;
+				bmh_set_error("sorted BAM: writing a run of %llu bytes to the temporary file: %s", (unsigned long long)bytes, w < 0 ? strerror(errno) : "nothing was written (no space left?)");
+				return BMH_EINVAL;
+			}
+			p += (uint64_t)w;
+		}
+		r.file_at = (int64_t)file_bytes; file_bytes += bytes; ++spilled;
+	}
+	runs.push_back(std::move(r));
+	return BMH_OK;
+}
+
+int bsr_store_t::read(const bsr_run_t &r, uint64_t a, uint64_t b, uint8_t *dst) const
+{
+	if (r.mem) { memcpy(dst, r.mem + a, b - a); return BMH_OK; }
+	for (uint64_t p = a; p < b;) {
+		const ssize_t g = pread(fd, dst + (p - a), (size_t)std::min<uint64_t>(b - p, 1u << 30), (off_t)((uint64_t)r.file_at + p));
+		if (g <= 0) { if (g < 0 && errno == EINTR) continue; bmh_set_error("sorted BAM: reading a run back from the temporary file: %s", g < 0 ? strerror(errno) : "it is shorter than what was written"); return BMH_EINVAL; }
+		p += (uint64_t)g;
+	}
+	return BMH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the host entry points
+
+extern "C" int bmh_bam_sort_host(const uint8_t *recs, uint64_t n_bytes, uint8_t **out)
+{
+	const char *fn = "bmh_bam_sort_host";
+	if (!out || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	*out = nullptr;
+	std::vector<uint64_t> off, keys; std::vector<uint32_t> ord;
+	const int rc = bsr_walk(recs, n_bytes, -1, off, fn);
+	if (rc != BMH_OK) return rc;
+	bsr_sort_host(recs, off, keys, ord);
+	uint8_t *o = (uint8_t *)malloc(n_bytes + 1);
+	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+	uint64_t p = 0;
+	for (uint32_t i : ord) { memcpy(o + p, recs + off[i], off[i + 1] - off[i]); p += off[i + 1] - off[i]; }
+	*out = o;
+	return BMH_OK;
+}
+
+// header members, the sorted records in windows of `window` records (0: as many as hold about 64 MiB), the end-of-file member; and the index
+extern "C" int bmh_bam_sorted_file_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                        int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes)
+{
+	const char *fn = "bmh_bam_sorted_file_host";
+	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
+	bsr_index_t ix;
+	int rc = ix.init(n_contigs, contig_len, fn);
+	if (rc != BMH_OK) return rc;
+	std::vector<uint64_t> off, keys; std::vector<uint32_t> ord;
+	if ((rc = bsr_walk(recs, n_bytes, n_contigs, off, fn)) != BMH_OK) return rc;
+	bsr_sort_host(recs, off, keys, ord);
+	const size_t n = ord.size();
+	std::string file;
+	auto members = [&](const uint8_t *p, uint64_t nb, std::vector<uint64_t> *moff) {
+		uint8_t *m = nullptr; uint64_t mb = 0;
+		const int r = bmh_bgzf_deflate_host(p, nb, level, 0, &m, &mb);
+		if (r != BMH_OK) return r;
+		if (moff) {                                   // the members' offsets: every member's BSIZE
+			moff->assign(1, 0);
+			for (uint64_t q = 0; q < mb;) { q += ((uint64_t)m[q + 16] | (uint64_t)m[q + 17] << 8) + 1; moff->push_back(q); }
+		}
+		file.append((const char *)m, mb); bmh_free(m);
+		return (int)BMH_OK;
+	};
+	uint8_t *hdr = nullptr; uint64_t hb = 0;
+	if ((rc = bmh_bam_header(header_text, n_contigs, contig_names, contig_len, &hdr, &hb)) != BMH_OK) return rc;
+	rc = members(hdr, hb, nullptr); bmh_free(hdr);
+	if (rc != BMH_OK) return rc;
+	const uint64_t base = file.size();
+	const uint64_t W = window ? window : std::max<uint64_t>(1, (64ull << 20) / std::max<uint64_t>(1, n ? n_bytes / n : 1));
+	std::vector<uint8_t> buf; std::vector<uint64_t> soff, moff;
+	for (size_t a = 0; a < n; a += W) {
+		const size_t b = std::min<uint64_t>(n, a + W);
+		soff.assign(1, 0); buf.clear();
+		for (size_t j = a; j < b; ++j) { const uint64_t o = off[ord[j]], s = off[ord[j] + 1] - o; buf.insert(buf.end(), recs + o, recs + o + s); soff.push_back(buf.size()); }
+		if ((rc = members(buf.data(), buf.size(), &moff)) != BMH_OK) return rc;
+		ix.window_host(buf.data(), soff.data(), (uint32_t)(b - a), moff.data());
+	}
+	file.append((const char *)bmh_bgzf_eof, 28);
+	std::string ib; ix.bai(base, ib);
+	uint8_t *f = (uint8_t *)malloc(file.size() + 1), *i = (uint8_t *)malloc(ib.size() + 1);
+	if (!f || !i) { free(f); free(i); bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+	memcpy(f, file.data(), file.size()); memcpy(i, ib.data(), ib.size());
+	*bam = f; *bam_bytes = file.size(); *bai = i; *bai_bytes = ib.size();
+	return BMH_OK;
+}

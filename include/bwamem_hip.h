@@ -729,7 +729,7 @@ typedef int (*bmh_sam_sink_t)(void *user, const char *text, size_t len);
 typedef struct {
 	uint64_t n_reads, n_bytes; uint32_t n_batches; int n_lanes;
 	double seconds;                 /* wall clock of the run */
-	double format_seconds;          /* in the writer thread (overlaps the workers) */
+	double format_seconds;          /* in the writer thread (overlaps the workers); a BMH_OUT_BAM_SORTED run adds its final merge, which follows them */
 	double h2d_seconds, seed_seconds, chain_extend_seconds, tail_seconds, select_seconds, cigar_seconds;    /* summed over the lanes' host clocks */
 	double gate_wait_seconds;       /* lanes waiting for a slot in the path's device stages (ALIGNER_GPU_SLOTS), summed likewise */
 	/* the copies themselves, timed by HIP events on the lanes' streams (h2d_seconds / cigar_seconds above are HOST clocks around whole stages: the staging of
@@ -811,6 +811,29 @@ int bmh_bgzf_deflate_host(const uint8_t *in, uint64_t n_bytes, int level, int n_
 int bmh_deflate_blocks_host(const uint8_t *in, uint64_t n_bytes, int level, uint8_t *slots, uint32_t *sizes, int n_threads);
 int bmh_bam_header(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, uint8_t **out, uint64_t *out_bytes);
 int bmh_aligner_set_output(bmh_aligner_t *a, int format, int level);
+
+/* ---- Coordinate-sorted BAM and its BAI index (csrc/bam_sort_core.h, csrc/bam_sort_kernels.hip, csrc/bam_sort_host.cpp).
+ *
+ * The order is `samtools sort`'s: key (uint32)refID << 32 | (uint32)(pos + 1) << 1 | reverse strand; records without a reference last; equal keys in the order
+ * they came in.  The index is the SAM specification's section 5.2 (bins as the records carry them, the pseudo-bin 37450, the 16 KiB linear index, n_no_coor).
+ * bmh_bam_sort_device / _host: a record stream in host memory (whole records, else refused) -> the same records in order (malloc'd; bmh_free).
+ * bmh_bam_sorted_file_device / _host: header members, the sorted records in windows of `window` records (0: about 64 MiB of records; a window's last member
+ * is short), the end-of-file member; and the .bai bytes.  Both forms give the same bytes.  A contig of 2^29 bases or more is refused (BAI cannot index it).
+ * bmh_aligner_set_output(a, BMH_OUT_BAM_SORTED, level): every batch becomes a sorted run kept on the host (in memory up to mem_bytes of records, beyond that in
+ * an unnamed temporary file in tmp_dir); at the end of the input all runs' keys are sorted once more on the device -- 24 bytes of device memory per record and
+ * the sort's work space, fewer than 2^32 records, else the run is refused with a message naming the count -- and the sink receives the record members of the
+ * sorted file, window after window.  The header members and the end-of-file member stay with the caller.
+ * bmh_aligner_set_sort: the run store's budget (0: 4 GiB), its directory (NULL: $TMPDIR, else /tmp) and the window (0: about 64 MiB of records).
+ * bmh_aligner_sort_index: the index of the last sorted run (malloc'd; bmh_free); base_offset: the bytes the caller wrote before the sink's first. */
+#define BMH_OUT_BAM_SORTED 2
+int bmh_bam_sort_device(const uint8_t *records, uint64_t n_bytes, void *stream, uint8_t **out);
+int bmh_bam_sort_host(const uint8_t *records, uint64_t n_bytes, uint8_t **out);
+int bmh_bam_sorted_file_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
+                               int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes);
+int bmh_bam_sorted_file_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
+                             int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes);
+int bmh_aligner_set_sort(bmh_aligner_t *a, uint64_t mem_bytes, const char *tmp_dir, uint32_t window_records);
+int bmh_aligner_sort_index(bmh_aligner_t *a, uint64_t base_offset, uint8_t **bai, uint64_t *bai_bytes);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,126 @@
+#!/usr/bin/env python
+"""What coordinate-sorted BAM output costs: reads -> unsorted BAM (the yardstick: the path before sorting existed, unchanged), reads -> sorted BAM + index with every
+run in memory and with every run spilled to the temporary file -- each split into the per-batch part and the final merge (stats.format_seconds of a sorted run is
+the merge: key sort, windows, compression, index pass, sink) --, and bam_sort alone in records/s -- on the bench's index and read set, in one process, medians of
+--runs runs with their spreads.  Writes profiles/bam_sort.json (or --out).  The read set is the bench's two batches, each twice: every read occurs twice, so the
+sorted file's size (the two copies land next to each other) and the merge's compression rate are not those of real data.
+
+    python scripts/bam_sort_rate.py [--runs 3] [--reads 1000000] [--genome-mbp 3100] [--out FILE]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "bwa-mem_gpu_amd"))
+import numpy as np
+import torch
+
+import bwamem_hip as B
+from bwamem_hip import fmindex as F
+from bwamem_hip.lib import ChainOpt, ExtParams, NativeAligner, PeOpt, PostOpt, bam_sort
+
+
+def stats(secs, unit_count, scale):
+    med = sorted(secs)[len(secs) // 2]
+    return {"median": round(unit_count / med / scale, 3), "runs": [round(unit_count / s / scale, 3) for s in secs], "spread_pct": round(100 * (max(secs) - min(secs)) / med, 1)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--genome-mbp", type=float, default=3100)
+    ap.add_argument("--reads", type=int, default=1_000_000, help="reads per distinct batch; a run takes four times as many")
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    L = B.load_library()
+    n_genome = int(a.genome_mbp * 1e6)
+    t0 = time.time()
+    g_t, meta = B.synth.make_genome_device(n_genome, dev, seed=42, return_meta=True)
+    pac_t = F.pack_pac_device(g_t)
+    del g_t
+    torch.cuda.empty_cache()
+    d = F.build_fmd_index_device(pac_t, n_genome, sa_intv=1, verify=False)
+    dindex = B.Index.from_device(d.primary, d.L2.astype(np.uint64), d.seq_len, d.bwt_t, d.sa_intv, d.sa_t, d.bits_t, pac_t=pac_t, l_pac=n_genome)
+    g = F.unpack_pac_device(pac_t, n_genome).cpu().numpy()
+    pac_h = pac_t.cpu().numpy()
+    contigs, holes = meta["contigs"], meta["holes"]
+    nth = int(L.bmh_effective_cpus())
+    co = ChainOpt(); L.bmh_chain_opt_default(C.byref(co))
+    po = PostOpt(); L.bmh_post_opt_default(C.byref(po))
+    pe_o = PeOpt(); L.bmh_pe_opt_default(C.byref(pe_o))
+    rl, n = 150, a.reads
+    r1 = B.synth.make_reads(g, n, rl, seed=7, holes=holes)[0]; r2 = B.synth.make_reads(g, n, rl, seed=1007, holes=holes)[0]
+    asc = B.synth.codes_to_ascii(np.concatenate([r1.reshape(-1), r2.reshape(-1), r1.reshape(-1), r2.reshape(-1)]))
+    n4 = 4 * n
+    w = len(str(n4))
+    names = np.frombuffer("".join(np.char.add(">r", np.char.zfill(np.arange(n4).astype(str), w)).tolist()).encode(), np.uint8).reshape(n4, w + 2)
+    recs = np.empty((n4, w + 3 + rl + 1), np.uint8)
+    recs[:, :w + 2] = names; recs[:, w + 2] = 10; recs[:, w + 3:w + 3 + rl] = asc.reshape(n4, rl); recs[:, -1] = 10
+    tmp = tempfile.mkdtemp(prefix="bmh_bam_sort_")
+    path = os.path.join(tmp, "se.fa")
+    recs.tofile(path)
+    del recs
+    nat = NativeAligner(dindex, pac_h, n_genome, contigs, None, co, ExtParams.default(), po, pe_o)
+    result = {"genome_mbp": a.genome_mbp, "reads_per_run": n4, "setup_s": round(time.time() - t0, 1), "runs": a.runs, "host_threads": nth, "rows": {}}
+
+    def run(fmt, spill=False, keep=None):
+        nat.set_output(fmt, 1)
+        if fmt == "bam_sorted":
+            nat.set_sort(1 if spill else 64 << 30, tmp, 0)
+        nbytes = [0]
+
+        def sink(mv):
+            nbytes[0] += len(mv)
+            if keep is not None and len(keep) < 1:
+                keep.append(bytes(mv))
+        secs, merge = [], []
+        for it in range(a.runs + 1):
+            nbytes[0] = 0
+            t1 = time.perf_counter()
+            st = nat.run_file(path, False, sink, batch_reads=n4 // 4, n_lanes=2, n_threads=nth)
+            if it:
+                secs.append(time.perf_counter() - t1); merge.append(st.format_seconds)
+        row = stats(secs, n4, 1e6)
+        row["unit"] = "Mreads/s"; row["bytes_out_per_read"] = round(nbytes[0] / n4, 1)
+        if fmt == "bam_sorted":
+            nat.sort_index(0)
+            row["final_merge"] = stats(merge, n4, 1e6); row["per_batch_part"] = stats([s - m for s, m in zip(secs, merge)], n4, 1e6)
+            row["final_merge_share_pct"] = round(100 * sorted(merge)[len(merge) // 2] / sorted(secs)[len(secs) // 2], 1)
+        return row
+    keep = []
+    result["rows"]["reads_to_bam_unsorted"] = run("bam", keep=keep)
+    result["rows"]["reads_to_sorted_bam_in_memory"] = run("bam_sorted")
+    result["rows"]["reads_to_sorted_bam_spilled"] = run("bam_sorted", spill=True)
+    nat.set_output("sam", 1)
+    # ---- bam_sort alone: the first batch's records (its members inflated), host bytes in, host bytes out
+    import zlib
+    blob, recs, p = keep[0], [], 0
+    while p < len(blob):
+        bs = int.from_bytes(blob[p + 16:p + 18], "little") + 1
+        recs.append(zlib.decompress(blob[p:p + bs], 31)); p += bs
+    stream = b"".join(recs)
+    n_rec, p = 0, 0
+    while p < len(stream):
+        p += int.from_bytes(stream[p:p + 4], "little") + 4; n_rec += 1
+    secs = []
+    for it in range(a.runs + 1):
+        torch.cuda.synchronize(); t1 = time.perf_counter()
+        bam_sort(stream)
+        if it:
+            secs.append(time.perf_counter() - t1)
+    row = stats(secs, n_rec, 1e6); row["unit"] = "Mrecords/s (the entry point: the host's walk, both copies, keys, sort, gather)"; row["records"] = n_rec; row["bytes"] = len(stream)
+    result["rows"]["bam_sort_device"] = row
+    os.remove(path); os.rmdir(tmp)
+    out = a.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bam_sort.json")
+    with open(out, "w") as f:
+        json.dump(result, f, indent=1)
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
