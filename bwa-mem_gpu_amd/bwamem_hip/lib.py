@@ -470,8 +470,11 @@ class NativeAligner:
         L.bmh_aligner_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.POINTER(ChainOpt), C.POINTER(ExtParams),
                                          C.POINTER(PostOpt), C.POINTER(PeOpt)]
         L.bmh_aligner_free.argtypes = [C.c_void_p]
-        L.bmh_aligner_run.restype = C.c_int
-        L.bmh_aligner_run.argtypes = [C.c_void_p, C.POINTER(ReadSetT), C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, SAM_SINK, C.c_void_p, C.POINTER(AlignStats)]
+        run_tail = [C.c_int, C.c_int, C.c_int, SAM_SINK, C.c_void_p, C.POINTER(AlignStats)]      # paired, n_lanes, n_threads, sink, user, stats: the runs' common arguments
+        for name, head in (("bmh_aligner_run", [C.POINTER(ReadSetT), C.c_void_p, C.c_uint32]), ("bmh_aligner_run_fasta", [C.c_char_p, C.c_uint64, C.c_uint64]),
+                           ("bmh_aligner_run_file", [C.c_char_p, C.c_uint64, C.c_uint64]), ("bmh_aligner_run_files", [C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64])):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [C.c_void_p] + head + run_tail
         names = (C.c_char_p * len(contigs))(*[c[0].encode() for c in contigs])
         lens = np.ascontiguousarray([c[1] for c in contigs], dtype=np.int32)
         alt = np.ascontiguousarray(is_alt, dtype=np.uint8) if is_alt is not None else None
@@ -531,10 +534,36 @@ class NativeAligner:
         L.bmh_aligner_host_tail_batches.argtypes = [C.c_void_p]
         return int(L.bmh_aligner_host_tail_batches(self.handle))
 
+    def _run(self, name: str, args, write, bam_refusal: bool = True, read_errors=()) -> "AlignStats":
+        """one run through the native entry point `name`: write(memoryview) receives every batch's records in order.  An exception of `write` is raised again after
+        the run (it must not cross the C frames); else a return code raises BamRefusal (where bam_refusal), ReadFileError (a message with one of read_errors),
+        CapacityError or RuntimeError"""
+        L = load_library()
+        err = []
+
+        def sink(_user, ptr, n):
+            try:
+                write(memoryview((C.c_char * n).from_address(ptr)))
+                return 0
+            except BaseException as e:                      # noqa: BLE001 -- reported after the run
+                err.append(e)
+                return 1
+        st = AlignStats()
+        rc = getattr(L, name)(self.handle, *args, SAM_SINK(sink), None, C.byref(st))
+        if err:
+            raise err[0]
+        if rc != 0:
+            msg = _err(L)
+            if bam_refusal and msg.startswith("BAM output:"):
+                raise BamRefusal(msg)
+            if any(m in msg for m in read_errors):
+                raise ReadFileError(msg)
+            raise (CapacityError if rc == -3 else RuntimeError)(f"{name} rc={rc}: " + msg)
+        return st
+
     def run(self, rs, cuts, paired: bool, write, n_lanes: int = 2, n_threads: int = 0) -> "AlignStats":
         """the batches [cuts[b], cuts[b+1]) of the read set `rs` (an aligner.ReadSet; codes required); write(memoryview) receives every
         batch's SAM records in order"""
-        L = load_library()
         keep = [np.ascontiguousarray(rs.ascii, dtype=np.uint8), np.ascontiguousarray(rs.codes, dtype=np.uint8), np.ascontiguousarray(rs.offs, dtype=np.uint64),
                 np.ascontiguousarray(rs.lens, dtype=np.uint32), np.ascontiguousarray(rs.name_blob, dtype=np.uint8), np.ascontiguousarray(rs.name_off, dtype=np.uint64)]
         c = ReadSetT()
@@ -546,106 +575,22 @@ class NativeAligner:
             keep.append(np.ascontiguousarray(rs.comments[0], dtype=np.uint8)); c.comments = keep[-1].ctypes.data; c.n_comment_bytes = len(keep[-1])
             keep.append(np.ascontiguousarray(rs.comments[1], dtype=np.uint64)); c.comment_offs = keep[-1].ctypes.data
         cu = np.ascontiguousarray(cuts, dtype=np.uint64)
-        err = []
-
-        def sink(_user, ptr, n):
-            try:
-                write(memoryview((C.c_char * n).from_address(ptr)))
-                return 0
-            except BaseException as e:                      # noqa: BLE001 -- reported after the run (an exception must not cross the C frames)
-                err.append(e)
-                return 1
-        cb = SAM_SINK(sink)
-        st = AlignStats()
-        rc = L.bmh_aligner_run(self.handle, C.byref(c), cu.ctypes.data, len(cu) - 1, 1 if paired else 0, int(n_lanes), int(n_threads), cb, None, C.byref(st))
-        if err:
-            raise err[0]
-        if rc != 0:
-            if _err(L).startswith("BAM output:"):
-                raise BamRefusal(_err(L))
-            raise (CapacityError if rc == -3 else RuntimeError)(f"bmh_aligner_run rc={rc}: " + _err(L))
-        return st
+        return self._run("bmh_aligner_run", (C.byref(c), cu.ctypes.data, len(cu) - 1, 1 if paired else 0, int(n_lanes), int(n_threads)), write)
 
     def run_fasta(self, path: str, paired: bool, write, batch_bases: int = 0, batch_reads: int = 0, n_lanes: int = 2, n_threads: int = 0) -> "AlignStats":
         """bmh_aligner_run_fasta: the read file `path` batch by batch (cut by bases like the reference's bseq_read, or by reads), a loader thread ahead of the
         lanes; write(memoryview) receives every batch's SAM records in order"""
-        L = load_library()
-        L.bmh_aligner_run_fasta.restype = C.c_int
-        L.bmh_aligner_run_fasta.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, SAM_SINK, C.c_void_p, C.POINTER(AlignStats)]
-        err = []
-
-        def sink(_user, ptr, n):
-            try:
-                write(memoryview((C.c_char * n).from_address(ptr)))
-                return 0
-            except BaseException as e:                      # noqa: BLE001 -- reported after the run (an exception must not cross the C frames)
-                err.append(e)
-                return 1
-        cb = SAM_SINK(sink)
-        st = AlignStats()
-        rc = L.bmh_aligner_run_fasta(self.handle, path.encode(), int(batch_bases), int(batch_reads), 1 if paired else 0, int(n_lanes), int(n_threads), cb, None, C.byref(st))
-        if err:
-            raise err[0]
-        if rc != 0:
-            raise (CapacityError if rc == -3 else RuntimeError)(f"bmh_aligner_run_fasta rc={rc}: " + _err(L))
-        return st
+        return self._run("bmh_aligner_run_fasta", (path.encode(), int(batch_bases), int(batch_reads), 1 if paired else 0, int(n_lanes), int(n_threads)), write, bam_refusal=False)
 
     def run_file(self, path: str, paired: bool, write, batch_bases: int = 0, batch_reads: int = 0, n_lanes: int = 2, n_threads: int = 0) -> "AlignStats":
         """bmh_aligner_run_file: run_fasta for a FASTA or FASTQ file (QUAL from the qualities; the comments with -C)"""
-        L = load_library()
-        L.bmh_aligner_run_file.restype = C.c_int
-        L.bmh_aligner_run_file.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, SAM_SINK, C.c_void_p, C.POINTER(AlignStats)]
-        err = []
-
-        def sink(_user, ptr, n):
-            try:
-                write(memoryview((C.c_char * n).from_address(ptr)))
-                return 0
-            except BaseException as e:                      # noqa: BLE001 -- reported after the run (an exception must not cross the C frames)
-                err.append(e)
-                return 1
-        cb = SAM_SINK(sink)
-        st = AlignStats()
-        rc = L.bmh_aligner_run_file(self.handle, path.encode(), int(batch_bases), int(batch_reads), 1 if paired else 0, int(n_lanes), int(n_threads), cb, None, C.byref(st))
-        if err:
-            raise err[0]
-        if rc != 0:
-            msg = _err(L)
-            if msg.startswith("BAM output:"):
-                raise BamRefusal(msg)
-            if "FASTQ:" in msg or "reads file:" in msg:
-                raise ReadFileError(msg)
-            raise (CapacityError if rc == -3 else RuntimeError)(f"bmh_aligner_run_file rc={rc}: " + msg)
-        return st
+        return self._run("bmh_aligner_run_file", (path.encode(), int(batch_bases), int(batch_reads), 1 if paired else 0, int(n_lanes), int(n_threads)), write,
+                         read_errors=("FASTQ:", "reads file:"))
 
     def run_files(self, path1: str, path2: str | None, paired: bool, write, batch_bases: int = 0, batch_reads: int = 0, n_lanes: int = 2, n_threads: int = 0) -> "AlignStats":
         """bmh_aligner_run_files: run_file for one or two read files of any shape (multi-line records, gzip / BGZF, pipes; path2: the mates)"""
-        L = load_library()
-        L.bmh_aligner_run_files.restype = C.c_int
-        L.bmh_aligner_run_files.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, SAM_SINK, C.c_void_p, C.POINTER(AlignStats)]
-        err = []
-
-        def sink(_user, ptr, n):
-            try:
-                write(memoryview((C.c_char * n).from_address(ptr)))
-                return 0
-            except BaseException as e:                      # noqa: BLE001 -- reported after the run (an exception must not cross the C frames)
-                err.append(e)
-                return 1
-        cb = SAM_SINK(sink)
-        st = AlignStats()
-        rc = L.bmh_aligner_run_files(self.handle, os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, int(batch_bases), int(batch_reads),
-                                     1 if paired else 0, int(n_lanes), int(n_threads), cb, None, C.byref(st))
-        if err:
-            raise err[0]
-        if rc != 0:
-            msg = _err(L)
-            if msg.startswith("BAM output:"):
-                raise BamRefusal(msg)
-            if "FASTQ:" in msg or "reads file" in msg:
-                raise ReadFileError(msg)
-            raise (CapacityError if rc == -3 else RuntimeError)(f"bmh_aligner_run_files rc={rc}: " + msg)
-        return st
+        return self._run("bmh_aligner_run_files", (os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, int(batch_bases), int(batch_reads),
+                                                   1 if paired else 0, int(n_lanes), int(n_threads)), write, read_errors=("FASTQ:", "reads file"))
 
     def free(self):
         if self.handle:

@@ -1,5 +1,5 @@
 // Reads in host memory -> SAM text, driven from C threads (the host side of the gase_aln run around the
-// device path; what worker1 / worker2 + kt_pipeline do in the reference, /root/reference/src/bwamem.c:2042-2340, src/fastmap.c:59-120).
+// device path; what worker1 / worker2 + kt_pipeline do in the reference, src/bwamem.c:2042-2340, src/fastmap.c:59-120).
 //
 // The stages exist already as C-ABI entry points (seeding, chaining, extension, merge, the region tail, CIGARs, the formatter); until
 // round 4 a Python loop called them batch after batch and was three to ten times slower than the device path it drove.  Here:
@@ -17,10 +17,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <functional>
-#include <fcntl.h>
 #include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -34,6 +31,7 @@
 #include "pair_kernels.h"
 #include "bam_ws.h"
 #include "bam_sort.h"
+#include "batch_queue.h"
 
 namespace {
 
@@ -80,40 +78,28 @@ namespace {
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// device / pinned buffers that only ever grow
-template <class T> struct dbuf_t {
+// device (dbuf_t) / pinned host (hbuf_t) buffers that only ever grow
+template <class T, bool PINNED> struct gbuf_t {
 	T *p = nullptr; size_t cap = 0;
-	dbuf_t() = default;
-	dbuf_t(const dbuf_t &) = delete;
-	dbuf_t &operator=(const dbuf_t &) = delete;
-	void swap(dbuf_t &o) { T *q = p; p = o.p; o.p = q; const size_t c = cap; cap = o.cap; o.cap = c; }
+	gbuf_t() = default;
+	gbuf_t(const gbuf_t &) = delete;
+	gbuf_t &operator=(const gbuf_t &) = delete;
+	void swap(gbuf_t &o) { T *q = p; p = o.p; o.p = q; const size_t c = cap; cap = o.cap; o.cap = c; }
+	void drop() { if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
 	int need(size_t n) {
 		if (n <= cap) return BMH_OK;
-		if (p) (void)hipFree(p);
-		p = nullptr; cap = 0;
+		drop();
 		const size_t c = n + n / 4 + 1024;
-		if (hipMalloc((void **)&p, c * sizeof(T)) != hipSuccess) { bmh_set_error("bmh_aligner_run: %zu bytes of device memory: %s", c * sizeof(T), hipGetErrorString(hipGetLastError())); return BMH_ENOMEM; }
+		if ((PINNED ? hipHostMalloc((void **)&p, c * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p, c * sizeof(T))) != hipSuccess) {
+			bmh_set_error("bmh_aligner_run: %zu bytes of %s memory: %s", c * sizeof(T), PINNED ? "pinned" : "device", hipGetErrorString(hipGetLastError())); return BMH_ENOMEM;
+		}
 		cap = c;
 		return BMH_OK;
 	}
-	~dbuf_t() { if (p) (void)hipFree(p); }
+	~gbuf_t() { drop(); }
 };
-template <class T> struct hbuf_t {
-	T *p = nullptr; size_t cap = 0;
-	hbuf_t() = default;
-	hbuf_t(const hbuf_t &) = delete;
-	hbuf_t &operator=(const hbuf_t &) = delete;
-	int need(size_t n) {
-		if (n <= cap) return BMH_OK;
-		if (p) (void)hipHostFree(p);
-		p = nullptr; cap = 0;
-		const size_t c = n + n / 4 + 1024;
-		if (hipHostMalloc((void **)&p, c * sizeof(T), hipHostMallocDefault) != hipSuccess) { bmh_set_error("bmh_aligner_run: %zu bytes of pinned memory: %s", c * sizeof(T), hipGetErrorString(hipGetLastError())); return BMH_ENOMEM; }
-		cap = c;
-		return BMH_OK;
-	}
-	~hbuf_t() { if (p) (void)hipHostFree(p); }
-};
+template <class T> using dbuf_t = gbuf_t<T, false>;
+template <class T> using hbuf_t = gbuf_t<T, true>;
 
 // What the writer needs of a finished batch.  The large arrays are PINNED buffers the device copies straight into; a result goes back
 // to a pool when its text is written, so the buffers are allocated a few times per run, not per batch (a million reads leave 70 MB
@@ -229,16 +215,20 @@ int cigars(const aligner_t &A, lane_t &Ln, const int32_t *d_fin, uint64_t n_sel,
 	return BMH_OK;
 }
 
+// a record BAM cannot hold fails the run: the one message of the device's converter (text_on_device) and the host's (out_stage_t)
+int bam_refused(const std::string &read_name, uint32_t status)
+{
+	bmh_set_error("BAM output: read '%s': its SAM record cannot be written as BAM: %s", read_name.c_str(), bmh_bam_status_name(status));
+	return BMH_EINVAL;
+}
+
 // the batch's SAM text written on the device (bmh_sam_text_sizes / _write) and copied into R.text
 int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, const int32_t *d_fin, uint32_t n, bool paired, result_t &R)
 {
 	if (!Ln.ctg_up) {                                              // the sequences' names and offsets, once per lane
-		std::vector<char> blob; std::vector<uint32_t> noff;
-		for (const std::string &s : A.names) { noff.push_back((uint32_t)blob.size()); blob.insert(blob.end(), s.begin(), s.end()); blob.push_back(0); }
-		noff.push_back((uint32_t)blob.size());
-		RCK(Ln.d_ctg_names.need(blob.size())); RCK(Ln.d_ctg_name_off.need(noff.size())); RCK(Ln.d_ctg_off.need(A.off.size()));
-		LCK(hipMemcpy(Ln.d_ctg_names.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
-		LCK(hipMemcpy(Ln.d_ctg_name_off.p, noff.data(), 4 * noff.size(), hipMemcpyHostToDevice));
+		RCK(Ln.d_ctg_names.need(A.ctg_blob.size())); RCK(Ln.d_ctg_name_off.need(A.ctg_noff.size())); RCK(Ln.d_ctg_off.need(A.off.size()));
+		LCK(hipMemcpy(Ln.d_ctg_names.p, A.ctg_blob.data(), A.ctg_blob.size(), hipMemcpyHostToDevice));
+		LCK(hipMemcpy(Ln.d_ctg_name_off.p, A.ctg_noff.data(), 4 * A.ctg_noff.size(), hipMemcpyHostToDevice));
 		LCK(hipMemcpy(Ln.d_ctg_off.p, A.off.data(), 8 * A.off.size(), hipMemcpyHostToDevice));
 		Ln.ctg_up = true;
 	}
@@ -265,11 +255,7 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 		if (!Ln.bam && !(Ln.bam = bmh_bam_ws_create())) return BMH_ENOMEM;
 		bmh_bam_out_t bo;
 		RCK(bmh_sam_to_bam_device(Ln.bam, Ln.d_text.p, (uint64_t)total, A.n_contigs, Ln.d_ctg_names.p, Ln.d_ctg_name_off.p, Ln.st, &bo));
-		if (bo.n_refused) {
-			const std::string nm = bmh_bam_record_name_device(Ln.bam, Ln.d_text.p, (uint64_t)total, bo.first_refused);
-			bmh_set_error("BAM output: read '%s': its SAM record cannot be written as BAM: %s", nm.c_str(), bmh_bam_status_name(bo.first_status));
-			return BMH_EINVAL;
-		}
+		if (bo.n_refused) return bam_refused(bmh_bam_record_name_device(Ln.bam, Ln.d_text.p, (uint64_t)total, bo.first_refused), bo.first_status);
 		if (A.out_fmt == BMH_OUT_BAM_SORTED) {
 			// sorted output: records -> keys -> sort -> gather on the lane's stream; the run (records, keys, offsets) crosses uncompressed, the writer stores it
 			if (!Ln.bsr && !(Ln.bsr = bsr_dev_create())) return BMH_ENOMEM;
@@ -543,16 +529,19 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 	const bool host_select = getenv("BMH_ALIGNER_HOST_SELECT") != nullptr;          // (A/B and cross-check: the host's selection for every batch; implies the host's text)
 	const bool text_dev = !host_format && !host_select;
 	R.has_text = false; R.text_len = 0;
-	if (text_dev) {
-		const uint64_t n0 = rs.name_offs[b0], n1 = b1 < rs.n_reads ? rs.name_offs[b1] : rs.n_name_bytes;
-		RCK(Ln.h_names.need(n1 - n0 + 1)); RCK(Ln.h_name_off.need(n + 2)); RCK(Ln.d_names.need(n1 - n0 + 1)); RCK(Ln.d_name_off.need(n + 2));
-		memcpy(Ln.h_names.p, rs.names + n0, n1 - n0);
-		for (uint32_t r = 0; r < n; ++r) Ln.h_name_off.p[r] = rs.name_offs[b0 + r] - n0;
-		Ln.h_name_off.p[n] = n1 - n0;
-		LCK(hipMemcpyAsync(Ln.d_names.p, Ln.h_names.p, n1 - n0, hipMemcpyHostToDevice, Ln.st));
-		LCK(hipMemcpyAsync(Ln.d_name_off.p, Ln.h_name_off.p, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, Ln.st));
-		h2d_bytes += (n1 - n0) + 8 * ((uint64_t)n + 1);
-	}
+	// a blob with its offsets (the names; -C: the comments): the batch's part, its offsets from 0, through pinned memory
+	auto send_blob = [&](const void *blob, const uint64_t *off, uint64_t n_bytes, hbuf_t<char> &hb, hbuf_t<uint64_t> &ho, dbuf_t<char> &db, dbuf_t<uint64_t> &dof) -> int {
+		const uint64_t c0 = off[b0], c1 = b1 < rs.n_reads ? off[b1] : n_bytes;
+		RCK(hb.need(c1 - c0 + 1)); RCK(ho.need(n + 2)); RCK(db.need(c1 - c0 + 1)); RCK(dof.need(n + 2));
+		memcpy(hb.p, (const char *)blob + c0, c1 - c0);
+		for (uint32_t r = 0; r < n; ++r) ho.p[r] = off[b0 + r] - c0;
+		ho.p[n] = c1 - c0;
+		LCK(hipMemcpyAsync(db.p, hb.p, c1 - c0, hipMemcpyHostToDevice, Ln.st));
+		LCK(hipMemcpyAsync(dof.p, ho.p, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, Ln.st));
+		h2d_bytes += (c1 - c0) + 8 * ((uint64_t)n + 1);
+		return BMH_OK;
+	};
+	if (text_dev) RCK(send_blob(rs.names, rs.name_offs, rs.n_name_bytes, Ln.h_names, Ln.h_name_off, Ln.d_names, Ln.d_name_off));
 	// FASTQ: the qualities go beside the letters (same offsets); -C: the comments beside the names.  A read set without them takes none of this
 	Ln.has_quals = text_dev && rs.quals != nullptr;
 	Ln.has_comments = text_dev && A.po.copy_comment && rs.comments != nullptr && rs.comment_offs != nullptr;
@@ -566,16 +555,7 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 		}
 		h2d_bytes += nb;
 	}
-	if (Ln.has_comments) {
-		const uint64_t c0 = rs.comment_offs[b0], c1 = b1 < rs.n_reads ? rs.comment_offs[b1] : rs.n_comment_bytes;
-		RCK(Ln.h_comments.need(c1 - c0 + 1)); RCK(Ln.h_comment_off.need(n + 2)); RCK(Ln.d_comments.need(c1 - c0 + 1)); RCK(Ln.d_comment_off.need(n + 2));
-		memcpy(Ln.h_comments.p, rs.comments + c0, c1 - c0);
-		for (uint32_t r = 0; r < n; ++r) Ln.h_comment_off.p[r] = rs.comment_offs[b0 + r] - c0;
-		Ln.h_comment_off.p[n] = c1 - c0;
-		LCK(hipMemcpyAsync(Ln.d_comments.p, Ln.h_comments.p, c1 - c0, hipMemcpyHostToDevice, Ln.st));
-		LCK(hipMemcpyAsync(Ln.d_comment_off.p, Ln.h_comment_off.p, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, Ln.st));
-		h2d_bytes += (c1 - c0) + 8 * ((uint64_t)n + 1);
-	}
+	if (Ln.has_comments) RCK(send_blob(rs.comments, rs.comment_offs, rs.n_comment_bytes, Ln.h_comments, Ln.h_comment_off, Ln.d_comments, Ln.d_comment_off));
 	LCK(hipEventRecord(Ln.ev_c[1], Ln.st));
 	Ln.copy_bytes[0] += h2d_bytes;
 	// ---- seeding
@@ -788,20 +768,32 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 	return BMH_OK;
 }
 
+// a batch of a read file in pinned host memory, filled by the loader thread (batch_queue.h) and read by a lane: the letters go to the device straight from here
+struct fbatch_t {
+	hbuf_t<uint8_t> ascii, codes, names; hbuf_t<uint64_t> offs, name_offs; hbuf_t<uint32_t> lens;
+	hbuf_t<uint8_t> quals, comments; hbuf_t<uint64_t> comment_offs;        // a FASTQ file's qualities; -C: the comments
+	bmh_read_set_t rs; uint32_t index = 0; int64_t id0 = 0;
+	// room for a batch of nr reads, nb bases, nn bytes of names (fq: with qualities; cm: with ncm bytes of comments), and o's pointers into it.  The nt4 codes always:
+	// every host form reads them (pairs' walks, ALT reads, a batch the device tail refuses, the host formatter)
+	int size(const char *fn, uint64_t nr, uint64_t nb, uint64_t nn, uint64_t ncm, bool fq, bool cm, bmh_read_set_t *o)
+	{
+		if (nb >> 31) { bmh_set_error("%s: a batch holds 2^31 bases or more", fn); return BMH_EINVAL; }      // offsets inside a batch are 32-bit
+		RCK(ascii.need(nb + 16)); RCK(codes.need(nb + 16)); RCK(names.need(nn + 16)); RCK(offs.need(nr + 2)); RCK(name_offs.need(nr + 2)); RCK(lens.need(nr + 2));
+		if (fq) RCK(quals.need(nb + 16));
+		if (cm) { RCK(comments.need(ncm + 16)); RCK(comment_offs.need(nr + 2)); }
+		o->ascii = ascii.p; o->codes = codes.p; o->names = names.p; o->offs = offs.p; o->name_offs = name_offs.p; o->lens = lens.p;
+		if (fq) o->quals = quals.p;
+		if (cm) { o->comments = comments.p; o->comment_offs = comment_offs.p; }
+		return BMH_OK;
+	}
+};
+
 }   // namespace
 
 extern "C" {
 
 // (lanes and result objects stay with the aligner between runs: their workspaces and pinned buffers -- gigabytes for million-read batches
 // -- cost more to allocate than a batch costs to align)
-namespace {
-struct fbatch_t {
-	hbuf_t<uint8_t> ascii, codes, names; hbuf_t<uint64_t> offs, name_offs; hbuf_t<uint32_t> lens;
-	hbuf_t<uint8_t> quals, comments; hbuf_t<uint64_t> comment_offs;        // a FASTQ file's qualities; -C: the comments
-	bmh_read_set_t rs; uint32_t index = 0; int64_t id0 = 0;
-};
-}
-
 struct bmh_aligner {
 	std::vector<std::unique_ptr<fbatch_t>> fbatches;      // batch buffers of bmh_aligner_run_fasta (pinned host memory), kept between runs
 	aligner_t a;
@@ -907,6 +899,93 @@ struct batch_src_t {
 	std::function<void()> stop;                       // the run failed: stop producing, unblock next()
 };
 
+// ---- the output stage: what becomes of a finished batch's records.  One per run, its format the aligner's (h->a.out_fmt) when the run begins: SAM text and BAM members
+// go to the sink batch by batch; the runs of a sorted BAM are kept (h->store) and merged into the file at the end of the input.  A batch comes as its lane left it --
+// written on the device (R.text: text, members or a sorted run) -- or as the host formatter's parts of SAM text.  Not BMH_OK: the run fails, the message is set
+struct out_stage_t {
+	bmh_aligner *h; const int fmt; bmh_sam_sink_t sink; void *user; int n_threads; const char *fn;
+	uint64_t n_bytes = 0;                                           // handed to the sink so far
+	int emit(const void *p, size_t n) { if (n && sink(user, (const char *)p, n) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; } n_bytes += n; return BMH_OK; }
+	// (the index is valid again once the merge has written the whole file)
+	int begin() { if (fmt == BMH_OUT_BAM_SORTED) { h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), fn)); h->sort_ix.valid = false; } return BMH_OK; }
+	int device_batch(const result_t &R)
+	{
+		if (fmt != BMH_OUT_BAM_SORTED) return emit(R.text.p, (size_t)R.text_len);
+		return R.n_rec ? h->store.append((const uint8_t *)R.text.p, R.text_len, R.skeys.p, R.soff.p, R.n_rec) : BMH_OK;      // a sorted run: kept until the end of the input
+	}
+	int host_batch(const std::vector<std::string> &parts)
+	{
+		if (fmt == BMH_OUT_SAM) { for (const std::string &part : parts) RCK(emit(part.data(), part.size())); return BMH_OK; }
+		// BAM: the text through the two host cores, the same records and members (sorted: the same run) as the device's
+		const aligner_t &A = h->a;
+		std::string all;
+		for (const std::string &part : parts) all += part;
+		uint8_t *bam = nullptr, *mem = nullptr; uint64_t bb = 0, mb = 0; uint32_t *st = nullptr, nrec = 0, r = 0;
+		int rc = bmh_sam_to_bam_host(all.data(), all.size(), A.n_contigs, A.ctg_blob.data(), A.ctg_noff.data(), n_threads, &bam, &bb, &st, &nrec);
+		while (rc == BMH_OK && r < nrec && !st[r]) ++r;
+		if (rc == BMH_OK && r < nrec) {                              // the first refused record: line r of the text, its name the line's first field
+			const char *a = all.data(), *const end = a + all.size();
+			for (uint32_t k = 0; k < r; ++k) a = (const char *)memchr(a, '\n', (size_t)(end - a)) + 1;
+			const char *e = a;
+			while (e < end && e - a < 254 && *e != '\t' && *e != '\n') ++e;
+			rc = bam_refused(std::string(a, e), st[r]);
+		}
+		if (rc == BMH_OK && fmt == BMH_OUT_BAM_SORTED) {
+			std::vector<uint64_t> off, keys, soff(1, 0); std::vector<uint32_t> ord; std::vector<uint8_t> srt;
+			rc = bsr_walk(bam, bb, A.n_contigs, off, fn);
+			if (rc == BMH_OK) {
+				bsr_sort_host(bam, off, keys, ord);
+				srt.reserve((size_t)bb + 1);
+				for (uint32_t i : ord) { srt.insert(srt.end(), bam + off[i], bam + off[i + 1]); soff.push_back(srt.size()); }
+				if (!ord.empty()) rc = h->store.append(srt.data(), bb, keys.data(), soff.data(), ord.size());
+			}
+		} else if (rc == BMH_OK) {
+			rc = bmh_bgzf_deflate_host(bam, bb, A.out_level, n_threads, &mem, &mb);
+			if (rc == BMH_OK) rc = emit(mem, (size_t)mb);
+		}
+		bmh_free(bam); bmh_free(st); bmh_free(mem);
+		return rc;
+	}
+	// the end of the input.  Sorted: every run's keys sorted once more, the file written window by window (csrc/bam_sort_kernels.hip), on the first lane's stream
+	static int forward(void *u, const char *b, size_t n) { out_stage_t *o = (out_stage_t *)u; o->n_bytes += n; return o->sink(o->user, b, n); }
+	int end(bool trace)
+	{
+		if (fmt != BMH_OUT_BAM_SORTED) return BMH_OK;
+		lane_t &L0 = *h->lanes[0];
+		int rc = BMH_OK;
+		if (!L0.bam && !(L0.bam = bmh_bam_ws_create())) rc = BMH_ENOMEM;
+		if (rc == BMH_OK && !L0.bsr && !(L0.bsr = bsr_dev_create())) rc = BMH_ENOMEM;
+		const double tm0 = now_s();
+		if (rc == BMH_OK) rc = bsr_merge_device(L0.bsr, L0.bam, h->store, h->sort_window, h->a.out_level, L0.st, h->sort_ix, forward, this);
+		if (trace) fprintf(stderr, "[aligner] sorted output: %zu runs (%llu spilled) merged in %.1f ms\n", h->store.runs.size(), (unsigned long long)h->store.spilled, (now_s() - tm0) * 1e3);
+		h->store.clear();
+		if (rc == BMH_OK) h->sort_ix.valid = true;
+		return rc;
+	}
+};
+
+// a batch whose text the device did not write (the A/B and cross-check forms of run_batch), through the host formatter: its text in `parts`
+static bool format_on_host(const aligner_t &A, const result_t &R, bool paired, std::vector<std::string> &parts)
+{
+	const bmh_read_set_t *rs = R.rs;
+	bmh_post_opt_t po = A.po; po.id0 = R.id0;
+	const uint64_t a0 = rs->offs[R.b0];
+	std::vector<uint64_t> offs64(R.n), noff(R.n);
+	const uint64_t n0 = rs->name_offs[R.b0];
+	for (uint32_t r = 0; r < R.n; ++r) { offs64[r] = rs->offs[R.b0 + r] - a0; noff[r] = rs->name_offs[R.b0 + r] - n0; }
+	const bool cm = A.po.copy_comment && rs->comments && rs->comment_offs;
+	std::vector<uint64_t> coff(cm ? R.n : 0);
+	const uint64_t c0 = cm ? rs->comment_offs[R.b0] : 0;
+	for (uint32_t r = 0; cm && r < R.n; ++r) coff[r] = rs->comment_offs[R.b0 + r] - c0;
+	bmh_cigar_src_t cs;
+	if (R.slot.empty()) cs.slot32 = R.slot32.p; else cs.slot64 = R.slot.data();
+	cs.aln = R.aln.p; cs.packed = R.packed.p; cs.off = R.off.p;
+	return bmh_format_sam_parts(&po, R.n, (const char *)rs->names + n0, noff.data(), rs->codes + a0, offs64.data(), rs->lens + R.b0, A.n_contigs,
+	                            A.name_ptr.data(), A.off.data(), R.fin.p, R.opr.p, cs,
+	                            paired ? R.h_rec.data() : nullptr, paired ? R.unflag.data() : nullptr, parts,
+	                            rs->quals ? rs->quals + a0 : nullptr, cm ? (const char *)rs->comments + c0 : nullptr, cm ? coff.data() : nullptr);
+}
+
 static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int paired, int n_lanes, int n_threads, bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats)
 {
 	const aligner_t &A = h->a;
@@ -947,8 +1026,8 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 	}
 	for (auto &ln : h->lanes) { for (double &v : ln->t) v = 0.0; ln->copy_ms[0] = ln->copy_ms[1] = 0.0; ln->copy_bytes[0] = ln->copy_bytes[1] = 0; ln->host_tail = 0; }
 	h->host_tail_batches = 0;
-	const bool sorted = A.out_fmt == BMH_OUT_BAM_SORTED;
-	if (sorted) { h->store.clear(); RCK(h->sort_ix.init(A.n_contigs, A.len.data(), fn)); h->sort_ix.valid = false; }      // (valid again once the merge has written the whole file)
+	out_stage_t out = {h, A.out_fmt, sink, user, n_threads, fn};
+	RCK(out.begin());
 	auto worker = [&](int lane_index) {
 		if (hipSetDevice(dev) != hipSuccess) { fail(BMH_ENODEV, "hipSetDevice failed in a worker thread"); return; }
 		lane_t &Ln = *h->lanes[(size_t)lane_index];
@@ -985,7 +1064,7 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 		--workers_alive;                                             // (the writer ends when every worker has: a batch that was taken is in `done` by then)
 		cv.notify_all();
 	};
-	double t_format = 0.0; uint64_t n_bytes = 0; uint32_t n_written = 0;
+	double t_format = 0.0; uint32_t n_written = 0;
 	auto writer = [&]() {
 		std::vector<std::string> &parts = h->parts;                  // (kept with the aligner: their capacity is the text of a batch)
 		for (uint32_t b = 0;; ++b) {
@@ -997,72 +1076,17 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 				if (!done.count(b)) return;                             // (every batch written)
 				R = std::move(done[b]); done.erase(b);
 			}
-			const bmh_read_set_t *rs = R->rs;
-			if (R->n && R->has_text) {                               // written on the device: nothing to format
-				const double ts0 = now_s();
-				if (sorted) {                                          // a sorted run: kept until the end of the input
-					if (R->n_rec) { const int rc = h->store.append((const uint8_t *)R->text.p, R->text_len, R->skeys.p, R->soff.p, R->n_rec); if (rc != BMH_OK) { fail(rc, bmh_last_error()); return; } }
-				} else
-				if (R->text_len) { if (sink(user, R->text.p, (size_t)R->text_len) != 0) { fail(BMH_EINVAL, "the sink refused the text"); return; } n_bytes += R->text_len; }
-				if (trace) fprintf(stderr, "[aligner] writer batch %u: text of the device, sink %.1f .. %.1f ms\n", b, (ts0 - t_start) * 1e3, (now_s() - t_start) * 1e3);
-			} else if (R->n) {
+			if (R->n) {                                              // written on the device: nothing to format; else the host formatter first
 				const double t0 = now_s();
-				bmh_post_opt_t po = A.po; po.id0 = R->id0;
-				const uint64_t a0 = rs->offs[R->b0];
-				std::vector<uint64_t> offs64(R->n), noff(R->n);
-				const uint64_t n0 = rs->name_offs[R->b0];
-				for (uint32_t r = 0; r < R->n; ++r) { offs64[r] = rs->offs[R->b0 + r] - a0; noff[r] = rs->name_offs[R->b0 + r] - n0; }
-				const bool cm = A.po.copy_comment && rs->comments && rs->comment_offs;
-				std::vector<uint64_t> coff(cm ? R->n : 0);
-				const uint64_t c0 = cm ? rs->comment_offs[R->b0] : 0;
-				for (uint32_t r = 0; cm && r < R->n; ++r) coff[r] = rs->comment_offs[R->b0 + r] - c0;
-				bmh_cigar_src_t cs;
-				if (R->slot.empty()) cs.slot32 = R->slot32.p; else cs.slot64 = R->slot.data();
-				cs.aln = R->aln.p; cs.packed = R->packed.p; cs.off = R->off.p;
-				const bool ok = bmh_format_sam_parts(&po, R->n, (const char *)rs->names + n0, noff.data(), rs->codes + a0, offs64.data(), rs->lens + R->b0, A.n_contigs,
-				                                     A.name_ptr.data(), A.off.data(), R->fin.p, R->opr.p, cs,
-				                                     paired ? R->h_rec.data() : nullptr, paired ? R->unflag.data() : nullptr, parts,
-				                                     rs->quals ? rs->quals + a0 : nullptr, cm ? (const char *)rs->comments + c0 : nullptr, cm ? coff.data() : nullptr);
-				if (!ok) { fail(BMH_EINVAL, bmh_last_error()); return; }
-				t_format += now_s() - t0;
-				const double ts0 = now_s();
-				if (A.out_fmt == BMH_OUT_BAM || sorted) {               // the host formatter's text through the two host cores: the same members as the device's
-					std::string all;
-					for (const std::string &part : parts) all += part;
-					uint8_t *bam = nullptr, *mem = nullptr; uint64_t bb = 0, mb = 0; uint32_t *st = nullptr, nrec = 0;
-					int rc = bmh_sam_to_bam_host(all.data(), all.size(), A.n_contigs, A.ctg_blob.data(), A.ctg_noff.data(), n_threads, &bam, &bb, &st, &nrec);
-					if (rc == BMH_OK) for (uint32_t r = 0; r < nrec; ++r) if (st[r]) {
-						size_t a = 0;
-						for (uint32_t k = 0; k < r; ++k) a = all.find('\n', a) + 1;
-						size_t e = a;
-						while (e < all.size() && e - a < 254 && all[e] != '\t' && all[e] != '\n') ++e;
-						bmh_set_error("BAM output: read '%s': its SAM record cannot be written as BAM: %s", all.substr(a, e - a).c_str(), bmh_bam_status_name(st[r]));
-						rc = BMH_EINVAL; break;
-					}
-					if (rc == BMH_OK && sorted) {                        // the host form of the sort: the same run as the device's
-						std::vector<uint64_t> off, keys, soff(1, 0); std::vector<uint32_t> ord; std::vector<uint8_t> srt;
-						rc = bsr_walk(bam, bb, A.n_contigs, off, fn);
-						if (rc == BMH_OK) {
-							bsr_sort_host(bam, off, keys, ord);
-							srt.reserve((size_t)bb + 1);
-							for (uint32_t i : ord) { srt.insert(srt.end(), bam + off[i], bam + off[i + 1]); soff.push_back(srt.size()); }
-							if (!ord.empty()) rc = h->store.append(srt.data(), bb, keys.data(), soff.data(), ord.size());
-						}
-					} else
-					if (rc == BMH_OK) rc = bmh_bgzf_deflate_host(bam, bb, A.out_level, n_threads, &mem, &mb);
-					bmh_free(bam); bmh_free(st);
-					if (rc != BMH_OK) { bmh_free(mem); fail(rc, bmh_last_error()); return; }
-					const int refused = mb ? sink(user, (const char *)mem, (size_t)mb) : 0;
-					bmh_free(mem);
-					if (refused) { fail(BMH_EINVAL, "the sink refused the text"); return; }
-					n_bytes += mb;
-				} else
-				for (const std::string &part : parts) {
-					if (part.empty()) continue;
-					if (sink(user, part.data(), part.size()) != 0) { fail(BMH_EINVAL, "the sink refused the text"); return; }
-					n_bytes += part.size();
+				if (!R->has_text) {
+					if (!format_on_host(A, *R, paired != 0, parts)) { fail(BMH_EINVAL, bmh_last_error()); return; }
+					t_format += now_s() - t0;
 				}
-				if (trace) fprintf(stderr, "[aligner] writer batch %u: format %.1f .. %.1f ms, sink .. %.1f\n", b, (t0 - t_start) * 1e3, (ts0 - t_start) * 1e3, (now_s() - t_start) * 1e3);
+				const double ts0 = now_s();
+				const int rc = R->has_text ? out.device_batch(*R) : out.host_batch(parts);
+				if (rc != BMH_OK) { fail(rc, bmh_last_error()); return; }
+				if (trace && R->has_text) fprintf(stderr, "[aligner] writer batch %u: text of the device, sink %.1f .. %.1f ms\n", b, (ts0 - t_start) * 1e3, (now_s() - t_start) * 1e3);
+				else if (trace) fprintf(stderr, "[aligner] writer batch %u: format %.1f .. %.1f ms, sink .. %.1f\n", b, (t0 - t_start) * 1e3, (ts0 - t_start) * 1e3, (now_s() - t_start) * 1e3);
 			}
 			if (src.release) src.release(R->token);
 			R->token = nullptr; R->rs = nullptr;
@@ -1083,25 +1107,11 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 	n_results = (int)pool.size();                                   // (after a failed run the results that were in flight are gone)
 	for (auto &ln : h->lanes) h->host_tail_batches += ln->host_tail;
 	if (first_rc != BMH_OK) { h->store.clear(); bmh_set_error("%s", first_err.c_str()); return first_rc; }
-	if (sorted) {
-		// the end of the input: every run's keys sorted once more, the file written window by window (csrc/bam_sort_kernels.hip), on the first lane's stream
-		struct out_t { bmh_sam_sink_t sink; void *user; uint64_t n; } o = {sink, user, 0};
-		auto fwd = [](void *u, const char *b, size_t n) { out_t *p = (out_t *)u; p->n += n; return p->sink(p->user, b, n); };
-		lane_t &L0 = *h->lanes[0];
-		int rc = BMH_OK;
-		if (!L0.bam && !(L0.bam = bmh_bam_ws_create())) rc = BMH_ENOMEM;
-		if (rc == BMH_OK && !L0.bsr && !(L0.bsr = bsr_dev_create())) rc = BMH_ENOMEM;
-		const double tm0 = now_s();
-		if (rc == BMH_OK) rc = bsr_merge_device(L0.bsr, L0.bam, h->store, h->sort_window, A.out_level, L0.st, h->sort_ix, fwd, &o);
-		if (trace) fprintf(stderr, "[aligner] sorted output: %zu runs (%llu spilled) merged in %.1f ms\n", h->store.runs.size(), (unsigned long long)h->store.spilled, (now_s() - tm0) * 1e3);
-		t_format += now_s() - tm0;
-		h->store.clear();
-		if (rc != BMH_OK) return rc;
-		h->sort_ix.valid = true;
-		n_bytes += o.n;
-	}
+	const double te = now_s();
+	RCK(out.end(trace));
+	t_format += now_s() - te;
 	if (stats) {
-		stats->n_reads = n_reads_total; stats->n_bytes = n_bytes; stats->n_batches = n_written; stats->n_lanes = n_lanes;
+		stats->n_reads = n_reads_total; stats->n_bytes = out.n_bytes; stats->n_batches = n_written; stats->n_lanes = n_lanes;
 		stats->seconds = now_s() - t_start; stats->format_seconds = t_format;
 		stats->h2d_seconds = lane_t_sum[0]; stats->seed_seconds = lane_t_sum[1]; stats->chain_extend_seconds = lane_t_sum[2]; stats->tail_seconds = lane_t_sum[3];
 		stats->select_seconds = lane_t_sum[4]; stats->cigar_seconds = lane_t_sum[5]; stats->gate_wait_seconds = lane_t_sum[6];
@@ -1164,14 +1174,12 @@ int bmh_aligner_run(bmh_aligner_t *h, const bmh_read_set_t *rs, const uint64_t *
 	return run_core(h, src, "bmh_aligner_run", paired, n_lanes, n_threads, sink, user, stats);
 }
 
-// ---- the same from a read FILE, batch by batch: a loader thread cuts the mapped file the way the reference's bseq_read cuts its stream (reads are added until the
-// batch holds at least batch_bases bases -- or exactly batch_reads reads if that is not 0 -- and, paired, an even number of reads; src/bwa.c:48-66) and fills every
-// batch into pinned host memory (csrc/reads_io.cpp: bmh_fasta_cut / bmh_fasta_fill, on host threads) while the lanes are on the batches before it: the letters go to
-// the device straight from there, nothing of the file is held beyond the batches in flight (n_lanes + 3 of them).
+// ---- the same from read FILES, batch by batch: a loader thread (batch_queue.h) fills every batch into pinned host memory (fbatch_t) while the lanes are on the batches
+// before it; nothing of the file is held beyond the batches in flight (n_lanes + 3 of them).  A batch ends the way the reference's bseq_read ends one (reads are added
+// until it holds at least batch_bases bases -- or exactly batch_reads reads if that is not 0 -- and, paired, an even number of reads; src/bwa.c:48-66).
 
-// either: FASTA or FASTQ (bmh_aligner_run_file), else FASTA only (bmh_aligner_run_fasta); fn: the entry point's name in messages
-static int run_file(bmh_aligner_t *h, const char *path, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
-                    bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats, bool either, const char *fn)
+// the arguments every such run checks, and the clamps of the batch's size
+static int file_run_args(const char *fn, bmh_aligner_t *h, const char *path, bmh_sam_sink_t sink, bmh_align_stats_t *stats, uint64_t &batch_bases, uint64_t &batch_reads, int paired, int &n_lanes, int &n_threads)
 {
 	if (!h || !path || !sink) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	if (stats) memset(stats, 0, sizeof(*stats));
@@ -1180,184 +1188,102 @@ static int run_file(bmh_aligner_t *h, const char *path, uint64_t batch_bases, ui
 	if (paired && (batch_reads & 1)) --batch_reads;
 	if (n_lanes < 1) n_lanes = 1;
 	if (n_threads < 1) n_threads = bmh_effective_cpus();
-	const int fd = open(path, O_RDONLY);
-	if (fd < 0) { bmh_set_error("%s: cannot open %s", fn, path); return BMH_EINVAL; }
-	struct stat sb;
-	if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { close(fd); bmh_set_error("%s: %s is not a regular, seekable file", fn, path); return BMH_EINVAL; }
-	const size_t sz = (size_t)sb.st_size;
-	if (sz == 0) { close(fd); return BMH_OK; }
-	void *m = mmap(nullptr, sz, PROT_READ, MAP_PRIVATE, fd, 0);
-	close(fd);
-	if (m == MAP_FAILED) { bmh_set_error("%s: cannot map %s (%zu bytes)", fn, path, sz); return BMH_ENOMEM; }
-	(void)madvise(m, sz, MADV_SEQUENTIAL);
-	const uint8_t *buf = (const uint8_t *)m;
+	return BMH_OK;
+}
+
+// what the loaders refuse of a batch: an odd number of reads in a paired file; once it is filled, a read longer than the aligner takes.  Else 1: the batch's place in the run
+static int even_batch(const char *fn, int paired, uint64_t nr) { if (paired && (nr & 1)) { bmh_set_error("%s: an odd number of reads in a paired file", fn); return BMH_EINVAL; } return BMH_OK; }
+static int accept_batch(const char *fn, int paired, fbatch_t &fb, int64_t &id0)
+{
+	const uint64_t nr = fb.rs.n_reads;
+	RCK(even_batch(fn, paired, nr));
+	for (uint64_t r = 0; r < nr; ++r)
+		if (fb.lens.p[r] > BMH_EXT_LONG_MAX) { bmh_set_error("%s: read %lld has %u bases: the longest read the aligner takes has %d (BMH_EXT_LONG_MAX)", fn, (long long)(id0 + (int64_t)r), fb.lens.p[r], BMH_EXT_LONG_MAX); return BMH_EINVAL; }
+	fb.id0 = id0; id0 += (int64_t)nr;
+	return 1;
+}
+
+// the run: `fill` (1: fb holds the next batch, 0: the end, < 0: refused, the message set) on the loader thread, the lanes behind it.  after_release: a refusal fails
+// the run only when the batches before it have been written (a file that ends before its mate file: the complete pairs first); else as soon as the lanes reach it
+static int run_loaded(bmh_aligner_t *h, const char *fn, int dev, const std::function<int(fbatch_t &)> &fill, bool after_release, int paired, int n_lanes, int n_threads,
+                      bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats)
+{
+	batch_queue_t<fbatch_t> q(h->fbatches, n_lanes + 3, after_release);
+	batch_src_t src;
+	src.next = [&](batch_t &bt) {
+		fbatch_t *fb = nullptr; std::string err;
+		const int got = q.next(&fb, err);
+		if (got < 0) bmh_set_error("%s", err.c_str());
+		if (got == 1) { bt.index = fb->index; bt.rs = &fb->rs; bt.b0 = 0; bt.b1 = (uint32_t)fb->rs.n_reads; bt.id0 = fb->id0; bt.pinned = true; bt.token = fb; }
+		return got;
+	};
+	src.release = [&](void *tok) { q.release((fbatch_t *)tok); };
+	src.stop = [&]() { q.stop(); };
+	q.start([&](fbatch_t &fb, std::string &err) { const int rc = fill(fb); if (rc < 0) err = bmh_last_error(); return rc; },
+	        [dev](std::string &err) { if (hipSetDevice(dev) == hipSuccess) return (int)BMH_OK; err = "hipSetDevice failed in the loader thread"; return (int)BMH_ENODEV; });
+	const int rc = run_core(h, src, fn, paired, n_lanes, n_threads, sink, user, stats);
+	q.join();
+	return rc;
+}
+
+// one FASTA file (bmh_aligner_run_fasta) or, either: one FASTA or FASTQ file (bmh_aligner_run_file), one record per line group: the mapped file cut and filled on
+// host threads (csrc/reads_io.cpp: bmh_fasta_cut / bmh_fasta_fill); fn: the entry point's name in messages
+static int run_file(bmh_aligner_t *h, const char *path, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
+                    bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats, bool either, const char *fn)
+{
+	RCK(file_run_args(fn, h, path, sink, stats, batch_bases, batch_reads, paired, n_lanes, n_threads));
+	const uint8_t *buf = nullptr; size_t sz = 0;
+	RCK(bmh_map_file(fn, path, &buf, &sz));
+	if (sz == 0) return BMH_OK;
 	bmh_reads_fmt_t fmt;
 	fmt.either = either;
 	fmt.fq = either && bmh_reads_detect(buf, sz);
 	fmt.comments = either && h->a.po.copy_comment;        // (the comments are read only when the records carry them)
-	const bool need_codes = true;        // nt4 codes: every host form reads them (pairs' walks, ALT reads, a batch the device tail refuses, the host formatter)
 	int dev = 0;
-	if (hipGetDevice(&dev) != hipSuccess) { (void)munmap(m, sz); bmh_set_error("%s: no HIP device", fn); return BMH_ENODEV; }
-	// the loader: batches in file order into `ready`; at most n_lanes + 3 batch buffers exist
-	std::mutex qm; std::condition_variable qcv;
-	std::vector<std::unique_ptr<fbatch_t>> &all = h->fbatches; std::vector<fbatch_t *> free_list; std::map<uint32_t, fbatch_t *> ready;
-	for (auto &fb : all) free_list.push_back(fb.get());
-	uint32_t next_out = 0; bool eof = false, stopped = false; int load_rc = BMH_OK; std::string load_err;
-	const int max_batches = n_lanes + 3;
+	if (hipGetDevice(&dev) != hipSuccess) { (void)munmap((void *)buf, sz); bmh_set_error("%s: no HIP device", fn); return BMH_ENODEV; }
 	const int load_threads = n_threads < 8 ? n_threads : 8;
-	auto loader = [&]() {
-		if (hipSetDevice(dev) != hipSuccess) { std::lock_guard<std::mutex> lk(qm); load_rc = BMH_ENODEV; load_err = "hipSetDevice failed in the loader thread"; eof = true; qcv.notify_all(); return; }
-		size_t p = 0, est = 0; uint32_t index = 0; int64_t id0 = 0;
+	size_t p = 0, est = 0; int64_t id0 = 0;                 // where the next batch begins, the last one's size in the file, its first read's index in the run
+	auto fill = [&](fbatch_t &fb) {
 		while (p < sz) {
-			fbatch_t *fb = nullptr;
-			{
-				std::unique_lock<std::mutex> lk(qm);
-				qcv.wait(lk, [&] { return stopped || !free_list.empty() || (int)all.size() < max_batches; });
-				if (stopped) break;
-				if (!free_list.empty()) { fb = free_list.back(); free_list.pop_back(); }
-				else { all.emplace_back(new fbatch_t()); fb = all.back().get(); }
-			}
-			size_t end = sz; uint64_t nr = 0, nb = 0, nn = 0;
-			uint64_t ncm = 0;
-			int rc = bmh_fasta_cut(buf, sz, p, batch_bases, batch_reads, /* even counts, as bseq_read ends its batches */ batch_reads == 0, load_threads, est, &end, &nr, &nb, &nn,
-			                       fmt, &ncm);
-			if (rc == BMH_OK && paired && (nr & 1)) { bmh_set_error("%s: an odd number of reads in a paired file", fn); rc = BMH_EINVAL; }
-			if (rc == BMH_OK && (nb >> 31)) { bmh_set_error("%s: a batch holds 2^31 bases or more", fn); rc = BMH_EINVAL; }
-			if (rc == BMH_OK && nr) {
-				if (fb->ascii.need(nb + 16) != BMH_OK || (need_codes && fb->codes.need(nb + 16) != BMH_OK) || fb->names.need(nn + 16) != BMH_OK || fb->offs.need(nr + 2) != BMH_OK ||
-				    fb->name_offs.need(nr + 2) != BMH_OK || fb->lens.need(nr + 2) != BMH_OK) rc = BMH_ENOMEM;
-				if (fmt.fq && fb->quals.need(nb + 16) != BMH_OK) rc = BMH_ENOMEM;
-				if (fmt.comments && (fb->comments.need(ncm + 16) != BMH_OK || fb->comment_offs.need(nr + 2) != BMH_OK)) rc = BMH_ENOMEM;
-			}
-			if (rc == BMH_OK && nr) {
-				memset(&fb->rs, 0, sizeof(fb->rs));
-				fb->rs.ascii = fb->ascii.p; fb->rs.codes = need_codes ? fb->codes.p : nullptr; fb->rs.names = fb->names.p; fb->rs.offs = fb->offs.p; fb->rs.name_offs = fb->name_offs.p; fb->rs.lens = fb->lens.p;
-				if (fmt.fq) fb->rs.quals = fb->quals.p;
-				if (fmt.comments) { fb->rs.comments = fb->comments.p; fb->rs.comment_offs = fb->comment_offs.p; }
-				rc = bmh_fasta_fill(buf, p, end, nr, nb, nn, load_threads, &fb->rs, fmt, ncm);
-				if (rc == BMH_OK) for (uint64_t r = 0; r < nr; ++r) if (fb->lens.p[r] > BMH_EXT_LONG_MAX) { bmh_set_error("%s: read %lld has %u bases: the longest read the aligner takes has %d (BMH_EXT_LONG_MAX)", fn, (long long)(id0 + (int64_t)r), fb->lens.p[r], BMH_EXT_LONG_MAX); rc = BMH_EINVAL; break; }
-			}
-			std::lock_guard<std::mutex> lk(qm);
-			if (rc != BMH_OK) { load_rc = rc; load_err = bmh_last_error(); free_list.push_back(fb); break; }
-			if (nr == 0) { free_list.push_back(fb); p = end; continue; }
-			fb->index = index++; fb->id0 = id0; id0 += (int64_t)nr;
+			size_t end = sz; uint64_t nr = 0, nb = 0, nn = 0, ncm = 0;
+			RCK(bmh_fasta_cut(buf, sz, p, batch_bases, batch_reads, /* even counts, as bseq_read ends its batches */ batch_reads == 0, load_threads, est, &end, &nr, &nb, &nn, fmt, &ncm));
+			if (nr == 0) { p = end; continue; }
+			RCK(even_batch(fn, paired, nr));                        // (before anything is allocated for it)
+			memset(&fb.rs, 0, sizeof(fb.rs));
+			RCK(fb.size(fn, nr, nb, nn, ncm, fmt.fq, fmt.comments, &fb.rs));
+			RCK(bmh_fasta_fill(buf, p, end, nr, nb, nn, load_threads, &fb.rs, fmt, ncm));
 			est = end - p; p = end;
-			ready[fb->index] = fb;
-			qcv.notify_all();
+			return accept_batch(fn, paired, fb, id0);
 		}
-		std::lock_guard<std::mutex> lk(qm);
-		eof = true;
-		qcv.notify_all();
+		return 0;
 	};
-	batch_src_t src;
-	src.next = [&](batch_t &bt) {
-		std::unique_lock<std::mutex> lk(qm);
-		qcv.wait(lk, [&] { return stopped || ready.count(next_out) || eof; });
-		if (stopped) return 0;
-		if (!ready.count(next_out)) { if (load_rc != BMH_OK) { bmh_set_error("%s", load_err.c_str()); return load_rc; } return 0; }
-		fbatch_t *fb = ready[next_out]; ready.erase(next_out); ++next_out;
-		bt.index = fb->index; bt.rs = &fb->rs; bt.b0 = 0; bt.b1 = (uint32_t)fb->rs.n_reads; bt.id0 = fb->id0; bt.pinned = true; bt.token = fb;
-		return 1;
-	};
-	src.release = [&](void *tok) { if (!tok) return; std::lock_guard<std::mutex> lk(qm); free_list.push_back((fbatch_t *)tok); qcv.notify_all(); };
-	src.stop = [&]() { std::lock_guard<std::mutex> lk(qm); stopped = true; qcv.notify_all(); };
-	std::thread lt(loader);
-	const int rc = run_core(h, src, fn, paired, n_lanes, n_threads, sink, user, stats);
-	src.stop();
-	lt.join();
-	(void)munmap(m, sz);
+	const int rc = run_loaded(h, fn, dev, fill, false, paired, n_lanes, n_threads, sink, user, stats);
+	(void)munmap((void *)buf, sz);
 	return rc;
 }
 
-}
+}   // extern "C"
 
-// ---- the same from one or two read files of any shape (multi-line, gzip / BGZF, R1 + R2): the loader thread drives the pump of csrc/reads_parse.hip -- text
-// windows in pinned memory, records cut on the device (or walked by the host where the device hands a window back) -- and every batch lands in an fbatch_t
-// as run_file's batches do, so the lanes take them exactly as they take those
+// one or two read files of any shape (multi-line, gzip / BGZF, R1 + R2): the loader drives the pump of csrc/reads_parse.hip -- text windows in pinned memory, records
+// cut on the device (or walked by the host where the device hands a window back)
 int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
                           bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats)
 {
 	const char *fn = "bmh_aligner_run_files";
-	if (!h || !path1 || !sink) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (stats) memset(stats, 0, sizeof(*stats));
-	if (batch_bases == 0 && batch_reads == 0) { bmh_set_error("%s: batch_bases or batch_reads must be given", fn); return BMH_EINVAL; }
-	if (batch_bases >= (1ull << 31) - 4096) batch_bases = (1ull << 31) - 4096;      // offsets inside a batch are 32-bit
 	if (path2) paired = 1;
-	if (paired && (batch_reads & 1)) --batch_reads;
-	if (n_lanes < 1) n_lanes = 1;
-	if (n_threads < 1) n_threads = bmh_effective_cpus();
+	RCK(file_run_args(fn, h, path1, sink, stats, batch_bases, batch_reads, paired, n_lanes, n_threads));
 	int dev = 0;
 	if (hipGetDevice(&dev) != hipSuccess) { bmh_set_error("%s: no HIP device", fn); return BMH_ENODEV; }
 	const bool cm = h->a.po.copy_comment != 0;
 	bmh_reads_pump_t *P = bmh_pump_open(path1, path2, n_threads, cm, false, 0);
 	if (!P) return BMH_EINVAL;
-	std::mutex qm; std::condition_variable qcv;
-	std::vector<std::unique_ptr<fbatch_t>> &all = h->fbatches; std::vector<fbatch_t *> free_list; std::map<uint32_t, fbatch_t *> ready;
-	for (auto &fb : all) free_list.push_back(fb.get());
-	uint32_t next_out = 0; bool eof = false, stopped = false; int load_rc = BMH_OK; std::string load_err;
-	int outstanding = 0;                                  // batches handed to the lanes whose text has not been written yet
-	const int max_batches = n_lanes + 3;
-	auto loader = [&]() {
-		if (hipSetDevice(dev) != hipSuccess) { std::lock_guard<std::mutex> lk(qm); load_rc = BMH_ENODEV; load_err = "hipSetDevice failed in the loader thread"; eof = true; qcv.notify_all(); return; }
-		uint32_t index = 0; int64_t id0 = 0;
-		for (;;) {
-			fbatch_t *fb = nullptr;
-			{
-				std::unique_lock<std::mutex> lk(qm);
-				qcv.wait(lk, [&] { return stopped || !free_list.empty() || (int)all.size() < max_batches; });
-				if (stopped) break;
-				if (!free_list.empty()) { fb = free_list.back(); free_list.pop_back(); }
-				else { all.emplace_back(new fbatch_t()); fb = all.back().get(); }
-			}
-			bmh_batch_alloc_t alloc = [&](uint64_t nr, uint64_t nb, uint64_t nn, uint64_t ncm, bool fq, bmh_read_set_t *rs) {
-				if (nb >> 31) { bmh_set_error("%s: a batch holds 2^31 bases or more", fn); return (int)BMH_EINVAL; }
-				if (fb->ascii.need(nb + 16) != BMH_OK || fb->codes.need(nb + 16) != BMH_OK || fb->names.need(nn + 16) != BMH_OK || fb->offs.need(nr + 2) != BMH_OK ||
-				    fb->name_offs.need(nr + 2) != BMH_OK || fb->lens.need(nr + 2) != BMH_OK) return (int)BMH_ENOMEM;
-				if (fq && fb->quals.need(nb + 16) != BMH_OK) return (int)BMH_ENOMEM;
-				if (cm && (fb->comments.need(ncm + 16) != BMH_OK || fb->comment_offs.need(nr + 2) != BMH_OK)) return (int)BMH_ENOMEM;
-				rs->ascii = fb->ascii.p; rs->codes = fb->codes.p; rs->names = fb->names.p; rs->offs = fb->offs.p; rs->name_offs = fb->name_offs.p; rs->lens = fb->lens.p;
-				if (fq) rs->quals = fb->quals.p;
-				if (cm) { rs->comments = fb->comments.p; rs->comment_offs = fb->comment_offs.p; }
-				return (int)BMH_OK;
-			};
-			int rc = bmh_pump_next(P, batch_bases, batch_reads, /* even counts, as bseq_read ends its batches */ batch_reads == 0, false, alloc, &fb->rs);
-			const uint64_t nr = rc == 1 ? fb->rs.n_reads : 0;
-			if (rc == 1 && paired && (nr & 1)) { bmh_set_error("%s: an odd number of reads in a paired file", fn); rc = BMH_EINVAL; }
-			if (rc == 1) for (uint64_t r = 0; r < nr; ++r) if (fb->lens.p[r] > BMH_EXT_LONG_MAX) { bmh_set_error("%s: read %lld has %u bases: the longest read the aligner takes has %d (BMH_EXT_LONG_MAX)", fn, (long long)(id0 + (int64_t)r), fb->lens.p[r], BMH_EXT_LONG_MAX); rc = BMH_EINVAL; break; }
-			std::lock_guard<std::mutex> lk(qm);
-			if (rc < 0) { load_rc = rc; load_err = bmh_last_error(); free_list.push_back(fb); break; }
-			if (rc == 0) { free_list.push_back(fb); break; }
-			fb->index = index++; fb->id0 = id0; id0 += (int64_t)nr;
-			ready[fb->index] = fb;
-			qcv.notify_all();
-		}
-		std::lock_guard<std::mutex> lk(qm);
-		eof = true;
-		qcv.notify_all();
+	int64_t id0 = 0;
+	auto fill = [&](fbatch_t &fb) {
+		const bmh_batch_alloc_t alloc = [&](uint64_t nr, uint64_t nb, uint64_t nn, uint64_t ncm, bool fq, bmh_read_set_t *rs) { return fb.size(fn, nr, nb, nn, ncm, fq, cm, rs); };
+		const int rc = bmh_pump_next(P, batch_bases, batch_reads, /* even counts, as bseq_read ends its batches */ batch_reads == 0, false, alloc, &fb.rs);
+		return rc == 1 ? accept_batch(fn, paired, fb, id0) : rc;
 	};
-	batch_src_t src;
-	src.next = [&](batch_t &bt) {
-		std::unique_lock<std::mutex> lk(qm);
-		qcv.wait(lk, [&] { return stopped || ready.count(next_out) || eof; });
-		if (stopped) return 0;
-		if (!ready.count(next_out)) {
-			if (load_rc == BMH_OK) return 0;
-			// a refused file fails the run only when the batches before the refusal have been written (a file that ends before its mate file: the complete pairs first)
-			qcv.wait(lk, [&] { return stopped || outstanding == 0; });
-			if (stopped) return 0;
-			bmh_set_error("%s", load_err.c_str()); return load_rc;
-		}
-		fbatch_t *fb = ready[next_out]; ready.erase(next_out); ++next_out;
-		bt.index = fb->index; bt.rs = &fb->rs; bt.b0 = 0; bt.b1 = (uint32_t)fb->rs.n_reads; bt.id0 = fb->id0; bt.pinned = true; bt.token = fb;
-		++outstanding;
-		return 1;
-	};
-	src.release = [&](void *tok) { if (!tok) return; std::lock_guard<std::mutex> lk(qm); free_list.push_back((fbatch_t *)tok); --outstanding; qcv.notify_all(); };
-	src.stop = [&]() { std::lock_guard<std::mutex> lk(qm); stopped = true; qcv.notify_all(); };
-	std::thread lt(loader);
-	const int rc = run_core(h, src, fn, paired, n_lanes, n_threads, sink, user, stats);
-	src.stop();
-	lt.join();
+	const int rc = run_loaded(h, fn, dev, fill, true, paired, n_lanes, n_threads, sink, user, stats);
 	uint64_t cnt[4]; bmh_pump_counts(P, cnt); bmh_reads_note_counts(cnt);
 	uint64_t icnt[2]; bmh_pump_inflate_counts(P, icnt); bmh_reads_note_inflate_counts(icnt);
 	bmh_pump_close(P);
@@ -1366,12 +1292,8 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 
 int bmh_aligner_run_fasta(bmh_aligner_t *h, const char *path, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
                           bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats)
-{
-	return run_file(h, path, batch_bases, batch_reads, paired, n_lanes, n_threads, sink, user, stats, false, "bmh_aligner_run_fasta");
-}
+{ return run_file(h, path, batch_bases, batch_reads, paired, n_lanes, n_threads, sink, user, stats, false, "bmh_aligner_run_fasta"); }
 
 int bmh_aligner_run_file(bmh_aligner_t *h, const char *path, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
                          bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats)
-{
-	return run_file(h, path, batch_bases, batch_reads, paired, n_lanes, n_threads, sink, user, stats, true, "bmh_aligner_run_file");
-}   // extern "C"
+{ return run_file(h, path, batch_bases, batch_reads, paired, n_lanes, n_threads, sink, user, stats, true, "bmh_aligner_run_file"); }

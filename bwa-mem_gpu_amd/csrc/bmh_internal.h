@@ -73,6 +73,7 @@ int bmh_alt_records_device(int32_t *d_fin, uint64_t m, const uint32_t *d_rec_off
 // problems; a FASTA-only caller keeps its one message).  bmh_reads_detect: 1 when the first non-blank byte is '@'
 struct bmh_reads_fmt_t { bool fq = false; bool comments = false; bool either = false; };
 int bmh_reads_detect(const uint8_t *buf, size_t sz);
+int bmh_map_file(const char *fn, const char *path, const uint8_t **buf, size_t *sz);        // the file mapped for reading (the caller's to munmap); *sz = 0: empty, nothing mapped
 int bmh_fasta_cut(const uint8_t *buf, size_t sz, size_t p, uint64_t want_bases, uint64_t want_reads, bool even, int n_threads, size_t est_bytes,
                   size_t *end, uint64_t *n_reads, uint64_t *n_bases, uint64_t *n_name_bytes, const bmh_reads_fmt_t &fmt = bmh_reads_fmt_t(),
                   uint64_t *n_comment_bytes = nullptr);

@@ -451,22 +451,32 @@ int bmh_fasta_fill(const uint8_t *buf, size_t p, size_t end, uint64_t n_reads, u
 	return BMH_OK;
 }
 
+// a regular file mapped for reading from its start to its end: *buf [*sz], the caller's to munmap; an empty file: *sz = 0 and nothing mapped.  fn: the name in messages
+int bmh_map_file(const char *fn, const char *path, const uint8_t **buf, size_t *sz)
+{
+	*buf = nullptr; *sz = 0;
+	const int fd = open(path, O_RDONLY);
+	if (fd < 0) { bmh_set_error("%s: cannot open %s", fn, path); return BMH_EINVAL; }
+	struct stat sb;
+	if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { close(fd); bmh_set_error("%s: %s is not a regular, seekable file", fn, path); return BMH_EINVAL; }
+	const size_t n = (size_t)sb.st_size;
+	void *m = n ? mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0) : nullptr;
+	close(fd);
+	if (m == MAP_FAILED) { bmh_set_error("%s: cannot map %s (%zu bytes)", fn, path, n); return BMH_ENOMEM; }
+	if (n) (void)madvise(m, n, MADV_SEQUENTIAL);
+	*buf = (const uint8_t *)m; *sz = n;
+	return BMH_OK;
+}
+
 // reads, bases, name bytes and the longest read of a read file, without loading it (one counting pass of the mapped file on host threads): out[4]
 static int scan_reads(const char *fn, const char *path, int n_threads, bool fq_ok, uint64_t *out)
 {
 	if (!path || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	out[0] = out[1] = out[2] = out[3] = 0;
-	const int fd = open(path, O_RDONLY);
-	if (fd < 0) { bmh_set_error("%s: cannot open %s", fn, path); return BMH_EINVAL; }
-	struct stat sb;
-	if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { close(fd); bmh_set_error("%s: %s is not a regular, seekable file", fn, path); return BMH_EINVAL; }
-	const size_t sz = (size_t)sb.st_size;
-	if (sz == 0) { close(fd); return BMH_OK; }
-	void *m = mmap(nullptr, sz, PROT_READ, MAP_PRIVATE, fd, 0);
-	close(fd);
-	if (m == MAP_FAILED) { bmh_set_error("%s: cannot map %s (%zu bytes)", fn, path, sz); return BMH_ENOMEM; }
-	(void)madvise(m, sz, MADV_SEQUENTIAL);
-	const uint8_t *buf = (const uint8_t *)m;
+	const uint8_t *buf = nullptr; size_t sz = 0;
+	const int mrc = bmh_map_file(fn, path, &buf, &sz);
+	if (mrc != BMH_OK || sz == 0) return mrc;
+	void *m = (void *)buf;
 	const bool fq = fq_ok && bmh_reads_detect(buf, sz);
 	unsigned T = n_threads > 0 ? (unsigned)n_threads : (unsigned)bmh_effective_cpus();
 	if (T == 0) T = 1;
