@@ -213,6 +213,20 @@ def _raise_beyond_cap(e: Exception) -> None:
                                   "flanks of up to EXT_LONG_MAX bases; the reference's own GASAL2 build is sized by MAX_SEQ_LEN, README.md:38)") from e
 
 
+def markdup_metrics_text(counts: dict, rg_line: str = "") -> str:
+    """the Picard-style metrics table of a marked run: a class line, the header row and one row (one library per run: the read group's LB, else Unknown Library)"""
+    lib = "Unknown Library"
+    for f in rg_line.split("\t")[1:]:
+        if f.startswith("LB:") and len(f) > 3:
+            lib = f[3:]
+    fr, pr, df, dp = counts["fragments_examined"], counts["pairs_examined"], counts["duplicate_fragments"], counts["duplicate_pairs"]
+    den = fr + 2 * pr
+    cols = [("LIBRARY", lib), ("UNPAIRED_READS_EXAMINED", fr), ("READ_PAIRS_EXAMINED", pr), ("SECONDARY_OR_SUPPLEMENTARY_RDS", counts["secondary_or_supplementary"]),
+            ("UNMAPPED_READS", counts["unmapped_records"]), ("UNPAIRED_READ_DUPLICATES", df), ("READ_PAIR_DUPLICATES", dp),
+            ("PERCENT_DUPLICATION", "%.6f" % ((df + 2 * dp) / den) if den else "0")]
+    return "## METRICS CLASS\tbwamem_hip.DuplicationMetrics\n" + "\t".join(c for c, _v in cols) + "\n" + "\t".join(str(v) for _c, v in cols) + "\n"
+
+
 class Aligner:
     def __init__(self, prefix: str | None, device: str = "cuda:0", n_threads: int = 0, _mem=None, sa_intv: int | None = 1,
                  long_reads: bool = False):
@@ -363,10 +377,12 @@ class Aligner:
             raise BamRefusal(f"BAM output: read '{line.split(chr(9).encode())[0].decode(errors='replace')}': its SAM record cannot be written as BAM: {bam_status_name(int(st[bad[0]]))}")
         return bgzf_compress(bam, level)
 
-    def align_batch(self, names, seqs=None, id0: int = 0, paired: bool = False, as_bytes: bool = False, quals=None, comments=None, fmt: str = "sam", level: int = 1, sort: bool = False):
+    def align_batch(self, names, seqs=None, id0: int = 0, paired: bool = False, as_bytes: bool = False, quals=None, comments=None, fmt: str = "sam", level: int = 1, sort: bool = False, markdup: bool = False):
         """SAM records of one batch of reads: a ReadSet, or (names, seqs) lists of str / ASCII uint8 arrays (quals, comments: lists as
         ReadSet.from_lists takes them); id0 = index of its first read in the run.  paired: interleaved pairs (gase_aln -p); the insert-size
         statistics are the batch's.  QUAL comes from the reads' qualities, '*' without; with -C the comments end the records."""
+        if markdup:
+            raise ValueError("align_batch: markdup=True marks the duplicates of a sorted file, and one batch is not a file (align_file / align_files)")
         if sort:
             raise ValueError("align_batch: sort=True sorts a file's records, and one batch is not a file (align_file / align_files)")
         if fmt != "sam":                                          # fmt="bam": the batch's records as BGZF members (bytes; no header, no end-of-file member)
@@ -544,13 +560,14 @@ class Aligner:
         nat.set_output(*getattr(self, "_out_fmt", ("sam", 1)))
         if getattr(self, "_out_fmt", ("sam", 1))[0] == "bam_sorted":
             nat.set_sort(*self._sort_knobs)
+            nat.set_markdup(bool(getattr(self, "_markdup", False)))
         return nat
 
     def align_file(self, reads_fa: str, out, batch_reads: int = 0, paired: bool = False, chunk_bases: int = 0, fmt: str = "sam", level: int = 1,
-                   sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None) -> int:
-        if fmt != "sam" or sort or index is not None:
+                   sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None) -> int:
+        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None:
             return self._align_bam(lambda o: self.align_file(reads_fa, o, batch_reads=batch_reads, paired=paired, chunk_bases=chunk_bases), out, fmt, level,
-                                   sort, index, sort_mem, sort_tmp, sort_window)
+                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics)
         """out: a text or binary file object.  Batches are cut the way the reference's bseq_read cuts them (src/bwa.c, called with
         chunk_size * n_threads = 10 Mbases per thread, or -K, src/fastmap.c:527): reads are added until the batch holds at least
         chunk_bases bases and an even number of reads -- in paired mode the insert-size statistics are those of the batch, so the
@@ -626,12 +643,17 @@ class Aligner:
                 out.write(self.align_batch(rs.slice(b, e), id0=b, paired=paired, as_bytes="view" if binary else False))   # (binary: the library's buffer, uncopied)
         return n
 
-    def _align_bam(self, run, out, fmt: str, level: int, sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None) -> int:
+    def _align_bam(self, run, out, fmt: str, level: int, sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None) -> int:
         """fmt="bam" of align_file / align_files: the header members, the batches' members (`run` with the native aligner's output switched; the Python
         loop's batches converted here), the end-of-file member.  The file is written through a shim that drops the SAM header `run` writes first.
         sort=True: the batches become sorted runs and the members are those of the coordinate-sorted file, written at the end of the input; `index` (a path or
-        a binary file object) receives its .bai."""
+        a binary file object) receives its .bai.  markdup=True (needs sort=True): flag 0x400 on every record of every duplicate template (Picard MarkDuplicates'
+        rules); self.markdup_counts holds the counts afterwards and `markdup_metrics` (a path or a text file object) receives a Picard-style table."""
         from .lib import bgzf_eof
+        if (markdup or markdup_metrics is not None) and not sort:
+            raise ValueError("markdup=True needs sort=True: duplicates are marked where the sorted file is written" if markdup else "markdup_metrics needs markdup=True and sort=True")
+        if markdup_metrics is not None and not markdup:
+            raise ValueError("markdup_metrics needs markdup=True")
         if sort and fmt != "bam":
             raise ValueError(f'sort=True needs fmt="bam" (fmt {fmt!r})')
         if index is not None and not sort:
@@ -660,10 +682,15 @@ class Aligner:
                 raise NotImplementedError("sort=True needs the native pipeline (BMH_ALIGNER_NATIVE=0 and profile runs write batch after batch)")
             self._sort_knobs = (int(sort_mem or 0), sort_tmp, int(sort_window or 0))
         self._out_fmt = ("bam_sorted" if sort else "bam", level)
+        self._markdup = bool(markdup)
         try:
             n = run(shim)
+            if markdup:
+                from .lib import MARKDUP_COUNTS
+                self.markdup_counts = self._native.markdup_counts() if n else dict.fromkeys(MARKDUP_COUNTS, 0)
         finally:
             self._out_fmt = ("sam", 1)
+            self._markdup = False
             nat = getattr(self, "_native", None)
             if nat is not None:
                 nat.set_output("sam", 1)
@@ -680,18 +707,25 @@ class Aligner:
             else:
                 with open(index, "wb") as f:
                     f.write(bai)
+        if markdup_metrics is not None:
+            text = markdup_metrics_text(self.markdup_counts, getattr(self, "rg_line", ""))
+            if hasattr(markdup_metrics, "write"):
+                markdup_metrics.write(text)
+            else:
+                with open(markdup_metrics, "w") as f:
+                    f.write(text)
         return n
 
     def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
-                    sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None) -> int:
+                    sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None) -> int:
         """align_file for the files users have (bmh_aligner_run_files): `reads` (and `mates`: the second file of a pair, which implies paired) may be
         multi-line FASTA or FASTQ, plain, gzip or BGZF, a regular file or a pipe.  Batches are cut by align_file's rules (-t, -K, the 150 Mbase floor for
         single-end runs), so the text equals align_file's on the single-line interleaved file of the same reads.  Returns the number of reads."""
         if out is None:
             raise ValueError("align_files: out (a text or binary file object) is required")
-        if fmt != "sam" or sort or index is not None:
+        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None:
             return self._align_bam(lambda o: self.align_files(reads, mates, out=o, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads), out, fmt, level,
-                                   sort, index, sort_mem, sort_tmp, sort_window)
+                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics)
         binary = "b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")
         paired = bool(paired or mates is not None)
         cb = 0

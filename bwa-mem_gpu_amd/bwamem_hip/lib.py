@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "bmh_bam_ws_create", "bmh_bam_ws_free", "bmh_sam_to_bam_device", "bmh_sam_to_bam_host", "bmh_bam_status_name", "bmh_bgzf_deflate_device", "bmh_bgzf_deflate_host",
     "bmh_deflate_blocks_host", "bmh_bam_header", "bmh_aligner_set_output",
     "bmh_bam_sort_device", "bmh_bam_sort_host", "bmh_bam_sorted_file_device", "bmh_bam_sorted_file_host", "bmh_aligner_set_sort", "bmh_aligner_sort_index",
+    "bmh_bam_markdup_device", "bmh_bam_markdup_host", "bmh_bam_sorted_file_markdup_device", "bmh_bam_sorted_file_markdup_host", "bmh_aligner_set_markdup", "bmh_aligner_markdup_counts", "bmh_aligner_markdup_times",
 ]
 
 
@@ -386,9 +387,38 @@ def bam_sort(records: bytes, host: bool = False) -> bytes:
         L.bmh_free(out)
 
 
-def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False) -> tuple:
+# ---- duplicate marking (csrc/bam_dup_core.h, csrc/bam_dup_kernels.hip, csrc/bam_dup_host.cpp)
+MARKDUP_COUNTS = ("pairs_examined", "fragments_examined", "duplicate_pairs", "duplicate_fragments", "records_flagged", "secondary_or_supplementary", "unmapped_records", "templates")
+
+
+def bam_markdup(records: bytes, host: bool = False) -> tuple:
+    """bmh_bam_markdup_device (host=True: bmh_bam_markdup_host, no device needed): a stream of BAM records in the writer's order (a template's records next to
+    each other, its first primary line first) -> (the same records with flag 0x400 on every record of every duplicate template, the counts by MARKDUP_COUNTS'
+    names).  Picard MarkDuplicates' rules.  A cut stream, one whose first record begins no template and a paired template without both of its
+    primary lines raise ValueError."""
+    L = load_library()
+    records = bytes(records)
+    L.bmh_free.argtypes = [C.c_void_p]
+    out, counts = C.c_void_p(), (C.c_uint64 * 8)()
+    if host:
+        L.bmh_bam_markdup_host.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        rc = L.bmh_bam_markdup_host(records, len(records), C.byref(out), counts)
+    else:
+        import torch
+        L.bmh_bam_markdup_device.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        rc = L.bmh_bam_markdup_device(records, len(records), torch.cuda.current_stream().cuda_stream, C.byref(out), counts)
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_markdup: " + _err(L))
+    try:
+        return (C.string_at(out.value, len(records)) if records else b""), dict(zip(MARKDUP_COUNTS, (int(v) for v in counts)))
+    finally:
+        L.bmh_free(out)
+
+
+def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False, markdup: bool = False) -> tuple:
     """bmh_bam_sorted_file_device (host=True: _host): (the complete sorted BAM file -- header members, the records in coordinate order in windows of `window`
-    records (0: about 64 MiB), the end-of-file member --, its .bai index).  contigs: (name, length) pairs; both forms give the same bytes."""
+    records (0: about 64 MiB), the end-of-file member --, its .bai index).  contigs: (name, length) pairs; both forms give the same bytes.
+    markdup=True (bmh_bam_sorted_file_markdup_*): `records` come in the writer's order, the duplicates among them are marked (bam_markdup's rules) and the counts come third."""
     L = load_library()
     records = bytes(records)
     L.bmh_free.argtypes = [C.c_void_p]
@@ -402,16 +432,23 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
     tail = [C.byref(bam), C.byref(nb), C.byref(bai), C.byref(ni)]
     sig = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_uint32]
     out = [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p]
+    counts = (C.c_uint64 * 8)()
+    if markdup:
+        tail.append(counts); out.append(C.POINTER(C.c_uint64))
     if host:
-        L.bmh_bam_sorted_file_host.argtypes = sig + out
-        rc = L.bmh_bam_sorted_file_host(*head, *tail)
+        fn = L.bmh_bam_sorted_file_markdup_host if markdup else L.bmh_bam_sorted_file_host
+        fn.argtypes = sig + out
+        rc = fn(*head, *tail)
     else:
         import torch
-        L.bmh_bam_sorted_file_device.argtypes = sig + [C.c_void_p] + out
-        rc = L.bmh_bam_sorted_file_device(*head, torch.cuda.current_stream().cuda_stream, *tail)
+        fn = L.bmh_bam_sorted_file_markdup_device if markdup else L.bmh_bam_sorted_file_device
+        fn.argtypes = sig + [C.c_void_p] + out
+        rc = fn(*head, torch.cuda.current_stream().cuda_stream, *tail)
     if rc != 0:
         raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_sorted_file: " + _err(L))
     try:
+        if markdup:
+            return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value), dict(zip(MARKDUP_COUNTS, (int(v) for v in counts)))
         return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)
     finally:
         L.bmh_free(bam); L.bmh_free(bai)
@@ -513,6 +550,32 @@ class NativeAligner:
         L.bmh_aligner_set_sort.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint32]
         if L.bmh_aligner_set_sort(self.handle, int(mem_bytes), os.fsencode(tmp_dir) if tmp_dir is not None else None, int(window_records)) != 0:
             raise ValueError("bmh_aligner_set_sort: " + _err(L))
+
+    def set_markdup(self, on: bool = True) -> None:
+        """bmh_aligner_set_markdup: the sorted runs that follow mark duplicates (refused unless the output is "bam_sorted"; any other set_output switches it off)"""
+        L = load_library()
+        L.bmh_aligner_set_markdup.argtypes = [C.c_void_p, C.c_int]
+        if L.bmh_aligner_set_markdup(self.handle, 1 if on else 0) != 0:
+            raise ValueError("bmh_aligner_set_markdup: " + _err(L))
+
+    def markdup_counts(self) -> dict:
+        """bmh_aligner_markdup_counts: the counts of the last run that marked duplicates, by MARKDUP_COUNTS' names"""
+        L = load_library()
+        L.bmh_aligner_markdup_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        c = (C.c_uint64 * 8)()
+        if L.bmh_aligner_markdup_counts(self.handle, c) != 0:
+            raise ValueError("bmh_aligner_markdup_counts: " + _err(L))
+        return dict(zip(MARKDUP_COUNTS, (int(v) for v in c)))
+
+    def markdup_times(self) -> dict:
+        """bmh_aligner_markdup_times: where the last marked run's extra time went -- the decision and the windows' flag steps in ms, the bytes of ordinals and entries
+        that came down with the batches"""
+        L = load_library()
+        L.bmh_aligner_markdup_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        t = (C.c_double * 3)()
+        if L.bmh_aligner_markdup_times(self.handle, t) != 0:
+            raise ValueError("bmh_aligner_markdup_times: " + _err(L))
+        return dict(decision_ms=t[0], window_flags_ms=t[1], entries_d2h_bytes=int(t[2]))
 
     def sort_index(self, base_offset: int) -> bytes:
         """bmh_aligner_sort_index: the .bai bytes of the last sorted run; base_offset: the bytes written before the sink's first (the header members)"""

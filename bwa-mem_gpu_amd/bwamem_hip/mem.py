@@ -8,7 +8,11 @@ stdout), --long-reads (reads of up to 16 384 bases), --device (the torch device,
 compressed on the device; -o is unchanged, a name ending in .bam does not switch formats), --bam-level 0|1 (stored, or LZ77 + dynamic Huffman; 1),
 --sort (implies --bam: the records in coordinate order, `samtools sort`'s, sorted on the device; with -o PATH the BAI index goes to PATH.bai, --index PATH
 names it otherwise, and on stdout without --index none is written), --sort-mem BYTES (records kept in host memory before the sorted runs spill to a temporary
-file; 4 GiB) and --sort-tmp DIR (where that file lives; $TMPDIR, else /tmp).  An option that is not on that list is
+file; 4 GiB), --sort-tmp DIR (where that file lives; $TMPDIR, else /tmp), --markdup (needs --sort: flag 0x400 on every record of every duplicate template,
+decided on the device by Picard MarkDuplicates' rules -- the unclipped 5' ends and strands of a template's primary lines are the key, the sum of the base
+qualities >= 15 the score, ties go to the template that came first in the input, a fragment is a duplicate wherever a pair has an end; unlike Picard and
+`samtools markdup` on coordinate-sorted input the secondary and supplementary lines of a duplicate template are flagged too; no optical duplicates, one library
+per run, no library-size estimate, nothing is removed) and --markdup-metrics PATH (a Picard-style table of the counts).  An option that is not on that list is
 refused by name.  Two input files imply pairs.  One plain, regular file is offered to Aligner.align_file first, which takes it when every
 record has one sequence line (its own counting pass decides, before anything is written); every other input goes through
 Aligner.align_files; the text is the same.  A refused file ends the command with status 1 and the library's message on stderr.
@@ -39,6 +43,7 @@ def main(argv=None) -> int:
     opts, pos, out_path, interleaved, long_reads, device = [], [], None, False, False, "cuda:0"
     bam, bam_level = False, 1
     sort, index_path, sort_mem, sort_tmp = False, None, None, None
+    markdup, metrics_path = False, None
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -56,7 +61,9 @@ def main(argv=None) -> int:
             i += 1
         elif a == "--sort":
             sort = bam = True
-        elif a in ("-o", "--device", "--index", "--sort-mem", "--sort-tmp"):
+        elif a == "--markdup":
+            markdup = True
+        elif a in ("-o", "--device", "--index", "--sort-mem", "--sort-tmp", "--markdup-metrics"):
             if i + 1 >= len(argv):
                 print(f"[bwamem_hip.mem] option {a} needs a value", file=sys.stderr)
                 return 2
@@ -64,6 +71,8 @@ def main(argv=None) -> int:
                 out_path = argv[i + 1]
             elif a == "--index":
                 index_path = argv[i + 1]
+            elif a == "--markdup-metrics":
+                metrics_path = argv[i + 1]
             elif a == "--sort-tmp":
                 sort_tmp = argv[i + 1]
             elif a == "--sort-mem":
@@ -95,6 +104,12 @@ def main(argv=None) -> int:
     if not sort and (index_path is not None or sort_mem is not None or sort_tmp is not None):
         print("[bwamem_hip.mem] --index, --sort-mem and --sort-tmp need --sort", file=sys.stderr)
         return 2
+    if markdup and not sort:
+        print("[bwamem_hip.mem] --markdup needs --sort", file=sys.stderr)
+        return 2
+    if metrics_path is not None and not markdup:
+        print("[bwamem_hip.mem] --markdup-metrics needs --markdup", file=sys.stderr)
+        return 2
     if sort and index_path is None and out_path is not None:
         index_path = out_path + ".bai"
     from .aligner import Aligner
@@ -110,6 +125,8 @@ def main(argv=None) -> int:
         fmt_kw = dict(fmt="bam", level=bam_level) if bam else {}
         if sort:
             fmt_kw.update(sort=True, index=index_path, sort_mem=sort_mem, sort_tmp=sort_tmp)
+        if markdup:
+            fmt_kw.update(markdup=True, markdup_metrics=metrics_path)
         done = False
         if mates is None and _plain_regular(reads):
             from .lib import ReadFileError

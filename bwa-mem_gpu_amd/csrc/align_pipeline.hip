@@ -31,6 +31,7 @@
 #include "pair_kernels.h"
 #include "bam_ws.h"
 #include "bam_sort.h"
+#include "bam_dup.h"
 #include "batch_queue.h"
 
 namespace {
@@ -45,6 +46,7 @@ struct aligner_t {
 	std::string rg_id;             // the aligner's own copy of popt->rg_id (po.rg_id points into it): the caller's string need not outlive the call that created the aligner
 	uint32_t max_qlen = 768;       // the extension cap of the chain workspaces (bmh_aligner_set_max_qlen)
 	bmh_reseed_opt_t rs = {0, 1.5f, 10, 20};   // the seeding rounds (bmh_aligner_set_reseed; enable 0: the first round only)
+	bool markdup = false;                      // sorted BAM output: flag 0x400 on the records of duplicate templates (bmh_aligner_set_markdup)
 	int out_fmt = BMH_OUT_SAM, out_level = 1;  // what the sink receives (bmh_aligner_set_output): the records' text, or BGZF members of BAM records
 	std::vector<char> ctg_blob; std::vector<uint32_t> ctg_noff;      // the contig table as the BAM converter takes it
 };
@@ -110,6 +112,7 @@ struct result_t {
 	hbuf_t<int32_t> fin, aln, slot32; hbuf_t<uint32_t> opr, off, packed;
 	hbuf_t<char> text; uint64_t text_len = 0; bool has_text = false;     // the text written on the device (no formatting on the host)
 	hbuf_t<uint64_t> skeys, soff; uint32_t n_rec = 0;                   // sorted BAM: text holds the batch's records in order; their keys and offsets [n_rec + 1]
+	hbuf_t<uint32_t> stpl; hbuf_t<bdp_entry_t> dup_e; uint32_t dup_info[4] = {0, 0, 0, 0}; uint64_t dup_d2h = 0;      // duplicate marking: the records' template ordinals in that order, the templates' entries, bdp_batch_device's info
 	std::vector<int64_t> slot;                   // (host selection only; empty: slot32)
 	std::vector<int32_t> h_rec, unflag;          // pairs
 	std::vector<uint32_t> dev_index;             // record -> its place in the lane's d_fin when that is not the record's own index (ALT indexes); empty: identity
@@ -137,10 +140,12 @@ struct lane_t {
 	uint32_t host_tail = 0;                      // batches of the run whose region tail the device refused (BMH_ECAPACITY): the host forms took them
 	bmh_bam_ws_t *bam = nullptr;                 // BAM output: the converter's and the compressor's buffers
 	bsr_dev_t *bsr = nullptr;                    // sorted BAM output: the sort's, the gather's and the index pass's buffers
+	bdp_dev_t *bdp = nullptr;                    // duplicate marking: the batch's heads, ordinals and entries
 	~lane_t()
 	{
 		if (bam) bmh_bam_ws_free(bam);
 		if (bsr) bsr_dev_free(bsr);
+		if (bdp) bdp_dev_free(bdp);
 		for (hipEvent_t e : ev_c) if (e) (void)hipEventDestroy(e);
 		if (sws) bmh_seed_ws_free(sws);
 		if (cws) bmh_chain_ws_free(cws);
@@ -261,15 +266,36 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 			if (!Ln.bsr && !(Ln.bsr = bsr_dev_create())) return BMH_ENOMEM;
 			const uint8_t *ds = nullptr; const uint64_t *dk = nullptr, *dso = nullptr;
 			const uint32_t nrec = bo.n_records;
-			RCK(bsr_sort_run_device(Ln.bsr, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &ds, &dk, &dso));
+			// duplicate marking: on the records in the writer's order, before the sort -- heads, their scan, one entry per template; the ordinals follow the records
+			const uint32_t *d_tpl = nullptr, *d_info = nullptr, *d_stpl = nullptr; const bdp_entry_t *d_e = nullptr;
+			const uint32_t tmax = paired ? n / 2 : n;                   // the batch's templates: every read or pair leaves at least one record, so no more entries than this come down
+			if (A.markdup) {
+				if (!Ln.bdp && !(Ln.bdp = bdp_dev_create())) return BMH_ENOMEM;
+				RCK(bdp_batch_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &d_tpl, &d_e, &d_info));
+				RCK(R.stpl.need((size_t)nrec + 1)); RCK(R.dup_e.need((size_t)std::min(nrec, tmax) + 1));
+			}
+			RCK(bsr_sort_run_device(Ln.bsr, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &ds, &dk, &dso, d_tpl, &d_stpl));
 			RCK(R.text.need((size_t)bo.bam_bytes + 1)); RCK(R.skeys.need((size_t)nrec + 1)); RCK(R.soff.need((size_t)nrec + 2));
 			LCK(hipEventRecord(Ln.ev_c[2], Ln.st));
 			if (bo.bam_bytes) LCK(hipMemcpyAsync(R.text.p, ds, (size_t)bo.bam_bytes, hipMemcpyDeviceToHost, Ln.st));
 			if (nrec) LCK(hipMemcpyAsync(R.skeys.p, dk, 8 * (size_t)nrec, hipMemcpyDeviceToHost, Ln.st));
 			LCK(hipMemcpyAsync(R.soff.p, dso, 8 * ((size_t)nrec + 1), hipMemcpyDeviceToHost, Ln.st));
+			R.dup_d2h = 0;
+			if (A.markdup) {                                          // (the count comes down with them and is checked below)
+				const size_t ne = std::min(nrec, tmax);
+				if (nrec) LCK(hipMemcpyAsync(R.stpl.p, d_stpl, 4 * (size_t)nrec, hipMemcpyDeviceToHost, Ln.st));
+				if (ne) LCK(hipMemcpyAsync(R.dup_e.p, d_e, sizeof(bdp_entry_t) * ne, hipMemcpyDeviceToHost, Ln.st));
+				LCK(hipMemcpyAsync(R.dup_info, d_info, 16, hipMemcpyDeviceToHost, Ln.st));
+				R.dup_d2h = 4ull * nrec + sizeof(bdp_entry_t) * ne + 16;
+				Ln.copy_bytes[1] += R.dup_d2h;
+			}
 			LCK(hipEventRecord(Ln.ev_c[3], Ln.st));
 			Ln.copy_bytes[1] += bo.bam_bytes + 16ull * nrec; Ln.d2h_marked = true;
 			LCK(hipStreamSynchronize(Ln.st));
+			if (A.markdup && nrec) {
+				if (R.dup_info[1] != 0xffffffffu) return bdp_batch_refused(nrec, R.dup_info[1] ? R.dup_info[1] : nrec + 1, "sorted BAM");
+				if (R.dup_info[0] == 0 || R.dup_info[0] > std::min(nrec, tmax)) { bmh_set_error("sorted BAM: internal error: %u templates among %u records", R.dup_info[0], nrec); return BMH_EINVAL; }
+			}
 			if (R.soff.p[nrec] != bo.bam_bytes) {                 // (the gather skips a record whose offsets lie outside the buffers: the scan of the sizes shows it)
 				bmh_set_error("sorted BAM: internal error: the sorted run holds %llu bytes, the batch's records %llu", (unsigned long long)R.soff.p[nrec], (unsigned long long)bo.bam_bytes);
 				return BMH_EINVAL;
@@ -803,6 +829,8 @@ struct bmh_aligner {
 	int dev = -1;
 	uint64_t host_tail_batches = 0;                      // of the last run (bmh_aligner_host_tail_batches)
 	bsr_store_t store; bsr_index_t sort_ix; uint32_t sort_window = 0;      // sorted BAM output: the runs of the run in progress, the index of the last one, the window
+	uint64_t dup_counts[BDP_N_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0}; bool dup_valid = false;      // duplicate marking: the counts of the last marked run
+	double dup_times[3] = {0, 0, 0};                     // ... its decision and its windows' flag steps in ms, the bytes its batches' ordinals and entries took on their way down
 };
 
 bmh_aligner_t *bmh_aligner_create(const bmh_index_t *idx, const uint8_t *pac, int64_t l_pac, int n_contigs, const char *const *contig_names,
@@ -835,6 +863,7 @@ int bmh_aligner_set_output(bmh_aligner_t *h, int format, int level)
 	if (format != BMH_OUT_SAM && format != BMH_OUT_BAM && format != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_output: format %d (BMH_OUT_SAM, BMH_OUT_BAM or BMH_OUT_BAM_SORTED)", format); return BMH_EINVAL; }
 	if (format != BMH_OUT_SAM && level != 0 && level != 1) { bmh_set_error("bmh_aligner_set_output: level %d (0 or 1)", level); return BMH_EINVAL; }
 	if (format == BMH_OUT_BAM_SORTED) { h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), "sorted BAM output")); }
+	if (format != BMH_OUT_BAM_SORTED) h->a.markdup = false;          // (duplicates are marked in sorted output only: the option goes with the format)
 	h->a.out_fmt = format; h->a.out_level = level;
 	return BMH_OK;
 }
@@ -859,6 +888,30 @@ int bmh_aligner_set_sort(bmh_aligner_t *h, uint64_t mem_bytes, const char *tmp_d
 {
 	if (!h) { bmh_set_error("bmh_aligner_set_sort: null aligner"); return BMH_EINVAL; }
 	h->store.mem_bytes = mem_bytes ? mem_bytes : 4ull << 30; h->store.tmp_dir = tmp_dir ? tmp_dir : ""; h->sort_window = window_records;
+	return BMH_OK;
+}
+
+int bmh_aligner_set_markdup(bmh_aligner_t *h, int on)
+{
+	if (!h) { bmh_set_error("bmh_aligner_set_markdup: null aligner"); return BMH_EINVAL; }
+	if (on && h->a.out_fmt != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_markdup: duplicates are marked in sorted output (bmh_aligner_set_output with BMH_OUT_BAM_SORTED comes first)"); return BMH_EINVAL; }
+	h->a.markdup = on != 0;
+	return BMH_OK;
+}
+
+int bmh_aligner_markdup_counts(bmh_aligner_t *h, uint64_t out[8])
+{
+	if (!h || !out) { bmh_set_error("bmh_aligner_markdup_counts: null argument"); return BMH_EINVAL; }
+	if (!h->dup_valid) { bmh_set_error("bmh_aligner_markdup_counts: no run has marked duplicates (or the last one failed before its file was complete)"); return BMH_EINVAL; }
+	for (int k = 0; k < BDP_N_COUNTS; ++k) out[k] = h->dup_counts[k];
+	return BMH_OK;
+}
+
+int bmh_aligner_markdup_times(bmh_aligner_t *h, double out[3])
+{
+	if (!h || !out) { bmh_set_error("bmh_aligner_markdup_times: null argument"); return BMH_EINVAL; }
+	if (!h->dup_valid) { bmh_set_error("bmh_aligner_markdup_times: no run has marked duplicates (or the last one failed before its file was complete)"); return BMH_EINVAL; }
+	for (int k = 0; k < 3; ++k) out[k] = h->dup_times[k];
 	return BMH_OK;
 }
 
@@ -907,11 +960,14 @@ struct out_stage_t {
 	uint64_t n_bytes = 0;                                           // handed to the sink so far
 	int emit(const void *p, size_t n) { if (n && sink(user, (const char *)p, n) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; } n_bytes += n; return BMH_OK; }
 	// (the index is valid again once the merge has written the whole file)
-	int begin() { if (fmt == BMH_OUT_BAM_SORTED) { h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), fn)); h->sort_ix.valid = false; } return BMH_OK; }
+	int begin() { if (fmt == BMH_OUT_BAM_SORTED) { h->dup_valid = false; h->dup_times[0] = h->dup_times[1] = h->dup_times[2] = 0; h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), fn)); h->sort_ix.valid = false; } return BMH_OK; }
 	int device_batch(const result_t &R)
 	{
 		if (fmt != BMH_OUT_BAM_SORTED) return emit(R.text.p, (size_t)R.text_len);
-		return R.n_rec ? h->store.append((const uint8_t *)R.text.p, R.text_len, R.skeys.p, R.soff.p, R.n_rec) : BMH_OK;      // a sorted run: kept until the end of the input
+		if (!R.n_rec) return BMH_OK;
+		const bsr_dup_t bd = {R.stpl.p, R.dup_e.p, R.dup_info[0], R.dup_info[2], R.dup_info[3]};
+		if (h->a.markdup) h->dup_times[2] += (double)R.dup_d2h;
+		return h->store.append((const uint8_t *)R.text.p, R.text_len, R.skeys.p, R.soff.p, R.n_rec, h->a.markdup ? &bd : nullptr);      // a sorted run: kept until the end of the input
 	}
 	int host_batch(const std::vector<std::string> &parts)
 	{
@@ -937,7 +993,13 @@ struct out_stage_t {
 				bsr_sort_host(bam, off, keys, ord);
 				srt.reserve((size_t)bb + 1);
 				for (uint32_t i : ord) { srt.insert(srt.end(), bam + off[i], bam + off[i + 1]); soff.push_back(srt.size()); }
-				if (!ord.empty()) rc = h->store.append(srt.data(), bb, keys.data(), soff.data(), ord.size());
+				std::vector<uint32_t> tpl, stpl; std::vector<bdp_entry_t> E; uint64_t info[2] = {0, 0};
+				if (A.markdup) {                                   // the host forms of the device's heads, ordinals and entries
+					rc = bdp_entries_host(bam, off.data(), (uint32_t)ord.size(), tpl, E, info, fn);
+					for (uint32_t i : ord) stpl.push_back(tpl[i]);
+				}
+				const bsr_dup_t bd = {stpl.data(), E.data(), (uint32_t)E.size(), info[0], info[1]};
+				if (rc == BMH_OK && !ord.empty()) rc = h->store.append(srt.data(), bb, keys.data(), soff.data(), ord.size(), A.markdup ? &bd : nullptr);
 			}
 		} else if (rc == BMH_OK) {
 			rc = bmh_bgzf_deflate_host(bam, bb, A.out_level, n_threads, &mem, &mb);
@@ -956,10 +1018,11 @@ struct out_stage_t {
 		if (!L0.bam && !(L0.bam = bmh_bam_ws_create())) rc = BMH_ENOMEM;
 		if (rc == BMH_OK && !L0.bsr && !(L0.bsr = bsr_dev_create())) rc = BMH_ENOMEM;
 		const double tm0 = now_s();
-		if (rc == BMH_OK) rc = bsr_merge_device(L0.bsr, L0.bam, h->store, h->sort_window, h->a.out_level, L0.st, h->sort_ix, forward, this);
+		if (rc == BMH_OK) rc = bsr_merge_device(L0.bsr, L0.bam, h->store, h->sort_window, h->a.out_level, L0.st, h->sort_ix, forward, this, h->a.markdup ? h->dup_counts : nullptr, h->dup_times);
+		if (trace && h->a.markdup) fprintf(stderr, "[aligner] duplicate marking: %.0f bytes of ordinals and entries came down with the batches\n", h->dup_times[2]);
 		if (trace) fprintf(stderr, "[aligner] sorted output: %zu runs (%llu spilled) merged in %.1f ms\n", h->store.runs.size(), (unsigned long long)h->store.spilled, (now_s() - tm0) * 1e3);
 		h->store.clear();
-		if (rc == BMH_OK) h->sort_ix.valid = true;
+		if (rc == BMH_OK) { h->sort_ix.valid = true; h->dup_valid = h->a.markdup; }
 		return rc;
 	}
 };

@@ -1,0 +1,41 @@
+// Duplicate marking, internal: the host forms (csrc/bam_dup_host.cpp) and what csrc/bam_dup_kernels.hip offers csrc/bam_sort_kernels.hip and csrc/align_pipeline.hip.
+#pragma once
+#include <stdint.h>
+#include <vector>
+#ifndef BDP_STANDALONE
+#include "bmh_internal.h"
+#else                                                              // tests/bam_dup_core_host.cpp: the host forms alone, without the library
+enum { BMH_OK = 0, BMH_EINVAL = -2, BMH_ENOMEM = -4 };
+void bmh_set_error(const char *fmt, ...);
+#endif
+#include "bam_dup_core.h"
+
+// counts of a run: [0] pairs examined [1] fragments examined [2] duplicate pairs [3] duplicate fragments [4] records flagged [5] secondary or supplementary
+// records [6] unmapped records [7] templates
+enum { BDP_PAIRS = 0, BDP_FRAGS, BDP_DUP_PAIRS, BDP_DUP_FRAGS, BDP_FLAGGED, BDP_SECSUP, BDP_UNMAPPED, BDP_TEMPLATES, BDP_N_COUNTS };
+
+// csrc/bam_dup_host.cpp
+// records in the writer's order with offsets off [n + 1] -> tpl [n]: every record's template ordinal in the stream; entries: one per template; info [2] += the
+// secondary or supplementary and the unmapped records.  Not BMH_OK (message set): the first record begins no template, or a paired template lacks a primary line
+int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn);
+// the decision: bits [(T + 31) / 32]: bit t set when template t is a duplicate; counts [0 .. 4]
+void bdp_decide_host(const bdp_entry_t *entries, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5]);
+// the whole of it on a walked stream: flags set in place
+int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn);
+
+// csrc/bam_dup_kernels.hip
+struct bdp_dev_t;                                                  // device buffers of the batches' entries, the decision and the bitmap; kept between calls
+bdp_dev_t *bdp_dev_create(void);
+void bdp_dev_free(bdp_dev_t *d);
+// a batch's records d_recs with offsets d_off [n + 1] (device, writer's order) -> *d_tpl [n], *d_entries [up to n], *d_info [4]: templates, the first bad record + 1
+// (0: none; n + 1: the first record begins no template), secondary or supplementary records, unmapped records -- all in d until its next call
+int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint32_t **d_tpl,
+                     const bdp_entry_t **d_entries, const uint32_t **d_info);
+// the message of a batch whose info [1] is not 0
+int bdp_batch_refused(uint32_t n, uint32_t bad, const char *fn);
+// every template's entry (host) -> the bitmap, kept in d for bdp_flag_device, and counts [0 .. 4]
+// n_records: the records of the final sort that follows (csrc/bam_sort_kernels.hip: 24 bytes each and the sort's work space) -- the decision's buffers are freed
+// before that sort allocates, so one check of the larger of the two needs refuses here what either would refuse
+int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records = 0);
+// records d_recs at d_off [n] (device; all inside `total` bytes) whose global template ordinals are tord [n] (host): byte 19 |= 0x04 where the bitmap says so
+int bdp_flag_device(bdp_dev_t *d, uint8_t *d_recs, const uint64_t *d_off, const uint32_t *tord, uint32_t n, uint64_t total, void *stream);

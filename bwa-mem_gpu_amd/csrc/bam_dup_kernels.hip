@@ -1,0 +1,349 @@
+// Duplicate marking on the device (csrc/bam_dup_core.h's rules).
+//
+//   per batch   heads: one lane per record, through the converter's offsets -- does it begin a template, is it a secondary / supplementary / unmapped line;
+//               an inclusive scan of the heads gives every record its batch-local template ordinal; starts: a head writes its record index at its ordinal;
+//               entries: one lane per template over its few records -> (end word lo, end word hi, score, kind | records << 2), 24 bytes
+//   decision    at the end of the input, over all templates' entries.  Pair pass: three stable 64-bit radix passes (rank word, hi, lo; templates that are no
+//               pair carry all-ones words and sort behind the pairs), then a lane is a duplicate iff its (lo, hi) equals the lane's before it.  Fragment pass:
+//               the fragments plus two items per pair (one per end), compacted through a scan; two stable passes (pair ends first, fragments best-first; then
+//               the end word); run heads, a max-scan of the heads' indices, and a lane decides from the first item of its run -- a run may span workgroups.
+//               Output: a bitmap over global template ordinals and five counters.
+//   per window  one lane per record tests the bitmap through the record's global template ordinal and ORs 0x04 into byte 19 (a byte store: records are unaligned)
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+#include <rocprim/rocprim.hpp>
+#include <algorithm>
+#include <vector>
+#include "bam_dup.h"
+#include "bam_sort.h"
+#include "bam_ws.h"
+
+#define HIPCK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
+#define RCK(x) do { const int rc_ = (x); if (rc_ != BMH_OK) return rc_; } while (0)
+
+struct bdp_dev_t {
+	bmh_grow_t head, tpl, start, entries, info, tmp;                        // per batch
+	bmh_grow_t bits, tord;                                                  // the bitmap of the run, a window's ordinals
+	uint64_t n_tpl = 0;                                                     // templates the bitmap covers
+};
+
+namespace {
+
+// info: [0] templates (written by the host side from the scan) [1] the first bad record + 1 (atomicMin; 0xffffffff: none) [2] secondary / supplementary [3] unmapped
+__global__ void __launch_bounds__(256) bdp_heads(const uint8_t *__restrict__ recs, const uint64_t *__restrict__ off, uint32_t n, uint64_t total, uint32_t *__restrict__ head, uint32_t *info)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	uint32_t fl = 0; bool valid = false;
+	if (i < n) {
+		const uint64_t o = off[i];
+		valid = o <= total && total - o >= BSR_FIXED;
+		if (valid) fl = bsr_flag(recs + o);
+		head[i] = valid && bdp_head(fl) ? 1u : 0u;
+		if (i == 0 && !(valid && bdp_head(fl))) atomicMin(info + 1, 0u);      // (0: the first record begins no template -- reported as n + 1 by the host side)
+	}
+	const int c0 = __syncthreads_count(valid && (fl & 0x900u)), c1 = __syncthreads_count(valid && (fl & 4u));
+	if (threadIdx.x == 0) { if (c0) atomicAdd(info + 2, (uint32_t)c0); if (c1) atomicAdd(info + 3, (uint32_t)c1); }
+}
+
+// tpl: the inclusive scan of head -> ordinals (scan - 1); a head writes its record index at its ordinal
+__global__ void __launch_bounds__(256) bdp_starts(const uint32_t *__restrict__ head, uint32_t *__restrict__ tpl, uint32_t n, uint32_t *__restrict__ start, uint32_t *info)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t s = tpl[i];
+	const uint32_t t = s ? s - 1 : 0;                                      // (s == 0 only when the first record begins no template: the batch is refused)
+	tpl[i] = t;
+	if (head[i] && t < n) start[t] = i;
+	if (i == n - 1) { info[0] = s; if (s < n + 1) start[s < n ? s : n] = n; }
+}
+
+__global__ void __launch_bounds__(256) bdp_entries(const uint8_t *__restrict__ recs, const uint64_t *__restrict__ off, uint32_t n, uint64_t total, const uint32_t *__restrict__ start,
+                                                   bdp_entry_t *__restrict__ entries, uint32_t *info)
+{
+	const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+	if (t >= n || t >= info[0] || info[1] == 0) return;
+	const uint32_t a = start[t], b = start[t + 1];
+	bdp_entry_t e; e.lo = e.hi = ~0ull; e.score = 0; e.kind_n = 0;
+	bool ok = a < b && b <= n && off[b] <= total;                          // (offsets ascend: every record of the template lies inside the buffer)
+	if (ok) ok = bdp_entry(recs, off, a, b, &e);
+	entries[t] = e;
+	if (!ok) atomicMin(info + 1, a + 1);
+}
+
+// ---- the decision
+__global__ void __launch_bounds__(256) bdp_iota(uint32_t *__restrict__ v, uint64_t n)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i < n) v[i] = (uint32_t)i;
+}
+
+// the pair pass's key of pass k (0: rank word, 1: hi, 2: lo) through the permutation so far
+__global__ void __launch_bounds__(256) bdp_pair_keys(const bdp_entry_t *__restrict__ E, const uint32_t *__restrict__ perm, uint64_t n, int pass, uint64_t *__restrict__ key)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t t = perm[i];
+	const bdp_entry_t e = E[t];
+	const bool pair = bdp_kind(e) == BDP_PAIR;
+	key[i] = pass == 0 ? bdp_rank_word(e, t) : !pair ? ~0ull : pass == 1 ? e.hi : e.lo;
+}
+
+// counts: [0] pairs [1] fragments [2] duplicate pairs [3] duplicate fragments [4] records flagged
+__global__ void __launch_bounds__(256) bdp_pair_decide(const bdp_entry_t *__restrict__ E, const uint32_t *__restrict__ perm, uint64_t n, uint32_t *bits, unsigned long long *counts)
+{
+	__shared__ unsigned long long recs_s;
+	if (threadIdx.x == 0) recs_s = 0;
+	__syncthreads();
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	bool pair = false, dup = false;
+	if (i < n) {
+		const uint32_t t = perm[i];
+		const bdp_entry_t e = E[t];
+		pair = bdp_kind(e) == BDP_PAIR;
+		if (pair && i) {
+			const bdp_entry_t p = E[perm[i - 1]];
+			dup = bdp_kind(p) == BDP_PAIR && p.lo == e.lo && p.hi == e.hi;
+		}
+		if (dup) { atomicOr(bits + (t >> 5), 1u << (t & 31)); atomicAdd(&recs_s, (unsigned long long)bdp_n_rec(e)); }
+	}
+	const int cp = __syncthreads_count(pair), cd = __syncthreads_count(dup);
+	if (threadIdx.x == 0) {
+		if (cp) atomicAdd(counts + 0, (unsigned long long)cp);
+		if (cd) atomicAdd(counts + 2, (unsigned long long)cd);
+		if (recs_s) atomicAdd(counts + 4, recs_s);
+	}
+}
+
+// items of the fragment pass per template: 2 for a pair, 1 for a fragment
+__global__ void __launch_bounds__(256) bdp_item_counts(const bdp_entry_t *__restrict__ E, uint64_t n, uint32_t *__restrict__ cnt, unsigned long long *counts)
+{
+	const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	uint32_t k = BDP_NONE;
+	if (t < n) { k = bdp_kind(E[t]); cnt[t] = k == BDP_PAIR ? 2u : k == BDP_FRAG ? 1u : 0u; }
+	const int cf = __syncthreads_count(k == BDP_FRAG);
+	if (threadIdx.x == 0 && cf) atomicAdd(counts + 1, (unsigned long long)cf);
+}
+
+// item ids: template << 1 | end (0: lo, 1: hi)
+__global__ void __launch_bounds__(256) bdp_items(const bdp_entry_t *__restrict__ E, uint64_t n, const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ base, uint64_t m, uint32_t *__restrict__ item)
+{
+	const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (t >= n) return;
+	const uint32_t c = cnt[t], b = base[t];
+	if (c >= 1 && b < m) item[b] = (uint32_t)t << 1;
+	if (c == 2 && (uint64_t)b + 1 < m) item[b + 1] = (uint32_t)t << 1 | 1u;
+}
+
+__global__ void __launch_bounds__(256) bdp_frag_keys(const bdp_entry_t *__restrict__ E, const uint32_t *__restrict__ item, uint64_t m, int pass, uint64_t *__restrict__ key)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= m) return;
+	const uint32_t id = item[i], t = id >> 1;
+	const bdp_entry_t e = E[t];
+	key[i] = pass == 0 ? bdp_frag_word(e, t) : (id & 1u) ? e.hi : e.lo;
+}
+
+// word: the sorted end words; hidx [i] = i where a run begins, else 0
+__global__ void __launch_bounds__(256) bdp_run_heads(const uint64_t *__restrict__ word, uint64_t m, uint32_t *__restrict__ hidx)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i < m) hidx[i] = i && word[i] != word[i - 1] ? (uint32_t)i : 0u;
+}
+
+// first [i]: the index of the first item of lane i's run (the max-scan of hidx)
+__global__ void __launch_bounds__(256) bdp_frag_decide(const bdp_entry_t *__restrict__ E, const uint32_t *__restrict__ item, const uint32_t *__restrict__ first, uint64_t m, uint32_t *bits,
+                                                       unsigned long long *counts)
+{
+	__shared__ unsigned long long recs_s;
+	if (threadIdx.x == 0) recs_s = 0;
+	__syncthreads();
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	bool dup = false;
+	if (i < m) {
+		const uint32_t t = item[i] >> 1;
+		const bdp_entry_t e = E[t];
+		if (bdp_kind(e) == BDP_FRAG) {
+			const uint32_t f = first[i];
+			dup = f != i;
+			if (f < m && bdp_kind(E[item[f] >> 1]) == BDP_PAIR) dup = true;
+			if (dup) { atomicOr(bits + (t >> 5), 1u << (t & 31)); atomicAdd(&recs_s, (unsigned long long)bdp_n_rec(e)); }
+		}
+	}
+	const int cd = __syncthreads_count(dup);
+	if (threadIdx.x == 0) { if (cd) atomicAdd(counts + 3, (unsigned long long)cd); if (recs_s) atomicAdd(counts + 4, recs_s); }
+}
+
+// ---- the flags of a window
+__global__ void __launch_bounds__(256) bdp_flag(uint8_t *__restrict__ recs, const uint64_t *__restrict__ off, const uint32_t *__restrict__ tord, uint32_t n, uint64_t total,
+                                                const uint32_t *__restrict__ bits, uint64_t n_tpl)
+{
+	const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+	if (j >= n) return;
+	const uint32_t t = tord[j];
+	const uint64_t o = off[j];
+	if (t >= n_tpl || o > total || total - o < BSR_FIXED) return;
+	if (bits[t >> 5] >> (t & 31) & 1u) recs[o + 19] |= 0x04;
+}
+
+size_t sort_bytes(size_t n) { size_t t = 0; (void)rocprim::radix_sort_pairs(nullptr, t, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, n, 0, 64, 0); return t + 256; }
+size_t iscan_bytes(size_t n) { size_t t = 0; (void)rocprim::inclusive_scan(nullptr, t, (uint32_t *)nullptr, (uint32_t *)nullptr, n, rocprim::plus<uint32_t>(), 0); return t + 256; }
+size_t mscan_bytes(size_t n) { size_t t = 0; (void)rocprim::inclusive_scan(nullptr, t, (uint32_t *)nullptr, (uint32_t *)nullptr, n, rocprim::maximum<uint32_t>(), 0); return t + 256; }
+size_t escan_bytes(size_t n) { size_t t = 0; (void)rocprim::exclusive_scan(nullptr, t, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, n, rocprim::plus<uint32_t>(), 0); return t + 256; }
+unsigned blocks(uint64_t n) { return (unsigned)((n + 255) / 256); }
+
+}   // namespace
+
+bdp_dev_t *bdp_dev_create(void) { return new bdp_dev_t(); }
+void bdp_dev_free(bdp_dev_t *d) { delete d; }
+
+int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint32_t **d_tpl, const bdp_entry_t **d_entries, const uint32_t **d_info)
+{
+	hipStream_t st = (hipStream_t)stream;
+	size_t tb = iscan_bytes((size_t)n + 1);
+	RCK(d->head.need(4 * ((size_t)n + 1))); RCK(d->tpl.need(4 * ((size_t)n + 1))); RCK(d->start.need(4 * ((size_t)n + 2))); RCK(d->entries.need(sizeof(bdp_entry_t) * ((size_t)n + 1)));
+	RCK(d->info.need(16)); RCK(d->tmp.need(tb));
+	const uint32_t init[4] = {0u, 0xffffffffu, 0u, 0u};
+	HIPCK(hipMemcpyAsync(d->info.p, init, 16, hipMemcpyHostToDevice, st));
+	if (n) {
+		bdp_heads<<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, (uint32_t *)d->head.p, (uint32_t *)d->info.p);
+		HIPCK(rocprim::inclusive_scan(d->tmp.p, tb, (uint32_t *)d->head.p, (uint32_t *)d->tpl.p, (size_t)n, rocprim::plus<uint32_t>(), st));
+		bdp_starts<<<blocks(n), 256, 0, st>>>((const uint32_t *)d->head.p, (uint32_t *)d->tpl.p, n, (uint32_t *)d->start.p, (uint32_t *)d->info.p);
+		bdp_entries<<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, (const uint32_t *)d->start.p, (bdp_entry_t *)d->entries.p, (uint32_t *)d->info.p);
+		HIPCK(hipGetLastError());
+	}
+	*d_tpl = (const uint32_t *)d->tpl.p; *d_entries = (const bdp_entry_t *)d->entries.p; *d_info = (const uint32_t *)d->info.p;
+	return BMH_OK;
+}
+
+int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records)
+{
+	hipStream_t st = (hipStream_t)stream;
+	for (int k = 0; k < 5; ++k) counts[k] = 0;
+	d->n_tpl = T;
+	RCK(d->bits.need(4 * (size_t)((T + 31) / 32) + 4));
+	HIPCK(hipMemsetAsync(d->bits.p, 0, 4 * (size_t)((T + 31) / 32) + 4, st));
+	if (T == 0) { HIPCK(hipStreamSynchronize(st)); return BMH_OK; }
+	if (T >= 1ull << 31) { bmh_set_error("duplicate marking: %llu templates: the decision takes fewer than 2^31", (unsigned long long)T); return BMH_EINVAL; }
+	// entries, two key and two value arrays of up to 2 T items (T templates in the pair pass), the item counts and their scan, the sorts' work space, the bitmap:
+	// 24 + 2 * (16 + 8) + 8 = 80 bytes per template and the work space -- freed before the final sort allocates its own
+	const size_t M = 2 * (size_t)T; size_t sb = sort_bytes(M); const size_t cb = std::max(std::max(escan_bytes((size_t)T + 1), mscan_bytes(M)), sb);
+	size_t fr = 0, tot = 0;
+	HIPCK(hipMemGetInfo(&fr, &tot));
+	// (a buffer is allocated a quarter larger than asked: that is what is counted)
+	const size_t ask = sizeof(bdp_entry_t) * (size_t)T + 2 * 8 * M + 2 * 4 * M + 2 * 4 * ((size_t)T + 1) + cb, want = ask + ask / 4 + (64u << 20);
+	// the final sort that follows: keys and ordinals in and out, 24 bytes per record, a quarter more as allocated, and its work space
+	const size_t sort_ask = 24 * (size_t)n_records + (n_records ? sort_bytes((size_t)n_records) : 0), sort_want = sort_ask + sort_ask / 4 + (64u << 20);
+	if (want <= fr && sort_want > fr) {
+		bmh_set_error("sorted BAM: the final sort of %llu records (%llu templates to mark duplicates among) needs %zu bytes of device memory, %zu are free (sort fewer reads per run, or on a device with more memory)",
+		              (unsigned long long)n_records, (unsigned long long)T, sort_want, fr);
+		return BMH_ENOMEM;
+	}
+	if (want > fr) {
+		bmh_set_error("sorted BAM: marking the duplicates among %llu templates needs %zu bytes of device memory, %zu are free (align fewer reads per run, or on a device with more memory)",
+		              (unsigned long long)T, want, fr);
+		return BMH_ENOMEM;
+	}
+	// (nine buffers allocated and freed per decision: it runs once per sorted file, and what it frees is what the final sort then takes)
+	bmh_grow_t E, k0, k1, v0, v1, cnt, base, tmp, dc;
+	RCK(E.need(sizeof(bdp_entry_t) * (size_t)T)); RCK(k0.need(8 * M)); RCK(k1.need(8 * M)); RCK(v0.need(4 * M)); RCK(v1.need(4 * M)); RCK(cnt.need(4 * ((size_t)T + 1)));
+	RCK(base.need(4 * ((size_t)T + 1))); RCK(tmp.need(cb)); RCK(dc.need(8 * 5));
+	HIPCK(hipMemcpyAsync(E.p, entries, sizeof(bdp_entry_t) * (size_t)T, hipMemcpyHostToDevice, st));
+	HIPCK(hipMemsetAsync(dc.p, 0, 8 * 5, st));
+	const bdp_entry_t *dE = (const bdp_entry_t *)E.p;
+	uint64_t *ka = (uint64_t *)k0.p, *kb = (uint64_t *)k1.p; uint32_t *va = (uint32_t *)v0.p, *vb = (uint32_t *)v1.p;
+	unsigned long long *dcnt = (unsigned long long *)dc.p;
+	// the pair pass: after every radix pass vb holds the permutation, swapped into va for the next.  (tmp and sb are sized for M items and serve the sorts of T and
+	// of m <= M items: rocprim takes a work space larger than it asks for, as csrc/bam_sort_kernels.hip's sorts rely on too)
+	bdp_iota<<<blocks(T), 256, 0, st>>>(va, T);
+	for (int pass = 0; pass < 3; ++pass) {
+		bdp_pair_keys<<<blocks(T), 256, 0, st>>>(dE, va, T, pass, ka);
+		HIPCK(rocprim::radix_sort_pairs(tmp.p, sb, ka, kb, va, vb, (size_t)T, 0, 64, st));
+		std::swap(va, vb);
+	}
+	bdp_pair_decide<<<blocks(T), 256, 0, st>>>(dE, va, T, (uint32_t *)d->bits.p, dcnt);
+	// the fragment pass
+	size_t eb = escan_bytes((size_t)T + 1);
+	HIPCK(hipMemsetAsync((uint32_t *)cnt.p + T, 0, 4, st));
+	bdp_item_counts<<<blocks(T), 256, 0, st>>>(dE, T, (uint32_t *)cnt.p, dcnt);
+	HIPCK(rocprim::exclusive_scan(tmp.p, eb, (uint32_t *)cnt.p, (uint32_t *)base.p, 0u, (size_t)T + 1, rocprim::plus<uint32_t>(), st));
+	uint32_t m32 = 0;
+	HIPCK(hipMemcpyAsync(&m32, (const uint32_t *)base.p + T, 4, hipMemcpyDeviceToHost, st));
+	HIPCK(hipStreamSynchronize(st));
+	const uint64_t m = m32;
+	if (m > M) { bmh_set_error("duplicate marking: internal error: %llu items of %llu templates", (unsigned long long)m, (unsigned long long)T); return BMH_EINVAL; }
+	if (m) {
+		bdp_items<<<blocks(T), 256, 0, st>>>(dE, T, (const uint32_t *)cnt.p, (const uint32_t *)base.p, m, va);
+		for (int pass = 0; pass < 2; ++pass) {
+			bdp_frag_keys<<<blocks(m), 256, 0, st>>>(dE, va, m, pass, ka);
+			HIPCK(rocprim::radix_sort_pairs(tmp.p, sb, ka, kb, va, vb, (size_t)m, 0, 64, st));
+			std::swap(va, vb);
+		}
+		// kb: the sorted end words, va: the items in that order; vb is free: it takes the run heads' indices, whose max-scan goes into k0's bytes
+		uint32_t *hidx = vb, *first = (uint32_t *)k0.p;                   // (ka's bytes: the keys have been read)
+		size_t mb = mscan_bytes((size_t)m);
+		bdp_run_heads<<<blocks(m), 256, 0, st>>>(kb, m, hidx);
+		HIPCK(rocprim::inclusive_scan(tmp.p, mb, hidx, first, (size_t)m, rocprim::maximum<uint32_t>(), st));
+		bdp_frag_decide<<<blocks(m), 256, 0, st>>>(dE, va, first, m, (uint32_t *)d->bits.p, dcnt);
+	}
+	unsigned long long h[5] = {0, 0, 0, 0, 0};
+	HIPCK(hipMemcpyAsync(h, dcnt, 8 * 5, hipMemcpyDeviceToHost, st));
+	HIPCK(hipStreamSynchronize(st));
+	HIPCK(hipGetLastError());
+	for (int k = 0; k < 5; ++k) counts[k] = h[k];
+	return BMH_OK;
+}
+
+int bdp_flag_device(bdp_dev_t *d, uint8_t *d_recs, const uint64_t *d_off, const uint32_t *tord, uint32_t n, uint64_t total, void *stream)
+{
+	hipStream_t st = (hipStream_t)stream;
+	if (n == 0) return BMH_OK;
+	RCK(d->tord.need(4 * (size_t)n));
+	HIPCK(hipMemcpyAsync(d->tord.p, tord, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+	bdp_flag<<<blocks(n), 256, 0, st>>>(d_recs, d_off, (const uint32_t *)d->tord.p, n, total, (const uint32_t *)d->bits.p, d->n_tpl);
+	HIPCK(hipGetLastError());
+	return BMH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the stand-alone entry point
+
+extern "C" int bmh_bam_markdup_device(const uint8_t *recs, uint64_t n_bytes, void *stream, uint8_t **out, uint64_t counts[8])
+{
+	const char *fn = "bmh_bam_markdup_device";
+	hipStream_t st = (hipStream_t)stream;
+	if (!out || !counts || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	*out = nullptr;
+	for (int k = 0; k < BDP_N_COUNTS; ++k) counts[k] = 0;
+	std::vector<uint64_t> off;
+	RCK(bsr_walk(recs, n_bytes, -1, off, fn));
+	const uint32_t n = (uint32_t)(off.size() - 1);
+	for (uint32_t i = 0; i < n; ++i)
+		if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) { bmh_set_error("%s: record %u is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL; }
+	bdp_dev_t d;
+	bmh_grow_t in, in_off;
+	RCK(in.need((size_t)n_bytes + 16)); RCK(in_off.need(8 * off.size()));
+	if (n_bytes) HIPCK(hipMemcpyAsync(in.p, recs, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+	HIPCK(hipMemcpyAsync(in_off.p, off.data(), 8 * off.size(), hipMemcpyHostToDevice, st));
+	const uint32_t *d_tpl; const bdp_entry_t *d_e; const uint32_t *d_info;
+	RCK(bdp_batch_device(&d, (const uint8_t *)in.p, (const uint64_t *)in_off.p, n, n_bytes, st, &d_tpl, &d_e, &d_info));
+	uint32_t info[4] = {0, 0, 0, 0};
+	HIPCK(hipMemcpyAsync(info, d_info, 16, hipMemcpyDeviceToHost, st));
+	HIPCK(hipStreamSynchronize(st));
+	if (n && info[1] != 0xffffffffu) return bdp_batch_refused(n, info[1] ? info[1] : n + 1, fn);
+	const uint32_t T = n ? info[0] : 0;
+	if (T > n) { bmh_set_error("%s: internal error: %u templates among %u records", fn, T, n); return BMH_EINVAL; }
+	std::vector<bdp_entry_t> E(T); std::vector<uint32_t> tpl(n);
+	if (T) HIPCK(hipMemcpyAsync(E.data(), d_e, sizeof(bdp_entry_t) * (size_t)T, hipMemcpyDeviceToHost, st));
+	if (n) HIPCK(hipMemcpyAsync(tpl.data(), d_tpl, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+	HIPCK(hipStreamSynchronize(st));
+	RCK(bdp_decide_device(&d, E.data(), T, st, counts));
+	counts[BDP_SECSUP] = info[2]; counts[BDP_UNMAPPED] = info[3]; counts[BDP_TEMPLATES] = T;
+	RCK(bdp_flag_device(&d, (uint8_t *)in.p, (const uint64_t *)in_off.p, tpl.data(), n, n_bytes, st));
+	uint8_t *o = (uint8_t *)malloc((size_t)n_bytes + 1);
+	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+	if (n_bytes && hipMemcpyAsync(o, in.p, (size_t)n_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) { free(o); bmh_set_error("%s: the copy of the records failed", fn); return BMH_ENODEV; }
+	if (hipStreamSynchronize(st) != hipSuccess) { free(o); bmh_set_error("%s: %s", fn, hipGetErrorString(hipGetLastError())); return BMH_ENODEV; }
+	*out = o;
+	return BMH_OK;
+}

@@ -5,6 +5,7 @@
 #include <vector>
 #include "bmh_internal.h"
 #include "bam_sort_core.h"
+#include "bam_dup_core.h"
 
 typedef int (*bsr_sink_t)(void *user, const char *bytes, size_t n);
 
@@ -28,14 +29,17 @@ struct bsr_index_t {
 };
 
 // Sorted runs kept until the end of the input: the records in host memory up to mem_bytes, beyond that in one unnamed temporary file; keys and offsets
-// (16 bytes per record) always in memory
-struct bsr_run_t { uint64_t n = 0, bytes = 0; std::vector<uint64_t> keys, off; uint8_t *mem = nullptr; int64_t file_at = -1; };
+// (16 bytes per record) always in memory.  With duplicate marking (csrc/bam_dup_core.h) a run also keeps every record's template ordinal within its batch (tpl, 4 bytes
+// per record, outside the budget like keys and offsets) and the ordinal of its first template in the whole run (tbase); the store keeps the templates' entries
+struct bsr_run_t { uint64_t n = 0, bytes = 0; std::vector<uint64_t> keys, off; uint8_t *mem = nullptr; int64_t file_at = -1; std::vector<uint32_t> tpl; uint64_t tbase = 0; };
+struct bsr_dup_t { const uint32_t *tpl; const bdp_entry_t *entries; uint32_t n_tpl; uint64_t secsup, unmapped; };      // what a batch adds when duplicates are marked
 struct bsr_store_t {
 	uint64_t mem_bytes = 4ull << 30, used = 0, spilled = 0; std::string tmp_dir; int fd = -1; uint64_t file_bytes = 0;
 	std::vector<bsr_run_t> runs;
+	std::vector<bdp_entry_t> entries; uint64_t dup_info[2] = {0, 0};         // duplicate marking: every template's entry in input order; secondary / supplementary and unmapped records
 	~bsr_store_t() { clear(); }
 	void clear();
-	int append(const uint8_t *recs, uint64_t bytes, const uint64_t *keys, const uint64_t *off, uint64_t n);
+	int append(const uint8_t *recs, uint64_t bytes, const uint64_t *keys, const uint64_t *off, uint64_t n, const bsr_dup_t *dup = nullptr);
 	int read(const bsr_run_t &r, uint64_t a, uint64_t b, uint8_t *dst) const;       // bytes [a, b) of the run's records
 };
 
@@ -48,16 +52,22 @@ struct bsr_dev_t;                                                  // device buf
 bsr_dev_t *bsr_dev_create(void);
 void bsr_dev_free(bsr_dev_t *d);
 // a batch's records d_recs with offsets d_off [n + 1] (device) -> the sorted run: *d_sorted (total bytes), *d_keys [n], *d_soff [n + 1], all in d until its next call
+// d_side [n] (device, or NULL): a word per record that follows it through the sort -> *d_side_sorted [n]
 int bsr_sort_run_device(bsr_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream,
-                        const uint8_t **d_sorted, const uint64_t **d_keys, const uint64_t **d_soff);
+                        const uint8_t **d_sorted, const uint64_t **d_keys, const uint64_t **d_soff, const uint32_t *d_side = nullptr, const uint32_t **d_side_sorted = nullptr);
 // every run's keys (host) -> ord [n]: the records' global ordinals (run after run) in sorted order
 int bsr_sort_keys_device(bsr_dev_t *d, const uint64_t *keys, uint64_t n, void *stream, uint32_t *ord);
 // one window of the final file.  src (host, pinned or not) [src_bytes]: the records of the window as the runs hold them; src_off / size [n] (host): record j of the
 // window in src.  The records are gathered into order, compressed (ws), indexed (ix: heads appended; lin and counts stay on the device until bsr_index_finish) and
 // the members handed to the sink
+// dup, tord [n] (host): the decided duplicates (bdp_decide_device) and every record's global template ordinal -- the flags are set between the gather and the compressor
 int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64_t src_bytes, const uint64_t *src_off, const uint32_t *size, uint32_t n, int level,
-                      void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user);
+                      void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, struct bdp_dev_t *dup = nullptr, const uint32_t *tord = nullptr, double *flag_ms = nullptr);
 // every run of the store -> the record members of the sorted file (to the sink, in windows of `window` records; 0: about 64 MiB of records) and its index
-int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user);
+// dup_counts (or NULL) [8]: mark the duplicates among the store's templates first (csrc/bam_dup_kernels.hip) and flag every window's records; the counts of bam_dup.h
+int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user,
+                     uint64_t *dup_counts = nullptr, double *dup_ms = nullptr);
+// dup_ms (or NULL) [2]: += the decision's milliseconds (host clock around bdp_decide_device) and the windows' flag steps' (events around the upload of the ordinals
+// and the flag kernel)
 int bsr_index_begin(bsr_dev_t *d, const bsr_index_t &ix, void *stream);
 int bsr_index_finish(bsr_dev_t *d, bsr_index_t &ix, void *stream);

@@ -9,6 +9,7 @@
 #include <map>
 #include <numeric>
 #include "bam_sort.h"
+#include "bam_dup.h"
 
 #ifndef O_TMPFILE
 #define O_TMPFILE 0
@@ -115,14 +116,16 @@ void bsr_store_t::clear()
 {
 	for (bsr_run_t &r : runs) free(r.mem);
 	runs.clear(); used = 0; spilled = 0; file_bytes = 0;
+	entries.clear(); dup_info[0] = dup_info[1] = 0;
 	if (fd >= 0) close(fd);
 	fd = -1;
 }
 
-int bsr_store_t::append(const uint8_t *recs, uint64_t bytes, const uint64_t *keys, const uint64_t *off, uint64_t n)
+int bsr_store_t::append(const uint8_t *recs, uint64_t bytes, const uint64_t *keys, const uint64_t *off, uint64_t n, const bsr_dup_t *dup)
 {
 	bsr_run_t r;
 	r.n = n; r.bytes = bytes; r.keys.assign(keys, keys + n); r.off.assign(off, off + n + 1);
+	if (dup) { r.tpl.assign(dup->tpl, dup->tpl + n); r.tbase = entries.size(); }
 	if (bytes <= mem_bytes - std::min(used, mem_bytes)) {
 		r.mem = (uint8_t *)malloc(bytes + 1);
 		if (!r.mem) { bmh_set_error("sorted BAM: out of memory for a run of %llu bytes", (unsigned long long)bytes); return BMH_ENOMEM; }
@@ -150,6 +153,7 @@ int bsr_store_t::append(const uint8_t *recs, uint64_t bytes, const uint64_t *key
 		}
 		r.file_at = (int64_t)file_bytes; file_bytes += bytes; ++spilled;
 	}
+	if (dup) { entries.insert(entries.end(), dup->entries, dup->entries + dup->n_tpl); dup_info[0] += dup->secsup; dup_info[1] += dup->unmapped; }
 	runs.push_back(std::move(r));
 	return BMH_OK;
 }
@@ -185,10 +189,9 @@ extern "C" int bmh_bam_sort_host(const uint8_t *recs, uint64_t n_bytes, uint8_t 
 }
 
 // header members, the sorted records in windows of `window` records (0: as many as hold about 64 MiB), the end-of-file member; and the index
-extern "C" int bmh_bam_sorted_file_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                        int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes)
+static int sorted_file_host(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                            int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts)
 {
-	const char *fn = "bmh_bam_sorted_file_host";
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
 	bsr_index_t ix;
@@ -196,6 +199,12 @@ extern "C" int bmh_bam_sorted_file_host(const char *header_text, int n_contigs, 
 	if (rc != BMH_OK) return rc;
 	std::vector<uint64_t> off, keys; std::vector<uint32_t> ord;
 	if ((rc = bsr_walk(recs, n_bytes, n_contigs, off, fn)) != BMH_OK) return rc;
+	std::vector<uint8_t> marked;                                   // duplicate marking: the flags are set before the sort (0x400 enters no key, bin or index)
+	if (dup_counts) {
+		marked.assign(recs, recs + n_bytes);
+		if ((rc = bdp_markdup_host(marked.data(), off, dup_counts, fn)) != BMH_OK) return rc;
+		recs = marked.data();
+	}
 	bsr_sort_host(recs, off, keys, ord);
 	const size_t n = ord.size();
 	std::string file;
@@ -231,4 +240,18 @@ extern "C" int bmh_bam_sorted_file_host(const char *header_text, int n_contigs, 
 	memcpy(f, file.data(), file.size()); memcpy(i, ib.data(), ib.size());
 	*bam = f; *bam_bytes = file.size(); *bai = i; *bai_bytes = ib.size();
 	return BMH_OK;
+}
+
+extern "C" int bmh_bam_sorted_file_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                        int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes)
+{
+	return sorted_file_host("bmh_bam_sorted_file_host", header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, bai, bai_bytes, nullptr);
+}
+
+extern "C" int bmh_bam_sorted_file_markdup_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                                int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8])
+{
+	const char *fn = "bmh_bam_sorted_file_markdup_host";
+	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, bai, bai_bytes, counts);
 }

@@ -17,9 +17,12 @@
 #include <stdlib.h>
 #include <string.h>
 #include <rocprim/rocprim.hpp>
+#include <stdio.h>
 #include <algorithm>
+#include <chrono>
 #include <vector>
 #include "bam_sort.h"
+#include "bam_dup.h"
 #include "bam_ws.h"
 
 #define HIPCK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
@@ -27,6 +30,8 @@
 
 struct bsr_dev_t {
 	bmh_grow_t keys, keys2, ord, ord2, tmp, src_off, size, soff, sorted, in, in_off;      // sort and gather
+	hipEvent_t ev_flag[2] = {nullptr, nullptr};                                          // around a window's flag step (duplicate marking)
+	bmh_grow_t side;                                                                      // a word per record, permuted with a batch's records (duplicate marking)
 	bmh_grow_t head, hpos, heads, lin, counts, n_win, lin_off;                            // the index pass; lin, counts: of the whole file
 	uint8_t *h_buf = nullptr; size_t h_cap = 0;                                          // pinned: a window's records on their way up, its members on their way down
 	int n_ref = 0;
@@ -40,12 +45,14 @@ struct bsr_dev_t {
 		h_cap = c;
 		return BMH_OK;
 	}
-	~bsr_dev_t() { if (h_buf) (void)hipHostFree(h_buf); }
+	~bsr_dev_t() { if (h_buf) (void)hipHostFree(h_buf); for (hipEvent_t e : ev_flag) if (e) (void)hipEventDestroy(e); }
 };
 
 namespace {
 
 constexpr int G = 16;              // lanes per record of the gather
+
+double bsr_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 __global__ void __launch_bounds__(256) bsr_keys(const uint8_t *__restrict__ recs, const uint64_t *__restrict__ off, uint32_t n, uint64_t total, uint64_t *__restrict__ keys, uint32_t *__restrict__ ord)
 {
@@ -62,12 +69,14 @@ __global__ void __launch_bounds__(256) bsr_iota(uint32_t *__restrict__ ord, uint
 	if (i < n) ord[i] = (uint32_t)i;
 }
 
-__global__ void __launch_bounds__(256) bsr_perm(const uint64_t *__restrict__ off, const uint32_t *__restrict__ ord, uint32_t n, uint64_t *__restrict__ src_off, uint32_t *__restrict__ size)
+__global__ void __launch_bounds__(256) bsr_perm(const uint64_t *__restrict__ off, const uint32_t *__restrict__ ord, uint32_t n, uint64_t *__restrict__ src_off, uint32_t *__restrict__ size,
+                                                const uint32_t *__restrict__ side, uint32_t *__restrict__ side_out)
 {
 	const uint32_t j = blockIdx.x * 256 + threadIdx.x;
 	if (j >= n) return;
 	const uint32_t i = ord[j] < n ? ord[j] : 0;
 	src_off[j] = off[i]; size[j] = (uint32_t)(off[i + 1] - off[i]);
+	if (side) side_out[j] = side[i];
 }
 
 // src and dst are 4-byte aligned buffers with at least 4 bytes of room behind src_bytes / dst_bytes (the last source word of a record may lie partly behind it)
@@ -155,19 +164,22 @@ int scan_and_gather(bsr_dev_t *d, const uint8_t *d_src, uint64_t src_bytes, uint
 bsr_dev_t *bsr_dev_create(void) { return new bsr_dev_t(); }
 void bsr_dev_free(bsr_dev_t *d) { delete d; }
 
-int bsr_sort_run_device(bsr_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint8_t **d_sorted, const uint64_t **d_keys, const uint64_t **d_soff)
+int bsr_sort_run_device(bsr_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint8_t **d_sorted, const uint64_t **d_keys, const uint64_t **d_soff,
+                        const uint32_t *d_side, const uint32_t **d_side_sorted)
 {
 	hipStream_t st = (hipStream_t)stream;
 	size_t sb = sort_bytes(n);
 	RCK(d->keys.need(8 * ((size_t)n + 1))); RCK(d->keys2.need(8 * ((size_t)n + 1))); RCK(d->ord.need(4 * ((size_t)n + 1))); RCK(d->ord2.need(4 * ((size_t)n + 1)));
 	RCK(d->src_off.need(8 * ((size_t)n + 1))); RCK(d->size.need(4 * ((size_t)n + 2))); RCK(d->tmp.need(sb));
+	if (d_side) RCK(d->side.need(4 * ((size_t)n + 1)));
 	if (n) {
 		bsr_keys<<<(n + 255) / 256, 256, 0, st>>>(d_recs, d_off, n, total, (uint64_t *)d->keys.p, (uint32_t *)d->ord.p);
 		HIPCK(rocprim::radix_sort_pairs(d->tmp.p, sb, (uint64_t *)d->keys.p, (uint64_t *)d->keys2.p, (uint32_t *)d->ord.p, (uint32_t *)d->ord2.p, (size_t)n, 0, 64, st));
-		bsr_perm<<<(n + 255) / 256, 256, 0, st>>>(d_off, (const uint32_t *)d->ord2.p, n, (uint64_t *)d->src_off.p, (uint32_t *)d->size.p);
+		bsr_perm<<<(n + 255) / 256, 256, 0, st>>>(d_off, (const uint32_t *)d->ord2.p, n, (uint64_t *)d->src_off.p, (uint32_t *)d->size.p, d_side, d_side ? (uint32_t *)d->side.p : nullptr);
 	}
 	RCK(scan_and_gather(d, d_recs, total, n, total, st));
 	*d_sorted = (const uint8_t *)d->sorted.p; *d_keys = (const uint64_t *)d->keys2.p; *d_soff = (const uint64_t *)d->soff.p;
+	if (d_side_sorted) *d_side_sorted = d_side ? (const uint32_t *)d->side.p : nullptr;
 	return BMH_OK;
 }
 
@@ -225,7 +237,7 @@ int bsr_index_finish(bsr_dev_t *d, bsr_index_t &ix, void *stream)
 }
 
 int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64_t src_bytes, const uint64_t *src_off, const uint32_t *size, uint32_t n, int level,
-                      void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user)
+                      void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, bdp_dev_t *dup, const uint32_t *tord, double *flag_ms)
 {
 	hipStream_t st = (hipStream_t)stream;
 	if (n == 0) return BMH_OK;
@@ -239,6 +251,11 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 	HIPCK(hipMemcpyAsync(d->src_off.p, src_off, 8 * (size_t)n, hipMemcpyHostToDevice, st));
 	HIPCK(hipMemcpyAsync(d->size.p, size, 4 * (size_t)n, hipMemcpyHostToDevice, st));
 	RCK(scan_and_gather(d, (const uint8_t *)d->in.p, src_bytes, n, total, st));
+	if (dup) {                                                  // (sort key, bin and index do not read 0x400)
+		if (flag_ms) { for (hipEvent_t &e : d->ev_flag) if (!e) HIPCK(hipEventCreate(&e)); HIPCK(hipEventRecord(d->ev_flag[0], st)); }
+		RCK(bdp_flag_device(dup, (uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, tord, n, total, st));
+		if (flag_ms) HIPCK(hipEventRecord(d->ev_flag[1], st));
+	}
 	const uint8_t *d_members = nullptr; uint64_t mb = 0;
 	RCK(bmh_bgzf_deflate_device(ws, (const uint8_t *)d->sorted.p, total, level, st, &d_members, &mb));
 	// the index pass: the members' offsets are the compressor's scan (ws->moff [n_members + 1])
@@ -256,6 +273,7 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 	HIPCK(hipMemcpyAsync(d->h_buf, d_members, (size_t)mb, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
 	HIPCK(hipGetLastError());
+	if (dup && flag_ms) { float ms = 0; HIPCK(hipEventElapsedTime(&ms, d->ev_flag[0], d->ev_flag[1])); *flag_ms += ms; }
 	if (nh == 0 || nh > n) { bmh_set_error("sorted BAM: internal error: %u chunk heads among %u records", nh, n); return BMH_EINVAL; }
 	const size_t h0 = ix.heads.size();
 	ix.heads.resize(h0 + nh);
@@ -266,12 +284,24 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 }
 
 // every run of the store -> the sorted file's record members (to the sink) and its index
-int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user)
+int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, uint64_t *dup_counts, double *dup_ms)
 {
 	uint64_t n = 0, bytes = 0;
 	std::vector<uint64_t> first;
 	for (const bsr_run_t &r : S.runs) { first.push_back(n); n += r.n; bytes += r.bytes; }
 	RCK(bsr_index_begin(d, ix, stream));
+	// duplicate marking: the decision over every template's entry comes first (its work space is freed before the final sort takes its own); the bitmap stays
+	struct dup_own_t { bdp_dev_t *p = nullptr; ~dup_own_t() { if (p) bdp_dev_free(p); } } dup;
+	std::vector<uint32_t> tord; double decide_ms = 0, flag_ms = 0;
+	if (dup_counts) {
+		for (int k = 0; k < BDP_N_COUNTS; ++k) dup_counts[k] = 0;
+		for (const bsr_run_t &r : S.runs) if (r.tpl.size() != r.n) { bmh_set_error("sorted BAM: internal error: a run without its records' template ordinals"); return BMH_EINVAL; }
+		if (!(dup.p = bdp_dev_create())) return BMH_ENOMEM;
+		const double t0 = bsr_now_ms();
+		RCK(bdp_decide_device(dup.p, S.entries.data(), S.entries.size(), stream, dup_counts, n));
+		dup_counts[BDP_SECSUP] = S.dup_info[0]; dup_counts[BDP_UNMAPPED] = S.dup_info[1]; dup_counts[BDP_TEMPLATES] = S.entries.size();
+		decide_ms = bsr_now_ms() - t0;
+	}
 	if (n) {
 		std::vector<uint64_t> keys; keys.reserve((size_t)n);
 		for (const bsr_run_t &r : S.runs) keys.insert(keys.end(), r.keys.begin(), r.keys.end());
@@ -284,7 +314,7 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint3
 		for (uint64_t a = 0; a < n; a += W) {
 			const uint64_t b = std::min(n, a + W); const uint32_t m = (uint32_t)(b - a);
 			std::fill(lo.begin(), lo.end(), ~0ull); std::fill(hi.begin(), hi.end(), 0);
-			run_of.resize(m); src_off.resize(m); size.resize(m);
+			run_of.resize(m); src_off.resize(m); size.resize(m); if (dup.p) tord.resize(m);
 			for (uint32_t j = 0; j < m; ++j) {
 				const uint64_t g = ord[(size_t)(a + j)];
 				const size_t r = (size_t)(std::upper_bound(first.begin(), first.end(), g) - first.begin()) - 1;
@@ -300,10 +330,17 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint3
 				const bsr_run_t &R = S.runs[run_of[j]];
 				const uint64_t i = ord[(size_t)(a + j)] - first[run_of[j]];
 				src_off[j] = place[run_of[j]] + (R.off[i] - R.off[lo[run_of[j]]]); size[j] = (uint32_t)(R.off[i + 1] - R.off[i]);
+				if (dup.p) tord[j] = (uint32_t)(R.tbase + R.tpl[i]);
 			}
 			// (the pinned buffer takes the members once the records are on the device: the compressor waits for the stream in between)
-			RCK(bsr_window_device(d, ws, d->h_buf, sb, src_off.data(), size.data(), m, level, stream, ix, sink, user));
+			RCK(bsr_window_device(d, ws, d->h_buf, sb, src_off.data(), size.data(), m, level, stream, ix, sink, user, dup.p, dup.p ? tord.data() : nullptr, dup.p ? &flag_ms : nullptr));
 		}
+	}
+	if (dup_counts) {
+		if (dup_ms) { dup_ms[0] += decide_ms; dup_ms[1] += flag_ms; }
+		if (getenv("BMH_ALIGNER_TRACE"))
+			fprintf(stderr, "[aligner] duplicate marking: %zu templates (%zu bytes of entries, %llu of ordinals kept) decided in %.1f ms, the windows' flags set in %.1f ms\n", S.entries.size(),
+			        sizeof(bdp_entry_t) * S.entries.size(), 4ull * (unsigned long long)n, decide_ms, flag_ms);
 	}
 	return bsr_index_finish(d, ix, stream);
 }
@@ -311,14 +348,33 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint3
 // ---------------------------------------------------------------------------------------------------------------- the stand-alone entry points
 
 namespace {
-int to_store(bsr_dev_t *d, const uint8_t *recs, uint64_t n_bytes, const std::vector<uint64_t> &off, hipStream_t st, std::vector<uint8_t> &sorted, std::vector<uint64_t> &keys, std::vector<uint64_t> &soff)
+// what duplicate marking keeps of a stream: its records' template ordinals in sorted order, the templates' entries, the line counts
+struct dup_host_t { std::vector<uint32_t> tpl; std::vector<bdp_entry_t> entries; uint64_t secsup = 0, unmapped = 0; };
+int to_store(bsr_dev_t *d, const uint8_t *recs, uint64_t n_bytes, const std::vector<uint64_t> &off, hipStream_t st, std::vector<uint8_t> &sorted, std::vector<uint64_t> &keys, std::vector<uint64_t> &soff,
+             dup_host_t *dh = nullptr, const char *fn = "")
 {
 	const uint32_t n = (uint32_t)(off.size() - 1);
 	RCK(d->in.need((size_t)n_bytes + 16)); RCK(d->in_off.need(8 * off.size()));
 	HIPCK(hipMemcpyAsync(d->in.p, recs, (size_t)n_bytes, hipMemcpyHostToDevice, st));
 	HIPCK(hipMemcpyAsync(d->in_off.p, off.data(), 8 * off.size(), hipMemcpyHostToDevice, st));
 	const uint8_t *ds; const uint64_t *dk, *dso;
-	RCK(bsr_sort_run_device(d, (const uint8_t *)d->in.p, (const uint64_t *)d->in_off.p, n, n_bytes, st, &ds, &dk, &dso));
+	struct dup_own_t { bdp_dev_t *p = nullptr; ~dup_own_t() { if (p) bdp_dev_free(p); } } dup;
+	const uint32_t *d_tpl = nullptr, *d_info = nullptr, *d_tpl_sorted = nullptr; const bdp_entry_t *d_e = nullptr;
+	if (dh) {
+		if (!(dup.p = bdp_dev_create())) return BMH_ENOMEM;
+		RCK(bdp_batch_device(dup.p, (const uint8_t *)d->in.p, (const uint64_t *)d->in_off.p, n, n_bytes, st, &d_tpl, &d_e, &d_info));
+	}
+	RCK(bsr_sort_run_device(d, (const uint8_t *)d->in.p, (const uint64_t *)d->in_off.p, n, n_bytes, st, &ds, &dk, &dso, d_tpl, &d_tpl_sorted));
+	if (dh) {
+		uint32_t info[4] = {0, 0, 0, 0};
+		HIPCK(hipMemcpyAsync(info, d_info, 16, hipMemcpyDeviceToHost, st));
+		HIPCK(hipStreamSynchronize(st));
+		if (n && info[1] != 0xffffffffu) return bdp_batch_refused(n, info[1] ? info[1] : n + 1, fn);
+		if (info[0] > n) { bmh_set_error("%s: internal error: %u templates among %u records", fn, info[0], n); return BMH_EINVAL; }
+		dh->tpl.resize(n); dh->entries.resize(n ? info[0] : 0); dh->secsup = info[2]; dh->unmapped = info[3];
+		if (n) HIPCK(hipMemcpyAsync(dh->tpl.data(), d_tpl_sorted, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+		if (!dh->entries.empty()) HIPCK(hipMemcpyAsync(dh->entries.data(), d_e, sizeof(bdp_entry_t) * dh->entries.size(), hipMemcpyDeviceToHost, st));
+	}
 	sorted.resize((size_t)n_bytes + 1); keys.resize((size_t)n + 1); soff.resize((size_t)n + 1);
 	if (n_bytes) HIPCK(hipMemcpyAsync(sorted.data(), ds, (size_t)n_bytes, hipMemcpyDeviceToHost, st));
 	if (n) HIPCK(hipMemcpyAsync(keys.data(), dk, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
@@ -347,10 +403,9 @@ extern "C" int bmh_bam_sort_device(const uint8_t *recs, uint64_t n_bytes, void *
 	return BMH_OK;
 }
 
-extern "C" int bmh_bam_sorted_file_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                          int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes)
+static int sorted_file_device(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                              int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts)
 {
-	const char *fn = "bmh_bam_sorted_file_device";
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
 	if (level != 0 && level != 1) { bmh_set_error("%s: level %d (0 or 1)", fn, level); return BMH_EINVAL; }
@@ -360,9 +415,14 @@ extern "C" int bmh_bam_sorted_file_device(const char *header_text, int n_contigs
 	RCK(bsr_walk(recs, n_bytes, n_contigs, off, fn));
 	bsr_dev_t d;
 	bsr_store_t S;
+	if (dup_counts)
+		for (size_t i = 0; i + 1 < off.size(); ++i)
+			if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) { bmh_set_error("%s: record %zu is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL; }
 	if (off.size() > 1) {
-		RCK(to_store(&d, recs, n_bytes, off, (hipStream_t)stream, sorted, keys, soff));
-		RCK(S.append(sorted.data(), n_bytes, keys.data(), soff.data(), off.size() - 1));
+		dup_host_t dh;
+		RCK(to_store(&d, recs, n_bytes, off, (hipStream_t)stream, sorted, keys, soff, dup_counts ? &dh : nullptr, fn));
+		const bsr_dup_t bd = {dh.tpl.data(), dh.entries.data(), (uint32_t)dh.entries.size(), dh.secsup, dh.unmapped};
+		RCK(S.append(sorted.data(), n_bytes, keys.data(), soff.data(), off.size() - 1, dup_counts ? &bd : nullptr));
 	}
 	std::string file;
 	uint8_t *hdr = nullptr, *hm = nullptr; uint64_t hb = 0, hmb = 0;
@@ -373,7 +433,7 @@ extern "C" int bmh_bam_sorted_file_device(const char *header_text, int n_contigs
 	file.append((const char *)hm, hmb); bmh_free(hm);
 	const uint64_t base = file.size();
 	bmh_bam_ws_t *ws = bmh_bam_ws_create();
-	rc = bsr_merge_device(&d, ws, S, window, level, stream, ix, sink_string, &file);
+	rc = bsr_merge_device(&d, ws, S, window, level, stream, ix, sink_string, &file, dup_counts);
 	bmh_bam_ws_free(ws);
 	if (rc != BMH_OK) return rc;
 	file.append((const char *)bmh_bgzf_eof, 28);
@@ -383,4 +443,18 @@ extern "C" int bmh_bam_sorted_file_device(const char *header_text, int n_contigs
 	memcpy(f, file.data(), file.size()); memcpy(i, ib.data(), ib.size());
 	*bam = f; *bam_bytes = file.size(); *bai = i; *bai_bytes = ib.size();
 	return BMH_OK;
+}
+
+extern "C" int bmh_bam_sorted_file_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                          int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes)
+{
+	return sorted_file_device("bmh_bam_sorted_file_device", header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, bai, bai_bytes, nullptr);
+}
+
+extern "C" int bmh_bam_sorted_file_markdup_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                                  int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8])
+{
+	const char *fn = "bmh_bam_sorted_file_markdup_device";
+	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, bai, bai_bytes, counts);
 }

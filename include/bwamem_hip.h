@@ -835,6 +835,29 @@ int bmh_bam_sorted_file_host(const char *header_text, int n_contigs, const char 
 int bmh_aligner_set_sort(bmh_aligner_t *a, uint64_t mem_bytes, const char *tmp_dir, uint32_t window_records);
 int bmh_aligner_sort_index(bmh_aligner_t *a, uint64_t base_offset, uint8_t **bai, uint64_t *bai_bytes);
 
+/* ---- Duplicate marking in sorted BAM (csrc/bam_dup_core.h, csrc/bam_dup_kernels.hip, csrc/bam_dup_host.cpp).
+ * Picard MarkDuplicates' rules on templates (a single read or a read pair, its records next to each other in the writer's order): the unclipped 5' ends and
+ * strands of the primary lines are the key, the sum of the base qualities >= 15 the score, ties go to the template that came first in the input; a fragment is
+ * a duplicate wherever a pair has an end.  Every record of a duplicate template gets flag 0x400.  No optical duplicates, one library, nothing removed.
+ * counts [8]: pairs examined, fragments examined, duplicate pairs, duplicate fragments, records flagged, secondary or supplementary records, unmapped records,
+ * templates.
+ * bmh_bam_markdup_device / _host: a record stream in the writer's order (whole records; the first begins a template; paired templates hold both primary lines --
+ * else BMH_EINVAL with a message) -> the same records with the flags set (malloc'd; bmh_free).
+ * bmh_bam_sorted_file_markdup_device / _host: bmh_bam_sorted_file_* with the duplicates of the stream (given in the writer's order) marked.
+ * bmh_aligner_set_markdup: the runs that follow mark duplicates; refused (the aligner stays as it was) unless the output format is BMH_OUT_BAM_SORTED, and switched
+ * off by every bmh_aligner_set_output of another format.  bmh_aligner_markdup_counts: the counts of the last marked run. */
+int bmh_bam_markdup_device(const uint8_t *records, uint64_t n_bytes, void *stream, uint8_t **out, uint64_t counts[8]);
+int bmh_bam_markdup_host(const uint8_t *records, uint64_t n_bytes, uint8_t **out, uint64_t counts[8]);
+int bmh_bam_sorted_file_markdup_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
+                                       int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8]);
+int bmh_bam_sorted_file_markdup_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
+                                     int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8]);
+int bmh_aligner_set_markdup(bmh_aligner_t *a, int on);
+int bmh_aligner_markdup_counts(bmh_aligner_t *a, uint64_t out[8]);
+/* where the last marked run's extra time went: [0] the decision, ms  [1] the windows' flag steps (ordinals up, flag kernel), ms  [2] bytes of ordinals and entries
+ * that came down with the batches */
+int bmh_aligner_markdup_times(bmh_aligner_t *a, double out[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,12 @@ the merge: key sort, windows, compression, index pass, sink) --, and bam_sort al
 --runs runs with their spreads.  Writes profiles/bam_sort.json (or --out).  The read set is the bench's two batches, each twice: every read occurs twice, so the
 sorted file's size (the two copies land next to each other) and the merge's compression rate are not those of real data.
 
-    python scripts/bam_sort_rate.py [--runs 3] [--reads 1000000] [--genome-mbp 3100] [--out FILE]
+    python scripts/bam_sort_rate.py [--runs 3] [--reads 1000000] [--genome-mbp 3100] [--out FILE] [--markdup]
+
+--markdup: the duplicate-marking leg instead (profiles/bam_markdup.json): the sorted in-memory row re-run, the same row with duplicates marked -- with the
+decision alone and the windows' flag steps alone, as the library times them (bmh_aligner_markdup_times) --, the same two rows on a paired read set (FR pairs
+of the same genome, each batch twice), and bam_markdup alone on one batch's records (walk, copies, heads, entries, decision, flags).  Every read of the set occurs twice, so half its templates are duplicates: the
+duplicate rate says nothing about real data.
 """
 import argparse
 import ctypes as C
@@ -35,6 +40,7 @@ def main():
     ap.add_argument("--reads", type=int, default=1_000_000, help="reads per distinct batch; a run takes four times as many")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--out", default="")
+    ap.add_argument("--markdup", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     L = B.load_library()
@@ -65,34 +71,86 @@ def main():
     path = os.path.join(tmp, "se.fa")
     recs.tofile(path)
     del recs
+    ppath = os.path.join(tmp, "pe.fa")
+    if a.markdup:                                             # FR pairs, n reads per distinct batch, each batch twice; mates share a name
+        p1 = B.synth.make_pairs(g, n // 2, rl, seed=7, holes=holes)[0]; p2 = B.synth.make_pairs(g, n // 2, rl, seed=1007, holes=holes)[0]
+        pasc = B.synth.codes_to_ascii(np.concatenate([p1.reshape(-1), p2.reshape(-1), p1.reshape(-1), p2.reshape(-1)]))
+        pn = np.frombuffer("".join(np.char.add(">p", np.char.zfill((np.arange(n4) // 2).astype(str), w)).tolist()).encode(), np.uint8).reshape(n4, w + 2)
+        prec = np.empty((n4, w + 3 + rl + 1), np.uint8)
+        prec[:, :w + 2] = pn; prec[:, w + 2] = 10; prec[:, w + 3:w + 3 + rl] = pasc.reshape(n4, rl); prec[:, -1] = 10
+        prec.tofile(ppath)
+        del prec
     nat = NativeAligner(dindex, pac_h, n_genome, contigs, None, co, ExtParams.default(), po, pe_o)
     result = {"genome_mbp": a.genome_mbp, "reads_per_run": n4, "setup_s": round(time.time() - t0, 1), "runs": a.runs, "host_threads": nth, "rows": {}}
 
-    def run(fmt, spill=False, keep=None):
+    def run(fmt, spill=False, keep=None, markdup=False, paired=False):
+        src = ppath if paired else path
         nat.set_output(fmt, 1)
         if fmt == "bam_sorted":
             nat.set_sort(1 if spill else 64 << 30, tmp, 0)
+            nat.set_markdup(markdup)
         nbytes = [0]
 
         def sink(mv):
             nbytes[0] += len(mv)
             if keep is not None and len(keep) < 1:
                 keep.append(bytes(mv))
-        secs, merge = [], []
+        secs, merge, times = [], [], []
         for it in range(a.runs + 1):
             nbytes[0] = 0
             t1 = time.perf_counter()
-            st = nat.run_file(path, False, sink, batch_reads=n4 // 4, n_lanes=2, n_threads=nth)
+            st = nat.run_file(src, paired, sink, batch_reads=n4 // 4, n_lanes=3 if paired else 2, n_threads=nth)
             if it:
                 secs.append(time.perf_counter() - t1); merge.append(st.format_seconds)
+                if markdup:
+                    times.append(nat.markdup_times())
         row = stats(secs, n4, 1e6)
         row["unit"] = "Mreads/s"; row["bytes_out_per_read"] = round(nbytes[0] / n4, 1)
         if fmt == "bam_sorted":
             nat.sort_index(0)
             row["final_merge"] = stats(merge, n4, 1e6); row["per_batch_part"] = stats([s - m for s, m in zip(secs, merge)], n4, 1e6)
             row["final_merge_share_pct"] = round(100 * sorted(merge)[len(merge) // 2] / sorted(secs)[len(secs) // 2], 1)
+            if markdup:
+                row["counts"] = nat.markdup_counts()
+                tpl = row["counts"]["templates"]
+                row["decision_alone"] = stats([t["decision_ms"] / 1e3 for t in times], tpl, 1e6); row["decision_alone"]["unit"] = "Mtemplates/s"
+                row["decision_alone"]["ms"] = [round(t["decision_ms"], 2) for t in times]
+                row["window_flags_alone"] = stats([max(t["window_flags_ms"], 1e-6) / 1e3 for t in times], n4, 1e6); row["window_flags_alone"]["unit"] = "Mrecords/s (ordinals up, flag kernel)"
+                row["window_flags_alone"]["ms"] = [round(t["window_flags_ms"], 2) for t in times]
+                row["entries_d2h_bytes_per_read"] = round(times[0]["entries_d2h_bytes"] / n4, 1)
         return row
     keep = []
+    if a.markdup:
+        from bwamem_hip.lib import bam_markdup
+        result["rows"]["reads_to_bam_unsorted"] = run("bam", keep=keep)
+        result["rows"]["reads_to_sorted_bam_in_memory"] = run("bam_sorted")
+        result["rows"]["reads_to_sorted_bam_in_memory_markdup"] = run("bam_sorted", markdup=True)
+        result["rows"]["paired_reads_to_sorted_bam_in_memory"] = run("bam_sorted", paired=True)
+        result["rows"]["paired_reads_to_sorted_bam_in_memory_markdup"] = run("bam_sorted", markdup=True, paired=True)
+        nat.set_output("sam", 1)
+        import zlib
+        blob, recs, p = keep[0], [], 0
+        while p < len(blob):
+            bs = int.from_bytes(blob[p + 16:p + 18], "little") + 1
+            recs.append(zlib.decompress(blob[p:p + bs], 31)); p += bs
+        stream = b"".join(recs)
+        secs = []
+        for it in range(a.runs + 1):
+            torch.cuda.synchronize(); t1 = time.perf_counter()
+            _marked, counts = bam_markdup(stream)
+            if it:
+                secs.append(time.perf_counter() - t1)
+        row = stats(secs, counts["templates"], 1e6); row["unit"] = "Mtemplates/s (the entry point: the host's walk, both copies, heads, entries, decision, flags)"
+        row["templates"] = counts["templates"]; row["bytes"] = len(stream)
+        result["rows"]["bam_markdup_device"] = row
+        result["not_measured"] = "the flag kernel without the upload of its ordinals, spilled runs with marking, reads with base qualities (FASTA: every score is 0, ties go to the ordinal)"
+        os.remove(ppath)
+        os.remove(path); os.rmdir(tmp)
+        out = a.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bam_markdup.json")
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+        print(json.dumps(result))
+        return
     result["rows"]["reads_to_bam_unsorted"] = run("bam", keep=keep)
     result["rows"]["reads_to_sorted_bam_in_memory"] = run("bam_sorted")
     result["rows"]["reads_to_sorted_bam_spilled"] = run("bam_sorted", spill=True)
