@@ -27,7 +27,9 @@
 #include <string>
 #include <thread>
 #include <vector>
+#define BMH_CK_PREFIX "bmh_aligner_run: "
 #include "bmh_internal.h"
+#include "devmem.h"
 #include "pair_kernels.h"
 #include "bam_ws.h"
 #include "bam_sort.h"
@@ -80,28 +82,9 @@ namespace {
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// device (dbuf_t) / pinned host (hbuf_t) buffers that only ever grow
-template <class T, bool PINNED> struct gbuf_t {
-	T *p = nullptr; size_t cap = 0;
-	gbuf_t() = default;
-	gbuf_t(const gbuf_t &) = delete;
-	gbuf_t &operator=(const gbuf_t &) = delete;
-	void swap(gbuf_t &o) { T *q = p; p = o.p; o.p = q; const size_t c = cap; cap = o.cap; o.cap = c; }
-	void drop() { if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
-	int need(size_t n) {
-		if (n <= cap) return BMH_OK;
-		drop();
-		const size_t c = n + n / 4 + 1024;
-		if ((PINNED ? hipHostMalloc((void **)&p, c * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p, c * sizeof(T))) != hipSuccess) {
-			bmh_set_error("bmh_aligner_run: %zu bytes of %s memory: %s", c * sizeof(T), PINNED ? "pinned" : "device", hipGetErrorString(hipGetLastError())); return BMH_ENOMEM;
-		}
-		cap = c;
-		return BMH_OK;
-	}
-	~gbuf_t() { drop(); }
-};
-template <class T> using dbuf_t = gbuf_t<T, false>;
-template <class T> using hbuf_t = gbuf_t<T, true>;
+// device (dbuf_t) / pinned host (hbuf_t) buffers that only ever grow (csrc/devmem.h)
+template <class T> using dbuf_t = dev_buf<T>;
+template <class T> using hbuf_t = pin_buf<T>;
 
 // What the writer needs of a finished batch.  The large arrays are PINNED buffers the device copies straight into; a result goes back
 // to a pool when its text is written, so the buffers are allocated a few times per run, not per batch (a million reads leave 70 MB
@@ -156,9 +139,6 @@ struct lane_t {
 	}
 };
 
-#define LCK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("bmh_aligner_run: %s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
-#define RCK(x) do { const int rc_ = (x); if (rc_ != BMH_OK) return rc_; } while (0)
-
 // pageable -> pinned on a few threads (one thread copies 15 GB/s: the letters of a million reads were 10 ms of a lane's batch)
 void par_memcpy(void *dst, const void *src, size_t n, int n_threads)
 {
@@ -211,10 +191,10 @@ int cigars(const aligner_t &A, lane_t &Ln, const int32_t *d_fin, uint64_t n_sel,
 	*words_out = (uint64_t)words;
 	if (!to_host) return BMH_OK;
 	RCK(R.packed.need((size_t)words + 1));
-	LCK(hipMemcpyAsync(R.aln.p, Ln.d_aln.p, 32 * n_sel, hipMemcpyDeviceToHost, Ln.st));
-	LCK(hipMemcpyAsync(R.off.p, Ln.d_off.p, 4 * (n_sel + 1), hipMemcpyDeviceToHost, Ln.st));
-	if (words) LCK(hipMemcpyAsync(R.packed.p, Ln.d_packed.p, 4 * (size_t)words, hipMemcpyDeviceToHost, Ln.st));
-	LCK(hipStreamSynchronize(Ln.st));
+	HIPCK(hipMemcpyAsync(R.aln.p, Ln.d_aln.p, 32 * n_sel, hipMemcpyDeviceToHost, Ln.st));
+	HIPCK(hipMemcpyAsync(R.off.p, Ln.d_off.p, 4 * (n_sel + 1), hipMemcpyDeviceToHost, Ln.st));
+	if (words) HIPCK(hipMemcpyAsync(R.packed.p, Ln.d_packed.p, 4 * (size_t)words, hipMemcpyDeviceToHost, Ln.st));
+	HIPCK(hipStreamSynchronize(Ln.st));
 	for (uint64_t k = 0; k < n_sel; ++k)
 		if (R.aln.p[8 * k + 7] & ~2) { bmh_set_error("bmh_aligner_run: bmh_cigar_batch flagged an alignment (CIGAR or MD longer than the buffers)"); return BMH_ECAPACITY; }
 	return BMH_OK;
@@ -232,9 +212,9 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 {
 	if (!Ln.ctg_up) {                                              // the sequences' names and offsets, once per lane
 		RCK(Ln.d_ctg_names.need(A.ctg_blob.size())); RCK(Ln.d_ctg_name_off.need(A.ctg_noff.size())); RCK(Ln.d_ctg_off.need(A.off.size()));
-		LCK(hipMemcpy(Ln.d_ctg_names.p, A.ctg_blob.data(), A.ctg_blob.size(), hipMemcpyHostToDevice));
-		LCK(hipMemcpy(Ln.d_ctg_name_off.p, A.ctg_noff.data(), 4 * A.ctg_noff.size(), hipMemcpyHostToDevice));
-		LCK(hipMemcpy(Ln.d_ctg_off.p, A.off.data(), 8 * A.off.size(), hipMemcpyHostToDevice));
+		HIPCK(hipMemcpy(Ln.d_ctg_names.p, A.ctg_blob.data(), A.ctg_blob.size(), hipMemcpyHostToDevice));
+		HIPCK(hipMemcpy(Ln.d_ctg_name_off.p, A.ctg_noff.data(), 4 * A.ctg_noff.size(), hipMemcpyHostToDevice));
+		HIPCK(hipMemcpy(Ln.d_ctg_off.p, A.off.data(), 8 * A.off.size(), hipMemcpyHostToDevice));
 		Ln.ctg_up = true;
 	}
 	bmh_sam_dev_t d;
@@ -276,22 +256,22 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 			}
 			RCK(bsr_sort_run_device(Ln.bsr, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &ds, &dk, &dso, d_tpl, &d_stpl));
 			RCK(R.text.need((size_t)bo.bam_bytes + 1)); RCK(R.skeys.need((size_t)nrec + 1)); RCK(R.soff.need((size_t)nrec + 2));
-			LCK(hipEventRecord(Ln.ev_c[2], Ln.st));
-			if (bo.bam_bytes) LCK(hipMemcpyAsync(R.text.p, ds, (size_t)bo.bam_bytes, hipMemcpyDeviceToHost, Ln.st));
-			if (nrec) LCK(hipMemcpyAsync(R.skeys.p, dk, 8 * (size_t)nrec, hipMemcpyDeviceToHost, Ln.st));
-			LCK(hipMemcpyAsync(R.soff.p, dso, 8 * ((size_t)nrec + 1), hipMemcpyDeviceToHost, Ln.st));
+			HIPCK(hipEventRecord(Ln.ev_c[2], Ln.st));
+			if (bo.bam_bytes) HIPCK(hipMemcpyAsync(R.text.p, ds, (size_t)bo.bam_bytes, hipMemcpyDeviceToHost, Ln.st));
+			if (nrec) HIPCK(hipMemcpyAsync(R.skeys.p, dk, 8 * (size_t)nrec, hipMemcpyDeviceToHost, Ln.st));
+			HIPCK(hipMemcpyAsync(R.soff.p, dso, 8 * ((size_t)nrec + 1), hipMemcpyDeviceToHost, Ln.st));
 			R.dup_d2h = 0;
 			if (A.markdup) {                                          // (the count comes down with them and is checked below)
 				const size_t ne = std::min(nrec, tmax);
-				if (nrec) LCK(hipMemcpyAsync(R.stpl.p, d_stpl, 4 * (size_t)nrec, hipMemcpyDeviceToHost, Ln.st));
-				if (ne) LCK(hipMemcpyAsync(R.dup_e.p, d_e, sizeof(bdp_entry_t) * ne, hipMemcpyDeviceToHost, Ln.st));
-				LCK(hipMemcpyAsync(R.dup_info, d_info, 16, hipMemcpyDeviceToHost, Ln.st));
+				if (nrec) HIPCK(hipMemcpyAsync(R.stpl.p, d_stpl, 4 * (size_t)nrec, hipMemcpyDeviceToHost, Ln.st));
+				if (ne) HIPCK(hipMemcpyAsync(R.dup_e.p, d_e, sizeof(bdp_entry_t) * ne, hipMemcpyDeviceToHost, Ln.st));
+				HIPCK(hipMemcpyAsync(R.dup_info, d_info, 16, hipMemcpyDeviceToHost, Ln.st));
 				R.dup_d2h = 4ull * nrec + sizeof(bdp_entry_t) * ne + 16;
 				Ln.copy_bytes[1] += R.dup_d2h;
 			}
-			LCK(hipEventRecord(Ln.ev_c[3], Ln.st));
+			HIPCK(hipEventRecord(Ln.ev_c[3], Ln.st));
 			Ln.copy_bytes[1] += bo.bam_bytes + 16ull * nrec; Ln.d2h_marked = true;
-			LCK(hipStreamSynchronize(Ln.st));
+			HIPCK(hipStreamSynchronize(Ln.st));
 			if (A.markdup && nrec) {
 				if (R.dup_info[1] != 0xffffffffu) return bdp_batch_refused(nrec, R.dup_info[1] ? R.dup_info[1] : nrec + 1, "sorted BAM");
 				if (R.dup_info[0] == 0 || R.dup_info[0] > std::min(nrec, tmax)) { bmh_set_error("sorted BAM: internal error: %u templates among %u records", R.dup_info[0], nrec); return BMH_EINVAL; }
@@ -307,19 +287,19 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 		RCK(bmh_bgzf_deflate_device(Ln.bam, bo.d_bam, bo.bam_bytes, A.out_level, Ln.st, &d_members, &mb));
 		RCK(R.text.need((size_t)mb + 1));
 		if (mb) {
-			LCK(hipEventRecord(Ln.ev_c[2], Ln.st));
-			LCK(hipMemcpyAsync(R.text.p, d_members, (size_t)mb, hipMemcpyDeviceToHost, Ln.st));
-			LCK(hipEventRecord(Ln.ev_c[3], Ln.st));
+			HIPCK(hipEventRecord(Ln.ev_c[2], Ln.st));
+			HIPCK(hipMemcpyAsync(R.text.p, d_members, (size_t)mb, hipMemcpyDeviceToHost, Ln.st));
+			HIPCK(hipEventRecord(Ln.ev_c[3], Ln.st));
 			Ln.copy_bytes[1] += mb; Ln.d2h_marked = true;
 		}
-		LCK(hipStreamSynchronize(Ln.st));
+		HIPCK(hipStreamSynchronize(Ln.st));
 		R.text_len = mb;
 		return BMH_OK;
 	}
 	if (total) {
-		LCK(hipEventRecord(Ln.ev_c[2], Ln.st));
-		LCK(hipMemcpyAsync(R.text.p, Ln.d_text.p, (size_t)total, hipMemcpyDeviceToHost, Ln.st));
-		LCK(hipEventRecord(Ln.ev_c[3], Ln.st));
+		HIPCK(hipEventRecord(Ln.ev_c[2], Ln.st));
+		HIPCK(hipMemcpyAsync(R.text.p, Ln.d_text.p, (size_t)total, hipMemcpyDeviceToHost, Ln.st));
+		HIPCK(hipEventRecord(Ln.ev_c[3], Ln.st));
 		Ln.copy_bytes[1] += (uint64_t)total; Ln.d2h_marked = true;
 	}
 	RCK(bmh_sam_text_check(Ln.d_work.p, n, Ln.st));
@@ -337,10 +317,10 @@ int patch_alt_reads(const aligner_t &A, lane_t &Ln, const bmh_dev_jobs_t &dj, co
 	const bool tr = getenv("BMH_ALIGNER_TRACE") != nullptr;
 	const double ta = now_s();
 	RCK(Ln.h_regs.need(8 * (nr + 1))); RCK(Ln.h_rpr.need(n + 1)); RCK(Ln.h_fr.need(n + 1));
-	if (nr) LCK(hipMemcpyAsync(Ln.h_regs.p, Ln.d_regs.p, 32 * (size_t)nr, hipMemcpyDeviceToHost, Ln.st));
-	LCK(hipMemcpyAsync(Ln.h_rpr.p, dj.d_regs_per_read, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
-	LCK(hipMemcpyAsync(Ln.h_fr.p, dj.d_frac_rep, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
-	LCK(hipStreamSynchronize(Ln.st));
+	if (nr) HIPCK(hipMemcpyAsync(Ln.h_regs.p, Ln.d_regs.p, 32 * (size_t)nr, hipMemcpyDeviceToHost, Ln.st));
+	HIPCK(hipMemcpyAsync(Ln.h_rpr.p, dj.d_regs_per_read, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
+	HIPCK(hipMemcpyAsync(Ln.h_fr.p, dj.d_frac_rep, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
+	HIPCK(hipStreamSynchronize(Ln.st));
 	const double tb = now_s();
 	std::vector<uint64_t> rec_off((size_t)n + 1, 0), reg_off((size_t)n + 1, 0);
 	for (uint32_t r = 0; r < n; ++r) { rec_off[r + 1] = rec_off[r] + R.opr.p[r]; reg_off[r + 1] = reg_off[r] + Ln.h_rpr.p[r]; }
@@ -398,11 +378,11 @@ int patch_alt_reads(const aligner_t &A, lane_t &Ln, const bmh_dev_jobs_t &dj, co
 	// the redone records take their places in the device's array too (a read keeps its number of records: mem_sort_dedup_patch does not look at the table), after every
 	// record of the batch has become an ALT-mode record ([11] = secondary_all)
 	RCK(Ln.d_alt_ids.need(ns)); RCK(Ln.d_alt_off.need((size_t)ns + 1)); RCK(Ln.d_alt_sub.need(16 * ((size_t)ms + 1)));
-	LCK(hipMemcpyAsync(Ln.d_alt_ids.p, ids.data(), 4 * (size_t)ns, hipMemcpyHostToDevice, Ln.st));
-	LCK(hipMemcpyAsync(Ln.d_alt_off.p, sub_off.data(), 4 * ((size_t)ns + 1), hipMemcpyHostToDevice, Ln.st));
-	if (ms) LCK(hipMemcpyAsync(Ln.d_alt_sub.p, sub_out.data(), 64 * (size_t)ms, hipMemcpyHostToDevice, Ln.st));
+	HIPCK(hipMemcpyAsync(Ln.d_alt_ids.p, ids.data(), 4 * (size_t)ns, hipMemcpyHostToDevice, Ln.st));
+	HIPCK(hipMemcpyAsync(Ln.d_alt_off.p, sub_off.data(), 4 * ((size_t)ns + 1), hipMemcpyHostToDevice, Ln.st));
+	if (ms) HIPCK(hipMemcpyAsync(Ln.d_alt_sub.p, sub_out.data(), 64 * (size_t)ms, hipMemcpyHostToDevice, Ln.st));
 	RCK(bmh_alt_records_device(Ln.d_fin.p, m, Ln.d_roff.p, Ln.d_alt_ids.p, Ln.d_alt_off.p, Ln.d_alt_sub.p, ns, Ln.st));
-	LCK(hipStreamSynchronize(Ln.st));                              // (ids, sub_off, sub_out are locals)
+	HIPCK(hipStreamSynchronize(Ln.st));                              // (ids, sub_off, sub_out are locals)
 	if (tr) fprintf(stderr, "[aligner] ALT contigs: host tail of those reads and their way back %.1f ms\n", (now_s() - tc) * 1e3);
 	return BMH_OK;
 }
@@ -419,13 +399,13 @@ int pd_after_pestat(void *u_, const double *pes)
 	lane_t &Ln = *u.Ln; const aligner_t &A = *u.A;
 	RCK(bmh_pair_device(&A.co, &A.ep, u.po, &A.pe, pes, A.l_pac, A.n_contigs, u.ex->d_ctg_off, u.ex->d_logtab, u.ex->n_log, Ln.d_fin.p, Ln.d_opr.p, Ln.d_roff.p,
 	                    u.dj->d_frac_rep, u.n, Ln.d_hrec.p, Ln.d_unflag.p, Ln.d_todo.p, Ln.st));
-	LCK(hipMemcpyAsync(Ln.h_todo.p, Ln.d_todo.p, u.n / 2, hipMemcpyDeviceToHost, Ln.st));
+	HIPCK(hipMemcpyAsync(Ln.h_todo.p, Ln.d_todo.p, u.n / 2, hipMemcpyDeviceToHost, Ln.st));
 	return BMH_OK;
 }
 int pd_before_final(void *u_, const uint8_t **extra)
 {
 	pd_user_t &u = *(pd_user_t *)u_;
-	LCK(hipStreamSynchronize(u.Ln->st));
+	HIPCK(hipStreamSynchronize(u.Ln->st));
 	*extra = u.Ln->h_todo.p;
 	return BMH_OK;
 }
@@ -442,10 +422,10 @@ int pairs_on_device(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, co
 	                                               A.n_contigs, A.n_contigs > 1 ? A.off.data() : nullptr, Ln.d_fin.p, Ln.d_opr.p, Ln.st, &ex);
 	if (m1 < 0) return (int)m1;
 	RCK(Ln.h_regs.need(16 * ((size_t)m1 + 1))); RCK(Ln.h_rpr.need(n + 1)); RCK(Ln.h_fr.need(n + 1));
-	if (m1) LCK(hipMemcpyAsync(Ln.h_regs.p, Ln.d_dedup.p, 64 * (size_t)m1, hipMemcpyDeviceToHost, Ln.st));
-	LCK(hipMemcpyAsync(Ln.h_rpr.p, Ln.d_opr.p, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
-	LCK(hipMemcpyAsync(Ln.h_fr.p, dj.d_frac_rep, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
-	LCK(hipStreamSynchronize(Ln.st));
+	if (m1) HIPCK(hipMemcpyAsync(Ln.h_regs.p, Ln.d_dedup.p, 64 * (size_t)m1, hipMemcpyDeviceToHost, Ln.st));
+	HIPCK(hipMemcpyAsync(Ln.h_rpr.p, Ln.d_opr.p, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
+	HIPCK(hipMemcpyAsync(Ln.h_fr.p, dj.d_frac_rep, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
+	HIPCK(hipStreamSynchronize(Ln.st));
 	const double t1 = now_s();
 	// the host: statistics, the rescue's windows (aligned on the device), the pairs that are the host's
 	pd_user_t u = {&A, &Ln, &dj, &po, &ex, n};
@@ -478,21 +458,21 @@ int pairs_on_device(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, co
 	RCK(Ln.d_todo_pairs.need(nt + 1)); RCK(Ln.d_oprh.need(2 * (size_t)nt + 1)); RCK(Ln.d_offh.need(2 * (size_t)nt + 1)); RCK(Ln.d_hh.need(2 * (size_t)nt + 1)); RCK(Ln.d_ufh.need(2 * (size_t)nt + 1));
 	RCK(Ln.d_finh.need(16 * ((size_t)mh + 1))); RCK(Ln.d_rslot.need(n + 1)); RCK(Ln.d_opr2.need(n + 1)); RCK(Ln.d_hrec2.need(n + 1)); RCK(Ln.d_unflag2.need(n + 1)); RCK(Ln.d_roff2.need(n + 1));
 	if (nt) {
-		LCK(hipMemcpyAsync(Ln.d_todo_pairs.p, Ln.todo_pairs.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, Ln.st));
-		LCK(hipMemcpyAsync(Ln.d_oprh.p, R.opr.p, 8 * (size_t)nt, hipMemcpyHostToDevice, Ln.st));
-		LCK(hipMemcpyAsync(Ln.d_offh.p, Ln.offh.data(), 8 * (size_t)nt, hipMemcpyHostToDevice, Ln.st));
-		LCK(hipMemcpyAsync(Ln.d_hh.p, R.h_rec.data(), 8 * (size_t)nt, hipMemcpyHostToDevice, Ln.st));
-		LCK(hipMemcpyAsync(Ln.d_ufh.p, R.unflag.data(), 8 * (size_t)nt, hipMemcpyHostToDevice, Ln.st));
-		if (mh) LCK(hipMemcpyAsync(Ln.d_finh.p, R.fin.p, 64 * (size_t)mh, hipMemcpyHostToDevice, Ln.st));
+		HIPCK(hipMemcpyAsync(Ln.d_todo_pairs.p, Ln.todo_pairs.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, Ln.st));
+		HIPCK(hipMemcpyAsync(Ln.d_oprh.p, R.opr.p, 8 * (size_t)nt, hipMemcpyHostToDevice, Ln.st));
+		HIPCK(hipMemcpyAsync(Ln.d_offh.p, Ln.offh.data(), 8 * (size_t)nt, hipMemcpyHostToDevice, Ln.st));
+		HIPCK(hipMemcpyAsync(Ln.d_hh.p, R.h_rec.data(), 8 * (size_t)nt, hipMemcpyHostToDevice, Ln.st));
+		HIPCK(hipMemcpyAsync(Ln.d_ufh.p, R.unflag.data(), 8 * (size_t)nt, hipMemcpyHostToDevice, Ln.st));
+		if (mh) HIPCK(hipMemcpyAsync(Ln.d_finh.p, R.fin.p, 64 * (size_t)mh, hipMemcpyHostToDevice, Ln.st));
 	}
 	RCK(bmh_pair_merge_counts(n, Ln.d_todo_pairs.p, nt, Ln.d_rslot.p, Ln.d_opr.p, Ln.d_hrec.p, Ln.d_unflag.p, Ln.d_oprh.p, Ln.d_hh.p, Ln.d_ufh.p, Ln.d_opr2.p, Ln.d_hrec2.p, Ln.d_unflag2.p, Ln.st));
 	const size_t sb = bmh_pair_scan_bytes(n);
 	RCK(Ln.d_scan.need(sb));
 	RCK(bmh_pair_scan(Ln.d_opr2.p, Ln.d_roff2.p, n, Ln.d_scan.p, Ln.d_scan.cap, Ln.st));
 	uint32_t last[2] = {0, 0};
-	LCK(hipMemcpyAsync(&last[0], Ln.d_roff2.p + (n - 1), 4, hipMemcpyDeviceToHost, Ln.st));
-	LCK(hipMemcpyAsync(&last[1], Ln.d_opr2.p + (n - 1), 4, hipMemcpyDeviceToHost, Ln.st));
-	LCK(hipStreamSynchronize(Ln.st));
+	HIPCK(hipMemcpyAsync(&last[0], Ln.d_roff2.p + (n - 1), 4, hipMemcpyDeviceToHost, Ln.st));
+	HIPCK(hipMemcpyAsync(&last[1], Ln.d_opr2.p + (n - 1), 4, hipMemcpyDeviceToHost, Ln.st));
+	HIPCK(hipStreamSynchronize(Ln.st));
 	const uint64_t m = (uint64_t)last[0] + last[1];
 	RCK(Ln.d_fin2.need(16 * (m + 1)));
 	RCK(bmh_pair_merge_records(n, Ln.d_rslot.p, Ln.d_fin.p, Ln.d_roff.p, Ln.d_finh.p, Ln.d_offh.p, Ln.d_opr2.p, Ln.d_roff2.p, Ln.d_fin2.p, Ln.st));
@@ -540,16 +520,16 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 	RCK(Ln.d_reads.need(nb + 16)); RCK(Ln.d_offs.need(n + 1)); RCK(Ln.d_lens.need(n + 1)); RCK(Ln.h_offs.need(n + 1));
 	Ln.max_read_len = 0;
 	for (uint32_t r = 0; r < n; ++r) { Ln.h_offs.p[r] = (uint32_t)(rs.offs[b0 + r] - a0); if (rs.lens[b0 + r] > Ln.max_read_len) Ln.max_read_len = rs.lens[b0 + r]; }
-	for (hipEvent_t &e : Ln.ev_c) if (!e) LCK(hipEventCreate(&e));
+	for (hipEvent_t &e : Ln.ev_c) if (!e) HIPCK(hipEventCreate(&e));
 	Ln.d2h_marked = false;
 	uint64_t h2d_bytes = nb + 8 * (uint64_t)n;
 	if (!src_pinned) RCK(Ln.h_reads.need(nb + 16));
 	if (!src_pinned) par_memcpy(Ln.h_reads.p, rs.ascii + a0, nb, n_threads);       // (pageable -> pinned by this lane's threads, then one DMA: the lanes stage side by side)
-	LCK(hipEventRecord(Ln.ev_c[0], Ln.st));
-	if (src_pinned) LCK(hipMemcpyAsync(Ln.d_reads.p, rs.ascii + a0, nb, hipMemcpyHostToDevice, Ln.st));       // (pinned or registered host memory -- a batch of a read file filled by the loader, a caller's registered buffer: no staging copy)
-	else LCK(hipMemcpyAsync(Ln.d_reads.p, Ln.h_reads.p, nb, hipMemcpyHostToDevice, Ln.st));
-	LCK(hipMemcpyAsync(Ln.d_offs.p, Ln.h_offs.p, 4 * (size_t)n, hipMemcpyHostToDevice, Ln.st));
-	LCK(hipMemcpyAsync(Ln.d_lens.p, rs.lens + b0, 4 * (size_t)n, hipMemcpyHostToDevice, Ln.st));
+	HIPCK(hipEventRecord(Ln.ev_c[0], Ln.st));
+	if (src_pinned) HIPCK(hipMemcpyAsync(Ln.d_reads.p, rs.ascii + a0, nb, hipMemcpyHostToDevice, Ln.st));       // (pinned or registered host memory -- a batch of a read file filled by the loader, a caller's registered buffer: no staging copy)
+	else HIPCK(hipMemcpyAsync(Ln.d_reads.p, Ln.h_reads.p, nb, hipMemcpyHostToDevice, Ln.st));
+	HIPCK(hipMemcpyAsync(Ln.d_offs.p, Ln.h_offs.p, 4 * (size_t)n, hipMemcpyHostToDevice, Ln.st));
+	HIPCK(hipMemcpyAsync(Ln.d_lens.p, rs.lens + b0, 4 * (size_t)n, hipMemcpyHostToDevice, Ln.st));
 	// the text is written on the device (bmh_sam_text_*): the names go along
 	const bool host_format = getenv("BMH_ALIGNER_HOST_FORMAT") != nullptr;          // (A/B and cross-check: records to the host, text by bmh_format_sam)
 	const bool host_select = getenv("BMH_ALIGNER_HOST_SELECT") != nullptr;          // (A/B and cross-check: the host's selection for every batch; implies the host's text)
@@ -562,8 +542,8 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 		memcpy(hb.p, (const char *)blob + c0, c1 - c0);
 		for (uint32_t r = 0; r < n; ++r) ho.p[r] = off[b0 + r] - c0;
 		ho.p[n] = c1 - c0;
-		LCK(hipMemcpyAsync(db.p, hb.p, c1 - c0, hipMemcpyHostToDevice, Ln.st));
-		LCK(hipMemcpyAsync(dof.p, ho.p, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, Ln.st));
+		HIPCK(hipMemcpyAsync(db.p, hb.p, c1 - c0, hipMemcpyHostToDevice, Ln.st));
+		HIPCK(hipMemcpyAsync(dof.p, ho.p, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, Ln.st));
 		h2d_bytes += (c1 - c0) + 8 * ((uint64_t)n + 1);
 		return BMH_OK;
 	};
@@ -573,16 +553,16 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 	Ln.has_comments = text_dev && A.po.copy_comment && rs.comments != nullptr && rs.comment_offs != nullptr;
 	if (Ln.has_quals) {
 		RCK(Ln.d_quals.need(nb + 16));
-		if (src_pinned) LCK(hipMemcpyAsync(Ln.d_quals.p, rs.quals + a0, nb, hipMemcpyHostToDevice, Ln.st));
+		if (src_pinned) HIPCK(hipMemcpyAsync(Ln.d_quals.p, rs.quals + a0, nb, hipMemcpyHostToDevice, Ln.st));
 		else {
 			RCK(Ln.h_quals.need(nb + 16));
 			par_memcpy(Ln.h_quals.p, rs.quals + a0, nb, n_threads);
-			LCK(hipMemcpyAsync(Ln.d_quals.p, Ln.h_quals.p, nb, hipMemcpyHostToDevice, Ln.st));
+			HIPCK(hipMemcpyAsync(Ln.d_quals.p, Ln.h_quals.p, nb, hipMemcpyHostToDevice, Ln.st));
 		}
 		h2d_bytes += nb;
 	}
 	if (Ln.has_comments) RCK(send_blob(rs.comments, rs.comment_offs, rs.n_comment_bytes, Ln.h_comments, Ln.h_comment_off, Ln.d_comments, Ln.d_comment_off));
-	LCK(hipEventRecord(Ln.ev_c[1], Ln.st));
+	HIPCK(hipEventRecord(Ln.ev_c[1], Ln.st));
 	Ln.copy_bytes[0] += h2d_bytes;
 	// ---- seeding
 	if (!Ln.sws || n > Ln.sws_reads || nb > Ln.sws_bases) {
@@ -640,8 +620,8 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 	// highest priority: beside the other lanes' extension kernels, whose waves fill the register files, these are the kernels that should get the slots that
 	// become free.  The host waits for the lane's stream first (see bmh_seed_batch: no barrier packet waits in a high-priority queue).
 	struct swap_back_t { lane_t &L; bool on; ~swap_back_t() { if (on) std::swap(L.st, L.st_hi); } } sb{Ln, false};
-	if (Ln.st_hi) { LCK(hipStreamSynchronize(Ln.st)); std::swap(Ln.st, Ln.st_hi); sb.on = true; }
-	else if (gate.held) LCK(hipStreamSynchronize(Ln.st));
+	if (Ln.st_hi) { HIPCK(hipStreamSynchronize(Ln.st)); std::swap(Ln.st, Ln.st_hi); sb.on = true; }
+	else if (gate.held) HIPCK(hipStreamSynchronize(Ln.st));
 	gate.release();
 	double t3 = now_s(); Ln.t[2] += t3 - t2;
 	bmh_post_opt_t po = A.po; po.id0 = id0;
@@ -669,12 +649,12 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 				// (the stream is idle: the records go home on the second stream while the selection and the CIGAR kernels run on the first)
 				if (!text_dev || alt_patch) {                        // (the host looks the records through for hits on ALT contigs)
 					RCK(R.fin.need(16 * (size_t)m + 16)); RCK(R.opr.need(n + 1));
-					if (m) LCK(hipMemcpyAsync(R.fin.p, Ln.d_fin.p, 64 * (size_t)m, hipMemcpyDeviceToHost, Ln.st2));
-					LCK(hipMemcpyAsync(R.opr.p, Ln.d_opr.p, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st2));
+					if (m) HIPCK(hipMemcpyAsync(R.fin.p, Ln.d_fin.p, 64 * (size_t)m, hipMemcpyDeviceToHost, Ln.st2));
+					HIPCK(hipMemcpyAsync(R.opr.p, Ln.d_opr.p, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st2));
 				}
 				d_fin = Ln.d_fin.p;
 				if (alt_patch) {
-					LCK(hipStreamSynchronize(Ln.st2));
+					HIPCK(hipStreamSynchronize(Ln.st2));
 					RCK(patch_alt_reads(A, Ln, dj, po, codes, host_offs(), n, nr, (uint64_t)m, n_threads, R));
 				}
 			}
@@ -682,17 +662,17 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 		if (m < 0) {                                                // the host tail: a read beyond the device tail's fixed limits
 			++Ln.host_tail;
 			RCK(Ln.h_regs.need(8 * (nr + 1))); RCK(Ln.h_rpr.need(n + 1)); RCK(Ln.h_fr.need(n + 1));
-			if (nr) LCK(hipMemcpyAsync(Ln.h_regs.p, Ln.d_regs.p, 32 * (size_t)nr, hipMemcpyDeviceToHost, Ln.st));
-			LCK(hipMemcpyAsync(Ln.h_rpr.p, dj.d_regs_per_read, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
-			LCK(hipMemcpyAsync(Ln.h_fr.p, dj.d_frac_rep, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
-			LCK(hipStreamSynchronize(Ln.st));
+			if (nr) HIPCK(hipMemcpyAsync(Ln.h_regs.p, Ln.d_regs.p, 32 * (size_t)nr, hipMemcpyDeviceToHost, Ln.st));
+			HIPCK(hipMemcpyAsync(Ln.h_rpr.p, dj.d_regs_per_read, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
+			HIPCK(hipMemcpyAsync(Ln.h_fr.p, dj.d_frac_rep, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
+			HIPCK(hipStreamSynchronize(Ln.st));
 			RCK(R.fin.need(16 * (size_t)(nr + 1))); RCK(R.opr.need(n + 1));
 			m = bmh_finalize_regs(&A.co, &A.ep, &po, A.l_pac, A.pac, n, codes, host_offs(), Ln.h_regs.p, Ln.h_rpr.p, Ln.h_fr.p, A.n_contigs,
 			                      A.n_contigs > 1 ? A.off.data() : nullptr, R.fin.p, R.opr.p, n_threads);
 			if (m < 0) return (int)m;
 			RCK(Ln.d_fin.need(16 * ((size_t)m + 1))); RCK(Ln.d_opr.need(n + 1));
-			if (m) LCK(hipMemcpyAsync(Ln.d_fin.p, R.fin.p, 64 * (size_t)m, hipMemcpyHostToDevice, Ln.st));
-			LCK(hipMemcpyAsync(Ln.d_opr.p, R.opr.p, 4 * (size_t)n, hipMemcpyHostToDevice, Ln.st));
+			if (m) HIPCK(hipMemcpyAsync(Ln.d_fin.p, R.fin.p, 64 * (size_t)m, hipMemcpyHostToDevice, Ln.st));
+			HIPCK(hipMemcpyAsync(Ln.d_opr.p, R.opr.p, 4 * (size_t)n, hipMemcpyHostToDevice, Ln.st));
 			d_fin = Ln.d_fin.p;
 		}
 		R.m = (uint64_t)m;
@@ -717,10 +697,10 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 		const bool deduped = md >= 0;
 		const uint64_t n_in = deduped ? (uint64_t)md : nr;
 		RCK(Ln.h_regs.need((deduped ? 16 : 8) * (n_in + 1))); RCK(Ln.h_rpr.need(n + 1)); RCK(Ln.h_fr.need(n + 1));
-		if (n_in) LCK(hipMemcpyAsync(Ln.h_regs.p, deduped ? Ln.d_fin.p : Ln.d_regs.p, (deduped ? 64 : 32) * (size_t)n_in, hipMemcpyDeviceToHost, Ln.st));
-		LCK(hipMemcpyAsync(Ln.h_rpr.p, deduped ? Ln.d_opr.p : dj.d_regs_per_read, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
-		LCK(hipMemcpyAsync(Ln.h_fr.p, dj.d_frac_rep, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
-		LCK(hipStreamSynchronize(Ln.st));
+		if (n_in) HIPCK(hipMemcpyAsync(Ln.h_regs.p, deduped ? Ln.d_fin.p : Ln.d_regs.p, (deduped ? 64 : 32) * (size_t)n_in, hipMemcpyDeviceToHost, Ln.st));
+		HIPCK(hipMemcpyAsync(Ln.h_rpr.p, deduped ? Ln.d_opr.p : dj.d_regs_per_read, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
+		HIPCK(hipMemcpyAsync(Ln.h_fr.p, dj.d_frac_rep, 4 * (size_t)n, hipMemcpyDeviceToHost, Ln.st));
+		HIPCK(hipStreamSynchronize(Ln.st));
 		if (getenv("BMH_PAIR_PROFILE")) fprintf(stderr, "[pairs] regions on the host after %.1f ms of the tail\n", (now_s() - t3) * 1e3);
 		uint64_t cap = n_in + 2ull * n + 1024;                      // mate rescue adds a few regions per pair
 		int64_t m = BMH_ECAPACITY;
@@ -735,10 +715,10 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 		if (getenv("BMH_PAIR_PROFILE")) fprintf(stderr, "[pairs] bmh_finalize_pairs_dev back after %.1f ms of the tail\n", (now_s() - t3) * 1e3);
 		R.m = (uint64_t)m;
 		RCK(Ln.d_fin.need(16 * ((size_t)m + 1))); RCK(Ln.d_opr.need(n + 1)); RCK(Ln.d_hrec.need(n + 1));
-		if (m) LCK(hipMemcpyAsync(Ln.d_fin.p, R.fin.p, 64 * (size_t)m, hipMemcpyHostToDevice, Ln.st));
-		LCK(hipMemcpyAsync(Ln.d_opr.p, R.opr.p, 4 * (size_t)n, hipMemcpyHostToDevice, Ln.st));
-		LCK(hipMemcpyAsync(Ln.d_hrec.p, R.h_rec.data(), 4 * (size_t)n, hipMemcpyHostToDevice, Ln.st));
-		if (text_dev) { RCK(Ln.d_unflag.need(n + 1)); LCK(hipMemcpyAsync(Ln.d_unflag.p, R.unflag.data(), 4 * (size_t)n, hipMemcpyHostToDevice, Ln.st)); }
+		if (m) HIPCK(hipMemcpyAsync(Ln.d_fin.p, R.fin.p, 64 * (size_t)m, hipMemcpyHostToDevice, Ln.st));
+		HIPCK(hipMemcpyAsync(Ln.d_opr.p, R.opr.p, 4 * (size_t)n, hipMemcpyHostToDevice, Ln.st));
+		HIPCK(hipMemcpyAsync(Ln.d_hrec.p, R.h_rec.data(), 4 * (size_t)n, hipMemcpyHostToDevice, Ln.st));
+		if (text_dev) { RCK(Ln.d_unflag.need(n + 1)); HIPCK(hipMemcpyAsync(Ln.d_unflag.p, R.unflag.data(), 4 * (size_t)n, hipMemcpyHostToDevice, Ln.st)); }
 		d_fin = Ln.d_fin.p;
 		}
 	}
@@ -755,9 +735,9 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 		const int64_t k = bmh_sam_select_device(&po, d_fin, Ln.d_opr.p, paired ? Ln.d_hrec.p : nullptr, n, m, Ln.d_sel.p, Ln.d_slot.p, Ln.d_work.p, Ln.d_work.cap, Ln.st);
 		if (k < 0) return (int)k;
 		ns_sel = (uint64_t)k;
-		if (m && !text_dev) LCK(hipMemcpyAsync(R.slot32.p, Ln.d_slot.p, 4 * (size_t)m, hipMemcpyDeviceToHost, Ln.st2));
+		if (m && !text_dev) HIPCK(hipMemcpyAsync(R.slot32.p, Ln.d_slot.p, 4 * (size_t)m, hipMemcpyDeviceToHost, Ln.st2));
 	} else {
-		LCK(hipStreamSynchronize(Ln.st2));                          // (the records)
+		HIPCK(hipStreamSynchronize(Ln.st2));                          // (the records)
 		RCK(Ln.h_need.need(m + 1));
 		// (reads are independent: ranges of them on host threads -- 3 M records of a million reads were 11 ms on one)
 		std::vector<uint64_t> base((size_t)n + 1, 0);
@@ -776,15 +756,15 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 		for (int64_t v : part_rc) if (v < 0) return (int)v;
 		R.slot.assign(m ? m : 1, -1);
 		for (uint64_t k = 0; k < m; ++k) if (Ln.h_need.p[k]) { Ln.h_sel.p[ns_sel] = R.dev_index.empty() ? (uint32_t)k : R.dev_index[k]; R.slot[k] = (int64_t)ns_sel; ++ns_sel; }
-		if (ns_sel) LCK(hipMemcpyAsync(Ln.d_sel.p, Ln.h_sel.p, 4 * ns_sel, hipMemcpyHostToDevice, Ln.st));
+		if (ns_sel) HIPCK(hipMemcpyAsync(Ln.d_sel.p, Ln.h_sel.p, 4 * ns_sel, hipMemcpyHostToDevice, Ln.st));
 	}
 	double t5 = now_s(); Ln.t[4] += t5 - t4;
 	uint64_t words = 0;
 	const bool dev_text_now = text_dev && dev_select;
 	RCK(cigars(A, Ln, d_fin, ns_sel, R, !dev_text_now, &words));
 	if (dev_text_now) RCK(text_on_device(A, Ln, po, d_fin, n, paired, R));
-	LCK(hipStreamSynchronize(Ln.st2));
-	if (sb.on) LCK(hipStreamSynchronize(Ln.st));                   // (the priority stream is idle before the lane's own takes its place again)
+	HIPCK(hipStreamSynchronize(Ln.st2));
+	if (sb.on) HIPCK(hipStreamSynchronize(Ln.st));                   // (the priority stream is idle before the lane's own takes its place again)
 	{
 		float ms = 0.f;
 		if (hipEventSynchronize(Ln.ev_c[1]) == hipSuccess && hipEventElapsedTime(&ms, Ln.ev_c[0], Ln.ev_c[1]) == hipSuccess) Ln.copy_ms[0] += ms;

@@ -20,12 +20,9 @@
 #include "bam_sort.h"
 #include "bam_ws.h"
 
-#define HIPCK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
-#define RCK(x) do { const int rc_ = (x); if (rc_ != BMH_OK) return rc_; } while (0)
-
 struct bdp_dev_t {
-	bmh_grow_t head, tpl, start, entries, info, tmp;                        // per batch
-	bmh_grow_t bits, tord;                                                  // the bitmap of the run, a window's ordinals
+	dev_buf<uint8_t> head, tpl, start, entries, info, tmp;                        // per batch
+	dev_buf<uint8_t> bits, tord;                                                  // the bitmap of the run, a window's ordinals
 	uint64_t n_tpl = 0;                                                     // templates the bitmap covers
 };
 
@@ -187,10 +184,6 @@ __global__ void __launch_bounds__(256) bdp_flag(uint8_t *__restrict__ recs, cons
 	if (bits[t >> 5] >> (t & 31) & 1u) recs[o + 19] |= 0x04;
 }
 
-size_t sort_bytes(size_t n) { size_t t = 0; (void)rocprim::radix_sort_pairs(nullptr, t, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, n, 0, 64, 0); return t + 256; }
-size_t iscan_bytes(size_t n) { size_t t = 0; (void)rocprim::inclusive_scan(nullptr, t, (uint32_t *)nullptr, (uint32_t *)nullptr, n, rocprim::plus<uint32_t>(), 0); return t + 256; }
-size_t mscan_bytes(size_t n) { size_t t = 0; (void)rocprim::inclusive_scan(nullptr, t, (uint32_t *)nullptr, (uint32_t *)nullptr, n, rocprim::maximum<uint32_t>(), 0); return t + 256; }
-size_t escan_bytes(size_t n) { size_t t = 0; (void)rocprim::exclusive_scan(nullptr, t, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, n, rocprim::plus<uint32_t>(), 0); return t + 256; }
 unsigned blocks(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
 }   // namespace
@@ -201,7 +194,7 @@ void bdp_dev_free(bdp_dev_t *d) { delete d; }
 int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint32_t **d_tpl, const bdp_entry_t **d_entries, const uint32_t **d_info)
 {
 	hipStream_t st = (hipStream_t)stream;
-	size_t tb = iscan_bytes((size_t)n + 1);
+	size_t tb = scan_tmp_bytes<uint32_t, uint32_t, true>((size_t)n + 1);
 	RCK(d->head.need(4 * ((size_t)n + 1))); RCK(d->tpl.need(4 * ((size_t)n + 1))); RCK(d->start.need(4 * ((size_t)n + 2))); RCK(d->entries.need(sizeof(bdp_entry_t) * ((size_t)n + 1)));
 	RCK(d->info.need(16)); RCK(d->tmp.need(tb));
 	const uint32_t init[4] = {0u, 0xffffffffu, 0u, 0u};
@@ -228,13 +221,13 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 	if (T >= 1ull << 31) { bmh_set_error("duplicate marking: %llu templates: the decision takes fewer than 2^31", (unsigned long long)T); return BMH_EINVAL; }
 	// entries, two key and two value arrays of up to 2 T items (T templates in the pair pass), the item counts and their scan, the sorts' work space, the bitmap:
 	// 24 + 2 * (16 + 8) + 8 = 80 bytes per template and the work space -- freed before the final sort allocates its own
-	const size_t M = 2 * (size_t)T; size_t sb = sort_bytes(M); const size_t cb = std::max(std::max(escan_bytes((size_t)T + 1), mscan_bytes(M)), sb);
+	const size_t M = 2 * (size_t)T; size_t sb = sort_pairs_tmp_bytes<uint64_t, uint32_t>(M); const size_t cb = std::max(std::max(scan_tmp_bytes<uint32_t, uint32_t>((size_t)T + 1), max_scan_tmp_bytes<uint32_t>(M)), sb);
 	size_t fr = 0, tot = 0;
 	HIPCK(hipMemGetInfo(&fr, &tot));
 	// (a buffer is allocated a quarter larger than asked: that is what is counted)
 	const size_t ask = sizeof(bdp_entry_t) * (size_t)T + 2 * 8 * M + 2 * 4 * M + 2 * 4 * ((size_t)T + 1) + cb, want = ask + ask / 4 + (64u << 20);
 	// the final sort that follows: keys and ordinals in and out, 24 bytes per record, a quarter more as allocated, and its work space
-	const size_t sort_ask = 24 * (size_t)n_records + (n_records ? sort_bytes((size_t)n_records) : 0), sort_want = sort_ask + sort_ask / 4 + (64u << 20);
+	const size_t sort_ask = 24 * (size_t)n_records + (n_records ? sort_pairs_tmp_bytes<uint64_t, uint32_t>((size_t)n_records) : 0), sort_want = sort_ask + sort_ask / 4 + (64u << 20);
 	if (want <= fr && sort_want > fr) {
 		bmh_set_error("sorted BAM: the final sort of %llu records (%llu templates to mark duplicates among) needs %zu bytes of device memory, %zu are free (sort fewer reads per run, or on a device with more memory)",
 		              (unsigned long long)n_records, (unsigned long long)T, sort_want, fr);
@@ -246,7 +239,7 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 		return BMH_ENOMEM;
 	}
 	// (nine buffers allocated and freed per decision: it runs once per sorted file, and what it frees is what the final sort then takes)
-	bmh_grow_t E, k0, k1, v0, v1, cnt, base, tmp, dc;
+	dev_buf<uint8_t> E, k0, k1, v0, v1, cnt, base, tmp, dc;
 	RCK(E.need(sizeof(bdp_entry_t) * (size_t)T)); RCK(k0.need(8 * M)); RCK(k1.need(8 * M)); RCK(v0.need(4 * M)); RCK(v1.need(4 * M)); RCK(cnt.need(4 * ((size_t)T + 1)));
 	RCK(base.need(4 * ((size_t)T + 1))); RCK(tmp.need(cb)); RCK(dc.need(8 * 5));
 	HIPCK(hipMemcpyAsync(E.p, entries, sizeof(bdp_entry_t) * (size_t)T, hipMemcpyHostToDevice, st));
@@ -264,7 +257,7 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 	}
 	bdp_pair_decide<<<blocks(T), 256, 0, st>>>(dE, va, T, (uint32_t *)d->bits.p, dcnt);
 	// the fragment pass
-	size_t eb = escan_bytes((size_t)T + 1);
+	size_t eb = scan_tmp_bytes<uint32_t, uint32_t>((size_t)T + 1);
 	HIPCK(hipMemsetAsync((uint32_t *)cnt.p + T, 0, 4, st));
 	bdp_item_counts<<<blocks(T), 256, 0, st>>>(dE, T, (uint32_t *)cnt.p, dcnt);
 	HIPCK(rocprim::exclusive_scan(tmp.p, eb, (uint32_t *)cnt.p, (uint32_t *)base.p, 0u, (size_t)T + 1, rocprim::plus<uint32_t>(), st));
@@ -282,7 +275,7 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 		}
 		// kb: the sorted end words, va: the items in that order; vb is free: it takes the run heads' indices, whose max-scan goes into k0's bytes
 		uint32_t *hidx = vb, *first = (uint32_t *)k0.p;                   // (ka's bytes: the keys have been read)
-		size_t mb = mscan_bytes((size_t)m);
+		size_t mb = max_scan_tmp_bytes<uint32_t>((size_t)m);
 		bdp_run_heads<<<blocks(m), 256, 0, st>>>(kb, m, hidx);
 		HIPCK(rocprim::inclusive_scan(tmp.p, mb, hidx, first, (size_t)m, rocprim::maximum<uint32_t>(), st));
 		bdp_frag_decide<<<blocks(m), 256, 0, st>>>(dE, va, first, m, (uint32_t *)d->bits.p, dcnt);
@@ -321,7 +314,7 @@ extern "C" int bmh_bam_markdup_device(const uint8_t *recs, uint64_t n_bytes, voi
 	for (uint32_t i = 0; i < n; ++i)
 		if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) { bmh_set_error("%s: record %u is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL; }
 	bdp_dev_t d;
-	bmh_grow_t in, in_off;
+	dev_buf<uint8_t> in, in_off;
 	RCK(in.need((size_t)n_bytes + 16)); RCK(in_off.need(8 * off.size()));
 	if (n_bytes) HIPCK(hipMemcpyAsync(in.p, recs, (size_t)n_bytes, hipMemcpyHostToDevice, st));
 	HIPCK(hipMemcpyAsync(in_off.p, off.data(), 8 * off.size(), hipMemcpyHostToDevice, st));

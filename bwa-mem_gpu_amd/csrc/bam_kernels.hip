@@ -19,9 +19,6 @@
 #include "bam_core.h"
 #include "bam_ws.h"
 
-#define HIPCK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
-#define RCK(x) do { const int rc_ = (x); if (rc_ != BMH_OK) return rc_; } while (0)
-
 namespace {
 
 constexpr uint32_t CH = 64;        // bytes of text per thread of the newline walks
@@ -69,9 +66,6 @@ __global__ void __launch_bounds__(256) bam_records(const uint8_t *__restrict__ t
 	if (st != BAM_OK) { atomicAdd(flags, 1u); atomicMin(flags + 1, r); }
 }
 
-size_t scan32_bytes(size_t n) { size_t t = 0; (void)rocprim::exclusive_scan(nullptr, t, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, n, rocprim::plus<uint32_t>(), 0); return t + 256; }
-size_t scan64_bytes(size_t n) { size_t t = 0; (void)rocprim::exclusive_scan(nullptr, t, (uint32_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, n, rocprim::plus<uint64_t>(), 0); return t + 256; }
-
 const char *bam_what(uint32_t s)
 {
 	static const char *const w[] = {"ok", "fewer than 11 fields", "a read name that is empty or longer than 254 bytes", "a bad CIGAR, or more than 65535 operations",
@@ -100,7 +94,7 @@ extern "C" int bmh_sam_to_bam_device(bmh_bam_ws_t *ws, const char *d_text, uint6
 	const uint64_t n_chunks = (n + CH - 1) / CH;
 	if (n_chunks >= 0xffffff00ull) { bmh_set_error("%s: %llu bytes of text in one call", fn, (unsigned long long)n); return BMH_EINVAL; }
 	RCK(ws->cnt.need(4 * (n_chunks + 1))); RCK(ws->cnt_off.need(4 * (n_chunks + 1))); RCK(ws->flags.need(64));
-	size_t tb = scan32_bytes(n_chunks + 1);
+	size_t tb = scan_tmp_bytes<uint32_t, uint32_t>(n_chunks + 1);
 	RCK(ws->tmp.need(tb));
 	uint32_t *cnt = (uint32_t *)ws->cnt.p, *cnt_off = (uint32_t *)ws->cnt_off.p, *flags = (uint32_t *)ws->flags.p;
 	HIPCK(hipMemsetAsync(cnt + n_chunks, 0, 4, st));
@@ -113,7 +107,7 @@ extern "C" int bmh_sam_to_bam_device(bmh_bam_ws_t *ws, const char *d_text, uint6
 	const uint32_t n_rec = n_lines + (last != '\n' ? 1u : 0u);
 	if (n_rec < n_lines) { bmh_set_error("%s: 2^32 lines", fn); return BMH_EINVAL; }
 	RCK(ws->line_end.need(8 * ((size_t)n_lines + 1))); RCK(ws->size.need(4 * ((size_t)n_rec + 1))); RCK(ws->status.need(4 * ((size_t)n_rec + 1))); RCK(ws->off.need(8 * ((size_t)n_rec + 2)));
-	tb = scan64_bytes((size_t)n_rec + 1);
+	tb = scan_tmp_bytes<uint32_t, uint64_t>((size_t)n_rec + 1);
 	RCK(ws->tmp.need(tb));
 	uint64_t *line_end = (uint64_t *)ws->line_end.p, *off = (uint64_t *)ws->off.p; uint32_t *size = (uint32_t *)ws->size.p, *status = (uint32_t *)ws->status.p;
 	bam_nl_fill<<<(unsigned)((n_chunks + 255) / 256), 256, 0, st>>>(text, n, cnt_off, line_end, n_chunks, n_lines);

@@ -25,14 +25,11 @@
 #include "bam_dup.h"
 #include "bam_ws.h"
 
-#define HIPCK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
-#define RCK(x) do { const int rc_ = (x); if (rc_ != BMH_OK) return rc_; } while (0)
-
 struct bsr_dev_t {
-	bmh_grow_t keys, keys2, ord, ord2, tmp, src_off, size, soff, sorted, in, in_off;      // sort and gather
+	dev_buf<uint8_t> keys, keys2, ord, ord2, tmp, src_off, size, soff, sorted, in, in_off;      // sort and gather
 	hipEvent_t ev_flag[2] = {nullptr, nullptr};                                          // around a window's flag step (duplicate marking)
-	bmh_grow_t side;                                                                      // a word per record, permuted with a batch's records (duplicate marking)
-	bmh_grow_t head, hpos, heads, lin, counts, n_win, lin_off;                            // the index pass; lin, counts: of the whole file
+	dev_buf<uint8_t> side;                                                                      // a word per record, permuted with a batch's records (duplicate marking)
+	dev_buf<uint8_t> head, hpos, heads, lin, counts, n_win, lin_off;                            // the index pass; lin, counts: of the whole file
 	uint8_t *h_buf = nullptr; size_t h_cap = 0;                                          // pinned: a window's records on their way up, its members on their way down
 	int n_ref = 0;
 	int pinned(size_t n)
@@ -143,14 +140,10 @@ __global__ void __launch_bounds__(256) bsr_index_heads(const uint8_t *__restrict
 	out[hpos[j]] = h;
 }
 
-size_t sort_bytes(size_t n) { size_t t = 0; (void)rocprim::radix_sort_pairs(nullptr, t, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, n, 0, 64, 0); return t + 256; }
-size_t scan_bytes(size_t n) { size_t t = 0; (void)rocprim::exclusive_scan(nullptr, t, (uint32_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, n, rocprim::plus<uint64_t>(), 0); return t + 256; }
-size_t scan32_bytes(size_t n) { size_t t = 0; (void)rocprim::exclusive_scan(nullptr, t, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, n, rocprim::plus<uint32_t>(), 0); return t + 256; }
-
 // size [n] on the device -> soff [n + 1], then the n records src + src_off[j] into d->sorted at soff[j]
 int scan_and_gather(bsr_dev_t *d, const uint8_t *d_src, uint64_t src_bytes, uint32_t n, uint64_t total, hipStream_t st)
 {
-	size_t tb = scan_bytes((size_t)n + 1);
+	size_t tb = scan_tmp_bytes<uint32_t, uint64_t>((size_t)n + 1);
 	RCK(d->tmp.need(tb)); RCK(d->soff.need(8 * ((size_t)n + 2))); RCK(d->sorted.need((size_t)total + 16));
 	HIPCK(hipMemsetAsync((uint32_t *)d->size.p + n, 0, 4, st));
 	HIPCK(rocprim::exclusive_scan(d->tmp.p, tb, (uint32_t *)d->size.p, (uint64_t *)d->soff.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
@@ -168,7 +161,7 @@ int bsr_sort_run_device(bsr_dev_t *d, const uint8_t *d_recs, const uint64_t *d_o
                         const uint32_t *d_side, const uint32_t **d_side_sorted)
 {
 	hipStream_t st = (hipStream_t)stream;
-	size_t sb = sort_bytes(n);
+	size_t sb = sort_pairs_tmp_bytes<uint64_t, uint32_t>(n);
 	RCK(d->keys.need(8 * ((size_t)n + 1))); RCK(d->keys2.need(8 * ((size_t)n + 1))); RCK(d->ord.need(4 * ((size_t)n + 1))); RCK(d->ord2.need(4 * ((size_t)n + 1)));
 	RCK(d->src_off.need(8 * ((size_t)n + 1))); RCK(d->size.need(4 * ((size_t)n + 2))); RCK(d->tmp.need(sb));
 	if (d_side) RCK(d->side.need(4 * ((size_t)n + 1)));
@@ -188,12 +181,12 @@ int bsr_sort_keys_device(bsr_dev_t *d, const uint64_t *keys, uint64_t n, void *s
 	hipStream_t st = (hipStream_t)stream;
 	if (n == 0) return BMH_OK;
 	if (n > 0xfffffff0ull) { bmh_set_error("sorted BAM: %llu records: the final sort takes fewer than 2^32", (unsigned long long)n); return BMH_EINVAL; }
-	size_t sb = sort_bytes((size_t)n);
+	size_t sb = sort_pairs_tmp_bytes<uint64_t, uint32_t>((size_t)n);
 	// keys and ordinals, in and out, and the sort's work space must fit the device: 24 bytes per record and the work space
 	size_t fr = 0, tot = 0;
 	HIPCK(hipMemGetInfo(&fr, &tot));
 	// (a buffer that has to grow is freed and allocated anew a quarter larger than asked: that is what is counted; one that is large enough costs nothing)
-	bmh_grow_t *const buf[5] = {&d->keys, &d->keys2, &d->ord, &d->ord2, &d->tmp};
+	dev_buf<uint8_t> *const buf[5] = {&d->keys, &d->keys2, &d->ord, &d->ord2, &d->tmp};
 	const size_t ask[5] = {8 * (size_t)n, 8 * (size_t)n, 4 * (size_t)n, 4 * (size_t)n, sb};
 	size_t have = 0, want = 64u << 20;
 	for (int k = 0; k < 5; ++k) if (ask[k] > buf[k]->cap) { have += buf[k]->cap; want += ask[k] + ask[k] / 4 + 1024; }
@@ -259,7 +252,7 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 	const uint8_t *d_members = nullptr; uint64_t mb = 0;
 	RCK(bmh_bgzf_deflate_device(ws, (const uint8_t *)d->sorted.p, total, level, st, &d_members, &mb));
 	// the index pass: the members' offsets are the compressor's scan (ws->moff [n_members + 1])
-	size_t tb = scan32_bytes((size_t)n + 1);
+	size_t tb = scan_tmp_bytes<uint32_t, uint32_t>((size_t)n + 1);
 	RCK(d->head.need(4 * ((size_t)n + 2))); RCK(d->hpos.need(4 * ((size_t)n + 2))); RCK(d->heads.need(sizeof(bsr_head_t) * ((size_t)n + 1))); RCK(d->tmp.need(tb));
 	HIPCK(hipMemsetAsync((uint32_t *)d->head.p + n, 0, 4, st));
 	bsr_index_marks<<<(n + 255) / 256, 256, 0, st>>>((const uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, n, (const uint64_t *)ws->moff.p, ix.file_pos, d->n_ref, (const uint32_t *)d->n_win.p,

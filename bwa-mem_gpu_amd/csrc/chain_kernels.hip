@@ -15,10 +15,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include "bmh_internal.h"
+#include "devmem.h"
 #include "wtrace.h"
 #include "chain_core.h"
-
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
 
 struct ch_outreg_t { int64_t seed_rbeg; int32_t seed_qbeg, seedlen0, job0, job1; uint32_t read; int32_t l_query; };   // 32 B
 

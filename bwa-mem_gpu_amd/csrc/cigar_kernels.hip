@@ -8,16 +8,12 @@
 // The direction matrix (one byte per in-band cell) lives in LDS when it fits, else in a per-wave slab in HBM; the
 // traceback, the run-length CIGAR, NM and the MD string are produced by the wave in lock step (one lane writes).
 #include <hip/hip_runtime.h>
-#include <map>
-#include <mutex>
-#include <utility>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include <stdio.h>
 #include <stdlib.h>
 #include "bmh_internal.h"
-
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
+#include "devmem.h"
 
 #define G_NEG (-0x40000000)          // MINUS_INF of ksw.c:997
 #define G_SENT (-0x60000000)         // below every value the reference arithmetic can produce; only ever max()ed and shifted a little
@@ -743,35 +739,18 @@ __global__ void __launch_bounds__(256) cigar_size_kernel(const int32_t *regs, in
 // gigabytes: allocating them per run of a worker thread cost more than the kernels), dropped by bmh_cigar_release(stream) when the caller retires the stream.
 // A stream belongs to one thread at a time (the library's rule for all per-stream scratch).
 struct cigar_scratch_t {
-	unsigned long long *d_sizes = nullptr;       // [0] largest rectangle [1] longest sequence [2] fast-path matrix bytes; then CG_NKIND list counts (u32)
-	uint8_t *slab = nullptr; size_t slab_bytes = 0;
-	uint8_t *lslab = nullptr; size_t lslab_bytes = 0;            // the long form's direction matrices + bases / H / E rows
-	cg_job_t *jobs = nullptr; uint32_t *lists = nullptr, *rev = nullptr; size_t cap_n = 0, cap_rev = 0; uint8_t *z = nullptr; size_t z_bytes = 0;
-	void drop()
-	{
-		void *ps[] = {d_sizes, slab, jobs, lists, rev, z, lslab};
-		for (void *q : ps) if (q) (void)hipFree(q);
-		d_sizes = nullptr; slab = nullptr; jobs = nullptr; lists = rev = nullptr; z = nullptr; lslab = nullptr;
-		slab_bytes = cap_n = cap_rev = z_bytes = lslab_bytes = 0;
-	}
+	dev_buf<unsigned long long> d_sizes;         // [0] largest rectangle [1] longest sequence [2] fast-path matrix bytes; then CG_NKIND list counts (u32)
+	dev_buf<uint8_t> slab;
+	dev_buf<uint8_t> lslab;                      // the long form's direction matrices + bases / H / E rows
+	dev_buf<cg_job_t> jobs; dev_buf<uint32_t[CG_NKIND]> lists; dev_buf<uint32_t> rev; dev_buf<uint8_t> z;      // jobs and lists grow together
 };
-static std::mutex g_cs_mu;
-static std::map<std::pair<int, void *>, cigar_scratch_t *> g_cs_map;
+static stream_scratch<cigar_scratch_t> g_cs_reg;
 
 extern "C" void bmh_cigar_release(void *stream_)
 {
 	int dev = 0;
 	if (hipGetDevice(&dev) != hipSuccess) return;
-	cigar_scratch_t *S = nullptr;
-	{
-		std::lock_guard<std::mutex> lk(g_cs_mu);
-		auto it = g_cs_map.find(std::make_pair(dev, stream_));
-		if (it == g_cs_map.end()) return;
-		S = it->second;
-		g_cs_map.erase(it);
-	}
-	S->drop();
-	delete S;
+	g_cs_reg.take(dev, stream_);
 }
 
 template <int C, int CLO>
@@ -779,13 +758,6 @@ static int launch_cigar(const cigar_args_t &a, unsigned grid, size_t lds, hipStr
 {
 	HIPCK(hipFuncSetAttribute((const void *)cigar_kernel<C, CLO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 	cigar_kernel<C, CLO><<<grid, 64, lds, st>>>(a);
-	return BMH_OK;
-}
-
-template <class T> static int cg_grow(T *&p, size_t bytes)
-{
-	if (p) { (void)hipFree(p); p = nullptr; }
-	if (hipMalloc((void **)&p, bytes) != hipSuccess) { bmh_set_error("bmh_cigar_batch: hipMalloc of %zu bytes failed", bytes); return BMH_ENOMEM; }
 	return BMH_OK;
 }
 
@@ -799,20 +771,12 @@ extern "C" int bmh_cigar_batch(const bmh_index_t *idx, const uint8_t *d_reads, c
 	if (n == 0) return BMH_OK;
 	hipStream_t st = (hipStream_t)stream_;
 	static const bool slow_only = getenv("BMH_CIGAR_SLOW") != nullptr;
-	cigar_scratch_t *gs;
-	{
-		int dev = 0;
-		HIPCK(hipGetDevice(&dev));
-		std::lock_guard<std::mutex> lk(g_cs_mu);
-		auto key = std::make_pair(dev, stream_);
-		auto it = g_cs_map.find(key);
-		if (it == g_cs_map.end()) { gs = new cigar_scratch_t(); g_cs_map[key] = gs; }
-		else gs = it->second;
-	}
-	cigar_scratch_t &g_cs = *gs;
-	if (!g_cs.d_sizes) HIPCK(hipMalloc((void **)&g_cs.d_sizes, 64));
-	HIPCK(hipMemsetAsync(g_cs.d_sizes, 0, 64, st));
-	cigar_size_kernel<<<(n + 255) / 256, 256, 0, st>>>(d_regs, reg_stride, d_sel, n, g_cs.d_sizes);
+	int dev = 0;
+	HIPCK(hipGetDevice(&dev));
+	cigar_scratch_t &g_cs = g_cs_reg.get(dev, stream_);
+	if (!g_cs.d_sizes.p) RCK(g_cs.d_sizes.resize(8));
+	HIPCK(hipMemsetAsync(g_cs.d_sizes.p, 0, 64, st));
+	cigar_size_kernel<<<(n + 255) / 256, 256, 0, st>>>(d_regs, reg_stride, d_sel, n, g_cs.d_sizes.p);
 	cigar_args_t a;
 	memset(&a, 0, sizeof(a));
 	a.reads = d_reads; a.offs = d_offs; a.lens = d_lens; a.pac = idx->dev.pac; a.l_pac = (long long)idx->dev.l_pac;
@@ -820,16 +784,12 @@ extern "C" int bmh_cigar_batch(const bmh_index_t *idx, const uint8_t *d_reads, c
 	a.a = p->a; a.b = p->b; a.o_del = p->o_del; a.e_del = p->e_del; a.o_ins = p->o_ins; a.e_ins = p->e_ins; a.opt_w = opt_w;
 	a.max_cigar = max_cigar; a.md_cap = d_md ? md_cap : 0; a.cigar = d_cigar; a.aln = d_aln; a.md = d_md;
 	if (!slow_only) {
-		if (g_cs.cap_n < n) {
-			const size_t c = (size_t)n + n / 4 + 1024;
-			if (cg_grow(g_cs.jobs, sizeof(cg_job_t) * c) != BMH_OK || cg_grow(g_cs.lists, 4 * CG_NKIND * c) != BMH_OK) return BMH_ENOMEM;
-			g_cs.cap_n = c;
-		}
-		a.jobs = g_cs.jobs; a.lists = g_cs.lists; a.list_n = (uint32_t *)(g_cs.d_sizes + 3); a.z_total = g_cs.d_sizes + 2;
+		if (g_cs.lists.cap < n) { RCK(g_cs.jobs.need(n)); RCK(g_cs.lists.need(n)); }
+		a.jobs = g_cs.jobs.p; a.lists = g_cs.lists.as<uint32_t>(); a.list_n = (uint32_t *)(g_cs.d_sizes.p + 3); a.z_total = g_cs.d_sizes.p + 2;
 		cigar_classify_kernel<<<(n + 255) / 256, 256, 0, st>>>(a);
 	}
 	unsigned long long h[8];
-	HIPCK(hipMemcpyAsync(h, g_cs.d_sizes, 64, hipMemcpyDeviceToHost, st));
+	HIPCK(hipMemcpyAsync(h, g_cs.d_sizes.p, 64, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
 	const uint32_t *h_list_n = (const uint32_t *)(h + 3);
 	if (!slow_only && getenv("BMH_CIGAR_STATS"))
@@ -843,9 +803,9 @@ extern "C" int bmh_cigar_batch(const bmh_index_t *idx, const uint8_t *d_reads, c
 	a.long_split = long_len > CG_LDS_MAX;
 	if (!slow_only) {
 		// fast path: direction matrices of all single-band jobs at once (HBM is large), then one lane per region
-		if (g_cs.z_bytes < h[2] + 256) { const size_t c = (size_t)h[2] + (size_t)h[2] / 4 + 4096; if (cg_grow(g_cs.z, c) != BMH_OK) return BMH_ENOMEM; g_cs.z_bytes = c; }
-		if (g_cs.cap_rev < (size_t)n * max_cigar) { const size_t c = (size_t)n * max_cigar + 1024; if (cg_grow(g_cs.rev, 4 * c) != BMH_OK) return BMH_ENOMEM; g_cs.cap_rev = c; }
-		a.z = g_cs.z; a.rev = g_cs.rev;
+		if (g_cs.z.cap < h[2] + 256) RCK(g_cs.z.resize((size_t)h[2] + (size_t)h[2] / 4 + 4096));
+		if (g_cs.rev.cap < (size_t)n * max_cigar) RCK(g_cs.rev.resize((size_t)n * max_cigar + 1024));
+		a.z = g_cs.z.p; a.rev = g_cs.rev.p;
 		if (h_list_n[CG_F2]) cigar_dp16_kernel<2><<<(h_list_n[CG_F2] + 15) / 16, 256, 0, st>>>(a, CG_F2);
 		if (h_list_n[CG_F3]) cigar_dp16_kernel<3><<<(h_list_n[CG_F3] + 15) / 16, 256, 0, st>>>(a, CG_F3);
 		if (h_list_n[CG_F5]) cigar_dp16_kernel<5><<<(h_list_n[CG_F5] + 15) / 16, 256, 0, st>>>(a, CG_F5);
@@ -867,13 +827,8 @@ extern "C" int bmh_cigar_batch(const bmh_index_t *idx, const uint8_t *d_reads, c
 	a.z_slab_stride = (h[0] + 255) & ~255ull;
 	if (a.long_split) a.z_slab_stride = (unsigned long long)max_len * max_len;      // (the LDS forms' largest rectangle)
 	const size_t slab = (size_t)a.z_slab_stride * grid;
-	if (g_cs.slab_bytes < slab) {
-		if (g_cs.slab) (void)hipFree(g_cs.slab);
-		g_cs.slab = nullptr; g_cs.slab_bytes = 0;
-		if (hipMalloc((void **)&g_cs.slab, slab) != hipSuccess) { bmh_set_error("bmh_cigar_batch: hipMalloc of %zu bytes failed", slab); return BMH_ENOMEM; }
-		g_cs.slab_bytes = slab;
-	}
-	a.z_slab = g_cs.slab;
+	if (g_cs.slab.cap < slab) RCK(g_cs.slab.resize(slab));
+	a.z_slab = g_cs.slab.p;
 	int rc = BMH_OK;
 	rc = launch_cigar<1, 0>(a, grid, lds, st);
 	if (rc == BMH_OK && max_len > 64) rc = launch_cigar<2, 1>(a, grid, lds, st);
@@ -902,13 +857,8 @@ extern "C" int bmh_cigar_batch(const bmh_index_t *idx, const uint8_t *d_reads, c
 		if (g < 1) g = 1;
 		if (g > n) g = n;
 		const size_t need = (size_t)(per * g);
-		if (g_cs.lslab_bytes < need) {
-			if (g_cs.lslab) (void)hipFree(g_cs.lslab);
-			g_cs.lslab = nullptr; g_cs.lslab_bytes = 0;
-			if (hipMalloc((void **)&g_cs.lslab, need) != hipSuccess) { bmh_set_error("bmh_cigar_batch: hipMalloc of %zu bytes failed", need); return BMH_ENOMEM; }
-			g_cs.lslab_bytes = need;
-		}
-		b.z_slab = g_cs.lslab; b.lws = g_cs.lslab + (size_t)(b.z_slab_stride * g);
+		if (g_cs.lslab.cap < need) RCK(g_cs.lslab.resize(need));
+		b.z_slab = g_cs.lslab.p; b.lws = g_cs.lslab.p + (size_t)(b.z_slab_stride * g);
 		const size_t llds = 4 * (size_t)max_cigar;
 		HIPCK(hipFuncSetAttribute((const void *)cigar_kernel<1, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)llds));
 		cigar_kernel<1, 0, true><<<(unsigned)g, 64, llds, st>>>(b);

@@ -17,9 +17,6 @@
 #include "deflate_core.h"
 #include "bam_ws.h"
 
-#define HIPCK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
-#define RCK(x) do { const int rc_ = (x); if (rc_ != BMH_OK) return rc_; } while (0)
-
 extern "C" const uint8_t bmh_bgzf_eof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 namespace {
@@ -43,8 +40,6 @@ __global__ void __launch_bounds__(256) dfl_gather(const uint8_t *__restrict__ sl
 	for (uint32_t k = threadIdx.x; k < sz; k += 256) out[o + k] = s[k];
 }
 
-size_t scan64_bytes(size_t n) { size_t t = 0; (void)rocprim::exclusive_scan(nullptr, t, (uint32_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, n, rocprim::plus<uint64_t>(), 0); return t + 256; }
-
 }   // namespace
 
 extern "C" int bmh_bgzf_deflate_device(bmh_bam_ws_t *ws, const uint8_t *d_in, uint64_t n, int level, void *stream_, const uint8_t **d_out, uint64_t *out_bytes)
@@ -58,7 +53,7 @@ extern "C" int bmh_bgzf_deflate_device(bmh_bam_ws_t *ws, const uint8_t *d_in, ui
 	const uint64_t nm = (n + DFL_PIECE - 1) / DFL_PIECE;
 	if (nm > 0x7fffffffull) { bmh_set_error("%s: %llu bytes in one call", fn, (unsigned long long)n); return BMH_EINVAL; }
 	RCK(ws->slots.need((size_t)nm * DFL_SLOT)); RCK(ws->msize.need(4 * (nm + 1))); RCK(ws->moff.need(8 * (nm + 2)));
-	size_t tb = scan64_bytes((size_t)nm + 1);
+	size_t tb = scan_tmp_bytes<uint32_t, uint64_t>((size_t)nm + 1);
 	RCK(ws->mtmp.need(tb));
 	uint32_t *sizes = (uint32_t *)ws->msize.p; uint64_t *off = (uint64_t *)ws->moff.p;
 	HIPCK(hipMemsetAsync(ws->slots.p, 0, (size_t)nm * DFL_SLOT, st));

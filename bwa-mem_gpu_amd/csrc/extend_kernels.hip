@@ -32,10 +32,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <map>
-#include <mutex>
-#include <utility>
 #include "bmh_internal.h"
+#include "devmem.h"
 #include "wtrace.h"
 
 #define NEG_INF (-(1 << 29))
@@ -1151,45 +1149,29 @@ __global__ void __launch_bounds__(256) ext_scatter_kernel(ext_args_t A, const ui
 	}
 }
 
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
-
 // scratch for the sorted job list: one per (device, stream), grown on demand and reused across calls, so
 // that batches in flight on different streams never share it
 struct ext_scratch_t {
-	uint32_t *keys, *vals2, *counts, *bins; uint4 *recs; size_t cap; int dev;      // keys: bin of every job; vals2: job ids grouped by bin; bins: [3][EXT_N_BINS] count / base / cursor
-	hipEvent_t ev0, ev1; bool have_ev;
-	hipStream_t side[4]; hipEvent_t fork, join[4];     // class kernels run concurrently on side streams
+	dev_buf<uint32_t> keys, vals2, counts, bins; dev_buf<uint4[2]> recs;      // keys: bin of every job; vals2: job ids grouped by bin; bins: [3][EXT_N_BINS] count / base / cursor
+	hipEvent_t ev0 = nullptr, ev1 = nullptr; bool have_ev = false;
+	hipStream_t side[4] = {}; hipEvent_t fork = nullptr, join[4] = {};     // class kernels run concurrently on side streams
+	~ext_scratch_t()
+	{
+		for (hipEvent_t e : {ev0, ev1, fork, join[0], join[1], join[2], join[3]}) if (e) (void)hipEventDestroy(e);
+		for (hipStream_t q : side) if (q) (void)hipStreamDestroy(q);
+	}
 };
-static std::mutex g_scr_mu;
-static std::map<std::pair<int, void *>, ext_scratch_t *> g_scr_map;
+static stream_scratch<ext_scratch_t> g_scr_reg;
 static thread_local ext_scratch_t *g_last = nullptr;
-
-static ext_scratch_t *scratch_for(int dev, void *stream)
-{
-	std::lock_guard<std::mutex> lk(g_scr_mu);
-	auto key = std::make_pair(dev, stream);
-	auto it = g_scr_map.find(key);
-	if (it != g_scr_map.end()) return it->second;
-	ext_scratch_t *s = (ext_scratch_t *)calloc(1, sizeof(ext_scratch_t));
-	s->dev = dev;
-	g_scr_map[key] = s;
-	return s;
-}
 
 // room for n jobs; grown by a quarter beyond the request, so that batches of slowly growing size do not reallocate every time
 // (hipFree waits for the whole device: a reallocation between the two extension passes of bmh_chain_extend_merge would serialise them)
-static int scratch_reserve(ext_scratch_t &g_scr, int dev, size_t n)
+static int scratch_reserve(ext_scratch_t &g_scr, size_t n)
 {
-	if (g_scr.cap >= n) return BMH_OK;
-	const size_t c = n + n / 4 + 1024;
-	void *ps[] = {g_scr.keys, g_scr.vals2, g_scr.counts, g_scr.bins, g_scr.recs};
-	for (void *q : ps) if (q) (void)hipFree(q);
-	g_scr.keys = g_scr.vals2 = g_scr.counts = g_scr.bins = nullptr; g_scr.recs = nullptr; g_scr.cap = 0;
-	HIPCK(hipMalloc((void **)&g_scr.keys, 4 * c)); HIPCK(hipMalloc((void **)&g_scr.vals2, 4 * c));
-	HIPCK(hipMalloc((void **)&g_scr.recs, 32 * c));
-	HIPCK(hipMalloc((void **)&g_scr.counts, 4 * 3 * EXT_N_CLS));
-	HIPCK(hipMalloc((void **)&g_scr.bins, 4 * 3 * EXT_N_BINS));
-	g_scr.cap = c; g_scr.dev = dev;
+	if (!g_scr.counts.p) { RCK(g_scr.counts.resize(3 * EXT_N_CLS)); RCK(g_scr.bins.resize(3 * EXT_N_BINS)); }
+	if (g_scr.recs.cap >= n) return BMH_OK;                            // (the last of the group to grow: a growth that failed half way is done again)
+	g_scr.keys.drop(); g_scr.vals2.drop(); g_scr.recs.drop();           // one burst of frees, then the allocations
+	RCK(g_scr.keys.need(n)); RCK(g_scr.vals2.need(n)); RCK(g_scr.recs.need(n));
 	return BMH_OK;
 }
 // (internal, bmh_internal.h) the scratch of (current device, stream) sized for batches of up to n jobs before any of them is launched
@@ -1197,7 +1179,7 @@ int bmh_extend_reserve(void *stream_, uint64_t n)
 {
 	int dev = 0;
 	HIPCK(hipGetDevice(&dev));
-	return scratch_reserve(*scratch_for(dev, stream_), dev, (size_t)n);
+	return scratch_reserve(g_scr_reg.get(dev, stream_), (size_t)n);
 }
 
 // Frees the scratch (sorted job list, side streams, events) that bmh_extend_batch keeps per (device, stream); call it before
@@ -1211,22 +1193,8 @@ extern "C" void bmh_extend_release(void *stream_)
 	int dev = 0;
 	if (hipGetDevice(&dev) != hipSuccess) return;
 	bmh_finalize_release(stream_); bmh_matesw_release(stream_); bmh_cigar_release(stream_);      // the per-stream scratch of the stages after the extension goes with it
-	ext_scratch_t *s = nullptr;
-	{
-		std::lock_guard<std::mutex> lk(g_scr_mu);
-		auto it = g_scr_map.find(std::make_pair(dev, stream_));
-		if (it == g_scr_map.end()) return;
-		s = it->second;
-		g_scr_map.erase(it);
-	}
-	if (g_last == s) g_last = nullptr;
-	void *ps[] = {s->keys, s->vals2, s->counts, s->bins, s->recs};
-	for (void *q : ps) if (q) (void)hipFree(q);
-	if (s->have_ev) {
-		(void)hipEventDestroy(s->ev0); (void)hipEventDestroy(s->ev1); (void)hipEventDestroy(s->fork);
-		for (int i = 0; i < 4; ++i) { (void)hipStreamDestroy(s->side[i]); (void)hipEventDestroy(s->join[i]); }
-	}
-	free(s);
+	const std::unique_ptr<ext_scratch_t> s = g_scr_reg.take(dev, stream_);
+	if (g_last == s.get()) g_last = nullptr;
 }
 
 // device time of the last bmh_extend_batch issued by this thread (HIP events on its stream)
@@ -1246,7 +1214,7 @@ extern "C" int64_t bmh_extend_last_unsupported(void)
 	if (!g_last || !g_last->have_ev) return 0;
 	uint32_t n0 = 0;
 	if (hipEventSynchronize(g_last->ev1) != hipSuccess) return -1;
-	if (hipMemcpy(&n0, g_last->counts, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+	if (hipMemcpy(&n0, g_last->counts.p, 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
 	return (int64_t)n0;
 }
 
@@ -1257,7 +1225,7 @@ extern "C" int bmh_extend_last_class_sizes(uint32_t *sizes, int cap)
 	if (!g_last || !g_last->have_ev) return 0;
 	uint32_t c[2 * EXT_N_CLS];
 	HIPCK(hipEventSynchronize(g_last->ev1));
-	HIPCK(hipMemcpy(c, g_last->counts, sizeof(c), hipMemcpyDeviceToHost));
+	HIPCK(hipMemcpy(c, g_last->counts.p, sizeof(c), hipMemcpyDeviceToHost));
 	for (int k = 0; k < cap && k < EXT_N_CLS; ++k) sizes[k] = c[2 * k];
 	return EXT_N_CLS;
 }
@@ -1363,9 +1331,9 @@ static int extend_launch(const uint8_t *d_q, const uint32_t *d_qoff, const uint3
 	hipStream_t st = (hipStream_t)stream_;
 	int dev = 0;
 	HIPCK(hipGetDevice(&dev));
-	ext_scratch_t &g_scr = *scratch_for(dev, stream_);
+	ext_scratch_t &g_scr = g_scr_reg.get(dev, stream_);
 	g_last = &g_scr;
-	{ const int rc = scratch_reserve(g_scr, dev, n); if (rc != BMH_OK) return rc; }
+	RCK(scratch_reserve(g_scr, n));
 	if (!g_scr.have_ev) {
 		HIPCK(hipEventCreate(&g_scr.ev0)); HIPCK(hipEventCreate(&g_scr.ev1));
 		HIPCK(hipEventCreateWithFlags(&g_scr.fork, hipEventDisableTiming));
@@ -1380,7 +1348,7 @@ static int extend_launch(const uint8_t *d_q, const uint32_t *d_qoff, const uint3
 	a.desc = desc ? 1 : 0;
 	a.reads = desc ? desc->reads : nullptr; a.pac = desc ? desc->pac : nullptr; a.l_pac = desc ? desc->l_pac : 0;
 	a.jq_src = desc ? desc->jq_src : nullptr; a.job_side = desc ? desc->job_side : nullptr; a.jt0 = desc ? (const long long *)desc->jt0 : nullptr;
-	a.ids = g_scr.vals2; a.recs = g_scr.recs; a.count = g_scr.counts; a.ctr = g_scr.counts + 2 * EXT_N_CLS; a.out = d_out; a.raw = d_raw;
+	a.ids = g_scr.vals2.p; a.recs = g_scr.recs.as<uint4>(); a.count = g_scr.counts.p; a.ctr = g_scr.counts.p + 2 * EXT_N_CLS; a.out = d_out; a.raw = d_raw;
 	a.a = p->a; a.b = p->b; a.o_del = p->o_del; a.e_del = p->e_del; a.o_ins = p->o_ins; a.e_ins = p->e_ins;
 	a.zdrop = p->zdrop; a.end_bonus = p->end_bonus;
 	a.stats = nullptr;
@@ -1397,19 +1365,19 @@ static int extend_launch(const uint8_t *d_q, const uint32_t *d_qoff, const uint3
 	static thread_local hipEvent_t ph[4] = {nullptr, nullptr, nullptr, nullptr};
 	if (want_phases && !ph[0]) for (hipEvent_t &e : ph) HIPCK(hipEventCreate(&e));
 	if (want_phases) HIPCK(hipEventRecord(ph[0], st));
-	HIPCK(hipMemsetAsync(g_scr.counts, 0, 4 * 3 * EXT_N_CLS, st));
-	HIPCK(hipMemsetAsync(g_scr.bins, 0, 4 * 3 * EXT_N_BINS, st));
+	HIPCK(hipMemsetAsync(g_scr.counts.p, 0, 4 * 3 * EXT_N_CLS, st));
+	HIPCK(hipMemsetAsync(g_scr.bins.p, 0, 4 * 3 * EXT_N_BINS, st));
 	// packed 16-bit rows need 1 <= b, a + b <= 255 (byte score table), a >= 0 and gap penalties that fit the 16-bit lanes
 	const bool pk_ok = g_ext_packed && p->a > 0 && p->b >= 1 && p->a + p->b <= 255 && p->o_del + p->e_del < 4096 && p->o_ins + p->e_ins < 4096 && p->e_ins * 32 < 4096;
 	const int persist = pk_ok ? bmh_tune("EXT_PERSIST", PK_PERSIST_DEFAULT) : 0;
 	{
 		unsigned gp = (unsigned)((n + 31) / 32);
 		if (gp > 4096) gp = 4096;
-		ext_closed_form_kernel<<<gp, 256, 0, st>>>(a, n, g_scr.keys, g_scr.bins, pk_ok ? p->a : 0, persist == 0 ? bmh_tune("EXT_G2", 1) : 0);      // (EXT_G2 = k: the two-lane classes for queries beyond 16 (k - 1) columns, 0: none; the persistent kernel knows them not)
+		ext_closed_form_kernel<<<gp, 256, 0, st>>>(a, n, g_scr.keys.p, g_scr.bins.p, pk_ok ? p->a : 0, persist == 0 ? bmh_tune("EXT_G2", 1) : 0);      // (EXT_G2 = k: the two-lane classes for queries beyond 16 (k - 1) columns, 0: none; the persistent kernel knows them not)
 	}
 	if (want_phases) { HIPCK(hipEventRecord(ph[1], st)); HIPCK(hipEventRecord(ph[2], st)); }
-	ext_offsets_kernel<<<1, 64, 0, st>>>(g_scr.counts, g_scr.bins, g_scr.bins + EXT_N_BINS);
-	ext_scatter_kernel<<<(n + 255) / 256, 256, 0, st>>>(a, g_scr.keys, n, g_scr.bins + EXT_N_BINS, g_scr.bins + 2 * EXT_N_BINS, g_scr.vals2, g_scr.recs);
+	ext_offsets_kernel<<<1, 64, 0, st>>>(g_scr.counts.p, g_scr.bins.p, g_scr.bins.p + EXT_N_BINS);
+	ext_scatter_kernel<<<(n + 255) / 256, 256, 0, st>>>(a, g_scr.keys.p, n, g_scr.bins.p + EXT_N_BINS, g_scr.bins.p + 2 * EXT_N_BINS, g_scr.vals2.p, g_scr.recs.as<uint4>());
 	// class sizes stay on the device (no host sync): every class kernel is launched with a grid
 	// that covers the whole batch and its waves stride over the class's slice of the sorted list
 	unsigned g16 = (unsigned)((n + 15) / 16), gw = (unsigned)((n + 3) / 4);
@@ -1525,7 +1493,7 @@ static int extend_launch(const uint8_t *d_q, const uint32_t *d_qoff, const uint3
 		fprintf(stderr, "[ext] packed kernels (-DPK_STATS builds): idle group-rows while the wave still had jobs to draw %llu, in the wave's drain %llu\n", h[6], h[7]);
 		{
 			uint32_t hc[2 * EXT_N_CLS];
-			HIPCK(hipMemcpy(hc, g_scr.counts, sizeof(hc), hipMemcpyDeviceToHost));
+			HIPCK(hipMemcpy(hc, g_scr.counts.p, sizeof(hc), hipMemcpyDeviceToHost));
 			fprintf(stderr, "[ext] jobs per class:");
 			for (int c = 0; c < EXT_N_CLS; ++c) if (hc[2 * c]) fprintf(stderr, " %d:%u", c, hc[2 * c]);
 			fprintf(stderr, "\n");

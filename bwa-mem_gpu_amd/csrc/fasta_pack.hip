@@ -43,7 +43,9 @@
 #include <future>
 #include <string>
 #include <vector>
+#define BMH_CK_PREFIX "index_fasta: "
 #include "bmh_internal.h"
+#include "devmem.h"
 
 namespace {
 
@@ -293,29 +295,26 @@ struct record_t { std::string name, comment; uint64_t offset; };
 
 double secs(std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); }
 
-#define FCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("index_fasta: %s: %s", #x, hipGetErrorString(e_)); rc = BMH_ENODEV; goto done; } } while (0)
+// a failed HIP call / a non-OK code ends bmh_fasta_pack through its `done:` label
+#define FCK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { rc = bmh_hip_failed(BMH_CK_PREFIX, e_, #x); goto done; } } while (0)
+#define FRC(x) do { if ((rc = (x)) != BMH_OK) goto done; } while (0)
 
 struct packer_t {
 	// device
-	uint8_t *d_b = nullptr; uint32_t *lid = nullptr, *L = nullptr, *klen = nullptr, *lend = nullptr, *amb = nullptr, *arank = nullptr, *hpos = nullptr, *hseg = nullptr;
-	seg_t *seg = nullptr; ord_t *ord = nullptr, *ord2 = nullptr; uint8_t *hdr_flag = nullptr, *hole_flag = nullptr; uint16_t *t = nullptr;
-	hole_dev_t *holes = nullptr; hdr_dev_t *hdrs = nullptr; ctl_t *ctl = nullptr; void *tmp = nullptr; size_t tmp_bytes = 0;
-	uint8_t *d_pac = nullptr; uint64_t pac_cap = 0;
+	dev_buf<uint8_t> d_b; dev_buf<uint32_t> lid, L, klen, lend, amb, arank, hpos, hseg;
+	dev_buf<seg_t> seg; dev_buf<ord_t> ord, ord2; dev_buf<uint8_t> hdr_flag, hole_flag; dev_buf<uint16_t> t;
+	dev_buf<hole_dev_t> holes; dev_buf<hdr_dev_t> hdrs; dev_buf<ctl_t> ctl; dev_buf<uint8_t> tmp;
+	uint8_t *d_pac = nullptr; uint64_t pac_cap = 0;      // (a plain pointer: it is handed to the caller at the end)
 	// host
-	uint8_t *h_buf[2] = {nullptr, nullptr}; ctl_t *h_ctl = nullptr; hole_dev_t *h_holes = nullptr; hdr_dev_t *h_hdrs = nullptr;
+	pin_buf<uint8_t> h_buf[2]; pin_buf<ctl_t> h_ctl; pin_buf<hole_dev_t> h_holes; pin_buf<hdr_dev_t> h_hdrs;
 	hipStream_t st = nullptr;
-	uint32_t tab_cap = 0;
 	size_t cap = 0;     // bytes per chunk buffer (one held-back byte + chunk_bytes)
 
 	void free_work()
 	{
-		void *d[] = {d_b, lid, L, klen, lend, amb, arank, hpos, hseg, seg, ord, ord2, hdr_flag, hole_flag, t, holes, hdrs, ctl, tmp};
-		for (void *p : d) if (p) (void)hipFree(p);
-		d_b = nullptr; lid = L = klen = lend = amb = arank = hpos = hseg = nullptr; seg = nullptr; ord = ord2 = nullptr;
-		hdr_flag = hole_flag = nullptr; t = nullptr; holes = nullptr; hdrs = nullptr; ctl = nullptr; tmp = nullptr;
-		void *h[] = {h_buf[0], h_buf[1], h_ctl, h_holes, h_hdrs};
-		for (void *p : h) if (p) (void)hipHostFree(p);
-		h_buf[0] = h_buf[1] = nullptr; h_ctl = nullptr; h_holes = nullptr; h_hdrs = nullptr; tab_cap = 0;
+		d_b.drop(); lid.drop(); L.drop(); klen.drop(); lend.drop(); amb.drop(); arank.drop(); hpos.drop(); hseg.drop(); seg.drop(); ord.drop(); ord2.drop();
+		hdr_flag.drop(); hole_flag.drop(); t.drop(); holes.drop(); hdrs.drop(); ctl.drop(); tmp.drop();
+		h_buf[0].drop(); h_buf[1].drop(); h_ctl.drop(); h_holes.drop(); h_hdrs.drop();
 		if (st) (void)hipStreamDestroy(st);
 		st = nullptr;
 	}
@@ -376,26 +375,25 @@ extern "C" int bmh_fasta_pack(const char *fa_path, size_t chunk_bytes, bmh_fasta
 	P.cap = chunk_bytes + 1;
 	FCK(hipStreamCreateWithFlags(&P.st, hipStreamNonBlocking));
 	FCK(hipMemcpyToSymbol(HIP_SYMBOL(fp_jump), jt, sizeof(jt)));
-	FCK(hipHostMalloc((void **)&P.h_buf[0], P.cap)); FCK(hipHostMalloc((void **)&P.h_buf[1], P.cap));
-	FCK(hipHostMalloc((void **)&P.h_ctl, sizeof(ctl_t)));
-	FCK(hipMalloc((void **)&P.d_b, P.cap + 8));
-	FCK(hipMalloc((void **)&P.lid, P.cap * 4)); FCK(hipMalloc((void **)&P.L, P.cap * 4));
-	FCK(hipMalloc((void **)&P.klen, P.cap * 4)); FCK(hipMalloc((void **)&P.lend, P.cap * 4));
-	FCK(hipMalloc((void **)&P.amb, P.cap * 4)); FCK(hipMalloc((void **)&P.arank, P.cap * 4));
-	FCK(hipMalloc((void **)&P.hpos, P.cap * 4)); FCK(hipMalloc((void **)&P.hseg, P.cap * 4));
-	FCK(hipMalloc((void **)&P.seg, P.cap * sizeof(seg_t))); FCK(hipMalloc((void **)&P.ord, P.cap * sizeof(ord_t))); FCK(hipMalloc((void **)&P.ord2, P.cap * sizeof(ord_t)));
-	FCK(hipMalloc((void **)&P.hdr_flag, P.cap)); FCK(hipMalloc((void **)&P.hole_flag, P.cap)); FCK(hipMalloc((void **)&P.t, P.cap * 2));
-	FCK(hipMalloc((void **)&P.ctl, sizeof(ctl_t)));
+	FRC(P.h_buf[0].resize(P.cap)); FRC(P.h_buf[1].resize(P.cap));
+	FRC(P.h_ctl.resize(1));
+	FRC(P.d_b.resize(P.cap + 8));
+	FRC(P.lid.resize(P.cap)); FRC(P.L.resize(P.cap));
+	FRC(P.klen.resize(P.cap)); FRC(P.lend.resize(P.cap));
+	FRC(P.amb.resize(P.cap)); FRC(P.arank.resize(P.cap));
+	FRC(P.hpos.resize(P.cap)); FRC(P.hseg.resize(P.cap));
+	FRC(P.seg.resize(P.cap)); FRC(P.ord.resize(P.cap)); FRC(P.ord2.resize(P.cap));
+	FRC(P.hdr_flag.resize(P.cap)); FRC(P.hole_flag.resize(P.cap)); FRC(P.t.resize(P.cap));
+	FRC(P.ctl.resize(1));
 	{   // one temporary buffer for every scan and select of a chunk
 		size_t b1 = 0, b2 = 0, b3 = 0, b4 = 0;
 		const uint32_t N = (uint32_t)P.cap;
-		FCK(rocprim::inclusive_scan(nullptr, b1, rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), ls_flag{P.d_b}), P.lid, (size_t)N, rocprim::plus<uint32_t>(), P.st));
-		FCK(rocprim::inclusive_scan(nullptr, b2, P.ord, P.ord2, (size_t)N, ord_op(), P.st));
-		FCK(rocprim::inclusive_scan(nullptr, b3, P.klen, P.lend, (size_t)N, rocprim::plus<uint32_t>(), P.st));
-		FCK(rocprim::select(nullptr, b4, rocprim::counting_iterator<uint32_t>(0), P.hole_flag, P.hpos, &P.ctl->n_holes, (size_t)N, P.st));
+		FCK(rocprim::inclusive_scan(nullptr, b1, rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), ls_flag{P.d_b.p}), P.lid.p, (size_t)N, rocprim::plus<uint32_t>(), P.st));
+		FCK(rocprim::inclusive_scan(nullptr, b2, P.ord.p, P.ord2.p, (size_t)N, ord_op(), P.st));
+		FCK(rocprim::inclusive_scan(nullptr, b3, P.klen.p, P.lend.p, (size_t)N, rocprim::plus<uint32_t>(), P.st));
+		FCK(rocprim::select(nullptr, b4, rocprim::counting_iterator<uint32_t>(0), P.hole_flag.p, P.hpos.p, &P.ctl.p->n_holes, (size_t)N, P.st));
 		tb = std::max(std::max(b1, b2), std::max(b3, b4));
-		P.tmp_bytes = tb;
-		FCK(hipMalloc(&P.tmp, tb));
+		FRC(P.tmp.resize(tb));
 	}
 	{   // the .pac grows as needed; a plain file bounds it
 		FILE *p = fopen(fa_path, "rb");
@@ -407,7 +405,7 @@ extern "C" int bmh_fasta_pack(const char *fa_path, size_t chunk_bytes, bmh_fasta
 	}
 	{
 		auto t0 = std::chrono::steady_clock::now();
-		int64_t r = src.read(P.h_buf[0], chunk_bytes);
+		int64_t r = src.read(P.h_buf[0].p, chunk_bytes);
 		S.read_seconds += secs(t0);
 		if (r < 0) { bmh_set_error("index_fasta: read error in %s", fa_path); rc = BMH_EINVAL; goto done; }
 		file_bytes += (uint64_t)r;
@@ -415,12 +413,12 @@ extern "C" int bmh_fasta_pack(const char *fa_path, size_t chunk_bytes, bmh_fasta
 		eof = (size_t)r < chunk_bytes;
 	}
 	for (;;) {
-		uint8_t *hb = P.h_buf[cur];
+		uint8_t *hb = P.h_buf[cur].p;
 		const size_t len = hold;
 		// the next chunk is read while this one is packed; it starts with this one's last byte
 		bool next_eof = true;
 		if (!eof) {
-			uint8_t *nb = P.h_buf[cur ^ 1];
+			uint8_t *nb = P.h_buf[cur ^ 1].p;
 			nb[0] = hb[len - 1];
 			pending = std::async(std::launch::async, [&src, nb, chunk_bytes]() { return src.read(nb + 1, chunk_bytes); });
 			next_eof = false;
@@ -433,36 +431,36 @@ extern "C" int bmh_fasta_pack(const char *fa_path, size_t chunk_bytes, bmh_fasta
 		}
 		if (started && off < n) {
 			const uint32_t nn = (uint32_t)(n - off);
-			const uint8_t *db = P.d_b + off;
+			const uint8_t *db = P.d_b.p + off;
 			const uint64_t P0 = l_pac, A0 = n_amb;
 			auto t0 = std::chrono::steady_clock::now();
-			FCK(hipMemcpyAsync(P.d_b, hb, len, hipMemcpyHostToDevice, P.st));
+			FCK(hipMemcpyAsync(P.d_b.p, hb, len, hipMemcpyHostToDevice, P.st));
 			FCK(hipStreamSynchronize(P.st));
 			S.h2d_seconds += secs(t0);
 			t0 = std::chrono::steady_clock::now();
-			FCK(hipMemsetAsync(P.ctl, 0, sizeof(ctl_t), P.st));
+			FCK(hipMemsetAsync(P.ctl.p, 0, sizeof(ctl_t), P.st));
 			size_t b = tb;
-			FCK(rocprim::inclusive_scan(P.tmp, b, rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), ls_flag{db}), P.lid, (size_t)nn, rocprim::plus<uint32_t>(), P.st));
+			FCK(rocprim::inclusive_scan(P.tmp.p, b, rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), ls_flag{db}), P.lid.p, (size_t)nn, rocprim::plus<uint32_t>(), P.st));
 			const uint32_t g_n = (nn + 255) / 256;
-			fp_seg_starts<<<g_n, 256, 0, P.st>>>(db, nn, P.lid, P.L);
-			FCK(hipMemcpyAsync(&P.h_ctl->m, P.lid + nn - 1, 4, hipMemcpyDeviceToHost, P.st));
+			fp_seg_starts<<<g_n, 256, 0, P.st>>>(db, nn, P.lid.p, P.L.p);
+			FCK(hipMemcpyAsync(&P.h_ctl.p->m, P.lid.p + nn - 1, 4, hipMemcpyDeviceToHost, P.st));
 			FCK(hipStreamSynchronize(P.st));
-			const uint32_t m = P.h_ctl->m, g_m = (m + 255) / 256;
-			fp_seg_kind<<<g_m, 256, 0, P.st>>>(db, m, P.L, at_ls, (int)carry_kind, P.seg, P.ord, P.hdr_flag, P.ctl);
+			const uint32_t m = P.h_ctl.p->m, g_m = (m + 255) / 256;
+			fp_seg_kind<<<g_m, 256, 0, P.st>>>(db, m, P.L.p, at_ls, (int)carry_kind, P.seg.p, P.ord.p, P.hdr_flag.p, P.ctl.p);
 			b = tb;
-			FCK(rocprim::inclusive_scan(P.tmp, b, P.ord, P.ord2, (size_t)m, ord_op(), P.st));
-			fp_seg_klen<<<g_m, 256, 0, P.st>>>(db, nn, m, eof ? 1 : 0, carry_ord, P.L, P.seg, P.ord2, P.klen, P.ctl);
+			FCK(rocprim::inclusive_scan(P.tmp.p, b, P.ord.p, P.ord2.p, (size_t)m, ord_op(), P.st));
+			fp_seg_klen<<<g_m, 256, 0, P.st>>>(db, nn, m, eof ? 1 : 0, carry_ord, P.L.p, P.seg.p, P.ord2.p, P.klen.p, P.ctl.p);
 			b = tb;
-			FCK(rocprim::inclusive_scan(P.tmp, b, P.klen, P.lend, (size_t)m, rocprim::plus<uint32_t>(), P.st));
-			fp_seg_loff<<<g_m, 256, 0, P.st>>>(m, P.seg, P.lend, P.ctl);
-			fp_scatter<<<g_n, 256, 0, P.st>>>(db, nn, P.lid, P.seg, P.t, P.ctl);
+			FCK(rocprim::inclusive_scan(P.tmp.p, b, P.klen.p, P.lend.p, (size_t)m, rocprim::plus<uint32_t>(), P.st));
+			fp_seg_loff<<<g_m, 256, 0, P.st>>>(m, P.seg.p, P.lend.p, P.ctl.p);
+			fp_scatter<<<g_n, 256, 0, P.st>>>(db, nn, P.lid.p, P.seg.p, P.t.p, P.ctl.p);
 			b = tb;
-			FCK(rocprim::select(P.tmp, b, rocprim::counting_iterator<uint32_t>(0), P.hdr_flag, P.hseg, &P.ctl->n_hdr, (size_t)m, P.st));
-			FCK(hipMemcpyAsync(P.h_ctl, P.ctl, sizeof(ctl_t), hipMemcpyDeviceToHost, P.st));
+			FCK(rocprim::select(P.tmp.p, b, rocprim::counting_iterator<uint32_t>(0), P.hdr_flag.p, P.hseg.p, &P.ctl.p->n_hdr, (size_t)m, P.st));
+			FCK(hipMemcpyAsync(P.h_ctl.p, P.ctl.p, sizeof(ctl_t), hipMemcpyDeviceToHost, P.st));
 			FCK(hipStreamSynchronize(P.st));
-			const uint32_t nk = P.h_ctl->n_kept;
-			if (P.h_ctl->err & ERR_FASTQ) { bmh_set_error("index_fasta: %s has a '+' line: FASTQ references are not indexed", fa_path); rc = BMH_EINVAL; goto done; }
-			if (P.h_ctl->err & ERR_BYTE) { bmh_set_error("index_fasta: %s has a sequence byte 0 or >= 128", fa_path); rc = BMH_EINVAL; goto done; }
+			const uint32_t nk = P.h_ctl.p->n_kept;
+			if (P.h_ctl.p->err & ERR_FASTQ) { bmh_set_error("index_fasta: %s has a '+' line: FASTQ references are not indexed", fa_path); rc = BMH_EINVAL; goto done; }
+			if (P.h_ctl.p->err & ERR_BYTE) { bmh_set_error("index_fasta: %s has a sequence byte 0 or >= 128", fa_path); rc = BMH_EINVAL; goto done; }
 			if (nk) {
 				const uint64_t need = (P0 + nk + 3) / 4 + 64;
 				if (need > P.pac_cap) {
@@ -476,37 +474,35 @@ extern "C" int bmh_fasta_pack(const char *fa_path, size_t chunk_bytes, bmh_fasta
 					P.d_pac = np; P.pac_cap = nc;
 				}
 				const uint32_t g_k = (nk + 255) / 256;
-				fp_flags<<<g_k, 256, 0, P.st>>>(P.t, nk, carry_prev, P.amb, P.hole_flag, P.ctl);
+				fp_flags<<<g_k, 256, 0, P.st>>>(P.t.p, nk, carry_prev, P.amb.p, P.hole_flag.p, P.ctl.p);
 				b = tb;
-				FCK(rocprim::inclusive_scan(P.tmp, b, P.amb, P.arank, (size_t)nk, rocprim::plus<uint32_t>(), P.st));
+				FCK(rocprim::inclusive_scan(P.tmp.p, b, P.amb.p, P.arank.p, (size_t)nk, rocprim::plus<uint32_t>(), P.st));
 				const uint64_t nq = ((P0 + nk - 1) >> 2) - (P0 >> 2) + 1;
-				fp_pack<<<(uint32_t)((nq + 255) / 256), 256, 0, P.st>>>(P.t, P.arank, nk, P0, A0, P.d_pac);
+				fp_pack<<<(uint32_t)((nq + 255) / 256), 256, 0, P.st>>>(P.t.p, P.arank.p, nk, P0, A0, P.d_pac);
 				b = tb;
-				FCK(rocprim::select(P.tmp, b, rocprim::counting_iterator<uint32_t>(0), P.hole_flag, P.hpos, &P.ctl->n_holes, (size_t)nk, P.st));
-				FCK(hipMemcpyAsync(&P.ctl->n_amb, P.arank + nk - 1, 4, hipMemcpyDeviceToDevice, P.st));
+				FCK(rocprim::select(P.tmp.p, b, rocprim::counting_iterator<uint32_t>(0), P.hole_flag.p, P.hpos.p, &P.ctl.p->n_holes, (size_t)nk, P.st));
+				FCK(hipMemcpyAsync(&P.ctl.p->n_amb, P.arank.p + nk - 1, 4, hipMemcpyDeviceToDevice, P.st));
 			}
-			FCK(hipMemcpyAsync(P.h_ctl, P.ctl, sizeof(ctl_t), hipMemcpyDeviceToHost, P.st));
+			FCK(hipMemcpyAsync(P.h_ctl.p, P.ctl.p, sizeof(ctl_t), hipMemcpyDeviceToHost, P.st));
 			FCK(hipStreamSynchronize(P.st));
 			{
-				const ctl_t c = *P.h_ctl;
+				const ctl_t c = *P.h_ctl.p;
 				const uint32_t nh = std::max(c.n_holes, c.n_hdr);
 				if (nh) {
 					// small tables (holes and headers are few): they grow with the largest count seen
-					if (nh > P.tab_cap) {
-						if (P.holes) { (void)hipFree(P.holes); (void)hipFree(P.hdrs); (void)hipHostFree(P.h_holes); (void)hipHostFree(P.h_hdrs); }
-						P.holes = nullptr; P.hdrs = nullptr; P.h_holes = nullptr; P.h_hdrs = nullptr;
-						P.tab_cap = std::max(nh, 2 * P.tab_cap);
-						const size_t nh = P.tab_cap;
-						FCK(hipMalloc((void **)&P.holes, (size_t)nh * sizeof(hole_dev_t))); FCK(hipMalloc((void **)&P.hdrs, (size_t)nh * sizeof(hdr_dev_t)));
-						FCK(hipHostMalloc((void **)&P.h_holes, (size_t)nh * sizeof(hole_dev_t))); FCK(hipHostMalloc((void **)&P.h_hdrs, (size_t)nh * sizeof(hdr_dev_t)));
+					if (nh > P.h_hdrs.cap) {              // (the last of the four to grow)
+						const size_t tab_cap = std::max<size_t>(nh, 2 * P.h_hdrs.cap);
+						P.holes.drop(); P.hdrs.drop(); P.h_holes.drop(); P.h_hdrs.drop();
+						FRC(P.holes.resize(tab_cap)); FRC(P.hdrs.resize(tab_cap));
+						FRC(P.h_holes.resize(tab_cap)); FRC(P.h_hdrs.resize(tab_cap));
 					}
-					fp_gather<<<(nh + 255) / 256, 256, 0, P.st>>>(P.t, P.arank, P.hpos, P.seg, P.hseg, P.ctl, P0, A0, P.holes, P.hdrs);
-					if (c.n_holes) FCK(hipMemcpyAsync(P.h_holes, P.holes, (size_t)c.n_holes * sizeof(hole_dev_t), hipMemcpyDeviceToHost, P.st));
-					if (c.n_hdr) FCK(hipMemcpyAsync(P.h_hdrs, P.hdrs, (size_t)c.n_hdr * sizeof(hdr_dev_t), hipMemcpyDeviceToHost, P.st));
+					fp_gather<<<(nh + 255) / 256, 256, 0, P.st>>>(P.t.p, P.arank.p, P.hpos.p, P.seg.p, P.hseg.p, P.ctl.p, P0, A0, P.holes.p, P.hdrs.p);
+					if (c.n_holes) FCK(hipMemcpyAsync(P.h_holes.p, P.holes.p, (size_t)c.n_holes * sizeof(hole_dev_t), hipMemcpyDeviceToHost, P.st));
+					if (c.n_hdr) FCK(hipMemcpyAsync(P.h_hdrs.p, P.hdrs.p, (size_t)c.n_hdr * sizeof(hdr_dev_t), hipMemcpyDeviceToHost, P.st));
 					FCK(hipStreamSynchronize(P.st));
 				}
 				S.pack_seconds += secs(t0);
-				for (uint32_t h = 0; h < c.n_holes; ++h) { hole_off.push_back(P.h_holes[h].off); hole_rank.push_back(P.h_holes[h].rank); hole_ch.push_back((uint8_t)P.h_holes[h].ch); }
+				for (uint32_t h = 0; h < c.n_holes; ++h) { hole_off.push_back(P.h_holes.p[h].off); hole_rank.push_back(P.h_holes.p[h].rank); hole_ch.push_back((uint8_t)P.h_holes.p[h].ch); }
 				// header text from the pinned chunk: an open one continues at the chunk's start
 				const uint8_t *cb = hb + off;
 				auto take = [&](uint32_t from) {
@@ -518,9 +514,9 @@ extern "C" int bmh_fasta_pack(const char *fa_path, size_t chunk_bytes, bmh_fasta
 				if (hdr_open) take(0);
 				for (uint32_t h = 0; h < c.n_hdr; ++h) {
 					hdr = header_t();
-					hdr.offset = P0 + P.h_hdrs[h].loff;
+					hdr.offset = P0 + P.h_hdrs.p[h].loff;
 					hdr_open = true;
-					take(P.h_hdrs[h].start + 1);
+					take(P.h_hdrs.p[h].start + 1);
 				}
 				if (m) { carry_kind = c.last_kind; carry_ord = c.last_ord; }
 				if (nk) carry_prev = c.last_prev;

@@ -34,9 +34,9 @@
 #include <string.h>
 #include <chrono>
 #include <vector>
+#define BMH_CK_PREFIX "index build: "
 #include "bmh_internal.h"
-
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("index build: %s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
+#include "devmem.h"
 
 typedef unsigned long long u64;
 
@@ -295,9 +295,8 @@ __global__ void __launch_bounds__(256) ib_verify_kernel(const u64 *__restrict__ 
 static inline unsigned ib_nblk(u64 n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 struct ib_bufs_t {
-	u64 *tw = nullptr, *SA = nullptr, *ISA = nullptr, *U = nullptr, *kA = nullptr, *kB = nullptr, *vA = nullptr, *vB = nullptr, *small = nullptr;
-	uint32_t *h1 = nullptr, *h2 = nullptr; uint8_t *uf = nullptr; void *tmp = nullptr; cnt4_t *cnt = nullptr, *occ = nullptr;
-	~ib_bufs_t() { void *ps[] = {tw, SA, ISA, U, kA, kB, vA, vB, small, h1, h2, uf, tmp, cnt, occ}; for (void *p : ps) if (p) (void)hipFree(p); }
+	dev_buf<u64> tw, SA, ISA, U, kA, kB, vA, vB, small;
+	dev_buf<uint32_t> h1, h2; dev_buf<uint8_t> uf, tmp; dev_buf<cnt4_t> cnt, occ;
 };
 
 extern "C" int bmh_index_build(const uint8_t *d_pac, uint64_t l_pac, int sa_intv, uint32_t *d_bwt_words, uint32_t *d_sa, uint32_t *d_sa_bits,
@@ -318,24 +317,24 @@ extern "C" int bmh_index_build(const uint8_t *d_pac, uint64_t l_pac, int sa_intv
 	hipStream_t st = nullptr;
 	ib_bufs_t B;
 	const u64 n_tw = n / 32 + 3;
-	HIPCK(hipMalloc((void **)&B.tw, n_tw * 8)); HIPCK(hipMalloc((void **)&B.SA, n * 8)); HIPCK(hipMalloc((void **)&B.ISA, n * 8));
-	HIPCK(hipMalloc((void **)&B.U, n * 8));
-	HIPCK(hipMalloc((void **)&B.kA, CAP * 8)); HIPCK(hipMalloc((void **)&B.kB, CAP * 8)); HIPCK(hipMalloc((void **)&B.vA, CAP * 8)); HIPCK(hipMalloc((void **)&B.vB, CAP * 8));
-	HIPCK(hipMalloc((void **)&B.h1, CAP * 4)); HIPCK(hipMalloc((void **)&B.h2, CAP * 4)); HIPCK(hipMalloc((void **)&B.uf, CAP));
-	HIPCK(hipMalloc((void **)&B.small, (IB_N_BUCKETS + 16) * 8));
+	RCK(B.tw.resize(n_tw)); RCK(B.SA.resize(n)); RCK(B.ISA.resize(n));
+	RCK(B.U.resize(n));
+	RCK(B.kA.resize(CAP)); RCK(B.kB.resize(CAP)); RCK(B.vA.resize(CAP)); RCK(B.vB.resize(CAP));
+	RCK(B.h1.resize(CAP)); RCK(B.h2.resize(CAP)); RCK(B.uf.resize(CAP));
+	RCK(B.small.resize(IB_N_BUCKETS + 16));
 	size_t t_sort = 0, t_scan = 0, t_sel = 0;
-	HIPCK(rocprim::radix_sort_pairs(nullptr, t_sort, B.kA, B.kB, B.vA, B.vB, (size_t)CAP, 0, 64, st));
-	HIPCK(rocprim::inclusive_scan(nullptr, t_scan, B.h1, B.h2, (size_t)CAP, rocprim::maximum<uint32_t>(), st));
-	HIPCK(rocprim::select(nullptr, t_sel, rocprim::counting_iterator<u64>(0), B.uf, B.kA, B.small, (size_t)CAP, st));
+	HIPCK(rocprim::radix_sort_pairs(nullptr, t_sort, B.kA.p, B.kB.p, B.vA.p, B.vB.p, (size_t)CAP, 0, 64, st));
+	HIPCK(rocprim::inclusive_scan(nullptr, t_scan, B.h1.p, B.h2.p, (size_t)CAP, rocprim::maximum<uint32_t>(), st));
+	HIPCK(rocprim::select(nullptr, t_sel, rocprim::counting_iterator<u64>(0), B.uf.p, B.kA.p, B.small.p, (size_t)CAP, st));
 	size_t tmp_bytes = std::max(t_sort, std::max(t_scan, t_sel)) + 256;
-	HIPCK(hipMalloc(&B.tmp, tmp_bytes));
+	RCK(B.tmp.resize(tmp_bytes));
 
-	ib_text_kernel<<<ib_nblk(n_tw, 256), 256, 0, st>>>(d_pac, l_pac, n_tw, B.tw);
+	ib_text_kernel<<<ib_nblk(n_tw, 256), 256, 0, st>>>(d_pac, l_pac, n_tw, B.tw.p);
 	HIPCK(hipGetLastError());
 	// ---- round 0
-	u64 *d_hist = B.small, *d_cursor = B.small + IB_N_BUCKETS, *d_count = B.small + IB_N_BUCKETS + 1, *d_gs = B.small + IB_N_BUCKETS + 2;
-	HIPCK(hipMemsetAsync(B.small, 0, (IB_N_BUCKETS + 16) * 8, st));
-	ib_hist_kernel<<<4096, 256, 0, st>>>(B.tw, n, d_hist);
+	u64 *d_hist = B.small.p, *d_cursor = B.small.p + IB_N_BUCKETS, *d_count = B.small.p + IB_N_BUCKETS + 1, *d_gs = B.small.p + IB_N_BUCKETS + 2;
+	HIPCK(hipMemsetAsync(B.small.p, 0, (IB_N_BUCKETS + 16) * 8, st));
+	ib_hist_kernel<<<4096, 256, 0, st>>>(B.tw.p, n, d_hist);
 	HIPCK(hipGetLastError());
 	std::vector<u64> hist(IB_N_BUCKETS);
 	HIPCK(hipMemcpy(hist.data(), d_hist, IB_N_BUCKETS * 8, hipMemcpyDeviceToHost));
@@ -347,18 +346,18 @@ extern "C" int bmh_index_build(const uint8_t *d_pac, uint64_t l_pac, int sa_intv
 		if (bhi == blo) { bmh_set_error("bmh_index_build: %llu suffixes share their first 6 symbols, more than the chunk capacity %llu (raise BMH_BUILD_CAP_LOG2)", hist[blo], CAP); return BMH_ECAPACITY; }
 		if (m) {
 			HIPCK(hipMemsetAsync(d_cursor, 0, 8, st));
-			ib_collect_kernel<<<8192, 256, 0, st>>>(B.tw, n, blo, bhi, B.kA, B.vA, d_cursor);
+			ib_collect_kernel<<<8192, 256, 0, st>>>(B.tw.p, n, blo, bhi, B.kA.p, B.vA.p, d_cursor);
 			HIPCK(hipGetLastError());
 			size_t tb = tmp_bytes;
-			HIPCK(rocprim::radix_sort_pairs(B.tmp, tb, B.kA, B.kB, B.vA, B.vB, (size_t)m, 0, 64, st));
-			ib_headmark_kernel<<<ib_nblk(m, 256), 256, 0, st>>>(B.kB, m, B.h1);
+			HIPCK(rocprim::radix_sort_pairs(B.tmp.p, tb, B.kA.p, B.kB.p, B.vA.p, B.vB.p, (size_t)m, 0, 64, st));
+			ib_headmark_kernel<<<ib_nblk(m, 256), 256, 0, st>>>(B.kB.p, m, B.h1.p);
 			HIPCK(hipGetLastError());
 			tb = tmp_bytes;
-			HIPCK(rocprim::inclusive_scan(B.tmp, tb, B.h1, B.h2, (size_t)m, rocprim::maximum<uint32_t>(), st));
-			ib_finish0_kernel<<<ib_nblk(m, 256), 256, 0, st>>>(B.kB, B.vB, B.h2, m, base, B.SA, B.ISA, B.uf);
+			HIPCK(rocprim::inclusive_scan(B.tmp.p, tb, B.h1.p, B.h2.p, (size_t)m, rocprim::maximum<uint32_t>(), st));
+			ib_finish0_kernel<<<ib_nblk(m, 256), 256, 0, st>>>(B.kB.p, B.vB.p, B.h2.p, m, base, B.SA.p, B.ISA.p, B.uf.p);
 			HIPCK(hipGetLastError());
 			tb = tmp_bytes;
-			HIPCK(rocprim::select(B.tmp, tb, rocprim::counting_iterator<u64>(base), B.uf, B.U + n_unres, d_count, (size_t)m, st));
+			HIPCK(rocprim::select(B.tmp.p, tb, rocprim::counting_iterator<u64>(base), B.uf.p, B.U.p + n_unres, d_count, (size_t)m, st));
 			u64 cnt = 0;
 			HIPCK(hipMemcpy(&cnt, d_count, 8, hipMemcpyDeviceToHost));
 			n_unres += cnt; base += m; ++n_pass;
@@ -376,32 +375,32 @@ extern "C" int bmh_index_build(const uint8_t *d_pac, uint64_t l_pac, int sa_intv
 		for (u64 cs = 0; cs < n_unres;) {
 			u64 ce = std::min(cs + CAP, n_unres);
 			if (ce < n_unres) {
-				ib_group_start_kernel<<<1, 1, 0, st>>>(B.U, ce, B.SA, B.ISA, d_gs);
+				ib_group_start_kernel<<<1, 1, 0, st>>>(B.U.p, ce, B.SA.p, B.ISA.p, d_gs);
 				HIPCK(hipGetLastError());
 				HIPCK(hipMemcpy(&ce, d_gs, 8, hipMemcpyDeviceToHost));
 				if (ce <= cs) { bmh_set_error("bmh_index_build: a group of equal %llu-symbol prefixes exceeds the chunk capacity %llu (raise BMH_BUILD_CAP_LOG2)", h, CAP); return BMH_ECAPACITY; }
 			}
 			const u64 m = ce - cs;
-			const u64 *Uc = B.U + cs;
-			ib_dkey_kernel<<<ib_nblk(m, 256), 256, 0, st>>>(Uc, m, B.SA, B.ISA, n, h, B.kA, B.vA, B.h1);
+			const u64 *Uc = B.U.p + cs;
+			ib_dkey_kernel<<<ib_nblk(m, 256), 256, 0, st>>>(Uc, m, B.SA.p, B.ISA.p, n, h, B.kA.p, B.vA.p, B.h1.p);
 			HIPCK(hipGetLastError());
 			size_t tb = tmp_bytes;
-			HIPCK(rocprim::inclusive_scan(B.tmp, tb, B.h1, B.h2, (size_t)m, rocprim::plus<uint32_t>(), st));
-			ib_dseg_kernel<<<ib_nblk(m, 256), 256, 0, st>>>(B.kA, B.h2, m);
+			HIPCK(rocprim::inclusive_scan(B.tmp.p, tb, B.h1.p, B.h2.p, (size_t)m, rocprim::plus<uint32_t>(), st));
+			ib_dseg_kernel<<<ib_nblk(m, 256), 256, 0, st>>>(B.kA.p, B.h2.p, m);
 			HIPCK(hipGetLastError());
 			tb = tmp_bytes;
-			HIPCK(rocprim::radix_sort_pairs(B.tmp, tb, B.kA, B.kB, B.vA, B.vB, (size_t)m, 0, 64, st));
-			ib_headmark_kernel<<<ib_nblk(m, 256), 256, 0, st>>>(B.kB, m, B.h1);
+			HIPCK(rocprim::radix_sort_pairs(B.tmp.p, tb, B.kA.p, B.kB.p, B.vA.p, B.vB.p, (size_t)m, 0, 64, st));
+			ib_headmark_kernel<<<ib_nblk(m, 256), 256, 0, st>>>(B.kB.p, m, B.h1.p);
 			HIPCK(hipGetLastError());
 			tb = tmp_bytes;
-			HIPCK(rocprim::inclusive_scan(B.tmp, tb, B.h1, B.h2, (size_t)m, rocprim::maximum<uint32_t>(), st));
-			ib_dfinish_kernel<<<ib_nblk(m, 256), 256, 0, st>>>(Uc, B.kB, B.vB, B.h2, m, B.SA, B.ISA, B.uf);
+			HIPCK(rocprim::inclusive_scan(B.tmp.p, tb, B.h1.p, B.h2.p, (size_t)m, rocprim::maximum<uint32_t>(), st));
+			ib_dfinish_kernel<<<ib_nblk(m, 256), 256, 0, st>>>(Uc, B.kB.p, B.vB.p, B.h2.p, m, B.SA.p, B.ISA.p, B.uf.p);
 			HIPCK(hipGetLastError());
 			tb = tmp_bytes;
-			HIPCK(rocprim::select(B.tmp, tb, Uc, B.uf, B.kA, d_count, (size_t)m, st));        // survivors -> kA, then behind the write cursor of U
+			HIPCK(rocprim::select(B.tmp.p, tb, Uc, B.uf.p, B.kA.p, d_count, (size_t)m, st));        // survivors -> kA, then behind the write cursor of U
 			u64 cnt = 0;
 			HIPCK(hipMemcpy(&cnt, d_count, 8, hipMemcpyDeviceToHost));
-			if (cnt) HIPCK(hipMemcpyAsync(B.U + wcur, B.kA, cnt * 8, hipMemcpyDeviceToDevice, st));
+			if (cnt) HIPCK(hipMemcpyAsync(B.U.p + wcur, B.kA.p, cnt * 8, hipMemcpyDeviceToDevice, st));
 			wcur += cnt;
 			cs = ce;
 		}
@@ -410,13 +409,13 @@ extern "C" int bmh_index_build(const uint8_t *d_pac, uint64_t l_pac, int sa_intv
 	}
 	if (stats) { stats->doubling_rounds = rounds; stats->sa_seconds = secs(); }
 	// the sort buffers are no longer needed: make room for the block counts
-	(void)hipFree(B.kA); (void)hipFree(B.kB); (void)hipFree(B.vA); (void)hipFree(B.vB); B.kA = B.kB = B.vA = B.vB = nullptr;
-	(void)hipFree(B.U); B.U = nullptr;
+	B.kA.drop(); B.kB.drop(); B.vA.drop(); B.vB.drop();
+	B.U.drop();
 	// ---- verification (optional)
 	if (flags & BMH_BUILD_VERIFY) {
-		u64 *d_err = B.small;
+		u64 *d_err = B.small.p;
 		HIPCK(hipMemsetAsync(d_err, 0, 16, st));
-		ib_verify_kernel<<<(unsigned)std::min<u64>(ib_nblk(n, 256), 1u << 20), 256, 0, st>>>(B.tw, B.SA, B.ISA, n, d_err);
+		ib_verify_kernel<<<(unsigned)std::min<u64>(ib_nblk(n, 256), 1u << 20), 256, 0, st>>>(B.tw.p, B.SA.p, B.ISA.p, n, d_err);
 		HIPCK(hipGetLastError());
 		u64 err[2] = {0, 0};
 		HIPCK(hipMemcpy(err, d_err, 16, hipMemcpyDeviceToHost));
@@ -426,25 +425,25 @@ extern "C" int bmh_index_build(const uint8_t *d_pac, uint64_t l_pac, int sa_intv
 	}
 	// ---- output: primary, BWT blocks + Occ, samples
 	u64 pos0 = 0;
-	HIPCK(hipMemcpy(&pos0, B.ISA, 8, hipMemcpyDeviceToHost));
+	HIPCK(hipMemcpy(&pos0, B.ISA.p, 8, hipMemcpyDeviceToHost));
 	const u64 primary = pos0 + 1;
-	(void)hipFree(B.ISA); B.ISA = nullptr;
+	B.ISA.drop();
 	const u64 n_blk = (n + 63) / 64;
-	HIPCK(hipMalloc((void **)&B.cnt, (n_blk + 1) * sizeof(cnt4_t))); HIPCK(hipMalloc((void **)&B.occ, (n_blk + 1) * sizeof(cnt4_t)));
+	RCK(B.cnt.resize(n_blk + 1)); RCK(B.occ.resize(n_blk + 1));
 	HIPCK(hipMemsetAsync(d_bwt_words, 0, (n_blk + 1) * 32, st));
-	HIPCK(hipMemsetAsync(B.cnt + n_blk, 0, sizeof(cnt4_t), st));
-	ib_bwt_kernel<<<16384, 256, 0, st>>>(B.tw, B.SA, n, primary, n_blk, d_bwt_words, B.cnt);
+	HIPCK(hipMemsetAsync(B.cnt.p + n_blk, 0, sizeof(cnt4_t), st));
+	ib_bwt_kernel<<<16384, 256, 0, st>>>(B.tw.p, B.SA.p, n, primary, n_blk, d_bwt_words, B.cnt.p);
 	HIPCK(hipGetLastError());
 	{
 		size_t tb = 0; cnt4_t zero = {{0, 0, 0, 0}};
-		HIPCK(rocprim::exclusive_scan(nullptr, tb, B.cnt, B.occ, zero, (size_t)n_blk + 1, cnt4_plus(), st));
-		if (tb > tmp_bytes) { (void)hipFree(B.tmp); B.tmp = nullptr; HIPCK(hipMalloc(&B.tmp, tb)); tmp_bytes = tb; }
-		HIPCK(rocprim::exclusive_scan(B.tmp, tb, B.cnt, B.occ, zero, (size_t)n_blk + 1, cnt4_plus(), st));
+		HIPCK(rocprim::exclusive_scan(nullptr, tb, B.cnt.p, B.occ.p, zero, (size_t)n_blk + 1, cnt4_plus(), st));
+		if (tb > tmp_bytes) { RCK(B.tmp.resize(tb)); tmp_bytes = tb; }
+		HIPCK(rocprim::exclusive_scan(B.tmp.p, tb, B.cnt.p, B.occ.p, zero, (size_t)n_blk + 1, cnt4_plus(), st));
 	}
-	ib_occ_kernel<<<ib_nblk(n_blk + 1, 256), 256, 0, st>>>(B.occ, n_blk + 1, d_bwt_words);
+	ib_occ_kernel<<<ib_nblk(n_blk + 1, 256), 256, 0, st>>>(B.occ.p, n_blk + 1, d_bwt_words);
 	HIPCK(hipGetLastError());
 	cnt4_t tot;
-	HIPCK(hipMemcpy(&tot, B.occ + n_blk, sizeof(tot), hipMemcpyDeviceToHost));
+	HIPCK(hipMemcpy(&tot, B.occ.p + n_blk, sizeof(tot), hipMemcpyDeviceToHost));
 	// per-symbol counts above 2^32 would have wrapped in the 32-bit Occ columns of this layout: recount in 64 bits from the histogram
 	u64 c64[4] = {0, 0, 0, 0};
 	for (unsigned b = 0; b < IB_N_BUCKETS; ++b) c64[b >> (IB_BUCKET_BITS - 2)] += hist[b];
@@ -458,7 +457,7 @@ extern "C" int bmh_index_build(const uint8_t *d_pac, uint64_t l_pac, int sa_intv
 	while ((1 << shift) < sa_intv) ++shift;
 	const u64 n_sa = (n + (u64)sa_intv) / (u64)sa_intv;
 	HIPCK(hipMemsetAsync(d_sa_bits, 0, (n_sa / 32 + 1) * 4, st));
-	ib_sample_kernel<<<(unsigned)std::min<u64>(ib_nblk(n_sa, 256), 1u << 20), 256, 0, st>>>(B.SA, n_sa, shift, (n >> 32) & 1, d_sa, d_sa_bits);
+	ib_sample_kernel<<<(unsigned)std::min<u64>(ib_nblk(n_sa, 256), 1u << 20), 256, 0, st>>>(B.SA.p, n_sa, shift, (n >> 32) & 1, d_sa, d_sa_bits);
 	HIPCK(hipGetLastError());
 	HIPCK(hipStreamSynchronize(st));
 	HIPCK(hipGetLastError());

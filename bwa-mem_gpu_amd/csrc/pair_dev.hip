@@ -18,9 +18,8 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include "bmh_internal.h"
+#include "devmem.h"
 #include "regs_core.h"
-
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
 
 #define PD_NMAX 64          // hits of a pair's two reads together the kernel takes (a lane's private arrays)
 
@@ -319,12 +318,7 @@ int bmh_pair_merge_records(uint32_t n_reads, const int32_t *d_slot, const int32_
 }
 
 // an exclusive scan of n words for the callers above (d_tmp: bmh_pair_scan_bytes(n) bytes of device memory)
-size_t bmh_pair_scan_bytes(uint32_t n)
-{
-	size_t t = 0;
-	(void)rocprim::exclusive_scan(nullptr, t, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), 0);
-	return t + 256;
-}
+size_t bmh_pair_scan_bytes(uint32_t n) { return scan_tmp_bytes<uint32_t, uint32_t>((size_t)n + 1); }
 int bmh_pair_scan(const uint32_t *d_in, uint32_t *d_out, uint32_t n, void *d_tmp, size_t tmp_bytes, void *stream)
 {
 	if (n == 0) return BMH_OK;

@@ -15,15 +15,11 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <map>
-#include <mutex>
 #include <type_traits>
-#include <utility>
 #include "bmh_internal.h"
+#include "devmem.h"
 #include "local_sw.h"
 #include "pair_kernels.h"
-
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
 
 #define MSW_SLEN 40            // segments per lane the kernel keeps in LDS: queries up to 16 * 40 columns in byte mode (which ends at 249), 8 * 40 = 320 in 16-bit mode
 #define MSW_JOBS_PER_BLOCK 8   // 128 threads
@@ -558,30 +554,19 @@ template <int PASS> __global__ void __launch_bounds__(64) rescue_jobs_kernel(rj_
 
 // ---- host side
 struct msw_scratch_t {
-	bmh_msw_job_t *d_jobs; int32_t *d_out; uint32_t *d_bl; size_t cap_jobs, cap_bl;
-	// the rescue's windows found on the device
-	uint32_t *d_cnt, *d_blw, *d_stat; uint8_t *d_active; bmh_msw_key_t *d_keys; void *d_scan; size_t cap_pairs, cap_keys, cap_scan;
-	uint32_t rj_n_jobs, rj_cap; uint64_t rj_bl; bool rj_byte_all; rj_args_t rj;
+	dev_buf<bmh_msw_job_t> d_jobs; dev_buf<int32_t[7]> d_out; dev_buf<uint32_t> d_bl;      // d_jobs and d_out grow together
+	// the rescue's windows found on the device (d_cnt, d_blw, d_active grow together)
+	dev_buf<uint32_t> d_cnt, d_blw, d_stat; dev_buf<uint8_t> d_active; dev_buf<bmh_msw_key_t> d_keys; dev_buf<uint8_t> d_scan;
+	uint32_t rj_n_jobs = 0, rj_cap = 0; uint64_t rj_bl = 0; bool rj_byte_all = false; rj_args_t rj = {};
 };
-static std::mutex g_msw_mu;
-static std::map<std::pair<int, void *>, msw_scratch_t *> g_msw_map;
+static stream_scratch<msw_scratch_t> g_msw_reg;
 
 // the (device, stream) scratch of bmh_matesw_batch_device / bmh_rescue_*_device: freed when the caller retires the stream (stream idle, its device current)
 extern "C" void bmh_matesw_release(void *stream_)
 {
 	int dev = 0;
 	if (hipGetDevice(&dev) != hipSuccess) return;
-	msw_scratch_t *S = nullptr;
-	{
-		std::lock_guard<std::mutex> lk(g_msw_mu);
-		auto it = g_msw_map.find(std::make_pair(dev, stream_));
-		if (it == g_msw_map.end()) return;
-		S = it->second;
-		g_msw_map.erase(it);
-	}
-	void *ps[] = {S->d_jobs, S->d_out, S->d_bl, S->d_cnt, S->d_blw, S->d_stat, S->d_active, S->d_keys, S->d_scan};
-	for (void *q : ps) if (q) (void)hipFree(q);
-	delete S;
+	g_msw_reg.take(dev, stream_);
 }
 
 // can the kernel take this job? (the host computes the others itself)
@@ -595,39 +580,24 @@ static int msw_scratch_of(void *stream_, msw_scratch_t **out)
 {
 	int dev = 0;
 	HIPCK(hipGetDevice(&dev));
-	std::lock_guard<std::mutex> lk(g_msw_mu);
-	auto key = std::make_pair(dev, stream_);
-	auto it = g_msw_map.find(key);
-	if (it == g_msw_map.end()) { *out = new msw_scratch_t(); memset((void *)*out, 0, sizeof(msw_scratch_t)); g_msw_map[key] = *out; }
-	else *out = it->second;
+	*out = &g_msw_reg.get(dev, stream_);
 	return BMH_OK;
 }
 static int msw_room(msw_scratch_t *S, uint64_t n_jobs, uint64_t bl)
 {
-	if (n_jobs > S->cap_jobs) {
-		if (S->d_jobs) (void)hipFree(S->d_jobs);
-		if (S->d_out) (void)hipFree(S->d_out);
-		S->d_jobs = nullptr; S->d_out = nullptr; S->cap_jobs = 0;
-		const size_t c = n_jobs + n_jobs / 4 + 1024;
-		HIPCK(hipMalloc((void **)&S->d_jobs, sizeof(bmh_msw_job_t) * c)); HIPCK(hipMalloc((void **)&S->d_out, sizeof(int32_t) * 7 * c));
-		S->cap_jobs = c;
+	if (n_jobs > S->d_out.cap) {                 // (the last of the two to grow: a growth that failed half way is done again)
+		S->d_jobs.drop(); S->d_out.drop();
+		RCK(S->d_jobs.need(n_jobs)); RCK(S->d_out.need(n_jobs));
 	}
-	if (bl > S->cap_bl) {
-		if (S->d_bl) (void)hipFree(S->d_bl);
-		S->d_bl = nullptr; S->cap_bl = 0;
-		const size_t c = bl + bl / 4 + 1024;
-		HIPCK(hipMalloc((void **)&S->d_bl, 4 * c));
-		S->cap_bl = c;
-	}
-	return BMH_OK;
+	return S->d_bl.need(bl);
 }
 // the jobs in S->d_jobs (bl_off set) -> S->d_out
 static int msw_launch(msw_scratch_t *S, const bmh_index_t *idx, const uint8_t *d_reads, const uint32_t *d_offs, const bmh_ext_params_t *ep, uint64_t n_jobs, int cap, bool byte_all, hipStream_t st)
 {
 	msw_args_t A;
-	A.jobs = S->d_jobs; A.n_jobs = (uint32_t)n_jobs; A.reads = d_reads; A.read_offs = d_offs; A.pac = idx->dev.pac; A.l_pac = (long long)idx->dev.l_pac;
+	A.jobs = S->d_jobs.p; A.n_jobs = (uint32_t)n_jobs; A.reads = d_reads; A.read_offs = d_offs; A.pac = idx->dev.pac; A.l_pac = (long long)idx->dev.l_pac;
 	A.a = ep->a; A.b = ep->b; A.o_del = ep->o_del; A.e_del = ep->e_del; A.o_ins = ep->o_ins; A.e_ins = ep->e_ins;
-	A.blist = S->d_bl; A.out = S->d_out;
+	A.blist = S->d_bl.p; A.out = S->d_out.as<int32_t>();
 	// the register form: every job in byte mode, columns of at most 16 segments, gap opens that cost something (its F is the plain recurrence only then)
 	const unsigned nblk = (unsigned)((n_jobs + MSW_JOBS_PER_BLOCK - 1) / MSW_JOBS_PER_BLOCK);
 	const bool reg_form = byte_all && cap <= 16 && ep->o_ins > 0 && ep->e_ins > 0 && ep->a < 100 && ep->b < 100 && bmh_tune("MSW_REG", 1) != 0;
@@ -647,17 +617,17 @@ extern "C" int bmh_matesw_batch_device(const bmh_index_t *idx, const uint8_t *d_
 	if (n_jobs >> 31) { bmh_set_error("bmh_matesw_batch_device: too many jobs"); return BMH_ECAPACITY; }
 	hipStream_t st = (hipStream_t)stream_;
 	msw_scratch_t *S;
-	{ const int rc = msw_scratch_of(stream_, &S); if (rc != BMH_OK) return rc; }
+	RCK(msw_scratch_of(stream_, &S));
 	uint64_t bl = 0;
 	int cap = 1;                                             // the longest lane-private column of the batch, in segments
 	bool byte_all = true;
 	for (uint64_t k = 0; k < n_jobs; ++k) { const int lanes = (jobs[k].xtra & BMH_SW_XBYTE) ? 16 : 8; const int sl = (jobs[k].l_ms + lanes - 1) / lanes; cap = sl > cap ? sl : cap; byte_all = byte_all && lanes == 16; }
 	if (cap > MSW_SLEN) { bmh_set_error("bmh_matesw_batch_device: a job the kernel does not take (see bmh_matesw_device_takes)"); return BMH_EINVAL; }
 	for (uint64_t k = 0; k < n_jobs; ++k) { jobs[k].bl_off = (uint32_t)bl; bl += (uint64_t)(jobs[k].re - jobs[k].rb) / 2 + 2; if (bl >> 32) { bmh_set_error("bmh_matesw_batch_device: windows too long"); return BMH_ECAPACITY; } }
-	{ const int rc = msw_room(S, n_jobs, bl); if (rc != BMH_OK) return rc; }
-	HIPCK(hipMemcpyAsync(S->d_jobs, jobs, sizeof(bmh_msw_job_t) * n_jobs, hipMemcpyHostToDevice, st));
-	{ const int rc = msw_launch(S, idx, d_reads, d_offs, ep, n_jobs, cap, byte_all, st); if (rc != BMH_OK) return rc; }
-	HIPCK(hipMemcpyAsync(out, S->d_out, sizeof(int32_t) * 7 * n_jobs, hipMemcpyDeviceToHost, st));
+	RCK(msw_room(S, n_jobs, bl));
+	HIPCK(hipMemcpyAsync(S->d_jobs.p, jobs, sizeof(bmh_msw_job_t) * n_jobs, hipMemcpyHostToDevice, st));
+	RCK(msw_launch(S, idx, d_reads, d_offs, ep, n_jobs, cap, byte_all, st));
+	HIPCK(hipMemcpyAsync(out, S->d_out.as<int32_t>(), sizeof(int32_t) * 7 * n_jobs, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
 	HIPCK(hipGetLastError());
 	return BMH_OK;
@@ -676,43 +646,40 @@ extern "C" int64_t bmh_rescue_count_device(const bmh_index_t *idx, const bmh_res
 	const uint32_t np = n_reads / 2;
 	hipStream_t st = (hipStream_t)stream_;
 	msw_scratch_t *S;
-	{ const int rc = msw_scratch_of(stream_, &S); if (rc != BMH_OK) return rc; }
+	RCK(msw_scratch_of(stream_, &S));
 	S->rj_n_jobs = 0;
 	pair_off[0] = 0;
 	if (np == 0) return 0;
-	if ((size_t)np + 1 > S->cap_pairs) {
-		void *ps[] = {S->d_cnt, S->d_blw, S->d_active};
-		for (void *q : ps) if (q) (void)hipFree(q);
-		S->d_cnt = S->d_blw = nullptr; S->d_active = nullptr; S->cap_pairs = 0;
-		const size_t c = (size_t)np + np / 4 + 1024;
-		HIPCK(hipMalloc((void **)&S->d_cnt, 4 * c)); HIPCK(hipMalloc((void **)&S->d_blw, 4 * c)); HIPCK(hipMalloc((void **)&S->d_active, c));
-		S->cap_pairs = c;
+	if ((size_t)np + 1 > S->d_active.cap) {       // (the last of the three to grow)
+		S->d_cnt.drop(); S->d_blw.drop(); S->d_active.drop();
+		const size_t c = bmh_grow_cap(np);
+		RCK(S->d_cnt.resize(c)); RCK(S->d_blw.resize(c)); RCK(S->d_active.resize(c));
 	}
-	if (!S->d_stat) HIPCK(hipMalloc((void **)&S->d_stat, 16));
+	if (!S->d_stat.p) RCK(S->d_stat.resize(4));
 	const size_t sb = bmh_pair_scan_bytes(np + 1);
-	if (sb > S->cap_scan) { if (S->d_scan) (void)hipFree(S->d_scan); S->d_scan = nullptr; S->cap_scan = 0; HIPCK(hipMalloc(&S->d_scan, sb)); S->cap_scan = sb; }
+	if (sb > S->d_scan.cap) RCK(S->d_scan.resize(sb));
 	rj_args_t &A = S->rj;
 	memset(&A, 0, sizeof(A));
 	A.l_pac = (long long)idx->dev.l_pac; A.n_contigs = in->n_contigs > 1 ? in->n_contigs : 1; A.ctg_off = in->n_contigs > 1 ? in->d_ctg_off : nullptr;
 	for (int d = 0; d < 4; ++d) { A.pes[d].low = (int)pes[5 * d]; A.pes[d].high = (int)pes[5 * d + 1]; A.pes[d].failed = (int)pes[5 * d + 2]; }
 	A.pen_unpaired = pe->pen_unpaired; A.max_matesw = pe->max_matesw; A.min_seed_len = min_seed_len; A.a = ep->a;
 	A.ded = in->d_dedup; A.opr = in->d_opr; A.off = in->d_roff; A.lens = in->d_lens; A.n_pairs = np;
-	A.cnt = S->d_cnt; A.blw = S->d_blw; A.active = S->d_active; A.stat = S->d_stat;
-	HIPCK(hipMemsetAsync(S->d_stat, 0, 16, st));
-	HIPCK(hipMemsetAsync(S->d_cnt + np, 0, 4, st)); HIPCK(hipMemsetAsync(S->d_blw + np, 0, 4, st));
+	A.cnt = S->d_cnt.p; A.blw = S->d_blw.p; A.active = S->d_active.p; A.stat = S->d_stat.p;
+	HIPCK(hipMemsetAsync(S->d_stat.p, 0, 16, st));
+	HIPCK(hipMemsetAsync(S->d_cnt.p + np, 0, 4, st)); HIPCK(hipMemsetAsync(S->d_blw.p + np, 0, 4, st));
 	rescue_jobs_kernel<0><<<(np + 3) / 4, 64, 0, st>>>(A);
 	HIPCK(hipGetLastError());
-	{ const int rc = bmh_pair_scan(S->d_cnt, S->d_cnt, np + 1, S->d_scan, S->cap_scan, st); if (rc != BMH_OK) return rc; }
+	RCK(bmh_pair_scan(S->d_cnt.p, S->d_cnt.p, np + 1, S->d_scan.p, S->d_scan.cap, st));
 	uint32_t stat[4] = {0, 0, 0, 0}, last_bl = 0;
-	HIPCK(hipMemcpyAsync(pair_off, S->d_cnt, 4 * ((size_t)np + 1), hipMemcpyDeviceToHost, st));
-	HIPCK(hipMemcpyAsync(active, S->d_active, np, hipMemcpyDeviceToHost, st));
-	HIPCK(hipMemcpyAsync(stat, S->d_stat, 16, hipMemcpyDeviceToHost, st));
+	HIPCK(hipMemcpyAsync(pair_off, S->d_cnt.p, 4 * ((size_t)np + 1), hipMemcpyDeviceToHost, st));
+	HIPCK(hipMemcpyAsync(active, S->d_active.p, np, hipMemcpyDeviceToHost, st));
+	HIPCK(hipMemcpyAsync(stat, S->d_stat.p, 16, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
 	const uint32_t nj = pair_off[np];
 	if (nj >> 31) { bmh_set_error("bmh_rescue_count_device: too many jobs"); return BMH_ECAPACITY; }
 	if (stat[3]) { bmh_set_error("bmh_rescue_count_device: windows too long"); return BMH_ECAPACITY; }      // (the words of bookkeeping: offsets of 32 bits, like bmh_matesw_batch_device)
-	{ const int rc = bmh_pair_scan(S->d_blw, S->d_blw, np + 1, S->d_scan, S->cap_scan, st); if (rc != BMH_OK) return rc; }
-	HIPCK(hipMemcpyAsync(&last_bl, S->d_blw + np, 4, hipMemcpyDeviceToHost, st));
+	RCK(bmh_pair_scan(S->d_blw.p, S->d_blw.p, np + 1, S->d_scan.p, S->d_scan.cap, st));
+	HIPCK(hipMemcpyAsync(&last_bl, S->d_blw.p + np, 4, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
 	S->rj_n_jobs = nj; S->rj_bl = last_bl; S->rj_cap = stat[0] ? stat[0] : 1; S->rj_byte_all = stat[1] == 0;
 	return (int64_t)nj;
@@ -723,26 +690,20 @@ extern "C" int bmh_rescue_run_device(const bmh_index_t *idx, const uint8_t *d_re
 	if (!idx || !idx->dev.pac || !d_reads || !d_offs || !ep) { bmh_set_error("bmh_rescue_run_device: null argument"); return BMH_EINVAL; }
 	hipStream_t st = (hipStream_t)stream_;
 	msw_scratch_t *S;
-	{ const int rc = msw_scratch_of(stream_, &S); if (rc != BMH_OK) return rc; }
+	RCK(msw_scratch_of(stream_, &S));
 	const uint64_t nj = S->rj_n_jobs;
 	if (nj == 0) return BMH_OK;
 	if (!keys || !out) { bmh_set_error("bmh_rescue_run_device: null argument"); return BMH_EINVAL; }
 	if ((int)S->rj_cap > MSW_SLEN) { bmh_set_error("bmh_rescue_run_device: internal error: a job the kernel does not take"); return BMH_EINVAL; }
-	{ const int rc = msw_room(S, nj, S->rj_bl); if (rc != BMH_OK) return rc; }
-	if (nj > S->cap_keys) {
-		if (S->d_keys) (void)hipFree(S->d_keys);
-		S->d_keys = nullptr; S->cap_keys = 0;
-		const size_t c = nj + nj / 4 + 1024;
-		HIPCK(hipMalloc((void **)&S->d_keys, sizeof(bmh_msw_key_t) * c));
-		S->cap_keys = c;
-	}
+	RCK(msw_room(S, nj, S->rj_bl));
+	RCK(S->d_keys.need(nj));
 	rj_args_t A = S->rj;
-	A.jobs = S->d_jobs; A.keys = S->d_keys;
+	A.jobs = S->d_jobs.p; A.keys = S->d_keys.p;
 	rescue_jobs_kernel<1><<<(A.n_pairs + 3) / 4, 64, 0, st>>>(A);
 	HIPCK(hipGetLastError());
-	{ const int rc = msw_launch(S, idx, d_reads, d_offs, ep, nj, (int)S->rj_cap, S->rj_byte_all, st); if (rc != BMH_OK) return rc; }
-	HIPCK(hipMemcpyAsync(keys, S->d_keys, sizeof(bmh_msw_key_t) * nj, hipMemcpyDeviceToHost, st));
-	HIPCK(hipMemcpyAsync(out, S->d_out, sizeof(int32_t) * 7 * nj, hipMemcpyDeviceToHost, st));
+	RCK(msw_launch(S, idx, d_reads, d_offs, ep, nj, (int)S->rj_cap, S->rj_byte_all, st));
+	HIPCK(hipMemcpyAsync(keys, S->d_keys.p, sizeof(bmh_msw_key_t) * nj, hipMemcpyDeviceToHost, st));
+	HIPCK(hipMemcpyAsync(out, S->d_out.as<int32_t>(), sizeof(int32_t) * 7 * nj, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
 	return BMH_OK;
 }

@@ -26,7 +26,9 @@
 #include <mutex>
 #include <string>
 #include <vector>
+#define BMH_CK_PREFIX "reads parser: "
 #include "bmh_internal.h"
+#include "devmem.h"
 
 namespace {
 
@@ -215,39 +217,6 @@ __global__ void __launch_bounds__(256) rp_names(const uint8_t *__restrict__ b0, 
 	}
 }
 
-struct dbuf_t {
-	void *p = nullptr; size_t cap = 0;
-	~dbuf_t() { if (p) (void)hipFree(p); }
-	int need(size_t bytes)
-	{
-		if (bytes <= cap) return BMH_OK;
-		if (p) (void)hipFree(p);
-		p = nullptr; cap = 0;
-		const size_t c = bytes + bytes / 4 + 256;
-		if (hipMalloc(&p, c) != hipSuccess) { (void)hipGetLastError(); bmh_set_error("reads parser: hipMalloc of %zu bytes failed", c); return BMH_ENOMEM; }
-		cap = c;
-		return BMH_OK;
-	}
-	template <class T> T *as() const { return (T *)p; }
-};
-struct pbuf_t {         // pinned host memory
-	void *p = nullptr; size_t cap = 0;
-	~pbuf_t() { if (p) (void)hipHostFree(p); }
-	int need(size_t bytes)
-	{
-		if (bytes <= cap) return BMH_OK;
-		if (p) (void)hipHostFree(p);
-		p = nullptr; cap = 0;
-		const size_t c = bytes + bytes / 4 + 256;
-		if (hipHostMalloc(&p, c) != hipSuccess) { (void)hipGetLastError(); bmh_set_error("reads parser: hipHostMalloc of %zu bytes failed", c); return BMH_ENOMEM; }
-		cap = c;
-		return BMH_OK;
-	}
-	template <class T> T *as() const { return (T *)p; }
-};
-
-#define RCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("reads parser: %s: %s", #x, hipGetErrorString(e_)); (void)hipGetLastError(); return BMH_ENODEV; } } while (0)
-
 // one file: its source and the window of its text
 struct stream_t {
 	std::string path; bmh_text_src_t *src = nullptr;
@@ -255,7 +224,7 @@ struct stream_t {
 	// a BGZF file inflated on the device (csrc/inflate_kernels.hip): the window's text is dtext[cur][0 .. have) in HBM and never was on the host; whole compressed
 	// members go up from hcomp, the statuses come back in hstat with the parser's first wait (check_status), and buf is the host's copy for the walker (mirror)
 	bool on_dev = false, comp_busy = false; int cur = 0; uint32_t n_stat = 0; uint64_t n_dev_members = 0, comp_seen = 0, text_seen = 0;
-	dbuf_t dtext[2], dcomp, dtab, dstat; pbuf_t hcomp, htab, hstat; std::vector<bmh_inflate_member_t> tab;
+	dev_buf<uint8_t> dtext[2], dcomp, dtab, dstat; pin_buf<uint8_t> hcomp, htab, hstat; std::vector<bmh_inflate_member_t> tab;
 	uint8_t *text_dev() const { return dtext[cur].as<uint8_t>(); }
 	int check_status()
 	{
@@ -269,16 +238,16 @@ struct stream_t {
 	int grow_text(size_t bytes, hipStream_t st)
 	{
 		if (dtext[cur].cap >= bytes) return BMH_OK;
-		dbuf_t &o = dtext[1 - cur];
+		dev_buf<uint8_t> &o = dtext[1 - cur];
 		if (o.need(bytes) != BMH_OK) return BMH_ENOMEM;
-		if (have) { RCK(hipMemcpyAsync(o.p, dtext[cur].p, have, hipMemcpyDeviceToDevice, st)); RCK(hipStreamSynchronize(st)); }
+		if (have) { HIPCK(hipMemcpyAsync(o.p, dtext[cur].p, have, hipMemcpyDeviceToDevice, st)); HIPCK(hipStreamSynchronize(st)); }
 		cur = 1 - cur;
 		return BMH_OK;
 	}
 	int fill_dev(size_t target, hipStream_t st)
 	{
 		while (!eof && have < target) {
-			if (comp_busy) { RCK(hipStreamSynchronize(st)); const int rc = check_status(); if (rc != BMH_OK) return rc; }     // (a second round of one window: poorly compressed members)
+			if (comp_busy) { HIPCK(hipStreamSynchronize(st)); const int rc = check_status(); if (rc != BMH_OK) return rc; }     // (a second round of one window: poorly compressed members)
 			const size_t want = target - have;
 			// room for the compressed bytes of the text wanted, by the ratio this file has shown so far (half the text before any is known; at most all of it plus the
 			// members' headers), so that a poorly compressed file does not take two rounds, and a fourth host wait, per window
@@ -295,11 +264,11 @@ struct stream_t {
 			if (grc != BMH_OK) return grc;
 			if (dcomp.need((size_t)r + 16) != BMH_OK || dtab.need(tb) != BMH_OK || dstat.need(nm * 4) != BMH_OK || htab.need(tb) != BMH_OK || hstat.need(nm * 4) != BMH_OK) return BMH_ENOMEM;
 			memcpy(htab.p, tab.data(), tb);
-			RCK(hipMemcpyAsync(dcomp.p, hcomp.p, (size_t)r, hipMemcpyHostToDevice, st));
-			RCK(hipMemcpyAsync(dtab.p, htab.p, tb, hipMemcpyHostToDevice, st));
+			HIPCK(hipMemcpyAsync(dcomp.p, hcomp.p, (size_t)r, hipMemcpyHostToDevice, st));
+			HIPCK(hipMemcpyAsync(dtab.p, htab.p, tb, hipMemcpyHostToDevice, st));
 			const int irc = bmh_inflate_members_device(dcomp.as<uint8_t>(), (uint64_t)r, dtab.as<bmh_inflate_member_t>(), (uint32_t)nm, text_dev() + have, text, dstat.as<uint32_t>(), st);
 			if (irc != BMH_OK) return irc;
-			RCK(hipMemcpyAsync(hstat.p, dstat.p, nm * 4, hipMemcpyDeviceToHost, st));
+			HIPCK(hipMemcpyAsync(hstat.p, dstat.p, nm * 4, hipMemcpyDeviceToHost, st));
 			comp_busy = true; n_stat = (uint32_t)nm; n_dev_members += nm; comp_seen += (uint64_t)r; text_seen += text;
 			have += (size_t)text; bytes += text;
 		}
@@ -311,9 +280,9 @@ struct stream_t {
 		if (k >= have) { have = 0; return BMH_OK; }
 		if (k == 0) return BMH_OK;
 		const size_t rest = have - k;
-		dbuf_t &o = dtext[1 - cur];
+		dev_buf<uint8_t> &o = dtext[1 - cur];
 		if (o.need(rest + 16) != BMH_OK) return BMH_ENOMEM;
-		RCK(hipMemcpyAsync(o.p, text_dev() + k, rest, hipMemcpyDeviceToDevice, st));
+		HIPCK(hipMemcpyAsync(o.p, text_dev() + k, rest, hipMemcpyDeviceToDevice, st));
 		cur = 1 - cur; have = rest;
 		return BMH_OK;
 	}
@@ -325,8 +294,8 @@ struct stream_t {
 			if (!nb) { bmh_set_error("reads file: out of memory (%zu bytes of text)", have + 16); return BMH_ENOMEM; }
 			free(buf); buf = nb; cap = have + 16;
 		}
-		if (comp_busy) { RCK(hipStreamSynchronize(st)); const int rc = check_status(); if (rc != BMH_OK) return rc; }
-		if (have) { RCK(hipMemcpyAsync(buf, text_dev(), have, hipMemcpyDeviceToHost, st)); RCK(hipStreamSynchronize(st)); }
+		if (comp_busy) { HIPCK(hipStreamSynchronize(st)); const int rc = check_status(); if (rc != BMH_OK) return rc; }
+		if (have) { HIPCK(hipMemcpyAsync(buf, text_dev(), have, hipMemcpyDeviceToHost, st)); HIPCK(hipStreamSynchronize(st)); }
 		return BMH_OK;
 	}
 	~stream_t() { if (src) bmh_text_close(src); release(buf); }
@@ -372,17 +341,17 @@ uint64_t cut_batch(const uint32_t *lens, uint64_t n, int step, uint64_t want_bas
 struct dev_parser_t {
 	hipStream_t st = nullptr;
 	static constexpr uint32_t PEEK = 64;
-	int stream(hipStream_t *out) { if (!st) RCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); *out = st; return BMH_OK; }
-	struct per_file_t { dbuf_t b, lid, L, kind, klen, flag, fs, role, rec, seqk, sloff, hdr_line, seq_line, qual_line, rend, rsl, ctl; } D[2];
-	dbuf_t tmp, lens, nlen, clen, nstart, cstart, offs, noffs, coffs, ascii, codes, quals, names, cm;
-	pbuf_t h_small, h_lens, h_offs, h_noffs, h_coffs, h_rend[2];
+	int stream(hipStream_t *out) { if (!st) HIPCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); *out = st; return BMH_OK; }
+	struct per_file_t { dev_buf<uint8_t> b, lid, L, kind, klen, flag, fs, role, rec, seqk, sloff, hdr_line, seq_line, qual_line, rend, rsl, ctl; } D[2];
+	dev_buf<uint8_t> tmp, lens, nlen, clen, nstart, cstart, offs, noffs, coffs, ascii, codes, quals, names, cm;
+	pin_buf<uint8_t> h_small, h_lens, h_offs, h_noffs, h_coffs, h_rend[2];
 	~dev_parser_t() { if (st) (void)hipStreamDestroy(st); }
 
 	// 1: parsed (R; the arrays are in what alloc gave when the batch is delivered), 2: the window is the host's, < 0: error
 	int run(stream_t *S, int nf, bool comments, uint64_t want_bases, uint64_t want_reads, bool even, bool take_all, const bmh_batch_alloc_t &alloc,
 	        bmh_read_set_t *rs, result_t &R)
 	{
-		if (!st) RCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+		if (!st) HIPCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
 		rp_file_t F[2]; memset(F, 0, sizeof(F));
 		if (h_small.need(128 * sizeof(uint32_t)) != BMH_OK) return BMH_ENOMEM;
 		uint32_t *hs = h_small.as<uint32_t>();
@@ -397,26 +366,26 @@ struct dev_parser_t {
 				// the text is in HBM already (inflated there): its first bytes come back with the line count
 				if (P.lid.need((size_t)n * 4) != BMH_OK || P.ctl.need(sizeof(rp_ctl_t)) != BMH_OK) return BMH_ENOMEM;
 				F[f].b = S[f].text_dev();
-				RCK(hipMemcpyAsync(hs + 64 + 16 * f, F[f].b, std::min<uint32_t>(n, PEEK), hipMemcpyDeviceToHost, st));
+				HIPCK(hipMemcpyAsync(hs + 64 + 16 * f, F[f].b, std::min<uint32_t>(n, PEEK), hipMemcpyDeviceToHost, st));
 			} else {
 				size_t p = 0;
 				while (p < n && (S[f].buf[p] == '\n' || S[f].buf[p] == '\r')) ++p;
 				if (p < n && S[f].buf[p] != '>' && S[f].buf[p] != '@') return 2;
 				F[f].fq = p < n && S[f].buf[p] == '@';
 				if (P.b.need(n + 16) != BMH_OK || P.lid.need((size_t)n * 4) != BMH_OK || P.ctl.need(sizeof(rp_ctl_t)) != BMH_OK) return BMH_ENOMEM;
-				RCK(hipMemcpyAsync(P.b.p, S[f].buf, n, hipMemcpyHostToDevice, st));
+				HIPCK(hipMemcpyAsync(P.b.p, S[f].buf, n, hipMemcpyHostToDevice, st));
 				F[f].b = P.b.as<uint8_t>();
 			}
-			RCK(hipMemsetAsync(P.ctl.p, 0, sizeof(rp_ctl_t), st));
+			HIPCK(hipMemsetAsync(P.ctl.p, 0, sizeof(rp_ctl_t), st));
 			size_t tb = 0;
 			auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), rp_ls_flag{F[f].b});
-			RCK(rocprim::inclusive_scan(nullptr, tb, in, P.lid.as<uint32_t>(), (size_t)n, rocprim::plus<uint32_t>(), st));
-			if (tb > tmp.cap) { RCK(hipStreamSynchronize(st)); if (tmp.need(tb) != BMH_OK) return BMH_ENOMEM; }
-			RCK(rocprim::inclusive_scan(tmp.p, tb, in, P.lid.as<uint32_t>(), (size_t)n, rocprim::plus<uint32_t>(), st));
-			RCK(hipMemcpyAsync(hs + f, P.lid.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, st));
+			HIPCK(rocprim::inclusive_scan(nullptr, tb, in, P.lid.as<uint32_t>(), (size_t)n, rocprim::plus<uint32_t>(), st));
+			if (tb > tmp.cap) { HIPCK(hipStreamSynchronize(st)); if (tmp.need(tb) != BMH_OK) return BMH_ENOMEM; }
+			HIPCK(rocprim::inclusive_scan(tmp.p, tb, in, P.lid.as<uint32_t>(), (size_t)n, rocprim::plus<uint32_t>(), st));
+			HIPCK(hipMemcpyAsync(hs + f, P.lid.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, st));
 			F[f].lid = P.lid.as<uint32_t>();
 		}
-		RCK(hipStreamSynchronize(st));
+		HIPCK(hipStreamSynchronize(st));
 		for (int f = 0; f < nf; ++f) {
 			if (!S[f].on_dev) continue;
 			const int src_rc = S[f].check_status();                    // every member of the window inflated to its size and CRC, or the file is refused
@@ -446,15 +415,15 @@ struct dev_parser_t {
 			hipLaunchKernelGGL(rp_line_starts, dim3(gb), dim3(256), 0, st, F[f].b, n, F[f].lid, P.L.as<uint32_t>());
 			hipLaunchKernelGGL(rp_line_kind, dim3(gl), dim3(256), 0, st, F[f].b, n, m, F[f].eof, F[f].fq, F[f].L, P.kind.as<uint8_t>(), P.klen.as<uint32_t>(), P.flag.as<uint32_t>(), ctl);
 			size_t tb = 0;
-			RCK(rocprim::exclusive_scan(nullptr, tb, P.flag.as<uint32_t>(), P.fs.as<uint32_t>(), 0u, (size_t)m, rocprim::plus<uint32_t>(), st));
-			if (tb > tmp.cap) { RCK(hipStreamSynchronize(st)); if (tmp.need(tb) != BMH_OK) return BMH_ENOMEM; }
-			RCK(rocprim::exclusive_scan(tmp.p, tb, P.flag.as<uint32_t>(), P.fs.as<uint32_t>(), 0u, (size_t)m, rocprim::plus<uint32_t>(), st));
+			HIPCK(rocprim::exclusive_scan(nullptr, tb, P.flag.as<uint32_t>(), P.fs.as<uint32_t>(), 0u, (size_t)m, rocprim::plus<uint32_t>(), st));
+			if (tb > tmp.cap) { HIPCK(hipStreamSynchronize(st)); if (tmp.need(tb) != BMH_OK) return BMH_ENOMEM; }
+			HIPCK(rocprim::exclusive_scan(tmp.p, tb, P.flag.as<uint32_t>(), P.fs.as<uint32_t>(), 0u, (size_t)m, rocprim::plus<uint32_t>(), st));
 			hipLaunchKernelGGL(rp_line_role, dim3(gl), dim3(256), 0, st, m, F[f].fq, P.kind.as<uint8_t>(), F[f].klen, F[f].flag, F[f].fs, P.role.as<uint8_t>(), P.rec.as<uint32_t>(),
 			                   P.seqk.as<uint32_t>(), P.hdr_line.as<uint32_t>(), P.seq_line.as<uint32_t>(), P.qual_line.as<uint32_t>(), ctl);
-			RCK(rocprim::exclusive_scan(tmp.p, tb, P.seqk.as<uint32_t>(), P.sloff.as<uint32_t>(), 0u, (size_t)m, rocprim::plus<uint32_t>(), st));
-			RCK(hipMemcpyAsync(hs + 8 + 4 * f, ctl, sizeof(rp_ctl_t), hipMemcpyDeviceToHost, st));
+			HIPCK(rocprim::exclusive_scan(tmp.p, tb, P.seqk.as<uint32_t>(), P.sloff.as<uint32_t>(), 0u, (size_t)m, rocprim::plus<uint32_t>(), st));
+			HIPCK(hipMemcpyAsync(hs + 8 + 4 * f, ctl, sizeof(rp_ctl_t), hipMemcpyDeviceToHost, st));
 		}
-		RCK(hipStreamSynchronize(st));
+		HIPCK(hipStreamSynchronize(st));
 		uint64_t nrec[2] = {0, 0};
 		for (int f = 0; f < nf; ++f) {
 			if (F[f].n == 0) continue;
@@ -487,23 +456,23 @@ struct dev_parser_t {
 		{
 			size_t tb = 0;
 			auto in = rocprim::make_transform_iterator(lens.as<uint32_t>(), rp_to64());
-			RCK(rocprim::exclusive_scan(nullptr, tb, in, offs.as<uint64_t>(), (uint64_t)0, (size_t)nt, rocprim::plus<uint64_t>(), st));
-			if (tb > tmp.cap) { RCK(hipStreamSynchronize(st)); if (tmp.need(tb) != BMH_OK) return BMH_ENOMEM; }
-			RCK(rocprim::exclusive_scan(tmp.p, tb, in, offs.as<uint64_t>(), (uint64_t)0, (size_t)nt, rocprim::plus<uint64_t>(), st));
+			HIPCK(rocprim::exclusive_scan(nullptr, tb, in, offs.as<uint64_t>(), (uint64_t)0, (size_t)nt, rocprim::plus<uint64_t>(), st));
+			if (tb > tmp.cap) { HIPCK(hipStreamSynchronize(st)); if (tmp.need(tb) != BMH_OK) return BMH_ENOMEM; }
+			HIPCK(rocprim::exclusive_scan(tmp.p, tb, in, offs.as<uint64_t>(), (uint64_t)0, (size_t)nt, rocprim::plus<uint64_t>(), st));
 			auto in2 = rocprim::make_transform_iterator(nlen.as<uint32_t>(), rp_to64());
-			RCK(rocprim::exclusive_scan(tmp.p, tb, in2, noffs.as<uint64_t>(), (uint64_t)0, (size_t)nt, rocprim::plus<uint64_t>(), st));
+			HIPCK(rocprim::exclusive_scan(tmp.p, tb, in2, noffs.as<uint64_t>(), (uint64_t)0, (size_t)nt, rocprim::plus<uint64_t>(), st));
 			auto in3 = rocprim::make_transform_iterator(clen.as<uint32_t>(), rp_to64());
-			RCK(rocprim::exclusive_scan(tmp.p, tb, in3, coffs.as<uint64_t>(), (uint64_t)0, (size_t)nt, rocprim::plus<uint64_t>(), st));
+			HIPCK(rocprim::exclusive_scan(tmp.p, tb, in3, coffs.as<uint64_t>(), (uint64_t)0, (size_t)nt, rocprim::plus<uint64_t>(), st));
 		}
-		RCK(hipMemcpyAsync(h_lens.p, lens.p, t4, hipMemcpyDeviceToHost, st));
-		RCK(hipMemcpyAsync(h_offs.p, offs.p, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
-		RCK(hipMemcpyAsync(h_noffs.p, noffs.p, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
-		RCK(hipMemcpyAsync(h_coffs.p, coffs.p, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
+		HIPCK(hipMemcpyAsync(h_lens.p, lens.p, t4, hipMemcpyDeviceToHost, st));
+		HIPCK(hipMemcpyAsync(h_offs.p, offs.p, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
+		HIPCK(hipMemcpyAsync(h_noffs.p, noffs.p, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
+		HIPCK(hipMemcpyAsync(h_coffs.p, coffs.p, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
 		for (int f = 0; f < nf; ++f) {
-			RCK(hipMemcpyAsync(h_rend[f].p, D[f].rend.p, (size_t)nuse * 4, hipMemcpyDeviceToHost, st));
-			RCK(hipMemcpyAsync(hs + 8 + 4 * f, D[f].ctl.p, sizeof(rp_ctl_t), hipMemcpyDeviceToHost, st));
+			HIPCK(hipMemcpyAsync(h_rend[f].p, D[f].rend.p, (size_t)nuse * 4, hipMemcpyDeviceToHost, st));
+			HIPCK(hipMemcpyAsync(hs + 8 + 4 * f, D[f].ctl.p, sizeof(rp_ctl_t), hipMemcpyDeviceToHost, st));
 		}
-		RCK(hipStreamSynchronize(st));
+		HIPCK(hipStreamSynchronize(st));
 		for (int f = 0; f < nf; ++f) if (((const rp_ctl_t *)(hs + 8 + 4 * f))->flag) return 2;
 		const uint32_t *hl = h_lens.as<uint32_t>();
 		const uint64_t *ho = h_offs.as<uint64_t>(), *hn = h_noffs.as<uint64_t>(), *hc = h_coffs.as<uint64_t>();
@@ -516,9 +485,9 @@ struct dev_parser_t {
 		{   // (the lengths of the last read's name and comment are on the device: from the spans of the next read, or of the whole)
 			uint32_t last[2] = {0, 0};
 			if (k == nt) {
-				RCK(hipMemcpyAsync(&hs[32], nlen.as<uint32_t>() + (nt - 1), 4, hipMemcpyDeviceToHost, st));
-				RCK(hipMemcpyAsync(&hs[33], clen.as<uint32_t>() + (nt - 1), 4, hipMemcpyDeviceToHost, st));
-				RCK(hipStreamSynchronize(st));
+				HIPCK(hipMemcpyAsync(&hs[32], nlen.as<uint32_t>() + (nt - 1), 4, hipMemcpyDeviceToHost, st));
+				HIPCK(hipMemcpyAsync(&hs[33], clen.as<uint32_t>() + (nt - 1), 4, hipMemcpyDeviceToHost, st));
+				HIPCK(hipStreamSynchronize(st));
 				last[0] = hs[32]; last[1] = hs[33];
 			}
 			nn = k < nt ? hn[k] : hn[nt - 1] + last[0];
@@ -534,14 +503,14 @@ struct dev_parser_t {
 		for (int f = 0; f < nf; ++f)
 			hipLaunchKernelGGL(rp_scatter, dim3((F[f].n + 255) / 256), dim3(256), 0, st, F[f], f, nf, (uint32_t)(k / (uint64_t)nf), lens.as<uint32_t>(), offs.as<uint64_t>(), ascii.as<uint8_t>(),
 			                   codes.as<uint8_t>(), quals.as<uint8_t>());
-		RCK(hipMemcpyAsync(rs->ascii, ascii.p, nb, hipMemcpyDeviceToHost, st));
-		if (rs->codes) RCK(hipMemcpyAsync(rs->codes, codes.p, nb, hipMemcpyDeviceToHost, st));
-		if (fq && rs->quals) RCK(hipMemcpyAsync(rs->quals, quals.p, nb, hipMemcpyDeviceToHost, st));
-		RCK(hipMemcpyAsync(rs->names, names.p, nn, hipMemcpyDeviceToHost, st));
-		if (comments && rs->comments) RCK(hipMemcpyAsync(rs->comments, cm.p, nc, hipMemcpyDeviceToHost, st));
+		HIPCK(hipMemcpyAsync(rs->ascii, ascii.p, nb, hipMemcpyDeviceToHost, st));
+		if (rs->codes) HIPCK(hipMemcpyAsync(rs->codes, codes.p, nb, hipMemcpyDeviceToHost, st));
+		if (fq && rs->quals) HIPCK(hipMemcpyAsync(rs->quals, quals.p, nb, hipMemcpyDeviceToHost, st));
+		HIPCK(hipMemcpyAsync(rs->names, names.p, nn, hipMemcpyDeviceToHost, st));
+		if (comments && rs->comments) HIPCK(hipMemcpyAsync(rs->comments, cm.p, nc, hipMemcpyDeviceToHost, st));
 		memcpy(rs->offs, ho, k * 8); memcpy(rs->lens, hl, k * 4); memcpy(rs->name_offs, hn, k * 8);
 		if (comments && rs->comment_offs) memcpy(rs->comment_offs, hc, k * 8);
-		RCK(hipStreamSynchronize(st));
+		HIPCK(hipStreamSynchronize(st));
 		rs->n_reads = k; rs->n_bases = nb; rs->n_name_bytes = nn; rs->n_comment_bytes = nc;
 		R.n_reads = k;
 		const uint64_t kf = k / (uint64_t)nf;

@@ -19,14 +19,10 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <map>
-#include <mutex>
-#include <utility>
 #include "bmh_internal.h"
+#include "devmem.h"
 #include "chain_core.h"
 #include "regs_core.h"
-
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
 
 using namespace regs_core;
 
@@ -645,22 +641,24 @@ __global__ void __launch_bounds__(256) fin_compact_kernel(const int32_t *__restr
 
 // ---- host side: scratch per (device, stream), grown on demand
 struct fin_scratch_t {
-	uint32_t *in_off, *out_off, *opr_tmp, *defer, *ctr; size_t cap_reads; int32_t *g_dp;
-	hipStream_t side[3]; hipEvent_t fork, join[3];
-	int32_t *work, *work2; uint64_t *g_keys, *g_k128; uint32_t *g_tmp, *g_order; int32_t *g_z; size_t cap_regs;
-	int32_t *dedup; size_t cap_dedup;       // the regions between the two halves of the tail, for callers that ask (bmh_finalize_regs_device_ex)
-	uint8_t *ctg_alt; int cap_alt;          // the ALT table on the device
-	void *scan_tmp; size_t scan_bytes;
-	double *logtab; int64_t *ctg; int cap_ctg;
-	uint32_t *h_pin;
-	hipEvent_t ev0, ev1;
-	bool inited;             // the one-time part below went through completely
+	dev_buf<uint32_t> in_off, out_off, defer, ctr; dev_buf<uint8_t> scan_tmp; size_t cap_reads = 0;      // in_off .. scan_tmp grow together
+	dev_buf<int32_t> g_dp;
+	hipStream_t side[3] = {}; hipEvent_t fork = nullptr, join[3] = {};
+	dev_buf<int32_t[16]> work, work2; dev_buf<uint64_t> g_keys; dev_buf<uint64_t[2]> g_k128; dev_buf<uint32_t> g_tmp, g_order; dev_buf<int32_t> g_z; size_t cap_regs = 0;      // grow together
+	dev_buf<int32_t[16]> dedup;           // the regions between the two halves of the tail, for callers that ask (bmh_finalize_regs_device_ex)
+	dev_buf<uint8_t> ctg_alt;             // the ALT table on the device
+	dev_buf<double> logtab; dev_buf<int64_t> ctg;
+	pin_buf<uint32_t> h_pin;
+	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	bool inited = false;     // the one-time part below went through completely
+	~fin_scratch_t()
+	{
+		for (hipEvent_t e : {ev0, ev1, fork, join[0], join[1], join[2]}) if (e) (void)hipEventDestroy(e);
+		for (hipStream_t q : side) if (q) (void)hipStreamDestroy(q);
+	}
 };
-static std::mutex g_fin_mu;
-static std::map<std::pair<int, void *>, fin_scratch_t *> g_fin_map;
+static stream_scratch<fin_scratch_t> g_fin_reg;
 static thread_local fin_scratch_t *g_fin_last = nullptr;
-
-template <class T> static int fin_grow(T *&p, size_t n) { if (p) (void)hipFree(p); p = nullptr; return hipMalloc((void **)&p, sizeof(T) * n) == hipSuccess ? BMH_OK : BMH_ENOMEM; }
 
 // the (device, stream) scratch of bmh_finalize_regs_device (device buffers, three side streams, events, pinned words): freed when
 // the caller retires the stream (stream idle, its device current)
@@ -668,23 +666,8 @@ extern "C" void bmh_finalize_release(void *stream_)
 {
 	int dev = 0;
 	if (hipGetDevice(&dev) != hipSuccess) return;
-	fin_scratch_t *S = nullptr;
-	{
-		std::lock_guard<std::mutex> lk(g_fin_mu);
-		auto it = g_fin_map.find(std::make_pair(dev, stream_));
-		if (it == g_fin_map.end()) return;
-		S = it->second;
-		g_fin_map.erase(it);
-	}
-	if (g_fin_last == S) g_fin_last = nullptr;
-	void *ps[] = {S->in_off, S->out_off, S->opr_tmp, S->defer, S->ctr, S->g_dp, S->work, S->work2, S->g_keys, S->g_k128, S->g_tmp, S->g_order, S->g_z, S->scan_tmp, S->logtab, S->ctg, S->dedup, S->ctg_alt};
-	for (void *q : ps) if (q) (void)hipFree(q);
-	if (S->h_pin) (void)hipHostFree(S->h_pin);
-	if (S->ev0) (void)hipEventDestroy(S->ev0);
-	if (S->ev1) (void)hipEventDestroy(S->ev1);
-	if (S->fork) (void)hipEventDestroy(S->fork);
-	for (int i = 0; i < 3; ++i) { if (S->side[i]) (void)hipStreamDestroy(S->side[i]); if (S->join[i]) (void)hipEventDestroy(S->join[i]); }
-	free(S);
+	const std::unique_ptr<fin_scratch_t> S = g_fin_reg.take(dev, stream_);
+	if (g_fin_last == S.get()) g_fin_last = nullptr;
 }
 
 extern "C" float bmh_finalize_regs_device_last_ms(void)
@@ -748,34 +731,27 @@ static int64_t finalize_regs_device_impl(const bmh_index_t *idx, const bmh_chain
 	hipStream_t st = (hipStream_t)stream_;
 	int dev = 0;
 	HIPCK(hipGetDevice(&dev));
-	fin_scratch_t *S;
-	{
-		std::lock_guard<std::mutex> lk(g_fin_mu);
-		auto key = std::make_pair(dev, stream_);
-		auto it = g_fin_map.find(key);
-		if (it == g_fin_map.end()) { S = (fin_scratch_t *)calloc(1, sizeof(fin_scratch_t)); g_fin_map[key] = S; }
-		else S = it->second;
-	}
+	fin_scratch_t *S = &g_fin_reg.get(dev, stream_);
 	g_fin_last = S;
 	if (!S->inited) {
 		// one-time part of a (device, stream) pair; a step that fails leaves `inited` false and the next call starts over (what was
 		// created so far is kept and not created twice)
-		if (!S->logtab) {
+		if (!S->logtab.p) {
 			// log(k) by the host's libm (the reference's MAPQ is computed there): the device reads these values, it never calls log()
 			double *h = (double *)malloc(sizeof(double) * FIN_NLOG);
 			if (!h) { bmh_set_error("bmh_finalize_regs_device: out of host memory"); return BMH_ENOMEM; }
 			for (int k = 0; k < FIN_NLOG; ++k) h[k] = log((double)k);
-			double *d_log = nullptr;
-			const bool ok = fin_grow(d_log, FIN_NLOG) == BMH_OK && hipMemcpy(d_log, h, sizeof(double) * FIN_NLOG, hipMemcpyHostToDevice) == hipSuccess;
+			dev_buf<double> d_log;
+			const bool ok = d_log.resize(FIN_NLOG) == BMH_OK && hipMemcpy(d_log.p, h, sizeof(double) * FIN_NLOG, hipMemcpyHostToDevice) == hipSuccess;
 			free(h);
-			if (!ok) { if (d_log) (void)hipFree(d_log); bmh_set_error("bmh_finalize_regs_device: log table: %s", hipGetErrorString(hipGetLastError())); return BMH_ENOMEM; }
-			S->logtab = d_log;
+			if (!ok) { bmh_set_error("bmh_finalize_regs_device: log table: %s", hipGetErrorString(hipGetLastError())); return BMH_ENOMEM; }
+			S->logtab.swap(d_log);
 		}
 		if (!S->ev0) HIPCK(hipEventCreate(&S->ev0));
 		if (!S->ev1) HIPCK(hipEventCreate(&S->ev1));
-		if (!S->h_pin) HIPCK(hipHostMalloc((void **)&S->h_pin, 128));
-		if (!S->ctr && fin_grow(S->ctr, 32) != BMH_OK) return BMH_ENOMEM;
-		if (!S->g_dp && fin_grow(S->g_dp, (size_t)FIN_NCLS * FIN_WAVE_GRID * 2 * FIN_DPCAP) != BMH_OK) return BMH_ENOMEM;
+		if (!S->h_pin.p) RCK(S->h_pin.resize(32));
+		if (!S->ctr.p) RCK(S->ctr.resize(32));
+		if (!S->g_dp.p) RCK(S->g_dp.resize((size_t)FIN_NCLS * FIN_WAVE_GRID * 2 * FIN_DPCAP));
 		if (!S->fork) HIPCK(hipEventCreateWithFlags(&S->fork, hipEventDisableTiming));
 		for (int i = 0; i < 3; ++i) {
 			if (!S->side[i]) HIPCK(hipStreamCreateWithFlags(&S->side[i], hipStreamNonBlocking));
@@ -784,50 +760,46 @@ static int64_t finalize_regs_device_impl(const bmh_index_t *idx, const bmh_chain
 		S->inited = true;
 	}
 	if ((size_t)n_reads + 1 > S->cap_reads) {
-		const size_t c = (size_t)n_reads + n_reads / 4 + 1024;
-		if (fin_grow(S->in_off, c) != BMH_OK || fin_grow(S->out_off, c) != BMH_OK || fin_grow(S->defer, FIN_NCLS * c) != BMH_OK) return BMH_ENOMEM;
-		size_t t1 = 0;
-		(void)rocprim::exclusive_scan(nullptr, t1, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, c, rocprim::plus<uint32_t>(), 0);
-		if (S->scan_tmp) (void)hipFree(S->scan_tmp);
-		S->scan_tmp = nullptr;
-		HIPCK(hipMalloc(&S->scan_tmp, t1 + 256)); S->scan_bytes = t1 + 256;
+		const size_t c = bmh_grow_cap(n_reads);
+		S->cap_reads = 0;
+		RCK(S->in_off.resize(c)); RCK(S->out_off.resize(c)); RCK(S->defer.resize(FIN_NCLS * c)); RCK(S->scan_tmp.resize(scan_tmp_bytes<uint32_t, uint32_t>(c)));
 		S->cap_reads = c;
 	}
 	if (n_regs + 1 > S->cap_regs) {
-		const size_t c = n_regs + n_regs / 4 + 1024;
-		if (fin_grow(S->work, 16 * c) != BMH_OK || fin_grow(S->work2, 16 * c) != BMH_OK || fin_grow(S->g_keys, c) != BMH_OK || fin_grow(S->g_k128, 2 * c) != BMH_OK ||
-		    fin_grow(S->g_tmp, c) != BMH_OK || fin_grow(S->g_order, c) != BMH_OK || fin_grow(S->g_z, c) != BMH_OK) return BMH_ENOMEM;
+		const size_t c = bmh_grow_cap(n_regs);
+		S->cap_regs = 0;
+		RCK(S->work.resize(c)); RCK(S->work2.resize(c)); RCK(S->g_keys.resize(c)); RCK(S->g_k128.resize(c)); RCK(S->g_tmp.resize(c)); RCK(S->g_order.resize(c)); RCK(S->g_z.resize(c));
 		S->cap_regs = c;
 	}
 	if (n_contigs > 1) {
-		if (n_contigs > S->cap_ctg) { if (fin_grow(S->ctg, (size_t)n_contigs) != BMH_OK) return BMH_ENOMEM; S->cap_ctg = n_contigs; }
-		HIPCK(hipMemcpyAsync(S->ctg, contig_offset, sizeof(int64_t) * n_contigs, hipMemcpyHostToDevice, st));
+		if ((size_t)n_contigs > S->ctg.cap) RCK(S->ctg.resize((size_t)n_contigs));
+		HIPCK(hipMemcpyAsync(S->ctg.p, contig_offset, sizeof(int64_t) * n_contigs, hipMemcpyHostToDevice, st));
 	}
 	fin_args_t A;
 	memset(&A, 0, sizeof(A));
 	A.x.co = *copt; A.x.ep = *ep; A.x.po = *popt; A.x.l_pac = (int64_t)idx->dev.l_pac; A.x.pac = idx->dev.pac;
-	A.x.n_contigs = n_contigs > 1 ? n_contigs : 1; A.x.ctg_off = n_contigs > 1 ? S->ctg : nullptr;
-	A.x.logtab = S->logtab; A.x.n_log = FIN_NLOG; A.x.dp_h = A.x.dp_e = nullptr; A.x.dp_cap = 0; A.x.dedup_only = dedup_only;
+	A.x.n_contigs = n_contigs > 1 ? n_contigs : 1; A.x.ctg_off = n_contigs > 1 ? S->ctg.p : nullptr;
+	A.x.logtab = S->logtab.p; A.x.n_log = FIN_NLOG; A.x.dp_h = A.x.dp_e = nullptr; A.x.dp_cap = 0; A.x.dedup_only = dedup_only;
 	A.x.po.contig_is_alt = nullptr;                               // (a host pointer: never followed on the device)
 	A.x.ctg_alt = nullptr; A.x.alt_keep_sub_n = extra ? extra->alt_keep_sub_n : 0;
 	if (alt_mode) {
 		const int nc = n_contigs > 1 ? n_contigs : 1;
-		if (nc > S->cap_alt) { if (fin_grow(S->ctg_alt, (size_t)nc) != BMH_OK) return BMH_ENOMEM; S->cap_alt = nc; }
-		HIPCK(hipMemcpyAsync(S->ctg_alt, popt->contig_is_alt, (size_t)nc, hipMemcpyHostToDevice, st));
-		A.x.ctg_alt = S->ctg_alt;
+		if ((size_t)nc > S->ctg_alt.cap) RCK(S->ctg_alt.resize((size_t)nc));
+		HIPCK(hipMemcpyAsync(S->ctg_alt.p, popt->contig_is_alt, (size_t)nc, hipMemcpyHostToDevice, st));
+		A.x.ctg_alt = S->ctg_alt.p;
 	}
-	A.reads = d_reads; A.read_offs = d_offs; A.regs_in = d_regs; A.rpr = d_regs_per_read; A.in_off = S->in_off; A.frac_rep = d_frac_rep;
-	A.work = S->work; A.work2 = S->work2; A.g_keys = S->g_keys; A.g_k128 = S->g_k128; A.g_tmp = S->g_tmp; A.g_order = S->g_order; A.g_z = S->g_z;
-	A.opr = d_out_per_read; A.n_reads = n_reads; A.defer = S->defer; A.ctr = S->ctr; A.g_dp = S->g_dp;
+	A.reads = d_reads; A.read_offs = d_offs; A.regs_in = d_regs; A.rpr = d_regs_per_read; A.in_off = S->in_off.p; A.frac_rep = d_frac_rep;
+	A.work = S->work.as<int32_t>(); A.work2 = S->work2.as<int32_t>(); A.g_keys = S->g_keys.p; A.g_k128 = S->g_k128.as<uint64_t>(); A.g_tmp = S->g_tmp.p; A.g_order = S->g_order.p; A.g_z = S->g_z.p;
+	A.opr = d_out_per_read; A.n_reads = n_reads; A.defer = S->defer.p; A.ctr = S->ctr.p; A.g_dp = S->g_dp.p;
 	A.dedup_out = nullptr;
 	if (extra && extra->d_dedup_out) {
-		if (n_regs + 1 > S->cap_dedup) { const size_t c = n_regs + n_regs / 4 + 1024; if (fin_grow(S->dedup, 16 * c) != BMH_OK) return BMH_ENOMEM; S->cap_dedup = c; }
-		A.dedup_out = S->dedup;
+		if (n_regs + 1 > S->dedup.cap) RCK(S->dedup.resize(bmh_grow_cap(n_regs)));
+		A.dedup_out = S->dedup.as<int32_t>();
 	}
 	HIPCK(hipEventRecord(S->ev0, st));
-	HIPCK(hipMemsetAsync(S->ctr, 0, 128, st));
-	size_t tb = S->scan_bytes;
-	HIPCK(rocprim::exclusive_scan(S->scan_tmp, tb, d_regs_per_read, S->in_off, 0u, (size_t)n_reads, rocprim::plus<uint32_t>(), st));
+	HIPCK(hipMemsetAsync(S->ctr.p, 0, 128, st));
+	size_t tb = S->scan_tmp.cap;
+	HIPCK(rocprim::exclusive_scan(S->scan_tmp.p, tb, d_regs_per_read, S->in_off.p, 0u, (size_t)n_reads, rocprim::plus<uint32_t>(), st));
 	static const bool want_phases = getenv("BMH_FIN_PHASES") != nullptr;      // debug: time of the kernels of every call
 	static thread_local hipEvent_t ph[4] = {nullptr, nullptr, nullptr, nullptr};
 	if (want_phases && !ph[0]) for (hipEvent_t &e : ph) HIPCK(hipEventCreate(&e));
@@ -855,17 +827,17 @@ static int64_t finalize_regs_device_impl(const bmh_index_t *idx, const bmh_chain
 		for (int i = 0; i < 3; ++i) { HIPCK(hipEventRecord(S->join[i], S->side[i])); HIPCK(hipStreamWaitEvent(st, S->join[i], 0)); }
 	}
 	if (want_phases) HIPCK(hipEventRecord(ph[2], st));
-	tb = S->scan_bytes;
-	HIPCK(rocprim::exclusive_scan(S->scan_tmp, tb, d_out_per_read, S->out_off, 0u, (size_t)n_reads, rocprim::plus<uint32_t>(), st));
-	fin_compact_kernel<<<(unsigned)(((size_t)n_reads * 16 + 255) / 256), 256, 0, st>>>(S->work, S->in_off, S->out_off, d_out_per_read, n_reads, d_out);
+	tb = S->scan_tmp.cap;
+	HIPCK(rocprim::exclusive_scan(S->scan_tmp.p, tb, d_out_per_read, S->out_off.p, 0u, (size_t)n_reads, rocprim::plus<uint32_t>(), st));
+	fin_compact_kernel<<<(unsigned)(((size_t)n_reads * 16 + 255) / 256), 256, 0, st>>>(S->work.as<int32_t>(), S->in_off.p, S->out_off.p, d_out_per_read, n_reads, d_out);
 	if (extra) {
-		if (extra->d_dedup_out) fin_compact_kernel<<<(unsigned)(((size_t)n_reads * 16 + 255) / 256), 256, 0, st>>>(A.dedup_out, S->in_off, S->out_off, d_out_per_read, n_reads, extra->d_dedup_out);
-		if (extra->d_out_off) HIPCK(hipMemcpyAsync(extra->d_out_off, S->out_off, 4 * (size_t)n_reads, hipMemcpyDeviceToDevice, st));
-		extra->d_logtab = S->logtab; extra->n_log = FIN_NLOG; extra->d_ctg_off = n_contigs > 1 ? S->ctg : nullptr;
+		if (extra->d_dedup_out) fin_compact_kernel<<<(unsigned)(((size_t)n_reads * 16 + 255) / 256), 256, 0, st>>>(A.dedup_out, S->in_off.p, S->out_off.p, d_out_per_read, n_reads, extra->d_dedup_out);
+		if (extra->d_out_off) HIPCK(hipMemcpyAsync(extra->d_out_off, S->out_off.p, 4 * (size_t)n_reads, hipMemcpyDeviceToDevice, st));
+		extra->d_logtab = S->logtab.p; extra->n_log = FIN_NLOG; extra->d_ctg_off = n_contigs > 1 ? S->ctg.p : nullptr;
 	}
-	HIPCK(hipMemcpyAsync(S->h_pin, S->out_off + (n_reads - 1), 4, hipMemcpyDeviceToHost, st));
-	HIPCK(hipMemcpyAsync(S->h_pin + 1, d_out_per_read + (n_reads - 1), 4, hipMemcpyDeviceToHost, st));
-	HIPCK(hipMemcpyAsync(S->h_pin + 2, S->ctr, 68, hipMemcpyDeviceToHost, st));
+	HIPCK(hipMemcpyAsync(S->h_pin.p, S->out_off.p + (n_reads - 1), 4, hipMemcpyDeviceToHost, st));
+	HIPCK(hipMemcpyAsync(S->h_pin.p + 1, d_out_per_read + (n_reads - 1), 4, hipMemcpyDeviceToHost, st));
+	HIPCK(hipMemcpyAsync(S->h_pin.p + 2, S->ctr.p, 68, hipMemcpyDeviceToHost, st));
 	HIPCK(hipEventRecord(S->ev1, st));
 	HIPCK(hipStreamSynchronize(st));
 	HIPCK(hipGetLastError());
@@ -888,12 +860,12 @@ static int64_t finalize_regs_device_impl(const bmh_index_t *idx, const bmh_chain
 		}
 #endif
 		fprintf(stderr, "[finalize] wave classes one after the other: %.3f / %.3f / %.3f / %.3f / %.3f ms\n", q[0], q[1], q[2], q[3], q[4]);
-		fprintf(stderr, "[finalize] %u reads, %llu regions: lane kernel %.3f ms, wave kernels %.3f ms (%u / %u / %u / %u / %u reads with up to 32 / 128 / 256 / 512 / more regions), scan + compaction %.3f ms\n", n_reads, (unsigned long long)n_regs, a, b, S->h_pin[2], S->h_pin[3], S->h_pin[4], S->h_pin[5], S->h_pin[6], c);
+		fprintf(stderr, "[finalize] %u reads, %llu regions: lane kernel %.3f ms, wave kernels %.3f ms (%u / %u / %u / %u / %u reads with up to 32 / 128 / 256 / 512 / more regions), scan + compaction %.3f ms\n", n_reads, (unsigned long long)n_regs, a, b, S->h_pin.p[2], S->h_pin.p[3], S->h_pin.p[4], S->h_pin.p[5], S->h_pin.p[6], c);
 	}
-	if (S->h_pin[18] != 0) {
-		const uint32_t e = S->h_pin[18];
+	if (S->h_pin.p[18] != 0) {
+		const uint32_t e = S->h_pin.p[18];
 		bmh_set_error("bmh_finalize_regs_device: %s", e == E_LOG ? "a region longer than the logarithm table (65535)" : e == E_DPCAP ? "a patch alignment beyond the kernel's capacity (query side of 1022 bases) or a sort beyond its stack" : "internal error");
 		return BMH_ECAPACITY;
 	}
-	return (int64_t)S->h_pin[0] + (int64_t)S->h_pin[1];
+	return (int64_t)S->h_pin.p[0] + (int64_t)S->h_pin.p[1];
 }

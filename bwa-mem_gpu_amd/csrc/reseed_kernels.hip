@@ -25,6 +25,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include "bmh_internal.h"
+#include "devmem.h"
 #include "fmd_dev.h"
 #include "seed_dev.h"
 
@@ -286,37 +287,12 @@ __global__ void __launch_bounds__(256) reseed_gather_kernel(const uint64_t *__re
 
 // ---------------------------------------------------------------- host side
 
-#define RCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
-
-struct rs_buf_t { void *p = nullptr; size_t bytes = 0; };
-
 struct reseed_state_t {
-	rs_buf_t tsk_off, tasks, list, out2, n2, ovf, list_b, out_b, n2b, off3, out3, n3, keys, keys2, vals, vals2, mk, ms, ra, rk, rocc, roff, tmp;
-	unsigned long long *ctr = nullptr;      // [0] round-2 groups [1] overflowing tasks [2] round-3 groups [3] groups of the second round-2 launch [4] merge cursor
+	dev_buf<uint8_t> tsk_off, tasks, list, out2, n2, ovf, list_b, out_b, n2b, off3, out3, n3, keys, keys2, vals, vals2, mk, ms, ra, rk, rocc, roff, tmp;
+	dev_buf<unsigned long long> ctr;        // [0] round-2 groups [1] overflowing tasks [2] round-3 groups [3] groups of the second round-2 launch [4] merge cursor
 };
 
-static int rs_reserve(rs_buf_t &b, size_t bytes)
-{
-	if (bytes <= b.bytes) return BMH_OK;
-	if (b.p) (void)hipFree(b.p);
-	b.p = nullptr; b.bytes = 0;
-	const size_t cap = bytes + bytes / 4 + 256;
-	if (hipMalloc(&b.p, cap) != hipSuccess) { bmh_set_error("bmh_seed_batch_reseed: no memory for %zu bytes", cap); return BMH_ENOMEM; }
-	b.bytes = cap;
-	return BMH_OK;
-}
-#define RRES(b, n) do { const int rc_ = rs_reserve((b), (size_t)(n)); if (rc_ != BMH_OK) return rc_; } while (0)
-template <class T> static T *P(rs_buf_t &b) { return (T *)b.p; }
-
-void reseed_state_free(reseed_state_t *R)
-{
-	if (!R) return;
-	rs_buf_t *bs[] = {&R->tsk_off, &R->tasks, &R->list, &R->out2, &R->n2, &R->ovf, &R->list_b, &R->out_b, &R->n2b, &R->off3, &R->out3, &R->n3,
-	                  &R->keys, &R->keys2, &R->vals, &R->vals2, &R->mk, &R->ms, &R->ra, &R->rk, &R->rocc, &R->roff, &R->tmp};
-	for (rs_buf_t *b : bs) if (b->p) (void)hipFree(b->p);
-	if (R->ctr) (void)hipFree(R->ctr);
-	delete R;
-}
+void reseed_state_free(reseed_state_t *R) { delete R; }
 
 static inline unsigned rs_nblk(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -324,7 +300,7 @@ int reseed_merge(reseed_state_t **Rp, const reseed_in_t &in, hipStream_t st, res
 {
 	if (!*Rp) {
 		*Rp = new reseed_state_t();
-		if (hipMalloc((void **)&(*Rp)->ctr, 64) != hipSuccess) { bmh_set_error("bmh_seed_batch_reseed: hipMalloc failed"); return BMH_ENOMEM; }
+		RCK((*Rp)->ctr.resize(8));
 	}
 	reseed_state_t &R = **Rp;
 	memset(out, 0, sizeof(*out));
@@ -332,7 +308,7 @@ int reseed_merge(reseed_state_t **Rp, const reseed_in_t &in, hipStream_t st, res
 	const int split_len = (int)(in.min_seed_len * in.opt.split_factor + .499);      // as mem_collect_intv: int * float + .499
 	const uint64_t n_cands = in.n_cands, n_reads = in.n_reads;
 	const bool r3 = in.opt.max_mem_intv > 0;
-	RCHK(hipMemsetAsync(R.ctr, 0, 64, st));
+	HIPCK(hipMemsetAsync(R.ctr.p, 0, 64, st));
 
 	// ---- select the round-2 tasks (scan of the flags) and size the round-3 columns (scan of the bounds): one wait for both totals
 	size_t tb = 0, t2 = 0;
@@ -340,87 +316,87 @@ int reseed_merge(reseed_state_t **Rp, const reseed_in_t &in, hipStream_t st, res
 	auto fit = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), fl);
 	rs_bound_in bd = {in.lens, in.n_reads, k};
 	auto bit = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), bd);
-	RCHK(rocprim::exclusive_scan(nullptr, tb, fit, (uint32_t *)nullptr, 0u, (size_t)n_cands + 1, rocprim::plus<uint32_t>(), st));
-	RCHK(rocprim::exclusive_scan(nullptr, t2, bit, (uint64_t *)nullptr, (uint64_t)0, (size_t)n_reads + 1, rocprim::plus<uint64_t>(), st));
-	RRES(R.tmp, tb > t2 ? tb : t2);
-	RRES(R.tsk_off, 4 * (n_cands + 1));
-	RRES(R.off3, 8 * (n_reads + 1));
-	tb = R.tmp.bytes;
-	RCHK(rocprim::exclusive_scan(R.tmp.p, tb, fit, P<uint32_t>(R.tsk_off), 0u, (size_t)n_cands + 1, rocprim::plus<uint32_t>(), st));
-	if (r3) { tb = R.tmp.bytes; RCHK(rocprim::exclusive_scan(R.tmp.p, tb, bit, P<uint64_t>(R.off3), (uint64_t)0, (size_t)n_reads + 1, rocprim::plus<uint64_t>(), st)); }
+	HIPCK(rocprim::exclusive_scan(nullptr, tb, fit, (uint32_t *)nullptr, 0u, (size_t)n_cands + 1, rocprim::plus<uint32_t>(), st));
+	HIPCK(rocprim::exclusive_scan(nullptr, t2, bit, (uint64_t *)nullptr, (uint64_t)0, (size_t)n_reads + 1, rocprim::plus<uint64_t>(), st));
+	RCK(R.tmp.need(tb > t2 ? tb : t2));
+	RCK(R.tsk_off.need(4 * (n_cands + 1)));
+	RCK(R.off3.need(8 * (n_reads + 1)));
+	tb = R.tmp.cap;
+	HIPCK(rocprim::exclusive_scan(R.tmp.p, tb, fit, R.tsk_off.as<uint32_t>(), 0u, (size_t)n_cands + 1, rocprim::plus<uint32_t>(), st));
+	if (r3) { tb = R.tmp.cap; HIPCK(rocprim::exclusive_scan(R.tmp.p, tb, bit, R.off3.as<uint64_t>(), (uint64_t)0, (size_t)n_reads + 1, rocprim::plus<uint64_t>(), st)); }
 	uint32_t n_tasks = 0; uint64_t n_slots3 = 0;
-	RCHK(hipMemcpyAsync(&n_tasks, P<uint32_t>(R.tsk_off) + n_cands, 4, hipMemcpyDeviceToHost, st));
-	if (r3) RCHK(hipMemcpyAsync(&n_slots3, P<uint64_t>(R.off3) + n_reads, 8, hipMemcpyDeviceToHost, st));
-	RCHK(hipStreamSynchronize(st));
+	HIPCK(hipMemcpyAsync(&n_tasks, R.tsk_off.as<uint32_t>() + n_cands, 4, hipMemcpyDeviceToHost, st));
+	if (r3) HIPCK(hipMemcpyAsync(&n_slots3, R.off3.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost, st));
+	HIPCK(hipStreamSynchronize(st));
 
 	// ---- round 2 (first launch) and round 3
 	if (n_tasks) {
-		RRES(R.tasks, sizeof(rs_task_t) * (size_t)n_tasks);
-		RRES(R.list, 16 * (size_t)n_tasks * RS2_CAP); RRES(R.out2, 16 * (size_t)n_tasks * RS2_CAP);
-		RRES(R.n2, 4 * (size_t)n_tasks); RRES(R.ovf, 4 * (size_t)n_tasks);
-		reseed_task_kernel<<<rs_nblk(n_cands), 256, 0, st>>>(in.res_a, in.occ, n_cands, split_len, in.opt.split_width, P<uint32_t>(R.tsk_off), P<rs_task_t>(R.tasks));
-		reseed_r2_kernel<<<rs_nblk(n_tasks), 256, 0, st>>>(in.f, in.rv, in.lens, k, P<rs_task_t>(R.tasks), nullptr, n_tasks, RS2_CAP,
-		                                                   P<uint4>(R.list), P<uint4>(R.out2), P<uint32_t>(R.n2), P<uint32_t>(R.ovf), R.ctr);
+		RCK(R.tasks.need(sizeof(rs_task_t) * (size_t)n_tasks));
+		RCK(R.list.need(16 * (size_t)n_tasks * RS2_CAP)); RCK(R.out2.need(16 * (size_t)n_tasks * RS2_CAP));
+		RCK(R.n2.need(4 * (size_t)n_tasks)); RCK(R.ovf.need(4 * (size_t)n_tasks));
+		reseed_task_kernel<<<rs_nblk(n_cands), 256, 0, st>>>(in.res_a, in.occ, n_cands, split_len, in.opt.split_width, R.tsk_off.as<uint32_t>(), R.tasks.as<rs_task_t>());
+		reseed_r2_kernel<<<rs_nblk(n_tasks), 256, 0, st>>>(in.f, in.rv, in.lens, k, R.tasks.as<rs_task_t>(), nullptr, n_tasks, RS2_CAP,
+		                                                   R.list.as<uint4>(), R.out2.as<uint4>(), R.n2.as<uint32_t>(), R.ovf.as<uint32_t>(), R.ctr.p);
 	}
 	if (r3) {
-		RRES(R.out3, 16 * (n_slots3 + 1)); RRES(R.n3, 4 * (n_reads + 1));
-		reseed_r3_kernel<<<rs_nblk(n_reads), 256, 0, st>>>(in.f, in.rv, in.lens, k, (uint64_t)in.opt.max_mem_intv, P<uint64_t>(R.off3),
-		                                                   P<uint4>(R.out3), P<uint32_t>(R.n3), R.ctr + 2);
+		RCK(R.out3.need(16 * (n_slots3 + 1))); RCK(R.n3.need(4 * (n_reads + 1)));
+		reseed_r3_kernel<<<rs_nblk(n_reads), 256, 0, st>>>(in.f, in.rv, in.lens, k, (uint64_t)in.opt.max_mem_intv, R.off3.as<uint64_t>(),
+		                                                   R.out3.as<uint4>(), R.n3.as<uint32_t>(), R.ctr.p + 2);
 	}
 	unsigned long long c[5] = {0, 0, 0, 0, 0};
-	RCHK(hipMemcpyAsync(c, R.ctr, 40, hipMemcpyDeviceToHost, st));
-	RCHK(hipStreamSynchronize(st));
+	HIPCK(hipMemcpyAsync(c, R.ctr.p, 40, hipMemcpyDeviceToHost, st));
+	HIPCK(hipStreamSynchronize(st));
 	// ---- the tasks whose forward list did not fit: again, with columns of max_len + 1 entries (the list holds at most len - x)
 	const uint32_t n_ovf = (uint32_t)(c[1] & 0xFFFFFFFFull);
 	const uint32_t cap_b = in.max_len + 1;
 	if (n_ovf) {
-		RRES(R.list_b, 16 * (size_t)n_ovf * cap_b); RRES(R.out_b, 16 * (size_t)n_ovf * cap_b); RRES(R.n2b, 4 * (size_t)n_ovf);
-		reseed_r2_kernel<<<rs_nblk(n_ovf), 256, 0, st>>>(in.f, in.rv, in.lens, k, P<rs_task_t>(R.tasks), P<uint32_t>(R.ovf), n_ovf, cap_b,
-		                                                 P<uint4>(R.list_b), P<uint4>(R.out_b), P<uint32_t>(R.n2b), P<uint32_t>(R.ovf) /* (cannot overflow) */, R.ctr + 3);
-		RCHK(hipMemcpyAsync(&c[3], R.ctr + 3, 8, hipMemcpyDeviceToHost, st));
-		RCHK(hipStreamSynchronize(st));
+		RCK(R.list_b.need(16 * (size_t)n_ovf * cap_b)); RCK(R.out_b.need(16 * (size_t)n_ovf * cap_b)); RCK(R.n2b.need(4 * (size_t)n_ovf));
+		reseed_r2_kernel<<<rs_nblk(n_ovf), 256, 0, st>>>(in.f, in.rv, in.lens, k, R.tasks.as<rs_task_t>(), R.ovf.as<uint32_t>(), n_ovf, cap_b,
+		                                                 R.list_b.as<uint4>(), R.out_b.as<uint4>(), R.n2b.as<uint32_t>(), R.ovf.as<uint32_t>() /* (cannot overflow) */, R.ctr.p + 3);
+		HIPCK(hipMemcpyAsync(&c[3], R.ctr.p + 3, 8, hipMemcpyDeviceToHost, st));
+		HIPCK(hipStreamSynchronize(st));
 	}
 	const uint64_t n1 = in.n_kept, n2 = c[0] + c[3], n3 = c[2], n = n1 + n2 + n3;
 	if (n >> 32) { bmh_set_error("bmh_seed_batch_reseed: more than 2^32 seed groups in one batch"); return BMH_ECAPACITY; }
 	out->n_round[0] = n1; out->n_round[1] = n2; out->n_round[2] = n3;
 
 	// ---- merge: keys of every group, radix sort, columns
-	RRES(R.keys, 8 * (n + 1)); RRES(R.keys2, 8 * (n + 1)); RRES(R.vals, 4 * (n + 1)); RRES(R.vals2, 4 * (n + 1));
-	RRES(R.mk, 8 * (n + 1)); RRES(R.ms, 4 * (n + 1));
-	RRES(R.ra, sizeof(res_t) * (n + 1)); RRES(R.rk, 8 * (n + 1)); RRES(R.rocc, 4 * (n + 1)); RRES(R.roff, 8 * (n + 1));
-	uint64_t *keys = P<uint64_t>(R.keys), *mk = P<uint64_t>(R.mk); uint32_t *vals = P<uint32_t>(R.vals), *ms = P<uint32_t>(R.ms);
+	RCK(R.keys.need(8 * (n + 1))); RCK(R.keys2.need(8 * (n + 1))); RCK(R.vals.need(4 * (n + 1))); RCK(R.vals2.need(4 * (n + 1)));
+	RCK(R.mk.need(8 * (n + 1))); RCK(R.ms.need(4 * (n + 1)));
+	RCK(R.ra.need(sizeof(res_t) * (n + 1))); RCK(R.rk.need(8 * (n + 1))); RCK(R.rocc.need(4 * (n + 1))); RCK(R.roff.need(8 * (n + 1)));
+	uint64_t *keys = R.keys.as<uint64_t>(), *mk = R.mk.as<uint64_t>(); uint32_t *vals = R.vals.as<uint32_t>(), *ms = R.ms.as<uint32_t>();
 	if (n_cands) reseed_copy_r1_kernel<<<rs_nblk(n_cands), 256, 0, st>>>(in.res_a, in.res_k, in.occ, in.occ_off, n_cands, keys, vals, mk, ms);
-	reseed_set_kernel<<<1, 1, 0, st>>>(R.ctr + 4, (unsigned long long)n1);
+	reseed_set_kernel<<<1, 1, 0, st>>>(R.ctr.p + 4, (unsigned long long)n1);
 	if (n_tasks)
-		reseed_copy_out_kernel<<<rs_nblk(n_tasks), 256, 0, st>>>(P<uint4>(R.out2), P<uint32_t>(R.n2), nullptr, RS2_CAP, n_tasks, P<rs_task_t>(R.tasks), nullptr,
-		                                                         R.ctr + 4, keys, vals, mk, ms);
+		reseed_copy_out_kernel<<<rs_nblk(n_tasks), 256, 0, st>>>(R.out2.as<uint4>(), R.n2.as<uint32_t>(), nullptr, RS2_CAP, n_tasks, R.tasks.as<rs_task_t>(), nullptr,
+		                                                         R.ctr.p + 4, keys, vals, mk, ms);
 	if (n_ovf)
-		reseed_copy_out_kernel<<<rs_nblk(n_ovf), 256, 0, st>>>(P<uint4>(R.out_b), P<uint32_t>(R.n2b), nullptr, cap_b, n_ovf, P<rs_task_t>(R.tasks), P<uint32_t>(R.ovf),
-		                                                       R.ctr + 4, keys, vals, mk, ms);
+		reseed_copy_out_kernel<<<rs_nblk(n_ovf), 256, 0, st>>>(R.out_b.as<uint4>(), R.n2b.as<uint32_t>(), nullptr, cap_b, n_ovf, R.tasks.as<rs_task_t>(), R.ovf.as<uint32_t>(),
+		                                                       R.ctr.p + 4, keys, vals, mk, ms);
 	if (r3)
-		reseed_copy_out_kernel<<<rs_nblk(n_reads), 256, 0, st>>>(P<uint4>(R.out3), P<uint32_t>(R.n3), P<uint64_t>(R.off3), 0u, (uint32_t)n_reads, nullptr, nullptr,
-		                                                         R.ctr + 4, keys, vals, mk, ms);
+		reseed_copy_out_kernel<<<rs_nblk(n_reads), 256, 0, st>>>(R.out3.as<uint4>(), R.n3.as<uint32_t>(), R.off3.as<uint64_t>(), 0u, (uint32_t)n_reads, nullptr, nullptr,
+		                                                         R.ctr.p + 4, keys, vals, mk, ms);
 	int end_bit = 33;
 	while (end_bit < 64 && (n_reads >> (end_bit - 32)) != 0) ++end_bit;
 	size_t ts = 0, tsc = 0, tsr = 0;
-	RCHK(rocprim::radix_sort_pairs(nullptr, ts, keys, P<uint64_t>(R.keys2), vals, P<uint32_t>(R.vals2), (size_t)n, 0, end_bit, st));
-	RCHK(rocprim::exclusive_scan(nullptr, tsc, P<uint32_t>(R.rocc), P<uint64_t>(R.roff), (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
-	RCHK(rocprim::exclusive_scan(nullptr, tsr, in.n_ref_pos, in.prefix, 0u, (size_t)n_reads, rocprim::plus<uint32_t>(), st));
+	HIPCK(rocprim::radix_sort_pairs(nullptr, ts, keys, R.keys2.as<uint64_t>(), vals, R.vals2.as<uint32_t>(), (size_t)n, 0, end_bit, st));
+	HIPCK(rocprim::exclusive_scan(nullptr, tsc, R.rocc.as<uint32_t>(), R.roff.as<uint64_t>(), (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+	HIPCK(rocprim::exclusive_scan(nullptr, tsr, in.n_ref_pos, in.prefix, 0u, (size_t)n_reads, rocprim::plus<uint32_t>(), st));
 	if (tsc > ts) ts = tsc;
 	if (tsr > ts) ts = tsr;
-	RRES(R.tmp, ts);
-	if (n) { tb = R.tmp.bytes; RCHK(rocprim::radix_sort_pairs(R.tmp.p, tb, keys, P<uint64_t>(R.keys2), vals, P<uint32_t>(R.vals2), (size_t)n, 0, end_bit, st)); }
-	RCHK(hipMemsetAsync(in.n_ref_pos, 0, 4 * n_reads, st));
-	reseed_gather_kernel<<<rs_nblk(n + 1), 256, 0, st>>>(P<uint64_t>(R.keys2), P<uint32_t>(R.vals2), n, mk, ms, P<res_t>(R.ra), P<uint64_t>(R.rk), P<uint32_t>(R.rocc), in.n_ref_pos);
-	tb = R.tmp.bytes;
-	RCHK(rocprim::exclusive_scan(R.tmp.p, tb, P<uint32_t>(R.rocc), P<uint64_t>(R.roff), (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
-	tb = R.tmp.bytes;
-	RCHK(rocprim::exclusive_scan(R.tmp.p, tb, in.n_ref_pos, in.prefix, 0u, (size_t)n_reads, rocprim::plus<uint32_t>(), st));
+	RCK(R.tmp.need(ts));
+	if (n) { tb = R.tmp.cap; HIPCK(rocprim::radix_sort_pairs(R.tmp.p, tb, keys, R.keys2.as<uint64_t>(), vals, R.vals2.as<uint32_t>(), (size_t)n, 0, end_bit, st)); }
+	HIPCK(hipMemsetAsync(in.n_ref_pos, 0, 4 * n_reads, st));
+	reseed_gather_kernel<<<rs_nblk(n + 1), 256, 0, st>>>(R.keys2.as<uint64_t>(), R.vals2.as<uint32_t>(), n, mk, ms, R.ra.as<res_t>(), R.rk.as<uint64_t>(), R.rocc.as<uint32_t>(), in.n_ref_pos);
+	tb = R.tmp.cap;
+	HIPCK(rocprim::exclusive_scan(R.tmp.p, tb, R.rocc.as<uint32_t>(), R.roff.as<uint64_t>(), (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+	tb = R.tmp.cap;
+	HIPCK(rocprim::exclusive_scan(R.tmp.p, tb, in.n_ref_pos, in.prefix, 0u, (size_t)n_reads, rocprim::plus<uint32_t>(), st));
 	uint64_t tot = 0;
-	RCHK(hipMemcpyAsync(&tot, P<uint64_t>(R.roff) + n, 8, hipMemcpyDeviceToHost, st));
-	RCHK(hipStreamSynchronize(st));
-	RCHK(hipGetLastError());
-	out->res_a = P<res_t>(R.ra); out->res_k = P<uint64_t>(R.rk); out->occ = P<uint32_t>(R.rocc); out->occ_off = P<uint64_t>(R.roff);
+	HIPCK(hipMemcpyAsync(&tot, R.roff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+	HIPCK(hipStreamSynchronize(st));
+	HIPCK(hipGetLastError());
+	out->res_a = R.ra.as<res_t>(); out->res_k = R.rk.as<uint64_t>(); out->occ = R.rocc.as<uint32_t>(); out->occ_off = R.roff.as<uint64_t>();
 	out->n = n; out->n_occ = tot;
 	return BMH_OK;
 }

@@ -11,8 +11,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include "bmh_internal.h"
-
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
+#include "devmem.h"
 
 namespace {
 

@@ -40,6 +40,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include "bmh_internal.h"
+#include "devmem.h"
 #include "wtrace.h"
 #include "fmd_dev.h"
 #include "seed_dev.h"
@@ -771,8 +772,6 @@ __global__ void __launch_bounds__(256) smem_gather_kernel(const cand_t *__restri
 }
 
 // ---------------------------------------------------------------- host side
-
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { bmh_set_error("%s: %s", #x, hipGetErrorString(e_)); return BMH_ENODEV; } } while (0)
 
 struct bmh_seed_ws {
 	uint32_t max_reads; uint64_t max_bases, max_cands, max_occ;
