@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include "bmh_internal.h"
 #include "devmem.h"
+#include "sam_core.h"
 
 namespace {
 
@@ -21,21 +22,16 @@ struct sel_args_t {
 	int flag_all, sa, max_XA_hits, max_XA_hits_alt; double drop;
 };
 
-// bmh_sam_need_cigar (csrc/sam_format.cpp), one RECORD per lane (a record carries its read in field [0]; a lane per read spent its time in the
-// serial loops of the few reads with hundreds of records): first cnt[k] = hits listed under primary k (bit 31: one of them on an ALT contig),
-// then need = reported, or an XA candidate whose primary lists no more hits than the XA limits allow (src/bwamem_extra.c:125)
-__device__ __forceinline__ int sel_pri(const sel_args_t &A, const int32_t *a, int i)
-{
-	const int k = a[16 * i + A.sa];
-	return (k >= 0 && (double)a[16 * i + 1] >= (double)a[16 * k + 1] * A.drop) ? k : -1;
-}
+// bmh_sam_need_cigar (csrc/sam_format.cpp) by the same two rules of csrc/sam_core.h, one RECORD per lane (a record carries its read in field [0]; a lane per read
+// spent its time in the serial loops of the few reads with hundreds of records): first cnt[k] = hits listed under primary k (bit 31: one of them on an ALT contig),
+// then need = reported, or an XA candidate whose primary lists no more hits than the XA limits allow
 __global__ void __launch_bounds__(256) sam_count_kernel(sel_args_t A, uint64_t m)
 {
 	const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
 	if (g >= m) return;
 	const uint32_t r = (uint32_t)A.fin[16 * g];
 	const uint64_t base = A.off[r];
-	const int k = sel_pri(A, A.fin + 16 * base, (int)(g - base));
+	const int k = sam_core::xa_primary(A.fin + 16 * base, (int)(g - base), A.sa, A.drop);
 	if (k >= 0) {
 		atomicAdd(A.cnt + base + (uint64_t)k, 1u);
 		if (A.fin[16 * g + 15] & 2) atomicOr(A.cnt + base + (uint64_t)k, 0x80000000u);
@@ -50,11 +46,10 @@ __global__ void __launch_bounds__(256) sam_select_kernel(sel_args_t A, uint64_t 
 	const int i = (int)(g - base);
 	uint32_t need = (A.fin[16 * g + 15] & 1) ? 1u : 0u;
 	if (!A.flag_all) {
-		const int k = sel_pri(A, A.fin + 16 * base, i);
+		const int k = sam_core::xa_primary(A.fin + 16 * base, i, A.sa, A.drop);
 		if (k >= 0) {
 			const uint32_t c = A.cnt[base + (uint64_t)k];
-			const int n = (int)(c & 0x7FFFFFFFu); const bool has_alt = c >> 31;
-			if (!(n > A.max_XA_hits_alt || (!has_alt && n > A.max_XA_hits))) need = 1u;
+			if (sam_core::xa_listed((int)(c & 0x7FFFFFFFu), c >> 31, A.max_XA_hits, A.max_XA_hits_alt)) need = 1u;
 		}
 	}
 	if (A.h_rec && A.h_rec[r] == i) need = 1u;                   // pairs: the read's own alignment lends its mate the mate fields
@@ -187,7 +182,8 @@ extern "C" int bmh_cigar_pack(const int32_t *d_aln, const uint32_t *d_cigar, int
 // 1506-1683; mem_gen_alt, src/bwamem_extra.c:97-150), one read per lane, two passes over the same code: the first counts the bytes of every
 // read's records, a scan places them, the second writes.  On the host the text of a million reads was 0.9 s of CPU time (14 ms on 64
 // threads) and needed the records, the alignments and the CIGAR / MD arrays in host memory: 300 MB of copies for 230 MB of text.  Here the
-// text is the only thing that leaves the device.  Without ALT contigs (their soft clips and the pa:f tag stay with the host formatter).
+// text is the only thing that leaves the device.  What a record says is csrc/sam_core.h (read_records), shared with the host formatter: ALT-mode
+// records (soft clips on ALT hits, the larger XA limit, pa:f) included.
 namespace {
 
 struct sam_args_t {
@@ -200,277 +196,75 @@ struct sam_args_t {
 	int copy_comment;              // -C with comments given (d.d_comments): every record ends with its read's comment
 };
 
-// where the text goes: W = 0 counts the bytes, 1 writes them to global memory, 2 into the wave's image in LDS (copied out in dwords afterwards:
-// a lane's byte stores to global memory are one memory transaction each, 230 M of them for a million reads)
+// where the text goes: sam_core::count_out counts the bytes, ptr_out<char *> writes them to global memory, ptr_out<sam_lds_char *> into the wave's image in LDS
+// (copied out in dwords afterwards: a lane's byte stores to global memory are one memory transaction each, 230 M of them for a million reads)
 typedef __attribute__((address_space(3))) char sam_lds_char;
-template <int W> struct sam_ptr_t { typedef char *type; };
-template <> struct sam_ptr_t<2> { typedef sam_lds_char *type; };
-template <int W> struct sam_out_t {
-	typename sam_ptr_t<W>::type p; uint32_t n;
-	__device__ __forceinline__ void ch(char c) { if (W) *p++ = c; else ++n; }
-	__device__ __forceinline__ void str(const char *s, int len) { if (W) { for (int i = 0; i < len; ++i) *p++ = s[i]; } else n += (uint32_t)len; }   // len bytes, from global memory
-	template <int N> __device__ __forceinline__ void lit(const char (&s)[N]) { for (int i = 0; i < N - 1; ++i) ch(s[i]); }
-	__device__ void num(long long v)                                                             // put_int
-	{
-		unsigned long long u = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
-		if (v < 0) ch('-');
-		int nd = 1;
-		for (unsigned long long t = u; t >= 10; t /= 10) ++nd;
-		if (W) { typename sam_ptr_t<W>::type q = p + nd; do { *--q = (char)('0' + u % 10); u /= 10; } while (u); p += nd; }
-		else n += (uint32_t)nd;
-	}
-};
 
-// a / b as printf("%.3f") writes it (the pa:f tag, src/bwamem.c:1663): the double nearest to a / b, rounded to three decimals from its EXACT value, ties to even
-// -- m x 2^e x 1000 in integers
-template <int W> __device__ void sam_fmt3(sam_out_t<W> &o, int a, int b)
-{
-#pragma clang fp contract(off)
-	const double x = (double)a / (double)b;
-	unsigned long long q = 0;
-	if (x > 0.) {
-		const unsigned long long bits = (unsigned long long)__double_as_longlong(x);
-		const int ex = (int)(bits >> 52 & 0x7FF);
-		const unsigned long long m = ex ? (bits & 0xFFFFFFFFFFFFFull) | 1ull << 52 : (bits & 0xFFFFFFFFFFFFFull);
-		const int e = (ex ? ex : 1) - 1075;                         // x = m * 2^e
-		const unsigned long long N = m * 1000ull;                   // < 2^63
-		if (e >= 0) q = N << e;                                     // (not reached for a ratio of two scores)
-		else if (-e >= 64) q = 0;
-		else {
-			const int sft = -e;
-			q = N >> sft;
-			const unsigned long long rem = N & ((1ull << sft) - 1), half = 1ull << (sft - 1);
-			if (rem > half || (rem == half && (q & 1))) ++q;
+// sam_core's Src over the device arrays: ASCII reads, name blobs with [n + 1] offsets (NUL-terminated back to back: no strlen), 32-bit slots, packed words
+struct sam_src_t {
+	const sam_args_t &A;
+	struct read_t {
+		const sam_args_t &A; uint64_t base; int n; const int32_t *fin;
+		__device__ __forceinline__ sam_core::aln_t aln(int i) const
+		{
+			sam_core::aln_t x; x.aln = nullptr; x.cigar = nullptr; x.md = nullptr;
+			const int32_t s = A.d.d_slot[base + (uint64_t)i];
+			if (s >= 0) {
+				x.aln = A.d.d_aln + 8 * (size_t)s;
+				if (x.aln[7] & ~2) { x.aln = nullptr; return x; }       // (an alignment bmh_cigar_batch flagged has no words in the packed array)
+				x.cigar = A.d.d_packed + A.d.d_cig_off[s]; x.md = (const char *)(x.cigar + x.aln[3]);
+			}
+			return x;
 		}
+	};
+	__device__ __forceinline__ read_t read(uint32_t r) const { const uint64_t base = A.rec_off[r]; return read_t{A, base, (int)A.d.d_fin_per_read[r], A.d.d_fin + 16 * base}; }
+	__device__ __forceinline__ bool flag_all() const { return A.flag_all; }
+	__device__ __forceinline__ bool softclip() const { return A.softclip; }
+	__device__ __forceinline__ int sa() const { return A.sa; }
+	__device__ __forceinline__ double drop() const { return A.drop; }
+	__device__ __forceinline__ int max_XA_hits() const { return A.max_XA_hits; }
+	__device__ __forceinline__ int max_XA_hits_alt() const { return A.max_XA_hits_alt; }
+	__device__ __forceinline__ const char *rg() const { return A.rg; }
+	__device__ __forceinline__ int rg_len() const { return A.rg_len; }
+	__device__ __forceinline__ bool paired() const { return A.d.d_h_rec != nullptr; }
+	__device__ __forceinline__ int h_rec(uint32_t r) const { return A.d.d_h_rec[r]; }
+	__device__ __forceinline__ int unflag(uint32_t r) const { return A.d.d_unflag ? A.d.d_unflag[r] : 0; }
+	__device__ __forceinline__ int md_len(const sam_core::aln_t &x) const { return x.aln[6]; }
+	__device__ __forceinline__ const char *name(uint32_t r) const { return A.d.d_names + A.d.d_name_off[r]; }
+	__device__ __forceinline__ int name_len(uint32_t r) const { return (int)(A.d.d_name_off[r + 1] - A.d.d_name_off[r]) - 1; }
+	__device__ __forceinline__ int l_seq(uint32_t r) const { return (int)A.d.d_lens[r]; }
+	__device__ __forceinline__ const uint8_t *seq(uint32_t r) const { return A.d.d_reads + A.d.d_offs[r]; }
+	__device__ __forceinline__ const uint8_t *qual(uint32_t r) const { return A.d.d_quals ? A.d.d_quals + A.d.d_offs[r] : nullptr; }       // (FASTQ: the qualities at the letters' offsets)
+	__device__ __forceinline__ const char *comment(uint32_t r, int &len) const                                                        // (-C: NUL-terminated back to back like the names)
+	{
+		if (!A.copy_comment) return nullptr;
+		len = (int)(A.d.d_comment_off[r + 1] - A.d.d_comment_off[r]) - 1;
+		return A.d.d_comments + A.d.d_comment_off[r];
 	}
-	o.num((long long)(q / 1000));
-	o.ch('.');
-	const int f = (int)(q % 1000);
-	o.ch((char)('0' + f / 100)); o.ch((char)('0' + f / 10 % 10)); o.ch((char)('0' + f % 10));
-}
-
-struct sam_rec_t { const int32_t *fin; const int32_t *aln; const uint32_t *cigar; const char *md; };
-
-__device__ __forceinline__ sam_rec_t sam_rec(const sam_args_t &A, uint64_t base, int i)
-{
-	sam_rec_t x; x.fin = A.d.d_fin + 16 * (base + (uint64_t)i);
-	const int32_t s = A.d.d_slot[base + (uint64_t)i];
-	x.aln = nullptr; x.cigar = nullptr; x.md = nullptr;
-	if (s >= 0) {
-		x.aln = A.d.d_aln + 8 * (size_t)s;
-		if (x.aln[7] & ~2) { x.aln = nullptr; return x; }       // (an alignment bmh_cigar_batch flagged has no words in the packed array)
-		x.cigar = A.d.d_packed + A.d.d_cig_off[s]; x.md = (const char *)(x.cigar + x.aln[3]);
-	}
-	return x;
-}
-__device__ __forceinline__ long long sam_pos(const int32_t *a) { return (long long)(uint32_t)a[0] | (long long)a[1] << 32; }
-__device__ __forceinline__ int sam_rid(const sam_args_t &A, long long pos)
-{
-	if (A.d.n_contigs <= 1) return 0;
-	int lo = 0, hi = A.d.n_contigs;
-	while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (A.d.d_contig_offset[mid] <= pos) lo = mid; else hi = mid; }
-	return lo;
-}
-__device__ __forceinline__ long long sam_ctg0(const sam_args_t &A, int rid) { return A.d.n_contigs > 1 ? A.d.d_contig_offset[rid] : 0; }
-__device__ __forceinline__ const char *sam_ctg(const sam_args_t &A, int rid) { return A.d.d_contig_names + A.d.d_contig_name_off[rid]; }
-__device__ __forceinline__ int sam_ctg_len(const sam_args_t &A, int rid) { return (int)(A.d.d_contig_name_off[rid + 1] - A.d.d_contig_name_off[rid]) - 1; }
-template <int W> __device__ void sam_cigar(sam_out_t<W> &o, const sam_rec_t &r, bool hard)
-{
-	const int n = r.aln[3];
-	for (int i = 0; i < n; ++i) {
-		int c = (int)(r.cigar[i] & 0xf);
-		if (hard && (c == 3 || c == 4)) c = 4;
-		o.num(r.cigar[i] >> 4);
-		o.ch("MIDSH"[c]);
-	}
-}
-__device__ __forceinline__ int sam_ref_len(int n, const uint32_t *cg)
-{
-	int l = 0;
-	for (int k = 0; k < n; ++k) { const int op = (int)(cg[k] & 0xf); if (op == 0 || op == 2) l += (int)(cg[k] >> 4); }
-	return l;
-}
-__device__ __forceinline__ int sam_nt4(uint8_t c)            // nst_nt4_table as far as the text needs it: A C G T in either case, everything else N
-{
-	c &= 0xDF;
-	return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4;
-}
-// the letter SEQ shows for a read's letter: upper case, N for everything that is not A C G T; complemented on the reverse strand
-__device__ __forceinline__ char sam_letter(uint8_t c, bool rev)
-{
-	c &= 0xDF;
-	const bool a = c == 'A', cc = c == 'C', g = c == 'G', t = c == 'T';
-	if (!rev) return (a || cc || g || t) ? (char)c : 'N';
-	return a ? 'T' : cc ? 'G' : g ? 'C' : t ? 'A' : 'N';
-}
-template <int W> __device__ void sam_seq(sam_out_t<W> &o, const uint8_t *seq, int qb, int qe, bool rev)
-{
-	if (qe <= qb) return;
-	if (!W) { o.n += (uint32_t)(qe - qb); return; }
+	// the letter SEQ shows for a read's letter: upper case, N for everything that is not A C G T; complemented on the reverse strand
 	// (eight letters in flight at a time, and the whole wave copying read after read in coalesced steps, were both tried: the writing pass is bound
 	// by its two waves per SIMD -- 16 KB of LDS per wave -- and the dependent loads of the records, not by these bytes)
-	if (!rev) for (int k = qb; k < qe; ++k) *o.p++ = sam_letter(seq[k], false);
-	else for (int k = qe - 1; k >= qb; --k) *o.p++ = sam_letter(seq[k], true);
-}
-
-// QUAL: the qualities of [qb, qe) as they are, reversed (not complemented) on the reverse strand -- a byte store per lane, like SEQ
-template <int W> __device__ void sam_qual(sam_out_t<W> &o, const uint8_t *q, int qb, int qe, bool rev)
-{
-	if (qe <= qb) return;
-	if (!W) { o.n += (uint32_t)(qe - qb); return; }
-	if (!rev) for (int k = qb; k < qe; ++k) *o.p++ = (char)q[k];
-	else for (int k = qe - 1; k >= qb; --k) *o.p++ = (char)q[k];
-}
-
-struct sam_mate_t { int rid; long long pos; int is_rev, n_cigar; const uint32_t *cigar; };
-
-template <int W> __device__ void sam_mate_fields(const sam_args_t &A, sam_out_t<W> &o, bool pe, int p_rid, long long p_pos, int p_rev, int p_ncig, const uint32_t *p_cig,
-                                                  bool mate_mapped, int m_rid, long long m_pos, int m_rev, int m_ncig, const uint32_t *m_cig)
-{
-	if (pe && mate_mapped) {
-		if (p_rid == m_rid) o.ch('='); else o.str(sam_ctg(A, m_rid), sam_ctg_len(A, m_rid));
-		o.ch('\t'); o.num(m_pos - sam_ctg0(A, m_rid) + 1); o.ch('\t');
-		if (p_rid == m_rid) {
-			const long long p0 = p_pos + (p_rev ? sam_ref_len(p_ncig, p_cig) - 1 : 0), p1 = m_pos + (m_rev ? sam_ref_len(m_ncig, m_cig) - 1 : 0);
-			if (m_ncig == 0 || p_ncig == 0) o.ch('0');
-			else o.num(-(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0)));
-		} else o.ch('0');
-	} else o.lit("*\t0\t0");
-	o.ch('\t');
-}
-
-// the records of read r (the body of bmh_format_sam_parts' loop); false: a record the text needs has no alignment
-template <int W> __device__ bool sam_read(const sam_args_t &A, uint32_t r, sam_out_t<W> &out)
-{
-	const uint64_t base = A.rec_off[r];
-	const int n = (int)A.d.d_fin_per_read[r];
-	const int32_t *a = A.d.d_fin + 16 * base;
-	const bool pe = A.d.d_h_rec != nullptr;
-	sam_mate_t m; m.rid = -1; m.pos = 0; m.is_rev = 0; m.n_cigar = 0; m.cigar = nullptr;
-	if (pe) {
-		const uint32_t mr = r ^ 1u;
-		const int h = A.d.d_h_rec[mr];
-		if (h >= 0) {
-			const sam_rec_t y = sam_rec(A, A.rec_off[mr], h);
-			if (!y.aln) return false;
-			m.pos = sam_pos(y.aln); m.rid = sam_rid(A, m.pos); m.is_rev = y.aln[2]; m.n_cigar = y.aln[3]; m.cigar = y.cigar;
-		}
+	__device__ __forceinline__ char letter(uint8_t c, bool rev) const
+	{
+		c &= 0xDF;
+		const bool a = c == 'A', cc = c == 'C', g = c == 'G', t = c == 'T';
+		if (!rev) return (a || cc || g || t) ? (char)c : 'N';
+		return a ? 'T' : cc ? 'G' : g ? 'C' : t ? 'A' : 'N';
 	}
-	const char *name = A.d.d_names + A.d.d_name_off[r];
-	const int name_len = (int)(A.d.d_name_off[r + 1] - A.d.d_name_off[r]) - 1;     // (names are NUL-terminated back to back: no strlen)
-	const uint8_t *seq = A.d.d_reads + A.d.d_offs[r];
-	const uint8_t *qual = A.d.d_quals ? A.d.d_quals + A.d.d_offs[r] : nullptr;       // (FASTQ: the qualities at the letters' offsets)
-	const char *cmt = nullptr; int cmt_len = 0;                                       // (-C: the read's comment, NUL-terminated back to back like the names)
-	if (A.copy_comment) { cmt = A.d.d_comments + A.d.d_comment_off[r]; cmt_len = (int)(A.d.d_comment_off[r + 1] - A.d.d_comment_off[r]) - 1; }
-	const int l_seq = (int)A.d.d_lens[r];
-	int n_rep = 0;
-	for (int i = 0; i < n; ++i) n_rep += a[16 * i + 15] & 1;
-	if (n_rep == 0) {                                           // unmapped record (mem_reg2sam's aa.n == 0 branch)
-		int flag = 4 | (A.d.d_unflag ? A.d.d_unflag[r] : 0);
-		const bool mm = pe && m.rid >= 0;
-		if (pe && m.rid < 0) flag |= 8;
-		const int p_rev = mm ? m.is_rev : 0;
-		if (p_rev) flag |= 0x10;
-		if (mm && m.is_rev) flag |= 0x20;
-		out.str(name, name_len); out.ch('\t'); out.num(flag); out.ch('\t');
-		if (mm) { out.str(sam_ctg(A, m.rid), sam_ctg_len(A, m.rid)); out.ch('\t'); out.num(m.pos - sam_ctg0(A, m.rid) + 1); out.lit("\t0\t*\t"); }
-		else out.lit("*\t0\t0\t*\t");
-		sam_mate_fields<W>(A, out, pe, mm ? m.rid : -1, m.pos, p_rev, 0, nullptr, mm, m.rid, m.pos, m.is_rev, m.n_cigar, m.cigar);
-		sam_seq<W>(out, seq, 0, l_seq, p_rev != 0);
-		out.ch('\t');
-		if (qual) sam_qual<W>(out, qual, 0, l_seq, p_rev != 0); else out.ch('*');
-		out.lit("\tAS:i:0\tXS:i:0");
-		if (A.rg_len) { out.lit("\tRG:Z:"); out.str(A.rg, A.rg_len); }
-		if (cmt_len > 0) { out.ch('\t'); out.str(cmt, cmt_len); }
-		out.ch('\n');
-		return true;
-	}
-	auto pri = [&](int i) { const int k = a[16 * i + A.sa]; return (k >= 0 && (double)a[16 * i + 1] >= (double)a[16 * k + 1] * A.drop) ? k : -1; };
-	int which = 0;
-	for (int i = 0; i < n; ++i) {
-		if (!(a[16 * i + 15] & 1)) continue;
-		const sam_rec_t x = sam_rec(A, base, i);
-		if (!x.aln) return false;
-		const long long pos = sam_pos(x.aln);
-		const int rid = sam_rid(A, pos);
-		const bool mate_mapped = pe && m.rid >= 0;
-		const int m_rid = mate_mapped ? m.rid : rid; const long long m_pos = mate_mapped ? m.pos : pos; const int m_rev = mate_mapped ? m.is_rev : (x.aln[2] ? 1 : 0);
-		int flag = (x.aln[2] ? 0x10 : 0) | x.fin[14];
-		if (pe) { if (m.rid < 0) flag |= 8; if (m_rev) flag |= 0x20; }
-		const bool hard = which > 0 && !A.softclip && !(x.fin[15] & 2);
-		out.str(name, name_len); out.ch('\t'); out.num((flag & 0xffff) | (flag & 0x10000 ? 0x100 : 0)); out.ch('\t');
-		out.str(sam_ctg(A, rid), sam_ctg_len(A, rid)); out.ch('\t'); out.num(pos - sam_ctg0(A, rid) + 1); out.ch('\t');
-		out.num(x.fin[13]); out.ch('\t');
-		if (x.aln[3]) sam_cigar<W>(out, x, hard); else out.ch('*');
-		out.ch('\t');
-		sam_mate_fields<W>(A, out, pe, rid, pos, x.aln[2] ? 1 : 0, x.aln[3], x.cigar, pe, m_rid, m_pos, m_rev, mate_mapped ? m.n_cigar : 0, mate_mapped ? m.cigar : nullptr);
-		if (flag & 0x100) out.lit("*\t*");
-		else {
-			int qb = 0, qe = l_seq;
-			const int nc = x.aln[3];
-			if (nc && hard) {
-				const int c0 = (int)(x.cigar[0] & 0xf), c1 = (int)(x.cigar[nc - 1] & 0xf);
-				if (!x.aln[2]) { if (c0 == 3 || c0 == 4) qb += x.cigar[0] >> 4; if (c1 == 3 || c1 == 4) qe -= x.cigar[nc - 1] >> 4; }
-				else { if (c0 == 3 || c0 == 4) qe -= x.cigar[0] >> 4; if (c1 == 3 || c1 == 4) qb += x.cigar[nc - 1] >> 4; }
-			}
-			sam_seq<W>(out, seq, qb, qe, x.aln[2] != 0);
-			out.ch('\t');
-			if (qual) sam_qual<W>(out, qual, qb, qe, x.aln[2] != 0); else out.ch('*');
-		}
-		if (x.aln[3]) { out.lit("\tNM:i:"); out.num(x.aln[4]); out.lit("\tMD:Z:"); out.str(x.md, x.aln[6]); }
-		if (x.fin[1] >= 0) { out.lit("\tAS:i:"); out.num(x.fin[1]); }
-		if (!(flag & 0x100) && x.fin[10] >= 0) { out.lit("\tXS:i:"); out.num(x.fin[10]); }
-		if (A.rg_len) { out.lit("\tRG:Z:"); out.str(A.rg, A.rg_len); }      // src/bwamem.c:1631-1634
-		if (!(flag & 0x100)) {
-			bool other = false;
-			for (int j = 0; j < n; ++j) if (j != i && (a[16 * j + 15] & 1) && !(a[16 * j + 14] & 0x100)) other = true;
-			if (other) {
-				out.lit("\tSA:Z:");
-				for (int j = 0; j < n; ++j) {
-					if (j == i || !(a[16 * j + 15] & 1) || (a[16 * j + 14] & 0x100)) continue;
-					const sam_rec_t y = sam_rec(A, base, j);
-					if (!y.aln) return false;
-					const long long p2 = sam_pos(y.aln);
-					const int rid2 = sam_rid(A, p2);
-					out.str(sam_ctg(A, rid2), sam_ctg_len(A, rid2)); out.ch(','); out.num(p2 - sam_ctg0(A, rid2) + 1); out.ch(',');
-					out.ch("+-"[y.aln[2] ? 1 : 0]); out.ch(',');
-					sam_cigar<W>(out, y, false);
-					out.ch(','); out.num(y.fin[13]); out.ch(','); out.num(y.aln[4]); out.ch(';');
-				}
-			}
-		}
-		if (!(flag & 0x100) && (x.fin[15] >> 2) > 0) { out.lit("\tpa:f:"); sam_fmt3<W>(out, x.fin[1], x.fin[15] >> 2); }      // score / score of the ALT hit that shadows it
-		if (!A.flag_all) {                                       // the XA tag of this record: the hits listed under it (mem_gen_alt)
-			int cnt = 0; bool has_alt = false;
-			for (int j = 0; j < n; ++j) if (pri(j) == i) { ++cnt; has_alt = has_alt || (a[16 * j + 15] & 2); }
-			if (cnt > 0 && !(cnt > A.max_XA_hits_alt || (!has_alt && cnt > A.max_XA_hits))) {         // src/bwamem_extra.c:125
-				out.lit("\tXA:Z:");
-				for (int j = 0; j < n; ++j) {
-					if (pri(j) != i) continue;
-					const sam_rec_t y = sam_rec(A, base, j);
-					if (!y.aln) return false;
-					const long long p2 = sam_pos(y.aln);
-					const int rid2 = sam_rid(A, p2);
-					out.str(sam_ctg(A, rid2), sam_ctg_len(A, rid2)); out.ch(','); out.ch("+-"[y.aln[2] ? 1 : 0]); out.num(p2 - sam_ctg0(A, rid2) + 1); out.ch(',');
-					sam_cigar<W>(out, y, false);
-					out.ch(','); out.num(y.aln[4]); out.ch(';');
-				}
-			}
-		}
-		if (cmt_len > 0) { out.ch('\t'); out.str(cmt, cmt_len); }              // src/bwamem.c:1670-1673
-		out.ch('\n');
-		++which;
-	}
-	return true;
-}
+	__device__ __forceinline__ int n_contigs() const { return A.d.n_contigs; }
+	__device__ __forceinline__ long long ctg_off(int i) const { return A.d.d_contig_offset[i]; }
+	__device__ __forceinline__ long long ctg0(int rid) const { return A.d.n_contigs > 1 ? A.d.d_contig_offset[rid] : 0; }
+	__device__ __forceinline__ const char *ctg(int rid) const { return A.d.d_contig_names + A.d.d_contig_name_off[rid]; }
+	__device__ __forceinline__ int ctg_len(int rid) const { return (int)(A.d.d_contig_name_off[rid + 1] - A.d.d_contig_name_off[rid]) - 1; }
+};
 
 // first pass: the bytes of every read's records
 __global__ void __launch_bounds__(256) sam_text_count_kernel(sam_args_t A)
 {
 	const uint32_t r = blockIdx.x * 256u + threadIdx.x;
 	if (r >= A.d.n_reads) return;
-	sam_out_t<0> o; o.p = nullptr; o.n = 0;
-	const bool ok = sam_read<0>(A, r, o);
+	sam_core::count_out o;
+	const bool ok = sam_core::read_records(sam_src_t{A}, r, o) < 0;
 	if (!ok) atomicOr(A.err, 1u);
 	A.len[r] = ok ? o.n : 0u;
 }
@@ -507,9 +301,8 @@ __global__ void __launch_bounds__(256) sam_text_write_kernel(sam_args_t A)
 		if (t1 - t0 + a <= SAM_LDS_WAVE) {
 			sam_lds_char *img = (sam_lds_char *)lds[wv] + a;
 			if (mine) {
-				sam_out_t<2> o; o.n = 0;
-				o.p = img + (uint32_t)(A.text_off[r] - t0);
-				const bool ok = sam_read<2>(A, r, o);
+				sam_core::ptr_out<sam_lds_char *> o{img + (uint32_t)(A.text_off[r] - t0)};
+				const bool ok = sam_core::read_records(sam_src_t{A}, r, o) < 0;
 				if (ok && (uint32_t)(o.p - img) != (uint32_t)(A.text_off[r + 1] - t0)) atomicOr(A.err, 2u);   // (the two passes disagree: internal error)
 				if (!ok) { atomicOr(A.err, 1u); }
 			}
@@ -528,8 +321,8 @@ __global__ void __launch_bounds__(256) sam_text_write_kernel(sam_args_t A)
 			__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 			__builtin_amdgcn_s_waitcnt(0xC07F);                                       // (the copy has read the image before the next part overwrites it)
 		} else if (mine) {
-			sam_out_t<1> o; o.p = A.text + A.text_off[r]; o.n = 0;
-			const bool ok = sam_read<1>(A, r, o);
+			sam_core::ptr_out<char *> o{A.text + A.text_off[r]};
+			const bool ok = sam_core::read_records(sam_src_t{A}, r, o) < 0;
 			if (!ok) atomicOr(A.err, 1u);
 			else if ((uint64_t)(o.p - A.text) != A.text_off[r + 1]) atomicOr(A.err, 2u);
 		}
