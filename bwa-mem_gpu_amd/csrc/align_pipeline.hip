@@ -387,6 +387,17 @@ int patch_alt_reads(const aligner_t &A, lane_t &Ln, const bmh_dev_jobs_t &dj, co
 	return BMH_OK;
 }
 
+// The single-end tail of a batch of interleaved pairs in the form the pairing kernel reads (regs_core.h: alt_keep_sub_n), with the regions behind mem_sort_dedup_patch
+// (d_dedup) and the first record of every read (d_roff) beside the records; *ex: the tail's logarithm table and contig offsets for bmh_pair_device
+int64_t pair_tail_device(const bmh_index_t *idx, const bmh_chain_opt_t *co, const bmh_ext_params_t *ep, const bmh_post_opt_t *po, const uint8_t *d_reads, const uint32_t *d_offs, uint32_t n,
+                         const int32_t *d_regs, uint64_t nr, const uint32_t *d_rpr, const float *d_frac_rep, int n_contigs, const int64_t *ctg_off, int32_t *d_fin, int32_t *d_dedup,
+                         uint32_t *d_opr, uint32_t *d_roff, void *st, bmh_fin_extra_t *ex)
+{
+	memset(ex, 0, sizeof(*ex));
+	ex->d_dedup_out = d_dedup; ex->d_out_off = d_roff; ex->alt_keep_sub_n = 1;
+	return bmh_finalize_regs_device_ex(idx, co, ep, po, d_reads, d_offs, n, d_regs, nr, d_rpr, d_frac_rep, n_contigs, n_contigs > 1 ? ctg_off : nullptr, d_fin, d_opr, st, ex);
+}
+
 // Interleaved pairs with mem_pair / mem_sam_pe's choices on the device (csrc/pair_dev.hip) for the pairs the mate rescue does not touch: the single-end tail
 // for every read (mem_sort_dedup_patch, mem_mark_primary_se, mem_reg2sam's selection) with a copy of the regions behind mem_sort_dedup_patch for the host;
 // the host computes the insert-size statistics and finds the pairs the rescue touches (bmh_finalize_pairs_split), the device pairs the others meanwhile;
@@ -416,10 +427,9 @@ int pairs_on_device(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, co
 	const double t0 = now_s();
 	RCK(Ln.d_fin.need(16 * (nr + 1))); RCK(Ln.d_opr.need(n + 1)); RCK(Ln.d_dedup.need(16 * (nr + 1))); RCK(Ln.d_roff.need(n + 1));
 	RCK(Ln.d_hrec.need(n + 1)); RCK(Ln.d_unflag.need(n + 1)); RCK(Ln.d_todo.need(n / 2 + 1)); RCK(Ln.h_todo.need(n / 2 + 1));
-	bmh_fin_extra_t ex; memset(&ex, 0, sizeof(ex));
-	ex.d_dedup_out = Ln.d_dedup.p; ex.d_out_off = Ln.d_roff.p; ex.alt_keep_sub_n = 1;
-	const int64_t m1 = bmh_finalize_regs_device_ex(A.idx, &A.co, &A.ep, &po, Ln.d_reads.p, Ln.d_offs.p, n, Ln.d_regs.p, nr, dj.d_regs_per_read, dj.d_frac_rep,
-	                                               A.n_contigs, A.n_contigs > 1 ? A.off.data() : nullptr, Ln.d_fin.p, Ln.d_opr.p, Ln.st, &ex);
+	bmh_fin_extra_t ex;
+	const int64_t m1 = pair_tail_device(A.idx, &A.co, &A.ep, &po, Ln.d_reads.p, Ln.d_offs.p, n, Ln.d_regs.p, nr, dj.d_regs_per_read, dj.d_frac_rep, A.n_contigs, A.off.data(),
+	                                    Ln.d_fin.p, Ln.d_dedup.p, Ln.d_opr.p, Ln.d_roff.p, Ln.st, &ex);
 	if (m1 < 0) return (int)m1;
 	RCK(Ln.h_regs.need(16 * ((size_t)m1 + 1))); RCK(Ln.h_rpr.need(n + 1)); RCK(Ln.h_fr.need(n + 1));
 	if (m1) HIPCK(hipMemcpyAsync(Ln.h_regs.p, Ln.d_dedup.p, 64 * (size_t)m1, hipMemcpyDeviceToHost, Ln.st));
@@ -442,8 +452,8 @@ int pairs_on_device(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, co
 	RCK(R.opr.need(n + 1)); R.h_rec.resize(n); R.unflag.resize(n);
 	for (int attempt = 0; attempt < 4 && mh == BMH_ECAPACITY; ++attempt, cap *= 4) {
 		// (a second attempt repeats the device's pair kernel on records it has changed already: they are restored first)
-		if (attempt) { bmh_fin_extra_t ex2 = ex; const int64_t m2 = bmh_finalize_regs_device_ex(A.idx, &A.co, &A.ep, &po, Ln.d_reads.p, Ln.d_offs.p, n, Ln.d_regs.p, nr, dj.d_regs_per_read, dj.d_frac_rep,
-		                                               A.n_contigs, A.n_contigs > 1 ? A.off.data() : nullptr, Ln.d_fin.p, Ln.d_opr.p, Ln.st, &ex2); if (m2 != m1) return m2 < 0 ? (int)m2 : BMH_EINVAL; }
+		if (attempt) { bmh_fin_extra_t ex2; const int64_t m2 = pair_tail_device(A.idx, &A.co, &A.ep, &po, Ln.d_reads.p, Ln.d_offs.p, n, Ln.d_regs.p, nr, dj.d_regs_per_read, dj.d_frac_rep, A.n_contigs, A.off.data(),
+		                                                                        Ln.d_fin.p, Ln.d_dedup.p, Ln.d_opr.p, Ln.d_roff.p, Ln.st, &ex2); if (m2 != m1) return m2 < 0 ? (int)m2 : BMH_EINVAL; }
 		RCK(R.fin.need(16 * (size_t)cap));
 		mh = bmh_finalize_pairs_split(A.idx, Ln.d_reads.p, Ln.d_offs.p, Ln.st, &A.co, &A.ep, &po, &A.pe, A.l_pac, A.pac, n, codes, offs64, rs.lens + b0,
 		                              Ln.h_regs.p, Ln.h_rpr.p, Ln.h_fr.p, A.n_contigs, A.n_contigs > 1 ? A.off.data() : nullptr, A.n_contigs > 1 ? A.len.data() : nullptr,
@@ -480,9 +490,9 @@ int pairs_on_device(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, co
 	*d_fin_out = Ln.d_fin2.p;
 	R.m = m;
 	if (prof) {
-		uint32_t n1 = 0, n2 = 0, n3 = 0;
-		for (uint32_t q = 0; q < n / 2; ++q) { n1 += Ln.h_todo.p[q] == 1; n2 += Ln.h_todo.p[q] == 2; n3 += Ln.h_todo.p[q] == 3; }
-		fprintf(stderr, "[pairs] handed back by the device: %u pairs with a score too close to an integer, %u beyond %d hits, %u with a hit on an ALT contig\n", n1, n2, bmh_pair_limit(), n3);
+		uint32_t n1 = 0, n2 = 0;                                      // (the kernel writes 0, 1 or 2: a pair with a hit on an ALT contig is not handed back)
+		for (uint32_t q = 0; q < n / 2; ++q) { n1 += Ln.h_todo.p[q] == 1; n2 += Ln.h_todo.p[q] == 2; }
+		fprintf(stderr, "[pairs] handed back by the device: %u pairs with a score too close to an integer, %u beyond %d hits\n", n1, n2, bmh_pair_limit());
 	}
 	if (prof) fprintf(stderr, "[pairs] on the device: single-end tail + regions to the host %.1f ms, host (statistics, rescue, %u of %u pairs walked) %.1f ms, merge %.1f ms\n",
 	                  (t1 - t0) * 1e3, nt, n / 2, (t2 - t1) * 1e3, (now_s() - t2) * 1e3);
@@ -797,6 +807,23 @@ struct fbatch_t {
 }   // namespace
 
 extern "C" {
+
+// For the tests (csrc/bmh_internal.h): the device's part of pairs_on_device -- the tail, then the pairing kernel -- on the caller's arrays and statistics.
+int64_t bmh_pairs_device_records(const bmh_index_t *idx, const bmh_chain_opt_t *copt, const bmh_ext_params_t *ep, const bmh_post_opt_t *popt, const bmh_pe_opt_t *pe,
+                                 const double *pes, const uint8_t *d_reads, const uint32_t *d_offs, uint32_t n_reads, const int32_t *d_regs, uint64_t n_regs,
+                                 const uint32_t *d_regs_per_read, const float *d_frac_rep, int n_contigs, const int64_t *contig_offset,
+                                 int32_t *d_fin, int32_t *d_dedup, uint32_t *d_opr, uint32_t *d_off, int32_t *d_h_rec, int32_t *d_unflag, uint8_t *d_todo, void *stream)
+{
+	if (!idx || !copt || !ep || !popt || !pe || !pes || !d_fin || !d_dedup || !d_opr || !d_off || !d_h_rec || !d_unflag || !d_todo) { bmh_set_error("bmh_pairs_device_records: null argument"); return BMH_EINVAL; }
+	if ((n_reads & 1) || (popt->id0 & 1)) { bmh_set_error("bmh_pairs_device_records: an odd number of reads or an odd id0 (pairs are interleaved)"); return BMH_EINVAL; }
+	bmh_fin_extra_t ex;
+	const int64_t m = pair_tail_device(idx, copt, ep, popt, d_reads, d_offs, n_reads, d_regs, n_regs, d_regs_per_read, d_frac_rep, n_contigs, contig_offset,
+	                                   d_fin, d_dedup, d_opr, d_off, stream, &ex);
+	if (m < 0) return m;
+	RCK(bmh_pair_device(copt, ep, popt, pe, pes, (int64_t)idx->dev.l_pac, n_contigs, ex.d_ctg_off, ex.d_logtab, ex.n_log, d_fin, d_opr, d_off, d_frac_rep, n_reads, d_h_rec, d_unflag, d_todo, stream));
+	HIPCK(hipStreamSynchronize((hipStream_t)stream));
+	return m;
+}
 
 // (lanes and result objects stay with the aligner between runs: their workspaces and pinned buffers -- gigabytes for million-read batches
 // -- cost more to allocate than a batch costs to align)

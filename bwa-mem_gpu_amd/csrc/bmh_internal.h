@@ -116,6 +116,24 @@ extern "C" int bmh_reads_last_counts(uint64_t *out);
 void bmh_pump_inflate_counts(const bmh_reads_pump_t *p, uint64_t out[2]);
 void bmh_reads_note_inflate_counts(const uint64_t *c);
 extern "C" int bmh_reads_last_inflate_counts(uint64_t *out);
+// csrc/pair_dev.hip, csrc/align_pipeline.hip: the device's pairing stage with C linkage -- for the tests, not part of the public interface.
+// bmh_pair_limit: the hits of a pair's two reads together the pairing kernel takes; the merge, its counts and the scan: see the definitions.
+// bmh_pairs_device_records: what the aligner does for a batch of interleaved pairs before the host's split walk, with the insert-size statistics
+// given (pes [4][5] = low, high, failed, avg, std): the single-end tail in the form the pairing kernel reads, then the pairing kernel.  Device pointers:
+// reads (ASCII) / offsets, regions [n_regs][8], regions per read, frac_rep; contig_offset: host.  Out (device): d_fin [n_regs][16], d_dedup [n_regs][16]
+// (the regions behind mem_sort_dedup_patch: scratch here), d_opr / d_off / d_h_rec / d_unflag [n_reads], d_todo [n_reads / 2].  popt->id0 must be even.
+// Returns the record count or a negative status; waits for the stream.
+extern "C" int bmh_pair_limit(void);
+extern "C" int bmh_pair_merge_counts(uint32_t n_reads, const uint32_t *d_todo_pairs, uint32_t n_todo, int32_t *d_slot, const uint32_t *d_opr_dev, const int32_t *d_h_dev, const int32_t *d_uf_dev,
+                                     const uint32_t *d_opr_host, const int32_t *d_h_host, const int32_t *d_uf_host, uint32_t *d_opr, int32_t *d_h, int32_t *d_uf, void *stream);
+extern "C" int bmh_pair_merge_records(uint32_t n_reads, const int32_t *d_slot, const int32_t *d_fin_dev, const uint32_t *d_off_dev, const int32_t *d_fin_host, const uint32_t *d_off_host,
+                                      const uint32_t *d_opr, const uint32_t *d_off, int32_t *d_fin, void *stream);
+extern "C" size_t bmh_pair_scan_bytes(uint32_t n);
+extern "C" int bmh_pair_scan(const uint32_t *d_in, uint32_t *d_out, uint32_t n, void *d_tmp, size_t tmp_bytes, void *stream);
+extern "C" int64_t bmh_pairs_device_records(const bmh_index_t *idx, const bmh_chain_opt_t *copt, const bmh_ext_params_t *ep, const bmh_post_opt_t *popt, const bmh_pe_opt_t *pe,
+                                            const double *pes, const uint8_t *d_reads, const uint32_t *d_offs, uint32_t n_reads, const int32_t *d_regs, uint64_t n_regs,
+                                            const uint32_t *d_regs_per_read, const float *d_frac_rep, int n_contigs, const int64_t *contig_offset,
+                                            int32_t *d_fin, int32_t *d_dedup, uint32_t *d_opr, uint32_t *d_off, int32_t *d_h_rec, int32_t *d_unflag, uint8_t *d_todo, void *stream);
 // ---- interleaved pairs with mem_pair / mem_sam_pe's choices on the device (csrc/pair_dev.hip) for the pairs the mate rescue does not touch
 // The host call (csrc/pair_post.cpp: bmh_finalize_pairs_split = bmh_finalize_pairs_deduped on a subset) tells the caller the insert-size statistics as
 // soon as it has them (after_pestat: the caller starts the device's pair kernel), asks before its own final walk which pairs the device handed back
@@ -138,13 +156,7 @@ int64_t bmh_finalize_pairs_split(const bmh_index_t *idx, const uint8_t *d_reads,
 int bmh_pair_device(const bmh_chain_opt_t *copt, const bmh_ext_params_t *ep, const bmh_post_opt_t *popt, const bmh_pe_opt_t *pe, const double *pes, int64_t l_pac,
                     int n_contigs, const int64_t *d_ctg_off, const double *d_logtab, int n_log, int32_t *d_fin, const uint32_t *d_opr, const uint32_t *d_off,
                     const float *d_frac_rep, uint32_t n_reads, int32_t *d_h_rec, int32_t *d_unflag, uint8_t *d_todo, void *stream);
-int bmh_pair_limit(void);
-int bmh_pair_merge_counts(uint32_t n_reads, const uint32_t *d_todo_pairs, uint32_t n_todo, int32_t *d_slot, const uint32_t *d_opr_dev, const int32_t *d_h_dev, const int32_t *d_uf_dev,
-                          const uint32_t *d_opr_host, const int32_t *d_h_host, const int32_t *d_uf_host, uint32_t *d_opr, int32_t *d_h, int32_t *d_uf, void *stream);
-int bmh_pair_merge_records(uint32_t n_reads, const int32_t *d_slot, const int32_t *d_fin_dev, const uint32_t *d_off_dev, const int32_t *d_fin_host, const uint32_t *d_off_host,
-                           const uint32_t *d_opr, const uint32_t *d_off, int32_t *d_fin, void *stream);
-size_t bmh_pair_scan_bytes(uint32_t n);
-int bmh_pair_scan(const uint32_t *d_in, uint32_t *d_out, uint32_t n, void *d_tmp, size_t tmp_bytes, void *stream);
+// (bmh_pair_limit, the merge and the scan: C linkage, declared beside bmh_reads_last_counts above)
 // bmh_finalize_regs on a subset of a batch's reads: read_ids[r] = the read's index in its batch (hash seed, record field [0]); NULL = r
 int64_t bmh_finalize_regs_ids(const bmh_chain_opt_t *copt, const bmh_ext_params_t *ep, const bmh_post_opt_t *popt, int64_t l_pac,
                               const uint8_t *pac, uint32_t n_reads, const uint8_t *reads, const uint64_t *read_offs,

@@ -33,7 +33,8 @@ struct pd_args_t {
 	int32_t *fin; const uint32_t *opr; const uint32_t *off; const float *frac_rep;
 	uint32_t n_pairs; int64_t id0;
 	int32_t *h_rec, *unflag; uint8_t *todo;
-	int alt_mode;                   // the index has ALT contigs: a pair with a hit on one is the host's (todo = 3); the others leave as ALT-mode records ([11] = [12])
+	int alt_mode;                   // the index has ALT contigs: the kernel pairs the hits of the primary assembly, adds the best ALT hit as a supplementary record and
+	                                // leaves ALT-mode records ([11] = [12]).  A pair with an ALT hit stays the device's: todo is 0, 1 or 2, there is no other value
 };
 
 __device__ __forceinline__ int pd_infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t *dist)      // mem_infer_dir
@@ -141,6 +142,7 @@ __global__ void __launch_bounds__(64) pair_kernel(pd_args_t A)
 				const int score_un = a[0][0].v[1] + a[1][0].v[1] - A.pe.pen_unpaired;
 				subo = subo > score_un ? subo : score_un;
 				q_pe = pd_raw_mapq(o - subo, x.ep.a);
+				// (n_sub + 1 >= n_log takes 65 535 candidate pairs: out of reach while a lane takes PD_NMAX hits, so no test asks for it)
 				if (n_sub > 0) { if (n_sub + 1 >= x.n_log) { A.todo[p] = 2; return; } q_pe -= (int)(4.343 * x.logtab[n_sub + 1] + .499); }
 				if (q_pe < 0) q_pe = 0;
 				if (q_pe > 60) q_pe = 60;
@@ -285,11 +287,11 @@ int bmh_pair_device(const bmh_chain_opt_t *copt, const bmh_ext_params_t *ep, con
 	return BMH_OK;
 }
 
-int bmh_pair_limit(void) { return PD_NMAX; }
+extern "C" int bmh_pair_limit(void) { return PD_NMAX; }
 
 // d_slot [n_reads] int32 scratch; the host's compact arrays (already on the device): d_todo_pairs [n_todo], d_fin_host, d_opr_host / d_off_host / d_h_host /
 // d_uf_host [2 n_todo].  First call: counts (d_opr, d_h, d_uf final); the caller scans d_opr into d_off; second call: the records.  Asynchronous.
-int bmh_pair_merge_counts(uint32_t n_reads, const uint32_t *d_todo_pairs, uint32_t n_todo, int32_t *d_slot, const uint32_t *d_opr_dev, const int32_t *d_h_dev, const int32_t *d_uf_dev,
+extern "C" int bmh_pair_merge_counts(uint32_t n_reads, const uint32_t *d_todo_pairs, uint32_t n_todo, int32_t *d_slot, const uint32_t *d_opr_dev, const int32_t *d_h_dev, const int32_t *d_uf_dev,
                           const uint32_t *d_opr_host, const int32_t *d_h_host, const int32_t *d_uf_host, uint32_t *d_opr, int32_t *d_h, int32_t *d_uf, void *stream)
 {
 	hipStream_t st = (hipStream_t)stream;
@@ -304,7 +306,7 @@ int bmh_pair_merge_counts(uint32_t n_reads, const uint32_t *d_todo_pairs, uint32
 	HIPCK(hipGetLastError());
 	return BMH_OK;
 }
-int bmh_pair_merge_records(uint32_t n_reads, const int32_t *d_slot, const int32_t *d_fin_dev, const uint32_t *d_off_dev, const int32_t *d_fin_host, const uint32_t *d_off_host,
+extern "C" int bmh_pair_merge_records(uint32_t n_reads, const int32_t *d_slot, const int32_t *d_fin_dev, const uint32_t *d_off_dev, const int32_t *d_fin_host, const uint32_t *d_off_host,
                            const uint32_t *d_opr, const uint32_t *d_off, int32_t *d_fin, void *stream)
 {
 	if (n_reads == 0) return BMH_OK;
@@ -318,8 +320,8 @@ int bmh_pair_merge_records(uint32_t n_reads, const int32_t *d_slot, const int32_
 }
 
 // an exclusive scan of n words for the callers above (d_tmp: bmh_pair_scan_bytes(n) bytes of device memory)
-size_t bmh_pair_scan_bytes(uint32_t n) { return scan_tmp_bytes<uint32_t, uint32_t>((size_t)n + 1); }
-int bmh_pair_scan(const uint32_t *d_in, uint32_t *d_out, uint32_t n, void *d_tmp, size_t tmp_bytes, void *stream)
+extern "C" size_t bmh_pair_scan_bytes(uint32_t n) { return scan_tmp_bytes<uint32_t, uint32_t>((size_t)n + 1); }
+extern "C" int bmh_pair_scan(const uint32_t *d_in, uint32_t *d_out, uint32_t n, void *d_tmp, size_t tmp_bytes, void *stream)
 {
 	if (n == 0) return BMH_OK;
 	size_t tb = tmp_bytes;
