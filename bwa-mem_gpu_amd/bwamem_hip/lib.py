@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "bmh_pe_opt_default", "bmh_finalize_pairs", "bmh_finalize_pairs_dev", "bmh_dedup_regs_device", "bmh_finalize_pairs_deduped", "bmh_rescue_check_counts", "bmh_sam_need_cigar_pe", "bmh_format_sam_pe",
     "bmh_chain_opt_default", "bmh_chain_last_timing", "bmh_build_jobs", "bmh_jobs_free", "bmh_jobs_sizes", "bmh_jobs_arrays", "bmh_merge_regs",
     "bmh_chain_ws_create", "bmh_chain_ws_free", "bmh_chain_set_contigs", "bmh_chain_set_alt", "bmh_effective_cpus", "bmh_aligner_create", "bmh_aligner_free", "bmh_aligner_run", "bmh_aligner_run_fasta", "bmh_chain_set_materialize", "bmh_chain_batch",
-    "bmh_chain_extend", "bmh_chain_merge", "bmh_chain_extend_merge", "bmh_chain_extend_merge_timing", "bmh_cigar_batch", "bmh_cigar_release",
+    "bmh_chain_extend", "bmh_chain_merge", "bmh_chain_extend_merge", "bmh_chain_extend_merge_timing", "bmh_chain_class_counts", "bmh_cigar_batch", "bmh_cigar_release",
     "bmh_sam_select_work", "bmh_sam_select_device", "bmh_cigar_pack_work", "bmh_cigar_pack_sizes", "bmh_cigar_pack", "bmh_sam_text_work", "bmh_sam_text_sizes", "bmh_sam_text_write", "bmh_sam_text_check",
     "bwt_destroy_gpu", "bwt_restore_sa_gpu", "bwt_restore_bwt_gpu", "gpu_cpy_wrapper",
     "pre_calc_seed_intervals_wrapper", "free_gpuseed_data", "seed_gpu", "seed_gpu_last_n_reads",
@@ -906,6 +906,8 @@ def load_library() -> C.CDLL:
     L.bmh_chain_extend_merge_timing.restype = C.c_int
     L.bmh_chain_extend_merge_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), _u64p]
     L.bmh_chain_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.bmh_chain_class_counts.restype = C.c_int
+    L.bmh_chain_class_counts.argtypes = [C.c_void_p, _u32p]
     L.bmh_chain_merge.restype = C.c_int
     L.bmh_chain_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bmh_cigar_batch.restype = C.c_int
@@ -1146,6 +1148,15 @@ class ChainWorkspace:
         ms = (C.c_float * 8)()
         load_library().bmh_chain_last_timing(self.handle, ms)
         return {"classify": ms[0], "lane": ms[1], "wave": ms[2], "to_counts": ms[3], "reads_small_scratch": int(ms[6]), "reads_large_scratch": int(ms[7])}
+
+    def class_counts(self) -> np.ndarray:
+        """bmh_chain_class_counts: which form chained how many reads of the last batch -- [0..11) the size classes of the cooperative kernels,
+        [11..15) the need bins of the lane kernel, [15] the reads of the long-read kernel"""
+        L = load_library()
+        out = np.zeros(16, np.uint32)
+        if L.bmh_chain_class_counts(self.handle, _np_ptr(out, _u32p)) != 0:
+            raise RuntimeError("bmh_chain_class_counts: " + _err(L))
+        return out
 
     def merge(self, out3_t, regs_t, stream: int = 0) -> None:
         L = load_library()

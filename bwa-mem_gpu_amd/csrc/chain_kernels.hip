@@ -349,13 +349,16 @@ struct emit_args_t {
 	uint32_t n_reads;
 	uint32_t reg_base, job_base;      // added to reg_off / job_off (second pass of bmh_chain_extend_merge)
 	const uint32_t *need; uint32_t thresh; int pass;      // need != nullptr: only the reads of one pass count (pass 1: need > thresh, pass 0: the others)
+	const uint32_t *lane_need; uint32_t lane_thresh;      // need of every read and the lane kernel's threshold: a read within it is on no list of emit_wave_kernel
 	ch_outreg_t *outregs;
 	uint32_t *qlen, *tlen, *h0, *job_read, *job_reg, *job_side, *jq_src; int64_t *jt0;
 	uint32_t qcap; uint32_t *over;    // the longest query side beyond qcap (the extension cap of the workspace) goes to *over: the batch is refused
 };
 
 // (reads with more regions than this are emitted by a wave each, emit_wave_kernel: a repetitive read has up to max_occ regions per
-// SMEM, and one lane writing a thousand job descriptors one after the other was what the second extension pass waited for)
+// SMEM, and one lane writing a thousand job descriptors one after the other was what the second extension pass waited for --
+// but for the reads of the lane kernel, which are on none of that kernel's lists: with a lane threshold beyond this number
+// (BMH_CHAIN_HEAVY) such a read can have more regions, and a lane emits them all)
 #define CH_EMIT_LANE_MAX 32
 __global__ void __launch_bounds__(256) emit_kernel(emit_args_t A)
 {
@@ -363,7 +366,7 @@ __global__ void __launch_bounds__(256) emit_kernel(emit_args_t A)
 	const uint32_t r = blockIdx.x * 256u + threadIdx.x;
 	if (r >= A.n_reads) return;
 	const uint32_t nr = (A.need && (A.need[r] > A.thresh) != (A.pass == 1)) ? 0u : A.regs_per_read[r];
-	if (nr == 0 || nr > CH_EMIT_LANE_MAX) return;
+	if (nr == 0 || (nr > CH_EMIT_LANE_MAX && A.lane_need[r] > A.lane_thresh)) return;
 	const ch_reg_t *R = A.regs + A.prefix[r];
 	uint32_t g = A.reg_base + A.reg_off[r], j = A.job_base + A.job_off[r];
 	const uint32_t roff = A.read_offs[r]; const int lq_ = (int)A.read_lens[r];
@@ -506,6 +509,10 @@ __global__ void __launch_bounds__(256) merge_kernel(const ch_outreg_t *__restric
 
 // ------------------------------------------------------------------------------------------------ workspace / API
 
+// words of h_pin that hold counters [32..38) of the batch: the reads per need bin, the longest read, the reads of chain_long_kernel (one copy)
+#define CH_PIN_BINS 44
+#define CH_PIN_MAXLEN (CH_PIN_BINS + CH_N_BINS)
+#define CH_PIN_LONG (CH_PIN_BINS + CH_N_BINS + 1)
 #define CH_EXT_QMAX 768u           // the longest query side of the extension's classes below the long-query ones (extend_kernels.hip: 64 x EXT_WIDE_MAX_C)
 struct bmh_chain_ws {
 	uint32_t max_reads; uint64_t max_seeds;
@@ -525,6 +532,7 @@ struct bmh_chain_ws {
 	void *scan_tmp; size_t scan_tmp_bytes;
 	uint64_t n_regs, n_jobs;
 	uint32_t *h_pin;               // pinned host words for the small D2H copies
+	uint32_t class_counts[16];     // reads of the last batch per size class [0..CH_N_CLASSES), per need bin of the lane kernel [CH_N_CLASSES..+CH_N_BINS), long reads [15] (bmh_chain_class_counts)
 	bmh_chain_opt_t last_opt;      // the options of the last batch (the merge kernels' score of a bare seed depends on them)
 	hipStream_t side; hipEvent_t ev_fork, ev_join;   // the wave kernels run beside the lane kernel
 	hipStream_t st_hi;                // bmh_chain_extend_merge: classification, lane kernel and counts (what the first extension pass waits for) at the highest priority
@@ -637,6 +645,21 @@ extern "C" void bmh_chain_last_timing(const bmh_chain_ws_t *w, float ms[8])
 	ms[4] = w->ms[4]; ms[5] = w->ms[5];
 	ms[6] = ms[7] = 0.f;                                       // reads chained by a wave: up to 512 entries / beyond
 	for (int c = 0; c < CH_N_CLASSES; ++c) ms[c <= 6 ? 6 : 7] += (float)w->heavy_per_class[c];
+}
+
+// which form chained how many reads of the last batch (tests: every size class and bin is seen to run)
+static void chain_note_counts(bmh_chain_ws *w)
+{
+	static_assert(CH_N_CLASSES + CH_N_BINS + 1 == 16, "bmh_chain_class_counts: 16 words");
+	for (int c = 0; c < CH_N_CLASSES; ++c) w->class_counts[c] = w->h_pin[2 + c];
+	for (int b = 0; b < CH_N_BINS; ++b) w->class_counts[CH_N_CLASSES + b] = w->h_pin[CH_PIN_BINS + b];
+	w->class_counts[CH_N_CLASSES + CH_N_BINS] = w->h_pin[CH_PIN_LONG];
+}
+extern "C" int bmh_chain_class_counts(const bmh_chain_ws_t *w, uint32_t out[16])
+{
+	if (!w || !out) { bmh_set_error("bmh_chain_class_counts: null argument"); return BMH_EINVAL; }
+	memcpy(out, w->class_counts, sizeof(w->class_counts));
+	return BMH_OK;
 }
 
 extern "C" int bmh_chain_set_contigs(bmh_chain_ws_t *w, int n_contigs, const int64_t *offset, const int32_t *len)
@@ -780,6 +803,10 @@ static int chain_launch_t(bmh_chain_ws *w, const chain_args_t &A, hipStream_t st
 	const unsigned wave_prio = (unsigned)bmh_tune("CHAIN_WAVE_PRIO", 0);      // bit c: the waves of size class c raise their priority (s_setprio 3)
 	const unsigned sub_mask = (unsigned)bmh_tune("CHAIN_SUB", (1 << CH_N_SUB) - 1);
 	const bool sub_ctg = w->n_contigs > 1 && w->n_contigs <= CH_SUB_LDS_CONTIGS;
+	// test knob CHAIN_GRID_MAX (0: none): at most that many blocks per launch of the four-per-wave and the wave kernels, so that a block strides over its class's
+	// list and chains read after read through the same scratch at a few reads per class (tests/test_chain_classes_gpu.py)
+	const uint32_t grid_max = (uint32_t)bmh_tune("CHAIN_GRID_MAX", 0);
+	const auto grid_of = [grid_max](uint32_t g) { return grid_max && grid_max < g ? grid_max : g; };
 	if (sub_mask) {
 		const int mx = (int)(4 * (size_t)CH_CLASS_CAP[CH_N_SUB - 1] * ch_lds_entry_bytes<ch_wide_ty>(false));
 		HIPCK(hipFuncSetAttribute(sub_ctg ? (const void *)chain_sub_kernel<CH_SUB_LDS_CONTIGS, FLT> : (const void *)chain_sub_kernel<0, FLT>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
@@ -793,8 +820,8 @@ static int chain_launch_t(bmh_chain_ws *w, const chain_args_t &A, hipStream_t st
 		if (replay >> cls & 1u) { }                                                                                       // (ablation: the class's stored output stands)
 		else if (cls < CH_N_SUB && (sub_mask >> cls & 1u)) {                                                              // four reads per wave (blocks beyond the list leave at once)
 			const size_t sub_lds = 4 * (size_t)lds_cap * ch_lds_entry_bytes<TY>(false);
-			if (sub_ctg) chain_sub_kernel<CH_SUB_LDS_CONTIGS, FLT><<<CH_SUB_GRID[cls], 64, sub_lds, w->cls_stream[cls]>>>(A, (uint32_t)cls, lds_cap);
-			else chain_sub_kernel<0, FLT><<<CH_SUB_GRID[cls], 64, sub_lds, w->cls_stream[cls]>>>(A, (uint32_t)cls, lds_cap);
+			if (sub_ctg) chain_sub_kernel<CH_SUB_LDS_CONTIGS, FLT><<<grid_of(CH_SUB_GRID[cls]), 64, sub_lds, w->cls_stream[cls]>>>(A, (uint32_t)cls, lds_cap);
+			else chain_sub_kernel<0, FLT><<<grid_of(CH_SUB_GRID[cls]), 64, sub_lds, w->cls_stream[cls]>>>(A, (uint32_t)cls, lds_cap);
 		}
 		else if (cls < 2) {                                                                                               // (round-5 form: a lane per read over the class's list)
 			const int ll = bmh_tune("CHAIN_LIST_LANES", CH_LIST_LANES);
@@ -803,9 +830,9 @@ static int chain_launch_t(bmh_chain_ws *w, const chain_args_t &A, hipStream_t st
 			if (list_private && !FLT) chain_lane_list_kernel<FLT, 32><<<lgrid, 256, 0, w->cls_stream[cls]>>>(A, (uint32_t)cls, lanes);
 			else chain_lane_list_kernel<FLT, 0><<<lgrid, 256, 0, w->cls_stream[cls]>>>(A, (uint32_t)cls, lanes);
 		}
-		else if (ctg_lds == 64) chain_wave_kernel<64, FLT><<<CH_CLASS_GRID[cls], 64, lds_bytes, w->cls_stream[cls]>>>(A, (uint32_t)cls, lds_cap, hybrid, (int)(wave_prio >> cls & 1u));
-		else if (ctg_lds) chain_wave_kernel<CH_LDS_CONTIGS, FLT><<<CH_CLASS_GRID[cls], 64, lds_bytes, w->cls_stream[cls]>>>(A, (uint32_t)cls, lds_cap, hybrid, (int)(wave_prio >> cls & 1u));
-		else chain_wave_kernel<0, FLT><<<CH_CLASS_GRID[cls], 64, lds_bytes, w->cls_stream[cls]>>>(A, (uint32_t)cls, lds_cap, hybrid, (int)(wave_prio >> cls & 1u));
+		else if (ctg_lds == 64) chain_wave_kernel<64, FLT><<<grid_of(CH_CLASS_GRID[cls]), 64, lds_bytes, w->cls_stream[cls]>>>(A, (uint32_t)cls, lds_cap, hybrid, (int)(wave_prio >> cls & 1u));
+		else if (ctg_lds) chain_wave_kernel<CH_LDS_CONTIGS, FLT><<<grid_of(CH_CLASS_GRID[cls]), 64, lds_bytes, w->cls_stream[cls]>>>(A, (uint32_t)cls, lds_cap, hybrid, (int)(wave_prio >> cls & 1u));
+		else chain_wave_kernel<0, FLT><<<grid_of(CH_CLASS_GRID[cls]), 64, lds_bytes, w->cls_stream[cls]>>>(A, (uint32_t)cls, lds_cap, hybrid, (int)(wave_prio >> cls & 1u));
 		HIPCK(hipEventRecord(w->cls_done[cls], w->cls_stream[cls]));
 		HIPCK(hipStreamWaitEvent(w->side, w->cls_done[cls], 0));
 	}
@@ -863,6 +890,7 @@ extern "C" int bmh_chain_batch(bmh_chain_ws_t *w, const bmh_chain_opt_t *opt, co
 	{ const int rc = chain_check_args("bmh_chain_batch", w, opt, idx, n_reads, seeds); if (rc != BMH_OK) return rc; }
 	hipStream_t st = (hipStream_t)stream_;
 	w->n_regs = w->n_jobs = 0; w->over_qlen = 0;
+	memset(w->class_counts, 0, sizeof(w->class_counts));
 	w->last_reads = d_reads; w->last_pac = idx->dev.pac; w->last_l_pac = idx->dev.l_pac;
 	if (n_reads == 0) return BMH_OK;
 	chain_args_t A;
@@ -877,17 +905,18 @@ extern "C" int bmh_chain_batch(bmh_chain_ws_t *w, const bmh_chain_opt_t *opt, co
 		HIPCK(hipMemcpyAsync(w->h_pin + 0, w->reg_off + n_reads, 4, hipMemcpyDeviceToHost, st));
 		HIPCK(hipMemcpyAsync(w->h_pin + 1, w->job_off + n_reads, 4, hipMemcpyDeviceToHost, st));
 		HIPCK(hipMemcpyAsync(w->h_pin + 2, w->counters, 4 * (CH_N_CLASSES + 1), hipMemcpyDeviceToHost, st));
-		HIPCK(hipMemcpyAsync(w->h_pin + 40, w->counters + 32 + CH_N_BINS, 4, hipMemcpyDeviceToHost, st));
+		HIPCK(hipMemcpyAsync(w->h_pin + CH_PIN_BINS, w->counters + 32, 4 * (CH_N_BINS + 2), hipMemcpyDeviceToHost, st));
 		HIPCK(hipEventRecord(w->ev_t[5], st));
 		HIPCK(hipStreamSynchronize(st));
 		// a read beyond CH_MAX_READ_LEN: chain_long_kernel, then the counts again
-		if (round > 0 || w->h_pin[40] <= CH_MAX_READ_LEN) break;
+		if (round > 0 || w->h_pin[CH_PIN_MAXLEN] <= CH_MAX_READ_LEN) break;
 		{ const int rc = chain_launch_long(A, st); if (rc != BMH_OK) return rc; }
 	}
 	HIPCK(hipGetLastError());
 	(void)hipEventElapsedTime(&w->ms[0], w->ev_t[0], w->ev_t[1]); (void)hipEventElapsedTime(&w->ms[1], w->ev_t[1], w->ev_t[2]);
 	(void)hipEventElapsedTime(&w->ms[2], w->ev_t[3], w->ev_t[4]); (void)hipEventElapsedTime(&w->ms[3], w->ev_t[0], w->ev_t[5]);
 	for (int c = 0; c < CH_N_CLASSES; ++c) w->heavy_per_class[c] = w->h_pin[2 + c];
+	chain_note_counts(w);
 	if (getenv("BMH_CHAIN_STATS")) chain_print_stats(w);
 	if (w->h_pin[2 + CH_N_CLASSES] == 1) { bmh_set_error("bmh_chain_batch: a read is longer than %d bases (BMH_EXT_LONG_MAX, the cap of the long-query extension)", CH_LONG_READ_MAX); return BMH_EINVAL; }
 	if (w->h_pin[2 + CH_N_CLASSES] != 0) { bmh_set_error("bmh_chain_batch: internal error %u in the chaining kernel", w->h_pin[2 + CH_N_CLASSES]); return BMH_ENODEV; }
@@ -920,12 +949,13 @@ extern "C" int bmh_chain_batch(bmh_chain_ws_t *w, const bmh_chain_opt_t *opt, co
 	if (n_regs == 0) return BMH_OK;
 	emit_args_t E;
 	E.regs = w->regs; E.prefix = seeds->d_prefix; E.regs_per_read = w->regs_per_read; E.reg_off = w->reg_off; E.job_off = w->job_off; E.need = nullptr; E.thresh = 0; E.pass = 0;
+	E.lane_need = w->need; E.lane_thresh = A.heavy_thresh;
 	E.read_offs = d_offs; E.read_lens = d_lens; E.n_reads = n_reads; E.outregs = w->outregs; E.reg_base = E.job_base = 0;
 	E.qlen = w->qlen; E.tlen = w->tlen; E.h0 = w->h0; E.job_read = w->job_read; E.job_reg = w->job_reg; E.job_side = w->job_side; E.jq_src = w->jq_src; E.jt0 = w->jt0;
 	E.qcap = w->max_qlen; E.over = w->counters + 38;
 	emit_kernel<<<nblk(n_reads, 256), 256, 0, st>>>(E);
 	emit_wave_kernel<<<1024, 256, 0, st>>>(E, w->heavy_list, w->counters, 0, CH_N_CLASSES - 1, A.long_list, A.long_n);
-	if (w->h_pin[40] > w->max_qlen) {                       // (only a read longer than the cap can have a query side beyond it)
+	if (w->h_pin[CH_PIN_MAXLEN] > w->max_qlen) {                       // (only a read longer than the cap can have a query side beyond it)
 		HIPCK(hipMemcpyAsync(w->h_pin + 41, w->counters + 38, 4, hipMemcpyDeviceToHost, st));
 		HIPCK(hipStreamSynchronize(st));
 		w->over_qlen = w->h_pin[41];
@@ -1062,6 +1092,7 @@ extern "C" int bmh_chain_extend_merge(bmh_chain_ws_t *w, const bmh_chain_opt_t *
 	{ const int rc = chain_check_args("bmh_chain_extend_merge", w, opt, idx, n_reads, seeds); if (rc != BMH_OK) return rc; }
 	hipStream_t st = (hipStream_t)stream_;
 	w->n_regs = w->n_jobs = 0;
+	memset(w->class_counts, 0, sizeof(w->class_counts));
 	w->last_reads = d_reads; w->last_pac = idx->dev.pac; w->last_l_pac = idx->dev.l_pac;
 	if (n_reads == 0) return BMH_OK;
 	chain_args_t A;
@@ -1081,7 +1112,7 @@ extern "C" int bmh_chain_extend_merge(bmh_chain_ws_t *w, const bmh_chain_opt_t *
 	HIPCK(hipMemcpyAsync(w->h_pin + 0, w->off2[0] + n_reads, 4, hipMemcpyDeviceToHost, st));
 	HIPCK(hipMemcpyAsync(w->h_pin + 1, w->off2[1] + n_reads, 4, hipMemcpyDeviceToHost, st));
 	HIPCK(hipMemcpyAsync(h64, w->need_sum, 8, hipMemcpyDeviceToHost, st));
-	HIPCK(hipMemcpyAsync(w->h_pin + 40, w->counters + 32 + CH_N_BINS, 4, hipMemcpyDeviceToHost, st));
+	HIPCK(hipMemcpyAsync(w->h_pin + CH_PIN_BINS, w->counters + 32, 4 * (CH_N_BINS + 2), hipMemcpyDeviceToHost, st));
 	HIPCK(hipEventRecord(w->ev_t[5], st));
 	HIPCK(hipStreamSynchronize(st));                          // (the lane kernel; the wave kernels go on)
 	st = st_user;
@@ -1095,9 +1126,10 @@ extern "C" int bmh_chain_extend_merge(bmh_chain_ws_t *w, const bmh_chain_opt_t *
 	E.qlen = w->qlen; E.tlen = w->tlen; E.h0 = w->h0; E.job_read = w->job_read; E.job_reg = w->job_reg; E.job_side = w->job_side; E.jq_src = w->jq_src; E.jt0 = w->jt0;
 	bmh_ext_desc_t d;
 	d.reads = d_reads; d.pac = idx->dev.pac; d.l_pac = (long long)idx->dev.l_pac;
-	d.max_qlen = w->h_pin[40];                                  // (the longest read: the extension skips the classes beyond it)
+	d.max_qlen = w->h_pin[CH_PIN_MAXLEN];                                  // (the longest read: the extension skips the classes beyond it)
 	d.long_cap = w->max_qlen > CH_EXT_QMAX ? w->max_qlen : 0;
 	E.qcap = w->max_qlen; E.over = w->counters + 38;
+	E.lane_need = w->need; E.lane_thresh = A.heavy_thresh;
 	HIPCK(hipEventRecord(w->ev_x[0], st));
 	if (n_regs_a) {
 		E.regs_per_read = w->regs_per_read; E.need = w->need; E.thresh = A.heavy_thresh; E.pass = 0; E.reg_off = w->off2[0]; E.job_off = w->off2[1]; E.reg_base = E.job_base = 0;
@@ -1111,7 +1143,7 @@ extern "C" int bmh_chain_extend_merge(bmh_chain_ws_t *w, const bmh_chain_opt_t *
 	HIPCK(hipEventRecord(w->ev_x[1], st));
 	// ---- pass B: the reads of the wave kernels, counted on a second stream so that the host does not wait for pass A's extension
 	// (the reads beyond CH_MAX_READ_LEN -- pass B's too -- are chained on that stream first: the classification is through, the host has seen it)
-	if (w->h_pin[40] > CH_MAX_READ_LEN) { const int rc = chain_launch_long(A, w->side2); if (rc != BMH_OK) return rc; }
+	if (w->h_pin[CH_PIN_MAXLEN] > CH_MAX_READ_LEN) { const int rc = chain_launch_long(A, w->side2); if (rc != BMH_OK) return rc; }
 	HIPCK(hipStreamWaitEvent(w->side2, w->ev_join, 0));
 	// (its own scan scratch: pass A's extension may still be using nothing of ours, but the scans above share scan_tmp with nothing in flight on st)
 	tb = w->scan_tmp_bytes;
@@ -1126,6 +1158,7 @@ extern "C" int bmh_chain_extend_merge(bmh_chain_ws_t *w, const bmh_chain_opt_t *
 	(void)hipEventElapsedTime(&w->ms[0], w->ev_t[0], w->ev_t[1]); (void)hipEventElapsedTime(&w->ms[1], w->ev_t[1], w->ev_t[2]);
 	(void)hipEventElapsedTime(&w->ms[2], w->ev_t[3], w->ev_t[4]); (void)hipEventElapsedTime(&w->ms[3], w->ev_t[0], w->ev_t[5]);
 	for (int c = 0; c < CH_N_CLASSES; ++c) w->heavy_per_class[c] = w->h_pin[2 + c];
+	chain_note_counts(w);
 	if (getenv("BMH_CHAIN_STATS")) chain_print_stats(w);
 	if (w->h_pin[2 + CH_N_CLASSES] == 1) { bmh_set_error("bmh_chain_extend_merge: a read is longer than %d bases (BMH_EXT_LONG_MAX, the cap of the long-query extension)", CH_LONG_READ_MAX); return BMH_EINVAL; }
 	if (w->h_pin[2 + CH_N_CLASSES] != 0) { bmh_set_error("bmh_chain_extend_merge: internal error %u in the chaining kernel", w->h_pin[2 + CH_N_CLASSES]); return BMH_ENODEV; }
@@ -1143,7 +1176,7 @@ extern "C" int bmh_chain_extend_merge(bmh_chain_ws_t *w, const bmh_chain_opt_t *
 		E.regs_per_read = w->regs_per_read; E.need = w->need; E.thresh = A.heavy_thresh; E.pass = 1; E.reg_off = w->off2[2]; E.job_off = w->off2[3]; E.reg_base = (uint32_t)n_regs_a; E.job_base = (uint32_t)n_jobs_a;
 		emit_kernel<<<nblk(n_reads, 256), 256, 0, sb>>>(E);
 		emit_wave_kernel<<<1024, 256, 0, sb>>>(E, w->heavy_list, w->counters, 0, CH_N_CLASSES - 1, A.long_list, A.long_n);
-		if (w->h_pin[40] > w->max_qlen) {
+		if (w->h_pin[CH_PIN_MAXLEN] > w->max_qlen) {
 			// a read longer than the cap (only those are in this pass) may have a query side beyond it: such a batch is refused before its extension --
 			// the kernels would leave INT32_MIN placeholders, and no region may be built from them
 			HIPCK(hipMemcpyAsync(w->h_pin + 41, w->counters + 38, 4, hipMemcpyDeviceToHost, sb));

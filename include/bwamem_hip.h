@@ -605,6 +605,11 @@ typedef struct {
  * entries on side streams) [3] the stage up to the (first) counts; [6] reads whose scratch has at most 512 entries, [7] the larger ones */
 void bmh_chain_last_timing(const bmh_chain_ws_t *ws, float ms[8]);
 
+/* which form chained how many reads of the last bmh_chain_batch / bmh_chain_extend_merge: out[0..11) reads per size class of the cooperative
+ * kernels (at most 16, 32, 64, 128, 256, 384, 512, 620, 1250, 1860 sampled seed occurrences, more), out[11..15) reads per bin of the lane
+ * kernel (at most 2, 4, 8 occurrences, the rest up to BMH_CHAIN_HEAVY), out[15] reads beyond 700 bases (chained by their own kernel) */
+int bmh_chain_class_counts(const bmh_chain_ws_t *ws, uint32_t out[16]);
+
 /* on (default): bmh_chain_batch also materialises the base arrays d_q/d_t/d_qoff/d_toff for bmh_extend_batch;
  * off: it stops at the job descriptors (those four pointers come back NULL, q_bytes = t_bytes = 0) and the batch is
  * extended with bmh_chain_extend, which reads the bases where they already are (reads, 2-bit reference). */

@@ -66,12 +66,17 @@ def _chain_core_lib():
 
 def _run_core(lib, opt, g, reads, seeds, compact=False):
     import ctypes as C
-    n, L = reads.shape
+    if isinstance(reads, tuple):                             # ragged: (flat, offs, lens)
+        flat, offs, lens = reads
+        n = len(lens)
+    else:
+        n, L = reads.shape
+        flat, offs, lens = reads.reshape(-1), np.arange(n, dtype=np.uint64) * L, np.full(n, L, np.uint32)
     pad = (-len(g)) % 4
     codes = np.concatenate([g, np.zeros(pad, np.uint8)]).reshape(-1, 4)
     pac = np.ascontiguousarray(((codes[:, 0] << 6) | (codes[:, 1] << 4) | (codes[:, 2] << 2) | codes[:, 3]).astype(np.uint8))
     a = lambda x, dt: np.ascontiguousarray(x, dtype=dt)
-    keep = [pac, a(reads.reshape(-1), np.uint8), np.arange(n, dtype=np.uint64) * L, np.full(n, L, np.uint32), a(seeds["rbeg"], np.uint64),
+    keep = [pac, a(flat, np.uint8), a(offs, np.uint64), a(lens, np.uint32), a(seeds["rbeg"], np.uint64),
             a(seeds["qbeg"], np.int32), a(seeds["score"], np.uint32), a(seeds["n_ref_pos"], np.uint32), a(seeds["prefix"], np.uint32)]
     p = lambda x: x.ctypes.data_as(C.c_void_p)
     fn = lib.chain_core_run_compact if compact else lib.chain_core_run
@@ -127,6 +132,39 @@ def test_device_chain_core_matches_reference_jobs_and_host_builder(oracle):
             for k in ("qoff", "qlen", "toff", "tlen", "h0", "job_read", "job_reg", "job_side", "regs_per_read", "q", "t"):
                 assert np.array_equal(cc[k], getattr(hj, k)), ("compact", over, k)
         hj.free()
+
+
+@pytest.mark.parametrize("over", [{}, dict(max_occ=50), dict(max_occ=7, max_chain_extend=3), dict(min_chain_weight=3)], ids=["default", "c50", "c7_x3", "W3"])
+def test_chain_class_fixture_core_matches_host_builder(oracle, over):
+    """The reads of tests/chain_classes.py -- both sides of every size-class and lane-bin boundary of the device job builder, 2 to 2002 sampled seed
+    occurrences a read -- through the serial CPU build of csrc/chain_core.h, wide and compact records, against bmh_build_jobs array for array: what
+    tests/test_chain_classes_gpu.py expects of the device forms does not depend on the device.  The fixture's need is what its recipe says."""
+    import ctypes as C
+    import chain_classes as cc
+    from bwamem_hip.lib import ChainOpt, load_library
+    lib = _chain_core_lib()
+    g, idx, _, _, _ = cc.genome()
+    flat, offs, lens = common.ragged_reads(cc.reads())
+    s = oracle.seed_reads(oracle.fmd(idx), flat, offs, lens, 19, n_threads=4)
+    o = ChainOpt(); load_library().bmh_chain_opt_default(C.byref(o))
+    for k, v in over.items():
+        setattr(o, k, v)
+    need, _, counts = cc.classify(s, lens, o.max_occ)
+    assert np.array_equal(need, cc.expected_need(o.max_occ))
+    if not over:                                             # every class and every bin at the default options, two reads at least
+        assert o.max_occ == 500 and (counts[:14] >= 2).all(), counts        # (the fourth bin -- beyond 8 entries, up to the lane threshold -- is empty at the default threshold of 8)
+        for cap in cc.BIN_CAPS + (cc.DEFAULT_HEAVY,) + cc.CLASS_CAPS:
+            assert (need == cap).sum() >= 2 and (need == cap + 1).sum() >= 2, cap
+        assert (s["n_ref_pos"].astype(np.int64) > need).sum() >= 2          # more located than sampled
+    hj = HostJobs(g, flat, offs, lens, s, n_threads=4, opt=o)
+    assert hj.n_jobs > 100 and (over or hj.regs_per_read.max() > 32)          # (default: reads beyond CH_EMIT_LANE_MAX regions, the wave form of the emit kernel)
+    keys = ("qoff", "qlen", "toff", "tlen", "h0", "job_read", "job_reg", "job_side", "regs_per_read", "q", "t")
+    for compact in (False, True) if not over.get("min_chain_weight") else (False,):      # (the compact records are for the forms without the seed filter)
+        c = _run_core(lib, o, g, (flat, offs, lens), s, compact=compact)
+        assert c["err"] == 0 and c["n_jobs"] == hj.n_jobs and c["n_regs"] == hj.n_regs
+        for k in keys:
+            assert np.array_equal(c[k], getattr(hj, k)), (compact, over, k)
+    hj.free()
 
 
 def _golden_regions(oracle, z):
