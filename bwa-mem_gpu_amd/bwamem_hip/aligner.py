@@ -156,6 +156,18 @@ def read_reads_files(path1: str, path2: str | None = None, comments: bool = Fals
         raise
 
 
+def bam_to_reads(records: bytes, comments: bool = False, host: bool = False) -> ReadSet:
+    """uncompressed BAM records (without the header) as the reads read_reads_files gives for the BAM file that holds them (bmh_bam_reads_device; host=True:
+    bmh_bam_reads_host, no device needed): `samtools fastq`'s rules -- secondary and supplementary records skipped, reverse-strand records turned back, pairs
+    (flag 0x1) as reads 2i / 2i+1, and with comments=True the tags as the comment -C copies.  Refused records raise ValueError (lib.ReadFileError)."""
+    from .lib import bam_reads
+    d = bam_reads(records, comments=comments, host=host)
+    if len(d["lens"]) == 0:
+        return ReadSet.from_lists([], [], comments=[] if comments else None)
+    cm = (d["comments"], d["comment_offs"]) if d["comments"] is not None else None
+    return ReadSet(d["ascii"], d["offs"], d["lens"], d["names"], d["name_offs"], codes=d["codes"], qual=d["quals"], comments=cm)
+
+
 def read_fasta_reads_numpy(path: str) -> ReadSet:
     """the same parse with numpy array operations (what read_fasta_reads was before the library had a loader; kept as its cross-check)"""
     buf = np.fromfile(path, dtype=np.uint8)
@@ -719,7 +731,8 @@ class Aligner:
     def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
                     sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None) -> int:
         """align_file for the files users have (bmh_aligner_run_files): `reads` (and `mates`: the second file of a pair, which implies paired) may be
-        multi-line FASTA or FASTQ, plain, gzip or BGZF, a regular file or a pipe.  Batches are cut by align_file's rules (-t, -K, the 150 Mbase floor for
+        multi-line FASTA or FASTQ, plain, gzip or BGZF, a regular file or a pipe; or `reads` alone is a BAM file (unaligned, or grouped by read name: recognised
+        from its bytes, pairs from flag 0x1 of its records -- paired=True on a BAM without it is refused).  Batches are cut by align_file's rules (-t, -K, the 150 Mbase floor for
         single-end runs), so the text equals align_file's on the single-line interleaved file of the same reads.  Returns the number of reads."""
         if out is None:
             raise ValueError("align_files: out (a text or binary file object) is required")
@@ -736,6 +749,9 @@ class Aligner:
             cb = min(cb, (1 << 31) - 1024)
         out.write(self.header().encode() if binary else self.header())
         nat = self._native_aligner()
+        # (a BAM says itself whether it holds pairs, once the library has opened it: the batch size and lanes of a paired run, for that case)
+        cb_pairs = 0 if batch_reads > 0 else min(chunk_bases or int(getattr(self, "ref_chunk_bases", 0)) or 10_000_000 * max(1, int(getattr(self, "ref_threads", 1))), (1 << 31) - 1024)
+        nat.set_bam_pairs(cb_pairs, int(os.environ.get("BMH_ALIGNER_LANES", "3")))
         try:
             self.last_stats = nat.run_files(reads, mates, paired, (lambda mv: out.write(mv)) if binary else (lambda mv: out.write(bytes(mv).decode())),
                                              batch_bases=cb, batch_reads=max(batch_reads, 0),

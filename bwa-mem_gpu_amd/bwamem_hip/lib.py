@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "bmh_bam_ws_create", "bmh_bam_ws_free", "bmh_sam_to_bam_device", "bmh_sam_to_bam_host", "bmh_bam_status_name", "bmh_bgzf_deflate_device", "bmh_bgzf_deflate_host",
     "bmh_deflate_blocks_host", "bmh_bam_header", "bmh_aligner_set_output",
     "bmh_bam_sort_device", "bmh_bam_sort_host", "bmh_bam_sorted_file_device", "bmh_bam_sorted_file_host", "bmh_aligner_set_sort", "bmh_aligner_sort_index",
+    "bmh_bam_reads_device", "bmh_bam_reads_host", "bmh_reads_last_bam_counts", "bmh_aligner_set_bam_pairs",
     "bmh_bam_markdup_device", "bmh_bam_markdup_host", "bmh_bam_sorted_file_markdup_device", "bmh_bam_sorted_file_markdup_host", "bmh_aligner_set_markdup", "bmh_aligner_markdup_counts", "bmh_aligner_markdup_times",
 ]
 
@@ -454,19 +455,33 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
         L.bmh_free(bam); L.bmh_free(bai)
 
 
-def load_reads_files(path1: str, path2: str | None = None, comments: bool = False, host: bool = False, n_threads: int = 0) -> dict:
-    """bmh_reads_load_files: one or two read files of any shape (multi-line records, gzip / BGZF, pipes) as load_reads gives them; path2: the mates (reads 2i
-    and 2i+1).  host=True: the host walker alone (no device).  A refused file raises ReadFileError; when one file ends before the other its `partial`
-    attribute holds the complete pairs before the end."""
+def reads_last_bam_counts() -> dict:
+    """bmh_reads_last_bam_counts: what the process's last load_reads_files / run_files / bam_reads call left out of its BAM input -- records skipped (flag 0x100
+    or 0x800), f and B tags left out of the comments"""
     L = load_library()
+    L.bmh_reads_last_bam_counts.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 2)()
+    L.bmh_reads_last_bam_counts(out)
+    return dict(records_skipped=int(out[0]), tags_left_out=int(out[1]))
+
+
+def bam_reads(records: bytes, comments: bool = False, host: bool = False) -> dict:
+    """bmh_bam_reads_device (host=True: bmh_bam_reads_host, no device needed): uncompressed BAM records, without the header, as load_reads_files gives a file's
+    reads -- `samtools fastq`'s rules (include/bwamem_hip.h).  Refused records raise ReadFileError naming the record's index."""
+    L = load_library()
+    records = bytes(records)
     rs = ReadSetT()
-    L.bmh_reads_load_files.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(ReadSetT)]
+    fn = L.bmh_bam_reads_host if host else L.bmh_bam_reads_device
+    fn.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(ReadSetT)]
     L.bmh_reads_free.argtypes = [C.POINTER(ReadSetT)]
-    rc = L.bmh_reads_load_files(os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, n_threads,
-                                (READS_COMMENTS if comments else 0) | (READS_HOST if host else 0), C.byref(rs))
-    msg = _err(L) if rc != 0 else ""
-    if rc != 0 and not rs.ascii:
-        raise ReadFileError(msg) if msg.startswith(("FASTQ:", "reads file", "reads files")) else RuntimeError("bmh_reads_load_files: " + msg)
+    if fn(records, len(records), READS_COMMENTS if comments else 0, C.byref(rs)) != 0:
+        msg = _err(L)
+        raise ReadFileError(msg) if msg.startswith("reads file") else RuntimeError("bmh_bam_reads: " + msg)
+    return _read_set_dict(L, rs)
+
+
+def _read_set_dict(L, rs) -> dict:
+    """a filled bmh_read_set_t as numpy arrays over the library's own arrays (no copies; freed with the last of them)"""
     owner = _ReadSetOwner(L, rs)
 
     def arr(ptr, n, dt):
@@ -476,11 +491,27 @@ def load_reads_files(path1: str, path2: str | None = None, comments: bool = Fals
         buf = (C.c_uint8 * (n * np.dtype(dt).itemsize)).from_address(ptr)
         buf._owner = owner
         return np.frombuffer(buf, dtype=dt)
-    d = dict(ascii=arr(rs.ascii, rs.n_bases, np.uint8), codes=arr(rs.codes, rs.n_bases, np.uint8), offs=arr(rs.offs, rs.n_reads, np.uint64),
-             lens=arr(rs.lens, rs.n_reads, np.uint32), names=arr(rs.names, rs.n_name_bytes, np.uint8), name_offs=arr(rs.name_offs, rs.n_reads, np.uint64),
-             quals=arr(rs.quals, rs.n_bases, np.uint8) if rs.quals else None,
-             comments=arr(rs.comments, rs.n_comment_bytes, np.uint8) if rs.comments else None,
-             comment_offs=arr(rs.comment_offs, rs.n_reads, np.uint64) if rs.comments else None)
+    return dict(ascii=arr(rs.ascii, rs.n_bases, np.uint8), codes=arr(rs.codes, rs.n_bases, np.uint8), offs=arr(rs.offs, rs.n_reads, np.uint64),
+                lens=arr(rs.lens, rs.n_reads, np.uint32), names=arr(rs.names, rs.n_name_bytes, np.uint8), name_offs=arr(rs.name_offs, rs.n_reads, np.uint64),
+                quals=arr(rs.quals, rs.n_bases, np.uint8) if rs.quals else None,
+                comments=arr(rs.comments, rs.n_comment_bytes, np.uint8) if rs.comments else None,
+                comment_offs=arr(rs.comment_offs, rs.n_reads, np.uint64) if rs.comments else None)
+
+
+def load_reads_files(path1: str, path2: str | None = None, comments: bool = False, host: bool = False, n_threads: int = 0) -> dict:
+    """bmh_reads_load_files: one or two read files of any shape (multi-line records, gzip / BGZF, pipes) as load_reads gives them; path2: the mates (reads 2i
+    and 2i+1).  A BGZF file that holds a BAM (unaligned, or grouped by read name) is taken in place of a text file, alone.  host=True: the host walker alone
+    (no device).  A refused file raises ReadFileError; when one file ends before the other its `partial` attribute holds the complete pairs before the end."""
+    L = load_library()
+    rs = ReadSetT()
+    L.bmh_reads_load_files.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(ReadSetT)]
+    L.bmh_reads_free.argtypes = [C.POINTER(ReadSetT)]
+    rc = L.bmh_reads_load_files(os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, n_threads,
+                                (READS_COMMENTS if comments else 0) | (READS_HOST if host else 0), C.byref(rs))
+    msg = _err(L) if rc != 0 else ""
+    if rc != 0 and not rs.ascii:
+        raise ReadFileError(msg) if msg.startswith(("FASTQ:", "reads file", "reads files")) else RuntimeError("bmh_reads_load_files: " + msg)
+    d = _read_set_dict(L, rs)
     if rc != 0:
         e = ReadFileError(msg)
         e.partial = d
@@ -649,6 +680,13 @@ class NativeAligner:
         """bmh_aligner_run_file: run_fasta for a FASTA or FASTQ file (QUAL from the qualities; the comments with -C)"""
         return self._run("bmh_aligner_run_file", (path.encode(), int(batch_bases), int(batch_reads), 1 if paired else 0, int(n_lanes), int(n_threads)), write,
                          read_errors=("FASTQ:", "reads file:"))
+
+    def set_bam_pairs(self, batch_bases: int = 0, n_lanes: int = 0) -> None:
+        """bmh_aligner_set_bam_pairs: the batch size and lanes run_files takes when its input turns out to be a BAM that holds pairs and paired was False"""
+        L = load_library()
+        L.bmh_aligner_set_bam_pairs.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
+        if L.bmh_aligner_set_bam_pairs(self.handle, int(batch_bases), int(n_lanes)) != 0:
+            raise ValueError("bmh_aligner_set_bam_pairs: " + _err(L))
 
     def run_files(self, path1: str, path2: str | None, paired: bool, write, batch_bases: int = 0, batch_reads: int = 0, n_lanes: int = 2, n_threads: int = 0) -> "AlignStats":
         """bmh_aligner_run_files: run_file for one or two read files of any shape (multi-line records, gzip / BGZF, pipes; path2: the mates)"""

@@ -1,4 +1,5 @@
-"""`bwa mem` on the device: reads (FASTA or FASTQ, multi-line or not, plain, gzip or BGZF, one file or an R1 / R2 pair) -> SAM.
+"""`bwa mem` on the device: reads (FASTA or FASTQ, multi-line or not, plain, gzip or BGZF, one file or an R1 / R2 pair; or one BAM file, unaligned or
+grouped by read name, which says itself whether it holds pairs) -> SAM.
 
     python -m bwamem_hip.mem [options] PREFIX reads [mates] [-o out.sam]
 

@@ -835,6 +835,7 @@ struct bmh_aligner {
 	std::vector<std::string> parts;
 	int dev = -1;
 	uint64_t host_tail_batches = 0;                      // of the last run (bmh_aligner_host_tail_batches)
+	uint64_t bam_pairs_bases = 0; int bam_pairs_lanes = 0;   // bmh_aligner_set_bam_pairs
 	bsr_store_t store; bsr_index_t sort_ix; uint32_t sort_window = 0;      // sorted BAM output: the runs of the run in progress, the index of the last one, the window
 	uint64_t dup_counts[BDP_N_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0}; bool dup_valid = false;      // duplicate marking: the counts of the last marked run
 	double dup_times[3] = {0, 0, 0};                     // ... its decision and its windows' flag steps in ms, the bytes its batches' ordinals and entries took on their way down
@@ -1347,6 +1348,15 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 	const bool cm = h->a.po.copy_comment != 0;
 	bmh_reads_pump_t *P = bmh_pump_open(path1, path2, n_threads, cm, false, 0);
 	if (!P) return BMH_EINVAL;
+	// a BAM file says itself whether it holds pairs (flag 0x1 of its first record kept, known since the file was opened): the run's lanes start with that
+	const int bam_pairs = bmh_pump_bam_paired(P);
+	if (bam_pairs == 0 && paired) { bmh_pump_close(P); bmh_set_error("reads file: %s: paired reads were asked for and the BAM's records do not carry flag 0x1", path1); return BMH_EINVAL; }
+	if (bam_pairs == 1 && !paired) {
+		paired = 1;
+		if (batch_reads & 1) --batch_reads;
+		if (h->bam_pairs_bases && batch_reads == 0) batch_bases = std::min<uint64_t>(h->bam_pairs_bases, (1ull << 31) - 4096);
+		if (h->bam_pairs_lanes > 0) n_lanes = h->bam_pairs_lanes;
+	}
 	int64_t id0 = 0;
 	auto fill = [&](fbatch_t &fb) {
 		const bmh_batch_alloc_t alloc = [&](uint64_t nr, uint64_t nb, uint64_t nn, uint64_t ncm, bool fq, bmh_read_set_t *rs) { return fb.size(fn, nr, nb, nn, ncm, fq, cm, rs); };
@@ -1356,8 +1366,16 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 	const int rc = run_loaded(h, fn, dev, fill, true, paired, n_lanes, n_threads, sink, user, stats);
 	uint64_t cnt[4]; bmh_pump_counts(P, cnt); bmh_reads_note_counts(cnt);
 	uint64_t icnt[2]; bmh_pump_inflate_counts(P, icnt); bmh_reads_note_inflate_counts(icnt);
+	uint64_t bcnt[2]; bmh_pump_bam_counts(P, bcnt); bmh_reads_note_bam_counts(bcnt);
 	bmh_pump_close(P);
 	return rc;
+}
+
+int bmh_aligner_set_bam_pairs(bmh_aligner_t *h, uint64_t batch_bases, int n_lanes)
+{
+	if (!h) { bmh_set_error("bmh_aligner_set_bam_pairs: null aligner"); return BMH_EINVAL; }
+	h->bam_pairs_bases = batch_bases; h->bam_pairs_lanes = n_lanes;
+	return BMH_OK;
 }
 
 int bmh_aligner_run_fasta(bmh_aligner_t *h, const char *path, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,

@@ -116,6 +116,50 @@ extern "C" int bmh_reads_last_counts(uint64_t *out);
 void bmh_pump_inflate_counts(const bmh_reads_pump_t *p, uint64_t out[2]);
 void bmh_reads_note_inflate_counts(const uint64_t *c);
 extern "C" int bmh_reads_last_inflate_counts(uint64_t *out);
+// ---- BAM as read input (csrc/bam_in_core.h): a BGZF file whose text begins with "BAM\1" is the pump's third kind.  A BAM record names its own length, so the
+// record starts of a window are one dependent chain: the host walks it over the window it has just inflated (bmh_bam_chain: one 4-byte read per record); BAM
+// therefore always takes the host inflate.  Everything else is done per record, base and read on the device (csrc/bam_in_kernels.hip: bmh_bam_dev_run) or, as
+// the definition, the fallback that words the refusals and the form without a device, on the host (csrc/reads_io.cpp: bmh_bam_host_run).
+// csrc/reads_src.cpp: 0 text, 1 a BGZF file that holds a BAM, 2 a plain gzip stream that holds one (refused); looked at without taking a byte of the text
+int bmh_text_bam(bmh_text_src_t *s);
+// the whole BAM header (magic, text, reference table) at the front of b[0, n): its bytes, 0 when it is not whole yet, -1 when the bytes are no BAM header
+int64_t bmh_bam_header_bytes(const uint8_t *b, size_t n);
+// the record starts of b[0, n) -> starts (one more entry: the end of the last whole record); a record is whole when start + 4 + block_size <= n
+void bmh_bam_chain(const uint8_t *b, size_t n, std::vector<uint32_t> &starts);
+// the same walk taken up where it stood: starts is not empty, its last entry is the end of the last whole record found so far (0 at first)
+void bmh_bam_chain_extend(const uint8_t *b, size_t n, std::vector<uint32_t> &starts);
+extern "C" int bmh_bam_chain_count(const uint8_t *records, uint64_t n_bytes, uint64_t *n_records, uint64_t *end);   // the walk alone, timed by scripts/reads_input_rate.py --bam-only
+// the flag of the first record of b[0, n) that gives a read: 1 and *flag, or 0 when the whole records of b hold none (yet)
+int bmh_bam_first_kept(const uint8_t *b, size_t n, uint32_t *flag);      // (-1: a record too short for its fixed fields comes first)
+// what a BAM file's windows share.  paired: flag 0x1 of the first record kept; qual: 0 unknown, 1 the records have qualities, 2 they have none
+struct bmh_bam_state_t { std::string path; int paired = 0, qual = 0; uint64_t n_recs = 0, n_skipped = 0, n_tags_left_out = 0; };
+// chain: the record starts of buf[0, have) when the caller has walked them already (bmh_bam_chain's result), else NULL
+struct bmh_bam_win_t { const uint8_t *buf; size_t have; bool eof, comments; uint64_t want_bases, want_reads; bool even, take_all; const std::vector<uint32_t> *chain; };
+// consumed: the end of the last record taken; n_recs: the records before it; skipped / tags_left_out: among those; qual: the state behind them
+struct bmh_bam_res_t { uint64_t n_reads = 0; bool complete = false, final_ = false; size_t consumed = 0; uint64_t n_recs = 0, skipped = 0, tags_left_out = 0; int qual = 0; };
+int bmh_bam_host_run(const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bmh_batch_alloc_t &alloc, bmh_read_set_t *rs, bmh_bam_res_t &R, bmh_hbatch_t &hb);   // 1, or < 0: refused
+struct bmh_bam_dev_t;
+bmh_bam_dev_t *bmh_bam_dev_create();
+void bmh_bam_dev_free(bmh_bam_dev_t *d);
+int bmh_bam_dev_run(bmh_bam_dev_t *d, const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bmh_batch_alloc_t &alloc, bmh_read_set_t *rs, bmh_bam_res_t &R);   // 1, 2: the window is the host's, < 0
+int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out);   // csrc/reads_io.cpp: bmh_bam_reads_device / _host
+// the pump's answer for bmh_aligner_run_files: -1 the input is no BAM, else flag 0x1 of its first record kept
+int bmh_pump_bam_paired(const bmh_reads_pump_t *p);
+void bmh_pump_bam_counts(const bmh_reads_pump_t *p, uint64_t out[2]);    // records skipped (0x100 / 0x800), f and B tags left out
+void bmh_reads_note_bam_counts(const uint64_t *c);
+// the end of the batch among n reads of these lengths (step: 1, or 2 when pairs stay together); *complete: the wanted size was reached -- bseq_read's rule
+inline uint64_t bmh_cut_batch(const uint32_t *lens, uint64_t n, int step, uint64_t want_bases, uint64_t want_reads, bool even, bool *complete)
+{
+	uint64_t acc = 0;
+	*complete = false;
+	for (uint64_t r = 0; r + step <= n;) {
+		for (int k = 0; k < step; ++k) acc += lens[r + k];
+		r += step;
+		const bool full = want_reads ? r >= want_reads : acc >= want_bases;
+		if (full && (!even || !(r & 1))) { *complete = true; return r; }
+	}
+	return n;
+}
 // csrc/pair_dev.hip, csrc/align_pipeline.hip: the device's pairing stage with C linkage -- for the tests, not part of the public interface.
 // bmh_pair_limit: the hits of a pair's two reads together the pairing kernel takes; the merge, its counts and the scan: see the definitions.
 // bmh_pairs_device_records: what the aligner does for a batch of interleaved pairs before the host's split walk, with the insert-size statistics

@@ -18,6 +18,7 @@
 #include <chrono>
 #include <vector>
 #include "bmh_internal.h"
+#include "bam_in_core.h"
 #include "../../include/bwamem_hip.h"
 
 namespace {
@@ -576,4 +577,208 @@ int bmh_walk_record(const uint8_t *b, size_t n, bool eof, size_t *pp, bmh_hbatch
 	o.lens.push_back((uint32_t)L); o.nlen.push_back((uint32_t)nl_ + 1);
 	*pp = q;
 	return 1;
+}
+
+// ---- BAM records as reads, the host form (csrc/bam_in_core.h has the rules): the definition the device kernels (csrc/bam_in_kernels.hip) must equal, the fallback
+// that words their refusals -- every one names the record's index in the file -- and what BMH_READS_HOST runs without a device.
+int64_t bmh_bam_header_bytes(const uint8_t *b, size_t n)
+{
+	if (n >= 4 && memcmp(b, "BAM\1", 4) != 0) return -1;
+	if (n < 12) return 0;
+	size_t p = 8 + (size_t)bi_u32(b + 4);                  // magic, l_text, text: walked and ignored
+	if (n < p + 4 || p + 4 < p) return 0;
+	const uint32_t n_ref = bi_u32(b + p);
+	p += 4;
+	for (uint32_t i = 0; i < n_ref; ++i) {                 // l_name, name, l_ref
+		if (n < p + 4) return 0;
+		p += 8 + (size_t)bi_u32(b + p);
+		if (n < p) return 0;
+	}
+	return (int64_t)p;
+}
+
+void bmh_bam_chain_extend(const uint8_t *b, size_t n, std::vector<uint32_t> &starts)
+{
+	for (size_t p = starts.back(); n - p >= 4;) {
+		const size_t e = p + 4 + (size_t)bi_u32(b + p);
+		if (e > n) break;
+		starts.push_back((uint32_t)e);
+		p = e;
+	}
+}
+
+void bmh_bam_chain(const uint8_t *b, size_t n, std::vector<uint32_t> &starts)
+{
+	starts.assign(1, 0u);
+	bmh_bam_chain_extend(b, n, starts);
+}
+
+// for scripts/reads_input_rate.py, not part of the public interface: the chain walk alone over records in memory -- *n_records whole records, *end where they end
+extern "C" int bmh_bam_chain_count(const uint8_t *records, uint64_t n_bytes, uint64_t *n_records, uint64_t *end)
+{
+	if ((!records && n_bytes) || !n_records || !end || n_bytes >= ((uint64_t)1 << 31)) { bmh_set_error("bmh_bam_chain_count: null argument, or 2^31 bytes or more"); return BMH_EINVAL; }
+	std::vector<uint32_t> starts;
+	bmh_bam_chain(records, (size_t)n_bytes, starts);
+	*n_records = starts.size() - 1; *end = starts.back();
+	return BMH_OK;
+}
+
+int bmh_bam_first_kept(const uint8_t *b, size_t n, uint32_t *flag)
+{
+	for (size_t p = 0; n - p >= 4;) {
+		const size_t e = p + 4 + (size_t)bi_u32(b + p);
+		if (e > n) return 0;
+		if (e - p < 36) return -1;                           // (damaged: the parse names it)
+		const uint32_t f = bi_u16(b + p + 18);
+		if (!(f & BI_SKIP_FLAGS)) { *flag = f; return 1; }
+		p = e;
+	}
+	return 0;
+}
+
+int bmh_bam_host_run(const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bmh_batch_alloc_t &alloc, bmh_read_set_t *rs, bmh_bam_res_t &R, bmh_hbatch_t &hb)
+{
+	hb.clear();
+	R = bmh_bam_res_t(); R.qual = st.qual;
+	std::vector<uint32_t> walked;
+	if (!w.chain) bmh_bam_chain(w.buf, w.have, walked);
+	const std::vector<uint32_t> &starts = w.chain ? *w.chain : walked;
+	const size_t nrec = starts.size() - 1, chain_end = starts.back();
+	const char *path = st.path.c_str();
+	auto idx = [&](size_t i) { return (unsigned long long)(st.n_recs + i); };
+	auto name = [&](size_t i) { return (const char *)w.buf + starts[i] + BI_NAME_OFF; };
+	int qual = st.qual;
+	uint64_t acc = 0, cnt = 0, skipped = 0, left_out = 0;
+	bool complete = false;
+	size_t pend = (size_t)-1, i = 0; bi_rec_t pend_rec; uint32_t pend_hq = 0;
+	auto append = [&](size_t k, const bi_rec_t &B, uint32_t hq) {
+		const uint8_t *r = w.buf + starts[k];
+		for (uint32_t t = 0; t < B.l_seq; ++t) hb.ascii.push_back(bi_base(r, B, t));
+		if (hq) for (uint32_t t = 0; t < B.l_seq; ++t) hb.quals.push_back(bi_qual(r, B, t));
+		hb.names.insert(hb.names.end(), r + BI_NAME_OFF, r + BI_NAME_OFF + B.l_name);
+		hb.lens.push_back(B.l_seq); hb.nlen.push_back(B.l_name);
+		uint32_t lo = 0;
+		const uint32_t cl = bi_comment(r, B, nullptr, 0, &lo);
+		left_out += lo;
+		if (w.comments) {
+			const size_t c0 = hb.comments.size();
+			hb.comments.resize(c0 + cl + 1);
+			(void)bi_comment(r, B, hb.comments.data() + c0, cl, &lo);
+			hb.comments[c0 + cl] = 0; hb.clen.push_back(cl + 1);
+		}
+		acc += B.l_seq; ++cnt;
+	};
+	auto commit = [&](size_t k) {
+		R.consumed = starts[k + 1]; R.n_recs = k + 1; R.skipped = skipped; R.tags_left_out = left_out; R.qual = qual;
+		if (!w.take_all) {
+			const bool full = w.want_reads ? cnt >= w.want_reads : acc >= w.want_bases;
+			if (full && (!w.even || !(cnt & 1))) complete = true;
+		}
+	};
+	for (; i < nrec && !complete; ++i) {
+		const uint8_t *r = w.buf + starts[i];
+		bi_rec_t B;
+		int s = bi_check(r, starts[i + 1] - starts[i], &B);
+		if (s != BI_OK) { bmh_set_error("reads file: %s: BAM record %llu: %s", path, idx(i), bi_status_text(s)); return BMH_EINVAL; }
+		const uint32_t role = bi_role(B.flag);
+		if (role == 0) { ++skipped; continue; }
+		uint32_t hq = 0;
+		s = bi_check_kept(r, B, &hq);
+		if (s != BI_OK) { bmh_set_error("reads file: %s: BAM record %llu (%s): %s", path, idx(i), name(i), bi_status_text(s)); return BMH_EINVAL; }
+		if ((int)(B.flag & 1u) != st.paired) { bmh_set_error("reads file: %s: BAM record %llu (%s): the file mixes records with and without flag 0x1", path, idx(i), name(i)); return BMH_EINVAL; }
+		if (qual && qual != (hq ? 1 : 2)) {
+			bmh_set_error("reads file: %s: BAM record %llu (%s) has %s base qualities and the records before it have %s: a file mixes both", path, idx(i), name(i), hq ? "its" : "no", hq ? "none" : "theirs");
+			return BMH_EINVAL;
+		}
+		qual = hq ? 1 : 2;
+		if (!st.paired) { append(i, B, hq); commit(i); continue; }
+		if (role == 3) { bmh_set_error("reads file: %s: BAM record %llu (%s): flag 0x1 with neither or both of 0x40 and 0x80", path, idx(i), name(i)); return BMH_EINVAL; }
+		if (pend == (size_t)-1) { pend = i; pend_rec = B; pend_hq = hq; continue; }
+		if (strcmp(name(pend), name(i)) != 0) {
+			bmh_set_error("reads file: %s: BAM records %llu and %llu carry different names (%s and %s): is the file grouped by read name?", path, idx(pend), idx(i), name(pend), name(i));
+			return BMH_EINVAL;
+		}
+		if (bi_role(pend_rec.flag) == role) { bmh_set_error("reads file: %s: BAM records %llu and %llu (%s) both carry flag %s", path, idx(pend), idx(i), name(i), role == 1 ? "0x40" : "0x80"); return BMH_EINVAL; }
+		if (role == 2) { append(pend, pend_rec, pend_hq); append(i, B, hq); }
+		else { append(i, B, hq); append(pend, pend_rec, pend_hq); }
+		pend = (size_t)-1;
+		commit(i);
+	}
+	R.complete = complete;
+	R.final_ = w.eof && !complete;
+	if (R.final_) {
+		// what the file's end leaves over is refused once the reads before it have been delivered
+		if (cnt == 0 && chain_end < w.have) { bmh_set_error("reads file: %s: the file ends inside BAM record %llu", path, idx(nrec)); return BMH_EINVAL; }
+		if (cnt == 0 && pend != (size_t)-1) { bmh_set_error("reads file: %s: BAM record %llu (%s): flag 0x1 and no partner", path, idx(pend), name(pend)); return BMH_EINVAL; }
+		if (chain_end == w.have && pend == (size_t)-1) { R.consumed = chain_end; R.n_recs = nrec; R.skipped = skipped; R.tags_left_out = left_out; R.qual = qual; }
+	}
+	if (!(complete || w.take_all || R.final_) || cnt == 0) { hb.clear(); return 1; }
+	// (the records behind the last commit -- a first record whose partner the window does not hold -- were not appended: append runs at the commit only)
+	const bool fq = qual == 1;
+	memset(rs, 0, sizeof(*rs));
+	const int arc = alloc(cnt, hb.ascii.size(), hb.names.size(), w.comments ? hb.comments.size() : 0, fq, rs);
+	if (arc != BMH_OK) return arc;
+	memcpy(rs->ascii, hb.ascii.data(), hb.ascii.size());
+	if (rs->codes) bmh_nt4_codes(hb.ascii.data(), rs->codes, hb.ascii.size());
+	if (fq && rs->quals) memcpy(rs->quals, hb.quals.data(), hb.quals.size());
+	memcpy(rs->names, hb.names.data(), hb.names.size());
+	if (w.comments && rs->comments) memcpy(rs->comments, hb.comments.data(), hb.comments.size());
+	uint64_t o = 0, no = 0, co = 0;
+	for (uint64_t r = 0; r < cnt; ++r) {
+		rs->offs[r] = o; rs->lens[r] = hb.lens[r]; rs->name_offs[r] = no; o += hb.lens[r]; no += hb.nlen[r];
+		if (w.comments && rs->comment_offs) { rs->comment_offs[r] = co; co += hb.clen[r]; }
+	}
+	rs->n_reads = cnt; rs->n_bases = o; rs->n_name_bytes = no; rs->n_comment_bytes = w.comments ? co : 0;
+	R.n_reads = cnt;
+	return 1;
+}
+
+// bmh_bam_reads_device / bmh_bam_reads_host: the records are one window that ends the file, and every read of it is taken.  d: the device form, or NULL
+int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out)
+{
+	memset(out, 0, sizeof(*out));
+	if (n_bytes >= ((uint64_t)1 << 31) - 4096) { bmh_set_error("%s: 2^31 bytes of records or more (offsets inside a window are 32-bit)", fn); return BMH_EINVAL; }
+	const bool cm = (flags & BMH_READS_COMMENTS) != 0;
+	bmh_bam_state_t st;
+	st.path = "(records in memory)";
+	uint32_t flag = 0;
+	if (bmh_bam_first_kept(records, (size_t)n_bytes, &flag) == 1) st.paired = (int)(flag & 1u);
+	const bmh_batch_alloc_t alloc = [&](uint64_t nr, uint64_t nb, uint64_t nn, uint64_t nc, bool fq, bmh_read_set_t *rs) {
+		out->ascii = (uint8_t *)malloc(nb + 1); out->codes = (uint8_t *)malloc(nb + 1); out->offs = (uint64_t *)malloc(8 * (nr + 1)); out->lens = (uint32_t *)malloc(4 * (nr + 1));
+		out->names = (uint8_t *)malloc(nn + 1); out->name_offs = (uint64_t *)malloc(8 * (nr + 1));
+		bool ok = out->ascii && out->codes && out->offs && out->lens && out->names && out->name_offs;
+		if (fq) { out->quals = (uint8_t *)malloc(nb + 1); ok = ok && out->quals; }
+		if (cm) { out->comments = (uint8_t *)malloc(nc + 1); out->comment_offs = (uint64_t *)malloc(8 * (nr + 1)); ok = ok && out->comments && out->comment_offs; }
+		if (!ok) { bmh_set_error("%s: out of memory", fn); return (int)BMH_ENOMEM; }
+		out->ascii[nb] = out->codes[nb] = 0; out->names[nn] = 0;
+		if (fq) out->quals[nb] = 0;
+		if (cm) out->comments[nc] = 0;
+		*rs = *out;
+		return (int)BMH_OK;
+	};
+	const bmh_batch_alloc_t none = [&](uint64_t, uint64_t, uint64_t, uint64_t, bool, bmh_read_set_t *) { bmh_set_error("%s: internal error: reads behind the end of the records", fn); return (int)BMH_EINVAL; };
+	bmh_bam_win_t w = {records, (size_t)n_bytes, true, cm, 0, 0, false, true, nullptr};
+	bmh_bam_res_t R; bmh_hbatch_t hb; bmh_read_set_t rs;
+	memset(&rs, 0, sizeof(rs));
+	int rc = 2;
+	if (d) rc = bmh_bam_dev_run(d, st, w, alloc, &rs, R);
+	if (rc == 2) rc = bmh_bam_host_run(st, w, alloc, &rs, R, hb);
+	if (rc >= 0 && R.consumed < n_bytes) {                  // what the end leaves over (a cut record, a record without its partner) is refused by name
+		st.n_recs = R.n_recs; st.qual = R.qual;
+		w.buf = records + R.consumed; w.have = (size_t)n_bytes - R.consumed;
+		bmh_bam_res_t R2;
+		rc = bmh_bam_host_run(st, w, none, &rs, R2, hb);
+		if (rc >= 0) { bmh_set_error("%s: internal error: the bytes behind the last read were not refused", fn); rc = BMH_EINVAL; }
+	}
+	if (rc < 0) { bmh_reads_free(out); return rc; }
+	if (R.n_reads) { out->n_reads = rs.n_reads; out->n_bases = rs.n_bases; out->n_name_bytes = rs.n_name_bytes; out->n_comment_bytes = rs.n_comment_bytes; }
+	const uint64_t bc[2] = {R.skipped, R.tags_left_out};
+	bmh_reads_note_bam_counts(bc);
+	return BMH_OK;
+}
+
+extern "C" int bmh_bam_reads_host(const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out)
+{
+	if ((!records && n_bytes) || !out) { bmh_set_error("bmh_bam_reads_host: null argument"); return BMH_EINVAL; }
+	return bmh_bam_reads_run("bmh_bam_reads_host", nullptr, records, n_bytes, flags, out);
 }

@@ -17,6 +17,8 @@
 // Records that are not complete in the window (a FASTA record is complete when the next header is there, or the file ends) stay in the text: the pump moves
 // the text behind the last record taken to the front of the buffer and reads on.  A batch always comes from ONE parse: if the window does not reach the
 // wanted bases, more text is read and the window is parsed again (the window is sized from the batch before it, so this is rare).
+// A BGZF file that holds a BAM is the pump's third kind (bam_open, bam_fill, bam_next below): its windows hold records instead of text, the host walks their chain
+// of starts and csrc/bam_in_kernels.hip decodes them; the carry rule, the batch cut and the growth of the window are the ones above.
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -300,9 +302,9 @@ struct stream_t {
 	}
 	~stream_t() { if (src) bmh_text_close(src); release(buf); }
 	void release(uint8_t *p) { if (!p) return; if (pinned && !on_dev) (void)hipHostFree(p); else free(p); }
-	int fill(size_t target)
+	// room for a window of `target` bytes, the text held kept
+	int reserve(size_t target)
 	{
-		if (eof || have >= target) return BMH_OK;
 		if (cap < target + 16) {
 			const size_t c = target + 16;
 			uint8_t *nb = nullptr;
@@ -312,6 +314,12 @@ struct stream_t {
 			if (have) memcpy(nb, buf, have);
 			release(buf); buf = nb; cap = c;
 		}
+		return BMH_OK;
+	}
+	int fill(size_t target)
+	{
+		if (eof || have >= target) return BMH_OK;
+		RCK(reserve(target));
 		const int64_t r = bmh_text_read(src, buf + have, target - have);
 		if (r < 0) return BMH_EINVAL;
 		if ((size_t)r < target - have) eof = true;
@@ -323,20 +331,6 @@ struct stream_t {
 
 // final: no further record can join this batch (the file -- with two files the one with fewer records in the window -- has ended)
 struct result_t { uint64_t n_reads = 0; bool complete = false, final_ = false; size_t consumed[2] = {0, 0}; int kind[2] = {0, 0}; uint64_t extra[2] = {0, 0}; bool took_all = false; };
-
-// the end of the batch among n reads of these lengths (step: 1, or 2 with two files); *complete: the wanted size was reached
-uint64_t cut_batch(const uint32_t *lens, uint64_t n, int step, uint64_t want_bases, uint64_t want_reads, bool even, bool *complete)
-{
-	uint64_t acc = 0;
-	*complete = false;
-	for (uint64_t r = 0; r + step <= n;) {
-		for (int k = 0; k < step; ++k) acc += lens[r + k];
-		r += step;
-		const bool full = want_reads ? r >= want_reads : acc >= want_bases;
-		if (full && (!even || !(r & 1))) { *complete = true; return r; }
-	}
-	return n;
-}
 
 struct dev_parser_t {
 	hipStream_t st = nullptr;
@@ -477,7 +471,7 @@ struct dev_parser_t {
 		const uint32_t *hl = h_lens.as<uint32_t>();
 		const uint64_t *ho = h_offs.as<uint64_t>(), *hn = h_noffs.as<uint64_t>(), *hc = h_coffs.as<uint64_t>();
 		bool complete = false;
-		const uint64_t k = take_all ? nt : cut_batch(hl, nt, nf, want_bases, want_reads, even, &complete);
+		const uint64_t k = take_all ? nt : bmh_cut_batch(hl, nt, nf, want_bases, want_reads, even, &complete);
 		R.complete = complete; R.took_all = k == nt;
 		if (!(complete || take_all || final_)) return 1;               // the window is too short for the batch: the pump reads on
 		const uint64_t nb = k < nt ? ho[k] : ho[nt - 1] + hl[nt - 1];
@@ -598,8 +592,92 @@ struct bmh_reads_pump_t {
 	stream_t S[2]; int nf = 1; bool comments = false, host_only = false;
 	dev_parser_t *dev = nullptr; bmh_hbatch_t hb;
 	size_t target = 0, chunk = 0; std::string pending; uint64_t n_dev = 0, n_host = 0, n_records = 0;
-	~bmh_reads_pump_t() { delete dev; }
+	// the third kind: S[0] delivers BAM records (csrc/bam_in_core.h), bs is what its windows share
+	bool bam = false; bmh_bam_state_t bs; bmh_bam_dev_t *bdev = nullptr;
+	std::vector<uint32_t> chain;                           // the record starts of S[0]'s window found so far; its last entry is where the walk stands
+	~bmh_reads_pump_t() { delete dev; if (bdev) bmh_bam_dev_free(bdev); }
 };
+
+namespace {
+constexpr size_t MAX_WINDOW = ((size_t)1 << 31) - 4096;
+
+// A BAM file is opened: its header (magic, text, reference table: walked and ignored) is consumed whole, and the first record that gives a read says whether the
+// file holds pairs (flag 0x1) -- before a run starts its lanes.  The window grows by the doubling rule until it holds both.
+int bam_open(bmh_reads_pump_t *P)
+{
+	stream_t &S = P->S[0];
+	const char *path = S.path.c_str();
+	P->bs.path = S.path;
+	size_t t = P->chunk ? P->chunk : 65536;
+	for (;;) {
+		RCK(S.fill(t));
+		const int64_t hb = bmh_bam_header_bytes(S.buf, S.have);
+		if (hb < 0) { bmh_set_error("reads file: %s: no BAM header behind the magic bytes", path); return BMH_EINVAL; }
+		if (hb > 0) { S.consume((size_t)hb); break; }
+		if (S.eof) { bmh_set_error("reads file: %s: the file ends inside the BAM header", path); return BMH_EINVAL; }
+		if (t >= MAX_WINDOW) { bmh_set_error("reads file: %s: a BAM header of 2^31 bytes or more", path); return BMH_EINVAL; }
+		t = std::min(MAX_WINDOW, t * 2);
+	}
+	for (;;) {
+		RCK(S.fill(t));
+		uint32_t flag = 0;
+		const int k = bmh_bam_first_kept(S.buf, S.have, &flag);
+		if (k == 1) P->bs.paired = (int)(flag & 1u);
+		if (k != 0 || S.eof || t >= MAX_WINDOW) break;        // (found; damaged, cut or endless: the first parse names it)
+		t = std::min(MAX_WINDOW, t * 2);
+	}
+	return BMH_OK;
+}
+
+// The window is filled a piece at a time and the chain of record starts walked behind every piece, while the bytes the inflate has just written are still in
+// the loader thread's cache: the walk is one dependent load per record, and over a whole window that has left the cache it costs a memory latency each (31 ms per
+// million 150 bp records measured that way).
+int bam_fill(bmh_reads_pump_t *P)
+{
+	constexpr size_t PIECE = (size_t)1 << 20;
+	stream_t &S = P->S[0];
+	if (P->chain.empty()) P->chain.push_back(0);
+	RCK(S.reserve(P->target));
+	for (;;) {
+		bmh_bam_chain_extend(S.buf, S.have, P->chain);
+		if (S.eof || S.have >= P->target) return BMH_OK;
+		RCK(S.fill(std::min(P->target, S.have + PIECE)));
+	}
+}
+
+int bam_next(bmh_reads_pump_t *P, uint64_t want_bases, uint64_t want_reads, bool even, bool take_all, const bmh_batch_alloc_t &alloc, bmh_read_set_t *rs)
+{
+	stream_t &S = P->S[0];
+	for (;;) {
+		RCK(bam_fill(P));
+		if (S.eof && S.have == 0) return 0;
+		const bmh_bam_win_t w = {S.buf, S.have, S.eof, P->comments, want_bases, want_reads, even, take_all, &P->chain};
+		bmh_bam_res_t R;
+		int rc = 2;
+		if (!P->host_only) rc = bmh_bam_dev_run(P->bdev, P->bs, w, alloc, rs, R);
+		if (rc == 2) { rc = bmh_bam_host_run(P->bs, w, alloc, rs, R, P->hb); if (rc >= 0) ++P->n_host; }
+		else if (rc >= 0) ++P->n_dev;
+		if (rc < 0) return rc;
+		if (R.complete || (take_all && R.n_reads > 0) || R.final_) {
+			S.consume(R.consumed);
+			// (R.consumed is the start of record R.n_recs: the chain behind it stays, moved with the bytes)
+			P->chain.erase(P->chain.begin(), P->chain.begin() + (size_t)R.n_recs);
+			for (uint32_t &c : P->chain) c -= (uint32_t)R.consumed;
+			P->bs.n_recs += R.n_recs; P->bs.n_skipped += R.skipped; P->bs.n_tags_left_out += R.tags_left_out; P->bs.qual = R.qual;
+			P->n_records += R.n_reads;
+			if (R.n_reads > 0) {
+				if (!take_all && !P->chunk) P->target = std::min(MAX_WINDOW, R.consumed + R.consumed / 16 + (1u << 16));
+				return 1;
+			}
+			if (S.eof && S.have == 0) return 0;
+			if (R.consumed > 0 || (!S.eof && S.have < P->target)) continue;
+		}
+		// the window holds no complete batch (or not one whole record): a larger one
+		if (P->target >= MAX_WINDOW) { bmh_set_error("reads file: a batch (or one record) needs more than 2^31 bytes of BAM records"); return BMH_EINVAL; }
+		P->target = std::min(MAX_WINDOW, P->target * 2);
+	}
+}
+}   // namespace
 
 bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_threads, bool comments, bool host_only, size_t chunk_bytes)
 {
@@ -614,9 +692,26 @@ bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_thre
 		// section 4.8); BMH_INFLATE_HOST=1 overrides it (the A/B switch); a plain gzip stream stays with the host
 		P->S[f].on_dev = !host_only && bmh_text_kind(P->S[f].src) == 2 && bmh_tune("INFLATE_DEVICE", 0) != 0 && bmh_tune("INFLATE_HOST", 0) == 0;
 	}
+	for (int f = 0; f < P->nf; ++f) {
+		const int b = bmh_text_bam(P->S[f].src);
+		if (b == 1 && P->nf == 1) { P->bam = true; continue; }
+		if (b == 1) bmh_set_error("reads files: %s is a BAM file, which holds both reads of its pairs: no mates file is taken beside it", paths[f]);
+		else if (b == 2) bmh_set_error("reads file: %s holds a BAM in a plain gzip stream: a BAM file is BGZF (what samtools and bgzip write)", paths[f]);
+		if (b != 0) { delete P; return nullptr; }
+	}
+	if (P->bam) {
+		// BAM always takes the host inflate, also with BMH_INFLATE_DEVICE=1: the record starts are a chain the host walks over the window it has just inflated
+		P->S[0].on_dev = false;
+		if (!host_only) P->bdev = bmh_bam_dev_create();
+		if (bam_open(P) != BMH_OK) { delete P; return nullptr; }
+		return P;
+	}
 	if (!host_only) P->dev = new dev_parser_t();
 	return P;
 }
+
+int bmh_pump_bam_paired(const bmh_reads_pump_t *p) { return p->bam ? p->bs.paired : -1; }
+void bmh_pump_bam_counts(const bmh_reads_pump_t *p, uint64_t out[2]) { out[0] = p->bs.n_skipped; out[1] = p->bs.n_tags_left_out; }
 
 void bmh_pump_counts(const bmh_reads_pump_t *p, uint64_t out[4])
 {
@@ -635,12 +730,12 @@ int bmh_pump_next(bmh_reads_pump_t *P, uint64_t want_bases, uint64_t want_reads,
 {
 	if (!P->pending.empty()) { bmh_set_error("%s", P->pending.c_str()); return BMH_EINVAL; }
 	const int nf = P->nf;
-	constexpr size_t MAX_WINDOW = ((size_t)1 << 31) - 4096;
 	if (P->target == 0) {
 		if (P->chunk) P->target = P->chunk;
 		else if (take_all) P->target = (size_t)64 << 20;
 		else P->target = (size_t)std::min<uint64_t>(MAX_WINDOW, (want_reads ? want_reads * 400 : want_bases * 5 / 2) / (uint64_t)nf + (1u << 20));
 	}
+	if (P->bam) return bam_next(P, want_bases, want_reads, even, take_all, alloc, rs);
 	for (;;) {
 		hipStream_t st = nullptr;
 		if (P->dev) { const int src = P->dev->stream(&st); if (src != BMH_OK) return src; }
@@ -707,7 +802,10 @@ int bmh_pump_next(bmh_reads_pump_t *P, uint64_t want_bases, uint64_t want_reads,
 }
 
 // ---- the whole of one or two files as a read set
-namespace { uint64_t g_last_counts[4] = {0, 0, 0, 0}, g_last_inflate[2] = {0, 0}; std::mutex g_counts_mu; }
+namespace { uint64_t g_last_counts[4] = {0, 0, 0, 0}, g_last_inflate[2] = {0, 0}, g_last_bam[2] = {0, 0}; std::mutex g_counts_mu; }
+
+extern "C" int bmh_reads_last_bam_counts(uint64_t *out) { if (!out) return BMH_EINVAL; std::lock_guard<std::mutex> lk(g_counts_mu); memcpy(out, g_last_bam, sizeof(g_last_bam)); return BMH_OK; }
+void bmh_reads_note_bam_counts(const uint64_t *c) { std::lock_guard<std::mutex> lk(g_counts_mu); memcpy(g_last_bam, c, sizeof(g_last_bam)); }
 
 extern "C" int bmh_reads_last_inflate_counts(uint64_t *out) { if (!out) return BMH_EINVAL; std::lock_guard<std::mutex> lk(g_counts_mu); memcpy(out, g_last_inflate, sizeof(g_last_inflate)); return BMH_OK; }
 void bmh_reads_note_inflate_counts(const uint64_t *c) { std::lock_guard<std::mutex> lk(g_counts_mu); memcpy(g_last_inflate, c, sizeof(g_last_inflate)); }
@@ -745,6 +843,7 @@ extern "C" int bmh_reads_load_files(const char *path1, const char *path2, int n_
 	}
 	uint64_t cnt[4]; bmh_pump_counts(P, cnt); bmh_reads_note_counts(cnt);
 	uint64_t icnt[2]; bmh_pump_inflate_counts(P, icnt); bmh_reads_note_inflate_counts(icnt);
+	uint64_t bcnt[2]; bmh_pump_bam_counts(P, bcnt); bmh_reads_note_bam_counts(bcnt);
 	const bool partial = rc < 0 && strstr(bmh_last_error(), " ends before ") != nullptr;       // the complete pairs come back with the refusal
 	bmh_pump_close(P);
 	if (rc < 0 && !partial) return rc;

@@ -1,7 +1,8 @@
 // The text of a read file, in order, whatever it is wrapped in (bmh_reads_load_files, bmh_aligner_run_files): a plain file or pipe, a gzip stream
 // (recognised by its magic bytes 1f 8b, concatenated members read as one stream, as gzread does) or BGZF (gzip members of at most 64 KiB whose extra field
 // "BC" carries the member's size: what bgzip and the sequencers' converters write) -- BGZF members are independent, so they are inflated on several host
-// threads, in order; a plain gzip stream is one dependent bit stream and stays on one thread.  zlib is loaded at run time (dlopen("libz.so.1"), as
+// threads, in order; a plain gzip stream is one dependent bit stream and stays on one thread.  A BGZF file whose text begins with "BAM\1" holds BAM records, not
+// text: it is recognised here from those bytes (peek_bam), never from the file's name, and the pump (csrc/reads_parse.hip) takes it as its third kind.  zlib is loaded at run time (dlopen("libz.so.1"), as
 // csrc/fasta_pack.hip does): no link dependency, and a clear message when it is missing.  Nothing is mapped and nothing is sought: every form reads its
 // descriptor front to back.
 #include <dlfcn.h>
@@ -233,6 +234,44 @@ struct bmh_text_src_t {
 		return (int64_t)p;
 	}
 
+	// Does the text begin with "BAM\1"?  Looked at without taking a byte: the first members are inflated into a buffer of their own (BGZF), or the stream's first
+	// bytes with a z_stream of its own (gzip).  0 no, 1 a BGZF file that does, 2 a plain gzip stream that does, -1 a read error.  A damaged first member is no
+	// BAM here: the reader meets it again and words the refusal.
+	int peek_bam()
+	{
+		uint8_t head[4]; size_t got = 0;
+		if (kind == SRC_BGZF) {
+			std::vector<uint8_t> tmp(BGZF_MAX);
+			size_t rel = 0;
+			for (int m = 0; got < 4 && m < 16; ++m) {                 // (empty members in front of the text are legal)
+				if (in_len - in_pos - rel < BGZF_MAX + 18 && !in_eof && !refill(rel + 2 * (BGZF_MAX + 18))) return -1;
+				const uint8_t *mp = in.data() + in_pos + rel;
+				const size_t avail = in_len - in_pos - rel;
+				size_t data = 0;
+				const size_t bs = bgzf_size(mp, avail, &data);
+				if (bs == (size_t)-1 || bs == 0 || bs < data + 8 || avail < bs) break;
+				zs_t s; memset(&s, 0, sizeof(s));
+				if (z.init2(&s, -15, z.ver, (int)sizeof(zs_t)) != Z_OK_) break;
+				s.next_in = mp + data; s.avail_in = (unsigned)(bs - data - 8); s.next_out = tmp.data(); s.avail_out = (unsigned)BGZF_MAX;
+				const int rc = z.inflate(&s, 4 /* Z_FINISH */);
+				const size_t n = BGZF_MAX - s.avail_out;
+				z.end(&s);
+				if (rc != Z_STREAM_END_) break;
+				for (size_t k = 0; k < n && got < 4; ++k) head[got++] = tmp[k];
+				rel += bs;
+			}
+		} else if (kind == SRC_GZIP) {
+			if (in_len - in_pos < 4096 && !in_eof && !refill(4096)) return -1;
+			zs_t s; memset(&s, 0, sizeof(s));
+			if (z.init2(&s, 15 + 16, z.ver, (int)sizeof(zs_t)) != Z_OK_) return 0;
+			s.next_in = in.data() + in_pos; s.avail_in = (unsigned)(in_len - in_pos); s.next_out = head; s.avail_out = 4;
+			(void)z.inflate(&s, 0);
+			got = 4 - s.avail_out;
+			z.end(&s);
+		}
+		return got == 4 && memcmp(head, "BAM\1", 4) == 0 ? (kind == SRC_BGZF ? 1 : 2) : 0;
+	}
+
 	int64_t read_bgzf(uint8_t *dst, size_t n)
 	{
 		size_t done = 0;
@@ -285,6 +324,7 @@ int64_t bmh_text_read(bmh_text_src_t *s, uint8_t *dst, size_t n)
 }
 
 int bmh_text_kind(const bmh_text_src_t *s) { return s->kind; }
+int bmh_text_bam(bmh_text_src_t *s) { return s->peek_bam(); }
 size_t bmh_text_pending(const bmh_text_src_t *s) { return s->in_len - s->in_pos; }
 uint64_t bmh_text_host_members(const bmh_text_src_t *s) { return s->n_host_members; }
 int64_t bmh_text_members(bmh_text_src_t *s, uint8_t *dst, size_t cap, size_t want_text, std::vector<bmh_inflate_member_t> &tab, uint64_t *text_bytes, bool *end)

@@ -477,6 +477,27 @@ void bmh_reads_free(bmh_read_set_t *r);
  */
 #define BMH_READS_HOST 2
 int bmh_reads_load_files(const char *path1, const char *path2, int n_threads, int flags, bmh_read_set_t *out);
+/* ---- BAM as read input (csrc/bam_in_core.h, csrc/bam_in_kernels.hip): unaligned BAM, or an aligned one grouped by read name.  bmh_reads_load_files and
+ * bmh_aligner_run_files take a BGZF file whose inflated bytes begin with "BAM\1" -- recognised from those bytes, a regular file or a pipe -- in place of a text file;
+ * a mates file beside it and a BAM in a plain gzip stream are refused with a message.  The rules are those of `samtools fastq`: records with flag 0x100 or 0x800
+ * give no read; a record with flag 0x10 gives its read back in sequencing orientation (bases complemented and reversed, qualities reversed); letters from
+ * "=ACMGRSVTWYHKDBN"; qualities + 33, a record whose qualities are all 0xff has none (quals is NULL when no record has any; a file that mixes both, a quality above
+ * 93 and l_seq 0 are refused); names verbatim.  Flag 0x1 on the first record kept means pairs: the two records of a pair are adjacent, in either order, and the 0x40
+ * record becomes read 2i, the 0x80 record read 2i+1 (two names, two records of one role, a record without partner, 0x1 on some records only: refused, naming the
+ * record's index in the file).  With BMH_READS_COMMENTS the tags become the comment: XX:T:value fields joined by tabs in file order, A as it is, c C s S i I as i,
+ * Z and H copied; f and B tags are left out, and so are NM MD AS XS SA XA pa RG MC MQ.  The header's text and reference table, refID, pos, mapq, the CIGAR and the
+ * mate fields are ignored.  The host walks the chain of record starts (a record names its own length) over each inflated window -- BAM therefore always takes the
+ * host inflate, also with BMH_INFLATE_DEVICE=1 --; validation, pairing, the scans, bases, qualities, names and comments are kernels.  A record that fails a check
+ * hands its window to the host form, which words the refusal.
+ * bmh_bam_reads_device / bmh_bam_reads_host: the step on its own -- uncompressed BAM records in host memory, without the header, as one read set (bmh_reads_free);
+ * flags: BMH_READS_COMMENTS.  bmh_reads_last_bam_counts: out[2] of the process's last such call, bmh_reads_load_files or bmh_aligner_run_files call: records
+ * skipped (0x100 / 0x800), f and B tags left out.
+ * bmh_aligner_set_bam_pairs: bmh_aligner_run_files is told `paired` before it has opened its file; when a BAM then turns out to hold pairs and paired was 0, the
+ * run takes this batch_bases (0: the argument's; ignored with batch_reads) and this n_lanes (0: the argument's) in place of its arguments.  A BAM without flag 0x1
+ * and paired != 0 is refused. */
+int bmh_bam_reads_device(const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out);
+int bmh_bam_reads_host(const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out);
+int bmh_reads_last_bam_counts(uint64_t *out);
 
 /* ---- BGZF members inflated on the device (csrc/inflate_core.h, csrc/inflate_kernels.hip): all of RFC 1951, one lane per member, the CRC32 of the text
  * computed and compared there too.  BGZF (what bgzip writes) is a series of gzip members of at most 64 KiB of text, each naming its own size in the extra
@@ -858,6 +879,7 @@ int bmh_bam_sorted_file_markdup_device(const char *header_text, int n_contigs, c
 int bmh_bam_sorted_file_markdup_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
                                      int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8]);
 int bmh_aligner_set_markdup(bmh_aligner_t *a, int on);
+int bmh_aligner_set_bam_pairs(bmh_aligner_t *a, uint64_t batch_bases, int n_lanes);        /* (described with bmh_bam_reads_device above) */
 int bmh_aligner_markdup_counts(bmh_aligner_t *a, uint64_t out[8]);
 /* where the last marked run's extra time went: [0] the decision, ms  [1] the windows' flag steps (ordinals up, flag kernel), ms  [2] bytes of ordinals and entries
  * that came down with the batches */

@@ -2,7 +2,8 @@
 (scripts/fastq_cost.py's setup), single-end and paired, through
   * bmh_aligner_run_file on the plain interleaved file (the yardstick: the path that exists without csrc/reads_parse.hip) -- in this tree
     and, with --parent DIR, in a built tree of the parent commit (a child process with that tree's package and library, the same files),
-  * bmh_aligner_run_files on the same plain file, on two plain files (paired), on BGZF and on single-member gzip.
+  * bmh_aligner_run_files on the same plain file, on two plain files (paired), on BGZF and on single-member gzip,
+  * bmh_aligner_run_files on the same reads as unaligned BAM (align_files_bam; --configs align_files_bgzf,align_files_bam gives the two rows to compare).
 Every configuration runs once to warm the lanes, then --runs times; each row lists every run, the median, the spread, the host CPU
 seconds of the process per million reads, and how many windows the device parser cut and how many the host walker took.
 
@@ -12,6 +13,8 @@ kernel trace in a run of its own (rocprofv3 --kernel-trace --stats -- python scr
 --inflate-only times nothing else than the device inflate (csrc/inflate_kernels.hip): the BGZF members of a FASTQ text of --reads reads go up once, then the
 kernel alone runs on the first 1024, 4096, 16384 ... and on all of them, several launches each (rocprofv3 --kernel-trace --stats -- python
 scripts/reads_input_rate.py --inflate-only); beside it zlib on the same members on the host's threads, the yardstick, and the library's own host decoder.
+
+--bam-only times nothing else than the BAM input path: the host's chain walk over the records alone, then loads of the BAM file for a kernel trace.
 
     python scripts/reads_input_rate.py [--genome-mbp 3100] [--reads 1000000] [--runs 3] [--modes se,pe] [--parent DIR] [--out profiles/reads_input.json]
 """
@@ -62,6 +65,39 @@ def fastq_records(names: np.ndarray, w: int, asc: np.ndarray, qual: np.ndarray, 
     return recs
 
 
+NT16 = np.zeros(256, np.uint8)
+for _i, _c in enumerate(b"=ACMGRSVTWYHKDBN"):
+    NT16[_c] = _i
+
+
+def bam_records(names: np.ndarray, w: int, asc: np.ndarray, qual: np.ndarray, rl: int, paired: bool) -> np.ndarray:
+    """the same reads as unaligned BAM records (one row each): flag 4, or 0x4D / 0x8D in turn for pairs; no CIGAR, no tags"""
+    n = asc.size // rl
+    nm = np.frombuffer("".join(names.tolist()).encode(), np.uint8).reshape(n, w + 1)
+    l_name, half = w + 2, (rl + 1) // 2
+    bs = 32 + l_name + half + rl
+    rec = np.zeros((n, 4 + bs), np.uint8)
+    rec[:, 0:4] = np.frombuffer(struct.pack("<I", bs), np.uint8)
+    rec[:, 4:12] = 0xff                                                          # refID, pos: -1
+    rec[:, 12] = l_name
+    rec[:, 14:16] = np.frombuffer(struct.pack("<H", 4680), np.uint8)
+    rec[:, 18] = 4
+    if paired:
+        rec[0::2, 18] = 0x4D; rec[1::2, 18] = 0x8D
+    rec[:, 20:24] = np.frombuffer(struct.pack("<I", rl), np.uint8)
+    rec[:, 24:32] = 0xff                                                         # next_refID, next_pos: -1
+    rec[:, 36:36 + w + 1] = nm
+    nib = np.zeros((n, 2 * half), np.uint8); nib[:, :rl] = NT16[asc.reshape(n, rl)]
+    s0 = 36 + l_name
+    rec[:, s0:s0 + half] = (nib[:, 0::2] << 4) | nib[:, 1::2]
+    rec[:, s0 + half:] = qual.reshape(n, rl) - 33
+    return rec
+
+
+BAM_TEXT = b"@HD\tVN:1.6\tSO:unsorted\n"
+BAM_HEADER = b"BAM\1" + struct.pack("<I", len(BAM_TEXT)) + BAM_TEXT + struct.pack("<I", 0)      # no reference sequences: the reads are unaligned
+
+
 def measure(fn, runs: int, n4: int) -> dict:
     """fn once to warm, then `runs` times: median rate, every run, spread, host CPU seconds (user + system of the process) per million reads"""
     secs, cpus = [], []
@@ -93,6 +129,38 @@ def parser_only(a):
         rs = read_reads_files(path, comments=True)
         dt = time.perf_counter() - t0
         print(json.dumps({"reads": len(rs), "text_bytes": os.path.getsize(path), "load_s": round(dt, 3), "counts": reads_last_counts()}), flush=True)
+    os.remove(path)
+
+
+def bam_only(a):
+    """nothing but the BAM input path: the host's chain walk over the records of --reads reads in memory, timed alone, then the file loaded through
+    bmh_reads_load_files (64 MiB windows), for a kernel trace in a run of its own (rocprofv3 --kernel-trace --stats -- python scripts/reads_input_rate.py --bam-only)"""
+    from bwamem_hip.aligner import read_reads_files
+    from bwamem_hip.lib import reads_last_counts
+    L = B.load_library()
+    n, rl = a.reads, 150
+    rng = np.random.default_rng(1)
+    asc = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, n * rl)]
+    qual = rng.integers(33, 75, size=n * rl).astype(np.uint8)
+    w = len(str(n))
+    names = np.char.add("r", np.char.zfill(np.arange(n).astype(str), w))
+    records = bam_records(names, w, asc, qual, rl, False).tobytes()
+    L.bmh_bam_chain_count.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    nr, end = C.c_uint64(), C.c_uint64()
+    ms = []
+    for it in range(4):
+        t0 = time.perf_counter()
+        assert L.bmh_bam_chain_count(records, len(records), C.byref(nr), C.byref(end)) == 0
+        ms.append((time.perf_counter() - t0) * 1e3)
+    assert nr.value == n and end.value == len(records)
+    print(json.dumps({"chain_walk_ms": [round(x, 3) for x in ms], "records": n, "ms_per_Mrecords": round(sorted(ms[1:])[1] / (n / 1e6), 3)}), flush=True)
+    path = os.path.join(tempfile.gettempdir(), "bmh_bam_only_%d.bam" % os.getpid())
+    write_bgzf(path, BAM_HEADER + records)
+    for it in range(3):
+        t0 = time.perf_counter()
+        rs = read_reads_files(path, comments=True)
+        dt = time.perf_counter() - t0
+        print(json.dumps({"reads": len(rs), "record_bytes": len(records), "file_bytes": os.path.getsize(path), "load_s": round(dt, 3), "counts": reads_last_counts()}), flush=True)
     os.remove(path)
 
 
@@ -175,12 +243,16 @@ def main():
     ap.add_argument("--parent", default="", help="a built tree of the parent commit: its align_file on the same plain file, in a child process")
     ap.add_argument("--parser-only", action="store_true")
     ap.add_argument("--inflate-only", action="store_true")
+    ap.add_argument("--bam-only", action="store_true")
+    ap.add_argument("--configs", default="", help="only these rows (comma-separated keys, e.g. align_files_bgzf,align_files_bam); default: all")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)          # the plain file the --parent child aligns (mode and sizes from the other options)
     a = ap.parse_args()
     if a.parser_only:
         return parser_only(a)
     if a.inflate_only:
         return inflate_only(a)
+    if a.bam_only:
+        return bam_only(a)
     dev = torch.device("cuda:0")
     L = B.load_library()
     n_genome = int(a.genome_mbp * 1e6)
@@ -227,8 +299,12 @@ def main():
         recs = fastq_records(names, w, asc, qual, rl)
         p = lambda s: os.path.join(tmp, mode + "." + s)  # noqa: E731
         recs.tofile(p("fq"))
-        write_bgzf(p("fq.bgzf"), recs.tobytes()); write_gzip(p("fq.gz"), recs.tobytes())
-        if paired:
+        only = set(a.configs.split(",")) if a.configs else None
+        write_bgzf(p("fq.bgzf"), recs.tobytes())
+        if only is None or any("gzip" in k for k in only):
+            write_gzip(p("fq.gz"), recs.tobytes())
+        write_bgzf(p("bam"), BAM_HEADER + bam_records(names, w, asc, qual, rl, paired).tobytes())       # the same reads as unaligned BAM: half the bytes, no lines
+        if paired and (only is None or any("two" in k for k in only)):
             recs[0::2].tofile(p("r1.fq")); recs[1::2].tofile(p("r2.fq"))
             write_bgzf(p("r1.bgzf"), recs[0::2].tobytes()); write_bgzf(p("r2.bgzf"), recs[1::2].tobytes())
             write_gzip(p("r1.gz"), recs[0::2].tobytes()); write_gzip(p("r2.gz"), recs[1::2].tobytes())
@@ -253,12 +329,15 @@ def main():
                    "align_files_plain": lambda: nat.run_files(p("fq"), None, paired, sink, **kw),
                    "align_files_bgzf": lambda: nat.run_files(p("fq.bgzf"), None, paired, sink, **kw),
                    "align_files_bgzf_device_inflate": lambda: device_inflate(lambda: nat.run_files(p("fq.bgzf"), None, paired, sink, **kw)),
-                   "align_files_gzip": lambda: nat.run_files(p("fq.gz"), None, paired, sink, **kw)}
+                   "align_files_gzip": lambda: nat.run_files(p("fq.gz"), None, paired, sink, **kw),
+                   "align_files_bam": lambda: nat.run_files(p("bam"), None, paired, sink, **kw)}
         if paired:
             configs.update({"align_files_two_plain": lambda: nat.run_files(p("r1.fq"), p("r2.fq"), True, sink, **kw),
                             "align_files_two_bgzf": lambda: nat.run_files(p("r1.bgzf"), p("r2.bgzf"), True, sink, **kw),
                             "align_files_two_bgzf_device_inflate": lambda: device_inflate(lambda: nat.run_files(p("r1.bgzf"), p("r2.bgzf"), True, sink, **kw)),
                             "align_files_two_gzip": lambda: nat.run_files(p("r1.gz"), p("r2.gz"), True, sink, **kw)})
+        if only is not None:
+            configs = {k: v for k, v in configs.items() if k in only}
         rows, sizes = {}, set()
         if a.parent:
             import subprocess
@@ -275,6 +354,8 @@ def main():
             rows[key]["sam_bytes"] = int(bytes_out[0]); sizes.add(bytes_out[0])
             if key != "align_file_plain":
                 rows[key]["parser"] = reads_last_counts()
+            if key == "align_files_bam":
+                rows[key]["file_bytes"] = os.path.getsize(p("bam")); rows[key]["bgzf_fastq_file_bytes"] = os.path.getsize(p("fq.bgzf"))
             print(mode, key, json.dumps(rows[key]), flush=True)
         assert len(sizes) == 1, ("the configurations wrote different amounts of text", sizes)
         nat.free()
