@@ -225,6 +225,48 @@ def _raise_beyond_cap(e: Exception) -> None:
                                   "flanks of up to EXT_LONG_MAX bases; the reference's own GASAL2 build is sized by MAX_SEQ_LEN, README.md:38)") from e
 
 
+def parse_rg_line(v: str, what: str = "-R"):
+    """a read group line as the command line gives it -> (the line, its ID) by bwa_set_rg's rules (src/bwa.c:425-452); `what` names the option in messages.
+    bwa_escape (src/bwa.c:409-423): ONE pass from the left -- a backslash consumes the character behind it, which becomes a tab / newline / carriage return /
+    backslash for t / n / r / \\ and nothing at all otherwise ("\\\\t" is a backslash and a 't', not a backslash and a tab)"""
+    import re
+    if not v.startswith("@RG"):
+        raise ValueError(f"{what}: the read group line must start with @RG")
+    line = re.sub(r"\\(.?)", lambda m: {"t": "\t", "n": "\n", "r": "\r", "\\": "\\"}.get(m.group(1), ""), v, flags=re.S)
+    if "\tID:" not in line:
+        raise ValueError(f"{what}: the read group line must hold an ID")
+    rid = re.split("[\t\n]", line.split("\tID:", 1)[1], 1)[0]            # the ID ends at the first tab or newline (src/bwa.c:440-446)
+    if len(rid) > 255:
+        raise ValueError(f"{what}: @RG:ID is longer than 255 characters")
+    return line, rid
+
+
+def rg_library(rg_line: str) -> str:
+    """the library of a read group line: its LB field, else Picard's Unknown Library"""
+    lib = "Unknown Library"
+    for f in rg_line.split("\t")[1:]:
+        if f.startswith("LB:") and len(f) > 3:
+            lib = f[3:]
+    return lib
+
+
+_METRICS_COLUMNS = ("LIBRARY", "UNPAIRED_READS_EXAMINED", "READ_PAIRS_EXAMINED", "SECONDARY_OR_SUPPLEMENTARY_RDS", "UNMAPPED_READS", "UNPAIRED_READ_DUPLICATES", "READ_PAIR_DUPLICATES",
+                    "PERCENT_DUPLICATION")
+
+
+def _metrics_row(lib: str, counts: dict) -> list:
+    fr, pr, df, dp = counts["fragments_examined"], counts["pairs_examined"], counts["duplicate_fragments"], counts["duplicate_pairs"]
+    den = fr + 2 * pr
+    return [lib, fr, pr, counts["secondary_or_supplementary"], counts["unmapped_records"], df, dp, "%.6f" % ((df + 2 * dp) / den) if den else "0"]
+
+
+def markdup_metrics_text_libraries(library_counts: dict) -> str:
+    """markdup_metrics_text for a run over read groups: the class line, the header row and one row per library -- library_counts: {library name: counts}, in order
+    of first appearance (dicts keep it)"""
+    return "## METRICS CLASS\tbwamem_hip.DuplicationMetrics\n" + "\t".join(_METRICS_COLUMNS) + "\n" + \
+           "".join("\t".join(str(v) for v in _metrics_row(lib, c)) + "\n" for lib, c in library_counts.items())
+
+
 def markdup_metrics_text(counts: dict, rg_line: str = "") -> str:
     """the Picard-style metrics table of a marked run: a class line, the header row and one row (one library per run: the read group's LB, else Unknown Library)"""
     lib = "Unknown Library"
@@ -337,17 +379,7 @@ class Aligner:
             elif f == "-U": pe.pen_unpaired = int(v)
             elif f == "-m": pe.max_matesw = int(v)
             elif f == "-R":                                             # read group (bwa_set_rg, src/bwa.c:425-452): the header line and the records' RG:Z tag
-                # bwa_escape (src/bwa.c:409-423): ONE pass from the left -- a backslash consumes the character behind it, which becomes a tab / newline /
-                # carriage return / backslash for t / n / r / \\ and nothing at all otherwise ("\\\\t" is a backslash and a 't', not a backslash and a tab)
-                if not v.startswith("@RG"):
-                    raise ValueError("-R: the read group line must start with @RG")
-                import re
-                line = re.sub(r"\\(.?)", lambda m: {"t": "\t", "n": "\n", "r": "\r", "\\": "\\"}.get(m.group(1), ""), v, flags=re.S)
-                if "\tID:" not in line:
-                    raise ValueError("-R: the read group line must hold an ID")
-                rid = re.split("[\t\n]", line.split("\tID:", 1)[1], 1)[0]            # the ID ends at the first tab or newline (src/bwa.c:440-446)
-                if len(rid) > 255:
-                    raise ValueError("-R: @RG:ID is longer than 255 characters")
+                line, rid = parse_rg_line(v, "-R")                      # (unescaped and checked by bwa_set_rg's rules)
                 self.rg_line = line; self._rg_id = rid.encode(); po.rg_id = self._rg_id
                 if getattr(self, "_native", None) is not None: self._native.free(); self._native = None
             elif f == "-t": self.ref_threads = int(v)                   # the reference cuts its batches at chunk_size * n_threads bases (align_file)
@@ -360,7 +392,9 @@ class Aligner:
         if max_mem_intv is not None: self.reseed.max_mem_intv = int(max_mem_intv)
 
     def header(self) -> str:
-        return "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in self.contigs) + (getattr(self, "rg_line", "") + "\n" if getattr(self, "rg_line", "") else "")
+        """the @SQ lines and the read group's line; during a run over read groups (align_groups) every group's @RG line, in group order"""
+        rg = [g[0] for g in getattr(self, "_groups", None) or ()] or ([self.rg_line] if getattr(self, "rg_line", "") else [])
+        return "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in self.contigs) + "".join(line + "\n" for line in rg)
 
     def _bam_open(self, out, fmt: str, level: int, sort: bool = False) -> bool:
         """fmt="bam": checks `out` and writes the header members (bmh_bam_header of header(), compressed by the host core); True for BAM"""
@@ -700,6 +734,9 @@ class Aligner:
             if markdup:
                 from .lib import MARKDUP_COUNTS
                 self.markdup_counts = self._native.markdup_counts() if n else dict.fromkeys(MARKDUP_COUNTS, 0)
+                if getattr(self, "_groups", None):                # per library, in order of first appearance (the library index of the run)
+                    libs = list(dict.fromkeys(rg_library(g[0]) for g in self._groups))
+                    self.markdup_library_counts = {lb: (self._native.markdup_library_counts(k) if n else dict.fromkeys(MARKDUP_COUNTS, 0)) for k, lb in enumerate(libs)}
         finally:
             self._out_fmt = ("sam", 1)
             self._markdup = False
@@ -720,7 +757,7 @@ class Aligner:
                 with open(index, "wb") as f:
                     f.write(bai)
         if markdup_metrics is not None:
-            text = markdup_metrics_text(self.markdup_counts, getattr(self, "rg_line", ""))
+            text = markdup_metrics_text_libraries(self.markdup_library_counts) if getattr(self, "_groups", None) else markdup_metrics_text(self.markdup_counts, getattr(self, "rg_line", ""))
             if hasattr(markdup_metrics, "write"):
                 markdup_metrics.write(text)
             else:
@@ -756,6 +793,68 @@ class Aligner:
             self.last_stats = nat.run_files(reads, mates, paired, (lambda mv: out.write(mv)) if binary else (lambda mv: out.write(bytes(mv).decode())),
                                              batch_bases=cb, batch_reads=max(batch_reads, 0),
                                              n_lanes=int(os.environ.get("BMH_ALIGNER_LANES", "3" if paired else "2")), n_threads=self.n_threads)
+        except RuntimeError as e:
+            _raise_beyond_cap(e)
+            raise
+        self.host_tail_batches = nat.host_tail_batches()
+        return int(self.last_stats.n_reads)
+
+    def align_groups(self, groups, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
+                     sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None) -> int:
+        """several read groups -- a sample's lanes and libraries -- into one output (bmh_aligner_run_groups).  groups: [(rg_line, reads, mates or None), ...]; every
+        rg_line is unescaped and checked as -R's value is, reads / mates are what align_files takes (one file or R1 + R2; plain, gzip or BGZF; FASTA or FASTQ; or
+        one BAM, whose own @RG lines and RG tags stay ignored).  Group g's records are byte for byte those of align_files(reads_g, mates_g) alone under -R rg_g, and
+        the unsorted output is the groups' outputs in order; the header holds every @RG line.  All groups hold pairs or none does (paired applies to every group).
+        markdup=True calls duplicates within a library only (a group's library is its LB field; groups without one share "Unknown Library"):
+        self.markdup_library_counts holds the counts per library, markdup_metrics one row per library.  Needs the native pipeline; -R must not be set.
+        Returns the number of reads."""
+        if out is None:
+            raise ValueError("align_groups: out (a text or binary file object) is required")
+        if not groups:
+            raise ValueError("align_groups: no read groups were given")
+        if getattr(self, "rg_line", ""):
+            raise ValueError("align_groups: -R is set: a run over read groups takes its read groups from `groups` alone")
+        parsed = []
+        for k, g in enumerate(groups):
+            if len(g) not in (2, 3) or g[1] is None:
+                raise ValueError(f"align_groups: group {k}: (rg_line, reads, mates or None)")
+            line, rid = parse_rg_line(g[0], f"align_groups: group {k}")
+            if any(rid == q[1] for q in parsed):
+                raise ValueError(f"align_groups: group {k}: the read group ID '{rid}' is given twice")
+            parsed.append((line, rid, g[1], g[2] if len(g) == 3 else None))
+        libs = list(dict.fromkeys(rg_library(q[0]) for q in parsed))
+        if len(libs) > 255:
+            raise ValueError(f"align_groups: {len(libs)} libraries: a run holds at most 255 (the library is a byte of the duplicate key)")
+        if os.environ.get("BMH_ALIGNER_NATIVE", "1") == "0" or self.profile:
+            raise NotImplementedError("align_groups needs the native pipeline (BMH_ALIGNER_NATIVE=0 and profile runs write batch after batch)")
+        self._groups = parsed
+        try:
+            if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None:
+                return self._align_bam(lambda o: self._run_groups(parsed, libs, o, paired, chunk_bases, batch_reads), out, fmt, level,
+                                       sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics)
+            return self._run_groups(parsed, libs, out, paired, chunk_bases, batch_reads)
+        finally:
+            self._groups = None
+
+    def _run_groups(self, parsed, libs, out, paired, chunk_bases, batch_reads) -> int:
+        binary = "b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")
+        stated = bool(paired or any(q[3] is not None for q in parsed))             # (pairs by what the caller says; a BAM says the rest itself: align_files)
+        cb_pairs = 0 if batch_reads > 0 else min(chunk_bases or int(getattr(self, "ref_chunk_bases", 0)) or 10_000_000 * max(1, int(getattr(self, "ref_threads", 1))), (1 << 31) - 1024)
+        cb = cb_pairs
+        if batch_reads <= 0 and not stated and not chunk_bases:
+            cb = min(max(cb, 150_000_000), (1 << 31) - 1024)                       # (single-end records do not depend on the cuts: align_file)
+        for _line, rid, reads, mates in parsed:                                    # (before the header is written: a refused run leaves `out` empty)
+            for path in (reads, mates):
+                if path is not None and not os.path.exists(path):
+                    from .lib import ReadFileError
+                    raise ReadFileError(f"read group '{rid}': reads file: {path}: no such file")
+        out.write(self.header().encode() if binary else self.header())
+        nat = self._native_aligner()
+        nat.set_bam_pairs(cb_pairs, int(os.environ.get("BMH_ALIGNER_LANES", "3")))
+        try:
+            self.last_stats = nat.run_groups([(q[1], libs.index(rg_library(q[0])), q[2], q[3]) for q in parsed], bool(paired),
+                                             (lambda mv: out.write(mv)) if binary else (lambda mv: out.write(bytes(mv).decode())), batch_bases=cb, batch_reads=max(batch_reads, 0),
+                                             n_lanes=int(os.environ.get("BMH_ALIGNER_LANES", "3" if stated else "2")), n_threads=self.n_threads)
         except RuntimeError as e:
             _raise_beyond_cap(e)
             raise

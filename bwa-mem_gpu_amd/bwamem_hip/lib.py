@@ -43,6 +43,8 @@ EXPORTED_SYMBOLS = [
     "bmh_bam_sort_device", "bmh_bam_sort_host", "bmh_bam_sorted_file_device", "bmh_bam_sorted_file_host", "bmh_aligner_set_sort", "bmh_aligner_sort_index",
     "bmh_bam_reads_device", "bmh_bam_reads_host", "bmh_reads_last_bam_counts", "bmh_aligner_set_bam_pairs",
     "bmh_bam_markdup_device", "bmh_bam_markdup_host", "bmh_bam_sorted_file_markdup_device", "bmh_bam_sorted_file_markdup_host", "bmh_aligner_set_markdup", "bmh_aligner_markdup_counts", "bmh_aligner_markdup_times",
+    "bmh_bam_markdup_groups_device", "bmh_bam_markdup_groups_host", "bmh_bam_sorted_file_markdup_groups_device", "bmh_bam_sorted_file_markdup_groups_host",
+    "bmh_aligner_markdup_library_counts", "bmh_aligner_run_groups",
 ]
 
 
@@ -392,15 +394,53 @@ def bam_sort(records: bytes, host: bool = False) -> bytes:
 MARKDUP_COUNTS = ("pairs_examined", "fragments_examined", "duplicate_pairs", "duplicate_fragments", "records_flagged", "secondary_or_supplementary", "unmapped_records", "templates")
 
 
-def bam_markdup(records: bytes, host: bool = False) -> tuple:
+def _library_table(read_groups):
+    """[(id, library_name), ...] -> (the C arrays of the _groups entry points: ids, library indices, their count; the library names in order of first appearance).
+    Groups with one library name are lanes of one library; the indices are not checked here (the library refuses more than 255 and repeated IDs by row)"""
+    names = []
+    for _rid, lb in read_groups:
+        if lb not in names:
+            names.append(lb)
+    ids = (C.c_char_p * max(len(read_groups), 1))(*[(rid if isinstance(rid, bytes) else str(rid).encode()) for rid, _lb in read_groups])
+    lib = (C.c_int32 * max(len(read_groups), 1))(*[names.index(lb) for _rid, lb in read_groups])
+    return ids, lib, len(read_groups), names
+
+
+def _library_counts(names, flat) -> dict:
+    return {nm: dict(zip(MARKDUP_COUNTS, (int(v) for v in flat[8 * k:8 * k + 8]))) for k, nm in enumerate(names)}
+
+
+def bam_markdup(records: bytes, host: bool = False, read_groups=None) -> tuple:
     """bmh_bam_markdup_device (host=True: bmh_bam_markdup_host, no device needed): a stream of BAM records in the writer's order (a template's records next to
     each other, its first primary line first) -> (the same records with flag 0x400 on every record of every duplicate template, the counts by MARKDUP_COUNTS'
     names).  Picard MarkDuplicates' rules.  A cut stream, one whose first record begins no template and a paired template without both of its
-    primary lines raise ValueError."""
+    primary lines raise ValueError.
+    read_groups: [(id, library_name), ...] (bmh_bam_markdup_groups_*) -- duplicates are called within a library only, a template's library being that of the RG:Z
+    tag on its first record; the counts gain "libraries": {library_name: counts}, in order of first appearance.  A template without the tag or with an ID that is
+    not listed, more than 255 libraries and a repeated ID raise ValueError.  Without read_groups no tag is read."""
     L = load_library()
     records = bytes(records)
     L.bmh_free.argtypes = [C.c_void_p]
     out, counts = C.c_void_p(), (C.c_uint64 * 8)()
+    if read_groups is not None:
+        ids, lib, ng, names = _library_table(read_groups)
+        lc = (C.c_uint64 * (8 * max(len(names), 1)))()
+        grp = [C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int]
+        if host:
+            L.bmh_bam_markdup_groups_host.argtypes = [C.c_char_p, C.c_uint64] + grp + [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+            rc = L.bmh_bam_markdup_groups_host(records, len(records), ids, lib, ng, C.byref(out), counts, lc)
+        else:
+            import torch
+            L.bmh_bam_markdup_groups_device.argtypes = [C.c_char_p, C.c_uint64] + grp + [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+            rc = L.bmh_bam_markdup_groups_device(records, len(records), ids, lib, ng, torch.cuda.current_stream().cuda_stream, C.byref(out), counts, lc)
+        if rc != 0:
+            raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_markdup: " + _err(L))
+        try:
+            c = dict(zip(MARKDUP_COUNTS, (int(v) for v in counts)))
+            c["libraries"] = _library_counts(names, lc)
+            return (C.string_at(out.value, len(records)) if records else b""), c
+        finally:
+            L.bmh_free(out)
     if host:
         L.bmh_bam_markdup_host.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         rc = L.bmh_bam_markdup_host(records, len(records), C.byref(out), counts)
@@ -416,10 +456,13 @@ def bam_markdup(records: bytes, host: bool = False) -> tuple:
         L.bmh_free(out)
 
 
-def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False, markdup: bool = False) -> tuple:
+def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False, markdup: bool = False, read_groups=None) -> tuple:
     """bmh_bam_sorted_file_device (host=True: _host): (the complete sorted BAM file -- header members, the records in coordinate order in windows of `window`
     records (0: about 64 MiB), the end-of-file member --, its .bai index).  contigs: (name, length) pairs; both forms give the same bytes.
-    markdup=True (bmh_bam_sorted_file_markdup_*): `records` come in the writer's order, the duplicates among them are marked (bam_markdup's rules) and the counts come third."""
+    markdup=True (bmh_bam_sorted_file_markdup_*): `records` come in the writer's order, the duplicates among them are marked (bam_markdup's rules) and the counts come third.
+    read_groups (needs markdup=True): as bam_markdup takes them -- duplicates per library, and the counts gain "libraries"."""
+    if read_groups is not None and not markdup:
+        raise ValueError("bam_sorted_file: read_groups needs markdup=True (they decide which templates may be duplicates of each other)")
     L = load_library()
     records = bytes(records)
     L.bmh_free.argtypes = [C.c_void_p]
@@ -436,20 +479,30 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
     counts = (C.c_uint64 * 8)()
     if markdup:
         tail.append(counts); out.append(C.POINTER(C.c_uint64))
+    grp = ""
+    if read_groups is not None:
+        ids, lib, ng, lib_names = _library_table(read_groups)
+        lc = (C.c_uint64 * (8 * max(len(lib_names), 1)))()
+        head += [ids, lib, ng]; sig += [C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int]
+        tail.append(lc); out.append(C.POINTER(C.c_uint64))
+        grp = "_groups"
     if host:
-        fn = L.bmh_bam_sorted_file_markdup_host if markdup else L.bmh_bam_sorted_file_host
+        fn = getattr(L, "bmh_bam_sorted_file_markdup" + grp + "_host") if markdup else L.bmh_bam_sorted_file_host
         fn.argtypes = sig + out
         rc = fn(*head, *tail)
     else:
         import torch
-        fn = L.bmh_bam_sorted_file_markdup_device if markdup else L.bmh_bam_sorted_file_device
+        fn = getattr(L, "bmh_bam_sorted_file_markdup" + grp + "_device") if markdup else L.bmh_bam_sorted_file_device
         fn.argtypes = sig + [C.c_void_p] + out
         rc = fn(*head, torch.cuda.current_stream().cuda_stream, *tail)
     if rc != 0:
         raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_sorted_file: " + _err(L))
     try:
         if markdup:
-            return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value), dict(zip(MARKDUP_COUNTS, (int(v) for v in counts)))
+            c = dict(zip(MARKDUP_COUNTS, (int(v) for v in counts)))
+            if read_groups is not None:
+                c["libraries"] = _library_counts(lib_names, lc)
+            return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value), c
         return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)
     finally:
         L.bmh_free(bam); L.bmh_free(bai)
@@ -517,6 +570,11 @@ def load_reads_files(path1: str, path2: str | None = None, comments: bool = Fals
         e.partial = d
         raise e
     return d
+
+
+class ReadGroupT(C.Structure):
+    """bmh_read_group_t"""
+    _fields_ = [("id", C.c_char_p), ("library", C.c_int32), ("path1", C.c_char_p), ("path2", C.c_char_p)]
 
 
 class AlignStats(C.Structure):
@@ -596,6 +654,15 @@ class NativeAligner:
         c = (C.c_uint64 * 8)()
         if L.bmh_aligner_markdup_counts(self.handle, c) != 0:
             raise ValueError("bmh_aligner_markdup_counts: " + _err(L))
+        return dict(zip(MARKDUP_COUNTS, (int(v) for v in c)))
+
+    def markdup_library_counts(self, lib: int) -> dict:
+        """bmh_aligner_markdup_library_counts: library `lib`'s counts of the last marked run over read groups"""
+        L = load_library()
+        L.bmh_aligner_markdup_library_counts.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
+        c = (C.c_uint64 * 8)()
+        if L.bmh_aligner_markdup_library_counts(self.handle, int(lib), c) != 0:
+            raise ValueError("bmh_aligner_markdup_library_counts: " + _err(L))
         return dict(zip(MARKDUP_COUNTS, (int(v) for v in c)))
 
     def markdup_times(self) -> dict:
@@ -692,6 +759,19 @@ class NativeAligner:
         """bmh_aligner_run_files: run_file for one or two read files of any shape (multi-line records, gzip / BGZF, pipes; path2: the mates)"""
         return self._run("bmh_aligner_run_files", (os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, int(batch_bases), int(batch_reads),
                                                    1 if paired else 0, int(n_lanes), int(n_threads)), write, read_errors=("FASTQ:", "reads file"))
+
+    def run_groups(self, groups, paired: bool, write, batch_bases: int = 0, batch_reads: int = 0, n_lanes: int = 2, n_threads: int = 0) -> "AlignStats":
+        """bmh_aligner_run_groups: run_files over several read groups in one run -- groups: [(id, library index, path1, path2 or None)]; every batch's records
+        carry their group's ID.  What the library refuses of the groups or their files raises ReadFileError (a ValueError) naming the group"""
+        L = load_library()
+        g = (ReadGroupT * max(len(groups), 1))()
+        for k, (rid, lib, p1, p2) in enumerate(groups):
+            g[k].id = rid if isinstance(rid, bytes) else str(rid).encode(); g[k].library = int(lib)
+            g[k].path1 = os.fsencode(p1); g[k].path2 = os.fsencode(p2) if p2 is not None else None
+        L.bmh_aligner_run_groups.restype = C.c_int
+        L.bmh_aligner_run_groups.argtypes = [C.c_void_p, C.POINTER(ReadGroupT), C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, SAM_SINK, C.c_void_p, C.POINTER(AlignStats)]
+        return self._run("bmh_aligner_run_groups", (g, len(groups), int(batch_bases), int(batch_reads), 1 if paired else 0, int(n_lanes), int(n_threads)), write,
+                         read_errors=("FASTQ:", "reads file", "read group", "bmh_aligner_run_groups:"))
 
     def free(self):
         if self.handle:

@@ -2,6 +2,7 @@
 grouped by read name, which says itself whether it holds pairs) -> SAM.
 
     python -m bwamem_hip.mem [options] PREFIX reads [mates] [-o out.sam]
+    python -m bwamem_hip.mem [options] PREFIX --rg LINE reads [mates] --rg LINE reads [mates] ... [-o out.sam]
 
 PREFIX is what `python -m bwamem_hip.index` (or `bwa index`) wrote.  Options are Aligner.set_options' list (-k -w -c -D -G -N -W -X -A -B
 -O -E -T -h -Q -U -m -R -a -M -Y -S -P -j -C -g -t -K ...) plus -p (the one file holds interleaved pairs), -o (the output file; default
@@ -12,8 +13,11 @@ names it otherwise, and on stdout without --index none is written), --sort-mem B
 file; 4 GiB), --sort-tmp DIR (where that file lives; $TMPDIR, else /tmp), --markdup (needs --sort: flag 0x400 on every record of every duplicate template,
 decided on the device by Picard MarkDuplicates' rules -- the unclipped 5' ends and strands of a template's primary lines are the key, the sum of the base
 qualities >= 15 the score, ties go to the template that came first in the input, a fragment is a duplicate wherever a pair has an end; unlike Picard and
-`samtools markdup` on coordinate-sorted input the secondary and supplementary lines of a duplicate template are flagged too; no optical duplicates, one library
-per run, no library-size estimate, nothing is removed) and --markdup-metrics PATH (a Picard-style table of the counts).  An option that is not on that list is
+`samtools markdup` on coordinate-sorted input the secondary and supplementary lines of a duplicate template are flagged too; no optical duplicates, no
+library-size estimate, nothing is removed) and --markdup-metrics PATH (a Picard-style table of the counts, one row per library).  --rg LINE opens a read group:
+LINE is an @RG line as -R takes it, and the one or two files that follow it, up to the next --rg, are that group's input (Aligner.align_groups): a sample's lanes
+and libraries go into one output, every record with its group's RG:Z, the header with every @RG line, and --markdup calls duplicates within a library (the LB
+field; groups with one LB are lanes of one library) only.  -p applies to every group; --rg and -R exclude each other.  An option that is not on that list is
 refused by name.  Two input files imply pairs.  One plain, regular file is offered to Aligner.align_file first, which takes it when every
 record has one sequence line (its own counting pass decides, before anything is written); every other input goes through
 Aligner.align_files; the text is the same.  A refused file ends the command with status 1 and the library's message on stderr.
@@ -45,6 +49,7 @@ def main(argv=None) -> int:
     bam, bam_level = False, 1
     sort, index_path, sort_mem, sort_tmp = False, None, None, None
     markdup, metrics_path = False, None
+    groups = []                                                     # --rg LINE: [line, files...]; the positionals behind it are its files
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -64,6 +69,12 @@ def main(argv=None) -> int:
             sort = bam = True
         elif a == "--markdup":
             markdup = True
+        elif a == "--rg":
+            if i + 1 >= len(argv):
+                print("[bwamem_hip.mem] option --rg needs a value", file=sys.stderr)
+                return 2
+            groups.append([argv[i + 1]])
+            i += 1
         elif a in ("-o", "--device", "--index", "--sort-mem", "--sort-tmp", "--markdup-metrics"):
             if i + 1 >= len(argv):
                 print(f"[bwamem_hip.mem] option {a} needs a value", file=sys.stderr)
@@ -95,13 +106,29 @@ def main(argv=None) -> int:
                 return 2
             opts += [a, argv[i + 1]]
             i += 1
+        elif groups:
+            groups[-1].append(a)
         else:
             pos.append(a)
         i += 1
-    if len(pos) not in (2, 3):
+    if groups:
+        if "-R" in opts:
+            print("[bwamem_hip.mem] --rg and -R exclude each other: with --rg every group brings its own @RG line", file=sys.stderr)
+            return 2
+        if len(pos) > 1:
+            print(f"[bwamem_hip.mem] read files before the first --rg ({pos[1]}): with --rg every read file follows its group's --rg", file=sys.stderr)
+            return 2
+        for g in groups:
+            if len(g) not in (2, 3):
+                print(f"[bwamem_hip.mem] --rg {g[0]!r} is followed by {len(g) - 1} files: a group is one file of reads, or reads and mates", file=sys.stderr)
+                return 2
+        if len(pos) != 1:
+            print(__doc__, file=sys.stderr)
+            return 2
+    elif len(pos) not in (2, 3):
         print(__doc__, file=sys.stderr)
         return 2
-    prefix, reads, mates = pos[0], pos[1], pos[2] if len(pos) == 3 else None
+    prefix, reads, mates = pos[0], pos[1] if len(pos) > 1 else None, pos[2] if len(pos) == 3 else None
     if not sort and (index_path is not None or sort_mem is not None or sort_tmp is not None):
         print("[bwamem_hip.mem] --index, --sort-mem and --sort-tmp need --sort", file=sys.stderr)
         return 2
@@ -129,7 +156,10 @@ def main(argv=None) -> int:
         if markdup:
             fmt_kw.update(markdup=True, markdup_metrics=metrics_path)
         done = False
-        if mates is None and _plain_regular(reads):
+        if groups:
+            al.align_groups([(g[0], g[1], g[2] if len(g) == 3 else None) for g in groups], out=out, paired=interleaved, **fmt_kw)
+            done = True
+        elif mates is None and _plain_regular(reads):
             from .lib import ReadFileError
             try:
                 al.align_file(reads, out, paired=paired, **fmt_kw)

@@ -18,6 +18,8 @@
 #include <condition_variable>
 #include <functional>
 #include <sys/mman.h>
+#include <sys/stat.h>
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,6 +53,10 @@ struct aligner_t {
 	bool markdup = false;                      // sorted BAM output: flag 0x400 on the records of duplicate templates (bmh_aligner_set_markdup)
 	int out_fmt = BMH_OUT_SAM, out_level = 1;  // what the sink receives (bmh_aligner_set_output): the records' text, or BGZF members of BAM records
 	std::vector<char> ctg_blob; std::vector<uint32_t> ctg_noff;      // the contig table as the BAM converter takes it
+	// a run over read groups (bmh_aligner_run_groups), while it lasts: every group's ID (a batch's records carry its group's) and the table duplicate marking reads;
+	// the serial changes whenever the table does, so a lane knows whether its copy on the device is the run's
+	std::vector<std::string> group_ids; bdp_table_t groups; uint64_t groups_serial = 0;
+	const char *rg_of(int group) const { return group >= 0 && (size_t)group < group_ids.size() ? group_ids[(size_t)group].c_str() : po.rg_id; }
 };
 
 }   // namespace
@@ -91,11 +97,12 @@ template <class T> using hbuf_t = pin_buf<T>;
 // of records and 190 MB of CIGAR / MD arrays: every extra pass over them on one thread costs what a device stage costs).
 struct result_t {
 	uint32_t b0 = 0, n = 0; uint64_t m = 0, n_sel = 0;
+	int group = -1;                                                     // the read group of the batch (a run over groups), -1: the aligner's -R or none
 	const bmh_read_set_t *rs = nullptr; int64_t id0 = 0; void *token = nullptr;      // the read set the batch [b0, b0 + n) lies in, the index of its first read in the run, the source's handle
 	hbuf_t<int32_t> fin, aln, slot32; hbuf_t<uint32_t> opr, off, packed;
 	hbuf_t<char> text; uint64_t text_len = 0; bool has_text = false;     // the text written on the device (no formatting on the host)
 	hbuf_t<uint64_t> skeys, soff; uint32_t n_rec = 0;                   // sorted BAM: text holds the batch's records in order; their keys and offsets [n_rec + 1]
-	hbuf_t<uint32_t> stpl; hbuf_t<bdp_entry_t> dup_e; uint32_t dup_info[4] = {0, 0, 0, 0}; uint64_t dup_d2h = 0;      // duplicate marking: the records' template ordinals in that order, the templates' entries, bdp_batch_device's info
+	hbuf_t<uint32_t> stpl; hbuf_t<bdp_entry_t> dup_e; uint32_t dup_info[BDP_INFO_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0}; uint64_t dup_d2h = 0;      // duplicate marking: the records' template ordinals in that order, the templates' entries, bdp_batch_device's info
 	std::vector<int64_t> slot;                   // (host selection only; empty: slot32)
 	std::vector<int32_t> h_rec, unflag;          // pairs
 	std::vector<uint32_t> dev_index;             // record -> its place in the lane's d_fin when that is not the record's own index (ALT indexes); empty: identity
@@ -124,6 +131,7 @@ struct lane_t {
 	bmh_bam_ws_t *bam = nullptr;                 // BAM output: the converter's and the compressor's buffers
 	bsr_dev_t *bsr = nullptr;                    // sorted BAM output: the sort's, the gather's and the index pass's buffers
 	bdp_dev_t *bdp = nullptr;                    // duplicate marking: the batch's heads, ordinals and entries
+	uint64_t groups_serial = 0;                  // ... the read groups it holds are those of the run with this serial (aligner_t)
 	~lane_t()
 	{
 		if (bam) bmh_bam_ws_free(bam);
@@ -251,6 +259,7 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 			const uint32_t tmax = paired ? n / 2 : n;                   // the batch's templates: every read or pair leaves at least one record, so no more entries than this come down
 			if (A.markdup) {
 				if (!Ln.bdp && !(Ln.bdp = bdp_dev_create())) return BMH_ENOMEM;
+				if (Ln.groups_serial != A.groups_serial) { RCK(bdp_dev_set_groups(Ln.bdp, &A.groups, Ln.st)); Ln.groups_serial = A.groups_serial; }
 				RCK(bdp_batch_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &d_tpl, &d_e, &d_info));
 				RCK(R.stpl.need((size_t)nrec + 1)); RCK(R.dup_e.need((size_t)std::min(nrec, tmax) + 1));
 			}
@@ -265,15 +274,16 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 				const size_t ne = std::min(nrec, tmax);
 				if (nrec) HIPCK(hipMemcpyAsync(R.stpl.p, d_stpl, 4 * (size_t)nrec, hipMemcpyDeviceToHost, Ln.st));
 				if (ne) HIPCK(hipMemcpyAsync(R.dup_e.p, d_e, sizeof(bdp_entry_t) * ne, hipMemcpyDeviceToHost, Ln.st));
-				HIPCK(hipMemcpyAsync(R.dup_info, d_info, 16, hipMemcpyDeviceToHost, Ln.st));
-				R.dup_d2h = 4ull * nrec + sizeof(bdp_entry_t) * ne + 16;
+				const size_t ni = A.groups.empty() ? 16 : 4 * BDP_INFO_WORDS;      // (with read groups: the words of a template without a known group)
+				HIPCK(hipMemcpyAsync(R.dup_info, d_info, ni, hipMemcpyDeviceToHost, Ln.st));
+				R.dup_d2h = 4ull * nrec + sizeof(bdp_entry_t) * ne + ni;
 				Ln.copy_bytes[1] += R.dup_d2h;
 			}
 			HIPCK(hipEventRecord(Ln.ev_c[3], Ln.st));
 			Ln.copy_bytes[1] += bo.bam_bytes + 16ull * nrec; Ln.d2h_marked = true;
 			HIPCK(hipStreamSynchronize(Ln.st));
 			if (A.markdup && nrec) {
-				if (R.dup_info[1] != 0xffffffffu) return bdp_batch_refused(nrec, R.dup_info[1] ? R.dup_info[1] : nrec + 1, "sorted BAM");
+				RCK(bdp_batch_check(nrec, R.dup_info, !A.groups.empty(), "sorted BAM"));
 				if (R.dup_info[0] == 0 || R.dup_info[0] > std::min(nrec, tmax)) { bmh_set_error("sorted BAM: internal error: %u templates among %u records", R.dup_info[0], nrec); return BMH_EINVAL; }
 			}
 			if (R.soff.p[nrec] != bo.bam_bytes) {                 // (the gather skips a record whose offsets lie outside the buffers: the scan of the sizes shows it)
@@ -518,10 +528,10 @@ struct gate_hold_t {
 	~gate_hold_t() { release(); }
 };
 
-int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t b0, uint32_t b1, int64_t id0, bool src_pinned, bool paired, int n_threads, gate_t &gpu_gate, result_t &R)
+int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t b0, uint32_t b1, int64_t id0, int group, bool src_pinned, bool paired, int n_threads, gate_t &gpu_gate, result_t &R)
 {
 	const uint32_t n = b1 - b0;
-	R.b0 = b0; R.n = n; R.rs = &rs; R.id0 = id0;
+	R.b0 = b0; R.n = n; R.rs = &rs; R.id0 = id0; R.group = group;
 	R.dev_index.clear();
 	const uint64_t a0 = rs.offs[b0], a1 = rs.offs[b1 - 1] + rs.lens[b1 - 1], nb = a1 - a0;
 	if (nb >> 31) { bmh_set_error("bmh_aligner_run: a batch holds 2^31 bases or more (offsets inside a batch are 32-bit)"); return BMH_EINVAL; }
@@ -634,7 +644,7 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 	else if (gate.held) HIPCK(hipStreamSynchronize(Ln.st));
 	gate.release();
 	double t3 = now_s(); Ln.t[2] += t3 - t2;
-	bmh_post_opt_t po = A.po; po.id0 = id0;
+	bmh_post_opt_t po = A.po; po.id0 = id0; po.rg_id = A.rg_of(group);
 	const uint8_t *codes = rs.codes + a0;
 	std::vector<uint64_t> offs64;                                   // offsets relative to the batch, for the host forms
 	auto host_offs = [&]() { if (offs64.empty()) { offs64.resize(n); for (uint32_t r = 0; r < n; ++r) offs64[r] = rs.offs[b0 + r] - a0; } return offs64.data(); };
@@ -788,7 +798,7 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 struct fbatch_t {
 	hbuf_t<uint8_t> ascii, codes, names; hbuf_t<uint64_t> offs, name_offs; hbuf_t<uint32_t> lens;
 	hbuf_t<uint8_t> quals, comments; hbuf_t<uint64_t> comment_offs;        // a FASTQ file's qualities; -C: the comments
-	bmh_read_set_t rs; uint32_t index = 0; int64_t id0 = 0;
+	bmh_read_set_t rs; uint32_t index = 0; int64_t id0 = 0; int group = -1;        // (id0: the first read's index in its file or group; group: of a run over read groups)
 	// room for a batch of nr reads, nb bases, nn bytes of names (fq: with qualities; cm: with ncm bytes of comments), and o's pointers into it.  The nt4 codes always:
 	// every host form reads them (pairs' walks, ALT reads, a batch the device tail refuses, the host formatter)
 	int size(const char *fn, uint64_t nr, uint64_t nb, uint64_t nn, uint64_t ncm, bool fq, bool cm, bmh_read_set_t *o)
@@ -838,6 +848,7 @@ struct bmh_aligner {
 	uint64_t bam_pairs_bases = 0; int bam_pairs_lanes = 0;   // bmh_aligner_set_bam_pairs
 	bsr_store_t store; bsr_index_t sort_ix; uint32_t sort_window = 0;      // sorted BAM output: the runs of the run in progress, the index of the last one, the window
 	uint64_t dup_counts[BDP_N_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0}; bool dup_valid = false;      // duplicate marking: the counts of the last marked run
+	std::vector<uint64_t> lib_counts;                    // ... with read groups: the same eight per library (bmh_aligner_markdup_library_counts)
 	double dup_times[3] = {0, 0, 0};                     // ... its decision and its windows' flag steps in ms, the bytes its batches' ordinals and entries took on their way down
 };
 
@@ -915,6 +926,16 @@ int bmh_aligner_markdup_counts(bmh_aligner_t *h, uint64_t out[8])
 	return BMH_OK;
 }
 
+int bmh_aligner_markdup_library_counts(bmh_aligner_t *h, int lib, uint64_t out[8])
+{
+	const char *fn = "bmh_aligner_markdup_library_counts";
+	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (!h->dup_valid) { bmh_set_error("%s: no run has marked duplicates (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
+	if (lib < 0 || (size_t)lib >= h->lib_counts.size() / BDP_N_COUNTS) { bmh_set_error("%s: library %d: the last marked run had %zu (a run without read groups has none)", fn, lib, h->lib_counts.size() / BDP_N_COUNTS); return BMH_EINVAL; }
+	for (int k = 0; k < BDP_N_COUNTS; ++k) out[k] = h->lib_counts[(size_t)BDP_N_COUNTS * (size_t)lib + k];
+	return BMH_OK;
+}
+
 int bmh_aligner_markdup_times(bmh_aligner_t *h, double out[3])
 {
 	if (!h || !out) { bmh_set_error("bmh_aligner_markdup_times: null argument"); return BMH_EINVAL; }
@@ -953,7 +974,7 @@ void bmh_aligner_free(bmh_aligner_t *h)
 }
 
 // where the batches of a run come from: a read set in host memory cut at given places, or a read file cut and filled by a loader thread
-struct batch_t { uint32_t index = 0; const bmh_read_set_t *rs = nullptr; uint32_t b0 = 0, b1 = 0; int64_t id0 = 0; bool pinned = false; void *token = nullptr; };
+struct batch_t { uint32_t index = 0; const bmh_read_set_t *rs = nullptr; uint32_t b0 = 0, b1 = 0; int64_t id0 = 0; bool pinned = false; void *token = nullptr; int group = -1; };
 struct batch_src_t {
 	std::function<int(batch_t &)> next;               // 1: a batch (in index order over the callers), 0: no more, < 0: an error (message set); thread-safe, may block
 	std::function<void(void *)> release;              // the text of the batch with this token has been written
@@ -966,6 +987,7 @@ struct batch_src_t {
 struct out_stage_t {
 	bmh_aligner *h; const int fmt; bmh_sam_sink_t sink; void *user; int n_threads; const char *fn;
 	uint64_t n_bytes = 0;                                           // handed to the sink so far
+	int lib_of(int group) const { return group >= 0 && (size_t)group < h->a.groups.lib.size() ? (int)h->a.groups.lib[(size_t)group] : -1; }
 	int emit(const void *p, size_t n) { if (n && sink(user, (const char *)p, n) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; } n_bytes += n; return BMH_OK; }
 	// (the index is valid again once the merge has written the whole file)
 	int begin() { if (fmt == BMH_OUT_BAM_SORTED) { h->dup_valid = false; h->dup_times[0] = h->dup_times[1] = h->dup_times[2] = 0; h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), fn)); h->sort_ix.valid = false; } return BMH_OK; }
@@ -973,11 +995,11 @@ struct out_stage_t {
 	{
 		if (fmt != BMH_OUT_BAM_SORTED) return emit(R.text.p, (size_t)R.text_len);
 		if (!R.n_rec) return BMH_OK;
-		const bsr_dup_t bd = {R.stpl.p, R.dup_e.p, R.dup_info[0], R.dup_info[2], R.dup_info[3]};
+		const bsr_dup_t bd = {R.stpl.p, R.dup_e.p, R.dup_info[0], R.dup_info[2], R.dup_info[3], lib_of(R.group)};
 		if (h->a.markdup) h->dup_times[2] += (double)R.dup_d2h;
 		return h->store.append((const uint8_t *)R.text.p, R.text_len, R.skeys.p, R.soff.p, R.n_rec, h->a.markdup ? &bd : nullptr);      // a sorted run: kept until the end of the input
 	}
-	int host_batch(const std::vector<std::string> &parts)
+	int host_batch(const std::vector<std::string> &parts, int group)
 	{
 		if (fmt == BMH_OUT_SAM) { for (const std::string &part : parts) RCK(emit(part.data(), part.size())); return BMH_OK; }
 		// BAM: the text through the two host cores, the same records and members (sorted: the same run) as the device's
@@ -1003,10 +1025,11 @@ struct out_stage_t {
 				for (uint32_t i : ord) { srt.insert(srt.end(), bam + off[i], bam + off[i + 1]); soff.push_back(srt.size()); }
 				std::vector<uint32_t> tpl, stpl; std::vector<bdp_entry_t> E; uint64_t info[2] = {0, 0};
 				if (A.markdup) {                                   // the host forms of the device's heads, ordinals and entries
-					rc = bdp_entries_host(bam, off.data(), (uint32_t)ord.size(), tpl, E, info, fn);
+					const bdp_groups_t G = A.groups.view();
+					rc = bdp_entries_host(bam, off.data(), (uint32_t)ord.size(), tpl, E, info, fn, A.groups.empty() ? nullptr : &G);
 					for (uint32_t i : ord) stpl.push_back(tpl[i]);
 				}
-				const bsr_dup_t bd = {stpl.data(), E.data(), (uint32_t)E.size(), info[0], info[1]};
+				const bsr_dup_t bd = {stpl.data(), E.data(), (uint32_t)E.size(), info[0], info[1], lib_of(group)};
 				if (rc == BMH_OK && !ord.empty()) rc = h->store.append(srt.data(), bb, keys.data(), soff.data(), ord.size(), A.markdup ? &bd : nullptr);
 			}
 		} else if (rc == BMH_OK) {
@@ -1026,7 +1049,11 @@ struct out_stage_t {
 		if (!L0.bam && !(L0.bam = bmh_bam_ws_create())) rc = BMH_ENOMEM;
 		if (rc == BMH_OK && !L0.bsr && !(L0.bsr = bsr_dev_create())) rc = BMH_ENOMEM;
 		const double tm0 = now_s();
-		if (rc == BMH_OK) rc = bsr_merge_device(L0.bsr, L0.bam, h->store, h->sort_window, h->a.out_level, L0.st, h->sort_ix, forward, this, h->a.markdup ? h->dup_counts : nullptr, h->dup_times);
+		const uint32_t n_lib = h->a.markdup ? h->a.groups.n_lib : 0;
+		h->lib_counts.assign((size_t)BDP_N_COUNTS * n_lib, 0);
+		if (rc == BMH_OK) rc = bsr_merge_device(L0.bsr, L0.bam, h->store, h->sort_window, h->a.out_level, L0.st, h->sort_ix, forward, this, h->a.markdup ? h->dup_counts : nullptr, h->dup_times,
+		                                        n_lib, n_lib ? h->lib_counts.data() : nullptr);
+		for (size_t k = 0; rc == BMH_OK && k < h->store.lib_info.size() && k / 3 < n_lib; ++k) h->lib_counts[BDP_N_COUNTS * (k / 3) + BDP_SECSUP + k % 3] = h->store.lib_info[k];
 		if (trace && h->a.markdup) fprintf(stderr, "[aligner] duplicate marking: %.0f bytes of ordinals and entries came down with the batches\n", h->dup_times[2]);
 		if (trace) fprintf(stderr, "[aligner] sorted output: %zu runs (%llu spilled) merged in %.1f ms\n", h->store.runs.size(), (unsigned long long)h->store.spilled, (now_s() - tm0) * 1e3);
 		h->store.clear();
@@ -1039,7 +1066,7 @@ struct out_stage_t {
 static bool format_on_host(const aligner_t &A, const result_t &R, bool paired, std::vector<std::string> &parts)
 {
 	const bmh_read_set_t *rs = R.rs;
-	bmh_post_opt_t po = A.po; po.id0 = R.id0;
+	bmh_post_opt_t po = A.po; po.id0 = R.id0; po.rg_id = A.rg_of(R.group);
 	const uint64_t a0 = rs->offs[R.b0];
 	std::vector<uint64_t> offs64(R.n), noff(R.n);
 	const uint64_t n0 = rs->name_offs[R.b0];
@@ -1121,8 +1148,8 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 			R->token = bt.token;
 			int rc = BMH_OK;
 			const double tb0 = now_s();
-			if (bt.b1 > bt.b0) rc = run_batch(A, Ln, *bt.rs, bt.b0, bt.b1, bt.id0, bt.pinned, paired != 0, n_threads, gpu_gate, *R);
-			else { R->b0 = bt.b0; R->n = 0; R->rs = bt.rs; R->id0 = bt.id0; R->has_text = false; }
+			if (bt.b1 > bt.b0) rc = run_batch(A, Ln, *bt.rs, bt.b0, bt.b1, bt.id0, bt.group, bt.pinned, paired != 0, n_threads, gpu_gate, *R);
+			else { R->b0 = bt.b0; R->n = 0; R->rs = bt.rs; R->id0 = bt.id0; R->group = bt.group; R->has_text = false; }
 			if (trace) fprintf(stderr, "[aligner] lane %d batch %u: %.1f .. %.1f ms\n", lane_index, b, (tb0 - t_start) * 1e3, (now_s() - t_start) * 1e3);
 			if (rc != BMH_OK) { if (src.release) src.release(bt.token); fail(rc, bmh_last_error()); break; }
 			std::lock_guard<std::mutex> lk(mu);
@@ -1154,7 +1181,7 @@ static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int pair
 					t_format += now_s() - t0;
 				}
 				const double ts0 = now_s();
-				const int rc = R->has_text ? out.device_batch(*R) : out.host_batch(parts);
+				const int rc = R->has_text ? out.device_batch(*R) : out.host_batch(parts, R->group);
 				if (rc != BMH_OK) { fail(rc, bmh_last_error()); return; }
 				if (trace && R->has_text) fprintf(stderr, "[aligner] writer batch %u: text of the device, sink %.1f .. %.1f ms\n", b, (ts0 - t_start) * 1e3, (now_s() - t_start) * 1e3);
 				else if (trace) fprintf(stderr, "[aligner] writer batch %u: format %.1f .. %.1f ms, sink .. %.1f\n", b, (t0 - t_start) * 1e3, (ts0 - t_start) * 1e3, (now_s() - t_start) * 1e3);
@@ -1285,7 +1312,7 @@ static int run_loaded(bmh_aligner_t *h, const char *fn, int dev, const std::func
 		fbatch_t *fb = nullptr; std::string err;
 		const int got = q.next(&fb, err);
 		if (got < 0) bmh_set_error("%s", err.c_str());
-		if (got == 1) { bt.index = fb->index; bt.rs = &fb->rs; bt.b0 = 0; bt.b1 = (uint32_t)fb->rs.n_reads; bt.id0 = fb->id0; bt.pinned = true; bt.token = fb; }
+		if (got == 1) { bt.index = fb->index; bt.rs = &fb->rs; bt.b0 = 0; bt.b1 = (uint32_t)fb->rs.n_reads; bt.id0 = fb->id0; bt.pinned = true; bt.token = fb; bt.group = fb->group; }
 		return got;
 	};
 	src.release = [&](void *tok) { q.release((fbatch_t *)tok); };
@@ -1368,6 +1395,94 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 	uint64_t icnt[2]; bmh_pump_inflate_counts(P, icnt); bmh_reads_note_inflate_counts(icnt);
 	uint64_t bcnt[2]; bmh_pump_bam_counts(P, bcnt); bmh_reads_note_bam_counts(bcnt);
 	bmh_pump_close(P);
+	return rc;
+}
+
+// several read groups in one run: the loader opens group g + 1's pump when group g's is at its end and goes on filling the same queue -- the lanes see one
+// stream of batches, each with its group (the records' RG:Z, the batch's library), its reads indexed from 0 within the group
+int bmh_aligner_run_groups(bmh_aligner_t *h, const bmh_read_group_t *groups, int n_groups, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes, int n_threads,
+                           bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats)
+{
+	const char *fn = "bmh_aligner_run_groups";
+	if (!h || !sink) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (stats) memset(stats, 0, sizeof(*stats));
+	if (n_groups < 1 || !groups) { bmh_set_error("%s: no read groups were given", fn); return BMH_EINVAL; }
+	if (h->a.po.rg_id && h->a.po.rg_id[0]) { bmh_set_error("%s: the aligner has a read group of its own ('%s', -R): a run over read groups takes them from its groups alone", fn, h->a.po.rg_id); return BMH_EINVAL; }
+	std::vector<const char *> ids; std::vector<int32_t> libs;
+	int stated = paired ? 1 : 0;                                       // pairs by what the caller says: `paired`, or a group with two files
+	for (int g = 0; g < n_groups; ++g) {
+		if (!groups[g].id || !groups[g].path1) { bmh_set_error("%s: read group %d lacks its ID or its reads file", fn, g); return BMH_EINVAL; }
+		if (strlen(groups[g].id) > 255) { bmh_set_error("%s: read group %d: its ID is longer than 255 characters", fn, g); return BMH_EINVAL; }
+		ids.push_back(groups[g].id); libs.push_back(groups[g].library);
+		if (groups[g].path2) stated = 1;
+	}
+	bdp_table_t T;
+	RCK(bdp_table_make(T, ids.data(), libs.data(), n_groups, fn));
+	if (h->a.markdup && h->a.n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d reference sequences: with read groups duplicate marking takes at most 2^24 (the library is the top byte of its key)", fn, h->a.n_contigs); return BMH_EINVAL; }
+	for (int g = 0; g < n_groups; ++g)
+		for (const char *path : {groups[g].path1, groups[g].path2}) {
+			struct stat sb;
+			if (path && stat(path, &sb) != 0) { bmh_set_error("read group '%s': reads file: %s: %s", groups[g].id, path, strerror(errno)); return BMH_EINVAL; }
+		}
+	RCK(file_run_args(fn, h, groups[0].path1, sink, stats, batch_bases, batch_reads, stated, n_lanes, n_threads));
+	int dev = 0;
+	if (hipGetDevice(&dev) != hipSuccess) { bmh_set_error("%s: no HIP device", fn); return BMH_ENODEV; }
+	const bool cm = h->a.po.copy_comment != 0;
+	// the state of the loader: the group being read, its pump, the index of its next read; what the pumps counted
+	struct loader_t { bmh_reads_pump_t *P = nullptr; int g = 0; int64_t id0 = 0; uint64_t cnt[4] = {0, 0, 0, 0}, icnt[2] = {0, 0}, bcnt[2] = {0, 0}; } ld;
+	auto named = [&](int g) { const std::string m = bmh_last_error(); bmh_set_error("read group '%s': %s", groups[g].id, m.c_str()); return (int)BMH_EINVAL; };
+	auto close_pump = [&]() {
+		if (!ld.P) return;
+		uint64_t c[4], ic[2], bc[2];
+		bmh_pump_counts(ld.P, c); bmh_pump_inflate_counts(ld.P, ic); bmh_pump_bam_counts(ld.P, bc);
+		for (int k = 0; k < 4; ++k) ld.cnt[k] += c[k];
+		for (int k = 0; k < 2; ++k) { ld.icnt[k] += ic[k]; ld.bcnt[k] += bc[k]; }
+		bmh_pump_close(ld.P); ld.P = nullptr;
+	};
+	// group g's pump; *pairs: does the group hold pairs (two files, a BAM with flag 0x1, else what `paired` says)
+	auto open_pump = [&](int g, int *pairs) -> int {
+		ld.P = bmh_pump_open(groups[g].path1, groups[g].path2, n_threads, cm, false, 0);
+		if (!ld.P) return named(g);
+		const int bam_pairs = bmh_pump_bam_paired(ld.P);
+		if (bam_pairs == 0 && paired) { bmh_set_error("read group '%s': reads file: %s: paired reads were asked for and the BAM's records do not carry flag 0x1", groups[g].id, groups[g].path1); return BMH_EINVAL; }
+		*pairs = groups[g].path2 || bam_pairs == 1 || (bam_pairs < 0 && paired) ? 1 : 0;
+		ld.g = g; ld.id0 = 0;
+		return BMH_OK;
+	};
+	int run_pairs = 0;
+	int rc = open_pump(0, &run_pairs);
+	if (rc != BMH_OK) { close_pump(); return rc; }
+	if (run_pairs && !stated) {                                        // (the first group is a BAM that holds pairs: bmh_aligner_run_files' choices for that case)
+		if (batch_reads & 1) --batch_reads;
+		if (h->bam_pairs_bases && batch_reads == 0) batch_bases = std::min<uint64_t>(h->bam_pairs_bases, (1ull << 31) - 4096);
+		if (h->bam_pairs_lanes > 0) n_lanes = h->bam_pairs_lanes;
+	}
+	auto fill = [&](fbatch_t &fb) -> int {
+		for (;;) {
+			if (!ld.P) {
+				if (ld.g + 1 >= n_groups) return 0;
+				int pairs = 0;
+				RCK(open_pump(ld.g + 1, &pairs));
+				if (pairs != run_pairs) {
+					bmh_set_error("read group '%s': reads file: %s: the group holds %s and the groups before it %s (all groups of a run hold pairs, or none does)", groups[ld.g].id, groups[ld.g].path1,
+					              pairs ? "pairs" : "single-end reads", run_pairs ? "pairs" : "single-end reads");
+					return BMH_EINVAL;
+				}
+			}
+			const bmh_batch_alloc_t alloc = [&](uint64_t nr, uint64_t nb, uint64_t nn, uint64_t ncm, bool fq, bmh_read_set_t *rs) { return fb.size(fn, nr, nb, nn, ncm, fq, cm, rs); };
+			int got = bmh_pump_next(ld.P, batch_bases, batch_reads, /* even counts, as bseq_read ends its batches */ batch_reads == 0, false, alloc, &fb.rs);
+			if (got == 1) { fb.group = ld.g; got = accept_batch(fn, run_pairs, fb, ld.id0); }
+			if (got < 0) return named(ld.g);
+			if (got == 1) return 1;
+			close_pump();                                              // the group's end: the next group's first batch follows in the same queue
+		}
+	};
+	aligner_t &A = h->a;
+	A.group_ids.assign(ids.begin(), ids.end()); A.groups = T; ++A.groups_serial;
+	rc = run_loaded(h, fn, dev, fill, true, run_pairs, n_lanes, n_threads, sink, user, stats);
+	A.group_ids.clear(); A.groups = bdp_table_t(); ++A.groups_serial;
+	close_pump();
+	bmh_reads_note_counts(ld.cnt); bmh_reads_note_inflate_counts(ld.icnt); bmh_reads_note_bam_counts(ld.bcnt);
 	return rc;
 }
 

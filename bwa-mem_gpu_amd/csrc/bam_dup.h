@@ -1,6 +1,7 @@
 // Duplicate marking, internal: the host forms (csrc/bam_dup_host.cpp) and what csrc/bam_dup_kernels.hip offers csrc/bam_sort_kernels.hip and csrc/align_pipeline.hip.
 #pragma once
 #include <stdint.h>
+#include <string>
 #include <vector>
 #ifndef BDP_STANDALONE
 #include "bmh_internal.h"
@@ -15,13 +16,31 @@ void bmh_set_error(const char *fmt, ...);
 enum { BDP_PAIRS = 0, BDP_FRAGS, BDP_DUP_PAIRS, BDP_DUP_FRAGS, BDP_FLAGGED, BDP_SECSUP, BDP_UNMAPPED, BDP_TEMPLATES, BDP_N_COUNTS };
 
 // csrc/bam_dup_host.cpp
+// a run's read groups as the entry points take them (ids [n], lib [n]: every group's library index) -> the table of csrc/bam_dup_core.h; n_lib: 1 + the largest
+// index.  Refused (BMH_EINVAL, the row named): no rows, an empty ID, two rows with one ID, a library index outside 0 .. BDP_MAX_LIBS - 1
+struct bdp_table_t {
+	std::string ids; std::vector<uint32_t> id_off; std::vector<uint8_t> lib; uint32_t n_lib = 0;
+	bool empty() const { return lib.empty(); }
+	bdp_groups_t view() const { return {ids.data(), id_off.data(), lib.data(), (uint32_t)lib.size()}; }
+};
+int bdp_table_make(bdp_table_t &T, const char *const *ids, const int32_t *lib, int n, const char *fn);
+// with a table every record's refID stays below BDP_MAX_REF (the library takes the end words' top byte): the first that does not is refused by its index
+int bdp_refs_fit(const uint8_t *recs, const uint64_t *off, uint32_t n, const char *fn);
+// the message of a template bdp_entry_lib refuses (st: BDP_E_NO_RG or BDP_E_RG_UNKNOWN) that begins at record `rec`
+int bdp_group_refused(uint32_t rec, int st, const char *fn);
 // records in the writer's order with offsets off [n + 1] -> tpl [n]: every record's template ordinal in the stream; entries: one per template; info [2] += the
 // secondary or supplementary and the unmapped records.  Not BMH_OK (message set): the first record begins no template, or a paired template lacks a primary line
-int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn);
-// the decision: bits [(T + 31) / 32]: bit t set when template t is a duplicate; counts [0 .. 4]
-void bdp_decide_host(const bdp_entry_t *entries, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5]);
-// the whole of it on a walked stream: flags set in place
-int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn);
+// G (or NULL): the run's read groups -- the entries carry their templates' libraries; a first record without RG:Z, or with an ID G does not hold, is refused too
+int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn,
+                     const bdp_groups_t *G = nullptr);
+// the decision: bits [(T + 31) / 32]: bit t set when template t is a duplicate; counts [0 .. 4]; lib_counts (or NULL) [BDP_N_COUNTS * n_lib]: every library's own
+// counts, of which the decision fills (and zeroes the rest of) words 0 .. 4
+void bdp_decide_host(const bdp_entry_t *entries, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5], uint32_t n_lib = 0, uint64_t *lib_counts = nullptr);
+// words 5 .. 7 of every library's counts += the secondary or supplementary records, the unmapped records and the templates of the stream (off [n + 1], tpl [n]: the
+// records' template ordinals, E [T]: entries made with read groups)
+void bdp_lib_tally_host(const uint8_t *recs, const uint64_t *off, uint32_t n, const uint32_t *tpl, const bdp_entry_t *E, uint64_t T, uint32_t n_lib, uint64_t *lib_counts);
+// the whole of it on a walked stream: flags set in place; T, lib_counts [BDP_N_COUNTS * T->n_lib] (or NULL): with read groups, and every library's counts
+int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn, const bdp_table_t *T = nullptr, uint64_t *lib_counts = nullptr);
 
 // csrc/bam_dup_kernels.hip
 struct bdp_dev_t;                                                  // device buffers of the batches' entries, the decision and the bitmap; kept between calls
@@ -29,13 +48,21 @@ bdp_dev_t *bdp_dev_create(void);
 void bdp_dev_free(bdp_dev_t *d);
 // a batch's records d_recs with offsets d_off [n + 1] (device, writer's order) -> *d_tpl [n], *d_entries [up to n], *d_info [4]: templates, the first bad record + 1
 // (0: none; n + 1: the first record begins no template), secondary or supplementary records, unmapped records -- all in d until its next call
+// With read groups (bdp_dev_set_groups) *d_info has BDP_INFO_WORDS words: [4], [5] the first template's first record + 1 without an RG:Z tag / with an ID the
+// table does not hold (0xffffffff: none)
+enum { BDP_INFO_WORDS = 8 };
 int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint32_t **d_tpl,
                      const bdp_entry_t **d_entries, const uint32_t **d_info);
+// the run's read groups go to the device (T NULL or empty: none, the entries are made without libraries); the batches that follow use them
+int bdp_dev_set_groups(bdp_dev_t *d, const bdp_table_t *T, void *stream);
 // the message of a batch whose info [1] is not 0
 int bdp_batch_refused(uint32_t n, uint32_t bad, const char *fn);
+// the verdict on a batch's info words (n records; groups: all BDP_INFO_WORDS were read): BMH_OK, or the message of the first refused record
+int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *fn);
 // every template's entry (host) -> the bitmap, kept in d for bdp_flag_device, and counts [0 .. 4]
 // n_records: the records of the final sort that follows (csrc/bam_sort_kernels.hip: 24 bytes each and the sort's work space) -- the decision's buffers are freed
 // before that sort allocates, so one check of the larger of the two needs refuses here what either would refuse
-int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records = 0);
+// n_lib, lib_counts [BDP_N_COUNTS * n_lib] (or 0, NULL): words 0 .. 4 of every library's counts, from the entries' library bytes and the bitmap (the other words zeroed)
+int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records = 0, uint32_t n_lib = 0, uint64_t *lib_counts = nullptr);
 // records d_recs at d_off [n] (device; all inside `total` bytes) whose global template ordinals are tord [n] (host): byte 19 |= 0x04 where the bitmap says so
 int bdp_flag_device(bdp_dev_t *d, uint8_t *d_recs, const uint64_t *d_off, const uint32_t *tord, uint32_t n, uint64_t total, void *stream);

@@ -14,11 +14,22 @@
 //   fragments key: the end word; a duplicate if some pair has an end with that word, otherwise the best fragment at that word (score, then ordinal) stays
 //   flagging  every record of a duplicate template gets 0x400 (byte 19 |= 0x04): primary, secondary and supplementary lines, the unmapped mate of a fragment
 //
-// No optical duplicates, one library per run, no library-size estimate, nothing is removed.
+//   library   only when the run gives a table of (read group ID, library index): a template's library is that of the RG:Z tag on its first record.  The index
+//             replaces the top 8 bits of both end words (above a refID below 2^24), so pairs are duplicates of each other, a fragment is a duplicate through a
+//             pair's end, and the best fragment stays, within one library only -- keys of different libraries differ, the decision's passes do not change.
+//             Without a table no tag is read and every byte is as it was
+//
+// No optical duplicates, no library-size estimate, nothing is removed.
 #pragma once
 #include "bam_sort_core.h"
 
 enum { BDP_NONE = 0, BDP_FRAG = 1, BDP_PAIR = 2, BDP_QMIN = 15 };
+enum { BDP_LIB_SHIFT = 56, BDP_MAX_LIBS = 255, BDP_MAX_REF = 1 << 24 };
+// what bdp_entry_lib says of a template
+enum { BDP_E_OK = 0, BDP_E_TEMPLATE = 1, BDP_E_NO_RG = 2, BDP_E_RG_UNKNOWN = 3 };
+
+// a run's read groups: the IDs back to back (no terminators) with offsets id_off [n + 1], and every group's library index (below BDP_MAX_LIBS)
+struct bdp_groups_t { const char *ids; const uint32_t *id_off; const uint8_t *lib; uint32_t n; };
 
 // one template: lo <= hi the end words of a pair, hi all ones for a fragment (both for kind none); kind_n: kind | records of the template << 2
 struct bdp_entry_t { uint64_t lo, hi; uint32_t score, kind_n; };
@@ -94,3 +105,71 @@ BSR_FN bool bdp_entry(const uint8_t *recs, const uint64_t *off, uint32_t a, uint
 BSR_FN uint64_t bdp_rank_word(const bdp_entry_t &e, uint32_t ordinal) { return (uint64_t)(0xffffffffu - e.score) << 32 | ordinal; }
 // the fragment pass's second word: pair ends (0) before fragments, those best-first (ordinals stay below 2^31)
 BSR_FN uint64_t bdp_frag_word(const bdp_entry_t &e, uint32_t ordinal) { return bdp_kind(e) == BDP_PAIR ? 0ull : 1ull << 63 | (uint64_t)(0xffffffffu - e.score) << 31 | ordinal; }
+
+// ---- libraries
+
+BSR_FN uint32_t bdp_aux_width(uint8_t type) { return type == 'A' || type == 'c' || type == 'C' ? 1u : type == 's' || type == 'S' ? 2u : type == 'i' || type == 'I' || type == 'f' ? 4u : 0u; }
+
+// the value of the record's RG:Z tag (its length in *len), found by a walk over the tags behind the qualities; nullptr: none, or tags that cannot be walked
+BSR_FN const uint8_t *bdp_rg_tag(const uint8_t *rec, uint64_t sz, uint32_t *len)
+{
+	if (sz < BSR_FIXED || !bdp_record_whole(rec, sz)) return nullptr;
+	const uint64_t l_seq = bsr_u32(rec + 20);
+	uint64_t p = (uint64_t)BSR_FIXED + rec[12] + 4ull * bsr_u16(rec + 16) + (l_seq + 1) / 2 + l_seq;
+	while (p + 3 <= sz) {
+		const uint8_t t0 = rec[p], t1 = rec[p + 1], ty = rec[p + 2];
+		p += 3;
+		if (ty == 'Z' || ty == 'H') {
+			uint64_t e = p;
+			while (e < sz && rec[e]) ++e;
+			if (e >= sz) return nullptr;
+			if (t0 == 'R' && t1 == 'G' && ty == 'Z') { *len = (uint32_t)(e - p); return rec + p; }
+			p = e + 1;
+		} else if (ty == 'B') {
+			if (p + 5 > sz) return nullptr;
+			const uint32_t w = bdp_aux_width(rec[p]);
+			if (!w) return nullptr;
+			p += 5 + (uint64_t)w * bsr_u32(rec + p + 1);
+		} else {
+			const uint32_t w = bdp_aux_width(ty);
+			if (!w) return nullptr;
+			p += w;
+		}
+	}
+	return nullptr;
+}
+
+// the library of the record's read group by the table (compared row by row: a run has a handful of groups); -1: no RG:Z tag, -2: an ID the table does not hold
+BSR_FN int bdp_library(const uint8_t *rec, uint64_t sz, const bdp_groups_t &G)
+{
+	uint32_t len = 0;
+	const uint8_t *id = bdp_rg_tag(rec, sz, &len);
+	if (!id) return -1;
+	for (uint32_t g = 0; g < G.n; ++g) {
+		const uint32_t a = G.id_off[g];
+		if (G.id_off[g + 1] - a != len) continue;
+		uint32_t k = 0;
+		while (k < len && (uint8_t)G.ids[a + k] == id[k]) ++k;
+		if (k == len) return G.lib[g];
+	}
+	return -2;
+}
+
+BSR_FN uint64_t bdp_lib_word(uint64_t word, uint32_t lib) { return (word & ((1ull << BDP_LIB_SHIFT) - 1)) | (uint64_t)lib << BDP_LIB_SHIFT; }
+// the library of an entry that bdp_entry_lib made
+BSR_FN uint32_t bdp_lib_of(const bdp_entry_t &e) { return (uint32_t)(e.lo >> BDP_LIB_SHIFT); }
+
+// bdp_entry with the library of the template's first record in the end words; BDP_E_*
+BSR_FN int bdp_entry_lib(const uint8_t *recs, const uint64_t *off, uint32_t a, uint32_t b, const bdp_groups_t &G, bdp_entry_t *e)
+{
+	const bool ok = bdp_entry(recs, off, a, b, e);
+	const int lib = bdp_library(recs + off[a], off[a + 1] - off[a], G);
+	if (lib < 0) return lib == -1 ? BDP_E_NO_RG : BDP_E_RG_UNKNOWN;
+	if (!ok) return BDP_E_TEMPLATE;
+	e->lo = bdp_lib_word(e->lo, (uint32_t)lib);                            // (of every kind: a template that is neither pair nor fragment keeps its library here too, for the counts)
+	if (bdp_kind(*e) == BDP_PAIR) e->hi = bdp_lib_word(e->hi, (uint32_t)lib);
+	return BDP_E_OK;
+}
+
+// where a pair's or a fragment's entry counts among its library's five counters: examined (0 pairs, 1 fragments), and as a duplicate 2 / 3 and its records at 4
+BSR_FN uint32_t bdp_examined_slot(const bdp_entry_t &e) { return bdp_kind(e) == BDP_PAIR ? 0u : 1u; }

@@ -16,7 +16,53 @@ int bdp_batch_refused(uint32_t n, uint32_t bad, const char *fn)
 	return BMH_EINVAL;
 }
 
-int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn)
+int bdp_group_refused(uint32_t rec, int st, const char *fn)
+{
+	if (st == BDP_E_NO_RG) bmh_set_error("%s: duplicate marking: record %u begins a template and carries no RG:Z tag (read groups were given: every template's library comes from that tag)", fn, rec);
+	else bmh_set_error("%s: duplicate marking: record %u begins a template and names a read group that is not among those given", fn, rec);
+	return BMH_EINVAL;
+}
+
+int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *fn)
+{
+	if (!n) return BMH_OK;
+	// (the smallest record index wins, as a walk from the front would find it)
+	if (info[1] == 0) return bdp_batch_refused(n, n + 1, fn);
+	uint32_t bad = info[1]; int st = BDP_E_TEMPLATE;
+	if (groups) for (int k = 0; k < 2; ++k) if (info[4 + k] < bad) { bad = info[4 + k]; st = k ? BDP_E_RG_UNKNOWN : BDP_E_NO_RG; }
+	if (bad == 0xffffffffu) return BMH_OK;
+	return st == BDP_E_TEMPLATE ? bdp_batch_refused(n, bad, fn) : bdp_group_refused(bad - 1, st, fn);
+}
+
+int bdp_table_make(bdp_table_t &T, const char *const *ids, const int32_t *lib, int n, const char *fn)
+{
+	T.ids.clear(); T.id_off.assign(1, 0); T.lib.clear(); T.n_lib = 0;
+	if (n < 1 || !ids || !lib) { bmh_set_error("%s: no read groups were given", fn); return BMH_EINVAL; }
+	for (int g = 0; g < n; ++g) {
+		if (!ids[g] || !ids[g][0]) { bmh_set_error("%s: read group %d has no ID", fn, g); return BMH_EINVAL; }
+		for (int k = 0; k < g; ++k)
+			if (!strcmp(ids[k], ids[g])) { bmh_set_error("%s: read groups %d and %d share the ID '%s'", fn, k, g, ids[g]); return BMH_EINVAL; }
+		if (lib[g] < 0 || lib[g] >= BDP_MAX_LIBS) {
+			bmh_set_error("%s: read group %d ('%s') is of library %d: a run holds at most %d libraries (the library is a byte of the duplicate key)", fn, g, ids[g], lib[g], (int)BDP_MAX_LIBS);
+			return BMH_EINVAL;
+		}
+		T.ids += ids[g]; T.id_off.push_back((uint32_t)T.ids.size()); T.lib.push_back((uint8_t)lib[g]);
+		if ((uint32_t)lib[g] + 1 > T.n_lib) T.n_lib = (uint32_t)lib[g] + 1;
+	}
+	return BMH_OK;
+}
+
+int bdp_refs_fit(const uint8_t *recs, const uint64_t *off, uint32_t n, const char *fn)
+{
+	for (uint32_t i = 0; i < n; ++i)
+		if (bsr_ref(recs + off[i]) >= (int32_t)BDP_MAX_REF) {
+			bmh_set_error("%s: duplicate marking: record %u names reference %d: with read groups references stay below 2^24 (the library takes the key's top byte)", fn, i, bsr_ref(recs + off[i]));
+			return BMH_EINVAL;
+		}
+	return BMH_OK;
+}
+
+int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn, const bdp_groups_t *G)
 {
 	tpl.resize(n); entries.clear();
 	if (n && !bdp_head(bsr_flag(recs + off[0]))) return bdp_batch_refused(n, n + 1, fn);
@@ -30,12 +76,16 @@ int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::
 	}
 	if (start.size() >= 1ull << 31) { bmh_set_error("%s: duplicate marking: 2^31 templates", fn); return BMH_EINVAL; }
 	entries.resize(start.size());
-	for (size_t t = 0; t < start.size(); ++t)
-		if (!bdp_entry(recs, off, start[t], t + 1 < start.size() ? start[t + 1] : n, &entries[t])) return bdp_batch_refused(n, start[t] + 1, fn);
+	for (size_t t = 0; t < start.size(); ++t) {
+		const uint32_t a = start[t], b = t + 1 < start.size() ? start[t + 1] : n;
+		const int st = G ? bdp_entry_lib(recs, off, a, b, *G, &entries[t]) : bdp_entry(recs, off, a, b, &entries[t]) ? BDP_E_OK : BDP_E_TEMPLATE;
+		if (st == BDP_E_TEMPLATE) return bdp_batch_refused(n, a + 1, fn);
+		if (st != BDP_E_OK) return bdp_group_refused(a, st, fn);
+	}
 	return BMH_OK;
 }
 
-void bdp_decide_host(const bdp_entry_t *E, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5])
+void bdp_decide_host(const bdp_entry_t *E, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5], uint32_t n_lib, uint64_t *lib_counts)
 {
 	bits.assign((size_t)((T + 31) / 32), 0u);
 	for (int k = 0; k < 5; ++k) counts[k] = 0;
@@ -62,9 +112,30 @@ void bdp_decide_host(const bdp_entry_t *E, uint64_t T, std::vector<uint32_t> &bi
 		if (bdp_kind(E[items[i].t]) != BDP_FRAG) continue;
 		if (bdp_kind(E[items[first].t]) == BDP_PAIR || i != first) { mark(items[i].t); ++counts[BDP_DUP_FRAGS]; }
 	}
+	if (!lib_counts) return;
+	for (uint32_t k = 0; k < BDP_N_COUNTS * n_lib; ++k) lib_counts[k] = 0;
+	for (uint64_t t = 0; t < T; ++t) {
+		if (bdp_kind(E[t]) == BDP_NONE || bdp_lib_of(E[t]) >= n_lib) continue;
+		uint64_t *c = lib_counts + BDP_N_COUNTS * (size_t)bdp_lib_of(E[t]);
+		const uint32_t s = bdp_examined_slot(E[t]);
+		++c[s];
+		if (bits[t >> 5] >> (t & 31) & 1u) { ++c[2 + s]; c[BDP_FLAGGED] += bdp_n_rec(E[t]); }
+	}
 }
 
-int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn)
+void bdp_lib_tally_host(const uint8_t *recs, const uint64_t *off, uint32_t n, const uint32_t *tpl, const bdp_entry_t *E, uint64_t T, uint32_t n_lib, uint64_t *lib_counts)
+{
+	for (uint64_t t = 0; t < T; ++t) if (bdp_lib_of(E[t]) < n_lib) ++lib_counts[BDP_N_COUNTS * (size_t)bdp_lib_of(E[t]) + BDP_TEMPLATES];
+	for (uint32_t i = 0; i < n; ++i) {
+		if (tpl[i] >= T || bdp_lib_of(E[tpl[i]]) >= n_lib) continue;
+		uint64_t *c = lib_counts + BDP_N_COUNTS * (size_t)bdp_lib_of(E[tpl[i]]);
+		const uint32_t fl = bsr_flag(recs + off[i]);
+		if (fl & 0x900u) ++c[BDP_SECSUP];
+		if (fl & 4u) ++c[BDP_UNMAPPED];
+	}
+}
+
+int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn, const bdp_table_t *T, uint64_t *lib_counts)
 {
 	const uint32_t n = (uint32_t)(off.size() - 1);
 	for (int k = 0; k < BDP_N_COUNTS; ++k) counts[k] = 0;
@@ -73,18 +144,22 @@ int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t c
 			bmh_set_error("%s: record %u is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL;
 		}
 	std::vector<uint32_t> tpl, bits; std::vector<bdp_entry_t> E;
-	const int rc = bdp_entries_host(recs, off.data(), n, tpl, E, counts + BDP_SECSUP, fn);
+	bdp_groups_t G = {nullptr, nullptr, nullptr, 0};
+	if (T) G = T->view();
+	int rc = T ? bdp_refs_fit(recs, off.data(), n, fn) : BMH_OK;
+	if (rc != BMH_OK) return rc;
+	rc = bdp_entries_host(recs, off.data(), n, tpl, E, counts + BDP_SECSUP, fn, T ? &G : nullptr);
 	if (rc != BMH_OK) return rc;
 	counts[BDP_TEMPLATES] = E.size();
-	bdp_decide_host(E.data(), E.size(), bits, counts);
+	bdp_decide_host(E.data(), E.size(), bits, counts, T ? T->n_lib : 0, T ? lib_counts : nullptr);
+	if (T && lib_counts) bdp_lib_tally_host(recs, off.data(), n, tpl.data(), E.data(), E.size(), T->n_lib, lib_counts);
 	for (uint32_t i = 0; i < n; ++i) if (bits[tpl[i] >> 5] >> (tpl[i] & 31) & 1u) recs[off[i] + 19] |= 0x04;
 	return BMH_OK;
 }
 
 #ifndef BDP_STANDALONE
-extern "C" int bmh_bam_markdup_host(const uint8_t *recs, uint64_t n_bytes, uint8_t **out, uint64_t counts[8])
+static int markdup_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_table_t *T, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts)
 {
-	const char *fn = "bmh_bam_markdup_host";
 	if (!out || !counts || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*out = nullptr;
 	std::vector<uint64_t> off;
@@ -93,8 +168,24 @@ extern "C" int bmh_bam_markdup_host(const uint8_t *recs, uint64_t n_bytes, uint8
 	uint8_t *o = (uint8_t *)malloc(n_bytes + 1);
 	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
 	if (n_bytes) memcpy(o, recs, n_bytes);
-	if ((rc = bdp_markdup_host(o, off, counts, fn)) != BMH_OK) { free(o); return rc; }
+	if ((rc = bdp_markdup_host(o, off, counts, fn, T, lib_counts)) != BMH_OK) { free(o); return rc; }
 	*out = o;
 	return BMH_OK;
+}
+
+extern "C" int bmh_bam_markdup_host(const uint8_t *recs, uint64_t n_bytes, uint8_t **out, uint64_t counts[8])
+{
+	return markdup_host("bmh_bam_markdup_host", recs, n_bytes, nullptr, out, counts, nullptr);
+}
+
+extern "C" int bmh_bam_markdup_groups_host(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, uint8_t **out, uint64_t counts[8],
+                                           uint64_t *lib_counts)
+{
+	const char *fn = "bmh_bam_markdup_groups_host";
+	bdp_table_t T;
+	if (out) *out = nullptr;
+	const int rc = bdp_table_make(T, rg_ids, rg_lib, n_groups, fn);
+	if (rc != BMH_OK) return rc;
+	return markdup_host(fn, recs, n_bytes, &T, out, counts, lib_counts);
 }
 #endif

@@ -2,12 +2,15 @@
 //
 //   per batch   heads: one lane per record, through the converter's offsets -- does it begin a template, is it a secondary / supplementary / unmapped line;
 //               an inclusive scan of the heads gives every record its batch-local template ordinal; starts: a head writes its record index at its ordinal;
-//               entries: one lane per template over its few records -> (end word lo, end word hi, score, kind | records << 2), 24 bytes
+//               entries: one lane per template over its few records -> (end word lo, end word hi, score, kind | records << 2), 24 bytes; with read groups the
+//               lane also walks its first record's tags to RG:Z and compares the ID with the run's table row by row (a few short IDs in global memory, the
+//               same rows for every lane of a pipeline's batch) -- the library goes into the end words' top byte
 //   decision    at the end of the input, over all templates' entries.  Pair pass: three stable 64-bit radix passes (rank word, hi, lo; templates that are no
 //               pair carry all-ones words and sort behind the pairs), then a lane is a duplicate iff its (lo, hi) equals the lane's before it.  Fragment pass:
 //               the fragments plus two items per pair (one per end), compacted through a scan; two stable passes (pair ends first, fragments best-first; then
 //               the end word); run heads, a max-scan of the heads' indices, and a lane decides from the first item of its run -- a run may span workgroups.
-//               Output: a bitmap over global template ordinals and five counters.
+//               Output: a bitmap over global template ordinals and five counters.  Libraries need no pass of their own: their keys differ.  With read groups
+//               one more kernel counts the five per library from the entries' library bytes and the bitmap (a histogram in LDS per workgroup)
 //   per window  one lane per record tests the bitmap through the record's global template ordinal and ORs 0x04 into byte 19 (a byte store: records are unaligned)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,6 +26,7 @@
 struct bdp_dev_t {
 	dev_buf<uint8_t> head, tpl, start, entries, info, tmp;                        // per batch
 	dev_buf<uint8_t> bits, tord;                                                  // the bitmap of the run, a window's ordinals
+	dev_buf<uint8_t> g_ids, g_off, g_lib; uint32_t g_n = 0;                       // the run's read groups (bdp_dev_set_groups): IDs, their offsets, libraries; 0: none
 	uint64_t n_tpl = 0;                                                     // templates the bitmap covers
 };
 
@@ -56,17 +60,20 @@ __global__ void __launch_bounds__(256) bdp_starts(const uint32_t *__restrict__ h
 	if (i == n - 1) { info[0] = s; if (s < n + 1) start[s < n ? s : n] = n; }
 }
 
+// LIB: the run has read groups (G) -- info [4], [5]: the first template without an RG:Z tag / with an unknown ID, as info [1]
+template <bool LIB>
 __global__ void __launch_bounds__(256) bdp_entries(const uint8_t *__restrict__ recs, const uint64_t *__restrict__ off, uint32_t n, uint64_t total, const uint32_t *__restrict__ start,
-                                                   bdp_entry_t *__restrict__ entries, uint32_t *info)
+                                                   bdp_entry_t *__restrict__ entries, uint32_t *info, bdp_groups_t G)
 {
 	const uint32_t t = blockIdx.x * 256 + threadIdx.x;
 	if (t >= n || t >= info[0] || info[1] == 0) return;
 	const uint32_t a = start[t], b = start[t + 1];
 	bdp_entry_t e; e.lo = e.hi = ~0ull; e.score = 0; e.kind_n = 0;
-	bool ok = a < b && b <= n && off[b] <= total;                          // (offsets ascend: every record of the template lies inside the buffer)
-	if (ok) ok = bdp_entry(recs, off, a, b, &e);
+	int st = a < b && b <= n && off[b] <= total ? BDP_E_OK : BDP_E_TEMPLATE;      // (offsets ascend: every record of the template lies inside the buffer)
+	if (st == BDP_E_OK) st = LIB ? bdp_entry_lib(recs, off, a, b, G, &e) : bdp_entry(recs, off, a, b, &e) ? BDP_E_OK : BDP_E_TEMPLATE;
 	entries[t] = e;
-	if (!ok) atomicMin(info + 1, a + 1);
+	if (st == BDP_E_TEMPLATE) atomicMin(info + 1, a + 1);
+	else if (LIB && st != BDP_E_OK) atomicMin(info + (st == BDP_E_NO_RG ? 4 : 5), a + 1);
 }
 
 // ---- the decision
@@ -172,6 +179,27 @@ __global__ void __launch_bounds__(256) bdp_frag_decide(const bdp_entry_t *__rest
 	if (threadIdx.x == 0) { if (cd) atomicAdd(counts + 3, (unsigned long long)cd); if (recs_s) atomicAdd(counts + 4, recs_s); }
 }
 
+// the decision's five counters per library: out [BDP_N_COUNTS * n_lib] (words 0 .. 4 of every library), through a histogram in LDS (5 * n_lib 64-bit words, 10 KiB at the most)
+__global__ void __launch_bounds__(256) bdp_lib_counts(const bdp_entry_t *__restrict__ E, uint64_t n, const uint32_t *__restrict__ bits, uint32_t n_lib, unsigned long long *out)
+{
+	extern __shared__ unsigned long long lib_s[];
+	for (uint32_t k = threadIdx.x; k < 5 * n_lib; k += 256) lib_s[k] = 0;
+	__syncthreads();
+	const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (t < n) {
+		const bdp_entry_t e = E[t];
+		const uint32_t lib = bdp_lib_of(e);
+		if (bdp_kind(e) != BDP_NONE && lib < n_lib) {
+			unsigned long long *c = lib_s + 5 * lib;
+			const uint32_t s = bdp_examined_slot(e);
+			atomicAdd(c + s, 1ull);
+			if (bits[t >> 5] >> (t & 31) & 1u) { atomicAdd(c + 2 + s, 1ull); atomicAdd(c + 4, (unsigned long long)bdp_n_rec(e)); }
+		}
+	}
+	__syncthreads();
+	for (uint32_t k = threadIdx.x; k < 5 * n_lib; k += 256) if (lib_s[k]) atomicAdd(out + BDP_N_COUNTS * (k / 5) + k % 5, lib_s[k]);
+}
+
 // ---- the flags of a window
 __global__ void __launch_bounds__(256) bdp_flag(uint8_t *__restrict__ recs, const uint64_t *__restrict__ off, const uint32_t *__restrict__ tord, uint32_t n, uint64_t total,
                                                 const uint32_t *__restrict__ bits, uint64_t n_tpl)
@@ -196,24 +224,44 @@ int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off,
 	hipStream_t st = (hipStream_t)stream;
 	size_t tb = scan_tmp_bytes<uint32_t, uint32_t, true>((size_t)n + 1);
 	RCK(d->head.need(4 * ((size_t)n + 1))); RCK(d->tpl.need(4 * ((size_t)n + 1))); RCK(d->start.need(4 * ((size_t)n + 2))); RCK(d->entries.need(sizeof(bdp_entry_t) * ((size_t)n + 1)));
-	RCK(d->info.need(16)); RCK(d->tmp.need(tb));
-	const uint32_t init[4] = {0u, 0xffffffffu, 0u, 0u};
-	HIPCK(hipMemcpyAsync(d->info.p, init, 16, hipMemcpyHostToDevice, st));
+	RCK(d->info.need(4 * BDP_INFO_WORDS)); RCK(d->tmp.need(tb));
+	static const uint32_t init[BDP_INFO_WORDS] = {0u, 0xffffffffu, 0u, 0u, 0xffffffffu, 0xffffffffu, 0u, 0u};
+	HIPCK(hipMemcpyAsync(d->info.p, init, 4 * BDP_INFO_WORDS, hipMemcpyHostToDevice, st));
 	if (n) {
 		bdp_heads<<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, (uint32_t *)d->head.p, (uint32_t *)d->info.p);
 		HIPCK(rocprim::inclusive_scan(d->tmp.p, tb, (uint32_t *)d->head.p, (uint32_t *)d->tpl.p, (size_t)n, rocprim::plus<uint32_t>(), st));
 		bdp_starts<<<blocks(n), 256, 0, st>>>((const uint32_t *)d->head.p, (uint32_t *)d->tpl.p, n, (uint32_t *)d->start.p, (uint32_t *)d->info.p);
-		bdp_entries<<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, (const uint32_t *)d->start.p, (bdp_entry_t *)d->entries.p, (uint32_t *)d->info.p);
+		const bdp_groups_t G = {(const char *)d->g_ids.p, (const uint32_t *)d->g_off.p, (const uint8_t *)d->g_lib.p, d->g_n};
+		if (d->g_n) bdp_entries<true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, (const uint32_t *)d->start.p, (bdp_entry_t *)d->entries.p, (uint32_t *)d->info.p, G);
+		else bdp_entries<false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, (const uint32_t *)d->start.p, (bdp_entry_t *)d->entries.p, (uint32_t *)d->info.p, G);
 		HIPCK(hipGetLastError());
 	}
 	*d_tpl = (const uint32_t *)d->tpl.p; *d_entries = (const bdp_entry_t *)d->entries.p; *d_info = (const uint32_t *)d->info.p;
 	return BMH_OK;
 }
 
-int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records)
+int bdp_dev_set_groups(bdp_dev_t *d, const bdp_table_t *T, void *stream)
+{
+	hipStream_t st = (hipStream_t)stream;
+	d->g_n = 0;
+	if (!T || T->empty()) return BMH_OK;
+	const size_t n = T->lib.size();
+	RCK(d->g_ids.need(T->ids.size() + 1)); RCK(d->g_off.need(4 * (n + 1))); RCK(d->g_lib.need(n));
+	HIPCK(hipMemcpyAsync(d->g_ids.p, T->ids.data(), T->ids.size(), hipMemcpyHostToDevice, st));
+	HIPCK(hipMemcpyAsync(d->g_off.p, T->id_off.data(), 4 * (n + 1), hipMemcpyHostToDevice, st));
+	HIPCK(hipMemcpyAsync(d->g_lib.p, T->lib.data(), n, hipMemcpyHostToDevice, st));
+	HIPCK(hipStreamSynchronize(st));                                      // (the table may go before the kernels that read it have run)
+	d->g_n = (uint32_t)n;
+	return BMH_OK;
+}
+
+int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records, uint32_t n_lib, uint64_t *lib_counts)
 {
 	hipStream_t st = (hipStream_t)stream;
 	for (int k = 0; k < 5; ++k) counts[k] = 0;
+	if (!lib_counts) n_lib = 0;
+	for (uint32_t k = 0; k < BDP_N_COUNTS * n_lib; ++k) lib_counts[k] = 0;
+	if (n_lib > BDP_MAX_LIBS) { bmh_set_error("duplicate marking: %u libraries: a run holds at most %d", n_lib, (int)BDP_MAX_LIBS); return BMH_EINVAL; }
 	d->n_tpl = T;
 	RCK(d->bits.need(4 * (size_t)((T + 31) / 32) + 4));
 	HIPCK(hipMemsetAsync(d->bits.p, 0, 4 * (size_t)((T + 31) / 32) + 4, st));
@@ -282,6 +330,13 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 	}
 	unsigned long long h[5] = {0, 0, 0, 0, 0};
 	HIPCK(hipMemcpyAsync(h, dcnt, 8 * 5, hipMemcpyDeviceToHost, st));
+	dev_buf<uint8_t> lc;                                                  // (64 bytes per library: beside the decision's buffers nothing)
+	if (n_lib) {
+		RCK(lc.need(8 * BDP_N_COUNTS * (size_t)n_lib));
+		HIPCK(hipMemsetAsync(lc.p, 0, 8 * BDP_N_COUNTS * (size_t)n_lib, st));
+		bdp_lib_counts<<<blocks(T), 256, 8 * 5 * (size_t)n_lib, st>>>(dE, T, (const uint32_t *)d->bits.p, n_lib, (unsigned long long *)lc.p);
+		HIPCK(hipMemcpyAsync(lib_counts, lc.p, 8 * BDP_N_COUNTS * (size_t)n_lib, hipMemcpyDeviceToHost, st));
+	}
 	HIPCK(hipStreamSynchronize(st));
 	HIPCK(hipGetLastError());
 	for (int k = 0; k < 5; ++k) counts[k] = h[k];
@@ -301,9 +356,8 @@ int bdp_flag_device(bdp_dev_t *d, uint8_t *d_recs, const uint64_t *d_off, const 
 
 // ---------------------------------------------------------------------------------------------------------------- the stand-alone entry point
 
-extern "C" int bmh_bam_markdup_device(const uint8_t *recs, uint64_t n_bytes, void *stream, uint8_t **out, uint64_t counts[8])
+static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_table_t *G, void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts)
 {
-	const char *fn = "bmh_bam_markdup_device";
 	hipStream_t st = (hipStream_t)stream;
 	if (!out || !counts || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*out = nullptr;
@@ -313,25 +367,28 @@ extern "C" int bmh_bam_markdup_device(const uint8_t *recs, uint64_t n_bytes, voi
 	const uint32_t n = (uint32_t)(off.size() - 1);
 	for (uint32_t i = 0; i < n; ++i)
 		if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) { bmh_set_error("%s: record %u is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL; }
+	if (G) RCK(bdp_refs_fit(recs, off.data(), n, fn));
 	bdp_dev_t d;
 	dev_buf<uint8_t> in, in_off;
+	RCK(bdp_dev_set_groups(&d, G, st));
 	RCK(in.need((size_t)n_bytes + 16)); RCK(in_off.need(8 * off.size()));
 	if (n_bytes) HIPCK(hipMemcpyAsync(in.p, recs, (size_t)n_bytes, hipMemcpyHostToDevice, st));
 	HIPCK(hipMemcpyAsync(in_off.p, off.data(), 8 * off.size(), hipMemcpyHostToDevice, st));
 	const uint32_t *d_tpl; const bdp_entry_t *d_e; const uint32_t *d_info;
 	RCK(bdp_batch_device(&d, (const uint8_t *)in.p, (const uint64_t *)in_off.p, n, n_bytes, st, &d_tpl, &d_e, &d_info));
-	uint32_t info[4] = {0, 0, 0, 0};
-	HIPCK(hipMemcpyAsync(info, d_info, 16, hipMemcpyDeviceToHost, st));
+	uint32_t info[BDP_INFO_WORDS];
+	HIPCK(hipMemcpyAsync(info, d_info, 4 * BDP_INFO_WORDS, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
-	if (n && info[1] != 0xffffffffu) return bdp_batch_refused(n, info[1] ? info[1] : n + 1, fn);
+	RCK(bdp_batch_check(n, info, G != nullptr, fn));
 	const uint32_t T = n ? info[0] : 0;
 	if (T > n) { bmh_set_error("%s: internal error: %u templates among %u records", fn, T, n); return BMH_EINVAL; }
 	std::vector<bdp_entry_t> E(T); std::vector<uint32_t> tpl(n);
 	if (T) HIPCK(hipMemcpyAsync(E.data(), d_e, sizeof(bdp_entry_t) * (size_t)T, hipMemcpyDeviceToHost, st));
 	if (n) HIPCK(hipMemcpyAsync(tpl.data(), d_tpl, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
-	RCK(bdp_decide_device(&d, E.data(), T, st, counts));
+	RCK(bdp_decide_device(&d, E.data(), T, st, counts, 0, G ? G->n_lib : 0, G ? lib_counts : nullptr));
 	counts[BDP_SECSUP] = info[2]; counts[BDP_UNMAPPED] = info[3]; counts[BDP_TEMPLATES] = T;
+	if (G && lib_counts) bdp_lib_tally_host(recs, off.data(), n, tpl.data(), E.data(), T, G->n_lib, lib_counts);
 	RCK(bdp_flag_device(&d, (uint8_t *)in.p, (const uint64_t *)in_off.p, tpl.data(), n, n_bytes, st));
 	uint8_t *o = (uint8_t *)malloc((size_t)n_bytes + 1);
 	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
@@ -339,4 +396,19 @@ extern "C" int bmh_bam_markdup_device(const uint8_t *recs, uint64_t n_bytes, voi
 	if (hipStreamSynchronize(st) != hipSuccess) { free(o); bmh_set_error("%s: %s", fn, hipGetErrorString(hipGetLastError())); return BMH_ENODEV; }
 	*out = o;
 	return BMH_OK;
+}
+
+extern "C" int bmh_bam_markdup_device(const uint8_t *recs, uint64_t n_bytes, void *stream, uint8_t **out, uint64_t counts[8])
+{
+	return markdup_device("bmh_bam_markdup_device", recs, n_bytes, nullptr, stream, out, counts, nullptr);
+}
+
+extern "C" int bmh_bam_markdup_groups_device(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, void *stream, uint8_t **out,
+                                             uint64_t counts[8], uint64_t *lib_counts)
+{
+	const char *fn = "bmh_bam_markdup_groups_device";
+	bdp_table_t G;
+	if (out) *out = nullptr;
+	RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
+	return markdup_device(fn, recs, n_bytes, &G, stream, out, counts, lib_counts);
 }

@@ -116,7 +116,7 @@ void bsr_store_t::clear()
 {
 	for (bsr_run_t &r : runs) free(r.mem);
 	runs.clear(); used = 0; spilled = 0; file_bytes = 0;
-	entries.clear(); dup_info[0] = dup_info[1] = 0;
+	entries.clear(); dup_info[0] = dup_info[1] = 0; lib_info.clear();
 	if (fd >= 0) close(fd);
 	fd = -1;
 }
@@ -154,6 +154,11 @@ int bsr_store_t::append(const uint8_t *recs, uint64_t bytes, const uint64_t *key
 		r.file_at = (int64_t)file_bytes; file_bytes += bytes; ++spilled;
 	}
 	if (dup) { entries.insert(entries.end(), dup->entries, dup->entries + dup->n_tpl); dup_info[0] += dup->secsup; dup_info[1] += dup->unmapped; }
+	if (dup && dup->lib >= 0) {
+		if (lib_info.size() < 3 * ((size_t)dup->lib + 1)) lib_info.resize(3 * ((size_t)dup->lib + 1), 0);
+		uint64_t *c = &lib_info[3 * (size_t)dup->lib];
+		c[0] += dup->secsup; c[1] += dup->unmapped; c[2] += dup->n_tpl;
+	}
 	runs.push_back(std::move(r));
 	return BMH_OK;
 }
@@ -190,10 +195,12 @@ extern "C" int bmh_bam_sort_host(const uint8_t *recs, uint64_t n_bytes, uint8_t 
 
 // header members, the sorted records in windows of `window` records (0: as many as hold about 64 MiB), the end-of-file member; and the index
 static int sorted_file_host(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                            int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts)
+                            int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts,
+                            const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr)
 {
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
+	if (G && n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d references: with read groups a run holds at most 2^24 (the library takes the duplicate key's top byte)", fn, n_contigs); return BMH_EINVAL; }
 	bsr_index_t ix;
 	int rc = ix.init(n_contigs, contig_len, fn);
 	if (rc != BMH_OK) return rc;
@@ -202,7 +209,7 @@ static int sorted_file_host(const char *fn, const char *header_text, int n_conti
 	std::vector<uint8_t> marked;                                   // duplicate marking: the flags are set before the sort (0x400 enters no key, bin or index)
 	if (dup_counts) {
 		marked.assign(recs, recs + n_bytes);
-		if ((rc = bdp_markdup_host(marked.data(), off, dup_counts, fn)) != BMH_OK) return rc;
+		if ((rc = bdp_markdup_host(marked.data(), off, dup_counts, fn, G, lib_counts)) != BMH_OK) return rc;
 		recs = marked.data();
 	}
 	bsr_sort_host(recs, off, keys, ord);
@@ -254,4 +261,16 @@ extern "C" int bmh_bam_sorted_file_markdup_host(const char *header_text, int n_c
 	const char *fn = "bmh_bam_sorted_file_markdup_host";
 	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, bai, bai_bytes, counts);
+}
+
+extern "C" int bmh_bam_sorted_file_markdup_groups_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                                       int level, uint32_t window, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, uint8_t **bam, uint64_t *bam_bytes,
+                                                       uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8], uint64_t *lib_counts)
+{
+	const char *fn = "bmh_bam_sorted_file_markdup_groups_host";
+	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	bdp_table_t G;
+	const int rc = bdp_table_make(G, rg_ids, rg_lib, n_groups, fn);
+	if (rc != BMH_OK) return rc;
+	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, bai, bai_bytes, counts, &G, lib_counts);
 }

@@ -277,7 +277,8 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 }
 
 // every run of the store -> the sorted file's record members (to the sink) and its index
-int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, uint64_t *dup_counts, double *dup_ms)
+int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, uint64_t *dup_counts, double *dup_ms,
+                     uint32_t n_lib, uint64_t *lib_counts)
 {
 	uint64_t n = 0, bytes = 0;
 	std::vector<uint64_t> first;
@@ -291,7 +292,7 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint3
 		for (const bsr_run_t &r : S.runs) if (r.tpl.size() != r.n) { bmh_set_error("sorted BAM: internal error: a run without its records' template ordinals"); return BMH_EINVAL; }
 		if (!(dup.p = bdp_dev_create())) return BMH_ENOMEM;
 		const double t0 = bsr_now_ms();
-		RCK(bdp_decide_device(dup.p, S.entries.data(), S.entries.size(), stream, dup_counts, n));
+		RCK(bdp_decide_device(dup.p, S.entries.data(), S.entries.size(), stream, dup_counts, n, n_lib, lib_counts));
 		dup_counts[BDP_SECSUP] = S.dup_info[0]; dup_counts[BDP_UNMAPPED] = S.dup_info[1]; dup_counts[BDP_TEMPLATES] = S.entries.size();
 		decide_ms = bsr_now_ms() - t0;
 	}
@@ -344,7 +345,7 @@ namespace {
 // what duplicate marking keeps of a stream: its records' template ordinals in sorted order, the templates' entries, the line counts
 struct dup_host_t { std::vector<uint32_t> tpl; std::vector<bdp_entry_t> entries; uint64_t secsup = 0, unmapped = 0; };
 int to_store(bsr_dev_t *d, const uint8_t *recs, uint64_t n_bytes, const std::vector<uint64_t> &off, hipStream_t st, std::vector<uint8_t> &sorted, std::vector<uint64_t> &keys, std::vector<uint64_t> &soff,
-             dup_host_t *dh = nullptr, const char *fn = "")
+             dup_host_t *dh = nullptr, const char *fn = "", const bdp_table_t *G = nullptr)
 {
 	const uint32_t n = (uint32_t)(off.size() - 1);
 	RCK(d->in.need((size_t)n_bytes + 16)); RCK(d->in_off.need(8 * off.size()));
@@ -355,14 +356,15 @@ int to_store(bsr_dev_t *d, const uint8_t *recs, uint64_t n_bytes, const std::vec
 	const uint32_t *d_tpl = nullptr, *d_info = nullptr, *d_tpl_sorted = nullptr; const bdp_entry_t *d_e = nullptr;
 	if (dh) {
 		if (!(dup.p = bdp_dev_create())) return BMH_ENOMEM;
+		RCK(bdp_dev_set_groups(dup.p, G, st));
 		RCK(bdp_batch_device(dup.p, (const uint8_t *)d->in.p, (const uint64_t *)d->in_off.p, n, n_bytes, st, &d_tpl, &d_e, &d_info));
 	}
 	RCK(bsr_sort_run_device(d, (const uint8_t *)d->in.p, (const uint64_t *)d->in_off.p, n, n_bytes, st, &ds, &dk, &dso, d_tpl, &d_tpl_sorted));
 	if (dh) {
-		uint32_t info[4] = {0, 0, 0, 0};
-		HIPCK(hipMemcpyAsync(info, d_info, 16, hipMemcpyDeviceToHost, st));
+		uint32_t info[BDP_INFO_WORDS];
+		HIPCK(hipMemcpyAsync(info, d_info, 4 * BDP_INFO_WORDS, hipMemcpyDeviceToHost, st));
 		HIPCK(hipStreamSynchronize(st));
-		if (n && info[1] != 0xffffffffu) return bdp_batch_refused(n, info[1] ? info[1] : n + 1, fn);
+		RCK(bdp_batch_check(n, info, G != nullptr, fn));
 		if (info[0] > n) { bmh_set_error("%s: internal error: %u templates among %u records", fn, info[0], n); return BMH_EINVAL; }
 		dh->tpl.resize(n); dh->entries.resize(n ? info[0] : 0); dh->secsup = info[2]; dh->unmapped = info[3];
 		if (n) HIPCK(hipMemcpyAsync(dh->tpl.data(), d_tpl_sorted, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
@@ -397,10 +399,12 @@ extern "C" int bmh_bam_sort_device(const uint8_t *recs, uint64_t n_bytes, void *
 }
 
 static int sorted_file_device(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                              int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts)
+                              int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts,
+                              const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr)
 {
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
+	if (G && n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d references: with read groups a run holds at most 2^24 (the library takes the duplicate key's top byte)", fn, n_contigs); return BMH_EINVAL; }
 	if (level != 0 && level != 1) { bmh_set_error("%s: level %d (0 or 1)", fn, level); return BMH_EINVAL; }
 	bsr_index_t ix;
 	RCK(ix.init(n_contigs, contig_len, fn));
@@ -411,9 +415,9 @@ static int sorted_file_device(const char *fn, const char *header_text, int n_con
 	if (dup_counts)
 		for (size_t i = 0; i + 1 < off.size(); ++i)
 			if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) { bmh_set_error("%s: record %zu is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL; }
+	dup_host_t dh;
 	if (off.size() > 1) {
-		dup_host_t dh;
-		RCK(to_store(&d, recs, n_bytes, off, (hipStream_t)stream, sorted, keys, soff, dup_counts ? &dh : nullptr, fn));
+		RCK(to_store(&d, recs, n_bytes, off, (hipStream_t)stream, sorted, keys, soff, dup_counts ? &dh : nullptr, fn, G));
 		const bsr_dup_t bd = {dh.tpl.data(), dh.entries.data(), (uint32_t)dh.entries.size(), dh.secsup, dh.unmapped};
 		RCK(S.append(sorted.data(), n_bytes, keys.data(), soff.data(), off.size() - 1, dup_counts ? &bd : nullptr));
 	}
@@ -426,9 +430,11 @@ static int sorted_file_device(const char *fn, const char *header_text, int n_con
 	file.append((const char *)hm, hmb); bmh_free(hm);
 	const uint64_t base = file.size();
 	bmh_bam_ws_t *ws = bmh_bam_ws_create();
-	rc = bsr_merge_device(&d, ws, S, window, level, stream, ix, sink_string, &file, dup_counts);
+	rc = bsr_merge_device(&d, ws, S, window, level, stream, ix, sink_string, &file, dup_counts, nullptr, G ? G->n_lib : 0, G ? lib_counts : nullptr);
 	bmh_bam_ws_free(ws);
 	if (rc != BMH_OK) return rc;
+	if (G && lib_counts && off.size() > 1)
+		bdp_lib_tally_host(sorted.data(), soff.data(), (uint32_t)(off.size() - 1), dh.tpl.data(), dh.entries.data(), dh.entries.size(), G->n_lib, lib_counts);
 	file.append((const char *)bmh_bgzf_eof, 28);
 	std::string ib; ix.bai(base, ib);
 	uint8_t *f = (uint8_t *)malloc(file.size() + 1), *i = (uint8_t *)malloc(ib.size() + 1);
@@ -450,4 +456,15 @@ extern "C" int bmh_bam_sorted_file_markdup_device(const char *header_text, int n
 	const char *fn = "bmh_bam_sorted_file_markdup_device";
 	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, bai, bai_bytes, counts);
+}
+
+extern "C" int bmh_bam_sorted_file_markdup_groups_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                                         int level, uint32_t window, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, void *stream, uint8_t **bam,
+                                                         uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8], uint64_t *lib_counts)
+{
+	const char *fn = "bmh_bam_sorted_file_markdup_groups_device";
+	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	bdp_table_t G;
+	RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
+	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, bai, bai_bytes, counts, &G, lib_counts);
 }

@@ -864,7 +864,8 @@ int bmh_aligner_sort_index(bmh_aligner_t *a, uint64_t base_offset, uint8_t **bai
 /* ---- Duplicate marking in sorted BAM (csrc/bam_dup_core.h, csrc/bam_dup_kernels.hip, csrc/bam_dup_host.cpp).
  * Picard MarkDuplicates' rules on templates (a single read or a read pair, its records next to each other in the writer's order): the unclipped 5' ends and
  * strands of the primary lines are the key, the sum of the base qualities >= 15 the score, ties go to the template that came first in the input; a fragment is
- * a duplicate wherever a pair has an end.  Every record of a duplicate template gets flag 0x400.  No optical duplicates, one library, nothing removed.
+ * a duplicate wherever a pair has an end.  Every record of a duplicate template gets flag 0x400.  No optical duplicates, nothing removed.  One library unless
+ * read groups are given (the _groups entry points below).
  * counts [8]: pairs examined, fragments examined, duplicate pairs, duplicate fragments, records flagged, secondary or supplementary records, unmapped records,
  * templates.
  * bmh_bam_markdup_device / _host: a record stream in the writer's order (whole records; the first begins a template; paired templates hold both primary lines --
@@ -884,6 +885,41 @@ int bmh_aligner_markdup_counts(bmh_aligner_t *a, uint64_t out[8]);
 /* where the last marked run's extra time went: [0] the decision, ms  [1] the windows' flag steps (ordinals up, flag kernel), ms  [2] bytes of ordinals and entries
  * that came down with the batches */
 int bmh_aligner_markdup_times(bmh_aligner_t *a, double out[3]);
+
+/* ---- Read groups and libraries.
+ * Duplicates per library: rg_ids [n_groups] and rg_lib [n_groups] are the run's read groups and every group's library index (0 .. 254; groups with one index are
+ * lanes of one library).  A template's library is that of the RG:Z tag on its first record; pairs are duplicates of each other, a fragment is a duplicate through a
+ * pair's end, and the best fragment stays, within one library only.  The library takes the top byte of the duplicate key, above the refID: more than 255 libraries,
+ * a refID of 2^24 or more, an empty table, an empty ID and two rows with one ID are refused (BMH_EINVAL) before anything is allocated; so is a template whose first
+ * record has no RG:Z tag or names a group the table does not hold, by the record's index.  counts [8]: the totals, as without groups.  lib_counts (or NULL)
+ * [8 * n_lib], n_lib = 1 + the largest index: the same eight per library.  Without groups (the entry points above) no tag is read.
+ * bmh_aligner_markdup_library_counts: library `lib`'s eight of the last marked run over read groups. */
+int bmh_bam_markdup_groups_device(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, void *stream, uint8_t **out,
+                                  uint64_t counts[8], uint64_t *lib_counts);
+int bmh_bam_markdup_groups_host(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, uint8_t **out, uint64_t counts[8],
+                                uint64_t *lib_counts);
+int bmh_bam_sorted_file_markdup_groups_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records,
+                                              uint64_t n_bytes, int level, uint32_t window, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, void *stream,
+                                              uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8], uint64_t *lib_counts);
+int bmh_bam_sorted_file_markdup_groups_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records,
+                                            uint64_t n_bytes, int level, uint32_t window, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
+                                            uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8], uint64_t *lib_counts);
+int bmh_aligner_markdup_library_counts(bmh_aligner_t *a, int lib, uint64_t out[8]);
+
+/* A run over several read groups: one sample's lanes and libraries into one output.  A group is a read group ID, its library index (as above) and an input as
+ * bmh_aligner_run_files takes it (path2: the mates, or NULL; a BAM's own @RG lines and RG tags stay ignored).  One loader thread walks the groups in order into the
+ * one queue of batches: the lanes are not drained between groups.  A batch never spans two groups and is cut inside its group as bmh_aligner_run_files cuts it; the
+ * read index behind the tie-break hash restarts at 0 in every group; every record carries its group's ID as RG:Z.  So group g's records are byte for byte those of
+ * bmh_aligner_run_files on its input alone by an aligner whose read group is g's, and the unsorted output is the groups' outputs in order.  Sorted output with
+ * duplicate marking decides per library; the template ordinal behind its tie-break counts on across the groups (the input order of the whole run).
+ * All groups hold pairs or none does (two files, `paired`, or a BAM whose first kept record has flag 0x1 mean pairs): a group that disagrees is refused by its ID
+ * when the loader reaches it -- the groups before it have been written by then, as with a file that ends before its mate file.  When no group has two files, paired
+ * is 0 and the first group is a BAM that holds pairs, the run takes bmh_aligner_set_bam_pairs' values as bmh_aligner_run_files does.  Refused before anything is
+ * written: n_groups < 1, an aligner created with a read group of its own (popt->rg_id), an empty ID or one beyond 255 bytes, two groups with one ID, a library
+ * index outside 0 .. 254, a path that does not exist.  Messages about a file or a read name the group's ID, and the read by its index within its group. */
+typedef struct { const char *id; int32_t library; const char *path1, *path2; } bmh_read_group_t;
+int bmh_aligner_run_groups(bmh_aligner_t *a, const bmh_read_group_t *groups, int n_groups, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes,
+                           int n_threads, bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats);
 
 #ifdef __cplusplus
 }

@@ -5,12 +5,18 @@ the merge: key sort, windows, compression, index pass, sink) --, and bam_sort al
 --runs runs with their spreads.  Writes profiles/bam_sort.json (or --out).  The read set is the bench's two batches, each twice: every read occurs twice, so the
 sorted file's size (the two copies land next to each other) and the merge's compression rate are not those of real data.
 
-    python scripts/bam_sort_rate.py [--runs 3] [--reads 1000000] [--genome-mbp 3100] [--out FILE] [--markdup]
+    python scripts/bam_sort_rate.py [--runs 3] [--reads 1000000] [--genome-mbp 3100] [--out FILE] [--markdup [--groups [--parent-json FILE]]]
 
 --markdup: the duplicate-marking leg instead (profiles/bam_markdup.json): the sorted in-memory row re-run, the same row with duplicates marked -- with the
 decision alone and the windows' flag steps alone, as the library times them (bmh_aligner_markdup_times) --, the same two rows on a paired read set (FR pairs
 of the same genome, each batch twice), and bam_markdup alone on one batch's records (walk, copies, heads, entries, decision, flags).  Every read of the set occurs twice, so half its templates are duplicates: the
 duplicate rate says nothing about real data.
+
+--markdup --groups: the read-group leg (profiles/bam_markdup_groups.json): --markdup's rows without groups (what a run paid before read groups existed:
+the opt-in path must cost nothing when it is off), the sorted rows through bmh_aligner_run_files' loader (the one a run over groups reads through), and the same reads given as 4 groups -- one file per batch -- of one library and of 4 libraries
+(bmh_aligner_run_groups; the marked rows, so the entries kernel walks the tags and the decision counts per library).  --parent-json FILE: the output of
+`--markdup` on the parent commit in the same GPU visit; its rows are kept beside this commit's and every shared row is compared: the difference of the medians
+against the larger of the two rows' own spreads.
 """
 import argparse
 import ctypes as C
@@ -41,6 +47,8 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--out", default="")
     ap.add_argument("--markdup", action="store_true")
+    ap.add_argument("--groups", action="store_true")
+    ap.add_argument("--parent-json", default="")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     L = B.load_library()
@@ -83,7 +91,7 @@ def main():
     nat = NativeAligner(dindex, pac_h, n_genome, contigs, None, co, ExtParams.default(), po, pe_o)
     result = {"genome_mbp": a.genome_mbp, "reads_per_run": n4, "setup_s": round(time.time() - t0, 1), "runs": a.runs, "host_threads": nth, "rows": {}}
 
-    def run(fmt, spill=False, keep=None, markdup=False, paired=False):
+    def run(fmt, spill=False, keep=None, markdup=False, paired=False, groups=None, files=False):
         src = ppath if paired else path
         nat.set_output(fmt, 1)
         if fmt == "bam_sorted":
@@ -99,7 +107,12 @@ def main():
         for it in range(a.runs + 1):
             nbytes[0] = 0
             t1 = time.perf_counter()
-            st = nat.run_file(src, paired, sink, batch_reads=n4 // 4, n_lanes=3 if paired else 2, n_threads=nth)
+            if groups is not None:
+                st = nat.run_groups(groups, paired, sink, batch_reads=n4 // 4, n_lanes=3 if paired else 2, n_threads=nth)
+            elif files:
+                st = nat.run_files(src, None, paired, sink, batch_reads=n4 // 4, n_lanes=3 if paired else 2, n_threads=nth)
+            else:
+                st = nat.run_file(src, paired, sink, batch_reads=n4 // 4, n_lanes=3 if paired else 2, n_threads=nth)
             if it:
                 secs.append(time.perf_counter() - t1); merge.append(st.format_seconds)
                 if markdup:
@@ -118,8 +131,49 @@ def main():
                 row["window_flags_alone"] = stats([max(t["window_flags_ms"], 1e-6) / 1e3 for t in times], n4, 1e6); row["window_flags_alone"]["unit"] = "Mrecords/s (ordinals up, flag kernel)"
                 row["window_flags_alone"]["ms"] = [round(t["window_flags_ms"], 2) for t in times]
                 row["entries_d2h_bytes_per_read"] = round(times[0]["entries_d2h_bytes"] / n4, 1)
+                if groups is not None:
+                    row["library_counts"] = [nat.markdup_library_counts(k) for k in range(1 + max(g[1] for g in groups))]
         return row
     keep = []
+    if a.markdup and a.groups:
+        result["rows"]["reads_to_bam_unsorted"] = run("bam")
+        result["rows"]["reads_to_sorted_bam_in_memory"] = run("bam_sorted")
+        result["rows"]["reads_to_sorted_bam_in_memory_markdup"] = run("bam_sorted", markdup=True)
+        result["rows"]["paired_reads_to_sorted_bam_in_memory"] = run("bam_sorted", paired=True)
+        result["rows"]["paired_reads_to_sorted_bam_in_memory_markdup"] = run("bam_sorted", markdup=True, paired=True)
+        # the group runs read through bmh_aligner_run_files' loader (windows of text cut into records on the device), the rows above through bmh_aligner_run_file's
+        # (the mapped file cut by host threads): the same file through that loader, without groups, is what the group rows compare with
+        result["rows"]["reads_to_sorted_bam_in_memory_files_loader"] = run("bam_sorted", files=True)
+        result["rows"]["reads_to_sorted_bam_in_memory_markdup_files_loader"] = run("bam_sorted", markdup=True, files=True)
+        whole = np.fromfile(path, np.uint8).reshape(4, -1)                # one file per batch: a group each
+        parts = []
+        for k in range(4):
+            parts.append(os.path.join(tmp, "g%d.fa" % k)); whole[k].tofile(parts[-1])
+        del whole
+        for what, libs in (("4_groups_1_library", (0, 0, 0, 0)), ("4_groups_4_libraries", (0, 1, 2, 3))):
+            groups = [("g%d" % k, libs[k], parts[k], None) for k in range(4)]
+            result["rows"]["reads_to_sorted_bam_in_memory_" + what] = run("bam_sorted", groups=groups)
+            result["rows"]["reads_to_sorted_bam_in_memory_markdup_" + what] = run("bam_sorted", markdup=True, groups=groups)
+        nat.set_output("sam", 1)
+        if a.parent_json:
+            with open(a.parent_json) as f:
+                parent = json.load(f)
+            result["parent_rows"] = {k: v for k, v in parent["rows"].items() if k in result["rows"]}
+            result["no_groups_vs_parent"] = {}
+            for k, pr in result["parent_rows"].items():
+                tr = result["rows"][k]
+                diff = 100 * abs(tr["median"] - pr["median"]) / pr["median"]
+                result["no_groups_vs_parent"][k] = {"difference_pct": round(diff, 1), "larger_spread_pct": max(tr["spread_pct"], pr["spread_pct"]), "within_spread": diff <= max(tr["spread_pct"], pr["spread_pct"])}
+        result["not_measured"] = ("groups of unequal size (a group's last batch is short: up to one extra short batch per group), paired groups, BAM groups, more than 4 libraries, "
+                                  "spilled runs with marking, reads with base qualities")
+        for q in parts + [path, ppath]:
+            os.remove(q)
+        os.rmdir(tmp)
+        out = a.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bam_markdup_groups.json")
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+        print(json.dumps(result))
+        return
     if a.markdup:
         from bwamem_hip.lib import bam_markdup
         result["rows"]["reads_to_bam_unsorted"] = run("bam", keep=keep)
