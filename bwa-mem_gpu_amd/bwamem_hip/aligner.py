@@ -73,6 +73,7 @@ class ReadSet:
         self.ascii, self.offs, self.lens, self.name_blob, self.name_off = ascii_, offs, lens, name_blob, name_off
         self.codes = codes                      # nt4 codes of the letters when the loader made them (bmh_reads_load_fasta), else None
         self.qual, self.comments = qual, comments
+        self.groups = None                      # bam_to_reads(read_groups=...): every read's index in that list
 
     def __len__(self):
         return len(self.lens)
@@ -156,16 +157,33 @@ def read_reads_files(path1: str, path2: str | None = None, comments: bool = Fals
         raise
 
 
-def bam_to_reads(records: bytes, comments: bool = False, host: bool = False) -> ReadSet:
+def bam_to_reads(records: bytes, comments: bool = False, host: bool = False, read_groups=None) -> ReadSet:
     """uncompressed BAM records (without the header) as the reads read_reads_files gives for the BAM file that holds them (bmh_bam_reads_device; host=True:
     bmh_bam_reads_host, no device needed): `samtools fastq`'s rules -- secondary and supplementary records skipped, reverse-strand records turned back, pairs
-    (flag 0x1) as reads 2i / 2i+1, and with comments=True the tags as the comment -C copies.  Refused records raise ValueError (lib.ReadFileError)."""
+    (flag 0x1) as reads 2i / 2i+1, and with comments=True the tags as the comment -C copies.  Refused records raise ValueError (lib.ReadFileError).
+    read_groups: a list of read group IDs -- the ReadSet's `groups` is then the index of every read's RG:Z value in that list (whole IDs compared); a kept
+    record without an RG tag, with one of another type than Z or with an ID that is not listed, and a pair whose two records name different groups are refused
+    naming the record's index.  Records skipped by their flag are not looked at."""
     from .lib import bam_reads
-    d = bam_reads(records, comments=comments, host=host)
+    d = bam_reads(records, comments=comments, host=host, read_groups=read_groups)
     if len(d["lens"]) == 0:
-        return ReadSet.from_lists([], [], comments=[] if comments else None)
+        rs = ReadSet.from_lists([], [], comments=[] if comments else None)
+        rs.groups = np.zeros(0, np.uint32) if read_groups is not None else None
+        return rs
     cm = (d["comments"], d["comment_offs"]) if d["comments"] is not None else None
-    return ReadSet(d["ascii"], d["offs"], d["lens"], d["names"], d["name_offs"], codes=d["codes"], qual=d["quals"], comments=cm)
+    rs = ReadSet(d["ascii"], d["offs"], d["lens"], d["names"], d["name_offs"], codes=d["codes"], qual=d["quals"], comments=cm)
+    rs.groups = d["groups"] if read_groups is not None else None
+    return rs
+
+
+def bam_read_groups(header_text, markdup: bool = False) -> list:
+    """the read groups of a BAM header's text (str or bytes): [(the @RG line verbatim, its ID, its library), ...] in file order -- the library by rg_library's
+    rules.  The text ends at its first NUL, the last line may lack its newline, a CR before the newline is dropped, other lines are ignored.  Raises ValueError
+    naming the line: no @RG line, a line without a non-empty ID of at most 255 bytes or whose fields are not tab-separated XX:value, a repeated ID, more than
+    65535 groups; with markdup=True also more than 255 distinct libraries."""
+    from .lib import bam_header_read_groups
+    lines, _lib = bam_header_read_groups(header_text, markdup=markdup)
+    return [(ln, next(f[3:] for f in ln.split("\t")[1:] if f.startswith("ID:")), rg_library(ln)) for ln in lines]
 
 
 def read_fasta_reads_numpy(path: str) -> ReadSet:
@@ -392,7 +410,8 @@ class Aligner:
         if max_mem_intv is not None: self.reseed.max_mem_intv = int(max_mem_intv)
 
     def header(self) -> str:
-        """the @SQ lines and the read group's line; during a run over read groups (align_groups) every group's @RG line, in group order"""
+        """the @SQ lines and the read group's line; during a run over read groups (align_groups) every group's @RG line, in group order; during a run that keeps
+        its input's read groups (align_files(keep_rg=True)) the input's @RG lines, verbatim and in file order"""
         rg = [g[0] for g in getattr(self, "_groups", None) or ()] or ([self.rg_line] if getattr(self, "rg_line", "") else [])
         return "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in self.contigs) + "".join(line + "\n" for line in rg)
 
@@ -766,15 +785,38 @@ class Aligner:
         return n
 
     def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
-                    sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None) -> int:
+                    sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None, keep_rg: bool = False) -> int:
         """align_file for the files users have (bmh_aligner_run_files): `reads` (and `mates`: the second file of a pair, which implies paired) may be
         multi-line FASTA or FASTQ, plain, gzip or BGZF, a regular file or a pipe; or `reads` alone is a BAM file (unaligned, or grouped by read name: recognised
         from its bytes, pairs from flag 0x1 of its records -- paired=True on a BAM without it is refused).  Batches are cut by align_file's rules (-t, -K, the 150 Mbase floor for
-        single-end runs), so the text equals align_file's on the single-line interleaved file of the same reads.  Returns the number of reads."""
+        single-end runs), so the text equals align_file's on the single-line interleaved file of the same reads.  Returns the number of reads.
+        keep_rg=True keeps the input's read groups: `reads` is one BAM (a regular file or a pipe), the @RG lines of its header are the run's read groups and go
+        verbatim, in file order, where -R's line goes in the output header, and every read's records carry RG:Z:<the ID its own record names> where -R's tag goes.
+        Batches are cut and reads indexed as without it, and a batch may hold reads of any number of groups.  markdup=True calls duplicates within a library (the
+        LB field, rg_library's rules): self.markdup_library_counts and markdup_metrics have a row per library.  Refused before anything is written (ValueError):
+        text input, `mates`, -R, a header without a valid @RG line (bam_read_groups' rules).  A record without an RG:Z tag, with an ID the header does not hold,
+        or a pair of two groups fails the run naming the record's index, after the batches before it were written."""
         if out is None:
             raise ValueError("align_files: out (a text or binary file object) is required")
+        if keep_rg and getattr(self, "_keep_rg", None) is None:          # the outermost call of such a run: the refusals, and the state that lasts as long as it
+            if mates is not None:
+                raise ValueError("align_files: keep_rg=True and a mates file: a run that keeps its input's read groups takes one BAM file")
+            if getattr(self, "rg_line", ""):
+                raise ValueError("align_files: keep_rg=True and -R is set: the read groups come from the input's header or from -R, not both")
+            if os.environ.get("BMH_ALIGNER_NATIVE", "1") == "0" or self.profile:
+                raise NotImplementedError("keep_rg=True needs the native pipeline (BMH_ALIGNER_NATIVE=0 and profile runs write batch after batch)")
+            self._keep_rg = True
+            try:
+                return self.align_files(reads, None, out=out, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads, fmt=fmt, level=level, sort=sort, index=index,
+                                        sort_mem=sort_mem, sort_tmp=sort_tmp, sort_window=sort_window, markdup=markdup, markdup_metrics=markdup_metrics, keep_rg=True)
+            finally:
+                self._keep_rg = None
+                self._groups = None
+                nat = getattr(self, "_native", None)
+                if nat is not None:
+                    nat.set_keep_rg(False)
         if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None:
-            return self._align_bam(lambda o: self.align_files(reads, mates, out=o, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads), out, fmt, level,
+            return self._align_bam(lambda o: self.align_files(reads, mates, out=o, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads, keep_rg=keep_rg), out, fmt, level,
                                    sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics)
         binary = "b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")
         paired = bool(paired or mates is not None)
@@ -784,8 +826,16 @@ class Aligner:
             if not paired and not chunk_bases:
                 cb = max(cb, 150_000_000)                 # (single-end records do not depend on the cuts: align_file)
             cb = min(cb, (1 << 31) - 1024)
-        out.write(self.header().encode() if binary else self.header())
         nat = self._native_aligner()
+        if keep_rg:
+            # the header waits for the input's: the library calls back once it has read the BAM's header whole -- before the first record -- and the @RG lines go
+            # into ours there (header() reads self._groups); a refused input has written nothing by then
+            def rg_header(lines, _libs):
+                self._groups = [(ln, next(f[3:] for f in ln.split("\t")[1:] if f.startswith("ID:")), None, None) for ln in lines]
+                out.write(self.header().encode() if binary else self.header())
+            nat.set_keep_rg(True, rg_header)
+        else:
+            out.write(self.header().encode() if binary else self.header())
         # (a BAM says itself whether it holds pairs, once the library has opened it: the batch size and lanes of a paired run, for that case)
         cb_pairs = 0 if batch_reads > 0 else min(chunk_bases or int(getattr(self, "ref_chunk_bases", 0)) or 10_000_000 * max(1, int(getattr(self, "ref_threads", 1))), (1 << 31) - 1024)
         nat.set_bam_pairs(cb_pairs, int(os.environ.get("BMH_ALIGNER_LANES", "3")))
@@ -803,7 +853,7 @@ class Aligner:
                      sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None) -> int:
         """several read groups -- a sample's lanes and libraries -- into one output (bmh_aligner_run_groups).  groups: [(rg_line, reads, mates or None), ...]; every
         rg_line is unescaped and checked as -R's value is, reads / mates are what align_files takes (one file or R1 + R2; plain, gzip or BGZF; FASTA or FASTQ; or
-        one BAM, whose own @RG lines and RG tags stay ignored).  Group g's records are byte for byte those of align_files(reads_g, mates_g) alone under -R rg_g, and
+        one BAM, whose own @RG lines and RG tags stay ignored: align_files(keep_rg=True) is the run that keeps them, and the two do not combine).  Group g's records are byte for byte those of align_files(reads_g, mates_g) alone under -R rg_g, and
         the unsorted output is the groups' outputs in order; the header holds every @RG line.  All groups hold pairs or none does (paired applies to every group).
         markdup=True calls duplicates within a library only (a group's library is its LB field; groups without one share "Unknown Library"):
         self.markdup_library_counts holds the counts per library, markdup_metrics one row per library.  Needs the native pipeline; -R must not be set.

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "bmh_bam_markdup_device", "bmh_bam_markdup_host", "bmh_bam_sorted_file_markdup_device", "bmh_bam_sorted_file_markdup_host", "bmh_aligner_set_markdup", "bmh_aligner_markdup_counts", "bmh_aligner_markdup_times",
     "bmh_bam_markdup_groups_device", "bmh_bam_markdup_groups_host", "bmh_bam_sorted_file_markdup_groups_device", "bmh_bam_sorted_file_markdup_groups_host",
     "bmh_aligner_markdup_library_counts", "bmh_aligner_run_groups",
+    "bmh_bam_reads_groups_device", "bmh_bam_reads_groups_host", "bmh_bam_header_read_groups", "bmh_format_sam_groups", "bmh_aligner_set_keep_rg",
 ]
 
 
@@ -53,14 +54,26 @@ class SamDev(C.Structure):
     _fields_ = [("n_reads", C.c_uint32), ("d_names", C.c_void_p), ("d_name_off", C.c_void_p), ("d_reads", C.c_void_p), ("d_offs", C.c_void_p), ("d_lens", C.c_void_p),
                 ("n_contigs", C.c_int), ("d_contig_names", C.c_void_p), ("d_contig_name_off", C.c_void_p), ("d_contig_offset", C.c_void_p),
                 ("d_fin", C.c_void_p), ("d_fin_per_read", C.c_void_p), ("d_slot", C.c_void_p), ("d_aln", C.c_void_p), ("d_cig_off", C.c_void_p), ("d_packed", C.c_void_p),
-                ("d_h_rec", C.c_void_p), ("d_unflag", C.c_void_p), ("d_quals", C.c_void_p), ("d_comments", C.c_void_p), ("d_comment_off", C.c_void_p)]
+                ("d_h_rec", C.c_void_p), ("d_unflag", C.c_void_p), ("d_quals", C.c_void_p), ("d_comments", C.c_void_p), ("d_comment_off", C.c_void_p),
+                ("d_read_group", C.c_void_p), ("d_rg_ids", C.c_void_p), ("d_rg_id_off", C.c_void_p), ("n_rg", C.c_uint32)]
+
+
+class ReadGroupsT(C.Structure):
+    """bmh_read_groups_t: a read group per read for bmh_format_sam_groups"""
+    _fields_ = [("read_group", C.c_void_p), ("ids", C.c_void_p), ("id_off", C.c_void_p), ("n_groups", C.c_uint32)]
+
+
+def _rg_id_table(ids):
+    """read group IDs -> (the IDs back to back as a uint8 array, their offsets [n + 1] as uint32): the table bmh_read_groups_t and bmh_sam_dev_t take"""
+    enc = [(i if isinstance(i, bytes) else str(i).encode()) for i in ids]
+    return np.frombuffer(b"".join(enc) or b"\0", dtype=np.uint8).copy(), np.concatenate([[0], np.cumsum([len(e) for e in enc])]).astype(np.uint32)
 
 
 class ReadSetT(C.Structure):
     """bmh_read_set_t"""
     _fields_ = [("n_reads", C.c_uint64), ("n_bases", C.c_uint64), ("n_name_bytes", C.c_uint64), ("ascii", C.c_void_p), ("codes", C.c_void_p),
                 ("offs", C.c_void_p), ("lens", C.c_void_p), ("names", C.c_void_p), ("name_offs", C.c_void_p),
-                ("quals", C.c_void_p), ("comments", C.c_void_p), ("comment_offs", C.c_void_p), ("n_comment_bytes", C.c_uint64)]
+                ("quals", C.c_void_p), ("comments", C.c_void_p), ("comment_offs", C.c_void_p), ("n_comment_bytes", C.c_uint64), ("groups", C.c_void_p)]
 
 
 class _ReadSetOwner:
@@ -518,15 +531,44 @@ def reads_last_bam_counts() -> dict:
     return dict(records_skipped=int(out[0]), tags_left_out=int(out[1]))
 
 
-def bam_reads(records: bytes, comments: bool = False, host: bool = False) -> dict:
+def bam_header_read_groups(text, markdup: bool = False) -> tuple:
+    """bmh_bam_header_read_groups: the @RG lines of a BAM header's text (bytes or str) -> (the lines verbatim, every line's library index by first appearance).
+    The text ends at its first NUL, the last line may lack its newline, CR LF is accepted and other lines are ignored.  Raises ValueError naming the line: no
+    @RG line, a line without a non-empty ID of at most 255 bytes or with a field that is not XX:value, a repeated ID, more than 65535 groups, and with
+    markdup=True more than 255 libraries."""
+    L = load_library()
+    text = text.encode() if isinstance(text, str) else bytes(text)
+    L.bmh_free.argtypes = [C.c_void_p]
+    lines, lib, nb, ng = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_int32()
+    L.bmh_bam_header_read_groups.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]
+    rc = L.bmh_bam_header_read_groups(text, len(text), 1 if markdup else 0, C.byref(lines), C.byref(nb), C.byref(lib), C.byref(ng))
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)(_err(L))
+    try:
+        return C.string_at(lines.value, nb.value).decode("latin-1").split("\n")[:-1], [int(v) for v in (C.c_int32 * ng.value).from_address(lib.value)]
+    finally:
+        L.bmh_free(lines); L.bmh_free(lib)
+
+
+def bam_reads(records: bytes, comments: bool = False, host: bool = False, read_groups=None) -> dict:
     """bmh_bam_reads_device (host=True: bmh_bam_reads_host, no device needed): uncompressed BAM records, without the header, as load_reads_files gives a file's
-    reads -- `samtools fastq`'s rules (include/bwamem_hip.h).  Refused records raise ReadFileError naming the record's index."""
+    reads -- `samtools fastq`'s rules (include/bwamem_hip.h).  Refused records raise ReadFileError naming the record's index.
+    read_groups: a list of read group IDs (bmh_bam_reads_groups_*) -- the result gains "groups", the index of every read's RG:Z value in that list; a kept record
+    without the tag, with an RG tag of another type or an ID that is not listed, and a pair of two groups are refused the same way."""
     L = load_library()
     records = bytes(records)
     rs = ReadSetT()
+    L.bmh_reads_free.argtypes = [C.POINTER(ReadSetT)]
+    if read_groups is not None:
+        ids = (C.c_char_p * max(len(read_groups), 1))(*[(i if isinstance(i, bytes) else str(i).encode()) for i in read_groups])
+        fn = L.bmh_bam_reads_groups_host if host else L.bmh_bam_reads_groups_device
+        fn.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(ReadSetT)]
+        if fn(records, len(records), READS_COMMENTS if comments else 0, ids, len(read_groups), C.byref(rs)) != 0:
+            msg = _err(L)
+            raise ReadFileError(msg) if msg.startswith("reads file") else ValueError("bmh_bam_reads: " + msg)
+        return _read_set_dict(L, rs)
     fn = L.bmh_bam_reads_host if host else L.bmh_bam_reads_device
     fn.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(ReadSetT)]
-    L.bmh_reads_free.argtypes = [C.POINTER(ReadSetT)]
     if fn(records, len(records), READS_COMMENTS if comments else 0, C.byref(rs)) != 0:
         msg = _err(L)
         raise ReadFileError(msg) if msg.startswith("reads file") else RuntimeError("bmh_bam_reads: " + msg)
@@ -548,7 +590,8 @@ def _read_set_dict(L, rs) -> dict:
                 lens=arr(rs.lens, rs.n_reads, np.uint32), names=arr(rs.names, rs.n_name_bytes, np.uint8), name_offs=arr(rs.name_offs, rs.n_reads, np.uint64),
                 quals=arr(rs.quals, rs.n_bases, np.uint8) if rs.quals else None,
                 comments=arr(rs.comments, rs.n_comment_bytes, np.uint8) if rs.comments else None,
-                comment_offs=arr(rs.comment_offs, rs.n_reads, np.uint64) if rs.comments else None)
+                comment_offs=arr(rs.comment_offs, rs.n_reads, np.uint64) if rs.comments else None,
+                groups=arr(rs.groups, rs.n_reads, np.uint32) if rs.groups else None)
 
 
 def load_reads_files(path1: str, path2: str | None = None, comments: bool = False, host: bool = False, n_threads: int = 0) -> dict:
@@ -585,6 +628,7 @@ class AlignStats(C.Structure):
 
 
 SAM_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
+RG_HEADER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_int32))
 
 
 class NativeAligner:
@@ -755,10 +799,34 @@ class NativeAligner:
         if L.bmh_aligner_set_bam_pairs(self.handle, int(batch_bases), int(n_lanes)) != 0:
             raise ValueError("bmh_aligner_set_bam_pairs: " + _err(L))
 
+    def set_keep_rg(self, on: bool, header=None) -> None:
+        """bmh_aligner_set_keep_rg: run_files keeps the read groups of its input, one BAM.  header(lines, libraries) -- the @RG lines verbatim and every line's
+        library index -- is called once the input's header has been read, before write() receives anything; an exception it raises ends the run and is raised
+        again by run_files"""
+        L = load_library()
+        self._rg_err = []
+
+        def cb(_user, ptr, n, ng, lib):
+            try:
+                header(C.string_at(ptr, n).decode("latin-1").split("\n")[:-1], [int(lib[k]) for k in range(ng)])
+                return 0
+            except BaseException as e:                      # noqa: BLE001 -- reported after the run
+                self._rg_err.append(e)
+                return 1
+        self._rg_cb = RG_HEADER(cb) if on and header is not None else C.cast(None, RG_HEADER)      # (kept alive while the aligner may call it)
+        L.bmh_aligner_set_keep_rg.argtypes = [C.c_void_p, C.c_int, RG_HEADER, C.c_void_p]
+        if L.bmh_aligner_set_keep_rg(self.handle, 1 if on else 0, self._rg_cb, None) != 0:
+            raise ValueError("bmh_aligner_set_keep_rg: " + _err(L))
+
     def run_files(self, path1: str, path2: str | None, paired: bool, write, batch_bases: int = 0, batch_reads: int = 0, n_lanes: int = 2, n_threads: int = 0) -> "AlignStats":
         """bmh_aligner_run_files: run_file for one or two read files of any shape (multi-line records, gzip / BGZF, pipes; path2: the mates)"""
-        return self._run("bmh_aligner_run_files", (os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, int(batch_bases), int(batch_reads),
-                                                   1 if paired else 0, int(n_lanes), int(n_threads)), write, read_errors=("FASTQ:", "reads file"))
+        try:
+            return self._run("bmh_aligner_run_files", (os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, int(batch_bases), int(batch_reads),
+                                                       1 if paired else 0, int(n_lanes), int(n_threads)), write, read_errors=("FASTQ:", "reads file", "bmh_aligner_run_files: the input's read groups"))
+        except Exception:
+            if getattr(self, "_rg_err", None):              # the header callback's own exception, not the library's account of it
+                raise self._rg_err.pop()
+            raise
 
     def run_groups(self, groups, paired: bool, write, batch_bases: int = 0, batch_reads: int = 0, n_lanes: int = 2, n_threads: int = 0) -> "AlignStats":
         """bmh_aligner_run_groups: run_files over several read groups in one run -- groups: [(id, library index, path1, path2 or None)]; every batch's records
@@ -1002,6 +1070,10 @@ def load_library() -> C.CDLL:
     L.bmh_format_sam_pe_ex.argtypes = [C.POINTER(PostOpt), C.c_uint32, C.c_void_p, _u64p, _u8p, _u64p, _u32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                        C.POINTER(C.c_char_p), C.c_void_p, _i32p, _u32p, _i32p, _i32p, C.c_void_p, _i32p, _u32p, C.c_int, C.c_void_p, C.c_int,
                                        C.POINTER(C.c_size_t)]
+    L.bmh_format_sam_groups.restype = C.c_void_p
+    L.bmh_format_sam_groups.argtypes = [C.POINTER(PostOpt), C.c_uint32, C.c_void_p, _u64p, _u8p, _u64p, _u32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.POINTER(C.c_char_p), C.c_void_p, _i32p, _u32p, C.c_void_p, C.c_void_p, C.c_void_p, _i32p, _u32p, C.c_int, C.c_void_p, C.c_int,
+                                        C.POINTER(ReadGroupsT), C.POINTER(C.c_size_t)]
     L.bmh_merge_regs.restype = C.c_int
     L.bmh_merge_regs.argtypes = [C.c_void_p, _i32p, _i32p]
     L.bmh_chain_ws_create.restype = C.c_void_p
@@ -1345,7 +1417,7 @@ def cigar_pack(aln_t, cigar_t, md_t=None, stream: int = 0):
 
 
 def sam_text_device(po: "PostOpt", names, reads_t, offs_t, lens_t, contigs, fin_t, fin_per_read_t, slot_t, aln_t, cig_off_t, packed_t, h_rec_t=None, unflag_t=None,
-                    stream: int = 0, quals_t=None, comments=None) -> bytes:
+                    stream: int = 0, quals_t=None, comments=None, read_groups=None) -> bytes:
     """bmh_sam_text_sizes + bmh_sam_text_write on torch CUDA tensors: the SAM text of a batch written on the device.  names: list of str;
     contigs: list of (name, length); reads_t / offs_t / lens_t: the batch's ASCII reads; the rest as sam_select_device / cigar_batch / cigar_pack
     left them.  quals_t: the qualities at offs_t (QUAL); comments: list of str (written with po.copy_comment).  Returns the text as bytes."""
@@ -1370,6 +1442,11 @@ def sam_text_device(po: "PostOpt", names, reads_t, offs_t, lens_t, contigs, fin_
         cmblob = torch.from_numpy(np.frombuffer(b"".join(cm) or b"\0", dtype=np.uint8).copy()).to(dev)
         cmoff = torch.from_numpy(np.concatenate([[0], np.cumsum([len(e) for e in cm])]).astype(np.int64)).to(dev)
         d.d_comments, d.d_comment_off = cmblob.data_ptr(), cmoff.data_ptr()
+    if read_groups is not None:                             # (ids, group index per read): a read group per read (po.rg_id must be unset)
+        gb, go = _rg_id_table(read_groups[0])
+        gb_t, go_t = torch.from_numpy(gb).to(dev), torch.from_numpy(go.astype(np.int32)).to(dev)
+        gr_t = torch.from_numpy(np.ascontiguousarray(read_groups[1], dtype=np.uint32).astype(np.int32)).to(dev)
+        d.d_read_group, d.d_rg_ids, d.d_rg_id_off, d.n_rg = gr_t.data_ptr(), gb_t.data_ptr(), go_t.data_ptr(), len(read_groups[0])
     wb = int(L.bmh_sam_text_work(n))
     work = torch.empty(wb, dtype=torch.uint8, device=dev)
     toff = torch.empty(n + 2, dtype=torch.int64, device=dev)
@@ -1453,7 +1530,7 @@ def finalize_pairs(copt, ep, po, genome_len: int, pac: np.ndarray, reads_flat: n
 
 def format_sam(po: "PostOpt", names, reads_flat: np.ndarray, read_offs: np.ndarray, read_lens: np.ndarray, contigs, fin: np.ndarray,
                fin_per_read: np.ndarray, slot: np.ndarray, aln: np.ndarray, cigar: np.ndarray, md: np.ndarray, h_rec=None, unflag=None,
-               as_bytes: bool = False, quals=None, comments=None):
+               as_bytes: bool = False, quals=None, comments=None, read_groups=None):
     """bmh_format_sam (or bmh_format_sam_pe when h_rec / unflag are given) on numpy arrays; contigs = list of (name, length).
     names: list of str, or (blob uint8 array of NUL-terminated names, uint64 offsets).  Returns the text as bytes if
     as_bytes, as a uint8 array over the library's own buffer if as_bytes == "view", else as str.  quals: the qualities at read_offs (QUAL; None:
@@ -1472,7 +1549,18 @@ def format_sam(po: "PostOpt", names, reads_flat: np.ndarray, read_offs: np.ndarr
     keep = [a(reads_flat, np.uint8), a(read_offs, np.uint64), a(read_lens, np.uint32), a(fin, np.int32), a(fin_per_read, np.uint32), a(slot, np.int64),
             a(aln, np.int32), a(cigar, np.uint32), a(md, np.uint8)]
     ln = C.c_size_t()
-    if quals is not None or comments is not None:
+    if read_groups is not None:                             # (ids, group index per read): bmh_format_sam_groups -- a read group per read (po.rg_id must be unset)
+        vp = lambda x: x.ctypes.data_as(C.c_void_p) if x is not None else None
+        qq = a(quals, np.uint8) if quals is not None else None
+        cb, co = (a(comments[0], np.uint8), a(comments[1], np.uint64)) if comments is not None else (None, None)
+        hh, uu = (a(h_rec, np.int32), a(unflag, np.int32)) if h_rec is not None else (None, None)
+        gb, go = _rg_id_table(read_groups[0])
+        gr = a(read_groups[1], np.uint32)
+        G = ReadGroupsT(gr.ctypes.data, gb.ctypes.data, go.ctypes.data, len(read_groups[0]))
+        p = L.bmh_format_sam_groups(C.byref(po), len(read_lens), vp(nblob), _np_ptr(noff, _u64p), _np_ptr(keep[0], _u8p), _np_ptr(keep[1], _u64p), _np_ptr(keep[2], _u32p),
+                                    vp(qq), vp(cb), vp(co), len(contigs), cn, vp(off), _np_ptr(keep[3], _i32p), _np_ptr(keep[4], _u32p), vp(hh), vp(uu), vp(keep[5]),
+                                    _np_ptr(keep[6], _i32p), _np_ptr(keep[7], _u32p), int(keep[7].shape[1]), vp(keep[8]), int(keep[8].shape[1]), C.byref(G), C.byref(ln))
+    elif quals is not None or comments is not None:
         qq = a(quals, np.uint8) if quals is not None else None
         cb, co = (a(comments[0], np.uint8), a(comments[1], np.uint64)) if comments is not None else (None, None)
         ex = (qq.ctypes.data_as(C.c_void_p) if qq is not None else None, cb.ctypes.data_as(C.c_void_p) if cb is not None else None,

@@ -17,8 +17,10 @@ qualities >= 15 the score, ties go to the template that came first in the input,
 library-size estimate, nothing is removed) and --markdup-metrics PATH (a Picard-style table of the counts, one row per library).  --rg LINE opens a read group:
 LINE is an @RG line as -R takes it, and the one or two files that follow it, up to the next --rg, are that group's input (Aligner.align_groups): a sample's lanes
 and libraries go into one output, every record with its group's RG:Z, the header with every @RG line, and --markdup calls duplicates within a library (the LB
-field; groups with one LB are lanes of one library) only.  -p applies to every group; --rg and -R exclude each other.  An option that is not on that list is
-refused by name.  Two input files imply pairs.  One plain, regular file is offered to Aligner.align_file first, which takes it when every
+field; groups with one LB are lanes of one library) only.  -p applies to every group; --rg and -R exclude each other.  --keep-rg keeps the read groups of the
+input, one BAM file (Aligner.align_files(keep_rg=True)): the @RG lines of its header go into the output's header verbatim, every read's records carry the RG:Z of
+the read's own record, and --markdup calls duplicates within a library; it is refused on text input, with a mates file, and beside -R or --rg.  An option that is
+not on that list is refused by name.  Two input files imply pairs.  One plain, regular file is offered to Aligner.align_file first, which takes it when every
 record has one sequence line (its own counting pass decides, before anything is written); every other input goes through
 Aligner.align_files; the text is the same.  A refused file ends the command with status 1 and the library's message on stderr.
 """
@@ -49,6 +51,7 @@ def main(argv=None) -> int:
     bam, bam_level = False, 1
     sort, index_path, sort_mem, sort_tmp = False, None, None, None
     markdup, metrics_path = False, None
+    keep_rg = False
     groups = []                                                     # --rg LINE: [line, files...]; the positionals behind it are its files
     i = 0
     while i < len(argv):
@@ -69,6 +72,8 @@ def main(argv=None) -> int:
             sort = bam = True
         elif a == "--markdup":
             markdup = True
+        elif a == "--keep-rg":
+            keep_rg = True
         elif a == "--rg":
             if i + 1 >= len(argv):
                 print("[bwamem_hip.mem] option --rg needs a value", file=sys.stderr)
@@ -111,6 +116,9 @@ def main(argv=None) -> int:
         else:
             pos.append(a)
         i += 1
+    if keep_rg and (groups or "-R" in opts):
+        print("[bwamem_hip.mem] --keep-rg excludes --rg and -R: the read groups come from the input BAM's own header and tags, or from the command line, not both", file=sys.stderr)
+        return 2
     if groups:
         if "-R" in opts:
             print("[bwamem_hip.mem] --rg and -R exclude each other: with --rg every group brings its own @RG line", file=sys.stderr)
@@ -159,7 +167,7 @@ def main(argv=None) -> int:
         if groups:
             al.align_groups([(g[0], g[1], g[2] if len(g) == 3 else None) for g in groups], out=out, paired=interleaved, **fmt_kw)
             done = True
-        elif mates is None and _plain_regular(reads):
+        elif mates is None and _plain_regular(reads) and not keep_rg:
             from .lib import ReadFileError
             try:
                 al.align_file(reads, out, paired=paired, **fmt_kw)
@@ -167,7 +175,7 @@ def main(argv=None) -> int:
             except ReadFileError:                                    # (its counting pass refused the layout: nothing has been written)
                 pass
         if not done:
-            al.align_files(reads, mates, out=out, paired=paired, **fmt_kw)
+            al.align_files(reads, mates, out=out, paired=paired, **fmt_kw, **(dict(keep_rg=True) if keep_rg else {}))
         out.flush()
     except (ValueError, NotImplementedError) as e:
         print(f"[bwamem_hip.mem] {e}", file=sys.stderr)

@@ -57,6 +57,10 @@ struct aligner_t {
 	// the serial changes whenever the table does, so a lane knows whether its copy on the device is the run's
 	std::vector<std::string> group_ids; bdp_table_t groups; uint64_t groups_serial = 0;
 	const char *rg_of(int group) const { return group >= 0 && (size_t)group < group_ids.size() ? group_ids[(size_t)group].c_str() : po.rg_id; }
+	// a run that keeps its input's read groups (bmh_aligner_set_keep_rg), while it lasts: the same table holds the header's @RG lines, but the group is a property of
+	// a read (rs.groups), not of a batch -- a batch's group stays -1 and its records take their IDs from the table by the read's index
+	bool per_read = false;
+	bmh_read_groups_t read_groups(const uint32_t *read_group) const { return {read_group, groups.ids.data(), groups.id_off.data(), (uint32_t)groups.lib.size()}; }
 };
 
 }   // namespace
@@ -102,6 +106,7 @@ struct result_t {
 	hbuf_t<int32_t> fin, aln, slot32; hbuf_t<uint32_t> opr, off, packed;
 	hbuf_t<char> text; uint64_t text_len = 0; bool has_text = false;     // the text written on the device (no formatting on the host)
 	hbuf_t<uint64_t> skeys, soff; uint32_t n_rec = 0;                   // sorted BAM: text holds the batch's records in order; their keys and offsets [n_rec + 1]
+	hbuf_t<uint32_t> lib3;                                             // ... of a batch that mixes libraries (aligner_t::per_read): its counts per library [3 * libraries]
 	hbuf_t<uint32_t> stpl; hbuf_t<bdp_entry_t> dup_e; uint32_t dup_info[BDP_INFO_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0}; uint64_t dup_d2h = 0;      // duplicate marking: the records' template ordinals in that order, the templates' entries, bdp_batch_device's info
 	std::vector<int64_t> slot;                   // (host selection only; empty: slot32)
 	std::vector<int32_t> h_rec, unflag;          // pairs
@@ -123,6 +128,8 @@ struct lane_t {
 	// a FASTQ batch: its qualities (at the letters' offsets) and, with -C, its comments -- staged and sent only when the read set carries them
 	dbuf_t<uint8_t> d_quals; dbuf_t<char> d_comments; dbuf_t<uint64_t> d_comment_off; hbuf_t<uint8_t> h_quals; hbuf_t<char> h_comments; hbuf_t<uint64_t> h_comment_off;
 	bool has_quals = false, has_comments = false;
+	// a run that keeps its input's read groups: every read's group beside the lengths, and the table of IDs (sent when the run's serial changes)
+	dbuf_t<uint32_t> d_rgrp, d_rg_off; dbuf_t<char> d_rg_ids; uint64_t rg_serial = 0; bool has_rgrp = false;
 	double t[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // h2d, seed, chain+extend+merge, tail, select, cigar + d2h, wait at the gate
 	// the copies themselves, timed by events on the lane's stream (what t[0] and t[5] are NOT: those are host clocks around the whole stage -- the staging of the
 	// letters, offsets and names on host threads / the CIGAR and text kernels the host waits for): [0] reads, offsets, names H2D  [1] SAM text D2H
@@ -233,6 +240,7 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 	d.d_h_rec = paired ? Ln.d_hrec.p : nullptr; d.d_unflag = paired ? Ln.d_unflag.p : nullptr;
 	if (Ln.has_quals) d.d_quals = Ln.d_quals.p;
 	if (Ln.has_comments) { d.d_comments = Ln.d_comments.p; d.d_comment_off = Ln.d_comment_off.p; }
+	if (Ln.has_rgrp) { d.d_read_group = Ln.d_rgrp.p; d.d_rg_ids = Ln.d_rg_ids.p; d.d_rg_id_off = Ln.d_rg_off.p; d.n_rg = (uint32_t)A.groups.lib.size(); }
 	const size_t wb = bmh_sam_text_work(n);
 	RCK(Ln.d_work.need(wb)); RCK(Ln.d_text_off.need((size_t)n + 2));
 	const int64_t total = bmh_sam_text_sizes(&po, &d, Ln.d_text_off.p, Ln.d_work.p, Ln.d_work.cap, Ln.st);
@@ -255,13 +263,17 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 			const uint8_t *ds = nullptr; const uint64_t *dk = nullptr, *dso = nullptr;
 			const uint32_t nrec = bo.n_records;
 			// duplicate marking: on the records in the writer's order, before the sort -- heads, their scan, one entry per template; the ordinals follow the records
-			const uint32_t *d_tpl = nullptr, *d_info = nullptr, *d_stpl = nullptr; const bdp_entry_t *d_e = nullptr;
+			const uint32_t *d_tpl = nullptr, *d_info = nullptr, *d_stpl = nullptr, *d_lib3 = nullptr; const bdp_entry_t *d_e = nullptr;
 			const uint32_t tmax = paired ? n / 2 : n;                   // the batch's templates: every read or pair leaves at least one record, so no more entries than this come down
 			if (A.markdup) {
 				if (!Ln.bdp && !(Ln.bdp = bdp_dev_create())) return BMH_ENOMEM;
 				if (Ln.groups_serial != A.groups_serial) { RCK(bdp_dev_set_groups(Ln.bdp, &A.groups, Ln.st)); Ln.groups_serial = A.groups_serial; }
 				RCK(bdp_batch_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &d_tpl, &d_e, &d_info));
 				RCK(R.stpl.need((size_t)nrec + 1)); RCK(R.dup_e.need((size_t)std::min(nrec, tmax) + 1));
+				if (A.per_read) {                                     // a batch of several libraries: its counts per library, from the entries' library bytes
+					RCK(bdp_batch_lib_counts_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, A.groups.n_lib, Ln.st, &d_lib3));
+					RCK(R.lib3.need(3 * (size_t)A.groups.n_lib));
+				}
 			}
 			RCK(bsr_sort_run_device(Ln.bsr, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &ds, &dk, &dso, d_tpl, &d_stpl));
 			RCK(R.text.need((size_t)bo.bam_bytes + 1)); RCK(R.skeys.need((size_t)nrec + 1)); RCK(R.soff.need((size_t)nrec + 2));
@@ -276,7 +288,8 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 				if (ne) HIPCK(hipMemcpyAsync(R.dup_e.p, d_e, sizeof(bdp_entry_t) * ne, hipMemcpyDeviceToHost, Ln.st));
 				const size_t ni = A.groups.empty() ? 16 : 4 * BDP_INFO_WORDS;      // (with read groups: the words of a template without a known group)
 				HIPCK(hipMemcpyAsync(R.dup_info, d_info, ni, hipMemcpyDeviceToHost, Ln.st));
-				R.dup_d2h = 4ull * nrec + sizeof(bdp_entry_t) * ne + ni;
+				if (d_lib3) HIPCK(hipMemcpyAsync(R.lib3.p, d_lib3, 12 * (size_t)A.groups.n_lib, hipMemcpyDeviceToHost, Ln.st));
+				R.dup_d2h = 4ull * nrec + sizeof(bdp_entry_t) * ne + ni + (d_lib3 ? 12ull * A.groups.n_lib : 0);
 				Ln.copy_bytes[1] += R.dup_d2h;
 			}
 			HIPCK(hipEventRecord(Ln.ev_c[3], Ln.st));
@@ -582,6 +595,23 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 		h2d_bytes += nb;
 	}
 	if (Ln.has_comments) RCK(send_blob(rs.comments, rs.comment_offs, rs.n_comment_bytes, Ln.h_comments, Ln.h_comment_off, Ln.d_comments, Ln.d_comment_off));
+	// a run that keeps its input's read groups: every read's group goes up with the batch, like the comment offsets; the table of IDs once per run and lane
+	Ln.has_rgrp = false;
+	if (A.per_read) {
+		if (!rs.groups) { bmh_set_error("bmh_aligner_run: internal error: a run that keeps read groups met a batch without them"); return BMH_EINVAL; }
+		if (text_dev) {
+			if (Ln.rg_serial != A.groups_serial) {
+				RCK(Ln.d_rg_ids.need(A.groups.ids.size() + 1)); RCK(Ln.d_rg_off.need(A.groups.id_off.size()));
+				HIPCK(hipMemcpyAsync(Ln.d_rg_ids.p, A.groups.ids.data(), A.groups.ids.size(), hipMemcpyHostToDevice, Ln.st));
+				HIPCK(hipMemcpyAsync(Ln.d_rg_off.p, A.groups.id_off.data(), 4 * A.groups.id_off.size(), hipMemcpyHostToDevice, Ln.st));
+				Ln.rg_serial = A.groups_serial;                       // (the aligner's table outlives the run's batches: the copy reads it in its own time)
+			}
+			RCK(Ln.d_rgrp.need(n + 1));
+			HIPCK(hipMemcpyAsync(Ln.d_rgrp.p, rs.groups + b0, 4 * (size_t)n, hipMemcpyHostToDevice, Ln.st));
+			h2d_bytes += 4 * (uint64_t)n;
+			Ln.has_rgrp = true;
+		}
+	}
 	HIPCK(hipEventRecord(Ln.ev_c[1], Ln.st));
 	Ln.copy_bytes[0] += h2d_bytes;
 	// ---- seeding
@@ -798,10 +828,11 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 struct fbatch_t {
 	hbuf_t<uint8_t> ascii, codes, names; hbuf_t<uint64_t> offs, name_offs; hbuf_t<uint32_t> lens;
 	hbuf_t<uint8_t> quals, comments; hbuf_t<uint64_t> comment_offs;        // a FASTQ file's qualities; -C: the comments
+	hbuf_t<uint32_t> groups;                                               // a BAM whose read groups are kept: every read's
 	bmh_read_set_t rs; uint32_t index = 0; int64_t id0 = 0; int group = -1;        // (id0: the first read's index in its file or group; group: of a run over read groups)
 	// room for a batch of nr reads, nb bases, nn bytes of names (fq: with qualities; cm: with ncm bytes of comments), and o's pointers into it.  The nt4 codes always:
 	// every host form reads them (pairs' walks, ALT reads, a batch the device tail refuses, the host formatter)
-	int size(const char *fn, uint64_t nr, uint64_t nb, uint64_t nn, uint64_t ncm, bool fq, bool cm, bmh_read_set_t *o)
+	int size(const char *fn, uint64_t nr, uint64_t nb, uint64_t nn, uint64_t ncm, bool fq, bool cm, bmh_read_set_t *o, bool rg = false)
 	{
 		if (nb >> 31) { bmh_set_error("%s: a batch holds 2^31 bases or more", fn); return BMH_EINVAL; }      // offsets inside a batch are 32-bit
 		RCK(ascii.need(nb + 16)); RCK(codes.need(nb + 16)); RCK(names.need(nn + 16)); RCK(offs.need(nr + 2)); RCK(name_offs.need(nr + 2)); RCK(lens.need(nr + 2));
@@ -810,6 +841,7 @@ struct fbatch_t {
 		o->ascii = ascii.p; o->codes = codes.p; o->names = names.p; o->offs = offs.p; o->name_offs = name_offs.p; o->lens = lens.p;
 		if (fq) o->quals = quals.p;
 		if (cm) { o->comments = comments.p; o->comment_offs = comment_offs.p; }
+		if (rg) { RCK(groups.need(nr + 2)); o->groups = groups.p; }
 		return BMH_OK;
 	}
 };
@@ -846,6 +878,7 @@ struct bmh_aligner {
 	int dev = -1;
 	uint64_t host_tail_batches = 0;                      // of the last run (bmh_aligner_host_tail_batches)
 	uint64_t bam_pairs_bases = 0; int bam_pairs_lanes = 0;   // bmh_aligner_set_bam_pairs
+	bool keep_rg = false; bmh_rg_header_fn rg_header = nullptr; void *rg_user = nullptr;      // bmh_aligner_set_keep_rg
 	bsr_store_t store; bsr_index_t sort_ix; uint32_t sort_window = 0;      // sorted BAM output: the runs of the run in progress, the index of the last one, the window
 	uint64_t dup_counts[BDP_N_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0}; bool dup_valid = false;      // duplicate marking: the counts of the last marked run
 	std::vector<uint64_t> lib_counts;                    // ... with read groups: the same eight per library (bmh_aligner_markdup_library_counts)
@@ -995,7 +1028,8 @@ struct out_stage_t {
 	{
 		if (fmt != BMH_OUT_BAM_SORTED) return emit(R.text.p, (size_t)R.text_len);
 		if (!R.n_rec) return BMH_OK;
-		const bsr_dup_t bd = {R.stpl.p, R.dup_e.p, R.dup_info[0], R.dup_info[2], R.dup_info[3], lib_of(R.group)};
+		bsr_dup_t bd = {R.stpl.p, R.dup_e.p, R.dup_info[0], R.dup_info[2], R.dup_info[3], lib_of(R.group)};
+		if (h->a.markdup && h->a.per_read) { bd.lib3 = R.lib3.p; bd.n_lib3 = h->a.groups.n_lib; }
 		if (h->a.markdup) h->dup_times[2] += (double)R.dup_d2h;
 		return h->store.append((const uint8_t *)R.text.p, R.text_len, R.skeys.p, R.soff.p, R.n_rec, h->a.markdup ? &bd : nullptr);      // a sorted run: kept until the end of the input
 	}
@@ -1029,7 +1063,14 @@ struct out_stage_t {
 					rc = bdp_entries_host(bam, off.data(), (uint32_t)ord.size(), tpl, E, info, fn, A.groups.empty() ? nullptr : &G);
 					for (uint32_t i : ord) stpl.push_back(tpl[i]);
 				}
-				const bsr_dup_t bd = {stpl.data(), E.data(), (uint32_t)E.size(), info[0], info[1], lib_of(group)};
+				bsr_dup_t bd = {stpl.data(), E.data(), (uint32_t)E.size(), info[0], info[1], lib_of(group)};
+				std::vector<uint32_t> lib3;
+				if (rc == BMH_OK && A.markdup && A.per_read) {        // the host form of bdp_batch_lib_counts_device
+					std::vector<uint64_t> lc((size_t)BDP_N_COUNTS * A.groups.n_lib, 0);
+					bdp_lib_tally_host(bam, off.data(), (uint32_t)ord.size(), tpl.data(), E.data(), E.size(), A.groups.n_lib, lc.data());
+					for (uint32_t l = 0; l < A.groups.n_lib; ++l) for (int k = 0; k < 3; ++k) lib3.push_back((uint32_t)lc[(size_t)BDP_N_COUNTS * l + BDP_SECSUP + k]);
+					bd.lib3 = lib3.data(); bd.n_lib3 = A.groups.n_lib;
+				}
 				if (rc == BMH_OK && !ord.empty()) rc = h->store.append(srt.data(), bb, keys.data(), soff.data(), ord.size(), A.markdup ? &bd : nullptr);
 			}
 		} else if (rc == BMH_OK) {
@@ -1078,10 +1119,11 @@ static bool format_on_host(const aligner_t &A, const result_t &R, bool paired, s
 	bmh_cigar_src_t cs;
 	if (R.slot.empty()) cs.slot32 = R.slot32.p; else cs.slot64 = R.slot.data();
 	cs.aln = R.aln.p; cs.packed = R.packed.p; cs.off = R.off.p;
+	const bmh_read_groups_t rgs = A.read_groups(A.per_read ? rs->groups + R.b0 : nullptr);
 	return bmh_format_sam_parts(&po, R.n, (const char *)rs->names + n0, noff.data(), rs->codes + a0, offs64.data(), rs->lens + R.b0, A.n_contigs,
 	                            A.name_ptr.data(), A.off.data(), R.fin.p, R.opr.p, cs,
 	                            paired ? R.h_rec.data() : nullptr, paired ? R.unflag.data() : nullptr, parts,
-	                            rs->quals ? rs->quals + a0 : nullptr, cm ? (const char *)rs->comments + c0 : nullptr, cm ? coff.data() : nullptr);
+	                            rs->quals ? rs->quals + a0 : nullptr, cm ? (const char *)rs->comments + c0 : nullptr, cm ? coff.data() : nullptr, A.per_read ? &rgs : nullptr);
 }
 
 static int run_core(bmh_aligner_t *h, batch_src_t &src, const char *fn, int paired, int n_lanes, int n_threads, bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats)
@@ -1240,6 +1282,7 @@ int bmh_aligner_run(bmh_aligner_t *h, const bmh_read_set_t *rs, const uint64_t *
 {
 	if (!h || !rs || !cuts || !sink) { bmh_set_error("bmh_aligner_run: null argument"); return BMH_EINVAL; }
 	if (stats) memset(stats, 0, sizeof(*stats));
+	if (h->keep_rg) { bmh_set_error("bmh_aligner_run: the input's read groups are kept (bmh_aligner_set_keep_rg): that takes a BAM file (bmh_aligner_run_files), not reads in memory"); return BMH_EINVAL; }
 	if (n_batches == 0 || rs->n_reads == 0) return BMH_OK;
 	// (the device path reads ascii / offs / lens only, but the host forms -- the pairs' walks, the host tail after BMH_ECAPACITY, the host formatter -- read every array)
 	if (!rs->ascii || !rs->codes || !rs->offs || !rs->lens || !rs->names || !rs->name_offs) { bmh_set_error("bmh_aligner_run: the read set lacks one of ascii / codes / offs / lens / names / name_offs"); return BMH_EINVAL; }
@@ -1330,6 +1373,7 @@ static int run_file(bmh_aligner_t *h, const char *path, uint64_t batch_bases, ui
                     bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats, bool either, const char *fn)
 {
 	RCK(file_run_args(fn, h, path, sink, stats, batch_bases, batch_reads, paired, n_lanes, n_threads));
+	if (h->keep_rg) { bmh_set_error("%s: the input's read groups are kept (bmh_aligner_set_keep_rg): that takes a BAM file (bmh_aligner_run_files); text input carries none", fn); return BMH_EINVAL; }
 	const uint8_t *buf = nullptr; size_t sz = 0;
 	RCK(bmh_map_file(fn, path, &buf, &sz));
 	if (sz == 0) return BMH_OK;
@@ -1351,6 +1395,7 @@ static int run_file(bmh_aligner_t *h, const char *path, uint64_t batch_bases, ui
 			RCK(fb.size(fn, nr, nb, nn, ncm, fmt.fq, fmt.comments, &fb.rs));
 			RCK(bmh_fasta_fill(buf, p, end, nr, nb, nn, load_threads, &fb.rs, fmt, ncm));
 			est = end - p; p = end;
+			fb.group = -1;
 			return accept_batch(fn, paired, fb, id0);
 		}
 		return 0;
@@ -1373,8 +1418,32 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 	int dev = 0;
 	if (hipGetDevice(&dev) != hipSuccess) { bmh_set_error("%s: no HIP device", fn); return BMH_ENODEV; }
 	const bool cm = h->a.po.copy_comment != 0;
-	bmh_reads_pump_t *P = bmh_pump_open(path1, path2, n_threads, cm, false, 0);
+	const bool keep = h->keep_rg;
+	if (keep) {                                                        // refused before the file is opened
+		if (path2) { bmh_set_error("%s: the input's read groups are kept (bmh_aligner_set_keep_rg) and a mates file was given: such a run takes one BAM file", fn); return BMH_EINVAL; }
+		if (h->a.po.rg_id && h->a.po.rg_id[0]) { bmh_set_error("%s: the input's read groups are kept (bmh_aligner_set_keep_rg) and the aligner has a read group of its own ('%s', -R): one or the other", fn, h->a.po.rg_id); return BMH_EINVAL; }
+		if (h->a.markdup && h->a.n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d reference sequences: with read groups duplicate marking takes at most 2^24 (the library is the top byte of its key)", fn, h->a.n_contigs); return BMH_EINVAL; }
+	}
+	// (BMH_READS_HOST=1: the pump's host forms cut every window -- the A/B and cross-check switch of the device parser and the BAM decoder kernels)
+	bmh_reads_pump_t *P = bmh_pump_open(path1, path2, n_threads, cm, bmh_tune("READS_HOST", 0) != 0, 0, keep, keep && h->a.markdup);
 	if (!P) return BMH_EINVAL;
+	aligner_t &A = h->a;
+	// the run's table is the aligner's until the run is over, whichever way it ends
+	struct table_guard_t { aligner_t &A; bool on; ~table_guard_t() { if (on) { A.group_ids.clear(); A.groups = bdp_table_t(); A.per_read = false; ++A.groups_serial; } } } guard{A, false};
+	if (keep) {
+		// the header was read whole when the pump opened the file: its @RG lines are the run's read groups, and the caller hears of them before the first record
+		const bmh_rg_table_t *T = bmh_pump_read_groups(P);
+		bdp_table_t G;
+		G.id_off.assign(1, 0u);
+		for (size_t g = 0; g < T->ids.size(); ++g) { G.ids += T->ids[g]; G.id_off.push_back((uint32_t)G.ids.size()); G.lib.push_back((uint8_t)T->lib[g]); }      // (beyond 255 libraries the byte is not read: no duplicate marking)
+		G.n_lib = (uint32_t)T->lib_names.size();
+		A.group_ids.assign(T->ids.begin(), T->ids.end()); A.groups = G; A.per_read = true; ++A.groups_serial; guard.on = true;
+		if (h->rg_header) {
+			std::string lines;
+			for (const std::string &l : T->lines) { lines += l; lines += '\n'; }
+			if (h->rg_header(h->rg_user, lines.data(), lines.size(), (int)T->lib.size(), T->lib.data()) != 0) { bmh_pump_close(P); bmh_set_error("%s: the caller refused the input's read groups", fn); return BMH_EINVAL; }
+		}
+	}
 	// a BAM file says itself whether it holds pairs (flag 0x1 of its first record kept, known since the file was opened): the run's lanes start with that
 	const int bam_pairs = bmh_pump_bam_paired(P);
 	if (bam_pairs == 0 && paired) { bmh_pump_close(P); bmh_set_error("reads file: %s: paired reads were asked for and the BAM's records do not carry flag 0x1", path1); return BMH_EINVAL; }
@@ -1386,8 +1455,9 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 	}
 	int64_t id0 = 0;
 	auto fill = [&](fbatch_t &fb) {
-		const bmh_batch_alloc_t alloc = [&](uint64_t nr, uint64_t nb, uint64_t nn, uint64_t ncm, bool fq, bmh_read_set_t *rs) { return fb.size(fn, nr, nb, nn, ncm, fq, cm, rs); };
+		const bmh_batch_alloc_t alloc = [&](uint64_t nr, uint64_t nb, uint64_t nn, uint64_t ncm, bool fq, bmh_read_set_t *rs) { return fb.size(fn, nr, nb, nn, ncm, fq, cm, rs, keep); };
 		const int rc = bmh_pump_next(P, batch_bases, batch_reads, /* even counts, as bseq_read ends its batches */ batch_reads == 0, false, alloc, &fb.rs);
+		fb.group = -1;                                                 // (the buffers are kept between runs: one of a run over groups still names its group)
 		return rc == 1 ? accept_batch(fn, paired, fb, id0) : rc;
 	};
 	const int rc = run_loaded(h, fn, dev, fill, true, paired, n_lanes, n_threads, sink, user, stats);
@@ -1408,6 +1478,7 @@ int bmh_aligner_run_groups(bmh_aligner_t *h, const bmh_read_group_t *groups, int
 	if (stats) memset(stats, 0, sizeof(*stats));
 	if (n_groups < 1 || !groups) { bmh_set_error("%s: no read groups were given", fn); return BMH_EINVAL; }
 	if (h->a.po.rg_id && h->a.po.rg_id[0]) { bmh_set_error("%s: the aligner has a read group of its own ('%s', -R): a run over read groups takes them from its groups alone", fn, h->a.po.rg_id); return BMH_EINVAL; }
+	if (h->keep_rg) { bmh_set_error("%s: the input's read groups are kept (bmh_aligner_set_keep_rg): that and a run over read groups do not combine", fn); return BMH_EINVAL; }
 	std::vector<const char *> ids; std::vector<int32_t> libs;
 	int stated = paired ? 1 : 0;                                       // pairs by what the caller says: `paired`, or a group with two files
 	for (int g = 0; g < n_groups; ++g) {
@@ -1484,6 +1555,13 @@ int bmh_aligner_run_groups(bmh_aligner_t *h, const bmh_read_group_t *groups, int
 	close_pump();
 	bmh_reads_note_counts(ld.cnt); bmh_reads_note_inflate_counts(ld.icnt); bmh_reads_note_bam_counts(ld.bcnt);
 	return rc;
+}
+
+int bmh_aligner_set_keep_rg(bmh_aligner_t *h, int on, bmh_rg_header_fn header, void *user)
+{
+	if (!h) { bmh_set_error("bmh_aligner_set_keep_rg: null aligner"); return BMH_EINVAL; }
+	h->keep_rg = on != 0; h->rg_header = on ? header : nullptr; h->rg_user = on ? user : nullptr;
+	return BMH_OK;
 }
 
 int bmh_aligner_set_bam_pairs(bmh_aligner_t *h, uint64_t batch_bases, int n_lanes)

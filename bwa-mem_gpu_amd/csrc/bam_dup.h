@@ -53,6 +53,10 @@ void bdp_dev_free(bdp_dev_t *d);
 enum { BDP_INFO_WORDS = 8 };
 int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint32_t **d_tpl,
                      const bdp_entry_t **d_entries, const uint32_t **d_info);
+// a batch whose templates are of several libraries (a run that keeps its input's read groups), after bdp_batch_device on the same batch: *d_lib3 [3 * n_lib] -- every
+// library's secondary / supplementary records, unmapped records and templates, a record counted under the library of its template's entry (bdp_lib_tally_host's
+// three, per batch) -- in d until its next call.  n_lib <= BDP_MAX_LIBS.
+int bdp_batch_lib_counts_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, uint32_t n_lib, void *stream, const uint32_t **d_lib3);
 // the run's read groups go to the device (T NULL or empty: none, the entries are made without libraries); the batches that follow use them
 int bdp_dev_set_groups(bdp_dev_t *d, const bdp_table_t *T, void *stream);
 // the message of a batch whose info [1] is not 0

@@ -3,8 +3,10 @@
 //   per batch   heads: one lane per record, through the converter's offsets -- does it begin a template, is it a secondary / supplementary / unmapped line;
 //               an inclusive scan of the heads gives every record its batch-local template ordinal; starts: a head writes its record index at its ordinal;
 //               entries: one lane per template over its few records -> (end word lo, end word hi, score, kind | records << 2), 24 bytes; with read groups the
-//               lane also walks its first record's tags to RG:Z and compares the ID with the run's table row by row (a few short IDs in global memory, the
-//               same rows for every lane of a pipeline's batch) -- the library goes into the end words' top byte
+//               lane also walks its first record's tags to RG:Z and compares the ID with the run's table row by row (a few short IDs in global memory: the
+//               same rows for every lane of a batch of a run over groups, rows that differ from lane to lane in a run that keeps its input's read groups,
+//               whose batches mix them) -- the library goes into the end words' top byte; such a mixed batch also counts its secondary / supplementary,
+//               unmapped and template records per library (bdp_batch_lib_counts)
 //   decision    at the end of the input, over all templates' entries.  Pair pass: three stable 64-bit radix passes (rank word, hi, lo; templates that are no
 //               pair carry all-ones words and sort behind the pairs), then a lane is a duplicate iff its (lo, hi) equals the lane's before it.  Fragment pass:
 //               the fragments plus two items per pair (one per end), compacted through a scan; two stable passes (pair ends first, fragments best-first; then
@@ -24,7 +26,7 @@
 #include "bam_ws.h"
 
 struct bdp_dev_t {
-	dev_buf<uint8_t> head, tpl, start, entries, info, tmp;                        // per batch
+	dev_buf<uint8_t> head, tpl, start, entries, info, tmp, lib3;                  // per batch
 	dev_buf<uint8_t> bits, tord;                                                  // the bitmap of the run, a window's ordinals
 	dev_buf<uint8_t> g_ids, g_off, g_lib; uint32_t g_n = 0;                       // the run's read groups (bdp_dev_set_groups): IDs, their offsets, libraries; 0: none
 	uint64_t n_tpl = 0;                                                     // templates the bitmap covers
@@ -74,6 +76,32 @@ __global__ void __launch_bounds__(256) bdp_entries(const uint8_t *__restrict__ r
 	entries[t] = e;
 	if (st == BDP_E_TEMPLATE) atomicMin(info + 1, a + 1);
 	else if (LIB && st != BDP_E_OK) atomicMin(info + (st == BDP_E_NO_RG ? 4 : 5), a + 1);
+}
+
+// A batch whose templates are of several libraries: per library its secondary / supplementary records, unmapped records and templates -- out [3 * n_lib], through a
+// histogram in LDS (3 * n_lib 32-bit words, 3 KiB at the most; a batch holds fewer than 2^32 records).  A record's library is that of its template's entry; a batch
+// that bdp_batch_device's info words refuse leaves nothing here that is used.
+__global__ void __launch_bounds__(256) bdp_batch_lib_counts(const uint8_t *__restrict__ recs, const uint64_t *__restrict__ off, uint32_t n, uint64_t total, const uint32_t *__restrict__ tpl,
+                                                            const bdp_entry_t *__restrict__ entries, const uint32_t *__restrict__ info, uint32_t n_lib, uint32_t *out)
+{
+	extern __shared__ uint32_t lib3_s[];
+	for (uint32_t k = threadIdx.x; k < 3 * n_lib; k += 256) lib3_s[k] = 0;
+	__syncthreads();
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i < n && info[1] != 0) {                                       // (info [1] == 0: the first record begins no template -- no ordinal means anything)
+		const uint64_t o = off[i];
+		const uint32_t t = tpl[i];
+		if (o <= total && total - o >= BSR_FIXED && t < info[0] && t < n) {
+			const uint32_t fl = bsr_flag(recs + o), lib = bdp_lib_of(entries[t]);
+			if (lib < n_lib) {
+				if (fl & 0x900u) atomicAdd(lib3_s + 3 * lib, 1u);
+				if (fl & 4u) atomicAdd(lib3_s + 3 * lib + 1, 1u);
+				if (bdp_head(fl)) atomicAdd(lib3_s + 3 * lib + 2, 1u);
+			}
+		}
+	}
+	__syncthreads();
+	for (uint32_t k = threadIdx.x; k < 3 * n_lib; k += 256) if (lib3_s[k]) atomicAdd(out + k, lib3_s[k]);
 }
 
 // ---- the decision
@@ -237,6 +265,20 @@ int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off,
 		HIPCK(hipGetLastError());
 	}
 	*d_tpl = (const uint32_t *)d->tpl.p; *d_entries = (const bdp_entry_t *)d->entries.p; *d_info = (const uint32_t *)d->info.p;
+	return BMH_OK;
+}
+
+int bdp_batch_lib_counts_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, uint32_t n_lib, void *stream, const uint32_t **d_lib3)
+{
+	hipStream_t st = (hipStream_t)stream;
+	if (n_lib == 0 || n_lib > BDP_MAX_LIBS) { bmh_set_error("duplicate marking: %u libraries in a batch's counts (1 .. %d)", n_lib, (int)BDP_MAX_LIBS); return BMH_EINVAL; }
+	RCK(d->lib3.need(4 * 3 * (size_t)n_lib));
+	HIPCK(hipMemsetAsync(d->lib3.p, 0, 4 * 3 * (size_t)n_lib, st));
+	if (n) {
+		bdp_batch_lib_counts<<<blocks(n), 256, 4 * 3 * n_lib, st>>>(d_recs, d_off, n, total, (const uint32_t *)d->tpl.p, (const bdp_entry_t *)d->entries.p, (const uint32_t *)d->info.p, n_lib, (uint32_t *)d->lib3.p);
+		HIPCK(hipGetLastError());
+	}
+	*d_lib3 = (const uint32_t *)d->lib3.p;
 	return BMH_OK;
 }
 

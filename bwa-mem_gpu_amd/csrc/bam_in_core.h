@@ -27,7 +27,11 @@ enum {
 	BI_ETAGEXT = 4,      // a tag runs past the end of the record
 	BI_ETAGTYPE = 5,     // a tag of unknown type (or a B array of unknown element type)
 	BI_ELSEQ0 = 6,       // a read without bases (l_seq 0) -- kept records only
-	BI_EQUAL = 7         // a quality above 93 -- kept records only
+	BI_EQUAL = 7,        // a quality above 93 -- kept records only
+	// a run that keeps the input's read groups (bi_read_group) -- kept records only
+	BI_ERGNONE = 8,      // no RG tag
+	BI_ERGTYPE = 9,      // an RG tag of a type other than Z
+	BI_ERGUNKNOWN = 10   // RG:Z names an ID the header's @RG lines do not hold
 };
 
 BI_FN const char *bi_status_text(int st)
@@ -40,6 +44,9 @@ BI_FN const char *bi_status_text(int st)
 	case BI_ETAGTYPE: return "a tag of unknown type";
 	case BI_ELSEQ0: return "a read without bases (l_seq 0)";
 	case BI_EQUAL: return "a base quality above 93";
+	case BI_ERGNONE: return "no RG tag (the run keeps the input's read groups)";
+	case BI_ERGTYPE: return "an RG tag of a type other than Z";
+	case BI_ERGUNKNOWN: return "its RG:Z names a read group the header's @RG lines do not hold";
 	}
 	return "ok";
 }
@@ -144,6 +151,35 @@ BI_FN int bi_check_kept(const uint8_t *r, const bi_rec_t &R, uint32_t *has_qual)
 	*has_qual = n_ff != R.l_seq;
 	if (*has_qual && (n_ff != 0 || top > 93)) return BI_EQUAL;
 	return BI_OK;
+}
+
+// The read groups a run keeps: the IDs back to back (no terminators) with offsets off [n + 1] -- the shape of bdp_groups_t (csrc/bam_dup_core.h).
+struct bi_groups_t { const uint8_t *ids; const uint32_t *off; uint32_t n; };
+
+// The read group of a record that passed bi_check: the first RG tag among its tags, its Z value looked up in G row by row, whole IDs compared ("a" is not "ab").
+// BI_OK and *group, or BI_ERGNONE / BI_ERGTYPE / BI_ERGUNKNOWN.  The tags are walked with bi_tag_size inside [tag_off, size), so B arrays and every other type are
+// stepped over by their own extent; the value's NUL lies inside the record (bi_tag_size found it).
+BI_FN int bi_read_group(const uint8_t *r, const bi_rec_t &R, const bi_groups_t &G, uint32_t *group)
+{
+	for (uint32_t p = R.tag_off; p < R.size;) {
+		uint32_t b;
+		if (bi_tag_size(r, R.size, p, &b) != BI_OK) break;          // (not reached: bi_check walked the same tags)
+		if (r[p] == 'R' && r[p + 1] == 'G') {
+			if (r[p + 2] != 'Z') return BI_ERGTYPE;
+			const uint8_t *v = r + p + 3;
+			const uint32_t len = b - 4;                             // (3 bytes of name and type, the value, its NUL)
+			for (uint32_t g = 0; g < G.n; ++g) {
+				const uint32_t o = G.off[g];
+				if (G.off[g + 1] - o != len) continue;
+				uint32_t k = 0;
+				while (k < len && G.ids[o + k] == v[k]) ++k;
+				if (k == len) { *group = g; return BI_OK; }
+			}
+			return BI_ERGUNKNOWN;
+		}
+		p += b;
+	}
+	return BI_ERGNONE;
 }
 
 struct bi_out_t {

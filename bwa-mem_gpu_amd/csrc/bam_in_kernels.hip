@@ -11,6 +11,10 @@
 //   4 per read    exclusive scans of the lengths -> offs, name_offs, comment_offs                                                              (rocPRIM)
 //   5 per base    one wave per read: nibble -> letter and nt4 code, quality + 33; mirrored (and the base complemented) for flag 0x10            (bin_scatter)
 //   6 per read    its name, and its tags as the comment text                                                                                   (bin_names)
+// A run that keeps the input's read groups gives the kernels the table of IDs (bi_groups_t, in global memory: a few hundred bytes that every lane reads row by row,
+// so the rows come from the scalar and L2 caches; staging them in LDS would add a barrier to a kernel that has none): step 1 finds each kept record's RG:Z
+// (bi_read_group) and its index, step 3 checks that a pair's two records agree and writes one index per read beside the lengths.  Without a table (RG = false) the
+// kernels are what they were.
 // A record that fails a check raises the window's flag (a plain store to a status word); so do a window whose records disagree about having qualities and, at
 // the file's end, a record without its partner or bytes that are no whole record.  A flagged window is decoded by the host form (csrc/reads_io.cpp:
 // bmh_bam_host_run), which delivers what comes before the damage and words the refusal with the record's index -- the fallback rule that exists for text.
@@ -33,9 +37,10 @@ struct bin_ctl_t { uint32_t flag, n_qual, n_noqual, pad; };
 struct bin_to64 { __host__ __device__ uint64_t operator()(uint32_t v) const { return v; } };
 
 // per record: kept, and for a kept one its flag, lengths and where its bases start
-struct bin_rec_t { uint32_t *kept, *flag, *lseq, *lname, *seqoff, *clen, *left_out; };
+struct bin_rec_t { uint32_t *kept, *flag, *lseq, *lname, *seqoff, *clen, *left_out, *grp; };
 
-__global__ void __launch_bounds__(256) bin_validate(const uint8_t *__restrict__ b, const uint32_t *__restrict__ starts, uint32_t nrec, int comments, bin_rec_t M, bin_ctl_t *ctl)
+template <bool RG>
+__global__ void __launch_bounds__(256) bin_validate(const uint8_t *__restrict__ b, const uint32_t *__restrict__ starts, uint32_t nrec, int comments, bin_rec_t M, bin_ctl_t *ctl, bi_groups_t G)
 {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= nrec) return;
@@ -46,9 +51,12 @@ __global__ void __launch_bounds__(256) bin_validate(const uint8_t *__restrict__ 
 	bool bad = bi_check(r, starts[i + 1] - s, &R) != BI_OK;
 	if (!bad && bi_role(R.flag) != 0) {
 		uint32_t hq = 0;
+		uint32_t g = 0;
 		if (bi_check_kept(r, R, &hq) != BI_OK) bad = true;
+		else if (RG && bi_read_group(r, R, G, &g) != BI_OK) bad = true;
 		else {
 			kept = 1;
+			if (RG) M.grp[i] = g;
 			uint32_t lo = 0;
 			const uint32_t cl = bi_comment(r, R, nullptr, 0, &lo);
 			M.flag[i] = R.flag; M.lseq[i] = R.l_seq; M.lname[i] = R.l_name; M.seqoff[i] = R.seq_off; M.clen[i] = comments ? cl + 1 : 0u; M.left_out[i] = lo;
@@ -67,9 +75,10 @@ __global__ void __launch_bounds__(256) bin_compact(uint32_t nrec, const uint32_t
 }
 
 // kept record j < nuse -> its read (nuse is even with pairs): lengths, the record it comes from, where the records taken with it end
+template <bool RG>
 __global__ void __launch_bounds__(256) bin_place(const uint8_t *__restrict__ b, const uint32_t *__restrict__ starts, uint32_t nuse, int paired, bin_rec_t M, const uint32_t *__restrict__ krec,
                                                  uint32_t *__restrict__ lens, uint32_t *__restrict__ nlen, uint32_t *__restrict__ clen, uint32_t *__restrict__ rrec, uint32_t *__restrict__ left_out,
-                                                 uint32_t *__restrict__ rend, bin_ctl_t *ctl)
+                                                 uint32_t *__restrict__ rend, bin_ctl_t *ctl, uint32_t *__restrict__ rgrp)
 {
 	const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
 	if (j >= nuse) return;
@@ -82,6 +91,7 @@ __global__ void __launch_bounds__(256) bin_place(const uint8_t *__restrict__ b, 
 		if (!(j & 1u)) {                                       // the pair's first record looks at its partner
 			const uint32_t i2 = krec[j + 1], ln = M.lname[i];
 			if (bi_role(M.flag[i2]) + role != 3 || M.lname[i2] != ln) bad = true;
+			else if (RG && M.grp[i2] != M.grp[i]) bad = true;       // a pair of two read groups
 			else {
 				const uint8_t *n1 = b + starts[i] + BI_NAME_OFF, *n2 = b + starts[i2] + BI_NAME_OFF;
 				for (uint32_t k = 0; k < ln; ++k) if (n1[k] != n2[k]) { bad = true; break; }
@@ -91,6 +101,7 @@ __global__ void __launch_bounds__(256) bin_place(const uint8_t *__restrict__ b, 
 	rend[j] = starts[i + 1];
 	if (bad) { ctl->flag = 1; return; }                        // (two records of one role would write one read twice: the window is the host's anyway)
 	lens[r] = M.lseq[i]; nlen[r] = M.lname[i]; clen[r] = M.clen[i]; rrec[r] = i; left_out[r] = M.left_out[i];
+	if (RG) rgrp[r] = M.grp[i];
 }
 
 // one wave per read
@@ -139,6 +150,7 @@ struct bmh_bam_dev_t {
 	dev_buf<uint8_t> b, starts, kept, kidx, krec, flag, lseq, lname, seqoff, rclen, rleft, ctl, tmp;
 	dev_buf<uint8_t> lens, nlen, clen, rrec, left, rend, offs, noffs, coffs, ascii, codes, quals, names, cm;
 	pin_buf<uint8_t> h_starts, h_small, h_lens, h_left, h_rend, h_offs, h_noffs, h_coffs;
+	dev_buf<uint8_t> grp, rgrp, g_ids, g_off; bool g_up = false;      // a run that keeps read groups: per record, per read, the table (sent once)
 	std::vector<uint32_t> walked;
 	~bmh_bam_dev_t() { if (st) (void)hipStreamDestroy(st); }
 
@@ -162,13 +174,25 @@ struct bmh_bam_dev_t {
 		const uint8_t *db = b.as<uint8_t>();
 		const uint32_t *ds = starts.as<uint32_t>();
 		bin_ctl_t *dctl = ctl.as<bin_ctl_t>();
-		const bin_rec_t M = {kept.as<uint32_t>(), flag.as<uint32_t>(), lseq.as<uint32_t>(), lname.as<uint32_t>(), seqoff.as<uint32_t>(), rclen.as<uint32_t>(), rleft.as<uint32_t>()};
+		const bool rg = S.keep_rg();
+		if (rg && grp.need(n4) != BMH_OK) return BMH_ENOMEM;
+		if (rg && !g_up) {
+			const size_t ob = 4 * S.rg_off.size();
+			if (g_ids.need(S.rg_ids.size() + 16) != BMH_OK || g_off.need(ob) != BMH_OK) return BMH_ENOMEM;
+			HIPCK(hipMemcpyAsync(g_ids.p, S.rg_ids.data(), S.rg_ids.size(), hipMemcpyHostToDevice, st));
+			HIPCK(hipMemcpyAsync(g_off.p, S.rg_off.data(), ob, hipMemcpyHostToDevice, st));
+			HIPCK(hipStreamSynchronize(st));                       // (the state's arrays are pageable: the copy has left them before anything else happens)
+			g_up = true;
+		}
+		const bi_groups_t G = {rg ? g_ids.as<uint8_t>() : nullptr, rg ? g_off.as<uint32_t>() : nullptr, rg ? (uint32_t)S.rg_off.size() - 1 : 0u};
+		const bin_rec_t M = {kept.as<uint32_t>(), flag.as<uint32_t>(), lseq.as<uint32_t>(), lname.as<uint32_t>(), seqoff.as<uint32_t>(), rclen.as<uint32_t>(), rleft.as<uint32_t>(), rg ? grp.as<uint32_t>() : nullptr};
 		HIPCK(hipMemcpyAsync(b.p, w.buf, chain_end, hipMemcpyHostToDevice, st));
 		HIPCK(hipMemcpyAsync(starts.p, h_starts.p, n4 + 4, hipMemcpyHostToDevice, st));
 		HIPCK(hipMemsetAsync(ctl.p, 0, sizeof(bin_ctl_t), st));
 		HIPCK(hipMemsetAsync(kept.p + n4, 0, 4, st));            // (one entry behind the records: the scan's last entry is then the number kept)
 		const unsigned gr = (nrec + 255) / 256;
-		hipLaunchKernelGGL(bin_validate, dim3(gr), dim3(256), 0, st, db, ds, nrec, w.comments ? 1 : 0, M, dctl);
+		if (rg) hipLaunchKernelGGL(bin_validate<true>, dim3(gr), dim3(256), 0, st, db, ds, nrec, w.comments ? 1 : 0, M, dctl, G);
+		else hipLaunchKernelGGL(bin_validate<false>, dim3(gr), dim3(256), 0, st, db, ds, nrec, w.comments ? 1 : 0, M, dctl, G);
 		{
 			size_t tb = 0;
 			HIPCK(rocprim::exclusive_scan(nullptr, tb, kept.as<uint32_t>(), kidx.as<uint32_t>(), 0u, (size_t)nrec + 1, rocprim::plus<uint32_t>(), st));
@@ -198,8 +222,11 @@ struct bmh_bam_dev_t {
 		if (h_lens.need(t4) != BMH_OK || h_left.need(t4) != BMH_OK || h_rend.need(t4) != BMH_OK || h_offs.need(t8) != BMH_OK || h_noffs.need(t8) != BMH_OK || h_coffs.need(t8) != BMH_OK) return BMH_ENOMEM;
 		// (every read's entry is set before the scans read it, also in a window that bin_place flags: its sizes are not used then, but they are defined)
 		HIPCK(hipMemsetAsync(lens.p, 0, t4 + 4, st)); HIPCK(hipMemsetAsync(nlen.p, 0, t4 + 4, st)); HIPCK(hipMemsetAsync(clen.p, 0, t4 + 4, st));
-		hipLaunchKernelGGL(bin_place, dim3((nuse + 255) / 256), dim3(256), 0, st, db, ds, nuse, S.paired, M, krec.as<uint32_t>(), lens.as<uint32_t>(), nlen.as<uint32_t>(), clen.as<uint32_t>(),
-		                   rrec.as<uint32_t>(), left.as<uint32_t>(), rend.as<uint32_t>(), dctl);
+		if (rg && rgrp.need(t4) != BMH_OK) return BMH_ENOMEM;
+		if (rg) hipLaunchKernelGGL(bin_place<true>, dim3((nuse + 255) / 256), dim3(256), 0, st, db, ds, nuse, S.paired, M, krec.as<uint32_t>(), lens.as<uint32_t>(), nlen.as<uint32_t>(), clen.as<uint32_t>(),
+		                           rrec.as<uint32_t>(), left.as<uint32_t>(), rend.as<uint32_t>(), dctl, rgrp.as<uint32_t>());
+		else hipLaunchKernelGGL(bin_place<false>, dim3((nuse + 255) / 256), dim3(256), 0, st, db, ds, nuse, S.paired, M, krec.as<uint32_t>(), lens.as<uint32_t>(), nlen.as<uint32_t>(), clen.as<uint32_t>(),
+		                        rrec.as<uint32_t>(), left.as<uint32_t>(), rend.as<uint32_t>(), dctl, (uint32_t *)nullptr);
 		{
 			size_t tb = 0;
 			auto in = rocprim::make_transform_iterator(lens.as<uint32_t>(), bin_to64());
@@ -241,6 +268,7 @@ struct bmh_bam_dev_t {
 		if (fq && rs->quals) HIPCK(hipMemcpyAsync(rs->quals, quals.p, nb, hipMemcpyDeviceToHost, st));
 		HIPCK(hipMemcpyAsync(rs->names, names.p, nn, hipMemcpyDeviceToHost, st));
 		if (w.comments && rs->comments) HIPCK(hipMemcpyAsync(rs->comments, cm.p, nc, hipMemcpyDeviceToHost, st));
+		if (rg && rs->groups) HIPCK(hipMemcpyAsync(rs->groups, rgrp.p, k * 4, hipMemcpyDeviceToHost, st));
 		HIPCK(hipMemcpyAsync(hs + 1, krec.as<uint32_t>() + (k - 1), 4, hipMemcpyDeviceToHost, st));     // the last kept record taken: the records before its end
 		memcpy(rs->offs, ho, k * 8); memcpy(rs->lens, hl, k * 4); memcpy(rs->name_offs, hn, k * 8);
 		if (w.comments && rs->comment_offs) memcpy(rs->comment_offs, hc, k * 8);
@@ -267,4 +295,14 @@ extern "C" int bmh_bam_reads_device(const uint8_t *records, uint64_t n_bytes, in
 	if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) { (void)hipGetLastError(); bmh_set_error("bmh_bam_reads_device: no HIP device (bmh_bam_reads_host decodes on the host)"); return BMH_ENODEV; }
 	bmh_bam_dev_t d;
 	return bmh_bam_reads_run("bmh_bam_reads_device", &d, records, n_bytes, flags, out);
+}
+
+// ... with a table of read group IDs: out->groups [n_reads] is every read's index in it (csrc/bam_in_core.h: bi_read_group)
+extern "C" int bmh_bam_reads_groups_device(const uint8_t *records, uint64_t n_bytes, int flags, const char *const *rg_ids, int n_groups, bmh_read_set_t *out)
+{
+	if ((!records && n_bytes) || !out || !rg_ids) { bmh_set_error("bmh_bam_reads_groups_device: null argument"); return BMH_EINVAL; }
+	int nd = 0;
+	if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) { (void)hipGetLastError(); bmh_set_error("bmh_bam_reads_groups_device: no HIP device (bmh_bam_reads_groups_host decodes on the host)"); return BMH_ENODEV; }
+	bmh_bam_dev_t d;
+	return bmh_bam_reads_run("bmh_bam_reads_groups_device", &d, records, n_bytes, flags, out, rg_ids, n_groups);
 }

@@ -32,7 +32,7 @@ struct bsr_index_t {
 // (16 bytes per record) always in memory.  With duplicate marking (csrc/bam_dup_core.h) a run also keeps every record's template ordinal within its batch (tpl, 4 bytes
 // per record, outside the budget like keys and offsets) and the ordinal of its first template in the whole run (tbase); the store keeps the templates' entries
 struct bsr_run_t { uint64_t n = 0, bytes = 0; std::vector<uint64_t> keys, off; uint8_t *mem = nullptr; int64_t file_at = -1; std::vector<uint32_t> tpl; uint64_t tbase = 0; };
-struct bsr_dup_t { const uint32_t *tpl; const bdp_entry_t *entries; uint32_t n_tpl; uint64_t secsup, unmapped; int lib = -1; };      // what a batch adds when duplicates are marked; lib: the library of the batch's read group (-1: a run without groups)
+struct bsr_dup_t { const uint32_t *tpl; const bdp_entry_t *entries; uint32_t n_tpl; uint64_t secsup, unmapped; int lib = -1; const uint32_t *lib3 = nullptr; uint32_t n_lib3 = 0; };      // what a batch adds when duplicates are marked; lib: the library of the batch's read group (-1: a run without groups); lib3 [3 * n_lib3]: a batch of several libraries -- every library's secondary / supplementary records, unmapped records and templates (lib stays -1)
 struct bsr_store_t {
 	uint64_t mem_bytes = 4ull << 30, used = 0, spilled = 0; std::string tmp_dir; int fd = -1; uint64_t file_bytes = 0;
 	std::vector<bsr_run_t> runs;

@@ -159,6 +159,10 @@ int bsr_store_t::append(const uint8_t *recs, uint64_t bytes, const uint64_t *key
 		uint64_t *c = &lib_info[3 * (size_t)dup->lib];
 		c[0] += dup->secsup; c[1] += dup->unmapped; c[2] += dup->n_tpl;
 	}
+	if (dup && dup->lib < 0 && dup->lib3) {                // a batch of several libraries: its own per-library counts
+		if (lib_info.size() < 3 * (size_t)dup->n_lib3) lib_info.resize(3 * (size_t)dup->n_lib3, 0);
+		for (size_t k = 0; k < 3 * (size_t)dup->n_lib3; ++k) lib_info[k] += dup->lib3[k];
+	}
 	runs.push_back(std::move(r));
 	return BMH_OK;
 }

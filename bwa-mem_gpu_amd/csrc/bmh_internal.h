@@ -50,7 +50,8 @@ bool bmh_format_sam_parts(const bmh_post_opt_t *po, uint32_t n_reads, const char
                           const uint64_t *read_offs, const uint32_t *read_lens, int n_contigs, const char *const *contig_names,
                           const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read, const bmh_cigar_src_t &cs,
                           const int32_t *h_rec, const int32_t *unflag, std::vector<std::string> &parts,
-                          const uint8_t *quals = nullptr, const char *comments = nullptr, const uint64_t *comment_off = nullptr);
+                          const uint8_t *quals = nullptr, const char *comments = nullptr, const uint64_t *comment_off = nullptr,
+                          const bmh_read_groups_t *groups = nullptr);       // groups: a read group per read (include/bwamem_hip.h), checked by the caller
 // csrc/sam_kernels.hip, for csrc/align_pipeline.hip: the alignments whose fixed slots overflowed (flags 1, 8) found and, once redone with large
 // slots, put in place on the device (see the definitions)
 int64_t bmh_cigar_overflowed(const int32_t *d_aln, uint32_t n, const uint32_t *d_sel, uint32_t *d_over, uint32_t *d_sel2, uint32_t *d_counter, void *stream);
@@ -93,8 +94,8 @@ int64_t bmh_text_members(bmh_text_src_t *s, uint8_t *dst, size_t cap, size_t wan
 uint64_t bmh_text_host_members(const bmh_text_src_t *s);                // BGZF members inflated by the host threads so far
 // csrc/reads_io.cpp: the host walker (kseq_read restated) appends a record to growing arrays; nlen / clen: bytes of its name / comment with their NUL
 struct bmh_hbatch_t {
-	std::vector<uint8_t> ascii, quals, names, comments; std::vector<uint32_t> lens, nlen, clen;
-	void clear() { ascii.clear(); quals.clear(); names.clear(); comments.clear(); lens.clear(); nlen.clear(); clen.clear(); }
+	std::vector<uint8_t> ascii, quals, names, comments; std::vector<uint32_t> lens, nlen, clen, grp;      // grp: a BAM run that keeps read groups -- every read's
+	void clear() { ascii.clear(); quals.clear(); names.clear(); comments.clear(); lens.clear(); nlen.clear(); clen.clear(); grp.clear(); }
 };
 int bmh_walk_record(const uint8_t *b, size_t n, bool eof, size_t *p, bmh_hbatch_t &o, bool comments, int *kind);
 void bmh_nt4_codes(const uint8_t *src, uint8_t *dst, size_t n);
@@ -103,8 +104,11 @@ void bmh_nt4_codes(const uint8_t *src, uint8_t *dst, size_t n);
 // start at 0), 0 = the end, < 0 = refused.  The batch ends as bseq_read ends its batches (bases >= want_bases -- or reads == want_reads if not 0 -- and an
 // even count when `even`; pairs stay together with two files); take_all: every complete record of the window instead.
 struct bmh_reads_pump_t;
+struct bmh_rg_table_t;
 typedef std::function<int(uint64_t n_reads, uint64_t n_bases, uint64_t n_name_bytes, uint64_t n_comment_bytes, bool fq, bmh_read_set_t *rs)> bmh_batch_alloc_t;
-bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_threads, bool comments, bool host_only, size_t chunk_bytes);
+// keep_rg / markdup: the input must be one BAM, its header's @RG lines become the run's read groups (bmh_pump_read_groups) and every read carries its own (rs->groups)
+bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_threads, bool comments, bool host_only, size_t chunk_bytes, bool keep_rg = false, bool markdup = false);
+const bmh_rg_table_t *bmh_pump_read_groups(const bmh_reads_pump_t *p);   // of a pump opened with keep_rg, else NULL
 int bmh_pump_next(bmh_reads_pump_t *p, uint64_t want_bases, uint64_t want_reads, bool even, bool take_all, const bmh_batch_alloc_t &alloc, bmh_read_set_t *rs);
 void bmh_pump_counts(const bmh_reads_pump_t *p, uint64_t out[4]);        // windows parsed on the device, windows walked on the host, text bytes, records
 void bmh_pump_close(bmh_reads_pump_t *p);
@@ -132,7 +136,22 @@ extern "C" int bmh_bam_chain_count(const uint8_t *records, uint64_t n_bytes, uin
 // the flag of the first record of b[0, n) that gives a read: 1 and *flag, or 0 when the whole records of b hold none (yet)
 int bmh_bam_first_kept(const uint8_t *b, size_t n, uint32_t *flag);      // (-1: a record too short for its fixed fields comes first)
 // what a BAM file's windows share.  paired: flag 0x1 of the first record kept; qual: 0 unknown, 1 the records have qualities, 2 they have none
-struct bmh_bam_state_t { std::string path; int paired = 0, qual = 0; uint64_t n_recs = 0, n_skipped = 0, n_tags_left_out = 0; };
+// rg_ids / rg_off: a run that keeps the input's read groups -- the IDs of the header's @RG lines back to back with offsets [n + 1] (bi_groups_t); empty: no tag is read.
+// Such a run writes every read's group index to rs->groups when the allocator has provided the array.
+struct bmh_bam_state_t {
+	std::string path; int paired = 0, qual = 0; uint64_t n_recs = 0, n_skipped = 0, n_tags_left_out = 0;
+	std::string rg_ids; std::vector<uint32_t> rg_off;
+	bool keep_rg() const { return rg_off.size() > 1; }
+};
+// The @RG lines of a BAM header's text (it ends at its first NUL; the last line may lack its newline; a CR before the newline is dropped; other lines are ignored):
+// lines verbatim without their line ends, their IDs, and every group's library index by first appearance (the LB field as bwamem_hip.aligner.rg_library reads it:
+// the last non-empty one, groups without one share "Unknown Library") with the libraries' names.  Refused (BMH_EINVAL, the line named, `what` in front): no @RG line, a line
+// without a non-empty ID of at most 255 bytes or with a field that is not XX:value, a repeated ID, more than 65535 groups, and with markdup more than 255 libraries.
+struct bmh_rg_table_t {
+	std::vector<std::string> lines, ids, lib_names; std::vector<int32_t> lib;
+	void clear() { lines.clear(); ids.clear(); lib_names.clear(); lib.clear(); }
+};
+int bmh_bam_header_groups(const char *what, const char *text, size_t n, bool markdup, bmh_rg_table_t &T);
 // chain: the record starts of buf[0, have) when the caller has walked them already (bmh_bam_chain's result), else NULL
 struct bmh_bam_win_t { const uint8_t *buf; size_t have; bool eof, comments; uint64_t want_bases, want_reads; bool even, take_all; const std::vector<uint32_t> *chain; };
 // consumed: the end of the last record taken; n_recs: the records before it; skipped / tags_left_out: among those; qual: the state behind them
@@ -142,7 +161,7 @@ struct bmh_bam_dev_t;
 bmh_bam_dev_t *bmh_bam_dev_create();
 void bmh_bam_dev_free(bmh_bam_dev_t *d);
 int bmh_bam_dev_run(bmh_bam_dev_t *d, const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bmh_batch_alloc_t &alloc, bmh_read_set_t *rs, bmh_bam_res_t &R);   // 1, 2: the window is the host's, < 0
-int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out);   // csrc/reads_io.cpp: bmh_bam_reads_device / _host
+int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out, const char *const *rg_ids = nullptr, int n_groups = 0);   // csrc/reads_io.cpp: bmh_bam_reads_device / _host
 // the pump's answer for bmh_aligner_run_files: -1 the input is no BAM, else flag 0x1 of its first record kept
 int bmh_pump_bam_paired(const bmh_reads_pump_t *p);
 void bmh_pump_bam_counts(const bmh_reads_pump_t *p, uint64_t out[2]);    // records skipped (0x100 / 0x800), f and B tags left out

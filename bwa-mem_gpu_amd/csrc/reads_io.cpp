@@ -14,6 +14,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
+#include <string>
 #include <thread>
 #include <chrono>
 #include <vector>
@@ -319,7 +321,7 @@ extern "C" void bmh_reads_free(bmh_read_set_t *r)
 {
 	if (!r) return;
 	free(r->ascii); free(r->codes); free(r->offs); free(r->lens); free(r->names); free(r->name_offs);
-	free(r->quals); free(r->comments); free(r->comment_offs);
+	free(r->quals); free(r->comments); free(r->comment_offs); free(r->groups);
 	memset(r, 0, sizeof(*r));
 }
 
@@ -650,13 +652,17 @@ int bmh_bam_host_run(const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bm
 	int qual = st.qual;
 	uint64_t acc = 0, cnt = 0, skipped = 0, left_out = 0;
 	bool complete = false;
-	size_t pend = (size_t)-1, i = 0; bi_rec_t pend_rec; uint32_t pend_hq = 0;
-	auto append = [&](size_t k, const bi_rec_t &B, uint32_t hq) {
+	size_t pend = (size_t)-1, i = 0; bi_rec_t pend_rec; uint32_t pend_hq = 0, pend_g = 0;
+	const bool keep = st.keep_rg();
+	const bi_groups_t G = {(const uint8_t *)st.rg_ids.data(), st.rg_off.data(), keep ? (uint32_t)st.rg_off.size() - 1 : 0u};
+	auto gid = [&](uint32_t g) { return st.rg_ids.substr(st.rg_off[g], st.rg_off[g + 1] - st.rg_off[g]); };
+	auto append = [&](size_t k, const bi_rec_t &B, uint32_t hq, uint32_t g) {
 		const uint8_t *r = w.buf + starts[k];
 		for (uint32_t t = 0; t < B.l_seq; ++t) hb.ascii.push_back(bi_base(r, B, t));
 		if (hq) for (uint32_t t = 0; t < B.l_seq; ++t) hb.quals.push_back(bi_qual(r, B, t));
 		hb.names.insert(hb.names.end(), r + BI_NAME_OFF, r + BI_NAME_OFF + B.l_name);
 		hb.lens.push_back(B.l_seq); hb.nlen.push_back(B.l_name);
+		if (keep) hb.grp.push_back(g);
 		uint32_t lo = 0;
 		const uint32_t cl = bi_comment(r, B, nullptr, 0, &lo);
 		left_out += lo;
@@ -691,16 +697,25 @@ int bmh_bam_host_run(const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bm
 			return BMH_EINVAL;
 		}
 		qual = hq ? 1 : 2;
-		if (!st.paired) { append(i, B, hq); commit(i); continue; }
+		uint32_t g = 0;
+		if (keep) {                                          // (kept records only: a record skipped by its flag is never inspected for its group)
+			s = bi_read_group(r, B, G, &g);
+			if (s != BI_OK) { bmh_set_error("reads file: %s: BAM record %llu (%s): %s", path, idx(i), name(i), bi_status_text(s)); return BMH_EINVAL; }
+		}
+		if (!st.paired) { append(i, B, hq, g); commit(i); continue; }
 		if (role == 3) { bmh_set_error("reads file: %s: BAM record %llu (%s): flag 0x1 with neither or both of 0x40 and 0x80", path, idx(i), name(i)); return BMH_EINVAL; }
-		if (pend == (size_t)-1) { pend = i; pend_rec = B; pend_hq = hq; continue; }
+		if (pend == (size_t)-1) { pend = i; pend_rec = B; pend_hq = hq; pend_g = g; continue; }
 		if (strcmp(name(pend), name(i)) != 0) {
 			bmh_set_error("reads file: %s: BAM records %llu and %llu carry different names (%s and %s): is the file grouped by read name?", path, idx(pend), idx(i), name(pend), name(i));
 			return BMH_EINVAL;
 		}
 		if (bi_role(pend_rec.flag) == role) { bmh_set_error("reads file: %s: BAM records %llu and %llu (%s) both carry flag %s", path, idx(pend), idx(i), name(i), role == 1 ? "0x40" : "0x80"); return BMH_EINVAL; }
-		if (role == 2) { append(pend, pend_rec, pend_hq); append(i, B, hq); }
-		else { append(i, B, hq); append(pend, pend_rec, pend_hq); }
+		if (keep && pend_g != g) {
+			bmh_set_error("reads file: %s: BAM records %llu and %llu (%s) name different read groups (%s and %s): the two reads of a pair are of one", path, idx(pend), idx(i), name(i), gid(pend_g).c_str(), gid(g).c_str());
+			return BMH_EINVAL;
+		}
+		if (role == 2) { append(pend, pend_rec, pend_hq, pend_g); append(i, B, hq, g); }
+		else { append(i, B, hq, g); append(pend, pend_rec, pend_hq, pend_g); }
 		pend = (size_t)-1;
 		commit(i);
 	}
@@ -723,6 +738,7 @@ int bmh_bam_host_run(const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bm
 	if (fq && rs->quals) memcpy(rs->quals, hb.quals.data(), hb.quals.size());
 	memcpy(rs->names, hb.names.data(), hb.names.size());
 	if (w.comments && rs->comments) memcpy(rs->comments, hb.comments.data(), hb.comments.size());
+	if (keep && rs->groups) memcpy(rs->groups, hb.grp.data(), 4 * (size_t)cnt);
 	uint64_t o = 0, no = 0, co = 0;
 	for (uint64_t r = 0; r < cnt; ++r) {
 		rs->offs[r] = o; rs->lens[r] = hb.lens[r]; rs->name_offs[r] = no; o += hb.lens[r]; no += hb.nlen[r];
@@ -733,14 +749,89 @@ int bmh_bam_host_run(const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bm
 	return 1;
 }
 
+// ---- the read groups of a BAM header's text (declared in csrc/bmh_internal.h with its rules)
+int bmh_bam_header_groups(const char *what, const char *text, size_t n, bool markdup, bmh_rg_table_t &T)
+{
+	T.clear();
+	const void *nul = n ? memchr(text, 0, n) : nullptr;
+	if (nul) n = (size_t)((const char *)nul - text);
+	int n_line = 0;
+	for (size_t p = 0; p < n;) {
+		const char *nl = (const char *)memchr(text + p, '\n', n - p);
+		size_t le = nl ? (size_t)(nl - text) : n;
+		const size_t next = nl ? le + 1 : n;
+		if (nl && le > p && text[le - 1] == '\r') --le;
+		const std::string line(text + p, le - p);
+		p = next;
+		if (line.compare(0, 3, "@RG") != 0 || (line.size() > 3 && line[3] != '\t')) continue;
+		++n_line;
+		auto refuse = [&](const char *why) {
+			bmh_set_error("%s: BAM header: @RG line %d ('%.120s'): %s", what, n_line, line.c_str(), why);
+			T.clear();
+			return (int)BMH_EINVAL;
+		};
+		std::string id, lb; bool has_id = false;
+		for (size_t q = 3; q < line.size();) {                  // (line[q] is the tab in front of a field)
+			const size_t e = std::min(line.find('\t', q + 1), line.size());
+			const std::string f = line.substr(q + 1, e - q - 1);
+			if (f.size() < 3 || f[2] != ':') return refuse("a field that is not XX:value");
+			if (f.compare(0, 3, "ID:") == 0 && !has_id) { id = f.substr(3); has_id = true; }
+			if (f.compare(0, 3, "LB:") == 0 && f.size() > 3) lb = f.substr(3);
+			q = e;
+		}
+		if (!has_id || id.empty()) return refuse("no ID field, or an empty one");
+		if (id.size() > 255) return refuse("an ID longer than 255 bytes");
+		for (const std::string &o : T.ids) if (o == id) return refuse("its ID names an earlier @RG line's read group");
+		if (T.ids.size() >= 65535) return refuse("more than 65535 read groups");
+		if (lb.empty()) lb = "Unknown Library";
+		size_t l = 0;
+		while (l < T.lib_names.size() && T.lib_names[l] != lb) ++l;
+		if (l == T.lib_names.size()) {
+			if (markdup && l >= 255) return refuse("its library is the run's 256th: duplicate marking holds at most 255 (the library is a byte of the duplicate key)");
+			T.lib_names.push_back(lb);
+		}
+		T.lines.push_back(line); T.ids.push_back(id); T.lib.push_back((int32_t)l);
+	}
+	if (T.ids.empty()) { bmh_set_error("%s: BAM header: no @RG line: the run keeps the input's read groups and the header names none", what); return BMH_EINVAL; }
+	return BMH_OK;
+}
+
+// the table as one malloc'd blob for a caller without C++: every line with a '\n' behind it (*lines, *lines_bytes), and lib [*n_groups]; bmh_free both
+extern "C" int bmh_bam_header_read_groups(const char *text, uint64_t n_bytes, int markdup, char **lines, uint64_t *lines_bytes, int32_t **lib, int32_t *n_groups)
+{
+	if ((!text && n_bytes) || !lines || !lines_bytes || !lib || !n_groups) { bmh_set_error("bmh_bam_header_read_groups: null argument"); return BMH_EINVAL; }
+	*lines = nullptr; *lib = nullptr; *lines_bytes = 0; *n_groups = 0;
+	bmh_rg_table_t T;
+	const int rc = bmh_bam_header_groups("bmh_bam_header_read_groups", text ? text : "", (size_t)n_bytes, markdup != 0, T);
+	if (rc != BMH_OK) return rc;
+	std::string all;
+	for (const std::string &l : T.lines) { all += l; all += '\n'; }
+	*lines = (char *)malloc(all.size() + 1); *lib = (int32_t *)malloc(4 * T.lib.size());
+	if (!*lines || !*lib) { free(*lines); free(*lib); *lines = nullptr; *lib = nullptr; bmh_set_error("bmh_bam_header_read_groups: out of memory"); return BMH_ENOMEM; }
+	memcpy(*lines, all.data(), all.size()); (*lines)[all.size()] = 0; memcpy(*lib, T.lib.data(), 4 * T.lib.size());
+	*lines_bytes = all.size(); *n_groups = (int32_t)T.lib.size();
+	return BMH_OK;
+}
+
 // bmh_bam_reads_device / bmh_bam_reads_host: the records are one window that ends the file, and every read of it is taken.  d: the device form, or NULL
-int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out)
+int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out, const char *const *rg_ids, int n_groups)
 {
 	memset(out, 0, sizeof(*out));
+	const bool keep = rg_ids != nullptr;
+	if (keep && (n_groups < 1 || n_groups > 65535)) { bmh_set_error("%s: %d read groups (1 .. 65535)", fn, n_groups); return BMH_EINVAL; }
 	if (n_bytes >= ((uint64_t)1 << 31) - 4096) { bmh_set_error("%s: 2^31 bytes of records or more (offsets inside a window are 32-bit)", fn); return BMH_EINVAL; }
 	const bool cm = (flags & BMH_READS_COMMENTS) != 0;
 	bmh_bam_state_t st;
 	st.path = "(records in memory)";
+	if (keep) {
+		st.rg_off.push_back(0);
+		for (int g = 0; g < n_groups; ++g) {
+			const size_t l = rg_ids[g] ? strlen(rg_ids[g]) : 0;
+			if (l == 0 || l > 255) { bmh_set_error("%s: read group %d: an ID of %zu bytes (1 .. 255)", fn, g, l); return BMH_EINVAL; }
+			for (int o = 0; o < g; ++o) if (strcmp(rg_ids[o], rg_ids[g]) == 0) { bmh_set_error("%s: read groups %d and %d share the ID '%s'", fn, o, g, rg_ids[g]); return BMH_EINVAL; }
+			st.rg_ids += rg_ids[g]; st.rg_off.push_back((uint32_t)st.rg_ids.size());
+		}
+	}
 	uint32_t flag = 0;
 	if (bmh_bam_first_kept(records, (size_t)n_bytes, &flag) == 1) st.paired = (int)(flag & 1u);
 	const bmh_batch_alloc_t alloc = [&](uint64_t nr, uint64_t nb, uint64_t nn, uint64_t nc, bool fq, bmh_read_set_t *rs) {
@@ -749,6 +840,7 @@ int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, 
 		bool ok = out->ascii && out->codes && out->offs && out->lens && out->names && out->name_offs;
 		if (fq) { out->quals = (uint8_t *)malloc(nb + 1); ok = ok && out->quals; }
 		if (cm) { out->comments = (uint8_t *)malloc(nc + 1); out->comment_offs = (uint64_t *)malloc(8 * (nr + 1)); ok = ok && out->comments && out->comment_offs; }
+		if (keep) { out->groups = (uint32_t *)malloc(4 * (nr + 1)); ok = ok && out->groups; }
 		if (!ok) { bmh_set_error("%s: out of memory", fn); return (int)BMH_ENOMEM; }
 		out->ascii[nb] = out->codes[nb] = 0; out->names[nn] = 0;
 		if (fq) out->quals[nb] = 0;
@@ -775,6 +867,12 @@ int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, 
 	const uint64_t bc[2] = {R.skipped, R.tags_left_out};
 	bmh_reads_note_bam_counts(bc);
 	return BMH_OK;
+}
+
+extern "C" int bmh_bam_reads_groups_host(const uint8_t *records, uint64_t n_bytes, int flags, const char *const *rg_ids, int n_groups, bmh_read_set_t *out)
+{
+	if ((!records && n_bytes) || !out || !rg_ids) { bmh_set_error("bmh_bam_reads_groups_host: null argument"); return BMH_EINVAL; }
+	return bmh_bam_reads_run("bmh_bam_reads_groups_host", nullptr, records, n_bytes, flags, out, rg_ids, n_groups);
 }
 
 extern "C" int bmh_bam_reads_host(const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out)

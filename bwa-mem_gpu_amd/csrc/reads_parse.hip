@@ -595,6 +595,7 @@ struct bmh_reads_pump_t {
 	// the third kind: S[0] delivers BAM records (csrc/bam_in_core.h), bs is what its windows share
 	bool bam = false; bmh_bam_state_t bs; bmh_bam_dev_t *bdev = nullptr;
 	std::vector<uint32_t> chain;                           // the record starts of S[0]'s window found so far; its last entry is where the walk stands
+	bool keep_rg = false, markdup = false; bmh_rg_table_t rg;      // a run that keeps the input's read groups: the header's @RG lines (bam_open), their IDs in bs
 	~bmh_reads_pump_t() { delete dev; if (bdev) bmh_bam_dev_free(bdev); }
 };
 
@@ -613,7 +614,15 @@ int bam_open(bmh_reads_pump_t *P)
 		RCK(S.fill(t));
 		const int64_t hb = bmh_bam_header_bytes(S.buf, S.have);
 		if (hb < 0) { bmh_set_error("reads file: %s: no BAM header behind the magic bytes", path); return BMH_EINVAL; }
-		if (hb > 0) { S.consume((size_t)hb); break; }
+		if (hb > 0) {
+			if (P->keep_rg) {                                   // the header's text is whole here, before a record is looked at: its @RG lines are the run's read groups
+				const std::string what = "reads file: " + S.path;
+				RCK(bmh_bam_header_groups(what.c_str(), (const char *)S.buf + 8, (size_t)((uint32_t)S.buf[4] | ((uint32_t)S.buf[5] << 8) | ((uint32_t)S.buf[6] << 16) | ((uint32_t)S.buf[7] << 24)), P->markdup, P->rg));
+				P->bs.rg_off.assign(1, 0u);
+				for (const std::string &id : P->rg.ids) { P->bs.rg_ids += id; P->bs.rg_off.push_back((uint32_t)P->bs.rg_ids.size()); }
+			}
+			S.consume((size_t)hb); break;
+		}
 		if (S.eof) { bmh_set_error("reads file: %s: the file ends inside the BAM header", path); return BMH_EINVAL; }
 		if (t >= MAX_WINDOW) { bmh_set_error("reads file: %s: a BAM header of 2^31 bytes or more", path); return BMH_EINVAL; }
 		t = std::min(MAX_WINDOW, t * 2);
@@ -679,9 +688,12 @@ int bam_next(bmh_reads_pump_t *P, uint64_t want_bases, uint64_t want_reads, bool
 }
 }   // namespace
 
-bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_threads, bool comments, bool host_only, size_t chunk_bytes)
+const bmh_rg_table_t *bmh_pump_read_groups(const bmh_reads_pump_t *p) { return p->keep_rg ? &p->rg : nullptr; }
+
+bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_threads, bool comments, bool host_only, size_t chunk_bytes, bool keep_rg, bool markdup)
 {
 	bmh_reads_pump_t *P = new bmh_reads_pump_t();
+	P->keep_rg = keep_rg; P->markdup = markdup;
 	P->nf = path2 ? 2 : 1; P->comments = comments; P->host_only = host_only; P->chunk = chunk_bytes;
 	const char *paths[2] = {path1, path2};
 	for (int f = 0; f < P->nf; ++f) {
@@ -706,6 +718,7 @@ bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_thre
 		if (bam_open(P) != BMH_OK) { delete P; return nullptr; }
 		return P;
 	}
+	if (keep_rg) { bmh_set_error("reads file: %s: the input's read groups can be kept only when it is a BAM file (text input carries none)", path1); delete P; return nullptr; }
 	if (!host_only) P->dev = new dev_parser_t();
 	return P;
 }

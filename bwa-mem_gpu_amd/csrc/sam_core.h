@@ -5,6 +5,7 @@
 //
 // read_records<Src, Out> is what a record says.  Where the inputs live is the Src's business, where the bytes go the Out's:
 //   Src   flag_all() softclip() sa() drop() max_XA_hits() max_XA_hits_alt() rg() rg_len()          the options (sa: the record field of the XA key)
+//         rg_read(r, len)                                                                          optional: read r's own read group (a run that keeps its input's); a Src without it: rg() / rg_len() for every read
 //         paired() h_rec(r) unflag(r)                                                              pairs: own-alignment record, flags of the unmapped record
 //         read(r) -> { n, fin, aln(i) }                                                            the read's 16-int records; aln(i).aln == nullptr: none
 //         md_len(x)  name(r) name_len(r)  l_seq(r) seq(r) letter(c, rev) qual(r)  comment(r, len)  MD length; name; bases, SEQ letter of a base, QUAL or nullptr
@@ -162,6 +163,10 @@ template <class Out> SAM_FN void fmt3(Out &o, int a, int b)
 	o.ch((char)('0' + f / 100)); o.ch((char)('0' + f / 10 % 10)); o.ch((char)('0' + f % 10));
 }
 
+// ---- the read group of read r's records: the Src's rg_read(r, len) when it has one, else its one rg() / rg_len() (overload resolution prefers the int form)
+template <class Src> SAM_INL auto read_rg(const Src &S, uint32_t r, int &len, int) -> decltype(S.rg_read(r, len)) { return S.rg_read(r, len); }
+template <class Src> SAM_INL const char *read_rg(const Src &S, uint32_t, int &len, long) { len = S.rg_len(); return S.rg(); }
+
 // ---- the records of read r: the unmapped record when nothing is reported, else every reported record in order.  Returns a negative value, or -- a record the
 // text needs has no alignment -- the index of that record in its read (the mate's own-alignment record is looked at first, before anything is written)
 template <class Src, class Out> SAM_FN int read_records(const Src &S, uint32_t r, Out &out)
@@ -187,7 +192,8 @@ template <class Src, class Out> SAM_FN int read_records(const Src &S, uint32_t r
 	int cmt_len = 0;
 	const char *cmt = S.comment(r, cmt_len);
 	const int l_seq = S.l_seq(r);
-	const int rg_len = S.rg_len();
+	int rg_len = 0;
+	const char *rg = read_rg(S, r, rg_len, 0);
 	int n_rep = 0;
 	for (int i = 0; i < n; ++i) n_rep += a[16 * i + 15] & 1;
 	if (n_rep == 0) {                                           // unmapped record (mem_reg2sam's aa.n == 0 branch)
@@ -205,7 +211,7 @@ template <class Src, class Out> SAM_FN int read_records(const Src &S, uint32_t r
 		out.ch('\t');
 		if (qual) put_qual(out, qual, 0, l_seq, p_rev != 0); else out.ch('*');
 		out.lit("\tAS:i:0\tXS:i:0");
-		if (rg_len) { out.lit("\tRG:Z:"); out.str(S.rg(), rg_len); }
+		if (rg_len) { out.lit("\tRG:Z:"); out.str(rg, rg_len); }
 		if (cmt_len > 0) { out.ch('\t'); out.str(cmt, cmt_len); }
 		out.ch('\n');
 		return -1;
@@ -243,7 +249,7 @@ template <class Src, class Out> SAM_FN int read_records(const Src &S, uint32_t r
 		if (x.aln[3]) { out.lit("\tNM:i:"); out.num(x.aln[4]); out.lit("\tMD:Z:"); out.str(x.md, S.md_len(x)); }
 		if (fin[1] >= 0) { out.lit("\tAS:i:"); out.num(fin[1]); }
 		if (!(flag & 0x100) && fin[10] >= 0) { out.lit("\tXS:i:"); out.num(fin[10]); }      // sub is not printed for secondary records (q->sub = -1)
-		if (rg_len) { out.lit("\tRG:Z:"); out.str(S.rg(), rg_len); }      // src/bwamem.c:1631-1634
+		if (rg_len) { out.lit("\tRG:Z:"); out.str(rg, rg_len); }      // src/bwamem.c:1631-1634
 		if (!(flag & 0x100)) {                                     // SA: the other reported records that are not secondary
 			bool other = false;
 			for (int j = 0; j < n; ++j) if (j != i && (a[16 * j + 15] & 1) && !(a[16 * j + 14] & 0x100)) other = true;

@@ -30,6 +30,7 @@ struct host_src_t {
 	const int32_t *h_recs, *unflags; const uint8_t *quals; const char *comments; const uint64_t *comment_off;      // (comments: NULL unless -C copies them)
 	const uint64_t *bases;                 // [n_reads] first record of every read
 	const char *rg_id; int rg_n;           // read group: RG:Z:<id> on every record
+	const bmh_read_groups_t *groups;       // ... or a read group per read (NULL: rg_id)
 	struct read_t {
 		const bmh_cigar_src_t &cs; uint64_t base; int n; const int32_t *fin;
 		sam_core::aln_t aln(int i) const
@@ -53,6 +54,13 @@ struct host_src_t {
 	int max_XA_hits_alt() const { return po->max_XA_hits_alt; }
 	const char *rg() const { return rg_id; }
 	int rg_len() const { return rg_n; }
+	const char *rg_read(uint32_t r, int &len) const
+	{
+		if (!groups) { len = rg_n; return rg_id; }
+		const uint32_t g = groups->read_group[r], o = groups->id_off[g];
+		len = (int)(groups->id_off[g + 1] - o);
+		return groups->ids + o;
+	}
 	bool paired() const { return h_recs != nullptr; }
 	int h_rec(uint32_t r) const { return h_recs[r]; }
 	int unflag(uint32_t r) const { return unflags ? unflags[r] : 0; }
@@ -112,14 +120,14 @@ bool bmh_format_sam_parts(const bmh_post_opt_t *po, uint32_t n_reads, const char
                           const uint64_t *read_offs, const uint32_t *read_lens, int n_contigs, const char *const *contig_names,
                           const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read, const bmh_cigar_src_t &cs,
                           const int32_t *h_rec, const int32_t *unflag, std::vector<std::string> &parts,
-                          const uint8_t *quals, const char *comments, const uint64_t *comment_off)
+                          const uint8_t *quals, const char *comments, const uint64_t *comment_off, const bmh_read_groups_t *groups)
 {
 	std::vector<uint64_t> bases((size_t)n_reads + 1, 0);
 	for (uint32_t r = 0; r < n_reads; ++r) bases[r + 1] = bases[r] + fin_per_read[r];
 	const bool cm = po->copy_comment && comments && comment_off;           // -C: the header comment behind every record (an empty one is not written)
 	const char *rg = po->rg_id && po->rg_id[0] ? po->rg_id : nullptr;
 	const host_src_t S{po, names, name_off, reads, read_offs, read_lens, n_contigs, contig_names, contig_offset, fin, fin_per_read, cs, h_rec, unflag, quals,
-	                   cm ? comments : nullptr, comment_off, bases.data(), rg, rg ? (int)strlen(rg) : 0};
+	                   cm ? comments : nullptr, comment_off, bases.data(), rg, rg ? (int)strlen(rg) : 0, groups};
 	// reads are independent: format ranges of them on host threads (the reference formats inside its worker threads)
 	// (threads: the hardware's, not bmh_effective_cpus(): a CPU quota limits the RATE of CPU time, and a batch's text is a burst -- on a box that
 	// shows 256 threads and grants 16 CPUs' worth of time, 64 threads format a million reads in 14 ms, 16 threads in 45 ms)
@@ -153,13 +161,14 @@ static char *format_sam(const bmh_post_opt_t *po, uint32_t n_reads, const char *
                         const uint64_t *read_offs, const uint32_t *read_lens, int n_contigs, const char *const *contig_names,
                         const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read, const int64_t *slot,
                         const int32_t *aln, const uint32_t *cigar, int max_cigar, const char *md, int md_cap,
-                        const int32_t *h_rec, const int32_t *unflag, const uint8_t *quals, const char *comments, const uint64_t *comment_off, size_t *len_out)
+                        const int32_t *h_rec, const int32_t *unflag, const uint8_t *quals, const char *comments, const uint64_t *comment_off, size_t *len_out,
+                        const bmh_read_groups_t *groups = nullptr)
 {
 	std::vector<std::string> parts;
 	bmh_cigar_src_t cs;
 	cs.slot64 = slot; cs.aln = aln; cs.cigar = cigar; cs.max_cigar = max_cigar; cs.md = md; cs.md_cap = md_cap;
 	if (!bmh_format_sam_parts(po, n_reads, names, name_off, reads, read_offs, read_lens, n_contigs, contig_names, contig_offset, fin, fin_per_read, cs, h_rec, unflag, parts,
-	                          quals, comments, comment_off)) return nullptr;
+	                          quals, comments, comment_off, groups)) return nullptr;
 	const unsigned n_thr = (unsigned)parts.size();
 	size_t total = 0;
 	for (const std::string &p : parts) total += p.size();
@@ -197,6 +206,25 @@ extern "C" char *bmh_format_sam(const bmh_post_opt_t *po, uint32_t n_reads, cons
 {
 	return bmh_format_sam_ex(po, n_reads, names, name_off, reads, read_offs, read_lens, nullptr, nullptr, nullptr, n_contigs, contig_names, contig_offset, fin,
 	                         fin_per_read, slot, aln, cigar, max_cigar, md, md_cap, len_out);
+}
+
+// a read group per read (include/bwamem_hip.h: bmh_read_groups_t); h_rec / unflag NULL: single-end reads
+extern "C" char *bmh_format_sam_groups(const bmh_post_opt_t *po, uint32_t n_reads, const char *names, const uint64_t *name_off, const uint8_t *reads,
+                                       const uint64_t *read_offs, const uint32_t *read_lens, const uint8_t *quals, const char *comments, const uint64_t *comment_off,
+                                       int n_contigs, const char *const *contig_names, const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read,
+                                       const int32_t *h_rec, const int32_t *unflag, const int64_t *slot, const int32_t *aln, const uint32_t *cigar, int max_cigar,
+                                       const char *md, int md_cap, const bmh_read_groups_t *groups, size_t *len_out)
+{
+	const char *fn = "bmh_format_sam_groups";
+	if (!po || !names || !name_off || !reads || !read_offs || !read_lens || !contig_names || !fin_per_read || !len_out || (n_contigs > 1 && !contig_offset) ||
+	    (!comments) != (!comment_off) || (!h_rec) != (!unflag) || (h_rec && (n_reads & 1)) || !groups || !groups->ids || !groups->id_off || (n_reads && !groups->read_group)) {
+		bmh_set_error("%s: bad argument", fn); return nullptr;
+	}
+	if (po->rg_id && po->rg_id[0]) { bmh_set_error("%s: a read group per read beside the options' one read group (rg_id '%s')", fn, po->rg_id); return nullptr; }
+	for (uint32_t r = 0; r < n_reads; ++r)
+		if (groups->read_group[r] >= groups->n_groups) { bmh_set_error("%s: read %u is of group %u: the table holds %u", fn, r, groups->read_group[r], groups->n_groups); return nullptr; }
+	return format_sam(po, n_reads, names, name_off, reads, read_offs, read_lens, n_contigs, contig_names, contig_offset, fin, fin_per_read, slot, aln, cigar, max_cigar,
+	                  md, md_cap, h_rec, unflag, quals, comments, comment_off, len_out, groups);
 }
 
 // interleaved pairs: fin / fin_per_read / h_rec / unflag from bmh_finalize_pairs (mem_aln2sam with the mate: flags 0x8 0x20,

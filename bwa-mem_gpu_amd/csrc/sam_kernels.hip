@@ -226,6 +226,16 @@ struct sam_src_t {
 	__device__ __forceinline__ int max_XA_hits_alt() const { return A.max_XA_hits_alt; }
 	__device__ __forceinline__ const char *rg() const { return A.rg; }
 	__device__ __forceinline__ int rg_len() const { return A.rg_len; }
+	// per-read read groups (d_read_group): the read's ID out of the table; an index outside it raises flag 4 and writes no tag
+	__device__ __forceinline__ const char *rg_read(uint32_t r, int &len) const
+	{
+		if (!A.d.d_read_group) { len = A.rg_len; return A.rg; }
+		const uint32_t g = A.d.d_read_group[r];
+		if (g >= A.d.n_rg) { atomicOr(A.err, 4u); len = 0; return A.rg; }
+		const uint32_t o = A.d.d_rg_id_off[g];
+		len = (int)(A.d.d_rg_id_off[g + 1] - o);
+		return A.d.d_rg_ids + o;
+	}
 	__device__ __forceinline__ bool paired() const { return A.d.d_h_rec != nullptr; }
 	__device__ __forceinline__ int h_rec(uint32_t r) const { return A.d.d_h_rec[r]; }
 	__device__ __forceinline__ int unflag(uint32_t r) const { return A.d.d_unflag ? A.d.d_unflag[r] : 0; }
@@ -341,9 +351,10 @@ int sam_args(const bmh_post_opt_t *popt, const bmh_sam_dev_t *d, const char *fn,
 	if (!popt || !d) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	if (d->n_reads && (!d->d_names || !d->d_name_off || !d->d_reads || !d->d_offs || !d->d_lens || !d->d_contig_names || !d->d_contig_name_off || !d->d_fin_per_read ||
 	                   !d->d_slot || !d->d_aln || !d->d_cig_off || !d->d_packed || (d->n_contigs > 1 && !d->d_contig_offset) || (d->d_h_rec && (!d->d_unflag || (d->n_reads & 1))) ||
-	                   (!d->d_comments) != (!d->d_comment_off))) {
+	                   (!d->d_comments) != (!d->d_comment_off) || (d->d_read_group && (!d->d_rg_ids || !d->d_rg_id_off || !d->n_rg)))) {
 		bmh_set_error("%s: null argument", fn); return BMH_EINVAL;
 	}
+	if (d->d_read_group && popt->rg_id && popt->rg_id[0]) { bmh_set_error("%s: per-read read groups (d_read_group) beside the options' one read group (rg_id '%s')", fn, popt->rg_id); return BMH_EINVAL; }
 	memset(&A, 0, sizeof(A));
 	A.d = *d;
 	A.flag_all = popt->flag_all; A.max_XA_hits = popt->max_XA_hits; A.max_XA_hits_alt = popt->max_XA_hits_alt; A.no_multi = popt->no_multi; A.softclip = popt->softclip;
@@ -418,6 +429,7 @@ extern "C" int64_t bmh_sam_text_sizes(const bmh_post_opt_t *popt, const bmh_sam_
 	HIPCK(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
 	HIPCK(hipGetLastError());
+	if (h_err & 4u) { bmh_set_error("bmh_sam_text_sizes: a read's group (d_read_group) lies outside the table of n_rg read groups"); return BMH_EINVAL; }
 	if (h_err) { bmh_set_error("bmh_sam_text_sizes: a record the text needs has no CIGAR (see bmh_sam_select_device), or one that bmh_cigar_batch flagged"); return BMH_EINVAL; }
 	return (int64_t)total;
 }

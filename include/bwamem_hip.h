@@ -433,6 +433,15 @@ char *bmh_format_sam_ex(const bmh_post_opt_t *po, uint32_t n_reads, const char *
                         int n_contigs, const char *const *contig_names, const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read,
                         const int64_t *slot, const int32_t *aln, const uint32_t *cigar, int max_cigar, const char *md, int md_cap, size_t *len_out);
 
+/* bmh_format_sam_ex / bmh_format_sam_pe_ex (h_rec and unflag NULL: single-end reads) with a read group per read: the same table on the host -- read r's records
+ * carry RG:Z:<ID read_group[r]>, ID g = ids[id_off[g] .. id_off[g + 1]), at the place po->rg_id's tag takes.  Refused: po->rg_id beside it, an index outside the table. */
+typedef struct { const uint32_t *read_group; const char *ids; const uint32_t *id_off; uint32_t n_groups; } bmh_read_groups_t;
+char *bmh_format_sam_groups(const bmh_post_opt_t *po, uint32_t n_reads, const char *names, const uint64_t *name_off, const uint8_t *reads,
+                            const uint64_t *read_offs, const uint32_t *read_lens, const uint8_t *quals, const char *comments, const uint64_t *comment_off,
+                            int n_contigs, const char *const *contig_names, const int64_t *contig_offset, const int32_t *fin, const uint32_t *fin_per_read,
+                            const int32_t *h_rec, const int32_t *unflag, const int64_t *slot, const int32_t *aln, const uint32_t *cigar, int max_cigar,
+                            const char *md, int md_cap, const bmh_read_groups_t *groups, size_t *len_out);
+
 /* ---- the read file: one '>' header line and one sequence line per read, the only layout the reference's seeding library parses
  * (src/GPUSeed/seed_gen.cu:1698-1728; the host takes the same file through kseq, bseq_read src/bwa.c:48-66).  Loads it into the flat
  * arrays this API takes: the letters back to back (what bmh_seed_batch / bmh_chain_* read in HBM), their nt4 codes (nst_nt4_table,
@@ -461,6 +470,7 @@ typedef struct {
 	uint8_t *comments;             /* [n_comment_bytes] as names, or NULL (none) */
 	uint64_t *comment_offs;        /* [n_reads] */
 	uint64_t n_comment_bytes;
+	uint32_t *groups;              /* [n_reads] every read's read group, an index into the run's table (BAM input that keeps its read groups), or NULL */
 } bmh_read_set_t;
 int bmh_reads_load_fasta(const char *path, int n_threads, bmh_read_set_t *out);
 int bmh_reads_load(const char *path, int n_threads, int flags, bmh_read_set_t *out);
@@ -497,6 +507,16 @@ int bmh_reads_load_files(const char *path1, const char *path2, int n_threads, in
  * and paired != 0 is refused. */
 int bmh_bam_reads_device(const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out);
 int bmh_bam_reads_host(const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out);
+/* The same step for a run that keeps the input's read groups: rg_ids [n_groups] are the IDs of the header's @RG lines (1 .. 255 bytes each, no two equal), and
+ * out->groups [n_reads] is the index of every read's RG:Z value among them -- whole IDs compared.  Refused naming the record's index: a kept record without an RG
+ * tag, with one of another type than Z or with an ID that is not listed, a pair whose two records name different groups.  Records skipped by their flag are not looked at.
+ * bmh_bam_header_read_groups: the @RG lines of a BAM header's text (it ends at its first NUL; CR LF accepted; the last line may lack its newline; other lines
+ * ignored) -- *lines: the lines verbatim, each with a '\n' behind it; *lib [*n_groups]: every group's library by first appearance (the last non-empty LB field;
+ * groups without one share a library); bmh_free both.  Refused naming the line: no @RG line, a line without a non-empty ID of at most 255 bytes or with a field that
+ * is not XX:value, a repeated ID, more than 65535 groups, and with markdup != 0 more than 255 libraries. */
+int bmh_bam_reads_groups_device(const uint8_t *records, uint64_t n_bytes, int flags, const char *const *rg_ids, int n_groups, bmh_read_set_t *out);
+int bmh_bam_reads_groups_host(const uint8_t *records, uint64_t n_bytes, int flags, const char *const *rg_ids, int n_groups, bmh_read_set_t *out);
+int bmh_bam_header_read_groups(const char *text, uint64_t n_bytes, int markdup, char **lines, uint64_t *lines_bytes, int32_t **lib, int32_t *n_groups);
 int bmh_reads_last_bam_counts(uint64_t *out);
 
 /* ---- BGZF members inflated on the device (csrc/inflate_core.h, csrc/inflate_kernels.hip): all of RFC 1951, one lane per member, the CRC32 of the text
@@ -726,6 +746,9 @@ typedef struct {
 	const int32_t *d_h_rec, *d_unflag;                         /* interleaved pairs (bmh_finalize_pairs' out_h / out_unflag) or NULL */
 	const uint8_t *d_quals;                                    /* Phred+33 at d_offs, or NULL (QUAL '*') */
 	const char *d_comments; const uint64_t *d_comment_off;     /* as d_names / d_name_off, or NULL (written only with popt->copy_comment) */
+	/* per-read read groups, or NULL / 0 (popt->rg_id on every record, as before): read r's records carry RG:Z:<ID d_read_group[r]> where popt->rg_id's tag goes;
+	 * the IDs lie back to back without terminators, ID g = d_rg_ids[d_rg_id_off[g] .. d_rg_id_off[g + 1]) (d_rg_id_off [n_rg + 1]).  Not beside popt->rg_id. */
+	const uint32_t *d_read_group; const char *d_rg_ids; const uint32_t *d_rg_id_off; uint32_t n_rg;
 } bmh_sam_dev_t;
 size_t bmh_sam_text_work(uint32_t n_reads);
 int64_t bmh_sam_text_sizes(const bmh_post_opt_t *popt, const bmh_sam_dev_t *d, uint64_t *d_text_off, void *d_work, size_t work_bytes, void *stream);
@@ -881,6 +904,17 @@ int bmh_bam_sorted_file_markdup_host(const char *header_text, int n_contigs, con
                                      int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8]);
 int bmh_aligner_set_markdup(bmh_aligner_t *a, int on);
 int bmh_aligner_set_bam_pairs(bmh_aligner_t *a, uint64_t batch_bases, int n_lanes);        /* (described with bmh_bam_reads_device above) */
+/* Keep the input's read groups (off by default; with it off nothing about a run changes).  bmh_aligner_run_files then takes one BAM -- a regular file or a pipe --
+ * whose header's @RG lines are the run's read groups, in file order (bmh_bam_header_read_groups' rules and refusals), and every read's records carry RG:Z:<the ID its
+ * own record names> where popt->rg_id's tag goes: the decoder gives every read its group (bmh_bam_reads_groups_device's rules and refusals), a batch holds reads of
+ * any number of groups and is cut as without the option, and a read's index (the tie-break hash) is its index in the file.  `header` is called once, after the
+ * input's header has been read whole and before the first call of the sink: rg_lines holds the @RG lines verbatim, each with a '\n' behind it -- what the caller
+ * writes into its output header --, lib [n_groups] every group's library (bmh_bam_header_read_groups); a non-zero return ends the run.  A refused header ends the
+ * run before either is called.  With BMH_OUT_BAM_SORTED and duplicate marking the duplicates are called within a library and bmh_aligner_markdup_library_counts gives
+ * a row per library.  Refused: text input, a mates file, an aligner with a read group of its own (popt->rg_id), bmh_aligner_run_groups (keep-rg and a run over
+ * groups do not combine), more than 255 libraries with duplicate marking. */
+typedef int (*bmh_rg_header_fn)(void *user, const char *rg_lines, size_t len, int n_groups, const int32_t *lib);
+int bmh_aligner_set_keep_rg(bmh_aligner_t *a, int on, bmh_rg_header_fn header, void *user);
 int bmh_aligner_markdup_counts(bmh_aligner_t *a, uint64_t out[8]);
 /* where the last marked run's extra time went: [0] the decision, ms  [1] the windows' flag steps (ordinals up, flag kernel), ms  [2] bytes of ordinals and entries
  * that came down with the batches */
@@ -907,7 +941,7 @@ int bmh_bam_sorted_file_markdup_groups_host(const char *header_text, int n_conti
 int bmh_aligner_markdup_library_counts(bmh_aligner_t *a, int lib, uint64_t out[8]);
 
 /* A run over several read groups: one sample's lanes and libraries into one output.  A group is a read group ID, its library index (as above) and an input as
- * bmh_aligner_run_files takes it (path2: the mates, or NULL; a BAM's own @RG lines and RG tags stay ignored).  One loader thread walks the groups in order into the
+ * bmh_aligner_run_files takes it (path2: the mates, or NULL; a BAM's own @RG lines and RG tags stay ignored: keeping the input's read groups, bmh_aligner_set_keep_rg, and a run over groups do not combine).  One loader thread walks the groups in order into the
  * one queue of batches: the lanes are not drained between groups.  A batch never spans two groups and is cut inside its group as bmh_aligner_run_files cuts it; the
  * read index behind the tie-break hash restarts at 0 in every group; every record carries its group's ID as RG:Z.  So group g's records are byte for byte those of
  * bmh_aligner_run_files on its input alone by an aligner whose read group is g's, and the unsorted output is the groups' outputs in order.  Sorted output with

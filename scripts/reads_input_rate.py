@@ -3,7 +3,11 @@
   * bmh_aligner_run_file on the plain interleaved file (the yardstick: the path that exists without csrc/reads_parse.hip) -- in this tree
     and, with --parent DIR, in a built tree of the parent commit (a child process with that tree's package and library, the same files),
   * bmh_aligner_run_files on the same plain file, on two plain files (paired), on BGZF and on single-member gzip,
-  * bmh_aligner_run_files on the same reads as unaligned BAM (align_files_bam; --configs align_files_bgzf,align_files_bam gives the two rows to compare).
+  * bmh_aligner_run_files on the same reads as unaligned BAM (align_files_bam; --configs align_files_bgzf,align_files_bam gives the two rows to compare),
+  * that BAM rewritten with four read groups -- @RG lines in its header, RG:Z on every record, the groups changing read by read (pairs: template by template) --
+    once plain (align_files_bam_rg_plain: the tags are ignored, the code path of a run without the option) and once keeping its read groups
+    (align_files_bam_keep_rg: bmh_aligner_set_keep_rg); --configs align_files_bam_rg_plain,align_files_bam_keep_rg --out FILE --out-key keep_rg adds the two rows
+    to FILE under that key and leaves the rest of it as it is.
 Every configuration runs once to warm the lanes, then --runs times; each row lists every run, the median, the spread, the host CPU
 seconds of the process per million reads, and how many windows the device parser cut and how many the host walker took.
 
@@ -70,13 +74,17 @@ for _i, _c in enumerate(b"=ACMGRSVTWYHKDBN"):
     NT16[_c] = _i
 
 
-def bam_records(names: np.ndarray, w: int, asc: np.ndarray, qual: np.ndarray, rl: int, paired: bool) -> np.ndarray:
-    """the same reads as unaligned BAM records (one row each): flag 4, or 0x4D / 0x8D in turn for pairs; no CIGAR, no tags"""
+def bam_records(names: np.ndarray, w: int, asc: np.ndarray, qual: np.ndarray, rl: int, paired: bool, n_groups: int = 0) -> np.ndarray:
+    """the same reads as unaligned BAM records (one row each): flag 4, or 0x4D / 0x8D in turn for pairs; no CIGAR; no tags, or with n_groups (up to 10) the tag
+    RG:Z:g<k>, k changing template by template"""
     n = asc.size // rl
     nm = np.frombuffer("".join(names.tolist()).encode(), np.uint8).reshape(n, w + 1)
     l_name, half = w + 2, (rl + 1) // 2
-    bs = 32 + l_name + half + rl
+    bs = 32 + l_name + half + rl + (6 if n_groups else 0)
     rec = np.zeros((n, 4 + bs), np.uint8)
+    if n_groups:
+        rec[:, -6:-2] = np.frombuffer(b"RGZg", np.uint8)
+        rec[:, -2] = ord("0") + (np.arange(n) // (2 if paired else 1)) % n_groups
     rec[:, 0:4] = np.frombuffer(struct.pack("<I", bs), np.uint8)
     rec[:, 4:12] = 0xff                                                          # refID, pos: -1
     rec[:, 12] = l_name
@@ -90,12 +98,14 @@ def bam_records(names: np.ndarray, w: int, asc: np.ndarray, qual: np.ndarray, rl
     nib = np.zeros((n, 2 * half), np.uint8); nib[:, :rl] = NT16[asc.reshape(n, rl)]
     s0 = 36 + l_name
     rec[:, s0:s0 + half] = (nib[:, 0::2] << 4) | nib[:, 1::2]
-    rec[:, s0 + half:] = qual.reshape(n, rl) - 33
+    rec[:, s0 + half:s0 + half + rl] = qual.reshape(n, rl) - 33
     return rec
 
 
 BAM_TEXT = b"@HD\tVN:1.6\tSO:unsorted\n"
 BAM_HEADER = b"BAM\1" + struct.pack("<I", len(BAM_TEXT)) + BAM_TEXT + struct.pack("<I", 0)      # no reference sequences: the reads are unaligned
+BAM_RG_TEXT = BAM_TEXT + b"".join(b"@RG\tID:g%d\tLB:lib%d\tSM:s\n" % (k, k // 2) for k in range(4))      # four groups in two libraries
+BAM_RG_HEADER = b"BAM\1" + struct.pack("<I", len(BAM_RG_TEXT)) + BAM_RG_TEXT + struct.pack("<I", 0)
 
 
 def measure(fn, runs: int, n4: int) -> dict:
@@ -245,6 +255,7 @@ def main():
     ap.add_argument("--inflate-only", action="store_true")
     ap.add_argument("--bam-only", action="store_true")
     ap.add_argument("--configs", default="", help="only these rows (comma-separated keys, e.g. align_files_bgzf,align_files_bam); default: all")
+    ap.add_argument("--out-key", default="", help="with --out: the result goes into the existing JSON of that file under this key; the rest of the file stays")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)          # the plain file the --parent child aligns (mode and sizes from the other options)
     a = ap.parse_args()
     if a.parser_only:
@@ -304,6 +315,8 @@ def main():
         if only is None or any("gzip" in k for k in only):
             write_gzip(p("fq.gz"), recs.tobytes())
         write_bgzf(p("bam"), BAM_HEADER + bam_records(names, w, asc, qual, rl, paired).tobytes())       # the same reads as unaligned BAM: half the bytes, no lines
+        if only is None or any("_rg" in k for k in only):
+            write_bgzf(p("rg.bam"), BAM_RG_HEADER + bam_records(names, w, asc, qual, rl, paired, 4).tobytes())
         if paired and (only is None or any("two" in k for k in only)):
             recs[0::2].tofile(p("r1.fq")); recs[1::2].tofile(p("r2.fq"))
             write_bgzf(p("r1.bgzf"), recs[0::2].tobytes()); write_bgzf(p("r2.bgzf"), recs[1::2].tobytes())
@@ -325,12 +338,20 @@ def main():
                 return fn()
             finally:
                 L.bmh_tune_set(b"INFLATE_DEVICE", 0, 1)
+        def keep_rg(fn):                       # bmh_aligner_set_keep_rg for one call (the header callback counts the lines)
+            nat.set_keep_rg(True, lambda lines, libs: None)
+            try:
+                return fn()
+            finally:
+                nat.set_keep_rg(False)
         configs = {"align_file_plain": lambda: nat.run_file(p("fq"), paired, sink, **kw),
                    "align_files_plain": lambda: nat.run_files(p("fq"), None, paired, sink, **kw),
                    "align_files_bgzf": lambda: nat.run_files(p("fq.bgzf"), None, paired, sink, **kw),
                    "align_files_bgzf_device_inflate": lambda: device_inflate(lambda: nat.run_files(p("fq.bgzf"), None, paired, sink, **kw)),
                    "align_files_gzip": lambda: nat.run_files(p("fq.gz"), None, paired, sink, **kw),
-                   "align_files_bam": lambda: nat.run_files(p("bam"), None, paired, sink, **kw)}
+                   "align_files_bam": lambda: nat.run_files(p("bam"), None, paired, sink, **kw),
+                   "align_files_bam_rg_plain": lambda: nat.run_files(p("rg.bam"), None, paired, sink, **kw),
+                   "align_files_bam_keep_rg": lambda: keep_rg(lambda: nat.run_files(p("rg.bam"), None, paired, sink, **kw))}
         if paired:
             configs.update({"align_files_two_plain": lambda: nat.run_files(p("r1.fq"), p("r2.fq"), True, sink, **kw),
                             "align_files_two_bgzf": lambda: nat.run_files(p("r1.bgzf"), p("r2.bgzf"), True, sink, **kw),
@@ -351,9 +372,13 @@ def main():
             print(mode, "parent_align_file_plain", json.dumps(rows["parent_align_file_plain"]), flush=True)
         for key, fn in configs.items():
             rows[key] = measure(lambda: (bytes_out.__setitem__(0, 0), fn()), a.runs, n4)
-            rows[key]["sam_bytes"] = int(bytes_out[0]); sizes.add(bytes_out[0])
+            rows[key]["sam_bytes"] = int(bytes_out[0])
+            if key != "align_files_bam_keep_rg":                   # (its records carry RG:Z tags: more text)
+                sizes.add(bytes_out[0])
             if key != "align_file_plain":
                 rows[key]["parser"] = reads_last_counts()
+            if key == "align_files_bam_keep_rg":
+                rows[key]["file_bytes"] = os.path.getsize(p("rg.bam"))
             if key == "align_files_bam":
                 rows[key]["file_bytes"] = os.path.getsize(p("bam")); rows[key]["bgzf_fastq_file_bytes"] = os.path.getsize(p("fq.bgzf"))
             print(mode, key, json.dumps(rows[key]), flush=True)
@@ -365,7 +390,13 @@ def main():
     os.rmdir(tmp)
     line = json.dumps(result)
     print(line)
-    if a.out:
+    if a.out and a.out_key:
+        with open(a.out) as f:
+            whole = json.loads(f.read())
+        whole[a.out_key] = result
+        with open(a.out, "w") as f:
+            f.write(json.dumps(whole) + "\n")
+    elif a.out:
         with open(a.out, "w") as f:
             f.write(line + "\n")
 
