@@ -622,6 +622,7 @@ class Aligner:
             if self.long_reads:
                 nat.set_max_qlen(EXT_LONG_MAX)
         nat.set_reseed(self.reseed if self.reseed.enable else None)
+        nat.set_index_format(*getattr(self, "_index_format", ("bai", 14)))
         nat.set_output(*getattr(self, "_out_fmt", ("sam", 1)))
         if getattr(self, "_out_fmt", ("sam", 1))[0] == "bam_sorted":
             nat.set_sort(*self._sort_knobs)
@@ -629,10 +630,11 @@ class Aligner:
         return nat
 
     def align_file(self, reads_fa: str, out, batch_reads: int = 0, paired: bool = False, chunk_bases: int = 0, fmt: str = "sam", level: int = 1,
-                   sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None) -> int:
-        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None:
+                   sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
+                   index_format: str = "bai", csi_min_shift: int = 14) -> int:
+        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14:
             return self._align_bam(lambda o: self.align_file(reads_fa, o, batch_reads=batch_reads, paired=paired, chunk_bases=chunk_bases), out, fmt, level,
-                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics)
+                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift)
         """out: a text or binary file object.  Batches are cut the way the reference's bseq_read cuts them (src/bwa.c, called with
         chunk_size * n_threads = 10 Mbases per thread, or -K, src/fastmap.c:527): reads are added until the batch holds at least
         chunk_bases bases and an even number of reads -- in paired mode the insert-size statistics are those of the batch, so the
@@ -708,13 +710,19 @@ class Aligner:
                 out.write(self.align_batch(rs.slice(b, e), id0=b, paired=paired, as_bytes="view" if binary else False))   # (binary: the library's buffer, uncopied)
         return n
 
-    def _align_bam(self, run, out, fmt: str, level: int, sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None) -> int:
+    def _align_bam(self, run, out, fmt: str, level: int, sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
+                   index_format: str = "bai", csi_min_shift: int = 14) -> int:
         """fmt="bam" of align_file / align_files: the header members, the batches' members (`run` with the native aligner's output switched; the Python
         loop's batches converted here), the end-of-file member.  The file is written through a shim that drops the SAM header `run` writes first.
         sort=True: the batches become sorted runs and the members are those of the coordinate-sorted file, written at the end of the input; `index` (a path or
         a binary file object) receives its .bai.  markdup=True (needs sort=True): flag 0x400 on every record of every duplicate template (Picard MarkDuplicates'
-        rules); self.markdup_counts holds the counts afterwards and `markdup_metrics` (a path or a text file object) receives a Picard-style table."""
-        from .lib import bgzf_eof
+        rules); self.markdup_counts holds the counts afterwards and `markdup_metrics` (a path or a text file object) receives a Picard-style table.
+        index_format="csi" (needs sort=True): `index` receives a .csi in place of the .bai, with bins of 2^csi_min_shift bases (10 .. 24) -- what a
+        reference with a contig of 2^29 bases or more needs; the BAM bytes do not depend on it."""
+        from .lib import bgzf_eof, index_format_code
+        index_format_code(index_format, csi_min_shift, "align_file")          # (csi_min_shift without "csi", a shift outside 10 .. 24: before anything is touched)
+        if index_format != "bai" and not sort:
+            raise ValueError(f'index_format="{index_format}" needs sort=True: only a coordinate-sorted file has an index')
         if (markdup or markdup_metrics is not None) and not sort:
             raise ValueError("markdup=True needs sort=True: duplicates are marked where the sorted file is written" if markdup else "markdup_metrics needs markdup=True and sort=True")
         if markdup_metrics is not None and not markdup:
@@ -748,6 +756,7 @@ class Aligner:
             self._sort_knobs = (int(sort_mem or 0), sort_tmp, int(sort_window or 0))
         self._out_fmt = ("bam_sorted" if sort else "bam", level)
         self._markdup = bool(markdup)
+        self._index_format = (index_format, int(csi_min_shift))
         try:
             n = run(shim)
             if markdup:
@@ -759,6 +768,7 @@ class Aligner:
         finally:
             self._out_fmt = ("sam", 1)
             self._markdup = False
+            self._index_format = ("bai", 14)
             nat = getattr(self, "_native", None)
             if nat is not None:
                 nat.set_output("sam", 1)
@@ -768,8 +778,8 @@ class Aligner:
         if index is not None:
             nat = self._native_aligner() if n == 0 else self._native
             if n == 0:                                            # (no run was made: the index of a file without records)
-                nat.set_output("bam_sorted", level); nat.set_output("sam", 1)
-            bai = nat.sort_index(self._bam_header_bytes)
+                nat.set_index_format(index_format, int(csi_min_shift)); nat.set_output("bam_sorted", level); nat.set_output("sam", 1)
+            bai = nat.sort_index(self._bam_header_bytes)                 # (the bytes of the format the run was made under: .bai or .csi)
             if hasattr(index, "write"):
                 index.write(bai)
             else:
@@ -785,7 +795,8 @@ class Aligner:
         return n
 
     def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
-                    sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None, keep_rg: bool = False) -> int:
+                    sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None, keep_rg: bool = False,
+                    index_format: str = "bai", csi_min_shift: int = 14) -> int:
         """align_file for the files users have (bmh_aligner_run_files): `reads` (and `mates`: the second file of a pair, which implies paired) may be
         multi-line FASTA or FASTQ, plain, gzip or BGZF, a regular file or a pipe; or `reads` alone is a BAM file (unaligned, or grouped by read name: recognised
         from its bytes, pairs from flag 0x1 of its records -- paired=True on a BAM without it is refused).  Batches are cut by align_file's rules (-t, -K, the 150 Mbase floor for
@@ -808,16 +819,17 @@ class Aligner:
             self._keep_rg = True
             try:
                 return self.align_files(reads, None, out=out, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads, fmt=fmt, level=level, sort=sort, index=index,
-                                        sort_mem=sort_mem, sort_tmp=sort_tmp, sort_window=sort_window, markdup=markdup, markdup_metrics=markdup_metrics, keep_rg=True)
+                                        sort_mem=sort_mem, sort_tmp=sort_tmp, sort_window=sort_window, markdup=markdup, markdup_metrics=markdup_metrics, keep_rg=True,
+                                        index_format=index_format, csi_min_shift=csi_min_shift)
             finally:
                 self._keep_rg = None
                 self._groups = None
                 nat = getattr(self, "_native", None)
                 if nat is not None:
                     nat.set_keep_rg(False)
-        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None:
+        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14:
             return self._align_bam(lambda o: self.align_files(reads, mates, out=o, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads, keep_rg=keep_rg), out, fmt, level,
-                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics)
+                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift)
         binary = "b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")
         paired = bool(paired or mates is not None)
         cb = 0
@@ -850,7 +862,8 @@ class Aligner:
         return int(self.last_stats.n_reads)
 
     def align_groups(self, groups, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
-                     sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None) -> int:
+                     sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
+                     index_format: str = "bai", csi_min_shift: int = 14) -> int:
         """several read groups -- a sample's lanes and libraries -- into one output (bmh_aligner_run_groups).  groups: [(rg_line, reads, mates or None), ...]; every
         rg_line is unescaped and checked as -R's value is, reads / mates are what align_files takes (one file or R1 + R2; plain, gzip or BGZF; FASTA or FASTQ; or
         one BAM, whose own @RG lines and RG tags stay ignored: align_files(keep_rg=True) is the run that keeps them, and the two do not combine).  Group g's records are byte for byte those of align_files(reads_g, mates_g) alone under -R rg_g, and
@@ -879,9 +892,9 @@ class Aligner:
             raise NotImplementedError("align_groups needs the native pipeline (BMH_ALIGNER_NATIVE=0 and profile runs write batch after batch)")
         self._groups = parsed
         try:
-            if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None:
+            if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14:
                 return self._align_bam(lambda o: self._run_groups(parsed, libs, o, paired, chunk_bases, batch_reads), out, fmt, level,
-                                       sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics)
+                                       sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift)
             return self._run_groups(parsed, libs, out, paired, chunk_bases, batch_reads)
         finally:
             self._groups = None

@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = [
     "bmh_bam_markdup_groups_device", "bmh_bam_markdup_groups_host", "bmh_bam_sorted_file_markdup_groups_device", "bmh_bam_sorted_file_markdup_groups_host",
     "bmh_aligner_markdup_library_counts", "bmh_aligner_run_groups",
     "bmh_bam_reads_groups_device", "bmh_bam_reads_groups_host", "bmh_bam_header_read_groups", "bmh_format_sam_groups", "bmh_aligner_set_keep_rg",
+    "bmh_aligner_set_index_format", "bmh_bam_sorted_file_ex_device", "bmh_bam_sorted_file_ex_host",
 ]
 
 
@@ -469,20 +470,44 @@ def bam_markdup(records: bytes, host: bool = False, read_groups=None) -> tuple:
         L.bmh_free(out)
 
 
-def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False, markdup: bool = False, read_groups=None) -> tuple:
+INDEX_BAI, INDEX_CSI = 0, 1
+
+
+def index_format_code(index_format, csi_min_shift, what: str) -> tuple:
+    """the keywords index_format ("bai" or "csi") and csi_min_shift (10 .. 24, with "csi" only) of the sorting calls -> (BMH_INDEX_*, min_shift); ValueError otherwise"""
+    if index_format not in ("bai", "csi"):
+        raise ValueError(f"{what}: index_format {index_format!r}: bai or csi")
+    if not isinstance(csi_min_shift, (int, np.integer)) or isinstance(csi_min_shift, bool):
+        raise ValueError(f"{what}: csi_min_shift {csi_min_shift!r}: an integer in 10 .. 24")
+    if index_format != "csi":
+        if csi_min_shift != 14:
+            raise ValueError(f'{what}: csi_min_shift={csi_min_shift} needs index_format="csi" (a BAI index has no other than 14)')
+        return INDEX_BAI, 14
+    if not 10 <= csi_min_shift <= 24:
+        raise ValueError(f"{what}: csi_min_shift {csi_min_shift}: a CSI index takes 10 .. 24 (14 is BAI's)")
+    return INDEX_CSI, int(csi_min_shift)
+
+
+def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False, markdup: bool = False, read_groups=None,
+                    index_format: str = "bai", csi_min_shift: int = 14) -> tuple:
     """bmh_bam_sorted_file_device (host=True: _host): (the complete sorted BAM file -- header members, the records in coordinate order in windows of `window`
     records (0: about 64 MiB), the end-of-file member --, its .bai index).  contigs: (name, length) pairs; both forms give the same bytes.
     markdup=True (bmh_bam_sorted_file_markdup_*): `records` come in the writer's order, the duplicates among them are marked (bam_markdup's rules) and the counts come third.
-    read_groups (needs markdup=True): as bam_markdup takes them -- duplicates per library, and the counts gain "libraries"."""
+    read_groups (needs markdup=True): as bam_markdup takes them -- duplicates per library, and the counts gain "libraries".
+    index_format="csi" (bmh_bam_sorted_file_ex_*): the second element is the .csi index -- BGZF-compressed, bins of 2^csi_min_shift bases (10 .. 24) at the depth the
+    longest contig asks for --, contigs may hold up to 2^31 - 1 bases (with markdup=True up to 2^30 - 2^24) and the BAM bytes are those of the "bai" call."""
     if read_groups is not None and not markdup:
         raise ValueError("bam_sorted_file: read_groups needs markdup=True (they decide which templates may be duplicates of each other)")
+    ix_code, ix_shift = index_format_code(index_format, csi_min_shift, "bam_sorted_file")
     L = load_library()
     records = bytes(records)
     L.bmh_free.argtypes = [C.c_void_p]
     names = (C.c_char_p * max(len(contigs), 1))(*[c[0].encode() for c in contigs])
     lens = np.ascontiguousarray([c[1] for c in contigs] or [0], dtype=np.int64)
-    if ((lens < 0) | (lens >= 1 << 29)).any():
+    if ix_code == INDEX_BAI and ((lens < 0) | (lens >= 1 << 29)).any():
         raise ValueError("bam_sorted_file: a BAI index holds contigs below 2^29 bases (CSI is not written)")
+    if ((lens < 0) | (lens >= 1 << 31)).any():
+        raise ValueError("bam_sorted_file: BAM and its CSI index hold contigs of at most 2^31 - 1 bases")
     lens = lens.astype(np.int32)
     bam, bai, nb, ni = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
     head = [header_text.encode(), len(contigs), names, lens.ctypes.data, records, len(records), int(level), int(window)]
@@ -490,16 +515,31 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
     sig = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_uint32]
     out = [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p]
     counts = (C.c_uint64 * 8)()
-    if markdup:
+    if ix_code == INDEX_CSI:                                  # the one entry point that takes everything: counts and library counts always have their place
+        ids, lib, ng, lib_names = _library_table(read_groups) if read_groups is not None else (None, None, 0, [])
+        lc = (C.c_uint64 * (8 * max(len(lib_names), 1)))()
+        head += [ix_code, ix_shift, 1 if markdup else 0, ids, lib, ng]; sig += [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int]
+        tail += [counts if markdup else None, lc if read_groups is not None else None]; out += [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    elif markdup:
         tail.append(counts); out.append(C.POINTER(C.c_uint64))
     grp = ""
-    if read_groups is not None:
+    if read_groups is not None and ix_code != INDEX_CSI:
         ids, lib, ng, lib_names = _library_table(read_groups)
         lc = (C.c_uint64 * (8 * max(len(lib_names), 1)))()
         head += [ids, lib, ng]; sig += [C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int]
         tail.append(lc); out.append(C.POINTER(C.c_uint64))
         grp = "_groups"
-    if host:
+    if ix_code == INDEX_CSI:
+        if host:
+            fn = L.bmh_bam_sorted_file_ex_host
+            fn.argtypes = sig + out
+            rc = fn(*head, *tail)
+        else:
+            import torch
+            fn = L.bmh_bam_sorted_file_ex_device
+            fn.argtypes = sig + [C.c_void_p] + out
+            rc = fn(*head, torch.cuda.current_stream().cuda_stream, *tail)
+    elif host:
         fn = getattr(L, "bmh_bam_sorted_file_markdup" + grp + "_host") if markdup else L.bmh_bam_sorted_file_host
         fn.argtypes = sig + out
         rc = fn(*head, *tail)
@@ -684,6 +724,14 @@ class NativeAligner:
         if L.bmh_aligner_set_sort(self.handle, int(mem_bytes), os.fsencode(tmp_dir) if tmp_dir is not None else None, int(window_records)) != 0:
             raise ValueError("bmh_aligner_set_sort: " + _err(L))
 
+    def set_index_format(self, index_format: str = "bai", csi_min_shift: int = 14) -> None:
+        """bmh_aligner_set_index_format: the index of the sorted runs that follow ("bai", or "csi" with bins of 2^csi_min_shift bases); before set_output("bam_sorted")"""
+        L = load_library()
+        code, shift = index_format_code(index_format, csi_min_shift, "bmh_aligner_set_index_format")
+        L.bmh_aligner_set_index_format.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        if L.bmh_aligner_set_index_format(self.handle, code, shift) != 0:
+            raise ValueError("bmh_aligner_set_index_format: " + _err(L))
+
     def set_markdup(self, on: bool = True) -> None:
         """bmh_aligner_set_markdup: the sorted runs that follow mark duplicates (refused unless the output is "bam_sorted"; any other set_output switches it off)"""
         L = load_library()
@@ -720,7 +768,7 @@ class NativeAligner:
         return dict(decision_ms=t[0], window_flags_ms=t[1], entries_d2h_bytes=int(t[2]))
 
     def sort_index(self, base_offset: int) -> bytes:
-        """bmh_aligner_sort_index: the .bai bytes of the last sorted run; base_offset: the bytes written before the sink's first (the header members)"""
+        """bmh_aligner_sort_index: the .bai (or, for a run under set_index_format("csi"), .csi) bytes of the last sorted run; base_offset: the bytes written before the sink's first (the header members)"""
         L = load_library()
         L.bmh_aligner_sort_index.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), _u64p]
         L.bmh_free.argtypes = [C.c_void_p]

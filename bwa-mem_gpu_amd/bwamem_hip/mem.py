@@ -10,11 +10,15 @@ stdout), --long-reads (reads of up to 16 384 bases), --device (the torch device,
 compressed on the device; -o is unchanged, a name ending in .bam does not switch formats), --bam-level 0|1 (stored, or LZ77 + dynamic Huffman; 1),
 --sort (implies --bam: the records in coordinate order, `samtools sort`'s, sorted on the device; with -o PATH the BAI index goes to PATH.bai, --index PATH
 names it otherwise, and on stdout without --index none is written), --sort-mem BYTES (records kept in host memory before the sorted runs spill to a temporary
-file; 4 GiB), --sort-tmp DIR (where that file lives; $TMPDIR, else /tmp), --markdup (needs --sort: flag 0x400 on every record of every duplicate template,
+file; 4 GiB), --sort-tmp DIR (where that file lives; $TMPDIR, else /tmp), --csi (implies --sort: the index is a CSI index, which a reference with a contig
+of 2^29 bases or more needs -- a BAI cannot hold one, and --sort alone refuses it; with -o PATH it goes to PATH.csi, --index PATH names it otherwise; the BAM
+bytes are those of --sort), --csi-min-shift N (needs --csi: the index's smallest bins and windows hold 2^N bases, 10 .. 24; 14, as in a BAI), --markdup
+(needs --sort: flag 0x400 on every record of every duplicate template,
 decided on the device by Picard MarkDuplicates' rules -- the unclipped 5' ends and strands of a template's primary lines are the key, the sum of the base
 qualities >= 15 the score, ties go to the template that came first in the input, a fragment is a duplicate wherever a pair has an end; unlike Picard and
 `samtools markdup` on coordinate-sorted input the secondary and supplementary lines of a duplicate template are flagged too; no optical duplicates, no
-library-size estimate, nothing is removed) and --markdup-metrics PATH (a Picard-style table of the counts, one row per library).  --rg LINE opens a read group:
+library-size estimate, nothing is removed; with --csi a contig beyond 2^30 - 2^24 bases is refused for --markdup, by name) and --markdup-metrics PATH
+(a Picard-style table of the counts, one row per library).  --rg LINE opens a read group:
 LINE is an @RG line as -R takes it, and the one or two files that follow it, up to the next --rg, are that group's input (Aligner.align_groups): a sample's lanes
 and libraries go into one output, every record with its group's RG:Z, the header with every @RG line, and --markdup calls duplicates within a library (the LB
 field; groups with one LB are lanes of one library) only.  -p applies to every group; --rg and -R exclude each other.  --keep-rg keeps the read groups of the
@@ -51,6 +55,7 @@ def main(argv=None) -> int:
     bam, bam_level = False, 1
     sort, index_path, sort_mem, sort_tmp = False, None, None, None
     markdup, metrics_path = False, None
+    csi, csi_shift = False, None
     keep_rg = False
     groups = []                                                     # --rg LINE: [line, files...]; the positionals behind it are its files
     i = 0
@@ -72,6 +77,14 @@ def main(argv=None) -> int:
             sort = bam = True
         elif a == "--markdup":
             markdup = True
+        elif a == "--csi":
+            csi = sort = bam = True
+        elif a == "--csi-min-shift":
+            if i + 1 >= len(argv) or not argv[i + 1].isdigit() or not 10 <= int(argv[i + 1]) <= 24:
+                print("[bwamem_hip.mem] option --csi-min-shift needs a number in 10 .. 24", file=sys.stderr)
+                return 2
+            csi_shift = int(argv[i + 1])
+            i += 1
         elif a == "--keep-rg":
             keep_rg = True
         elif a == "--rg":
@@ -146,8 +159,11 @@ def main(argv=None) -> int:
     if metrics_path is not None and not markdup:
         print("[bwamem_hip.mem] --markdup-metrics needs --markdup", file=sys.stderr)
         return 2
+    if csi_shift is not None and not csi:
+        print("[bwamem_hip.mem] --csi-min-shift needs --csi (a BAI index has one bin size)", file=sys.stderr)
+        return 2
     if sort and index_path is None and out_path is not None:
-        index_path = out_path + ".bai"
+        index_path = out_path + (".csi" if csi else ".bai")
     from .aligner import Aligner
     try:
         al = Aligner(prefix, device=device, long_reads=long_reads)
@@ -163,6 +179,8 @@ def main(argv=None) -> int:
             fmt_kw.update(sort=True, index=index_path, sort_mem=sort_mem, sort_tmp=sort_tmp)
         if markdup:
             fmt_kw.update(markdup=True, markdup_metrics=metrics_path)
+        if csi:
+            fmt_kw.update(index_format="csi", csi_min_shift=14 if csi_shift is None else csi_shift)
         done = False
         if groups:
             al.align_groups([(g[0], g[1], g[2] if len(g) == 3 else None) for g in groups], out=out, paired=interleaved, **fmt_kw)

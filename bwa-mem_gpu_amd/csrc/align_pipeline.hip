@@ -880,6 +880,7 @@ struct bmh_aligner {
 	uint64_t bam_pairs_bases = 0; int bam_pairs_lanes = 0;   // bmh_aligner_set_bam_pairs
 	bool keep_rg = false; bmh_rg_header_fn rg_header = nullptr; void *rg_user = nullptr;      // bmh_aligner_set_keep_rg
 	bsr_store_t store; bsr_index_t sort_ix; uint32_t sort_window = 0;      // sorted BAM output: the runs of the run in progress, the index of the last one, the window
+	int ix_format = BSR_IX_BAI, ix_shift = BSR_LIN_SHIFT;                  // bmh_aligner_set_index_format: the index of the sorted runs that follow
 	uint64_t dup_counts[BDP_N_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0}; bool dup_valid = false;      // duplicate marking: the counts of the last marked run
 	std::vector<uint64_t> lib_counts;                    // ... with read groups: the same eight per library (bmh_aligner_markdup_library_counts)
 	double dup_times[3] = {0, 0, 0};                     // ... its decision and its windows' flag steps in ms, the bytes its batches' ordinals and entries took on their way down
@@ -914,9 +915,17 @@ int bmh_aligner_set_output(bmh_aligner_t *h, int format, int level)
 	if (!h) { bmh_set_error("bmh_aligner_set_output: null aligner"); return BMH_EINVAL; }
 	if (format != BMH_OUT_SAM && format != BMH_OUT_BAM && format != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_output: format %d (BMH_OUT_SAM, BMH_OUT_BAM or BMH_OUT_BAM_SORTED)", format); return BMH_EINVAL; }
 	if (format != BMH_OUT_SAM && level != 0 && level != 1) { bmh_set_error("bmh_aligner_set_output: level %d (0 or 1)", level); return BMH_EINVAL; }
-	if (format == BMH_OUT_BAM_SORTED) { h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), "sorted BAM output")); }
+	if (format == BMH_OUT_BAM_SORTED) { h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), "sorted BAM output", h->ix_format, h->ix_shift)); }
 	if (format != BMH_OUT_BAM_SORTED) h->a.markdup = false;          // (duplicates are marked in sorted output only: the option goes with the format)
 	h->a.out_fmt = format; h->a.out_level = level;
+	return BMH_OK;
+}
+
+int bmh_aligner_set_index_format(bmh_aligner_t *h, int index_format, int min_shift)
+{
+	if (!h) { bmh_set_error("bmh_aligner_set_index_format: null aligner"); return BMH_EINVAL; }
+	RCK(bsr_index_format_check(index_format, min_shift, "bmh_aligner_set_index_format"));
+	h->ix_format = index_format; h->ix_shift = index_format == BSR_IX_CSI ? min_shift : (int)BSR_LIN_SHIFT;
 	return BMH_OK;
 }
 
@@ -947,6 +956,7 @@ int bmh_aligner_set_markdup(bmh_aligner_t *h, int on)
 {
 	if (!h) { bmh_set_error("bmh_aligner_set_markdup: null aligner"); return BMH_EINVAL; }
 	if (on && h->a.out_fmt != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_markdup: duplicates are marked in sorted output (bmh_aligner_set_output with BMH_OUT_BAM_SORTED comes first)"); return BMH_EINVAL; }
+	if (on) RCK(bsr_markdup_contigs(h->a.n_contigs, h->a.len.data(), h->a.name_ptr.data(), "bmh_aligner_set_markdup"));      // (only a CSI run can hold such a contig)
 	h->a.markdup = on != 0;
 	return BMH_OK;
 }
@@ -983,7 +993,8 @@ int bmh_aligner_sort_index(bmh_aligner_t *h, uint64_t base_offset, uint8_t **bai
 	*bai = nullptr; *bai_bytes = 0;
 	if (h->sort_ix.lin.empty()) { bmh_set_error("bmh_aligner_sort_index: no sorted run has been made (bmh_aligner_set_output with BMH_OUT_BAM_SORTED comes first)"); return BMH_EINVAL; }
 	if (!h->sort_ix.valid) { bmh_set_error("bmh_aligner_sort_index: the last sorted run failed before its file was complete: there is no index of it"); return BMH_EINVAL; }
-	std::string s; h->sort_ix.bai(base_offset, s);
+	std::string s;
+	RCK(h->sort_ix.bytes(base_offset, s));                    // (.bai or .csi: the format the run was made under)
 	uint8_t *o = (uint8_t *)malloc(s.size() + 1);
 	if (!o) { bmh_set_error("bmh_aligner_sort_index: out of memory"); return BMH_ENOMEM; }
 	memcpy(o, s.data(), s.size());
@@ -1023,7 +1034,8 @@ struct out_stage_t {
 	int lib_of(int group) const { return group >= 0 && (size_t)group < h->a.groups.lib.size() ? (int)h->a.groups.lib[(size_t)group] : -1; }
 	int emit(const void *p, size_t n) { if (n && sink(user, (const char *)p, n) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; } n_bytes += n; return BMH_OK; }
 	// (the index is valid again once the merge has written the whole file)
-	int begin() { if (fmt == BMH_OUT_BAM_SORTED) { h->dup_valid = false; h->dup_times[0] = h->dup_times[1] = h->dup_times[2] = 0; h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), fn)); h->sort_ix.valid = false; } return BMH_OK; }
+	int begin() { if (fmt == BMH_OUT_BAM_SORTED) { h->dup_valid = false; h->dup_times[0] = h->dup_times[1] = h->dup_times[2] = 0; h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), fn, h->ix_format, h->ix_shift)); h->sort_ix.valid = false;
+		if (h->a.markdup) RCK(bsr_markdup_contigs(h->a.n_contigs, h->a.len.data(), h->a.name_ptr.data(), fn)); } return BMH_OK; }
 	int device_batch(const result_t &R)
 	{
 		if (fmt != BMH_OUT_BAM_SORTED) return emit(R.text.p, (size_t)R.text_len);

@@ -6,7 +6,10 @@
 //             read's primary line first and read 1's records before read 2's); a template's primary lines are its records without 0x100 / 0x800: one for an
 //             unpaired read, two (0x40, 0x80) for a pair
 //   end word  of a mapped primary line: u = the unclipped 5' coordinate -- forward: pos minus the leading S and H lengths; reverse: bsr_end - 1 plus the trailing
-//             S and H lengths --, word = (uint64)refID << 32 | (uint32)(u + 2^30) << 1 | reverse (contigs stay below 2^29 bases, so the bias cannot overflow)
+//             S and H lengths --, word = (uint64)refID << 32 | (uint32)(u + 2^30) << 1 | reverse: u + 2^30 must lie in [0, 2^31).  A record lies
+//             inside its contig and this aligner clips at most 16 384 bases, so contigs of up to BDP_MAX_CONTIG = 2^30 - 2^24 bases (16 M of slack on either
+//             side) keep it there; a run with a longer contig is refused before anything is marked (bsr_markdup_contigs).  Under a BAI index contigs stay
+//             below 2^29 anyway
 //   kind      pair: both primary lines mapped; fragment: an unpaired mapped read, or a pair with exactly one mapped primary line; none: everything else
 //   score     the sum of the base qualities >= 15 over the template's primary lines; a record without qualities (first byte 0xff) scores 0
 //   pairs     key (smaller end word, larger end word); among the pairs of one key the highest score stays, ties go to the smallest template ordinal (input
@@ -24,7 +27,7 @@
 #include "bam_sort_core.h"
 
 enum { BDP_NONE = 0, BDP_FRAG = 1, BDP_PAIR = 2, BDP_QMIN = 15 };
-enum { BDP_LIB_SHIFT = 56, BDP_MAX_LIBS = 255, BDP_MAX_REF = 1 << 24 };
+enum { BDP_LIB_SHIFT = 56, BDP_MAX_LIBS = 255, BDP_MAX_REF = 1 << 24, BDP_MAX_CONTIG = (1 << 30) - (1 << 24) };
 // what bdp_entry_lib says of a template
 enum { BDP_E_OK = 0, BDP_E_TEMPLATE = 1, BDP_E_NO_RG = 2, BDP_E_RG_UNKNOWN = 3 };
 

@@ -21,12 +21,23 @@ struct bsr_index_t {
 	std::vector<bsr_head_t> heads;
 	uint64_t file_pos = 0;                                         // bytes handed to the sink so far
 	bool valid = false;                                            // the index of a whole file (init: of one without records); false while a run builds it and after it failed
-	int init(int n_contigs, const int32_t *contig_len, const char *fn);
+	int format = BSR_IX_BAI, min_shift = BSR_LIN_SHIFT, depth = BSR_BAI_DEPTH;      // the binning scheme: BAI's (14, 5), or CSI's min_shift and the depth its longest contig asks for
+	// BAI: contigs below 2^29 bases; CSI: any length an int32 holds, min_shift in 10 .. 24, and a lin array that fits (counted before it is allocated)
+	int init(int n_contigs, const int32_t *contig_len, const char *fn, int format = BSR_IX_BAI, int min_shift = BSR_LIN_SHIFT);
 	// one window on the host: its n records recs [soff[n]], its members' offsets moff [n_members + 1]
 	void window_host(const uint8_t *recs, const uint64_t *soff, uint32_t n, const uint64_t *moff);
 	// the .bai bytes; base_offset: bytes in the file before the sink's first
 	void bai(uint64_t base_offset, std::string &out) const;
+	// the .csi bytes of a CSI index: the index as BGZF members (level 1) and the end-of-file member
+	int csi(uint64_t base_offset, std::string &out) const;
+	// the index file of `format`
+	int bytes(uint64_t base_offset, std::string &out) const { if (format == BSR_IX_CSI) return csi(base_offset, out); bai(base_offset, out); return 0; }
 };
+
+// duplicate marking keeps u + 2^30 in 31 bits (csrc/bam_dup_core.h): every contig at most BDP_MAX_CONTIG bases, else refused naming the first longer one
+int bsr_markdup_contigs(int n_contigs, const int32_t *contig_len, const char *const *contig_names, const char *fn);
+// format and min_shift as the entry points take them: BMH_EINVAL with a message, or BMH_OK
+int bsr_index_format_check(int format, int min_shift, const char *fn);
 
 // Sorted runs kept until the end of the input: the records in host memory up to mem_bytes, beyond that in one unnamed temporary file; keys and offsets
 // (16 bytes per record) always in memory.  With duplicate marking (csrc/bam_dup_core.h) a run also keeps every record's template ordinal within its batch (tpl, 4 bytes

@@ -1,5 +1,5 @@
-// Sorted BAM output on the host: the walk over a record stream, the host form of the sort (std::stable_sort), the index pass over a window and the .bai bytes
-// (csrc/bam_sort_core.h's rules), the run store of csrc/align_pipeline.hip, and bmh_bam_sort_host / bmh_bam_sorted_file_host.
+// Sorted BAM output on the host: the walk over a record stream, the host form of the sort (std::stable_sort), the index pass over a window and the .bai or .csi
+// bytes (csrc/bam_sort_core.h's rules), the run store of csrc/align_pipeline.hip, and bmh_bam_sort_host / bmh_bam_sorted_file_host / _ex_host.
 #include <errno.h>
 #include <fcntl.h>
 #include <stdlib.h>
@@ -7,6 +7,7 @@
 #include <unistd.h>
 #include <algorithm>
 #include <map>
+#include <new>
 #include <numeric>
 #include "bam_sort.h"
 #include "bam_dup.h"
@@ -40,16 +41,50 @@ void bsr_sort_host(const uint8_t *recs, const std::vector<uint64_t> &off, std::v
 	for (size_t j = 0; j < n; ++j) keys[j] = k[ord[j]];
 }
 
-int bsr_index_t::init(int n_contigs, const int32_t *contig_len, const char *fn)
+int bsr_index_format_check(int format, int min_shift, const char *fn)
+{
+	if (format != BSR_IX_BAI && format != BSR_IX_CSI) { bmh_set_error("%s: index format %d (BMH_INDEX_BAI or BMH_INDEX_CSI)", fn, format); return BMH_EINVAL; }
+	if (format == BSR_IX_CSI && (min_shift < BSR_CSI_SHIFT_MIN || min_shift > BSR_CSI_SHIFT_MAX)) {
+		bmh_set_error("%s: a CSI index takes a min_shift of %d .. %d (14 is BAI's), not %d", fn, BSR_CSI_SHIFT_MIN, BSR_CSI_SHIFT_MAX, min_shift); return BMH_EINVAL;
+	}
+	return BMH_OK;                                        // (BAI: min_shift is not read, it is 14)
+}
+
+int bsr_markdup_contigs(int n_contigs, const int32_t *contig_len, const char *const *contig_names, const char *fn)
+{
+	for (int c = 0; c < n_contigs; ++c)
+		if (contig_len[c] > BDP_MAX_CONTIG) {
+			bmh_set_error("%s: contig %d (%s) has %lld bases: duplicates are marked on contigs of at most 2^30 - 2^24 bases (the duplicate key holds an unclipped end in 31 bits); sort without marking",
+			              fn, c, contig_names && contig_names[c] ? contig_names[c] : "?", (long long)contig_len[c]);
+			return BMH_EINVAL;
+		}
+	return BMH_OK;
+}
+
+int bsr_index_t::init(int n_contigs, const int32_t *contig_len, const char *fn, int fmt, int shift)
 {
 	n_ref = n_contigs; n_win.clear(); lin_off.assign(1, 0); heads.clear(); file_pos = 0; valid = false;
+	const int rc = bsr_index_format_check(fmt, shift, fn);
+	if (rc != BMH_OK) return rc;
+	format = fmt; min_shift = fmt == BSR_IX_CSI ? shift : (int)BSR_LIN_SHIFT; depth = BSR_BAI_DEPTH;
+	int64_t longest = 0;
 	for (int c = 0; c < n_contigs; ++c) {
-		if (contig_len[c] < 0 || contig_len[c] >= BSR_MAX_CONTIG) {
+		if (fmt == BSR_IX_BAI && (contig_len[c] < 0 || contig_len[c] >= BSR_MAX_CONTIG)) {
 			bmh_set_error("%s: contig %d has %lld bases: a BAI index holds contigs below 2^29 bases (CSI is not written)", fn, c, (long long)(uint32_t)contig_len[c]); return BMH_EINVAL;
 		}
-		n_win.push_back(bsr_n_windows(contig_len[c])); lin_off.push_back(lin_off.back() + n_win.back());
+		if (contig_len[c] < 0) { bmh_set_error("%s: contig %d has %lld bases: BAM and its CSI index hold contigs of at most 2^31 - 1", fn, c, (long long)(uint32_t)contig_len[c]); return BMH_EINVAL; }
+		if (contig_len[c] > longest) longest = contig_len[c];
+		n_win.push_back(bsr_n_windows_at(contig_len[c], min_shift)); lin_off.push_back(lin_off.back() + n_win.back());
 	}
-	lin.assign(lin_off.back() + 1, ~0ull); counts.assign(2 * (size_t)n_ref + 1, 0);
+	if (fmt == BSR_IX_CSI) depth = bsr_csi_depth(longest, min_shift);
+	// (8 bytes a window, on the host and on the device: counted before either allocates)
+	if (lin_off.back() >= 1ull << 28) {
+		bmh_set_error("%s: the index would hold %llu windows of 2^%d bases (%llu bytes; at most 2^28 windows): choose a larger min_shift", fn, (unsigned long long)lin_off.back(), min_shift,
+		              8ull * (unsigned long long)lin_off.back());
+		return BMH_EINVAL;
+	}
+	try { lin.assign(lin_off.back() + 1, ~0ull); counts.assign(2 * (size_t)n_ref + 1, 0); }
+	catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory for %llu index windows", fn, (unsigned long long)lin_off.back()); return BMH_ENOMEM; }
 	valid = true;
 	return BMH_OK;
 }
@@ -57,39 +92,52 @@ int bsr_index_t::init(int n_contigs, const int32_t *contig_len, const char *fn)
 void bsr_index_t::window_host(const uint8_t *recs, const uint64_t *soff, uint32_t n, const uint64_t *moff)
 {
 	const uint64_t total = soff[n];
+	const bool csi = format == BSR_IX_CSI;
 	for (uint32_t j = 0; j < n; ++j) {
 		const uint8_t *rec = recs + soff[j], *prev = j ? recs + soff[j - 1] : nullptr;
 		const uint64_t v = bsr_voff(file_pos, moff, total, soff[j]);
 		const int32_t r = bsr_ref(rec);
-		if (bsr_chunk_head(rec, prev)) heads.push_back({r < 0 ? -1 : r, bsr_bin(rec), v});
+		const uint32_t nw = r >= 0 && r < n_ref ? n_win[r] : 1u;
+		if (csi) { if (bsr_csi_chunk_head(rec, prev, nw, min_shift, depth)) heads.push_back({r < 0 ? -1 : r, bsr_csi_rec_bin(rec, nw, min_shift, depth), v}); }
+		else if (bsr_chunk_head(rec, prev)) heads.push_back({r < 0 ? -1 : r, bsr_bin(rec), v});
 		if (r < 0 || r >= n_ref) { ++counts[2 * (size_t)n_ref]; continue; }
 		++counts[2 * (size_t)r + ((bsr_flag(rec) & 4u) ? 1 : 0)];
 		uint32_t lo, hi;
-		bsr_windows(rec, n_win[r], &lo, &hi);
+		bsr_windows_at(rec, n_win[r], min_shift, &lo, &hi);
 		for (uint32_t w = lo; w <= hi; ++w) { uint64_t &s = lin[lin_off[r] + w]; if (v < s) s = v; }
 	}
 	file_pos += moff[(total + BSR_PIECE - 1) / BSR_PIECE];
 }
+
+namespace {
+// a reference's chunks by bin, and the span of its records
+struct ix_ref_t { std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins; uint64_t beg = 0, end = 0; bool any = false; };
+// chunks: heads that continue the chunk before them (a window's first record) are dropped; a chunk ends where the next begins
+std::vector<ix_ref_t> ix_chunks(const bsr_index_t &ix, uint64_t sh)
+{
+	std::vector<ix_ref_t> refs((size_t)ix.n_ref);
+	std::vector<bsr_head_t> hs;
+	for (const bsr_head_t &h : ix.heads)
+		if (hs.empty() || hs.back().ref != h.ref || (h.ref >= 0 && hs.back().bin != h.bin)) hs.push_back(h);
+	for (size_t i = 0; i < hs.size(); ++i) {
+		if (hs[i].ref < 0 || hs[i].ref >= ix.n_ref) continue;
+		const uint64_t b = hs[i].beg + sh, e = (i + 1 < hs.size() ? hs[i + 1].beg : ix.file_pos << 16) + sh;
+		ix_ref_t &R = refs[(size_t)hs[i].ref];
+		R.bins[hs[i].bin].push_back({b, e});
+		if (!R.any) { R.any = true; R.beg = b; }
+		R.end = e;
+	}
+	return refs;
+}
+}   // namespace
 
 void bsr_index_t::bai(uint64_t base_offset, std::string &out) const
 {
 	const uint64_t sh = base_offset << 16;
 	auto u32 = [&](uint32_t v) { for (int k = 0; k < 4; ++k) out.push_back((char)(v >> (8 * k))); };
 	auto u64 = [&](uint64_t v) { for (int k = 0; k < 8; ++k) out.push_back((char)(v >> (8 * k))); };
-	// chunks: heads that continue the chunk before them (a window's first record) are dropped; a chunk ends where the next begins
-	struct ref_t { std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins; uint64_t beg = 0, end = 0; bool any = false; };
-	std::vector<ref_t> refs((size_t)n_ref);
-	std::vector<bsr_head_t> hs;
-	for (const bsr_head_t &h : heads)
-		if (hs.empty() || hs.back().ref != h.ref || (h.ref >= 0 && hs.back().bin != h.bin)) hs.push_back(h);
-	for (size_t i = 0; i < hs.size(); ++i) {
-		if (hs[i].ref < 0 || hs[i].ref >= n_ref) continue;
-		const uint64_t b = hs[i].beg + sh, e = (i + 1 < hs.size() ? hs[i + 1].beg : file_pos << 16) + sh;
-		ref_t &R = refs[(size_t)hs[i].ref];
-		R.bins[hs[i].bin].push_back({b, e});
-		if (!R.any) { R.any = true; R.beg = b; }
-		R.end = e;
-	}
+	typedef ix_ref_t ref_t;
+	const std::vector<ref_t> refs = ix_chunks(*this, sh);
 	out.clear();
 	out += "BAI\1"; u32((uint32_t)n_ref);
 	for (int r = 0; r < n_ref; ++r) {
@@ -108,6 +156,43 @@ void bsr_index_t::bai(uint64_t base_offset, std::string &out) const
 		for (uint32_t w = 0; w < n_intv; ++w) { const uint64_t v = lin[lin_off[r] + w]; if (v != ~0ull) last = v + sh; u64(last); }
 	}
 	u64(counts[2 * (size_t)n_ref]);
+}
+
+// "CSI\1" min_shift depth l_aux = 0 n_ref | per reference: n_bin, per bin (ascending, the pseudo-bin last): bin loffset n_chunk chunks | n_no_coor -- all of it
+// as BGZF members and the end-of-file member.  A bin's loffset is the linear value at its first window, a window without records taking that of the next window
+// that has some (htslib's back-fill; bai() above fills its holes forward): a lower bound on the first record that overlaps anything from the bin's start on
+int bsr_index_t::csi(uint64_t base_offset, std::string &out) const
+{
+	const uint64_t sh = base_offset << 16;
+	std::string raw;
+	auto u32 = [&](uint32_t v) { for (int k = 0; k < 4; ++k) raw.push_back((char)(v >> (8 * k))); };
+	auto u64 = [&](uint64_t v) { for (int k = 0; k < 8; ++k) raw.push_back((char)(v >> (8 * k))); };
+	const std::vector<ix_ref_t> refs = ix_chunks(*this, sh);
+	raw += "CSI\1"; u32((uint32_t)min_shift); u32((uint32_t)depth); u32(0); u32((uint32_t)n_ref);
+	std::vector<uint64_t> fill;
+	for (int r = 0; r < n_ref; ++r) {
+		const ix_ref_t &R = refs[(size_t)r];
+		if (!R.any) { u32(0); continue; }
+		fill.assign((size_t)n_win[r] + 1, ~0ull);
+		for (uint32_t w = n_win[r]; w-- > 0;) { const uint64_t v = lin[lin_off[r] + w]; fill[w] = v != ~0ull ? v + sh : fill[w + 1]; }
+		u32((uint32_t)R.bins.size() + 1);
+		for (const auto &kv : R.bins) {
+			int l = 0;
+			while (l < depth && kv.first < bsr_csi_level_first(depth, l)) ++l;
+			const uint64_t w0 = (uint64_t)(kv.first - bsr_csi_level_first(depth, l)) << (3 * l);
+			const uint64_t lo = w0 < n_win[r] ? fill[(size_t)w0] : ~0ull;
+			u32(kv.first); u64(lo != ~0ull ? lo : 0); u32((uint32_t)kv.second.size());
+			for (const auto &c : kv.second) { u64(c.first); u64(c.second); }
+		}
+		u32(bsr_csi_meta_bin(depth)); u64(0); u32(2); u64(R.beg); u64(R.end); u64(counts[2 * (size_t)r]); u64(counts[2 * (size_t)r + 1]);
+	}
+	u64(counts[2 * (size_t)n_ref]);
+	uint8_t *m = nullptr; uint64_t mb = 0;
+	const int rc = bmh_bgzf_deflate_host((const uint8_t *)raw.data(), raw.size(), 1, 0, &m, &mb);
+	if (rc != BMH_OK) return rc;
+	out.assign((const char *)m, mb); bmh_free(m);
+	out.append((const char *)bmh_bgzf_eof, 28);
+	return BMH_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the run store
@@ -200,14 +285,15 @@ extern "C" int bmh_bam_sort_host(const uint8_t *recs, uint64_t n_bytes, uint8_t 
 // header members, the sorted records in windows of `window` records (0: as many as hold about 64 MiB), the end-of-file member; and the index
 static int sorted_file_host(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
                             int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts,
-                            const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr)
+                            const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr, int format = BSR_IX_BAI, int min_shift = BSR_LIN_SHIFT)
 {
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
 	if (G && n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d references: with read groups a run holds at most 2^24 (the library takes the duplicate key's top byte)", fn, n_contigs); return BMH_EINVAL; }
 	bsr_index_t ix;
-	int rc = ix.init(n_contigs, contig_len, fn);
+	int rc = ix.init(n_contigs, contig_len, fn, format, min_shift);
 	if (rc != BMH_OK) return rc;
+	if (dup_counts && (rc = bsr_markdup_contigs(n_contigs, contig_len, contig_names, fn)) != BMH_OK) return rc;
 	std::vector<uint64_t> off, keys; std::vector<uint32_t> ord;
 	if ((rc = bsr_walk(recs, n_bytes, n_contigs, off, fn)) != BMH_OK) return rc;
 	std::vector<uint8_t> marked;                                   // duplicate marking: the flags are set before the sort (0x400 enters no key, bin or index)
@@ -245,7 +331,8 @@ static int sorted_file_host(const char *fn, const char *header_text, int n_conti
 		ix.window_host(buf.data(), soff.data(), (uint32_t)(b - a), moff.data());
 	}
 	file.append((const char *)bmh_bgzf_eof, 28);
-	std::string ib; ix.bai(base, ib);
+	std::string ib;
+	if ((rc = ix.bytes(base, ib)) != BMH_OK) return rc;
 	uint8_t *f = (uint8_t *)malloc(file.size() + 1), *i = (uint8_t *)malloc(ib.size() + 1);
 	if (!f || !i) { free(f); free(i); bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
 	memcpy(f, file.data(), file.size()); memcpy(i, ib.data(), ib.size());
@@ -277,4 +364,20 @@ extern "C" int bmh_bam_sorted_file_markdup_groups_host(const char *header_text, 
 	const int rc = bdp_table_make(G, rg_ids, rg_lib, n_groups, fn);
 	if (rc != BMH_OK) return rc;
 	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, bai, bai_bytes, counts, &G, lib_counts);
+}
+
+extern "C" int bmh_bam_sorted_file_ex_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                           int level, uint32_t window, int index_format, int min_shift, int markdup, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
+                                           uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts)
+{
+	const char *fn = "bmh_bam_sorted_file_ex_host";
+	if (markdup && !counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (!markdup && (rg_ids || rg_lib || n_groups)) { bmh_set_error("%s: read groups decide which templates may be duplicates of each other: they need markdup", fn); return BMH_EINVAL; }
+	int rc = bsr_index_format_check(index_format, min_shift, fn);
+	if (rc != BMH_OK) return rc;
+	bdp_table_t G;
+	const bool groups = rg_ids || rg_lib || n_groups;
+	if (groups && (rc = bdp_table_make(G, rg_ids, rg_lib, n_groups, fn)) != BMH_OK) return rc;
+	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, index, index_bytes, markdup ? counts : nullptr,
+	                        groups ? &G : nullptr, groups ? lib_counts : nullptr, index_format, min_shift);
 }

@@ -8,7 +8,8 @@
 //   index    one lane per record of a window whose members' sizes are known: the record's virtual offset, whether it begins a chunk, a 64-bit atomicMin on every
 //            16 KiB window it overlaps that the record before it does not (that one lies earlier in the file, so it has the smaller offset), and the counts --
 //            one atomicAdd per block where the block's records share a reference, which in a sorted file nearly every block does.  A scan and a second kernel
-//            compact the chunk heads.
+//            compact the chunk heads.  For a CSI index (bsr_index_marks<true>, bsr_index_heads<true>) the windows hold 2^min_shift bases and the heads are
+//            keyed on the CSI bin of the record's windows.
 //
 // The final merge of the runs (bsr_merge_device) sorts all runs' keys once more and builds the file window by window: the host reads each run's share of the window
 // (stability makes it one contiguous range of the run) into a pinned buffer, the device gathers, compresses and indexes it.
@@ -31,7 +32,7 @@ struct bsr_dev_t {
 	dev_buf<uint8_t> side;                                                                      // a word per record, permuted with a batch's records (duplicate marking)
 	dev_buf<uint8_t> head, hpos, heads, lin, counts, n_win, lin_off;                            // the index pass; lin, counts: of the whole file
 	uint8_t *h_buf = nullptr; size_t h_cap = 0;                                          // pinned: a window's records on their way up, its members on their way down
-	int n_ref = 0;
+	int n_ref = 0, ix_format = BSR_IX_BAI, ix_shift = BSR_LIN_SHIFT, ix_depth = BSR_BAI_DEPTH;   // of the index being built (bsr_index_begin)
 	int pinned(size_t n)
 	{
 		if (n <= h_cap) return BMH_OK;
@@ -99,8 +100,13 @@ __global__ void __launch_bounds__(256) bsr_gather(const uint8_t *__restrict__ sr
 	if (t < sz) d[t] = s[t];
 }
 
+// CSI: the windows hold 2^min_shift bases and a chunk begins where (refID, CSI bin) change -- the bin of the record's first and last window, which the lane has
+// anyway, and of the windows of the record before it, which it has wherever the two share a reference; the record's bin field is not read.  The BAI form reads
+// neither min_shift nor depth
+template <bool CSI>
 __global__ void __launch_bounds__(256) bsr_index_marks(const uint8_t *__restrict__ recs, const uint64_t *__restrict__ soff, uint32_t n, const uint64_t *__restrict__ moff, uint64_t base, int n_ref,
-                                                       const uint32_t *__restrict__ n_win, const uint64_t *__restrict__ lin_off, unsigned long long *lin, unsigned long long *counts, uint32_t *__restrict__ head)
+                                                       const uint32_t *__restrict__ n_win, const uint64_t *__restrict__ lin_off, unsigned long long *lin, unsigned long long *counts, uint32_t *__restrict__ head,
+                                                       int min_shift, int depth)
 {
 	__shared__ int r0;
 	const uint32_t j = blockIdx.x * 256 + threadIdx.x;
@@ -108,16 +114,21 @@ __global__ void __launch_bounds__(256) bsr_index_marks(const uint8_t *__restrict
 	int32_t r = -1; uint32_t slot = 2 * (uint32_t)n_ref;
 	if (valid) {
 		const uint8_t *rec = recs + soff[j], *prev = j ? recs + soff[j - 1] : nullptr;
-		head[j] = bsr_chunk_head(rec, prev) ? 1u : 0u;
+		if (!CSI) head[j] = bsr_chunk_head(rec, prev) ? 1u : 0u;
 		r = bsr_ref(rec);
 		if (r >= 0 && r < n_ref) {
 			slot = 2 * (uint32_t)r + ((bsr_flag(rec) & 4u) ? 1u : 0u);
 			const uint64_t v = bsr_voff(base, moff, soff[n], soff[j]);
 			uint32_t lo, hi, plo = 1, phi = 0;
-			bsr_windows(rec, n_win[r], &lo, &hi);
-			if (prev && bsr_ref(prev) == r) bsr_windows(prev, n_win[r], &plo, &phi);
+			const bool same = prev && bsr_ref(prev) == r;
+			if (CSI) { bsr_windows_at(rec, n_win[r], min_shift, &lo, &hi); if (same) bsr_windows_at(prev, n_win[r], min_shift, &plo, &phi); }
+			else { bsr_windows(rec, n_win[r], &lo, &hi); if (same) bsr_windows(prev, n_win[r], &plo, &phi); }
+			if (CSI) head[j] = !same || bsr_csi_bin(lo, hi, depth) != bsr_csi_bin(plo, phi, depth) ? 1u : 0u;
 			for (uint32_t w = lo; w <= hi; ++w) if (w < plo || w > phi) atomicMin(lin + lin_off[r] + w, (unsigned long long)v);
-		} else r = -1;
+		} else {
+			if (CSI) head[j] = bsr_csi_chunk_head(rec, prev, 1u, min_shift, depth) ? 1u : 0u;      // (no reference: a head behind a record that has one)
+			r = -1;
+		}
 	}
 	if (threadIdx.x == 0) r0 = r;                           // (lane 0 of a launched block always has a record)
 	__syncthreads();
@@ -129,14 +140,18 @@ __global__ void __launch_bounds__(256) bsr_index_marks(const uint8_t *__restrict
 	} else if (valid) atomicAdd(counts + slot, 1ull);
 }
 
+template <bool CSI>
 __global__ void __launch_bounds__(256) bsr_index_heads(const uint8_t *__restrict__ recs, const uint64_t *__restrict__ soff, uint32_t n, const uint64_t *__restrict__ moff, uint64_t base, int n_ref,
-                                                       const uint32_t *__restrict__ head, const uint32_t *__restrict__ hpos, bsr_head_t *__restrict__ out)
+                                                       const uint32_t *__restrict__ head, const uint32_t *__restrict__ hpos, bsr_head_t *__restrict__ out,
+                                                       const uint32_t *__restrict__ n_win, int min_shift, int depth)
 {
 	const uint32_t j = blockIdx.x * 256 + threadIdx.x;
 	if (j >= n || !head[j] || hpos[j] >= n) return;
 	const uint8_t *rec = recs + soff[j];
 	const int32_t r = bsr_ref(rec);
-	bsr_head_t h; h.ref = r >= 0 && r < n_ref ? r : -1; h.bin = bsr_bin(rec); h.beg = bsr_voff(base, moff, soff[n], soff[j]);
+	bsr_head_t h; h.ref = r >= 0 && r < n_ref ? r : -1;
+	h.bin = CSI ? bsr_csi_rec_bin(rec, h.ref >= 0 ? n_win[r] : 1u, min_shift, depth) : bsr_bin(rec);
+	h.beg = bsr_voff(base, moff, soff[n], soff[j]);
 	out[hpos[j]] = h;
 }
 
@@ -210,7 +225,16 @@ int bsr_sort_keys_device(bsr_dev_t *d, const uint64_t *keys, uint64_t n, void *s
 int bsr_index_begin(bsr_dev_t *d, const bsr_index_t &ix, void *stream)
 {
 	hipStream_t st = (hipStream_t)stream;
-	d->n_ref = ix.n_ref;
+	d->n_ref = ix.n_ref; d->ix_format = ix.format; d->ix_shift = ix.min_shift; d->ix_depth = ix.depth;
+	if (8 * ix.lin.size() > d->lin.cap) {                   // the lin array grows with the contigs and shrinks with min_shift (16 MB for 2^31 bases at 10): counted before it is allocated
+		size_t fr = 0, tot = 0;
+		HIPCK(hipMemGetInfo(&fr, &tot));
+		const size_t want = 8 * ix.lin.size() + 2 * ix.lin.size() + 1024 + (64u << 20);
+		if (want > fr + d->lin.cap) {
+			bmh_set_error("sorted BAM: the index's %zu windows of 2^%d bases need %zu bytes of device memory, %zu are free (choose a larger min_shift)", ix.lin.size(), ix.min_shift, want, fr + d->lin.cap);
+			return BMH_ENOMEM;
+		}
+	}
 	RCK(d->lin.need(8 * ix.lin.size())); RCK(d->counts.need(8 * ix.counts.size())); RCK(d->n_win.need(4 * ((size_t)ix.n_ref + 1))); RCK(d->lin_off.need(8 * ix.lin_off.size()));
 	HIPCK(hipMemsetAsync(d->lin.p, 0xff, 8 * ix.lin.size(), st));
 	HIPCK(hipMemsetAsync(d->counts.p, 0, 8 * ix.counts.size(), st));
@@ -255,11 +279,13 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 	size_t tb = scan_tmp_bytes<uint32_t, uint32_t>((size_t)n + 1);
 	RCK(d->head.need(4 * ((size_t)n + 2))); RCK(d->hpos.need(4 * ((size_t)n + 2))); RCK(d->heads.need(sizeof(bsr_head_t) * ((size_t)n + 1))); RCK(d->tmp.need(tb));
 	HIPCK(hipMemsetAsync((uint32_t *)d->head.p + n, 0, 4, st));
-	bsr_index_marks<<<(n + 255) / 256, 256, 0, st>>>((const uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, n, (const uint64_t *)ws->moff.p, ix.file_pos, d->n_ref, (const uint32_t *)d->n_win.p,
-	                                                 (const uint64_t *)d->lin_off.p, (unsigned long long *)d->lin.p, (unsigned long long *)d->counts.p, (uint32_t *)d->head.p);
+	const bool csi = d->ix_format == BSR_IX_CSI;
+	(csi ? bsr_index_marks<true> : bsr_index_marks<false>)<<<(n + 255) / 256, 256, 0, st>>>((const uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, n, (const uint64_t *)ws->moff.p, ix.file_pos, d->n_ref,
+	                                                 (const uint32_t *)d->n_win.p, (const uint64_t *)d->lin_off.p, (unsigned long long *)d->lin.p, (unsigned long long *)d->counts.p, (uint32_t *)d->head.p,
+	                                                 d->ix_shift, d->ix_depth);
 	HIPCK(rocprim::exclusive_scan(d->tmp.p, tb, (uint32_t *)d->head.p, (uint32_t *)d->hpos.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
-	bsr_index_heads<<<(n + 255) / 256, 256, 0, st>>>((const uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, n, (const uint64_t *)ws->moff.p, ix.file_pos, d->n_ref, (const uint32_t *)d->head.p,
-	                                                 (const uint32_t *)d->hpos.p, (bsr_head_t *)d->heads.p);
+	(csi ? bsr_index_heads<true> : bsr_index_heads<false>)<<<(n + 255) / 256, 256, 0, st>>>((const uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, n, (const uint64_t *)ws->moff.p, ix.file_pos, d->n_ref,
+	                                                 (const uint32_t *)d->head.p, (const uint32_t *)d->hpos.p, (bsr_head_t *)d->heads.p, (const uint32_t *)d->n_win.p, d->ix_shift, d->ix_depth);
 	uint32_t nh = 0;
 	HIPCK(hipMemcpyAsync(&nh, (const uint32_t *)d->hpos.p + n, 4, hipMemcpyDeviceToHost, st));
 	RCK(d->pinned((size_t)mb + 16));
@@ -400,14 +426,15 @@ extern "C" int bmh_bam_sort_device(const uint8_t *recs, uint64_t n_bytes, void *
 
 static int sorted_file_device(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
                               int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts,
-                              const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr)
+                              const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr, int format = BSR_IX_BAI, int min_shift = BSR_LIN_SHIFT)
 {
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
 	if (G && n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d references: with read groups a run holds at most 2^24 (the library takes the duplicate key's top byte)", fn, n_contigs); return BMH_EINVAL; }
 	if (level != 0 && level != 1) { bmh_set_error("%s: level %d (0 or 1)", fn, level); return BMH_EINVAL; }
 	bsr_index_t ix;
-	RCK(ix.init(n_contigs, contig_len, fn));
+	RCK(ix.init(n_contigs, contig_len, fn, format, min_shift));
+	if (dup_counts) RCK(bsr_markdup_contigs(n_contigs, contig_len, contig_names, fn));
 	std::vector<uint64_t> off, keys, soff; std::vector<uint8_t> sorted;
 	RCK(bsr_walk(recs, n_bytes, n_contigs, off, fn));
 	bsr_dev_t d;
@@ -436,7 +463,8 @@ static int sorted_file_device(const char *fn, const char *header_text, int n_con
 	if (G && lib_counts && off.size() > 1)
 		bdp_lib_tally_host(sorted.data(), soff.data(), (uint32_t)(off.size() - 1), dh.tpl.data(), dh.entries.data(), dh.entries.size(), G->n_lib, lib_counts);
 	file.append((const char *)bmh_bgzf_eof, 28);
-	std::string ib; ix.bai(base, ib);
+	std::string ib;
+	RCK(ix.bytes(base, ib));
 	uint8_t *f = (uint8_t *)malloc(file.size() + 1), *i = (uint8_t *)malloc(ib.size() + 1);
 	if (!f || !i) { free(f); free(i); bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
 	memcpy(f, file.data(), file.size()); memcpy(i, ib.data(), ib.size());
@@ -467,4 +495,19 @@ extern "C" int bmh_bam_sorted_file_markdup_groups_device(const char *header_text
 	bdp_table_t G;
 	RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
 	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, bai, bai_bytes, counts, &G, lib_counts);
+}
+
+extern "C" int bmh_bam_sorted_file_ex_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                             int level, uint32_t window, int index_format, int min_shift, int markdup, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
+                                             void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts)
+{
+	const char *fn = "bmh_bam_sorted_file_ex_device";
+	if (markdup && !counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (!markdup && (rg_ids || rg_lib || n_groups)) { bmh_set_error("%s: read groups decide which templates may be duplicates of each other: they need markdup", fn); return BMH_EINVAL; }
+	RCK(bsr_index_format_check(index_format, min_shift, fn));
+	bdp_table_t G;
+	const bool groups = rg_ids || rg_lib || n_groups;
+	if (groups) RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
+	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, index, index_bytes, markdup ? counts : nullptr,
+	                          groups ? &G : nullptr, groups ? lib_counts : nullptr, index_format, min_shift);
 }

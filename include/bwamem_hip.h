@@ -867,7 +867,8 @@ int bmh_aligner_set_output(bmh_aligner_t *a, int format, int level);
  * they came in.  The index is the SAM specification's section 5.2 (bins as the records carry them, the pseudo-bin 37450, the 16 KiB linear index, n_no_coor).
  * bmh_bam_sort_device / _host: a record stream in host memory (whole records, else refused) -> the same records in order (malloc'd; bmh_free).
  * bmh_bam_sorted_file_device / _host: header members, the sorted records in windows of `window` records (0: about 64 MiB of records; a window's last member
- * is short), the end-of-file member; and the .bai bytes.  Both forms give the same bytes.  A contig of 2^29 bases or more is refused (BAI cannot index it).
+ * is short), the end-of-file member; and the .bai bytes.  Both forms give the same bytes.  A contig of 2^29 bases or more is refused (BAI cannot index it;
+ * a CSI index, below, takes it).
  * bmh_aligner_set_output(a, BMH_OUT_BAM_SORTED, level): every batch becomes a sorted run kept on the host (in memory up to mem_bytes of records, beyond that in
  * an unnamed temporary file in tmp_dir); at the end of the input all runs' keys are sorted once more on the device -- 24 bytes of device memory per record and
  * the sort's work space, fewer than 2^32 records, else the run is refused with a message naming the count -- and the sink receives the record members of the
@@ -883,6 +884,33 @@ int bmh_bam_sorted_file_host(const char *header_text, int n_contigs, const char 
                              int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes);
 int bmh_aligner_set_sort(bmh_aligner_t *a, uint64_t mem_bytes, const char *tmp_dir, uint32_t window_records);
 int bmh_aligner_sort_index(bmh_aligner_t *a, uint64_t base_offset, uint8_t **bai, uint64_t *bai_bytes);
+
+/* ---- A CSI index in place of the BAI, for contigs of 2^29 bases and more (BAM holds positions up to 2^31 - 1; only BAI's bins stop at 2^29).  Opt-in: without
+ * it every byte is as before.  The binning scheme is (min_shift, depth): min_shift from the caller (10 .. 24, else refused; 14 is BAI's), depth the smallest d with
+ * 2^(min_shift + 3 d) >= the longest contig, as htslib chooses it.  A record's bin is that of the deepest level that holds its first and last 2^min_shift window
+ * (pos < 0 counts as 0, a record running off its contig is clamped to the contig's last window); the record's own 16-bit bin field is neither read nor changed, so the
+ * BAM bytes are those of the BAI call.  The .csi bytes, little-endian, as BGZF members and the end-of-file member:
+ *   "CSI\1"  int32 min_shift  int32 depth  int32 l_aux = 0  int32 n_ref
+ *   per reference: int32 n_bin, then per bin, ascending, the pseudo-bin ((1 << 3 (depth + 1)) - 1) / 7 + 1 last:
+ *     uint32 bin  uint64 loffset  int32 n_chunk  n_chunk x (uint64 beg, uint64 end)
+ *   uint64 n_no_coor
+ * loffset: the smallest begin offset over the records that overlap the bin's first window, or, if none does, the next window that has one; 0 for the pseudo-bin,
+ * whose two chunks are (first begin, last end) and (mapped, unmapped).  A reference without records has n_bin 0.
+ * bmh_aligner_set_index_format: the index of the sorted runs that follow; it comes before bmh_aligner_set_output(.., BMH_OUT_BAM_SORTED, ..), which checks the
+ * contig lengths against it as every run's begin does (BAI: below 2^29; CSI: at most 2^31 - 1, and an index of fewer than 2^28 windows).  bmh_aligner_sort_index
+ * gives the bytes of the format the last sorted run was made under.  For BMH_INDEX_BAI min_shift is not read.
+ * Duplicate marking holds an unclipped end in 31 bits around 2^30: with it on, a contig beyond 2^30 - 2^24 bases is refused by name before anything is written.
+ * bmh_bam_sorted_file_ex_device / _host: bmh_bam_sorted_file_* with everything its variants take -- the index format and min_shift; markdup (0: counts may be NULL);
+ * read groups (rg_ids NULL and n_groups 0: none; they need markdup) -- and the index of that format in *index. */
+#define BMH_INDEX_BAI 0
+#define BMH_INDEX_CSI 1
+int bmh_aligner_set_index_format(bmh_aligner_t *a, int index_format, int min_shift);
+int bmh_bam_sorted_file_ex_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
+                                  int level, uint32_t window, int index_format, int min_shift, int markdup, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
+                                  void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts);
+int bmh_bam_sorted_file_ex_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
+                                int level, uint32_t window, int index_format, int min_shift, int markdup, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
+                                uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts);
 
 /* ---- Duplicate marking in sorted BAM (csrc/bam_dup_core.h, csrc/bam_dup_kernels.hip, csrc/bam_dup_host.cpp).
  * Picard MarkDuplicates' rules on templates (a single read or a read pair, its records next to each other in the writer's order): the unclipped 5' ends and
