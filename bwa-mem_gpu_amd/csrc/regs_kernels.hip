@@ -679,6 +679,15 @@ extern "C" float bmh_finalize_regs_device_last_ms(void)
 	return ms;
 }
 
+// the deferral counts of the thread's last call (h_pin[2..6]: the lane kernel's ctr[0..4], copied back when the call ends)
+extern "C" int bmh_finalize_regs_device_last_classes(uint32_t out[5])
+{
+	if (!out) { bmh_set_error("bmh_finalize_regs_device_last_classes: null argument"); return BMH_EINVAL; }
+	if (!g_fin_last || !g_fin_last->h_pin.p) { bmh_set_error("bmh_finalize_regs_device_last_classes: no call of this thread to report on"); return BMH_EINVAL; }
+	for (int c = 0; c < FIN_NCLS; ++c) out[c] = g_fin_last->h_pin.p[2 + c];
+	return BMH_OK;
+}
+
 static int64_t finalize_regs_device_impl(const bmh_index_t *idx, const bmh_chain_opt_t *copt, const bmh_ext_params_t *ep, const bmh_post_opt_t *popt,
                                          const uint8_t *d_reads, const uint32_t *d_offs, uint32_t n_reads,
                                          const int32_t *d_regs, uint64_t n_regs, const uint32_t *d_regs_per_read, const float *d_frac_rep,
@@ -807,23 +816,27 @@ static int64_t finalize_regs_device_impl(const bmh_index_t *idx, const bmh_chain
 	fin_lane_kernel<<<(n_reads + 255) / 256, 256, 0, st>>>(A);
 	if (want_phases) HIPCK(hipEventRecord(ph[1], st));
 	// the wave classes side by side (their lists are short and uneven: the class of the largest reads is a handful of long jobs)
+	// (knob FIN_GRID_MAX: at most so many blocks per wave kernel, 0 = FIN_WAVE_GRID; for tests -- with one or two blocks a block takes read after read of
+	// a class through the same LDS and the same alignment scratch)
+	const int grid_max = bmh_tune("FIN_GRID_MAX", 0);
+	const unsigned wave_grid = grid_max > 0 && grid_max < FIN_WAVE_GRID ? (unsigned)grid_max : FIN_WAVE_GRID;
 	static thread_local hipEvent_t pc[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 	if (want_phases) {                       // (debug: one class after the other, each timed)
 		if (!pc[0]) for (hipEvent_t &e : pc) HIPCK(hipEventCreate(&e));
 		HIPCK(hipEventRecord(pc[0], st));
-		fin_wave_kernel<32, 0><<<FIN_WAVE_GRID, 64, 0, st>>>(A); HIPCK(hipEventRecord(pc[1], st));
-		fin_wave_kernel<128, 1><<<FIN_WAVE_GRID, 64, 0, st>>>(A); HIPCK(hipEventRecord(pc[2], st));
-		fin_wave_kernel<256, 2><<<FIN_WAVE_GRID, 64, 0, st>>>(A); HIPCK(hipEventRecord(pc[3], st));
-		fin_wave_kernel<FIN_NMAX, 3><<<FIN_WAVE_GRID, 64, 0, st>>>(A); HIPCK(hipEventRecord(pc[4], st));
-		fin_wave_kernel<0, 4><<<FIN_WAVE_GRID, 64, 0, st>>>(A); HIPCK(hipEventRecord(pc[5], st));
+		fin_wave_kernel<32, 0><<<wave_grid, 64, 0, st>>>(A); HIPCK(hipEventRecord(pc[1], st));
+		fin_wave_kernel<128, 1><<<wave_grid, 64, 0, st>>>(A); HIPCK(hipEventRecord(pc[2], st));
+		fin_wave_kernel<256, 2><<<wave_grid, 64, 0, st>>>(A); HIPCK(hipEventRecord(pc[3], st));
+		fin_wave_kernel<FIN_NMAX, 3><<<wave_grid, 64, 0, st>>>(A); HIPCK(hipEventRecord(pc[4], st));
+		fin_wave_kernel<0, 4><<<wave_grid, 64, 0, st>>>(A); HIPCK(hipEventRecord(pc[5], st));
 	} else {
 		HIPCK(hipEventRecord(S->fork, st));
 		for (int i = 0; i < 3; ++i) HIPCK(hipStreamWaitEvent(S->side[i], S->fork, 0));
-		fin_wave_kernel<FIN_NMAX, 3><<<FIN_WAVE_GRID, 64, 0, S->side[0]>>>(A);
-		fin_wave_kernel<0, 4><<<FIN_WAVE_GRID, 64, 0, S->side[1]>>>(A);
-		fin_wave_kernel<256, 2><<<FIN_WAVE_GRID, 64, 0, S->side[2]>>>(A);
-		fin_wave_kernel<128, 1><<<FIN_WAVE_GRID, 64, 0, S->side[0]>>>(A);
-		fin_wave_kernel<32, 0><<<FIN_WAVE_GRID, 64, 0, st>>>(A);
+		fin_wave_kernel<FIN_NMAX, 3><<<wave_grid, 64, 0, S->side[0]>>>(A);
+		fin_wave_kernel<0, 4><<<wave_grid, 64, 0, S->side[1]>>>(A);
+		fin_wave_kernel<256, 2><<<wave_grid, 64, 0, S->side[2]>>>(A);
+		fin_wave_kernel<128, 1><<<wave_grid, 64, 0, S->side[0]>>>(A);
+		fin_wave_kernel<32, 0><<<wave_grid, 64, 0, st>>>(A);
 		for (int i = 0; i < 3; ++i) { HIPCK(hipEventRecord(S->join[i], S->side[i])); HIPCK(hipStreamWaitEvent(st, S->join[i], 0)); }
 	}
 	if (want_phases) HIPCK(hipEventRecord(ph[2], st));

@@ -410,6 +410,10 @@ int64_t bmh_finalize_regs_device(const bmh_index_t *idx, const bmh_chain_opt_t *
                                  const int32_t *d_regs, uint64_t n_regs, const uint32_t *d_regs_per_read, const float *d_frac_rep,
                                  int n_contigs, const int64_t *contig_offset, int32_t *d_out, uint32_t *d_out_per_read, void *stream);
 float bmh_finalize_regs_device_last_ms(void);       /* device time of the thread's last bmh_finalize_regs_device (HIP events) */
+/* Which form took which read in the thread's last bmh_finalize_regs_device / bmh_dedup_regs_device: out[c] = the reads handed to the wave
+ * kernel of class c (up to 32 / 128 / 256 / 512 / more regions; class 0 includes the reads of at most 8 regions whose patch test reached
+ * its global alignment), every other read with regions was finished by the lane kernel.  0, or BMH_EINVAL without such a call.  For tests. */
+int bmh_finalize_regs_device_last_classes(uint32_t out[5]);
 
 /* SAM records of single-end reads (mem_aln2sam, src/bwamem.c:1506-1683; XA tag: mem_gen_alt, src/bwamem_extra.c:97-150).
  * bmh_sam_need_cigar marks (need[i] = 1) the records of bmh_finalize_regs that must go through bmh_cigar_batch first --

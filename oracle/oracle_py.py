@@ -2,6 +2,7 @@
 
 liboracle.so  : our C restatement (oracle/fmd_oracle.c, oracle/ksw_oracle.c)
 _ref/libref.so: the reference's own compiled C + oracle/ref_harness.c (optional)
+_ref/libref_tail.so: the reference's region tail + oracle/ref_tail_harness.cpp (optional)
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this.
 """
@@ -249,6 +250,38 @@ class Ref:
                                   _ptr(tlen, _u32p), _ptr(h0, _u32p), p.a, p.b, p.o_del, p.e_del, p.o_ins, p.e_ins, w,
                                   p.zdrop, p.end_bonus, _ptr(out3, _i32p), _ptr(raw6, _i32p))
         return out3, raw6
+
+
+class RefTail:
+    """The reference's own region tail (oracle/_ref/libref_tail.so: mem_sort_dedup_patch, mem_mark_primary_se, mem_approx_mapq_se behind
+    oracle/ref_tail_harness.cpp).  available() is False where it was not built."""
+
+    PATH = os.path.join(_HERE, "_ref", "libref_tail.so")
+
+    @classmethod
+    def available(cls) -> bool:
+        return os.path.exists(cls.PATH)
+
+    def __init__(self):
+        # lazily: the reference's GPU entry points stay unresolved in this library and are never called
+        self.lib = L = C.CDLL(self.PATH, mode=os.RTLD_LAZY)
+        L.ref_tail_run.restype = C.c_int
+        L.ref_tail_run.argtypes = [_i32p, C.POINTER(C.c_float), C.c_int64, _u8p, C.c_int, _u8p, C.c_int64, C.c_float, C.c_int, _i32p, _i32p, _u8p, _i32p]
+
+    def run(self, opt_i, opt_f, l_pac: int, pac: np.ndarray, query: np.ndarray, read_id: int, frac_rep: float, regs8: np.ndarray, rid: np.ndarray,
+            is_alt: "np.ndarray | None" = None) -> np.ndarray:
+        """One read through the reference's tail.  opt_i = (a, b, o_del, e_del, o_ins, e_ins, w, min_seed_len, max_chain_gap, mapQ_coef_fac), opt_f =
+        (mask_level, mask_level_redun, mapQ_coef_len); query: codes 0..4; regs8 int32 [n, 8]; rid int32 [n]; is_alt uint8 [n] or None.
+        -> int32 [m, 16]: see oracle/ref_tail_harness.cpp"""
+        oi = np.ascontiguousarray(opt_i, dtype=np.int32); of = np.ascontiguousarray(opt_f, dtype=np.float32)
+        q = np.ascontiguousarray(query, dtype=np.uint8); r8 = np.ascontiguousarray(regs8, dtype=np.int32).reshape(-1, 8)
+        rd = np.ascontiguousarray(rid, dtype=np.int32); n = r8.shape[0]
+        ia = np.ascontiguousarray(is_alt, dtype=np.uint8) if is_alt is not None else None
+        out = np.zeros((max(n, 1), 16), np.int32)
+        m = self.lib.ref_tail_run(_ptr(oi, _i32p), _ptr(of, C.POINTER(C.c_float)), int(l_pac), _ptr(np.ascontiguousarray(pac, dtype=np.uint8), _u8p), len(q),
+                                  _ptr(q, _u8p), int(read_id), float(frac_rep), n, _ptr(r8, _i32p), _ptr(rd, _i32p), _ptr(ia, _u8p) if ia is not None else None,
+                                  _ptr(out, _i32p))
+        return out[:m]
 
 
 def bwt_symbols(idx) -> np.ndarray:

@@ -7,7 +7,7 @@
 #include <vector>
 #include "../bwa-mem_gpu_amd/csrc/regs_core.h"
 
-extern "C" int64_t regs_core_run(const bmh_chain_opt_t *copt, const bmh_ext_params_t *ep, const bmh_post_opt_t *popt, int64_t l_pac,
+static int64_t core_run(int dedup_only, const bmh_chain_opt_t *copt, const bmh_ext_params_t *ep, const bmh_post_opt_t *popt, int64_t l_pac,
                                  const uint8_t *pac, uint32_t n_reads, const uint8_t *reads, const uint64_t *read_offs,
                                  const int32_t *regs_in, const uint32_t *regs_per_read, const float *frac_rep,
                                  int n_contigs, const int64_t *contig_offset, int32_t *out, uint32_t *out_per_read, int with_dp)
@@ -20,6 +20,7 @@ extern "C" int64_t regs_core_run(const bmh_chain_opt_t *copt, const bmh_ext_para
 	x.co = *copt; x.ep = *ep; x.po = *popt; x.l_pac = l_pac; x.pac = pac; x.n_contigs = n_contigs; x.ctg_off = contig_offset;
 	x.logtab = logtab.data(); x.n_log = (int)logtab.size();
 	x.ctg_alt = popt->contig_is_alt;                              // (ALT contigs: the table is host memory here)
+	x.dedup_only = dedup_only;
 	if (with_dp) { x.dp_h = dph.data(); x.dp_e = dpe.data(); x.dp_cap = (int)dph.size(); }
 	uint64_t in = 0, w = 0;
 	std::vector<rec_t> a; std::vector<int32_t> z;
@@ -34,4 +35,20 @@ extern "C" int64_t regs_core_run(const bmh_chain_opt_t *copt, const bmh_ext_para
 		in += n_in; w += n;
 	}
 	return (int64_t)w;
+}
+
+extern "C" int64_t regs_core_run(const bmh_chain_opt_t *copt, const bmh_ext_params_t *ep, const bmh_post_opt_t *popt, int64_t l_pac,
+                                 const uint8_t *pac, uint32_t n_reads, const uint8_t *reads, const uint64_t *read_offs,
+                                 const int32_t *regs_in, const uint32_t *regs_per_read, const float *frac_rep,
+                                 int n_contigs, const int64_t *contig_offset, int32_t *out, uint32_t *out_per_read, int with_dp)
+{
+	return core_run(0, copt, ep, popt, l_pac, pac, n_reads, reads, read_offs, regs_in, regs_per_read, frac_rep, n_contigs, contig_offset, out, out_per_read, with_dp);
+}
+// the same with ctx.dedup_only: the tail stops behind mem_sort_dedup_patch (what bmh_dedup_regs_device computes)
+extern "C" int64_t regs_core_dedup(const bmh_chain_opt_t *copt, const bmh_ext_params_t *ep, const bmh_post_opt_t *popt, int64_t l_pac,
+                                   const uint8_t *pac, uint32_t n_reads, const uint8_t *reads, const uint64_t *read_offs,
+                                   const int32_t *regs_in, const uint32_t *regs_per_read, const float *frac_rep,
+                                   int n_contigs, const int64_t *contig_offset, int32_t *out, uint32_t *out_per_read, int with_dp)
+{
+	return core_run(1, copt, ep, popt, l_pac, pac, n_reads, reads, read_offs, regs_in, regs_per_read, frac_rep, n_contigs, contig_offset, out, out_per_read, with_dp);
 }
