@@ -12,6 +12,9 @@ inline int sat0(int v) { return v < 0 ? 0 : v; }
 bmh_sw_result_t sw_pass(int lanes, int qlen, const uint8_t *query, int tlen, const uint8_t *target, const bmh_ext_params_t &p, int xtra)
 {
 	bmh_sw_result_t r = {0, -1, -1, -1, -1, -1, -1};
+	// an empty query: the second pass after a byte pass that overflowed (score 255 leaves qe = -1).  Nothing aligns and no array has an element to read;
+	// ksw_align2 discards that pass as well (255 is no score it can return), so the caller is left with {255, te, -1, -1, -1, -1, -1}
+	if (qlen <= 0) return r;
 	const bool byte = lanes == 16;
 	const int slen = (qlen + lanes - 1) / lanes, n = slen * lanes;
 	const int minsc = (xtra & BMH_SW_XSUBO) ? xtra & 0xffff : 0x10000, endsc = (xtra & BMH_SW_XSTOP) ? xtra & 0xffff : 0x10000;

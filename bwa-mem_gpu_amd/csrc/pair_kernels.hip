@@ -621,8 +621,16 @@ extern "C" int bmh_matesw_batch_device(const bmh_index_t *idx, const uint8_t *d_
 	uint64_t bl = 0;
 	int cap = 1;                                             // the longest lane-private column of the batch, in segments
 	bool byte_all = true;
-	for (uint64_t k = 0; k < n_jobs; ++k) { const int lanes = (jobs[k].xtra & BMH_SW_XBYTE) ? 16 : 8; const int sl = (jobs[k].l_ms + lanes - 1) / lanes; cap = sl > cap ? sl : cap; byte_all = byte_all && lanes == 16; }
-	if (cap > MSW_SLEN) { bmh_set_error("bmh_matesw_batch_device: a job the kernel does not take (see bmh_matesw_device_takes)"); return BMH_EINVAL; }
+	for (uint64_t k = 0; k < n_jobs; ++k) {
+		const int lanes = (jobs[k].xtra & BMH_SW_XBYTE) ? 16 : 8;
+		// every job is one the kernels take: a column that fits, a window of 1 .. 65535 rows (the 16-bit rows of the bookkeeping words)
+		if (!bmh_matesw_device_takes(jobs[k].l_ms, jobs[k].re - jobs[k].rb, jobs[k].xtra)) {
+			bmh_set_error("bmh_matesw_batch_device: job %llu is not one the kernel takes (l_ms %d in %s mode, a window of %lld rows; see bmh_matesw_device_takes)",
+			              (unsigned long long)k, jobs[k].l_ms, lanes == 16 ? "byte" : "word", (long long)(jobs[k].re - jobs[k].rb));
+			return BMH_EINVAL;
+		}
+		const int sl = (jobs[k].l_ms + lanes - 1) / lanes; cap = sl > cap ? sl : cap; byte_all = byte_all && lanes == 16;
+	}
 	for (uint64_t k = 0; k < n_jobs; ++k) { jobs[k].bl_off = (uint32_t)bl; bl += (uint64_t)(jobs[k].re - jobs[k].rb) / 2 + 2; if (bl >> 32) { bmh_set_error("bmh_matesw_batch_device: windows too long"); return BMH_ECAPACITY; } }
 	RCK(msw_room(S, n_jobs, bl));
 	HIPCK(hipMemcpyAsync(S->d_jobs.p, jobs, sizeof(bmh_msw_job_t) * n_jobs, hipMemcpyHostToDevice, st));

@@ -183,6 +183,17 @@ class Ref:
         if hasattr(L, "ref_global2"):
             L.ref_global2.restype = C.c_int
             L.ref_global2.argtypes = [C.c_int, _u8p, C.c_int, _u8p] + [C.c_int] * 7 + [_i32p, _u32p, C.c_int]
+        if hasattr(L, "ref_align2"):
+            L.ref_align2.restype = None
+            L.ref_align2.argtypes = [C.c_int, _u8p, C.c_int, _u8p] + [C.c_int] * 7 + [_i32p]
+
+    def align2(self, query, target, scoring, xtra: int) -> np.ndarray:
+        """the reference's ksw_align2 as mem_matesw calls it (5 x 5 matrix: a, -b, N = -1) -> int32 [7] = score, te, qe, score2, te2, tb, qb.
+        query / target: codes 0..4 (copied: the reference reverses them in place); scoring = (a, b, o_del, e_del, o_ins, e_ins)"""
+        q = np.array(query, dtype=np.uint8); t = np.array(target, dtype=np.uint8)
+        out = np.zeros(7, np.int32)
+        self.lib.ref_align2(len(q), _ptr(q, _u8p), len(t), _ptr(t, _u8p), *(int(v) for v in scoring), int(xtra), _ptr(out, _i32p))
+        return out
 
     def global2(self, query, target, w, params: "KswParams | None" = None, cap: int = 1024):
         """the reference's ksw_global2 -> (score, cigar ops)"""

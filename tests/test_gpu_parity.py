@@ -1542,8 +1542,8 @@ def test_region_tail_on_the_device_equals_the_host_form(hip, oracle):
 
 def test_mate_rescue_alignments_on_the_device(hip):
     """The ksw_align2 emulation of the mate rescue (csrc/pair_kernels.hip: 16 GPU lanes = the 16 byte lanes / 8 word lanes of the
-    reference's striped SSE2 kernel) against the host walk of the same kernel (local_sw.cpp, itself checked against the compiled
-    ksw_align2): score, ends, second-best score and row, start positions, for both widths, both strands, windows with and without
+    reference's striped SSE2 kernel) against the host walk of the same kernel (local_sw.cpp, itself pinned to the compiled ksw_align2 by
+    tests/test_msw_cases.py; the kernels' hand-made grid against the same reference is tests/test_msw_cases_gpu.py): score, ends, second-best score and row, start positions, for both widths, both strands, windows with and without
     the mate, repeats inside the window (second-best hits), N bases."""
     import ctypes as C, torch
     from bwamem_hip import fmindex, synth

@@ -1,7 +1,8 @@
 """CPU check of the algebra behind csrc/pair_kernels.hip: msw_reg_kernel -- the mate rescue's striped local alignment (ksw_align2's byte-mode kernel,
 /root/reference/src/ksw.c:389-547) computed as plain rows: first sweep with F starting at 0 at every lane's first column, the F that flows in from the lanes to the
 left as a max-plus scan, E and the row maximum from the first sweep's H.  scripts/proto/msw_rowform_fuzz.cpp holds that form in C++ and compares it with
-csrc/local_sw.cpp, the host walk of the striped kernel (itself pinned to the compiled reference by tests/test_oracle.py), on random windows: substitutions, gaps,
+csrc/local_sw.cpp, the host walk of the striped kernel (itself pinned to the compiled reference's ksw_align2 by tests/test_msw_cases.py: live where the reference's
+library was built, through tests/golden/msw_cases.npz everywhere), on random windows: substitutions, gaps,
 repeats, N, six scorings, both exit flags.  The GPU test (test_mate_rescue_alignments_on_the_device) compares the kernel itself with local_sw.cpp."""
 import os
 import subprocess
