@@ -272,25 +272,40 @@ _METRICS_COLUMNS = ("LIBRARY", "UNPAIRED_READS_EXAMINED", "READ_PAIRS_EXAMINED",
                     "PERCENT_DUPLICATION")
 
 
+# with optical duplicates counted: Picard's column order, the two columns that need them included
+_METRICS_COLUMNS_OPTICAL = _METRICS_COLUMNS[:-1] + ("READ_PAIR_OPTICAL_DUPLICATES", "PERCENT_DUPLICATION", "ESTIMATED_LIBRARY_SIZE")
+
+
 def _metrics_row(lib: str, counts: dict) -> list:
     fr, pr, df, dp = counts["fragments_examined"], counts["pairs_examined"], counts["duplicate_fragments"], counts["duplicate_pairs"]
     den = fr + 2 * pr
-    return [lib, fr, pr, counts["secondary_or_supplementary"], counts["unmapped_records"], df, dp, "%.6f" % ((df + 2 * dp) / den) if den else "0"]
+    row = [lib, fr, pr, counts["secondary_or_supplementary"], counts["unmapped_records"], df, dp, "%.6f" % ((df + 2 * dp) / den) if den else "0"]
+    if "optical_duplicate_pairs" in counts:                       # (counts of a run with an optical distance)
+        from .lib import estimate_library_size
+        od = counts["optical_duplicate_pairs"]
+        size = estimate_library_size(pr - od, pr - dp)
+        row = row[:-1] + [od, row[-1], "" if size is None else size]
+    return row
 
 
 def markdup_metrics_text_libraries(library_counts: dict) -> str:
     """markdup_metrics_text for a run over read groups: the class line, the header row and one row per library -- library_counts: {library name: counts}, in order
     of first appearance (dicts keep it)"""
-    return "## METRICS CLASS\tbwamem_hip.DuplicationMetrics\n" + "\t".join(_METRICS_COLUMNS) + "\n" + \
+    cols = _METRICS_COLUMNS_OPTICAL if any("optical_duplicate_pairs" in c for c in library_counts.values()) else _METRICS_COLUMNS
+    return "## METRICS CLASS\tbwamem_hip.DuplicationMetrics\n" + "\t".join(cols) + "\n" + \
            "".join("\t".join(str(v) for v in _metrics_row(lib, c)) + "\n" for lib, c in library_counts.items())
 
 
 def markdup_metrics_text(counts: dict, rg_line: str = "") -> str:
-    """the Picard-style metrics table of a marked run: a class line, the header row and one row (one library per run: the read group's LB, else Unknown Library)"""
+    """the Picard-style metrics table of a marked run: a class line, the header row and one row (one library per run: the read group's LB, else Unknown Library).
+    Counts that hold "optical_duplicate_pairs" (a run with optical_distance) give Picard's full column order: READ_PAIR_OPTICAL_DUPLICATES before
+    PERCENT_DUPLICATION and ESTIMATED_LIBRARY_SIZE (empty where Picard leaves it empty) behind it; so with markdup_metrics_text_libraries"""
     lib = "Unknown Library"
     for f in rg_line.split("\t")[1:]:
         if f.startswith("LB:") and len(f) > 3:
             lib = f[3:]
+    if "optical_duplicate_pairs" in counts:
+        return "## METRICS CLASS\tbwamem_hip.DuplicationMetrics\n" + "\t".join(_METRICS_COLUMNS_OPTICAL) + "\n" + "\t".join(str(v) for v in _metrics_row(lib, counts)) + "\n"
     fr, pr, df, dp = counts["fragments_examined"], counts["pairs_examined"], counts["duplicate_fragments"], counts["duplicate_pairs"]
     den = fr + 2 * pr
     cols = [("LIBRARY", lib), ("UNPAIRED_READS_EXAMINED", fr), ("READ_PAIRS_EXAMINED", pr), ("SECONDARY_OR_SUPPLEMENTARY_RDS", counts["secondary_or_supplementary"]),
@@ -627,14 +642,16 @@ class Aligner:
         if getattr(self, "_out_fmt", ("sam", 1))[0] == "bam_sorted":
             nat.set_sort(*self._sort_knobs)
             nat.set_markdup(bool(getattr(self, "_markdup", False)))
+            if getattr(self, "_markdup", False):
+                nat.set_markdup_optical(getattr(self, "_optical", None))
         return nat
 
     def align_file(self, reads_fa: str, out, batch_reads: int = 0, paired: bool = False, chunk_bases: int = 0, fmt: str = "sam", level: int = 1,
                    sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
-                   index_format: str = "bai", csi_min_shift: int = 14) -> int:
-        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14:
+                   index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None) -> int:
+        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None:
             return self._align_bam(lambda o: self.align_file(reads_fa, o, batch_reads=batch_reads, paired=paired, chunk_bases=chunk_bases), out, fmt, level,
-                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift)
+                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift, optical_distance)
         """out: a text or binary file object.  Batches are cut the way the reference's bseq_read cuts them (src/bwa.c, called with
         chunk_size * n_threads = 10 Mbases per thread, or -K, src/fastmap.c:527): reads are added until the batch holds at least
         chunk_bases bases and an even number of reads -- in paired mode the insert-size statistics are those of the batch, so the
@@ -711,15 +728,23 @@ class Aligner:
         return n
 
     def _align_bam(self, run, out, fmt: str, level: int, sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
-                   index_format: str = "bai", csi_min_shift: int = 14) -> int:
+                   index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None) -> int:
         """fmt="bam" of align_file / align_files: the header members, the batches' members (`run` with the native aligner's output switched; the Python
         loop's batches converted here), the end-of-file member.  The file is written through a shim that drops the SAM header `run` writes first.
         sort=True: the batches become sorted runs and the members are those of the coordinate-sorted file, written at the end of the input; `index` (a path or
         a binary file object) receives its .bai.  markdup=True (needs sort=True): flag 0x400 on every record of every duplicate template (Picard MarkDuplicates'
         rules); self.markdup_counts holds the counts afterwards and `markdup_metrics` (a path or a text file object) receives a Picard-style table.
         index_format="csi" (needs sort=True): `index` receives a .csi in place of the .bai, with bins of 2^csi_min_shift bases (10 .. 24) -- what a
-        reference with a contig of 2^29 bases or more needs; the BAM bytes do not depend on it."""
-        from .lib import bgzf_eof, index_format_code
+        reference with a contig of 2^29 bases or more needs; the BAM bytes do not depend on it.
+        optical_distance=D (needs markdup=True; 0 .. 2^31 - 1): the decision also counts the optical duplicates -- pairs of one duplicate set that the read names
+        place on one tile within D pixels in x and y (DESIGN.md 4.11).  The file and its index are byte for byte those of the run without it;
+        self.markdup_optical_counts (and, over read groups, self.markdup_library_optical_counts) hold the counts, and the metrics table gains
+        READ_PAIR_OPTICAL_DUPLICATES and ESTIMATED_LIBRARY_SIZE in Picard's column order."""
+        from .lib import bgzf_eof, index_format_code, optical_distance_value
+        if optical_distance is not None:
+            if not markdup:
+                raise ValueError("optical_distance needs markdup=True: optical duplicates are counted where duplicates are marked")
+            optical_distance = optical_distance_value(optical_distance, "align_file")
         index_format_code(index_format, csi_min_shift, "align_file")          # (csi_min_shift without "csi", a shift outside 10 .. 24: before anything is touched)
         if index_format != "bai" and not sort:
             raise ValueError(f'index_format="{index_format}" needs sort=True: only a coordinate-sorted file has an index')
@@ -756,6 +781,7 @@ class Aligner:
             self._sort_knobs = (int(sort_mem or 0), sort_tmp, int(sort_window or 0))
         self._out_fmt = ("bam_sorted" if sort else "bam", level)
         self._markdup = bool(markdup)
+        self._optical = optical_distance
         self._index_format = (index_format, int(csi_min_shift))
         try:
             n = run(shim)
@@ -765,9 +791,18 @@ class Aligner:
                 if getattr(self, "_groups", None):                # per library, in order of first appearance (the library index of the run)
                     libs = list(dict.fromkeys(rg_library(g[0]) for g in self._groups))
                     self.markdup_library_counts = {lb: (self._native.markdup_library_counts(k) if n else dict.fromkeys(MARKDUP_COUNTS, 0)) for k, lb in enumerate(libs)}
+                if optical_distance is not None:
+                    from .lib import OPTICAL_COUNTS
+                    self.markdup_optical_counts = self._native.markdup_optical_counts() if n else dict.fromkeys(OPTICAL_COUNTS, 0)
+                    self.markdup_counts.update(self.markdup_optical_counts)
+                    if getattr(self, "_groups", None):
+                        self.markdup_library_optical_counts = {lb: (self._native.markdup_optical_counts(k) if n else dict.fromkeys(OPTICAL_COUNTS, 0)) for k, lb in enumerate(libs)}
+                        for lb in libs:
+                            self.markdup_library_counts[lb].update(self.markdup_library_optical_counts[lb])
         finally:
             self._out_fmt = ("sam", 1)
             self._markdup = False
+            self._optical = None
             self._index_format = ("bai", 14)
             nat = getattr(self, "_native", None)
             if nat is not None:
@@ -796,7 +831,7 @@ class Aligner:
 
     def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
                     sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None, keep_rg: bool = False,
-                    index_format: str = "bai", csi_min_shift: int = 14) -> int:
+                    index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None) -> int:
         """align_file for the files users have (bmh_aligner_run_files): `reads` (and `mates`: the second file of a pair, which implies paired) may be
         multi-line FASTA or FASTQ, plain, gzip or BGZF, a regular file or a pipe; or `reads` alone is a BAM file (unaligned, or grouped by read name: recognised
         from its bytes, pairs from flag 0x1 of its records -- paired=True on a BAM without it is refused).  Batches are cut by align_file's rules (-t, -K, the 150 Mbase floor for
@@ -820,16 +855,16 @@ class Aligner:
             try:
                 return self.align_files(reads, None, out=out, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads, fmt=fmt, level=level, sort=sort, index=index,
                                         sort_mem=sort_mem, sort_tmp=sort_tmp, sort_window=sort_window, markdup=markdup, markdup_metrics=markdup_metrics, keep_rg=True,
-                                        index_format=index_format, csi_min_shift=csi_min_shift)
+                                        index_format=index_format, csi_min_shift=csi_min_shift, optical_distance=optical_distance)
             finally:
                 self._keep_rg = None
                 self._groups = None
                 nat = getattr(self, "_native", None)
                 if nat is not None:
                     nat.set_keep_rg(False)
-        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14:
+        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None:
             return self._align_bam(lambda o: self.align_files(reads, mates, out=o, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads, keep_rg=keep_rg), out, fmt, level,
-                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift)
+                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift, optical_distance)
         binary = "b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")
         paired = bool(paired or mates is not None)
         cb = 0
@@ -863,7 +898,7 @@ class Aligner:
 
     def align_groups(self, groups, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
                      sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
-                     index_format: str = "bai", csi_min_shift: int = 14) -> int:
+                     index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None) -> int:
         """several read groups -- a sample's lanes and libraries -- into one output (bmh_aligner_run_groups).  groups: [(rg_line, reads, mates or None), ...]; every
         rg_line is unescaped and checked as -R's value is, reads / mates are what align_files takes (one file or R1 + R2; plain, gzip or BGZF; FASTA or FASTQ; or
         one BAM, whose own @RG lines and RG tags stay ignored: align_files(keep_rg=True) is the run that keeps them, and the two do not combine).  Group g's records are byte for byte those of align_files(reads_g, mates_g) alone under -R rg_g, and
@@ -892,9 +927,9 @@ class Aligner:
             raise NotImplementedError("align_groups needs the native pipeline (BMH_ALIGNER_NATIVE=0 and profile runs write batch after batch)")
         self._groups = parsed
         try:
-            if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14:
+            if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None:
                 return self._align_bam(lambda o: self._run_groups(parsed, libs, o, paired, chunk_bases, batch_reads), out, fmt, level,
-                                       sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift)
+                                       sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift, optical_distance)
             return self._run_groups(parsed, libs, out, paired, chunk_bases, batch_reads)
         finally:
             self._groups = None

@@ -47,6 +47,8 @@ EXPORTED_SYMBOLS = [
     "bmh_aligner_markdup_library_counts", "bmh_aligner_run_groups",
     "bmh_bam_reads_groups_device", "bmh_bam_reads_groups_host", "bmh_bam_header_read_groups", "bmh_format_sam_groups", "bmh_aligner_set_keep_rg",
     "bmh_aligner_set_index_format", "bmh_bam_sorted_file_ex_device", "bmh_bam_sorted_file_ex_host",
+    "bmh_bam_markdup_optical_device", "bmh_bam_markdup_optical_host", "bmh_bam_dup_locations_device", "bmh_bam_dup_locations_host", "bmh_bam_name_location", "bmh_library_size",
+    "bmh_aligner_set_markdup_optical", "bmh_aligner_markdup_optical_counts", "bmh_aligner_markdup_optical_ms",
 ]
 
 
@@ -424,16 +426,123 @@ def _library_counts(names, flat) -> dict:
     return {nm: dict(zip(MARKDUP_COUNTS, (int(v) for v in flat[8 * k:8 * k + 8]))) for k, nm in enumerate(names)}
 
 
-def bam_markdup(records: bytes, host: bool = False, read_groups=None) -> tuple:
+OPTICAL_COUNTS = ("optical_duplicate_pairs", "located_pairs", "optical_sets_skipped")
+LOCATION_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("tile", "<u4"), ("rg", "<u2"), ("flags", "<u2")])      # bdp_loc_t; flags: 1 located, 2 role
+
+
+def optical_distance_value(value, what: str) -> int:
+    """the keyword optical_distance of the marking calls: an integer in 0 .. 2^31 - 1; ValueError otherwise"""
+    if not isinstance(value, (int, np.integer)) or isinstance(value, bool) or not 0 <= value <= 0x7fffffff:
+        raise ValueError(f"{what}: optical_distance {value!r}: an integer in 0 .. 2^31 - 1")
+    return int(value)
+
+
+def _bam_markdup_optical(records: bytes, host: bool, read_groups, distance, max_set) -> tuple:
+    L = load_library()
+    L.bmh_free.argtypes = [C.c_void_p]
+    distance = optical_distance_value(distance, "bam_markdup")
+    if max_set is None:
+        max_set = 0
+    elif not isinstance(max_set, (int, np.integer)) or isinstance(max_set, bool) or not 1 <= max_set <= 0x7fffffff:
+        raise ValueError(f"bam_markdup: optical_max_set {max_set!r}: an integer in 1 .. 2^31 - 1")
+    out, counts, opt = C.c_void_p(), (C.c_uint64 * 8)(), (C.c_uint64 * 3)()
+    names = []
+    ids = lib = lc = lo = None
+    ng = 0
+    if read_groups is not None:
+        ids, lib, ng, names = _library_table(read_groups)
+        lc = (C.c_uint64 * (8 * max(len(names), 1)))()
+        lo = (C.c_uint64 * (3 * max(len(names), 1)))()
+    head = [C.c_char_p, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int, C.c_int64, C.c_uint64]
+    tail = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    if host:
+        L.bmh_bam_markdup_optical_host.argtypes = head + tail
+        rc = L.bmh_bam_markdup_optical_host(records, len(records), ids, lib, ng, distance, int(max_set), C.byref(out), counts, lc, opt, lo)
+    else:
+        import torch
+        L.bmh_bam_markdup_optical_device.argtypes = head + [C.c_void_p] + tail
+        rc = L.bmh_bam_markdup_optical_device(records, len(records), ids, lib, ng, distance, int(max_set), torch.cuda.current_stream().cuda_stream, C.byref(out), counts, lc, opt, lo)
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_markdup: " + _err(L))
+    try:
+        c = dict(zip(MARKDUP_COUNTS, (int(v) for v in counts)))
+        c.update(zip(OPTICAL_COUNTS, (int(v) for v in opt)))
+        if read_groups is not None:
+            c["libraries"] = _library_counts(names, lc)
+            for k, nm in enumerate(names):
+                c["libraries"][nm].update(zip(OPTICAL_COUNTS, (int(v) for v in lo[3 * k:3 * k + 3])))
+        return (C.string_at(out.value, len(records)) if records else b""), c
+    finally:
+        L.bmh_free(out)
+
+
+def bam_dup_locations(records: bytes, host: bool = False, read_groups=None) -> np.ndarray:
+    """bmh_bam_dup_locations_device (host=True: _host): a record stream as bam_markdup takes it -> one location per template, a structured array of LOCATION_DTYPE
+    (x, y, tile, rg: the row of the template's read group in read_groups, 0 without them; flags: 1 located, 2 role).  This is the optical step's first half on its own."""
+    L = load_library()
+    records = bytes(records)
+    L.bmh_free.argtypes = [C.c_void_p]
+    out, nt = C.c_void_p(), C.c_uint64(0)
+    ids = lib = None
+    ng = 0
+    if read_groups is not None:
+        ids, lib, ng, _names = _library_table(read_groups)
+    head = [C.c_char_p, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int]
+    if host:
+        L.bmh_bam_dup_locations_host.argtypes = head + [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        rc = L.bmh_bam_dup_locations_host(records, len(records), ids, lib, ng, C.byref(out), C.byref(nt))
+    else:
+        import torch
+        L.bmh_bam_dup_locations_device.argtypes = head + [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        rc = L.bmh_bam_dup_locations_device(records, len(records), ids, lib, ng, torch.cuda.current_stream().cuda_stream, C.byref(out), C.byref(nt))
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_dup_locations: " + _err(L))
+    try:
+        return np.frombuffer(C.string_at(out.value, 16 * nt.value) if nt.value else b"", dtype=LOCATION_DTYPE).copy()
+    finally:
+        L.bmh_free(out)
+
+
+def bam_name_location(name):
+    """bmh_bam_name_location: the read name's (tile, x, y) by the optical step's rules, or None when it has no location"""
+    L = load_library()
+    name = name if isinstance(name, bytes) else str(name).encode()
+    out = (C.c_uint32 * 3)()
+    L.bmh_bam_name_location.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    rc = L.bmh_bam_name_location(name, len(name), out)
+    if rc < 0:
+        raise ValueError("bmh_bam_name_location: " + _err(L))
+    return (int(out[0]), int(out[1]), int(out[2])) if rc == 1 else None
+
+
+def estimate_library_size(n: int, c: int):
+    """bmh_library_size: Picard's ESTIMATED_LIBRARY_SIZE from n = pairs examined minus optical duplicate pairs and c = pairs examined minus duplicate pairs; None
+    where Picard leaves the column empty (n == 0 or nothing duplicated)"""
+    L = load_library()
+    if n < 0 or c < 0:
+        return None
+    size = C.c_int64(0)
+    L.bmh_library_size.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_int64)]
+    return int(size.value) if L.bmh_library_size(int(n), int(c), C.byref(size)) == 1 else None
+
+
+def bam_markdup(records: bytes, host: bool = False, read_groups=None, optical_distance=None, optical_max_set=None) -> tuple:
     """bmh_bam_markdup_device (host=True: bmh_bam_markdup_host, no device needed): a stream of BAM records in the writer's order (a template's records next to
     each other, its first primary line first) -> (the same records with flag 0x400 on every record of every duplicate template, the counts by MARKDUP_COUNTS'
     names).  Picard MarkDuplicates' rules.  A cut stream, one whose first record begins no template and a paired template without both of its
     primary lines raise ValueError.
     read_groups: [(id, library_name), ...] (bmh_bam_markdup_groups_*) -- duplicates are called within a library only, a template's library being that of the RG:Z
     tag on its first record; the counts gain "libraries": {library_name: counts}, in order of first appearance.  A template without the tag or with an ID that is
-    not listed, more than 255 libraries and a repeated ID raise ValueError.  Without read_groups no tag is read."""
+    not listed, more than 255 libraries and a repeated ID raise ValueError.  Without read_groups no tag is read.
+    optical_distance (bmh_bam_markdup_optical_*): also count the optical duplicates -- pairs of one duplicate set whose names place them on one tile within that
+    many pixels in x and y -- the counts gain OPTICAL_COUNTS' names, with read_groups per library too; the records are those of the call without
+    it.  optical_max_set (needs optical_distance; default 300 000): sets of more pairs are not examined."""
     L = load_library()
     records = bytes(records)
+    if optical_max_set is not None and optical_distance is None:
+        raise ValueError("bam_markdup: optical_max_set needs optical_distance")
+    if optical_distance is not None:
+        return _bam_markdup_optical(records, host, read_groups, optical_distance, optical_max_set)
     L.bmh_free.argtypes = [C.c_void_p]
     out, counts = C.c_void_p(), (C.c_uint64 * 8)()
     if read_groups is not None:
@@ -738,6 +847,31 @@ class NativeAligner:
         L.bmh_aligner_set_markdup.argtypes = [C.c_void_p, C.c_int]
         if L.bmh_aligner_set_markdup(self.handle, 1 if on else 0) != 0:
             raise ValueError("bmh_aligner_set_markdup: " + _err(L))
+
+    def set_markdup_optical(self, distance=None) -> None:
+        """bmh_aligner_set_markdup_optical: the marked runs that follow count optical duplicates within `distance` (None: off; refused unless marking is on)"""
+        L = load_library()
+        L.bmh_aligner_set_markdup_optical.argtypes = [C.c_void_p, C.c_int64]
+        if L.bmh_aligner_set_markdup_optical(self.handle, -1 if distance is None else int(distance)) != 0:
+            raise ValueError("bmh_aligner_set_markdup_optical: " + _err(L))
+
+    def markdup_optical_counts(self, lib: int = -1) -> dict:
+        """bmh_aligner_markdup_optical_counts: the optical counts of the last run that counted them, by OPTICAL_COUNTS' names -- of library `lib`, or (-1) in total"""
+        L = load_library()
+        L.bmh_aligner_markdup_optical_counts.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
+        c = (C.c_uint64 * 3)()
+        if L.bmh_aligner_markdup_optical_counts(self.handle, int(lib), c) != 0:
+            raise ValueError("bmh_aligner_markdup_optical_counts: " + _err(L))
+        return dict(zip(OPTICAL_COUNTS, (int(v) for v in c)))
+
+    def markdup_optical_ms(self) -> float:
+        """bmh_aligner_markdup_optical_ms: the share of the last such run's decision that the optical step took, in ms"""
+        L = load_library()
+        L.bmh_aligner_markdup_optical_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        t = C.c_double(0)
+        if L.bmh_aligner_markdup_optical_ms(self.handle, C.byref(t)) != 0:
+            raise ValueError("bmh_aligner_markdup_optical_ms: " + _err(L))
+        return float(t.value)
 
     def markdup_counts(self) -> dict:
         """bmh_aligner_markdup_counts: the counts of the last run that marked duplicates, by MARKDUP_COUNTS' names"""

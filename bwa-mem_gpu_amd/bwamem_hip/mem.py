@@ -16,9 +16,13 @@ bytes are those of --sort), --csi-min-shift N (needs --csi: the index's smallest
 (needs --sort: flag 0x400 on every record of every duplicate template,
 decided on the device by Picard MarkDuplicates' rules -- the unclipped 5' ends and strands of a template's primary lines are the key, the sum of the base
 qualities >= 15 the score, ties go to the template that came first in the input, a fragment is a duplicate wherever a pair has an end; unlike Picard and
-`samtools markdup` on coordinate-sorted input the secondary and supplementary lines of a duplicate template are flagged too; no optical duplicates, no
-library-size estimate, nothing is removed; with --csi a contig beyond 2^30 - 2^24 bases is refused for --markdup, by name) and --markdup-metrics PATH
-(a Picard-style table of the counts, one row per library).  --rg LINE opens a read group:
+`samtools markdup` on coordinate-sorted input the secondary and supplementary lines of a duplicate template are flagged too; nothing is removed, no DT:Z
+tag is written, keys know no UMI; with --csi a contig beyond 2^30 - 2^24 bases is refused for --markdup, by name), --markdup-metrics PATH
+(a Picard-style table of the counts, one row per library) and --optical-distance N (needs --markdup; a whole number, 0 .. 2^31 - 1 -- Picard uses 100, and 2500
+on patterned flow cells; there is no default: the option turns the step on -- the decision also counts the optical duplicates: pairs of one duplicate set whose
+read names, Illumina's 5 or 7 ':'-separated fields ending in tile:x:y, place them on one tile of one read group within N pixels in x and in y, clusters being
+the connected components; the BAM and its index stay byte for byte those of --markdup, and the metrics table gains READ_PAIR_OPTICAL_DUPLICATES and
+ESTIMATED_LIBRARY_SIZE in Picard's column order; the names' pattern is fixed).  --rg LINE opens a read group:
 LINE is an @RG line as -R takes it, and the one or two files that follow it, up to the next --rg, are that group's input (Aligner.align_groups): a sample's lanes
 and libraries go into one output, every record with its group's RG:Z, the header with every @RG line, and --markdup calls duplicates within a library (the LB
 field; groups with one LB are lanes of one library) only.  -p applies to every group; --rg and -R exclude each other.  --keep-rg keeps the read groups of the
@@ -54,7 +58,7 @@ def main(argv=None) -> int:
     opts, pos, out_path, interleaved, long_reads, device = [], [], None, False, False, "cuda:0"
     bam, bam_level = False, 1
     sort, index_path, sort_mem, sort_tmp = False, None, None, None
-    markdup, metrics_path = False, None
+    markdup, metrics_path, optical = False, None, None
     csi, csi_shift = False, None
     keep_rg = False
     groups = []                                                     # --rg LINE: [line, files...]; the positionals behind it are its files
@@ -84,6 +88,12 @@ def main(argv=None) -> int:
                 print("[bwamem_hip.mem] option --csi-min-shift needs a number in 10 .. 24", file=sys.stderr)
                 return 2
             csi_shift = int(argv[i + 1])
+            i += 1
+        elif a == "--optical-distance":
+            if i + 1 >= len(argv) or not (argv[i + 1].isascii() and argv[i + 1].isdigit()) or int(argv[i + 1]) > 0x7fffffff:
+                print("[bwamem_hip.mem] option --optical-distance needs a whole number of pixels, 0 .. 2^31 - 1", file=sys.stderr)
+                return 2
+            optical = int(argv[i + 1])
             i += 1
         elif a == "--keep-rg":
             keep_rg = True
@@ -159,6 +169,9 @@ def main(argv=None) -> int:
     if metrics_path is not None and not markdup:
         print("[bwamem_hip.mem] --markdup-metrics needs --markdup", file=sys.stderr)
         return 2
+    if optical is not None and not markdup:
+        print("[bwamem_hip.mem] --optical-distance needs --markdup (optical duplicates are counted where duplicates are marked)", file=sys.stderr)
+        return 2
     if csi_shift is not None and not csi:
         print("[bwamem_hip.mem] --csi-min-shift needs --csi (a BAI index has one bin size)", file=sys.stderr)
         return 2
@@ -179,6 +192,8 @@ def main(argv=None) -> int:
             fmt_kw.update(sort=True, index=index_path, sort_mem=sort_mem, sort_tmp=sort_tmp)
         if markdup:
             fmt_kw.update(markdup=True, markdup_metrics=metrics_path)
+        if optical is not None:
+            fmt_kw.update(optical_distance=optical)
         if csi:
             fmt_kw.update(index_format="csi", csi_min_shift=14 if csi_shift is None else csi_shift)
         done = False

@@ -31,8 +31,16 @@ int bdp_group_refused(uint32_t rec, int st, const char *fn);
 // records in the writer's order with offsets off [n + 1] -> tpl [n]: every record's template ordinal in the stream; entries: one per template; info [2] += the
 // secondary or supplementary and the unmapped records.  Not BMH_OK (message set): the first record begins no template, or a paired template lacks a primary line
 // G (or NULL): the run's read groups -- the entries carry their templates' libraries; a first record without RG:Z, or with an ID G does not hold, is refused too
+// locs (or NULL): optical duplicates are counted -- every template's location (csrc/bam_dup_core.h) beside its entry
 int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn,
-                     const bdp_groups_t *G = nullptr);
+                     const bdp_groups_t *G = nullptr, std::vector<bdp_loc_t> *locs = nullptr);
+// the optical step of a run: the distance (0 .. 2^31 - 1), the largest set examined, and where its three counts go (BDP_OPT_*): out [3], lib_out [3 * n_lib] or NULL
+struct bdp_optical_t { int64_t distance; uint32_t max_set; uint64_t *out, *lib_out; };
+// distance and max_set as the entry points take them (max_set 0: BDP_OPT_MAX_SET) -> BMH_EINVAL with a message, or BMH_OK
+int bdp_optical_check(int64_t distance, uint64_t max_set, const char *fn);
+// the optical duplicates among the pairs of E [T] with locations L [T], single-threaded through the clustering core of csrc/bam_dup_core.h (its invariant asserted);
+// n_lib 0: no libraries, lib_out unused
+void bdp_optical_host(const bdp_entry_t *E, const bdp_loc_t *L, uint64_t T, const bdp_optical_t &O, uint32_t n_lib);
 // the decision: bits [(T + 31) / 32]: bit t set when template t is a duplicate; counts [0 .. 4]; lib_counts (or NULL) [BDP_N_COUNTS * n_lib]: every library's own
 // counts, of which the decision fills (and zeroes the rest of) words 0 .. 4
 void bdp_decide_host(const bdp_entry_t *entries, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5], uint32_t n_lib = 0, uint64_t *lib_counts = nullptr);
@@ -40,7 +48,9 @@ void bdp_decide_host(const bdp_entry_t *entries, uint64_t T, std::vector<uint32_
 // records' template ordinals, E [T]: entries made with read groups)
 void bdp_lib_tally_host(const uint8_t *recs, const uint64_t *off, uint32_t n, const uint32_t *tpl, const bdp_entry_t *E, uint64_t T, uint32_t n_lib, uint64_t *lib_counts);
 // the whole of it on a walked stream: flags set in place; T, lib_counts [BDP_N_COUNTS * T->n_lib] (or NULL): with read groups, and every library's counts
-int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn, const bdp_table_t *T = nullptr, uint64_t *lib_counts = nullptr);
+// O (or NULL): count the optical duplicates too
+int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn, const bdp_table_t *T = nullptr, uint64_t *lib_counts = nullptr,
+                     const bdp_optical_t *O = nullptr);
 
 // csrc/bam_dup_kernels.hip
 struct bdp_dev_t;                                                  // device buffers of the batches' entries, the decision and the bitmap; kept between calls
@@ -51,8 +61,9 @@ void bdp_dev_free(bdp_dev_t *d);
 // With read groups (bdp_dev_set_groups) *d_info has BDP_INFO_WORDS words: [4], [5] the first template's first record + 1 without an RG:Z tag / with an ID the
 // table does not hold (0xffffffff: none)
 enum { BDP_INFO_WORDS = 8 };
+// d_locs (or NULL): optical duplicates are counted -- *d_locs [as many as entries]: every template's location, written by the lane that makes its entry
 int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint32_t **d_tpl,
-                     const bdp_entry_t **d_entries, const uint32_t **d_info);
+                     const bdp_entry_t **d_entries, const uint32_t **d_info, const bdp_loc_t **d_locs = nullptr);
 // a batch whose templates are of several libraries (a run that keeps its input's read groups), after bdp_batch_device on the same batch: *d_lib3 [3 * n_lib] -- every
 // library's secondary / supplementary records, unmapped records and templates, a record counted under the library of its template's entry (bdp_lib_tally_host's
 // three, per batch) -- in d until its next call.  n_lib <= BDP_MAX_LIBS.
@@ -67,6 +78,9 @@ int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *f
 // n_records: the records of the final sort that follows (csrc/bam_sort_kernels.hip: 24 bytes each and the sort's work space) -- the decision's buffers are freed
 // before that sort allocates, so one check of the larger of the two needs refuses here what either would refuse
 // n_lib, lib_counts [BDP_N_COUNTS * n_lib] (or 0, NULL): words 0 .. 4 of every library's counts, from the entries' library bytes and the bitmap (the other words zeroed)
-int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records = 0, uint32_t n_lib = 0, uint64_t *lib_counts = nullptr);
+// O, locs [T] (host; or NULL): the optical step after the pair pass, on the pairs as that pass left them -- sets of equal keys next to each other.  opt_ms (or NULL)
+// += its milliseconds (events around its kernels, the upload of the locations included)
+int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records = 0, uint32_t n_lib = 0, uint64_t *lib_counts = nullptr,
+                      const bdp_optical_t *O = nullptr, const bdp_loc_t *locs = nullptr, double *opt_ms = nullptr);
 // records d_recs at d_off [n] (device; all inside `total` bytes) whose global template ordinals are tord [n] (host): byte 19 |= 0x04 where the bitmap says so
 int bdp_flag_device(bdp_dev_t *d, uint8_t *d_recs, const uint64_t *d_off, const uint32_t *tord, uint32_t n, uint64_t total, void *stream);

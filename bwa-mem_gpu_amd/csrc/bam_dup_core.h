@@ -22,7 +22,22 @@
 //             pair's end, and the best fragment stays, within one library only -- keys of different libraries differ, the decision's passes do not change.
 //             Without a table no tag is read and every byte is as it was
 //
-// No optical duplicates, no library-size estimate, nothing is removed.
+//   optical   only when the run asks for it (an optical distance D): counts, never flags -- the records' bytes stay those of the run without it
+//     location  of a template, from the read name of its first record (without the NUL): split at ':'; with exactly 5 or 7 fields tile, x and y are the last
+//               three, any other field count gives none.  A field's value is its leading run of ASCII digits -- at least one, the value below 2^31; what
+//               follows the digits is ignored (..:15343#ACGT parses, as with Picard's rapidParseInt).  No digit, a sign, or 2^31 and more: no location.  A
+//               template without one is never an optical duplicate and joins no cluster
+//     role      1 when the pair's smaller end word belongs to the 0x80 record and the two end words differ, else 0 (Picard's orientationForOpticalDuplicates:
+//               copies of one cluster have the same mate on the same side)
+//     group     the row of the RG:Z ID in the run's table (the row whose library the end words carry); 0 without a table
+//     set       the pairs of one key (lo, hi), the one that stays included.  Sets of one pair, and sets of more than max_set pairs (300 000, Picard's
+//               MAX_OPTICAL_DUPLICATE_SET_SIZE), are not examined; the latter are counted
+//     edge      between two located pairs of a set: same group, same role, same tile, |x1 - x2| <= D and |y1 - y2| <= D (differences in 64 bits)
+//     count     clusters are the connected components; a cluster of k pairs has k - 1 optical duplicates, so a set counts its located members minus their
+//               components, whichever member stays.  In total and per library; fragments never count
+//     size      bdp_library_size: Picard's estimateLibrarySize
+//
+// Nothing is removed, no DT:Z tag is written, keys know no UMI, the names' pattern is fixed.
 #pragma once
 #include "bam_sort_core.h"
 
@@ -80,9 +95,10 @@ BSR_FN uint32_t bdp_score(const uint8_t *rec, uint64_t sz)
 }
 
 // the entry of the template whose records are a .. b - 1 of a stream with offsets off [n + 1]; false: a paired template without both of its primary lines
-BSR_FN bool bdp_entry(const uint8_t *recs, const uint64_t *off, uint32_t a, uint32_t b, bdp_entry_t *e)
+// role (or NULL): the pair's role for optical duplicates
+BSR_FN bool bdp_entry(const uint8_t *recs, const uint64_t *off, uint32_t a, uint32_t b, bdp_entry_t *e, uint32_t *role = nullptr)
 {
-	uint64_t w[2] = {0, 0}; uint32_t n_map = 0, n_pri = 0, seen = 0; uint64_t score = 0; bool paired = false;
+	uint64_t w[2] = {0, 0}; uint32_t n_map = 0, n_pri = 0, seen = 0, second[2] = {0, 0}; uint64_t score = 0; bool paired = false;
 	for (uint32_t i = a; i < b; ++i) {
 		const uint8_t *rec = recs + off[i];
 		const uint32_t fl = bsr_flag(rec);
@@ -90,7 +106,7 @@ BSR_FN bool bdp_entry(const uint8_t *recs, const uint64_t *off, uint32_t a, uint
 		++n_pri;
 		if (fl & 1u) { paired = true; seen |= (fl & 0x40u ? 1u : 0u) | (fl & 0x80u ? 2u : 0u); }
 		score += bdp_score(rec, off[i + 1] - off[i]);
-		if (!(fl & 4u) && n_map < 2) w[n_map++] = bdp_end_word(rec);
+		if (!(fl & 4u) && n_map < 2) { second[n_map] = (fl >> 7) & 1u; w[n_map++] = bdp_end_word(rec); }
 	}
 	e->score = score > 0xffffffffull ? 0xffffffffu : (uint32_t)score;
 	e->lo = e->hi = ~0ull;
@@ -101,6 +117,7 @@ BSR_FN bool bdp_entry(const uint8_t *recs, const uint64_t *off, uint32_t a, uint
 		else if (n_map == 1) { kind = BDP_FRAG; e->lo = w[0]; }
 	}
 	e->kind_n = kind | (b - a) << 2;
+	if (role) *role = kind == BDP_PAIR && w[0] != w[1] ? second[w[0] < w[1] ? 0 : 1] : 0u;
 	return ok;
 }
 
@@ -142,8 +159,8 @@ BSR_FN const uint8_t *bdp_rg_tag(const uint8_t *rec, uint64_t sz, uint32_t *len)
 	return nullptr;
 }
 
-// the library of the record's read group by the table (compared row by row: a run has a handful of groups); -1: no RG:Z tag, -2: an ID the table does not hold
-BSR_FN int bdp_library(const uint8_t *rec, uint64_t sz, const bdp_groups_t &G)
+// the row of the record's read group in the table (compared row by row: a run has a handful of groups); -1: no RG:Z tag, -2: an ID the table does not hold
+BSR_FN int bdp_group_row(const uint8_t *rec, uint64_t sz, const bdp_groups_t &G)
 {
 	uint32_t len = 0;
 	const uint8_t *id = bdp_rg_tag(rec, sz, &len);
@@ -153,21 +170,26 @@ BSR_FN int bdp_library(const uint8_t *rec, uint64_t sz, const bdp_groups_t &G)
 		if (G.id_off[g + 1] - a != len) continue;
 		uint32_t k = 0;
 		while (k < len && (uint8_t)G.ids[a + k] == id[k]) ++k;
-		if (k == len) return G.lib[g];
+		if (k == len) return (int)g;
 	}
 	return -2;
 }
+// the library of the record's read group; -1, -2 as bdp_group_row
+BSR_FN int bdp_library(const uint8_t *rec, uint64_t sz, const bdp_groups_t &G) { const int g = bdp_group_row(rec, sz, G); return g < 0 ? g : (int)G.lib[g]; }
 
 BSR_FN uint64_t bdp_lib_word(uint64_t word, uint32_t lib) { return (word & ((1ull << BDP_LIB_SHIFT) - 1)) | (uint64_t)lib << BDP_LIB_SHIFT; }
 // the library of an entry that bdp_entry_lib made
 BSR_FN uint32_t bdp_lib_of(const bdp_entry_t &e) { return (uint32_t)(e.lo >> BDP_LIB_SHIFT); }
 
 // bdp_entry with the library of the template's first record in the end words; BDP_E_*
-BSR_FN int bdp_entry_lib(const uint8_t *recs, const uint64_t *off, uint32_t a, uint32_t b, const bdp_groups_t &G, bdp_entry_t *e)
+// role, row (or NULL): the pair's role and the table row of its read group, for optical duplicates
+BSR_FN int bdp_entry_lib(const uint8_t *recs, const uint64_t *off, uint32_t a, uint32_t b, const bdp_groups_t &G, bdp_entry_t *e, uint32_t *role = nullptr, uint32_t *row = nullptr)
 {
-	const bool ok = bdp_entry(recs, off, a, b, e);
-	const int lib = bdp_library(recs + off[a], off[a + 1] - off[a], G);
-	if (lib < 0) return lib == -1 ? BDP_E_NO_RG : BDP_E_RG_UNKNOWN;
+	const bool ok = bdp_entry(recs, off, a, b, e, role);
+	const int g = bdp_group_row(recs + off[a], off[a + 1] - off[a], G);
+	if (g < 0) return g == -1 ? BDP_E_NO_RG : BDP_E_RG_UNKNOWN;
+	const int lib = G.lib[g];
+	if (row) *row = (uint32_t)g;
 	if (!ok) return BDP_E_TEMPLATE;
 	e->lo = bdp_lib_word(e->lo, (uint32_t)lib);                            // (of every kind: a template that is neither pair nor fragment keeps its library here too, for the counts)
 	if (bdp_kind(*e) == BDP_PAIR) e->hi = bdp_lib_word(e->hi, (uint32_t)lib);
@@ -176,3 +198,118 @@ BSR_FN int bdp_entry_lib(const uint8_t *recs, const uint64_t *off, uint32_t a, u
 
 // where a pair's or a fragment's entry counts among its library's five counters: examined (0 pairs, 1 fragments), and as a duplicate 2 / 3 and its records at 4
 BSR_FN uint32_t bdp_examined_slot(const bdp_entry_t &e) { return bdp_kind(e) == BDP_PAIR ? 0u : 1u; }
+
+// ---- optical duplicates
+
+enum { BDP_LOC_LOCATED = 1, BDP_LOC_ROLE = 2, BDP_OPT_MAX_SET = 300000, BDP_OPT_MAX_GROUPS = 65536 };
+// the three counts of the optical step: optical duplicate pairs, examined pairs with a location, sets skipped for their size
+enum { BDP_OPT_DUPS = 0, BDP_OPT_LOCATED = 1, BDP_OPT_SKIPPED = 2, BDP_OPT_N = 3 };
+
+// one template's place on the flow cell; flags: BDP_LOC_LOCATED | BDP_LOC_ROLE
+struct bdp_loc_t { int32_t x, y; uint32_t tile; uint16_t rg, flags; };
+static_assert(sizeof(bdp_loc_t) == 16, "a location is 16 bytes");
+
+// the leading run of ASCII digits of p [n] -> *v; false: no digit first, or 2^31 and more
+BSR_FN bool bdp_field_value(const uint8_t *p, uint32_t n, uint32_t *v)
+{
+	uint64_t x = 0; uint32_t k = 0;
+	while (k < n && p[k] >= '0' && p[k] <= '9') {                      // (x stays below 2^31 before every step: no overflow)
+		x = 10 * x + (uint32_t)(p[k] - '0');
+		if (x >> 31) return false;
+		++k;
+	}
+	*v = (uint32_t)x;
+	return k > 0;
+}
+
+// tile, x, y of a read name (len bytes, no NUL) -> out [3]; false: no location
+BSR_FN bool bdp_name_location(const uint8_t *name, uint32_t len, uint32_t out[3])
+{
+	uint32_t n_colon = 0, a0 = 0, a1 = 0, a2 = 0;                         // where the last three fields begin (scalars: nothing here is indexed, so nothing goes to scratch)
+	for (uint32_t i = 0; i < len; ++i) if (name[i] == ':') { ++n_colon; a0 = a1; a1 = a2; a2 = i + 1; }
+	if (n_colon != 4 && n_colon != 6) return false;
+	uint32_t tile = 0, x = 0, y = 0;
+	if (!bdp_field_value(name + a0, a1 - 1 - a0, &tile) || !bdp_field_value(name + a1, a2 - 1 - a1, &x) || !bdp_field_value(name + a2, len - a2, &y)) return false;
+	out[0] = tile; out[1] = x; out[2] = y;
+	return true;
+}
+
+// the location of the template whose first record is rec (its name vouched for by bsr_record_bytes)
+BSR_FN bdp_loc_t bdp_location(const uint8_t *rec, uint32_t role, uint32_t row)
+{
+	bdp_loc_t l; l.x = l.y = 0; l.tile = 0; l.rg = (uint16_t)row; l.flags = (uint16_t)(role ? BDP_LOC_ROLE : 0);
+	uint32_t v[3];
+	const uint32_t ln = rec[12];
+	if (ln && bdp_name_location(rec + BSR_FIXED, ln - 1, v)) { l.tile = v[0]; l.x = (int32_t)v[1]; l.y = (int32_t)v[2]; l.flags |= BDP_LOC_LOCATED; }
+	return l;
+}
+
+// the sort words of the clustering: members of one set, group and role next to each other, there by tile, then x
+BSR_FN uint64_t bdp_opt_word1(const bdp_loc_t &l) { return (uint64_t)l.tile << 32 | (uint32_t)l.x; }
+BSR_FN uint64_t bdp_opt_word2(uint32_t set_head, const bdp_loc_t &l) { return (uint64_t)set_head << 17 | (uint64_t)l.rg << 1 | ((l.flags & BDP_LOC_ROLE) ? 1u : 0u); }
+
+// Union-find over the members in sorted order.  The invariant: parent [v] <= v at all times, and a stored value only ever gets smaller -- so every find
+// descends strictly and ends at a root (parent [v] == v) after at most v steps.  On the device the lanes share `parent` in global memory: a root is hooked with
+// a compare-and-swap (only a root is hooked, and under a smaller index), paths are halved with an atomic minimum.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define BDP_UF_LOAD(p) __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define BDP_UF_MIN(p, v) atomicMin(p, v)
+#define BDP_UF_CAS(p, o, v) (atomicCAS(p, o, v) == (o))
+#else
+#define BDP_UF_LOAD(p) (*(p))
+#define BDP_UF_MIN(p, v) do { if ((v) < *(p)) *(p) = (v); } while (0)
+#define BDP_UF_CAS(p, o, v) (*(p) == (o) ? (*(p) = (v), true) : false)
+#endif
+
+BSR_FN uint32_t bdp_uf_find(uint32_t *parent, uint32_t v)
+{
+	for (;;) {                                                          // (every round ends or goes on at p < v)
+		const uint32_t p = BDP_UF_LOAD(parent + v);
+		if (p >= v) return v;                                         // (p == v: a root; p > v never is)
+		const uint32_t g = BDP_UF_LOAD(parent + p);
+		if (g < p) BDP_UF_MIN(parent + v, g);
+		v = p;
+	}
+}
+
+BSR_FN void bdp_uf_unite(uint32_t *parent, uint32_t a, uint32_t b)
+{
+	// every round either ends, or another lane's hook has taken a root away: roots only disappear, and there are finitely many
+	for (;;) {
+		a = bdp_uf_find(parent, a); b = bdp_uf_find(parent, b);
+		if (a == b) return;
+		if (a < b) { const uint32_t t = a; a = b; b = t; }               // the larger root goes under the smaller
+		if (BDP_UF_CAS(parent + a, a, b)) return;
+	}
+}
+
+// member i of n in sorted order (word2, then tile, then x): it walks j = i + 1 .. while set, group, role and tile are its own and x_j - x_i <= D, and unites with
+// those whose y lies within D.  The walk ends at n at the latest: j only grows
+BSR_FN void bdp_opt_walk(uint32_t i, uint32_t n, const uint64_t *word2, const uint32_t *tile, const int32_t *x, const int32_t *y, int64_t D, uint32_t *parent)
+{
+	const uint64_t w = word2[i]; const uint32_t t = tile[i]; const int64_t xi = x[i], yi = y[i];
+	for (uint32_t j = i + 1; j < n; ++j) {
+		if (word2[j] != w || tile[j] != t || (int64_t)x[j] - xi > D) break;
+		const int64_t dy = (int64_t)y[j] - yi;
+		if ((dy < 0 ? -dy : dy) <= D) bdp_uf_unite(parent, i, j);
+	}
+}
+
+// Picard's estimateLibrarySize: n pairs that are no optical duplicates, c of them distinct; 0: no estimate (the column stays empty)
+inline int64_t bdp_library_size(uint64_t n_pairs, uint64_t n_unique, bool *has)
+{
+	*has = false;
+	if (!(n_pairs > 0 && n_pairs > n_unique) || n_unique == 0) return 0;
+	const double n = (double)n_pairs, c = (double)n_unique;
+	auto f = [&](double x) { return c / x - 1 + __builtin_exp(-n / x); };
+	double m = 1, M = 100;
+	if (!(f(m * c) >= 0)) return 0;
+	while (f(M * c) > 0) M *= 10;
+	for (int i = 0; i < 40; ++i) {
+		const double r = (m + M) / 2, u = f(r * c);
+		if (u == 0) break;
+		if (u > 0) m = r; else M = r;
+	}
+	*has = true;
+	return (int64_t)(c * (m + M) / 2);
+}

@@ -2,6 +2,7 @@
 // passes), the flags, and bmh_bam_markdup_host.  Byte for byte what csrc/bam_dup_kernels.hip gives.
 #include <stdlib.h>
 #include <string.h>
+#include <assert.h>
 #include <algorithm>
 #include <numeric>
 #include "bam_dup.h"
@@ -62,9 +63,11 @@ int bdp_refs_fit(const uint8_t *recs, const uint64_t *off, uint32_t n, const cha
 	return BMH_OK;
 }
 
-int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn, const bdp_groups_t *G)
+int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn, const bdp_groups_t *G,
+                     std::vector<bdp_loc_t> *locs)
 {
 	tpl.resize(n); entries.clear();
+	if (locs) locs->clear();
 	if (n && !bdp_head(bsr_flag(recs + off[0]))) return bdp_batch_refused(n, n + 1, fn);
 	std::vector<uint32_t> start;
 	for (uint32_t i = 0; i < n; ++i) {
@@ -76,11 +79,14 @@ int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::
 	}
 	if (start.size() >= 1ull << 31) { bmh_set_error("%s: duplicate marking: 2^31 templates", fn); return BMH_EINVAL; }
 	entries.resize(start.size());
+	if (locs) locs->resize(start.size());
 	for (size_t t = 0; t < start.size(); ++t) {
 		const uint32_t a = start[t], b = t + 1 < start.size() ? start[t + 1] : n;
-		const int st = G ? bdp_entry_lib(recs, off, a, b, *G, &entries[t]) : bdp_entry(recs, off, a, b, &entries[t]) ? BDP_E_OK : BDP_E_TEMPLATE;
+		uint32_t role = 0, row = 0;
+		const int st = G ? bdp_entry_lib(recs, off, a, b, *G, &entries[t], &role, &row) : bdp_entry(recs, off, a, b, &entries[t], &role) ? BDP_E_OK : BDP_E_TEMPLATE;
 		if (st == BDP_E_TEMPLATE) return bdp_batch_refused(n, a + 1, fn);
 		if (st != BDP_E_OK) return bdp_group_refused(a, st, fn);
+		if (locs) (*locs)[t] = bdp_location(recs + off[a], role, row);
 	}
 	return BMH_OK;
 }
@@ -123,6 +129,42 @@ void bdp_decide_host(const bdp_entry_t *E, uint64_t T, std::vector<uint32_t> &bi
 	}
 }
 
+int bdp_optical_check(int64_t distance, uint64_t max_set, const char *fn)
+{
+	if (distance < 0 || distance > 0x7fffffffll) { bmh_set_error("%s: an optical distance of %lld (0 .. 2^31 - 1)", fn, (long long)distance); return BMH_EINVAL; }
+	if (max_set > 0x7fffffffull) { bmh_set_error("%s: a largest set of %llu pairs (below 2^31; 0: %d)", fn, (unsigned long long)max_set, (int)BDP_OPT_MAX_SET); return BMH_EINVAL; }
+	return BMH_OK;
+}
+
+void bdp_optical_host(const bdp_entry_t *E, const bdp_loc_t *L, uint64_t T, const bdp_optical_t &O, uint32_t n_lib)
+{
+	for (int k = 0; k < BDP_OPT_N; ++k) O.out[k] = 0;
+	if (!O.lib_out) n_lib = 0;
+	for (uint32_t k = 0; k < BDP_OPT_N * n_lib; ++k) O.lib_out[k] = 0;
+	auto add = [&](uint32_t t, int k, uint64_t v) { O.out[k] += v; if (bdp_lib_of(E[t]) < n_lib) O.lib_out[BDP_OPT_N * (size_t)bdp_lib_of(E[t]) + k] += v; };
+	std::vector<uint32_t> pairs;
+	for (uint64_t t = 0; t < T; ++t) if (bdp_kind(E[t]) == BDP_PAIR) { pairs.push_back((uint32_t)t); if (L[t].flags & BDP_LOC_LOCATED) add((uint32_t)t, BDP_OPT_LOCATED, 1); }
+	std::sort(pairs.begin(), pairs.end(), [&](uint32_t a, uint32_t b) { return E[a].lo != E[b].lo ? E[a].lo < E[b].lo : E[a].hi != E[b].hi ? E[a].hi < E[b].hi : a < b; });
+	// the located members of the sets of 2 .. max_set pairs, every one with the index of its set's first pair
+	struct member_t { uint64_t w2, w1; uint32_t t; };
+	std::vector<member_t> mem;
+	for (size_t a = 0, b; a < pairs.size(); a = b) {
+		for (b = a + 1; b < pairs.size() && E[pairs[b]].lo == E[pairs[a]].lo && E[pairs[b]].hi == E[pairs[a]].hi;) ++b;
+		if (b - a < 2) continue;
+		if (b - a > O.max_set) { add(pairs[a], BDP_OPT_SKIPPED, 1); continue; }
+		for (size_t i = a; i < b; ++i) if (L[pairs[i]].flags & BDP_LOC_LOCATED) mem.push_back({bdp_opt_word2((uint32_t)a, L[pairs[i]]), bdp_opt_word1(L[pairs[i]]), pairs[i]});
+	}
+	std::sort(mem.begin(), mem.end(), [](const member_t &a, const member_t &b) { return a.w2 != b.w2 ? a.w2 < b.w2 : a.w1 != b.w1 ? a.w1 < b.w1 : a.t < b.t; });
+	const uint32_t m = (uint32_t)mem.size();
+	std::vector<uint64_t> w2(m); std::vector<uint32_t> tile(m), parent(m); std::vector<int32_t> x(m), y(m);
+	for (uint32_t j = 0; j < m; ++j) { const bdp_loc_t &l = L[mem[j].t]; w2[j] = mem[j].w2; tile[j] = l.tile; x[j] = l.x; y[j] = l.y; parent[j] = j; }
+	for (uint32_t i = 0; i < m; ++i) {
+		bdp_opt_walk(i, m, w2.data(), tile.data(), x.data(), y.data(), O.distance, parent.data());
+		assert(parent[i] <= i);
+	}
+	for (uint32_t j = 0; j < m; ++j) { assert(parent[j] <= j); if (parent[j] != j) add(mem[j].t, BDP_OPT_DUPS, 1); }
+}
+
 void bdp_lib_tally_host(const uint8_t *recs, const uint64_t *off, uint32_t n, const uint32_t *tpl, const bdp_entry_t *E, uint64_t T, uint32_t n_lib, uint64_t *lib_counts)
 {
 	for (uint64_t t = 0; t < T; ++t) if (bdp_lib_of(E[t]) < n_lib) ++lib_counts[BDP_N_COUNTS * (size_t)bdp_lib_of(E[t]) + BDP_TEMPLATES];
@@ -135,7 +177,7 @@ void bdp_lib_tally_host(const uint8_t *recs, const uint64_t *off, uint32_t n, co
 	}
 }
 
-int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn, const bdp_table_t *T, uint64_t *lib_counts)
+int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn, const bdp_table_t *T, uint64_t *lib_counts, const bdp_optical_t *O)
 {
 	const uint32_t n = (uint32_t)(off.size() - 1);
 	for (int k = 0; k < BDP_N_COUNTS; ++k) counts[k] = 0;
@@ -143,22 +185,23 @@ int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t c
 		if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) {
 			bmh_set_error("%s: record %u is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL;
 		}
-	std::vector<uint32_t> tpl, bits; std::vector<bdp_entry_t> E;
+	std::vector<uint32_t> tpl, bits; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> locs;
 	bdp_groups_t G = {nullptr, nullptr, nullptr, 0};
 	if (T) G = T->view();
 	int rc = T ? bdp_refs_fit(recs, off.data(), n, fn) : BMH_OK;
 	if (rc != BMH_OK) return rc;
-	rc = bdp_entries_host(recs, off.data(), n, tpl, E, counts + BDP_SECSUP, fn, T ? &G : nullptr);
+	rc = bdp_entries_host(recs, off.data(), n, tpl, E, counts + BDP_SECSUP, fn, T ? &G : nullptr, O ? &locs : nullptr);
 	if (rc != BMH_OK) return rc;
 	counts[BDP_TEMPLATES] = E.size();
 	bdp_decide_host(E.data(), E.size(), bits, counts, T ? T->n_lib : 0, T ? lib_counts : nullptr);
+	if (O) bdp_optical_host(E.data(), locs.data(), E.size(), *O, T ? T->n_lib : 0);
 	if (T && lib_counts) bdp_lib_tally_host(recs, off.data(), n, tpl.data(), E.data(), E.size(), T->n_lib, lib_counts);
 	for (uint32_t i = 0; i < n; ++i) if (bits[tpl[i] >> 5] >> (tpl[i] & 31) & 1u) recs[off[i] + 19] |= 0x04;
 	return BMH_OK;
 }
 
 #ifndef BDP_STANDALONE
-static int markdup_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_table_t *T, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts)
+static int markdup_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_table_t *T, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, const bdp_optical_t *O = nullptr)
 {
 	if (!out || !counts || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*out = nullptr;
@@ -168,7 +211,7 @@ static int markdup_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, c
 	uint8_t *o = (uint8_t *)malloc(n_bytes + 1);
 	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
 	if (n_bytes) memcpy(o, recs, n_bytes);
-	if ((rc = bdp_markdup_host(o, off, counts, fn, T, lib_counts)) != BMH_OK) { free(o); return rc; }
+	if ((rc = bdp_markdup_host(o, off, counts, fn, T, lib_counts, O)) != BMH_OK) { free(o); return rc; }
 	*out = o;
 	return BMH_OK;
 }
@@ -187,5 +230,61 @@ extern "C" int bmh_bam_markdup_groups_host(const uint8_t *recs, uint64_t n_bytes
 	const int rc = bdp_table_make(T, rg_ids, rg_lib, n_groups, fn);
 	if (rc != BMH_OK) return rc;
 	return markdup_host(fn, recs, n_bytes, &T, out, counts, lib_counts);
+}
+
+extern "C" int bmh_bam_markdup_optical_host(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, uint8_t **out,
+                                            uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical)
+{
+	const char *fn = "bmh_bam_markdup_optical_host";
+	bdp_table_t T;
+	if (out) *out = nullptr;
+	if (!optical) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	int rc = bdp_optical_check(distance, max_set, fn);
+	if (rc != BMH_OK) return rc;
+	const bool groups = rg_ids || rg_lib || n_groups;
+	if (groups && (rc = bdp_table_make(T, rg_ids, rg_lib, n_groups, fn)) != BMH_OK) return rc;
+	if (groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
+	const bdp_optical_t O = {distance, max_set ? (uint32_t)max_set : (uint32_t)BDP_OPT_MAX_SET, optical, groups ? lib_optical : nullptr};
+	return markdup_host(fn, recs, n_bytes, groups ? &T : nullptr, out, counts, groups ? lib_counts : nullptr, &O);
+}
+
+extern "C" int bmh_bam_dup_locations_host(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, uint8_t **locs, uint64_t *n_templates)
+{
+	const char *fn = "bmh_bam_dup_locations_host";
+	if (!locs || !n_templates || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	*locs = nullptr; *n_templates = 0;
+	bdp_table_t T;
+	const bool groups = rg_ids || rg_lib || n_groups;
+	int rc = groups ? bdp_table_make(T, rg_ids, rg_lib, n_groups, fn) : BMH_OK;
+	if (rc != BMH_OK) return rc;
+	if (groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
+	std::vector<uint64_t> off;
+	if ((rc = bsr_walk(recs, n_bytes, -1, off, fn)) != BMH_OK) return rc;
+	const uint32_t n = (uint32_t)(off.size() - 1);
+	for (uint32_t i = 0; i < n; ++i)
+		if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) { bmh_set_error("%s: record %u is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL; }
+	std::vector<uint32_t> tpl; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> L; uint64_t info[2] = {0, 0};
+	const bdp_groups_t G = T.view();
+	if ((rc = bdp_entries_host(recs, off.data(), n, tpl, E, info, fn, groups ? &G : nullptr, &L)) != BMH_OK) return rc;
+	uint8_t *o = (uint8_t *)malloc(sizeof(bdp_loc_t) * L.size() + 1);
+	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+	if (!L.empty()) memcpy(o, L.data(), sizeof(bdp_loc_t) * L.size());
+	*locs = o; *n_templates = L.size();
+	return BMH_OK;
+}
+
+extern "C" int bmh_bam_name_location(const char *name, uint32_t len, uint32_t out[3])
+{
+	if (!out || (len && !name)) { bmh_set_error("bmh_bam_name_location: null argument"); return BMH_EINVAL; }
+	out[0] = out[1] = out[2] = 0;
+	return bdp_name_location((const uint8_t *)name, len, out) ? 1 : 0;
+}
+
+extern "C" int bmh_library_size(uint64_t n_pairs, uint64_t n_unique, int64_t *size)
+{
+	bool has = false;
+	const int64_t v = bdp_library_size(n_pairs, n_unique, &has);
+	if (size) *size = v;
+	return has ? 1 : 0;
 }
 #endif

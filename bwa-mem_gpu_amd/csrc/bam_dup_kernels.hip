@@ -13,6 +13,11 @@
 //               the end word); run heads, a max-scan of the heads' indices, and a lane decides from the first item of its run -- a run may span workgroups.
 //               Output: a bitmap over global template ordinals and five counters.  Libraries need no pass of their own: their keys differ.  With read groups
 //               one more kernel counts the five per library from the entries' library bytes and the bitmap (a histogram in LDS per workgroup)
+//   optical     only with an optical distance (csrc/bam_dup_core.h): per batch the entries kernel's LOC instance also parses the template's read name into a 16-byte
+//               location; at the decision, between the pair pass and the fragment pass and in their arrays: set heads and their scan, the sets' starts (so a
+//               lane knows its set's size), the located pairs of the sets of 2 .. max_set compacted through a scan, two stable radix passes (tile and x; then
+//               set head, read group and role), one lane per member walking its x window and uniting in a union-find in global memory (parent [v] <= v:
+//               every find descends; atomicMin halves paths, atomicCAS hooks the larger root under the smaller), members and roots counted per library in LDS
 //   per window  one lane per record tests the bitmap through the record's global template ordinal and ORs 0x04 into byte 19 (a byte store: records are unaligned)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,7 +31,7 @@
 #include "bam_ws.h"
 
 struct bdp_dev_t {
-	dev_buf<uint8_t> head, tpl, start, entries, info, tmp, lib3;                  // per batch
+	dev_buf<uint8_t> head, tpl, start, entries, info, tmp, lib3, locs;            // per batch (locs: only when optical duplicates are counted)
 	dev_buf<uint8_t> bits, tord;                                                  // the bitmap of the run, a window's ordinals
 	dev_buf<uint8_t> g_ids, g_off, g_lib; uint32_t g_n = 0;                       // the run's read groups (bdp_dev_set_groups): IDs, their offsets, libraries; 0: none
 	uint64_t n_tpl = 0;                                                     // templates the bitmap covers
@@ -63,17 +68,25 @@ __global__ void __launch_bounds__(256) bdp_starts(const uint32_t *__restrict__ h
 }
 
 // LIB: the run has read groups (G) -- info [4], [5]: the first template without an RG:Z tag / with an unknown ID, as info [1]
-template <bool LIB>
+// LOC: optical duplicates are counted -- the lane holds the template's first record and parses its name: locs [t]
+template <bool LIB, bool LOC>
 __global__ void __launch_bounds__(256) bdp_entries(const uint8_t *__restrict__ recs, const uint64_t *__restrict__ off, uint32_t n, uint64_t total, const uint32_t *__restrict__ start,
-                                                   bdp_entry_t *__restrict__ entries, uint32_t *info, bdp_groups_t G)
+                                                   bdp_entry_t *__restrict__ entries, uint32_t *info, bdp_groups_t G, bdp_loc_t *__restrict__ locs)
 {
 	const uint32_t t = blockIdx.x * 256 + threadIdx.x;
 	if (t >= n || t >= info[0] || info[1] == 0) return;
 	const uint32_t a = start[t], b = start[t + 1];
 	bdp_entry_t e; e.lo = e.hi = ~0ull; e.score = 0; e.kind_n = 0;
+	uint32_t role = 0, row = 0;
 	int st = a < b && b <= n && off[b] <= total ? BDP_E_OK : BDP_E_TEMPLATE;      // (offsets ascend: every record of the template lies inside the buffer)
-	if (st == BDP_E_OK) st = LIB ? bdp_entry_lib(recs, off, a, b, G, &e) : bdp_entry(recs, off, a, b, &e) ? BDP_E_OK : BDP_E_TEMPLATE;
+	const bool inside = st == BDP_E_OK;
+	if (st == BDP_E_OK) st = LIB ? bdp_entry_lib(recs, off, a, b, G, &e, LOC ? &role : nullptr, LOC ? &row : nullptr) : bdp_entry(recs, off, a, b, &e, LOC ? &role : nullptr) ? BDP_E_OK : BDP_E_TEMPLATE;
 	entries[t] = e;
+	if (LOC) {
+		bdp_loc_t l; l.x = l.y = 0; l.tile = 0; l.rg = 0; l.flags = 0;
+		if (inside && st == BDP_E_OK) l = bdp_location(recs + off[a], role, row);
+		locs[t] = l;
+	}
 	if (st == BDP_E_TEMPLATE) atomicMin(info + 1, a + 1);
 	else if (LIB && st != BDP_E_OK) atomicMin(info + (st == BDP_E_NO_RG ? 4 : 5), a + 1);
 }
@@ -228,6 +241,122 @@ __global__ void __launch_bounds__(256) bdp_lib_counts(const bdp_entry_t *__restr
 	for (uint32_t k = threadIdx.x; k < 5 * n_lib; k += 256) if (lib_s[k]) atomicAdd(out + BDP_N_COUNTS * (k / 5) + k % 5, lib_s[k]);
 }
 
+// ---- the optical step (csrc/bam_dup_core.h): after the pair pass perm [n] holds the templates with the pairs first, the pairs of one key (a set) next to each other
+
+BSR_FN bool bdp_same_set(const bdp_entry_t &a, const bdp_entry_t &b) { return a.lo == b.lo && a.hi == b.hi; }
+
+// head [i] = 1 where a set begins
+__global__ void __launch_bounds__(256) bdp_opt_heads(const bdp_entry_t *__restrict__ E, const uint32_t *__restrict__ perm, uint64_t n, uint32_t *__restrict__ head)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const bdp_entry_t e = E[perm[i]];
+	bool h = bdp_kind(e) == BDP_PAIR;
+	if (h && i) { const bdp_entry_t p = E[perm[i - 1]]; h = !(bdp_kind(p) == BDP_PAIR && bdp_same_set(p, e)); }
+	head[i] = h ? 1u : 0u;
+}
+
+// sid: the inclusive scan of head (a pair's set is sid - 1); start [s] = where set s begins, and behind the last set where the pairs end: start has n + 1 places
+__global__ void __launch_bounds__(256) bdp_opt_starts(const bdp_entry_t *__restrict__ E, const uint32_t *__restrict__ perm, uint64_t n, const uint32_t *__restrict__ sid, uint32_t *__restrict__ start)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n || bdp_kind(E[perm[i]]) != BDP_PAIR) return;
+	const uint32_t s = sid[i];                                            // (1 .. n: a pair follows at least its own set's head)
+	if (s == 0 || s > n) return;
+	if (s != (i ? sid[i - 1] : 0u)) start[s - 1] = (uint32_t)i;
+	if (i + 1 == n || bdp_kind(E[perm[i + 1]]) != BDP_PAIR) start[s] = (uint32_t)(i + 1);
+}
+
+// member [i] = 1 for a located pair in a set of 2 .. max_set pairs; oc [4 * lib]: += located pairs, sets skipped for their size (counted at their heads) -- through a
+// histogram in LDS (2 * n_lib 32-bit words; n_lib 0: one library, the entries carry none)
+__global__ void __launch_bounds__(256) bdp_opt_members(const bdp_entry_t *__restrict__ E, const bdp_loc_t *__restrict__ L, const uint32_t *__restrict__ perm, uint64_t n, const uint32_t *__restrict__ sid,
+                                                       const uint32_t *__restrict__ start, uint32_t max_set, uint32_t n_lib, uint32_t *__restrict__ member, unsigned long long *oc)
+{
+	extern __shared__ uint32_t opt_s[];
+	const uint32_t nl = n_lib ? n_lib : 1u;
+	for (uint32_t k = threadIdx.x; k < 2 * nl; k += 256) opt_s[k] = 0;
+	__syncthreads();
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i < n) {
+		const uint32_t t = perm[i];
+		const bdp_entry_t e = E[t];
+		uint32_t m = 0;
+		const uint32_t s = sid[i];
+		if (bdp_kind(e) == BDP_PAIR && s >= 1 && s <= n) {
+			const uint32_t lib = n_lib ? bdp_lib_of(e) : 0u;
+			const uint32_t a = start[s - 1], b = start[s], len = b - a;
+			const bool located = (L[t].flags & BDP_LOC_LOCATED) != 0;
+			if (lib < nl) {
+				if (located) atomicAdd(opt_s + 2 * lib, 1u);
+				if (a == i && len > max_set) atomicAdd(opt_s + 2 * lib + 1, 1u);
+			}
+			m = located && len >= 2 && len <= max_set ? 1u : 0u;
+		}
+		member[i] = m;
+	}
+	__syncthreads();
+	for (uint32_t k = threadIdx.x; k < 2 * nl; k += 256) if (opt_s[k]) atomicAdd(oc + 4 * (k / 2) + k % 2, (unsigned long long)opt_s[k]);
+}
+
+// the members, compacted: place p = mpos [i] - 1 (mpos: the inclusive scan of member) takes the template, the head of its set and the first sort word; m: the members
+__global__ void __launch_bounds__(256) bdp_opt_compact(const bdp_loc_t *__restrict__ L, const uint32_t *__restrict__ perm, uint64_t n, const uint32_t *__restrict__ sid, const uint32_t *__restrict__ start,
+                                                       const uint32_t *__restrict__ mpos, uint32_t m, uint32_t *__restrict__ otpl, uint32_t *__restrict__ oset, uint64_t *__restrict__ key, uint32_t *__restrict__ val)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t q = mpos[i];
+	if (q == (i ? mpos[i - 1] : 0u) || q == 0 || q > m) return;           // (no member; or a place outside the arrays: never, and never written)
+	const uint32_t p = q - 1, t = perm[i], s = sid[i];
+	otpl[p] = t; oset[p] = s >= 1 && s <= n ? start[s - 1] : 0u; key[p] = bdp_opt_word1(L[t]); val[p] = p;
+}
+
+// the second sort word through the order of the first pass (val: places of bdp_opt_compact)
+__global__ void __launch_bounds__(256) bdp_opt_keys2(const bdp_loc_t *__restrict__ L, const uint32_t *__restrict__ otpl, const uint32_t *__restrict__ oset, const uint32_t *__restrict__ val, uint32_t m,
+                                                     uint64_t *__restrict__ key)
+{
+	const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+	if (j >= m) return;
+	const uint32_t p = val[j];
+	key[j] = p < m ? bdp_opt_word2(oset[p], L[otpl[p]]) : ~0ull;
+}
+
+// the members in their final order: tile, x, y beside the sorted second words, every member its own root
+__global__ void __launch_bounds__(256) bdp_opt_gather(const bdp_loc_t *__restrict__ L, const uint32_t *__restrict__ otpl, const uint32_t *__restrict__ val, uint32_t m, uint32_t *__restrict__ tile,
+                                                      int32_t *__restrict__ x, int32_t *__restrict__ y, uint32_t *__restrict__ parent)
+{
+	const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+	if (j >= m) return;
+	const uint32_t p = val[j];
+	bdp_loc_t l; l.x = l.y = 0; l.tile = 0; l.rg = 0; l.flags = 0;
+	if (p < m) l = L[otpl[p]];
+	tile[j] = l.tile; x[j] = l.x; y[j] = l.y; parent[j] = j;
+}
+
+// one lane per member: bdp_opt_walk -- bounded by m, its finds by parent [v] <= v (csrc/bam_dup_core.h)
+__global__ void __launch_bounds__(256) bdp_opt_cluster(const uint64_t *__restrict__ word2, const uint32_t *__restrict__ tile, const int32_t *__restrict__ x, const int32_t *__restrict__ y, uint32_t m,
+                                                       int64_t D, uint32_t *parent)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i < m) bdp_opt_walk(i, m, word2, tile, x, y, D, parent);
+}
+
+// oc [4 * lib + 2], [+ 3]: += the members and those that are their own root (their difference: the optical duplicates), as bdp_opt_members counts
+__global__ void __launch_bounds__(256) bdp_opt_counts(const bdp_entry_t *__restrict__ E, const uint32_t *__restrict__ otpl, const uint32_t *__restrict__ val, const uint32_t *__restrict__ parent, uint32_t m,
+                                                      uint32_t n_lib, unsigned long long *oc)
+{
+	extern __shared__ uint32_t opt_s[];
+	const uint32_t nl = n_lib ? n_lib : 1u;
+	for (uint32_t k = threadIdx.x; k < 2 * nl; k += 256) opt_s[k] = 0;
+	__syncthreads();
+	const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+	if (j < m && val[j] < m) {
+		const uint32_t lib = n_lib ? bdp_lib_of(E[otpl[val[j]]]) : 0u;
+		if (lib < nl) { atomicAdd(opt_s + 2 * lib, 1u); if (parent[j] == j) atomicAdd(opt_s + 2 * lib + 1, 1u); }
+	}
+	__syncthreads();
+	for (uint32_t k = threadIdx.x; k < 2 * nl; k += 256) if (opt_s[k]) atomicAdd(oc + 4 * (k / 2) + 2 + k % 2, (unsigned long long)opt_s[k]);
+}
+
 // ---- the flags of a window
 __global__ void __launch_bounds__(256) bdp_flag(uint8_t *__restrict__ recs, const uint64_t *__restrict__ off, const uint32_t *__restrict__ tord, uint32_t n, uint64_t total,
                                                 const uint32_t *__restrict__ bits, uint64_t n_tpl)
@@ -247,12 +376,14 @@ unsigned blocks(uint64_t n) { return (unsigned)((n + 255) / 256); }
 bdp_dev_t *bdp_dev_create(void) { return new bdp_dev_t(); }
 void bdp_dev_free(bdp_dev_t *d) { delete d; }
 
-int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint32_t **d_tpl, const bdp_entry_t **d_entries, const uint32_t **d_info)
+int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint32_t **d_tpl, const bdp_entry_t **d_entries, const uint32_t **d_info,
+                     const bdp_loc_t **d_locs)
 {
 	hipStream_t st = (hipStream_t)stream;
 	size_t tb = scan_tmp_bytes<uint32_t, uint32_t, true>((size_t)n + 1);
 	RCK(d->head.need(4 * ((size_t)n + 1))); RCK(d->tpl.need(4 * ((size_t)n + 1))); RCK(d->start.need(4 * ((size_t)n + 2))); RCK(d->entries.need(sizeof(bdp_entry_t) * ((size_t)n + 1)));
 	RCK(d->info.need(4 * BDP_INFO_WORDS)); RCK(d->tmp.need(tb));
+	if (d_locs) RCK(d->locs.need(sizeof(bdp_loc_t) * ((size_t)n + 1)));
 	static const uint32_t init[BDP_INFO_WORDS] = {0u, 0xffffffffu, 0u, 0u, 0xffffffffu, 0xffffffffu, 0u, 0u};
 	HIPCK(hipMemcpyAsync(d->info.p, init, 4 * BDP_INFO_WORDS, hipMemcpyHostToDevice, st));
 	if (n) {
@@ -260,10 +391,15 @@ int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off,
 		HIPCK(rocprim::inclusive_scan(d->tmp.p, tb, (uint32_t *)d->head.p, (uint32_t *)d->tpl.p, (size_t)n, rocprim::plus<uint32_t>(), st));
 		bdp_starts<<<blocks(n), 256, 0, st>>>((const uint32_t *)d->head.p, (uint32_t *)d->tpl.p, n, (uint32_t *)d->start.p, (uint32_t *)d->info.p);
 		const bdp_groups_t G = {(const char *)d->g_ids.p, (const uint32_t *)d->g_off.p, (const uint8_t *)d->g_lib.p, d->g_n};
-		if (d->g_n) bdp_entries<true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, (const uint32_t *)d->start.p, (bdp_entry_t *)d->entries.p, (uint32_t *)d->info.p, G);
-		else bdp_entries<false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, (const uint32_t *)d->start.p, (bdp_entry_t *)d->entries.p, (uint32_t *)d->info.p, G);
+		const uint32_t *sp = (const uint32_t *)d->start.p; bdp_entry_t *ep = (bdp_entry_t *)d->entries.p; uint32_t *ip = (uint32_t *)d->info.p; bdp_loc_t *lp = (bdp_loc_t *)d->locs.p;
+		if (d_locs) {
+			if (d->g_n) bdp_entries<true, true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp);
+			else bdp_entries<false, true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp);
+		} else if (d->g_n) bdp_entries<true, false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr);
+		else bdp_entries<false, false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr);
 		HIPCK(hipGetLastError());
 	}
+	if (d_locs) *d_locs = (const bdp_loc_t *)d->locs.p;
 	*d_tpl = (const uint32_t *)d->tpl.p; *d_entries = (const bdp_entry_t *)d->entries.p; *d_info = (const uint32_t *)d->info.p;
 	return BMH_OK;
 }
@@ -297,10 +433,14 @@ int bdp_dev_set_groups(bdp_dev_t *d, const bdp_table_t *T, void *stream)
 	return BMH_OK;
 }
 
-int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records, uint32_t n_lib, uint64_t *lib_counts)
+int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records, uint32_t n_lib, uint64_t *lib_counts,
+                      const bdp_optical_t *O, const bdp_loc_t *locs, double *opt_ms)
 {
 	hipStream_t st = (hipStream_t)stream;
 	for (int k = 0; k < 5; ++k) counts[k] = 0;
+	const uint32_t o_lib = O && O->lib_out ? n_lib : 0;                    // (the optical counts per library do not hang on lib_counts)
+	if (O) { for (int k = 0; k < BDP_OPT_N; ++k) O->out[k] = 0; for (uint32_t k = 0; k < BDP_OPT_N * o_lib; ++k) O->lib_out[k] = 0; }
+	if (O && T && !locs) { bmh_set_error("duplicate marking: internal error: optical duplicates without the templates' locations"); return BMH_EINVAL; }
 	if (!lib_counts) n_lib = 0;
 	for (uint32_t k = 0; k < BDP_N_COUNTS * n_lib; ++k) lib_counts[k] = 0;
 	if (n_lib > BDP_MAX_LIBS) { bmh_set_error("duplicate marking: %u libraries: a run holds at most %d", n_lib, (int)BDP_MAX_LIBS); return BMH_EINVAL; }
@@ -315,7 +455,9 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 	size_t fr = 0, tot = 0;
 	HIPCK(hipMemGetInfo(&fr, &tot));
 	// (a buffer is allocated a quarter larger than asked: that is what is counted)
-	const size_t ask = sizeof(bdp_entry_t) * (size_t)T + 2 * 8 * M + 2 * 4 * M + 2 * 4 * ((size_t)T + 1) + cb, want = ask + ask / 4 + (64u << 20);
+	// optical duplicates: 16 bytes per template more -- the locations; the step's members, sort words and union-find live in the pair pass's key and value arrays
+	const size_t opt_ask = O ? sizeof(bdp_loc_t) * (size_t)T + 8 * 4 * (size_t)(o_lib ? o_lib : 1) : 0;
+	const size_t ask = sizeof(bdp_entry_t) * (size_t)T + 2 * 8 * M + 2 * 4 * M + 2 * 4 * ((size_t)T + 1) + cb + opt_ask, want = ask + ask / 4 + (64u << 20);
 	// the final sort that follows: keys and ordinals in and out, 24 bytes per record, a quarter more as allocated, and its work space
 	const size_t sort_ask = 24 * (size_t)n_records + (n_records ? sort_pairs_tmp_bytes<uint64_t, uint32_t>((size_t)n_records) : 0), sort_want = sort_ask + sort_ask / 4 + (64u << 20);
 	if (want <= fr && sort_want > fr) {
@@ -324,7 +466,9 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 		return BMH_ENOMEM;
 	}
 	if (want > fr) {
-		bmh_set_error("sorted BAM: marking the duplicates among %llu templates needs %zu bytes of device memory, %zu are free (align fewer reads per run, or on a device with more memory)",
+		if (O) bmh_set_error("sorted BAM: marking the duplicates among %llu templates and counting the optical ones needs %zu bytes of device memory (%zu of them the templates' locations and the optical step's counters), %zu are free (align fewer reads per run, or on a device with more memory)",
+		                     (unsigned long long)T, want, opt_ask + opt_ask / 4, fr);
+		else bmh_set_error("sorted BAM: marking the duplicates among %llu templates needs %zu bytes of device memory, %zu are free (align fewer reads per run, or on a device with more memory)",
 		              (unsigned long long)T, want, fr);
 		return BMH_ENOMEM;
 	}
@@ -346,6 +490,48 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 		std::swap(va, vb);
 	}
 	bdp_pair_decide<<<blocks(T), 256, 0, st>>>(dE, va, T, (uint32_t *)d->bits.p, dcnt);
+	// the optical step, on va as the pair pass left it.  Until the compaction it keeps its words in cnt, base and vb; from there on the pair pass's arrays are free
+	// and take the members (m <= T of them): ka -- sort words in, values in and out; kb -- sort words out, templates, set heads; va -- x, y; vb -- tile, parent
+	dev_buf<uint8_t> dL, oc; std::vector<unsigned long long> h_oc;
+	struct ev_pair_t { hipEvent_t e[2] = {nullptr, nullptr}; ~ev_pair_t() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } oev;
+	if (O) {
+		const uint32_t nl = o_lib ? o_lib : 1u;
+		HIPCK(hipEventCreate(&oev.e[0])); HIPCK(hipEventCreate(&oev.e[1]));
+		HIPCK(hipEventRecord(oev.e[0], st));
+		RCK(dL.need(sizeof(bdp_loc_t) * (size_t)T)); RCK(oc.need(8 * 4 * (size_t)nl));
+		HIPCK(hipMemcpyAsync(dL.p, locs, sizeof(bdp_loc_t) * (size_t)T, hipMemcpyHostToDevice, st));
+		HIPCK(hipMemsetAsync(oc.p, 0, 8 * 4 * (size_t)nl, st));
+		const bdp_loc_t *L = (const bdp_loc_t *)dL.p;
+		uint32_t *head = (uint32_t *)cnt.p, *sid = (uint32_t *)base.p, *start = vb;      // (start: T + 1 of vb's 2 T places)
+		size_t ib = scan_tmp_bytes<uint32_t, uint32_t, true>((size_t)T + 1);
+		if (ib > cb) { bmh_set_error("duplicate marking: internal error: the optical step's scan asks for %zu bytes of work space, %zu are there", ib, cb); return BMH_EINVAL; }
+		bdp_opt_heads<<<blocks(T), 256, 0, st>>>(dE, va, T, head);
+		HIPCK(rocprim::inclusive_scan(tmp.p, ib, head, sid, (size_t)T, rocprim::plus<uint32_t>(), st));
+		bdp_opt_starts<<<blocks(T), 256, 0, st>>>(dE, va, T, sid, start);
+		bdp_opt_members<<<blocks(T), 256, 4 * 2 * nl, st>>>(dE, L, va, T, sid, start, O->max_set, o_lib, head, (unsigned long long *)oc.p);
+		HIPCK(rocprim::inclusive_scan(tmp.p, ib, head, head, (size_t)T, rocprim::plus<uint32_t>(), st));      // (in place: member flags -> places + 1)
+		uint32_t m = 0;
+		HIPCK(hipMemcpyAsync(&m, head + (T - 1), 4, hipMemcpyDeviceToHost, st));
+		HIPCK(hipStreamSynchronize(st));
+		if (m > T) { bmh_set_error("duplicate marking: internal error: %u optical members among %llu templates", m, (unsigned long long)T); return BMH_EINVAL; }
+		if (m) {
+			uint64_t *keyA = ka, *keyB = kb;
+			uint32_t *valA = (uint32_t *)(ka + m), *valB = valA + m, *otpl = (uint32_t *)(kb + m), *oset = otpl + m;      // (16 m <= 16 T bytes of each array)
+			bdp_opt_compact<<<blocks(T), 256, 0, st>>>(L, va, T, sid, start, head, m, otpl, oset, keyA, valA);
+			HIPCK(rocprim::radix_sort_pairs(tmp.p, sb, keyA, keyB, valA, valB, (size_t)m, 0, 64, st));
+			bdp_opt_keys2<<<blocks(m), 256, 0, st>>>(L, otpl, oset, valB, m, keyA);
+			HIPCK(rocprim::radix_sort_pairs(tmp.p, sb, keyA, keyB, valB, valA, (size_t)m, 0, 64, st));
+			// keyB: the sorted second words, valA: the members' places in that order; the pair pass's permutation has been read: va and vb take the rest
+			uint32_t *gtile = vb, *parent = vb + m; int32_t *gx = (int32_t *)va, *gy = gx + m;
+			bdp_opt_gather<<<blocks(m), 256, 0, st>>>(L, otpl, valA, m, gtile, gx, gy, parent);
+			bdp_opt_cluster<<<blocks(m), 256, 0, st>>>(keyB, gtile, gx, gy, m, O->distance, parent);
+			bdp_opt_counts<<<blocks(m), 256, 4 * 2 * nl, st>>>(dE, otpl, valA, parent, m, o_lib, (unsigned long long *)oc.p);
+		}
+		h_oc.assign(4 * (size_t)nl, 0);
+		HIPCK(hipMemcpyAsync(h_oc.data(), oc.p, 8 * 4 * (size_t)nl, hipMemcpyDeviceToHost, st));
+		HIPCK(hipEventRecord(oev.e[1], st));
+		HIPCK(hipGetLastError());
+	}
 	// the fragment pass
 	size_t eb = scan_tmp_bytes<uint32_t, uint32_t>((size_t)T + 1);
 	HIPCK(hipMemsetAsync((uint32_t *)cnt.p + T, 0, 4, st));
@@ -382,6 +568,15 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 	HIPCK(hipStreamSynchronize(st));
 	HIPCK(hipGetLastError());
 	for (int k = 0; k < 5; ++k) counts[k] = h[k];
+	if (O) {
+		for (size_t l = 0; l < h_oc.size() / 4; ++l) {
+			const uint64_t v[BDP_OPT_N] = {h_oc[4 * l + 2] - h_oc[4 * l + 3], h_oc[4 * l], h_oc[4 * l + 1]};
+			for (int k = 0; k < BDP_OPT_N; ++k) { O->out[k] += v[k]; if (o_lib) O->lib_out[BDP_OPT_N * l + k] = v[k]; }
+		}
+		float ms = 0;
+		HIPCK(hipEventElapsedTime(&ms, oev.e[0], oev.e[1]));
+		if (opt_ms) *opt_ms += ms;
+	}
 	return BMH_OK;
 }
 
@@ -398,7 +593,9 @@ int bdp_flag_device(bdp_dev_t *d, uint8_t *d_recs, const uint64_t *d_off, const 
 
 // ---------------------------------------------------------------------------------------------------------------- the stand-alone entry point
 
-static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_table_t *G, void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts)
+// O (or NULL): count the optical duplicates too; locs_only: stop at the templates' locations -- *out takes them, counts [BDP_TEMPLATES] their number
+static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_table_t *G, void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts,
+                          const bdp_optical_t *O = nullptr, bool locs_only = false)
 {
 	hipStream_t st = (hipStream_t)stream;
 	if (!out || !counts || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
@@ -416,19 +613,28 @@ static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes,
 	RCK(in.need((size_t)n_bytes + 16)); RCK(in_off.need(8 * off.size()));
 	if (n_bytes) HIPCK(hipMemcpyAsync(in.p, recs, (size_t)n_bytes, hipMemcpyHostToDevice, st));
 	HIPCK(hipMemcpyAsync(in_off.p, off.data(), 8 * off.size(), hipMemcpyHostToDevice, st));
-	const uint32_t *d_tpl; const bdp_entry_t *d_e; const uint32_t *d_info;
-	RCK(bdp_batch_device(&d, (const uint8_t *)in.p, (const uint64_t *)in_off.p, n, n_bytes, st, &d_tpl, &d_e, &d_info));
+	const uint32_t *d_tpl; const bdp_entry_t *d_e; const uint32_t *d_info; const bdp_loc_t *d_l = nullptr;
+	const bool want_locs = O || locs_only;
+	RCK(bdp_batch_device(&d, (const uint8_t *)in.p, (const uint64_t *)in_off.p, n, n_bytes, st, &d_tpl, &d_e, &d_info, want_locs ? &d_l : nullptr));
 	uint32_t info[BDP_INFO_WORDS];
 	HIPCK(hipMemcpyAsync(info, d_info, 4 * BDP_INFO_WORDS, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
 	RCK(bdp_batch_check(n, info, G != nullptr, fn));
 	const uint32_t T = n ? info[0] : 0;
 	if (T > n) { bmh_set_error("%s: internal error: %u templates among %u records", fn, T, n); return BMH_EINVAL; }
-	std::vector<bdp_entry_t> E(T); std::vector<uint32_t> tpl(n);
+	std::vector<bdp_entry_t> E(T); std::vector<uint32_t> tpl(n); std::vector<bdp_loc_t> L(want_locs ? T : 0);
 	if (T) HIPCK(hipMemcpyAsync(E.data(), d_e, sizeof(bdp_entry_t) * (size_t)T, hipMemcpyDeviceToHost, st));
 	if (n) HIPCK(hipMemcpyAsync(tpl.data(), d_tpl, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+	if (T && want_locs) HIPCK(hipMemcpyAsync(L.data(), d_l, sizeof(bdp_loc_t) * (size_t)T, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
-	RCK(bdp_decide_device(&d, E.data(), T, st, counts, 0, G ? G->n_lib : 0, G ? lib_counts : nullptr));
+	if (locs_only) {
+		uint8_t *o = (uint8_t *)malloc(sizeof(bdp_loc_t) * (size_t)T + 1);
+		if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+		if (T) memcpy(o, L.data(), sizeof(bdp_loc_t) * (size_t)T);
+		*out = o; counts[BDP_TEMPLATES] = T;
+		return BMH_OK;
+	}
+	RCK(bdp_decide_device(&d, E.data(), T, st, counts, 0, G ? G->n_lib : 0, G ? lib_counts : nullptr, O, O ? L.data() : nullptr));
 	counts[BDP_SECSUP] = info[2]; counts[BDP_UNMAPPED] = info[3]; counts[BDP_TEMPLATES] = T;
 	if (G && lib_counts) bdp_lib_tally_host(recs, off.data(), n, tpl.data(), E.data(), T, G->n_lib, lib_counts);
 	RCK(bdp_flag_device(&d, (uint8_t *)in.p, (const uint64_t *)in_off.p, tpl.data(), n, n_bytes, st));
@@ -453,4 +659,35 @@ extern "C" int bmh_bam_markdup_groups_device(const uint8_t *recs, uint64_t n_byt
 	if (out) *out = nullptr;
 	RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
 	return markdup_device(fn, recs, n_bytes, &G, stream, out, counts, lib_counts);
+}
+
+extern "C" int bmh_bam_markdup_optical_device(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, void *stream,
+                                              uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical)
+{
+	const char *fn = "bmh_bam_markdup_optical_device";
+	bdp_table_t G;
+	if (out) *out = nullptr;
+	if (!optical) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	RCK(bdp_optical_check(distance, max_set, fn));
+	const bool groups = rg_ids || rg_lib || n_groups;
+	if (groups) RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
+	if (groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
+	const bdp_optical_t O = {distance, max_set ? (uint32_t)max_set : (uint32_t)BDP_OPT_MAX_SET, optical, groups ? lib_optical : nullptr};
+	return markdup_device(fn, recs, n_bytes, groups ? &G : nullptr, stream, out, counts, groups ? lib_counts : nullptr, &O);
+}
+
+extern "C" int bmh_bam_dup_locations_device(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, void *stream, uint8_t **locs, uint64_t *n_templates)
+{
+	const char *fn = "bmh_bam_dup_locations_device";
+	bdp_table_t G;
+	if (locs) *locs = nullptr;
+	if (!n_templates) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	*n_templates = 0;
+	const bool groups = rg_ids || rg_lib || n_groups;
+	if (groups) RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
+	if (groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
+	uint64_t counts[BDP_N_COUNTS];
+	RCK(markdup_device(fn, recs, n_bytes, groups ? &G : nullptr, stream, locs, counts, nullptr, nullptr, true));
+	*n_templates = counts[BDP_TEMPLATES];
+	return BMH_OK;
 }

@@ -201,7 +201,7 @@ void bsr_store_t::clear()
 {
 	for (bsr_run_t &r : runs) free(r.mem);
 	runs.clear(); used = 0; spilled = 0; file_bytes = 0;
-	entries.clear(); dup_info[0] = dup_info[1] = 0; lib_info.clear();
+	entries.clear(); locs.clear(); dup_info[0] = dup_info[1] = 0; lib_info.clear();
 	if (fd >= 0) close(fd);
 	fd = -1;
 }
@@ -238,6 +238,7 @@ int bsr_store_t::append(const uint8_t *recs, uint64_t bytes, const uint64_t *key
 		}
 		r.file_at = (int64_t)file_bytes; file_bytes += bytes; ++spilled;
 	}
+	if (dup && dup->locs) locs.insert(locs.end(), dup->locs, dup->locs + dup->n_tpl);
 	if (dup) { entries.insert(entries.end(), dup->entries, dup->entries + dup->n_tpl); dup_info[0] += dup->secsup; dup_info[1] += dup->unmapped; }
 	if (dup && dup->lib >= 0) {
 		if (lib_info.size() < 3 * ((size_t)dup->lib + 1)) lib_info.resize(3 * ((size_t)dup->lib + 1), 0);

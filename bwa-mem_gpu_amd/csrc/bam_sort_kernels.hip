@@ -304,7 +304,7 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 
 // every run of the store -> the sorted file's record members (to the sink) and its index
 int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, uint64_t *dup_counts, double *dup_ms,
-                     uint32_t n_lib, uint64_t *lib_counts)
+                     uint32_t n_lib, uint64_t *lib_counts, const bdp_optical_t *optical, double *opt_ms)
 {
 	uint64_t n = 0, bytes = 0;
 	std::vector<uint64_t> first;
@@ -312,13 +312,14 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint3
 	RCK(bsr_index_begin(d, ix, stream));
 	// duplicate marking: the decision over every template's entry comes first (its work space is freed before the final sort takes its own); the bitmap stays
 	struct dup_own_t { bdp_dev_t *p = nullptr; ~dup_own_t() { if (p) bdp_dev_free(p); } } dup;
-	std::vector<uint32_t> tord; double decide_ms = 0, flag_ms = 0;
+	std::vector<uint32_t> tord; double decide_ms = 0, flag_ms = 0, o_ms = 0;
 	if (dup_counts) {
 		for (int k = 0; k < BDP_N_COUNTS; ++k) dup_counts[k] = 0;
 		for (const bsr_run_t &r : S.runs) if (r.tpl.size() != r.n) { bmh_set_error("sorted BAM: internal error: a run without its records' template ordinals"); return BMH_EINVAL; }
 		if (!(dup.p = bdp_dev_create())) return BMH_ENOMEM;
 		const double t0 = bsr_now_ms();
-		RCK(bdp_decide_device(dup.p, S.entries.data(), S.entries.size(), stream, dup_counts, n, n_lib, lib_counts));
+		if (optical && S.locs.size() != S.entries.size()) { bmh_set_error("sorted BAM: internal error: %zu locations for %zu templates", S.locs.size(), S.entries.size()); return BMH_EINVAL; }
+		RCK(bdp_decide_device(dup.p, S.entries.data(), S.entries.size(), stream, dup_counts, n, n_lib, lib_counts, optical, optical ? S.locs.data() : nullptr, &o_ms));
 		dup_counts[BDP_SECSUP] = S.dup_info[0]; dup_counts[BDP_UNMAPPED] = S.dup_info[1]; dup_counts[BDP_TEMPLATES] = S.entries.size();
 		decide_ms = bsr_now_ms() - t0;
 	}
@@ -361,6 +362,10 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint3
 		if (getenv("BMH_ALIGNER_TRACE"))
 			fprintf(stderr, "[aligner] duplicate marking: %zu templates (%zu bytes of entries, %llu of ordinals kept) decided in %.1f ms, the windows' flags set in %.1f ms\n", S.entries.size(),
 			        sizeof(bdp_entry_t) * S.entries.size(), 4ull * (unsigned long long)n, decide_ms, flag_ms);
+		if (opt_ms) *opt_ms += o_ms;
+		if (optical && getenv("BMH_ALIGNER_TRACE"))
+			fprintf(stderr, "[aligner] optical duplicates: %zu bytes of locations, %llu optical pairs among %llu located ones (%llu sets skipped) counted in %.1f of the decision's ms\n",
+			        sizeof(bdp_loc_t) * S.locs.size(), (unsigned long long)optical->out[BDP_OPT_DUPS], (unsigned long long)optical->out[BDP_OPT_LOCATED], (unsigned long long)optical->out[BDP_OPT_SKIPPED], o_ms);
 	}
 	return bsr_index_finish(d, ix, stream);
 }

@@ -919,7 +919,7 @@ int bmh_bam_sorted_file_ex_host(const char *header_text, int n_contigs, const ch
 /* ---- Duplicate marking in sorted BAM (csrc/bam_dup_core.h, csrc/bam_dup_kernels.hip, csrc/bam_dup_host.cpp).
  * Picard MarkDuplicates' rules on templates (a single read or a read pair, its records next to each other in the writer's order): the unclipped 5' ends and
  * strands of the primary lines are the key, the sum of the base qualities >= 15 the score, ties go to the template that came first in the input; a fragment is
- * a duplicate wherever a pair has an end.  Every record of a duplicate template gets flag 0x400.  No optical duplicates, nothing removed.  One library unless
+ * a duplicate wherever a pair has an end.  Every record of a duplicate template gets flag 0x400.  Nothing is removed; optical duplicates are counted on request (below).  One library unless
  * read groups are given (the _groups entry points below).
  * counts [8]: pairs examined, fragments examined, duplicate pairs, duplicate fragments, records flagged, secondary or supplementary records, unmapped records,
  * templates.
@@ -971,6 +971,36 @@ int bmh_bam_sorted_file_markdup_groups_host(const char *header_text, int n_conti
                                             uint64_t n_bytes, int level, uint32_t window, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
                                             uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8], uint64_t *lib_counts);
 int bmh_aligner_markdup_library_counts(bmh_aligner_t *a, int lib, uint64_t out[8]);
+
+/* ---- Optical duplicates and the library-size estimate (csrc/bam_dup_core.h).  Counts only: the records, the flags, the file and its index are
+ * byte for byte those of the call without the option (Picard flags nothing more for an optical duplicate by default).
+ * A template's location is (tile, x, y): the last three of the 5 or 7 ':'-separated fields of its first record's read name, each the field's leading run of digits
+ * (a value below 2^31; what follows the digits is ignored); any other name has none.  Among the pairs of one duplicate key -- a set, the pair that stays included --
+ * two located pairs are neighbours when read group, role (which mate holds the smaller end), and tile are equal and x and y each differ by at most `distance`;
+ * the connected components are the clusters and a cluster of k pairs counts k - 1 optical duplicates.  Sets of one pair and sets of more than max_set pairs
+ * (0: 300 000) are not examined.  optical [3]: optical duplicate pairs, examined pairs with a location, sets skipped for their size; lib_optical (or NULL)
+ * [3 * n_lib]: the same per library.  distance: 0 .. 2^31 - 1.
+ * bmh_bam_markdup_optical_device / _host: bmh_bam_markdup_groups_* (rg_ids NULL, rg_lib NULL, n_groups 0: bmh_bam_markdup_*, no library) with the optical step; at
+ * most 65536 read groups.
+ * bmh_bam_dup_locations_device / _host: a record stream -> *locs: one 16-byte location per template {int32 x, y; uint32 tile; uint16 group row; uint16 flags --
+ * 1: located, 2: role} (malloc'd; bmh_free), *n_templates of them.
+ * bmh_bam_name_location: the parser on the host -> 1 and out = {tile, x, y}, or 0: no location.
+ * bmh_library_size: Picard's estimateLibrarySize of n_pairs pairs that are no optical duplicates, n_unique of them distinct -> 1 and *size, or 0: no estimate.
+ * bmh_aligner_set_markdup_optical: the marked runs that follow count optical duplicates within `distance` (-1: off, the default); refused unless marking is on,
+ * and switched off wherever marking is.  bmh_aligner_markdup_optical_counts: the three counts of the last such run, of library `lib` or (-1) in total.
+ * bmh_aligner_markdup_optical_ms: the milliseconds of the decision that the optical step took (the locations' upload included). */
+int bmh_bam_markdup_optical_device(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
+                                   void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical);
+int bmh_bam_markdup_optical_host(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
+                                 uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical);
+int bmh_bam_dup_locations_device(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, void *stream, uint8_t **locs,
+                                 uint64_t *n_templates);
+int bmh_bam_dup_locations_host(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, uint8_t **locs, uint64_t *n_templates);
+int bmh_bam_name_location(const char *name, uint32_t len, uint32_t out[3]);
+int bmh_library_size(uint64_t n_pairs, uint64_t n_unique, int64_t *size);
+int bmh_aligner_set_markdup_optical(bmh_aligner_t *a, int64_t distance);
+int bmh_aligner_markdup_optical_counts(bmh_aligner_t *a, int lib, uint64_t out[3]);
+int bmh_aligner_markdup_optical_ms(bmh_aligner_t *a, double *out);
 
 /* A run over several read groups: one sample's lanes and libraries into one output.  A group is a read group ID, its library index (as above) and an input as
  * bmh_aligner_run_files takes it (path2: the mates, or NULL; a BAM's own @RG lines and RG tags stay ignored: keeping the input's read groups, bmh_aligner_set_keep_rg, and a run over groups do not combine).  One loader thread walks the groups in order into the

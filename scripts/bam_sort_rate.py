@@ -5,12 +5,18 @@ the merge: key sort, windows, compression, index pass, sink) --, and bam_sort al
 --runs runs with their spreads.  Writes profiles/bam_sort.json (or --out).  The read set is the bench's two batches, each twice: every read occurs twice, so the
 sorted file's size (the two copies land next to each other) and the merge's compression rate are not those of real data.
 
-    python scripts/bam_sort_rate.py [--runs 3] [--reads 1000000] [--genome-mbp 3100] [--out FILE] [--markdup [--groups [--parent-json FILE]]]
+    python scripts/bam_sort_rate.py [--runs 3] [--reads 1000000] [--genome-mbp 3100] [--out FILE] [--markdup [--groups | --optical N] [--parent-json FILE]]
 
 --markdup: the duplicate-marking leg instead (profiles/bam_markdup.json): the sorted in-memory row re-run, the same row with duplicates marked -- with the
 decision alone and the windows' flag steps alone, as the library times them (bmh_aligner_markdup_times) --, the same two rows on a paired read set (FR pairs
 of the same genome, each batch twice), and bam_markdup alone on one batch's records (walk, copies, heads, entries, decision, flags).  Every read of the set occurs twice, so half its templates are duplicates: the
 duplicate rate says nothing about real data.
+
+--markdup --optical N: the optical-duplicate leg (profiles/bam_markdup_optical.json): --markdup's rows re-run as they are (the option off, the parent's reads),
+then the same reads under names with locations (FC:1:tile:x:y, 16 bytes longer; the second copy of every other read lies 50 pixels from the first, of the others
+far away): the marked rows without and with the optical distance N -- the decision alone (it holds the optical step) and the optical step alone, as the library
+times them --, and bam_markdup alone on one paired batch's records without and with the option.
+--parent-json FILE: the output of `--markdup` on the parent commit in the same GPU visit; every shared row is compared as under --groups.
 
 --markdup --groups: the read-group leg (profiles/bam_markdup_groups.json): --markdup's rows without groups (what a run paid before read groups existed:
 the opt-in path must cost nothing when it is off), the sorted rows through bmh_aligner_run_files' loader (the one a run over groups reads through), and the same reads given as 4 groups -- one file per batch -- of one library and of 4 libraries
@@ -48,8 +54,11 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--markdup", action="store_true")
     ap.add_argument("--groups", action="store_true")
+    ap.add_argument("--optical", type=int, default=None, help="with --markdup: the optical distance of the optical-duplicate leg")
     ap.add_argument("--parent-json", default="")
     a = ap.parse_args()
+    if a.optical is not None and (not a.markdup or a.groups or not 0 <= a.optical <= 0x7fffffff):
+        ap.error("--optical N (0 .. 2^31 - 1) goes with --markdup, without --groups")
     dev = torch.device("cuda:0")
     L = B.load_library()
     n_genome = int(a.genome_mbp * 1e6)
@@ -72,31 +81,40 @@ def main():
     asc = B.synth.codes_to_ascii(np.concatenate([r1.reshape(-1), r2.reshape(-1), r1.reshape(-1), r2.reshape(-1)]))
     n4 = 4 * n
     w = len(str(n4))
+    def loc_names(tpl, per_copy):
+        """names with locations for the templates tpl (ordinals in the file): copy k of template j lies 50 pixels (j even) or 60 000 (j odd) from copy 0"""
+        j, copy = tpl % per_copy, tpl // per_copy
+        x = 1000 + (j // 24) % 30000 + np.where(copy > 0, np.where(j % 2 == 0, 50, 60000), 0)
+        parts = [np.char.zfill((1101 + j % 24).astype(str), 4), np.char.zfill(x.astype(str), 6), np.char.zfill((1000 + j // 720000).astype(str), 6)]
+        s = np.char.add(np.char.add(np.char.add(">FC:1:", parts[0]), np.char.add(":", parts[1])), np.char.add(":", parts[2]))
+        return np.frombuffer("".join(s.tolist()).encode(), np.uint8).reshape(len(tpl), -1)
+    def write_fasta(dst, names, bases):
+        k = names.shape[1]
+        recs = np.empty((n4, k + 1 + rl + 1), np.uint8)
+        recs[:, :k] = names; recs[:, k] = 10; recs[:, k + 1:k + 1 + rl] = bases.reshape(n4, rl); recs[:, -1] = 10
+        recs.tofile(dst)
     names = np.frombuffer("".join(np.char.add(">r", np.char.zfill(np.arange(n4).astype(str), w)).tolist()).encode(), np.uint8).reshape(n4, w + 2)
-    recs = np.empty((n4, w + 3 + rl + 1), np.uint8)
-    recs[:, :w + 2] = names; recs[:, w + 2] = 10; recs[:, w + 3:w + 3 + rl] = asc.reshape(n4, rl); recs[:, -1] = 10
     tmp = tempfile.mkdtemp(prefix="bmh_bam_sort_")
     path = os.path.join(tmp, "se.fa")
-    recs.tofile(path)
-    del recs
+    write_fasta(path, names, asc)
     ppath = os.path.join(tmp, "pe.fa")
     if a.markdup:                                             # FR pairs, n reads per distinct batch, each batch twice; mates share a name
         p1 = B.synth.make_pairs(g, n // 2, rl, seed=7, holes=holes)[0]; p2 = B.synth.make_pairs(g, n // 2, rl, seed=1007, holes=holes)[0]
         pasc = B.synth.codes_to_ascii(np.concatenate([p1.reshape(-1), p2.reshape(-1), p1.reshape(-1), p2.reshape(-1)]))
         pn = np.frombuffer("".join(np.char.add(">p", np.char.zfill((np.arange(n4) // 2).astype(str), w)).tolist()).encode(), np.uint8).reshape(n4, w + 2)
-        prec = np.empty((n4, w + 3 + rl + 1), np.uint8)
-        prec[:, :w + 2] = pn; prec[:, w + 2] = 10; prec[:, w + 3:w + 3 + rl] = pasc.reshape(n4, rl); prec[:, -1] = 10
-        prec.tofile(ppath)
-        del prec
+        write_fasta(ppath, pn, pasc)
     nat = NativeAligner(dindex, pac_h, n_genome, contigs, None, co, ExtParams.default(), po, pe_o)
     result = {"genome_mbp": a.genome_mbp, "reads_per_run": n4, "setup_s": round(time.time() - t0, 1), "runs": a.runs, "host_threads": nth, "rows": {}}
 
-    def run(fmt, spill=False, keep=None, markdup=False, paired=False, groups=None, files=False):
+    def run(fmt, spill=False, keep=None, markdup=False, paired=False, groups=None, files=False, optical=None):
         src = ppath if paired else path
         nat.set_output(fmt, 1)
         if fmt == "bam_sorted":
             nat.set_sort(1 if spill else 64 << 30, tmp, 0)
             nat.set_markdup(markdup)
+            if markdup:
+                nat.set_markdup_optical(optical)
+        opt_ms = []
         nbytes = [0]
 
         def sink(mv):
@@ -117,6 +135,8 @@ def main():
                 secs.append(time.perf_counter() - t1); merge.append(st.format_seconds)
                 if markdup:
                     times.append(nat.markdup_times())
+                if optical is not None:
+                    opt_ms.append(nat.markdup_optical_ms())
         row = stats(secs, n4, 1e6)
         row["unit"] = "Mreads/s"; row["bytes_out_per_read"] = round(nbytes[0] / n4, 1)
         if fmt == "bam_sorted":
@@ -131,6 +151,10 @@ def main():
                 row["window_flags_alone"] = stats([max(t["window_flags_ms"], 1e-6) / 1e3 for t in times], n4, 1e6); row["window_flags_alone"]["unit"] = "Mrecords/s (ordinals up, flag kernel)"
                 row["window_flags_alone"]["ms"] = [round(t["window_flags_ms"], 2) for t in times]
                 row["entries_d2h_bytes_per_read"] = round(times[0]["entries_d2h_bytes"] / n4, 1)
+                if optical is not None:
+                    row["optical_counts"] = nat.markdup_optical_counts()
+                    row["optical_step_alone"] = stats([max(t, 1e-6) / 1e3 for t in opt_ms], tpl, 1e6); row["optical_step_alone"]["unit"] = "Mtemplates/s (inside the decision: locations up, sets, sorts, clustering, counts)"
+                    row["optical_step_alone"]["ms"] = [round(t, 2) for t in opt_ms]
                 if groups is not None:
                     row["library_counts"] = [nat.markdup_library_counts(k) for k in range(1 + max(g[1] for g in groups))]
         return row
@@ -197,6 +221,53 @@ def main():
         row = stats(secs, counts["templates"], 1e6); row["unit"] = "Mtemplates/s (the entry point: the host's walk, both copies, heads, entries, decision, flags)"
         row["templates"] = counts["templates"]; row["bytes"] = len(stream)
         result["rows"]["bam_markdup_device"] = row
+        if a.optical is not None:
+            # the rows above ran on the parent's reads (names r0000001); from here on the same reads under names with locations, 16 bytes longer each
+            result["optical_distance"] = a.optical
+            write_fasta(path, loc_names(np.arange(n4), 2 * n), asc)
+            write_fasta(ppath, loc_names(np.arange(n4) // 2, n), pasc)
+            result["rows"]["located_names_reads_to_sorted_bam_in_memory_markdup"] = run("bam_sorted", markdup=True)
+            result["rows"]["located_names_reads_to_sorted_bam_in_memory_markdup_optical"] = run("bam_sorted", markdup=True, optical=a.optical)
+            result["rows"]["located_names_paired_reads_to_sorted_bam_in_memory_markdup"] = run("bam_sorted", markdup=True, paired=True)
+            result["rows"]["located_names_paired_reads_to_sorted_bam_in_memory_markdup_optical"] = run("bam_sorted", markdup=True, paired=True, optical=a.optical)
+            keep2 = []
+            run("bam", keep=keep2, paired=True)
+            nat.set_output("sam", 1)
+            blob, recs, p = keep2[0], [], 0
+            while p < len(blob):
+                bs = int.from_bytes(blob[p + 16:p + 18], "little") + 1
+                recs.append(zlib.decompress(blob[p:p + bs], 31)); p += bs
+            pstream = b"".join(recs)
+            for what, kw in (("located_names_paired_bam_markdup_device", {}), ("located_names_paired_bam_markdup_optical_device", dict(optical_distance=a.optical))):
+                secs = []
+                for it in range(a.runs + 1):
+                    torch.cuda.synchronize(); t1 = time.perf_counter()
+                    _marked, counts = bam_markdup(pstream, **kw)
+                    if it:
+                        secs.append(time.perf_counter() - t1)
+                row = stats(secs, counts["templates"], 1e6); row["unit"] = "Mtemplates/s (the entry point on one paired batch's records)"
+                row["templates"] = counts["templates"]; row["bytes"] = len(pstream)
+                if kw:
+                    row["optical_duplicate_pairs"] = counts["optical_duplicate_pairs"]; row["located_pairs"] = counts["located_pairs"]
+                result["rows"][what] = row
+            if a.parent_json:
+                with open(a.parent_json) as f:
+                    parent = json.load(f)
+                result["parent_rows"] = {k: v for k, v in parent["rows"].items() if k in result["rows"]}
+                result["option_off_vs_parent"] = {}
+                for k, pr in result["parent_rows"].items():
+                    tr = result["rows"][k]
+                    diff = 100 * abs(tr["median"] - pr["median"]) / pr["median"]
+                    result["option_off_vs_parent"][k] = {"difference_pct": round(diff, 1), "larger_spread_pct": max(tr["spread_pct"], pr["spread_pct"]), "within_spread": diff <= max(tr["spread_pct"], pr["spread_pct"])}
+            result["not_measured"] = ("the share of templates in sets of two and more pairs on real data (here every read occurs twice: every pair lies in a set of two), sets of thousands of pairs, "
+                                      "single-end reads (they hold no pairs: the step uploads their locations and finds no member), spilled runs, reads with base qualities")
+            os.remove(ppath)
+            os.remove(path); os.rmdir(tmp)
+            out = a.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bam_markdup_optical.json")
+            with open(out, "w") as f:
+                json.dump(result, f, indent=1)
+            print(json.dumps(result))
+            return
         result["not_measured"] = "the flag kernel without the upload of its ordinals, spilled runs with marking, reads with base qualities (FASTA: every score is 0, ties go to the ordinal)"
         os.remove(ppath)
         os.remove(path); os.rmdir(tmp)
