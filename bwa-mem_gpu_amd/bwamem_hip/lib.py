@@ -49,6 +49,8 @@ EXPORTED_SYMBOLS = [
     "bmh_aligner_set_index_format", "bmh_bam_sorted_file_ex_device", "bmh_bam_sorted_file_ex_host",
     "bmh_bam_markdup_optical_device", "bmh_bam_markdup_optical_host", "bmh_bam_dup_locations_device", "bmh_bam_dup_locations_host", "bmh_bam_name_location", "bmh_library_size",
     "bmh_aligner_set_markdup_optical", "bmh_aligner_markdup_optical_counts", "bmh_aligner_markdup_optical_ms",
+    "bmh_bam_markdup_barcode_device", "bmh_bam_markdup_barcode_host", "bmh_bam_sorted_file_barcode_device", "bmh_bam_sorted_file_barcode_host",
+    "bmh_bam_dup_barcodes_device", "bmh_bam_dup_barcodes_host", "bmh_barcode_word", "bmh_aligner_set_markdup_barcode", "bmh_aligner_markdup_barcode_counts",
 ]
 
 
@@ -437,10 +439,71 @@ def optical_distance_value(value, what: str) -> int:
     return int(value)
 
 
-def _bam_markdup_optical(records: bytes, host: bool, read_groups, distance, max_set) -> tuple:
+BARCODE_OFF, BARCODE_TAG, BARCODE_NAME = 0, 1, 2
+_OWN_TAGS = ("RG", "NM", "MD", "AS", "XS", "SA", "XA", "pa")
+
+
+def barcode_source(barcode_tag, barcode_name, what: str) -> tuple:
+    """the keywords barcode_tag ("RX": a tag of type Z on a template's first record) and barcode_name (True: the read name's last ':' field) of the marking calls
+    -> (mode, tag bytes) for the C entry points; (0, None) when neither is given.  ValueError: both at once, a tag that is not [A-Za-z][A-Za-z0-9], RG, or a tag
+    the aligner writes itself (NM MD AS XS SA XA pa)"""
+    if barcode_name is not None and not isinstance(barcode_name, (bool, np.bool_)):
+        raise ValueError(f"{what}: barcode_name {barcode_name!r}: True or False")
+    if barcode_tag is not None and barcode_name:
+        raise ValueError(f"{what}: barcode_tag and barcode_name are two sources of one barcode: give one")
+    if barcode_tag is None:
+        return (BARCODE_NAME, None) if barcode_name else (BARCODE_OFF, None)
+    tag = barcode_tag.decode("latin-1") if isinstance(barcode_tag, bytes) else barcode_tag
+    if not isinstance(tag, str) or len(tag) != 2 or not (tag[0].isascii() and tag[0].isalpha() and tag[1].isascii() and tag[1].isalnum()):
+        raise ValueError(f"{what}: barcode_tag {barcode_tag!r}: two characters, [A-Za-z][A-Za-z0-9]")
+    if tag in _OWN_TAGS:
+        raise ValueError(f"{what}: barcode_tag {tag}: RG names the read group, and NM MD AS XS SA XA pa are written by the aligner itself")
+    return BARCODE_TAG, tag.encode()
+
+
+def barcode_word(value) -> int:
+    """bmh_barcode_word: the 64-bit word duplicate marking compares for a barcode value (bytes or str) -- FNV-1a, 0 for the empty value (no barcode), 1 for a
+    value that hashes to 0"""
+    L = load_library()
+    value = value if isinstance(value, bytes) else str(value).encode()
+    L.bmh_barcode_word.argtypes = [C.c_char_p, C.c_uint64]
+    L.bmh_barcode_word.restype = C.c_uint64
+    return int(L.bmh_barcode_word(value, len(value)))
+
+
+def bam_dup_barcodes(records: bytes, host: bool = False, tag=None, name=None) -> np.ndarray:
+    """bmh_bam_dup_barcodes_device (host=True: _host): a record stream as bam_markdup takes it -> one barcode word (uint64) per template, from tag `tag` of its first
+    record or (name=True) from its read name's last ':' field; 0: no barcode.  This is what bam_markdup(barcode_tag=...) compares."""
+    mode, tg = barcode_source(tag, name, "bam_dup_barcodes")
+    if mode == BARCODE_OFF:
+        raise ValueError("bam_dup_barcodes: give tag= or name=True")
+    L = load_library()
+    records = bytes(records)
+    L.bmh_free.argtypes = [C.c_void_p]
+    out, nt = C.c_void_p(), C.c_uint64(0)
+    head = [C.c_char_p, C.c_uint64, C.c_int, C.c_char_p]
+    if host:
+        L.bmh_bam_dup_barcodes_host.argtypes = head + [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        rc = L.bmh_bam_dup_barcodes_host(records, len(records), mode, tg, C.byref(out), C.byref(nt))
+    else:
+        import torch
+        L.bmh_bam_dup_barcodes_device.argtypes = head + [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        rc = L.bmh_bam_dup_barcodes_device(records, len(records), mode, tg, torch.cuda.current_stream().cuda_stream, C.byref(out), C.byref(nt))
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_dup_barcodes: " + _err(L))
+    try:
+        return np.frombuffer(C.string_at(out.value, 8 * nt.value) if nt.value else b"", dtype="<u8").copy()
+    finally:
+        L.bmh_free(out)
+
+
+def _bam_markdup_optical(records: bytes, host: bool, read_groups, distance, max_set, barcode=None) -> tuple:
     L = load_library()
     L.bmh_free.argtypes = [C.c_void_p]
-    distance = optical_distance_value(distance, "bam_markdup")
+    if barcode is not None and distance is None:
+        distance = -1
+    else:
+        distance = optical_distance_value(distance, "bam_markdup")
     if max_set is None:
         max_set = 0
     elif not isinstance(max_set, (int, np.integer)) or isinstance(max_set, bool) or not 1 <= max_set <= 0x7fffffff:
@@ -455,7 +518,17 @@ def _bam_markdup_optical(records: bytes, host: bool, read_groups, distance, max_
         lo = (C.c_uint64 * (3 * max(len(names), 1)))()
     head = [C.c_char_p, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int, C.c_int64, C.c_uint64]
     tail = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    if host:
+    if barcode is not None:                                   # bmh_bam_markdup_barcode_*: the optical call with the barcode's source; distance -1: no optical step
+        nb = C.c_uint64(0)
+        bc, btail, bargs = [C.c_int, C.c_char_p], tail + [C.POINTER(C.c_uint64)], (C.byref(out), counts, lc, opt, lo, C.byref(nb))
+        if host:
+            L.bmh_bam_markdup_barcode_host.argtypes = head + bc + btail
+            rc = L.bmh_bam_markdup_barcode_host(records, len(records), ids, lib, ng, distance, int(max_set), barcode[0], barcode[1], *bargs)
+        else:
+            import torch
+            L.bmh_bam_markdup_barcode_device.argtypes = head + bc + [C.c_void_p] + btail
+            rc = L.bmh_bam_markdup_barcode_device(records, len(records), ids, lib, ng, distance, int(max_set), barcode[0], barcode[1], torch.cuda.current_stream().cuda_stream, *bargs)
+    elif host:
         L.bmh_bam_markdup_optical_host.argtypes = head + tail
         rc = L.bmh_bam_markdup_optical_host(records, len(records), ids, lib, ng, distance, int(max_set), C.byref(out), counts, lc, opt, lo)
     else:
@@ -466,11 +539,15 @@ def _bam_markdup_optical(records: bytes, host: bool, read_groups, distance, max_
         raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_markdup: " + _err(L))
     try:
         c = dict(zip(MARKDUP_COUNTS, (int(v) for v in counts)))
-        c.update(zip(OPTICAL_COUNTS, (int(v) for v in opt)))
+        if distance >= 0:
+            c.update(zip(OPTICAL_COUNTS, (int(v) for v in opt)))
+        if barcode is not None:
+            c["templates_without_barcode"] = int(nb.value)
         if read_groups is not None:
             c["libraries"] = _library_counts(names, lc)
             for k, nm in enumerate(names):
-                c["libraries"][nm].update(zip(OPTICAL_COUNTS, (int(v) for v in lo[3 * k:3 * k + 3])))
+                if distance >= 0:
+                    c["libraries"][nm].update(zip(OPTICAL_COUNTS, (int(v) for v in lo[3 * k:3 * k + 3])))
         return (C.string_at(out.value, len(records)) if records else b""), c
     finally:
         L.bmh_free(out)
@@ -526,7 +603,7 @@ def estimate_library_size(n: int, c: int):
     return int(size.value) if L.bmh_library_size(int(n), int(c), C.byref(size)) == 1 else None
 
 
-def bam_markdup(records: bytes, host: bool = False, read_groups=None, optical_distance=None, optical_max_set=None) -> tuple:
+def bam_markdup(records: bytes, host: bool = False, read_groups=None, optical_distance=None, optical_max_set=None, barcode_tag=None, barcode_name=None) -> tuple:
     """bmh_bam_markdup_device (host=True: bmh_bam_markdup_host, no device needed): a stream of BAM records in the writer's order (a template's records next to
     each other, its first primary line first) -> (the same records with flag 0x400 on every record of every duplicate template, the counts by MARKDUP_COUNTS'
     names).  Picard MarkDuplicates' rules.  A cut stream, one whose first record begins no template and a paired template without both of its
@@ -536,11 +613,18 @@ def bam_markdup(records: bytes, host: bool = False, read_groups=None, optical_di
     not listed, more than 255 libraries and a repeated ID raise ValueError.  Without read_groups no tag is read.
     optical_distance (bmh_bam_markdup_optical_*): also count the optical duplicates -- pairs of one duplicate set whose names place them on one tile within that
     many pixels in x and y -- the counts gain OPTICAL_COUNTS' names, with read_groups per library too; the records are those of the call without
-    it.  optical_max_set (needs optical_distance; default 300 000): sets of more pairs are not examined."""
+    it.  optical_max_set (needs optical_distance; default 300 000): sets of more pairs are not examined.
+    barcode_tag="RX" or barcode_name=True (bmh_bam_markdup_barcode_*; one of the two): templates with different molecular barcodes (UMIs) are no duplicates of each
+    other -- the barcode is the value of that tag (type Z, verbatim) on the template's first record, or the read name's last ':' field; the keys become (lo, hi,
+    barcode) and (end, barcode), an optical set the pairs of one (lo, hi, barcode).  Templates without a barcode are comparable with each other only; the counts gain
+    "templates_without_barcode".  A first record whose tag has another type, or whose tags cannot be walked, raises ValueError with its index."""
     L = load_library()
     records = bytes(records)
     if optical_max_set is not None and optical_distance is None:
         raise ValueError("bam_markdup: optical_max_set needs optical_distance")
+    bc_mode, bc_tag = barcode_source(barcode_tag, barcode_name, "bam_markdup")
+    if bc_mode != BARCODE_OFF:
+        return _bam_markdup_optical(records, host, read_groups, optical_distance, optical_max_set, (bc_mode, bc_tag))
     if optical_distance is not None:
         return _bam_markdup_optical(records, host, read_groups, optical_distance, optical_max_set)
     L.bmh_free.argtypes = [C.c_void_p]
@@ -598,13 +682,17 @@ def index_format_code(index_format, csi_min_shift, what: str) -> tuple:
 
 
 def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False, markdup: bool = False, read_groups=None,
-                    index_format: str = "bai", csi_min_shift: int = 14) -> tuple:
+                    index_format: str = "bai", csi_min_shift: int = 14, barcode_tag=None, barcode_name=None) -> tuple:
     """bmh_bam_sorted_file_device (host=True: _host): (the complete sorted BAM file -- header members, the records in coordinate order in windows of `window`
     records (0: about 64 MiB), the end-of-file member --, its .bai index).  contigs: (name, length) pairs; both forms give the same bytes.
     markdup=True (bmh_bam_sorted_file_markdup_*): `records` come in the writer's order, the duplicates among them are marked (bam_markdup's rules) and the counts come third.
     read_groups (needs markdup=True): as bam_markdup takes them -- duplicates per library, and the counts gain "libraries".
     index_format="csi" (bmh_bam_sorted_file_ex_*): the second element is the .csi index -- BGZF-compressed, bins of 2^csi_min_shift bases (10 .. 24) at the depth the
-    longest contig asks for --, contigs may hold up to 2^31 - 1 bases (with markdup=True up to 2^30 - 2^24) and the BAM bytes are those of the "bai" call."""
+    longest contig asks for --, contigs may hold up to 2^31 - 1 bases (with markdup=True up to 2^30 - 2^24) and the BAM bytes are those of the "bai" call.
+    barcode_tag / barcode_name (bmh_bam_sorted_file_barcode_*; need markdup=True): as bam_markdup takes them; the counts gain "templates_without_barcode"."""
+    bc_mode, bc_tag = barcode_source(barcode_tag, barcode_name, "bam_sorted_file")
+    if bc_mode != BARCODE_OFF and not markdup:
+        raise ValueError("bam_sorted_file: barcode_tag / barcode_name need markdup=True (barcodes are compared where duplicates are marked)")
     if read_groups is not None and not markdup:
         raise ValueError("bam_sorted_file: read_groups needs markdup=True (they decide which templates may be duplicates of each other)")
     ix_code, ix_shift = index_format_code(index_format, csi_min_shift, "bam_sorted_file")
@@ -624,7 +712,13 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
     sig = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_uint32]
     out = [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p]
     counts = (C.c_uint64 * 8)()
-    if ix_code == INDEX_CSI:                                  # the one entry point that takes everything: counts and library counts always have their place
+    no_bc = C.c_uint64(0)
+    if bc_mode != BARCODE_OFF:                                # the _ex call (marking on) with the barcode's source and the count of templates without one
+        ids, lib, ng, lib_names = _library_table(read_groups) if read_groups is not None else (None, None, 0, [])
+        lc = (C.c_uint64 * (8 * max(len(lib_names), 1)))()
+        head += [ix_code, ix_shift, ids, lib, ng, bc_mode, bc_tag]; sig += [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_char_p]
+        tail += [counts, lc if read_groups is not None else None, C.byref(no_bc)]; out += [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    elif ix_code == INDEX_CSI:                                # the one entry point that takes everything: counts and library counts always have their place
         ids, lib, ng, lib_names = _library_table(read_groups) if read_groups is not None else (None, None, 0, [])
         lc = (C.c_uint64 * (8 * max(len(lib_names), 1)))()
         head += [ix_code, ix_shift, 1 if markdup else 0, ids, lib, ng]; sig += [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int]
@@ -632,13 +726,23 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
     elif markdup:
         tail.append(counts); out.append(C.POINTER(C.c_uint64))
     grp = ""
-    if read_groups is not None and ix_code != INDEX_CSI:
+    if read_groups is not None and ix_code != INDEX_CSI and bc_mode == BARCODE_OFF:
         ids, lib, ng, lib_names = _library_table(read_groups)
         lc = (C.c_uint64 * (8 * max(len(lib_names), 1)))()
         head += [ids, lib, ng]; sig += [C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int]
         tail.append(lc); out.append(C.POINTER(C.c_uint64))
         grp = "_groups"
-    if ix_code == INDEX_CSI:
+    if bc_mode != BARCODE_OFF:
+        if host:
+            fn = L.bmh_bam_sorted_file_barcode_host
+            fn.argtypes = sig + out
+            rc = fn(*head, *tail)
+        else:
+            import torch
+            fn = L.bmh_bam_sorted_file_barcode_device
+            fn.argtypes = sig + [C.c_void_p] + out
+            rc = fn(*head, torch.cuda.current_stream().cuda_stream, *tail)
+    elif ix_code == INDEX_CSI:
         if host:
             fn = L.bmh_bam_sorted_file_ex_host
             fn.argtypes = sig + out
@@ -664,6 +768,8 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
             c = dict(zip(MARKDUP_COUNTS, (int(v) for v in counts)))
             if read_groups is not None:
                 c["libraries"] = _library_counts(lib_names, lc)
+            if bc_mode != BARCODE_OFF:
+                c["templates_without_barcode"] = int(no_bc.value)
             return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value), c
         return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)
     finally:
@@ -854,6 +960,23 @@ class NativeAligner:
         L.bmh_aligner_set_markdup_optical.argtypes = [C.c_void_p, C.c_int64]
         if L.bmh_aligner_set_markdup_optical(self.handle, -1 if distance is None else int(distance)) != 0:
             raise ValueError("bmh_aligner_set_markdup_optical: " + _err(L))
+
+    def set_markdup_barcode(self, mode: int = 0, tag=None) -> None:
+        """bmh_aligner_set_markdup_barcode: the marked runs that follow compare the templates' barcodes -- mode 1: tag `tag`, 2: the read name's last field, 0: off
+        (refused unless marking is on)"""
+        L = load_library()
+        L.bmh_aligner_set_markdup_barcode.argtypes = [C.c_void_p, C.c_int, C.c_char_p]
+        if L.bmh_aligner_set_markdup_barcode(self.handle, int(mode), tag) != 0:
+            raise ValueError("bmh_aligner_set_markdup_barcode: " + _err(L))
+
+    def markdup_barcode_counts(self) -> dict:
+        """bmh_aligner_markdup_barcode_counts: {"templates_without_barcode": ...} of the last run that compared barcodes"""
+        L = load_library()
+        L.bmh_aligner_markdup_barcode_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        c = (C.c_uint64 * 1)()
+        if L.bmh_aligner_markdup_barcode_counts(self.handle, c) != 0:
+            raise ValueError("bmh_aligner_markdup_barcode_counts: " + _err(L))
+        return {"templates_without_barcode": int(c[0])}
 
     def markdup_optical_counts(self, lib: int = -1) -> dict:
         """bmh_aligner_markdup_optical_counts: the optical counts of the last run that counted them, by OPTICAL_COUNTS' names -- of library `lib`, or (-1) in total"""

@@ -17,12 +17,18 @@ bytes are those of --sort), --csi-min-shift N (needs --csi: the index's smallest
 decided on the device by Picard MarkDuplicates' rules -- the unclipped 5' ends and strands of a template's primary lines are the key, the sum of the base
 qualities >= 15 the score, ties go to the template that came first in the input, a fragment is a duplicate wherever a pair has an end; unlike Picard and
 `samtools markdup` on coordinate-sorted input the secondary and supplementary lines of a duplicate template are flagged too; nothing is removed, no DT:Z
-tag is written, keys know no UMI; with --csi a contig beyond 2^30 - 2^24 bases is refused for --markdup, by name), --markdup-metrics PATH
+tag is written; with --csi a contig beyond 2^30 - 2^24 bases is refused for --markdup, by name), --markdup-metrics PATH
 (a Picard-style table of the counts, one row per library) and --optical-distance N (needs --markdup; a whole number, 0 .. 2^31 - 1 -- Picard uses 100, and 2500
 on patterned flow cells; there is no default: the option turns the step on -- the decision also counts the optical duplicates: pairs of one duplicate set whose
 read names, Illumina's 5 or 7 ':'-separated fields ending in tile:x:y, place them on one tile of one read group within N pixels in x and in y, clusters being
 the connected components; the BAM and its index stay byte for byte those of --markdup, and the metrics table gains READ_PAIR_OPTICAL_DUPLICATES and
-ESTIMATED_LIBRARY_SIZE in Picard's column order; the names' pattern is fixed).  --rg LINE opens a read group:
+ESTIMATED_LIBRARY_SIZE in Picard's column order; the names' pattern is fixed), --barcode-tag XX and --barcode-name (need --markdup; one of the two: templates
+with different molecular barcodes -- UMIs -- are no duplicates of each other, as with Picard's BARCODE_TAG and `samtools markdup --barcode-tag / --barcode-name`.
+--barcode-tag XX: the barcode is the value of tag XX, type Z, on a template's first record, taken verbatim (a dual UMI ACGT-TTGA is one value); it needs -C,
+which copies a FASTQ comment such as RX:Z:ACGT, or a uBAM's own tags, into the records; XX is two characters [A-Za-z][A-Za-z0-9], not RG nor a tag the aligner
+writes itself.  --barcode-name: the barcode is what follows the last ':' of the read name, bcl-convert's ...:tile:x:y:UMI, and --optical-distance then locates a
+read by the name without that field.  A template without a barcode is comparable only with others without one; barcodes are compared exactly, grouping them by
+edit distance is not built; the metrics table keeps its columns).  --rg LINE opens a read group:
 LINE is an @RG line as -R takes it, and the one or two files that follow it, up to the next --rg, are that group's input (Aligner.align_groups): a sample's lanes
 and libraries go into one output, every record with its group's RG:Z, the header with every @RG line, and --markdup calls duplicates within a library (the LB
 field; groups with one LB are lanes of one library) only.  -p applies to every group; --rg and -R exclude each other.  --keep-rg keeps the read groups of the
@@ -59,6 +65,7 @@ def main(argv=None) -> int:
     bam, bam_level = False, 1
     sort, index_path, sort_mem, sort_tmp = False, None, None, None
     markdup, metrics_path, optical = False, None, None
+    barcode_tag, barcode_name = None, False
     csi, csi_shift = False, None
     keep_rg = False
     groups = []                                                     # --rg LINE: [line, files...]; the positionals behind it are its files
@@ -94,6 +101,14 @@ def main(argv=None) -> int:
                 print("[bwamem_hip.mem] option --optical-distance needs a whole number of pixels, 0 .. 2^31 - 1", file=sys.stderr)
                 return 2
             optical = int(argv[i + 1])
+            i += 1
+        elif a == "--barcode-name":
+            barcode_name = True
+        elif a == "--barcode-tag":
+            if i + 1 >= len(argv):
+                print("[bwamem_hip.mem] option --barcode-tag needs a tag of two characters", file=sys.stderr)
+                return 2
+            barcode_tag = argv[i + 1]
             i += 1
         elif a == "--keep-rg":
             keep_rg = True
@@ -172,6 +187,19 @@ def main(argv=None) -> int:
     if optical is not None and not markdup:
         print("[bwamem_hip.mem] --optical-distance needs --markdup (optical duplicates are counted where duplicates are marked)", file=sys.stderr)
         return 2
+    if barcode_tag is not None or barcode_name:
+        from .lib import barcode_source
+        try:
+            barcode_source(barcode_tag, barcode_name or None, "--barcode-tag")
+        except ValueError as e:
+            print(f"[bwamem_hip.mem] {e}", file=sys.stderr)
+            return 2
+        if not markdup:
+            print("[bwamem_hip.mem] --barcode-tag and --barcode-name need --markdup (barcodes are compared where duplicates are marked)", file=sys.stderr)
+            return 2
+        if barcode_tag is not None and "-C" not in opts:
+            print("[bwamem_hip.mem] --barcode-tag needs -C: the tag reaches a record only as the read's comment", file=sys.stderr)
+            return 2
     if csi_shift is not None and not csi:
         print("[bwamem_hip.mem] --csi-min-shift needs --csi (a BAI index has one bin size)", file=sys.stderr)
         return 2
@@ -194,6 +222,10 @@ def main(argv=None) -> int:
             fmt_kw.update(markdup=True, markdup_metrics=metrics_path)
         if optical is not None:
             fmt_kw.update(optical_distance=optical)
+        if barcode_tag is not None:
+            fmt_kw.update(barcode_tag=barcode_tag)
+        if barcode_name:
+            fmt_kw.update(barcode_name=True)
         if csi:
             fmt_kw.update(index_format="csi", csi_min_shift=14 if csi_shift is None else csi_shift)
         done = False

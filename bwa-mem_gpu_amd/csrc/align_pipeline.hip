@@ -50,6 +50,7 @@ struct aligner_t {
 	std::string rg_id;             // the aligner's own copy of popt->rg_id (po.rg_id points into it): the caller's string need not outlive the call that created the aligner
 	uint32_t max_qlen = 768;       // the extension cap of the chain workspaces (bmh_aligner_set_max_qlen)
 	bmh_reseed_opt_t rs = {0, 1.5f, 10, 20};   // the seeding rounds (bmh_aligner_set_reseed; enable 0: the first round only)
+	bdp_bc_t barcode = {BDP_BC_OFF, 0, 0};      // ... with markdup: compare the templates' barcodes, from a tag or the read name (bmh_aligner_set_markdup_barcode)
 	int64_t optical = -1;                      // ... with markdup: also count the optical duplicates within this distance (bmh_aligner_set_markdup_optical); -1: not
 	bool markdup = false;                      // sorted BAM output: flag 0x400 on the records of duplicate templates (bmh_aligner_set_markdup)
 	int out_fmt = BMH_OUT_SAM, out_level = 1;  // what the sink receives (bmh_aligner_set_output): the records' text, or BGZF members of BAM records
@@ -108,6 +109,7 @@ struct result_t {
 	hbuf_t<char> text; uint64_t text_len = 0; bool has_text = false;     // the text written on the device (no formatting on the host)
 	hbuf_t<uint64_t> skeys, soff; uint32_t n_rec = 0;                   // sorted BAM: text holds the batch's records in order; their keys and offsets [n_rec + 1]
 	hbuf_t<uint32_t> lib3;                                             // ... of a batch that mixes libraries (aligner_t::per_read): its counts per library [3 * libraries]
+	hbuf_t<uint64_t> dup_b;                                           // ... when barcodes are compared: the templates' barcode words
 	hbuf_t<bdp_loc_t> dup_l;                                          // ... when optical duplicates are counted: the templates' locations
 	hbuf_t<uint32_t> stpl; hbuf_t<bdp_entry_t> dup_e; uint32_t dup_info[BDP_INFO_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0}; uint64_t dup_d2h = 0;      // duplicate marking: the records' template ordinals in that order, the templates' entries, bdp_batch_device's info
 	std::vector<int64_t> slot;                   // (host selection only; empty: slot32)
@@ -265,15 +267,16 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 			const uint8_t *ds = nullptr; const uint64_t *dk = nullptr, *dso = nullptr;
 			const uint32_t nrec = bo.n_records;
 			// duplicate marking: on the records in the writer's order, before the sort -- heads, their scan, one entry per template; the ordinals follow the records
-			const uint32_t *d_tpl = nullptr, *d_info = nullptr, *d_stpl = nullptr, *d_lib3 = nullptr; const bdp_entry_t *d_e = nullptr; const bdp_loc_t *d_l = nullptr;
-			const bool optical = A.markdup && A.optical >= 0;
+			const uint32_t *d_tpl = nullptr, *d_info = nullptr, *d_stpl = nullptr, *d_lib3 = nullptr; const bdp_entry_t *d_e = nullptr; const bdp_loc_t *d_l = nullptr; const uint64_t *d_b = nullptr;
+			const bool optical = A.markdup && A.optical >= 0, barcode = A.markdup && A.barcode.mode != BDP_BC_OFF;
 			const uint32_t tmax = paired ? n / 2 : n;                   // the batch's templates: every read or pair leaves at least one record, so no more entries than this come down
 			if (A.markdup) {
 				if (!Ln.bdp && !(Ln.bdp = bdp_dev_create())) return BMH_ENOMEM;
 				if (Ln.groups_serial != A.groups_serial) { RCK(bdp_dev_set_groups(Ln.bdp, &A.groups, Ln.st)); Ln.groups_serial = A.groups_serial; }
-				RCK(bdp_batch_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &d_tpl, &d_e, &d_info, optical ? &d_l : nullptr));
+				RCK(bdp_batch_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &d_tpl, &d_e, &d_info, optical ? &d_l : nullptr, barcode ? &A.barcode : nullptr, barcode ? &d_b : nullptr));
 				RCK(R.stpl.need((size_t)nrec + 1)); RCK(R.dup_e.need((size_t)std::min(nrec, tmax) + 1));
 				if (optical) RCK(R.dup_l.need((size_t)std::min(nrec, tmax) + 1));
+				if (barcode) RCK(R.dup_b.need((size_t)std::min(nrec, tmax) + 1));
 				if (A.per_read) {                                     // a batch of several libraries: its counts per library, from the entries' library bytes
 					RCK(bdp_batch_lib_counts_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, A.groups.n_lib, Ln.st, &d_lib3));
 					RCK(R.lib3.need(3 * (size_t)A.groups.n_lib));
@@ -291,17 +294,18 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 				if (nrec) HIPCK(hipMemcpyAsync(R.stpl.p, d_stpl, 4 * (size_t)nrec, hipMemcpyDeviceToHost, Ln.st));
 				if (ne) HIPCK(hipMemcpyAsync(R.dup_e.p, d_e, sizeof(bdp_entry_t) * ne, hipMemcpyDeviceToHost, Ln.st));
 				if (ne && optical) HIPCK(hipMemcpyAsync(R.dup_l.p, d_l, sizeof(bdp_loc_t) * ne, hipMemcpyDeviceToHost, Ln.st));
-				const size_t ni = A.groups.empty() ? 16 : 4 * BDP_INFO_WORDS;      // (with read groups: the words of a template without a known group)
+				if (ne && barcode) HIPCK(hipMemcpyAsync(R.dup_b.p, d_b, 8 * ne, hipMemcpyDeviceToHost, Ln.st));
+				const size_t ni = A.groups.empty() && !barcode ? 16 : 4 * BDP_INFO_WORDS;      // (with read groups: the words of a template without a known group; with barcodes: of one whose tags are refused)
 				HIPCK(hipMemcpyAsync(R.dup_info, d_info, ni, hipMemcpyDeviceToHost, Ln.st));
 				if (d_lib3) HIPCK(hipMemcpyAsync(R.lib3.p, d_lib3, 12 * (size_t)A.groups.n_lib, hipMemcpyDeviceToHost, Ln.st));
-				R.dup_d2h = 4ull * nrec + sizeof(bdp_entry_t) * ne + ni + (d_lib3 ? 12ull * A.groups.n_lib : 0) + (optical ? sizeof(bdp_loc_t) * ne : 0);
+				R.dup_d2h = 4ull * nrec + sizeof(bdp_entry_t) * ne + ni + (d_lib3 ? 12ull * A.groups.n_lib : 0) + (optical ? sizeof(bdp_loc_t) * ne : 0) + (barcode ? 8ull * ne : 0);
 				Ln.copy_bytes[1] += R.dup_d2h;
 			}
 			HIPCK(hipEventRecord(Ln.ev_c[3], Ln.st));
 			Ln.copy_bytes[1] += bo.bam_bytes + 16ull * nrec; Ln.d2h_marked = true;
 			HIPCK(hipStreamSynchronize(Ln.st));
 			if (A.markdup && nrec) {
-				RCK(bdp_batch_check(nrec, R.dup_info, !A.groups.empty(), "sorted BAM"));
+				RCK(bdp_batch_check(nrec, R.dup_info, !A.groups.empty(), "sorted BAM", barcode));
 				if (R.dup_info[0] == 0 || R.dup_info[0] > std::min(nrec, tmax)) { bmh_set_error("sorted BAM: internal error: %u templates among %u records", R.dup_info[0], nrec); return BMH_EINVAL; }
 			}
 			if (R.soff.p[nrec] != bo.bam_bytes) {                 // (the gather skips a record whose offsets lie outside the buffers: the scan of the sizes shows it)
@@ -889,6 +893,7 @@ struct bmh_aligner {
 	uint64_t dup_counts[BDP_N_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0}; bool dup_valid = false;      // duplicate marking: the counts of the last marked run
 	std::vector<uint64_t> lib_counts;                    // ... with read groups: the same eight per library (bmh_aligner_markdup_library_counts)
 	uint64_t opt_counts[BDP_OPT_N] = {0, 0, 0}; std::vector<uint64_t> lib_opt; bool opt_valid = false; double opt_ms = 0;      // ... with an optical distance: the three optical counts of the last such run, per library, and the step's ms
+	uint64_t no_barcode = 0; bool bc_valid = false;      // ... with barcodes: the templates without one in the last such run
 	double dup_times[3] = {0, 0, 0};                     // ... its decision and its windows' flag steps in ms, the bytes its batches' ordinals and entries took on their way down
 };
 
@@ -922,7 +927,7 @@ int bmh_aligner_set_output(bmh_aligner_t *h, int format, int level)
 	if (format != BMH_OUT_SAM && format != BMH_OUT_BAM && format != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_output: format %d (BMH_OUT_SAM, BMH_OUT_BAM or BMH_OUT_BAM_SORTED)", format); return BMH_EINVAL; }
 	if (format != BMH_OUT_SAM && level != 0 && level != 1) { bmh_set_error("bmh_aligner_set_output: level %d (0 or 1)", level); return BMH_EINVAL; }
 	if (format == BMH_OUT_BAM_SORTED) { h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), "sorted BAM output", h->ix_format, h->ix_shift)); }
-	if (format != BMH_OUT_BAM_SORTED) { h->a.markdup = false; h->a.optical = -1; }      // (duplicates are marked in sorted output only: the options go with the format)
+	if (format != BMH_OUT_BAM_SORTED) { h->a.markdup = false; h->a.optical = -1; h->a.barcode.mode = BDP_BC_OFF; }      // (duplicates are marked in sorted output only: the options go with the format)
 	h->a.out_fmt = format; h->a.out_level = level;
 	return BMH_OK;
 }
@@ -964,7 +969,28 @@ int bmh_aligner_set_markdup(bmh_aligner_t *h, int on)
 	if (on && h->a.out_fmt != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_markdup: duplicates are marked in sorted output (bmh_aligner_set_output with BMH_OUT_BAM_SORTED comes first)"); return BMH_EINVAL; }
 	if (on) RCK(bsr_markdup_contigs(h->a.n_contigs, h->a.len.data(), h->a.name_ptr.data(), "bmh_aligner_set_markdup"));      // (only a CSI run can hold such a contig)
 	h->a.markdup = on != 0;
-	if (!on) h->a.optical = -1;
+	if (!on) { h->a.optical = -1; h->a.barcode.mode = BDP_BC_OFF; }
+	return BMH_OK;
+}
+
+int bmh_aligner_set_markdup_barcode(bmh_aligner_t *h, int mode, const char *tag)
+{
+	const char *fn = "bmh_aligner_set_markdup_barcode";
+	if (!h) { bmh_set_error("%s: null aligner", fn); return BMH_EINVAL; }
+	if (mode == BDP_BC_OFF) { h->a.barcode.mode = BDP_BC_OFF; return BMH_OK; }
+	if (!h->a.markdup) { bmh_set_error("%s: barcodes are compared where duplicates are marked (bmh_aligner_set_markdup comes first)", fn); return BMH_EINVAL; }
+	bdp_bc_t bc;
+	RCK(bdp_barcode_check(mode, tag, fn, &bc));
+	h->a.barcode = bc;
+	return BMH_OK;
+}
+
+int bmh_aligner_markdup_barcode_counts(bmh_aligner_t *h, uint64_t out[1])
+{
+	const char *fn = "bmh_aligner_markdup_barcode_counts";
+	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (!h->dup_valid || !h->bc_valid) { bmh_set_error("%s: no run has compared barcodes (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
+	out[0] = h->no_barcode;
 	return BMH_OK;
 }
 
@@ -1071,7 +1097,7 @@ struct out_stage_t {
 	int lib_of(int group) const { return group >= 0 && (size_t)group < h->a.groups.lib.size() ? (int)h->a.groups.lib[(size_t)group] : -1; }
 	int emit(const void *p, size_t n) { if (n && sink(user, (const char *)p, n) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; } n_bytes += n; return BMH_OK; }
 	// (the index is valid again once the merge has written the whole file)
-	int begin() { if (fmt == BMH_OUT_BAM_SORTED) { h->dup_valid = false; h->opt_valid = false; h->opt_ms = 0; h->dup_times[0] = h->dup_times[1] = h->dup_times[2] = 0; h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), fn, h->ix_format, h->ix_shift)); h->sort_ix.valid = false;
+	int begin() { if (fmt == BMH_OUT_BAM_SORTED) { h->dup_valid = false; h->opt_valid = false; h->bc_valid = false; h->opt_ms = 0; h->dup_times[0] = h->dup_times[1] = h->dup_times[2] = 0; h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), fn, h->ix_format, h->ix_shift)); h->sort_ix.valid = false;
 		if (h->a.markdup) RCK(bsr_markdup_contigs(h->a.n_contigs, h->a.len.data(), h->a.name_ptr.data(), fn)); } return BMH_OK; }
 	int device_batch(const result_t &R)
 	{
@@ -1080,6 +1106,7 @@ struct out_stage_t {
 		bsr_dup_t bd = {R.stpl.p, R.dup_e.p, R.dup_info[0], R.dup_info[2], R.dup_info[3], lib_of(R.group)};
 		if (h->a.markdup && h->a.per_read) { bd.lib3 = R.lib3.p; bd.n_lib3 = h->a.groups.n_lib; }
 		if (h->a.markdup && h->a.optical >= 0) bd.locs = R.dup_l.p;
+		if (h->a.markdup && h->a.barcode.mode != BDP_BC_OFF) bd.bcs = R.dup_b.p;
 		if (h->a.markdup) h->dup_times[2] += (double)R.dup_d2h;
 		return h->store.append((const uint8_t *)R.text.p, R.text_len, R.skeys.p, R.soff.p, R.n_rec, h->a.markdup ? &bd : nullptr);      // a sorted run: kept until the end of the input
 	}
@@ -1107,15 +1134,16 @@ struct out_stage_t {
 				bsr_sort_host(bam, off, keys, ord);
 				srt.reserve((size_t)bb + 1);
 				for (uint32_t i : ord) { srt.insert(srt.end(), bam + off[i], bam + off[i + 1]); soff.push_back(srt.size()); }
-				std::vector<uint32_t> tpl, stpl; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> locs; uint64_t info[2] = {0, 0};
-				const bool optical = A.markdup && A.optical >= 0;
+				std::vector<uint32_t> tpl, stpl; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> locs; std::vector<uint64_t> bcs; uint64_t info[2] = {0, 0};
+				const bool optical = A.markdup && A.optical >= 0, barcode = A.markdup && A.barcode.mode != BDP_BC_OFF;
 				if (A.markdup) {                                   // the host forms of the device's heads, ordinals and entries
 					const bdp_groups_t G = A.groups.view();
-					rc = bdp_entries_host(bam, off.data(), (uint32_t)ord.size(), tpl, E, info, fn, A.groups.empty() ? nullptr : &G, optical ? &locs : nullptr);
+					rc = bdp_entries_host(bam, off.data(), (uint32_t)ord.size(), tpl, E, info, fn, A.groups.empty() ? nullptr : &G, optical ? &locs : nullptr, barcode ? &A.barcode : nullptr, barcode ? &bcs : nullptr);
 					for (uint32_t i : ord) stpl.push_back(tpl[i]);
 				}
 				bsr_dup_t bd = {stpl.data(), E.data(), (uint32_t)E.size(), info[0], info[1], lib_of(group)};
 				if (optical) bd.locs = locs.data();
+				if (barcode) bd.bcs = bcs.data();
 				std::vector<uint32_t> lib3;
 				if (rc == BMH_OK && A.markdup && A.per_read) {        // the host form of bdp_batch_lib_counts_device
 					std::vector<uint64_t> lc((size_t)BDP_N_COUNTS * A.groups.n_lib, 0);
@@ -1147,13 +1175,15 @@ struct out_stage_t {
 		const bool optical = h->a.markdup && h->a.optical >= 0;
 		h->lib_opt.assign(optical ? (size_t)BDP_OPT_N * n_lib : 0, 0);
 		const bdp_optical_t O = {h->a.optical, (uint32_t)BDP_OPT_MAX_SET, h->opt_counts, n_lib ? h->lib_opt.data() : nullptr};
+		const bool barcode = h->a.markdup && h->a.barcode.mode != BDP_BC_OFF;
+		h->no_barcode = barcode ? bdp_no_barcode(h->store.bcs.data(), h->store.bcs.size()) : 0;
 		if (rc == BMH_OK) rc = bsr_merge_device(L0.bsr, L0.bam, h->store, h->sort_window, h->a.out_level, L0.st, h->sort_ix, forward, this, h->a.markdup ? h->dup_counts : nullptr, h->dup_times,
-		                                        n_lib, n_lib ? h->lib_counts.data() : nullptr, optical ? &O : nullptr, optical ? &h->opt_ms : nullptr);
+		                                        n_lib, n_lib ? h->lib_counts.data() : nullptr, optical ? &O : nullptr, optical ? &h->opt_ms : nullptr, barcode);
 		for (size_t k = 0; rc == BMH_OK && k < h->store.lib_info.size() && k / 3 < n_lib; ++k) h->lib_counts[BDP_N_COUNTS * (k / 3) + BDP_SECSUP + k % 3] = h->store.lib_info[k];
 		if (trace && h->a.markdup) fprintf(stderr, "[aligner] duplicate marking: %.0f bytes of ordinals and entries came down with the batches\n", h->dup_times[2]);
 		if (trace) fprintf(stderr, "[aligner] sorted output: %zu runs (%llu spilled) merged in %.1f ms\n", h->store.runs.size(), (unsigned long long)h->store.spilled, (now_s() - tm0) * 1e3);
 		h->store.clear();
-		if (rc == BMH_OK) { h->sort_ix.valid = true; h->dup_valid = h->a.markdup; h->opt_valid = optical; }
+		if (rc == BMH_OK) { h->sort_ix.valid = true; h->dup_valid = h->a.markdup; h->opt_valid = optical; h->bc_valid = barcode; }
 		return rc;
 	}
 };

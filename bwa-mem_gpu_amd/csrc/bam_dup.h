@@ -32,25 +32,37 @@ int bdp_group_refused(uint32_t rec, int st, const char *fn);
 // secondary or supplementary and the unmapped records.  Not BMH_OK (message set): the first record begins no template, or a paired template lacks a primary line
 // G (or NULL): the run's read groups -- the entries carry their templates' libraries; a first record without RG:Z, or with an ID G does not hold, is refused too
 // locs (or NULL): optical duplicates are counted -- every template's location (csrc/bam_dup_core.h) beside its entry
+// bc, bcs (or NULL): barcodes are compared -- every template's barcode word beside its entry; a first record whose barcode tag is of another type than Z, or whose
+// tags cannot be walked, is refused by its index
 int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn,
-                     const bdp_groups_t *G = nullptr, std::vector<bdp_loc_t> *locs = nullptr);
+                     const bdp_groups_t *G = nullptr, std::vector<bdp_loc_t> *locs = nullptr, const bdp_bc_t *bc = nullptr, std::vector<uint64_t> *bcs = nullptr);
+// barcode_mode and tag as the entry points take them -> *bc; BMH_EINVAL with a message: a mode other than 0, 1, 2; a tag that is not [A-Za-z][A-Za-z0-9], RG, or one
+// the writer produces itself (NM MD AS XS SA XA pa)
+int bdp_barcode_check(int barcode_mode, const char *tag, const char *fn, bdp_bc_t *bc);
+// the message of a template whose first record `rec` bdp_barcode refuses (st: BDP_E_BC_TYPE or BDP_E_BC_WALK)
+int bdp_barcode_refused(uint32_t rec, int st, const char *fn);
+// the templates without a barcode among B [T]
+uint64_t bdp_no_barcode(const uint64_t *B, uint64_t T);
 // the optical step of a run: the distance (0 .. 2^31 - 1), the largest set examined, and where its three counts go (BDP_OPT_*): out [3], lib_out [3 * n_lib] or NULL
 struct bdp_optical_t { int64_t distance; uint32_t max_set; uint64_t *out, *lib_out; };
 // distance and max_set as the entry points take them (max_set 0: BDP_OPT_MAX_SET) -> BMH_EINVAL with a message, or BMH_OK
 int bdp_optical_check(int64_t distance, uint64_t max_set, const char *fn);
 // the optical duplicates among the pairs of E [T] with locations L [T], single-threaded through the clustering core of csrc/bam_dup_core.h (its invariant asserted);
 // n_lib 0: no libraries, lib_out unused
-void bdp_optical_host(const bdp_entry_t *E, const bdp_loc_t *L, uint64_t T, const bdp_optical_t &O, uint32_t n_lib);
+// B [T] (or NULL): the barcode words -- a set is the pairs of one (lo, hi, word)
+void bdp_optical_host(const bdp_entry_t *E, const bdp_loc_t *L, uint64_t T, const bdp_optical_t &O, uint32_t n_lib, const uint64_t *B = nullptr);
 // the decision: bits [(T + 31) / 32]: bit t set when template t is a duplicate; counts [0 .. 4]; lib_counts (or NULL) [BDP_N_COUNTS * n_lib]: every library's own
 // counts, of which the decision fills (and zeroes the rest of) words 0 .. 4
-void bdp_decide_host(const bdp_entry_t *entries, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5], uint32_t n_lib = 0, uint64_t *lib_counts = nullptr);
+// B [T] (or NULL): the barcode words, part of the pairs' and the fragments' keys
+void bdp_decide_host(const bdp_entry_t *entries, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5], uint32_t n_lib = 0, uint64_t *lib_counts = nullptr, const uint64_t *B = nullptr);
 // words 5 .. 7 of every library's counts += the secondary or supplementary records, the unmapped records and the templates of the stream (off [n + 1], tpl [n]: the
 // records' template ordinals, E [T]: entries made with read groups)
 void bdp_lib_tally_host(const uint8_t *recs, const uint64_t *off, uint32_t n, const uint32_t *tpl, const bdp_entry_t *E, uint64_t T, uint32_t n_lib, uint64_t *lib_counts);
 // the whole of it on a walked stream: flags set in place; T, lib_counts [BDP_N_COUNTS * T->n_lib] (or NULL): with read groups, and every library's counts
 // O (or NULL): count the optical duplicates too
+// bc (or NULL): compare barcodes; *no_barcode (or NULL): the templates without one
 int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn, const bdp_table_t *T = nullptr, uint64_t *lib_counts = nullptr,
-                     const bdp_optical_t *O = nullptr);
+                     const bdp_optical_t *O = nullptr, const bdp_bc_t *bc = nullptr, uint64_t *no_barcode = nullptr);
 
 // csrc/bam_dup_kernels.hip
 struct bdp_dev_t;                                                  // device buffers of the batches' entries, the decision and the bitmap; kept between calls
@@ -62,8 +74,10 @@ void bdp_dev_free(bdp_dev_t *d);
 // table does not hold (0xffffffff: none)
 enum { BDP_INFO_WORDS = 8 };
 // d_locs (or NULL): optical duplicates are counted -- *d_locs [as many as entries]: every template's location, written by the lane that makes its entry
+// bc, d_bcs (or NULL): barcodes are compared -- *d_bcs [as many as entries]: every template's barcode word, written by the lane that makes its entry; *d_info [6],
+// [7]: the first template's first record + 1 whose barcode tag is of another type than Z / whose tags cannot be walked (0xffffffff: none)
 int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint32_t **d_tpl,
-                     const bdp_entry_t **d_entries, const uint32_t **d_info, const bdp_loc_t **d_locs = nullptr);
+                     const bdp_entry_t **d_entries, const uint32_t **d_info, const bdp_loc_t **d_locs = nullptr, const bdp_bc_t *bc = nullptr, const uint64_t **d_bcs = nullptr);
 // a batch whose templates are of several libraries (a run that keeps its input's read groups), after bdp_batch_device on the same batch: *d_lib3 [3 * n_lib] -- every
 // library's secondary / supplementary records, unmapped records and templates, a record counted under the library of its template's entry (bdp_lib_tally_host's
 // three, per batch) -- in d until its next call.  n_lib <= BDP_MAX_LIBS.
@@ -72,15 +86,17 @@ int bdp_batch_lib_counts_device(bdp_dev_t *d, const uint8_t *d_recs, const uint6
 int bdp_dev_set_groups(bdp_dev_t *d, const bdp_table_t *T, void *stream);
 // the message of a batch whose info [1] is not 0
 int bdp_batch_refused(uint32_t n, uint32_t bad, const char *fn);
-// the verdict on a batch's info words (n records; groups: all BDP_INFO_WORDS were read): BMH_OK, or the message of the first refused record
-int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *fn);
+// the verdict on a batch's info words (n records; groups, barcode: all BDP_INFO_WORDS were read): BMH_OK, or the message of the first refused record
+int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *fn, bool barcode = false);
 // every template's entry (host) -> the bitmap, kept in d for bdp_flag_device, and counts [0 .. 4]
 // n_records: the records of the final sort that follows (csrc/bam_sort_kernels.hip: 24 bytes each and the sort's work space) -- the decision's buffers are freed
 // before that sort allocates, so one check of the larger of the two needs refuses here what either would refuse
 // n_lib, lib_counts [BDP_N_COUNTS * n_lib] (or 0, NULL): words 0 .. 4 of every library's counts, from the entries' library bytes and the bitmap (the other words zeroed)
 // O, locs [T] (host; or NULL): the optical step after the pair pass, on the pairs as that pass left them -- sets of equal keys next to each other.  opt_ms (or NULL)
 // += its milliseconds (events around its kernels, the upload of the locations included)
+// bcs [T] (host; or NULL): the templates' barcode words -- one more stable radix pass on them in the pair pass and in the fragment pass, and the word compared where
+// keys are: 8 bytes per template more on the device
 int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records = 0, uint32_t n_lib = 0, uint64_t *lib_counts = nullptr,
-                      const bdp_optical_t *O = nullptr, const bdp_loc_t *locs = nullptr, double *opt_ms = nullptr);
+                      const bdp_optical_t *O = nullptr, const bdp_loc_t *locs = nullptr, double *opt_ms = nullptr, const uint64_t *bcs = nullptr);
 // records d_recs at d_off [n] (device; all inside `total` bytes) whose global template ordinals are tord [n] (host): byte 19 |= 0x04 where the bitmap says so
 int bdp_flag_device(bdp_dev_t *d, uint8_t *d_recs, const uint64_t *d_off, const uint32_t *tord, uint32_t n, uint64_t total, void *stream);

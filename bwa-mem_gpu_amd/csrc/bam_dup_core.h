@@ -37,14 +37,23 @@
 //               components, whichever member stays.  In total and per library; fragments never count
 //     size      bdp_library_size: Picard's estimateLibrarySize
 //
-// Nothing is removed, no DT:Z tag is written, keys know no UMI, the names' pattern is fixed.
+//   barcode   only when the run asks for it (a tag XX, or the read name): templates with different molecular barcodes (UMIs) are no duplicates of each other
+//     value     of a template, from its first record (the one the library and the location come from).  Tag: the value of tag XX of type Z, verbatim -- no case
+//               folding, no splitting at '-': a dual UMI ACGT-TTGA is one value.  Name: the bytes behind the last ':' of the read name (without the NUL).  An
+//               absent tag, an empty value, a name without ':' and a name that ends in ':' all mean no barcode; templates without one are comparable with each
+//               other and with no barcoded template.  A tag XX of another type, and tags that cannot be walked, are refused by the record's index
+//     word      64-bit FNV-1a over the value's bytes; 0 is kept for no barcode, so a value that hashes to 0 takes 1.  Words are compared, never strings
+//     pairs     key (lo, hi, word); fragments: key (end word, word) -- a fragment is a duplicate through a pair's end only if that pair has its word
+//     optical   a set is the pairs of one (lo, hi, word); in name mode the location is parsed from the name without its last field and that field's ':'
+//
+// Nothing is removed, no DT:Z tag is written, barcodes are compared exactly (no grouping by edit distance), the names' pattern is fixed.
 #pragma once
 #include "bam_sort_core.h"
 
 enum { BDP_NONE = 0, BDP_FRAG = 1, BDP_PAIR = 2, BDP_QMIN = 15 };
 enum { BDP_LIB_SHIFT = 56, BDP_MAX_LIBS = 255, BDP_MAX_REF = 1 << 24, BDP_MAX_CONTIG = (1 << 30) - (1 << 24) };
 // what bdp_entry_lib says of a template
-enum { BDP_E_OK = 0, BDP_E_TEMPLATE = 1, BDP_E_NO_RG = 2, BDP_E_RG_UNKNOWN = 3 };
+enum { BDP_E_OK = 0, BDP_E_TEMPLATE = 1, BDP_E_NO_RG = 2, BDP_E_RG_UNKNOWN = 3, BDP_E_BC_TYPE = 4, BDP_E_BC_WALK = 5 };
 
 // a run's read groups: the IDs back to back (no terminators) with offsets id_off [n + 1], and every group's library index (below BDP_MAX_LIBS)
 struct bdp_groups_t { const char *ids; const uint32_t *id_off; const uint8_t *lib; uint32_t n; };
@@ -130,20 +139,28 @@ BSR_FN uint64_t bdp_frag_word(const bdp_entry_t &e, uint32_t ordinal) { return b
 
 BSR_FN uint32_t bdp_aux_width(uint8_t type) { return type == 'A' || type == 'c' || type == 'C' ? 1u : type == 's' || type == 'S' ? 2u : type == 'i' || type == 'I' || type == 'f' ? 4u : 0u; }
 
-// the value of the record's RG:Z tag (its length in *len), found by a walk over the tags behind the qualities; nullptr: none, or tags that cannot be walked
-BSR_FN const uint8_t *bdp_rg_tag(const uint8_t *rec, uint64_t sz, uint32_t *len)
+// what bdp_aux_z says of a record's tags
+enum { BDP_AUX_FOUND = 0, BDP_AUX_ABSENT = 1, BDP_AUX_TYPE = 2, BDP_AUX_WALK = 3 };
+
+// the value of the record's first tag t0 t1 of type Z (its length in *len), found by a walk over the tags behind the qualities.  *st: found; absent; a tag of
+// that name and another type came first (the walk goes on: the value, if one follows, is still returned); or tags that cannot be walked (a cut tag, an unknown
+// type, bytes left over) -- nullptr then, and when absent
+BSR_FN const uint8_t *bdp_aux_z(const uint8_t *rec, uint64_t sz, uint8_t t0, uint8_t t1, uint32_t *len, int *st)
 {
+	*st = BDP_AUX_WALK;
 	if (sz < BSR_FIXED || !bdp_record_whole(rec, sz)) return nullptr;
 	const uint64_t l_seq = bsr_u32(rec + 20);
 	uint64_t p = (uint64_t)BSR_FIXED + rec[12] + 4ull * bsr_u16(rec + 16) + (l_seq + 1) / 2 + l_seq;
+	bool other = false;
 	while (p + 3 <= sz) {
-		const uint8_t t0 = rec[p], t1 = rec[p + 1], ty = rec[p + 2];
+		const bool hit = rec[p] == t0 && rec[p + 1] == t1;
+		const uint8_t ty = rec[p + 2];
 		p += 3;
 		if (ty == 'Z' || ty == 'H') {
 			uint64_t e = p;
 			while (e < sz && rec[e]) ++e;
 			if (e >= sz) return nullptr;
-			if (t0 == 'R' && t1 == 'G' && ty == 'Z') { *len = (uint32_t)(e - p); return rec + p; }
+			if (hit && ty == 'Z') { *len = (uint32_t)(e - p); *st = other ? BDP_AUX_TYPE : BDP_AUX_FOUND; return rec + p; }
 			p = e + 1;
 		} else if (ty == 'B') {
 			if (p + 5 > sz) return nullptr;
@@ -155,8 +172,17 @@ BSR_FN const uint8_t *bdp_rg_tag(const uint8_t *rec, uint64_t sz, uint32_t *len)
 			if (!w) return nullptr;
 			p += w;
 		}
+		other = other || hit;
 	}
+	if (p == sz) *st = other ? BDP_AUX_TYPE : BDP_AUX_ABSENT;
 	return nullptr;
+}
+
+// the value of the record's RG:Z tag (its length in *len); nullptr: none, or tags that cannot be walked
+BSR_FN const uint8_t *bdp_rg_tag(const uint8_t *rec, uint64_t sz, uint32_t *len)
+{
+	int st;
+	return bdp_aux_z(rec, sz, 'R', 'G', len, &st);
 }
 
 // the row of the record's read group in the table (compared row by row: a run has a handful of groups); -1: no RG:Z tag, -2: an ID the table does not hold
@@ -234,13 +260,58 @@ BSR_FN bool bdp_name_location(const uint8_t *name, uint32_t len, uint32_t out[3]
 	return true;
 }
 
-// the location of the template whose first record is rec (its name vouched for by bsr_record_bytes)
-BSR_FN bdp_loc_t bdp_location(const uint8_t *rec, uint32_t role, uint32_t row)
+// ---- barcodes
+
+// where a run's barcodes come from: mode (BDP_BC_*) and, for a tag, its two letters.  Passed by value to the kernel
+enum { BDP_BC_OFF = 0, BDP_BC_TAG = 1, BDP_BC_NAME = 2 };
+struct bdp_bc_t { uint32_t mode; uint8_t t0, t1; };
+
+// the barcode word of a value of n bytes: 64-bit FNV-1a, one walk over the bytes; 0 is no barcode, so an empty value gives 0 and a value that hashes to 0 gives 1
+BSR_FN uint64_t bdp_barcode_word(const uint8_t *v, uint64_t n)
+{
+	if (!n) return 0;
+	uint64_t h = 0xcbf29ce484222325ull;
+	for (uint64_t i = 0; i < n; ++i) h = (h ^ v[i]) * 0x100000001b3ull;
+	return h ? h : 1ull;
+}
+
+// where the last field of a read name (len bytes, no NUL) begins: behind its last ':'; len + 1 for a name without one (no barcode, nothing to cut)
+BSR_FN uint32_t bdp_name_last_field(const uint8_t *name, uint32_t len)
+{
+	uint32_t a = len + 1;
+	for (uint32_t i = 0; i < len; ++i) if (name[i] == ':') a = i + 1;
+	return a;
+}
+
+// the length of the name the location parser is given: in name mode the name without its last field and that field's ':'
+BSR_FN uint32_t bdp_located_name_len(const uint8_t *name, uint32_t len, bool cut) { const uint32_t a = cut ? bdp_name_last_field(name, len) : len + 1; return a <= len ? a - 1 : len; }
+
+// the barcode word of the template whose first record is rec (sz bytes; its name vouched for by bsr_record_bytes) -> *word; BDP_AUX_FOUND, or BDP_AUX_TYPE /
+// BDP_AUX_WALK: the record is refused
+BSR_FN int bdp_barcode(const uint8_t *rec, uint64_t sz, const bdp_bc_t &bc, uint64_t *word)
+{
+	*word = 0;
+	if (bc.mode == BDP_BC_NAME) {
+		if (sz < BSR_FIXED || sz - BSR_FIXED < rec[12]) return BDP_AUX_WALK;
+		const uint32_t ln = rec[12] ? rec[12] - 1u : 0u, a = bdp_name_last_field(rec + BSR_FIXED, ln);
+		if (a <= ln) *word = bdp_barcode_word(rec + BSR_FIXED + a, ln - a);
+		return BDP_AUX_FOUND;
+	}
+	uint32_t len = 0; int st;                                           // (a record holds fewer than 2^32 bytes)
+	const uint8_t *v = bdp_aux_z(rec, sz, bc.t0, bc.t1, &len, &st);
+	if (st == BDP_AUX_TYPE || st == BDP_AUX_WALK) return st;
+	if (v) *word = bdp_barcode_word(v, len);
+	return BDP_AUX_FOUND;
+}
+
+// the location of the template whose first record is rec (its name vouched for by bsr_record_bytes); cut: the barcode is the name's last field, which the parser
+// does not see
+BSR_FN bdp_loc_t bdp_location(const uint8_t *rec, uint32_t role, uint32_t row, bool cut = false)
 {
 	bdp_loc_t l; l.x = l.y = 0; l.tile = 0; l.rg = (uint16_t)row; l.flags = (uint16_t)(role ? BDP_LOC_ROLE : 0);
 	uint32_t v[3];
 	const uint32_t ln = rec[12];
-	if (ln && bdp_name_location(rec + BSR_FIXED, ln - 1, v)) { l.tile = v[0]; l.x = (int32_t)v[1]; l.y = (int32_t)v[2]; l.flags |= BDP_LOC_LOCATED; }
+	if (ln && bdp_name_location(rec + BSR_FIXED, bdp_located_name_len(rec + BSR_FIXED, ln - 1, cut), v)) { l.tile = v[0]; l.x = (int32_t)v[1]; l.y = (int32_t)v[2]; l.flags |= BDP_LOC_LOCATED; }
 	return l;
 }
 

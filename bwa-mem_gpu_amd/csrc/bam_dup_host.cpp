@@ -24,15 +24,43 @@ int bdp_group_refused(uint32_t rec, int st, const char *fn)
 	return BMH_EINVAL;
 }
 
-int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *fn)
+int bdp_barcode_refused(uint32_t rec, int st, const char *fn)
+{
+	if (st == BDP_E_BC_TYPE) bmh_set_error("%s: duplicate marking: record %u begins a template and carries the barcode tag with a type other than Z", fn, rec);
+	else bmh_set_error("%s: duplicate marking: record %u begins a template and its tags cannot be walked to the barcode tag (a cut tag, an unknown type, or bytes left over)", fn, rec);
+	return BMH_EINVAL;
+}
+
+int bdp_barcode_check(int mode, const char *tag, const char *fn, bdp_bc_t *bc)
+{
+	bc->mode = BDP_BC_OFF; bc->t0 = bc->t1 = 0;
+	if (mode != BDP_BC_OFF && mode != BDP_BC_TAG && mode != BDP_BC_NAME) { bmh_set_error("%s: barcode mode %d (0: none, 1: a tag, 2: the read name)", fn, mode); return BMH_EINVAL; }
+	if (mode == BDP_BC_TAG) {
+		if (!tag) { bmh_set_error("%s: a barcode tag has two characters, [A-Za-z][A-Za-z0-9]", fn); return BMH_EINVAL; }
+		const char a = tag[0], b = a ? tag[1] : 0;
+		const bool ok = ((a >= 'A' && a <= 'Z') || (a >= 'a' && a <= 'z')) && ((b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z') || (b >= '0' && b <= '9'));
+		if (!ok) { bmh_set_error("%s: a barcode tag has two characters, [A-Za-z][A-Za-z0-9]", fn); return BMH_EINVAL; }
+		static const char own[8][3] = {"RG", "NM", "MD", "AS", "XS", "SA", "XA", "pa"};
+		for (const char *o : own)
+			if (a == o[0] && b == o[1]) { bmh_set_error("%s: tag %c%c cannot be a barcode: RG names the read group, and NM MD AS XS SA XA pa are written by the aligner itself", fn, a, b); return BMH_EINVAL; }
+		bc->t0 = (uint8_t)a; bc->t1 = (uint8_t)b;
+	}
+	bc->mode = (uint32_t)mode;
+	return BMH_OK;
+}
+
+uint64_t bdp_no_barcode(const uint64_t *B, uint64_t T) { uint64_t c = 0; for (uint64_t t = 0; t < T; ++t) c += B[t] == 0; return c; }
+
+int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *fn, bool barcode)
 {
 	if (!n) return BMH_OK;
 	// (the smallest record index wins, as a walk from the front would find it)
 	if (info[1] == 0) return bdp_batch_refused(n, n + 1, fn);
 	uint32_t bad = info[1]; int st = BDP_E_TEMPLATE;
 	if (groups) for (int k = 0; k < 2; ++k) if (info[4 + k] < bad) { bad = info[4 + k]; st = k ? BDP_E_RG_UNKNOWN : BDP_E_NO_RG; }
+	if (barcode) for (int k = 0; k < 2; ++k) if (info[6 + k] < bad) { bad = info[6 + k]; st = k ? BDP_E_BC_WALK : BDP_E_BC_TYPE; }
 	if (bad == 0xffffffffu) return BMH_OK;
-	return st == BDP_E_TEMPLATE ? bdp_batch_refused(n, bad, fn) : bdp_group_refused(bad - 1, st, fn);
+	return st == BDP_E_TEMPLATE ? bdp_batch_refused(n, bad, fn) : st >= BDP_E_BC_TYPE ? bdp_barcode_refused(bad - 1, st, fn) : bdp_group_refused(bad - 1, st, fn);
 }
 
 int bdp_table_make(bdp_table_t &T, const char *const *ids, const int32_t *lib, int n, const char *fn)
@@ -64,10 +92,12 @@ int bdp_refs_fit(const uint8_t *recs, const uint64_t *off, uint32_t n, const cha
 }
 
 int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn, const bdp_groups_t *G,
-                     std::vector<bdp_loc_t> *locs)
+                     std::vector<bdp_loc_t> *locs, const bdp_bc_t *bc, std::vector<uint64_t> *bcs)
 {
 	tpl.resize(n); entries.clear();
 	if (locs) locs->clear();
+	if (bc && (bc->mode == BDP_BC_OFF || !bcs)) bc = nullptr;
+	if (bcs) bcs->clear();
 	if (n && !bdp_head(bsr_flag(recs + off[0]))) return bdp_batch_refused(n, n + 1, fn);
 	std::vector<uint32_t> start;
 	for (uint32_t i = 0; i < n; ++i) {
@@ -80,41 +110,48 @@ int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::
 	if (start.size() >= 1ull << 31) { bmh_set_error("%s: duplicate marking: 2^31 templates", fn); return BMH_EINVAL; }
 	entries.resize(start.size());
 	if (locs) locs->resize(start.size());
+	if (bc) bcs->resize(start.size());
 	for (size_t t = 0; t < start.size(); ++t) {
 		const uint32_t a = start[t], b = t + 1 < start.size() ? start[t + 1] : n;
 		uint32_t role = 0, row = 0;
 		const int st = G ? bdp_entry_lib(recs, off, a, b, *G, &entries[t], &role, &row) : bdp_entry(recs, off, a, b, &entries[t], &role) ? BDP_E_OK : BDP_E_TEMPLATE;
 		if (st == BDP_E_TEMPLATE) return bdp_batch_refused(n, a + 1, fn);
 		if (st != BDP_E_OK) return bdp_group_refused(a, st, fn);
-		if (locs) (*locs)[t] = bdp_location(recs + off[a], role, row);
+		if (locs) (*locs)[t] = bdp_location(recs + off[a], role, row, bc && bc->mode == BDP_BC_NAME);
+		if (bc) {
+			const int bs = bdp_barcode(recs + off[a], off[a + 1] - off[a], *bc, &(*bcs)[t]);
+			if (bs != BDP_AUX_FOUND) return bdp_barcode_refused(a, bs == BDP_AUX_TYPE ? BDP_E_BC_TYPE : BDP_E_BC_WALK, fn);
+		}
 	}
 	return BMH_OK;
 }
 
-void bdp_decide_host(const bdp_entry_t *E, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5], uint32_t n_lib, uint64_t *lib_counts)
+void bdp_decide_host(const bdp_entry_t *E, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5], uint32_t n_lib, uint64_t *lib_counts, const uint64_t *B)
 {
+	auto bc = [&](uint32_t t) { return B ? B[t] : 0ull; };              // (without barcodes every word is equal: the keys are those of old)
 	bits.assign((size_t)((T + 31) / 32), 0u);
 	for (int k = 0; k < 5; ++k) counts[k] = 0;
 	auto mark = [&](uint32_t t) { bits[t >> 5] |= 1u << (t & 31); counts[BDP_FLAGGED] += bdp_n_rec(E[t]); };
 	std::vector<uint32_t> pairs;
-	struct item_t { uint64_t word, rank; uint32_t t; };
+	struct item_t { uint64_t word, bc, rank; uint32_t t; };
 	std::vector<item_t> items;
 	for (uint64_t t = 0; t < T; ++t) {
 		const uint32_t k = bdp_kind(E[t]);
-		if (k == BDP_PAIR) { pairs.push_back((uint32_t)t); items.push_back({E[t].lo, 0, (uint32_t)t}); items.push_back({E[t].hi, 0, (uint32_t)t}); }
-		else if (k == BDP_FRAG) items.push_back({E[t].lo, bdp_frag_word(E[t], (uint32_t)t), (uint32_t)t});
+		if (k == BDP_PAIR) { pairs.push_back((uint32_t)t); items.push_back({E[t].lo, bc((uint32_t)t), 0, (uint32_t)t}); items.push_back({E[t].hi, bc((uint32_t)t), 0, (uint32_t)t}); }
+		else if (k == BDP_FRAG) items.push_back({E[t].lo, bc((uint32_t)t), bdp_frag_word(E[t], (uint32_t)t), (uint32_t)t});
 	}
 	counts[BDP_PAIRS] = pairs.size(); counts[BDP_FRAGS] = items.size() - 2 * pairs.size();
 	std::sort(pairs.begin(), pairs.end(), [&](uint32_t a, uint32_t b) {
 		if (E[a].lo != E[b].lo) return E[a].lo < E[b].lo;
 		if (E[a].hi != E[b].hi) return E[a].hi < E[b].hi;
+		if (bc(a) != bc(b)) return bc(a) < bc(b);
 		return bdp_rank_word(E[a], a) < bdp_rank_word(E[b], b);
 	});
 	for (size_t i = 1; i < pairs.size(); ++i)
-		if (E[pairs[i]].lo == E[pairs[i - 1]].lo && E[pairs[i]].hi == E[pairs[i - 1]].hi) { mark(pairs[i]); ++counts[BDP_DUP_PAIRS]; }
-	std::sort(items.begin(), items.end(), [](const item_t &a, const item_t &b) { return a.word != b.word ? a.word < b.word : a.rank < b.rank; });
+		if (E[pairs[i]].lo == E[pairs[i - 1]].lo && E[pairs[i]].hi == E[pairs[i - 1]].hi && bc(pairs[i]) == bc(pairs[i - 1])) { mark(pairs[i]); ++counts[BDP_DUP_PAIRS]; }
+	std::sort(items.begin(), items.end(), [](const item_t &a, const item_t &b) { return a.word != b.word ? a.word < b.word : a.bc != b.bc ? a.bc < b.bc : a.rank < b.rank; });
 	for (size_t i = 0, first = 0; i < items.size(); ++i) {
-		if (i && items[i].word != items[i - 1].word) first = i;
+		if (i && (items[i].word != items[i - 1].word || items[i].bc != items[i - 1].bc)) first = i;
 		if (bdp_kind(E[items[i].t]) != BDP_FRAG) continue;
 		if (bdp_kind(E[items[first].t]) == BDP_PAIR || i != first) { mark(items[i].t); ++counts[BDP_DUP_FRAGS]; }
 	}
@@ -136,20 +173,21 @@ int bdp_optical_check(int64_t distance, uint64_t max_set, const char *fn)
 	return BMH_OK;
 }
 
-void bdp_optical_host(const bdp_entry_t *E, const bdp_loc_t *L, uint64_t T, const bdp_optical_t &O, uint32_t n_lib)
+void bdp_optical_host(const bdp_entry_t *E, const bdp_loc_t *L, uint64_t T, const bdp_optical_t &O, uint32_t n_lib, const uint64_t *B)
 {
+	auto bc = [&](uint32_t t) { return B ? B[t] : 0ull; };
 	for (int k = 0; k < BDP_OPT_N; ++k) O.out[k] = 0;
 	if (!O.lib_out) n_lib = 0;
 	for (uint32_t k = 0; k < BDP_OPT_N * n_lib; ++k) O.lib_out[k] = 0;
 	auto add = [&](uint32_t t, int k, uint64_t v) { O.out[k] += v; if (bdp_lib_of(E[t]) < n_lib) O.lib_out[BDP_OPT_N * (size_t)bdp_lib_of(E[t]) + k] += v; };
 	std::vector<uint32_t> pairs;
 	for (uint64_t t = 0; t < T; ++t) if (bdp_kind(E[t]) == BDP_PAIR) { pairs.push_back((uint32_t)t); if (L[t].flags & BDP_LOC_LOCATED) add((uint32_t)t, BDP_OPT_LOCATED, 1); }
-	std::sort(pairs.begin(), pairs.end(), [&](uint32_t a, uint32_t b) { return E[a].lo != E[b].lo ? E[a].lo < E[b].lo : E[a].hi != E[b].hi ? E[a].hi < E[b].hi : a < b; });
+	std::sort(pairs.begin(), pairs.end(), [&](uint32_t a, uint32_t b) { return E[a].lo != E[b].lo ? E[a].lo < E[b].lo : E[a].hi != E[b].hi ? E[a].hi < E[b].hi : bc(a) != bc(b) ? bc(a) < bc(b) : a < b; });
 	// the located members of the sets of 2 .. max_set pairs, every one with the index of its set's first pair
 	struct member_t { uint64_t w2, w1; uint32_t t; };
 	std::vector<member_t> mem;
 	for (size_t a = 0, b; a < pairs.size(); a = b) {
-		for (b = a + 1; b < pairs.size() && E[pairs[b]].lo == E[pairs[a]].lo && E[pairs[b]].hi == E[pairs[a]].hi;) ++b;
+		for (b = a + 1; b < pairs.size() && E[pairs[b]].lo == E[pairs[a]].lo && E[pairs[b]].hi == E[pairs[a]].hi && bc(pairs[b]) == bc(pairs[a]);) ++b;
 		if (b - a < 2) continue;
 		if (b - a > O.max_set) { add(pairs[a], BDP_OPT_SKIPPED, 1); continue; }
 		for (size_t i = a; i < b; ++i) if (L[pairs[i]].flags & BDP_LOC_LOCATED) mem.push_back({bdp_opt_word2((uint32_t)a, L[pairs[i]]), bdp_opt_word1(L[pairs[i]]), pairs[i]});
@@ -177,8 +215,12 @@ void bdp_lib_tally_host(const uint8_t *recs, const uint64_t *off, uint32_t n, co
 	}
 }
 
-int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn, const bdp_table_t *T, uint64_t *lib_counts, const bdp_optical_t *O)
+int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn, const bdp_table_t *T, uint64_t *lib_counts, const bdp_optical_t *O,
+                     const bdp_bc_t *bc, uint64_t *no_barcode)
 {
+	if (bc && bc->mode == BDP_BC_OFF) bc = nullptr;
+	if (no_barcode) *no_barcode = 0;
+	std::vector<uint64_t> Bw;
 	const uint32_t n = (uint32_t)(off.size() - 1);
 	for (int k = 0; k < BDP_N_COUNTS; ++k) counts[k] = 0;
 	for (uint32_t i = 0; i < n; ++i)
@@ -190,18 +232,20 @@ int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t c
 	if (T) G = T->view();
 	int rc = T ? bdp_refs_fit(recs, off.data(), n, fn) : BMH_OK;
 	if (rc != BMH_OK) return rc;
-	rc = bdp_entries_host(recs, off.data(), n, tpl, E, counts + BDP_SECSUP, fn, T ? &G : nullptr, O ? &locs : nullptr);
+	rc = bdp_entries_host(recs, off.data(), n, tpl, E, counts + BDP_SECSUP, fn, T ? &G : nullptr, O ? &locs : nullptr, bc, bc ? &Bw : nullptr);
 	if (rc != BMH_OK) return rc;
 	counts[BDP_TEMPLATES] = E.size();
-	bdp_decide_host(E.data(), E.size(), bits, counts, T ? T->n_lib : 0, T ? lib_counts : nullptr);
-	if (O) bdp_optical_host(E.data(), locs.data(), E.size(), *O, T ? T->n_lib : 0);
+	if (bc && no_barcode) *no_barcode = bdp_no_barcode(Bw.data(), Bw.size());
+	bdp_decide_host(E.data(), E.size(), bits, counts, T ? T->n_lib : 0, T ? lib_counts : nullptr, bc ? Bw.data() : nullptr);
+	if (O) bdp_optical_host(E.data(), locs.data(), E.size(), *O, T ? T->n_lib : 0, bc ? Bw.data() : nullptr);
 	if (T && lib_counts) bdp_lib_tally_host(recs, off.data(), n, tpl.data(), E.data(), E.size(), T->n_lib, lib_counts);
 	for (uint32_t i = 0; i < n; ++i) if (bits[tpl[i] >> 5] >> (tpl[i] & 31) & 1u) recs[off[i] + 19] |= 0x04;
 	return BMH_OK;
 }
 
 #ifndef BDP_STANDALONE
-static int markdup_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_table_t *T, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, const bdp_optical_t *O = nullptr)
+static int markdup_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_table_t *T, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, const bdp_optical_t *O = nullptr,
+                        const bdp_bc_t *bc = nullptr, uint64_t *no_barcode = nullptr)
 {
 	if (!out || !counts || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*out = nullptr;
@@ -211,7 +255,7 @@ static int markdup_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, c
 	uint8_t *o = (uint8_t *)malloc(n_bytes + 1);
 	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
 	if (n_bytes) memcpy(o, recs, n_bytes);
-	if ((rc = bdp_markdup_host(o, off, counts, fn, T, lib_counts, O)) != BMH_OK) { free(o); return rc; }
+	if ((rc = bdp_markdup_host(o, off, counts, fn, T, lib_counts, O, bc, no_barcode)) != BMH_OK) { free(o); return rc; }
 	*out = o;
 	return BMH_OK;
 }
@@ -272,6 +316,49 @@ extern "C" int bmh_bam_dup_locations_host(const uint8_t *recs, uint64_t n_bytes,
 	*locs = o; *n_templates = L.size();
 	return BMH_OK;
 }
+
+extern "C" int bmh_bam_markdup_barcode_host(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, int barcode_mode,
+                                            const char tag[2], uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode)
+{
+	const char *fn = "bmh_bam_markdup_barcode_host";
+	bdp_table_t T; bdp_bc_t bc;
+	if (out) *out = nullptr;
+	int rc = bdp_barcode_check(barcode_mode, tag, fn, &bc);
+	if (rc != BMH_OK) return rc;
+	const bool opt = distance != -1;
+	if (opt && !optical) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (opt && (rc = bdp_optical_check(distance, max_set, fn)) != BMH_OK) return rc;
+	const bool groups = rg_ids || rg_lib || n_groups;
+	if (groups && (rc = bdp_table_make(T, rg_ids, rg_lib, n_groups, fn)) != BMH_OK) return rc;
+	if (opt && groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
+	const bdp_optical_t O = {distance, max_set ? (uint32_t)max_set : (uint32_t)BDP_OPT_MAX_SET, optical, groups ? lib_optical : nullptr};
+	return markdup_host(fn, recs, n_bytes, groups ? &T : nullptr, out, counts, groups ? lib_counts : nullptr, opt ? &O : nullptr, &bc, no_barcode);
+}
+
+extern "C" int bmh_bam_dup_barcodes_host(const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], uint64_t **words, uint64_t *n_templates)
+{
+	const char *fn = "bmh_bam_dup_barcodes_host";
+	if (!words || !n_templates || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	*words = nullptr; *n_templates = 0;
+	bdp_bc_t bc;
+	int rc = bdp_barcode_check(barcode_mode, tag, fn, &bc);
+	if (rc != BMH_OK) return rc;
+	if (bc.mode == BDP_BC_OFF) { bmh_set_error("%s: no barcode source (1: a tag, 2: the read name)", fn); return BMH_EINVAL; }
+	std::vector<uint64_t> off;
+	if ((rc = bsr_walk(recs, n_bytes, -1, off, fn)) != BMH_OK) return rc;
+	const uint32_t n = (uint32_t)(off.size() - 1);
+	for (uint32_t i = 0; i < n; ++i)
+		if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) { bmh_set_error("%s: record %u is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL; }
+	std::vector<uint32_t> tpl; std::vector<bdp_entry_t> E; std::vector<uint64_t> Bw; uint64_t info[2] = {0, 0};
+	if ((rc = bdp_entries_host(recs, off.data(), n, tpl, E, info, fn, nullptr, nullptr, &bc, &Bw)) != BMH_OK) return rc;
+	uint64_t *o = (uint64_t *)malloc(8 * Bw.size() + 8);
+	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+	if (!Bw.empty()) memcpy(o, Bw.data(), 8 * Bw.size());
+	*words = o; *n_templates = Bw.size();
+	return BMH_OK;
+}
+
+extern "C" uint64_t bmh_barcode_word(const uint8_t *value, uint64_t n) { return value || !n ? bdp_barcode_word(value, n) : 0; }
 
 extern "C" int bmh_bam_name_location(const char *name, uint32_t len, uint32_t out[3])
 {

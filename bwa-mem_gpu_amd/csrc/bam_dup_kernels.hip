@@ -18,6 +18,10 @@
 //               lane knows its set's size), the located pairs of the sets of 2 .. max_set compacted through a scan, two stable radix passes (tile and x; then
 //               set head, read group and role), one lane per member walking its x window and uniting in a union-find in global memory (parent [v] <= v:
 //               every find descends; atomicMin halves paths, atomicCAS hooks the larger root under the smaller), members and roots counted per library in LDS
+//   barcodes    only when the run compares them (csrc/bam_dup_core.h): per batch the entries kernel's BC instance also walks the first record's tags to the barcode's
+//               (or its name to the last field), hashes the value in one walk and writes one 64-bit word per template into a side array; at the decision the
+//               words go up once, the pair pass and the fragment pass each take one more stable radix pass on them (LSD order rank, barcode, hi, lo; and
+//               fragment word, barcode, end word), and the lanes that compare keys -- pair decide, run heads, the optical set heads -- compare the word too
 //   per window  one lane per record tests the bitmap through the record's global template ordinal and ORs 0x04 into byte 19 (a byte store: records are unaligned)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,7 +35,7 @@
 #include "bam_ws.h"
 
 struct bdp_dev_t {
-	dev_buf<uint8_t> head, tpl, start, entries, info, tmp, lib3, locs;            // per batch (locs: only when optical duplicates are counted)
+	dev_buf<uint8_t> head, tpl, start, entries, info, tmp, lib3, locs, bcs;       // per batch (locs: only when optical duplicates are counted; bcs: only when barcodes are compared)
 	dev_buf<uint8_t> bits, tord;                                                  // the bitmap of the run, a window's ordinals
 	dev_buf<uint8_t> g_ids, g_off, g_lib; uint32_t g_n = 0;                       // the run's read groups (bdp_dev_set_groups): IDs, their offsets, libraries; 0: none
 	uint64_t n_tpl = 0;                                                     // templates the bitmap covers
@@ -69,9 +73,11 @@ __global__ void __launch_bounds__(256) bdp_starts(const uint32_t *__restrict__ h
 
 // LIB: the run has read groups (G) -- info [4], [5]: the first template without an RG:Z tag / with an unknown ID, as info [1]
 // LOC: optical duplicates are counted -- the lane holds the template's first record and parses its name: locs [t]
-template <bool LIB, bool LOC>
+// BC: barcodes are compared -- the lane walks its first record's tags to the barcode's, or its name to the last field, hashes the value in one walk and writes the
+// word: bcs [t]; info [6], [7]: the first template whose tag is of another type than Z / whose tags cannot be walked, as info [1]
+template <bool LIB, bool LOC, bool BC>
 __global__ void __launch_bounds__(256) bdp_entries(const uint8_t *__restrict__ recs, const uint64_t *__restrict__ off, uint32_t n, uint64_t total, const uint32_t *__restrict__ start,
-                                                   bdp_entry_t *__restrict__ entries, uint32_t *info, bdp_groups_t G, bdp_loc_t *__restrict__ locs)
+                                                   bdp_entry_t *__restrict__ entries, uint32_t *info, bdp_groups_t G, bdp_loc_t *__restrict__ locs, bdp_bc_t bc, uint64_t *__restrict__ bcs)
 {
 	const uint32_t t = blockIdx.x * 256 + threadIdx.x;
 	if (t >= n || t >= info[0] || info[1] == 0) return;
@@ -84,8 +90,16 @@ __global__ void __launch_bounds__(256) bdp_entries(const uint8_t *__restrict__ r
 	entries[t] = e;
 	if (LOC) {
 		bdp_loc_t l; l.x = l.y = 0; l.tile = 0; l.rg = 0; l.flags = 0;
-		if (inside && st == BDP_E_OK) l = bdp_location(recs + off[a], role, row);
+		if (inside && st == BDP_E_OK) l = bdp_location(recs + off[a], role, row, BC && bc.mode == BDP_BC_NAME);
 		locs[t] = l;
+	}
+	if (BC) {
+		uint64_t w = 0;
+		if (inside) {                                                 // (record a lies inside the buffer: off [a + 1] <= off [b] <= total)
+			const int bs = bdp_barcode(recs + off[a], off[a + 1] - off[a], bc, &w);
+			if (bs != BDP_AUX_FOUND) atomicMin(info + (bs == BDP_AUX_TYPE ? 6 : 7), a + 1);
+		}
+		bcs[t] = w;
 	}
 	if (st == BDP_E_TEMPLATE) atomicMin(info + 1, a + 1);
 	else if (LIB && st != BDP_E_OK) atomicMin(info + (st == BDP_E_NO_RG ? 4 : 5), a + 1);
@@ -135,8 +149,18 @@ __global__ void __launch_bounds__(256) bdp_pair_keys(const bdp_entry_t *__restri
 	key[i] = pass == 0 ? bdp_rank_word(e, t) : !pair ? ~0ull : pass == 1 ? e.hi : e.lo;
 }
 
+// a barcode pass's key: the word of the template behind idx [i] (shift 0: a permutation of templates; 1: item ids)
+__global__ void __launch_bounds__(256) bdp_bc_keys(const uint64_t *__restrict__ B, const uint32_t *__restrict__ idx, uint64_t n, int shift, uint64_t *__restrict__ key)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i < n) key[i] = B[idx[i] >> shift];
+}
+
 // counts: [0] pairs [1] fragments [2] duplicate pairs [3] duplicate fragments [4] records flagged
-__global__ void __launch_bounds__(256) bdp_pair_decide(const bdp_entry_t *__restrict__ E, const uint32_t *__restrict__ perm, uint64_t n, uint32_t *bits, unsigned long long *counts)
+// BC: B [template] -- the barcode words, part of the key
+template <bool BC>
+__global__ void __launch_bounds__(256) bdp_pair_decide(const bdp_entry_t *__restrict__ E, const uint32_t *__restrict__ perm, uint64_t n, uint32_t *bits, unsigned long long *counts,
+                                                       const uint64_t *__restrict__ B)
 {
 	__shared__ unsigned long long recs_s;
 	if (threadIdx.x == 0) recs_s = 0;
@@ -148,8 +172,9 @@ __global__ void __launch_bounds__(256) bdp_pair_decide(const bdp_entry_t *__rest
 		const bdp_entry_t e = E[t];
 		pair = bdp_kind(e) == BDP_PAIR;
 		if (pair && i) {
-			const bdp_entry_t p = E[perm[i - 1]];
-			dup = bdp_kind(p) == BDP_PAIR && p.lo == e.lo && p.hi == e.hi;
+			const uint32_t tp = perm[i - 1];
+			const bdp_entry_t p = E[tp];
+			dup = bdp_kind(p) == BDP_PAIR && p.lo == e.lo && p.hi == e.hi && (!BC || B[tp] == B[t]);
 		}
 		if (dup) { atomicOr(bits + (t >> 5), 1u << (t & 31)); atomicAdd(&recs_s, (unsigned long long)bdp_n_rec(e)); }
 	}
@@ -191,10 +216,12 @@ __global__ void __launch_bounds__(256) bdp_frag_keys(const bdp_entry_t *__restri
 }
 
 // word: the sorted end words; hidx [i] = i where a run begins, else 0
-__global__ void __launch_bounds__(256) bdp_run_heads(const uint64_t *__restrict__ word, uint64_t m, uint32_t *__restrict__ hidx)
+// BC: a run is the items of one (end word, barcode word) -- item: the items in sorted order, B [template]
+template <bool BC>
+__global__ void __launch_bounds__(256) bdp_run_heads(const uint64_t *__restrict__ word, uint64_t m, uint32_t *__restrict__ hidx, const uint32_t *__restrict__ item, const uint64_t *__restrict__ B)
 {
 	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-	if (i < m) hidx[i] = i && word[i] != word[i - 1] ? (uint32_t)i : 0u;
+	if (i < m) hidx[i] = i && (word[i] != word[i - 1] || (BC && B[item[i] >> 1] != B[item[i - 1] >> 1])) ? (uint32_t)i : 0u;
 }
 
 // first [i]: the index of the first item of lane i's run (the max-scan of hidx)
@@ -246,13 +273,16 @@ __global__ void __launch_bounds__(256) bdp_lib_counts(const bdp_entry_t *__restr
 BSR_FN bool bdp_same_set(const bdp_entry_t &a, const bdp_entry_t &b) { return a.lo == b.lo && a.hi == b.hi; }
 
 // head [i] = 1 where a set begins
-__global__ void __launch_bounds__(256) bdp_opt_heads(const bdp_entry_t *__restrict__ E, const uint32_t *__restrict__ perm, uint64_t n, uint32_t *__restrict__ head)
+// BC: a set is the pairs of one (lo, hi, barcode word) -- B [template]
+template <bool BC>
+__global__ void __launch_bounds__(256) bdp_opt_heads(const bdp_entry_t *__restrict__ E, const uint32_t *__restrict__ perm, uint64_t n, uint32_t *__restrict__ head, const uint64_t *__restrict__ B)
 {
 	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
 	if (i >= n) return;
-	const bdp_entry_t e = E[perm[i]];
+	const uint32_t t = perm[i];
+	const bdp_entry_t e = E[t];
 	bool h = bdp_kind(e) == BDP_PAIR;
-	if (h && i) { const bdp_entry_t p = E[perm[i - 1]]; h = !(bdp_kind(p) == BDP_PAIR && bdp_same_set(p, e)); }
+	if (h && i) { const uint32_t tp = perm[i - 1]; const bdp_entry_t p = E[tp]; h = !(bdp_kind(p) == BDP_PAIR && bdp_same_set(p, e) && (!BC || B[tp] == B[t])); }
 	head[i] = h ? 1u : 0u;
 }
 
@@ -377,14 +407,17 @@ bdp_dev_t *bdp_dev_create(void) { return new bdp_dev_t(); }
 void bdp_dev_free(bdp_dev_t *d) { delete d; }
 
 int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint32_t **d_tpl, const bdp_entry_t **d_entries, const uint32_t **d_info,
-                     const bdp_loc_t **d_locs)
+                     const bdp_loc_t **d_locs, const bdp_bc_t *bc, const uint64_t **d_bcs)
 {
+	const bool want_bc = bc && bc->mode != BDP_BC_OFF;
+	if (want_bc && !d_bcs) { bmh_set_error("duplicate marking: internal error: barcodes without a place for their words"); return BMH_EINVAL; }
 	hipStream_t st = (hipStream_t)stream;
 	size_t tb = scan_tmp_bytes<uint32_t, uint32_t, true>((size_t)n + 1);
 	RCK(d->head.need(4 * ((size_t)n + 1))); RCK(d->tpl.need(4 * ((size_t)n + 1))); RCK(d->start.need(4 * ((size_t)n + 2))); RCK(d->entries.need(sizeof(bdp_entry_t) * ((size_t)n + 1)));
 	RCK(d->info.need(4 * BDP_INFO_WORDS)); RCK(d->tmp.need(tb));
 	if (d_locs) RCK(d->locs.need(sizeof(bdp_loc_t) * ((size_t)n + 1)));
-	static const uint32_t init[BDP_INFO_WORDS] = {0u, 0xffffffffu, 0u, 0u, 0xffffffffu, 0xffffffffu, 0u, 0u};
+	if (want_bc) RCK(d->bcs.need(8 * ((size_t)n + 1)));
+	static const uint32_t init[BDP_INFO_WORDS] = {0u, 0xffffffffu, 0u, 0u, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
 	HIPCK(hipMemcpyAsync(d->info.p, init, 4 * BDP_INFO_WORDS, hipMemcpyHostToDevice, st));
 	if (n) {
 		bdp_heads<<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, (uint32_t *)d->head.p, (uint32_t *)d->info.p);
@@ -392,14 +425,23 @@ int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off,
 		bdp_starts<<<blocks(n), 256, 0, st>>>((const uint32_t *)d->head.p, (uint32_t *)d->tpl.p, n, (uint32_t *)d->start.p, (uint32_t *)d->info.p);
 		const bdp_groups_t G = {(const char *)d->g_ids.p, (const uint32_t *)d->g_off.p, (const uint8_t *)d->g_lib.p, d->g_n};
 		const uint32_t *sp = (const uint32_t *)d->start.p; bdp_entry_t *ep = (bdp_entry_t *)d->entries.p; uint32_t *ip = (uint32_t *)d->info.p; bdp_loc_t *lp = (bdp_loc_t *)d->locs.p;
-		if (d_locs) {
-			if (d->g_n) bdp_entries<true, true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp);
-			else bdp_entries<false, true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp);
-		} else if (d->g_n) bdp_entries<true, false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr);
-		else bdp_entries<false, false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr);
+		const bdp_bc_t no_bc = {BDP_BC_OFF, 0, 0};
+		if (want_bc) {
+			uint64_t *bp = (uint64_t *)d->bcs.p;
+			if (d_locs) {
+				if (d->g_n) bdp_entries<true, true, true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, *bc, bp);
+				else bdp_entries<false, true, true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, *bc, bp);
+			} else if (d->g_n) bdp_entries<true, false, true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, *bc, bp);
+			else bdp_entries<false, false, true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, *bc, bp);
+		} else if (d_locs) {
+			if (d->g_n) bdp_entries<true, true, false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, no_bc, nullptr);
+			else bdp_entries<false, true, false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, no_bc, nullptr);
+		} else if (d->g_n) bdp_entries<true, false, false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, no_bc, nullptr);
+		else bdp_entries<false, false, false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, no_bc, nullptr);
 		HIPCK(hipGetLastError());
 	}
 	if (d_locs) *d_locs = (const bdp_loc_t *)d->locs.p;
+	if (want_bc) *d_bcs = (const uint64_t *)d->bcs.p;
 	*d_tpl = (const uint32_t *)d->tpl.p; *d_entries = (const bdp_entry_t *)d->entries.p; *d_info = (const uint32_t *)d->info.p;
 	return BMH_OK;
 }
@@ -434,7 +476,7 @@ int bdp_dev_set_groups(bdp_dev_t *d, const bdp_table_t *T, void *stream)
 }
 
 int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records, uint32_t n_lib, uint64_t *lib_counts,
-                      const bdp_optical_t *O, const bdp_loc_t *locs, double *opt_ms)
+                      const bdp_optical_t *O, const bdp_loc_t *locs, double *opt_ms, const uint64_t *bcs)
 {
 	hipStream_t st = (hipStream_t)stream;
 	for (int k = 0; k < 5; ++k) counts[k] = 0;
@@ -450,14 +492,16 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 	if (T == 0) { HIPCK(hipStreamSynchronize(st)); return BMH_OK; }
 	if (T >= 1ull << 31) { bmh_set_error("duplicate marking: %llu templates: the decision takes fewer than 2^31", (unsigned long long)T); return BMH_EINVAL; }
 	// entries, two key and two value arrays of up to 2 T items (T templates in the pair pass), the item counts and their scan, the sorts' work space, the bitmap:
-	// 24 + 2 * (16 + 8) + 8 = 80 bytes per template and the work space -- freed before the final sort allocates its own
+	// 24 + 2 * (16 + 8) + 8 = 80 bytes per template and the work space -- freed before the final sort allocates its own (with barcodes 88)
 	const size_t M = 2 * (size_t)T; size_t sb = sort_pairs_tmp_bytes<uint64_t, uint32_t>(M); const size_t cb = std::max(std::max(scan_tmp_bytes<uint32_t, uint32_t>((size_t)T + 1), max_scan_tmp_bytes<uint32_t>(M)), sb);
 	size_t fr = 0, tot = 0;
 	HIPCK(hipMemGetInfo(&fr, &tot));
 	// (a buffer is allocated a quarter larger than asked: that is what is counted)
 	// optical duplicates: 16 bytes per template more -- the locations; the step's members, sort words and union-find live in the pair pass's key and value arrays
 	const size_t opt_ask = O ? sizeof(bdp_loc_t) * (size_t)T + 8 * 4 * (size_t)(o_lib ? o_lib : 1) : 0;
-	const size_t ask = sizeof(bdp_entry_t) * (size_t)T + 2 * 8 * M + 2 * 4 * M + 2 * 4 * ((size_t)T + 1) + cb + opt_ask, want = ask + ask / 4 + (64u << 20);
+	// barcodes: 8 bytes per template more -- the words; their two radix passes run in the key and value arrays of the passes beside them
+	const size_t bc_ask = bcs ? 8 * (size_t)T : 0;
+	const size_t ask = sizeof(bdp_entry_t) * (size_t)T + 2 * 8 * M + 2 * 4 * M + 2 * 4 * ((size_t)T + 1) + cb + opt_ask + bc_ask, want = ask + ask / 4 + (64u << 20);
 	// the final sort that follows: keys and ordinals in and out, 24 bytes per record, a quarter more as allocated, and its work space
 	const size_t sort_ask = 24 * (size_t)n_records + (n_records ? sort_pairs_tmp_bytes<uint64_t, uint32_t>((size_t)n_records) : 0), sort_want = sort_ask + sort_ask / 4 + (64u << 20);
 	if (want <= fr && sort_want > fr) {
@@ -466,7 +510,11 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 		return BMH_ENOMEM;
 	}
 	if (want > fr) {
-		if (O) bmh_set_error("sorted BAM: marking the duplicates among %llu templates and counting the optical ones needs %zu bytes of device memory (%zu of them the templates' locations and the optical step's counters), %zu are free (align fewer reads per run, or on a device with more memory)",
+		if (O && bcs) bmh_set_error("sorted BAM: marking the duplicates among %llu templates by their barcodes and counting the optical ones needs %zu bytes of device memory (%zu of them the templates' locations and the optical step's counters, %zu the barcode words), %zu are free (align fewer reads per run, or on a device with more memory)",
+		                            (unsigned long long)T, want, opt_ask + opt_ask / 4, bc_ask + bc_ask / 4, fr);
+		else if (bcs) bmh_set_error("sorted BAM: marking the duplicates among %llu templates by their barcodes needs %zu bytes of device memory (%zu of them the barcode words), %zu are free (align fewer reads per run, or on a device with more memory)",
+		                            (unsigned long long)T, want, bc_ask + bc_ask / 4, fr);
+		else if (O) bmh_set_error("sorted BAM: marking the duplicates among %llu templates and counting the optical ones needs %zu bytes of device memory (%zu of them the templates' locations and the optical step's counters), %zu are free (align fewer reads per run, or on a device with more memory)",
 		                     (unsigned long long)T, want, opt_ask + opt_ask / 4, fr);
 		else bmh_set_error("sorted BAM: marking the duplicates among %llu templates needs %zu bytes of device memory, %zu are free (align fewer reads per run, or on a device with more memory)",
 		              (unsigned long long)T, want, fr);
@@ -483,13 +531,26 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 	unsigned long long *dcnt = (unsigned long long *)dc.p;
 	// the pair pass: after every radix pass vb holds the permutation, swapped into va for the next.  (tmp and sb are sized for M items and serve the sorts of T and
 	// of m <= M items: rocprim takes a work space larger than it asks for, as csrc/bam_sort_kernels.hip's sorts rely on too)
+	// barcodes: the words go up once; one more stable pass on them behind the rank pass (LSD order rank, barcode, hi, lo)
+	dev_buf<uint8_t> dB;
+	if (bcs) {
+		RCK(dB.need(8 * (size_t)T));
+		HIPCK(hipMemcpyAsync(dB.p, bcs, 8 * (size_t)T, hipMemcpyHostToDevice, st));
+	}
+	const uint64_t *B = (const uint64_t *)dB.p;
 	bdp_iota<<<blocks(T), 256, 0, st>>>(va, T);
 	for (int pass = 0; pass < 3; ++pass) {
 		bdp_pair_keys<<<blocks(T), 256, 0, st>>>(dE, va, T, pass, ka);
 		HIPCK(rocprim::radix_sort_pairs(tmp.p, sb, ka, kb, va, vb, (size_t)T, 0, 64, st));
 		std::swap(va, vb);
+		if (pass == 0 && bcs) {
+			bdp_bc_keys<<<blocks(T), 256, 0, st>>>(B, va, T, 0, ka);
+			HIPCK(rocprim::radix_sort_pairs(tmp.p, sb, ka, kb, va, vb, (size_t)T, 0, 64, st));
+			std::swap(va, vb);
+		}
 	}
-	bdp_pair_decide<<<blocks(T), 256, 0, st>>>(dE, va, T, (uint32_t *)d->bits.p, dcnt);
+	if (bcs) bdp_pair_decide<true><<<blocks(T), 256, 0, st>>>(dE, va, T, (uint32_t *)d->bits.p, dcnt, B);
+	else bdp_pair_decide<false><<<blocks(T), 256, 0, st>>>(dE, va, T, (uint32_t *)d->bits.p, dcnt, nullptr);
 	// the optical step, on va as the pair pass left it.  Until the compaction it keeps its words in cnt, base and vb; from there on the pair pass's arrays are free
 	// and take the members (m <= T of them): ka -- sort words in, values in and out; kb -- sort words out, templates, set heads; va -- x, y; vb -- tile, parent
 	dev_buf<uint8_t> dL, oc; std::vector<unsigned long long> h_oc;
@@ -505,7 +566,8 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 		uint32_t *head = (uint32_t *)cnt.p, *sid = (uint32_t *)base.p, *start = vb;      // (start: T + 1 of vb's 2 T places)
 		size_t ib = scan_tmp_bytes<uint32_t, uint32_t, true>((size_t)T + 1);
 		if (ib > cb) { bmh_set_error("duplicate marking: internal error: the optical step's scan asks for %zu bytes of work space, %zu are there", ib, cb); return BMH_EINVAL; }
-		bdp_opt_heads<<<blocks(T), 256, 0, st>>>(dE, va, T, head);
+		if (bcs) bdp_opt_heads<true><<<blocks(T), 256, 0, st>>>(dE, va, T, head, B);
+		else bdp_opt_heads<false><<<blocks(T), 256, 0, st>>>(dE, va, T, head, nullptr);
 		HIPCK(rocprim::inclusive_scan(tmp.p, ib, head, sid, (size_t)T, rocprim::plus<uint32_t>(), st));
 		bdp_opt_starts<<<blocks(T), 256, 0, st>>>(dE, va, T, sid, start);
 		bdp_opt_members<<<blocks(T), 256, 4 * 2 * nl, st>>>(dE, L, va, T, sid, start, O->max_set, o_lib, head, (unsigned long long *)oc.p);
@@ -548,11 +610,17 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 			bdp_frag_keys<<<blocks(m), 256, 0, st>>>(dE, va, m, pass, ka);
 			HIPCK(rocprim::radix_sort_pairs(tmp.p, sb, ka, kb, va, vb, (size_t)m, 0, 64, st));
 			std::swap(va, vb);
+			if (pass == 0 && bcs) {                                       // (the items carry their templates' words: LSD order frag word, barcode, end word)
+				bdp_bc_keys<<<blocks(m), 256, 0, st>>>(B, va, m, 1, ka);
+				HIPCK(rocprim::radix_sort_pairs(tmp.p, sb, ka, kb, va, vb, (size_t)m, 0, 64, st));
+				std::swap(va, vb);
+			}
 		}
 		// kb: the sorted end words, va: the items in that order; vb is free: it takes the run heads' indices, whose max-scan goes into k0's bytes
 		uint32_t *hidx = vb, *first = (uint32_t *)k0.p;                   // (ka's bytes: the keys have been read)
 		size_t mb = max_scan_tmp_bytes<uint32_t>((size_t)m);
-		bdp_run_heads<<<blocks(m), 256, 0, st>>>(kb, m, hidx);
+		if (bcs) bdp_run_heads<true><<<blocks(m), 256, 0, st>>>(kb, m, hidx, va, B);
+		else bdp_run_heads<false><<<blocks(m), 256, 0, st>>>(kb, m, hidx, nullptr, nullptr);
 		HIPCK(rocprim::inclusive_scan(tmp.p, mb, hidx, first, (size_t)m, rocprim::maximum<uint32_t>(), st));
 		bdp_frag_decide<<<blocks(m), 256, 0, st>>>(dE, va, first, m, (uint32_t *)d->bits.p, dcnt);
 	}
@@ -594,9 +662,12 @@ int bdp_flag_device(bdp_dev_t *d, uint8_t *d_recs, const uint64_t *d_off, const 
 // ---------------------------------------------------------------------------------------------------------------- the stand-alone entry point
 
 // O (or NULL): count the optical duplicates too; locs_only: stop at the templates' locations -- *out takes them, counts [BDP_TEMPLATES] their number
+// bc (or NULL): compare barcodes -- *no_barcode: the templates without one; bcs_only: stop at the templates' barcode words, as locs_only
 static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_table_t *G, void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts,
-                          const bdp_optical_t *O = nullptr, bool locs_only = false)
+                          const bdp_optical_t *O = nullptr, bool locs_only = false, const bdp_bc_t *bc = nullptr, uint64_t *no_barcode = nullptr, bool bcs_only = false)
 {
+	if (bc && bc->mode == BDP_BC_OFF) bc = nullptr;
+	if (no_barcode) *no_barcode = 0;
 	hipStream_t st = (hipStream_t)stream;
 	if (!out || !counts || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*out = nullptr;
@@ -613,16 +684,17 @@ static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes,
 	RCK(in.need((size_t)n_bytes + 16)); RCK(in_off.need(8 * off.size()));
 	if (n_bytes) HIPCK(hipMemcpyAsync(in.p, recs, (size_t)n_bytes, hipMemcpyHostToDevice, st));
 	HIPCK(hipMemcpyAsync(in_off.p, off.data(), 8 * off.size(), hipMemcpyHostToDevice, st));
-	const uint32_t *d_tpl; const bdp_entry_t *d_e; const uint32_t *d_info; const bdp_loc_t *d_l = nullptr;
+	const uint32_t *d_tpl; const bdp_entry_t *d_e; const uint32_t *d_info; const bdp_loc_t *d_l = nullptr; const uint64_t *d_b = nullptr;
 	const bool want_locs = O || locs_only;
-	RCK(bdp_batch_device(&d, (const uint8_t *)in.p, (const uint64_t *)in_off.p, n, n_bytes, st, &d_tpl, &d_e, &d_info, want_locs ? &d_l : nullptr));
+	RCK(bdp_batch_device(&d, (const uint8_t *)in.p, (const uint64_t *)in_off.p, n, n_bytes, st, &d_tpl, &d_e, &d_info, want_locs ? &d_l : nullptr, bc, bc ? &d_b : nullptr));
 	uint32_t info[BDP_INFO_WORDS];
 	HIPCK(hipMemcpyAsync(info, d_info, 4 * BDP_INFO_WORDS, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
-	RCK(bdp_batch_check(n, info, G != nullptr, fn));
+	RCK(bdp_batch_check(n, info, G != nullptr, fn, bc != nullptr));
 	const uint32_t T = n ? info[0] : 0;
 	if (T > n) { bmh_set_error("%s: internal error: %u templates among %u records", fn, T, n); return BMH_EINVAL; }
-	std::vector<bdp_entry_t> E(T); std::vector<uint32_t> tpl(n); std::vector<bdp_loc_t> L(want_locs ? T : 0);
+	std::vector<bdp_entry_t> E(T); std::vector<uint32_t> tpl(n); std::vector<bdp_loc_t> L(want_locs ? T : 0); std::vector<uint64_t> Bw(bc ? T : 0);
+	if (T && bc) HIPCK(hipMemcpyAsync(Bw.data(), d_b, 8 * (size_t)T, hipMemcpyDeviceToHost, st));
 	if (T) HIPCK(hipMemcpyAsync(E.data(), d_e, sizeof(bdp_entry_t) * (size_t)T, hipMemcpyDeviceToHost, st));
 	if (n) HIPCK(hipMemcpyAsync(tpl.data(), d_tpl, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
 	if (T && want_locs) HIPCK(hipMemcpyAsync(L.data(), d_l, sizeof(bdp_loc_t) * (size_t)T, hipMemcpyDeviceToHost, st));
@@ -634,7 +706,15 @@ static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes,
 		*out = o; counts[BDP_TEMPLATES] = T;
 		return BMH_OK;
 	}
-	RCK(bdp_decide_device(&d, E.data(), T, st, counts, 0, G ? G->n_lib : 0, G ? lib_counts : nullptr, O, O ? L.data() : nullptr));
+	if (bcs_only) {
+		uint8_t *o = (uint8_t *)malloc(8 * (size_t)T + 1);
+		if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+		if (T) memcpy(o, Bw.data(), 8 * (size_t)T);
+		*out = o; counts[BDP_TEMPLATES] = T;
+		return BMH_OK;
+	}
+	if (bc && no_barcode) *no_barcode = bdp_no_barcode(Bw.data(), T);
+	RCK(bdp_decide_device(&d, E.data(), T, st, counts, 0, G ? G->n_lib : 0, G ? lib_counts : nullptr, O, O ? L.data() : nullptr, nullptr, bc ? Bw.data() : nullptr));
 	counts[BDP_SECSUP] = info[2]; counts[BDP_UNMAPPED] = info[3]; counts[BDP_TEMPLATES] = T;
 	if (G && lib_counts) bdp_lib_tally_host(recs, off.data(), n, tpl.data(), E.data(), T, G->n_lib, lib_counts);
 	RCK(bdp_flag_device(&d, (uint8_t *)in.p, (const uint64_t *)in_off.p, tpl.data(), n, n_bytes, st));
@@ -689,5 +769,37 @@ extern "C" int bmh_bam_dup_locations_device(const uint8_t *recs, uint64_t n_byte
 	uint64_t counts[BDP_N_COUNTS];
 	RCK(markdup_device(fn, recs, n_bytes, groups ? &G : nullptr, stream, locs, counts, nullptr, nullptr, true));
 	*n_templates = counts[BDP_TEMPLATES];
+	return BMH_OK;
+}
+
+extern "C" int bmh_bam_markdup_barcode_device(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, int barcode_mode,
+                                              const char tag[2], void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode)
+{
+	const char *fn = "bmh_bam_markdup_barcode_device";
+	bdp_table_t G; bdp_bc_t bc;
+	if (out) *out = nullptr;
+	RCK(bdp_barcode_check(barcode_mode, tag, fn, &bc));
+	const bool opt = distance != -1;
+	if (opt && !optical) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (opt) RCK(bdp_optical_check(distance, max_set, fn));
+	const bool groups = rg_ids || rg_lib || n_groups;
+	if (groups) RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
+	if (opt && groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
+	const bdp_optical_t O = {distance, max_set ? (uint32_t)max_set : (uint32_t)BDP_OPT_MAX_SET, optical, groups ? lib_optical : nullptr};
+	return markdup_device(fn, recs, n_bytes, groups ? &G : nullptr, stream, out, counts, groups ? lib_counts : nullptr, opt ? &O : nullptr, false, &bc, no_barcode);
+}
+
+extern "C" int bmh_bam_dup_barcodes_device(const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], void *stream, uint64_t **words, uint64_t *n_templates)
+{
+	const char *fn = "bmh_bam_dup_barcodes_device";
+	bdp_bc_t bc;
+	if (words) *words = nullptr;
+	if (!words || !n_templates) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	*n_templates = 0;
+	RCK(bdp_barcode_check(barcode_mode, tag, fn, &bc));
+	if (bc.mode == BDP_BC_OFF) { bmh_set_error("%s: no barcode source (1: a tag, 2: the read name)", fn); return BMH_EINVAL; }
+	uint64_t counts[BDP_N_COUNTS]; uint8_t *o = nullptr;
+	RCK(markdup_device(fn, recs, n_bytes, nullptr, stream, &o, counts, nullptr, nullptr, false, &bc, nullptr, true));
+	*words = (uint64_t *)o; *n_templates = counts[BDP_TEMPLATES];
 	return BMH_OK;
 }

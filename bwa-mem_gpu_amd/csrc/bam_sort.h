@@ -43,12 +43,13 @@ int bsr_index_format_check(int format, int min_shift, const char *fn);
 // (16 bytes per record) always in memory.  With duplicate marking (csrc/bam_dup_core.h) a run also keeps every record's template ordinal within its batch (tpl, 4 bytes
 // per record, outside the budget like keys and offsets) and the ordinal of its first template in the whole run (tbase); the store keeps the templates' entries
 struct bsr_run_t { uint64_t n = 0, bytes = 0; std::vector<uint64_t> keys, off; uint8_t *mem = nullptr; int64_t file_at = -1; std::vector<uint32_t> tpl; uint64_t tbase = 0; };
-struct bsr_dup_t { const uint32_t *tpl; const bdp_entry_t *entries; uint32_t n_tpl; uint64_t secsup, unmapped; int lib = -1; const uint32_t *lib3 = nullptr; uint32_t n_lib3 = 0; const bdp_loc_t *locs = nullptr; };      // what a batch adds when duplicates are marked; lib: the library of the batch's read group (-1: a run without groups); lib3 [3 * n_lib3]: a batch of several libraries -- every library's secondary / supplementary records, unmapped records and templates (lib stays -1); locs [n_tpl] (or NULL): the templates' locations, when optical duplicates are counted
+struct bsr_dup_t { const uint32_t *tpl; const bdp_entry_t *entries; uint32_t n_tpl; uint64_t secsup, unmapped; int lib = -1; const uint32_t *lib3 = nullptr; uint32_t n_lib3 = 0; const bdp_loc_t *locs = nullptr; const uint64_t *bcs = nullptr; };      // what a batch adds when duplicates are marked; lib: the library of the batch's read group (-1: a run without groups); lib3 [3 * n_lib3]: a batch of several libraries -- every library's secondary / supplementary records, unmapped records and templates (lib stays -1); locs [n_tpl] (or NULL): the templates' locations, when optical duplicates are counted; bcs [n_tpl] (or NULL): the templates' barcode words, when barcodes are compared
 struct bsr_store_t {
 	uint64_t mem_bytes = 4ull << 30, used = 0, spilled = 0; std::string tmp_dir; int fd = -1; uint64_t file_bytes = 0;
 	std::vector<bsr_run_t> runs;
 	std::vector<bdp_entry_t> entries; uint64_t dup_info[2] = {0, 0};         // duplicate marking: every template's entry in input order; secondary / supplementary and unmapped records
 	std::vector<bdp_loc_t> locs;                                             // ... when optical duplicates are counted: every template's location beside its entry (else empty)
+	std::vector<uint64_t> bcs;                                               // ... when barcodes are compared: every template's barcode word beside its entry (else empty)
 	std::vector<uint64_t> lib_info;                                          // ... with read groups, per library: those two and the templates [3 * libraries]
 	~bsr_store_t() { clear(); }
 	void clear();
@@ -79,7 +80,8 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 // every run of the store -> the record members of the sorted file (to the sink, in windows of `window` records; 0: about 64 MiB of records) and its index
 // dup_counts (or NULL) [8]: mark the duplicates among the store's templates first (csrc/bam_dup_kernels.hip) and flag every window's records; the counts of bam_dup.h
 int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user,
-                     uint64_t *dup_counts = nullptr, double *dup_ms = nullptr, uint32_t n_lib = 0, uint64_t *lib_counts = nullptr, const struct bdp_optical_t *optical = nullptr, double *opt_ms = nullptr);
+                     uint64_t *dup_counts = nullptr, double *dup_ms = nullptr, uint32_t n_lib = 0, uint64_t *lib_counts = nullptr, const struct bdp_optical_t *optical = nullptr, double *opt_ms = nullptr, bool barcode = false);
+// barcode: the decision compares the barcode words the store keeps beside the entries
 // optical (or NULL; needs dup_counts): the decision also counts the optical duplicates among the store's templates, by the locations the store keeps; opt_ms (or NULL)
 // += that step's milliseconds
 // n_lib, lib_counts [8 * n_lib] (or 0, NULL): the run had read groups -- the entries carry their libraries -- and the decision's five counters come per library too

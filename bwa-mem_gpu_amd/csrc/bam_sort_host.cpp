@@ -201,7 +201,7 @@ void bsr_store_t::clear()
 {
 	for (bsr_run_t &r : runs) free(r.mem);
 	runs.clear(); used = 0; spilled = 0; file_bytes = 0;
-	entries.clear(); locs.clear(); dup_info[0] = dup_info[1] = 0; lib_info.clear();
+	entries.clear(); locs.clear(); bcs.clear(); dup_info[0] = dup_info[1] = 0; lib_info.clear();
 	if (fd >= 0) close(fd);
 	fd = -1;
 }
@@ -239,6 +239,7 @@ int bsr_store_t::append(const uint8_t *recs, uint64_t bytes, const uint64_t *key
 		r.file_at = (int64_t)file_bytes; file_bytes += bytes; ++spilled;
 	}
 	if (dup && dup->locs) locs.insert(locs.end(), dup->locs, dup->locs + dup->n_tpl);
+	if (dup && dup->bcs) bcs.insert(bcs.end(), dup->bcs, dup->bcs + dup->n_tpl);
 	if (dup) { entries.insert(entries.end(), dup->entries, dup->entries + dup->n_tpl); dup_info[0] += dup->secsup; dup_info[1] += dup->unmapped; }
 	if (dup && dup->lib >= 0) {
 		if (lib_info.size() < 3 * ((size_t)dup->lib + 1)) lib_info.resize(3 * ((size_t)dup->lib + 1), 0);
@@ -286,7 +287,8 @@ extern "C" int bmh_bam_sort_host(const uint8_t *recs, uint64_t n_bytes, uint8_t 
 // header members, the sorted records in windows of `window` records (0: as many as hold about 64 MiB), the end-of-file member; and the index
 static int sorted_file_host(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
                             int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts,
-                            const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr, int format = BSR_IX_BAI, int min_shift = BSR_LIN_SHIFT)
+                            const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr, int format = BSR_IX_BAI, int min_shift = BSR_LIN_SHIFT, const bdp_bc_t *bc = nullptr,
+                            uint64_t *no_barcode = nullptr)
 {
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
@@ -300,7 +302,7 @@ static int sorted_file_host(const char *fn, const char *header_text, int n_conti
 	std::vector<uint8_t> marked;                                   // duplicate marking: the flags are set before the sort (0x400 enters no key, bin or index)
 	if (dup_counts) {
 		marked.assign(recs, recs + n_bytes);
-		if ((rc = bdp_markdup_host(marked.data(), off, dup_counts, fn, G, lib_counts)) != BMH_OK) return rc;
+		if ((rc = bdp_markdup_host(marked.data(), off, dup_counts, fn, G, lib_counts, nullptr, bc, no_barcode)) != BMH_OK) return rc;
 		recs = marked.data();
 	}
 	bsr_sort_host(recs, off, keys, ord);
@@ -381,4 +383,23 @@ extern "C" int bmh_bam_sorted_file_ex_host(const char *header_text, int n_contig
 	if (groups && (rc = bdp_table_make(G, rg_ids, rg_lib, n_groups, fn)) != BMH_OK) return rc;
 	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, index, index_bytes, markdup ? counts : nullptr,
 	                        groups ? &G : nullptr, groups ? lib_counts : nullptr, index_format, min_shift);
+}
+
+extern "C" int bmh_bam_sorted_file_barcode_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                                int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
+                                                const char tag[2], uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts,
+                                                uint64_t *no_barcode)
+{
+	const char *fn = "bmh_bam_sorted_file_barcode_host";
+	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (no_barcode) *no_barcode = 0;
+	int rc = bsr_index_format_check(index_format, min_shift, fn);
+	if (rc != BMH_OK) return rc;
+	bdp_bc_t bc;
+	if ((rc = bdp_barcode_check(barcode_mode, tag, fn, &bc)) != BMH_OK) return rc;
+	bdp_table_t G;
+	const bool groups = rg_ids || rg_lib || n_groups;
+	if (groups && (rc = bdp_table_make(G, rg_ids, rg_lib, n_groups, fn)) != BMH_OK) return rc;
+	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, index, index_bytes, counts, groups ? &G : nullptr,
+	                        groups ? lib_counts : nullptr, index_format, min_shift, &bc, no_barcode);
 }

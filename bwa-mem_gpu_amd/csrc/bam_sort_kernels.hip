@@ -304,7 +304,7 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 
 // every run of the store -> the sorted file's record members (to the sink) and its index
 int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, uint64_t *dup_counts, double *dup_ms,
-                     uint32_t n_lib, uint64_t *lib_counts, const bdp_optical_t *optical, double *opt_ms)
+                     uint32_t n_lib, uint64_t *lib_counts, const bdp_optical_t *optical, double *opt_ms, bool barcode)
 {
 	uint64_t n = 0, bytes = 0;
 	std::vector<uint64_t> first;
@@ -319,7 +319,8 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint3
 		if (!(dup.p = bdp_dev_create())) return BMH_ENOMEM;
 		const double t0 = bsr_now_ms();
 		if (optical && S.locs.size() != S.entries.size()) { bmh_set_error("sorted BAM: internal error: %zu locations for %zu templates", S.locs.size(), S.entries.size()); return BMH_EINVAL; }
-		RCK(bdp_decide_device(dup.p, S.entries.data(), S.entries.size(), stream, dup_counts, n, n_lib, lib_counts, optical, optical ? S.locs.data() : nullptr, &o_ms));
+		if (barcode && S.bcs.size() != S.entries.size()) { bmh_set_error("sorted BAM: internal error: %zu barcode words for %zu templates", S.bcs.size(), S.entries.size()); return BMH_EINVAL; }
+		RCK(bdp_decide_device(dup.p, S.entries.data(), S.entries.size(), stream, dup_counts, n, n_lib, lib_counts, optical, optical ? S.locs.data() : nullptr, &o_ms, barcode ? S.bcs.data() : nullptr));
 		dup_counts[BDP_SECSUP] = S.dup_info[0]; dup_counts[BDP_UNMAPPED] = S.dup_info[1]; dup_counts[BDP_TEMPLATES] = S.entries.size();
 		decide_ms = bsr_now_ms() - t0;
 	}
@@ -360,7 +361,7 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint3
 	if (dup_counts) {
 		if (dup_ms) { dup_ms[0] += decide_ms; dup_ms[1] += flag_ms; }
 		if (getenv("BMH_ALIGNER_TRACE"))
-			fprintf(stderr, "[aligner] duplicate marking: %zu templates (%zu bytes of entries, %llu of ordinals kept) decided in %.1f ms, the windows' flags set in %.1f ms\n", S.entries.size(),
+			fprintf(stderr, "[aligner] duplicate marking: %zu templates (%zu bytes of entries, %llu of ordinals kept) decided in %.2f ms, the windows' flags set in %.2f ms\n", S.entries.size(),
 			        sizeof(bdp_entry_t) * S.entries.size(), 4ull * (unsigned long long)n, decide_ms, flag_ms);
 		if (opt_ms) *opt_ms += o_ms;
 		if (optical && getenv("BMH_ALIGNER_TRACE"))
@@ -374,9 +375,9 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint3
 
 namespace {
 // what duplicate marking keeps of a stream: its records' template ordinals in sorted order, the templates' entries, the line counts
-struct dup_host_t { std::vector<uint32_t> tpl; std::vector<bdp_entry_t> entries; uint64_t secsup = 0, unmapped = 0; };
+struct dup_host_t { std::vector<uint32_t> tpl; std::vector<bdp_entry_t> entries; uint64_t secsup = 0, unmapped = 0; std::vector<uint64_t> bcs; };
 int to_store(bsr_dev_t *d, const uint8_t *recs, uint64_t n_bytes, const std::vector<uint64_t> &off, hipStream_t st, std::vector<uint8_t> &sorted, std::vector<uint64_t> &keys, std::vector<uint64_t> &soff,
-             dup_host_t *dh = nullptr, const char *fn = "", const bdp_table_t *G = nullptr)
+             dup_host_t *dh = nullptr, const char *fn = "", const bdp_table_t *G = nullptr, const bdp_bc_t *bc = nullptr)
 {
 	const uint32_t n = (uint32_t)(off.size() - 1);
 	RCK(d->in.need((size_t)n_bytes + 16)); RCK(d->in_off.need(8 * off.size()));
@@ -384,22 +385,24 @@ int to_store(bsr_dev_t *d, const uint8_t *recs, uint64_t n_bytes, const std::vec
 	HIPCK(hipMemcpyAsync(d->in_off.p, off.data(), 8 * off.size(), hipMemcpyHostToDevice, st));
 	const uint8_t *ds; const uint64_t *dk, *dso;
 	struct dup_own_t { bdp_dev_t *p = nullptr; ~dup_own_t() { if (p) bdp_dev_free(p); } } dup;
-	const uint32_t *d_tpl = nullptr, *d_info = nullptr, *d_tpl_sorted = nullptr; const bdp_entry_t *d_e = nullptr;
+	const uint32_t *d_tpl = nullptr, *d_info = nullptr, *d_tpl_sorted = nullptr; const bdp_entry_t *d_e = nullptr; const uint64_t *d_b = nullptr;
 	if (dh) {
 		if (!(dup.p = bdp_dev_create())) return BMH_ENOMEM;
 		RCK(bdp_dev_set_groups(dup.p, G, st));
-		RCK(bdp_batch_device(dup.p, (const uint8_t *)d->in.p, (const uint64_t *)d->in_off.p, n, n_bytes, st, &d_tpl, &d_e, &d_info));
+		RCK(bdp_batch_device(dup.p, (const uint8_t *)d->in.p, (const uint64_t *)d->in_off.p, n, n_bytes, st, &d_tpl, &d_e, &d_info, nullptr, bc, bc ? &d_b : nullptr));
 	}
 	RCK(bsr_sort_run_device(d, (const uint8_t *)d->in.p, (const uint64_t *)d->in_off.p, n, n_bytes, st, &ds, &dk, &dso, d_tpl, &d_tpl_sorted));
 	if (dh) {
 		uint32_t info[BDP_INFO_WORDS];
 		HIPCK(hipMemcpyAsync(info, d_info, 4 * BDP_INFO_WORDS, hipMemcpyDeviceToHost, st));
 		HIPCK(hipStreamSynchronize(st));
-		RCK(bdp_batch_check(n, info, G != nullptr, fn));
+		RCK(bdp_batch_check(n, info, G != nullptr, fn, bc != nullptr));
 		if (info[0] > n) { bmh_set_error("%s: internal error: %u templates among %u records", fn, info[0], n); return BMH_EINVAL; }
 		dh->tpl.resize(n); dh->entries.resize(n ? info[0] : 0); dh->secsup = info[2]; dh->unmapped = info[3];
 		if (n) HIPCK(hipMemcpyAsync(dh->tpl.data(), d_tpl_sorted, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
 		if (!dh->entries.empty()) HIPCK(hipMemcpyAsync(dh->entries.data(), d_e, sizeof(bdp_entry_t) * dh->entries.size(), hipMemcpyDeviceToHost, st));
+		if (bc) dh->bcs.resize(dh->entries.size());
+		if (bc && !dh->bcs.empty()) HIPCK(hipMemcpyAsync(dh->bcs.data(), d_b, 8 * dh->bcs.size(), hipMemcpyDeviceToHost, st));
 	}
 	sorted.resize((size_t)n_bytes + 1); keys.resize((size_t)n + 1); soff.resize((size_t)n + 1);
 	if (n_bytes) HIPCK(hipMemcpyAsync(sorted.data(), ds, (size_t)n_bytes, hipMemcpyDeviceToHost, st));
@@ -431,8 +434,11 @@ extern "C" int bmh_bam_sort_device(const uint8_t *recs, uint64_t n_bytes, void *
 
 static int sorted_file_device(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
                               int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts,
-                              const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr, int format = BSR_IX_BAI, int min_shift = BSR_LIN_SHIFT)
+                              const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr, int format = BSR_IX_BAI, int min_shift = BSR_LIN_SHIFT, const bdp_bc_t *bc = nullptr,
+                              uint64_t *no_barcode = nullptr)
 {
+	if (bc && (bc->mode == BDP_BC_OFF || !dup_counts)) bc = nullptr;
+	if (no_barcode) *no_barcode = 0;
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
 	if (G && n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d references: with read groups a run holds at most 2^24 (the library takes the duplicate key's top byte)", fn, n_contigs); return BMH_EINVAL; }
@@ -449,8 +455,9 @@ static int sorted_file_device(const char *fn, const char *header_text, int n_con
 			if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) { bmh_set_error("%s: record %zu is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL; }
 	dup_host_t dh;
 	if (off.size() > 1) {
-		RCK(to_store(&d, recs, n_bytes, off, (hipStream_t)stream, sorted, keys, soff, dup_counts ? &dh : nullptr, fn, G));
-		const bsr_dup_t bd = {dh.tpl.data(), dh.entries.data(), (uint32_t)dh.entries.size(), dh.secsup, dh.unmapped};
+		RCK(to_store(&d, recs, n_bytes, off, (hipStream_t)stream, sorted, keys, soff, dup_counts ? &dh : nullptr, fn, G, bc));
+		bsr_dup_t bd = {dh.tpl.data(), dh.entries.data(), (uint32_t)dh.entries.size(), dh.secsup, dh.unmapped};
+		if (bc) { bd.bcs = dh.bcs.data(); if (no_barcode) *no_barcode = bdp_no_barcode(dh.bcs.data(), dh.bcs.size()); }
 		RCK(S.append(sorted.data(), n_bytes, keys.data(), soff.data(), off.size() - 1, dup_counts ? &bd : nullptr));
 	}
 	std::string file;
@@ -462,7 +469,7 @@ static int sorted_file_device(const char *fn, const char *header_text, int n_con
 	file.append((const char *)hm, hmb); bmh_free(hm);
 	const uint64_t base = file.size();
 	bmh_bam_ws_t *ws = bmh_bam_ws_create();
-	rc = bsr_merge_device(&d, ws, S, window, level, stream, ix, sink_string, &file, dup_counts, nullptr, G ? G->n_lib : 0, G ? lib_counts : nullptr);
+	rc = bsr_merge_device(&d, ws, S, window, level, stream, ix, sink_string, &file, dup_counts, nullptr, G ? G->n_lib : 0, G ? lib_counts : nullptr, nullptr, nullptr, bc != nullptr);
 	bmh_bam_ws_free(ws);
 	if (rc != BMH_OK) return rc;
 	if (G && lib_counts && off.size() > 1)
@@ -515,4 +522,22 @@ extern "C" int bmh_bam_sorted_file_ex_device(const char *header_text, int n_cont
 	if (groups) RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
 	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, index, index_bytes, markdup ? counts : nullptr,
 	                          groups ? &G : nullptr, groups ? lib_counts : nullptr, index_format, min_shift);
+}
+
+extern "C" int bmh_bam_sorted_file_barcode_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                                  int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
+                                                  const char tag[2], void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8],
+                                                  uint64_t *lib_counts, uint64_t *no_barcode)
+{
+	const char *fn = "bmh_bam_sorted_file_barcode_device";
+	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (no_barcode) *no_barcode = 0;
+	RCK(bsr_index_format_check(index_format, min_shift, fn));
+	bdp_bc_t bc;
+	RCK(bdp_barcode_check(barcode_mode, tag, fn, &bc));
+	bdp_table_t G;
+	const bool groups = rg_ids || rg_lib || n_groups;
+	if (groups) RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
+	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, index, index_bytes, counts, groups ? &G : nullptr,
+	                          groups ? lib_counts : nullptr, index_format, min_shift, &bc, no_barcode);
 }

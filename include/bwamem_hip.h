@@ -1002,6 +1002,42 @@ int bmh_aligner_set_markdup_optical(bmh_aligner_t *a, int64_t distance);
 int bmh_aligner_markdup_optical_counts(bmh_aligner_t *a, int lib, uint64_t out[3]);
 int bmh_aligner_markdup_optical_ms(bmh_aligner_t *a, double *out);
 
+/* ---- Barcode-aware duplicate keys (UMIs; csrc/bam_dup_core.h).  Opt-in: without it every output byte is that of the calls above.
+ * A template's barcode comes from its first record -- the record its library and its location come from.  barcode_mode 1 (a tag): the value of tag `tag` (two
+ * characters, [A-Za-z][A-Za-z0-9]; not RG, nor one the aligner writes itself: NM MD AS XS SA XA pa) of type Z, verbatim -- no case folding, no splitting at '-'.
+ * barcode_mode 2 (the name): the bytes behind the last ':' of the read name (bcl-convert's ...:tile:x:y:UMI); the optical step's parser is then given the name
+ * without that field and its ':'.  0: none (tag ignored).  An absent tag, an empty value, a name without ':' and a name that ends in ':' mean no barcode: such
+ * templates are comparable with each other and with no barcoded one; *no_barcode (or NULL) counts them.  The value becomes a 64-bit word -- FNV-1a over its
+ * bytes, 0 kept for no barcode (a value that hashes to 0 takes 1) -- and words are compared: pairs by (lo, hi, word), fragments by (end, word), a fragment a
+ * duplicate through a pair's end only if that pair has its word, an optical set the pairs of one (lo, hi, word).  Refused with BMH_EINVAL and the record's index: a
+ * first record whose tag has a type other than Z, or whose tags cannot be walked.
+ * bmh_bam_markdup_barcode_device / _host: bmh_bam_markdup_optical_* with the barcode's source; distance -1 runs without the optical step (optical may be NULL).
+ * bmh_bam_sorted_file_barcode_device / _host: bmh_bam_sorted_file_ex_* with marking on and the barcode's source.
+ * bmh_bam_dup_barcodes_device / _host: a record stream -> *words: one uint64 per template (malloc'd; bmh_free), *n_templates of them; barcode_mode 1 or 2.
+ * bmh_barcode_word: the word of a value of n bytes.
+ * bmh_aligner_set_markdup_barcode: the marked runs that follow compare barcodes (mode as above; 0: off, the default); refused unless marking is on, and switched
+ * off wherever marking is.  A tag reaches the records of an aligner run only as a read's comment (-C).
+ * bmh_aligner_markdup_barcode_counts: out [0]: the templates without a barcode in the last such run. */
+int bmh_bam_markdup_barcode_device(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
+                                   int barcode_mode, const char tag[2], void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3],
+                                   uint64_t *lib_optical, uint64_t *no_barcode);
+int bmh_bam_markdup_barcode_host(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
+                                 int barcode_mode, const char tag[2], uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical,
+                                 uint64_t *no_barcode);
+int bmh_bam_sorted_file_barcode_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
+                                       int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
+                                       int barcode_mode, const char tag[2], void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes,
+                                       uint64_t counts[8], uint64_t *lib_counts, uint64_t *no_barcode);
+int bmh_bam_sorted_file_barcode_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
+                                     int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
+                                     int barcode_mode, const char tag[2], uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8],
+                                     uint64_t *lib_counts, uint64_t *no_barcode);
+int bmh_bam_dup_barcodes_device(const uint8_t *records, uint64_t n_bytes, int barcode_mode, const char tag[2], void *stream, uint64_t **words, uint64_t *n_templates);
+int bmh_bam_dup_barcodes_host(const uint8_t *records, uint64_t n_bytes, int barcode_mode, const char tag[2], uint64_t **words, uint64_t *n_templates);
+uint64_t bmh_barcode_word(const uint8_t *value, uint64_t n);
+int bmh_aligner_set_markdup_barcode(bmh_aligner_t *a, int mode, const char *tag);
+int bmh_aligner_markdup_barcode_counts(bmh_aligner_t *a, uint64_t out[1]);
+
 /* A run over several read groups: one sample's lanes and libraries into one output.  A group is a read group ID, its library index (as above) and an input as
  * bmh_aligner_run_files takes it (path2: the mates, or NULL; a BAM's own @RG lines and RG tags stay ignored: keeping the input's read groups, bmh_aligner_set_keep_rg, and a run over groups do not combine).  One loader thread walks the groups in order into the
  * one queue of batches: the lanes are not drained between groups.  A batch never spans two groups and is cut inside its group as bmh_aligner_run_files cuts it; the
