@@ -645,14 +645,15 @@ class Aligner:
             if getattr(self, "_markdup", False):
                 nat.set_markdup_optical(getattr(self, "_optical", None))
                 nat.set_markdup_barcode(*getattr(self, "_barcode", (0, None)))
+                nat.set_markdup_barcode_edits(getattr(self, "_barcode_edits", -1))
         return nat
 
     def align_file(self, reads_fa: str, out, batch_reads: int = 0, paired: bool = False, chunk_bases: int = 0, fmt: str = "sam", level: int = 1,
                    sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
-                   index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None) -> int:
-        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None or barcode_tag is not None or barcode_name:
+                   index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None) -> int:
+        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None or barcode_tag is not None or barcode_name or barcode_edits is not None:
             return self._align_bam(lambda o: self.align_file(reads_fa, o, batch_reads=batch_reads, paired=paired, chunk_bases=chunk_bases), out, fmt, level,
-                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift, optical_distance, barcode_tag, barcode_name)
+                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift, optical_distance, barcode_tag, barcode_name, barcode_edits)
         """out: a text or binary file object.  Batches are cut the way the reference's bseq_read cuts them (src/bwa.c, called with
         chunk_size * n_threads = 10 Mbases per thread, or -K, src/fastmap.c:527): reads are added until the batch holds at least
         chunk_bases bases and an even number of reads -- in paired mode the insert-size statistics are those of the batch, so the
@@ -729,7 +730,7 @@ class Aligner:
         return n
 
     def _align_bam(self, run, out, fmt: str, level: int, sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
-                   index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None) -> int:
+                   index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None) -> int:
         """fmt="bam" of align_file / align_files: the header members, the batches' members (`run` with the native aligner's output switched; the Python
         loop's batches converted here), the end-of-file member.  The file is written through a shim that drops the SAM header `run` writes first.
         sort=True: the batches become sorted runs and the members are those of the coordinate-sorted file, written at the end of the input; `index` (a path or
@@ -743,9 +744,15 @@ class Aligner:
         READ_PAIR_OPTICAL_DUPLICATES and ESTIMATED_LIBRARY_SIZE in Picard's column order.
         barcode_tag="RX" or barcode_name=True (need markdup=True; one of the two): templates with different molecular barcodes (UMIs) are no duplicates of each
         other -- the barcode is the value of that tag on the template's first record, which an aligner run carries only as the read's comment
-        (so barcode_tag needs -C), or the read name's last ':' field.  self.markdup_counts gains "templates_without_barcode"; the metrics table keeps its columns."""
-        from .lib import bgzf_eof, index_format_code, optical_distance_value, barcode_source, BARCODE_OFF, BARCODE_TAG
+        (so barcode_tag needs -C), or the read name's last ':' field.  self.markdup_counts gains "templates_without_barcode"; the metrics table keeps its columns.
+        barcode_edits=N (needs a barcode source; 0 .. 21): barcodes within N mismatches are one molecule (packed values of at most 21 symbols of
+        A C G T N - +, transitive clusters per key, the pair pass and the fragment pass each on their own).  self.markdup_counts gains "pair_barcodes_observed",
+        "pair_barcodes_inferred" and "barcode_keys_skipped"; a value that does not pack fails the run by its record's index."""
+        from .lib import bgzf_eof, index_format_code, optical_distance_value, barcode_source, barcode_edits_value, BARCODE_OFF, BARCODE_TAG
         barcode = barcode_source(barcode_tag, barcode_name, "align_file")
+        if barcode_edits is not None and not markdup:
+            raise ValueError("barcode_edits needs markdup=True: barcodes are grouped where duplicates are marked")
+        edits = barcode_edits_value(barcode_edits, barcode[0], "align_file")
         if barcode[0] != BARCODE_OFF and not markdup:
             raise ValueError("barcode_tag / barcode_name need markdup=True: barcodes are compared where duplicates are marked")
         if barcode[0] == BARCODE_TAG and not self.po.copy_comment:
@@ -792,6 +799,7 @@ class Aligner:
         self._markdup = bool(markdup)
         self._optical = optical_distance
         self._barcode = barcode
+        self._barcode_edits = edits
         self._index_format = (index_format, int(csi_min_shift))
         try:
             n = run(shim)
@@ -803,6 +811,9 @@ class Aligner:
                     self.markdup_library_counts = {lb: (self._native.markdup_library_counts(k) if n else dict.fromkeys(MARKDUP_COUNTS, 0)) for k, lb in enumerate(libs)}
                 if barcode[0] != BARCODE_OFF:
                     self.markdup_counts.update(self._native.markdup_barcode_counts() if n else {"templates_without_barcode": 0})
+                if edits >= 0:
+                    from .lib import BARCODE_GROUP_COUNTS
+                    self.markdup_counts.update(self._native.markdup_barcode_group_counts() if n else dict.fromkeys(BARCODE_GROUP_COUNTS, 0))
                 if optical_distance is not None:
                     from .lib import OPTICAL_COUNTS
                     self.markdup_optical_counts = self._native.markdup_optical_counts() if n else dict.fromkeys(OPTICAL_COUNTS, 0)
@@ -816,6 +827,7 @@ class Aligner:
             self._markdup = False
             self._optical = None
             self._barcode = (0, None)
+            self._barcode_edits = -1
             self._index_format = ("bai", 14)
             nat = getattr(self, "_native", None)
             if nat is not None:
@@ -844,7 +856,7 @@ class Aligner:
 
     def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
                     sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None, keep_rg: bool = False,
-                    index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None) -> int:
+                    index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None) -> int:
         """align_file for the files users have (bmh_aligner_run_files): `reads` (and `mates`: the second file of a pair, which implies paired) may be
         multi-line FASTA or FASTQ, plain, gzip or BGZF, a regular file or a pipe; or `reads` alone is a BAM file (unaligned, or grouped by read name: recognised
         from its bytes, pairs from flag 0x1 of its records -- paired=True on a BAM without it is refused).  Batches are cut by align_file's rules (-t, -K, the 150 Mbase floor for
@@ -868,16 +880,16 @@ class Aligner:
             try:
                 return self.align_files(reads, None, out=out, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads, fmt=fmt, level=level, sort=sort, index=index,
                                         sort_mem=sort_mem, sort_tmp=sort_tmp, sort_window=sort_window, markdup=markdup, markdup_metrics=markdup_metrics, keep_rg=True,
-                                        index_format=index_format, csi_min_shift=csi_min_shift, optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name)
+                                        index_format=index_format, csi_min_shift=csi_min_shift, optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name, barcode_edits=barcode_edits)
             finally:
                 self._keep_rg = None
                 self._groups = None
                 nat = getattr(self, "_native", None)
                 if nat is not None:
                     nat.set_keep_rg(False)
-        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None or barcode_tag is not None or barcode_name:
+        if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None or barcode_tag is not None or barcode_name or barcode_edits is not None:
             return self._align_bam(lambda o: self.align_files(reads, mates, out=o, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads, keep_rg=keep_rg), out, fmt, level,
-                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift, optical_distance, barcode_tag, barcode_name)
+                                   sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift, optical_distance, barcode_tag, barcode_name, barcode_edits)
         binary = "b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")
         paired = bool(paired or mates is not None)
         cb = 0
@@ -911,7 +923,7 @@ class Aligner:
 
     def align_groups(self, groups, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
                      sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
-                     index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None) -> int:
+                     index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None) -> int:
         """several read groups -- a sample's lanes and libraries -- into one output (bmh_aligner_run_groups).  groups: [(rg_line, reads, mates or None), ...]; every
         rg_line is unescaped and checked as -R's value is, reads / mates are what align_files takes (one file or R1 + R2; plain, gzip or BGZF; FASTA or FASTQ; or
         one BAM, whose own @RG lines and RG tags stay ignored: align_files(keep_rg=True) is the run that keeps them, and the two do not combine).  Group g's records are byte for byte those of align_files(reads_g, mates_g) alone under -R rg_g, and
@@ -940,9 +952,9 @@ class Aligner:
             raise NotImplementedError("align_groups needs the native pipeline (BMH_ALIGNER_NATIVE=0 and profile runs write batch after batch)")
         self._groups = parsed
         try:
-            if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None or barcode_tag is not None or barcode_name:
+            if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None or barcode_tag is not None or barcode_name or barcode_edits is not None:
                 return self._align_bam(lambda o: self._run_groups(parsed, libs, o, paired, chunk_bases, batch_reads), out, fmt, level,
-                                       sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift, optical_distance, barcode_tag, barcode_name)
+                                       sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift, optical_distance, barcode_tag, barcode_name, barcode_edits)
             return self._run_groups(parsed, libs, out, paired, chunk_bases, batch_reads)
         finally:
             self._groups = None

@@ -51,6 +51,9 @@ EXPORTED_SYMBOLS = [
     "bmh_aligner_set_markdup_optical", "bmh_aligner_markdup_optical_counts", "bmh_aligner_markdup_optical_ms",
     "bmh_bam_markdup_barcode_device", "bmh_bam_markdup_barcode_host", "bmh_bam_sorted_file_barcode_device", "bmh_bam_sorted_file_barcode_host",
     "bmh_bam_dup_barcodes_device", "bmh_bam_dup_barcodes_host", "bmh_barcode_word", "bmh_aligner_set_markdup_barcode", "bmh_aligner_markdup_barcode_counts",
+    "bmh_bam_markdup_barcode_edits_device", "bmh_bam_markdup_barcode_edits_host", "bmh_bam_sorted_file_barcode_edits_device", "bmh_bam_sorted_file_barcode_edits_host",
+    "bmh_bam_dup_barcodes_packed_device", "bmh_bam_dup_barcodes_packed_host", "bmh_barcode_pack", "bmh_aligner_set_markdup_barcode_edits",
+    "bmh_aligner_markdup_barcode_group_counts",
 ]
 
 
@@ -461,6 +464,34 @@ def barcode_source(barcode_tag, barcode_name, what: str) -> tuple:
     return BARCODE_TAG, tag.encode()
 
 
+BARCODE_GROUP_COUNTS = ("pair_barcodes_observed", "pair_barcodes_inferred", "barcode_keys_skipped")
+BARCODE_MAX_EDITS = 21
+
+
+def barcode_edits_value(barcode_edits, bc_mode, what: str) -> int:
+    """the keyword barcode_edits (None: barcodes are compared exactly; N: barcodes within N mismatches are one molecule) of the marking calls -> the C entry
+    points' edits (-1: off).  ValueError: not an integer in 0 .. 21, or no barcode source beside it"""
+    if barcode_edits is None:
+        return -1
+    if not isinstance(barcode_edits, (int, np.integer)) or isinstance(barcode_edits, (bool, np.bool_)) or not 0 <= barcode_edits <= BARCODE_MAX_EDITS:
+        raise ValueError(f"{what}: barcode_edits {barcode_edits!r}: an integer in 0 .. {BARCODE_MAX_EDITS}")
+    if bc_mode == BARCODE_OFF:
+        raise ValueError(f"{what}: barcode_edits groups the barcodes that are compared: it needs barcode_tag or barcode_name")
+    return int(barcode_edits)
+
+
+def barcode_pack(value) -> int:
+    """bmh_barcode_pack: the packed word duplicate marking compares for a barcode value (bytes or str) when barcodes are grouped by edits -- 3 bits a byte (A 1, C 2,
+    G 3, T 4, N 5, - 6, + 7), symbol i in bits 3 i .. 3 i + 2, 0 for the empty value (no barcode).  ValueError: more than 21 bytes, or a byte without a symbol"""
+    L = load_library()
+    value = value if isinstance(value, bytes) else str(value).encode()
+    w = C.c_uint64(0)
+    L.bmh_barcode_pack.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    if L.bmh_barcode_pack(value, len(value), C.byref(w)) != 1:
+        raise ValueError(f"barcode_pack: {value!r} does not pack: at most 21 bytes of A C G T N - +")
+    return int(w.value)
+
+
 def barcode_word(value) -> int:
     """bmh_barcode_word: the 64-bit word duplicate marking compares for a barcode value (bytes or str) -- FNV-1a, 0 for the empty value (no barcode), 1 for a
     value that hashes to 0"""
@@ -471,9 +502,11 @@ def barcode_word(value) -> int:
     return int(L.bmh_barcode_word(value, len(value)))
 
 
-def bam_dup_barcodes(records: bytes, host: bool = False, tag=None, name=None) -> np.ndarray:
+def bam_dup_barcodes(records: bytes, host: bool = False, tag=None, name=None, edits: bool = False) -> np.ndarray:
     """bmh_bam_dup_barcodes_device (host=True: _host): a record stream as bam_markdup takes it -> one barcode word (uint64) per template, from tag `tag` of its first
-    record or (name=True) from its read name's last ':' field; 0: no barcode.  This is what bam_markdup(barcode_tag=...) compares."""
+    record or (name=True) from its read name's last ':' field; 0: no barcode.  This is what bam_markdup(barcode_tag=...) compares.
+    edits=True (bmh_bam_dup_barcodes_packed_*): the packed words (barcode_pack) that bam_markdup(barcode_edits=...) groups; a value that does not pack raises
+    ValueError with its record's index."""
     mode, tg = barcode_source(tag, name, "bam_dup_barcodes")
     if mode == BARCODE_OFF:
         raise ValueError("bam_dup_barcodes: give tag= or name=True")
@@ -483,12 +516,14 @@ def bam_dup_barcodes(records: bytes, host: bool = False, tag=None, name=None) ->
     out, nt = C.c_void_p(), C.c_uint64(0)
     head = [C.c_char_p, C.c_uint64, C.c_int, C.c_char_p]
     if host:
-        L.bmh_bam_dup_barcodes_host.argtypes = head + [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-        rc = L.bmh_bam_dup_barcodes_host(records, len(records), mode, tg, C.byref(out), C.byref(nt))
+        fn = L.bmh_bam_dup_barcodes_packed_host if edits else L.bmh_bam_dup_barcodes_host
+        fn.argtypes = head + [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        rc = fn(records, len(records), mode, tg, C.byref(out), C.byref(nt))
     else:
         import torch
-        L.bmh_bam_dup_barcodes_device.argtypes = head + [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-        rc = L.bmh_bam_dup_barcodes_device(records, len(records), mode, tg, torch.cuda.current_stream().cuda_stream, C.byref(out), C.byref(nt))
+        fn = L.bmh_bam_dup_barcodes_packed_device if edits else L.bmh_bam_dup_barcodes_device
+        fn.argtypes = head + [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        rc = fn(records, len(records), mode, tg, torch.cuda.current_stream().cuda_stream, C.byref(out), C.byref(nt))
     if rc != 0:
         raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_dup_barcodes: " + _err(L))
     try:
@@ -497,7 +532,7 @@ def bam_dup_barcodes(records: bytes, host: bool = False, tag=None, name=None) ->
         L.bmh_free(out)
 
 
-def _bam_markdup_optical(records: bytes, host: bool, read_groups, distance, max_set, barcode=None) -> tuple:
+def _bam_markdup_optical(records: bytes, host: bool, read_groups, distance, max_set, barcode=None, edits=-1, bc_max_set=0) -> tuple:
     L = load_library()
     L.bmh_free.argtypes = [C.c_void_p]
     if barcode is not None and distance is None:
@@ -518,7 +553,19 @@ def _bam_markdup_optical(records: bytes, host: bool, read_groups, distance, max_
         lo = (C.c_uint64 * (3 * max(len(names), 1)))()
     head = [C.c_char_p, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int, C.c_int64, C.c_uint64]
     tail = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    if barcode is not None:                                   # bmh_bam_markdup_barcode_*: the optical call with the barcode's source; distance -1: no optical step
+    if barcode is not None and edits >= 0:                    # bmh_bam_markdup_barcode_edits_*: the barcode call with the edits, the cap and the three grouping counts
+        nb, gc = C.c_uint64(0), (C.c_uint64 * 3)()
+        lg = (C.c_uint64 * (3 * max(len(names), 1)))() if read_groups is not None else None
+        bc, btail, bargs = [C.c_int, C.c_char_p, C.c_int, C.c_uint64], tail + [C.POINTER(C.c_uint64)] * 3, (C.byref(out), counts, lc, opt, lo, C.byref(nb), gc, lg)
+        if host:
+            L.bmh_bam_markdup_barcode_edits_host.argtypes = head + bc + btail
+            rc = L.bmh_bam_markdup_barcode_edits_host(records, len(records), ids, lib, ng, distance, int(max_set), barcode[0], barcode[1], edits, int(bc_max_set), *bargs)
+        else:
+            import torch
+            L.bmh_bam_markdup_barcode_edits_device.argtypes = head + bc + [C.c_void_p] + btail
+            rc = L.bmh_bam_markdup_barcode_edits_device(records, len(records), ids, lib, ng, distance, int(max_set), barcode[0], barcode[1], edits, int(bc_max_set),
+                                                        torch.cuda.current_stream().cuda_stream, *bargs)
+    elif barcode is not None:                                 # bmh_bam_markdup_barcode_*: the optical call with the barcode's source; distance -1: no optical step
         nb = C.c_uint64(0)
         bc, btail, bargs = [C.c_int, C.c_char_p], tail + [C.POINTER(C.c_uint64)], (C.byref(out), counts, lc, opt, lo, C.byref(nb))
         if host:
@@ -543,11 +590,15 @@ def _bam_markdup_optical(records: bytes, host: bool, read_groups, distance, max_
             c.update(zip(OPTICAL_COUNTS, (int(v) for v in opt)))
         if barcode is not None:
             c["templates_without_barcode"] = int(nb.value)
+        if barcode is not None and edits >= 0:
+            c.update(zip(BARCODE_GROUP_COUNTS, (int(v) for v in gc)))
         if read_groups is not None:
             c["libraries"] = _library_counts(names, lc)
             for k, nm in enumerate(names):
                 if distance >= 0:
                     c["libraries"][nm].update(zip(OPTICAL_COUNTS, (int(v) for v in lo[3 * k:3 * k + 3])))
+                if barcode is not None and edits >= 0:
+                    c["libraries"][nm].update(zip(BARCODE_GROUP_COUNTS, (int(v) for v in lg[3 * k:3 * k + 3])))
         return (C.string_at(out.value, len(records)) if records else b""), c
     finally:
         L.bmh_free(out)
@@ -603,7 +654,8 @@ def estimate_library_size(n: int, c: int):
     return int(size.value) if L.bmh_library_size(int(n), int(c), C.byref(size)) == 1 else None
 
 
-def bam_markdup(records: bytes, host: bool = False, read_groups=None, optical_distance=None, optical_max_set=None, barcode_tag=None, barcode_name=None) -> tuple:
+def bam_markdup(records: bytes, host: bool = False, read_groups=None, optical_distance=None, optical_max_set=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
+                barcode_max_set=None) -> tuple:
     """bmh_bam_markdup_device (host=True: bmh_bam_markdup_host, no device needed): a stream of BAM records in the writer's order (a template's records next to
     each other, its first primary line first) -> (the same records with flag 0x400 on every record of every duplicate template, the counts by MARKDUP_COUNTS'
     names).  Picard MarkDuplicates' rules.  A cut stream, one whose first record begins no template and a paired template without both of its
@@ -617,14 +669,24 @@ def bam_markdup(records: bytes, host: bool = False, read_groups=None, optical_di
     barcode_tag="RX" or barcode_name=True (bmh_bam_markdup_barcode_*; one of the two): templates with different molecular barcodes (UMIs) are no duplicates of each
     other -- the barcode is the value of that tag (type Z, verbatim) on the template's first record, or the read name's last ':' field; the keys become (lo, hi,
     barcode) and (end, barcode), an optical set the pairs of one (lo, hi, barcode).  Templates without a barcode are comparable with each other only; the counts gain
-    "templates_without_barcode".  A first record whose tag has another type, or whose tags cannot be walked, raises ValueError with its index."""
+    "templates_without_barcode".  A first record whose tag has another type, or whose tags cannot be walked, raises ValueError with its index.
+    barcode_edits=N (bmh_bam_markdup_barcode_edits_*; 0 .. 21, beside a barcode source): barcodes within N mismatches are one molecule -- within one
+    (library, lo, hi) the pairs' distinct barcodes are clustered transitively and compared by their cluster's smallest, and likewise, on their own, the barcodes at
+    one (library, end) before the fragment rule.  Barcodes are packed (barcode_pack): a value of more than 21 bytes or with a byte other than A C G T N - + raises
+    ValueError with its record's index.  The counts gain BARCODE_GROUP_COUNTS' names, with read_groups per library too.  barcode_max_set (needs barcode_edits; default
+    65 536; for tests): a key with more distinct barcodes is not clustered."""
     L = load_library()
     records = bytes(records)
     if optical_max_set is not None and optical_distance is None:
         raise ValueError("bam_markdup: optical_max_set needs optical_distance")
     bc_mode, bc_tag = barcode_source(barcode_tag, barcode_name, "bam_markdup")
+    edits = barcode_edits_value(barcode_edits, bc_mode, "bam_markdup")
+    if barcode_max_set is not None and edits < 0:
+        raise ValueError("bam_markdup: barcode_max_set needs barcode_edits")
+    if barcode_max_set is not None and (not isinstance(barcode_max_set, (int, np.integer)) or isinstance(barcode_max_set, bool) or not 1 <= barcode_max_set <= 0x7fffffff):
+        raise ValueError(f"bam_markdup: barcode_max_set {barcode_max_set!r}: an integer in 1 .. 2^31 - 1")
     if bc_mode != BARCODE_OFF:
-        return _bam_markdup_optical(records, host, read_groups, optical_distance, optical_max_set, (bc_mode, bc_tag))
+        return _bam_markdup_optical(records, host, read_groups, optical_distance, optical_max_set, (bc_mode, bc_tag), edits, barcode_max_set or 0)
     if optical_distance is not None:
         return _bam_markdup_optical(records, host, read_groups, optical_distance, optical_max_set)
     L.bmh_free.argtypes = [C.c_void_p]
@@ -682,15 +744,19 @@ def index_format_code(index_format, csi_min_shift, what: str) -> tuple:
 
 
 def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False, markdup: bool = False, read_groups=None,
-                    index_format: str = "bai", csi_min_shift: int = 14, barcode_tag=None, barcode_name=None) -> tuple:
+                    index_format: str = "bai", csi_min_shift: int = 14, barcode_tag=None, barcode_name=None, barcode_edits=None) -> tuple:
     """bmh_bam_sorted_file_device (host=True: _host): (the complete sorted BAM file -- header members, the records in coordinate order in windows of `window`
     records (0: about 64 MiB), the end-of-file member --, its .bai index).  contigs: (name, length) pairs; both forms give the same bytes.
     markdup=True (bmh_bam_sorted_file_markdup_*): `records` come in the writer's order, the duplicates among them are marked (bam_markdup's rules) and the counts come third.
     read_groups (needs markdup=True): as bam_markdup takes them -- duplicates per library, and the counts gain "libraries".
     index_format="csi" (bmh_bam_sorted_file_ex_*): the second element is the .csi index -- BGZF-compressed, bins of 2^csi_min_shift bases (10 .. 24) at the depth the
     longest contig asks for --, contigs may hold up to 2^31 - 1 bases (with markdup=True up to 2^30 - 2^24) and the BAM bytes are those of the "bai" call.
-    barcode_tag / barcode_name (bmh_bam_sorted_file_barcode_*; need markdup=True): as bam_markdup takes them; the counts gain "templates_without_barcode"."""
+    barcode_tag / barcode_name (bmh_bam_sorted_file_barcode_*; need markdup=True): as bam_markdup takes them; the counts gain "templates_without_barcode".
+    barcode_edits (bmh_bam_sorted_file_barcode_edits_*; needs a barcode source): as bam_markdup takes it; the counts gain BARCODE_GROUP_COUNTS' names."""
     bc_mode, bc_tag = barcode_source(barcode_tag, barcode_name, "bam_sorted_file")
+    if barcode_edits is not None and not markdup:
+        raise ValueError("bam_sorted_file: barcode_edits needs markdup=True (barcodes are grouped where duplicates are marked)")
+    edits = barcode_edits_value(barcode_edits, bc_mode, "bam_sorted_file")
     if bc_mode != BARCODE_OFF and not markdup:
         raise ValueError("bam_sorted_file: barcode_tag / barcode_name need markdup=True (barcodes are compared where duplicates are marked)")
     if read_groups is not None and not markdup:
@@ -718,6 +784,11 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
         lc = (C.c_uint64 * (8 * max(len(lib_names), 1)))()
         head += [ix_code, ix_shift, ids, lib, ng, bc_mode, bc_tag]; sig += [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_char_p]
         tail += [counts, lc if read_groups is not None else None, C.byref(no_bc)]; out += [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        if edits >= 0:                                        # ... and the edits, the cap (the default) and the grouping counts
+            gc = (C.c_uint64 * 3)()
+            lg = (C.c_uint64 * (3 * max(len(lib_names), 1)))() if read_groups is not None else None
+            head += [edits, 0]; sig += [C.c_int, C.c_uint64]
+            tail += [gc, lg]; out += [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     elif ix_code == INDEX_CSI:                                # the one entry point that takes everything: counts and library counts always have their place
         ids, lib, ng, lib_names = _library_table(read_groups) if read_groups is not None else (None, None, 0, [])
         lc = (C.c_uint64 * (8 * max(len(lib_names), 1)))()
@@ -734,12 +805,12 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
         grp = "_groups"
     if bc_mode != BARCODE_OFF:
         if host:
-            fn = L.bmh_bam_sorted_file_barcode_host
+            fn = L.bmh_bam_sorted_file_barcode_edits_host if edits >= 0 else L.bmh_bam_sorted_file_barcode_host
             fn.argtypes = sig + out
             rc = fn(*head, *tail)
         else:
             import torch
-            fn = L.bmh_bam_sorted_file_barcode_device
+            fn = L.bmh_bam_sorted_file_barcode_edits_device if edits >= 0 else L.bmh_bam_sorted_file_barcode_device
             fn.argtypes = sig + [C.c_void_p] + out
             rc = fn(*head, torch.cuda.current_stream().cuda_stream, *tail)
     elif ix_code == INDEX_CSI:
@@ -770,6 +841,10 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
                 c["libraries"] = _library_counts(lib_names, lc)
             if bc_mode != BARCODE_OFF:
                 c["templates_without_barcode"] = int(no_bc.value)
+            if bc_mode != BARCODE_OFF and edits >= 0:
+                c.update(zip(BARCODE_GROUP_COUNTS, (int(v) for v in gc)))
+                for k, nm in enumerate(lib_names if read_groups is not None else []):
+                    c["libraries"][nm].update(zip(BARCODE_GROUP_COUNTS, (int(v) for v in lg[3 * k:3 * k + 3])))
             return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value), c
         return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)
     finally:
@@ -968,6 +1043,22 @@ class NativeAligner:
         L.bmh_aligner_set_markdup_barcode.argtypes = [C.c_void_p, C.c_int, C.c_char_p]
         if L.bmh_aligner_set_markdup_barcode(self.handle, int(mode), tag) != 0:
             raise ValueError("bmh_aligner_set_markdup_barcode: " + _err(L))
+
+    def set_markdup_barcode_edits(self, n: int = -1) -> None:
+        """bmh_aligner_set_markdup_barcode_edits: the marked runs that follow group barcodes within n mismatches (0 .. 21; -1: off); after set_markdup_barcode"""
+        L = load_library()
+        L.bmh_aligner_set_markdup_barcode_edits.argtypes = [C.c_void_p, C.c_int]
+        if L.bmh_aligner_set_markdup_barcode_edits(self.handle, int(n)) != 0:
+            raise ValueError("bmh_aligner_set_markdup_barcode_edits: " + _err(L))
+
+    def markdup_barcode_group_counts(self) -> dict:
+        """bmh_aligner_markdup_barcode_group_counts: the grouping counts of the last run that grouped barcodes by edits, by BARCODE_GROUP_COUNTS' names"""
+        L = load_library()
+        L.bmh_aligner_markdup_barcode_group_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        c = (C.c_uint64 * 3)()
+        if L.bmh_aligner_markdup_barcode_group_counts(self.handle, c) != 0:
+            raise ValueError("bmh_aligner_markdup_barcode_group_counts: " + _err(L))
+        return dict(zip(BARCODE_GROUP_COUNTS, (int(v) for v in c)))
 
     def markdup_barcode_counts(self) -> dict:
         """bmh_aligner_markdup_barcode_counts: {"templates_without_barcode": ...} of the last run that compared barcodes"""

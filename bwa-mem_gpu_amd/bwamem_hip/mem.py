@@ -27,8 +27,12 @@ with different molecular barcodes -- UMIs -- are no duplicates of each other, as
 --barcode-tag XX: the barcode is the value of tag XX, type Z, on a template's first record, taken verbatim (a dual UMI ACGT-TTGA is one value); it needs -C,
 which copies a FASTQ comment such as RX:Z:ACGT, or a uBAM's own tags, into the records; XX is two characters [A-Za-z][A-Za-z0-9], not RG nor a tag the aligner
 writes itself.  --barcode-name: the barcode is what follows the last ':' of the read name, bcl-convert's ...:tile:x:y:UMI, and --optical-distance then locates a
-read by the name without that field.  A template without a barcode is comparable only with others without one; barcodes are compared exactly, grouping them by
-edit distance is not built; the metrics table keeps its columns).  --rg LINE opens a read group:
+read by the name without that field.  A template without a barcode is comparable only with others without one; barcodes are compared exactly unless
+--barcode-edits N is given; the metrics table keeps its columns), --barcode-edits N (needs --barcode-tag or --barcode-name; a whole number, 0 .. 21 -- Picard's
+UmiAwareMarkDuplicatesWithMateCigar uses 1: barcodes within N mismatches are one molecule.  The barcodes at one pair of ends are clustered transitively and
+compared by their cluster's smallest; those at one end likewise, on their own, before the fragment rule.  A barcode holds at most 21 bytes of A C G T N - +:
+any other value, lower case included, fails the run by its record's index; barcodes of different lengths are never joined, and a key with more than 65 536
+distinct barcodes is left exact; no MI or DT tag is written).  --rg LINE opens a read group:
 LINE is an @RG line as -R takes it, and the one or two files that follow it, up to the next --rg, are that group's input (Aligner.align_groups): a sample's lanes
 and libraries go into one output, every record with its group's RG:Z, the header with every @RG line, and --markdup calls duplicates within a library (the LB
 field; groups with one LB are lanes of one library) only.  -p applies to every group; --rg and -R exclude each other.  --keep-rg keeps the read groups of the
@@ -65,7 +69,7 @@ def main(argv=None) -> int:
     bam, bam_level = False, 1
     sort, index_path, sort_mem, sort_tmp = False, None, None, None
     markdup, metrics_path, optical = False, None, None
-    barcode_tag, barcode_name = None, False
+    barcode_tag, barcode_name, barcode_edits = None, False, None
     csi, csi_shift = False, None
     keep_rg = False
     groups = []                                                     # --rg LINE: [line, files...]; the positionals behind it are its files
@@ -101,6 +105,12 @@ def main(argv=None) -> int:
                 print("[bwamem_hip.mem] option --optical-distance needs a whole number of pixels, 0 .. 2^31 - 1", file=sys.stderr)
                 return 2
             optical = int(argv[i + 1])
+            i += 1
+        elif a == "--barcode-edits":
+            if i + 1 >= len(argv) or not (argv[i + 1].isascii() and argv[i + 1].isdigit()) or int(argv[i + 1]) > 21:
+                print("[bwamem_hip.mem] option --barcode-edits needs a whole number of mismatches, 0 .. 21", file=sys.stderr)
+                return 2
+            barcode_edits = int(argv[i + 1])
             i += 1
         elif a == "--barcode-name":
             barcode_name = True
@@ -187,6 +197,12 @@ def main(argv=None) -> int:
     if optical is not None and not markdup:
         print("[bwamem_hip.mem] --optical-distance needs --markdup (optical duplicates are counted where duplicates are marked)", file=sys.stderr)
         return 2
+    if barcode_edits is not None and not markdup:
+        print("[bwamem_hip.mem] --barcode-edits needs --markdup (barcodes are grouped where duplicates are marked)", file=sys.stderr)
+        return 2
+    if barcode_edits is not None and barcode_tag is None and not barcode_name:
+        print("[bwamem_hip.mem] --barcode-edits needs --barcode-tag or --barcode-name (it groups the barcodes that are compared)", file=sys.stderr)
+        return 2
     if barcode_tag is not None or barcode_name:
         from .lib import barcode_source
         try:
@@ -226,6 +242,8 @@ def main(argv=None) -> int:
             fmt_kw.update(barcode_tag=barcode_tag)
         if barcode_name:
             fmt_kw.update(barcode_name=True)
+        if barcode_edits is not None:
+            fmt_kw.update(barcode_edits=barcode_edits)
         if csi:
             fmt_kw.update(index_format="csi", csi_min_shift=14 if csi_shift is None else csi_shift)
         done = False

@@ -51,6 +51,7 @@ struct aligner_t {
 	uint32_t max_qlen = 768;       // the extension cap of the chain workspaces (bmh_aligner_set_max_qlen)
 	bmh_reseed_opt_t rs = {0, 1.5f, 10, 20};   // the seeding rounds (bmh_aligner_set_reseed; enable 0: the first round only)
 	bdp_bc_t barcode = {BDP_BC_OFF, 0, 0};      // ... with markdup: compare the templates' barcodes, from a tag or the read name (bmh_aligner_set_markdup_barcode)
+	uint32_t bc_edits = 0;                     // ... with barcode.pack (bmh_aligner_set_markdup_barcode_edits): the mismatches within which barcodes are one molecule
 	int64_t optical = -1;                      // ... with markdup: also count the optical duplicates within this distance (bmh_aligner_set_markdup_optical); -1: not
 	bool markdup = false;                      // sorted BAM output: flag 0x400 on the records of duplicate templates (bmh_aligner_set_markdup)
 	int out_fmt = BMH_OUT_SAM, out_level = 1;  // what the sink receives (bmh_aligner_set_output): the records' text, or BGZF members of BAM records
@@ -111,7 +112,7 @@ struct result_t {
 	hbuf_t<uint32_t> lib3;                                             // ... of a batch that mixes libraries (aligner_t::per_read): its counts per library [3 * libraries]
 	hbuf_t<uint64_t> dup_b;                                           // ... when barcodes are compared: the templates' barcode words
 	hbuf_t<bdp_loc_t> dup_l;                                          // ... when optical duplicates are counted: the templates' locations
-	hbuf_t<uint32_t> stpl; hbuf_t<bdp_entry_t> dup_e; uint32_t dup_info[BDP_INFO_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0}; uint64_t dup_d2h = 0;      // duplicate marking: the records' template ordinals in that order, the templates' entries, bdp_batch_device's info
+	hbuf_t<uint32_t> stpl; hbuf_t<bdp_entry_t> dup_e; uint32_t dup_info[BDP_INFO_WORDS_PACK] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; uint64_t dup_d2h = 0;      // duplicate marking: the records' template ordinals in that order, the templates' entries, bdp_batch_device's info
 	std::vector<int64_t> slot;                   // (host selection only; empty: slot32)
 	std::vector<int32_t> h_rec, unflag;          // pairs
 	std::vector<uint32_t> dev_index;             // record -> its place in the lane's d_fin when that is not the record's own index (ALT indexes); empty: identity
@@ -295,7 +296,7 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 				if (ne) HIPCK(hipMemcpyAsync(R.dup_e.p, d_e, sizeof(bdp_entry_t) * ne, hipMemcpyDeviceToHost, Ln.st));
 				if (ne && optical) HIPCK(hipMemcpyAsync(R.dup_l.p, d_l, sizeof(bdp_loc_t) * ne, hipMemcpyDeviceToHost, Ln.st));
 				if (ne && barcode) HIPCK(hipMemcpyAsync(R.dup_b.p, d_b, 8 * ne, hipMemcpyDeviceToHost, Ln.st));
-				const size_t ni = A.groups.empty() && !barcode ? 16 : 4 * BDP_INFO_WORDS;      // (with read groups: the words of a template without a known group; with barcodes: of one whose tags are refused)
+				const size_t ni = A.groups.empty() && !barcode ? 16 : 4 * bdp_info_words(barcode ? &A.barcode : nullptr);      // (with read groups: the words of a template without a known group; with barcodes: of one whose tags are refused)
 				HIPCK(hipMemcpyAsync(R.dup_info, d_info, ni, hipMemcpyDeviceToHost, Ln.st));
 				if (d_lib3) HIPCK(hipMemcpyAsync(R.lib3.p, d_lib3, 12 * (size_t)A.groups.n_lib, hipMemcpyDeviceToHost, Ln.st));
 				R.dup_d2h = 4ull * nrec + sizeof(bdp_entry_t) * ne + ni + (d_lib3 ? 12ull * A.groups.n_lib : 0) + (optical ? sizeof(bdp_loc_t) * ne : 0) + (barcode ? 8ull * ne : 0);
@@ -305,7 +306,7 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 			Ln.copy_bytes[1] += bo.bam_bytes + 16ull * nrec; Ln.d2h_marked = true;
 			HIPCK(hipStreamSynchronize(Ln.st));
 			if (A.markdup && nrec) {
-				RCK(bdp_batch_check(nrec, R.dup_info, !A.groups.empty(), "sorted BAM", barcode));
+				RCK(bdp_batch_check(nrec, R.dup_info, !A.groups.empty(), "sorted BAM", barcode, barcode && A.barcode.pack));
 				if (R.dup_info[0] == 0 || R.dup_info[0] > std::min(nrec, tmax)) { bmh_set_error("sorted BAM: internal error: %u templates among %u records", R.dup_info[0], nrec); return BMH_EINVAL; }
 			}
 			if (R.soff.p[nrec] != bo.bam_bytes) {                 // (the gather skips a record whose offsets lie outside the buffers: the scan of the sizes shows it)
@@ -893,6 +894,7 @@ struct bmh_aligner {
 	uint64_t dup_counts[BDP_N_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0}; bool dup_valid = false;      // duplicate marking: the counts of the last marked run
 	std::vector<uint64_t> lib_counts;                    // ... with read groups: the same eight per library (bmh_aligner_markdup_library_counts)
 	uint64_t opt_counts[BDP_OPT_N] = {0, 0, 0}; std::vector<uint64_t> lib_opt; bool opt_valid = false; double opt_ms = 0;      // ... with an optical distance: the three optical counts of the last such run, per library, and the step's ms
+	uint64_t grp_counts[BDP_GRP_N] = {0, 0, 0}; bool grp_valid = false;      // ... with barcode edits: the three grouping counts of the last such run
 	uint64_t no_barcode = 0; bool bc_valid = false;      // ... with barcodes: the templates without one in the last such run
 	double dup_times[3] = {0, 0, 0};                     // ... its decision and its windows' flag steps in ms, the bytes its batches' ordinals and entries took on their way down
 };
@@ -927,7 +929,7 @@ int bmh_aligner_set_output(bmh_aligner_t *h, int format, int level)
 	if (format != BMH_OUT_SAM && format != BMH_OUT_BAM && format != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_output: format %d (BMH_OUT_SAM, BMH_OUT_BAM or BMH_OUT_BAM_SORTED)", format); return BMH_EINVAL; }
 	if (format != BMH_OUT_SAM && level != 0 && level != 1) { bmh_set_error("bmh_aligner_set_output: level %d (0 or 1)", level); return BMH_EINVAL; }
 	if (format == BMH_OUT_BAM_SORTED) { h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), "sorted BAM output", h->ix_format, h->ix_shift)); }
-	if (format != BMH_OUT_BAM_SORTED) { h->a.markdup = false; h->a.optical = -1; h->a.barcode.mode = BDP_BC_OFF; }      // (duplicates are marked in sorted output only: the options go with the format)
+	if (format != BMH_OUT_BAM_SORTED) { h->a.markdup = false; h->a.optical = -1; h->a.barcode.mode = BDP_BC_OFF; h->a.barcode.pack = 0; }      // (duplicates are marked in sorted output only: the options go with the format)
 	h->a.out_fmt = format; h->a.out_level = level;
 	return BMH_OK;
 }
@@ -969,7 +971,7 @@ int bmh_aligner_set_markdup(bmh_aligner_t *h, int on)
 	if (on && h->a.out_fmt != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_markdup: duplicates are marked in sorted output (bmh_aligner_set_output with BMH_OUT_BAM_SORTED comes first)"); return BMH_EINVAL; }
 	if (on) RCK(bsr_markdup_contigs(h->a.n_contigs, h->a.len.data(), h->a.name_ptr.data(), "bmh_aligner_set_markdup"));      // (only a CSI run can hold such a contig)
 	h->a.markdup = on != 0;
-	if (!on) { h->a.optical = -1; h->a.barcode.mode = BDP_BC_OFF; }
+	if (!on) { h->a.optical = -1; h->a.barcode.mode = BDP_BC_OFF; h->a.barcode.pack = 0; }
 	return BMH_OK;
 }
 
@@ -977,11 +979,32 @@ int bmh_aligner_set_markdup_barcode(bmh_aligner_t *h, int mode, const char *tag)
 {
 	const char *fn = "bmh_aligner_set_markdup_barcode";
 	if (!h) { bmh_set_error("%s: null aligner", fn); return BMH_EINVAL; }
-	if (mode == BDP_BC_OFF) { h->a.barcode.mode = BDP_BC_OFF; return BMH_OK; }
+	if (mode == BDP_BC_OFF) { h->a.barcode.mode = BDP_BC_OFF; h->a.barcode.pack = 0; return BMH_OK; }
 	if (!h->a.markdup) { bmh_set_error("%s: barcodes are compared where duplicates are marked (bmh_aligner_set_markdup comes first)", fn); return BMH_EINVAL; }
 	bdp_bc_t bc;
 	RCK(bdp_barcode_check(mode, tag, fn, &bc));
 	h->a.barcode = bc;
+	return BMH_OK;
+}
+
+int bmh_aligner_set_markdup_barcode_edits(bmh_aligner_t *h, int n)
+{
+	const char *fn = "bmh_aligner_set_markdup_barcode_edits";
+	if (!h) { bmh_set_error("%s: null aligner", fn); return BMH_EINVAL; }
+	if (n == -1) { h->a.barcode.pack = 0; return BMH_OK; }
+	if (!h->a.markdup) { bmh_set_error("%s: barcodes are grouped where duplicates are marked (bmh_aligner_set_markdup comes first)", fn); return BMH_EINVAL; }
+	bdp_bc_t bc = h->a.barcode;
+	RCK(bdp_group_check(n, 0, fn, &bc));                              // (a source comes first: bmh_aligner_set_markdup_barcode)
+	h->a.barcode = bc; h->a.bc_edits = (uint32_t)n;
+	return BMH_OK;
+}
+
+int bmh_aligner_markdup_barcode_group_counts(bmh_aligner_t *h, uint64_t out[3])
+{
+	const char *fn = "bmh_aligner_markdup_barcode_group_counts";
+	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (!h->dup_valid || !h->grp_valid) { bmh_set_error("%s: no run has grouped barcodes by edits (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
+	for (int k = 0; k < BDP_GRP_N; ++k) out[k] = h->grp_counts[k];
 	return BMH_OK;
 }
 
@@ -1177,13 +1200,16 @@ struct out_stage_t {
 		const bdp_optical_t O = {h->a.optical, (uint32_t)BDP_OPT_MAX_SET, h->opt_counts, n_lib ? h->lib_opt.data() : nullptr};
 		const bool barcode = h->a.markdup && h->a.barcode.mode != BDP_BC_OFF;
 		h->no_barcode = barcode ? bdp_no_barcode(h->store.bcs.data(), h->store.bcs.size()) : 0;
+		const bool grouped = barcode && h->a.barcode.pack;
+		for (int k = 0; k < BDP_GRP_N; ++k) h->grp_counts[k] = 0;
+		const bdp_group_t GR = {h->a.bc_edits, (uint32_t)BDP_BC_MAX_SET, h->grp_counts, nullptr};
 		if (rc == BMH_OK) rc = bsr_merge_device(L0.bsr, L0.bam, h->store, h->sort_window, h->a.out_level, L0.st, h->sort_ix, forward, this, h->a.markdup ? h->dup_counts : nullptr, h->dup_times,
-		                                        n_lib, n_lib ? h->lib_counts.data() : nullptr, optical ? &O : nullptr, optical ? &h->opt_ms : nullptr, barcode);
+		                                        n_lib, n_lib ? h->lib_counts.data() : nullptr, optical ? &O : nullptr, optical ? &h->opt_ms : nullptr, barcode, grouped ? &GR : nullptr);
 		for (size_t k = 0; rc == BMH_OK && k < h->store.lib_info.size() && k / 3 < n_lib; ++k) h->lib_counts[BDP_N_COUNTS * (k / 3) + BDP_SECSUP + k % 3] = h->store.lib_info[k];
 		if (trace && h->a.markdup) fprintf(stderr, "[aligner] duplicate marking: %.0f bytes of ordinals and entries came down with the batches\n", h->dup_times[2]);
 		if (trace) fprintf(stderr, "[aligner] sorted output: %zu runs (%llu spilled) merged in %.1f ms\n", h->store.runs.size(), (unsigned long long)h->store.spilled, (now_s() - tm0) * 1e3);
 		h->store.clear();
-		if (rc == BMH_OK) { h->sort_ix.valid = true; h->dup_valid = h->a.markdup; h->opt_valid = optical; h->bc_valid = barcode; }
+		if (rc == BMH_OK) { h->sort_ix.valid = true; h->dup_valid = h->a.markdup; h->opt_valid = optical; h->bc_valid = barcode; h->grp_valid = grouped; }
 		return rc;
 	}
 };

@@ -39,30 +39,42 @@ int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::
 // barcode_mode and tag as the entry points take them -> *bc; BMH_EINVAL with a message: a mode other than 0, 1, 2; a tag that is not [A-Za-z][A-Za-z0-9], RG, or one
 // the writer produces itself (NM MD AS XS SA XA pa)
 int bdp_barcode_check(int barcode_mode, const char *tag, const char *fn, bdp_bc_t *bc);
-// the message of a template whose first record `rec` bdp_barcode refuses (st: BDP_E_BC_TYPE or BDP_E_BC_WALK)
+// the message of a template whose first record `rec` bdp_barcode refuses (st: BDP_E_BC_TYPE, BDP_E_BC_WALK or BDP_E_BC_PACK)
 int bdp_barcode_refused(uint32_t rec, int st, const char *fn);
 // the templates without a barcode among B [T]
 uint64_t bdp_no_barcode(const uint64_t *B, uint64_t T);
+// grouping barcodes by edits (csrc/bam_dup_core.h): the mismatches that still join (0 .. BDP_BC_MAX_EDITS), the most distinct words of a key that are clustered,
+// and where the three counts go (BDP_GRP_*): out [3], lib_out [3 * n_lib] or NULL.  The barcode words of such a run are packed (bdp_bc_t.pack)
+struct bdp_group_t { uint32_t edits, max_set; uint64_t *out, *lib_out; };
+// edits and max_set as the entry points take them (edits -1: no grouping; max_set 0: BDP_BC_MAX_SET) -> BMH_EINVAL with a message (edits outside 0 .. 21, edits
+// without a barcode source, a max_set of 2^31 and more), or BMH_OK and bc->pack set when edits >= 0
+int bdp_group_check(int edits, uint64_t max_set, const char *fn, bdp_bc_t *bc);
+// the canonical words of one pass, single-threaded through the clustering core (its invariant asserted).  frag false: the pair pass -- words [T], a barcoded pair's
+// the smallest word of its component, every other template's its own; the three counts go to G.out / G.lib_out (zeroed first).  frag true: the fragment pass --
+// words [2 T] by item id (template << 1 | end); only the keys over the cap are counted (added)
+void bdp_group_host(const bdp_entry_t *E, uint64_t T, const uint64_t *B, const bdp_group_t &G, uint32_t n_lib, bool frag, std::vector<uint64_t> &words);
 // the optical step of a run: the distance (0 .. 2^31 - 1), the largest set examined, and where its three counts go (BDP_OPT_*): out [3], lib_out [3 * n_lib] or NULL
 struct bdp_optical_t { int64_t distance; uint32_t max_set; uint64_t *out, *lib_out; };
 // distance and max_set as the entry points take them (max_set 0: BDP_OPT_MAX_SET) -> BMH_EINVAL with a message, or BMH_OK
 int bdp_optical_check(int64_t distance, uint64_t max_set, const char *fn);
 // the optical duplicates among the pairs of E [T] with locations L [T], single-threaded through the clustering core of csrc/bam_dup_core.h (its invariant asserted);
 // n_lib 0: no libraries, lib_out unused
-// B [T] (or NULL): the barcode words -- a set is the pairs of one (lo, hi, word)
+// B [T] (or NULL): the barcode words -- a set is the pairs of one (lo, hi, word); with grouping the pair pass's canonical words
 void bdp_optical_host(const bdp_entry_t *E, const bdp_loc_t *L, uint64_t T, const bdp_optical_t &O, uint32_t n_lib, const uint64_t *B = nullptr);
 // the decision: bits [(T + 31) / 32]: bit t set when template t is a duplicate; counts [0 .. 4]; lib_counts (or NULL) [BDP_N_COUNTS * n_lib]: every library's own
 // counts, of which the decision fills (and zeroes the rest of) words 0 .. 4
 // B [T] (or NULL): the barcode words, part of the pairs' and the fragments' keys
-void bdp_decide_host(const bdp_entry_t *entries, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5], uint32_t n_lib = 0, uint64_t *lib_counts = nullptr, const uint64_t *B = nullptr);
+// G (or NULL; needs B, packed): group the words by edits first; pair_words (or NULL): the pair pass's canonical words, for the optical step
+void bdp_decide_host(const bdp_entry_t *entries, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5], uint32_t n_lib = 0, uint64_t *lib_counts = nullptr, const uint64_t *B = nullptr,
+                     const bdp_group_t *G = nullptr, std::vector<uint64_t> *pair_words = nullptr);
 // words 5 .. 7 of every library's counts += the secondary or supplementary records, the unmapped records and the templates of the stream (off [n + 1], tpl [n]: the
 // records' template ordinals, E [T]: entries made with read groups)
 void bdp_lib_tally_host(const uint8_t *recs, const uint64_t *off, uint32_t n, const uint32_t *tpl, const bdp_entry_t *E, uint64_t T, uint32_t n_lib, uint64_t *lib_counts);
 // the whole of it on a walked stream: flags set in place; T, lib_counts [BDP_N_COUNTS * T->n_lib] (or NULL): with read groups, and every library's counts
 // O (or NULL): count the optical duplicates too
-// bc (or NULL): compare barcodes; *no_barcode (or NULL): the templates without one
+// bc (or NULL): compare barcodes; *no_barcode (or NULL): the templates without one; grp (or NULL; bc->pack set): group them by edits
 int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn, const bdp_table_t *T = nullptr, uint64_t *lib_counts = nullptr,
-                     const bdp_optical_t *O = nullptr, const bdp_bc_t *bc = nullptr, uint64_t *no_barcode = nullptr);
+                     const bdp_optical_t *O = nullptr, const bdp_bc_t *bc = nullptr, uint64_t *no_barcode = nullptr, const bdp_group_t *grp = nullptr);
 
 // csrc/bam_dup_kernels.hip
 struct bdp_dev_t;                                                  // device buffers of the batches' entries, the decision and the bitmap; kept between calls
@@ -72,7 +84,9 @@ void bdp_dev_free(bdp_dev_t *d);
 // (0: none; n + 1: the first record begins no template), secondary or supplementary records, unmapped records -- all in d until its next call
 // With read groups (bdp_dev_set_groups) *d_info has BDP_INFO_WORDS words: [4], [5] the first template's first record + 1 without an RG:Z tag / with an ID the
 // table does not hold (0xffffffff: none)
-enum { BDP_INFO_WORDS = 8 };
+// With packed barcodes (bc->pack) *d_info has BDP_INFO_WORDS_PACK words: [8] the first template's first record + 1 whose barcode does not pack
+enum { BDP_INFO_WORDS = 8, BDP_INFO_WORDS_PACK = 9 };
+inline uint32_t bdp_info_words(const bdp_bc_t *bc) { return bc && bc->mode != BDP_BC_OFF && bc->pack ? BDP_INFO_WORDS_PACK : BDP_INFO_WORDS; }
 // d_locs (or NULL): optical duplicates are counted -- *d_locs [as many as entries]: every template's location, written by the lane that makes its entry
 // bc, d_bcs (or NULL): barcodes are compared -- *d_bcs [as many as entries]: every template's barcode word, written by the lane that makes its entry; *d_info [6],
 // [7]: the first template's first record + 1 whose barcode tag is of another type than Z / whose tags cannot be walked (0xffffffff: none)
@@ -87,7 +101,8 @@ int bdp_dev_set_groups(bdp_dev_t *d, const bdp_table_t *T, void *stream);
 // the message of a batch whose info [1] is not 0
 int bdp_batch_refused(uint32_t n, uint32_t bad, const char *fn);
 // the verdict on a batch's info words (n records; groups, barcode: all BDP_INFO_WORDS were read): BMH_OK, or the message of the first refused record
-int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *fn, bool barcode = false);
+// pack: BDP_INFO_WORDS_PACK were read
+int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *fn, bool barcode = false, bool pack = false);
 // every template's entry (host) -> the bitmap, kept in d for bdp_flag_device, and counts [0 .. 4]
 // n_records: the records of the final sort that follows (csrc/bam_sort_kernels.hip: 24 bytes each and the sort's work space) -- the decision's buffers are freed
 // before that sort allocates, so one check of the larger of the two needs refuses here what either would refuse
@@ -96,7 +111,9 @@ int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *f
 // += its milliseconds (events around its kernels, the upload of the locations included)
 // bcs [T] (host; or NULL): the templates' barcode words -- one more stable radix pass on them in the pair pass and in the fragment pass, and the word compared where
 // keys are: 8 bytes per template more on the device
+// G (or NULL; needs bcs, packed): group the words by edits before the pair decision and before the fragment pass's run heads -- the passes then compare the canonical
+// words: 56 bytes per template more on the device (16 the canonical words, 40 the clustering's heads, members and union-find)
 int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records = 0, uint32_t n_lib = 0, uint64_t *lib_counts = nullptr,
-                      const bdp_optical_t *O = nullptr, const bdp_loc_t *locs = nullptr, double *opt_ms = nullptr, const uint64_t *bcs = nullptr);
+                      const bdp_optical_t *O = nullptr, const bdp_loc_t *locs = nullptr, double *opt_ms = nullptr, const uint64_t *bcs = nullptr, const bdp_group_t *G = nullptr);
 // records d_recs at d_off [n] (device; all inside `total` bytes) whose global template ordinals are tord [n] (host): byte 19 |= 0x04 where the bitmap says so
 int bdp_flag_device(bdp_dev_t *d, uint8_t *d_recs, const uint64_t *d_off, const uint32_t *tord, uint32_t n, uint64_t total, void *stream);

@@ -46,14 +46,31 @@
 //     pairs     key (lo, hi, word); fragments: key (end word, word) -- a fragment is a duplicate through a pair's end only if that pair has its word
 //     optical   a set is the pairs of one (lo, hi, word); in name mode the location is parsed from the name without its last field and that field's ':'
 //
-// Nothing is removed, no DT:Z tag is written, barcodes are compared exactly (no grouping by edit distance), the names' pattern is fixed.
+//   grouping  only when the run also asks for it (barcode edits N, 0 .. 21): barcodes within N mismatches are one molecule, as in Picard's
+//             UmiAwareMarkDuplicatesWithMateCigar (MAX_EDIT_DISTANCE_TO_JOIN), with the open points fixed
+//     word      the value itself, not its hash: 3 bits a byte -- A 1, C 2, G 3, T 4, N 5, '-' 6, '+' 7 --, symbol i in bits 3 i .. 3 i + 2, at most 21 symbols.  0
+//               stays no barcode; the packing is injective, so equal words are equal values.  A first record whose value holds another byte (lower case too) or
+//               more than 21 bytes is refused by the record's index.  The value's source, the no-barcode cases and the refused tags are those above
+//     distance  the positions at which the symbols differ, separators like the rest; values of different lengths, and a template without a barcode and one with,
+//               are never joined
+//     pairs     within one (library, lo, hi) the distinct words are vertices, with an edge where the distance is <= N; the clusters are the connected components
+//               (joining is transitive) and every pair takes the numerically smallest word of its component.  The pair rule then runs on (lo, hi, that word)
+//     fragments the same within one (library, end word), over the distinct words of the pass's items -- the fragments and both ends of every pair, each under
+//               its original word; the fragment rule then runs on (end word, the component's smallest word).  The two clusterings are independent
+//     optical   a set is the pairs of one (lo, hi, the pair clustering's word)
+//     cap       a key with more than max_set (65 536) distinct words is not clustered -- the walk is quadratic in them: its words stay exact, the key is counted
+//     counts    in total and per library: the distinct (library, lo, hi, word) over barcoded pairs, the components of those, and the keys of either pass over the cap
+//     clustering the union-find of the optical step over the distinct words in sorted order (key, then word): a root is its component's smallest word, and the
+//               components do not depend on the order of the unions
+//
+// Nothing is removed, no DT:Z or MI:Z tag is written, edits are mismatches (no indels, no count-based direction), the names' pattern is fixed.
 #pragma once
 #include "bam_sort_core.h"
 
 enum { BDP_NONE = 0, BDP_FRAG = 1, BDP_PAIR = 2, BDP_QMIN = 15 };
 enum { BDP_LIB_SHIFT = 56, BDP_MAX_LIBS = 255, BDP_MAX_REF = 1 << 24, BDP_MAX_CONTIG = (1 << 30) - (1 << 24) };
 // what bdp_entry_lib says of a template
-enum { BDP_E_OK = 0, BDP_E_TEMPLATE = 1, BDP_E_NO_RG = 2, BDP_E_RG_UNKNOWN = 3, BDP_E_BC_TYPE = 4, BDP_E_BC_WALK = 5 };
+enum { BDP_E_OK = 0, BDP_E_TEMPLATE = 1, BDP_E_NO_RG = 2, BDP_E_RG_UNKNOWN = 3, BDP_E_BC_TYPE = 4, BDP_E_BC_WALK = 5, BDP_E_BC_PACK = 6 };
 
 // a run's read groups: the IDs back to back (no terminators) with offsets id_off [n + 1], and every group's library index (below BDP_MAX_LIBS)
 struct bdp_groups_t { const char *ids; const uint32_t *id_off; const uint8_t *lib; uint32_t n; };
@@ -140,7 +157,7 @@ BSR_FN uint64_t bdp_frag_word(const bdp_entry_t &e, uint32_t ordinal) { return b
 BSR_FN uint32_t bdp_aux_width(uint8_t type) { return type == 'A' || type == 'c' || type == 'C' ? 1u : type == 's' || type == 'S' ? 2u : type == 'i' || type == 'I' || type == 'f' ? 4u : 0u; }
 
 // what bdp_aux_z says of a record's tags
-enum { BDP_AUX_FOUND = 0, BDP_AUX_ABSENT = 1, BDP_AUX_TYPE = 2, BDP_AUX_WALK = 3 };
+enum { BDP_AUX_FOUND = 0, BDP_AUX_ABSENT = 1, BDP_AUX_TYPE = 2, BDP_AUX_WALK = 3, BDP_AUX_PACK = 4 };      // (PACK: bdp_barcode alone -- a value that does not pack)
 
 // the value of the record's first tag t0 t1 of type Z (its length in *len), found by a walk over the tags behind the qualities.  *st: found; absent; a tag of
 // that name and another type came first (the walk goes on: the value, if one follows, is still returned); or tags that cannot be walked (a cut tag, an unknown
@@ -262,9 +279,11 @@ BSR_FN bool bdp_name_location(const uint8_t *name, uint32_t len, uint32_t out[3]
 
 // ---- barcodes
 
-// where a run's barcodes come from: mode (BDP_BC_*) and, for a tag, its two letters.  Passed by value to the kernel
+// where a run's barcodes come from: mode (BDP_BC_*) and, for a tag, its two letters; pack: the words are the packed values (grouping by edits), not hashes.
+// Passed by value to the kernel
 enum { BDP_BC_OFF = 0, BDP_BC_TAG = 1, BDP_BC_NAME = 2 };
-struct bdp_bc_t { uint32_t mode; uint8_t t0, t1; };
+struct bdp_bc_t { uint32_t mode; uint8_t t0, t1, pack; };
+static_assert(sizeof(bdp_bc_t) == 8, "the barcode source is 8 bytes");
 
 // the barcode word of a value of n bytes: 64-bit FNV-1a, one walk over the bytes; 0 is no barcode, so an empty value gives 0 and a value that hashes to 0 gives 1
 BSR_FN uint64_t bdp_barcode_word(const uint8_t *v, uint64_t n)
@@ -286,21 +305,44 @@ BSR_FN uint32_t bdp_name_last_field(const uint8_t *name, uint32_t len)
 // the length of the name the location parser is given: in name mode the name without its last field and that field's ':'
 BSR_FN uint32_t bdp_located_name_len(const uint8_t *name, uint32_t len, bool cut) { const uint32_t a = cut ? bdp_name_last_field(name, len) : len + 1; return a <= len ? a - 1 : len; }
 
+// grouping by edits: the limits, and the three counts (distinct words of barcoded pairs, their components, keys over the cap)
+enum { BDP_BC_SYMBOLS = 21, BDP_BC_MAX_EDITS = 21, BDP_BC_MAX_SET = 65536 };
+enum { BDP_GRP_OBSERVED = 0, BDP_GRP_INFERRED = 1, BDP_GRP_SKIPPED = 2, BDP_GRP_N = 3 };
+
+// a barcode byte's symbol; 0: a byte that does not pack
+BSR_FN uint32_t bdp_bc_symbol(uint8_t c) { return c == 'A' ? 1u : c == 'C' ? 2u : c == 'G' ? 3u : c == 'T' ? 4u : c == 'N' ? 5u : c == '-' ? 6u : c == '+' ? 7u : 0u; }
+
+// the packed word of a value of n bytes: symbol i in bits 3 i .. 3 i + 2; an empty value gives 0, no barcode.  false: more than 21 bytes, or a byte without a symbol
+BSR_FN bool bdp_barcode_pack(const uint8_t *v, uint64_t n, uint64_t *word)
+{
+	*word = 0;
+	if (n > BDP_BC_SYMBOLS) return false;
+	uint64_t w = 0;
+	for (uint32_t i = 0; i < (uint32_t)n; ++i) { const uint32_t s = bdp_bc_symbol(v[i]); if (!s) return false; w |= (uint64_t)s << 3 * i; }
+	*word = w;
+	return true;
+}
+
+// every 3-bit field of x folded to its lowest bit: set where the field is not 0
+BSR_FN uint64_t bdp_bc_fold(uint64_t x) { return (x | x >> 1 | x >> 2) & 0x1249249249249249ull; }
+// two packed words within N mismatches: the same places occupied (symbols are never 0, so that is the same length), and at most N fields of a ^ b not 0
+BSR_FN bool bdp_bc_near(uint64_t a, uint64_t b, uint32_t N) { return bdp_bc_fold(a) == bdp_bc_fold(b) && (uint32_t)__builtin_popcountll(bdp_bc_fold(a ^ b)) <= N; }
+
 // the barcode word of the template whose first record is rec (sz bytes; its name vouched for by bsr_record_bytes) -> *word; BDP_AUX_FOUND, or BDP_AUX_TYPE /
-// BDP_AUX_WALK: the record is refused
-BSR_FN int bdp_barcode(const uint8_t *rec, uint64_t sz, const bdp_bc_t &bc, uint64_t *word)
+// BDP_AUX_WALK: the record is refused.  pack: the packed word, not the hash -- BDP_AUX_PACK: a value that does not pack
+BSR_FN int bdp_barcode(const uint8_t *rec, uint64_t sz, const bdp_bc_t &bc, uint64_t *word, bool pack = false)
 {
 	*word = 0;
 	if (bc.mode == BDP_BC_NAME) {
 		if (sz < BSR_FIXED || sz - BSR_FIXED < rec[12]) return BDP_AUX_WALK;
 		const uint32_t ln = rec[12] ? rec[12] - 1u : 0u, a = bdp_name_last_field(rec + BSR_FIXED, ln);
-		if (a <= ln) *word = bdp_barcode_word(rec + BSR_FIXED + a, ln - a);
+		if (a <= ln) { if (!pack) *word = bdp_barcode_word(rec + BSR_FIXED + a, ln - a); else if (!bdp_barcode_pack(rec + BSR_FIXED + a, ln - a, word)) return BDP_AUX_PACK; }
 		return BDP_AUX_FOUND;
 	}
 	uint32_t len = 0; int st;                                           // (a record holds fewer than 2^32 bytes)
 	const uint8_t *v = bdp_aux_z(rec, sz, bc.t0, bc.t1, &len, &st);
 	if (st == BDP_AUX_TYPE || st == BDP_AUX_WALK) return st;
-	if (v) *word = bdp_barcode_word(v, len);
+	if (v) { if (!pack) *word = bdp_barcode_word(v, len); else if (!bdp_barcode_pack(v, len, word)) return BDP_AUX_PACK; }
 	return BDP_AUX_FOUND;
 }
 
@@ -364,6 +406,14 @@ BSR_FN void bdp_opt_walk(uint32_t i, uint32_t n, const uint64_t *word2, const ui
 		const int64_t dy = (int64_t)y[j] - yi;
 		if ((dy < 0 ? -dy : dy) <= D) bdp_uf_unite(parent, i, j);
 	}
+}
+
+// member i of m distinct (key, word) in sorted order (key, then word): it walks the members j > i of its key and unites with those within N mismatches.  The walk
+// ends at m at the latest: j only grows.  Indices ascend with the words inside a key, so a component's root is its smallest word
+BSR_FN void bdp_bc_walk(uint32_t i, uint32_t m, const uint32_t *key, const uint64_t *word, uint32_t N, uint32_t *parent)
+{
+	const uint32_t k = key[i]; const uint64_t w = word[i];
+	for (uint32_t j = i + 1; j < m && key[j] == k; ++j) if (bdp_bc_near(w, word[j], N)) bdp_uf_unite(parent, i, j);
 }
 
 // Picard's estimateLibrarySize: n pairs that are no optical duplicates, c of them distinct; 0: no estimate (the column stays empty)

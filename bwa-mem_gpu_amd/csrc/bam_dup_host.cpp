@@ -27,13 +27,14 @@ int bdp_group_refused(uint32_t rec, int st, const char *fn)
 int bdp_barcode_refused(uint32_t rec, int st, const char *fn)
 {
 	if (st == BDP_E_BC_TYPE) bmh_set_error("%s: duplicate marking: record %u begins a template and carries the barcode tag with a type other than Z", fn, rec);
+	else if (st == BDP_E_BC_PACK) bmh_set_error("%s: duplicate marking: record %u begins a template and its barcode does not pack for grouping by edits: more than %d bytes, or a byte other than A C G T N - +", fn, rec, (int)BDP_BC_SYMBOLS);
 	else bmh_set_error("%s: duplicate marking: record %u begins a template and its tags cannot be walked to the barcode tag (a cut tag, an unknown type, or bytes left over)", fn, rec);
 	return BMH_EINVAL;
 }
 
 int bdp_barcode_check(int mode, const char *tag, const char *fn, bdp_bc_t *bc)
 {
-	bc->mode = BDP_BC_OFF; bc->t0 = bc->t1 = 0;
+	bc->mode = BDP_BC_OFF; bc->t0 = bc->t1 = bc->pack = 0;
 	if (mode != BDP_BC_OFF && mode != BDP_BC_TAG && mode != BDP_BC_NAME) { bmh_set_error("%s: barcode mode %d (0: none, 1: a tag, 2: the read name)", fn, mode); return BMH_EINVAL; }
 	if (mode == BDP_BC_TAG) {
 		if (!tag) { bmh_set_error("%s: a barcode tag has two characters, [A-Za-z][A-Za-z0-9]", fn); return BMH_EINVAL; }
@@ -49,9 +50,20 @@ int bdp_barcode_check(int mode, const char *tag, const char *fn, bdp_bc_t *bc)
 	return BMH_OK;
 }
 
+int bdp_group_check(int edits, uint64_t max_set, const char *fn, bdp_bc_t *bc)
+{
+	bc->pack = 0;
+	if (edits == -1) return BMH_OK;
+	if (edits < 0 || edits > (int)BDP_BC_MAX_EDITS) { bmh_set_error("%s: barcode edits of %d (0 .. %d)", fn, edits, (int)BDP_BC_MAX_EDITS); return BMH_EINVAL; }
+	if (bc->mode == BDP_BC_OFF) { bmh_set_error("%s: barcode edits group the barcodes that are compared: they need a barcode source (a tag or the read name)", fn); return BMH_EINVAL; }
+	if (max_set > 0x7fffffffull) { bmh_set_error("%s: a largest key of %llu distinct barcodes (below 2^31; 0: %d)", fn, (unsigned long long)max_set, (int)BDP_BC_MAX_SET); return BMH_EINVAL; }
+	bc->pack = 1;
+	return BMH_OK;
+}
+
 uint64_t bdp_no_barcode(const uint64_t *B, uint64_t T) { uint64_t c = 0; for (uint64_t t = 0; t < T; ++t) c += B[t] == 0; return c; }
 
-int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *fn, bool barcode)
+int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *fn, bool barcode, bool pack)
 {
 	if (!n) return BMH_OK;
 	// (the smallest record index wins, as a walk from the front would find it)
@@ -59,6 +71,7 @@ int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *f
 	uint32_t bad = info[1]; int st = BDP_E_TEMPLATE;
 	if (groups) for (int k = 0; k < 2; ++k) if (info[4 + k] < bad) { bad = info[4 + k]; st = k ? BDP_E_RG_UNKNOWN : BDP_E_NO_RG; }
 	if (barcode) for (int k = 0; k < 2; ++k) if (info[6 + k] < bad) { bad = info[6 + k]; st = k ? BDP_E_BC_WALK : BDP_E_BC_TYPE; }
+	if (barcode && pack && info[8] < bad) { bad = info[8]; st = BDP_E_BC_PACK; }
 	if (bad == 0xffffffffu) return BMH_OK;
 	return st == BDP_E_TEMPLATE ? bdp_batch_refused(n, bad, fn) : st >= BDP_E_BC_TYPE ? bdp_barcode_refused(bad - 1, st, fn) : bdp_group_refused(bad - 1, st, fn);
 }
@@ -119,16 +132,57 @@ int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::
 		if (st != BDP_E_OK) return bdp_group_refused(a, st, fn);
 		if (locs) (*locs)[t] = bdp_location(recs + off[a], role, row, bc && bc->mode == BDP_BC_NAME);
 		if (bc) {
-			const int bs = bdp_barcode(recs + off[a], off[a + 1] - off[a], *bc, &(*bcs)[t]);
-			if (bs != BDP_AUX_FOUND) return bdp_barcode_refused(a, bs == BDP_AUX_TYPE ? BDP_E_BC_TYPE : BDP_E_BC_WALK, fn);
+			const int bs = bdp_barcode(recs + off[a], off[a + 1] - off[a], *bc, &(*bcs)[t], bc->pack != 0);
+			if (bs != BDP_AUX_FOUND) return bdp_barcode_refused(a, bs == BDP_AUX_TYPE ? BDP_E_BC_TYPE : bs == BDP_AUX_PACK ? BDP_E_BC_PACK : BDP_E_BC_WALK, fn);
 		}
 	}
 	return BMH_OK;
 }
 
-void bdp_decide_host(const bdp_entry_t *E, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5], uint32_t n_lib, uint64_t *lib_counts, const uint64_t *B)
+void bdp_group_host(const bdp_entry_t *E, uint64_t T, const uint64_t *B, const bdp_group_t &G, uint32_t n_lib, bool frag, std::vector<uint64_t> &words)
 {
-	auto bc = [&](uint32_t t) { return B ? B[t] : 0ull; };              // (without barcodes every word is equal: the keys are those of old)
+	if (!G.lib_out) n_lib = 0;
+	if (!frag) { for (int k = 0; k < BDP_GRP_N; ++k) G.out[k] = 0; for (uint32_t k = 0; k < BDP_GRP_N * n_lib; ++k) G.lib_out[k] = 0; }
+	auto add = [&](uint32_t t, int k) { ++G.out[k]; if (bdp_lib_of(E[t]) < n_lib) ++G.lib_out[BDP_GRP_N * (size_t)bdp_lib_of(E[t]) + k]; };
+	// the barcoded elements of the pass: a, b the key (b 0 in the fragment pass), w the word, id where the canonical word goes
+	struct elem_t { uint64_t a, b, w; uint32_t id, t; };
+	std::vector<elem_t> el;
+	words.assign((size_t)(frag ? 2 * T : T), 0);
+	for (uint64_t t = 0; t < T; ++t) {
+		const uint32_t k = bdp_kind(E[t]), u = (uint32_t)t;
+		if (frag) { words[2 * t] = words[2 * t + 1] = B[t]; if (k != BDP_NONE && B[t]) { el.push_back({E[t].lo, 0, B[t], u << 1, u}); if (k == BDP_PAIR) el.push_back({E[t].hi, 0, B[t], u << 1 | 1u, u}); } }
+		else { words[t] = B[t]; if (k == BDP_PAIR && B[t]) el.push_back({E[t].lo, E[t].hi, B[t], u, u}); }
+	}
+	std::sort(el.begin(), el.end(), [](const elem_t &x, const elem_t &y) { return x.a != y.a ? x.a < y.a : x.b != y.b ? x.b < y.b : x.w != y.w ? x.w < y.w : x.id < y.id; });
+	// the distinct (key, word) in that order: the members; wid: every element's member
+	std::vector<uint32_t> key, mt, parent, wid(el.size()), kstart; std::vector<uint64_t> word;
+	for (size_t i = 0; i < el.size(); ++i) {
+		const bool same_key = i && el[i].a == el[i - 1].a && el[i].b == el[i - 1].b;
+		if (!same_key) kstart.push_back((uint32_t)word.size());
+		if (!(same_key && el[i].w == el[i - 1].w)) { key.push_back((uint32_t)kstart.size() - 1); word.push_back(el[i].w); mt.push_back(el[i].t); parent.push_back((uint32_t)parent.size()); }
+		wid[i] = (uint32_t)word.size() - 1;
+	}
+	const uint32_t m = (uint32_t)word.size();
+	kstart.push_back(m);
+	for (uint32_t i = 0; i < m; ++i) {
+		const uint32_t size = kstart[key[i] + 1] - kstart[key[i]];
+		if (size > G.max_set) { if (kstart[key[i]] == i) add(mt[i], BDP_GRP_SKIPPED); continue; }
+		bdp_bc_walk(i, m, key.data(), word.data(), G.edits, parent.data());
+		assert(parent[i] <= i);
+	}
+	for (uint32_t i = 0; i < m && !frag; ++i) { add(mt[i], BDP_GRP_OBSERVED); if (parent[i] == i) add(mt[i], BDP_GRP_INFERRED); }
+	for (size_t i = 0; i < el.size(); ++i) words[el[i].id] = word[bdp_uf_find(parent.data(), wid[i])];
+}
+
+void bdp_decide_host(const bdp_entry_t *E, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5], uint32_t n_lib, uint64_t *lib_counts, const uint64_t *B, const bdp_group_t *G,
+                     std::vector<uint64_t> *pair_words)
+{
+	// grouping by edits: the pair pass and the fragment pass each compare their own canonical words
+	std::vector<uint64_t> Bp, Bf;
+	if (!B) G = nullptr;
+	if (G) { bdp_group_host(E, T, B, *G, n_lib, false, Bp); bdp_group_host(E, T, B, *G, n_lib, true, Bf); if (pair_words) *pair_words = Bp; }
+	auto bc = [&](uint32_t t) { return G ? Bp[t] : B ? B[t] : 0ull; };  // (without barcodes every word is equal: the keys are those of old)
+	auto bci = [&](uint32_t t, uint32_t end) { return G ? Bf[2 * (size_t)t + end] : B ? B[t] : 0ull; };
 	bits.assign((size_t)((T + 31) / 32), 0u);
 	for (int k = 0; k < 5; ++k) counts[k] = 0;
 	auto mark = [&](uint32_t t) { bits[t >> 5] |= 1u << (t & 31); counts[BDP_FLAGGED] += bdp_n_rec(E[t]); };
@@ -137,8 +191,8 @@ void bdp_decide_host(const bdp_entry_t *E, uint64_t T, std::vector<uint32_t> &bi
 	std::vector<item_t> items;
 	for (uint64_t t = 0; t < T; ++t) {
 		const uint32_t k = bdp_kind(E[t]);
-		if (k == BDP_PAIR) { pairs.push_back((uint32_t)t); items.push_back({E[t].lo, bc((uint32_t)t), 0, (uint32_t)t}); items.push_back({E[t].hi, bc((uint32_t)t), 0, (uint32_t)t}); }
-		else if (k == BDP_FRAG) items.push_back({E[t].lo, bc((uint32_t)t), bdp_frag_word(E[t], (uint32_t)t), (uint32_t)t});
+		if (k == BDP_PAIR) { pairs.push_back((uint32_t)t); items.push_back({E[t].lo, bci((uint32_t)t, 0), 0, (uint32_t)t}); items.push_back({E[t].hi, bci((uint32_t)t, 1), 0, (uint32_t)t}); }
+		else if (k == BDP_FRAG) items.push_back({E[t].lo, bci((uint32_t)t, 0), bdp_frag_word(E[t], (uint32_t)t), (uint32_t)t});
 	}
 	counts[BDP_PAIRS] = pairs.size(); counts[BDP_FRAGS] = items.size() - 2 * pairs.size();
 	std::sort(pairs.begin(), pairs.end(), [&](uint32_t a, uint32_t b) {
@@ -216,9 +270,11 @@ void bdp_lib_tally_host(const uint8_t *recs, const uint64_t *off, uint32_t n, co
 }
 
 int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn, const bdp_table_t *T, uint64_t *lib_counts, const bdp_optical_t *O,
-                     const bdp_bc_t *bc, uint64_t *no_barcode)
+                     const bdp_bc_t *bc, uint64_t *no_barcode, const bdp_group_t *grp)
 {
 	if (bc && bc->mode == BDP_BC_OFF) bc = nullptr;
+	if (!bc || !bc->pack) grp = nullptr;
+	std::vector<uint64_t> Bp;
 	if (no_barcode) *no_barcode = 0;
 	std::vector<uint64_t> Bw;
 	const uint32_t n = (uint32_t)(off.size() - 1);
@@ -236,8 +292,8 @@ int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t c
 	if (rc != BMH_OK) return rc;
 	counts[BDP_TEMPLATES] = E.size();
 	if (bc && no_barcode) *no_barcode = bdp_no_barcode(Bw.data(), Bw.size());
-	bdp_decide_host(E.data(), E.size(), bits, counts, T ? T->n_lib : 0, T ? lib_counts : nullptr, bc ? Bw.data() : nullptr);
-	if (O) bdp_optical_host(E.data(), locs.data(), E.size(), *O, T ? T->n_lib : 0, bc ? Bw.data() : nullptr);
+	bdp_decide_host(E.data(), E.size(), bits, counts, T ? T->n_lib : 0, T ? lib_counts : nullptr, bc ? Bw.data() : nullptr, grp, &Bp);
+	if (O) bdp_optical_host(E.data(), locs.data(), E.size(), *O, T ? T->n_lib : 0, grp ? Bp.data() : bc ? Bw.data() : nullptr);
 	if (T && lib_counts) bdp_lib_tally_host(recs, off.data(), n, tpl.data(), E.data(), E.size(), T->n_lib, lib_counts);
 	for (uint32_t i = 0; i < n; ++i) if (bits[tpl[i] >> 5] >> (tpl[i] & 31) & 1u) recs[off[i] + 19] |= 0x04;
 	return BMH_OK;
@@ -245,7 +301,7 @@ int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t c
 
 #ifndef BDP_STANDALONE
 static int markdup_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_table_t *T, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, const bdp_optical_t *O = nullptr,
-                        const bdp_bc_t *bc = nullptr, uint64_t *no_barcode = nullptr)
+                        const bdp_bc_t *bc = nullptr, uint64_t *no_barcode = nullptr, const bdp_group_t *grp = nullptr)
 {
 	if (!out || !counts || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*out = nullptr;
@@ -255,7 +311,7 @@ static int markdup_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, c
 	uint8_t *o = (uint8_t *)malloc(n_bytes + 1);
 	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
 	if (n_bytes) memcpy(o, recs, n_bytes);
-	if ((rc = bdp_markdup_host(o, off, counts, fn, T, lib_counts, O, bc, no_barcode)) != BMH_OK) { free(o); return rc; }
+	if ((rc = bdp_markdup_host(o, off, counts, fn, T, lib_counts, O, bc, no_barcode, grp)) != BMH_OK) { free(o); return rc; }
 	*out = o;
 	return BMH_OK;
 }
@@ -317,14 +373,18 @@ extern "C" int bmh_bam_dup_locations_host(const uint8_t *recs, uint64_t n_bytes,
 	return BMH_OK;
 }
 
-extern "C" int bmh_bam_markdup_barcode_host(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, int barcode_mode,
-                                            const char tag[2], uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode)
+// edits -1: barcodes compared exactly (grouped, lib_grouped unused)
+static int markdup_barcode_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, int barcode_mode,
+                                const char tag[2], int edits, uint64_t bc_max_set, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical,
+                                uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
 {
-	const char *fn = "bmh_bam_markdup_barcode_host";
 	bdp_table_t T; bdp_bc_t bc;
 	if (out) *out = nullptr;
 	int rc = bdp_barcode_check(barcode_mode, tag, fn, &bc);
 	if (rc != BMH_OK) return rc;
+	if ((rc = bdp_group_check(edits, bc_max_set, fn, &bc)) != BMH_OK) return rc;
+	if (bc.pack && !grouped) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (bc.pack) for (int k = 0; k < BDP_GRP_N; ++k) grouped[k] = 0;
 	const bool opt = distance != -1;
 	if (opt && !optical) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	if (opt && (rc = bdp_optical_check(distance, max_set, fn)) != BMH_OK) return rc;
@@ -332,18 +392,43 @@ extern "C" int bmh_bam_markdup_barcode_host(const uint8_t *recs, uint64_t n_byte
 	if (groups && (rc = bdp_table_make(T, rg_ids, rg_lib, n_groups, fn)) != BMH_OK) return rc;
 	if (opt && groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
 	const bdp_optical_t O = {distance, max_set ? (uint32_t)max_set : (uint32_t)BDP_OPT_MAX_SET, optical, groups ? lib_optical : nullptr};
-	return markdup_host(fn, recs, n_bytes, groups ? &T : nullptr, out, counts, groups ? lib_counts : nullptr, opt ? &O : nullptr, &bc, no_barcode);
+	const bdp_group_t grp = {(uint32_t)(edits < 0 ? 0 : edits), bc_max_set ? (uint32_t)bc_max_set : (uint32_t)BDP_BC_MAX_SET, grouped, groups ? lib_grouped : nullptr};
+	return markdup_host(fn, recs, n_bytes, groups ? &T : nullptr, out, counts, groups ? lib_counts : nullptr, opt ? &O : nullptr, &bc, no_barcode, bc.pack ? &grp : nullptr);
 }
 
+extern "C" int bmh_bam_markdup_barcode_host(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, int barcode_mode,
+                                            const char tag[2], uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode)
+{
+	return markdup_barcode_host("bmh_bam_markdup_barcode_host", recs, n_bytes, rg_ids, rg_lib, n_groups, distance, max_set, barcode_mode, tag, -1, 0, out, counts, lib_counts, optical, lib_optical,
+	                            no_barcode, nullptr, nullptr);
+}
+
+extern "C" int bmh_bam_markdup_barcode_edits_host(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
+                                                  int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3],
+                                                  uint64_t *lib_optical, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
+{
+	return markdup_barcode_host("bmh_bam_markdup_barcode_edits_host", recs, n_bytes, rg_ids, rg_lib, n_groups, distance, max_set, barcode_mode, tag, edits, barcode_max_set, out, counts, lib_counts,
+	                            optical, lib_optical, no_barcode, grouped, lib_grouped);
+}
+
+static int dup_barcodes_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], bool pack, uint64_t **words, uint64_t *n_templates);
 extern "C" int bmh_bam_dup_barcodes_host(const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], uint64_t **words, uint64_t *n_templates)
 {
-	const char *fn = "bmh_bam_dup_barcodes_host";
+	return dup_barcodes_host("bmh_bam_dup_barcodes_host", recs, n_bytes, barcode_mode, tag, false, words, n_templates);
+}
+extern "C" int bmh_bam_dup_barcodes_packed_host(const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], uint64_t **words, uint64_t *n_templates)
+{
+	return dup_barcodes_host("bmh_bam_dup_barcodes_packed_host", recs, n_bytes, barcode_mode, tag, true, words, n_templates);
+}
+static int dup_barcodes_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], bool pack, uint64_t **words, uint64_t *n_templates)
+{
 	if (!words || !n_templates || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*words = nullptr; *n_templates = 0;
 	bdp_bc_t bc;
 	int rc = bdp_barcode_check(barcode_mode, tag, fn, &bc);
 	if (rc != BMH_OK) return rc;
 	if (bc.mode == BDP_BC_OFF) { bmh_set_error("%s: no barcode source (1: a tag, 2: the read name)", fn); return BMH_EINVAL; }
+	bc.pack = pack ? 1 : 0;
 	std::vector<uint64_t> off;
 	if ((rc = bsr_walk(recs, n_bytes, -1, off, fn)) != BMH_OK) return rc;
 	const uint32_t n = (uint32_t)(off.size() - 1);
@@ -359,6 +444,12 @@ extern "C" int bmh_bam_dup_barcodes_host(const uint8_t *recs, uint64_t n_bytes, 
 }
 
 extern "C" uint64_t bmh_barcode_word(const uint8_t *value, uint64_t n) { return value || !n ? bdp_barcode_word(value, n) : 0; }
+
+extern "C" int bmh_barcode_pack(const uint8_t *value, uint64_t n, uint64_t *word)
+{
+	if (!word || (n && !value)) { bmh_set_error("bmh_barcode_pack: null argument"); return BMH_EINVAL; }
+	return bdp_barcode_pack(value, n, word) ? 1 : 0;
+}
 
 extern "C" int bmh_bam_name_location(const char *name, uint32_t len, uint32_t out[3])
 {

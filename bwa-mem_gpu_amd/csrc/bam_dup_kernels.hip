@@ -22,6 +22,13 @@
 //               (or its name to the last field), hashes the value in one walk and writes one 64-bit word per template into a side array; at the decision the
 //               words go up once, the pair pass and the fragment pass each take one more stable radix pass on them (LSD order rank, barcode, hi, lo; and
 //               fragment word, barcode, end word), and the lanes that compare keys -- pair decide, run heads, the optical set heads -- compare the word too
+//   grouping    only when the run groups barcodes by edits (csrc/bam_dup_core.h): per batch the entries kernel's PACK instance packs the value instead of hashing it.
+//               At the decision, before the pair pass and again before the fragment pass's sorts, over the pass's barcoded elements (pairs; items): stable radix
+//               passes to (key, word) order, heads of equal (key, word) and of equal key with their scans, one member per distinct (key, word) compacted with
+//               its key's first member, one lane per member walking the later members of its key -- one xor, three folds and a popcount per candidate -- and
+//               uniting in the optical step's union-find (members ascend by word inside a key, so a root is its component's smallest word), members, roots
+//               and keys over the cap counted per library in LDS, and every element's canonical word written: by template for the pair pass (which pair
+//               decide and the optical set heads then compare), by item for the fragment pass (whose barcode radix pass and run heads then read it)
 //   per window  one lane per record tests the bitmap through the record's global template ordinal and ORs 0x04 into byte 19 (a byte store: records are unaligned)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -75,7 +82,8 @@ __global__ void __launch_bounds__(256) bdp_starts(const uint32_t *__restrict__ h
 // LOC: optical duplicates are counted -- the lane holds the template's first record and parses its name: locs [t]
 // BC: barcodes are compared -- the lane walks its first record's tags to the barcode's, or its name to the last field, hashes the value in one walk and writes the
 // word: bcs [t]; info [6], [7]: the first template whose tag is of another type than Z / whose tags cannot be walked, as info [1]
-template <bool LIB, bool LOC, bool BC>
+// BC 2: the words are packed, not hashed (grouping by edits) -- info [8]: the first template whose value does not pack
+template <bool LIB, bool LOC, int BC>
 __global__ void __launch_bounds__(256) bdp_entries(const uint8_t *__restrict__ recs, const uint64_t *__restrict__ off, uint32_t n, uint64_t total, const uint32_t *__restrict__ start,
                                                    bdp_entry_t *__restrict__ entries, uint32_t *info, bdp_groups_t G, bdp_loc_t *__restrict__ locs, bdp_bc_t bc, uint64_t *__restrict__ bcs)
 {
@@ -96,8 +104,8 @@ __global__ void __launch_bounds__(256) bdp_entries(const uint8_t *__restrict__ r
 	if (BC) {
 		uint64_t w = 0;
 		if (inside) {                                                 // (record a lies inside the buffer: off [a + 1] <= off [b] <= total)
-			const int bs = bdp_barcode(recs + off[a], off[a + 1] - off[a], bc, &w);
-			if (bs != BDP_AUX_FOUND) atomicMin(info + (bs == BDP_AUX_TYPE ? 6 : 7), a + 1);
+			const int bs = bdp_barcode(recs + off[a], off[a + 1] - off[a], bc, &w, BC == 2);
+			if (bs != BDP_AUX_FOUND) atomicMin(info + (bs == BDP_AUX_TYPE ? 6 : BC == 2 && bs == BDP_AUX_PACK ? 8 : 7), a + 1);
 		}
 		bcs[t] = w;
 	}
@@ -216,12 +224,12 @@ __global__ void __launch_bounds__(256) bdp_frag_keys(const bdp_entry_t *__restri
 }
 
 // word: the sorted end words; hidx [i] = i where a run begins, else 0
-// BC: a run is the items of one (end word, barcode word) -- item: the items in sorted order, B [template]
-template <bool BC>
+// BC: a run is the items of one (end word, barcode word) -- item: the items in sorted order, B [template] (1) or, grouped by edits, B [item id] (2)
+template <int BC>
 __global__ void __launch_bounds__(256) bdp_run_heads(const uint64_t *__restrict__ word, uint64_t m, uint32_t *__restrict__ hidx, const uint32_t *__restrict__ item, const uint64_t *__restrict__ B)
 {
 	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-	if (i < m) hidx[i] = i && (word[i] != word[i - 1] || (BC && B[item[i] >> 1] != B[item[i - 1] >> 1])) ? (uint32_t)i : 0u;
+	if (i < m) hidx[i] = i && (word[i] != word[i - 1] || (BC && B[item[i] >> (BC == 1 ? 1 : 0)] != B[item[i - 1] >> (BC == 1 ? 1 : 0)])) ? (uint32_t)i : 0u;
 }
 
 // first [i]: the index of the first item of lane i's run (the max-scan of hidx)
@@ -387,6 +395,110 @@ __global__ void __launch_bounds__(256) bdp_opt_counts(const bdp_entry_t *__restr
 	for (uint32_t k = threadIdx.x; k < 2 * nl; k += 256) if (opt_s[k]) atomicAdd(oc + 4 * (k / 2) + 2 + k % 2, (unsigned long long)opt_s[k]);
 }
 
+// ---- grouping barcodes by edits (csrc/bam_dup_core.h).  An element is a barcoded pair (idx: a permutation of the templates) or, FRAG, a barcoded item of the fragment
+// pass (idx: item ids); its key is (lo, hi) or the item's end word
+
+template <bool FRAG>
+__device__ inline bool bdp_grp_elem(const bdp_entry_t *__restrict__ E, const uint64_t *__restrict__ B, uint32_t id, uint64_t *a, uint64_t *b, uint64_t *w, uint32_t *t)
+{
+	*t = FRAG ? id >> 1 : id;
+	const bdp_entry_t e = E[*t];
+	*w = B[*t];
+	*a = FRAG && (id & 1u) ? e.hi : e.lo; *b = FRAG ? 0ull : e.hi;
+	return *w != 0 && (FRAG ? bdp_kind(e) != BDP_NONE : bdp_kind(e) == BDP_PAIR);
+}
+
+// the key of radix pass k (0: word, 1: hi, 2: lo or the end word) through the permutation so far; what is no element sorts behind the elements
+template <bool FRAG>
+__global__ void __launch_bounds__(256) bdp_grp_keys(const bdp_entry_t *__restrict__ E, const uint64_t *__restrict__ B, const uint32_t *__restrict__ idx, uint64_t n, int pass, uint64_t *__restrict__ key)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	uint64_t a, b, w; uint32_t t;
+	const bool el = bdp_grp_elem<FRAG>(E, B, idx[i], &a, &b, &w, &t);
+	key[i] = !el ? ~0ull : pass == 0 ? w : pass == 1 ? b : a;
+}
+
+// hw [i] = 1 where a distinct (key, word) begins, hk [i] = 1 where a key begins, among the elements in sorted order
+template <bool FRAG>
+__global__ void __launch_bounds__(256) bdp_grp_heads(const bdp_entry_t *__restrict__ E, const uint64_t *__restrict__ B, const uint32_t *__restrict__ idx, uint64_t n, uint32_t *__restrict__ hw,
+                                                     uint32_t *__restrict__ hk)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	uint64_t a, b, w, pa = 0, pb = 0, pw = 0; uint32_t t;
+	const bool el = bdp_grp_elem<FRAG>(E, B, idx[i], &a, &b, &w, &t);
+	const bool prev = el && i && bdp_grp_elem<FRAG>(E, B, idx[i - 1], &pa, &pb, &pw, &t);
+	const bool same_key = prev && pa == a && pb == b;
+	hk[i] = el && !same_key ? 1u : 0u;
+	hw[i] = el && !(same_key && pw == w) ? 1u : 0u;
+}
+
+// wid, kid: the inclusive scans of hw and hk (an element's member is wid - 1, its key kid - 1).  The head of a member writes its word, key and template and makes it
+// its own root; the head of a key writes where the key's members begin: kstart has nk + 1 places, the last one m
+template <bool FRAG>
+__global__ void __launch_bounds__(256) bdp_grp_compact(const bdp_entry_t *__restrict__ E, const uint64_t *__restrict__ B, const uint32_t *__restrict__ idx, uint64_t n, const uint32_t *__restrict__ wid,
+                                                       const uint32_t *__restrict__ kid, uint32_t m, uint32_t nk, uint64_t *__restrict__ mword, uint32_t *__restrict__ mkey, uint32_t *__restrict__ mtpl,
+                                                       uint32_t *__restrict__ parent, uint32_t *__restrict__ kstart)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	if (i == 0) kstart[nk] = m;
+	const uint32_t q = wid[i], k = kid[i];
+	if (q == (i ? wid[i - 1] : 0u) || q == 0 || q > m || k == 0 || k > nk) return;      // (no head; or a place outside the arrays: never, and never written)
+	uint64_t a, b, w; uint32_t t;
+	(void)bdp_grp_elem<FRAG>(E, B, idx[i], &a, &b, &w, &t);
+	const uint32_t p = q - 1;
+	mword[p] = w; mkey[p] = k - 1; mtpl[p] = t; parent[p] = p;
+	if (k != (i ? kid[i - 1] : 0u)) kstart[k - 1] = p;
+}
+
+// one lane per member: bdp_bc_walk over the later members of its key -- bounded by m, its finds by parent [v] <= v; a key over the cap is left alone
+__global__ void __launch_bounds__(256) bdp_grp_cluster(const uint64_t *__restrict__ mword, const uint32_t *__restrict__ mkey, const uint32_t *__restrict__ kstart, uint32_t m, uint32_t nk, uint32_t edits,
+                                                       uint32_t max_set, uint32_t *parent)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= m) return;
+	const uint32_t k = mkey[i];
+	if (k >= nk || kstart[k + 1] - kstart[k] > max_set) return;
+	bdp_bc_walk(i, m, mkey, mword, edits, parent);
+}
+
+// gc [3 * lib + BDP_GRP_*]: += the members and those that are their own root (pairs: the pair pass alone counts them) and the keys over the cap, counted at their
+// first member -- through a histogram in LDS (3 * n_lib 32-bit words; n_lib 0: one library, the entries carry none)
+__global__ void __launch_bounds__(256) bdp_grp_counts(const bdp_entry_t *__restrict__ E, const uint32_t *__restrict__ mtpl, const uint32_t *__restrict__ mkey, const uint32_t *__restrict__ kstart,
+                                                      const uint32_t *__restrict__ parent, uint32_t m, uint32_t nk, uint32_t max_set, uint32_t n_lib, bool pairs, unsigned long long *gc)
+{
+	extern __shared__ uint32_t grp_s[];
+	const uint32_t nl = n_lib ? n_lib : 1u;
+	for (uint32_t k = threadIdx.x; k < BDP_GRP_N * nl; k += 256) grp_s[k] = 0;
+	__syncthreads();
+	const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+	if (j < m) {
+		const uint32_t lib = n_lib ? bdp_lib_of(E[mtpl[j]]) : 0u, k = mkey[j];
+		if (lib < nl) {
+			if (pairs) { atomicAdd(grp_s + BDP_GRP_N * lib + BDP_GRP_OBSERVED, 1u); if (parent[j] == j) atomicAdd(grp_s + BDP_GRP_N * lib + BDP_GRP_INFERRED, 1u); }
+			if (k < nk && kstart[k] == j && kstart[k + 1] - j > max_set) atomicAdd(grp_s + BDP_GRP_N * lib + BDP_GRP_SKIPPED, 1u);
+		}
+	}
+	__syncthreads();
+	for (uint32_t k = threadIdx.x; k < BDP_GRP_N * nl; k += 256) if (grp_s[k]) atomicAdd(gc + k, (unsigned long long)grp_s[k]);
+}
+
+// every element's canonical word -- its member's root's -- and every other's own: out [template], or FRAG out [item id]
+template <bool FRAG>
+__global__ void __launch_bounds__(256) bdp_grp_write(const bdp_entry_t *__restrict__ E, const uint64_t *__restrict__ B, const uint32_t *__restrict__ idx, uint64_t n, const uint32_t *__restrict__ wid,
+                                                     const uint64_t *__restrict__ mword, uint32_t *parent, uint32_t m, uint64_t *__restrict__ out)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t id = idx[i];
+	uint64_t a, b, w; uint32_t t;
+	const bool el = bdp_grp_elem<FRAG>(E, B, id, &a, &b, &w, &t);
+	const uint32_t q = wid[i];
+	out[id] = el && q >= 1 && q <= m ? mword[bdp_uf_find(parent, q - 1)] : w;
+}
+
 // ---- the flags of a window
 __global__ void __launch_bounds__(256) bdp_flag(uint8_t *__restrict__ recs, const uint64_t *__restrict__ off, const uint32_t *__restrict__ tord, uint32_t n, uint64_t total,
                                                 const uint32_t *__restrict__ bits, uint64_t n_tpl)
@@ -401,6 +513,43 @@ __global__ void __launch_bounds__(256) bdp_flag(uint8_t *__restrict__ recs, cons
 
 unsigned blocks(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
+// The arrays of one grouping of barcodes by edits: the decision's key and value arrays (free when it runs) and the step's own -- wid [n], mkey, mtpl, parent [m],
+// kstart [m + 1]; tmp: the sorts' (sb) and the scans' (ib) work space; gc [3 * libraries]: the counters
+struct grp_arrays_t { uint64_t *ka, *kb; uint32_t *va, *vb, *wid, *mkey, *mtpl, *parent, *kstart; void *tmp; size_t sb, ib; unsigned long long *gc; };
+
+// n elements behind W.va (templates, or FRAG item ids) -> out: every element's canonical word (csrc/bam_dup_core.h), by template or by item id; the counts are added
+// to W.gc.  One wait for the device: the members and the keys
+template <bool FRAG>
+int bdp_group_device(hipStream_t st, const bdp_entry_t *dE, const uint64_t *B, uint64_t n, grp_arrays_t W, const bdp_group_t &G, uint32_t n_lib, uint64_t *out)
+{
+	if (!n) return BMH_OK;
+	for (int pass = 0; pass < 3; ++pass) {
+		if (FRAG && pass == 1) continue;
+		bdp_grp_keys<FRAG><<<blocks(n), 256, 0, st>>>(dE, B, W.va, n, pass, W.ka);
+		HIPCK(rocprim::radix_sort_pairs(W.tmp, W.sb, W.ka, W.kb, W.va, W.vb, (size_t)n, 0, 64, st));
+		std::swap(W.va, W.vb);
+	}
+	// va: the elements in (key, word) order; vb takes the key heads and their scan, ka the members' words
+	uint32_t *kid = W.vb; uint64_t *mword = W.ka;
+	bdp_grp_heads<FRAG><<<blocks(n), 256, 0, st>>>(dE, B, W.va, n, W.wid, kid);
+	HIPCK(rocprim::inclusive_scan(W.tmp, W.ib, W.wid, W.wid, (size_t)n, rocprim::plus<uint32_t>(), st));      // (in place: heads -> members + 1, keys + 1)
+	HIPCK(rocprim::inclusive_scan(W.tmp, W.ib, kid, kid, (size_t)n, rocprim::plus<uint32_t>(), st));
+	uint32_t m = 0, nk = 0;
+	HIPCK(hipMemcpyAsync(&m, W.wid + (n - 1), 4, hipMemcpyDeviceToHost, st));
+	HIPCK(hipMemcpyAsync(&nk, kid + (n - 1), 4, hipMemcpyDeviceToHost, st));
+	HIPCK(hipStreamSynchronize(st));
+	if (m > n || nk > m) { bmh_set_error("duplicate marking: internal error: %u distinct barcodes on %u keys among %llu elements", m, nk, (unsigned long long)n); return BMH_EINVAL; }
+	if (m) {
+		const uint32_t nl = n_lib ? n_lib : 1u;
+		bdp_grp_compact<FRAG><<<blocks(n), 256, 0, st>>>(dE, B, W.va, n, W.wid, kid, m, nk, mword, W.mkey, W.mtpl, W.parent, W.kstart);
+		bdp_grp_cluster<<<blocks(m), 256, 0, st>>>(mword, W.mkey, W.kstart, m, nk, G.edits, G.max_set, W.parent);
+		bdp_grp_counts<<<blocks(m), 256, 4 * BDP_GRP_N * nl, st>>>(dE, W.mtpl, W.mkey, W.kstart, W.parent, m, nk, G.max_set, n_lib, !FRAG, W.gc);
+	}
+	bdp_grp_write<FRAG><<<blocks(n), 256, 0, st>>>(dE, B, W.va, n, W.wid, mword, W.parent, m, out);
+	HIPCK(hipGetLastError());
+	return BMH_OK;
+}
+
 }   // namespace
 
 bdp_dev_t *bdp_dev_create(void) { return new bdp_dev_t(); }
@@ -414,11 +563,12 @@ int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off,
 	hipStream_t st = (hipStream_t)stream;
 	size_t tb = scan_tmp_bytes<uint32_t, uint32_t, true>((size_t)n + 1);
 	RCK(d->head.need(4 * ((size_t)n + 1))); RCK(d->tpl.need(4 * ((size_t)n + 1))); RCK(d->start.need(4 * ((size_t)n + 2))); RCK(d->entries.need(sizeof(bdp_entry_t) * ((size_t)n + 1)));
-	RCK(d->info.need(4 * BDP_INFO_WORDS)); RCK(d->tmp.need(tb));
+	const bool pack = want_bc && bc->pack;
+	RCK(d->info.need(4 * (pack ? BDP_INFO_WORDS_PACK : BDP_INFO_WORDS))); RCK(d->tmp.need(tb));
 	if (d_locs) RCK(d->locs.need(sizeof(bdp_loc_t) * ((size_t)n + 1)));
 	if (want_bc) RCK(d->bcs.need(8 * ((size_t)n + 1)));
-	static const uint32_t init[BDP_INFO_WORDS] = {0u, 0xffffffffu, 0u, 0u, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-	HIPCK(hipMemcpyAsync(d->info.p, init, 4 * BDP_INFO_WORDS, hipMemcpyHostToDevice, st));
+	static const uint32_t init[BDP_INFO_WORDS_PACK] = {0u, 0xffffffffu, 0u, 0u, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+	HIPCK(hipMemcpyAsync(d->info.p, init, 4 * (pack ? BDP_INFO_WORDS_PACK : BDP_INFO_WORDS), hipMemcpyHostToDevice, st));
 	if (n) {
 		bdp_heads<<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, (uint32_t *)d->head.p, (uint32_t *)d->info.p);
 		HIPCK(rocprim::inclusive_scan(d->tmp.p, tb, (uint32_t *)d->head.p, (uint32_t *)d->tpl.p, (size_t)n, rocprim::plus<uint32_t>(), st));
@@ -426,18 +576,25 @@ int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off,
 		const bdp_groups_t G = {(const char *)d->g_ids.p, (const uint32_t *)d->g_off.p, (const uint8_t *)d->g_lib.p, d->g_n};
 		const uint32_t *sp = (const uint32_t *)d->start.p; bdp_entry_t *ep = (bdp_entry_t *)d->entries.p; uint32_t *ip = (uint32_t *)d->info.p; bdp_loc_t *lp = (bdp_loc_t *)d->locs.p;
 		const bdp_bc_t no_bc = {BDP_BC_OFF, 0, 0};
-		if (want_bc) {
+		if (pack) {
 			uint64_t *bp = (uint64_t *)d->bcs.p;
 			if (d_locs) {
-				if (d->g_n) bdp_entries<true, true, true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, *bc, bp);
-				else bdp_entries<false, true, true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, *bc, bp);
-			} else if (d->g_n) bdp_entries<true, false, true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, *bc, bp);
-			else bdp_entries<false, false, true><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, *bc, bp);
+				if (d->g_n) bdp_entries<true, true, 2><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, *bc, bp);
+				else bdp_entries<false, true, 2><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, *bc, bp);
+			} else if (d->g_n) bdp_entries<true, false, 2><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, *bc, bp);
+			else bdp_entries<false, false, 2><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, *bc, bp);
+		} else if (want_bc) {
+			uint64_t *bp = (uint64_t *)d->bcs.p;
+			if (d_locs) {
+				if (d->g_n) bdp_entries<true, true, 1><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, *bc, bp);
+				else bdp_entries<false, true, 1><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, *bc, bp);
+			} else if (d->g_n) bdp_entries<true, false, 1><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, *bc, bp);
+			else bdp_entries<false, false, 1><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, *bc, bp);
 		} else if (d_locs) {
-			if (d->g_n) bdp_entries<true, true, false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, no_bc, nullptr);
-			else bdp_entries<false, true, false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, no_bc, nullptr);
-		} else if (d->g_n) bdp_entries<true, false, false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, no_bc, nullptr);
-		else bdp_entries<false, false, false><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, no_bc, nullptr);
+			if (d->g_n) bdp_entries<true, true, 0><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, no_bc, nullptr);
+			else bdp_entries<false, true, 0><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, lp, no_bc, nullptr);
+		} else if (d->g_n) bdp_entries<true, false, 0><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, no_bc, nullptr);
+		else bdp_entries<false, false, 0><<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, sp, ep, ip, G, nullptr, no_bc, nullptr);
 		HIPCK(hipGetLastError());
 	}
 	if (d_locs) *d_locs = (const bdp_loc_t *)d->locs.p;
@@ -476,10 +633,13 @@ int bdp_dev_set_groups(bdp_dev_t *d, const bdp_table_t *T, void *stream)
 }
 
 int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records, uint32_t n_lib, uint64_t *lib_counts,
-                      const bdp_optical_t *O, const bdp_loc_t *locs, double *opt_ms, const uint64_t *bcs)
+                      const bdp_optical_t *O, const bdp_loc_t *locs, double *opt_ms, const uint64_t *bcs, const bdp_group_t *G)
 {
 	hipStream_t st = (hipStream_t)stream;
 	for (int k = 0; k < 5; ++k) counts[k] = 0;
+	if (!bcs) G = nullptr;
+	const uint32_t g_lib = G && G->lib_out ? n_lib : 0;                    // (as the optical counts: per library whether or not lib_counts is asked for)
+	if (G) { for (int k = 0; k < BDP_GRP_N; ++k) G->out[k] = 0; for (uint32_t k = 0; k < BDP_GRP_N * g_lib; ++k) G->lib_out[k] = 0; }
 	const uint32_t o_lib = O && O->lib_out ? n_lib : 0;                    // (the optical counts per library do not hang on lib_counts)
 	if (O) { for (int k = 0; k < BDP_OPT_N; ++k) O->out[k] = 0; for (uint32_t k = 0; k < BDP_OPT_N * o_lib; ++k) O->lib_out[k] = 0; }
 	if (O && T && !locs) { bmh_set_error("duplicate marking: internal error: optical duplicates without the templates' locations"); return BMH_EINVAL; }
@@ -493,7 +653,9 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 	if (T >= 1ull << 31) { bmh_set_error("duplicate marking: %llu templates: the decision takes fewer than 2^31", (unsigned long long)T); return BMH_EINVAL; }
 	// entries, two key and two value arrays of up to 2 T items (T templates in the pair pass), the item counts and their scan, the sorts' work space, the bitmap:
 	// 24 + 2 * (16 + 8) + 8 = 80 bytes per template and the work space -- freed before the final sort allocates its own (with barcodes 88)
-	const size_t M = 2 * (size_t)T; size_t sb = sort_pairs_tmp_bytes<uint64_t, uint32_t>(M); const size_t cb = std::max(std::max(scan_tmp_bytes<uint32_t, uint32_t>((size_t)T + 1), max_scan_tmp_bytes<uint32_t>(M)), sb);
+	const size_t M = 2 * (size_t)T; size_t sb = sort_pairs_tmp_bytes<uint64_t, uint32_t>(M);
+	const size_t gib = G ? scan_tmp_bytes<uint32_t, uint32_t, true>(M) : 0;      // (grouping by edits scans the heads of up to M items)
+	const size_t cb = std::max(std::max(std::max(scan_tmp_bytes<uint32_t, uint32_t>((size_t)T + 1), max_scan_tmp_bytes<uint32_t>(M)), sb), gib);
 	size_t fr = 0, tot = 0;
 	HIPCK(hipMemGetInfo(&fr, &tot));
 	// (a buffer is allocated a quarter larger than asked: that is what is counted)
@@ -501,7 +663,10 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 	const size_t opt_ask = O ? sizeof(bdp_loc_t) * (size_t)T + 8 * 4 * (size_t)(o_lib ? o_lib : 1) : 0;
 	// barcodes: 8 bytes per template more -- the words; their two radix passes run in the key and value arrays of the passes beside them
 	const size_t bc_ask = bcs ? 8 * (size_t)T : 0;
-	const size_t ask = sizeof(bdp_entry_t) * (size_t)T + 2 * 8 * M + 2 * 4 * M + 2 * 4 * ((size_t)T + 1) + cb + opt_ask + bc_ask, want = ask + ask / 4 + (64u << 20);
+	// grouping by edits: 56 bytes per template more -- the canonical words of a pass (by template, then by item: 16), and for up to M elements their members
+	// (4), the members' keys and templates (8), the union-find and the keys' starts (8); the sorts, the key heads and the members' words live in the key and value arrays
+	const size_t grp_ask = G ? 8 * M + 4 * M + 8 * M + 4 * M + 4 * (M + 2) + 8 * BDP_GRP_N * (size_t)(g_lib ? g_lib : 1) : 0;
+	const size_t ask = sizeof(bdp_entry_t) * (size_t)T + 2 * 8 * M + 2 * 4 * M + 2 * 4 * ((size_t)T + 1) + cb + opt_ask + bc_ask + grp_ask, want = ask + ask / 4 + (64u << 20);
 	// the final sort that follows: keys and ordinals in and out, 24 bytes per record, a quarter more as allocated, and its work space
 	const size_t sort_ask = 24 * (size_t)n_records + (n_records ? sort_pairs_tmp_bytes<uint64_t, uint32_t>((size_t)n_records) : 0), sort_want = sort_ask + sort_ask / 4 + (64u << 20);
 	if (want <= fr && sort_want > fr) {
@@ -510,7 +675,9 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 		return BMH_ENOMEM;
 	}
 	if (want > fr) {
-		if (O && bcs) bmh_set_error("sorted BAM: marking the duplicates among %llu templates by their barcodes and counting the optical ones needs %zu bytes of device memory (%zu of them the templates' locations and the optical step's counters, %zu the barcode words), %zu are free (align fewer reads per run, or on a device with more memory)",
+		if (G) bmh_set_error("sorted BAM: marking the duplicates among %llu templates with their barcodes grouped by edits needs %zu bytes of device memory (%zu of them the grouping's), %zu are free (align fewer reads per run, or on a device with more memory)",
+		                     (unsigned long long)T, want, grp_ask + grp_ask / 4, fr);
+		else if (O && bcs) bmh_set_error("sorted BAM: marking the duplicates among %llu templates by their barcodes and counting the optical ones needs %zu bytes of device memory (%zu of them the templates' locations and the optical step's counters, %zu the barcode words), %zu are free (align fewer reads per run, or on a device with more memory)",
 		                            (unsigned long long)T, want, opt_ask + opt_ask / 4, bc_ask + bc_ask / 4, fr);
 		else if (bcs) bmh_set_error("sorted BAM: marking the duplicates among %llu templates by their barcodes needs %zu bytes of device memory (%zu of them the barcode words), %zu are free (align fewer reads per run, or on a device with more memory)",
 		                            (unsigned long long)T, want, bc_ask + bc_ask / 4, fr);
@@ -538,18 +705,30 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 		HIPCK(hipMemcpyAsync(dB.p, bcs, 8 * (size_t)T, hipMemcpyHostToDevice, st));
 	}
 	const uint64_t *B = (const uint64_t *)dB.p;
+	// grouping by edits: the pair pass's canonical words first, in the arrays the pair pass then takes; the pass compares them in place of the words
+	dev_buf<uint8_t> gW, g0, g1, g2, gcb; std::vector<unsigned long long> h_gc;
+	grp_arrays_t GA = {};
+	if (G) {
+		const uint32_t nl = g_lib ? g_lib : 1u;
+		RCK(gW.need(8 * M)); RCK(g0.need(4 * M)); RCK(g1.need(8 * M)); RCK(g2.need(4 * M + 4 * (M + 2))); RCK(gcb.need(8 * BDP_GRP_N * (size_t)nl));
+		HIPCK(hipMemsetAsync(gcb.p, 0, 8 * BDP_GRP_N * (size_t)nl, st));
+		GA = {ka, kb, va, vb, (uint32_t *)g0.p, (uint32_t *)g1.p, (uint32_t *)g1.p + M, (uint32_t *)g2.p, (uint32_t *)g2.p + M, tmp.p, sb, gib, (unsigned long long *)gcb.p};
+		bdp_iota<<<blocks(T), 256, 0, st>>>(va, T);
+		RCK(bdp_group_device<false>(st, dE, B, T, GA, *G, g_lib, (uint64_t *)gW.p));
+	}
+	const uint64_t *Bp = G ? (const uint64_t *)gW.p : B;
 	bdp_iota<<<blocks(T), 256, 0, st>>>(va, T);
 	for (int pass = 0; pass < 3; ++pass) {
 		bdp_pair_keys<<<blocks(T), 256, 0, st>>>(dE, va, T, pass, ka);
 		HIPCK(rocprim::radix_sort_pairs(tmp.p, sb, ka, kb, va, vb, (size_t)T, 0, 64, st));
 		std::swap(va, vb);
 		if (pass == 0 && bcs) {
-			bdp_bc_keys<<<blocks(T), 256, 0, st>>>(B, va, T, 0, ka);
+			bdp_bc_keys<<<blocks(T), 256, 0, st>>>(Bp, va, T, 0, ka);
 			HIPCK(rocprim::radix_sort_pairs(tmp.p, sb, ka, kb, va, vb, (size_t)T, 0, 64, st));
 			std::swap(va, vb);
 		}
 	}
-	if (bcs) bdp_pair_decide<true><<<blocks(T), 256, 0, st>>>(dE, va, T, (uint32_t *)d->bits.p, dcnt, B);
+	if (bcs) bdp_pair_decide<true><<<blocks(T), 256, 0, st>>>(dE, va, T, (uint32_t *)d->bits.p, dcnt, Bp);
 	else bdp_pair_decide<false><<<blocks(T), 256, 0, st>>>(dE, va, T, (uint32_t *)d->bits.p, dcnt, nullptr);
 	// the optical step, on va as the pair pass left it.  Until the compaction it keeps its words in cnt, base and vb; from there on the pair pass's arrays are free
 	// and take the members (m <= T of them): ka -- sort words in, values in and out; kb -- sort words out, templates, set heads; va -- x, y; vb -- tile, parent
@@ -566,7 +745,7 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 		uint32_t *head = (uint32_t *)cnt.p, *sid = (uint32_t *)base.p, *start = vb;      // (start: T + 1 of vb's 2 T places)
 		size_t ib = scan_tmp_bytes<uint32_t, uint32_t, true>((size_t)T + 1);
 		if (ib > cb) { bmh_set_error("duplicate marking: internal error: the optical step's scan asks for %zu bytes of work space, %zu are there", ib, cb); return BMH_EINVAL; }
-		if (bcs) bdp_opt_heads<true><<<blocks(T), 256, 0, st>>>(dE, va, T, head, B);
+		if (bcs) bdp_opt_heads<true><<<blocks(T), 256, 0, st>>>(dE, va, T, head, Bp);
 		else bdp_opt_heads<false><<<blocks(T), 256, 0, st>>>(dE, va, T, head, nullptr);
 		HIPCK(rocprim::inclusive_scan(tmp.p, ib, head, sid, (size_t)T, rocprim::plus<uint32_t>(), st));
 		bdp_opt_starts<<<blocks(T), 256, 0, st>>>(dE, va, T, sid, start);
@@ -606,12 +785,18 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 	if (m > M) { bmh_set_error("duplicate marking: internal error: %llu items of %llu templates", (unsigned long long)m, (unsigned long long)T); return BMH_EINVAL; }
 	if (m) {
 		bdp_items<<<blocks(T), 256, 0, st>>>(dE, T, (const uint32_t *)cnt.p, (const uint32_t *)base.p, m, va);
+		if (G) {                                                          // (the pair pass's canonical words have been read: gW takes the items')
+			GA.ka = ka; GA.kb = kb; GA.va = va; GA.vb = vb;
+			RCK(bdp_group_device<true>(st, dE, B, m, GA, *G, g_lib, (uint64_t *)gW.p));
+			bdp_items<<<blocks(T), 256, 0, st>>>(dE, T, (const uint32_t *)cnt.p, (const uint32_t *)base.p, m, va);      // (the grouping has sorted its items: these are the pass's again)
+		}
 		for (int pass = 0; pass < 2; ++pass) {
 			bdp_frag_keys<<<blocks(m), 256, 0, st>>>(dE, va, m, pass, ka);
 			HIPCK(rocprim::radix_sort_pairs(tmp.p, sb, ka, kb, va, vb, (size_t)m, 0, 64, st));
 			std::swap(va, vb);
 			if (pass == 0 && bcs) {                                       // (the items carry their templates' words: LSD order frag word, barcode, end word)
-				bdp_bc_keys<<<blocks(m), 256, 0, st>>>(B, va, m, 1, ka);
+				if (G) bdp_bc_keys<<<blocks(m), 256, 0, st>>>((const uint64_t *)gW.p, va, m, 0, ka);
+				else bdp_bc_keys<<<blocks(m), 256, 0, st>>>(B, va, m, 1, ka);
 				HIPCK(rocprim::radix_sort_pairs(tmp.p, sb, ka, kb, va, vb, (size_t)m, 0, 64, st));
 				std::swap(va, vb);
 			}
@@ -619,13 +804,18 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 		// kb: the sorted end words, va: the items in that order; vb is free: it takes the run heads' indices, whose max-scan goes into k0's bytes
 		uint32_t *hidx = vb, *first = (uint32_t *)k0.p;                   // (ka's bytes: the keys have been read)
 		size_t mb = max_scan_tmp_bytes<uint32_t>((size_t)m);
-		if (bcs) bdp_run_heads<true><<<blocks(m), 256, 0, st>>>(kb, m, hidx, va, B);
-		else bdp_run_heads<false><<<blocks(m), 256, 0, st>>>(kb, m, hidx, nullptr, nullptr);
+		if (G) bdp_run_heads<2><<<blocks(m), 256, 0, st>>>(kb, m, hidx, va, (const uint64_t *)gW.p);
+		else if (bcs) bdp_run_heads<1><<<blocks(m), 256, 0, st>>>(kb, m, hidx, va, B);
+		else bdp_run_heads<0><<<blocks(m), 256, 0, st>>>(kb, m, hidx, nullptr, nullptr);
 		HIPCK(rocprim::inclusive_scan(tmp.p, mb, hidx, first, (size_t)m, rocprim::maximum<uint32_t>(), st));
 		bdp_frag_decide<<<blocks(m), 256, 0, st>>>(dE, va, first, m, (uint32_t *)d->bits.p, dcnt);
 	}
 	unsigned long long h[5] = {0, 0, 0, 0, 0};
 	HIPCK(hipMemcpyAsync(h, dcnt, 8 * 5, hipMemcpyDeviceToHost, st));
+	if (G) {
+		h_gc.assign(BDP_GRP_N * (size_t)(g_lib ? g_lib : 1u), 0);
+		HIPCK(hipMemcpyAsync(h_gc.data(), gcb.p, 8 * h_gc.size(), hipMemcpyDeviceToHost, st));
+	}
 	dev_buf<uint8_t> lc;                                                  // (64 bytes per library: beside the decision's buffers nothing)
 	if (n_lib) {
 		RCK(lc.need(8 * BDP_N_COUNTS * (size_t)n_lib));
@@ -636,6 +826,7 @@ int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void
 	HIPCK(hipStreamSynchronize(st));
 	HIPCK(hipGetLastError());
 	for (int k = 0; k < 5; ++k) counts[k] = h[k];
+	for (size_t k = 0; k < h_gc.size(); ++k) { G->out[k % BDP_GRP_N] += h_gc[k]; if (g_lib) G->lib_out[k] = h_gc[k]; }
 	if (O) {
 		for (size_t l = 0; l < h_oc.size() / 4; ++l) {
 			const uint64_t v[BDP_OPT_N] = {h_oc[4 * l + 2] - h_oc[4 * l + 3], h_oc[4 * l], h_oc[4 * l + 1]};
@@ -664,9 +855,11 @@ int bdp_flag_device(bdp_dev_t *d, uint8_t *d_recs, const uint64_t *d_off, const 
 // O (or NULL): count the optical duplicates too; locs_only: stop at the templates' locations -- *out takes them, counts [BDP_TEMPLATES] their number
 // bc (or NULL): compare barcodes -- *no_barcode: the templates without one; bcs_only: stop at the templates' barcode words, as locs_only
 static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_table_t *G, void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts,
-                          const bdp_optical_t *O = nullptr, bool locs_only = false, const bdp_bc_t *bc = nullptr, uint64_t *no_barcode = nullptr, bool bcs_only = false)
+                          const bdp_optical_t *O = nullptr, bool locs_only = false, const bdp_bc_t *bc = nullptr, uint64_t *no_barcode = nullptr, bool bcs_only = false,
+                          const bdp_group_t *grp = nullptr)
 {
 	if (bc && bc->mode == BDP_BC_OFF) bc = nullptr;
+	if (!bc || !bc->pack) grp = nullptr;
 	if (no_barcode) *no_barcode = 0;
 	hipStream_t st = (hipStream_t)stream;
 	if (!out || !counts || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
@@ -687,10 +880,10 @@ static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes,
 	const uint32_t *d_tpl; const bdp_entry_t *d_e; const uint32_t *d_info; const bdp_loc_t *d_l = nullptr; const uint64_t *d_b = nullptr;
 	const bool want_locs = O || locs_only;
 	RCK(bdp_batch_device(&d, (const uint8_t *)in.p, (const uint64_t *)in_off.p, n, n_bytes, st, &d_tpl, &d_e, &d_info, want_locs ? &d_l : nullptr, bc, bc ? &d_b : nullptr));
-	uint32_t info[BDP_INFO_WORDS];
-	HIPCK(hipMemcpyAsync(info, d_info, 4 * BDP_INFO_WORDS, hipMemcpyDeviceToHost, st));
+	uint32_t info[BDP_INFO_WORDS_PACK];
+	HIPCK(hipMemcpyAsync(info, d_info, 4 * bdp_info_words(bc), hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
-	RCK(bdp_batch_check(n, info, G != nullptr, fn, bc != nullptr));
+	RCK(bdp_batch_check(n, info, G != nullptr, fn, bc != nullptr, bc && bc->pack));
 	const uint32_t T = n ? info[0] : 0;
 	if (T > n) { bmh_set_error("%s: internal error: %u templates among %u records", fn, T, n); return BMH_EINVAL; }
 	std::vector<bdp_entry_t> E(T); std::vector<uint32_t> tpl(n); std::vector<bdp_loc_t> L(want_locs ? T : 0); std::vector<uint64_t> Bw(bc ? T : 0);
@@ -714,7 +907,7 @@ static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes,
 		return BMH_OK;
 	}
 	if (bc && no_barcode) *no_barcode = bdp_no_barcode(Bw.data(), T);
-	RCK(bdp_decide_device(&d, E.data(), T, st, counts, 0, G ? G->n_lib : 0, G ? lib_counts : nullptr, O, O ? L.data() : nullptr, nullptr, bc ? Bw.data() : nullptr));
+	RCK(bdp_decide_device(&d, E.data(), T, st, counts, 0, G ? G->n_lib : 0, G ? lib_counts : nullptr, O, O ? L.data() : nullptr, nullptr, bc ? Bw.data() : nullptr, grp));
 	counts[BDP_SECSUP] = info[2]; counts[BDP_UNMAPPED] = info[3]; counts[BDP_TEMPLATES] = T;
 	if (G && lib_counts) bdp_lib_tally_host(recs, off.data(), n, tpl.data(), E.data(), T, G->n_lib, lib_counts);
 	RCK(bdp_flag_device(&d, (uint8_t *)in.p, (const uint64_t *)in_off.p, tpl.data(), n, n_bytes, st));
@@ -772,13 +965,17 @@ extern "C" int bmh_bam_dup_locations_device(const uint8_t *recs, uint64_t n_byte
 	return BMH_OK;
 }
 
-extern "C" int bmh_bam_markdup_barcode_device(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, int barcode_mode,
-                                              const char tag[2], void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode)
+// edits -1: barcodes compared exactly (grouped, lib_grouped unused)
+static int markdup_barcode_device(const char *fn, const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, int barcode_mode,
+                                  const char tag[2], int edits, uint64_t bc_max_set, void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical,
+                                  uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
 {
-	const char *fn = "bmh_bam_markdup_barcode_device";
 	bdp_table_t G; bdp_bc_t bc;
 	if (out) *out = nullptr;
 	RCK(bdp_barcode_check(barcode_mode, tag, fn, &bc));
+	RCK(bdp_group_check(edits, bc_max_set, fn, &bc));
+	if (bc.pack && !grouped) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (bc.pack) for (int k = 0; k < BDP_GRP_N; ++k) grouped[k] = 0;
 	const bool opt = distance != -1;
 	if (opt && !optical) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	if (opt) RCK(bdp_optical_check(distance, max_set, fn));
@@ -786,18 +983,43 @@ extern "C" int bmh_bam_markdup_barcode_device(const uint8_t *recs, uint64_t n_by
 	if (groups) RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
 	if (opt && groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
 	const bdp_optical_t O = {distance, max_set ? (uint32_t)max_set : (uint32_t)BDP_OPT_MAX_SET, optical, groups ? lib_optical : nullptr};
-	return markdup_device(fn, recs, n_bytes, groups ? &G : nullptr, stream, out, counts, groups ? lib_counts : nullptr, opt ? &O : nullptr, false, &bc, no_barcode);
+	const bdp_group_t grp = {(uint32_t)(edits < 0 ? 0 : edits), bc_max_set ? (uint32_t)bc_max_set : (uint32_t)BDP_BC_MAX_SET, grouped, groups ? lib_grouped : nullptr};
+	return markdup_device(fn, recs, n_bytes, groups ? &G : nullptr, stream, out, counts, groups ? lib_counts : nullptr, opt ? &O : nullptr, false, &bc, no_barcode, false, bc.pack ? &grp : nullptr);
 }
 
+extern "C" int bmh_bam_markdup_barcode_device(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, int barcode_mode,
+                                              const char tag[2], void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode)
+{
+	return markdup_barcode_device("bmh_bam_markdup_barcode_device", recs, n_bytes, rg_ids, rg_lib, n_groups, distance, max_set, barcode_mode, tag, -1, 0, stream, out, counts, lib_counts, optical,
+	                              lib_optical, no_barcode, nullptr, nullptr);
+}
+
+extern "C" int bmh_bam_markdup_barcode_edits_device(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
+                                                    int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts,
+                                                    uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
+{
+	return markdup_barcode_device("bmh_bam_markdup_barcode_edits_device", recs, n_bytes, rg_ids, rg_lib, n_groups, distance, max_set, barcode_mode, tag, edits, barcode_max_set, stream, out, counts,
+	                              lib_counts, optical, lib_optical, no_barcode, grouped, lib_grouped);
+}
+
+static int dup_barcodes_device(const char *fn, const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], bool pack, void *stream, uint64_t **words, uint64_t *n_templates);
 extern "C" int bmh_bam_dup_barcodes_device(const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], void *stream, uint64_t **words, uint64_t *n_templates)
 {
-	const char *fn = "bmh_bam_dup_barcodes_device";
+	return dup_barcodes_device("bmh_bam_dup_barcodes_device", recs, n_bytes, barcode_mode, tag, false, stream, words, n_templates);
+}
+extern "C" int bmh_bam_dup_barcodes_packed_device(const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], void *stream, uint64_t **words, uint64_t *n_templates)
+{
+	return dup_barcodes_device("bmh_bam_dup_barcodes_packed_device", recs, n_bytes, barcode_mode, tag, true, stream, words, n_templates);
+}
+static int dup_barcodes_device(const char *fn, const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], bool pack, void *stream, uint64_t **words, uint64_t *n_templates)
+{
 	bdp_bc_t bc;
 	if (words) *words = nullptr;
 	if (!words || !n_templates) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*n_templates = 0;
 	RCK(bdp_barcode_check(barcode_mode, tag, fn, &bc));
 	if (bc.mode == BDP_BC_OFF) { bmh_set_error("%s: no barcode source (1: a tag, 2: the read name)", fn); return BMH_EINVAL; }
+	bc.pack = pack ? 1 : 0;
 	uint64_t counts[BDP_N_COUNTS]; uint8_t *o = nullptr;
 	RCK(markdup_device(fn, recs, n_bytes, nullptr, stream, &o, counts, nullptr, nullptr, false, &bc, nullptr, true));
 	*words = (uint64_t *)o; *n_templates = counts[BDP_TEMPLATES];

@@ -80,8 +80,8 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 // every run of the store -> the record members of the sorted file (to the sink, in windows of `window` records; 0: about 64 MiB of records) and its index
 // dup_counts (or NULL) [8]: mark the duplicates among the store's templates first (csrc/bam_dup_kernels.hip) and flag every window's records; the counts of bam_dup.h
 int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user,
-                     uint64_t *dup_counts = nullptr, double *dup_ms = nullptr, uint32_t n_lib = 0, uint64_t *lib_counts = nullptr, const struct bdp_optical_t *optical = nullptr, double *opt_ms = nullptr, bool barcode = false);
-// barcode: the decision compares the barcode words the store keeps beside the entries
+                     uint64_t *dup_counts = nullptr, double *dup_ms = nullptr, uint32_t n_lib = 0, uint64_t *lib_counts = nullptr, const struct bdp_optical_t *optical = nullptr, double *opt_ms = nullptr, bool barcode = false, const struct bdp_group_t *grp = nullptr);
+// barcode: the decision compares the barcode words the store keeps beside the entries; grp (or NULL): the words are packed and grouped by edits first (its counts filled)
 // optical (or NULL; needs dup_counts): the decision also counts the optical duplicates among the store's templates, by the locations the store keeps; opt_ms (or NULL)
 // += that step's milliseconds
 // n_lib, lib_counts [8 * n_lib] (or 0, NULL): the run had read groups -- the entries carry their libraries -- and the decision's five counters come per library too

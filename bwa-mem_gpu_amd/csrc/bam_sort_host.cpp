@@ -288,7 +288,7 @@ extern "C" int bmh_bam_sort_host(const uint8_t *recs, uint64_t n_bytes, uint8_t 
 static int sorted_file_host(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
                             int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts,
                             const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr, int format = BSR_IX_BAI, int min_shift = BSR_LIN_SHIFT, const bdp_bc_t *bc = nullptr,
-                            uint64_t *no_barcode = nullptr)
+                            uint64_t *no_barcode = nullptr, const bdp_group_t *grp = nullptr)
 {
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
@@ -302,7 +302,7 @@ static int sorted_file_host(const char *fn, const char *header_text, int n_conti
 	std::vector<uint8_t> marked;                                   // duplicate marking: the flags are set before the sort (0x400 enters no key, bin or index)
 	if (dup_counts) {
 		marked.assign(recs, recs + n_bytes);
-		if ((rc = bdp_markdup_host(marked.data(), off, dup_counts, fn, G, lib_counts, nullptr, bc, no_barcode)) != BMH_OK) return rc;
+		if ((rc = bdp_markdup_host(marked.data(), off, dup_counts, fn, G, lib_counts, nullptr, bc, no_barcode, grp)) != BMH_OK) return rc;
 		recs = marked.data();
 	}
 	bsr_sort_host(recs, off, keys, ord);
@@ -385,21 +385,48 @@ extern "C" int bmh_bam_sorted_file_ex_host(const char *header_text, int n_contig
 	                        groups ? &G : nullptr, groups ? lib_counts : nullptr, index_format, min_shift);
 }
 
+// edits -1: barcodes compared exactly (grouped, lib_grouped unused)
+static int sorted_file_barcode_host(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                    int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
+                                    const char tag[2], int edits, uint64_t bc_max_set, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8],
+                                    uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped);
+
 extern "C" int bmh_bam_sorted_file_barcode_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
                                                 int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
                                                 const char tag[2], uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts,
                                                 uint64_t *no_barcode)
 {
-	const char *fn = "bmh_bam_sorted_file_barcode_host";
+	return sorted_file_barcode_host("bmh_bam_sorted_file_barcode_host", header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, index_format, min_shift, rg_ids, rg_lib,
+	                                n_groups, barcode_mode, tag, -1, 0, bam, bam_bytes, index, index_bytes, counts, lib_counts, no_barcode, nullptr, nullptr);
+}
+
+extern "C" int bmh_bam_sorted_file_barcode_edits_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                                      int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
+                                                      int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index,
+                                                      uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
+{
+	return sorted_file_barcode_host("bmh_bam_sorted_file_barcode_edits_host", header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, index_format, min_shift, rg_ids,
+	                                rg_lib, n_groups, barcode_mode, tag, edits, barcode_max_set, bam, bam_bytes, index, index_bytes, counts, lib_counts, no_barcode, grouped, lib_grouped);
+}
+
+static int sorted_file_barcode_host(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                    int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
+                                    const char tag[2], int edits, uint64_t bc_max_set, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8],
+                                    uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
+{
 	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	if (no_barcode) *no_barcode = 0;
 	int rc = bsr_index_format_check(index_format, min_shift, fn);
 	if (rc != BMH_OK) return rc;
 	bdp_bc_t bc;
 	if ((rc = bdp_barcode_check(barcode_mode, tag, fn, &bc)) != BMH_OK) return rc;
+	if ((rc = bdp_group_check(edits, bc_max_set, fn, &bc)) != BMH_OK) return rc;
+	if (bc.pack && !grouped) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	bdp_table_t G;
 	const bool groups = rg_ids || rg_lib || n_groups;
 	if (groups && (rc = bdp_table_make(G, rg_ids, rg_lib, n_groups, fn)) != BMH_OK) return rc;
+	const bdp_group_t grp = {(uint32_t)(edits < 0 ? 0 : edits), bc_max_set ? (uint32_t)bc_max_set : (uint32_t)BDP_BC_MAX_SET, grouped, groups ? lib_grouped : nullptr};
+	if (bc.pack) for (int k = 0; k < BDP_GRP_N; ++k) grouped[k] = 0;
 	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, index, index_bytes, counts, groups ? &G : nullptr,
-	                        groups ? lib_counts : nullptr, index_format, min_shift, &bc, no_barcode);
+	                        groups ? lib_counts : nullptr, index_format, min_shift, &bc, no_barcode, bc.pack ? &grp : nullptr);
 }

@@ -304,7 +304,7 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 
 // every run of the store -> the sorted file's record members (to the sink) and its index
 int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, uint64_t *dup_counts, double *dup_ms,
-                     uint32_t n_lib, uint64_t *lib_counts, const bdp_optical_t *optical, double *opt_ms, bool barcode)
+                     uint32_t n_lib, uint64_t *lib_counts, const bdp_optical_t *optical, double *opt_ms, bool barcode, const bdp_group_t *grp)
 {
 	uint64_t n = 0, bytes = 0;
 	std::vector<uint64_t> first;
@@ -320,7 +320,7 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint3
 		const double t0 = bsr_now_ms();
 		if (optical && S.locs.size() != S.entries.size()) { bmh_set_error("sorted BAM: internal error: %zu locations for %zu templates", S.locs.size(), S.entries.size()); return BMH_EINVAL; }
 		if (barcode && S.bcs.size() != S.entries.size()) { bmh_set_error("sorted BAM: internal error: %zu barcode words for %zu templates", S.bcs.size(), S.entries.size()); return BMH_EINVAL; }
-		RCK(bdp_decide_device(dup.p, S.entries.data(), S.entries.size(), stream, dup_counts, n, n_lib, lib_counts, optical, optical ? S.locs.data() : nullptr, &o_ms, barcode ? S.bcs.data() : nullptr));
+		RCK(bdp_decide_device(dup.p, S.entries.data(), S.entries.size(), stream, dup_counts, n, n_lib, lib_counts, optical, optical ? S.locs.data() : nullptr, &o_ms, barcode ? S.bcs.data() : nullptr, barcode ? grp : nullptr));
 		dup_counts[BDP_SECSUP] = S.dup_info[0]; dup_counts[BDP_UNMAPPED] = S.dup_info[1]; dup_counts[BDP_TEMPLATES] = S.entries.size();
 		decide_ms = bsr_now_ms() - t0;
 	}
@@ -393,10 +393,10 @@ int to_store(bsr_dev_t *d, const uint8_t *recs, uint64_t n_bytes, const std::vec
 	}
 	RCK(bsr_sort_run_device(d, (const uint8_t *)d->in.p, (const uint64_t *)d->in_off.p, n, n_bytes, st, &ds, &dk, &dso, d_tpl, &d_tpl_sorted));
 	if (dh) {
-		uint32_t info[BDP_INFO_WORDS];
-		HIPCK(hipMemcpyAsync(info, d_info, 4 * BDP_INFO_WORDS, hipMemcpyDeviceToHost, st));
+		uint32_t info[BDP_INFO_WORDS_PACK];
+		HIPCK(hipMemcpyAsync(info, d_info, 4 * bdp_info_words(bc), hipMemcpyDeviceToHost, st));
 		HIPCK(hipStreamSynchronize(st));
-		RCK(bdp_batch_check(n, info, G != nullptr, fn, bc != nullptr));
+		RCK(bdp_batch_check(n, info, G != nullptr, fn, bc != nullptr, bc && bc->pack));
 		if (info[0] > n) { bmh_set_error("%s: internal error: %u templates among %u records", fn, info[0], n); return BMH_EINVAL; }
 		dh->tpl.resize(n); dh->entries.resize(n ? info[0] : 0); dh->secsup = info[2]; dh->unmapped = info[3];
 		if (n) HIPCK(hipMemcpyAsync(dh->tpl.data(), d_tpl_sorted, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
@@ -435,9 +435,10 @@ extern "C" int bmh_bam_sort_device(const uint8_t *recs, uint64_t n_bytes, void *
 static int sorted_file_device(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
                               int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts,
                               const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr, int format = BSR_IX_BAI, int min_shift = BSR_LIN_SHIFT, const bdp_bc_t *bc = nullptr,
-                              uint64_t *no_barcode = nullptr)
+                              uint64_t *no_barcode = nullptr, const bdp_group_t *grp = nullptr)
 {
 	if (bc && (bc->mode == BDP_BC_OFF || !dup_counts)) bc = nullptr;
+	if (!bc || !bc->pack) grp = nullptr;
 	if (no_barcode) *no_barcode = 0;
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
@@ -469,7 +470,7 @@ static int sorted_file_device(const char *fn, const char *header_text, int n_con
 	file.append((const char *)hm, hmb); bmh_free(hm);
 	const uint64_t base = file.size();
 	bmh_bam_ws_t *ws = bmh_bam_ws_create();
-	rc = bsr_merge_device(&d, ws, S, window, level, stream, ix, sink_string, &file, dup_counts, nullptr, G ? G->n_lib : 0, G ? lib_counts : nullptr, nullptr, nullptr, bc != nullptr);
+	rc = bsr_merge_device(&d, ws, S, window, level, stream, ix, sink_string, &file, dup_counts, nullptr, G ? G->n_lib : 0, G ? lib_counts : nullptr, nullptr, nullptr, bc != nullptr, grp);
 	bmh_bam_ws_free(ws);
 	if (rc != BMH_OK) return rc;
 	if (G && lib_counts && off.size() > 1)
@@ -524,20 +525,47 @@ extern "C" int bmh_bam_sorted_file_ex_device(const char *header_text, int n_cont
 	                          groups ? &G : nullptr, groups ? lib_counts : nullptr, index_format, min_shift);
 }
 
+// edits -1: barcodes compared exactly (grouped, lib_grouped unused)
+static int sorted_file_barcode_device(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                      int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
+                                      const char tag[2], int edits, uint64_t bc_max_set, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8],
+                                      uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped);
+
 extern "C" int bmh_bam_sorted_file_barcode_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
                                                   int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
                                                   const char tag[2], void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8],
                                                   uint64_t *lib_counts, uint64_t *no_barcode)
 {
-	const char *fn = "bmh_bam_sorted_file_barcode_device";
+	return sorted_file_barcode_device("bmh_bam_sorted_file_barcode_device", header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, index_format, min_shift, rg_ids, rg_lib,
+	                                  n_groups, barcode_mode, tag, -1, 0, stream, bam, bam_bytes, index, index_bytes, counts, lib_counts, no_barcode, nullptr, nullptr);
+}
+
+extern "C" int bmh_bam_sorted_file_barcode_edits_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                                        int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
+                                                        int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index,
+                                                        uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
+{
+	return sorted_file_barcode_device("bmh_bam_sorted_file_barcode_edits_device", header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, index_format, min_shift, rg_ids,
+	                                  rg_lib, n_groups, barcode_mode, tag, edits, barcode_max_set, stream, bam, bam_bytes, index, index_bytes, counts, lib_counts, no_barcode, grouped, lib_grouped);
+}
+
+static int sorted_file_barcode_device(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                      int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
+                                      const char tag[2], int edits, uint64_t bc_max_set, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8],
+                                      uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
+{
 	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	if (no_barcode) *no_barcode = 0;
 	RCK(bsr_index_format_check(index_format, min_shift, fn));
 	bdp_bc_t bc;
 	RCK(bdp_barcode_check(barcode_mode, tag, fn, &bc));
+	RCK(bdp_group_check(edits, bc_max_set, fn, &bc));
+	if (bc.pack && !grouped) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (bc.pack) for (int k = 0; k < BDP_GRP_N; ++k) grouped[k] = 0;
 	bdp_table_t G;
 	const bool groups = rg_ids || rg_lib || n_groups;
 	if (groups) RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
+	const bdp_group_t grp = {(uint32_t)(edits < 0 ? 0 : edits), bc_max_set ? (uint32_t)bc_max_set : (uint32_t)BDP_BC_MAX_SET, grouped, groups ? lib_grouped : nullptr};
 	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, index, index_bytes, counts, groups ? &G : nullptr,
-	                          groups ? lib_counts : nullptr, index_format, min_shift, &bc, no_barcode);
+	                          groups ? lib_counts : nullptr, index_format, min_shift, &bc, no_barcode, bc.pack ? &grp : nullptr);
 }

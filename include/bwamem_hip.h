@@ -1038,6 +1038,43 @@ uint64_t bmh_barcode_word(const uint8_t *value, uint64_t n);
 int bmh_aligner_set_markdup_barcode(bmh_aligner_t *a, int mode, const char *tag);
 int bmh_aligner_markdup_barcode_counts(bmh_aligner_t *a, uint64_t out[1]);
 
+/* ---- Barcodes grouped within an edit distance (csrc/bam_dup_core.h).  Opt-in beside a barcode source: `edits` N (0 .. 21; -1: off, the calls
+ * above) makes barcodes within N mismatches one molecule, as Picard's UmiAwareMarkDuplicatesWithMateCigar (MAX_EDIT_DISTANCE_TO_JOIN) does.  The barcode word is then
+ * the value itself, packed: 3 bits a byte -- A 1, C 2, G 3, T 4, N 5, '-' 6, '+' 7 --, symbol i in bits 3 i .. 3 i + 2, at most 21 symbols, 0 still no barcode.
+ * The distance of two words is the number of positions at which their symbols differ; values of different lengths are never joined, nor is a template without a
+ * barcode to one with.  Within one (library, lo, hi) the distinct words of the pairs are clustered -- connected components of distance <= N, so joining is
+ * transitive -- and every pair takes its component's smallest word; the pair rule then runs on (lo, hi, that word), and an optical set is the pairs of one such
+ * key.  Independently, within one (library, end word) the distinct words of the fragment pass's items -- the fragments and both ends of every pair -- are
+ * clustered the same way before the fragment rule.  A key with more than barcode_max_set distinct words (0: 65 536) is not clustered: its words stay exact.  With
+ * N = 0 flags and counts are those of the exact comparison.  grouped [3] (required), lib_grouped [3 * libraries] (or NULL; filled with read groups): the distinct
+ * (library, lo, hi, word) over barcoded pairs, their components, and the keys of either pass over the cap.
+ * Refused with BMH_EINVAL before anything is written: edits outside -1 .. 21, edits without a barcode source; and by the record's index: a first record whose
+ * value holds more than 21 bytes or a byte other than A C G T N - + (lower case too).
+ * bmh_bam_markdup_barcode_edits_* / bmh_bam_sorted_file_barcode_edits_*: the barcode calls with edits, barcode_max_set and the counts.
+ * bmh_bam_dup_barcodes_packed_*: bmh_bam_dup_barcodes_* with packed words.  bmh_barcode_pack: *word of a value of n bytes; 1, or 0 when it does not pack.
+ * bmh_aligner_set_markdup_barcode_edits: the marked runs that follow group barcodes within n mismatches (-1: off); after bmh_aligner_set_markdup_barcode, which
+ * switches it off again when called anew.  bmh_aligner_markdup_barcode_group_counts: the three counts of the last such run. */
+int bmh_bam_markdup_barcode_edits_device(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
+                                         int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts,
+                                         uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped);
+int bmh_bam_markdup_barcode_edits_host(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
+                                       int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts,
+                                       uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped);
+int bmh_bam_sorted_file_barcode_edits_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records,
+                                             uint64_t n_bytes, int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib,
+                                             int n_groups, int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, void *stream, uint8_t **bam, uint64_t *bam_bytes,
+                                             uint8_t **index, uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3],
+                                             uint64_t *lib_grouped);
+int bmh_bam_sorted_file_barcode_edits_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records,
+                                           uint64_t n_bytes, int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
+                                           int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index,
+                                           uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped);
+int bmh_bam_dup_barcodes_packed_device(const uint8_t *records, uint64_t n_bytes, int barcode_mode, const char tag[2], void *stream, uint64_t **words, uint64_t *n_templates);
+int bmh_bam_dup_barcodes_packed_host(const uint8_t *records, uint64_t n_bytes, int barcode_mode, const char tag[2], uint64_t **words, uint64_t *n_templates);
+int bmh_barcode_pack(const uint8_t *value, uint64_t n, uint64_t *word);
+int bmh_aligner_set_markdup_barcode_edits(bmh_aligner_t *a, int n);
+int bmh_aligner_markdup_barcode_group_counts(bmh_aligner_t *a, uint64_t out[3]);
+
 /* A run over several read groups: one sample's lanes and libraries into one output.  A group is a read group ID, its library index (as above) and an input as
  * bmh_aligner_run_files takes it (path2: the mates, or NULL; a BAM's own @RG lines and RG tags stay ignored: keeping the input's read groups, bmh_aligner_set_keep_rg, and a run over groups do not combine).  One loader thread walks the groups in order into the
  * one queue of batches: the lanes are not drained between groups.  A batch never spans two groups and is cut inside its group as bmh_aligner_run_files cuts it; the

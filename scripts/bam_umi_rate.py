@@ -4,10 +4,12 @@
 The decision's milliseconds are the library's own (the BMH_ALIGNER_TRACE line of the merge: a host clock around bdp_decide_device, which ends in a stream
 synchronise), read from the standard error of one child process per leg; the legs alternate, each runs --warmup calls and then --runs timed ones.
 
-    python scripts/bam_umi_rate.py [--runs 7] [--warmup 2] [--rounds 2] [--templates 1000000] [--parent DIR] [--out FILE]
+    python scripts/bam_umi_rate.py [--runs 7] [--warmup 2] [--rounds 2] [--templates 1000000] [--parent DIR] [--edits N] [--out FILE]
 
 --parent DIR: the bwa-mem_gpu_amd directory of another build of the library (the parent commit's, built beside this one): its leg without the option runs in
-turn with this build's two legs.  Writes profiles/bam_markdup_umi.json (or --out)."""
+turn with this build's two legs.  Writes profiles/bam_markdup_umi.json (or --out).
+--edits N: what grouping the barcodes within N mismatches costs instead -- the legs are barcode_tag="RX" alone (on --parent's build too) and with barcode_edits=N;
+two of the stream's four barcodes are one mismatch apart.  Writes profiles/bam_markdup_umi_edits.json (or --out)."""
 import argparse
 import json
 import os
@@ -57,7 +59,7 @@ def child(a):
     sys.path.insert(0, a.package)
     from bwamem_hip.lib import bam_sorted_file
     s, length = stream(a.templates)
-    kw = dict(barcode_tag="RX") if a.leg == "tag" else {}
+    kw = dict(barcode_tag="RX") if a.leg == "tag" else dict(barcode_tag="RX", barcode_edits=a.edits) if a.leg == "edits" else {}
     for k in range(a.warmup + a.runs):
         sys.stderr.write("[run] %s\n" % ("warm-up" if k < a.warmup else "timed")); sys.stderr.flush()
         _bam, _bai, counts = bam_sorted_file("@HD\tVN:1.6\tSO:coordinate\n", [("c1", length)], s, 1, 0, markdup=True, **kw)
@@ -71,17 +73,21 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--templates", type=int, default=1_000_000)
     ap.add_argument("--parent", default="")
-    ap.add_argument("--out", default=os.path.join(HERE, "..", "profiles", "bam_markdup_umi.json"))
+    ap.add_argument("--edits", type=int, default=-1)
+    ap.add_argument("--out", default="")
     ap.add_argument("--leg", default="")
     ap.add_argument("--package", default=os.path.join(HERE, "..", "bwa-mem_gpu_amd"))
     a = ap.parse_args()
     if a.leg:
         return child(a)
+    a.out = a.out or os.path.join(HERE, "..", "profiles", "bam_markdup_umi_edits.json" if a.edits >= 0 else "bam_markdup_umi.json")
     legs = ([("parent, option off", a.parent, "off")] if a.parent else []) + [("this commit, option off", a.package, "off"), ("this commit, barcode_tag", a.package, "tag")]
+    if a.edits >= 0:
+        legs = ([("parent, barcode_tag", a.parent, "tag")] if a.parent else []) + [("this commit, barcode_tag", a.package, "tag"), ("this commit, barcode_edits=%d" % a.edits, a.package, "edits")]
     res = {name: {"decision_ms": [], "counts": None} for name, _p, _l in legs}
     for _round in range(a.rounds):
         for name, package, leg in legs:                               # (one process at a time holds the device)
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg, "--package", package, "--runs", str(a.runs), "--warmup", str(a.warmup), "--templates", str(a.templates)],
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", leg, "--package", package, "--runs", str(a.runs), "--warmup", str(a.warmup), "--templates", str(a.templates), "--edits", str(a.edits)],
                                env=dict(os.environ, BMH_ALIGNER_TRACE="1"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
             if r.returncode != 0:
                 sys.stderr.write(r.stderr.decode(errors="replace")[-2000:])
@@ -103,7 +109,7 @@ def main():
         v["process_medians_ms"] = [sorted(ms)[len(ms) // 2] for ms in v["decision_ms"]]
         print(name, v["median_ms"], "ms, spread", v["spread_pct"], "%, per process", v["process_medians_ms"], v["counts"])
     with open(a.out, "w") as f:
-        json.dump({"templates": a.templates, "runs": a.runs, "warmup": a.warmup, "rounds": a.rounds, "legs": res}, f, indent=1)
+        json.dump(dict({"templates": a.templates, "runs": a.runs, "warmup": a.warmup, "rounds": a.rounds}, **({"edits": a.edits} if a.edits >= 0 else {}), legs=res), f, indent=1)
         f.write("\n")
     return 0
 

@@ -1,0 +1,119 @@
+// Grouping barcodes by edits (csrc/bam_dup_core.h, csrc/bam_dup_host.cpp) -- the packed word, the distance, the clustering and the widened decision through
+// bdp_markdup_host -- as plain C++ for tests/test_bam_umi_edits.py, built with -fsanitize=address,undefined: every value and every stream sits in an allocation
+// of exactly its size.
+//   in : u32 n_values, per value u32 len and the bytes; u32 n_pairs, per pair of values u32 len, the bytes, u32 len, the bytes, u32 N; u32 n_cases, per case
+//        u32 mode, 2 tag bytes, i32 edits, u32 barcode max_set (0: the default), i64 distance (-1: no optical step), u32 n_groups, per group u32 len, the ID,
+//        i32 library; u64 n_bytes and the record stream
+//   out: per value i32 packs (1 / 0) and u64 word; per pair i32 near (1 / 0; -1: one of the two does not pack); per case i32 status; for status 0: u32 T, T
+//        packed words of 8 bytes, u64 counts[8], u64 no_barcode, u64 grouped[3], u64 optical[3], u32 n_lib, u64 lib_counts[8 * n_lib], u64 lib_grouped[3 * n_lib],
+//        the marked stream (n_bytes); for any other status: u32 len and the message
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <string>
+#include <vector>
+#define BDP_STANDALONE
+#include "../bwa-mem_gpu_amd/csrc/bam_dup_host.cpp"
+
+static char g_msg[512];
+void bmh_set_error(const char *fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(g_msg, sizeof g_msg, fmt, ap); va_end(ap); }
+
+template <class T> static bool get(FILE *f, T *v) { return fread(v, sizeof(T), 1, f) == 1; }
+
+// len bytes of the file in an allocation of exactly that size (of one byte for none, never read)
+static uint8_t *exact(FILE *f, uint64_t len)
+{
+	uint8_t *p = new uint8_t[len ? len : 1];
+	if (len && fread(p, 1, len, f) != len) { delete[] p; return nullptr; }
+	return p;
+}
+
+int main(int argc, char **argv)
+{
+	if (argc != 3) return 2;
+	FILE *f = fopen(argv[1], "rb"), *o = fopen(argv[2], "wb");
+	if (!f || !o) return 2;
+	uint32_t n_values, n_pairs, n_cases;
+	if (!get(f, &n_values)) return 2;
+	for (uint32_t k = 0; k < n_values; ++k) {
+		uint32_t len;
+		if (!get(f, &len)) return 2;
+		uint8_t *v = exact(f, len);
+		if (!v) return 2;
+		uint64_t w = 0;
+		const int32_t ok = bdp_barcode_pack(v, len, &w) ? 1 : 0;
+		fwrite(&ok, 4, 1, o); fwrite(&w, 8, 1, o);
+		delete[] v;
+	}
+	if (!get(f, &n_pairs)) return 2;
+	for (uint32_t k = 0; k < n_pairs; ++k) {
+		uint32_t la, lb, N;
+		if (!get(f, &la)) return 2;
+		uint8_t *a = exact(f, la);
+		if (!a || !get(f, &lb)) return 2;
+		uint8_t *b = exact(f, lb);
+		if (!b || !get(f, &N)) return 2;
+		uint64_t wa = 0, wb = 0;
+		const int32_t near = bdp_barcode_pack(a, la, &wa) && bdp_barcode_pack(b, lb, &wb) ? (bdp_bc_near(wa, wb, N) ? 1 : 0) : -1;
+		fwrite(&near, 4, 1, o);
+		delete[] a; delete[] b;
+	}
+	if (!get(f, &n_cases)) return 2;
+	for (uint32_t c = 0; c < n_cases; ++c) {
+		uint32_t mode, bc_max, n_groups; char tag[2]; int32_t edits; int64_t D; uint64_t nb;
+		if (!get(f, &mode) || fread(tag, 1, 2, f) != 2 || !get(f, &edits) || !get(f, &bc_max) || !get(f, &D) || !get(f, &n_groups)) return 2;
+		std::vector<std::string> ids(n_groups); std::vector<const char *> idp; std::vector<int32_t> lib(n_groups);
+		for (uint32_t g = 0; g < n_groups; ++g) {
+			uint32_t len;
+			if (!get(f, &len)) return 2;
+			ids[g].resize(len);
+			if (len && fread(&ids[g][0], 1, len, f) != len) return 2;
+			if (!get(f, &lib[g])) return 2;
+		}
+		for (const std::string &s : ids) idp.push_back(s.c_str());
+		if (!get(f, &nb)) return 2;
+		uint8_t *all = exact(f, nb);
+		if (!all) return 2;
+		std::vector<uint64_t> off(1, 0);
+		int32_t rc = BMH_OK;
+		g_msg[0] = 0;
+		for (uint64_t p = 0; p < nb;) {
+			const uint64_t sz = bsr_record_bytes(all + p, nb - p);
+			if (!sz) { rc = BMH_EINVAL; break; }
+			p += sz; off.push_back(p);
+		}
+		bdp_table_t T; bdp_bc_t bc;
+		if (rc == BMH_OK && n_groups) rc = bdp_table_make(T, idp.data(), lib.data(), (int)n_groups, "test");
+		if (rc == BMH_OK) rc = bdp_barcode_check((int)mode, tag, "test", &bc);
+		if (rc == BMH_OK) rc = bdp_group_check(edits, bc_max, "test", &bc);
+		if (rc == BMH_OK && D != -1) rc = bdp_optical_check(D, 0, "test");
+		const uint32_t n = (uint32_t)(off.size() - 1);
+		for (uint32_t i = 0; rc == BMH_OK && i < n; ++i) if (!bdp_record_whole(all + off[i], off[i + 1] - off[i])) rc = BMH_EINVAL;
+		// the packed words on their own, then the whole of it
+		std::vector<uint32_t> tpl; std::vector<bdp_entry_t> E; std::vector<uint64_t> W; uint64_t info[2] = {0, 0};
+		const bdp_groups_t G = T.view();
+		if (rc == BMH_OK) rc = bdp_entries_host(all, off.data(), n, tpl, E, info, "test", n_groups ? &G : nullptr, nullptr, &bc, &W);
+		uint64_t counts[BDP_N_COUNTS], opt[BDP_OPT_N] = {0, 0, 0}, grp[BDP_GRP_N] = {0, 0, 0}, no_bc = 0;
+		std::vector<uint64_t> lib_counts((size_t)BDP_N_COUNTS * T.n_lib + 1), lib_opt((size_t)BDP_OPT_N * T.n_lib + 1), lib_grp((size_t)BDP_GRP_N * T.n_lib + 1);
+		const bdp_optical_t O = {D, (uint32_t)BDP_OPT_MAX_SET, opt, n_groups ? lib_opt.data() : nullptr};
+		const bdp_group_t GR = {(uint32_t)(edits < 0 ? 0 : edits), bc_max ? bc_max : (uint32_t)BDP_BC_MAX_SET, grp, n_groups ? lib_grp.data() : nullptr};
+		if (rc == BMH_OK) rc = bdp_markdup_host(all, off, counts, "test", n_groups ? &T : nullptr, n_groups ? lib_counts.data() : nullptr, D != -1 ? &O : nullptr, &bc, &no_bc, bc.pack ? &GR : nullptr);
+		fwrite(&rc, 4, 1, o);
+		if (rc == BMH_OK) {
+			const uint32_t nt = (uint32_t)W.size(), nl = n_groups ? T.n_lib : 0;
+			fwrite(&nt, 4, 1, o);
+			if (nt) fwrite(W.data(), 8, nt, o);
+			fwrite(counts, 8, BDP_N_COUNTS, o); fwrite(&no_bc, 8, 1, o); fwrite(grp, 8, BDP_GRP_N, o); fwrite(opt, 8, BDP_OPT_N, o);
+			fwrite(&nl, 4, 1, o);
+			if (nl) { fwrite(lib_counts.data(), 8, (size_t)BDP_N_COUNTS * nl, o); fwrite(lib_grp.data(), 8, (size_t)BDP_GRP_N * nl, o); }
+			if (nb) fwrite(all, 1, nb, o);
+		} else {
+			const uint32_t len = (uint32_t)strlen(g_msg);
+			fwrite(&len, 4, 1, o); fwrite(g_msg, 1, len, o);
+		}
+		delete[] all;
+	}
+	fclose(o); fclose(f);
+	return 0;
+}
