@@ -42,17 +42,14 @@ EXPORTED_SYMBOLS = [
     "bmh_deflate_blocks_host", "bmh_bam_header", "bmh_aligner_set_output",
     "bmh_bam_sort_device", "bmh_bam_sort_host", "bmh_bam_sorted_file_device", "bmh_bam_sorted_file_host", "bmh_aligner_set_sort", "bmh_aligner_sort_index",
     "bmh_bam_reads_device", "bmh_bam_reads_host", "bmh_reads_last_bam_counts", "bmh_aligner_set_bam_pairs",
-    "bmh_bam_markdup_device", "bmh_bam_markdup_host", "bmh_bam_sorted_file_markdup_device", "bmh_bam_sorted_file_markdup_host", "bmh_aligner_set_markdup", "bmh_aligner_markdup_counts", "bmh_aligner_markdup_times",
-    "bmh_bam_markdup_groups_device", "bmh_bam_markdup_groups_host", "bmh_bam_sorted_file_markdup_groups_device", "bmh_bam_sorted_file_markdup_groups_host",
+    "bmh_markdup_opt_default", "bmh_bam_markdup_device", "bmh_bam_markdup_host", "bmh_aligner_set_markdup", "bmh_aligner_markdup_counts", "bmh_aligner_markdup_times",
     "bmh_aligner_markdup_library_counts", "bmh_aligner_run_groups",
     "bmh_bam_reads_groups_device", "bmh_bam_reads_groups_host", "bmh_bam_header_read_groups", "bmh_format_sam_groups", "bmh_aligner_set_keep_rg",
-    "bmh_aligner_set_index_format", "bmh_bam_sorted_file_ex_device", "bmh_bam_sorted_file_ex_host",
-    "bmh_bam_markdup_optical_device", "bmh_bam_markdup_optical_host", "bmh_bam_dup_locations_device", "bmh_bam_dup_locations_host", "bmh_bam_name_location", "bmh_library_size",
+    "bmh_aligner_set_index_format",
+    "bmh_bam_dup_locations_device", "bmh_bam_dup_locations_host", "bmh_bam_name_location", "bmh_library_size",
     "bmh_aligner_set_markdup_optical", "bmh_aligner_markdup_optical_counts", "bmh_aligner_markdup_optical_ms",
-    "bmh_bam_markdup_barcode_device", "bmh_bam_markdup_barcode_host", "bmh_bam_sorted_file_barcode_device", "bmh_bam_sorted_file_barcode_host",
     "bmh_bam_dup_barcodes_device", "bmh_bam_dup_barcodes_host", "bmh_barcode_word", "bmh_aligner_set_markdup_barcode", "bmh_aligner_markdup_barcode_counts",
-    "bmh_bam_markdup_barcode_edits_device", "bmh_bam_markdup_barcode_edits_host", "bmh_bam_sorted_file_barcode_edits_device", "bmh_bam_sorted_file_barcode_edits_host",
-    "bmh_bam_dup_barcodes_packed_device", "bmh_bam_dup_barcodes_packed_host", "bmh_barcode_pack", "bmh_aligner_set_markdup_barcode_edits",
+    "bmh_barcode_pack", "bmh_aligner_set_markdup_barcode_edits",
     "bmh_aligner_markdup_barcode_group_counts",
 ]
 
@@ -505,7 +502,7 @@ def barcode_word(value) -> int:
 def bam_dup_barcodes(records: bytes, host: bool = False, tag=None, name=None, edits: bool = False) -> np.ndarray:
     """bmh_bam_dup_barcodes_device (host=True: _host): a record stream as bam_markdup takes it -> one barcode word (uint64) per template, from tag `tag` of its first
     record or (name=True) from its read name's last ':' field; 0: no barcode.  This is what bam_markdup(barcode_tag=...) compares.
-    edits=True (bmh_bam_dup_barcodes_packed_*): the packed words (barcode_pack) that bam_markdup(barcode_edits=...) groups; a value that does not pack raises
+    edits=True (packed = 1): the packed words (barcode_pack) that bam_markdup(barcode_edits=...) groups; a value that does not pack raises
     ValueError with its record's index."""
     mode, tg = barcode_source(tag, name, "bam_dup_barcodes")
     if mode == BARCODE_OFF:
@@ -514,16 +511,14 @@ def bam_dup_barcodes(records: bytes, host: bool = False, tag=None, name=None, ed
     records = bytes(records)
     L.bmh_free.argtypes = [C.c_void_p]
     out, nt = C.c_void_p(), C.c_uint64(0)
-    head = [C.c_char_p, C.c_uint64, C.c_int, C.c_char_p]
+    head = [C.c_char_p, C.c_uint64, C.c_int, C.c_char_p, C.c_int]
     if host:
-        fn = L.bmh_bam_dup_barcodes_packed_host if edits else L.bmh_bam_dup_barcodes_host
-        fn.argtypes = head + [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-        rc = fn(records, len(records), mode, tg, C.byref(out), C.byref(nt))
+        L.bmh_bam_dup_barcodes_host.argtypes = head + [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        rc = L.bmh_bam_dup_barcodes_host(records, len(records), mode, tg, 1 if edits else 0, C.byref(out), C.byref(nt))
     else:
         import torch
-        fn = L.bmh_bam_dup_barcodes_packed_device if edits else L.bmh_bam_dup_barcodes_device
-        fn.argtypes = head + [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-        rc = fn(records, len(records), mode, tg, torch.cuda.current_stream().cuda_stream, C.byref(out), C.byref(nt))
+        L.bmh_bam_dup_barcodes_device.argtypes = head + [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        rc = L.bmh_bam_dup_barcodes_device(records, len(records), mode, tg, 1 if edits else 0, torch.cuda.current_stream().cuda_stream, C.byref(out), C.byref(nt))
     if rc != 0:
         raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_dup_barcodes: " + _err(L))
     try:
@@ -532,76 +527,74 @@ def bam_dup_barcodes(records: bytes, host: bool = False, tag=None, name=None, ed
         L.bmh_free(out)
 
 
-def _bam_markdup_optical(records: bytes, host: bool, read_groups, distance, max_set, barcode=None, edits=-1, bc_max_set=0) -> tuple:
-    L = load_library()
-    L.bmh_free.argtypes = [C.c_void_p]
-    if barcode is not None and distance is None:
-        distance = -1
-    else:
-        distance = optical_distance_value(distance, "bam_markdup")
-    if max_set is None:
-        max_set = 0
-    elif not isinstance(max_set, (int, np.integer)) or isinstance(max_set, bool) or not 1 <= max_set <= 0x7fffffff:
-        raise ValueError(f"bam_markdup: optical_max_set {max_set!r}: an integer in 1 .. 2^31 - 1")
-    out, counts, opt = C.c_void_p(), (C.c_uint64 * 8)(), (C.c_uint64 * 3)()
-    names = []
-    ids = lib = lc = lo = None
-    ng = 0
+class MarkdupOpt(C.Structure):
+    """bmh_markdup_opt_t"""
+    _fields_ = [("rg_ids", C.POINTER(C.c_char_p)), ("rg_lib", C.POINTER(C.c_int32)), ("n_groups", C.c_int32), ("optical_distance", C.c_int64), ("optical_max_set", C.c_uint64),
+                ("barcode_mode", C.c_int32), ("barcode_tag", C.c_char * 2), ("barcode_edits", C.c_int32), ("barcode_max_set", C.c_uint64)]
+
+
+class MarkdupCounts(C.Structure):
+    """bmh_markdup_counts_t"""
+    _fields_ = [("counts", C.c_uint64 * 8), ("optical", C.c_uint64 * 3), ("grouped", C.c_uint64 * 3), ("no_barcode", C.c_uint64),
+                ("lib_counts", _u64p), ("lib_optical", _u64p), ("lib_grouped", _u64p)]
+
+
+class SortedFileOpt(C.Structure):
+    """bmh_sorted_file_opt_t"""
+    _fields_ = [("level", C.c_int32), ("window", C.c_uint32), ("index_format", C.c_int32), ("min_shift", C.c_int32), ("markdup", C.POINTER(MarkdupOpt))]
+
+
+def _markdup_api(L):
+    """the library with the argument types of the four calls that take the records above"""
+    if not getattr(L, "_markdup_api", False):
+        stream, file_head = [C.c_char_p, C.c_uint64, C.POINTER(MarkdupOpt)], [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(SortedFileOpt)]
+        out, file_out = [C.POINTER(C.c_void_p), C.POINTER(MarkdupCounts)], [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p, C.POINTER(MarkdupCounts)]
+        L.bmh_markdup_opt_default.argtypes, L.bmh_markdup_opt_default.restype = [C.POINTER(MarkdupOpt)], None
+        L.bmh_bam_markdup_host.argtypes, L.bmh_bam_markdup_device.argtypes = stream + out, stream + [C.c_void_p] + out
+        L.bmh_bam_sorted_file_host.argtypes, L.bmh_bam_sorted_file_device.argtypes = file_head + file_out, file_head + [C.c_void_p] + file_out
+        L.bmh_free.argtypes = [C.c_void_p]
+        L._markdup_api = True
+    return L
+
+
+def _markdup_records(L, read_groups, distance=-1, max_set=0, bc_mode=BARCODE_OFF, bc_tag=None, edits=-1, bc_max_set=0) -> tuple:
+    """the validated keywords of the marking calls -> (bmh_markdup_opt_t, bmh_markdup_counts_t with a library's arrays where read_groups are given, the library
+    names, what the records point into: kept by the caller until the call is over)"""
+    o, res = MarkdupOpt(), MarkdupCounts()
+    L.bmh_markdup_opt_default(C.byref(o))
+    o.optical_distance, o.optical_max_set, o.barcode_mode, o.barcode_edits, o.barcode_max_set = distance, max_set, bc_mode, edits, bc_max_set
+    if bc_tag is not None:
+        o.barcode_tag = bc_tag
+    names, keep = [], []
     if read_groups is not None:
-        ids, lib, ng, names = _library_table(read_groups)
-        lc = (C.c_uint64 * (8 * max(len(names), 1)))()
-        lo = (C.c_uint64 * (3 * max(len(names), 1)))()
-    head = [C.c_char_p, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int, C.c_int64, C.c_uint64]
-    tail = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    if barcode is not None and edits >= 0:                    # bmh_bam_markdup_barcode_edits_*: the barcode call with the edits, the cap and the three grouping counts
-        nb, gc = C.c_uint64(0), (C.c_uint64 * 3)()
-        lg = (C.c_uint64 * (3 * max(len(names), 1)))() if read_groups is not None else None
-        bc, btail, bargs = [C.c_int, C.c_char_p, C.c_int, C.c_uint64], tail + [C.POINTER(C.c_uint64)] * 3, (C.byref(out), counts, lc, opt, lo, C.byref(nb), gc, lg)
-        if host:
-            L.bmh_bam_markdup_barcode_edits_host.argtypes = head + bc + btail
-            rc = L.bmh_bam_markdup_barcode_edits_host(records, len(records), ids, lib, ng, distance, int(max_set), barcode[0], barcode[1], edits, int(bc_max_set), *bargs)
-        else:
-            import torch
-            L.bmh_bam_markdup_barcode_edits_device.argtypes = head + bc + [C.c_void_p] + btail
-            rc = L.bmh_bam_markdup_barcode_edits_device(records, len(records), ids, lib, ng, distance, int(max_set), barcode[0], barcode[1], edits, int(bc_max_set),
-                                                        torch.cuda.current_stream().cuda_stream, *bargs)
-    elif barcode is not None:                                 # bmh_bam_markdup_barcode_*: the optical call with the barcode's source; distance -1: no optical step
-        nb = C.c_uint64(0)
-        bc, btail, bargs = [C.c_int, C.c_char_p], tail + [C.POINTER(C.c_uint64)], (C.byref(out), counts, lc, opt, lo, C.byref(nb))
-        if host:
-            L.bmh_bam_markdup_barcode_host.argtypes = head + bc + btail
-            rc = L.bmh_bam_markdup_barcode_host(records, len(records), ids, lib, ng, distance, int(max_set), barcode[0], barcode[1], *bargs)
-        else:
-            import torch
-            L.bmh_bam_markdup_barcode_device.argtypes = head + bc + [C.c_void_p] + btail
-            rc = L.bmh_bam_markdup_barcode_device(records, len(records), ids, lib, ng, distance, int(max_set), barcode[0], barcode[1], torch.cuda.current_stream().cuda_stream, *bargs)
-    elif host:
-        L.bmh_bam_markdup_optical_host.argtypes = head + tail
-        rc = L.bmh_bam_markdup_optical_host(records, len(records), ids, lib, ng, distance, int(max_set), C.byref(out), counts, lc, opt, lo)
-    else:
-        import torch
-        L.bmh_bam_markdup_optical_device.argtypes = head + [C.c_void_p] + tail
-        rc = L.bmh_bam_markdup_optical_device(records, len(records), ids, lib, ng, distance, int(max_set), torch.cuda.current_stream().cuda_stream, C.byref(out), counts, lc, opt, lo)
-    if rc != 0:
-        raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_markdup: " + _err(L))
-    try:
-        c = dict(zip(MARKDUP_COUNTS, (int(v) for v in counts)))
-        if distance >= 0:
-            c.update(zip(OPTICAL_COUNTS, (int(v) for v in opt)))
-        if barcode is not None:
-            c["templates_without_barcode"] = int(nb.value)
-        if barcode is not None and edits >= 0:
-            c.update(zip(BARCODE_GROUP_COUNTS, (int(v) for v in gc)))
-        if read_groups is not None:
-            c["libraries"] = _library_counts(names, lc)
-            for k, nm in enumerate(names):
-                if distance >= 0:
-                    c["libraries"][nm].update(zip(OPTICAL_COUNTS, (int(v) for v in lo[3 * k:3 * k + 3])))
-                if barcode is not None and edits >= 0:
-                    c["libraries"][nm].update(zip(BARCODE_GROUP_COUNTS, (int(v) for v in lg[3 * k:3 * k + 3])))
-        return (C.string_at(out.value, len(records)) if records else b""), c
-    finally:
-        L.bmh_free(out)
+        ids, lib, o.n_groups, names = _library_table(read_groups)
+        o.rg_ids, o.rg_lib = ids, lib
+        arrays = [(C.c_uint64 * (k * max(len(names), 1)))() for k in (8, 3, 3)]
+        res.lib_counts, res.lib_optical, res.lib_grouped = (C.cast(a, _u64p) for a in arrays)
+        keep = [ids, lib] + arrays
+    return o, res, names, keep
+
+
+def _markdup_dict(o, res, names, with_libraries: bool) -> dict:
+    """the counts of a marking call by the names of MARKDUP_COUNTS, OPTICAL_COUNTS (with an optical distance), "templates_without_barcode" (with a barcode source),
+    BARCODE_GROUP_COUNTS (with edits) and "libraries" (with read groups)"""
+    optical, barcode = o.optical_distance >= 0, o.barcode_mode != BARCODE_OFF
+    grouped = barcode and o.barcode_edits >= 0
+    c = dict(zip(MARKDUP_COUNTS, (int(v) for v in res.counts)))
+    if optical:
+        c.update(zip(OPTICAL_COUNTS, (int(v) for v in res.optical)))
+    if barcode:
+        c["templates_without_barcode"] = int(res.no_barcode)
+    if grouped:
+        c.update(zip(BARCODE_GROUP_COUNTS, (int(v) for v in res.grouped)))
+    if with_libraries:
+        c["libraries"] = _library_counts(names, res.lib_counts)
+        for k, nm in enumerate(names):
+            if optical:
+                c["libraries"][nm].update(zip(OPTICAL_COUNTS, (int(v) for v in res.lib_optical[3 * k:3 * k + 3])))
+            if grouped:
+                c["libraries"][nm].update(zip(BARCODE_GROUP_COUNTS, (int(v) for v in res.lib_grouped[3 * k:3 * k + 3])))
+    return c
 
 
 def bam_dup_locations(records: bytes, host: bool = False, read_groups=None) -> np.ndarray:
@@ -656,26 +649,26 @@ def estimate_library_size(n: int, c: int):
 
 def bam_markdup(records: bytes, host: bool = False, read_groups=None, optical_distance=None, optical_max_set=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
                 barcode_max_set=None) -> tuple:
-    """bmh_bam_markdup_device (host=True: bmh_bam_markdup_host, no device needed): a stream of BAM records in the writer's order (a template's records next to
+    """bmh_bam_markdup_device (host=True: bmh_bam_markdup_host, no device needed) under one bmh_markdup_opt_t: a stream of BAM records in the writer's order (a template's records next to
     each other, its first primary line first) -> (the same records with flag 0x400 on every record of every duplicate template, the counts by MARKDUP_COUNTS'
     names).  Picard MarkDuplicates' rules.  A cut stream, one whose first record begins no template and a paired template without both of its
     primary lines raise ValueError.
-    read_groups: [(id, library_name), ...] (bmh_bam_markdup_groups_*) -- duplicates are called within a library only, a template's library being that of the RG:Z
+    read_groups: [(id, library_name), ...] (rg_ids, rg_lib, n_groups) -- duplicates are called within a library only, a template's library being that of the RG:Z
     tag on its first record; the counts gain "libraries": {library_name: counts}, in order of first appearance.  A template without the tag or with an ID that is
     not listed, more than 255 libraries and a repeated ID raise ValueError.  Without read_groups no tag is read.
-    optical_distance (bmh_bam_markdup_optical_*): also count the optical duplicates -- pairs of one duplicate set whose names place them on one tile within that
+    optical_distance (optical_distance, optical_max_set): also count the optical duplicates -- pairs of one duplicate set whose names place them on one tile within that
     many pixels in x and y -- the counts gain OPTICAL_COUNTS' names, with read_groups per library too; the records are those of the call without
     it.  optical_max_set (needs optical_distance; default 300 000): sets of more pairs are not examined.
-    barcode_tag="RX" or barcode_name=True (bmh_bam_markdup_barcode_*; one of the two): templates with different molecular barcodes (UMIs) are no duplicates of each
+    barcode_tag="RX" or barcode_name=True (barcode_mode, barcode_tag; one of the two): templates with different molecular barcodes (UMIs) are no duplicates of each
     other -- the barcode is the value of that tag (type Z, verbatim) on the template's first record, or the read name's last ':' field; the keys become (lo, hi,
     barcode) and (end, barcode), an optical set the pairs of one (lo, hi, barcode).  Templates without a barcode are comparable with each other only; the counts gain
     "templates_without_barcode".  A first record whose tag has another type, or whose tags cannot be walked, raises ValueError with its index.
-    barcode_edits=N (bmh_bam_markdup_barcode_edits_*; 0 .. 21, beside a barcode source): barcodes within N mismatches are one molecule -- within one
+    barcode_edits=N (barcode_edits, barcode_max_set; 0 .. 21, beside a barcode source): barcodes within N mismatches are one molecule -- within one
     (library, lo, hi) the pairs' distinct barcodes are clustered transitively and compared by their cluster's smallest, and likewise, on their own, the barcodes at
     one (library, end) before the fragment rule.  Barcodes are packed (barcode_pack): a value of more than 21 bytes or with a byte other than A C G T N - + raises
     ValueError with its record's index.  The counts gain BARCODE_GROUP_COUNTS' names, with read_groups per library too.  barcode_max_set (needs barcode_edits; default
     65 536; for tests): a key with more distinct barcodes is not clustered."""
-    L = load_library()
+    L = _markdup_api(load_library())
     records = bytes(records)
     if optical_max_set is not None and optical_distance is None:
         raise ValueError("bam_markdup: optical_max_set needs optical_distance")
@@ -685,42 +678,20 @@ def bam_markdup(records: bytes, host: bool = False, read_groups=None, optical_di
         raise ValueError("bam_markdup: barcode_max_set needs barcode_edits")
     if barcode_max_set is not None and (not isinstance(barcode_max_set, (int, np.integer)) or isinstance(barcode_max_set, bool) or not 1 <= barcode_max_set <= 0x7fffffff):
         raise ValueError(f"bam_markdup: barcode_max_set {barcode_max_set!r}: an integer in 1 .. 2^31 - 1")
-    if bc_mode != BARCODE_OFF:
-        return _bam_markdup_optical(records, host, read_groups, optical_distance, optical_max_set, (bc_mode, bc_tag), edits, barcode_max_set or 0)
-    if optical_distance is not None:
-        return _bam_markdup_optical(records, host, read_groups, optical_distance, optical_max_set)
-    L.bmh_free.argtypes = [C.c_void_p]
-    out, counts = C.c_void_p(), (C.c_uint64 * 8)()
-    if read_groups is not None:
-        ids, lib, ng, names = _library_table(read_groups)
-        lc = (C.c_uint64 * (8 * max(len(names), 1)))()
-        grp = [C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int]
-        if host:
-            L.bmh_bam_markdup_groups_host.argtypes = [C.c_char_p, C.c_uint64] + grp + [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-            rc = L.bmh_bam_markdup_groups_host(records, len(records), ids, lib, ng, C.byref(out), counts, lc)
-        else:
-            import torch
-            L.bmh_bam_markdup_groups_device.argtypes = [C.c_char_p, C.c_uint64] + grp + [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-            rc = L.bmh_bam_markdup_groups_device(records, len(records), ids, lib, ng, torch.cuda.current_stream().cuda_stream, C.byref(out), counts, lc)
-        if rc != 0:
-            raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_markdup: " + _err(L))
-        try:
-            c = dict(zip(MARKDUP_COUNTS, (int(v) for v in counts)))
-            c["libraries"] = _library_counts(names, lc)
-            return (C.string_at(out.value, len(records)) if records else b""), c
-        finally:
-            L.bmh_free(out)
+    distance = -1 if optical_distance is None else optical_distance_value(optical_distance, "bam_markdup")
+    if optical_max_set is not None and (not isinstance(optical_max_set, (int, np.integer)) or isinstance(optical_max_set, bool) or not 1 <= optical_max_set <= 0x7fffffff):
+        raise ValueError(f"bam_markdup: optical_max_set {optical_max_set!r}: an integer in 1 .. 2^31 - 1")
+    o, res, names, _keep = _markdup_records(L, read_groups, distance, int(optical_max_set or 0), bc_mode, bc_tag, edits, int(barcode_max_set or 0))
+    out = C.c_void_p()
     if host:
-        L.bmh_bam_markdup_host.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-        rc = L.bmh_bam_markdup_host(records, len(records), C.byref(out), counts)
+        rc = L.bmh_bam_markdup_host(records, len(records), C.byref(o), C.byref(out), C.byref(res))
     else:
         import torch
-        L.bmh_bam_markdup_device.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-        rc = L.bmh_bam_markdup_device(records, len(records), torch.cuda.current_stream().cuda_stream, C.byref(out), counts)
+        rc = L.bmh_bam_markdup_device(records, len(records), C.byref(o), torch.cuda.current_stream().cuda_stream, C.byref(out), C.byref(res))
     if rc != 0:
         raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_markdup: " + _err(L))
     try:
-        return (C.string_at(out.value, len(records)) if records else b""), dict(zip(MARKDUP_COUNTS, (int(v) for v in counts)))
+        return (C.string_at(out.value, len(records)) if records else b""), _markdup_dict(o, res, names, read_groups is not None)
     finally:
         L.bmh_free(out)
 
@@ -747,12 +718,12 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
                     index_format: str = "bai", csi_min_shift: int = 14, barcode_tag=None, barcode_name=None, barcode_edits=None) -> tuple:
     """bmh_bam_sorted_file_device (host=True: _host): (the complete sorted BAM file -- header members, the records in coordinate order in windows of `window`
     records (0: about 64 MiB), the end-of-file member --, its .bai index).  contigs: (name, length) pairs; both forms give the same bytes.
-    markdup=True (bmh_bam_sorted_file_markdup_*): `records` come in the writer's order, the duplicates among them are marked (bam_markdup's rules) and the counts come third.
+    markdup=True (a bmh_markdup_opt_t in bmh_sorted_file_opt_t): `records` come in the writer's order, the duplicates among them are marked (bam_markdup's rules) and the counts come third.
     read_groups (needs markdup=True): as bam_markdup takes them -- duplicates per library, and the counts gain "libraries".
-    index_format="csi" (bmh_bam_sorted_file_ex_*): the second element is the .csi index -- BGZF-compressed, bins of 2^csi_min_shift bases (10 .. 24) at the depth the
+    index_format="csi" (index_format, min_shift): the second element is the .csi index -- BGZF-compressed, bins of 2^csi_min_shift bases (10 .. 24) at the depth the
     longest contig asks for --, contigs may hold up to 2^31 - 1 bases (with markdup=True up to 2^30 - 2^24) and the BAM bytes are those of the "bai" call.
-    barcode_tag / barcode_name (bmh_bam_sorted_file_barcode_*; need markdup=True): as bam_markdup takes them; the counts gain "templates_without_barcode".
-    barcode_edits (bmh_bam_sorted_file_barcode_edits_*; needs a barcode source): as bam_markdup takes it; the counts gain BARCODE_GROUP_COUNTS' names."""
+    barcode_tag / barcode_name (need markdup=True): as bam_markdup takes them; the counts gain "templates_without_barcode".
+    barcode_edits (needs a barcode source): as bam_markdup takes it; the counts gain BARCODE_GROUP_COUNTS' names."""
     bc_mode, bc_tag = barcode_source(barcode_tag, barcode_name, "bam_sorted_file")
     if barcode_edits is not None and not markdup:
         raise ValueError("bam_sorted_file: barcode_edits needs markdup=True (barcodes are grouped where duplicates are marked)")
@@ -762,9 +733,8 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
     if read_groups is not None and not markdup:
         raise ValueError("bam_sorted_file: read_groups needs markdup=True (they decide which templates may be duplicates of each other)")
     ix_code, ix_shift = index_format_code(index_format, csi_min_shift, "bam_sorted_file")
-    L = load_library()
+    L = _markdup_api(load_library())
     records = bytes(records)
-    L.bmh_free.argtypes = [C.c_void_p]
     names = (C.c_char_p * max(len(contigs), 1))(*[c[0].encode() for c in contigs])
     lens = np.ascontiguousarray([c[1] for c in contigs] or [0], dtype=np.int64)
     if ix_code == INDEX_BAI and ((lens < 0) | (lens >= 1 << 29)).any():
@@ -772,80 +742,21 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
     if ((lens < 0) | (lens >= 1 << 31)).any():
         raise ValueError("bam_sorted_file: BAM and its CSI index hold contigs of at most 2^31 - 1 bases")
     lens = lens.astype(np.int32)
+    o, res, lib_names, _keep = _markdup_records(L, read_groups, bc_mode=bc_mode, bc_tag=bc_tag, edits=edits)
+    fo = SortedFileOpt(int(level), int(window), ix_code, ix_shift, C.pointer(o) if markdup else None)
     bam, bai, nb, ni = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
-    head = [header_text.encode(), len(contigs), names, lens.ctypes.data, records, len(records), int(level), int(window)]
-    tail = [C.byref(bam), C.byref(nb), C.byref(bai), C.byref(ni)]
-    sig = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_uint32]
-    out = [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p]
-    counts = (C.c_uint64 * 8)()
-    no_bc = C.c_uint64(0)
-    if bc_mode != BARCODE_OFF:                                # the _ex call (marking on) with the barcode's source and the count of templates without one
-        ids, lib, ng, lib_names = _library_table(read_groups) if read_groups is not None else (None, None, 0, [])
-        lc = (C.c_uint64 * (8 * max(len(lib_names), 1)))()
-        head += [ix_code, ix_shift, ids, lib, ng, bc_mode, bc_tag]; sig += [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_char_p]
-        tail += [counts, lc if read_groups is not None else None, C.byref(no_bc)]; out += [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        if edits >= 0:                                        # ... and the edits, the cap (the default) and the grouping counts
-            gc = (C.c_uint64 * 3)()
-            lg = (C.c_uint64 * (3 * max(len(lib_names), 1)))() if read_groups is not None else None
-            head += [edits, 0]; sig += [C.c_int, C.c_uint64]
-            tail += [gc, lg]; out += [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    elif ix_code == INDEX_CSI:                                # the one entry point that takes everything: counts and library counts always have their place
-        ids, lib, ng, lib_names = _library_table(read_groups) if read_groups is not None else (None, None, 0, [])
-        lc = (C.c_uint64 * (8 * max(len(lib_names), 1)))()
-        head += [ix_code, ix_shift, 1 if markdup else 0, ids, lib, ng]; sig += [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int]
-        tail += [counts if markdup else None, lc if read_groups is not None else None]; out += [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    elif markdup:
-        tail.append(counts); out.append(C.POINTER(C.c_uint64))
-    grp = ""
-    if read_groups is not None and ix_code != INDEX_CSI and bc_mode == BARCODE_OFF:
-        ids, lib, ng, lib_names = _library_table(read_groups)
-        lc = (C.c_uint64 * (8 * max(len(lib_names), 1)))()
-        head += [ids, lib, ng]; sig += [C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int]
-        tail.append(lc); out.append(C.POINTER(C.c_uint64))
-        grp = "_groups"
-    if bc_mode != BARCODE_OFF:
-        if host:
-            fn = L.bmh_bam_sorted_file_barcode_edits_host if edits >= 0 else L.bmh_bam_sorted_file_barcode_host
-            fn.argtypes = sig + out
-            rc = fn(*head, *tail)
-        else:
-            import torch
-            fn = L.bmh_bam_sorted_file_barcode_edits_device if edits >= 0 else L.bmh_bam_sorted_file_barcode_device
-            fn.argtypes = sig + [C.c_void_p] + out
-            rc = fn(*head, torch.cuda.current_stream().cuda_stream, *tail)
-    elif ix_code == INDEX_CSI:
-        if host:
-            fn = L.bmh_bam_sorted_file_ex_host
-            fn.argtypes = sig + out
-            rc = fn(*head, *tail)
-        else:
-            import torch
-            fn = L.bmh_bam_sorted_file_ex_device
-            fn.argtypes = sig + [C.c_void_p] + out
-            rc = fn(*head, torch.cuda.current_stream().cuda_stream, *tail)
-    elif host:
-        fn = getattr(L, "bmh_bam_sorted_file_markdup" + grp + "_host") if markdup else L.bmh_bam_sorted_file_host
-        fn.argtypes = sig + out
-        rc = fn(*head, *tail)
+    head = [header_text.encode(), len(contigs), names, lens.ctypes.data, records, len(records), C.byref(fo)]
+    tail = [C.byref(bam), C.byref(nb), C.byref(bai), C.byref(ni), C.byref(res) if markdup else None]
+    if host:
+        rc = L.bmh_bam_sorted_file_host(*head, *tail)
     else:
         import torch
-        fn = getattr(L, "bmh_bam_sorted_file_markdup" + grp + "_device") if markdup else L.bmh_bam_sorted_file_device
-        fn.argtypes = sig + [C.c_void_p] + out
-        rc = fn(*head, torch.cuda.current_stream().cuda_stream, *tail)
+        rc = L.bmh_bam_sorted_file_device(*head, torch.cuda.current_stream().cuda_stream, *tail)
     if rc != 0:
         raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_sorted_file: " + _err(L))
     try:
         if markdup:
-            c = dict(zip(MARKDUP_COUNTS, (int(v) for v in counts)))
-            if read_groups is not None:
-                c["libraries"] = _library_counts(lib_names, lc)
-            if bc_mode != BARCODE_OFF:
-                c["templates_without_barcode"] = int(no_bc.value)
-            if bc_mode != BARCODE_OFF and edits >= 0:
-                c.update(zip(BARCODE_GROUP_COUNTS, (int(v) for v in gc)))
-                for k, nm in enumerate(lib_names if read_groups is not None else []):
-                    c["libraries"][nm].update(zip(BARCODE_GROUP_COUNTS, (int(v) for v in lg[3 * k:3 * k + 3])))
-            return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value), c
+            return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value), _markdup_dict(o, res, lib_names, read_groups is not None)
         return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)
     finally:
         L.bmh_free(bam); L.bmh_free(bai)

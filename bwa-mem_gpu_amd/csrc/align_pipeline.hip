@@ -50,20 +50,21 @@ struct aligner_t {
 	std::string rg_id;             // the aligner's own copy of popt->rg_id (po.rg_id points into it): the caller's string need not outlive the call that created the aligner
 	uint32_t max_qlen = 768;       // the extension cap of the chain workspaces (bmh_aligner_set_max_qlen)
 	bmh_reseed_opt_t rs = {0, 1.5f, 10, 20};   // the seeding rounds (bmh_aligner_set_reseed; enable 0: the first round only)
-	bdp_bc_t barcode = {BDP_BC_OFF, 0, 0};      // ... with markdup: compare the templates' barcodes, from a tag or the read name (bmh_aligner_set_markdup_barcode)
-	uint32_t bc_edits = 0;                     // ... with barcode.pack (bmh_aligner_set_markdup_barcode_edits): the mismatches within which barcodes are one molecule
-	int64_t optical = -1;                      // ... with markdup: also count the optical duplicates within this distance (bmh_aligner_set_markdup_optical); -1: not
 	bool markdup = false;                      // sorted BAM output: flag 0x400 on the records of duplicate templates (bmh_aligner_set_markdup)
+	// ... and what the marking is made under (csrc/bam_dup.h).  Its barcode source, edits and optical distance are set through bmh_aligner_set_markdup_barcode, _barcode_edits
+	// and _optical, which refuse without markdup, and go where markdup goes: plan.barcode(), .grouping() and .optical() are NULL in a run that marks nothing.  Its table
+	// is the run's read groups (below), marked or not
+	bdp_plan_t plan;
 	int out_fmt = BMH_OUT_SAM, out_level = 1;  // what the sink receives (bmh_aligner_set_output): the records' text, or BGZF members of BAM records
 	std::vector<char> ctg_blob; std::vector<uint32_t> ctg_noff;      // the contig table as the BAM converter takes it
 	// a run over read groups (bmh_aligner_run_groups), while it lasts: every group's ID (a batch's records carry its group's) and the table duplicate marking reads;
 	// the serial changes whenever the table does, so a lane knows whether its copy on the device is the run's
-	std::vector<std::string> group_ids; bdp_table_t groups; uint64_t groups_serial = 0;
+	std::vector<std::string> group_ids; uint64_t groups_serial = 0;
 	const char *rg_of(int group) const { return group >= 0 && (size_t)group < group_ids.size() ? group_ids[(size_t)group].c_str() : po.rg_id; }
 	// a run that keeps its input's read groups (bmh_aligner_set_keep_rg), while it lasts: the same table holds the header's @RG lines, but the group is a property of
 	// a read (rs.groups), not of a batch -- a batch's group stays -1 and its records take their IDs from the table by the read's index
 	bool per_read = false;
-	bmh_read_groups_t read_groups(const uint32_t *read_group) const { return {read_group, groups.ids.data(), groups.id_off.data(), (uint32_t)groups.lib.size()}; }
+	bmh_read_groups_t read_groups(const uint32_t *read_group) const { return {read_group, plan.table.ids.data(), plan.table.id_off.data(), (uint32_t)plan.table.lib.size()}; }
 };
 
 }   // namespace
@@ -245,7 +246,7 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 	d.d_h_rec = paired ? Ln.d_hrec.p : nullptr; d.d_unflag = paired ? Ln.d_unflag.p : nullptr;
 	if (Ln.has_quals) d.d_quals = Ln.d_quals.p;
 	if (Ln.has_comments) { d.d_comments = Ln.d_comments.p; d.d_comment_off = Ln.d_comment_off.p; }
-	if (Ln.has_rgrp) { d.d_read_group = Ln.d_rgrp.p; d.d_rg_ids = Ln.d_rg_ids.p; d.d_rg_id_off = Ln.d_rg_off.p; d.n_rg = (uint32_t)A.groups.lib.size(); }
+	if (Ln.has_rgrp) { d.d_read_group = Ln.d_rgrp.p; d.d_rg_ids = Ln.d_rg_ids.p; d.d_rg_id_off = Ln.d_rg_off.p; d.n_rg = (uint32_t)A.plan.table.lib.size(); }
 	const size_t wb = bmh_sam_text_work(n);
 	RCK(Ln.d_work.need(wb)); RCK(Ln.d_text_off.need((size_t)n + 2));
 	const int64_t total = bmh_sam_text_sizes(&po, &d, Ln.d_text_off.p, Ln.d_work.p, Ln.d_work.cap, Ln.st);
@@ -269,18 +270,18 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 			const uint32_t nrec = bo.n_records;
 			// duplicate marking: on the records in the writer's order, before the sort -- heads, their scan, one entry per template; the ordinals follow the records
 			const uint32_t *d_tpl = nullptr, *d_info = nullptr, *d_stpl = nullptr, *d_lib3 = nullptr; const bdp_entry_t *d_e = nullptr; const bdp_loc_t *d_l = nullptr; const uint64_t *d_b = nullptr;
-			const bool optical = A.markdup && A.optical >= 0, barcode = A.markdup && A.barcode.mode != BDP_BC_OFF;
+			const bdp_bc_t *bc = A.plan.barcode(); const bool optical = A.plan.optical() != nullptr, barcode = bc != nullptr;
 			const uint32_t tmax = paired ? n / 2 : n;                   // the batch's templates: every read or pair leaves at least one record, so no more entries than this come down
 			if (A.markdup) {
 				if (!Ln.bdp && !(Ln.bdp = bdp_dev_create())) return BMH_ENOMEM;
-				if (Ln.groups_serial != A.groups_serial) { RCK(bdp_dev_set_groups(Ln.bdp, &A.groups, Ln.st)); Ln.groups_serial = A.groups_serial; }
-				RCK(bdp_batch_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &d_tpl, &d_e, &d_info, optical ? &d_l : nullptr, barcode ? &A.barcode : nullptr, barcode ? &d_b : nullptr));
+				if (Ln.groups_serial != A.groups_serial) { RCK(bdp_dev_set_groups(Ln.bdp, &A.plan.table, Ln.st)); Ln.groups_serial = A.groups_serial; }
+				RCK(bdp_batch_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &d_tpl, &d_e, &d_info, optical ? &d_l : nullptr, bc, barcode ? &d_b : nullptr));
 				RCK(R.stpl.need((size_t)nrec + 1)); RCK(R.dup_e.need((size_t)std::min(nrec, tmax) + 1));
 				if (optical) RCK(R.dup_l.need((size_t)std::min(nrec, tmax) + 1));
 				if (barcode) RCK(R.dup_b.need((size_t)std::min(nrec, tmax) + 1));
 				if (A.per_read) {                                     // a batch of several libraries: its counts per library, from the entries' library bytes
-					RCK(bdp_batch_lib_counts_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, A.groups.n_lib, Ln.st, &d_lib3));
-					RCK(R.lib3.need(3 * (size_t)A.groups.n_lib));
+					RCK(bdp_batch_lib_counts_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, A.plan.table.n_lib, Ln.st, &d_lib3));
+					RCK(R.lib3.need(3 * (size_t)A.plan.table.n_lib));
 				}
 			}
 			RCK(bsr_sort_run_device(Ln.bsr, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &ds, &dk, &dso, d_tpl, &d_stpl));
@@ -296,17 +297,17 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 				if (ne) HIPCK(hipMemcpyAsync(R.dup_e.p, d_e, sizeof(bdp_entry_t) * ne, hipMemcpyDeviceToHost, Ln.st));
 				if (ne && optical) HIPCK(hipMemcpyAsync(R.dup_l.p, d_l, sizeof(bdp_loc_t) * ne, hipMemcpyDeviceToHost, Ln.st));
 				if (ne && barcode) HIPCK(hipMemcpyAsync(R.dup_b.p, d_b, 8 * ne, hipMemcpyDeviceToHost, Ln.st));
-				const size_t ni = A.groups.empty() && !barcode ? 16 : 4 * bdp_info_words(barcode ? &A.barcode : nullptr);      // (with read groups: the words of a template without a known group; with barcodes: of one whose tags are refused)
+				const size_t ni = A.plan.table.empty() && !barcode ? 16 : 4 * bdp_info_words(bc);      // (with read groups: the words of a template without a known group; with barcodes: of one whose tags are refused)
 				HIPCK(hipMemcpyAsync(R.dup_info, d_info, ni, hipMemcpyDeviceToHost, Ln.st));
-				if (d_lib3) HIPCK(hipMemcpyAsync(R.lib3.p, d_lib3, 12 * (size_t)A.groups.n_lib, hipMemcpyDeviceToHost, Ln.st));
-				R.dup_d2h = 4ull * nrec + sizeof(bdp_entry_t) * ne + ni + (d_lib3 ? 12ull * A.groups.n_lib : 0) + (optical ? sizeof(bdp_loc_t) * ne : 0) + (barcode ? 8ull * ne : 0);
+				if (d_lib3) HIPCK(hipMemcpyAsync(R.lib3.p, d_lib3, 12 * (size_t)A.plan.table.n_lib, hipMemcpyDeviceToHost, Ln.st));
+				R.dup_d2h = 4ull * nrec + sizeof(bdp_entry_t) * ne + ni + (d_lib3 ? 12ull * A.plan.table.n_lib : 0) + (optical ? sizeof(bdp_loc_t) * ne : 0) + (barcode ? 8ull * ne : 0);
 				Ln.copy_bytes[1] += R.dup_d2h;
 			}
 			HIPCK(hipEventRecord(Ln.ev_c[3], Ln.st));
 			Ln.copy_bytes[1] += bo.bam_bytes + 16ull * nrec; Ln.d2h_marked = true;
 			HIPCK(hipStreamSynchronize(Ln.st));
 			if (A.markdup && nrec) {
-				RCK(bdp_batch_check(nrec, R.dup_info, !A.groups.empty(), "sorted BAM", barcode, barcode && A.barcode.pack));
+				RCK(bdp_batch_check(nrec, R.dup_info, !A.plan.table.empty(), "sorted BAM", barcode, barcode && bc->pack));
 				if (R.dup_info[0] == 0 || R.dup_info[0] > std::min(nrec, tmax)) { bmh_set_error("sorted BAM: internal error: %u templates among %u records", R.dup_info[0], nrec); return BMH_EINVAL; }
 			}
 			if (R.soff.p[nrec] != bo.bam_bytes) {                 // (the gather skips a record whose offsets lie outside the buffers: the scan of the sizes shows it)
@@ -611,9 +612,9 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 		if (!rs.groups) { bmh_set_error("bmh_aligner_run: internal error: a run that keeps read groups met a batch without them"); return BMH_EINVAL; }
 		if (text_dev) {
 			if (Ln.rg_serial != A.groups_serial) {
-				RCK(Ln.d_rg_ids.need(A.groups.ids.size() + 1)); RCK(Ln.d_rg_off.need(A.groups.id_off.size()));
-				HIPCK(hipMemcpyAsync(Ln.d_rg_ids.p, A.groups.ids.data(), A.groups.ids.size(), hipMemcpyHostToDevice, Ln.st));
-				HIPCK(hipMemcpyAsync(Ln.d_rg_off.p, A.groups.id_off.data(), 4 * A.groups.id_off.size(), hipMemcpyHostToDevice, Ln.st));
+				RCK(Ln.d_rg_ids.need(A.plan.table.ids.size() + 1)); RCK(Ln.d_rg_off.need(A.plan.table.id_off.size()));
+				HIPCK(hipMemcpyAsync(Ln.d_rg_ids.p, A.plan.table.ids.data(), A.plan.table.ids.size(), hipMemcpyHostToDevice, Ln.st));
+				HIPCK(hipMemcpyAsync(Ln.d_rg_off.p, A.plan.table.id_off.data(), 4 * A.plan.table.id_off.size(), hipMemcpyHostToDevice, Ln.st));
 				Ln.rg_serial = A.groups_serial;                       // (the aligner's table outlives the run's batches: the copy reads it in its own time)
 			}
 			RCK(Ln.d_rgrp.need(n + 1));
@@ -929,7 +930,7 @@ int bmh_aligner_set_output(bmh_aligner_t *h, int format, int level)
 	if (format != BMH_OUT_SAM && format != BMH_OUT_BAM && format != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_output: format %d (BMH_OUT_SAM, BMH_OUT_BAM or BMH_OUT_BAM_SORTED)", format); return BMH_EINVAL; }
 	if (format != BMH_OUT_SAM && level != 0 && level != 1) { bmh_set_error("bmh_aligner_set_output: level %d (0 or 1)", level); return BMH_EINVAL; }
 	if (format == BMH_OUT_BAM_SORTED) { h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), "sorted BAM output", h->ix_format, h->ix_shift)); }
-	if (format != BMH_OUT_BAM_SORTED) { h->a.markdup = false; h->a.optical = -1; h->a.barcode.mode = BDP_BC_OFF; h->a.barcode.pack = 0; }      // (duplicates are marked in sorted output only: the options go with the format)
+	if (format != BMH_OUT_BAM_SORTED) { h->a.markdup = false; h->a.plan.opt.distance = -1; h->a.plan.bc.mode = BDP_BC_OFF; h->a.plan.bc.pack = 0; }      // (duplicates are marked in sorted output only: the options go with the format)
 	h->a.out_fmt = format; h->a.out_level = level;
 	return BMH_OK;
 }
@@ -971,7 +972,7 @@ int bmh_aligner_set_markdup(bmh_aligner_t *h, int on)
 	if (on && h->a.out_fmt != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_markdup: duplicates are marked in sorted output (bmh_aligner_set_output with BMH_OUT_BAM_SORTED comes first)"); return BMH_EINVAL; }
 	if (on) RCK(bsr_markdup_contigs(h->a.n_contigs, h->a.len.data(), h->a.name_ptr.data(), "bmh_aligner_set_markdup"));      // (only a CSI run can hold such a contig)
 	h->a.markdup = on != 0;
-	if (!on) { h->a.optical = -1; h->a.barcode.mode = BDP_BC_OFF; h->a.barcode.pack = 0; }
+	if (!on) { h->a.plan.opt.distance = -1; h->a.plan.bc.mode = BDP_BC_OFF; h->a.plan.bc.pack = 0; }
 	return BMH_OK;
 }
 
@@ -979,11 +980,11 @@ int bmh_aligner_set_markdup_barcode(bmh_aligner_t *h, int mode, const char *tag)
 {
 	const char *fn = "bmh_aligner_set_markdup_barcode";
 	if (!h) { bmh_set_error("%s: null aligner", fn); return BMH_EINVAL; }
-	if (mode == BDP_BC_OFF) { h->a.barcode.mode = BDP_BC_OFF; h->a.barcode.pack = 0; return BMH_OK; }
+	if (mode == BDP_BC_OFF) { h->a.plan.bc.mode = BDP_BC_OFF; h->a.plan.bc.pack = 0; return BMH_OK; }
 	if (!h->a.markdup) { bmh_set_error("%s: barcodes are compared where duplicates are marked (bmh_aligner_set_markdup comes first)", fn); return BMH_EINVAL; }
 	bdp_bc_t bc;
 	RCK(bdp_barcode_check(mode, tag, fn, &bc));
-	h->a.barcode = bc;
+	h->a.plan.bc = bc;
 	return BMH_OK;
 }
 
@@ -991,11 +992,11 @@ int bmh_aligner_set_markdup_barcode_edits(bmh_aligner_t *h, int n)
 {
 	const char *fn = "bmh_aligner_set_markdup_barcode_edits";
 	if (!h) { bmh_set_error("%s: null aligner", fn); return BMH_EINVAL; }
-	if (n == -1) { h->a.barcode.pack = 0; return BMH_OK; }
+	if (n == -1) { h->a.plan.bc.pack = 0; return BMH_OK; }
 	if (!h->a.markdup) { bmh_set_error("%s: barcodes are grouped where duplicates are marked (bmh_aligner_set_markdup comes first)", fn); return BMH_EINVAL; }
-	bdp_bc_t bc = h->a.barcode;
+	bdp_bc_t bc = h->a.plan.bc;
 	RCK(bdp_group_check(n, 0, fn, &bc));                              // (a source comes first: bmh_aligner_set_markdup_barcode)
-	h->a.barcode = bc; h->a.bc_edits = (uint32_t)n;
+	h->a.plan.bc = bc; h->a.plan.grp.edits = (uint32_t)n;
 	return BMH_OK;
 }
 
@@ -1021,10 +1022,10 @@ int bmh_aligner_set_markdup_optical(bmh_aligner_t *h, int64_t distance)
 {
 	const char *fn = "bmh_aligner_set_markdup_optical";
 	if (!h) { bmh_set_error("%s: null aligner", fn); return BMH_EINVAL; }
-	if (distance == -1) { h->a.optical = -1; return BMH_OK; }
+	if (distance == -1) { h->a.plan.opt.distance = -1; return BMH_OK; }
 	if (!h->a.markdup) { bmh_set_error("%s: optical duplicates are counted where duplicates are marked (bmh_aligner_set_markdup comes first)", fn); return BMH_EINVAL; }
 	RCK(bdp_optical_check(distance, 0, fn));
-	h->a.optical = distance;
+	h->a.plan.opt.distance = distance;
 	return BMH_OK;
 }
 
@@ -1117,7 +1118,7 @@ struct batch_src_t {
 struct out_stage_t {
 	bmh_aligner *h; const int fmt; bmh_sam_sink_t sink; void *user; int n_threads; const char *fn;
 	uint64_t n_bytes = 0;                                           // handed to the sink so far
-	int lib_of(int group) const { return group >= 0 && (size_t)group < h->a.groups.lib.size() ? (int)h->a.groups.lib[(size_t)group] : -1; }
+	int lib_of(int group) const { return group >= 0 && (size_t)group < h->a.plan.table.lib.size() ? (int)h->a.plan.table.lib[(size_t)group] : -1; }
 	int emit(const void *p, size_t n) { if (n && sink(user, (const char *)p, n) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; } n_bytes += n; return BMH_OK; }
 	// (the index is valid again once the merge has written the whole file)
 	int begin() { if (fmt == BMH_OUT_BAM_SORTED) { h->dup_valid = false; h->opt_valid = false; h->bc_valid = false; h->opt_ms = 0; h->dup_times[0] = h->dup_times[1] = h->dup_times[2] = 0; h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), fn, h->ix_format, h->ix_shift)); h->sort_ix.valid = false;
@@ -1127,9 +1128,9 @@ struct out_stage_t {
 		if (fmt != BMH_OUT_BAM_SORTED) return emit(R.text.p, (size_t)R.text_len);
 		if (!R.n_rec) return BMH_OK;
 		bsr_dup_t bd = {R.stpl.p, R.dup_e.p, R.dup_info[0], R.dup_info[2], R.dup_info[3], lib_of(R.group)};
-		if (h->a.markdup && h->a.per_read) { bd.lib3 = R.lib3.p; bd.n_lib3 = h->a.groups.n_lib; }
-		if (h->a.markdup && h->a.optical >= 0) bd.locs = R.dup_l.p;
-		if (h->a.markdup && h->a.barcode.mode != BDP_BC_OFF) bd.bcs = R.dup_b.p;
+		if (h->a.markdup && h->a.per_read) { bd.lib3 = R.lib3.p; bd.n_lib3 = h->a.plan.table.n_lib; }
+		if (h->a.plan.optical()) bd.locs = R.dup_l.p;
+		if (h->a.plan.barcode()) bd.bcs = R.dup_b.p;
 		if (h->a.markdup) h->dup_times[2] += (double)R.dup_d2h;
 		return h->store.append((const uint8_t *)R.text.p, R.text_len, R.skeys.p, R.soff.p, R.n_rec, h->a.markdup ? &bd : nullptr);      // a sorted run: kept until the end of the input
 	}
@@ -1158,10 +1159,9 @@ struct out_stage_t {
 				srt.reserve((size_t)bb + 1);
 				for (uint32_t i : ord) { srt.insert(srt.end(), bam + off[i], bam + off[i + 1]); soff.push_back(srt.size()); }
 				std::vector<uint32_t> tpl, stpl; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> locs; std::vector<uint64_t> bcs; uint64_t info[2] = {0, 0};
-				const bool optical = A.markdup && A.optical >= 0, barcode = A.markdup && A.barcode.mode != BDP_BC_OFF;
+				const bool optical = A.plan.optical() != nullptr, barcode = A.plan.barcode() != nullptr;
 				if (A.markdup) {                                   // the host forms of the device's heads, ordinals and entries
-					const bdp_groups_t G = A.groups.view();
-					rc = bdp_entries_host(bam, off.data(), (uint32_t)ord.size(), tpl, E, info, fn, A.groups.empty() ? nullptr : &G, optical ? &locs : nullptr, barcode ? &A.barcode : nullptr, barcode ? &bcs : nullptr);
+					rc = bdp_entries_host(bam, off.data(), (uint32_t)ord.size(), tpl, E, info, fn, A.plan, optical ? &locs : nullptr, barcode ? &bcs : nullptr);
 					for (uint32_t i : ord) stpl.push_back(tpl[i]);
 				}
 				bsr_dup_t bd = {stpl.data(), E.data(), (uint32_t)E.size(), info[0], info[1], lib_of(group)};
@@ -1169,10 +1169,10 @@ struct out_stage_t {
 				if (barcode) bd.bcs = bcs.data();
 				std::vector<uint32_t> lib3;
 				if (rc == BMH_OK && A.markdup && A.per_read) {        // the host form of bdp_batch_lib_counts_device
-					std::vector<uint64_t> lc((size_t)BDP_N_COUNTS * A.groups.n_lib, 0);
-					bdp_lib_tally_host(bam, off.data(), (uint32_t)ord.size(), tpl.data(), E.data(), E.size(), A.groups.n_lib, lc.data());
-					for (uint32_t l = 0; l < A.groups.n_lib; ++l) for (int k = 0; k < 3; ++k) lib3.push_back((uint32_t)lc[(size_t)BDP_N_COUNTS * l + BDP_SECSUP + k]);
-					bd.lib3 = lib3.data(); bd.n_lib3 = A.groups.n_lib;
+					std::vector<uint64_t> lc((size_t)BDP_N_COUNTS * A.plan.table.n_lib, 0);
+					bdp_lib_tally_host(bam, off.data(), (uint32_t)ord.size(), tpl.data(), E.data(), E.size(), A.plan.table.n_lib, lc.data());
+					for (uint32_t l = 0; l < A.plan.table.n_lib; ++l) for (int k = 0; k < 3; ++k) lib3.push_back((uint32_t)lc[(size_t)BDP_N_COUNTS * l + BDP_SECSUP + k]);
+					bd.lib3 = lib3.data(); bd.n_lib3 = A.plan.table.n_lib;
 				}
 				if (rc == BMH_OK && !ord.empty()) rc = h->store.append(srt.data(), bb, keys.data(), soff.data(), ord.size(), A.markdup ? &bd : nullptr);
 			}
@@ -1193,18 +1193,15 @@ struct out_stage_t {
 		if (!L0.bam && !(L0.bam = bmh_bam_ws_create())) rc = BMH_ENOMEM;
 		if (rc == BMH_OK && !L0.bsr && !(L0.bsr = bsr_dev_create())) rc = BMH_ENOMEM;
 		const double tm0 = now_s();
-		const uint32_t n_lib = h->a.markdup ? h->a.groups.n_lib : 0;
+		const uint32_t n_lib = h->a.markdup ? h->a.plan.table.n_lib : 0;
 		h->lib_counts.assign((size_t)BDP_N_COUNTS * n_lib, 0);
-		const bool optical = h->a.markdup && h->a.optical >= 0;
+		bdp_plan_t P = h->a.plan;                                     // the aligner's plan with the places of this run's counts
+		const bool optical = P.optical() != nullptr, barcode = P.barcode() != nullptr, grouped = P.grouping() != nullptr;
 		h->lib_opt.assign(optical ? (size_t)BDP_OPT_N * n_lib : 0, 0);
-		const bdp_optical_t O = {h->a.optical, (uint32_t)BDP_OPT_MAX_SET, h->opt_counts, n_lib ? h->lib_opt.data() : nullptr};
-		const bool barcode = h->a.markdup && h->a.barcode.mode != BDP_BC_OFF;
+		P.lib_counts = n_lib ? h->lib_counts.data() : nullptr; P.opt.out = h->opt_counts; P.opt.lib_out = n_lib ? h->lib_opt.data() : nullptr; P.grp.out = h->grp_counts;
 		h->no_barcode = barcode ? bdp_no_barcode(h->store.bcs.data(), h->store.bcs.size()) : 0;
-		const bool grouped = barcode && h->a.barcode.pack;
 		for (int k = 0; k < BDP_GRP_N; ++k) h->grp_counts[k] = 0;
-		const bdp_group_t GR = {h->a.bc_edits, (uint32_t)BDP_BC_MAX_SET, h->grp_counts, nullptr};
-		if (rc == BMH_OK) rc = bsr_merge_device(L0.bsr, L0.bam, h->store, h->sort_window, h->a.out_level, L0.st, h->sort_ix, forward, this, h->a.markdup ? h->dup_counts : nullptr, h->dup_times,
-		                                        n_lib, n_lib ? h->lib_counts.data() : nullptr, optical ? &O : nullptr, optical ? &h->opt_ms : nullptr, barcode, grouped ? &GR : nullptr);
+		if (rc == BMH_OK) rc = bsr_merge_device(L0.bsr, L0.bam, h->store, h->sort_window, h->a.out_level, L0.st, h->sort_ix, forward, this, h->a.markdup ? h->dup_counts : nullptr, P, h->dup_times, &h->opt_ms);
 		for (size_t k = 0; rc == BMH_OK && k < h->store.lib_info.size() && k / 3 < n_lib; ++k) h->lib_counts[BDP_N_COUNTS * (k / 3) + BDP_SECSUP + k % 3] = h->store.lib_info[k];
 		if (trace && h->a.markdup) fprintf(stderr, "[aligner] duplicate marking: %.0f bytes of ordinals and entries came down with the batches\n", h->dup_times[2]);
 		if (trace) fprintf(stderr, "[aligner] sorted output: %zu runs (%llu spilled) merged in %.1f ms\n", h->store.runs.size(), (unsigned long long)h->store.spilled, (now_s() - tm0) * 1e3);
@@ -1540,7 +1537,7 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 	if (!P) return BMH_EINVAL;
 	aligner_t &A = h->a;
 	// the run's table is the aligner's until the run is over, whichever way it ends
-	struct table_guard_t { aligner_t &A; bool on; ~table_guard_t() { if (on) { A.group_ids.clear(); A.groups = bdp_table_t(); A.per_read = false; ++A.groups_serial; } } } guard{A, false};
+	struct table_guard_t { aligner_t &A; bool on; ~table_guard_t() { if (on) { A.group_ids.clear(); A.plan.table = bdp_table_t(); A.per_read = false; ++A.groups_serial; } } } guard{A, false};
 	if (keep) {
 		// the header was read whole when the pump opened the file: its @RG lines are the run's read groups, and the caller hears of them before the first record
 		const bmh_rg_table_t *T = bmh_pump_read_groups(P);
@@ -1548,7 +1545,7 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 		G.id_off.assign(1, 0u);
 		for (size_t g = 0; g < T->ids.size(); ++g) { G.ids += T->ids[g]; G.id_off.push_back((uint32_t)G.ids.size()); G.lib.push_back((uint8_t)T->lib[g]); }      // (beyond 255 libraries the byte is not read: no duplicate marking)
 		G.n_lib = (uint32_t)T->lib_names.size();
-		A.group_ids.assign(T->ids.begin(), T->ids.end()); A.groups = G; A.per_read = true; ++A.groups_serial; guard.on = true;
+		A.group_ids.assign(T->ids.begin(), T->ids.end()); A.plan.table = G; A.per_read = true; ++A.groups_serial; guard.on = true;
 		if (h->rg_header) {
 			std::string lines;
 			for (const std::string &l : T->lines) { lines += l; lines += '\n'; }
@@ -1601,7 +1598,7 @@ int bmh_aligner_run_groups(bmh_aligner_t *h, const bmh_read_group_t *groups, int
 	bdp_table_t T;
 	RCK(bdp_table_make(T, ids.data(), libs.data(), n_groups, fn));
 	if (h->a.markdup && h->a.n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d reference sequences: with read groups duplicate marking takes at most 2^24 (the library is the top byte of its key)", fn, h->a.n_contigs); return BMH_EINVAL; }
-	if (h->a.markdup && h->a.optical >= 0 && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: with an optical distance a run takes at most %d (a location holds its group's row in 16 bits)", fn, n_groups, (int)BDP_OPT_MAX_GROUPS); return BMH_EINVAL; }
+	if (h->a.plan.optical() && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: with an optical distance a run takes at most %d (a location holds its group's row in 16 bits)", fn, n_groups, (int)BDP_OPT_MAX_GROUPS); return BMH_EINVAL; }
 	for (int g = 0; g < n_groups; ++g)
 		for (const char *path : {groups[g].path1, groups[g].path2}) {
 			struct stat sb;
@@ -1661,9 +1658,9 @@ int bmh_aligner_run_groups(bmh_aligner_t *h, const bmh_read_group_t *groups, int
 		}
 	};
 	aligner_t &A = h->a;
-	A.group_ids.assign(ids.begin(), ids.end()); A.groups = T; ++A.groups_serial;
+	A.group_ids.assign(ids.begin(), ids.end()); A.plan.table = T; ++A.groups_serial;
 	rc = run_loaded(h, fn, dev, fill, true, run_pairs, n_lanes, n_threads, sink, user, stats);
-	A.group_ids.clear(); A.groups = bdp_table_t(); ++A.groups_serial;
+	A.group_ids.clear(); A.plan.table = bdp_table_t(); ++A.groups_serial;
 	close_pump();
 	bmh_reads_note_counts(ld.cnt); bmh_reads_note_inflate_counts(ld.icnt); bmh_reads_note_bam_counts(ld.bcnt);
 	return rc;

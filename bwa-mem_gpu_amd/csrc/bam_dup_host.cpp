@@ -104,12 +104,13 @@ int bdp_refs_fit(const uint8_t *recs, const uint64_t *off, uint32_t n, const cha
 	return BMH_OK;
 }
 
-int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn, const bdp_groups_t *G,
-                     std::vector<bdp_loc_t> *locs, const bdp_bc_t *bc, std::vector<uint64_t> *bcs)
+int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn, const bdp_plan_t &P,
+                     std::vector<bdp_loc_t> *locs, std::vector<uint64_t> *bcs)
 {
+	const bdp_bc_t *bc = bcs ? P.barcode() : nullptr;
+	const bdp_groups_t G = P.table.view();
 	tpl.resize(n); entries.clear();
 	if (locs) locs->clear();
-	if (bc && (bc->mode == BDP_BC_OFF || !bcs)) bc = nullptr;
 	if (bcs) bcs->clear();
 	if (n && !bdp_head(bsr_flag(recs + off[0]))) return bdp_batch_refused(n, n + 1, fn);
 	std::vector<uint32_t> start;
@@ -127,7 +128,7 @@ int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::
 	for (size_t t = 0; t < start.size(); ++t) {
 		const uint32_t a = start[t], b = t + 1 < start.size() ? start[t + 1] : n;
 		uint32_t role = 0, row = 0;
-		const int st = G ? bdp_entry_lib(recs, off, a, b, *G, &entries[t], &role, &row) : bdp_entry(recs, off, a, b, &entries[t], &role) ? BDP_E_OK : BDP_E_TEMPLATE;
+		const int st = P.groups() ? bdp_entry_lib(recs, off, a, b, G, &entries[t], &role, &row) : bdp_entry(recs, off, a, b, &entries[t], &role) ? BDP_E_OK : BDP_E_TEMPLATE;
 		if (st == BDP_E_TEMPLATE) return bdp_batch_refused(n, a + 1, fn);
 		if (st != BDP_E_OK) return bdp_group_refused(a, st, fn);
 		if (locs) (*locs)[t] = bdp_location(recs + off[a], role, row, bc && bc->mode == BDP_BC_NAME);
@@ -174,12 +175,12 @@ void bdp_group_host(const bdp_entry_t *E, uint64_t T, const uint64_t *B, const b
 	for (size_t i = 0; i < el.size(); ++i) words[el[i].id] = word[bdp_uf_find(parent.data(), wid[i])];
 }
 
-void bdp_decide_host(const bdp_entry_t *E, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5], uint32_t n_lib, uint64_t *lib_counts, const uint64_t *B, const bdp_group_t *G,
-                     std::vector<uint64_t> *pair_words)
+void bdp_decide_host(const bdp_entry_t *E, uint64_t T, std::vector<uint32_t> &bits, uint64_t counts[5], const bdp_plan_t &P, const uint64_t *B, std::vector<uint64_t> *pair_words)
 {
+	const uint32_t n_lib = P.n_lib(); uint64_t *lib_counts = n_lib ? P.lib_counts : nullptr;
+	const bdp_group_t *G = B ? P.grouping() : nullptr;
 	// grouping by edits: the pair pass and the fragment pass each compare their own canonical words
 	std::vector<uint64_t> Bp, Bf;
-	if (!B) G = nullptr;
 	if (G) { bdp_group_host(E, T, B, *G, n_lib, false, Bp); bdp_group_host(E, T, B, *G, n_lib, true, Bf); if (pair_words) *pair_words = Bp; }
 	auto bc = [&](uint32_t t) { return G ? Bp[t] : B ? B[t] : 0ull; };  // (without barcodes every word is equal: the keys are those of old)
 	auto bci = [&](uint32_t t, uint32_t end) { return G ? Bf[2 * (size_t)t + end] : B ? B[t] : 0ull; };
@@ -269,13 +270,11 @@ void bdp_lib_tally_host(const uint8_t *recs, const uint64_t *off, uint32_t n, co
 	}
 }
 
-int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn, const bdp_table_t *T, uint64_t *lib_counts, const bdp_optical_t *O,
-                     const bdp_bc_t *bc, uint64_t *no_barcode, const bdp_group_t *grp)
+int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t counts[BDP_N_COUNTS], const char *fn, const bdp_plan_t &P)
 {
-	if (bc && bc->mode == BDP_BC_OFF) bc = nullptr;
-	if (!bc || !bc->pack) grp = nullptr;
+	const bdp_table_t *T = P.groups(); const bdp_optical_t *O = P.optical(); const bdp_bc_t *bc = P.barcode(); const bdp_group_t *grp = P.grouping();
 	std::vector<uint64_t> Bp;
-	if (no_barcode) *no_barcode = 0;
+	if (P.no_barcode) *P.no_barcode = 0;
 	std::vector<uint64_t> Bw;
 	const uint32_t n = (uint32_t)(off.size() - 1);
 	for (int k = 0; k < BDP_N_COUNTS; ++k) counts[k] = 0;
@@ -284,162 +283,121 @@ int bdp_markdup_host(uint8_t *recs, const std::vector<uint64_t> &off, uint64_t c
 			bmh_set_error("%s: record %u is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL;
 		}
 	std::vector<uint32_t> tpl, bits; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> locs;
-	bdp_groups_t G = {nullptr, nullptr, nullptr, 0};
-	if (T) G = T->view();
 	int rc = T ? bdp_refs_fit(recs, off.data(), n, fn) : BMH_OK;
 	if (rc != BMH_OK) return rc;
-	rc = bdp_entries_host(recs, off.data(), n, tpl, E, counts + BDP_SECSUP, fn, T ? &G : nullptr, O ? &locs : nullptr, bc, bc ? &Bw : nullptr);
+	rc = bdp_entries_host(recs, off.data(), n, tpl, E, counts + BDP_SECSUP, fn, P, O ? &locs : nullptr, bc ? &Bw : nullptr);
 	if (rc != BMH_OK) return rc;
 	counts[BDP_TEMPLATES] = E.size();
-	if (bc && no_barcode) *no_barcode = bdp_no_barcode(Bw.data(), Bw.size());
-	bdp_decide_host(E.data(), E.size(), bits, counts, T ? T->n_lib : 0, T ? lib_counts : nullptr, bc ? Bw.data() : nullptr, grp, &Bp);
-	if (O) bdp_optical_host(E.data(), locs.data(), E.size(), *O, T ? T->n_lib : 0, grp ? Bp.data() : bc ? Bw.data() : nullptr);
-	if (T && lib_counts) bdp_lib_tally_host(recs, off.data(), n, tpl.data(), E.data(), E.size(), T->n_lib, lib_counts);
+	if (bc && P.no_barcode) *P.no_barcode = bdp_no_barcode(Bw.data(), Bw.size());
+	bdp_decide_host(E.data(), E.size(), bits, counts, P, bc ? Bw.data() : nullptr, &Bp);
+	if (O) bdp_optical_host(E.data(), locs.data(), E.size(), *O, P.n_lib(), grp ? Bp.data() : bc ? Bw.data() : nullptr);
+	if (T && P.lib_counts) bdp_lib_tally_host(recs, off.data(), n, tpl.data(), E.data(), E.size(), T->n_lib, P.lib_counts);
 	for (uint32_t i = 0; i < n; ++i) if (bits[tpl[i] >> 5] >> (tpl[i] & 31) & 1u) recs[off[i] + 19] |= 0x04;
 	return BMH_OK;
 }
 
 #ifndef BDP_STANDALONE
-static int markdup_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_table_t *T, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, const bdp_optical_t *O = nullptr,
-                        const bdp_bc_t *bc = nullptr, uint64_t *no_barcode = nullptr, const bdp_group_t *grp = nullptr)
+extern "C" void bmh_markdup_opt_default(bmh_markdup_opt_t *o)
 {
-	if (!out || !counts || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (!o) return;
+	memset(o, 0, sizeof *o);
+	o->optical_distance = -1; o->barcode_edits = -1;
+}
+
+int bdp_plan_make(bdp_plan_t &P, const bmh_markdup_opt_t *opt, bmh_markdup_counts_t *res, const char *fn)
+{
+	P = bdp_plan_t();
+	if (!res) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	for (uint64_t &c : res->counts) c = 0;
+	for (int k = 0; k < 3; ++k) res->optical[k] = res->grouped[k] = 0;
+	res->no_barcode = 0;
+	bmh_markdup_opt_t def;
+	if (!opt) { bmh_markdup_opt_default(&def); opt = &def; }
+	int rc = bdp_barcode_check(opt->barcode_mode, opt->barcode_tag, fn, &P.bc);
+	if (rc != BMH_OK) return rc;
+	if ((rc = bdp_group_check(opt->barcode_edits, opt->barcode_max_set, fn, &P.bc)) != BMH_OK) return rc;
+	const bool optical = opt->optical_distance != -1;
+	if (optical && (rc = bdp_optical_check(opt->optical_distance, opt->optical_max_set, fn)) != BMH_OK) return rc;
+	const bool groups = opt->rg_ids || opt->rg_lib || opt->n_groups;
+	if (groups && (rc = bdp_table_make(P.table, opt->rg_ids, opt->rg_lib, opt->n_groups, fn)) != BMH_OK) return rc;
+	if (optical && groups && opt->n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, opt->n_groups); return BMH_EINVAL; }
+	if (optical) P.opt = {opt->optical_distance, opt->optical_max_set ? (uint32_t)opt->optical_max_set : (uint32_t)BDP_OPT_MAX_SET, res->optical, groups ? res->lib_optical : nullptr};
+	if (P.bc.pack) P.grp = {(uint32_t)opt->barcode_edits, opt->barcode_max_set ? (uint32_t)opt->barcode_max_set : (uint32_t)BDP_BC_MAX_SET, res->grouped, groups ? res->lib_grouped : nullptr};
+	P.lib_counts = groups ? res->lib_counts : nullptr; P.no_barcode = &res->no_barcode;
+	return BMH_OK;
+}
+
+// probe: stop at the templates' locations or barcode words (bdp_probe_t)
+static int markdup_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_plan_t &P, bdp_probe_t probe, uint8_t **out, uint64_t counts[BDP_N_COUNTS])
+{
+	if (!out || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*out = nullptr;
 	std::vector<uint64_t> off;
 	int rc = bsr_walk(recs, n_bytes, -1, off, fn);
 	if (rc != BMH_OK) return rc;
-	uint8_t *o = (uint8_t *)malloc(n_bytes + 1);
+	std::vector<uint32_t> tpl; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> L; std::vector<uint64_t> Bw; uint64_t info[2] = {0, 0};
+	const uint8_t *src = recs; uint64_t nb = n_bytes;
+	if (probe != BDP_MARK) {
+		const uint32_t n = (uint32_t)(off.size() - 1);
+		for (uint32_t i = 0; i < n; ++i)
+			if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) { bmh_set_error("%s: record %u is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL; }
+		if ((rc = bdp_entries_host(recs, off.data(), n, tpl, E, info, fn, P, probe == BDP_PROBE_LOCS ? &L : nullptr, probe == BDP_PROBE_BCS ? &Bw : nullptr)) != BMH_OK) return rc;
+		counts[BDP_TEMPLATES] = E.size();
+		src = probe == BDP_PROBE_LOCS ? (const uint8_t *)L.data() : (const uint8_t *)Bw.data(); nb = (probe == BDP_PROBE_LOCS ? sizeof(bdp_loc_t) : 8) * E.size();
+	}
+	uint8_t *o = (uint8_t *)malloc(nb + 8);
 	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
-	if (n_bytes) memcpy(o, recs, n_bytes);
-	if ((rc = bdp_markdup_host(o, off, counts, fn, T, lib_counts, O, bc, no_barcode, grp)) != BMH_OK) { free(o); return rc; }
+	if (nb) memcpy(o, src, nb);
+	if (probe == BDP_MARK && (rc = bdp_markdup_host(o, off, counts, fn, P)) != BMH_OK) { free(o); return rc; }
 	*out = o;
 	return BMH_OK;
 }
 
-extern "C" int bmh_bam_markdup_host(const uint8_t *recs, uint64_t n_bytes, uint8_t **out, uint64_t counts[8])
+extern "C" int bmh_bam_markdup_host(const uint8_t *recs, uint64_t n_bytes, const bmh_markdup_opt_t *opt, uint8_t **out, bmh_markdup_counts_t *res)
 {
-	return markdup_host("bmh_bam_markdup_host", recs, n_bytes, nullptr, out, counts, nullptr);
+	const char *fn = "bmh_bam_markdup_host";
+	bdp_plan_t P;
+	if (out) *out = nullptr;
+	const int rc = bdp_plan_make(P, opt, res, fn);
+	return rc != BMH_OK ? rc : markdup_host(fn, recs, n_bytes, P, BDP_MARK, out, res->counts);
 }
 
-extern "C" int bmh_bam_markdup_groups_host(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, uint8_t **out, uint64_t counts[8],
-                                           uint64_t *lib_counts)
+int bdp_probe_plan(bdp_plan_t &P, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode, const char tag[2], int packed, const char *fn)
 {
-	const char *fn = "bmh_bam_markdup_groups_host";
-	bdp_table_t T;
-	if (out) *out = nullptr;
-	const int rc = bdp_table_make(T, rg_ids, rg_lib, n_groups, fn);
-	if (rc != BMH_OK) return rc;
-	return markdup_host(fn, recs, n_bytes, &T, out, counts, lib_counts);
-}
-
-extern "C" int bmh_bam_markdup_optical_host(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, uint8_t **out,
-                                            uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical)
-{
-	const char *fn = "bmh_bam_markdup_optical_host";
-	bdp_table_t T;
-	if (out) *out = nullptr;
-	if (!optical) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	int rc = bdp_optical_check(distance, max_set, fn);
-	if (rc != BMH_OK) return rc;
-	const bool groups = rg_ids || rg_lib || n_groups;
-	if (groups && (rc = bdp_table_make(T, rg_ids, rg_lib, n_groups, fn)) != BMH_OK) return rc;
-	if (groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
-	const bdp_optical_t O = {distance, max_set ? (uint32_t)max_set : (uint32_t)BDP_OPT_MAX_SET, optical, groups ? lib_optical : nullptr};
-	return markdup_host(fn, recs, n_bytes, groups ? &T : nullptr, out, counts, groups ? lib_counts : nullptr, &O);
+	bmh_markdup_opt_t o; bmh_markdup_counts_t res = {};
+	bmh_markdup_opt_default(&o);
+	o.rg_ids = rg_ids; o.rg_lib = rg_lib; o.n_groups = n_groups; o.barcode_mode = barcode_mode;
+	if (tag) { o.barcode_tag[0] = tag[0]; o.barcode_tag[1] = tag[0] ? tag[1] : 0; }
+	if (barcode_mode == BDP_BC_OFF) o.optical_distance = 0; else if (packed) o.barcode_edits = 0;
+	const int rc = bdp_plan_make(P, &o, &res, fn);
+	P.opt.out = P.grp.out = P.no_barcode = nullptr;               // (res ends here: a probe counts nothing)
+	return rc;
 }
 
 extern "C" int bmh_bam_dup_locations_host(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, uint8_t **locs, uint64_t *n_templates)
 {
 	const char *fn = "bmh_bam_dup_locations_host";
-	if (!locs || !n_templates || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	*locs = nullptr; *n_templates = 0;
-	bdp_table_t T;
-	const bool groups = rg_ids || rg_lib || n_groups;
-	int rc = groups ? bdp_table_make(T, rg_ids, rg_lib, n_groups, fn) : BMH_OK;
-	if (rc != BMH_OK) return rc;
-	if (groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
-	std::vector<uint64_t> off;
-	if ((rc = bsr_walk(recs, n_bytes, -1, off, fn)) != BMH_OK) return rc;
-	const uint32_t n = (uint32_t)(off.size() - 1);
-	for (uint32_t i = 0; i < n; ++i)
-		if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) { bmh_set_error("%s: record %u is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL; }
-	std::vector<uint32_t> tpl; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> L; uint64_t info[2] = {0, 0};
-	const bdp_groups_t G = T.view();
-	if ((rc = bdp_entries_host(recs, off.data(), n, tpl, E, info, fn, groups ? &G : nullptr, &L)) != BMH_OK) return rc;
-	uint8_t *o = (uint8_t *)malloc(sizeof(bdp_loc_t) * L.size() + 1);
-	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
-	if (!L.empty()) memcpy(o, L.data(), sizeof(bdp_loc_t) * L.size());
-	*locs = o; *n_templates = L.size();
+	if (locs) *locs = nullptr;
+	if (!n_templates) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	*n_templates = 0;
+	bdp_plan_t P; uint64_t counts[BDP_N_COUNTS];
+	int rc = bdp_probe_plan(P, rg_ids, rg_lib, n_groups, BDP_BC_OFF, nullptr, 0, fn);
+	if (rc != BMH_OK || (rc = markdup_host(fn, recs, n_bytes, P, BDP_PROBE_LOCS, locs, counts)) != BMH_OK) return rc;
+	*n_templates = counts[BDP_TEMPLATES];
 	return BMH_OK;
 }
 
-// edits -1: barcodes compared exactly (grouped, lib_grouped unused)
-static int markdup_barcode_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, int barcode_mode,
-                                const char tag[2], int edits, uint64_t bc_max_set, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical,
-                                uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
+extern "C" int bmh_bam_dup_barcodes_host(const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], int packed, uint64_t **words, uint64_t *n_templates)
 {
-	bdp_table_t T; bdp_bc_t bc;
-	if (out) *out = nullptr;
-	int rc = bdp_barcode_check(barcode_mode, tag, fn, &bc);
-	if (rc != BMH_OK) return rc;
-	if ((rc = bdp_group_check(edits, bc_max_set, fn, &bc)) != BMH_OK) return rc;
-	if (bc.pack && !grouped) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (bc.pack) for (int k = 0; k < BDP_GRP_N; ++k) grouped[k] = 0;
-	const bool opt = distance != -1;
-	if (opt && !optical) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (opt && (rc = bdp_optical_check(distance, max_set, fn)) != BMH_OK) return rc;
-	const bool groups = rg_ids || rg_lib || n_groups;
-	if (groups && (rc = bdp_table_make(T, rg_ids, rg_lib, n_groups, fn)) != BMH_OK) return rc;
-	if (opt && groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
-	const bdp_optical_t O = {distance, max_set ? (uint32_t)max_set : (uint32_t)BDP_OPT_MAX_SET, optical, groups ? lib_optical : nullptr};
-	const bdp_group_t grp = {(uint32_t)(edits < 0 ? 0 : edits), bc_max_set ? (uint32_t)bc_max_set : (uint32_t)BDP_BC_MAX_SET, grouped, groups ? lib_grouped : nullptr};
-	return markdup_host(fn, recs, n_bytes, groups ? &T : nullptr, out, counts, groups ? lib_counts : nullptr, opt ? &O : nullptr, &bc, no_barcode, bc.pack ? &grp : nullptr);
-}
-
-extern "C" int bmh_bam_markdup_barcode_host(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, int barcode_mode,
-                                            const char tag[2], uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode)
-{
-	return markdup_barcode_host("bmh_bam_markdup_barcode_host", recs, n_bytes, rg_ids, rg_lib, n_groups, distance, max_set, barcode_mode, tag, -1, 0, out, counts, lib_counts, optical, lib_optical,
-	                            no_barcode, nullptr, nullptr);
-}
-
-extern "C" int bmh_bam_markdup_barcode_edits_host(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
-                                                  int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3],
-                                                  uint64_t *lib_optical, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
-{
-	return markdup_barcode_host("bmh_bam_markdup_barcode_edits_host", recs, n_bytes, rg_ids, rg_lib, n_groups, distance, max_set, barcode_mode, tag, edits, barcode_max_set, out, counts, lib_counts,
-	                            optical, lib_optical, no_barcode, grouped, lib_grouped);
-}
-
-static int dup_barcodes_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], bool pack, uint64_t **words, uint64_t *n_templates);
-extern "C" int bmh_bam_dup_barcodes_host(const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], uint64_t **words, uint64_t *n_templates)
-{
-	return dup_barcodes_host("bmh_bam_dup_barcodes_host", recs, n_bytes, barcode_mode, tag, false, words, n_templates);
-}
-extern "C" int bmh_bam_dup_barcodes_packed_host(const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], uint64_t **words, uint64_t *n_templates)
-{
-	return dup_barcodes_host("bmh_bam_dup_barcodes_packed_host", recs, n_bytes, barcode_mode, tag, true, words, n_templates);
-}
-static int dup_barcodes_host(const char *fn, const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], bool pack, uint64_t **words, uint64_t *n_templates)
-{
-	if (!words || !n_templates || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	*words = nullptr; *n_templates = 0;
-	bdp_bc_t bc;
-	int rc = bdp_barcode_check(barcode_mode, tag, fn, &bc);
-	if (rc != BMH_OK) return rc;
-	if (bc.mode == BDP_BC_OFF) { bmh_set_error("%s: no barcode source (1: a tag, 2: the read name)", fn); return BMH_EINVAL; }
-	bc.pack = pack ? 1 : 0;
-	std::vector<uint64_t> off;
-	if ((rc = bsr_walk(recs, n_bytes, -1, off, fn)) != BMH_OK) return rc;
-	const uint32_t n = (uint32_t)(off.size() - 1);
-	for (uint32_t i = 0; i < n; ++i)
-		if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) { bmh_set_error("%s: record %u is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL; }
-	std::vector<uint32_t> tpl; std::vector<bdp_entry_t> E; std::vector<uint64_t> Bw; uint64_t info[2] = {0, 0};
-	if ((rc = bdp_entries_host(recs, off.data(), n, tpl, E, info, fn, nullptr, nullptr, &bc, &Bw)) != BMH_OK) return rc;
-	uint64_t *o = (uint64_t *)malloc(8 * Bw.size() + 8);
-	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
-	if (!Bw.empty()) memcpy(o, Bw.data(), 8 * Bw.size());
-	*words = o; *n_templates = Bw.size();
+	const char *fn = "bmh_bam_dup_barcodes_host";
+	if (words) *words = nullptr;
+	if (!n_templates) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	*n_templates = 0;
+	if (barcode_mode == BDP_BC_OFF) { bmh_set_error("%s: no barcode source (1: a tag, 2: the read name)", fn); return BMH_EINVAL; }
+	bdp_plan_t P; uint64_t counts[BDP_N_COUNTS];
+	int rc = bdp_probe_plan(P, nullptr, nullptr, 0, barcode_mode, tag, packed, fn);
+	if (rc != BMH_OK || (rc = markdup_host(fn, recs, n_bytes, P, BDP_PROBE_BCS, (uint8_t **)words, counts)) != BMH_OK) return rc;
+	*n_templates = counts[BDP_TEMPLATES];
 	return BMH_OK;
 }
 

@@ -632,12 +632,13 @@ int bdp_dev_set_groups(bdp_dev_t *d, const bdp_table_t *T, void *stream)
 	return BMH_OK;
 }
 
-int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, uint64_t T, void *stream, uint64_t counts[5], uint64_t n_records, uint32_t n_lib, uint64_t *lib_counts,
-                      const bdp_optical_t *O, const bdp_loc_t *locs, double *opt_ms, const uint64_t *bcs, const bdp_group_t *G)
+int bdp_decide_device(bdp_dev_t *d, const bdp_entry_t *entries, const bdp_loc_t *locs, const uint64_t *bcs, uint64_t T, void *stream, uint64_t counts[5], const bdp_plan_t &P,
+                      uint64_t n_records, double *opt_ms)
 {
 	hipStream_t st = (hipStream_t)stream;
+	uint32_t n_lib = P.n_lib(); uint64_t *lib_counts = P.lib_counts;
+	const bdp_optical_t *O = P.optical(); const bdp_group_t *G = bcs ? P.grouping() : nullptr;
 	for (int k = 0; k < 5; ++k) counts[k] = 0;
-	if (!bcs) G = nullptr;
 	const uint32_t g_lib = G && G->lib_out ? n_lib : 0;                    // (as the optical counts: per library whether or not lib_counts is asked for)
 	if (G) { for (int k = 0; k < BDP_GRP_N; ++k) G->out[k] = 0; for (uint32_t k = 0; k < BDP_GRP_N * g_lib; ++k) G->lib_out[k] = 0; }
 	const uint32_t o_lib = O && O->lib_out ? n_lib : 0;                    // (the optical counts per library do not hang on lib_counts)
@@ -852,17 +853,13 @@ int bdp_flag_device(bdp_dev_t *d, uint8_t *d_recs, const uint64_t *d_off, const 
 
 // ---------------------------------------------------------------------------------------------------------------- the stand-alone entry point
 
-// O (or NULL): count the optical duplicates too; locs_only: stop at the templates' locations -- *out takes them, counts [BDP_TEMPLATES] their number
-// bc (or NULL): compare barcodes -- *no_barcode: the templates without one; bcs_only: stop at the templates' barcode words, as locs_only
-static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_table_t *G, void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts,
-                          const bdp_optical_t *O = nullptr, bool locs_only = false, const bdp_bc_t *bc = nullptr, uint64_t *no_barcode = nullptr, bool bcs_only = false,
-                          const bdp_group_t *grp = nullptr)
+// probe: stop at the templates' locations or barcode words (bdp_probe_t)
+static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes, const bdp_plan_t &P, bdp_probe_t probe, void *stream, uint8_t **out, uint64_t counts[BDP_N_COUNTS])
 {
-	if (bc && bc->mode == BDP_BC_OFF) bc = nullptr;
-	if (!bc || !bc->pack) grp = nullptr;
-	if (no_barcode) *no_barcode = 0;
+	const bdp_table_t *G = P.groups(); const bdp_bc_t *bc = P.barcode();
+	if (P.no_barcode) *P.no_barcode = 0;
 	hipStream_t st = (hipStream_t)stream;
-	if (!out || !counts || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (!out || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*out = nullptr;
 	for (int k = 0; k < BDP_N_COUNTS; ++k) counts[k] = 0;
 	std::vector<uint64_t> off;
@@ -878,7 +875,7 @@ static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes,
 	if (n_bytes) HIPCK(hipMemcpyAsync(in.p, recs, (size_t)n_bytes, hipMemcpyHostToDevice, st));
 	HIPCK(hipMemcpyAsync(in_off.p, off.data(), 8 * off.size(), hipMemcpyHostToDevice, st));
 	const uint32_t *d_tpl; const bdp_entry_t *d_e; const uint32_t *d_info; const bdp_loc_t *d_l = nullptr; const uint64_t *d_b = nullptr;
-	const bool want_locs = O || locs_only;
+	const bool want_locs = probe == BDP_PROBE_LOCS || (probe == BDP_MARK && P.optical());
 	RCK(bdp_batch_device(&d, (const uint8_t *)in.p, (const uint64_t *)in_off.p, n, n_bytes, st, &d_tpl, &d_e, &d_info, want_locs ? &d_l : nullptr, bc, bc ? &d_b : nullptr));
 	uint32_t info[BDP_INFO_WORDS_PACK];
 	HIPCK(hipMemcpyAsync(info, d_info, 4 * bdp_info_words(bc), hipMemcpyDeviceToHost, st));
@@ -892,24 +889,18 @@ static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes,
 	if (n) HIPCK(hipMemcpyAsync(tpl.data(), d_tpl, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
 	if (T && want_locs) HIPCK(hipMemcpyAsync(L.data(), d_l, sizeof(bdp_loc_t) * (size_t)T, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
-	if (locs_only) {
-		uint8_t *o = (uint8_t *)malloc(sizeof(bdp_loc_t) * (size_t)T + 1);
+	if (probe != BDP_MARK) {
+		const size_t nb = (probe == BDP_PROBE_LOCS ? sizeof(bdp_loc_t) : 8) * (size_t)T;
+		uint8_t *o = (uint8_t *)malloc(nb + 1);
 		if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
-		if (T) memcpy(o, L.data(), sizeof(bdp_loc_t) * (size_t)T);
+		if (T) memcpy(o, probe == BDP_PROBE_LOCS ? (const void *)L.data() : (const void *)Bw.data(), nb);
 		*out = o; counts[BDP_TEMPLATES] = T;
 		return BMH_OK;
 	}
-	if (bcs_only) {
-		uint8_t *o = (uint8_t *)malloc(8 * (size_t)T + 1);
-		if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
-		if (T) memcpy(o, Bw.data(), 8 * (size_t)T);
-		*out = o; counts[BDP_TEMPLATES] = T;
-		return BMH_OK;
-	}
-	if (bc && no_barcode) *no_barcode = bdp_no_barcode(Bw.data(), T);
-	RCK(bdp_decide_device(&d, E.data(), T, st, counts, 0, G ? G->n_lib : 0, G ? lib_counts : nullptr, O, O ? L.data() : nullptr, nullptr, bc ? Bw.data() : nullptr, grp));
+	if (bc && P.no_barcode) *P.no_barcode = bdp_no_barcode(Bw.data(), T);
+	RCK(bdp_decide_device(&d, E.data(), L.data(), bc ? Bw.data() : nullptr, T, st, counts, P));
 	counts[BDP_SECSUP] = info[2]; counts[BDP_UNMAPPED] = info[3]; counts[BDP_TEMPLATES] = T;
-	if (G && lib_counts) bdp_lib_tally_host(recs, off.data(), n, tpl.data(), E.data(), T, G->n_lib, lib_counts);
+	if (G && P.lib_counts) bdp_lib_tally_host(recs, off.data(), n, tpl.data(), E.data(), T, G->n_lib, P.lib_counts);
 	RCK(bdp_flag_device(&d, (uint8_t *)in.p, (const uint64_t *)in_off.p, tpl.data(), n, n_bytes, st));
 	uint8_t *o = (uint8_t *)malloc((size_t)n_bytes + 1);
 	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
@@ -919,109 +910,38 @@ static int markdup_device(const char *fn, const uint8_t *recs, uint64_t n_bytes,
 	return BMH_OK;
 }
 
-extern "C" int bmh_bam_markdup_device(const uint8_t *recs, uint64_t n_bytes, void *stream, uint8_t **out, uint64_t counts[8])
+extern "C" int bmh_bam_markdup_device(const uint8_t *recs, uint64_t n_bytes, const bmh_markdup_opt_t *opt, void *stream, uint8_t **out, bmh_markdup_counts_t *res)
 {
-	return markdup_device("bmh_bam_markdup_device", recs, n_bytes, nullptr, stream, out, counts, nullptr);
-}
-
-extern "C" int bmh_bam_markdup_groups_device(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, void *stream, uint8_t **out,
-                                             uint64_t counts[8], uint64_t *lib_counts)
-{
-	const char *fn = "bmh_bam_markdup_groups_device";
-	bdp_table_t G;
+	const char *fn = "bmh_bam_markdup_device";
+	bdp_plan_t P;
 	if (out) *out = nullptr;
-	RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
-	return markdup_device(fn, recs, n_bytes, &G, stream, out, counts, lib_counts);
-}
-
-extern "C" int bmh_bam_markdup_optical_device(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, void *stream,
-                                              uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical)
-{
-	const char *fn = "bmh_bam_markdup_optical_device";
-	bdp_table_t G;
-	if (out) *out = nullptr;
-	if (!optical) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	RCK(bdp_optical_check(distance, max_set, fn));
-	const bool groups = rg_ids || rg_lib || n_groups;
-	if (groups) RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
-	if (groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
-	const bdp_optical_t O = {distance, max_set ? (uint32_t)max_set : (uint32_t)BDP_OPT_MAX_SET, optical, groups ? lib_optical : nullptr};
-	return markdup_device(fn, recs, n_bytes, groups ? &G : nullptr, stream, out, counts, groups ? lib_counts : nullptr, &O);
+	RCK(bdp_plan_make(P, opt, res, fn));
+	return markdup_device(fn, recs, n_bytes, P, BDP_MARK, stream, out, res->counts);
 }
 
 extern "C" int bmh_bam_dup_locations_device(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, void *stream, uint8_t **locs, uint64_t *n_templates)
 {
 	const char *fn = "bmh_bam_dup_locations_device";
-	bdp_table_t G;
 	if (locs) *locs = nullptr;
 	if (!n_templates) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*n_templates = 0;
-	const bool groups = rg_ids || rg_lib || n_groups;
-	if (groups) RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
-	if (groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
-	uint64_t counts[BDP_N_COUNTS];
-	RCK(markdup_device(fn, recs, n_bytes, groups ? &G : nullptr, stream, locs, counts, nullptr, nullptr, true));
+	bdp_plan_t P; uint64_t counts[BDP_N_COUNTS];
+	RCK(bdp_probe_plan(P, rg_ids, rg_lib, n_groups, BDP_BC_OFF, nullptr, 0, fn));
+	RCK(markdup_device(fn, recs, n_bytes, P, BDP_PROBE_LOCS, stream, locs, counts));
 	*n_templates = counts[BDP_TEMPLATES];
 	return BMH_OK;
 }
 
-// edits -1: barcodes compared exactly (grouped, lib_grouped unused)
-static int markdup_barcode_device(const char *fn, const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, int barcode_mode,
-                                  const char tag[2], int edits, uint64_t bc_max_set, void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical,
-                                  uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
+extern "C" int bmh_bam_dup_barcodes_device(const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], int packed, void *stream, uint64_t **words, uint64_t *n_templates)
 {
-	bdp_table_t G; bdp_bc_t bc;
-	if (out) *out = nullptr;
-	RCK(bdp_barcode_check(barcode_mode, tag, fn, &bc));
-	RCK(bdp_group_check(edits, bc_max_set, fn, &bc));
-	if (bc.pack && !grouped) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (bc.pack) for (int k = 0; k < BDP_GRP_N; ++k) grouped[k] = 0;
-	const bool opt = distance != -1;
-	if (opt && !optical) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (opt) RCK(bdp_optical_check(distance, max_set, fn));
-	const bool groups = rg_ids || rg_lib || n_groups;
-	if (groups) RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
-	if (opt && groups && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: a location holds a group's row in 16 bits", fn, n_groups); return BMH_EINVAL; }
-	const bdp_optical_t O = {distance, max_set ? (uint32_t)max_set : (uint32_t)BDP_OPT_MAX_SET, optical, groups ? lib_optical : nullptr};
-	const bdp_group_t grp = {(uint32_t)(edits < 0 ? 0 : edits), bc_max_set ? (uint32_t)bc_max_set : (uint32_t)BDP_BC_MAX_SET, grouped, groups ? lib_grouped : nullptr};
-	return markdup_device(fn, recs, n_bytes, groups ? &G : nullptr, stream, out, counts, groups ? lib_counts : nullptr, opt ? &O : nullptr, false, &bc, no_barcode, false, bc.pack ? &grp : nullptr);
-}
-
-extern "C" int bmh_bam_markdup_barcode_device(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set, int barcode_mode,
-                                              const char tag[2], void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode)
-{
-	return markdup_barcode_device("bmh_bam_markdup_barcode_device", recs, n_bytes, rg_ids, rg_lib, n_groups, distance, max_set, barcode_mode, tag, -1, 0, stream, out, counts, lib_counts, optical,
-	                              lib_optical, no_barcode, nullptr, nullptr);
-}
-
-extern "C" int bmh_bam_markdup_barcode_edits_device(const uint8_t *recs, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
-                                                    int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts,
-                                                    uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
-{
-	return markdup_barcode_device("bmh_bam_markdup_barcode_edits_device", recs, n_bytes, rg_ids, rg_lib, n_groups, distance, max_set, barcode_mode, tag, edits, barcode_max_set, stream, out, counts,
-	                              lib_counts, optical, lib_optical, no_barcode, grouped, lib_grouped);
-}
-
-static int dup_barcodes_device(const char *fn, const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], bool pack, void *stream, uint64_t **words, uint64_t *n_templates);
-extern "C" int bmh_bam_dup_barcodes_device(const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], void *stream, uint64_t **words, uint64_t *n_templates)
-{
-	return dup_barcodes_device("bmh_bam_dup_barcodes_device", recs, n_bytes, barcode_mode, tag, false, stream, words, n_templates);
-}
-extern "C" int bmh_bam_dup_barcodes_packed_device(const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], void *stream, uint64_t **words, uint64_t *n_templates)
-{
-	return dup_barcodes_device("bmh_bam_dup_barcodes_packed_device", recs, n_bytes, barcode_mode, tag, true, stream, words, n_templates);
-}
-static int dup_barcodes_device(const char *fn, const uint8_t *recs, uint64_t n_bytes, int barcode_mode, const char tag[2], bool pack, void *stream, uint64_t **words, uint64_t *n_templates)
-{
-	bdp_bc_t bc;
+	const char *fn = "bmh_bam_dup_barcodes_device";
 	if (words) *words = nullptr;
-	if (!words || !n_templates) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (!n_templates) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*n_templates = 0;
-	RCK(bdp_barcode_check(barcode_mode, tag, fn, &bc));
-	if (bc.mode == BDP_BC_OFF) { bmh_set_error("%s: no barcode source (1: a tag, 2: the read name)", fn); return BMH_EINVAL; }
-	bc.pack = pack ? 1 : 0;
-	uint64_t counts[BDP_N_COUNTS]; uint8_t *o = nullptr;
-	RCK(markdup_device(fn, recs, n_bytes, nullptr, stream, &o, counts, nullptr, nullptr, false, &bc, nullptr, true));
-	*words = (uint64_t *)o; *n_templates = counts[BDP_TEMPLATES];
+	if (barcode_mode == BDP_BC_OFF) { bmh_set_error("%s: no barcode source (1: a tag, 2: the read name)", fn); return BMH_EINVAL; }
+	bdp_plan_t P; uint64_t counts[BDP_N_COUNTS];
+	RCK(bdp_probe_plan(P, nullptr, nullptr, 0, barcode_mode, tag, packed, fn));
+	RCK(markdup_device(fn, recs, n_bytes, P, BDP_PROBE_BCS, stream, (uint8_t **)words, counts));
+	*n_templates = counts[BDP_TEMPLATES];
 	return BMH_OK;
 }

@@ -5,7 +5,7 @@
 #include <vector>
 #include "bmh_internal.h"
 #include "bam_sort_core.h"
-#include "bam_dup_core.h"
+#include "bam_dup.h"
 
 typedef int (*bsr_sink_t)(void *user, const char *bytes, size_t n);
 
@@ -38,6 +38,9 @@ struct bsr_index_t {
 int bsr_markdup_contigs(int n_contigs, const int32_t *contig_len, const char *const *contig_names, const char *fn);
 // format and min_shift as the entry points take them: BMH_EINVAL with a message, or BMH_OK
 int bsr_index_format_check(int format, int min_shift, const char *fn);
+// opt and res as the sorted-file entry points take them -> o: opt or its defaults, the index format checked; with o.markdup the plan P (bdp_plan_make; an optical
+// distance is refused: a stand-alone file has no optical step), its counts going to *res
+int bsr_file_opt_check(const bmh_sorted_file_opt_t *opt, bmh_markdup_counts_t *res, const char *fn, bmh_sorted_file_opt_t &o, bdp_plan_t &P);
 
 // Sorted runs kept until the end of the input: the records in host memory up to mem_bytes, beyond that in one unnamed temporary file; keys and offsets
 // (16 bytes per record) always in memory.  With duplicate marking (csrc/bam_dup_core.h) a run also keeps every record's template ordinal within its batch (tpl, 4 bytes
@@ -74,19 +77,15 @@ int bsr_sort_keys_device(bsr_dev_t *d, const uint64_t *keys, uint64_t n, void *s
 // one window of the final file.  src (host, pinned or not) [src_bytes]: the records of the window as the runs hold them; src_off / size [n] (host): record j of the
 // window in src.  The records are gathered into order, compressed (ws), indexed (ix: heads appended; lin and counts stay on the device until bsr_index_finish) and
 // the members handed to the sink
-// dup, tord [n] (host): the decided duplicates (bdp_decide_device) and every record's global template ordinal -- the flags are set between the gather and the compressor
+// dup, tord [n] (host), flag_ms (or NULL, all three): the decided duplicates (bdp_decide_device) and every record's global template ordinal -- the flags are set between the gather and the compressor
 int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64_t src_bytes, const uint64_t *src_off, const uint32_t *size, uint32_t n, int level,
-                      void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, struct bdp_dev_t *dup = nullptr, const uint32_t *tord = nullptr, double *flag_ms = nullptr);
+                      void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, struct bdp_dev_t *dup, const uint32_t *tord, double *flag_ms);
 // every run of the store -> the record members of the sorted file (to the sink, in windows of `window` records; 0: about 64 MiB of records) and its index
-// dup_counts (or NULL) [8]: mark the duplicates among the store's templates first (csrc/bam_dup_kernels.hip) and flag every window's records; the counts of bam_dup.h
-int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user,
-                     uint64_t *dup_counts = nullptr, double *dup_ms = nullptr, uint32_t n_lib = 0, uint64_t *lib_counts = nullptr, const struct bdp_optical_t *optical = nullptr, double *opt_ms = nullptr, bool barcode = false, const struct bdp_group_t *grp = nullptr);
-// barcode: the decision compares the barcode words the store keeps beside the entries; grp (or NULL): the words are packed and grouped by edits first (its counts filled)
-// optical (or NULL; needs dup_counts): the decision also counts the optical duplicates among the store's templates, by the locations the store keeps; opt_ms (or NULL)
-// += that step's milliseconds
-// n_lib, lib_counts [8 * n_lib] (or 0, NULL): the run had read groups -- the entries carry their libraries -- and the decision's five counters come per library too
-// (words 0 .. 4 of every library's eight; the others zeroed)
+// dup_counts (or NULL) [8]: mark the duplicates among the store's templates first, as P says (csrc/bam_dup_kernels.hip: the store keeps the locations and the barcode
+// words P's optical step and barcodes ask for), and flag every window's records; the counts of bam_dup.h
 // dup_ms (or NULL) [2]: += the decision's milliseconds (host clock around bdp_decide_device) and the windows' flag steps' (events around the upload of the ordinals
-// and the flag kernel)
+// and the flag kernel); opt_ms (or NULL) += the optical step's milliseconds
+int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user,
+                     uint64_t *dup_counts, const bdp_plan_t &P, double *dup_ms = nullptr, double *opt_ms = nullptr);
 int bsr_index_begin(bsr_dev_t *d, const bsr_index_t &ix, void *stream);
 int bsr_index_finish(bsr_dev_t *d, bsr_index_t &ix, void *stream);

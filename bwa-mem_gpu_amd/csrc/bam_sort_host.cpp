@@ -50,6 +50,15 @@ int bsr_index_format_check(int format, int min_shift, const char *fn)
 	return BMH_OK;                                        // (BAI: min_shift is not read, it is 14)
 }
 
+int bsr_file_opt_check(const bmh_sorted_file_opt_t *opt, bmh_markdup_counts_t *res, const char *fn, bmh_sorted_file_opt_t &o, bdp_plan_t &P)
+{
+	o = opt ? *opt : bmh_sorted_file_opt_t{1, 0, BSR_IX_BAI, BSR_LIN_SHIFT, nullptr};
+	int rc = bsr_index_format_check(o.index_format, o.min_shift, fn);
+	if (rc != BMH_OK || !o.markdup) return rc;
+	if (o.markdup->optical_distance != -1) { bmh_set_error("%s: a stand-alone sorted file has no optical step: optical_distance stays -1 (bmh_bam_markdup_* counts optical duplicates)", fn); return BMH_EINVAL; }
+	return bdp_plan_make(P, o.markdup, res, fn);
+}
+
 int bsr_markdup_contigs(int n_contigs, const int32_t *contig_len, const char *const *contig_names, const char *fn)
 {
 	for (int c = 0; c < n_contigs; ++c)
@@ -286,15 +295,14 @@ extern "C" int bmh_bam_sort_host(const uint8_t *recs, uint64_t n_bytes, uint8_t 
 
 // header members, the sorted records in windows of `window` records (0: as many as hold about 64 MiB), the end-of-file member; and the index
 static int sorted_file_host(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                            int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts,
-                            const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr, int format = BSR_IX_BAI, int min_shift = BSR_LIN_SHIFT, const bdp_bc_t *bc = nullptr,
-                            uint64_t *no_barcode = nullptr, const bdp_group_t *grp = nullptr)
+                            const bmh_sorted_file_opt_t &o, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts, const bdp_plan_t &P)
 {
+	const int level = o.level; const uint32_t window = o.window;
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
-	if (G && n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d references: with read groups a run holds at most 2^24 (the library takes the duplicate key's top byte)", fn, n_contigs); return BMH_EINVAL; }
+	if (P.groups() && n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d references: with read groups a run holds at most 2^24 (the library takes the duplicate key's top byte)", fn, n_contigs); return BMH_EINVAL; }
 	bsr_index_t ix;
-	int rc = ix.init(n_contigs, contig_len, fn, format, min_shift);
+	int rc = ix.init(n_contigs, contig_len, fn, o.index_format, o.min_shift);
 	if (rc != BMH_OK) return rc;
 	if (dup_counts && (rc = bsr_markdup_contigs(n_contigs, contig_len, contig_names, fn)) != BMH_OK) return rc;
 	std::vector<uint64_t> off, keys; std::vector<uint32_t> ord;
@@ -302,7 +310,7 @@ static int sorted_file_host(const char *fn, const char *header_text, int n_conti
 	std::vector<uint8_t> marked;                                   // duplicate marking: the flags are set before the sort (0x400 enters no key, bin or index)
 	if (dup_counts) {
 		marked.assign(recs, recs + n_bytes);
-		if ((rc = bdp_markdup_host(marked.data(), off, dup_counts, fn, G, lib_counts, nullptr, bc, no_barcode, grp)) != BMH_OK) return rc;
+		if ((rc = bdp_markdup_host(marked.data(), off, dup_counts, fn, P)) != BMH_OK) return rc;
 		recs = marked.data();
 	}
 	bsr_sort_host(recs, off, keys, ord);
@@ -344,89 +352,11 @@ static int sorted_file_host(const char *fn, const char *header_text, int n_conti
 }
 
 extern "C" int bmh_bam_sorted_file_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                        int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes)
+                                        const bmh_sorted_file_opt_t *opt, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res)
 {
-	return sorted_file_host("bmh_bam_sorted_file_host", header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, bai, bai_bytes, nullptr);
-}
-
-extern "C" int bmh_bam_sorted_file_markdup_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                                int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8])
-{
-	const char *fn = "bmh_bam_sorted_file_markdup_host";
-	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, bai, bai_bytes, counts);
-}
-
-extern "C" int bmh_bam_sorted_file_markdup_groups_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                                       int level, uint32_t window, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, uint8_t **bam, uint64_t *bam_bytes,
-                                                       uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8], uint64_t *lib_counts)
-{
-	const char *fn = "bmh_bam_sorted_file_markdup_groups_host";
-	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	bdp_table_t G;
-	const int rc = bdp_table_make(G, rg_ids, rg_lib, n_groups, fn);
+	const char *fn = "bmh_bam_sorted_file_host";
+	bmh_sorted_file_opt_t o; bdp_plan_t P;
+	const int rc = bsr_file_opt_check(opt, res, fn, o, P);
 	if (rc != BMH_OK) return rc;
-	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, bai, bai_bytes, counts, &G, lib_counts);
-}
-
-extern "C" int bmh_bam_sorted_file_ex_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                           int level, uint32_t window, int index_format, int min_shift, int markdup, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
-                                           uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts)
-{
-	const char *fn = "bmh_bam_sorted_file_ex_host";
-	if (markdup && !counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (!markdup && (rg_ids || rg_lib || n_groups)) { bmh_set_error("%s: read groups decide which templates may be duplicates of each other: they need markdup", fn); return BMH_EINVAL; }
-	int rc = bsr_index_format_check(index_format, min_shift, fn);
-	if (rc != BMH_OK) return rc;
-	bdp_table_t G;
-	const bool groups = rg_ids || rg_lib || n_groups;
-	if (groups && (rc = bdp_table_make(G, rg_ids, rg_lib, n_groups, fn)) != BMH_OK) return rc;
-	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, index, index_bytes, markdup ? counts : nullptr,
-	                        groups ? &G : nullptr, groups ? lib_counts : nullptr, index_format, min_shift);
-}
-
-// edits -1: barcodes compared exactly (grouped, lib_grouped unused)
-static int sorted_file_barcode_host(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                    int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
-                                    const char tag[2], int edits, uint64_t bc_max_set, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8],
-                                    uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped);
-
-extern "C" int bmh_bam_sorted_file_barcode_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                                int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
-                                                const char tag[2], uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts,
-                                                uint64_t *no_barcode)
-{
-	return sorted_file_barcode_host("bmh_bam_sorted_file_barcode_host", header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, index_format, min_shift, rg_ids, rg_lib,
-	                                n_groups, barcode_mode, tag, -1, 0, bam, bam_bytes, index, index_bytes, counts, lib_counts, no_barcode, nullptr, nullptr);
-}
-
-extern "C" int bmh_bam_sorted_file_barcode_edits_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                                      int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
-                                                      int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index,
-                                                      uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
-{
-	return sorted_file_barcode_host("bmh_bam_sorted_file_barcode_edits_host", header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, index_format, min_shift, rg_ids,
-	                                rg_lib, n_groups, barcode_mode, tag, edits, barcode_max_set, bam, bam_bytes, index, index_bytes, counts, lib_counts, no_barcode, grouped, lib_grouped);
-}
-
-static int sorted_file_barcode_host(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                    int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
-                                    const char tag[2], int edits, uint64_t bc_max_set, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8],
-                                    uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
-{
-	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (no_barcode) *no_barcode = 0;
-	int rc = bsr_index_format_check(index_format, min_shift, fn);
-	if (rc != BMH_OK) return rc;
-	bdp_bc_t bc;
-	if ((rc = bdp_barcode_check(barcode_mode, tag, fn, &bc)) != BMH_OK) return rc;
-	if ((rc = bdp_group_check(edits, bc_max_set, fn, &bc)) != BMH_OK) return rc;
-	if (bc.pack && !grouped) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	bdp_table_t G;
-	const bool groups = rg_ids || rg_lib || n_groups;
-	if (groups && (rc = bdp_table_make(G, rg_ids, rg_lib, n_groups, fn)) != BMH_OK) return rc;
-	const bdp_group_t grp = {(uint32_t)(edits < 0 ? 0 : edits), bc_max_set ? (uint32_t)bc_max_set : (uint32_t)BDP_BC_MAX_SET, grouped, groups ? lib_grouped : nullptr};
-	if (bc.pack) for (int k = 0; k < BDP_GRP_N; ++k) grouped[k] = 0;
-	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, bam, bam_bytes, index, index_bytes, counts, groups ? &G : nullptr,
-	                        groups ? lib_counts : nullptr, index_format, min_shift, &bc, no_barcode, bc.pack ? &grp : nullptr);
+	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P);
 }

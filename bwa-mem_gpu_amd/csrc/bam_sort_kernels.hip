@@ -303,9 +303,10 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 }
 
 // every run of the store -> the sorted file's record members (to the sink) and its index
-int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, uint64_t *dup_counts, double *dup_ms,
-                     uint32_t n_lib, uint64_t *lib_counts, const bdp_optical_t *optical, double *opt_ms, bool barcode, const bdp_group_t *grp)
+int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, uint64_t *dup_counts,
+                     const bdp_plan_t &P, double *dup_ms, double *opt_ms)
 {
+	const bdp_optical_t *optical = P.optical(); const bool barcode = P.barcode() != nullptr;
 	uint64_t n = 0, bytes = 0;
 	std::vector<uint64_t> first;
 	for (const bsr_run_t &r : S.runs) { first.push_back(n); n += r.n; bytes += r.bytes; }
@@ -320,7 +321,7 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint3
 		const double t0 = bsr_now_ms();
 		if (optical && S.locs.size() != S.entries.size()) { bmh_set_error("sorted BAM: internal error: %zu locations for %zu templates", S.locs.size(), S.entries.size()); return BMH_EINVAL; }
 		if (barcode && S.bcs.size() != S.entries.size()) { bmh_set_error("sorted BAM: internal error: %zu barcode words for %zu templates", S.bcs.size(), S.entries.size()); return BMH_EINVAL; }
-		RCK(bdp_decide_device(dup.p, S.entries.data(), S.entries.size(), stream, dup_counts, n, n_lib, lib_counts, optical, optical ? S.locs.data() : nullptr, &o_ms, barcode ? S.bcs.data() : nullptr, barcode ? grp : nullptr));
+		RCK(bdp_decide_device(dup.p, S.entries.data(), S.locs.data(), barcode ? S.bcs.data() : nullptr, S.entries.size(), stream, dup_counts, P, n, &o_ms));
 		dup_counts[BDP_SECSUP] = S.dup_info[0]; dup_counts[BDP_UNMAPPED] = S.dup_info[1]; dup_counts[BDP_TEMPLATES] = S.entries.size();
 		decide_ms = bsr_now_ms() - t0;
 	}
@@ -377,8 +378,9 @@ namespace {
 // what duplicate marking keeps of a stream: its records' template ordinals in sorted order, the templates' entries, the line counts
 struct dup_host_t { std::vector<uint32_t> tpl; std::vector<bdp_entry_t> entries; uint64_t secsup = 0, unmapped = 0; std::vector<uint64_t> bcs; };
 int to_store(bsr_dev_t *d, const uint8_t *recs, uint64_t n_bytes, const std::vector<uint64_t> &off, hipStream_t st, std::vector<uint8_t> &sorted, std::vector<uint64_t> &keys, std::vector<uint64_t> &soff,
-             dup_host_t *dh = nullptr, const char *fn = "", const bdp_table_t *G = nullptr, const bdp_bc_t *bc = nullptr)
+             dup_host_t *dh, const char *fn, const bdp_plan_t &P)
 {
+	const bdp_table_t *G = P.groups(); const bdp_bc_t *bc = P.barcode();
 	const uint32_t n = (uint32_t)(off.size() - 1);
 	RCK(d->in.need((size_t)n_bytes + 16)); RCK(d->in_off.need(8 * off.size()));
 	HIPCK(hipMemcpyAsync(d->in.p, recs, (size_t)n_bytes, hipMemcpyHostToDevice, st));
@@ -424,7 +426,7 @@ extern "C" int bmh_bam_sort_device(const uint8_t *recs, uint64_t n_bytes, void *
 	std::vector<uint64_t> off, keys, soff; std::vector<uint8_t> sorted;
 	RCK(bsr_walk(recs, n_bytes, -1, off, fn));
 	bsr_dev_t d;
-	RCK(to_store(&d, recs, n_bytes, off, (hipStream_t)stream, sorted, keys, soff));
+	RCK(to_store(&d, recs, n_bytes, off, (hipStream_t)stream, sorted, keys, soff, nullptr, fn, bdp_plan_t()));
 	uint8_t *o = (uint8_t *)malloc((size_t)n_bytes + 1);
 	if (!o) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
 	memcpy(o, sorted.data(), (size_t)n_bytes);
@@ -433,19 +435,16 @@ extern "C" int bmh_bam_sort_device(const uint8_t *recs, uint64_t n_bytes, void *
 }
 
 static int sorted_file_device(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                              int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts,
-                              const bdp_table_t *G = nullptr, uint64_t *lib_counts = nullptr, int format = BSR_IX_BAI, int min_shift = BSR_LIN_SHIFT, const bdp_bc_t *bc = nullptr,
-                              uint64_t *no_barcode = nullptr, const bdp_group_t *grp = nullptr)
+                              const bmh_sorted_file_opt_t &o, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts, const bdp_plan_t &P)
 {
-	if (bc && (bc->mode == BDP_BC_OFF || !dup_counts)) bc = nullptr;
-	if (!bc || !bc->pack) grp = nullptr;
-	if (no_barcode) *no_barcode = 0;
+	const int level = o.level; const uint32_t window = o.window;
+	const bdp_table_t *G = P.groups();
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
 	if (G && n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d references: with read groups a run holds at most 2^24 (the library takes the duplicate key's top byte)", fn, n_contigs); return BMH_EINVAL; }
 	if (level != 0 && level != 1) { bmh_set_error("%s: level %d (0 or 1)", fn, level); return BMH_EINVAL; }
 	bsr_index_t ix;
-	RCK(ix.init(n_contigs, contig_len, fn, format, min_shift));
+	RCK(ix.init(n_contigs, contig_len, fn, o.index_format, o.min_shift));
 	if (dup_counts) RCK(bsr_markdup_contigs(n_contigs, contig_len, contig_names, fn));
 	std::vector<uint64_t> off, keys, soff; std::vector<uint8_t> sorted;
 	RCK(bsr_walk(recs, n_bytes, n_contigs, off, fn));
@@ -456,9 +455,9 @@ static int sorted_file_device(const char *fn, const char *header_text, int n_con
 			if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) { bmh_set_error("%s: record %zu is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL; }
 	dup_host_t dh;
 	if (off.size() > 1) {
-		RCK(to_store(&d, recs, n_bytes, off, (hipStream_t)stream, sorted, keys, soff, dup_counts ? &dh : nullptr, fn, G, bc));
+		RCK(to_store(&d, recs, n_bytes, off, (hipStream_t)stream, sorted, keys, soff, dup_counts ? &dh : nullptr, fn, P));
 		bsr_dup_t bd = {dh.tpl.data(), dh.entries.data(), (uint32_t)dh.entries.size(), dh.secsup, dh.unmapped};
-		if (bc) { bd.bcs = dh.bcs.data(); if (no_barcode) *no_barcode = bdp_no_barcode(dh.bcs.data(), dh.bcs.size()); }
+		if (P.barcode()) { bd.bcs = dh.bcs.data(); if (P.no_barcode) *P.no_barcode = bdp_no_barcode(dh.bcs.data(), dh.bcs.size()); }
 		RCK(S.append(sorted.data(), n_bytes, keys.data(), soff.data(), off.size() - 1, dup_counts ? &bd : nullptr));
 	}
 	std::string file;
@@ -470,11 +469,11 @@ static int sorted_file_device(const char *fn, const char *header_text, int n_con
 	file.append((const char *)hm, hmb); bmh_free(hm);
 	const uint64_t base = file.size();
 	bmh_bam_ws_t *ws = bmh_bam_ws_create();
-	rc = bsr_merge_device(&d, ws, S, window, level, stream, ix, sink_string, &file, dup_counts, nullptr, G ? G->n_lib : 0, G ? lib_counts : nullptr, nullptr, nullptr, bc != nullptr, grp);
+	rc = bsr_merge_device(&d, ws, S, window, level, stream, ix, sink_string, &file, dup_counts, P);
 	bmh_bam_ws_free(ws);
 	if (rc != BMH_OK) return rc;
-	if (G && lib_counts && off.size() > 1)
-		bdp_lib_tally_host(sorted.data(), soff.data(), (uint32_t)(off.size() - 1), dh.tpl.data(), dh.entries.data(), dh.entries.size(), G->n_lib, lib_counts);
+	if (G && P.lib_counts && off.size() > 1)
+		bdp_lib_tally_host(sorted.data(), soff.data(), (uint32_t)(off.size() - 1), dh.tpl.data(), dh.entries.data(), dh.entries.size(), G->n_lib, P.lib_counts);
 	file.append((const char *)bmh_bgzf_eof, 28);
 	std::string ib;
 	RCK(ix.bytes(base, ib));
@@ -486,86 +485,10 @@ static int sorted_file_device(const char *fn, const char *header_text, int n_con
 }
 
 extern "C" int bmh_bam_sorted_file_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                          int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes)
+                                          const bmh_sorted_file_opt_t *opt, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res)
 {
-	return sorted_file_device("bmh_bam_sorted_file_device", header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, bai, bai_bytes, nullptr);
-}
-
-extern "C" int bmh_bam_sorted_file_markdup_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                                  int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8])
-{
-	const char *fn = "bmh_bam_sorted_file_markdup_device";
-	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, bai, bai_bytes, counts);
-}
-
-extern "C" int bmh_bam_sorted_file_markdup_groups_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                                         int level, uint32_t window, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, void *stream, uint8_t **bam,
-                                                         uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8], uint64_t *lib_counts)
-{
-	const char *fn = "bmh_bam_sorted_file_markdup_groups_device";
-	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	bdp_table_t G;
-	RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
-	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, bai, bai_bytes, counts, &G, lib_counts);
-}
-
-extern "C" int bmh_bam_sorted_file_ex_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                             int level, uint32_t window, int index_format, int min_shift, int markdup, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
-                                             void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts)
-{
-	const char *fn = "bmh_bam_sorted_file_ex_device";
-	if (markdup && !counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (!markdup && (rg_ids || rg_lib || n_groups)) { bmh_set_error("%s: read groups decide which templates may be duplicates of each other: they need markdup", fn); return BMH_EINVAL; }
-	RCK(bsr_index_format_check(index_format, min_shift, fn));
-	bdp_table_t G;
-	const bool groups = rg_ids || rg_lib || n_groups;
-	if (groups) RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
-	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, index, index_bytes, markdup ? counts : nullptr,
-	                          groups ? &G : nullptr, groups ? lib_counts : nullptr, index_format, min_shift);
-}
-
-// edits -1: barcodes compared exactly (grouped, lib_grouped unused)
-static int sorted_file_barcode_device(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                      int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
-                                      const char tag[2], int edits, uint64_t bc_max_set, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8],
-                                      uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped);
-
-extern "C" int bmh_bam_sorted_file_barcode_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                                  int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
-                                                  const char tag[2], void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8],
-                                                  uint64_t *lib_counts, uint64_t *no_barcode)
-{
-	return sorted_file_barcode_device("bmh_bam_sorted_file_barcode_device", header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, index_format, min_shift, rg_ids, rg_lib,
-	                                  n_groups, barcode_mode, tag, -1, 0, stream, bam, bam_bytes, index, index_bytes, counts, lib_counts, no_barcode, nullptr, nullptr);
-}
-
-extern "C" int bmh_bam_sorted_file_barcode_edits_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                                        int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
-                                                        int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index,
-                                                        uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
-{
-	return sorted_file_barcode_device("bmh_bam_sorted_file_barcode_edits_device", header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, index_format, min_shift, rg_ids,
-	                                  rg_lib, n_groups, barcode_mode, tag, edits, barcode_max_set, stream, bam, bam_bytes, index, index_bytes, counts, lib_counts, no_barcode, grouped, lib_grouped);
-}
-
-static int sorted_file_barcode_device(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                      int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int barcode_mode,
-                                      const char tag[2], int edits, uint64_t bc_max_set, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8],
-                                      uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped)
-{
-	if (!counts) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (no_barcode) *no_barcode = 0;
-	RCK(bsr_index_format_check(index_format, min_shift, fn));
-	bdp_bc_t bc;
-	RCK(bdp_barcode_check(barcode_mode, tag, fn, &bc));
-	RCK(bdp_group_check(edits, bc_max_set, fn, &bc));
-	if (bc.pack && !grouped) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (bc.pack) for (int k = 0; k < BDP_GRP_N; ++k) grouped[k] = 0;
-	bdp_table_t G;
-	const bool groups = rg_ids || rg_lib || n_groups;
-	if (groups) RCK(bdp_table_make(G, rg_ids, rg_lib, n_groups, fn));
-	const bdp_group_t grp = {(uint32_t)(edits < 0 ? 0 : edits), bc_max_set ? (uint32_t)bc_max_set : (uint32_t)BDP_BC_MAX_SET, grouped, groups ? lib_grouped : nullptr};
-	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, level, window, stream, bam, bam_bytes, index, index_bytes, counts, groups ? &G : nullptr,
-	                          groups ? lib_counts : nullptr, index_format, min_shift, &bc, no_barcode, bc.pack ? &grp : nullptr);
+	const char *fn = "bmh_bam_sorted_file_device";
+	bmh_sorted_file_opt_t o; bdp_plan_t P;
+	RCK(bsr_file_opt_check(opt, res, fn, o, P));
+	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, stream, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P);
 }

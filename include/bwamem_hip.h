@@ -882,10 +882,16 @@ int bmh_aligner_set_output(bmh_aligner_t *a, int format, int level);
 #define BMH_OUT_BAM_SORTED 2
 int bmh_bam_sort_device(const uint8_t *records, uint64_t n_bytes, void *stream, uint8_t **out);
 int bmh_bam_sort_host(const uint8_t *records, uint64_t n_bytes, uint8_t **out);
+typedef struct bmh_markdup_opt bmh_markdup_opt_t;                  /* (below, with duplicate marking) */
+typedef struct bmh_markdup_counts bmh_markdup_counts_t;
+/* what a sorted file is made under: the BGZF level (0 or 1), the window, the index (BMH_INDEX_*; min_shift is read for CSI only) and, to mark the duplicates of a
+ * stream given in the writer's order, the marking options (NULL: no marking; their optical step is not part of a stand-alone file: optical_distance stays -1,
+ * else BMH_EINVAL).  opt NULL: level 1, window 0, a BAI index, no marking.  res: the marking's counts (NULL without marking). */
+typedef struct { int32_t level; uint32_t window; int32_t index_format, min_shift; const bmh_markdup_opt_t *markdup; } bmh_sorted_file_opt_t;
 int bmh_bam_sorted_file_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                               int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes);
+                               const bmh_sorted_file_opt_t *opt, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res);
 int bmh_bam_sorted_file_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                             int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes);
+                             const bmh_sorted_file_opt_t *opt, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res);
 int bmh_aligner_set_sort(bmh_aligner_t *a, uint64_t mem_bytes, const char *tmp_dir, uint32_t window_records);
 int bmh_aligner_sort_index(bmh_aligner_t *a, uint64_t base_offset, uint8_t **bai, uint64_t *bai_bytes);
 
@@ -904,36 +910,42 @@ int bmh_aligner_sort_index(bmh_aligner_t *a, uint64_t base_offset, uint8_t **bai
  * contig lengths against it as every run's begin does (BAI: below 2^29; CSI: at most 2^31 - 1, and an index of fewer than 2^28 windows).  bmh_aligner_sort_index
  * gives the bytes of the format the last sorted run was made under.  For BMH_INDEX_BAI min_shift is not read.
  * Duplicate marking holds an unclipped end in 31 bits around 2^30: with it on, a contig beyond 2^30 - 2^24 bases is refused by name before anything is written.
- * bmh_bam_sorted_file_ex_device / _host: bmh_bam_sorted_file_* with everything its variants take -- the index format and min_shift; markdup (0: counts may be NULL);
- * read groups (rg_ids NULL and n_groups 0: none; they need markdup) -- and the index of that format in *index. */
+ * bmh_bam_sorted_file_device / _host with index_format BMH_INDEX_CSI give the index of that format in *index. */
 #define BMH_INDEX_BAI 0
 #define BMH_INDEX_CSI 1
 int bmh_aligner_set_index_format(bmh_aligner_t *a, int index_format, int min_shift);
-int bmh_bam_sorted_file_ex_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                                  int level, uint32_t window, int index_format, int min_shift, int markdup, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
-                                  void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts);
-int bmh_bam_sorted_file_ex_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                                int level, uint32_t window, int index_format, int min_shift, int markdup, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
-                                uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts);
 
 /* ---- Duplicate marking in sorted BAM (csrc/bam_dup_core.h, csrc/bam_dup_kernels.hip, csrc/bam_dup_host.cpp).
  * Picard MarkDuplicates' rules on templates (a single read or a read pair, its records next to each other in the writer's order): the unclipped 5' ends and
  * strands of the primary lines are the key, the sum of the base qualities >= 15 the score, ties go to the template that came first in the input; a fragment is
  * a duplicate wherever a pair has an end.  Every record of a duplicate template gets flag 0x400.  Nothing is removed; optical duplicates are counted on request (below).  One library unless
- * read groups are given (the _groups entry points below).
+ * read groups are given (below).
  * counts [8]: pairs examined, fragments examined, duplicate pairs, duplicate fragments, records flagged, secondary or supplementary records, unmapped records,
  * templates.
+ * One options record and one counts record serve every stand-alone marking call; the sections below say what each field means.  bmh_markdup_opt_default: no read
+ * groups, no optical step (-1, 0), no barcodes (0, -1, 0).  The counts record is zeroed by every call; lib_counts [8 * n_lib], lib_optical [3 * n_lib] and
+ * lib_grouped [3 * n_lib] are the caller's arrays (or NULL), filled with read groups only.
  * bmh_bam_markdup_device / _host: a record stream in the writer's order (whole records; the first begins a template; paired templates hold both primary lines --
- * else BMH_EINVAL with a message) -> the same records with the flags set (malloc'd; bmh_free).
- * bmh_bam_sorted_file_markdup_device / _host: bmh_bam_sorted_file_* with the duplicates of the stream (given in the writer's order) marked.
+ * else BMH_EINVAL with a message) -> the same records with the flags set (malloc'd; bmh_free).  opt NULL: plain marking; res is required.
+ * bmh_bam_sorted_file_device / _host with opt->markdup: the duplicates of the stream (given in the writer's order) marked.
  * bmh_aligner_set_markdup: the runs that follow mark duplicates; refused (the aligner stays as it was) unless the output format is BMH_OUT_BAM_SORTED, and switched
  * off by every bmh_aligner_set_output of another format.  bmh_aligner_markdup_counts: the counts of the last marked run. */
-int bmh_bam_markdup_device(const uint8_t *records, uint64_t n_bytes, void *stream, uint8_t **out, uint64_t counts[8]);
-int bmh_bam_markdup_host(const uint8_t *records, uint64_t n_bytes, uint8_t **out, uint64_t counts[8]);
-int bmh_bam_sorted_file_markdup_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                                       int level, uint32_t window, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8]);
-int bmh_bam_sorted_file_markdup_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                                     int level, uint32_t window, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8]);
+struct bmh_markdup_opt {
+	const char *const *rg_ids; const int32_t *rg_lib; int32_t n_groups;   /* all NULL / 0: no read groups */
+	int64_t  optical_distance;      /* -1: no optical step */
+	uint64_t optical_max_set;       /* 0: the default (300 000) */
+	int32_t  barcode_mode;          /* 0 off, 1 tag, 2 read name */
+	char     barcode_tag[2];
+	int32_t  barcode_edits;         /* -1: barcodes compared exactly */
+	uint64_t barcode_max_set;       /* 0: the default (65 536) */
+};
+void bmh_markdup_opt_default(bmh_markdup_opt_t *o);
+struct bmh_markdup_counts {
+	uint64_t counts[8], optical[3], grouped[3], no_barcode;
+	uint64_t *lib_counts, *lib_optical, *lib_grouped;   /* caller's arrays [8 | 3 | 3 per library], or NULL */
+};
+int bmh_bam_markdup_device(const uint8_t *records, uint64_t n_bytes, const bmh_markdup_opt_t *opt, void *stream, uint8_t **out, bmh_markdup_counts_t *res);
+int bmh_bam_markdup_host(const uint8_t *records, uint64_t n_bytes, const bmh_markdup_opt_t *opt, uint8_t **out, bmh_markdup_counts_t *res);
 int bmh_aligner_set_markdup(bmh_aligner_t *a, int on);
 int bmh_aligner_set_bam_pairs(bmh_aligner_t *a, uint64_t batch_bases, int n_lanes);        /* (described with bmh_bam_reads_device above) */
 /* Keep the input's read groups (off by default; with it off nothing about a run changes).  bmh_aligner_run_files then takes one BAM -- a regular file or a pipe --
@@ -958,18 +970,8 @@ int bmh_aligner_markdup_times(bmh_aligner_t *a, double out[3]);
  * pair's end, and the best fragment stays, within one library only.  The library takes the top byte of the duplicate key, above the refID: more than 255 libraries,
  * a refID of 2^24 or more, an empty table, an empty ID and two rows with one ID are refused (BMH_EINVAL) before anything is allocated; so is a template whose first
  * record has no RG:Z tag or names a group the table does not hold, by the record's index.  counts [8]: the totals, as without groups.  lib_counts (or NULL)
- * [8 * n_lib], n_lib = 1 + the largest index: the same eight per library.  Without groups (the entry points above) no tag is read.
+ * [8 * n_lib], n_lib = 1 + the largest index: the same eight per library.  Without groups no tag is read.
  * bmh_aligner_markdup_library_counts: library `lib`'s eight of the last marked run over read groups. */
-int bmh_bam_markdup_groups_device(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, void *stream, uint8_t **out,
-                                  uint64_t counts[8], uint64_t *lib_counts);
-int bmh_bam_markdup_groups_host(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, uint8_t **out, uint64_t counts[8],
-                                uint64_t *lib_counts);
-int bmh_bam_sorted_file_markdup_groups_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records,
-                                              uint64_t n_bytes, int level, uint32_t window, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, void *stream,
-                                              uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8], uint64_t *lib_counts);
-int bmh_bam_sorted_file_markdup_groups_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records,
-                                            uint64_t n_bytes, int level, uint32_t window, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
-                                            uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t counts[8], uint64_t *lib_counts);
 int bmh_aligner_markdup_library_counts(bmh_aligner_t *a, int lib, uint64_t out[8]);
 
 /* ---- Optical duplicates and the library-size estimate (csrc/bam_dup_core.h).  Counts only: the records, the flags, the file and its index are
@@ -980,8 +982,7 @@ int bmh_aligner_markdup_library_counts(bmh_aligner_t *a, int lib, uint64_t out[8
  * the connected components are the clusters and a cluster of k pairs counts k - 1 optical duplicates.  Sets of one pair and sets of more than max_set pairs
  * (0: 300 000) are not examined.  optical [3]: optical duplicate pairs, examined pairs with a location, sets skipped for their size; lib_optical (or NULL)
  * [3 * n_lib]: the same per library.  distance: 0 .. 2^31 - 1.
- * bmh_bam_markdup_optical_device / _host: bmh_bam_markdup_groups_* (rg_ids NULL, rg_lib NULL, n_groups 0: bmh_bam_markdup_*, no library) with the optical step; at
- * most 65536 read groups.
+ * With an optical distance a run holds at most 65536 read groups.
  * bmh_bam_dup_locations_device / _host: a record stream -> *locs: one 16-byte location per template {int32 x, y; uint32 tile; uint16 group row; uint16 flags --
  * 1: located, 2: role} (malloc'd; bmh_free), *n_templates of them.
  * bmh_bam_name_location: the parser on the host -> 1 and out = {tile, x, y}, or 0: no location.
@@ -989,10 +990,6 @@ int bmh_aligner_markdup_library_counts(bmh_aligner_t *a, int lib, uint64_t out[8
  * bmh_aligner_set_markdup_optical: the marked runs that follow count optical duplicates within `distance` (-1: off, the default); refused unless marking is on,
  * and switched off wherever marking is.  bmh_aligner_markdup_optical_counts: the three counts of the last such run, of library `lib` or (-1) in total.
  * bmh_aligner_markdup_optical_ms: the milliseconds of the decision that the optical step took (the locations' upload included). */
-int bmh_bam_markdup_optical_device(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
-                                   void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical);
-int bmh_bam_markdup_optical_host(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
-                                 uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical);
 int bmh_bam_dup_locations_device(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, void *stream, uint8_t **locs,
                                  uint64_t *n_templates);
 int bmh_bam_dup_locations_host(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, uint8_t **locs, uint64_t *n_templates);
@@ -1007,33 +1004,18 @@ int bmh_aligner_markdup_optical_ms(bmh_aligner_t *a, double *out);
  * characters, [A-Za-z][A-Za-z0-9]; not RG, nor one the aligner writes itself: NM MD AS XS SA XA pa) of type Z, verbatim -- no case folding, no splitting at '-'.
  * barcode_mode 2 (the name): the bytes behind the last ':' of the read name (bcl-convert's ...:tile:x:y:UMI); the optical step's parser is then given the name
  * without that field and its ':'.  0: none (tag ignored).  An absent tag, an empty value, a name without ':' and a name that ends in ':' mean no barcode: such
- * templates are comparable with each other and with no barcoded one; *no_barcode (or NULL) counts them.  The value becomes a 64-bit word -- FNV-1a over its
+ * templates are comparable with each other and with no barcoded one; no_barcode counts them.  The value becomes a 64-bit word -- FNV-1a over its
  * bytes, 0 kept for no barcode (a value that hashes to 0 takes 1) -- and words are compared: pairs by (lo, hi, word), fragments by (end, word), a fragment a
  * duplicate through a pair's end only if that pair has its word, an optical set the pairs of one (lo, hi, word).  Refused with BMH_EINVAL and the record's index: a
  * first record whose tag has a type other than Z, or whose tags cannot be walked.
- * bmh_bam_markdup_barcode_device / _host: bmh_bam_markdup_optical_* with the barcode's source; distance -1 runs without the optical step (optical may be NULL).
- * bmh_bam_sorted_file_barcode_device / _host: bmh_bam_sorted_file_ex_* with marking on and the barcode's source.
- * bmh_bam_dup_barcodes_device / _host: a record stream -> *words: one uint64 per template (malloc'd; bmh_free), *n_templates of them; barcode_mode 1 or 2.
+ * bmh_bam_dup_barcodes_device / _host: a record stream -> *words: one uint64 per template (malloc'd; bmh_free), *n_templates of them; barcode_mode 1 or 2; packed
+ * != 0: the packed words that grouping by edits compares (below).
  * bmh_barcode_word: the word of a value of n bytes.
  * bmh_aligner_set_markdup_barcode: the marked runs that follow compare barcodes (mode as above; 0: off, the default); refused unless marking is on, and switched
  * off wherever marking is.  A tag reaches the records of an aligner run only as a read's comment (-C).
  * bmh_aligner_markdup_barcode_counts: out [0]: the templates without a barcode in the last such run. */
-int bmh_bam_markdup_barcode_device(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
-                                   int barcode_mode, const char tag[2], void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3],
-                                   uint64_t *lib_optical, uint64_t *no_barcode);
-int bmh_bam_markdup_barcode_host(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
-                                 int barcode_mode, const char tag[2], uint8_t **out, uint64_t counts[8], uint64_t *lib_counts, uint64_t optical[3], uint64_t *lib_optical,
-                                 uint64_t *no_barcode);
-int bmh_bam_sorted_file_barcode_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                                       int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
-                                       int barcode_mode, const char tag[2], void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes,
-                                       uint64_t counts[8], uint64_t *lib_counts, uint64_t *no_barcode);
-int bmh_bam_sorted_file_barcode_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                                     int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
-                                     int barcode_mode, const char tag[2], uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, uint64_t counts[8],
-                                     uint64_t *lib_counts, uint64_t *no_barcode);
-int bmh_bam_dup_barcodes_device(const uint8_t *records, uint64_t n_bytes, int barcode_mode, const char tag[2], void *stream, uint64_t **words, uint64_t *n_templates);
-int bmh_bam_dup_barcodes_host(const uint8_t *records, uint64_t n_bytes, int barcode_mode, const char tag[2], uint64_t **words, uint64_t *n_templates);
+int bmh_bam_dup_barcodes_device(const uint8_t *records, uint64_t n_bytes, int barcode_mode, const char tag[2], int packed, void *stream, uint64_t **words, uint64_t *n_templates);
+int bmh_bam_dup_barcodes_host(const uint8_t *records, uint64_t n_bytes, int barcode_mode, const char tag[2], int packed, uint64_t **words, uint64_t *n_templates);
 uint64_t bmh_barcode_word(const uint8_t *value, uint64_t n);
 int bmh_aligner_set_markdup_barcode(bmh_aligner_t *a, int mode, const char *tag);
 int bmh_aligner_markdup_barcode_counts(bmh_aligner_t *a, uint64_t out[1]);
@@ -1046,31 +1028,13 @@ int bmh_aligner_markdup_barcode_counts(bmh_aligner_t *a, uint64_t out[1]);
  * transitive -- and every pair takes its component's smallest word; the pair rule then runs on (lo, hi, that word), and an optical set is the pairs of one such
  * key.  Independently, within one (library, end word) the distinct words of the fragment pass's items -- the fragments and both ends of every pair -- are
  * clustered the same way before the fragment rule.  A key with more than barcode_max_set distinct words (0: 65 536) is not clustered: its words stay exact.  With
- * N = 0 flags and counts are those of the exact comparison.  grouped [3] (required), lib_grouped [3 * libraries] (or NULL; filled with read groups): the distinct
+ * N = 0 flags and counts are those of the exact comparison.  grouped [3], lib_grouped [3 * libraries] (or NULL; filled with read groups): the distinct
  * (library, lo, hi, word) over barcoded pairs, their components, and the keys of either pass over the cap.
  * Refused with BMH_EINVAL before anything is written: edits outside -1 .. 21, edits without a barcode source; and by the record's index: a first record whose
  * value holds more than 21 bytes or a byte other than A C G T N - + (lower case too).
- * bmh_bam_markdup_barcode_edits_* / bmh_bam_sorted_file_barcode_edits_*: the barcode calls with edits, barcode_max_set and the counts.
- * bmh_bam_dup_barcodes_packed_*: bmh_bam_dup_barcodes_* with packed words.  bmh_barcode_pack: *word of a value of n bytes; 1, or 0 when it does not pack.
+ * bmh_barcode_pack: *word of a value of n bytes; 1, or 0 when it does not pack.
  * bmh_aligner_set_markdup_barcode_edits: the marked runs that follow group barcodes within n mismatches (-1: off); after bmh_aligner_set_markdup_barcode, which
  * switches it off again when called anew.  bmh_aligner_markdup_barcode_group_counts: the three counts of the last such run. */
-int bmh_bam_markdup_barcode_edits_device(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
-                                         int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, void *stream, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts,
-                                         uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped);
-int bmh_bam_markdup_barcode_edits_host(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, int64_t distance, uint64_t max_set,
-                                       int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, uint8_t **out, uint64_t counts[8], uint64_t *lib_counts,
-                                       uint64_t optical[3], uint64_t *lib_optical, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped);
-int bmh_bam_sorted_file_barcode_edits_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records,
-                                             uint64_t n_bytes, int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib,
-                                             int n_groups, int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, void *stream, uint8_t **bam, uint64_t *bam_bytes,
-                                             uint8_t **index, uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3],
-                                             uint64_t *lib_grouped);
-int bmh_bam_sorted_file_barcode_edits_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records,
-                                           uint64_t n_bytes, int level, uint32_t window, int index_format, int min_shift, const char *const *rg_ids, const int32_t *rg_lib, int n_groups,
-                                           int barcode_mode, const char tag[2], int edits, uint64_t barcode_max_set, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index,
-                                           uint64_t *index_bytes, uint64_t counts[8], uint64_t *lib_counts, uint64_t *no_barcode, uint64_t grouped[3], uint64_t *lib_grouped);
-int bmh_bam_dup_barcodes_packed_device(const uint8_t *records, uint64_t n_bytes, int barcode_mode, const char tag[2], void *stream, uint64_t **words, uint64_t *n_templates);
-int bmh_bam_dup_barcodes_packed_host(const uint8_t *records, uint64_t n_bytes, int barcode_mode, const char tag[2], uint64_t **words, uint64_t *n_templates);
 int bmh_barcode_pack(const uint8_t *value, uint64_t n, uint64_t *word);
 int bmh_aligner_set_markdup_barcode_edits(bmh_aligner_t *a, int n);
 int bmh_aligner_markdup_barcode_group_counts(bmh_aligner_t *a, uint64_t out[3]);

@@ -238,7 +238,7 @@ def main():
                 bs = int.from_bytes(blob[p + 16:p + 18], "little") + 1
                 recs.append(zlib.decompress(blob[p:p + bs], 31)); p += bs
             pstream = b"".join(recs)
-            for what, kw in (("located_names_paired_bam_markdup_device", {}), ("located_names_paired_bam_markdup_optical_device", dict(optical_distance=a.optical))):
+            for what, kw in (("located_names_paired_bam_markdup_device", {}), ("located_names_paired_bam_markdup_device_optical", dict(optical_distance=a.optical))):
                 secs = []
                 for it in range(a.runs + 1):
                     torch.cuda.synchronize(); t1 = time.perf_counter()

@@ -34,7 +34,7 @@ int main(int argc, char **argv)
 			p += sz; off.push_back(p);
 		}
 		uint64_t counts[BDP_N_COUNTS];
-		if (rc == BMH_OK) rc = bdp_markdup_host(all, off, counts, "test");
+		if (rc == BMH_OK) rc = bdp_markdup_host(all, off, counts, "test", bdp_plan_t());
 		fwrite(&rc, 4, 1, o);
 		if (rc == BMH_OK) {
 			const uint32_t n = (uint32_t)(off.size() - 1);

@@ -39,7 +39,7 @@ int main(int argc, char **argv)
 		if (fread(&nb, 8, 1, f) != 1) return 2;
 		uint8_t *all = new uint8_t[nb ? nb : 1];
 		if (nb && fread(all, 1, nb, f) != nb) return 2;
-		bdp_table_t T;
+		bdp_plan_t P; bdp_table_t &T = P.table;
 		int32_t rc = bdp_table_make(T, ids.data(), lib.data(), (int)ng, "test");
 		for (char *id : ids) delete[] id;                          // (the table keeps its own copy of the IDs)
 		std::vector<uint64_t> off(1, 0);
@@ -50,7 +50,8 @@ int main(int argc, char **argv)
 		}
 		uint64_t counts[BDP_N_COUNTS];
 		std::vector<uint64_t> lc((size_t)BDP_N_COUNTS * (T.n_lib ? T.n_lib : 1), 0);
-		if (rc == BMH_OK) rc = bdp_markdup_host(all, off, counts, "test", &T, lc.data());
+		P.lib_counts = lc.data();
+		if (rc == BMH_OK) rc = bdp_markdup_host(all, off, counts, "test", P);
 		fwrite(&rc, 4, 1, o);
 		if (rc == BMH_OK) {
 			const uint32_t n = (uint32_t)(off.size() - 1);

@@ -78,7 +78,7 @@ int main(int argc, char **argv)
 			if (!sz) { rc = BMH_EINVAL; break; }
 			p += sz; off.push_back(p);
 		}
-		bdp_table_t T; bdp_bc_t bc;
+		bdp_plan_t P; bdp_table_t &T = P.table; bdp_bc_t &bc = P.bc;
 		if (rc == BMH_OK && n_groups) rc = bdp_table_make(T, idp.data(), lib.data(), (int)n_groups, "test");
 		if (rc == BMH_OK) rc = bdp_barcode_check((int)mode, tag, "test", &bc);
 		if (rc == BMH_OK && D != -1) rc = bdp_optical_check(D, max_set, "test");
@@ -86,12 +86,12 @@ int main(int argc, char **argv)
 		for (uint32_t i = 0; rc == BMH_OK && i < n; ++i) if (!bdp_record_whole(all + off[i], off[i + 1] - off[i])) rc = BMH_EINVAL;
 		// the words on their own, then the whole of it
 		std::vector<uint32_t> tpl; std::vector<bdp_entry_t> E; std::vector<uint64_t> W; uint64_t info[2] = {0, 0};
-		const bdp_groups_t G = T.view();
-		if (rc == BMH_OK) rc = bdp_entries_host(all, off.data(), n, tpl, E, info, "test", n_groups ? &G : nullptr, nullptr, &bc, &W);
+		if (rc == BMH_OK) rc = bdp_entries_host(all, off.data(), n, tpl, E, info, "test", P, nullptr, &W);
 		uint64_t counts[BDP_N_COUNTS], opt[BDP_OPT_N] = {0, 0, 0}, no_bc = 0;
 		std::vector<uint64_t> lib_counts((size_t)BDP_N_COUNTS * T.n_lib + 1), lib_opt((size_t)BDP_OPT_N * T.n_lib + 1);
-		const bdp_optical_t O = {D, max_set ? max_set : (uint32_t)BDP_OPT_MAX_SET, opt, n_groups ? lib_opt.data() : nullptr};
-		if (rc == BMH_OK) rc = bdp_markdup_host(all, off, counts, "test", n_groups ? &T : nullptr, n_groups ? lib_counts.data() : nullptr, D != -1 ? &O : nullptr, &bc, &no_bc);
+		if (D != -1) P.opt = {D, max_set ? max_set : (uint32_t)BDP_OPT_MAX_SET, opt, n_groups ? lib_opt.data() : nullptr};
+		P.lib_counts = n_groups ? lib_counts.data() : nullptr; P.no_barcode = &no_bc;
+		if (rc == BMH_OK) rc = bdp_markdup_host(all, off, counts, "test", P);
 		fwrite(&rc, 4, 1, o);
 		if (rc == BMH_OK) {
 			const uint32_t nt = (uint32_t)W.size(), nl = n_groups ? T.n_lib : 0;

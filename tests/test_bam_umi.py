@@ -407,13 +407,20 @@ def test_refusals():
         bam_dup_barcodes(s, host=True)
     # the library's own check, behind Python's
     L = load_library()
-    out, counts, nb = C.c_void_p(), (C.c_uint64 * 8)(), C.c_uint64()
-    L.bmh_bam_markdup_barcode_host.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_int, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    from bwamem_hip.lib import MarkdupOpt, MarkdupCounts, _markdup_api
+    _markdup_api(L)
+    out, res = C.c_void_p(), MarkdupCounts()
+
+    def call(mode, tag, r=res):
+        o = MarkdupOpt()
+        L.bmh_markdup_opt_default(C.byref(o))
+        o.barcode_mode, o.barcode_tag = mode, tag or b""
+        return L.bmh_bam_markdup_host(s, len(s), C.byref(o), C.byref(out), C.byref(r) if r is not None else None)
     for mode, tag in ((1, b"RG"), (1, b"pa"), (1, b"1X"), (1, b"X-"), (1, b"X"), (1, None), (3, b"RX"), (-1, b"RX")):
-        assert L.bmh_bam_markdup_barcode_host(s, len(s), None, None, 0, -1, 0, mode, tag, C.byref(out), counts, None, None, None, C.byref(nb)) == -2, (mode, tag)
+        assert call(mode, tag) == -2, (mode, tag)
         assert out.value is None and ("barcode" in _err(L))
-    assert L.bmh_bam_markdup_barcode_host(s, len(s), None, None, 0, -1, 0, 1, b"RX", C.byref(out), counts, None, None, None, C.byref(nb)) == 0 and counts[2] == 1
+    assert call(1, b"RX", None) == -2 and out.value is None             # (a call without its counts record)
+    assert call(1, b"RX") == 0 and res.counts[2] == 1
     L.bmh_free.argtypes = [C.c_void_p]; L.bmh_free(out)
     # records: a tag of another type, tags that cannot be walked -- by the index of the template's first record
     good = upair(b"g", 100, 300, b"AC")

@@ -410,17 +410,22 @@ def test_refusals():
             bam_markdup(s, host=True, barcode_tag="RX", barcode_edits=1, barcode_max_set=bad)
     # the library's own check, behind Python's
     L = load_library()
-    out, counts, nb, grp = C.c_void_p(), (C.c_uint64 * 8)(), C.c_uint64(), (C.c_uint64 * 3)()
-    L.bmh_bam_markdup_barcode_edits_host.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_int, C.c_char_p, C.c_int, C.c_uint64,
-                                                     C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
-    call = lambda mode, tag, n, cap=0, g=grp: L.bmh_bam_markdup_barcode_edits_host(s, len(s), None, None, 0, -1, 0, mode, tag, n, cap, C.byref(out), counts, None, None, None, C.byref(nb), g, None)
+    from bwamem_hip.lib import MarkdupOpt, MarkdupCounts, _markdup_api
+    _markdup_api(L)
+    out, res = C.c_void_p(), MarkdupCounts()
+
+    def call(mode, tag, n, cap=0, r=res):
+        o = MarkdupOpt()
+        L.bmh_markdup_opt_default(C.byref(o))
+        o.barcode_mode, o.barcode_tag, o.barcode_edits, o.barcode_max_set = mode, tag or b"", n, cap
+        return L.bmh_bam_markdup_host(s, len(s), C.byref(o), C.byref(out), C.byref(r) if r is not None else None)
     for mode, tag, n, cap in ((1, b"RX", 22, 0), (1, b"RX", -2, 0), (0, None, 1, 0), (0, b"RX", 0, 0), (1, b"RX", 1, 1 << 31)):
         assert call(mode, tag, n, cap) == -2, (mode, tag, n, cap)
         assert out.value is None and "barcode" in _err(L)
-    assert call(1, b"RX", 1, 0, None) == -2 and out.value is None
-    assert call(1, b"RX", 1) == 0 and counts[2] == 1 and list(grp) == [2, 1, 0]
+    assert call(1, b"RX", 1, 0, None) == -2 and out.value is None      # (a call without its counts record)
+    assert call(1, b"RX", 1) == 0 and res.counts[2] == 1 and list(res.grouped) == [2, 1, 0]
     L.bmh_free.argtypes = [C.c_void_p]; L.bmh_free(out)
-    assert call(1, b"RX", -1) == 0 and counts[2] == 0                   # (-1: the exact comparison)
+    assert call(1, b"RX", -1) == 0 and res.counts[2] == 0               # (-1: the exact comparison)
     L.bmh_free(out)
     # records: a value that does not pack -- by the index of the template's first record, after the templates before it
     good = upair(b"g", 100, 300, b"AC")
