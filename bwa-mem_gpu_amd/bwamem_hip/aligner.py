@@ -1011,7 +1011,7 @@ class Aligner:
         if c is not None:
             c[0].free()
         cn, cb = (n, nb) if c is None else (n + n // 4, nb + nb // 4)
-        ws = SeedWorkspace(cn, cb, max_cands=cb, max_occ=max(64 * cn, 1 << 16))       # one candidate per base is the hard upper bound
+        ws = SeedWorkspace(cn, cb, max_cands=cb, max_occ=max(64 * cn, 1 << 16))       # one candidate per base bounds the candidates; the workspace adds what its chunked appends lose
         self._ws_cache = (ws, cn, cb)
         return ws
 

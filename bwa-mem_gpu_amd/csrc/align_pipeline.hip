@@ -632,7 +632,7 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 		// (64 occurrences per read of 150 bases: a batch of long reads gets that per 150 of its bases)
 		const uint64_t per = std::max<uint64_t>(Ln.sws_reads, Ln.sws_bases / 150);
 		const uint64_t occ = 64ull * per > (1ull << 16) ? 64ull * per : (1ull << 16);
-		Ln.sws = bmh_seed_ws_create(Ln.sws_reads, Ln.sws_bases, Ln.sws_bases, occ);          // one candidate per base is the hard upper bound
+		Ln.sws = bmh_seed_ws_create(Ln.sws_reads, Ln.sws_bases, Ln.sws_bases, occ);          // one candidate per base bounds the candidates; the workspace adds what its chunked appends lose
 		if (!Ln.sws) return BMH_ENOMEM;
 	}
 	const double tg = now_s(); Ln.t[0] += tg - t0;

@@ -805,7 +805,13 @@ extern "C" bmh_seed_ws_t *bmh_seed_ws_create(uint32_t max_reads, uint64_t max_ba
 	bmh_seed_ws *w = (bmh_seed_ws *)calloc(1, sizeof(bmh_seed_ws));
 	w->max_reads = max_reads; w->max_bases = max_bases;
 	w->max_cands = max_cands ? max_cands : (uint64_t)max_reads * 16 + max_bases * 2 / 5;
-	w->max_cands += ((uint64_t)max_reads / 64 + 1) * (CAND_CHUNK + 64);   // chunked appends: one open chunk per wave
+	// Chunked appends (cand_append): the list must hold the SLOTS handed out, not the candidates.  A wave leaves a chunk only when its next round -- at most
+	// 64 appends -- does not fit, so a chunk it has left holds more than CAND_CHUNK - 64 candidates: at least 961 of its 1024 slots are used, fewer than 64
+	// are lost.  A wave with c candidates leaves at most c / 961 chunks and has one open: slots <= 1024 (c / 961 + 1).  Over the at most max_reads / 64 + 1
+	// waves that append at all: slots <= max_cands * 1024 / 961 + one chunk per wave.  (Without the first term 57 poly-A reads of 2 000 bases in one
+	// wave -- 17 rounds of 57 per chunk, 55 slots lost in each -- took 119 808 slots where one candidate per base plus the open chunks gave 116 176.)
+	w->max_cands += w->max_cands * 63 / 961 + 1;                          // the rest of a chunk that a round did not fit
+	w->max_cands += ((uint64_t)max_reads / 64 + 1) * (CAND_CHUNK + 64);   // one open chunk per wave
 	w->max_occ = max_occ ? max_occ : (uint64_t)max_reads * 64;
 	// packed-read buffers are sized by the longest read of a batch: allocated on first use
 	w->n_grp_cap = 0;

@@ -6,7 +6,6 @@ e - b >= min_seed_len >= K, and then T would hold that window.  Checked three wa
 oracle's rank function against the oracle's SMEMs (CPU); the device bitmap against numpy's K-mer set; the device seeds with the
 bitmap on and off against each other and against the oracle.
 """
-import ctypes as C
 import functools
 import os
 
@@ -17,108 +16,7 @@ import common
 import oracle_py
 from bwamem_hip import fmindex, synth
 
-MAX_K = 18
-
-
-# ---------------------------------------------------------------------------------------------------------------- plain numpy
-
-def kmer_k(seq_len: int) -> int:
-    """the sizing rule: the smallest K with 4^K >= 8 seq_len, at most 18"""
-    K = 1
-    while K < MAX_K and 4 ** K < 8 * seq_len:
-        K += 1
-    return K
-
-
-def text_of(g: np.ndarray) -> np.ndarray:
-    return np.concatenate([g, 3 - g[::-1]]).astype(np.uint8)
-
-
-def kmer_keys(t: np.ndarray, K: int) -> np.ndarray:
-    """key of every length-K window of t: symbol j of the window at bits 2j+1:2j"""
-    n = len(t) - K + 1
-    if n <= 0:
-        return np.zeros(0, np.uint64)
-    key = np.zeros(n, np.uint64)
-    for j in range(K):
-        key |= t[j:j + n].astype(np.uint64) << np.uint64(2 * j)
-    return key
-
-
-def kmer_table(g: np.ndarray, K: int) -> np.ndarray:
-    """bool [4^K]: does the K-mer occur in fwd . revcomp(fwd)"""
-    tab = np.zeros(4 ** K, bool)
-    tab[kmer_keys(text_of(g), K)] = True
-    return tab
-
-
-def window_alive(tab: np.ndarray, K: int, q: np.ndarray, e: int) -> bool:
-    w = q[e - K:e]
-    if e < K or (w > 3).any():
-        return False
-    return bool(tab[int(kmer_keys(w, K)[0])])
-
-
-def smems_by_rule(orc, f, q: np.ndarray, min_seed_len: int, tab=None, K: int = 0):
-    """One read through the split pipeline's decomposition, in plain Python over the oracle's rank function: forward candidates at
-    every interval-size change, an independent backward walk for each, too-short results marked, contained results dropped by the
-    next valid result of the read.  tab: candidates shorter than K whose window is dead are not generated at all.
-    Returns ([(begin, end, k, s)], number of candidates, rank steps of the backward walks)."""
-    occ = orc.lib.fmd_occ
-    fp = C.byref(f)
-    L2 = [int(f.L2[i]) for i in range(5)]
-    primary, n = int(f.primary), len(q)
-    use = tab is not None and min_seed_len >= K
-    M64 = (1 << 64) - 1
-
-    def occ4(k):
-        return [int(occ(fp, k & M64, c)) for c in range(4)]
-    cands, i = [], 0
-    while i < n:
-        if q[i] > 3:
-            i += 1
-            continue
-        x, b = i, int(q[i])
-        k, s, l = L2[b] + 1, L2[b + 1] - L2[b], L2[3 - b] + 1
-        i += 1
-        while True:
-            if i == n or q[i] > 3:
-                cands.append((x, i, k, s))
-                break
-            cb = 3 - int(q[i])
-            tk, tl = occ4(l - 1), occ4(l - 1 + s)
-            ns = [tl[c] - tk[c] for c in range(4)]
-            nk = [0] * 4
-            nk[3] = k + (1 if l <= primary <= l + s - 1 else 0)
-            nk[2] = nk[3] + ns[3]; nk[1] = nk[2] + ns[2]; nk[0] = nk[1] + ns[1]
-            if ns[cb] != s:
-                cands.append((x, i, k, s))
-            if ns[cb] == 0:
-                break                                    # the next pass starts at i
-            k, l, s = nk[cb], L2[cb] + 1 + tk[cb], ns[cb]
-            i += 1
-    cands = [c for c in cands if c[1] >= min_seed_len]
-    if use:
-        cands = [c for c in cands if c[1] - c[0] >= K or window_alive(tab, K, q, c[1])]
-    res, steps = [], 0
-    for x, e, k, s in cands:
-        lo, hi, beg, p = k, k + s - 1, x, x - 1
-        while p >= 0 and q[p] < 4:
-            b = int(q[p])
-            steps += 1
-            nl, nu = L2[b] + int(occ(fp, (lo - 1) & M64, b)) + 1, L2[b] + int(occ(fp, hi, b))
-            if nl > nu:
-                break
-            lo, hi, beg, p = nl, nu, p, p - 1
-        res.append((beg, e, lo, hi - lo + 1 if e - beg >= min_seed_len else 0))
-    out = []
-    for t, (beg, e, lo, s) in enumerate(res):
-        if s == 0:
-            continue
-        nxt = next((r for r in res[t + 1:] if r[3] > 0), None)
-        if nxt is None or nxt[0] != beg:
-            out.append((beg, e, lo, s))
-    return out, len(cands), steps
+from seed_cases import MAX_K, kmer_k, kmer_keys, kmer_table, smems_by_rule, text_of, window_alive      # (the restatement lives beside the seeding case table)
 
 
 def case_reads(g: np.ndarray, K: int, rng, n_random: int, special=()):
