@@ -137,43 +137,72 @@ def read_reads(path: str, comments: bool = False) -> ReadSet:
     return ReadSet(d["ascii"], d["offs"], d["lens"], d["names"], d["name_offs"], codes=d["codes"], qual=d["quals"], comments=cm)
 
 
-def read_reads_files(path1: str, path2: str | None = None, comments: bool = False, host: bool = False) -> ReadSet:
+def read_reads_files(path1: str, path2: str | None = None, comments: bool = False, host: bool = False, collate: bool = False, collate_mem=None, keep_rg: bool = False) -> ReadSet:
     """one or two read files of any shape the reference takes (bmh_reads_load_files): FASTA or FASTQ with records over any number of lines, plain, gzip or
     BGZF, regular files or pipes; path2: the mates (read i of each file -> reads 2i, 2i+1).  The records are cut on the device; host=True: by the host
     walker alone (no device needed).  A refused file raises ValueError (lib.ReadFileError); when one file ends before the other, its `partial` attribute
-    is the ReadSet of the complete pairs."""
+    is the ReadSet of the complete pairs.
+    collate=True: `path1` is a paired BAM in any record order, a coordinate-sorted one for instance -- the mates of a pair are found by name, and the reads are
+    the pairs in the order in which their later record comes (include/bwamem_hip.h has the definition); text input is refused, a record whose partner never comes
+    is refused with the complete pairs in `partial`, and beyond collate_mem bytes of records that wait for their partners (8 GiB by default) the file is refused.
+    keep_rg=True: `path1` is a BAM read under its own read groups, as align_files(keep_rg=True) reads it -- the ReadSet's `groups` is the index of every read's
+    @RG line in the header, and the refusals are those of that run."""
     from .lib import ReadFileError, load_reads_files
 
     def wrap(d):
         if len(d["lens"]) == 0:
             return ReadSet.from_lists([], [], comments=[] if comments else None)
         cm = (d["comments"], d["comment_offs"]) if d["comments"] is not None else None
-        return ReadSet(d["ascii"], d["offs"], d["lens"], d["names"], d["name_offs"], codes=d["codes"], qual=d["quals"], comments=cm)
+        rs = ReadSet(d["ascii"], d["offs"], d["lens"], d["names"], d["name_offs"], codes=d["codes"], qual=d["quals"], comments=cm)
+        if keep_rg:
+            rs.groups = d["groups"]
+        return rs
     try:
-        return wrap(load_reads_files(path1, path2, comments=comments, host=host))
+        return wrap(load_reads_files(path1, path2, comments=comments, host=host, collate=collate, collate_mem=collate_mem, keep_rg=keep_rg))
     except ReadFileError as e:
         if getattr(e, "partial", None) is not None:
             e.partial = wrap(e.partial)
         raise
 
 
-def bam_to_reads(records: bytes, comments: bool = False, host: bool = False, read_groups=None) -> ReadSet:
+def bam_to_reads(records: bytes, comments: bool = False, host: bool = False, read_groups=None, collate: bool = False, collate_mem=None) -> ReadSet:
     """uncompressed BAM records (without the header) as the reads read_reads_files gives for the BAM file that holds them (bmh_bam_reads_device; host=True:
     bmh_bam_reads_host, no device needed): `samtools fastq`'s rules -- secondary and supplementary records skipped, reverse-strand records turned back, pairs
     (flag 0x1) as reads 2i / 2i+1, and with comments=True the tags as the comment -C copies.  Refused records raise ValueError (lib.ReadFileError).
     read_groups: a list of read group IDs -- the ReadSet's `groups` is then the index of every read's RG:Z value in that list (whole IDs compared); a kept
     record without an RG tag, with one of another type than Z or with an ID that is not listed, and a pair whose two records name different groups are refused
-    naming the record's index.  Records skipped by their flag are not looked at."""
-    from .lib import bam_reads
-    d = bam_reads(records, comments=comments, host=host, read_groups=read_groups)
-    if len(d["lens"]) == 0:
-        rs = ReadSet.from_lists([], [], comments=[] if comments else None)
-        rs.groups = np.zeros(0, np.uint32) if read_groups is not None else None
+    naming the record's index.  Records skipped by their flag are not looked at.
+    collate=True: the records are in any order and mates are found by name, as read_reads_files(collate=True) finds them (collate_mem: its cap)."""
+    from .lib import ReadFileError, bam_reads
+
+    def wrap(d):
+        if len(d["lens"]) == 0:
+            rs = ReadSet.from_lists([], [], comments=[] if comments else None)
+            rs.groups = np.zeros(0, np.uint32) if read_groups is not None else None
+            return rs
+        cm = (d["comments"], d["comment_offs"]) if d["comments"] is not None else None
+        rs = ReadSet(d["ascii"], d["offs"], d["lens"], d["names"], d["name_offs"], codes=d["codes"], qual=d["quals"], comments=cm)
+        rs.groups = d["groups"] if read_groups is not None else None
         return rs
-    cm = (d["comments"], d["comment_offs"]) if d["comments"] is not None else None
-    rs = ReadSet(d["ascii"], d["offs"], d["lens"], d["names"], d["name_offs"], codes=d["codes"], qual=d["quals"], comments=cm)
-    rs.groups = d["groups"] if read_groups is not None else None
-    return rs
+    try:
+        return wrap(bam_reads(records, comments=comments, host=host, read_groups=read_groups, collate=collate, collate_mem=collate_mem))
+    except ReadFileError as e:
+        if getattr(e, "partial", None) is not None:
+            e.partial = wrap(e.partial)
+        raise
+
+
+def _holds_bam(path) -> bool | None:
+    """does a regular file hold a BAM (a BGZF member whose text begins with the magic bytes)?  None for what cannot be looked at without taking its bytes (a pipe)"""
+    import zlib
+    try:
+        if not os.path.isfile(path) or os.path.getsize(path) == 0:      # (an empty file is the library's to name)
+            return None
+        with open(path, "rb") as f:
+            head = f.read(1 << 16)
+        return zlib.decompressobj(31).decompress(head, 4)[:4] == b"BAM\1"
+    except (OSError, zlib.error):
+        return False
 
 
 def bam_read_groups(header_text, markdup: bool = False) -> list:
@@ -856,7 +885,8 @@ class Aligner:
 
     def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
                     sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None, keep_rg: bool = False,
-                    index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None) -> int:
+                    index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
+                    collate: bool = False, collate_mem=None) -> int:
         """align_file for the files users have (bmh_aligner_run_files): `reads` (and `mates`: the second file of a pair, which implies paired) may be
         multi-line FASTA or FASTQ, plain, gzip or BGZF, a regular file or a pipe; or `reads` alone is a BAM file (unaligned, or grouped by read name: recognised
         from its bytes, pairs from flag 0x1 of its records -- paired=True on a BAM without it is refused).  Batches are cut by align_file's rules (-t, -K, the 150 Mbase floor for
@@ -866,9 +896,33 @@ class Aligner:
         Batches are cut and reads indexed as without it, and a batch may hold reads of any number of groups.  markdup=True calls duplicates within a library (the
         LB field, rg_library's rules): self.markdup_library_counts and markdup_metrics have a row per library.  Refused before anything is written (ValueError):
         text input, `mates`, -R, a header without a valid @RG line (bam_read_groups' rules).  A record without an RG:Z tag, with an ID the header does not hold,
-        or a pair of two groups fails the run naming the record's index, after the batches before it were written."""
+        or a pair of two groups fails the run naming the record's index, after the batches before it were written.
+        collate=True takes a paired BAM in any record order, a coordinate-sorted one -- this aligner's own sort=True output -- among them: the mates of a pair are
+        found by name on the device (bmh_aligner_set_collate; include/bwamem_hip.h has the definition), the reads are the pairs in the order in which their later
+        record comes, and the output is byte for byte that of a run without it on the name-grouped BAM of the same pairs in that order.  It composes with every
+        other option and changes none.  collate_mem: the cap in bytes on the records that wait for their partners (None: 8 GiB; needs collate); beyond it, and at
+        a record whose partner never comes, the run fails naming the record after the batches before it were written.  Text input is refused before anything is
+        written (a regular file is looked at first; a pipe of text is refused by the library once it is opened)."""
         if out is None:
             raise ValueError("align_files: out (a text or binary file object) is required")
+        if collate_mem is not None and not collate:
+            raise ValueError("align_files: collate_mem without collate=True: the cap is that of the collation's open records")
+        if collate and getattr(self, "_collate", None) is None:        # the outermost call of such a run: the refusals, and the state that lasts as long as it
+            if mates is not None or _holds_bam(reads) is False:
+                from .lib import ReadFileError
+                raise ReadFileError(f"reads file: {reads}: mates are collated by name (--collate) in BAM input only: text input is taken in the order of its records")
+            if os.environ.get("BMH_ALIGNER_NATIVE", "1") == "0" or self.profile:
+                raise NotImplementedError("collate=True needs the native pipeline (BMH_ALIGNER_NATIVE=0 and profile runs write batch after batch)")
+            self._collate = (True, collate_mem)
+            try:
+                return self.align_files(reads, None, out=out, paired=paired, chunk_bases=chunk_bases, batch_reads=batch_reads, fmt=fmt, level=level, sort=sort, index=index,
+                                        sort_mem=sort_mem, sort_tmp=sort_tmp, sort_window=sort_window, markdup=markdup, markdup_metrics=markdup_metrics, keep_rg=keep_rg,
+                                        index_format=index_format, csi_min_shift=csi_min_shift, optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name, barcode_edits=barcode_edits)
+            finally:
+                self._collate = None
+                nat = getattr(self, "_native", None)
+                if nat is not None:
+                    nat.set_collate(False)
         if keep_rg and getattr(self, "_keep_rg", None) is None:          # the outermost call of such a run: the refusals, and the state that lasts as long as it
             if mates is not None:
                 raise ValueError("align_files: keep_rg=True and a mates file: a run that keeps its input's read groups takes one BAM file")
@@ -899,6 +953,7 @@ class Aligner:
                 cb = max(cb, 150_000_000)                 # (single-end records do not depend on the cuts: align_file)
             cb = min(cb, (1 << 31) - 1024)
         nat = self._native_aligner()
+        nat.set_collate(*(getattr(self, "_collate", None) or (False, None)))
         if keep_rg:
             # the header waits for the input's: the library calls back once it has read the BAM's header whole -- before the first record -- and the @RG lines go
             # into ours there (header() reads self._groups); a refused input has written nothing by then
@@ -923,16 +978,20 @@ class Aligner:
 
     def align_groups(self, groups, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
                      sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
-                     index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None) -> int:
+                     index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
+                     collate: bool = False, collate_mem=None) -> int:
         """several read groups -- a sample's lanes and libraries -- into one output (bmh_aligner_run_groups).  groups: [(rg_line, reads, mates or None), ...]; every
         rg_line is unescaped and checked as -R's value is, reads / mates are what align_files takes (one file or R1 + R2; plain, gzip or BGZF; FASTA or FASTQ; or
         one BAM, whose own @RG lines and RG tags stay ignored: align_files(keep_rg=True) is the run that keeps them, and the two do not combine).  Group g's records are byte for byte those of align_files(reads_g, mates_g) alone under -R rg_g, and
         the unsorted output is the groups' outputs in order; the header holds every @RG line.  All groups hold pairs or none does (paired applies to every group).
         markdup=True calls duplicates within a library only (a group's library is its LB field; groups without one share "Unknown Library"):
         self.markdup_library_counts holds the counts per library, markdup_metrics one row per library.  Needs the native pipeline; -R must not be set.
+        collate / collate_mem: align_files' -- they apply to every group whose input is one BAM; groups of text files are taken as ever.
         Returns the number of reads."""
         if out is None:
             raise ValueError("align_groups: out (a text or binary file object) is required")
+        if collate_mem is not None and not collate:
+            raise ValueError("align_groups: collate_mem without collate=True: the cap is that of the collation's open records")
         if not groups:
             raise ValueError("align_groups: no read groups were given")
         if getattr(self, "rg_line", ""):
@@ -951,6 +1010,7 @@ class Aligner:
         if os.environ.get("BMH_ALIGNER_NATIVE", "1") == "0" or self.profile:
             raise NotImplementedError("align_groups needs the native pipeline (BMH_ALIGNER_NATIVE=0 and profile runs write batch after batch)")
         self._groups = parsed
+        self._collate = (True, collate_mem) if collate else None
         try:
             if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None or barcode_tag is not None or barcode_name or barcode_edits is not None:
                 return self._align_bam(lambda o: self._run_groups(parsed, libs, o, paired, chunk_bases, batch_reads), out, fmt, level,
@@ -958,6 +1018,10 @@ class Aligner:
             return self._run_groups(parsed, libs, out, paired, chunk_bases, batch_reads)
         finally:
             self._groups = None
+            self._collate = None
+            nat = getattr(self, "_native", None)
+            if nat is not None:
+                nat.set_collate(False)
 
     def _run_groups(self, parsed, libs, out, paired, chunk_bases, batch_reads) -> int:
         binary = "b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")
@@ -973,6 +1037,7 @@ class Aligner:
                     raise ReadFileError(f"read group '{rid}': reads file: {path}: no such file")
         out.write(self.header().encode() if binary else self.header())
         nat = self._native_aligner()
+        nat.set_collate(*(getattr(self, "_collate", None) or (False, None)))
         nat.set_bam_pairs(cb_pairs, int(os.environ.get("BMH_ALIGNER_LANES", "3")))
         try:
             self.last_stats = nat.run_groups([(q[1], libs.index(rg_library(q[0])), q[2], q[3]) for q in parsed], bool(paired),

@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "bmh_bam_dup_barcodes_device", "bmh_bam_dup_barcodes_host", "bmh_barcode_word", "bmh_aligner_set_markdup_barcode", "bmh_aligner_markdup_barcode_counts",
     "bmh_barcode_pack", "bmh_aligner_set_markdup_barcode_edits",
     "bmh_aligner_markdup_barcode_group_counts",
+    "bmh_reads_last_collate_counts", "bmh_aligner_set_collate", "bmh_reads_load_files_ex", "bmh_bam_reads_ex",
 ]
 
 
@@ -175,6 +176,35 @@ def load_reads(path: str, comments: bool = False, n_threads: int = 0) -> dict:
 
 
 READS_HOST = 2              # BMH_READS_HOST
+READS_COLLATE = 4           # BMH_READS_COLLATE
+
+
+class CollateCountsT(C.Structure):
+    """bmh_collate_counts_t"""
+    _fields_ = [(n, C.c_uint64) for n in ("pairs", "pairs_adjacent", "open_records_peak", "open_bytes_peak", "windows_to_host_for_hash_runs")]
+
+
+def reads_last_collate_counts() -> dict:
+    """bmh_reads_last_collate_counts: what the collation of mates by name (collate=True) did in the process's last load_reads_files / bam_reads / run_files /
+    run_groups call -- pairs, the pairs whose two records were adjacent, the peaks of the open records and of their bytes (the definition's table: pool and
+    window), windows the device handed to the host form for a run of equal hashes.  All zero after a call that did not collate."""
+    L = load_library()
+    L.bmh_reads_last_collate_counts.argtypes = [C.POINTER(CollateCountsT)]
+    c = CollateCountsT()
+    L.bmh_reads_last_collate_counts(C.byref(c))
+    return {n: int(getattr(c, n)) for n, _t in CollateCountsT._fields_}
+
+
+READS_KEEP_RG = 8           # BMH_READS_KEEP_RG
+
+
+def _collate_cap(collate, collate_mem) -> int:
+    """collate_mem as bmh_reads_load_files_ex / bmh_bam_reads_ex take it (0: the default cap)"""
+    if collate_mem is not None and not collate:
+        raise ValueError("collate_mem without collate=True: the cap is that of the collation's open records")
+    if collate_mem is not None and int(collate_mem) < 1:
+        raise ValueError("collate_mem: a number of bytes, 1 or more")
+    return int(collate_mem or 0)
 
 
 def reads_last_counts() -> dict:
@@ -791,28 +821,50 @@ def bam_header_read_groups(text, markdup: bool = False) -> tuple:
         L.bmh_free(lines); L.bmh_free(lib)
 
 
-def bam_reads(records: bytes, comments: bool = False, host: bool = False, read_groups=None) -> dict:
+def bam_reads(records: bytes, comments: bool = False, host: bool = False, read_groups=None, collate: bool = False, collate_mem=None) -> dict:
     """bmh_bam_reads_device (host=True: bmh_bam_reads_host, no device needed): uncompressed BAM records, without the header, as load_reads_files gives a file's
     reads -- `samtools fastq`'s rules (include/bwamem_hip.h).  Refused records raise ReadFileError naming the record's index.
     read_groups: a list of read group IDs (bmh_bam_reads_groups_*) -- the result gains "groups", the index of every read's RG:Z value in that list; a kept record
-    without the tag, with an RG tag of another type or an ID that is not listed, and a pair of two groups are refused the same way."""
+    without the tag, with an RG tag of another type or an ID that is not listed, and a pair of two groups are refused the same way.
+    collate=True: the mates of a pair are found by name wherever they lie (BMH_READS_COLLATE, include/bwamem_hip.h); a record still open at the end raises
+    ReadFileError whose `partial` holds the complete pairs.  collate_mem: the cap on the open records' bytes (bmh_bam_reads_ex)."""
     L = load_library()
     records = bytes(records)
     rs = ReadSetT()
     L.bmh_reads_free.argtypes = [C.POINTER(ReadSetT)]
+    flags = (READS_COMMENTS if comments else 0) | (READS_COLLATE if collate else 0)
+
+    def refused(prefix, other):
+        msg = _err(L)
+        if not msg.startswith("reads file"):
+            return other(prefix + msg)
+        e = ReadFileError(msg)
+        if rs.ascii:                                   # (an open record at the end of a collated input: the complete pairs before it)
+            e.partial = _read_set_dict(L, rs)
+        return e
     if read_groups is not None:
         ids = (C.c_char_p * max(len(read_groups), 1))(*[(i if isinstance(i, bytes) else str(i).encode()) for i in read_groups])
         fn = L.bmh_bam_reads_groups_host if host else L.bmh_bam_reads_groups_device
         fn.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(ReadSetT)]
-        if fn(records, len(records), READS_COMMENTS if comments else 0, ids, len(read_groups), C.byref(rs)) != 0:
-            msg = _err(L)
-            raise ReadFileError(msg) if msg.startswith("reads file") else ValueError("bmh_bam_reads: " + msg)
+        cap = _collate_cap(collate, collate_mem)
+        if cap:
+            L.bmh_bam_reads_ex.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_uint64, C.POINTER(ReadSetT)]
+            rc = L.bmh_bam_reads_ex(records, len(records), flags | (READS_HOST if host else 0), ids, len(read_groups), cap, C.byref(rs))
+        else:
+            rc = fn(records, len(records), flags, ids, len(read_groups), C.byref(rs))
+        if rc != 0:
+            raise refused("bmh_bam_reads: ", ValueError)
         return _read_set_dict(L, rs)
     fn = L.bmh_bam_reads_host if host else L.bmh_bam_reads_device
     fn.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(ReadSetT)]
-    if fn(records, len(records), READS_COMMENTS if comments else 0, C.byref(rs)) != 0:
-        msg = _err(L)
-        raise ReadFileError(msg) if msg.startswith("reads file") else RuntimeError("bmh_bam_reads: " + msg)
+    cap = _collate_cap(collate, collate_mem)
+    if cap:
+        L.bmh_bam_reads_ex.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_uint64, C.POINTER(ReadSetT)]
+        rc = L.bmh_bam_reads_ex(records, len(records), flags | (READS_HOST if host else 0), None, 0, cap, C.byref(rs))
+    else:
+        rc = fn(records, len(records), flags, C.byref(rs))
+    if rc != 0:
+        raise refused("bmh_bam_reads: ", RuntimeError)
     return _read_set_dict(L, rs)
 
 
@@ -835,16 +887,22 @@ def _read_set_dict(L, rs) -> dict:
                 groups=arr(rs.groups, rs.n_reads, np.uint32) if rs.groups else None)
 
 
-def load_reads_files(path1: str, path2: str | None = None, comments: bool = False, host: bool = False, n_threads: int = 0) -> dict:
+def load_reads_files(path1: str, path2: str | None = None, comments: bool = False, host: bool = False, n_threads: int = 0, collate: bool = False, collate_mem=None,
+                     keep_rg: bool = False) -> dict:
     """bmh_reads_load_files: one or two read files of any shape (multi-line records, gzip / BGZF, pipes) as load_reads gives them; path2: the mates (reads 2i
     and 2i+1).  A BGZF file that holds a BAM (unaligned, or grouped by read name) is taken in place of a text file, alone.  host=True: the host walker alone
-    (no device).  A refused file raises ReadFileError; when one file ends before the other its `partial` attribute holds the complete pairs before the end."""
+    (no device).  A refused file raises ReadFileError; when one file ends before the other its `partial` attribute holds the complete pairs before the end.
+    collate=True (BMH_READS_COLLATE): a paired BAM in any record order -- mates are found by name; text input is refused; a record still open at the file's end
+    is refused with the complete pairs in `partial`.  collate_mem: the cap on the open records' bytes (bmh_reads_load_files_ex).
+    keep_rg=True (BMH_READS_KEEP_RG): `path1` is a BAM read under its own read groups -- "groups" is the index of every read's @RG line in the header."""
     L = load_library()
     rs = ReadSetT()
     L.bmh_reads_load_files.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(ReadSetT)]
     L.bmh_reads_free.argtypes = [C.POINTER(ReadSetT)]
-    rc = L.bmh_reads_load_files(os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, n_threads,
-                                (READS_COMMENTS if comments else 0) | (READS_HOST if host else 0), C.byref(rs))
+    L.bmh_reads_load_files_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_uint64, C.POINTER(ReadSetT)]
+    rc = L.bmh_reads_load_files_ex(os.fsencode(path1), os.fsencode(path2) if path2 is not None else None, n_threads,
+                                   (READS_COMMENTS if comments else 0) | (READS_HOST if host else 0) | (READS_COLLATE if collate else 0) | (READS_KEEP_RG if keep_rg else 0),
+                                   _collate_cap(collate, collate_mem), C.byref(rs))
     msg = _err(L) if rc != 0 else ""
     if rc != 0 and not rs.ascii:
         raise ReadFileError(msg) if msg.startswith(("FASTQ:", "reads file", "reads files")) else RuntimeError("bmh_reads_load_files: " + msg)
@@ -1105,6 +1163,14 @@ class NativeAligner:
         L.bmh_aligner_set_bam_pairs.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
         if L.bmh_aligner_set_bam_pairs(self.handle, int(batch_bases), int(n_lanes)) != 0:
             raise ValueError("bmh_aligner_set_bam_pairs: " + _err(L))
+
+    def set_collate(self, on: bool, mem_bytes=None) -> None:
+        """bmh_aligner_set_collate: run_files / run_groups find the mates of a BAM's pairs by name, in any record order; mem_bytes: the cap on the open records'
+        bytes (None: the default of 8 GiB)"""
+        L = load_library()
+        L.bmh_aligner_set_collate.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
+        if L.bmh_aligner_set_collate(self.handle, 1 if on else 0, int(mem_bytes or 0)) != 0:
+            raise ValueError("bmh_aligner_set_collate: " + _err(L))
 
     def set_keep_rg(self, on: bool, header=None) -> None:
         """bmh_aligner_set_keep_rg: run_files keeps the read groups of its input, one BAM.  header(lines, libraries) -- the @RG lines verbatim and every line's

@@ -37,7 +37,12 @@ LINE is an @RG line as -R takes it, and the one or two files that follow it, up 
 and libraries go into one output, every record with its group's RG:Z, the header with every @RG line, and --markdup calls duplicates within a library (the LB
 field; groups with one LB are lanes of one library) only.  -p applies to every group; --rg and -R exclude each other.  --keep-rg keeps the read groups of the
 input, one BAM file (Aligner.align_files(keep_rg=True)): the @RG lines of its header go into the output's header verbatim, every read's records carry the RG:Z of
-the read's own record, and --markdup calls duplicates within a library; it is refused on text input, with a mates file, and beside -R or --rg.  An option that is
+the read's own record, and --markdup calls duplicates within a library; it is refused on text input, with a mates file, and beside -R or --rg.  --collate takes a
+paired BAM in any record order -- a coordinate-sorted one, this program's own --sort output among them: the mates of a pair are found by name on the device, the
+reads are the pairs in the order in which their later record comes, and the output is byte for byte that of a run on the name-grouped BAM of the same pairs in
+that order (Aligner.align_files(collate=True)); first mates wait for their partners in host memory, at most --collate-mem BYTES of them (needs --collate; 8 GiB by
+default; nothing is spilled to disk: beyond the cap the run stops after the batches before it, naming the record); a record whose partner never comes is refused
+after the complete batches; text input is refused (a regular file before anything is written, a pipe of text after the header); with --rg it applies to every group whose input is a BAM.  An option that is
 not on that list is refused by name.  Two input files imply pairs.  One plain, regular file is offered to Aligner.align_file first, which takes it when every
 record has one sequence line (its own counting pass decides, before anything is written); every other input goes through
 Aligner.align_files; the text is the same.  A refused file ends the command with status 1 and the library's message on stderr.
@@ -72,6 +77,7 @@ def main(argv=None) -> int:
     barcode_tag, barcode_name, barcode_edits = None, False, None
     csi, csi_shift = False, None
     keep_rg = False
+    collate, collate_mem = False, None
     groups = []                                                     # --rg LINE: [line, files...]; the positionals behind it are its files
     i = 0
     while i < len(argv):
@@ -122,6 +128,14 @@ def main(argv=None) -> int:
             i += 1
         elif a == "--keep-rg":
             keep_rg = True
+        elif a == "--collate":
+            collate = True
+        elif a == "--collate-mem":
+            if i + 1 >= len(argv) or not (argv[i + 1].isascii() and argv[i + 1].isdigit()) or int(argv[i + 1]) < 1:
+                print("[bwamem_hip.mem] option --collate-mem needs a number of bytes", file=sys.stderr)
+                return 2
+            collate_mem = int(argv[i + 1])
+            i += 1
         elif a == "--rg":
             if i + 1 >= len(argv):
                 print("[bwamem_hip.mem] option --rg needs a value", file=sys.stderr)
@@ -166,6 +180,9 @@ def main(argv=None) -> int:
         i += 1
     if keep_rg and (groups or "-R" in opts):
         print("[bwamem_hip.mem] --keep-rg excludes --rg and -R: the read groups come from the input BAM's own header and tags, or from the command line, not both", file=sys.stderr)
+        return 2
+    if collate_mem is not None and not collate:
+        print("[bwamem_hip.mem] --collate-mem needs --collate (it caps the records that wait for their mates)", file=sys.stderr)
         return 2
     if groups:
         if "-R" in opts:
@@ -246,11 +263,13 @@ def main(argv=None) -> int:
             fmt_kw.update(barcode_edits=barcode_edits)
         if csi:
             fmt_kw.update(index_format="csi", csi_min_shift=14 if csi_shift is None else csi_shift)
+        if collate:
+            fmt_kw.update(collate=True, collate_mem=collate_mem)
         done = False
         if groups:
             al.align_groups([(g[0], g[1], g[2] if len(g) == 3 else None) for g in groups], out=out, paired=interleaved, **fmt_kw)
             done = True
-        elif mates is None and _plain_regular(reads) and not keep_rg:
+        elif mates is None and _plain_regular(reads) and not keep_rg and not collate:
             from .lib import ReadFileError
             try:
                 al.align_file(reads, out, paired=paired, **fmt_kw)

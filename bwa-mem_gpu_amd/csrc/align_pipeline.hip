@@ -890,6 +890,7 @@ struct bmh_aligner {
 	uint64_t host_tail_batches = 0;                      // of the last run (bmh_aligner_host_tail_batches)
 	uint64_t bam_pairs_bases = 0; int bam_pairs_lanes = 0;   // bmh_aligner_set_bam_pairs
 	bool keep_rg = false; bmh_rg_header_fn rg_header = nullptr; void *rg_user = nullptr;      // bmh_aligner_set_keep_rg
+	bool collate = false; uint64_t collate_mem = 0;                                            // bmh_aligner_set_collate
 	bsr_store_t store; bsr_index_t sort_ix; uint32_t sort_window = 0;      // sorted BAM output: the runs of the run in progress, the index of the last one, the window
 	int ix_format = BSR_IX_BAI, ix_shift = BSR_LIN_SHIFT;                  // bmh_aligner_set_index_format: the index of the sorted runs that follow
 	uint64_t dup_counts[BDP_N_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0}; bool dup_valid = false;      // duplicate marking: the counts of the last marked run
@@ -1533,8 +1534,13 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 		if (h->a.markdup && h->a.n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d reference sequences: with read groups duplicate marking takes at most 2^24 (the library is the top byte of its key)", fn, h->a.n_contigs); return BMH_EINVAL; }
 	}
 	// (BMH_READS_HOST=1: the pump's host forms cut every window -- the A/B and cross-check switch of the device parser and the BAM decoder kernels)
-	bmh_reads_pump_t *P = bmh_pump_open(path1, path2, n_threads, cm, bmh_tune("READS_HOST", 0) != 0, 0, keep, keep && h->a.markdup);
+	bmh_reads_pump_t *P = bmh_pump_open(path1, path2, n_threads, cm, bmh_tune("READS_HOST", 0) != 0, (size_t)std::max(0, bmh_tune("READS_CHUNK_BYTES", 0)) /* (the tests' small windows; 0: sized by the batch) */, keep, keep && h->a.markdup, h->collate, h->collate_mem);
 	if (!P) return BMH_EINVAL;
+	if (h->collate && bmh_pump_bam_paired(P) < 0) {                    // refused before a batch is read
+		bmh_pump_close(P);
+		bmh_set_error("reads file: %s: mates are collated by name (--collate) in BAM input only: text input is taken in the order of its records", path1);
+		return BMH_EINVAL;
+	}
 	aligner_t &A = h->a;
 	// the run's table is the aligner's until the run is over, whichever way it ends
 	struct table_guard_t { aligner_t &A; bool on; ~table_guard_t() { if (on) { A.group_ids.clear(); A.plan.table = bdp_table_t(); A.per_read = false; ++A.groups_serial; } } } guard{A, false};
@@ -1572,6 +1578,7 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 	uint64_t cnt[4]; bmh_pump_counts(P, cnt); bmh_reads_note_counts(cnt);
 	uint64_t icnt[2]; bmh_pump_inflate_counts(P, icnt); bmh_reads_note_inflate_counts(icnt);
 	uint64_t bcnt[2]; bmh_pump_bam_counts(P, bcnt); bmh_reads_note_bam_counts(bcnt);
+	uint64_t ccnt[5]; bmh_pump_collate_counts(P, ccnt); bmh_reads_note_collate_counts(ccnt);
 	bmh_pump_close(P);
 	return rc;
 }
@@ -1609,7 +1616,7 @@ int bmh_aligner_run_groups(bmh_aligner_t *h, const bmh_read_group_t *groups, int
 	if (hipGetDevice(&dev) != hipSuccess) { bmh_set_error("%s: no HIP device", fn); return BMH_ENODEV; }
 	const bool cm = h->a.po.copy_comment != 0;
 	// the state of the loader: the group being read, its pump, the index of its next read; what the pumps counted
-	struct loader_t { bmh_reads_pump_t *P = nullptr; int g = 0; int64_t id0 = 0; uint64_t cnt[4] = {0, 0, 0, 0}, icnt[2] = {0, 0}, bcnt[2] = {0, 0}; } ld;
+	struct loader_t { bmh_reads_pump_t *P = nullptr; int g = 0; int64_t id0 = 0; uint64_t cnt[4] = {0, 0, 0, 0}, icnt[2] = {0, 0}, bcnt[2] = {0, 0}, ccnt[5] = {0, 0, 0, 0, 0}; } ld;
 	auto named = [&](int g) { const std::string m = bmh_last_error(); bmh_set_error("read group '%s': %s", groups[g].id, m.c_str()); return (int)BMH_EINVAL; };
 	auto close_pump = [&]() {
 		if (!ld.P) return;
@@ -1617,11 +1624,13 @@ int bmh_aligner_run_groups(bmh_aligner_t *h, const bmh_read_group_t *groups, int
 		bmh_pump_counts(ld.P, c); bmh_pump_inflate_counts(ld.P, ic); bmh_pump_bam_counts(ld.P, bc);
 		for (int k = 0; k < 4; ++k) ld.cnt[k] += c[k];
 		for (int k = 0; k < 2; ++k) { ld.icnt[k] += ic[k]; ld.bcnt[k] += bc[k]; }
+		uint64_t cc[5]; bmh_pump_collate_counts(ld.P, cc);             // (counts add up over the groups, peaks are the largest)
+		ld.ccnt[0] += cc[0]; ld.ccnt[1] += cc[1]; ld.ccnt[2] = std::max(ld.ccnt[2], cc[2]); ld.ccnt[3] = std::max(ld.ccnt[3], cc[3]); ld.ccnt[4] += cc[4];
 		bmh_pump_close(ld.P); ld.P = nullptr;
 	};
 	// group g's pump; *pairs: does the group hold pairs (two files, a BAM with flag 0x1, else what `paired` says)
 	auto open_pump = [&](int g, int *pairs) -> int {
-		ld.P = bmh_pump_open(groups[g].path1, groups[g].path2, n_threads, cm, false, 0);
+		ld.P = bmh_pump_open(groups[g].path1, groups[g].path2, n_threads, cm, false, (size_t)std::max(0, bmh_tune("READS_CHUNK_BYTES", 0)), false, false, h->collate && !groups[g].path2, h->collate_mem);     // (a group of text files is taken as ever)
 		if (!ld.P) return named(g);
 		const int bam_pairs = bmh_pump_bam_paired(ld.P);
 		if (bam_pairs == 0 && paired) { bmh_set_error("read group '%s': reads file: %s: paired reads were asked for and the BAM's records do not carry flag 0x1", groups[g].id, groups[g].path1); return BMH_EINVAL; }
@@ -1662,7 +1671,7 @@ int bmh_aligner_run_groups(bmh_aligner_t *h, const bmh_read_group_t *groups, int
 	rc = run_loaded(h, fn, dev, fill, true, run_pairs, n_lanes, n_threads, sink, user, stats);
 	A.group_ids.clear(); A.plan.table = bdp_table_t(); ++A.groups_serial;
 	close_pump();
-	bmh_reads_note_counts(ld.cnt); bmh_reads_note_inflate_counts(ld.icnt); bmh_reads_note_bam_counts(ld.bcnt);
+	bmh_reads_note_counts(ld.cnt); bmh_reads_note_inflate_counts(ld.icnt); bmh_reads_note_bam_counts(ld.bcnt); bmh_reads_note_collate_counts(ld.ccnt);
 	return rc;
 }
 
@@ -1670,6 +1679,14 @@ int bmh_aligner_set_keep_rg(bmh_aligner_t *h, int on, bmh_rg_header_fn header, v
 {
 	if (!h) { bmh_set_error("bmh_aligner_set_keep_rg: null aligner"); return BMH_EINVAL; }
 	h->keep_rg = on != 0; h->rg_header = on ? header : nullptr; h->rg_user = on ? user : nullptr;
+	return BMH_OK;
+}
+
+int bmh_aligner_set_collate(bmh_aligner_t *h, int on, uint64_t mem_bytes)
+{
+	if (!h) { bmh_set_error("bmh_aligner_set_collate: null aligner"); return BMH_EINVAL; }
+	if (!on && mem_bytes) { bmh_set_error("bmh_aligner_set_collate: a cap of %llu bytes (--collate-mem) without --collate: the cap is that of the collation's open records", (unsigned long long)mem_bytes); return BMH_EINVAL; }
+	h->collate = on != 0; h->collate_mem = mem_bytes;
 	return BMH_OK;
 }
 

@@ -286,11 +286,16 @@ struct bdp_bc_t { uint32_t mode; uint8_t t0, t1, pack; };
 static_assert(sizeof(bdp_bc_t) == 8, "the barcode source is 8 bytes");
 
 // the barcode word of a value of n bytes: 64-bit FNV-1a, one walk over the bytes; 0 is no barcode, so an empty value gives 0 and a value that hashes to 0 gives 1
+BSR_FN uint64_t bdp_fnv1a64(const uint8_t *v, uint64_t n)       // (the hash alone: csrc/bam_collate_core.h keys read names with it)
+{
+	uint64_t h = 0xcbf29ce484222325ull;
+	for (uint64_t i = 0; i < n; ++i) h = (h ^ v[i]) * 0x100000001b3ull;
+	return h;
+}
 BSR_FN uint64_t bdp_barcode_word(const uint8_t *v, uint64_t n)
 {
 	if (!n) return 0;
-	uint64_t h = 0xcbf29ce484222325ull;
-	for (uint64_t i = 0; i < n; ++i) h = (h ^ v[i]) * 0x100000001b3ull;
+	const uint64_t h = bdp_fnv1a64(v, n);
 	return h ? h : 1ull;
 }
 

@@ -107,7 +107,12 @@ struct bmh_reads_pump_t;
 struct bmh_rg_table_t;
 typedef std::function<int(uint64_t n_reads, uint64_t n_bases, uint64_t n_name_bytes, uint64_t n_comment_bytes, bool fq, bmh_read_set_t *rs)> bmh_batch_alloc_t;
 // keep_rg / markdup: the input must be one BAM, its header's @RG lines become the run's read groups (bmh_pump_read_groups) and every read carries its own (rs->groups)
-bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_threads, bool comments, bool host_only, size_t chunk_bytes, bool keep_rg = false, bool markdup = false);
+// collate: a BAM's mates are collated by name (csrc/bam_collate_core.h), collate_mem: the cap on its open records' bytes (0: 8 GiB); text input ignores both -- the
+// caller that must refuse it asks bmh_pump_bam_paired
+bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_threads, bool comments, bool host_only, size_t chunk_bytes, bool keep_rg = false, bool markdup = false,
+                                bool collate = false, uint64_t collate_mem = 0);
+void bmh_pump_collate_counts(const bmh_reads_pump_t *p, uint64_t out[5]);   // of a pump that collates, else zeros
+bool bmh_pump_collate_ended_open(const bmh_reads_pump_t *p);                // its refusal was that of a record still open at the file's end
 const bmh_rg_table_t *bmh_pump_read_groups(const bmh_reads_pump_t *p);   // of a pump opened with keep_rg, else NULL
 int bmh_pump_next(bmh_reads_pump_t *p, uint64_t want_bases, uint64_t want_reads, bool even, bool take_all, const bmh_batch_alloc_t &alloc, bmh_read_set_t *rs);
 void bmh_pump_counts(const bmh_reads_pump_t *p, uint64_t out[4]);        // windows parsed on the device, windows walked on the host, text bytes, records
@@ -138,11 +143,25 @@ int bmh_bam_first_kept(const uint8_t *b, size_t n, uint32_t *flag);      // (-1:
 // what a BAM file's windows share.  paired: flag 0x1 of the first record kept; qual: 0 unknown, 1 the records have qualities, 2 they have none
 // rg_ids / rg_off: a run that keeps the input's read groups -- the IDs of the header's @RG lines back to back with offsets [n + 1] (bi_groups_t); empty: no tag is read.
 // Such a run writes every read's group index to rs->groups when the allocator has provided the array.
+// col: mates are collated by name (--collate; csrc/bam_collate_core.h has the definition) -- the pool of open records that both forms work on; NULL: a pair's two
+// records are adjacent, as ever.  It changes nothing for a file without flag 0x1.
+struct bcl_pool_t;
 struct bmh_bam_state_t {
 	std::string path; int paired = 0, qual = 0; uint64_t n_recs = 0, n_skipped = 0, n_tags_left_out = 0;
 	std::string rg_ids; std::vector<uint32_t> rg_off;
+	bcl_pool_t *col = nullptr;
 	bool keep_rg() const { return rg_off.size() > 1; }
+	bool collate() const { return col != nullptr && paired != 0; }
 };
+// the pool of a run that collates (mem_bytes 0: the default cap of 8 GiB; the hash width is the knob COLLATE_HASH_BITS), its end, and its counts (out[5]: pairs,
+// pairs_adjacent, open_records_peak, open_bytes_peak, windows_to_host_for_hash_runs).  bmh_bam_collate_end: the file has ended and every batch is delivered --
+// BMH_OK, or the refusal that names the open record with the smallest index
+bcl_pool_t *bmh_bam_collate_create(uint64_t mem_bytes);
+void bmh_bam_collate_free(bcl_pool_t *p);
+bool bmh_bam_collate_ended_open(const bcl_pool_t *p);                    // the refusal was bmh_bam_collate_end's (or the host form's, of a window's own open record); p may be NULL
+int bmh_bam_collate_end(const bmh_bam_state_t &st);
+void bmh_bam_collate_counts(const bcl_pool_t *p, uint64_t out[5]);
+void bmh_reads_note_collate_counts(const uint64_t *c);
 // The @RG lines of a BAM header's text (it ends at its first NUL; the last line may lack its newline; a CR before the newline is dropped; other lines are ignored):
 // lines verbatim without their line ends, their IDs, and every group's library index by first appearance (the LB field as bwamem_hip.aligner.rg_library reads it:
 // the last non-empty one, groups without one share "Unknown Library") with the libraries' names.  Refused (BMH_EINVAL, the line named, `what` in front): no @RG line, a line
@@ -161,7 +180,7 @@ struct bmh_bam_dev_t;
 bmh_bam_dev_t *bmh_bam_dev_create();
 void bmh_bam_dev_free(bmh_bam_dev_t *d);
 int bmh_bam_dev_run(bmh_bam_dev_t *d, const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bmh_batch_alloc_t &alloc, bmh_read_set_t *rs, bmh_bam_res_t &R);   // 1, 2: the window is the host's, < 0
-int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out, const char *const *rg_ids = nullptr, int n_groups = 0);   // csrc/reads_io.cpp: bmh_bam_reads_device / _host
+int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out, const char *const *rg_ids = nullptr, int n_groups = 0, uint64_t collate_mem = 0);   // csrc/reads_io.cpp: bmh_bam_reads_device / _host
 // the pump's answer for bmh_aligner_run_files: -1 the input is no BAM, else flag 0x1 of its first record kept
 int bmh_pump_bam_paired(const bmh_reads_pump_t *p);
 void bmh_pump_bam_counts(const bmh_reads_pump_t *p, uint64_t out[2]);    // records skipped (0x100 / 0x800), f and B tags left out

@@ -21,6 +21,7 @@
 #include <vector>
 #include "bmh_internal.h"
 #include "bam_in_core.h"
+#include "bam_collate_core.h"
 #include "../../include/bwamem_hip.h"
 
 namespace {
@@ -638,6 +639,29 @@ int bmh_bam_first_kept(const uint8_t *b, size_t n, uint32_t *flag)
 	return 0;
 }
 
+// ---- the pool of a run that collates mates by name (csrc/bam_collate_core.h)
+bcl_pool_t *bmh_bam_collate_create(uint64_t mem_bytes)
+{
+	bcl_pool_t *p = new bcl_pool_t();
+	if (mem_bytes) p->cap = mem_bytes;
+	p->hash_bits = std::min(64, std::max(1, bmh_tune("COLLATE_HASH_BITS", 64)));
+	return p;
+}
+void bmh_bam_collate_free(bcl_pool_t *p) { delete p; }
+bool bmh_bam_collate_ended_open(const bcl_pool_t *p) { return p && p->ended_open; }
+void bmh_bam_collate_counts(const bcl_pool_t *p, uint64_t out[5])
+{
+	out[0] = p->cnt.pairs; out[1] = p->cnt.pairs_adjacent; out[2] = p->cnt.open_records_peak; out[3] = p->cnt.open_bytes_peak; out[4] = p->cnt.windows_to_host_for_hash_runs;
+}
+int bmh_bam_collate_end(const bmh_bam_state_t &st)
+{
+	if (!st.collate() || st.col->n == 0) return BMH_OK;
+	const uint32_t s = (uint32_t)st.col->smallest();
+	st.col->ended_open = true;
+	bmh_set_error("reads file: %s: BAM record %llu (%s): flag 0x1 and no partner", st.path.c_str(), (unsigned long long)st.col->slots[s].index, st.col->name(s));
+	return BMH_EINVAL;
+}
+
 int bmh_bam_host_run(const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bmh_batch_alloc_t &alloc, bmh_read_set_t *rs, bmh_bam_res_t &R, bmh_hbatch_t &hb)
 {
 	hb.clear();
@@ -656,8 +680,7 @@ int bmh_bam_host_run(const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bm
 	const bool keep = st.keep_rg();
 	const bi_groups_t G = {(const uint8_t *)st.rg_ids.data(), st.rg_off.data(), keep ? (uint32_t)st.rg_off.size() - 1 : 0u};
 	auto gid = [&](uint32_t g) { return st.rg_ids.substr(st.rg_off[g], st.rg_off[g + 1] - st.rg_off[g]); };
-	auto append = [&](size_t k, const bi_rec_t &B, uint32_t hq, uint32_t g) {
-		const uint8_t *r = w.buf + starts[k];
+	auto append_rec = [&](const uint8_t *r, const bi_rec_t &B, uint32_t hq, uint32_t g) {
 		for (uint32_t t = 0; t < B.l_seq; ++t) hb.ascii.push_back(bi_base(r, B, t));
 		if (hq) for (uint32_t t = 0; t < B.l_seq; ++t) hb.quals.push_back(bi_qual(r, B, t));
 		hb.names.insert(hb.names.end(), r + BI_NAME_OFF, r + BI_NAME_OFF + B.l_name);
@@ -674,6 +697,11 @@ int bmh_bam_host_run(const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bm
 		}
 		acc += B.l_seq; ++cnt;
 	};
+	auto append = [&](size_t k, const bi_rec_t &B, uint32_t hq, uint32_t g) { append_rec(w.buf + starts[k], B, hq, g); };
+	// mates collated by name (csrc/bam_collate_core.h): the walk below asks `cw` what a kept record does -- it opens its name, or closes the record that did
+	bcl_pool_t *col = st.collate() ? st.col : nullptr;
+	bcl_pool_t no_pool;
+	bcl_walk_t cw(col ? *col : no_pool, w.buf, starts.data(), st.n_recs);
 	auto commit = [&](size_t k) {
 		R.consumed = starts[k + 1]; R.n_recs = k + 1; R.skipped = skipped; R.tags_left_out = left_out; R.qual = qual;
 		if (!w.take_all) {
@@ -704,6 +732,31 @@ int bmh_bam_host_run(const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bm
 		}
 		if (!st.paired) { append(i, B, hq, g); commit(i); continue; }
 		if (role == 3) { bmh_set_error("reads file: %s: BAM record %llu (%s): flag 0x1 with neither or both of 0x40 and 0x80", path, idx(i), name(i)); return BMH_EINVAL; }
+		if (col) {
+			bcl_partner_t pt;
+			const int ev = cw.step((uint32_t)i, role, &pt);
+			if (ev == BCL_OPENED) continue;
+			if (ev == BCL_OVER_CAP) {
+				bmh_set_error("reads file: %s: BAM record %llu: the open records (first mates that wait for their partners) hold more than --collate-mem %llu bytes", path, (unsigned long long)pt.index, (unsigned long long)col->cap);
+				return BMH_EINVAL;
+			}
+			if (ev == BCL_SAME_ROLE) { bmh_set_error("reads file: %s: BAM records %llu and %llu (%s) both carry flag %s", path, (unsigned long long)pt.index, idx(i), name(i), role == 1 ? "0x40" : "0x80"); return BMH_EINVAL; }
+			// the partner was checked when it was walked (in this window, or in the one it came to the pool from): its fields are read again, not refused again
+			bi_rec_t PB; uint32_t phq = 0, pg = 0;
+			(void)bi_check(pt.bytes, pt.size, &PB); (void)bi_check_kept(pt.bytes, PB, &phq);
+			if (keep) {
+				(void)bi_read_group(pt.bytes, PB, G, &pg);
+				if (pg != g) {
+					bmh_set_error("reads file: %s: BAM records %llu and %llu (%s) name different read groups (%s and %s): the two reads of a pair are of one", path, (unsigned long long)pt.index, idx(i), name(i), gid(pg).c_str(), gid(g).c_str());
+					return BMH_EINVAL;
+				}
+			}
+			if (role == 2) { append_rec(pt.bytes, PB, phq, pg); append(i, B, hq, g); }
+			else { append(i, B, hq, g); append_rec(pt.bytes, PB, phq, pg); }
+			cw.commit((uint32_t)i);
+			commit(i);
+			continue;
+		}
 		if (pend == (size_t)-1) { pend = i; pend_rec = B; pend_hq = hq; pend_g = g; continue; }
 		if (strcmp(name(pend), name(i)) != 0) {
 			bmh_set_error("reads file: %s: BAM records %llu and %llu carry different names (%s and %s): is the file grouped by read name?", path, idx(pend), idx(i), name(pend), name(i));
@@ -725,9 +778,15 @@ int bmh_bam_host_run(const bmh_bam_state_t &st, const bmh_bam_win_t &w, const bm
 		// what the file's end leaves over is refused once the reads before it have been delivered
 		if (cnt == 0 && chain_end < w.have) { bmh_set_error("reads file: %s: the file ends inside BAM record %llu", path, idx(nrec)); return BMH_EINVAL; }
 		if (cnt == 0 && pend != (size_t)-1) { bmh_set_error("reads file: %s: BAM record %llu (%s): flag 0x1 and no partner", path, idx(pend), name(pend)); return BMH_EINVAL; }
-		if (chain_end == w.have && pend == (size_t)-1) { R.consumed = chain_end; R.n_recs = nrec; R.skipped = skipped; R.tags_left_out = left_out; R.qual = qual; }
+		if (col && cnt == 0) {                               // every pair is delivered: what is open now stays open
+			if (col->n) return bmh_bam_collate_end(st);
+			const int64_t fo = cw.first_open();
+			if (fo >= 0) { col->ended_open = true; bmh_set_error("reads file: %s: BAM record %llu (%s): flag 0x1 and no partner", path, idx((size_t)fo), name((size_t)fo)); return BMH_EINVAL; }
+		}
+		if (chain_end == w.have && pend == (size_t)-1 && !(col && cw.open_behind_commit())) { R.consumed = chain_end; R.n_recs = nrec; R.skipped = skipped; R.tags_left_out = left_out; R.qual = qual; }
 	}
 	if (!(complete || w.take_all || R.final_) || cnt == 0) { hb.clear(); return 1; }
+	if (col) cw.deliver();
 	// (the records behind the last commit -- a first record whose partner the window does not hold -- were not appended: append runs at the commit only)
 	const bool fq = qual == 1;
 	memset(rs, 0, sizeof(*rs));
@@ -814,7 +873,7 @@ extern "C" int bmh_bam_header_read_groups(const char *text, uint64_t n_bytes, in
 }
 
 // bmh_bam_reads_device / bmh_bam_reads_host: the records are one window that ends the file, and every read of it is taken.  d: the device form, or NULL
-int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out, const char *const *rg_ids, int n_groups)
+int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, uint64_t n_bytes, int flags, bmh_read_set_t *out, const char *const *rg_ids, int n_groups, uint64_t collate_mem)
 {
 	memset(out, 0, sizeof(*out));
 	const bool keep = rg_ids != nullptr;
@@ -822,6 +881,9 @@ int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, 
 	if (n_bytes >= ((uint64_t)1 << 31) - 4096) { bmh_set_error("%s: 2^31 bytes of records or more (offsets inside a window are 32-bit)", fn); return BMH_EINVAL; }
 	const bool cm = (flags & BMH_READS_COMMENTS) != 0;
 	bmh_bam_state_t st;
+	struct pool_guard_t { bcl_pool_t *p = nullptr; ~pool_guard_t() { if (p) bmh_bam_collate_free(p); } } pool;
+	if (collate_mem && !(flags & BMH_READS_COLLATE)) { bmh_set_error("%s: a cap of %llu bytes on the collation's open records without BMH_READS_COLLATE", fn, (unsigned long long)collate_mem); return BMH_EINVAL; }
+	if (flags & BMH_READS_COLLATE) st.col = pool.p = bmh_bam_collate_create(collate_mem);
 	st.path = "(records in memory)";
 	if (keep) {
 		st.rg_off.push_back(0);
@@ -855,18 +917,23 @@ int bmh_bam_reads_run(const char *fn, bmh_bam_dev_t *d, const uint8_t *records, 
 	int rc = 2;
 	if (d) rc = bmh_bam_dev_run(d, st, w, alloc, &rs, R);
 	if (rc == 2) rc = bmh_bam_host_run(st, w, alloc, &rs, R, hb);
+	uint64_t skipped_behind = 0;
 	if (rc >= 0 && R.consumed < n_bytes) {                  // what the end leaves over (a cut record, a record without its partner) is refused by name
 		st.n_recs = R.n_recs; st.qual = R.qual;
 		w.buf = records + R.consumed; w.have = (size_t)n_bytes - R.consumed;
 		bmh_bam_res_t R2;
 		rc = bmh_bam_host_run(st, w, none, &rs, R2, hb);
-		if (rc >= 0) { bmh_set_error("%s: internal error: the bytes behind the last read were not refused", fn); rc = BMH_EINVAL; }
+		// (a run that collates stops at the record that completes its last pair: records skipped by their flag may follow it)
+		if (rc >= 0 && st.collate() && R2.consumed == w.have) skipped_behind = R2.skipped;
+		else if (rc >= 0) { bmh_set_error("%s: internal error: the bytes behind the last read were not refused", fn); rc = BMH_EINVAL; }
 	}
-	if (rc < 0) { bmh_reads_free(out); return rc; }
+	if (rc >= 0) rc = bmh_bam_collate_end(st) == BMH_OK ? rc : BMH_EINVAL;
+	{ uint64_t cc[5] = {0, 0, 0, 0, 0}; if (st.col) bmh_bam_collate_counts(st.col, cc); bmh_reads_note_collate_counts(cc); }      // (zeros after a call that did not collate)
+	if (rc < 0 && !(R.n_reads && bmh_bam_collate_ended_open(st.col))) { bmh_reads_free(out); return rc; }
 	if (R.n_reads) { out->n_reads = rs.n_reads; out->n_bases = rs.n_bases; out->n_name_bytes = rs.n_name_bytes; out->n_comment_bytes = rs.n_comment_bytes; }
-	const uint64_t bc[2] = {R.skipped, R.tags_left_out};
+	const uint64_t bc[2] = {R.skipped + skipped_behind, R.tags_left_out};
 	bmh_reads_note_bam_counts(bc);
-	return BMH_OK;
+	return rc < 0 ? rc : BMH_OK;                            // (< 0: an open record at the end of a run that collates -- *out holds the complete pairs before it)
 }
 
 extern "C" int bmh_bam_reads_groups_host(const uint8_t *records, uint64_t n_bytes, int flags, const char *const *rg_ids, int n_groups, bmh_read_set_t *out)

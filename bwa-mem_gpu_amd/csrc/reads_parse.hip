@@ -596,7 +596,7 @@ struct bmh_reads_pump_t {
 	bool bam = false; bmh_bam_state_t bs; bmh_bam_dev_t *bdev = nullptr;
 	std::vector<uint32_t> chain;                           // the record starts of S[0]'s window found so far; its last entry is where the walk stands
 	bool keep_rg = false, markdup = false; bmh_rg_table_t rg;      // a run that keeps the input's read groups: the header's @RG lines (bam_open), their IDs in bs
-	~bmh_reads_pump_t() { delete dev; if (bdev) bmh_bam_dev_free(bdev); }
+	~bmh_reads_pump_t() { delete dev; if (bdev) bmh_bam_dev_free(bdev); if (bs.col) bmh_bam_collate_free(bs.col); }
 };
 
 namespace {
@@ -659,7 +659,7 @@ int bam_next(bmh_reads_pump_t *P, uint64_t want_bases, uint64_t want_reads, bool
 	stream_t &S = P->S[0];
 	for (;;) {
 		RCK(bam_fill(P));
-		if (S.eof && S.have == 0) return 0;
+		if (S.eof && S.have == 0) return bmh_bam_collate_end(P->bs);      // (BMH_OK is 0: the end; a run that collates refuses the records still open)
 		const bmh_bam_win_t w = {S.buf, S.have, S.eof, P->comments, want_bases, want_reads, even, take_all, &P->chain};
 		bmh_bam_res_t R;
 		int rc = 2;
@@ -678,7 +678,7 @@ int bam_next(bmh_reads_pump_t *P, uint64_t want_bases, uint64_t want_reads, bool
 				if (!take_all && !P->chunk) P->target = std::min(MAX_WINDOW, R.consumed + R.consumed / 16 + (1u << 16));
 				return 1;
 			}
-			if (S.eof && S.have == 0) return 0;
+			if (S.eof && S.have == 0) return bmh_bam_collate_end(P->bs);
 			if (R.consumed > 0 || (!S.eof && S.have < P->target)) continue;
 		}
 		// the window holds no complete batch (or not one whole record): a larger one
@@ -690,7 +690,15 @@ int bam_next(bmh_reads_pump_t *P, uint64_t want_bases, uint64_t want_reads, bool
 
 const bmh_rg_table_t *bmh_pump_read_groups(const bmh_reads_pump_t *p) { return p->keep_rg ? &p->rg : nullptr; }
 
-bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_threads, bool comments, bool host_only, size_t chunk_bytes, bool keep_rg, bool markdup)
+void bmh_pump_collate_counts(const bmh_reads_pump_t *p, uint64_t out[5])
+{
+	memset(out, 0, 5 * sizeof(uint64_t));
+	if (p->bs.col) bmh_bam_collate_counts(p->bs.col, out);
+}
+
+bool bmh_pump_collate_ended_open(const bmh_reads_pump_t *p) { return bmh_bam_collate_ended_open(p->bs.col); }
+
+bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_threads, bool comments, bool host_only, size_t chunk_bytes, bool keep_rg, bool markdup, bool collate, uint64_t collate_mem)
 {
 	bmh_reads_pump_t *P = new bmh_reads_pump_t();
 	P->keep_rg = keep_rg; P->markdup = markdup;
@@ -715,6 +723,7 @@ bmh_reads_pump_t *bmh_pump_open(const char *path1, const char *path2, int n_thre
 		// BAM always takes the host inflate, also with BMH_INFLATE_DEVICE=1: the record starts are a chain the host walks over the window it has just inflated
 		P->S[0].on_dev = false;
 		if (!host_only) P->bdev = bmh_bam_dev_create();
+		if (collate) P->bs.col = bmh_bam_collate_create(collate_mem);
 		if (bam_open(P) != BMH_OK) { delete P; return nullptr; }
 		return P;
 	}
@@ -815,7 +824,17 @@ int bmh_pump_next(bmh_reads_pump_t *P, uint64_t want_bases, uint64_t want_reads,
 }
 
 // ---- the whole of one or two files as a read set
-namespace { uint64_t g_last_counts[4] = {0, 0, 0, 0}, g_last_inflate[2] = {0, 0}, g_last_bam[2] = {0, 0}; std::mutex g_counts_mu; }
+namespace { uint64_t g_last_counts[4] = {0, 0, 0, 0}, g_last_inflate[2] = {0, 0}, g_last_bam[2] = {0, 0}, g_last_collate[5] = {0, 0, 0, 0, 0}; std::mutex g_counts_mu; }
+
+extern "C" int bmh_reads_last_collate_counts(bmh_collate_counts_t *out)
+{
+	if (!out) return BMH_EINVAL;
+	std::lock_guard<std::mutex> lk(g_counts_mu);
+	out->pairs = g_last_collate[0]; out->pairs_adjacent = g_last_collate[1]; out->open_records_peak = g_last_collate[2]; out->open_bytes_peak = g_last_collate[3];
+	out->windows_to_host_for_hash_runs = g_last_collate[4];
+	return BMH_OK;
+}
+void bmh_reads_note_collate_counts(const uint64_t *c) { std::lock_guard<std::mutex> lk(g_counts_mu); memcpy(g_last_collate, c, sizeof(g_last_collate)); }
 
 extern "C" int bmh_reads_last_bam_counts(uint64_t *out) { if (!out) return BMH_EINVAL; std::lock_guard<std::mutex> lk(g_counts_mu); memcpy(out, g_last_bam, sizeof(g_last_bam)); return BMH_OK; }
 void bmh_reads_note_bam_counts(const uint64_t *c) { std::lock_guard<std::mutex> lk(g_counts_mu); memcpy(g_last_bam, c, sizeof(g_last_bam)); }
@@ -826,21 +845,30 @@ void bmh_reads_note_inflate_counts(const uint64_t *c) { std::lock_guard<std::mut
 extern "C" int bmh_reads_last_counts(uint64_t *out) { if (!out) return BMH_EINVAL; std::lock_guard<std::mutex> lk(g_counts_mu); memcpy(out, g_last_counts, sizeof(g_last_counts)); return BMH_OK; }
 void bmh_reads_note_counts(const uint64_t *c) { std::lock_guard<std::mutex> lk(g_counts_mu); memcpy(g_last_counts, c, sizeof(g_last_counts)); }
 
-extern "C" int bmh_reads_load_files(const char *path1, const char *path2, int n_threads, int flags, bmh_read_set_t *out)
+extern "C" int bmh_reads_load_files(const char *path1, const char *path2, int n_threads, int flags, bmh_read_set_t *out) { return bmh_reads_load_files_ex(path1, path2, n_threads, flags, 0, out); }
+
+extern "C" int bmh_reads_load_files_ex(const char *path1, const char *path2, int n_threads, int flags, uint64_t collate_mem, bmh_read_set_t *out)
 {
 	if (!path1 || !out) { bmh_set_error("bmh_reads_load_files: null argument"); return BMH_EINVAL; }
 	memset(out, 0, sizeof(*out));
-	const bool cm = (flags & BMH_READS_COMMENTS) != 0, host = (flags & BMH_READS_HOST) != 0;
+	const bool cm = (flags & BMH_READS_COMMENTS) != 0, host = (flags & BMH_READS_HOST) != 0, collate = (flags & BMH_READS_COLLATE) != 0, keep = (flags & BMH_READS_KEEP_RG) != 0;
+	if (collate_mem && !collate) { bmh_set_error("bmh_reads_load_files: a cap of %llu bytes on the collation's open records without BMH_READS_COLLATE", (unsigned long long)collate_mem); return BMH_EINVAL; }
 	if (!host) { int nd = 0; if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) { (void)hipGetLastError(); bmh_set_error("bmh_reads_load_files: no HIP device (BMH_READS_HOST parses on the host)"); return BMH_ENODEV; } }
-	bmh_reads_pump_t *P = bmh_pump_open(path1, path2, n_threads, cm, host, (size_t)std::max(0, bmh_tune("READS_CHUNK_BYTES", 0)));
+	bmh_reads_pump_t *P = bmh_pump_open(path1, path2, n_threads, cm, host, (size_t)std::max(0, bmh_tune("READS_CHUNK_BYTES", 0)), keep, false, collate, collate_mem);
 	if (!P) return BMH_EINVAL;
-	std::vector<uint8_t> ascii, codes, quals, names, comments; std::vector<uint64_t> offs, noffs, coffs; std::vector<uint32_t> lens;
+	if (collate && bmh_pump_bam_paired(P) < 0) {
+		bmh_pump_close(P);
+		bmh_set_error("reads file: %s: mates are collated by name (--collate) in BAM input only: text input is taken in the order of its records", path1);
+		return BMH_EINVAL;
+	}
+	std::vector<uint8_t> ascii, codes, quals, names, comments; std::vector<uint64_t> offs, noffs, coffs; std::vector<uint32_t> lens, groups;
 	bool fq_any = false;
 	uint64_t r0 = 0, b0 = 0, n0 = 0, c0 = 0;
 	bmh_batch_alloc_t alloc = [&](uint64_t nr, uint64_t nb, uint64_t nn, uint64_t nc, bool fq, bmh_read_set_t *rs) {
 		r0 = lens.size(); b0 = ascii.size(); n0 = names.size(); c0 = comments.size();
 		ascii.resize(b0 + nb); codes.resize(b0 + nb); if (fq) quals.resize(b0 + nb); names.resize(n0 + nn); if (cm) { comments.resize(c0 + nc); coffs.resize(r0 + nr); }
 		offs.resize(r0 + nr); noffs.resize(r0 + nr); lens.resize(r0 + nr);
+		if (keep) { groups.resize(r0 + nr); rs->groups = groups.data() + r0; }
 		fq_any = fq_any || fq;
 		rs->ascii = ascii.data() + b0; rs->codes = codes.data() + b0; rs->quals = fq ? quals.data() + b0 : nullptr; rs->names = names.data() + n0;
 		rs->offs = offs.data() + r0; rs->name_offs = noffs.data() + r0; rs->lens = lens.data() + r0;
@@ -857,7 +885,9 @@ extern "C" int bmh_reads_load_files(const char *path1, const char *path2, int n_
 	uint64_t cnt[4]; bmh_pump_counts(P, cnt); bmh_reads_note_counts(cnt);
 	uint64_t icnt[2]; bmh_pump_inflate_counts(P, icnt); bmh_reads_note_inflate_counts(icnt);
 	uint64_t bcnt[2]; bmh_pump_bam_counts(P, bcnt); bmh_reads_note_bam_counts(bcnt);
-	const bool partial = rc < 0 && strstr(bmh_last_error(), " ends before ") != nullptr;       // the complete pairs come back with the refusal
+	uint64_t ccnt[5]; bmh_pump_collate_counts(P, ccnt); bmh_reads_note_collate_counts(ccnt);
+	// the complete pairs come back with the refusal: a file that ends before the other, and with --collate a record that is still open at the file's end
+	const bool partial = rc < 0 && (strstr(bmh_last_error(), " ends before ") != nullptr || (!lens.empty() && bmh_pump_collate_ended_open(P)));
 	bmh_pump_close(P);
 	if (rc < 0 && !partial) return rc;
 	const uint64_t nr = lens.size(), nb = ascii.size(), nn = names.size(), nm = comments.size();
@@ -867,6 +897,7 @@ extern "C" int bmh_reads_load_files(const char *path1, const char *path2, int n_
 	bool ok = out->ascii && out->codes && out->offs && out->lens && out->names && out->name_offs;
 	if (fq_any) { out->quals = (uint8_t *)malloc(nb + 1); ok = ok && out->quals; }
 	if (cm) { out->n_comment_bytes = nm; out->comments = (uint8_t *)malloc(nm + 1); out->comment_offs = (uint64_t *)malloc(8 * (nr + 1)); ok = ok && out->comments && out->comment_offs; }
+	if (keep) { out->groups = (uint32_t *)malloc(4 * (nr + 1)); ok = ok && out->groups; if (out->groups) memcpy(out->groups, groups.data(), 4 * nr); }
 	if (!ok) { bmh_reads_free(out); bmh_set_error("bmh_reads_load_files: out of memory"); return BMH_ENOMEM; }
 	memcpy(out->ascii, ascii.data(), nb); memcpy(out->codes, codes.data(), nb); out->ascii[nb] = out->codes[nb] = 0;
 	memcpy(out->offs, offs.data(), 8 * nr); memcpy(out->lens, lens.data(), 4 * nr); memcpy(out->names, names.data(), nn); out->names[nn] = 0; memcpy(out->name_offs, noffs.data(), 8 * nr);

@@ -522,6 +522,40 @@ int bmh_bam_reads_groups_device(const uint8_t *records, uint64_t n_bytes, int fl
 int bmh_bam_reads_groups_host(const uint8_t *records, uint64_t n_bytes, int flags, const char *const *rg_ids, int n_groups, bmh_read_set_t *out);
 int bmh_bam_header_read_groups(const char *text, uint64_t n_bytes, int markdup, char **lines, uint64_t *lines_bytes, int32_t **lib, int32_t *n_groups);
 int bmh_reads_last_bam_counts(uint64_t *out);
+/* ---- Mates collated by name (--collate; csrc/bam_collate_core.h has the definition): a paired BAM in any record order -- a coordinate-sorted one, the aligner's
+ * own --sort output among them -- is taken as read input.  Off by default, and with it off every path is what it was.  Kept records (no flag 0x100 / 0x800) are
+ * taken in file order, numbered as the messages number them, and every check made on a kept record still applies.  A record whose name (all its bytes up to the
+ * NUL) is open closes that record: the two are a pair, the 0x40 record read 2k and the 0x80 record read 2k+1, completed at the later record; two records of one
+ * role under one open name are refused, naming both.  Any other record opens its name.  The reads are the pairs in the order of their completion and batches are
+ * cut over that sequence by the usual rule, so the read set, the cuts and the SAM depend on the file and the batch size alone -- never on the windows -- and equal
+ * those of a run without the option on the name-grouped BAM that holds the same pairs in that order.  Records skipped by their flag open and close nothing.  At
+ * the file's end, after every complete batch, an open record is refused ("flag 0x1 and no partner", the smallest index named; bmh_reads_load_files and
+ * bmh_bam_reads_* then leave the complete pairs in *out).  With the input's read groups kept, a pair of two groups is refused naming both records.  A single-end
+ * BAM gives what it gives without the option; text input is refused.
+ * A window is consumed up to the record that completes the last pair of its batch; the open records inside that prefix move into a pool in host memory (their
+ * bytes, each with its file index), which the host form and the device form share.  The device keeps the pool's keys only (name hash, role, slot): per window it
+ * hashes the kept records' names (64-bit FNV-1a), sorts them with the pool's keys (rocPRIM), matches runs of equal hashes (names compared byte by byte), ranks the
+ * pairs by a scan over the completions, and hands the prefix's open records back as an index list; a pool record that a window record closes is copied behind the
+ * window's bytes by the host and decoded like any other record, so the extended window stays below 2^31 bytes.  A run of equal hashes that is not one 0x40 and one
+ * 0x80 record of one name hands the window to the host form (counted: windows_to_host_for_hash_runs).  The knob COLLATE_HASH_BITS (bmh_tune_set; default 64) cuts
+ * the hash to its low bits, for tests that force equal hashes.
+ * The open records' bytes (4 + block_size each) are capped: mem_bytes, 0 for the default of 8 GiB.  They are held against the cap at every completion; beyond it
+ * the run stops after the batches before it have been written, naming the option, the cap and the record.  Nothing is spilled to disk.  The 2^31-byte limit on one
+ * window stays: a file in which one batch's pairs complete only across more than 2^31 bytes of records is refused.
+ * The cap counts the records' bytes alone: the pool's bookkeeping (a slot, a vector and a name key per open record, on the order of 150 bytes) comes on top.
+ * bmh_reads_load_files_ex / bmh_bam_reads_ex: the readers with every option -- collate_mem is that cap (0: the default; refused without BMH_READS_COLLATE);
+ * bmh_bam_reads_ex takes BMH_READS_HOST for the host form and rg_ids (or NULL) as bmh_bam_reads_groups_* take them.  BMH_READS_KEEP_RG: bmh_reads_load_files reads
+ * a BAM under its own read groups as bmh_aligner_set_keep_rg does -- the header's @RG lines are the table, out->groups [n_reads] the index of every read's line.
+ * BMH_READS_COLLATE: the flag bit of bmh_reads_load_files, bmh_bam_reads_device / _host and their _groups forms.  bmh_aligner_set_collate: for bmh_aligner_run_files
+ * (text input is then refused) and every group of bmh_aligner_run_groups whose input is a BAM; mem_bytes without `on` is refused.  bmh_reads_last_collate_counts:
+ * of the process's last such call -- pairs, those whose two records were adjacent, the peaks of the open records and their bytes, windows handed to the host form
+ * for a run of equal hashes. */
+#define BMH_READS_COLLATE 4
+#define BMH_READS_KEEP_RG 8
+int bmh_reads_load_files_ex(const char *path1, const char *path2, int n_threads, int flags, uint64_t collate_mem, bmh_read_set_t *out);
+int bmh_bam_reads_ex(const uint8_t *records, uint64_t n_bytes, int flags, const char *const *rg_ids, int n_groups, uint64_t collate_mem, bmh_read_set_t *out);
+typedef struct { uint64_t pairs, pairs_adjacent, open_records_peak, open_bytes_peak, windows_to_host_for_hash_runs; } bmh_collate_counts_t;
+int bmh_reads_last_collate_counts(bmh_collate_counts_t *out);
 
 /* ---- BGZF members inflated on the device (csrc/inflate_core.h, csrc/inflate_kernels.hip): all of RFC 1951, one lane per member, the CRC32 of the text
  * computed and compared there too.  BGZF (what bgzip writes) is a series of gzip members of at most 64 KiB of text, each naming its own size in the extra
@@ -948,6 +982,7 @@ int bmh_bam_markdup_device(const uint8_t *records, uint64_t n_bytes, const bmh_m
 int bmh_bam_markdup_host(const uint8_t *records, uint64_t n_bytes, const bmh_markdup_opt_t *opt, uint8_t **out, bmh_markdup_counts_t *res);
 int bmh_aligner_set_markdup(bmh_aligner_t *a, int on);
 int bmh_aligner_set_bam_pairs(bmh_aligner_t *a, uint64_t batch_bases, int n_lanes);        /* (described with bmh_bam_reads_device above) */
+int bmh_aligner_set_collate(bmh_aligner_t *a, int on, uint64_t mem_bytes);                  /* (described with bmh_reads_last_collate_counts above) */
 /* Keep the input's read groups (off by default; with it off nothing about a run changes).  bmh_aligner_run_files then takes one BAM -- a regular file or a pipe --
  * whose header's @RG lines are the run's read groups, in file order (bmh_bam_header_read_groups' rules and refusals), and every read's records carry RG:Z:<the ID its
  * own record names> where popt->rg_id's tag goes: the decoder gives every read its group (bmh_bam_reads_groups_device's rules and refusals), a batch holds reads of

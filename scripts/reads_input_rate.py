@@ -18,6 +18,10 @@ kernel trace in a run of its own (rocprofv3 --kernel-trace --stats -- python scr
 kernel alone runs on the first 1024, 4096, 16384 ... and on all of them, several launches each (rocprofv3 --kernel-trace --stats -- python
 scripts/reads_input_rate.py --inflate-only); beside it zlib on the same members on the host's threads, the yardstick, and the library's own host decoder.
 
+--collate (paired mode) adds two rows: the aligner's own coordinate-sorted BAM of the run's pairs realigned with mates collated by name
+(align_files_bam_sorted_collate: bmh_aligner_set_collate) beside the name-grouped BAM of the same pairs in the order the collation gives them
+(align_files_bam_grouped: the code path of a run without the option); --modes pe --reads 500000 --collate --configs align_files_bam_grouped,align_files_bam_sorted_collate
+is one million pairs.
 --bam-only times nothing else than the BAM input path: the host's chain walk over the records alone, then loads of the BAM file for a kernel trace.
 
     python scripts/reads_input_rate.py [--genome-mbp 3100] [--reads 1000000] [--runs 3] [--modes se,pe] [--parent DIR] [--out profiles/reads_input.json]
@@ -106,6 +110,34 @@ BAM_TEXT = b"@HD\tVN:1.6\tSO:unsorted\n"
 BAM_HEADER = b"BAM\1" + struct.pack("<I", len(BAM_TEXT)) + BAM_TEXT + struct.pack("<I", 0)      # no reference sequences: the reads are unaligned
 BAM_RG_TEXT = BAM_TEXT + b"".join(b"@RG\tID:g%d\tLB:lib%d\tSM:s\n" % (k, k // 2) for k in range(4))      # four groups in two libraries
 BAM_RG_HEADER = b"BAM\1" + struct.pack("<I", len(BAM_RG_TEXT)) + BAM_RG_TEXT + struct.pack("<I", 0)
+
+
+def bgzf_members(blob: bytes):
+    """the inflated text of every member of a BGZF stream whose members carry the BC field alone (what write_bgzf and the library write)"""
+    p = 0
+    while p < len(blob):
+        size = struct.unpack_from("<H", blob, p + 16)[0] + 1
+        yield zlib.decompress(blob[p + 18:p + size - 8], -15)
+        p += size
+
+
+def grouped_records(records: bytes) -> bytes:
+    """--collate's definition over BAM records: the kept records of the pairs in the order in which their later record comes, the 0x40 record first"""
+    open_, out, p = {}, [], 0
+    while p < len(records):
+        n = 4 + struct.unpack_from("<I", records, p)[0]
+        flag = struct.unpack_from("<H", records, p + 18)[0]
+        if not flag & 0x900:
+            nm = records[p + 36:p + 36 + records[p + 12]]
+            q = open_.pop(nm, None)
+            if q is None:
+                open_[nm] = (p, n)
+            else:
+                a, b = records[q[0]:q[0] + q[1]], records[p:p + n]
+                out += [a, b] if flag & 0x80 else [b, a]
+        p += n
+    assert not open_, "the sorted BAM holds records without partner"
+    return b"".join(out)
 
 
 def measure(fn, runs: int, n4: int) -> dict:
@@ -254,6 +286,7 @@ def main():
     ap.add_argument("--parser-only", action="store_true")
     ap.add_argument("--inflate-only", action="store_true")
     ap.add_argument("--bam-only", action="store_true")
+    ap.add_argument("--collate", action="store_true", help="paired mode: the rows align_files_bam_grouped and align_files_bam_sorted_collate")
     ap.add_argument("--configs", default="", help="only these rows (comma-separated keys, e.g. align_files_bgzf,align_files_bam); default: all")
     ap.add_argument("--out-key", default="", help="with --out: the result goes into the existing JSON of that file under this key; the rest of the file stays")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)          # the plain file the --parent child aligns (mode and sizes from the other options)
@@ -352,6 +385,31 @@ def main():
                    "align_files_bam": lambda: nat.run_files(p("bam"), None, paired, sink, **kw),
                    "align_files_bam_rg_plain": lambda: nat.run_files(p("rg.bam"), None, paired, sink, **kw),
                    "align_files_bam_keep_rg": lambda: keep_rg(lambda: nat.run_files(p("rg.bam"), None, paired, sink, **kw))}
+        if paired and a.collate:
+            # the aligner's own sorted BAM of these pairs (its members as the sink receives them, behind a header), and the name-grouped BAM of the same pairs
+            from bwamem_hip.lib import bgzf_eof, reads_last_collate_counts
+            parts = []
+            nat.set_output("bam_sorted", 1)
+            try:
+                nat.run_files(p("bam"), None, True, lambda mv: parts.append(bytes(mv)), **kw)
+            finally:
+                nat.set_output("sam", 1)
+            stream = b"".join(parts)
+            del parts
+            write_bgzf(p("sorted.bam"), BAM_HEADER)
+            with open(p("sorted.bam"), "r+b") as f:
+                f.seek(-28, 2); f.write(stream + bgzf_eof())
+            write_bgzf(p("grouped.bam"), BAM_HEADER + grouped_records(b"".join(bgzf_members(stream))))
+            del stream
+
+            def collate(fn):
+                nat.set_collate(True)
+                try:
+                    return fn()
+                finally:
+                    nat.set_collate(False)
+            configs.update({"align_files_bam_grouped": lambda: nat.run_files(p("grouped.bam"), None, True, sink, **kw),
+                            "align_files_bam_sorted_collate": lambda: collate(lambda: nat.run_files(p("sorted.bam"), None, True, sink, **kw))})
         if paired:
             configs.update({"align_files_two_plain": lambda: nat.run_files(p("r1.fq"), p("r2.fq"), True, sink, **kw),
                             "align_files_two_bgzf": lambda: nat.run_files(p("r1.bgzf"), p("r2.bgzf"), True, sink, **kw),
@@ -373,7 +431,13 @@ def main():
         for key, fn in configs.items():
             rows[key] = measure(lambda: (bytes_out.__setitem__(0, 0), fn()), a.runs, n4)
             rows[key]["sam_bytes"] = int(bytes_out[0])
-            if key != "align_files_bam_keep_rg":                   # (its records carry RG:Z tags: more text)
+            if key in ("align_files_bam_grouped", "align_files_bam_sorted_collate"):      # (the pairs in another order: the two write the same text as each other)
+                rows[key]["file_bytes"] = os.path.getsize(p("grouped.bam" if key.endswith("grouped") else "sorted.bam"))
+                if key.endswith("collate"):
+                    rows[key]["collate"] = reads_last_collate_counts()
+                    if "align_files_bam_grouped" in rows:
+                        assert rows[key]["sam_bytes"] == rows["align_files_bam_grouped"]["sam_bytes"], "the collated run and the grouped run wrote different amounts of text"
+            elif key != "align_files_bam_keep_rg":                 # (its records carry RG:Z tags: more text)
                 sizes.add(bytes_out[0])
             if key != "align_file_plain":
                 rows[key]["parser"] = reads_last_counts()
@@ -382,7 +446,8 @@ def main():
             if key == "align_files_bam":
                 rows[key]["file_bytes"] = os.path.getsize(p("bam")); rows[key]["bgzf_fastq_file_bytes"] = os.path.getsize(p("fq.bgzf"))
             print(mode, key, json.dumps(rows[key]), flush=True)
-        assert len(sizes) == 1, ("the configurations wrote different amounts of text", sizes)
+        compared = [k for k in rows if k not in ("parent_align_file_plain", "align_files_bam_keep_rg", "align_files_bam_grouped", "align_files_bam_sorted_collate")]
+        assert len(sizes) == (1 if compared else 0), ("the configurations wrote different amounts of text", sizes)
         nat.free()
         for f in os.listdir(tmp):
             os.remove(os.path.join(tmp, f))
