@@ -14,6 +14,8 @@ a FASTA file still gives QUAL '*'.
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import inspect
 import os
 
 import numpy as np
@@ -341,6 +343,96 @@ def markdup_metrics_text(counts: dict, rg_line: str = "") -> str:
             ("UNMAPPED_READS", counts["unmapped_records"]), ("UNPAIRED_READ_DUPLICATES", df), ("READ_PAIR_DUPLICATES", dp),
             ("PERCENT_DUPLICATION", "%.6f" % ((df + 2 * dp) / den) if den else "0")]
     return "## METRICS CLASS\tbwamem_hip.DuplicationMetrics\n" + "\t".join(c for c, _v in cols) + "\n" + "\t".join(str(v) for _c, v in cols) + "\n"
+
+
+COVERAGE_TABLE_HEADER = "#rname\tstartpos\tendpos\tnumreads\tcovbases\tcoverage\tmeandepth\tmaxdepth\tmeanmapq"
+
+
+def coverage_table_text(cov: dict, contigs) -> str:
+    """the table of `samtools coverage`: a header line, one row per contig in header order and a last row `total` -- name, 1, length, counted reads, covered
+    bases, their percentage, mean depth, largest depth, mean mapq (the three with %.6g; a mean is 0 where its divisor is 0)"""
+    def row(name, length, reads, covb, sumd, maxd, mapq):
+        return "%s\t1\t%d\t%d\t%d\t%.6g\t%.6g\t%d\t%.6g" % (name, length, reads, covb, 100.0 * covb / length if length else 0.0, sumd / length if length else 0.0, maxd,
+                                                         mapq / reads if reads else 0.0)
+    lines = [COVERAGE_TABLE_HEADER]
+    for c, (name, length) in enumerate(contigs):
+        lines.append(row(name, int(length), int(cov["n_reads"][c]), int(cov["cov_bases"][c]), int(cov["sum_depth"][c]), int(cov["max_depth"][c]), int(cov["sum_mapq"][c])))
+    tot = {k: int(sum(int(v) for v in cov[k])) for k in ("n_reads", "cov_bases", "sum_depth", "sum_mapq")}
+    lines.append(row("total", sum(int(l) for _n, l in contigs), tot["n_reads"], tot["cov_bases"], tot["sum_depth"], max([int(v) for v in cov["max_depth"]] or [0]), tot["sum_mapq"]))
+    return "\n".join(lines) + "\n"
+
+
+def coverage_hist_text(cov: dict) -> str:
+    """depth, bases, fraction_at_or_above (%.6f): 1001 rows, the last labelled 1000+"""
+    hist = [int(v) for v in cov["hist"]]
+    total, lines, above = sum(hist), ["depth\tbases\tfraction_at_or_above"], sum(hist)
+    for d, h in enumerate(hist):
+        lines.append("%s\t%d\t%.6f" % ("1000+" if d == len(hist) - 1 else str(d), h, above / total if total else 0.0))
+        above -= h
+    return "\n".join(lines) + "\n"
+
+
+def coverage_bed_text(cov: dict, contigs, bin: int) -> str:
+    """name, start, end, mean depth (%.2f): one row per bin of `bin` positions, empty ones too, a contig's last bin ending at its length"""
+    lines, k = [], 0
+    for name, length in contigs:
+        for a in range(0, int(length), bin):
+            b = min(a + bin, int(length))
+            lines.append("%s\t%d\t%d\t%.2f" % (name, a, b, int(cov["bin_sum"][k]) / (b - a)))
+            k += 1
+    assert k == len(cov["bin_sum"])
+    return "".join(l + "\n" for l in lines)
+
+
+COVERAGE_KEYWORDS = ("coverage", "coverage_hist", "coverage_bed", "coverage_bin", "coverage_min_mapq", "coverage_deletions")
+
+
+def _coverage_keywords(f):
+    """align_file / align_files / align_groups: the outermost call's coverage keywords are checked (coverage_request, with the call's `sort`) and kept in
+    self._cov_req for as long as the run; the calls the method makes on its way (they hand no coverage keyword on) find the request there"""
+    sig = inspect.signature(f)
+
+    @functools.wraps(f)
+    def call(self, *args, **kw):
+        if getattr(self, "_cov_req", None) is not None:
+            return f(self, *args, **kw)
+        given = sig.bind(self, *args, **kw)
+        given.apply_defaults()
+        req = coverage_request(f.__name__, given.arguments["sort"], *(given.arguments[k] for k in COVERAGE_KEYWORDS))
+        if req is None:
+            return f(self, *args, **kw)
+        self._cov_req = req
+        try:
+            return f(self, *args, **kw)
+        finally:
+            self._cov_req = None
+    return call
+
+
+def coverage_request(what: str, sort: bool, coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False):
+    """the coverage keywords of align_file / align_files / align_groups, checked -> None (none given) or a dict of them; ValueError otherwise"""
+    outs = coverage is not None or coverage_hist is not None or coverage_bed is not None
+    mods = coverage_bin is not None or coverage_min_mapq is not None or bool(coverage_deletions)
+    if not outs and not mods:
+        return None
+    if not sort:
+        raise ValueError(f"{what}: the coverage options need sort=True: depth is computed where the sorted file is written")
+    if (coverage_bed is None) != (coverage_bin is None):
+        raise ValueError(f"{what}: coverage_bed and coverage_bin go together (the bins of the BED file)")
+    if not outs:
+        raise ValueError(f"{what}: coverage_min_mapq and coverage_deletions need coverage, coverage_hist or coverage_bed (they say what is counted, not where it goes)")
+    for nm, v, lo, hi in (("coverage_bin", coverage_bin, 1, 0xffffffff), ("coverage_min_mapq", coverage_min_mapq, 0, 255)):
+        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not lo <= v <= hi):
+            raise ValueError(f"{what}: {nm} {v!r}: an integer in {lo} .. {hi}")
+    return dict(table=coverage, hist=coverage_hist, bed=coverage_bed, bin=int(coverage_bin or 0), min_mapq=int(coverage_min_mapq or 0), deletions=bool(coverage_deletions))
+
+
+def _write_text(dst, text: str) -> None:
+    if hasattr(dst, "write"):
+        dst.write(text)
+    else:
+        with open(dst, "w") as f:
+            f.write(text)
 
 
 class Aligner:
@@ -671,15 +763,18 @@ class Aligner:
         if getattr(self, "_out_fmt", ("sam", 1))[0] == "bam_sorted":
             nat.set_sort(*self._sort_knobs)
             nat.set_markdup(bool(getattr(self, "_markdup", False)))
+            nat.set_coverage(getattr(self, "_coverage_opt", None))
             if getattr(self, "_markdup", False):
                 nat.set_markdup_optical(getattr(self, "_optical", None))
                 nat.set_markdup_barcode(*getattr(self, "_barcode", (0, None)))
                 nat.set_markdup_barcode_edits(getattr(self, "_barcode_edits", -1))
         return nat
 
+    @_coverage_keywords
     def align_file(self, reads_fa: str, out, batch_reads: int = 0, paired: bool = False, chunk_bases: int = 0, fmt: str = "sam", level: int = 1,
                    sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
-                   index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None) -> int:
+                   index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
+                   coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False) -> int:
         if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None or barcode_tag is not None or barcode_name or barcode_edits is not None:
             return self._align_bam(lambda o: self.align_file(reads_fa, o, batch_reads=batch_reads, paired=paired, chunk_bases=chunk_bases), out, fmt, level,
                                    sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift, optical_distance, barcode_tag, barcode_name, barcode_edits)
@@ -830,8 +925,15 @@ class Aligner:
         self._barcode = barcode
         self._barcode_edits = edits
         self._index_format = (index_format, int(csi_min_shift))
+        cov_req = getattr(self, "_cov_req", None) if sort else None
+        if cov_req is not None:
+            from .lib import coverage_opt
+            self._coverage_opt = coverage_opt(cov_req["min_mapq"], cov_req["deletions"], cov_req["bin"], 0, "align_file")
         try:
             n = run(shim)
+            if cov_req is not None:                                # (no reads: no run was made -- the coverage of a file without records)
+                from .lib import bam_coverage
+                self.coverage = self._native.coverage() if n else bam_coverage(b"", self.contigs, host=True, min_mapq=cov_req["min_mapq"], deletions=cov_req["deletions"], bin=cov_req["bin"])
             if markdup:
                 from .lib import MARKDUP_COUNTS
                 self.markdup_counts = self._native.markdup_counts() if n else dict.fromkeys(MARKDUP_COUNTS, 0)
@@ -858,6 +960,7 @@ class Aligner:
             self._barcode = (0, None)
             self._barcode_edits = -1
             self._index_format = ("bai", 14)
+            self._coverage_opt = None
             nat = getattr(self, "_native", None)
             if nat is not None:
                 nat.set_output("sam", 1)
@@ -874,6 +977,13 @@ class Aligner:
             else:
                 with open(index, "wb") as f:
                     f.write(bai)
+        if cov_req is not None:
+            if cov_req["table"] is not None:
+                _write_text(cov_req["table"], coverage_table_text(self.coverage, self.contigs))
+            if cov_req["hist"] is not None:
+                _write_text(cov_req["hist"], coverage_hist_text(self.coverage))
+            if cov_req["bed"] is not None:
+                _write_text(cov_req["bed"], coverage_bed_text(self.coverage, self.contigs, cov_req["bin"]))
         if markdup_metrics is not None:
             text = markdup_metrics_text_libraries(self.markdup_library_counts) if getattr(self, "_groups", None) else markdup_metrics_text(self.markdup_counts, getattr(self, "rg_line", ""))
             if hasattr(markdup_metrics, "write"):
@@ -883,11 +993,17 @@ class Aligner:
                     f.write(text)
         return n
 
+    @_coverage_keywords
     def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
                     sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None, keep_rg: bool = False,
                     index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
-                    collate: bool = False, collate_mem=None) -> int:
-        """align_file for the files users have (bmh_aligner_run_files): `reads` (and `mates`: the second file of a pair, which implies paired) may be
+                    collate: bool = False, collate_mem=None,
+                    coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False) -> int:
+        """coverage=, coverage_hist=, coverage_bed= (paths or text file objects; need sort=True): the coverage depth of the file being written, computed on the
+        device from every window of the final merge behind its flag step -- duplicates that markdup=True marks are counted out.  They receive
+        coverage_table_text, coverage_hist_text and coverage_bed_text (the last with coverage_bin=N positions a row); coverage_min_mapq=Q and coverage_deletions=True
+        say what counts.  self.coverage holds the arrays afterwards (bam_coverage's dict).  The BAM and its index are byte for byte those of the run without them.
+        align_file for the files users have (bmh_aligner_run_files): `reads` (and `mates`: the second file of a pair, which implies paired) may be
         multi-line FASTA or FASTQ, plain, gzip or BGZF, a regular file or a pipe; or `reads` alone is a BAM file (unaligned, or grouped by read name: recognised
         from its bytes, pairs from flag 0x1 of its records -- paired=True on a BAM without it is refused).  Batches are cut by align_file's rules (-t, -K, the 150 Mbase floor for
         single-end runs), so the text equals align_file's on the single-line interleaved file of the same reads.  Returns the number of reads.
@@ -976,10 +1092,12 @@ class Aligner:
         self.host_tail_batches = nat.host_tail_batches()
         return int(self.last_stats.n_reads)
 
+    @_coverage_keywords
     def align_groups(self, groups, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
                      sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
                      index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
-                     collate: bool = False, collate_mem=None) -> int:
+                     collate: bool = False, collate_mem=None,
+                     coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False) -> int:
         """several read groups -- a sample's lanes and libraries -- into one output (bmh_aligner_run_groups).  groups: [(rg_line, reads, mates or None), ...]; every
         rg_line is unescaped and checked as -R's value is, reads / mates are what align_files takes (one file or R1 + R2; plain, gzip or BGZF; FASTA or FASTQ; or
         one BAM, whose own @RG lines and RG tags stay ignored: align_files(keep_rg=True) is the run that keeps them, and the two do not combine).  Group g's records are byte for byte those of align_files(reads_g, mates_g) alone under -R rg_g, and
@@ -987,6 +1105,7 @@ class Aligner:
         markdup=True calls duplicates within a library only (a group's library is its LB field; groups without one share "Unknown Library"):
         self.markdup_library_counts holds the counts per library, markdup_metrics one row per library.  Needs the native pipeline; -R must not be set.
         collate / collate_mem: align_files' -- they apply to every group whose input is one BAM; groups of text files are taken as ever.
+        coverage / coverage_hist / coverage_bed / coverage_bin / coverage_min_mapq / coverage_deletions: align_files' -- the coverage is the whole file's, not per library.
         Returns the number of reads."""
         if out is None:
             raise ValueError("align_groups: out (a text or binary file object) is required")

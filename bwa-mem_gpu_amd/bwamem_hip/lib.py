@@ -52,6 +52,8 @@ EXPORTED_SYMBOLS = [
     "bmh_barcode_pack", "bmh_aligner_set_markdup_barcode_edits",
     "bmh_aligner_markdup_barcode_group_counts",
     "bmh_reads_last_collate_counts", "bmh_aligner_set_collate", "bmh_reads_load_files_ex", "bmh_bam_reads_ex",
+    "bmh_coverage_opt_default", "bmh_bam_coverage_device", "bmh_bam_coverage_host", "bmh_bam_sorted_file_coverage_device", "bmh_bam_sorted_file_coverage_host",
+    "bmh_aligner_set_coverage", "bmh_aligner_coverage", "bmh_aligner_coverage_ms",
 ]
 
 
@@ -745,8 +747,10 @@ def index_format_code(index_format, csi_min_shift, what: str) -> tuple:
 
 
 def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False, markdup: bool = False, read_groups=None,
-                    index_format: str = "bai", csi_min_shift: int = 14, barcode_tag=None, barcode_name=None, barcode_edits=None) -> tuple:
-    """bmh_bam_sorted_file_device (host=True: _host): (the complete sorted BAM file -- header members, the records in coordinate order in windows of `window`
+                    index_format: str = "bai", csi_min_shift: int = 14, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None) -> tuple:
+    """coverage={min_mapq, deletions, bin, tile} (bmh_bam_sorted_file_coverage_*; bam_coverage's keywords, {} for the defaults): the file's coverage, taken from
+    the windows of the merge as they are written -- with markdup=True the marked duplicates are counted out -- comes last in the tuple.
+    bmh_bam_sorted_file_device (host=True: _host): (the complete sorted BAM file -- header members, the records in coordinate order in windows of `window`
     records (0: about 64 MiB), the end-of-file member --, its .bai index).  contigs: (name, length) pairs; both forms give the same bytes.
     markdup=True (a bmh_markdup_opt_t in bmh_sorted_file_opt_t): `records` come in the writer's order, the duplicates among them are marked (bam_markdup's rules) and the counts come third.
     read_groups (needs markdup=True): as bam_markdup takes them -- duplicates per library, and the counts gain "libraries".
@@ -777,19 +781,91 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
     bam, bai, nb, ni = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
     head = [header_text.encode(), len(contigs), names, lens.ctypes.data, records, len(records), C.byref(fo)]
     tail = [C.byref(bam), C.byref(nb), C.byref(bai), C.byref(ni), C.byref(res) if markdup else None]
+    cov, co = Coverage(), None
+    if coverage is not None:
+        co = coverage_opt(what="bam_sorted_file", **coverage)
+        types = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(SortedFileOpt), C.POINTER(CoverageOpt)]
+        outs = [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p, C.POINTER(MarkdupCounts), C.POINTER(Coverage)]
+        L.bmh_bam_sorted_file_coverage_host.argtypes, L.bmh_bam_sorted_file_coverage_device.argtypes = types + outs, types + [C.c_void_p] + outs
+        head, tail = head + [C.byref(co)], tail + [C.byref(cov)]
     if host:
-        rc = L.bmh_bam_sorted_file_host(*head, *tail)
+        rc = (L.bmh_bam_sorted_file_coverage_host if co else L.bmh_bam_sorted_file_host)(*head, *tail)
     else:
         import torch
-        rc = L.bmh_bam_sorted_file_device(*head, torch.cuda.current_stream().cuda_stream, *tail)
+        rc = (L.bmh_bam_sorted_file_coverage_device if co else L.bmh_bam_sorted_file_device)(*head, torch.cuda.current_stream().cuda_stream, *tail)
     if rc != 0:
         raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_sorted_file: " + _err(L))
     try:
+        extra = (coverage_dict(L, cov),) if co else ()
         if markdup:
-            return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value), _markdup_dict(o, res, lib_names, read_groups is not None)
-        return C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)
+            return (C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value), _markdup_dict(o, res, lib_names, read_groups is not None)) + extra
+        return (C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)) + extra
     finally:
         L.bmh_free(bam); L.bmh_free(bai)
+
+
+class CoverageOpt(C.Structure):
+    """bmh_coverage_opt_t"""
+    _fields_ = [("min_mapq", C.c_int32), ("deletions", C.c_int32), ("bin", C.c_uint32), ("tile", C.c_uint32)]
+
+
+class Coverage(C.Structure):
+    """bmh_coverage_t"""
+    _fields_ = [("n_contigs", C.c_int32), ("n_bins", C.c_uint64), ("n_reads", _u64p), ("cov_bases", _u64p), ("sum_depth", _u64p), ("max_depth", _u64p), ("sum_mapq", _u64p),
+                ("hist", _u64p), ("bin_sum", _u64p)]
+
+
+COVERAGE_CONTIG_ARRAYS = ("n_reads", "cov_bases", "sum_depth", "max_depth", "sum_mapq")
+COVERAGE_HIST = 1001
+
+
+def coverage_opt(min_mapq=0, deletions=False, bin=0, tile=0, what="bam_coverage") -> CoverageOpt:
+    """the coverage keywords, checked -> bmh_coverage_opt_t; ValueError names the keyword"""
+    for nm, v, lo, hi in (("min_mapq", min_mapq, 0, 255), ("bin", bin, 0, 0xffffffff), ("tile", tile, 0, 4096)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not lo <= v <= hi:
+            raise ValueError(f"{what}: {nm} {v!r}: an integer in {lo} .. {hi}")
+    return CoverageOpt(int(min_mapq), 1 if deletions else 0, int(bin), int(tile))
+
+
+def coverage_dict(L, cov: Coverage) -> dict:
+    """bmh_coverage_t -> {name: numpy array of uint64}; the record's arrays are released"""
+    try:
+        out = {nm: np.ctypeslib.as_array(getattr(cov, nm), shape=(max(cov.n_contigs, 1),))[:cov.n_contigs].copy() for nm in COVERAGE_CONTIG_ARRAYS}
+        out["hist"] = np.ctypeslib.as_array(cov.hist, shape=(COVERAGE_HIST,)).copy()
+        out["bin_sum"] = np.ctypeslib.as_array(cov.bin_sum, shape=(max(int(cov.n_bins), 1),))[:int(cov.n_bins)].copy()
+        return out
+    finally:
+        L.bmh_free.argtypes = [C.c_void_p]
+        for nm in COVERAGE_CONTIG_ARRAYS + ("hist", "bin_sum"):
+            L.bmh_free(C.cast(getattr(cov, nm), C.c_void_p))
+
+
+def bam_coverage(records: bytes, contigs, host: bool = False, min_mapq: int = 0, deletions: bool = False, bin: int = 0, tile: int = 0) -> dict:
+    """bmh_bam_coverage_device (host=True: _host, no device needed): a stream of BAM records in coordinate order and the contigs ((name, length) pairs, or
+    lengths) -> the coverage depth as a dict of uint64 arrays: per contig n_reads, cov_bases, sum_depth, max_depth, sum_mapq; hist [1001]
+    (positions of all contigs at depth d, the last bin 1000 and more, depth 0 included); bin_sum (with bin=B: the depth summed over every B positions, contig
+    after contig).  `samtools depth`'s default filters (flags 0x4 0x100 0x200 0x400 out, mapq >= min_mapq); deletions=True: D covers (-J).  tile: the positions
+    swept at once (0: 4096) -- no result depends on it.  A stream out of order, a counted record that begins outside its contig or holds the long-CIGAR
+    placeholder, and 2^28 bins or more raise ValueError."""
+    L = load_library()
+    records = bytes(records)
+    o = coverage_opt(min_mapq, deletions, bin, tile)
+    lens = np.ascontiguousarray([c[1] if isinstance(c, (tuple, list)) else c for c in contigs] or [0], dtype=np.int64)
+    if ((lens < 0) | (lens >= 1 << 31)).any():
+        raise ValueError("bam_coverage: BAM holds contigs of at most 2^31 - 1 bases")
+    lens = lens.astype(np.int32)
+    cov = Coverage()
+    head = [C.c_char_p, C.c_uint64, C.c_int, C.c_void_p, C.POINTER(CoverageOpt)]
+    if host:
+        L.bmh_bam_coverage_host.argtypes = head + [C.POINTER(Coverage)]
+        rc = L.bmh_bam_coverage_host(records, len(records), len(contigs), lens.ctypes.data, C.byref(o), C.byref(cov))
+    else:
+        import torch
+        L.bmh_bam_coverage_device.argtypes = head + [C.c_void_p, C.POINTER(Coverage)]
+        rc = L.bmh_bam_coverage_device(records, len(records), len(contigs), lens.ctypes.data, C.byref(o), torch.cuda.current_stream().cuda_stream, C.byref(cov))
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_coverage: " + _err(L))
+    return coverage_dict(L, cov)
 
 
 def reads_last_bam_counts() -> dict:
@@ -1055,6 +1131,31 @@ class NativeAligner:
         if L.bmh_aligner_markdup_optical_ms(self.handle, C.byref(t)) != 0:
             raise ValueError("bmh_aligner_markdup_optical_ms: " + _err(L))
         return float(t.value)
+
+    def set_coverage(self, opt=None) -> None:
+        """bmh_aligner_set_coverage: the sorted runs that follow compute their coverage under `opt` (a CoverageOpt; None: off; refused unless the output is sorted BAM)"""
+        L = load_library()
+        L.bmh_aligner_set_coverage.argtypes = [C.c_void_p, C.POINTER(CoverageOpt)]
+        if L.bmh_aligner_set_coverage(self.handle, C.byref(opt) if opt is not None else None) != 0:
+            raise ValueError("bmh_aligner_set_coverage: " + _err(L))
+
+    def coverage(self) -> dict:
+        """bmh_aligner_coverage: the coverage of the last sorted run that computed it, as bam_coverage returns it"""
+        L = load_library()
+        L.bmh_aligner_coverage.argtypes = [C.c_void_p, C.POINTER(Coverage)]
+        cov = Coverage()
+        if L.bmh_aligner_coverage(self.handle, C.byref(cov)) != 0:
+            raise ValueError("bmh_aligner_coverage: " + _err(L))
+        return coverage_dict(L, cov)
+
+    def coverage_ms(self, windows: bool = False):
+        """bmh_aligner_coverage_ms: the device milliseconds the last such run's windows spent in the coverage step; windows=True: (milliseconds, windows timed)"""
+        L = load_library()
+        L.bmh_aligner_coverage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        t, w = C.c_double(0), C.c_uint64(0)
+        if L.bmh_aligner_coverage_ms(self.handle, C.byref(t), C.byref(w)) != 0:
+            raise ValueError("bmh_aligner_coverage_ms: " + _err(L))
+        return (float(t.value), int(w.value)) if windows else float(t.value)
 
     def markdup_counts(self) -> dict:
         """bmh_aligner_markdup_counts: the counts of the last run that marked duplicates, by MARKDUP_COUNTS' names"""

@@ -42,7 +42,13 @@ paired BAM in any record order -- a coordinate-sorted one, this program's own --
 reads are the pairs in the order in which their later record comes, and the output is byte for byte that of a run on the name-grouped BAM of the same pairs in
 that order (Aligner.align_files(collate=True)); first mates wait for their partners in host memory, at most --collate-mem BYTES of them (needs --collate; 8 GiB by
 default; nothing is spilled to disk: beyond the cap the run stops after the batches before it, naming the record); a record whose partner never comes is refused
-after the complete batches; text input is refused (a regular file before anything is written, a pipe of text after the header); with --rg it applies to every group whose input is a BAM.  An option that is
+after the complete batches; text input is refused (a regular file before anything is written, a pipe of text after the header); with --rg it applies to every group whose input is a BAM.
+--coverage PATH, --coverage-hist PATH and --coverage-bed PATH (need --sort) write the coverage depth of the file being written, computed on the device while it
+is written: `samtools coverage`'s table (one row per contig and a row `total`), the depth histogram (depth, bases, fraction at or above; the last row 1000+) and
+the mean depth of every --coverage-bin N positions (--coverage-bed and --coverage-bin go together).  A record counts by `samtools depth`'s default filters --
+unmapped, secondary, QC-failed and duplicate records are out, so --markdup's duplicates are counted out; supplementary records count -- and with
+--coverage-min-mapq Q (0 .. 255) only at mapq >= Q; it covers the positions under M, = and X, and under D with --coverage-deletions (`samtools depth -J`).
+There is no base-quality filter and no correction for overlapping mates.  With --rg the coverage is the whole file's, not per library.  An option that is
 not on that list is refused by name.  Two input files imply pairs.  One plain, regular file is offered to Aligner.align_file first, which takes it when every
 record has one sequence line (its own counting pass decides, before anything is written); every other input goes through
 Aligner.align_files; the text is the same.  A refused file ends the command with status 1 and the library's message on stderr.
@@ -78,6 +84,7 @@ def main(argv=None) -> int:
     csi, csi_shift = False, None
     keep_rg = False
     collate, collate_mem = False, None
+    cov_paths, cov_bin, cov_mapq, cov_del = {}, None, None, False
     groups = []                                                     # --rg LINE: [line, files...]; the positionals behind it are its files
     i = 0
     while i < len(argv):
@@ -136,6 +143,26 @@ def main(argv=None) -> int:
                 return 2
             collate_mem = int(argv[i + 1])
             i += 1
+        elif a in ("--coverage", "--coverage-hist", "--coverage-bed"):
+            if i + 1 >= len(argv):
+                print(f"[bwamem_hip.mem] option {a} needs a value", file=sys.stderr)
+                return 2
+            cov_paths[a] = argv[i + 1]
+            i += 1
+        elif a == "--coverage-bin":
+            if i + 1 >= len(argv) or not (argv[i + 1].isascii() and argv[i + 1].isdigit()) or not 1 <= int(argv[i + 1]) <= 0xffffffff:
+                print("[bwamem_hip.mem] option --coverage-bin needs a whole number of positions, 1 .. 2^32 - 1", file=sys.stderr)
+                return 2
+            cov_bin = int(argv[i + 1])
+            i += 1
+        elif a == "--coverage-min-mapq":
+            if i + 1 >= len(argv) or not (argv[i + 1].isascii() and argv[i + 1].isdigit()) or int(argv[i + 1]) > 255:
+                print("[bwamem_hip.mem] option --coverage-min-mapq needs a whole number, 0 .. 255", file=sys.stderr)
+                return 2
+            cov_mapq = int(argv[i + 1])
+            i += 1
+        elif a == "--coverage-deletions":
+            cov_del = True
         elif a == "--rg":
             if i + 1 >= len(argv):
                 print("[bwamem_hip.mem] option --rg needs a value", file=sys.stderr)
@@ -233,6 +260,15 @@ def main(argv=None) -> int:
         if barcode_tag is not None and "-C" not in opts:
             print("[bwamem_hip.mem] --barcode-tag needs -C: the tag reaches a record only as the read's comment", file=sys.stderr)
             return 2
+    if (cov_paths or cov_bin is not None or cov_mapq is not None or cov_del) and not sort:
+        print("[bwamem_hip.mem] --coverage, --coverage-hist, --coverage-bed, --coverage-bin, --coverage-min-mapq and --coverage-deletions need --sort (depth is computed where the sorted file is written)", file=sys.stderr)
+        return 2
+    if ("--coverage-bed" in cov_paths) != (cov_bin is not None):
+        print("[bwamem_hip.mem] --coverage-bed and --coverage-bin go together (the bins of the BED file)", file=sys.stderr)
+        return 2
+    if (cov_mapq is not None or cov_del) and not cov_paths:
+        print("[bwamem_hip.mem] --coverage-min-mapq and --coverage-deletions need --coverage, --coverage-hist or --coverage-bed (they say what is counted, not where it goes)", file=sys.stderr)
+        return 2
     if csi_shift is not None and not csi:
         print("[bwamem_hip.mem] --csi-min-shift needs --csi (a BAI index has one bin size)", file=sys.stderr)
         return 2
@@ -265,6 +301,9 @@ def main(argv=None) -> int:
             fmt_kw.update(index_format="csi", csi_min_shift=14 if csi_shift is None else csi_shift)
         if collate:
             fmt_kw.update(collate=True, collate_mem=collate_mem)
+        if cov_paths:
+            fmt_kw.update(coverage=cov_paths.get("--coverage"), coverage_hist=cov_paths.get("--coverage-hist"), coverage_bed=cov_paths.get("--coverage-bed"), coverage_bin=cov_bin,
+                          coverage_min_mapq=cov_mapq, coverage_deletions=cov_del)
         done = False
         if groups:
             al.align_groups([(g[0], g[1], g[2] if len(g) == 3 else None) for g in groups], out=out, paired=interleaved, **fmt_kw)

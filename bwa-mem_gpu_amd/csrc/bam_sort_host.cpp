@@ -11,6 +11,7 @@
 #include <numeric>
 #include "bam_sort.h"
 #include "bam_dup.h"
+#include "bam_cov.h"
 
 #ifndef O_TMPFILE
 #define O_TMPFILE 0
@@ -295,7 +296,8 @@ extern "C" int bmh_bam_sort_host(const uint8_t *recs, uint64_t n_bytes, uint8_t 
 
 // header members, the sorted records in windows of `window` records (0: as many as hold about 64 MiB), the end-of-file member; and the index
 static int sorted_file_host(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                            const bmh_sorted_file_opt_t &o, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts, const bdp_plan_t &P)
+                            const bmh_sorted_file_opt_t &o, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts, const bdp_plan_t &P,
+                            bcv_host_t *cov = nullptr)
 {
 	const int level = o.level; const uint32_t window = o.window;
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
@@ -340,7 +342,9 @@ static int sorted_file_host(const char *fn, const char *header_text, int n_conti
 		for (size_t j = a; j < b; ++j) { const uint64_t o = off[ord[j]], s = off[ord[j] + 1] - o; buf.insert(buf.end(), recs + o, recs + o + s); soff.push_back(buf.size()); }
 		if ((rc = members(buf.data(), buf.size(), &moff)) != BMH_OK) return rc;
 		ix.window_host(buf.data(), soff.data(), (uint32_t)(b - a), moff.data());
+		if (cov && (rc = cov->window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;      // the window in its final order, with its final flags
 	}
+	if (cov && (rc = cov->finish(fn)) != BMH_OK) return rc;
 	file.append((const char *)bmh_bgzf_eof, 28);
 	std::string ib;
 	if ((rc = ix.bytes(base, ib)) != BMH_OK) return rc;
@@ -359,4 +363,31 @@ extern "C" int bmh_bam_sorted_file_host(const char *header_text, int n_contigs, 
 	const int rc = bsr_file_opt_check(opt, res, fn, o, P);
 	if (rc != BMH_OK) return rc;
 	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P);
+}
+
+// the sorted file and, from the same windows of the merge, its coverage (the host form of csrc/bam_cov_kernels.hip)
+extern "C" int bmh_bam_sorted_file_coverage_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                                 const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes,
+                                                 bmh_markdup_counts_t *res, bmh_coverage_t *cov)
+{
+	const char *fn = "bmh_bam_sorted_file_coverage_host";
+	if (bam) *bam = nullptr;                                         // (before anything can be refused: a caller who frees what a failed call left frees nothing)
+	if (index) *index = nullptr;
+	if (!cov) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	memset(cov, 0, sizeof *cov);
+	bmh_sorted_file_opt_t o; bdp_plan_t P;
+	int rc = bsr_file_opt_check(opt, res, fn, o, P);
+	if (rc != BMH_OK) return rc;
+	bmh_coverage_opt_t co; bmh_coverage_opt_default(&co);
+	if (cov_opt) co = *cov_opt;
+	bcv_plan_t CP;
+	if ((rc = bcv_plan_make(CP, co.min_mapq, co.deletions, co.bin, co.tile, n_contigs, contig_len, fn)) != BMH_OK) return rc;
+	try {
+		bcv_host_t H; H.begin(CP);
+		rc = sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P, &H);
+		if (rc == BMH_OK && (rc = bcv_export(CP, H.R, cov, fn)) != BMH_OK) {      // the one failure behind the file's bytes: they are the call's to release
+			bmh_free(*bam); bmh_free(*index); *bam = *index = nullptr; *bam_bytes = *index_bytes = 0;
+		}
+	} catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); rc = BMH_ENOMEM; }
+	return rc;
 }

@@ -1089,6 +1089,46 @@ typedef struct { const char *id; int32_t library; const char *path1, *path2; } b
 int bmh_aligner_run_groups(bmh_aligner_t *a, const bmh_read_group_t *groups, int n_groups, uint64_t batch_bases, uint64_t batch_reads, int paired, int n_lanes,
                            int n_threads, bmh_sam_sink_t sink, void *user, bmh_align_stats_t *stats);
 
+/* ---- Coverage depth of sorted BAM, computed while the file is written (csrc/bam_cov_core.h, csrc/bam_cov_kernels.hip, csrc/bam_cov_host.cpp).
+ * A record counts when its refID names a contig, none of the flags 0x4 0x100 0x200 0x400 is set and mapq >= min_mapq (`samtools depth`'s default filters;
+ * supplementary records count).  It covers the reference positions under M, = and X, and under D with `deletions` (`samtools depth -J`); N never covers.  A run past
+ * the contig's end is clamped; a counted record without operations is a read that covers nothing.  No base-quality filter, no correction for overlapping mates.
+ * The results are exact integers and do not depend on windows, tiles or the form: per contig n_reads (counted records), cov_bases (positions of depth >= 1),
+ * sum_depth, max_depth and sum_mapq (over counted records); hist [1001]: the positions of all contigs at depth d, hist[1000] those at 1000 and more, depth 0
+ * included, so the bins add up to the genome; with bin = B >= 1, bin_sum [n_bins]: the depth summed over every B positions of a contig (its last bin short),
+ * contig after contig.  tile: the positions swept through one difference array (1 .. 4096; 0: 4096); work and memory follow the covered runs, not the genome.
+ * All arrays of bmh_coverage_t are malloc'd: bmh_free each (a failed call leaves them NULL).
+ * bmh_bam_coverage_device / _host: a record stream in coordinate order (whole records, else refused).  Both forms give the same integers.
+ * Refused with BMH_EINVAL: min_mapq outside 0 .. 255, a tile beyond 4096, 2^28 bins or more (before anything is written); and by the record's index: a record
+ * that lies before its predecessor, a counted record whose pos is negative or not below its contig's length, a counted record that holds the long-CIGAR
+ * placeholder (l_seq S, N, and a CG:B,I tag).
+ * bmh_bam_sorted_file_coverage_device / _host: bmh_bam_sorted_file_* and, from the same windows, the coverage of the file -- duplicates that opt->markdup marks are
+ * counted out.
+ * bmh_aligner_set_coverage: the sorted runs that follow compute their coverage on the device, every window behind its flag step (opt NULL: off); refused (the
+ * aligner stays as it was) unless the output format is BMH_OUT_BAM_SORTED, and switched off by every bmh_aligner_set_output of another format.  Without it nothing
+ * about a run changes.  bmh_aligner_coverage: the coverage of the last such run; bmh_aligner_coverage_ms: the milliseconds its windows' steps and its last sweep took on
+ * the device's stream (events around every step, read behind the window's own wait; a step's span holds its two host reads) and, with `windows`, the windows timed.
+ * A failed bmh_bam_sorted_file_coverage_* call leaves *bam and *index NULL, whatever they held before. */
+typedef struct { int32_t min_mapq, deletions; uint32_t bin; uint32_t tile; } bmh_coverage_opt_t;
+void bmh_coverage_opt_default(bmh_coverage_opt_t *o);
+typedef struct bmh_coverage {
+	int32_t n_contigs; uint64_t n_bins;
+	uint64_t *n_reads, *cov_bases, *sum_depth, *max_depth, *sum_mapq;   /* [n_contigs] each */
+	uint64_t *hist;                                                      /* [1001] */
+	uint64_t *bin_sum;                                                   /* [n_bins] */
+} bmh_coverage_t;
+int bmh_bam_coverage_device(const uint8_t *records, uint64_t n_bytes, int n_contigs, const int32_t *contig_len, const bmh_coverage_opt_t *opt, void *stream, bmh_coverage_t *out);
+int bmh_bam_coverage_host(const uint8_t *records, uint64_t n_bytes, int n_contigs, const int32_t *contig_len, const bmh_coverage_opt_t *opt, bmh_coverage_t *out);
+int bmh_bam_sorted_file_coverage_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
+                                        const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index,
+                                        uint64_t *index_bytes, bmh_markdup_counts_t *res, bmh_coverage_t *cov);
+int bmh_bam_sorted_file_coverage_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
+                                      const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes,
+                                      bmh_markdup_counts_t *res, bmh_coverage_t *cov);
+int bmh_aligner_set_coverage(bmh_aligner_t *a, const bmh_coverage_opt_t *opt);
+int bmh_aligner_coverage(bmh_aligner_t *a, bmh_coverage_t *out);
+int bmh_aligner_coverage_ms(bmh_aligner_t *a, double *out, uint64_t *windows);
+
 #ifdef __cplusplus
 }
 #endif
