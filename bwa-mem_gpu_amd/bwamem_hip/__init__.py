@@ -11,3 +11,9 @@ from . import fmindex, synth  # noqa: F401
 from .index import fasta_pack, index_fasta  # noqa: F401
 from .lib import (ExtParams, HipLibraryMissing, Index, SeedWorkspace, extend_batch, lib_path,  # noqa: F401
                   load_library, seed_file)
+
+
+def bam_post_file(*args, **kw):
+    """bwamem_hip.bam.bam_post_file (imported on first use, so that `python -m bwamem_hip.bam` finds its module unloaded)"""
+    from .bam import bam_post_file as f
+    return f(*args, **kw)

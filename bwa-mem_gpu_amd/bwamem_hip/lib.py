@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = [
     "bmh_reads_last_collate_counts", "bmh_aligner_set_collate", "bmh_reads_load_files_ex", "bmh_bam_reads_ex",
     "bmh_coverage_opt_default", "bmh_bam_coverage_device", "bmh_bam_coverage_host", "bmh_bam_sorted_file_coverage_device", "bmh_bam_sorted_file_coverage_host",
     "bmh_aligner_set_coverage", "bmh_aligner_coverage", "bmh_aligner_coverage_ms",
+    "bmh_bam_post_opt_default", "bmh_bam_post_result_free", "bmh_bam_post_file_device", "bmh_bam_post_file_host",
 ]
 
 
@@ -876,6 +877,106 @@ def reads_last_bam_counts() -> dict:
     out = (C.c_uint64 * 2)()
     L.bmh_reads_last_bam_counts(out)
     return dict(records_skipped=int(out[0]), tags_left_out=int(out[1]))
+
+
+class BamPostOpt(C.Structure):
+    """bmh_bam_post_opt_t"""
+    _fields_ = [("level", C.c_int32), ("window", C.c_uint32), ("index_format", C.c_int32), ("min_shift", C.c_int32), ("sort_mem", C.c_uint64), ("tmp_dir", C.c_char_p),
+                ("batch_bytes", C.c_uint64), ("markdup", C.POINTER(MarkdupOpt)), ("libraries", C.c_int32), ("coverage", C.POINTER(CoverageOpt))]
+
+
+class BamPostResult(C.Structure):
+    """bmh_bam_post_result_t"""
+    _fields_ = [("index", C.c_void_p), ("index_bytes", C.c_uint64), ("header_text", C.c_void_p), ("header_bytes", C.c_uint64), ("n_contigs", C.c_int32), ("contig_names", C.c_void_p),
+                ("contig_len", C.POINTER(C.c_int32)), ("n_libraries", C.c_int32), ("library_names", C.c_void_p), ("counts", C.c_uint64 * 6)]
+
+
+BAM_POST_COUNTS = ("records", "templates", "batches", "spilled_runs", "bins_changed", "duplicate_flags_cleared")
+_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
+
+
+def _names_blob(addr, n: int) -> list:
+    """n NUL-terminated names back to back at addr"""
+    out = []
+    for _ in range(n):
+        s = C.string_at(addr)
+        out.append(s.decode("latin-1")); addr += len(s) + 1
+    return out
+
+
+def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 0, index_format: str = "bai", csi_min_shift: int = 14, sort_mem=None, sort_tmp=None, batch_bytes=None,
+             markdup: bool = False, libraries: bool = False, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None) -> dict:
+    """bmh_bam_post_file_device (host=True: bmh_bam_post_file_host, no device needed; it holds the whole record stream in memory): the BAM or SAM file `src` of any
+    aligner (a path; plain, gzip or BGZF; a pipe) -> the coordinate-sorted BAM, handed to write(bytes) piece by piece, and a dict: "index" (the .bai or .csi
+    bytes), "header" (the output header's text), "contigs" ((name, length) pairs), "counts" (BAM_POST_COUNTS' names), with markdup=True "markdup" (bam_markdup's
+    counts; with libraries=True -- the header's @RG lines are the table of libraries -- "libraries" per library), with coverage={min_mapq, deletions, bin, tile}
+    "coverage" (bam_coverage's arrays).  DESIGN.md 4.14 has the definition.  The keywords are bam_markdup's and bam_sorted_file's and are refused as there;
+    libraries, optical_distance and the barcode keywords need markdup=True.  A refused input raises ValueError naming the record's index or the line's number."""
+    what = "bam_post"
+    bc_mode, bc_tag = barcode_source(barcode_tag, barcode_name, what)
+    if barcode_edits is not None and not markdup:
+        raise ValueError(f"{what}: barcode_edits needs markdup=True (barcodes are grouped where duplicates are marked)")
+    edits = barcode_edits_value(barcode_edits, bc_mode, what)
+    if bc_mode != BARCODE_OFF and not markdup:
+        raise ValueError(f"{what}: barcode_tag / barcode_name need markdup=True (barcodes are compared where duplicates are marked)")
+    if optical_distance is not None and not markdup:
+        raise ValueError(f"{what}: optical_distance needs markdup=True (optical duplicates are counted where duplicates are marked)")
+    if libraries and not markdup:
+        raise ValueError(f"{what}: libraries needs markdup=True (they decide which templates may be duplicates of each other)")
+    distance = -1 if optical_distance is None else optical_distance_value(optical_distance, what)
+    ix_code, ix_shift = index_format_code(index_format, csi_min_shift, what)
+    if level not in (0, 1):
+        raise ValueError(f"{what}: level {level}: 0 or 1")
+    for nm, v in (("sort_mem", sort_mem), ("batch_bytes", batch_bytes)):
+        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 1):
+            raise ValueError(f"{what}: {nm} {v!r}: a number of bytes, 1 and more")
+    if batch_bytes is not None and batch_bytes > 1 << 30:
+        raise ValueError(f"{what}: batch_bytes {batch_bytes}: at most 2^30")
+    L = _markdup_api(load_library())
+    mo, res, _names, _keep = _markdup_records(L, None, distance, 0, bc_mode, bc_tag, edits, 0)
+    arrays = [(C.c_uint64 * (k * 255))() for k in (8, 3, 3)] if libraries else []
+    if libraries:
+        res.lib_counts, res.lib_optical, res.lib_grouped = (C.cast(a, _u64p) for a in arrays)
+    co = coverage_opt(what=what, **coverage) if coverage is not None else None
+    o = BamPostOpt(int(level), int(window), ix_code, ix_shift, int(sort_mem or 0), os.fsencode(sort_tmp) if sort_tmp is not None else None, int(batch_bytes or 0),
+                   C.pointer(mo) if markdup else None, 1 if libraries else 0, C.pointer(co) if co is not None else None)
+    failed = []
+
+    def sink(_user, p, n):
+        try:
+            write(C.string_at(p, n))
+            return 0
+        except BaseException as e:                                 # (an exception must not cross the C frames: the run ends, then it is raised)
+            failed.append(e)
+            return 1
+    cb, out, cov = _SINK(sink), BamPostResult(), Coverage()
+    head = [C.c_char_p, C.POINTER(BamPostOpt)]
+    tail = [_SINK, C.c_void_p, C.POINTER(BamPostResult), C.POINTER(MarkdupCounts), C.POINTER(Coverage)]
+    args = [cb, None, C.byref(out), C.byref(res) if markdup else None, C.byref(cov) if co is not None else None]
+    L.bmh_bam_post_result_free.argtypes, L.bmh_bam_post_result_free.restype = [C.POINTER(BamPostResult)], None
+    if host:
+        L.bmh_bam_post_file_host.argtypes = head + tail
+        rc = L.bmh_bam_post_file_host(os.fsencode(src), C.byref(o), *args)
+    else:
+        import torch
+        L.bmh_bam_post_file_device.argtypes = head + [C.c_void_p] + tail
+        rc = L.bmh_bam_post_file_device(os.fsencode(src), C.byref(o), torch.cuda.current_stream().cuda_stream, *args)
+    if failed:
+        raise failed[0]
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_post_file: " + _err(L))
+    try:
+        names = _names_blob(out.contig_names, out.n_contigs)
+        r = dict(index=C.string_at(out.index, out.index_bytes), header=C.string_at(out.header_text, out.header_bytes).decode("latin-1"),
+                 contigs=[(nm, int(out.contig_len[k])) for k, nm in enumerate(names)], counts=dict(zip(BAM_POST_COUNTS, (int(v) for v in out.counts))))
+        if markdup:
+            lib_names = _names_blob(out.library_names, out.n_libraries) if libraries else []
+            r["markdup"] = _markdup_dict(mo, res, lib_names, libraries)
+        if co is not None:
+            r["coverage"] = coverage_dict(L, cov)
+        return r
+    finally:
+        L.bmh_bam_post_result_free(C.byref(out))
 
 
 def bam_header_read_groups(text, markdup: bool = False) -> tuple:

@@ -35,8 +35,12 @@ int bdp_group_refused(uint32_t rec, int st, const char *fn);
 // locs (or NULL): every template's location (csrc/bam_dup_core.h) beside its entry -- what the optical step reads
 // bcs (or NULL): with P's barcodes every template's barcode word beside its entry; a first record whose barcode tag is of another type than Z, or whose tags cannot
 // be walked, is refused by its index
+// tpl_rule: BDP_TPL_WRITER, or BDP_TPL_NAME -- a template is a run of adjacent records under one name (csrc/bam_post_core.h); the first record always heads one
 int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn,
-                     const bdp_plan_t &P, std::vector<bdp_loc_t> *locs = nullptr, std::vector<uint64_t> *bcs = nullptr);
+                     const bdp_plan_t &P, std::vector<bdp_loc_t> *locs = nullptr, std::vector<uint64_t> *bcs = nullptr, int tpl_rule = BDP_TPL_WRITER, uint64_t rec_base = 0);
+// under BDP_TPL_NAME the stream is a batch of a file: rec_base is the file index of its first record, which the messages name; a refused template is worded by
+// bdp_name_refused (rec: the file index of its first record)
+int bdp_name_refused(uint64_t rec, const char *fn);
 // barcode_mode and tag as the entry points take them -> *bc; BMH_EINVAL with a message: a mode other than 0, 1, 2; a tag that is not [A-Za-z][A-Za-z0-9], RG, or one
 // the writer produces itself (NM MD AS XS SA XA pa)
 int bdp_barcode_check(int barcode_mode, const char *tag, const char *fn, bdp_bc_t *bc);
@@ -110,8 +114,11 @@ inline uint32_t bdp_info_words(const bdp_bc_t *bc) { return bc && bc->mode != BD
 // d_locs (or NULL): *d_locs [as many as entries]: every template's location, written by the lane that makes its entry
 // bc, d_bcs (or NULL): barcodes are compared -- *d_bcs [as many as entries]: every template's barcode word, written by the lane that makes its entry; *d_info [6],
 // [7]: the first template's first record + 1 whose barcode tag is of another type than Z / whose tags cannot be walked (0xffffffff: none)
+// tpl_rule: BDP_TPL_WRITER, or BDP_TPL_NAME -- the heads come from a lane-per-record name compare against the predecessor; the scan and the entries are the same
 int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint32_t **d_tpl,
-                     const bdp_entry_t **d_entries, const uint32_t **d_info, const bdp_loc_t **d_locs, const bdp_bc_t *bc, const uint64_t **d_bcs);
+                     const bdp_entry_t **d_entries, const uint32_t **d_info, const bdp_loc_t **d_locs, const bdp_bc_t *bc, const uint64_t **d_bcs, int tpl_rule = BDP_TPL_WRITER);
+// the heads of BDP_TPL_NAME for bdp_batch_device's scan (csrc/bam_post_kernels.hip): d_head [n], and d_info [2], [3] counted as the writer's rule counts them
+int bpo_heads_device(const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, uint32_t *d_head, uint32_t *d_info, void *stream);
 // a batch whose templates are of several libraries (a run that keeps its input's read groups), after bdp_batch_device on the same batch: *d_lib3 [3 * n_lib] -- every
 // library's secondary / supplementary records, unmapped records and templates, a record counted under the library of its template's entry (bdp_lib_tally_host's
 // three, per batch) -- in d until its next call.  n_lib <= BDP_MAX_LIBS.
@@ -123,6 +130,8 @@ int bdp_batch_refused(uint32_t n, uint32_t bad, const char *fn);
 // the verdict on a batch's info words (n records; groups, barcode: all BDP_INFO_WORDS were read): BMH_OK, or the message of the first refused record
 // pack: BDP_INFO_WORDS_PACK were read
 int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *fn, bool barcode = false, bool pack = false);
+// the same verdict without the message: BDP_E_OK, or the status of the first refused record and *bad = its index + 1 (n + 1: the first record begins no template)
+int bdp_batch_verdict(uint32_t n, const uint32_t *info, bool groups, bool barcode, bool pack, uint32_t *bad);
 // every template's entry (host) -> the bitmap, kept in d for bdp_flag_device, and counts [0 .. 4], as P says
 // n_records: the records of the final sort that follows (csrc/bam_sort_kernels.hip: 24 bytes each and the sort's work space) -- the decision's buffers are freed
 // before that sort allocates, so one check of the larger of the two needs refuses here what either would refuse

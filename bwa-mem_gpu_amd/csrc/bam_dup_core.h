@@ -71,6 +71,9 @@ enum { BDP_NONE = 0, BDP_FRAG = 1, BDP_PAIR = 2, BDP_QMIN = 15 };
 enum { BDP_LIB_SHIFT = 56, BDP_MAX_LIBS = 255, BDP_MAX_REF = 1 << 24, BDP_MAX_CONTIG = (1 << 30) - (1 << 24) };
 // what bdp_entry_lib says of a template
 enum { BDP_E_OK = 0, BDP_E_TEMPLATE = 1, BDP_E_NO_RG = 2, BDP_E_RG_UNKNOWN = 3, BDP_E_BC_TYPE = 4, BDP_E_BC_WALK = 5, BDP_E_BC_PACK = 6 };
+// where a template begins: BDP_TPL_WRITER -- in the writer's order, by the flags (bdp_head); BDP_TPL_NAME -- where the read name changes (csrc/bam_post_core.h), for
+// files of other programs, whose records of one name are adjacent in any order
+enum { BDP_TPL_WRITER = 0, BDP_TPL_NAME = 1 };
 
 // a run's read groups: the IDs back to back (no terminators) with offsets id_off [n + 1], and every group's library index (below BDP_MAX_LIBS)
 struct bdp_groups_t { const char *ids; const uint32_t *id_off; const uint8_t *lib; uint32_t n; };

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <numeric>
 #include "bam_dup.h"
+#include "bam_post_core.h"
 #ifndef BDP_STANDALONE
 #include "bam_sort.h"
 #endif
@@ -63,17 +64,34 @@ int bdp_group_check(int edits, uint64_t max_set, const char *fn, bdp_bc_t *bc)
 
 uint64_t bdp_no_barcode(const uint64_t *B, uint64_t T) { uint64_t c = 0; for (uint64_t t = 0; t < T; ++t) c += B[t] == 0; return c; }
 
-int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *fn, bool barcode, bool pack)
+int bdp_batch_verdict(uint32_t n, const uint32_t *info, bool groups, bool barcode, bool pack, uint32_t *bad_out)
 {
-	if (!n) return BMH_OK;
+	*bad_out = 0;
+	if (!n) return BDP_E_OK;
 	// (the smallest record index wins, as a walk from the front would find it)
-	if (info[1] == 0) return bdp_batch_refused(n, n + 1, fn);
+	if (info[1] == 0) { *bad_out = n + 1; return BDP_E_TEMPLATE; }
 	uint32_t bad = info[1]; int st = BDP_E_TEMPLATE;
 	if (groups) for (int k = 0; k < 2; ++k) if (info[4 + k] < bad) { bad = info[4 + k]; st = k ? BDP_E_RG_UNKNOWN : BDP_E_NO_RG; }
 	if (barcode) for (int k = 0; k < 2; ++k) if (info[6 + k] < bad) { bad = info[6 + k]; st = k ? BDP_E_BC_WALK : BDP_E_BC_TYPE; }
 	if (barcode && pack && info[8] < bad) { bad = info[8]; st = BDP_E_BC_PACK; }
-	if (bad == 0xffffffffu) return BMH_OK;
+	if (bad == 0xffffffffu) return BDP_E_OK;
+	*bad_out = bad;
+	return st;
+}
+
+int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *fn, bool barcode, bool pack)
+{
+	uint32_t bad = 0;
+	const int st = bdp_batch_verdict(n, info, groups, barcode, pack, &bad);
+	if (st == BDP_E_OK) return BMH_OK;
 	return st == BDP_E_TEMPLATE ? bdp_batch_refused(n, bad, fn) : st >= BDP_E_BC_TYPE ? bdp_barcode_refused(bad - 1, st, fn) : bdp_group_refused(bad - 1, st, fn);
+}
+
+int bdp_name_refused(uint64_t rec, const char *fn)
+{
+	bmh_set_error("%s: duplicate marking: the records under the read name of record %llu, which lie next to each other, are paired and are not one 0x40 and one 0x80 primary line: "
+	              "marking needs the records of a read name next to each other (a coordinate-sorted file has them apart: sort it by name first, or realign it with --collate)", fn, (unsigned long long)rec);
+	return BMH_EINVAL;
 }
 
 int bdp_table_make(bdp_table_t &T, const char *const *ids, const int32_t *lib, int n, const char *fn)
@@ -105,18 +123,19 @@ int bdp_refs_fit(const uint8_t *recs, const uint64_t *off, uint32_t n, const cha
 }
 
 int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::vector<uint32_t> &tpl, std::vector<bdp_entry_t> &entries, uint64_t info[2], const char *fn, const bdp_plan_t &P,
-                     std::vector<bdp_loc_t> *locs, std::vector<uint64_t> *bcs)
+                     std::vector<bdp_loc_t> *locs, std::vector<uint64_t> *bcs, int tpl_rule, uint64_t rec_base)
 {
+	const bool by_name = tpl_rule == BDP_TPL_NAME;
 	const bdp_bc_t *bc = bcs ? P.barcode() : nullptr;
 	const bdp_groups_t G = P.table.view();
 	tpl.resize(n); entries.clear();
 	if (locs) locs->clear();
 	if (bcs) bcs->clear();
-	if (n && !bdp_head(bsr_flag(recs + off[0]))) return bdp_batch_refused(n, n + 1, fn);
+	if (n && !by_name && !bdp_head(bsr_flag(recs + off[0]))) return bdp_batch_refused(n, n + 1, fn);
 	std::vector<uint32_t> start;
 	for (uint32_t i = 0; i < n; ++i) {
 		const uint32_t fl = bsr_flag(recs + off[i]);
-		if (bdp_head(fl)) start.push_back(i);
+		if (by_name ? bpo_head(recs, off, i) : bdp_head(fl)) start.push_back(i);
 		tpl[i] = (uint32_t)start.size() - 1;
 		if (fl & 0x900u) ++info[0];
 		if (fl & 4u) ++info[1];
@@ -129,12 +148,12 @@ int bdp_entries_host(const uint8_t *recs, const uint64_t *off, uint32_t n, std::
 		const uint32_t a = start[t], b = t + 1 < start.size() ? start[t + 1] : n;
 		uint32_t role = 0, row = 0;
 		const int st = P.groups() ? bdp_entry_lib(recs, off, a, b, G, &entries[t], &role, &row) : bdp_entry(recs, off, a, b, &entries[t], &role) ? BDP_E_OK : BDP_E_TEMPLATE;
-		if (st == BDP_E_TEMPLATE) return bdp_batch_refused(n, a + 1, fn);
-		if (st != BDP_E_OK) return bdp_group_refused(a, st, fn);
+		if (st == BDP_E_TEMPLATE) return by_name ? bdp_name_refused(rec_base + a, fn) : bdp_batch_refused(n, a + 1, fn);
+		if (st != BDP_E_OK) return bdp_group_refused((uint32_t)(rec_base + a), st, fn);
 		if (locs) (*locs)[t] = bdp_location(recs + off[a], role, row, bc && bc->mode == BDP_BC_NAME);
 		if (bc) {
 			const int bs = bdp_barcode(recs + off[a], off[a + 1] - off[a], *bc, &(*bcs)[t], bc->pack != 0);
-			if (bs != BDP_AUX_FOUND) return bdp_barcode_refused(a, bs == BDP_AUX_TYPE ? BDP_E_BC_TYPE : bs == BDP_AUX_PACK ? BDP_E_BC_PACK : BDP_E_BC_WALK, fn);
+			if (bs != BDP_AUX_FOUND) return bdp_barcode_refused((uint32_t)(rec_base + a), bs ==BDP_AUX_TYPE ? BDP_E_BC_TYPE : bs == BDP_AUX_PACK ? BDP_E_BC_PACK : BDP_E_BC_WALK, fn);
 		}
 	}
 	return BMH_OK;

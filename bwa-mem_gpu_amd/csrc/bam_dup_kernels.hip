@@ -556,7 +556,7 @@ bdp_dev_t *bdp_dev_create(void) { return new bdp_dev_t(); }
 void bdp_dev_free(bdp_dev_t *d) { delete d; }
 
 int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off, uint32_t n, uint64_t total, void *stream, const uint32_t **d_tpl, const bdp_entry_t **d_entries, const uint32_t **d_info,
-                     const bdp_loc_t **d_locs, const bdp_bc_t *bc, const uint64_t **d_bcs)
+                     const bdp_loc_t **d_locs, const bdp_bc_t *bc, const uint64_t **d_bcs, int tpl_rule)
 {
 	const bool want_bc = bc && bc->mode != BDP_BC_OFF;
 	if (want_bc && !d_bcs) { bmh_set_error("duplicate marking: internal error: barcodes without a place for their words"); return BMH_EINVAL; }
@@ -570,7 +570,8 @@ int bdp_batch_device(bdp_dev_t *d, const uint8_t *d_recs, const uint64_t *d_off,
 	static const uint32_t init[BDP_INFO_WORDS_PACK] = {0u, 0xffffffffu, 0u, 0u, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
 	HIPCK(hipMemcpyAsync(d->info.p, init, 4 * (pack ? BDP_INFO_WORDS_PACK : BDP_INFO_WORDS), hipMemcpyHostToDevice, st));
 	if (n) {
-		bdp_heads<<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, (uint32_t *)d->head.p, (uint32_t *)d->info.p);
+		if (tpl_rule == BDP_TPL_NAME) RCK(bpo_heads_device(d_recs, d_off, n, total, (uint32_t *)d->head.p, (uint32_t *)d->info.p, stream));
+		else bdp_heads<<<blocks(n), 256, 0, st>>>(d_recs, d_off, n, total, (uint32_t *)d->head.p, (uint32_t *)d->info.p);
 		HIPCK(rocprim::inclusive_scan(d->tmp.p, tb, (uint32_t *)d->head.p, (uint32_t *)d->tpl.p, (size_t)n, rocprim::plus<uint32_t>(), st));
 		bdp_starts<<<blocks(n), 256, 0, st>>>((const uint32_t *)d->head.p, (uint32_t *)d->tpl.p, n, (uint32_t *)d->start.p, (uint32_t *)d->info.p);
 		const bdp_groups_t G = {(const char *)d->g_ids.p, (const uint32_t *)d->g_off.p, (const uint8_t *)d->g_lib.p, d->g_n};

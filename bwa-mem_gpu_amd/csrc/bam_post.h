@@ -1,0 +1,52 @@
+// Sort, mark and index a BAM or SAM of any aligner, internal: the input and the run that csrc/bam_post.cpp (the reader, the checks' words, the host
+// form) and csrc/bam_post_kernels.hip (the kernels, the device form) share.
+#pragma once
+#include <stdint.h>
+#include <functional>
+#include <string>
+#include <vector>
+#include "bmh_internal.h"
+#include "bam_sort.h"
+#include "bam_dup.h"
+#include "bam_cov.h"
+#include "bam_post_core.h"
+
+#define BPO_BATCH_DEFAULT (256ull << 20)
+#define BPO_BATCH_MAX (1ull << 30)
+
+// SAM record lines (every line ends with '\n', but perhaps the input's last) -> their records appended to recs; *bad: the first refused line (or ~0u) and *status why
+typedef std::function<int(const char *text, size_t n, int n_contigs, const std::string &ctg_blob, const std::vector<uint32_t> &ctg_noff, std::vector<uint8_t> &recs, uint32_t *bad, uint32_t *status)> bpo_convert_t;
+
+// The input: its header, and its records batch by batch in file order.  A batch ends at the first template head (BDP_TPL_NAME: the name differs from the
+// predecessor's) at or beyond batch_bytes, found by comparing names forward from there, so no template is split -- across the windows the bytes arrive in either
+struct bpo_input_t {
+	bmh_text_src_t *src = nullptr; std::string path; bool bam = false, eof = false, src_eof = false;
+	std::string header;                                                // the output header's text
+	std::vector<std::string> names; std::vector<int32_t> len; std::string ctg_blob; std::vector<uint32_t> ctg_noff;
+	std::vector<uint8_t> buf; size_t have = 0, taken = 0;                // record bytes not handed out yet: buf [0, have); the last batch: buf [0, taken)
+	std::vector<uint32_t> chain; size_t chunk = 8u << 20;
+	std::vector<uint64_t> off; uint32_t n = 0; uint64_t base = 0;       // the batch: records buf + off [i], i < n; base: the file index of its first
+	std::string text; uint64_t lines = 0; bpo_convert_t convert;         // SAM: text not converted yet, the lines before it
+	~bpo_input_t() { if (src) bmh_text_close(src); }
+	int open(const char *p, const char *fn, bpo_convert_t conv);
+	int next(uint64_t batch_bytes, const char *fn);                    // 1: a batch; 0: the end; < 0: refused
+private:
+	int fill(const char *fn);
+	int sam_header(const char *fn);
+	int bam_header(const char *fn);
+};
+
+// one run: the options as checked, the marking plan, the coverage plan, the index, the counts
+struct bpo_run_t {
+	const char *fn = ""; bmh_bam_post_opt_t o; bool markdup = false, coverage = false; uint32_t mode = 0;
+	bmh_markdup_opt_t mo; bmh_rg_table_t rg; std::vector<const char *> rg_ids;
+	bdp_plan_t P; bcv_plan_t CP; bsr_index_t ix; bpo_input_t in; bmh_bam_post_counts_t counts = {0, 0, 0, 0, 0, 0};
+	std::vector<const char *> name_ptr;
+	int begin(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res, bmh_coverage_t *cov, const char *f, bpo_convert_t conv);
+	int header_members(std::string &members) const;                    // the header as BGZF members of the run's level
+	int finish(const std::string &index_bytes, bmh_bam_post_result_t *out) const;     // the results' arrays (malloc'd)
+};
+// the message of the record with file index `index` that bpo_check refuses with `code` (rec: its sz bytes)
+int bpo_refused(const char *fn, uint64_t index, int code, const uint8_t *rec, uint64_t sz, int n_ref);
+// the first record of the template that holds record i of a batch: the templates before it are whole and can still be judged
+uint32_t bpo_template_start(const uint8_t *recs, const uint64_t *off, uint32_t i);

@@ -1129,6 +1129,52 @@ int bmh_aligner_set_coverage(bmh_aligner_t *a, const bmh_coverage_opt_t *opt);
 int bmh_aligner_coverage(bmh_aligner_t *a, bmh_coverage_t *out);
 int bmh_aligner_coverage_ms(bmh_aligner_t *a, double *out, uint64_t *windows);
 
+/* ---- Sort, mark duplicates and index a BAM or SAM that any aligner wrote (csrc/bam_post_core.h, csrc/bam_post_kernels.hip, csrc/bam_post.cpp).
+ * No index and no aligner handle: the input (a regular file or a pipe; BAM -- BGZF whose text begins "BAM\1" -- or SAM text, plain, gzip or BGZF, told apart by
+ * their bytes) is read in order, inflated on host threads, cut into batches of about batch_bytes record bytes that end where a read name ends, and every batch
+ * becomes a sorted run as a batch of the aligner does; at the end of the input the runs are merged into the coordinate-sorted file (header members, record
+ * members in windows, the end-of-file member: all of it goes to the sink) with its index, the duplicates marked and the coverage computed as
+ * BMH_OUT_BAM_SORTED, bmh_aligner_set_markdup and bmh_aligner_set_coverage do it -- the same calls underneath, so this aligner's own unsorted BAM or SAM gives
+ * byte for byte the file of its sorted run.
+ * The header's text is the input's with every @HD line removed and "@HD\tVN:1.6\tSO:coordinate\n" in front, nothing else added; the references are the BAM's
+ * binary table, or the SAM's @SQ lines (SN, LN) in order -- a SAM without one is refused.  Records stay verbatim but for the bin (recomputed: reg2bin(pos, end),
+ * 4680 for pos -1) and, with marking, flag 0x400 (cleared first, then set by the decision).  Equal keys stay in input order over the whole file.
+ * A template is a maximal run of adjacent records under one read name, in any order inside it (BDP_TPL_NAME); its ordinal is its place in the input.
+ * Refused with BMH_EINVAL, by the record's index in the file (SAM: the line's number), the smallest first, before anything is written: a record that is not
+ * whole; refID or next_refID outside -1 .. n_ref - 1; a SAM line the converter refuses (bmh_bam_status_name's words); with marking: the primary lines of a paired
+ * name that are not one 0x40 and one 0x80 record (a file that is not grouped by name, such as a coordinate-sorted one), a mapped primary line with refID or pos
+ * -1, an unclipped 5' end u with u + 2^30 outside [0, 2^31); with marking or coverage: a record that holds the long-CIGAR placeholder.  The contig-length
+ * refusals of the sorted output hold (BAI below 2^29, marking at most 2^30 - 2^24, the CSI window count).  The result does not depend on batch_bytes, window,
+ * sort_mem or spilling.
+ * opt (NULL: the defaults): level 0 or 1; window: records per window of the merge (0: about 64 MiB); index_format, min_shift: BMH_INDEX_*; sort_mem: record
+ * bytes kept in memory before runs spill to an unnamed file in tmp_dir (0: 4 GiB; NULL: $TMPDIR, else /tmp); batch_bytes (0: 256 MiB; at most 1 GiB);
+ * markdup: the marking options or NULL; libraries != 0 (needs markdup, whose rg_ids stay NULL): the header's @RG lines are the table of libraries, by
+ * bmh_bam_header_read_groups' rules with markdup on, and res->lib_* (or NULL) then hold room for 255 libraries; coverage: its options or NULL.
+ * out (zeroed first; bmh_bam_post_result_free releases it; a refused call leaves its pointers NULL): the index bytes, the output header's text, the references
+ * (names NUL-terminated back to back), with libraries their names likewise, and the counts: records, templates, batches, runs spilled, records whose bin
+ * changed, records whose 0x400 was cleared.  res: required with markdup; cov: required with coverage (bmh_free its arrays).
+ * The host form does the same with the host forms of every step and no device; it holds the whole record stream in memory. */
+typedef struct {
+	int32_t level; uint32_t window; int32_t index_format, min_shift;
+	uint64_t sort_mem; const char *tmp_dir; uint64_t batch_bytes;
+	const bmh_markdup_opt_t *markdup; int32_t libraries;
+	const bmh_coverage_opt_t *coverage;
+} bmh_bam_post_opt_t;
+typedef struct { uint64_t records, templates, batches, spilled_runs, bins_changed, dup_flags_cleared; } bmh_bam_post_counts_t;
+typedef struct {
+	uint8_t *index; uint64_t index_bytes;
+	char *header_text; uint64_t header_bytes;
+	int32_t n_contigs; char *contig_names; int32_t *contig_len;
+	int32_t n_libraries; char *library_names;
+	bmh_bam_post_counts_t counts;
+} bmh_bam_post_result_t;
+void bmh_bam_post_opt_default(bmh_bam_post_opt_t *o);
+void bmh_bam_post_result_free(bmh_bam_post_result_t *r);
+int bmh_bam_post_file_device(const char *path, const bmh_bam_post_opt_t *opt, void *stream, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out,
+                             bmh_markdup_counts_t *res, bmh_coverage_t *cov);
+int bmh_bam_post_file_host(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res,
+                           bmh_coverage_t *cov);
+
 #ifdef __cplusplus
 }
 #endif
