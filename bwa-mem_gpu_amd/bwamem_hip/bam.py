@@ -15,9 +15,13 @@ metrics table has a row per library; the rules and refusals of `bwamem_hip.mem -
 sorted run; 256 MiB, at most 1 GiB; no output depends on it), --host (the host forms of every step: no device is needed, and the whole record stream is held in
 memory) and --device (the torch device, cuda:0).
 
---markdup needs the records of a read name next to each other, in any order -- what every aligner writes.  A file that has them apart, such as a coordinate-sorted
-one, is sorted and indexed without --markdup and refused with it, by the index of the first record whose name holds no proper pair.  A refused input ends the
-command with status 1 and the library's message on stderr.
+--markdup alone needs the records of a read name next to each other, in any order -- what every aligner writes.  A file that has them apart, such as a
+coordinate-sorted one, takes --markdup --collate: templates are then the records of the whole file under one read name, adjacent or not, numbered by their first
+records (BDP_TPL_FILE).  --collate needs --markdup, works with every other option, and keeps 32 bytes per record in host memory (48 / 56 with
+--optical-distance / barcodes) until the last batch is in; a name whose records are no proper template -- a pair without exactly one 0x40 and one 0x80 primary
+line, two templates under one name -- is refused by the index of its first record.  On a name-grouped file with distinct names the output is that without it.
+Without --collate such a file is sorted and indexed without --markdup and refused with it.  A refused input ends the command with status 1 and the library's
+message on stderr.
 """
 from __future__ import annotations
 
@@ -26,10 +30,11 @@ import sys
 
 def bam_post_file(src, out, index=None, host: bool = False, level: int = 1, sort_window: int = 0, sort_mem=None, sort_tmp=None, batch_bytes=None, index_format: str = "bai",
                   csi_min_shift: int = 14, markdup: bool = False, markdup_metrics=None, libraries: bool = False, optical_distance=None, barcode_tag=None, barcode_name=None,
-                  barcode_edits=None, coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False) -> dict:
+                  barcode_edits=None, coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False, collate: bool = False) -> dict:
     """the BAM or SAM file `src` (a path; "-": stdin) -> the coordinate-sorted BAM written to `out` (a binary file object), its index to `index` (a path or a binary
     file object; None: not written), the metrics table to `markdup_metrics` and the coverage texts to coverage / coverage_hist / coverage_bed (paths or text file
-    objects), as Aligner.align_files(sort=True, ...) writes them.  Returns lib.bam_post's dict.  The keywords are align_files' and are refused as there."""
+    objects), as Aligner.align_files(sort=True, ...) writes them.  Returns lib.bam_post's dict.  The keywords are align_files' and are refused as there.
+    collate=True (needs markdup=True): templates by name over the whole file, for an input that is not grouped by name (lib.bam_post)."""
     from .aligner import coverage_request, coverage_table_text, coverage_hist_text, coverage_bed_text, markdup_metrics_text, markdup_metrics_text_libraries, _write_text
     from .lib import bam_post
     if not ("b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")):
@@ -39,7 +44,7 @@ def bam_post_file(src, out, index=None, host: bool = False, level: int = 1, sort
     req = coverage_request("bam_post_file", True, coverage, coverage_hist, coverage_bed, coverage_bin, coverage_min_mapq, coverage_deletions)
     r = bam_post("/dev/stdin" if src == "-" else src, out.write, host=host, level=level, window=sort_window, index_format=index_format, csi_min_shift=csi_min_shift, sort_mem=sort_mem,
                  sort_tmp=sort_tmp, batch_bytes=batch_bytes, markdup=markdup, libraries=libraries, optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name,
-                 barcode_edits=barcode_edits, coverage=None if req is None else dict(min_mapq=req["min_mapq"], deletions=req["deletions"], bin=req["bin"]))
+                 barcode_edits=barcode_edits, coverage=None if req is None else dict(min_mapq=req["min_mapq"], deletions=req["deletions"], bin=req["bin"]), collate=collate)
     if index is not None:
         if hasattr(index, "write"):
             index.write(r["index"])
@@ -73,7 +78,7 @@ def main(argv=None) -> int:
     i = 0
     while i < len(argv):
         a = argv[i]
-        if a in ("--markdup", "--barcode-name", "--coverage-deletions", "--csi", "--libraries", "--host"):
+        if a in ("--markdup", "--barcode-name", "--coverage-deletions", "--csi", "--libraries", "--host", "--collate"):
             flags.add(a)
         elif a in _VALUED:
             if i + 1 >= len(argv):
@@ -103,6 +108,7 @@ def main(argv=None) -> int:
               ("--optical-distance" in v and not markdup, "--optical-distance needs --markdup (optical duplicates are counted where duplicates are marked)"),
               ("--barcode-edits" in v and not markdup, "--barcode-edits needs --markdup (barcodes are grouped where duplicates are marked)"),
               ("--barcode-edits" in v and "--barcode-tag" not in v and "--barcode-name" not in flags, "--barcode-edits needs --barcode-tag or --barcode-name (it groups the barcodes that are compared)"),
+              ("--collate" in flags and not markdup, "--collate needs --markdup (templates by name over the whole file are formed where duplicates are marked)"),
               ("--libraries" in flags and not markdup, "--libraries needs --markdup (the libraries say which templates may be duplicates of each other)"),
               (("--coverage-bed" in cov_paths) != ("--coverage-bin" in v), "--coverage-bed and --coverage-bin go together (the bins of the BED file)"),
               (("--coverage-min-mapq" in v or "--coverage-deletions" in flags) and not cov_paths,
@@ -136,7 +142,7 @@ def main(argv=None) -> int:
                       markdup_metrics=v.get("--markdup-metrics"), libraries="--libraries" in flags, optical_distance=v.get("--optical-distance"), barcode_tag=v.get("--barcode-tag"),
                       barcode_name=True if "--barcode-name" in flags else None, barcode_edits=v.get("--barcode-edits"), coverage=cov_paths.get("--coverage"),
                       coverage_hist=cov_paths.get("--coverage-hist"), coverage_bed=cov_paths.get("--coverage-bed"), coverage_bin=v.get("--coverage-bin"),
-                      coverage_min_mapq=v.get("--coverage-min-mapq"), coverage_deletions="--coverage-deletions" in flags)
+                      coverage_min_mapq=v.get("--coverage-min-mapq"), coverage_deletions="--coverage-deletions" in flags, collate="--collate" in flags)
         out.flush()
     except (ValueError, OSError) as e:
         print(f"{me} {e}", file=sys.stderr)

@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = [
     "bmh_coverage_opt_default", "bmh_bam_coverage_device", "bmh_bam_coverage_host", "bmh_bam_sorted_file_coverage_device", "bmh_bam_sorted_file_coverage_host",
     "bmh_aligner_set_coverage", "bmh_aligner_coverage", "bmh_aligner_coverage_ms",
     "bmh_bam_post_opt_default", "bmh_bam_post_result_free", "bmh_bam_post_file_device", "bmh_bam_post_file_host",
+    "bmh_bam_templates_device", "bmh_bam_templates_host", "bmh_bam_templates_free",
 ]
 
 
@@ -882,7 +883,7 @@ def reads_last_bam_counts() -> dict:
 class BamPostOpt(C.Structure):
     """bmh_bam_post_opt_t"""
     _fields_ = [("level", C.c_int32), ("window", C.c_uint32), ("index_format", C.c_int32), ("min_shift", C.c_int32), ("sort_mem", C.c_uint64), ("tmp_dir", C.c_char_p),
-                ("batch_bytes", C.c_uint64), ("markdup", C.POINTER(MarkdupOpt)), ("libraries", C.c_int32), ("coverage", C.POINTER(CoverageOpt))]
+                ("batch_bytes", C.c_uint64), ("markdup", C.POINTER(MarkdupOpt)), ("libraries", C.c_int32), ("coverage", C.POINTER(CoverageOpt)), ("collate", C.c_int32)]
 
 
 class BamPostResult(C.Structure):
@@ -905,13 +906,16 @@ def _names_blob(addr, n: int) -> list:
 
 
 def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 0, index_format: str = "bai", csi_min_shift: int = 14, sort_mem=None, sort_tmp=None, batch_bytes=None,
-             markdup: bool = False, libraries: bool = False, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None) -> dict:
+             markdup: bool = False, libraries: bool = False, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None, collate: bool = False) -> dict:
     """bmh_bam_post_file_device (host=True: bmh_bam_post_file_host, no device needed; it holds the whole record stream in memory): the BAM or SAM file `src` of any
     aligner (a path; plain, gzip or BGZF; a pipe) -> the coordinate-sorted BAM, handed to write(bytes) piece by piece, and a dict: "index" (the .bai or .csi
     bytes), "header" (the output header's text), "contigs" ((name, length) pairs), "counts" (BAM_POST_COUNTS' names), with markdup=True "markdup" (bam_markdup's
     counts; with libraries=True -- the header's @RG lines are the table of libraries -- "libraries" per library), with coverage={min_mapq, deletions, bin, tile}
     "coverage" (bam_coverage's arrays).  DESIGN.md 4.14 has the definition.  The keywords are bam_markdup's and bam_sorted_file's and are refused as there;
-    libraries, optical_distance and the barcode keywords need markdup=True.  A refused input raises ValueError naming the record's index or the line's number."""
+    libraries, optical_distance and the barcode keywords need markdup=True.  A refused input raises ValueError naming the record's index or the line's number.
+    collate=True (needs markdup=True; the library refuses it otherwise): templates by name over the whole file (BDP_TPL_FILE), so that a coordinate-sorted file can
+    be marked -- a template is every record of the file under one read name, adjacent or not; a name whose records are no proper template is refused.  It keeps 32
+    bytes per record in host memory (48 / 56 with optical_distance / barcodes) until the last batch is in."""
     what = "bam_post"
     bc_mode, bc_tag = barcode_source(barcode_tag, barcode_name, what)
     if barcode_edits is not None and not markdup:
@@ -939,7 +943,7 @@ def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 
         res.lib_counts, res.lib_optical, res.lib_grouped = (C.cast(a, _u64p) for a in arrays)
     co = coverage_opt(what=what, **coverage) if coverage is not None else None
     o = BamPostOpt(int(level), int(window), ix_code, ix_shift, int(sort_mem or 0), os.fsencode(sort_tmp) if sort_tmp is not None else None, int(batch_bytes or 0),
-                   C.pointer(mo) if markdup else None, 1 if libraries else 0, C.pointer(co) if co is not None else None)
+                   C.pointer(mo) if markdup else None, 1 if libraries else 0, C.pointer(co) if co is not None else None, 1 if collate else 0)
     failed = []
 
     def sink(_user, p, n):
@@ -977,6 +981,60 @@ def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 
         return r
     finally:
         L.bmh_bam_post_result_free(C.byref(out))
+
+
+class BamTemplates(C.Structure):
+    """bmh_bam_templates_t"""
+    _fields_ = [("n_records", C.c_uint64), ("n_templates", C.c_uint64), ("tpl", C.c_void_p), ("entries", C.c_void_p), ("locs", C.c_void_p), ("barcodes", C.c_void_p),
+                ("counts", C.c_uint64 * 3), ("lib_counts", C.c_void_p), ("n_libraries", C.c_int32)]
+
+
+ENTRY_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8"), ("score", "<u4"), ("kind_n", "<u4")])                   # bdp_entry_t; kind_n: kind (0 none, 1 fragment, 2 pair) | records << 2
+TEMPLATE_COUNTS = ("secondary_or_supplementary", "unmapped_records", "templates")
+
+
+def bam_templates(records: bytes, host: bool = False, read_groups=None, barcode_tag=None, barcode_name=None, hash_bits: int = 128, barcode_edits=None) -> dict:
+    """bmh_bam_templates_device (host=True: bmh_bam_templates_host, no device needed): the grouping of bam_post(collate=True) on its own (DESIGN.md 4.14,
+    BDP_TPL_FILE).  A stream of whole BAM records in any order -> a dict: "tpl" (every record's template ordinal: templates are the records under one read name,
+    numbered by their first records in stream order), "entries" (ENTRY_DTYPE, one per template), "locations" (LOCATION_DTYPE), with a barcode source "barcodes"
+    (uint64 words; packed with barcode_edits), "counts" (TEMPLATE_COUNTS' names) and with read_groups "libraries" ({library name: the three counts}).  hash_bits
+    (1 .. 128) cuts the 128-bit name keys, so that a test can make two names collide.  A record that marking refuses, a first record without a usable read group
+    or barcode, and a name whose records are no proper template raise ValueError with the record's index."""
+    L = _markdup_api(load_library())
+    records = bytes(records)
+    what = "bam_templates"
+    bc_mode, bc_tag = barcode_source(barcode_tag, barcode_name, what)
+    edits = barcode_edits_value(barcode_edits, bc_mode, what)
+    if not isinstance(hash_bits, (int, np.integer)) or isinstance(hash_bits, bool) or not 1 <= hash_bits <= 128:
+        raise ValueError(f"{what}: hash_bits {hash_bits!r}: an integer in 1 .. 128")
+    o, _res, names, _keep = _markdup_records(L, read_groups, -1, 0, bc_mode, bc_tag, edits, 0)
+    out = BamTemplates()
+    head = [C.c_char_p, C.c_uint64, C.POINTER(MarkdupOpt), C.c_int32]
+    L.bmh_bam_templates_free.argtypes, L.bmh_bam_templates_free.restype = [C.POINTER(BamTemplates)], None
+    if host:
+        L.bmh_bam_templates_host.argtypes = head + [C.POINTER(BamTemplates)]
+        rc = L.bmh_bam_templates_host(records, len(records), C.byref(o), int(hash_bits), C.byref(out))
+    else:
+        import torch
+        L.bmh_bam_templates_device.argtypes = head + [C.c_void_p, C.POINTER(BamTemplates)]
+        rc = L.bmh_bam_templates_device(records, len(records), C.byref(o), int(hash_bits), torch.cuda.current_stream().cuda_stream, C.byref(out))
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_templates: " + _err(L))
+    try:
+        n, t = int(out.n_records), int(out.n_templates)
+
+        def arr(addr, count, dtype):
+            return np.frombuffer(C.string_at(addr, count * np.dtype(dtype).itemsize) if count else b"", dtype=dtype).copy()
+        r = dict(tpl=arr(out.tpl, n, "<u4"), entries=arr(out.entries, t, ENTRY_DTYPE), locations=arr(out.locs, t, LOCATION_DTYPE),
+                 counts=dict(zip(TEMPLATE_COUNTS, (int(v) for v in out.counts))))
+        if bc_mode != BARCODE_OFF:
+            r["barcodes"] = arr(out.barcodes, t, "<u8")
+        if read_groups is not None:
+            lc = arr(out.lib_counts, 3 * int(out.n_libraries), "<u8")
+            r["libraries"] = {nm: dict(zip(TEMPLATE_COUNTS, (int(v) for v in lc[3 * k:3 * k + 3]))) for k, nm in enumerate(names)}
+        return r
+    finally:
+        L.bmh_bam_templates_free(C.byref(out))
 
 
 def bam_header_read_groups(text, markdup: bool = False) -> tuple:

@@ -90,7 +90,8 @@ int bdp_batch_check(uint32_t n, const uint32_t *info, bool groups, const char *f
 int bdp_name_refused(uint64_t rec, const char *fn)
 {
 	bmh_set_error("%s: duplicate marking: the records under the read name of record %llu, which lie next to each other, are paired and are not one 0x40 and one 0x80 primary line: "
-	              "marking needs the records of a read name next to each other (a coordinate-sorted file has them apart: sort it by name first, or realign it with --collate)", fn, (unsigned long long)rec);
+	              "marking needs the records of a read name next to each other (a coordinate-sorted file has them apart: sort it by name first, or realign it with --collate); "
+	              "`python -m bwamem_hip.bam --markdup --collate` marks such a file as it is", fn, (unsigned long long)rec);
 	return BMH_EINVAL;
 }
 

@@ -1,7 +1,8 @@
 // Sort, mark duplicates and index a BAM or SAM that any aligner wrote, on the host (csrc/bam_post_core.h has the rules): the input -- its
 // header, its records in batches that end where a read name ends --, the words of the refusals, the run's options, and bmh_bam_post_file_host, which does with the
 // host forms of every step (bsr_sort_host, bdp_entries_host, bdp_decide_host, bcv_host_t, the host window and index path) what csrc/bam_post_kernels.hip does on
-// the device.  The host form holds the whole record stream in memory.
+// the device.  The host form holds the whole record stream in memory.  With collate (BDP_TPL_FILE, csrc/bam_tpl_core.h) batches are cut at record boundaries, a
+// batch leaves its records' parts instead of entries, and the templates of the whole file are formed behind the last batch (btp_group_host).
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -88,6 +89,7 @@ int bpo_input_t::sam_header(const char *fn)
 		text.append((const char *)tmp.data(), (size_t)g);
 	}
 	text.erase(0, a);
+	header_lines = lines;
 	eof = src_eof && text.empty();
 	hd_first(raw, header);
 	uint64_t line = 0;
@@ -170,7 +172,7 @@ int bpo_input_t::next(uint64_t batch_bytes, const char *fn)
 			// the first record at or beyond batch_bytes, then the first head from there on: records k - 1 and k are both whole
 			if (k < nrec && chain[k] < batch_bytes)
 				k = (size_t)(std::lower_bound(chain.begin() + (ptrdiff_t)k, chain.begin() + (ptrdiff_t)nrec, batch_bytes, [](uint32_t a, uint64_t b) { return a < b; }) - chain.begin());
-			while (k < nrec && bpo_name_equal(buf.data() + chain[k], chain[k + 1] - chain[k], buf.data() + chain[k - 1], chain[k] - chain[k - 1])) ++k;
+			while (!plain && k < nrec && bpo_name_equal(buf.data() + chain[k], chain[k + 1] - chain[k], buf.data() + chain[k - 1], chain[k] - chain[k - 1])) ++k;
 			if (k < nrec || eof) {                                   // (at the end of the input the batch is what is left; bytes behind its last whole record wait for the next call)
 				n = (uint32_t)k; taken = chain[k];
 				off.resize(k + 1);
@@ -237,6 +239,8 @@ int bpo_run_t::begin(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_si
 	if (rc != BMH_OK) return rc;
 	if (!o.batch_bytes) o.batch_bytes = BPO_BATCH_DEFAULT;
 	if (o.batch_bytes > BPO_BATCH_MAX) { bmh_set_error("%s: batch_bytes %llu (at most 2^30; 0: 2^28)", fn, (unsigned long long)o.batch_bytes); return BMH_EINVAL; }
+	collate = o.collate != 0; in.plain = collate;
+	if (collate && !markdup) { bmh_set_error("%s: collate needs marking: templates by name over the whole file are formed where duplicates are marked", fn); return BMH_EINVAL; }
 	if (o.libraries && !markdup) { bmh_set_error("%s: libraries need marking: the header's @RG lines say which templates may be duplicates of each other", fn); return BMH_EINVAL; }
 	if (markdup && !res) { bmh_set_error("%s: null argument (marking needs its counts record)", fn); return BMH_EINVAL; }
 	if (coverage && !cov) { bmh_set_error("%s: null argument (coverage needs its record)", fn); return BMH_EINVAL; }
@@ -318,6 +322,7 @@ namespace {
 struct host_state_t {
 	std::vector<uint8_t> recs; std::vector<uint64_t> off = std::vector<uint64_t>(1, 0);
 	std::vector<uint32_t> tpl; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> locs; std::vector<uint64_t> bcs; uint64_t info[2] = {0, 0};
+	btp_parts_t parts;                                                  // BDP_TPL_FILE: every record's part, until the grouping behind the last batch
 };
 
 int host_batch(bpo_run_t &R, host_state_t &S)
@@ -334,8 +339,9 @@ int host_batch(bpo_run_t &R, host_state_t &S)
 		if (bpo_head(recs, off, i)) ++R.counts.templates;
 	}
 	// a refused record: the templates before the one that holds it are whole, and a refusal among them comes first
-	const uint32_t n_ok = code == BPO_OK ? n : bpo_template_start(recs, off, bad);
-	if (R.markdup && n_ok) {
+	const uint32_t n_ok = code == BPO_OK ? n : R.collate ? 0 : bpo_template_start(recs, off, bad);
+	if (R.collate && code == BPO_OK) for (uint32_t i = 0; i < n; ++i) btp_append_host(S.parts, recs + off[i], off[i + 1] - off[i], R.P, 128);
+	if (R.markdup && n_ok && !R.collate) {
 		std::vector<uint32_t> tpl; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> locs; std::vector<uint64_t> bcs;
 		const bool optical = R.P.optical() != nullptr, barcode = R.P.barcode() != nullptr;
 		const int rc = bdp_entries_host(recs, off, n_ok, tpl, E, S.info, R.fn, R.P, optical ? &locs : nullptr, barcode ? &bcs : nullptr, BDP_TPL_NAME, in.base);
@@ -370,6 +376,13 @@ extern "C" int bmh_bam_post_file_host(const char *path, const bmh_bam_post_opt_t
 			const bdp_plan_t &P = R.P;
 			const bool barcode = P.barcode() != nullptr;
 			std::vector<uint32_t> bits; std::vector<uint64_t> Bp;
+			if (R.collate) {                                           // the templates of the whole file by name, from the records' parts
+				btp_result_t G;
+				if ((rc = btp_group_host(S.parts, R.P, G, fn)) != BMH_OK) return rc;
+				if (G.word != BPO_NONE) return btp_refused(S.parts, G.word, R.P, R.sam_line0(), fn);
+				S.tpl.swap(G.rec_tpl); S.E.swap(G.E); S.locs.swap(G.locs); S.bcs.swap(G.bcs); S.info[0] = G.info[0]; S.info[1] = G.info[1];
+				R.counts.templates = S.E.size();
+			}
 			if (S.E.size() >= 1ull << 31) { bmh_set_error("%s: duplicate marking: 2^31 templates", fn); return BMH_EINVAL; }
 			if (P.no_barcode) *P.no_barcode = barcode ? bdp_no_barcode(S.bcs.data(), S.bcs.size()) : 0;
 			bdp_decide_host(S.E.data(), S.E.size(), bits, res->counts, P, barcode ? S.bcs.data() : nullptr, &Bp);

@@ -27,6 +27,8 @@ struct bpo_input_t {
 	std::vector<uint32_t> chain; size_t chunk = 8u << 20;
 	std::vector<uint64_t> off; uint32_t n = 0; uint64_t base = 0;       // the batch: records buf + off [i], i < n; base: the file index of its first
 	std::string text; uint64_t lines = 0; bpo_convert_t convert;         // SAM: text not converted yet, the lines before it
+	uint64_t header_lines = 0;                                         // SAM: the lines of the header (record i is line header_lines + i + 1)
+	bool plain = false;                                                // BDP_TPL_FILE: a batch ends at the first record at or beyond batch_bytes, no name is compared
 	~bpo_input_t() { if (src) bmh_text_close(src); }
 	int open(const char *p, const char *fn, bpo_convert_t conv);
 	int next(uint64_t batch_bytes, const char *fn);                    // 1: a batch; 0: the end; < 0: refused
@@ -41,6 +43,8 @@ struct bpo_run_t {
 	const char *fn = ""; bmh_bam_post_opt_t o; bool markdup = false, coverage = false; uint32_t mode = 0;
 	bmh_markdup_opt_t mo; bmh_rg_table_t rg; std::vector<const char *> rg_ids;
 	bdp_plan_t P; bcv_plan_t CP; bsr_index_t ix; bpo_input_t in; bmh_bam_post_counts_t counts = {0, 0, 0, 0, 0, 0};
+	bool collate = false;                                              // templates by name over the whole file (BDP_TPL_FILE, csrc/bam_tpl_core.h)
+	uint64_t sam_line0() const { return in.bam ? 0 : in.header_lines + 1; }      // the SAM line of record 0 (0: a BAM)
 	std::vector<const char *> name_ptr;
 	int begin(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res, bmh_coverage_t *cov, const char *f, bpo_convert_t conv);
 	int header_members(std::string &members) const;                    // the header as BGZF members of the run's level

@@ -12,15 +12,20 @@
 // The driver takes the batches of csrc/bam_post.cpp's input: upload, check and fix, with marking the entries (bdp_batch_device under BDP_TPL_NAME, the per-library
 // counts), the sorted run (bsr_sort_run_device, the template ordinals as the side word), the run store; at the end of the input the merge of
 // csrc/bam_sort_kernels.hip with the plan and the coverage state -- the calls the aligner's output stage makes, without an aligner.
+// With collate (BDP_TPL_FILE, csrc/bam_tpl_kernels.hip) a batch makes no entries: it leaves every record's part in the store and sorts with the identity as the side
+// word; behind the last batch the grouping numbers the templates of the whole file, the runs' ordinals are rewritten, and the merge runs unchanged.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <chrono>
 #include <new>
 #include <vector>
 #include "bam_post.h"
 #include "bam_ws.h"
+#include "bam_tpl.h"
 
 namespace {
 
@@ -92,11 +97,11 @@ namespace {
 struct dev_state_t {
 	hipStream_t st = nullptr;
 	dev_buf<uint8_t> recs, off, word; dev_buf<char> text;
-	bsr_dev_t *bsr = nullptr; bdp_dev_t *bdp = nullptr; bmh_bam_ws_t *ws = nullptr, *sam_ws = nullptr; bcv_dev_t *cov = nullptr;
+	bsr_dev_t *bsr = nullptr; bdp_dev_t *bdp = nullptr; bmh_bam_ws_t *ws = nullptr, *sam_ws = nullptr; bcv_dev_t *cov = nullptr; btp_dev_t *btp = nullptr;
 	dev_buf<char> ctg_names; dev_buf<uint32_t> ctg_noff; bool ctg_up = false;
 	bsr_store_t store;
 	std::vector<uint8_t> sorted; std::vector<uint64_t> keys, soff, bcs; std::vector<uint32_t> stpl, lib3; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> locs;
-	~dev_state_t() { if (bsr) bsr_dev_free(bsr); if (bdp) bdp_dev_free(bdp); if (ws) bmh_bam_ws_free(ws); if (sam_ws) bmh_bam_ws_free(sam_ws); if (cov) bcv_dev_free(cov); }
+	~dev_state_t() { if (bsr) bsr_dev_free(bsr); if (bdp) bdp_dev_free(bdp); if (ws) bmh_bam_ws_free(ws); if (sam_ws) bmh_bam_ws_free(sam_ws); if (cov) bcv_dev_free(cov); if (btp) btp_dev_free(btp); }
 };
 
 // SAM lines through the device's converter; the records come back to the host, where the chain and the batches are made as for a BAM
@@ -157,18 +162,20 @@ int device_batch(bpo_run_t &R, dev_state_t &D)
 	HIPCK(hipStreamSynchronize(D.st));
 	const uint32_t *d_tpl = nullptr, *d_stpl = nullptr, *d_lib3 = nullptr; const bdp_entry_t *d_e = nullptr; const bdp_loc_t *d_l = nullptr; const uint64_t *d_b = nullptr;
 	uint32_t info[BDP_INFO_WORDS_PACK] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-	if (R.markdup && !D.bdp) { if (!(D.bdp = bdp_dev_create())) return BMH_ENOMEM; RCK(bdp_dev_set_groups(D.bdp, R.P.groups(), D.st)); }
+	if (R.collate && !D.btp) { if (!(D.btp = btp_dev_create())) return BMH_ENOMEM; RCK(btp_dev_set_groups(D.btp, R.P.groups(), D.st)); }
+	if (R.markdup && !R.collate && !D.bdp) { if (!(D.bdp = bdp_dev_create())) return BMH_ENOMEM; RCK(bdp_dev_set_groups(D.bdp, R.P.groups(), D.st)); }
 	if (w[0] != BPO_NONE) {
 		// a refused record: the templates before the one that holds it are whole, and a refusal among them comes first
 		const uint32_t bad = (uint32_t)(w[0] >> 3); const int code = (int)(w[0] & 7u);
 		if (bad >= n) { bmh_set_error("%s: internal error: record %u of %u refused", R.fn, bad, n); return BMH_EINVAL; }
-		const uint32_t n_ok = bpo_template_start(in.buf.data(), in.off.data(), bad);
+		const uint32_t n_ok = R.collate ? 0 : bpo_template_start(in.buf.data(), in.off.data(), bad);
 		if (R.markdup && n_ok) RCK(entries_device(R, D, n_ok, in.off[n_ok], &d_tpl, &d_e, &d_l, &d_b, info, nullptr));
 		return bpo_refused(R.fn, in.base + bad, code, in.buf.data() + in.off[bad], in.off[bad + 1] - in.off[bad], n_ref);
 	}
 	R.counts.bins_changed += w[1]; R.counts.dup_flags_cleared += w[2]; R.counts.templates += w[3];
 	const bool optical = R.P.optical() != nullptr, barcode = R.P.barcode() != nullptr, groups = R.P.groups() != nullptr;
-	if (R.markdup) RCK(entries_device(R, D, n, total, &d_tpl, &d_e, &d_l, &d_b, info, &d_lib3));
+	if (R.collate) RCK(btp_parts_device(D.btp, D.recs.p, (const uint64_t *)D.off.p, n, total, R.P, 128, D.st, D.store.tpl_parts, &d_tpl));
+	else if (R.markdup) RCK(entries_device(R, D, n, total, &d_tpl, &d_e, &d_l, &d_b, info, &d_lib3));
 	const uint8_t *ds = nullptr; const uint64_t *dk = nullptr, *dso = nullptr;
 	RCK(bsr_sort_run_device(D.bsr, D.recs.p, (const uint64_t *)D.off.p, n, total, D.st, &ds, &dk, &dso, d_tpl, &d_stpl));
 	D.sorted.resize((size_t)total + 1); D.keys.resize((size_t)n + 1); D.soff.resize((size_t)n + 2);
@@ -176,7 +183,8 @@ int device_batch(bpo_run_t &R, dev_state_t &D)
 	HIPCK(hipMemcpyAsync(D.keys.data(), dk, 8 * (size_t)n, hipMemcpyDeviceToHost, D.st));
 	HIPCK(hipMemcpyAsync(D.soff.data(), dso, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, D.st));
 	const uint32_t nt = R.markdup ? info[0] : 0;
-	if (R.markdup) {
+	if (R.collate) { D.stpl.resize(n); D.E.clear(); HIPCK(hipMemcpyAsync(D.stpl.data(), d_stpl, 4 * (size_t)n, hipMemcpyDeviceToHost, D.st)); }
+	else if (R.markdup) {
 		D.stpl.resize(n); D.E.resize(nt);
 		HIPCK(hipMemcpyAsync(D.stpl.data(), d_stpl, 4 * (size_t)n, hipMemcpyDeviceToHost, D.st));
 		HIPCK(hipMemcpyAsync(D.E.data(), d_e, sizeof(bdp_entry_t) * (size_t)nt, hipMemcpyDeviceToHost, D.st));
@@ -187,10 +195,11 @@ int device_batch(bpo_run_t &R, dev_state_t &D)
 	HIPCK(hipStreamSynchronize(D.st));
 	if (D.soff[n] != total) { bmh_set_error("%s: internal error: the sorted run holds %llu bytes, the batch's records %llu", R.fn, (unsigned long long)D.soff[n], (unsigned long long)total); return BMH_EINVAL; }
 	bsr_dup_t bd = {D.stpl.data(), D.E.data(), nt, info[2], info[3]};
-	if (groups) { bd.lib3 = D.lib3.data(); bd.n_lib3 = R.P.table.n_lib; }
-	if (optical) bd.locs = D.locs.data();
-	if (barcode) bd.bcs = D.bcs.data();
+	if (groups && !R.collate) { bd.lib3 = D.lib3.data(); bd.n_lib3 = R.P.table.n_lib; }
+	if (optical && !R.collate) bd.locs = D.locs.data();
+	if (barcode && !R.collate) bd.bcs = D.bcs.data();
 	RCK(D.store.append(D.sorted.data(), total, D.keys.data(), D.soff.data(), n, R.markdup ? &bd : nullptr));
+	if (R.collate) D.store.runs.back().tbase = in.base;                // (tpl holds batch indices: the file index of a record is tbase + tpl [i])
 	R.counts.records += n; ++R.counts.batches;
 	return BMH_OK;
 }
@@ -209,8 +218,26 @@ int post_device(const char *fn, const char *path, const bmh_bam_post_opt_t *opt,
 	if (R.o.sort_mem) D.store.mem_bytes = R.o.sort_mem;
 	if (R.o.tmp_dir) D.store.tmp_dir = R.o.tmp_dir;
 	int rc;
+	const bool trace = getenv("BMH_ALIGNER_TRACE") != nullptr;
+	auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+	const double t_begin = now_ms();
 	while ((rc = R.in.next(R.o.batch_bytes, fn)) == 1) RCK(device_batch(R, D));
 	if (rc < 0) return rc;
+	const double t_batches = now_ms();
+	if (R.collate) {                                                   // the templates of the whole file by name: the grouping, then the runs' ordinals rewritten
+		if (!D.btp && !(D.btp = btp_dev_create())) return BMH_ENOMEM;
+		btp_result_t G;
+		RCK(btp_group_device(D.btp, D.store.tpl_parts, R.P, D.st, G, fn));
+		if (G.word != BPO_NONE) return btp_refused(D.store.tpl_parts, G.word, R.P, R.sam_line0(), fn);
+		if (G.rec_tpl.size() != R.counts.records) { bmh_set_error("%s: internal error: %zu ordinals for %llu records", fn, G.rec_tpl.size(), (unsigned long long)R.counts.records); return BMH_EINVAL; }
+		D.store.retemplate(G.rec_tpl);
+		D.store.entries.swap(G.E); D.store.locs.swap(G.locs); D.store.bcs.swap(G.bcs); D.store.lib_info.swap(G.lib3);
+		D.store.dup_info[0] = G.info[0]; D.store.dup_info[1] = G.info[1];
+		D.store.tpl_parts = btp_parts_t();                             // (their memory goes back before the merge takes its own)
+		R.counts.templates = D.store.entries.size();
+		btp_dev_free(D.btp); D.btp = nullptr;
+	}
+	const double t_grouped = now_ms();
 	std::string members;
 	RCK(R.header_members(members));
 	if (sink(user, members.data(), members.size()) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; }
@@ -231,6 +258,9 @@ int post_device(const char *fn, const char *path, const bmh_bam_post_opt_t *opt,
 	std::string ib;
 	RCK(R.ix.bytes(members.size(), ib));
 	if (R.coverage) RCK(bcv_export(R.CP, CR, cov, fn));
+	if (trace)
+		fprintf(stderr, "[bam post] %llu records in %llu batches: read, checked and sorted in %.1f ms, templates by name over the file in %.1f ms, merged in %.1f ms\n",
+		        (unsigned long long)R.counts.records, (unsigned long long)R.counts.batches, t_batches - t_begin, t_grouped - t_batches, now_ms() - t_grouped);
 	return R.finish(ib, out);
 }
 

@@ -6,6 +6,7 @@
 #include "bmh_internal.h"
 #include "bam_sort_core.h"
 #include "bam_dup.h"
+#include "bam_tpl.h"
 
 typedef int (*bsr_sink_t)(void *user, const char *bytes, size_t n);
 
@@ -54,6 +55,12 @@ struct bsr_store_t {
 	std::vector<bdp_loc_t> locs;                                             // ... when optical duplicates are counted: every template's location beside its entry (else empty)
 	std::vector<uint64_t> bcs;                                               // ... when barcodes are compared: every template's barcode word beside its entry (else empty)
 	std::vector<uint64_t> lib_info;                                          // ... with read groups, per library: those two and the templates [3 * libraries]
+	// templates by name over the whole file (BDP_TPL_FILE, csrc/bam_tpl_core.h): every record's part in file order -- host memory outside the budget, like the keys:
+	// 32 bytes per record (16 and 8 more with locations and barcodes), never spilled.  A run's tpl then holds the records' batch indices in sorted order and tbase
+	// the file index of the batch's first record, until retemplate
+	btp_parts_t tpl_parts;
+	// rec_tpl [records of the file]: every record's template ordinal -> every run's tpl [i] = rec_tpl [tbase + tpl [i]], tbase = 0: what the merge reads
+	void retemplate(const std::vector<uint32_t> &rec_tpl);
 	~bsr_store_t() { clear(); }
 	void clear();
 	int append(const uint8_t *recs, uint64_t bytes, const uint64_t *keys, const uint64_t *off, uint64_t n, const bsr_dup_t *dup = nullptr);

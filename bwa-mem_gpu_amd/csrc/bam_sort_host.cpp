@@ -211,7 +211,7 @@ void bsr_store_t::clear()
 {
 	for (bsr_run_t &r : runs) free(r.mem);
 	runs.clear(); used = 0; spilled = 0; file_bytes = 0;
-	entries.clear(); locs.clear(); bcs.clear(); dup_info[0] = dup_info[1] = 0; lib_info.clear();
+	entries.clear(); locs.clear(); bcs.clear(); dup_info[0] = dup_info[1] = 0; lib_info.clear(); tpl_parts.clear();
 	if (fd >= 0) close(fd);
 	fd = -1;
 }
@@ -262,6 +262,14 @@ int bsr_store_t::append(const uint8_t *recs, uint64_t bytes, const uint64_t *key
 	}
 	runs.push_back(std::move(r));
 	return BMH_OK;
+}
+
+void bsr_store_t::retemplate(const std::vector<uint32_t> &rec_tpl)
+{
+	for (bsr_run_t &r : runs) {
+		for (uint32_t &t : r.tpl) t = rec_tpl[(size_t)(r.tbase + t)];
+		r.tbase = 0;
+	}
 }
 
 int bsr_store_t::read(const bsr_run_t &r, uint64_t a, uint64_t b, uint8_t *dst) const

@@ -1153,12 +1153,24 @@ int bmh_aligner_coverage_ms(bmh_aligner_t *a, double *out, uint64_t *windows);
  * out (zeroed first; bmh_bam_post_result_free releases it; a refused call leaves its pointers NULL): the index bytes, the output header's text, the references
  * (names NUL-terminated back to back), with libraries their names likewise, and the counts: records, templates, batches, runs spilled, records whose bin
  * changed, records whose 0x400 was cleared.  res: required with markdup; cov: required with coverage (bmh_free its arrays).
- * The host form does the same with the host forms of every step and no device; it holds the whole record stream in memory. */
+ * The host form does the same with the host forms of every step and no device; it holds the whole record stream in memory.
+ * collate != 0 (needs markdup, else BMH_EINVAL before anything is read; off by default, and with it off every byte, count and message is as without the field):
+ * templates by name over the whole file (BDP_TPL_FILE), so that a coordinate-sorted file can be marked.  A template is the records of the whole file that carry
+ * one read name, adjacent or not; its first record is the one with the smallest file index (library, barcode and location come from it), its ordinal the rank of
+ * that record among all first records; its entry is bdp_entry's rule on the set (n_rec the set's size, the two mapped primary lines in file order).  A set that
+ * is no proper template -- a paired one whose primary lines are not one 0x40 and one 0x80 record, an unpaired one without exactly one primary line, so also two
+ * templates under one name anywhere in the file -- is refused with BMH_EINVAL naming its first record's index (and the SAM line) and the primary lines found;
+ * of all refusals of first records and of sets the smallest (index, code) is reported, after the last batch and before the header reaches the sink.  Names are
+ * keyed by 128 bits (FNV-1a and a second hash) and never compared byte by byte; a collision merges two whole templates into an improper set, which is refused.
+ * Batches then end at the first record at or beyond batch_bytes.  Every record's 32-byte part (48 or 56 with optical_distance / barcodes) stays in host memory
+ * until the grouping: about 32 GB for 10^9 records, outside sort_mem, never spilled.  On a name-grouped file with distinct names the output is byte for byte
+ * that of collate 0. */
 typedef struct {
 	int32_t level; uint32_t window; int32_t index_format, min_shift;
 	uint64_t sort_mem; const char *tmp_dir; uint64_t batch_bytes;
 	const bmh_markdup_opt_t *markdup; int32_t libraries;
 	const bmh_coverage_opt_t *coverage;
+	int32_t collate;
 } bmh_bam_post_opt_t;
 typedef struct { uint64_t records, templates, batches, spilled_runs, bins_changed, dup_flags_cleared; } bmh_bam_post_counts_t;
 typedef struct {
@@ -1174,6 +1186,20 @@ int bmh_bam_post_file_device(const char *path, const bmh_bam_post_opt_t *opt, vo
                              bmh_markdup_counts_t *res, bmh_coverage_t *cov);
 int bmh_bam_post_file_host(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res,
                            bmh_coverage_t *cov);
+/* The grouping of collate on its own (csrc/bam_tpl_core.h, csrc/bam_tpl_kernels.hip, csrc/bam_tpl_host.cpp): a stream of whole BAM records in any order -> every
+ * record's template ordinal (tpl [n_records]), the templates' entries (24 bytes each: uint64 lo, hi; uint32 score, kind | records << 2), their locations (16
+ * bytes each: int32 x, y; uint32 tile; uint16 rg, flags), with opt's barcode source their barcode words, counts: secondary or supplementary records, unmapped
+ * records, templates; with opt's read groups the three per library (lib_counts [3 * n_libraries]).  opt (NULL: plain): the read groups, the barcode source and
+ * barcode_edits (packed words) are read.  hash_bits: 128; below it the name keys are cut, so that a test can make two names collide.  Records go through the
+ * per-record checks of marking first; an improper set and a refused first record give BMH_EINVAL as under collate.  bmh_bam_templates_free releases *out. */
+typedef struct {
+	uint64_t n_records, n_templates;
+	uint32_t *tpl; uint8_t *entries, *locs; uint64_t *barcodes;
+	uint64_t counts[3]; uint64_t *lib_counts; int32_t n_libraries;
+} bmh_bam_templates_t;
+int bmh_bam_templates_device(const uint8_t *records, uint64_t n_bytes, const bmh_markdup_opt_t *opt, int32_t hash_bits, void *stream, bmh_bam_templates_t *out);
+int bmh_bam_templates_host(const uint8_t *records, uint64_t n_bytes, const bmh_markdup_opt_t *opt, int32_t hash_bits, bmh_bam_templates_t *out);
+void bmh_bam_templates_free(bmh_bam_templates_t *r);
 
 #ifdef __cplusplus
 }
