@@ -10,7 +10,13 @@ raise.
 from . import fmindex, synth  # noqa: F401
 from .index import fasta_pack, index_fasta  # noqa: F401
 from .lib import (ExtParams, HipLibraryMissing, Index, SeedWorkspace, extend_batch, lib_path,  # noqa: F401
-                  load_library, seed_file)
+                  bam_stats, load_library, seed_file)
+
+
+def insert_size_metrics(hist, smallest, largest) -> dict:
+    """bwamem_hip.aligner.insert_size_metrics: median, MAD, mode, trimmed mean and SD of one orientation's insert-size histogram"""
+    from .aligner import insert_size_metrics as f
+    return f(hist, smallest, largest)
 
 
 def bam_post_file(*args, **kw):

@@ -427,6 +427,149 @@ def coverage_request(what: str, sort: bool, coverage=None, coverage_hist=None, c
     return dict(table=coverage, hist=coverage_hist, bed=coverage_bed, bin=int(coverage_bin or 0), min_mapq=int(coverage_min_mapq or 0), deletions=bool(coverage_deletions))
 
 
+STATS_KEYWORDS = ("flagstat", "idxstats", "stats", "insert_cap")
+
+
+def stats_request(what: str, sort: bool, flagstat=None, idxstats=None, stats=None, insert_cap=None):
+    """the statistics keywords of align_file / align_files / align_groups / bam_post_file, checked -> None (none given) or a dict of them; ValueError otherwise"""
+    outs = flagstat is not None or idxstats is not None or stats is not None
+    if not outs and insert_cap is None:
+        return None
+    if not sort:
+        raise ValueError(f"{what}: flagstat, idxstats, stats and insert_cap need sort=True: the statistics are computed where the sorted file is written")
+    if not outs:
+        raise ValueError(f"{what}: insert_cap needs flagstat, idxstats or stats (it says how the insert sizes are binned, not where they go)")
+    if insert_cap is not None and (not isinstance(insert_cap, (int, np.integer)) or isinstance(insert_cap, bool) or not 2 <= insert_cap <= 65536):
+        raise ValueError(f"{what}: insert_cap {insert_cap!r}: an integer in 2 .. 65536")
+    return dict(flagstat=flagstat, idxstats=idxstats, stats=stats, insert_cap=int(insert_cap or 65536))
+
+
+def _stats_keywords(f):
+    """_coverage_keywords for the statistics keywords: the outermost call's request stays in self._stats_req for as long as the run"""
+    sig = inspect.signature(f)
+
+    @functools.wraps(f)
+    def call(self, *args, **kw):
+        if getattr(self, "_stats_req", None) is not None:
+            return f(self, *args, **kw)
+        given = sig.bind(self, *args, **kw)
+        given.apply_defaults()
+        req = stats_request(f.__name__, given.arguments["sort"], *(given.arguments[k] for k in STATS_KEYWORDS))
+        if req is None:
+            return f(self, *args, **kw)
+        self._stats_req = req
+        try:
+            return f(self, *args, **kw)
+        finally:
+            self._stats_req = None
+    return call
+
+
+def _pct(a: int, b: int) -> str:
+    return "%.2f%%" % (100.0 * a / b) if b else "N/A"
+
+
+def flagstat_text(st: dict) -> str:
+    """`samtools flagstat`'s sixteen lines, in its order and wording, from bam_stats' "flag" (QC-passed + QC-failed); a percentage over 0 reads N/A"""
+    p, f = ([int(v) for v in row] for row in st["flag"])
+    (total, primary, secondary, supp, dup, pdup, mapped, pmapped, paired, read1, read2, proper, both, single, diff, diff5) = range(16)
+    def line(k, words, over=None):
+        tail = "" if over is None else " (%s : %s)" % (_pct(p[k], p[over]), _pct(f[k], f[over]))
+        return "%d + %d %s%s" % (p[k], f[k], words, tail)
+    return "\n".join([line(total, "in total (QC-passed reads + QC-failed reads)"), line(primary, "primary"), line(secondary, "secondary"), line(supp, "supplementary"),
+                      line(dup, "duplicates"), line(pdup, "primary duplicates"), line(mapped, "mapped", total), line(pmapped, "primary mapped", primary),
+                      line(paired, "paired in sequencing"), line(read1, "read1"), line(read2, "read2"), line(proper, "properly paired", paired),
+                      line(both, "with itself and mate mapped"), line(single, "singletons", paired), line(diff, "with mate mapped to a different chr"),
+                      line(diff5, "with mate mapped to a different chr (mapQ>=5)")]) + "\n"
+
+
+def idxstats_text(st: dict, contigs) -> str:
+    """`samtools idxstats`: name, length, mapped, unmapped per contig in header order, then the row of the records without a contig"""
+    rows = ["%s\t%d\t%d\t%d" % (name, int(length), int(st["contig_mapped"][c]), int(st["contig_unmapped"][c])) for c, (name, length) in enumerate(contigs)]
+    rows.append("*\t0\t0\t%d" % int(st["unplaced"][0]))
+    return "".join(r + "\n" for r in rows)
+
+
+def _hist_median(values, counts):
+    """the median of the values (ascending) with their counts: the mean of the two middle ones when their number is even"""
+    cum = np.cumsum(counts)
+    n = int(cum[-1])
+    lo, hi = values[int(np.searchsorted(cum, (n - 1) // 2 + 1))], values[int(np.searchsorted(cum, n // 2 + 1))]
+    return (float(lo) + float(hi)) / 2
+
+
+def insert_size_metrics(hist, smallest, largest) -> dict:
+    """the insert sizes of one orientation -- hist [cap + 1] (index s: the pairs of size s; the last bin: every size from cap up, taken as cap), the exact smallest
+    and largest size -- -> pairs, median, mad (the median of |x - median|), mode (the smallest size with the largest count), min, max, mean and sd over the
+    sizes <= min(median + 10 * mad, cap - 1) (Picard's trim of the tail; sd with n - 1, 0 for one value).  Medians of an even number of values are the mean of
+    the two middle ones.  No pair: every value 0."""
+    h = np.asarray(hist, dtype=np.uint64)
+    cap = len(h) - 1
+    at = [int(s) for s in np.flatnonzero(h)]
+    cnt = [int(h[s]) for s in at]
+    pairs = sum(cnt)
+    if not pairs:
+        return dict(pairs=0, median=0.0, mad=0.0, mode=0, min=0, max=0, mean=0.0, sd=0.0)
+    median = _hist_median(at, cnt)
+    dev = sorted((abs(s - median), c) for s, c in zip(at, cnt))
+    mad = _hist_median([d for d, _c in dev], [c for _d, c in dev])
+    mode = at[int(np.argmax(cnt))]
+    limit = min(median + 10 * mad, cap - 1)
+    kept = [(s, c) for s, c in zip(at, cnt) if s <= limit]
+    n = sum(c for _s, c in kept)
+    mean = sum(s * c for s, c in kept) / n if n else 0.0
+    sd = (sum(c * (s - mean) ** 2 for s, c in kept) / (n - 1)) ** 0.5 if n > 1 else 0.0
+    return dict(pairs=pairs, median=median, mad=mad, mode=int(mode), min=int(smallest), max=int(largest), mean=float(mean), sd=float(sd))
+
+
+def stats_text(st: dict, contigs) -> str:
+    """one tab-separated text, every line under a section key: FS name passed failed (the flag counts), IX name length mapped unmapped (the contigs, then *),
+    SN name value (the summary words and error_rate = edit_distance / bases_aligned, %.6e; 0 over no base), MQ mapq count (the bins that hold a read), IS size FR
+    RF TANDEM (the sizes that hold a pair; the overflow row is labelled `cap+`), IM orientation pairs median MAD mode min max mean SD (%.1f %.1f, then %.2f %.2f;
+    the orientations that hold a pair)"""
+    from .lib import BAM_STATS_FLAGS, BAM_STATS_ORIENTATIONS, BAM_STATS_SUMMARY
+    rows = ["FS\t%s\t%d\t%d" % (nm, int(st["flag"][0][k]), int(st["flag"][1][k])) for k, nm in enumerate(BAM_STATS_FLAGS)]
+    rows += ["IX\t" + l for l in idxstats_text(st, contigs).split("\n")[:-1]]
+    s = {nm: int(st["summary"][k]) for k, nm in enumerate(BAM_STATS_SUMMARY)}
+    rows += ["SN\t%s\t%d" % (nm, s[nm]) for nm in BAM_STATS_SUMMARY]
+    rows.append("SN\terror_rate\t%s" % ("%.6e" % (s["edit_distance"] / s["bases_aligned"]) if s["bases_aligned"] else "0"))
+    rows += ["MQ\t%d\t%d" % (q, int(v)) for q, v in enumerate(st["mapq"]) if int(v)]
+    h = st["insert_hist"]
+    cap = h.shape[1] - 1
+    for size in np.flatnonzero(h.any(axis=0)):
+        rows.append("IS\t%s\t%d\t%d\t%d" % ("%d+" % cap if size == cap else str(int(size)), int(h[0][size]), int(h[1][size]), int(h[2][size])))
+    for o, nm in enumerate(BAM_STATS_ORIENTATIONS):
+        m = insert_size_metrics(h[o], st["insert_min"][o], st["insert_max"][o])
+        if m["pairs"]:
+            rows.append("IM\t%s\t%d\t%.1f\t%.1f\t%d\t%d\t%d\t%.2f\t%.2f" % (nm, m["pairs"], m["median"], m["mad"], m["mode"], m["min"], m["max"], m["mean"], m["sd"]))
+    return "".join(r + "\n" for r in rows)
+
+
+def write_flagstat(st: dict, dst) -> None:
+    """flagstat_text of bam_stats' dict to dst: a path or a text file object"""
+    _write_text(dst, flagstat_text(st))
+
+
+def write_idxstats(st: dict, contigs, dst) -> None:
+    """idxstats_text to dst: a path or a text file object"""
+    _write_text(dst, idxstats_text(st, contigs))
+
+
+def write_stats(st: dict, contigs, dst) -> None:
+    """stats_text to dst: a path or a text file object"""
+    _write_text(dst, stats_text(st, contigs))
+
+
+def write_stats_texts(req: dict, st: dict, contigs) -> None:
+    """the texts a statistics request asks for, to their paths or file objects"""
+    if req["flagstat"] is not None:
+        write_flagstat(st, req["flagstat"])
+    if req["idxstats"] is not None:
+        write_idxstats(st, contigs, req["idxstats"])
+    if req["stats"] is not None:
+        write_stats(st, contigs, req["stats"])
+
+
 def _write_text(dst, text: str) -> None:
     if hasattr(dst, "write"):
         dst.write(text)
@@ -764,6 +907,7 @@ class Aligner:
             nat.set_sort(*self._sort_knobs)
             nat.set_markdup(bool(getattr(self, "_markdup", False)))
             nat.set_coverage(getattr(self, "_coverage_opt", None))
+            nat.set_stats(getattr(self, "_stats_opt", None))
             if getattr(self, "_markdup", False):
                 nat.set_markdup_optical(getattr(self, "_optical", None))
                 nat.set_markdup_barcode(*getattr(self, "_barcode", (0, None)))
@@ -771,10 +915,12 @@ class Aligner:
         return nat
 
     @_coverage_keywords
+    @_stats_keywords
     def align_file(self, reads_fa: str, out, batch_reads: int = 0, paired: bool = False, chunk_bases: int = 0, fmt: str = "sam", level: int = 1,
                    sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
                    index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
-                   coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False) -> int:
+                   coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False,
+                    flagstat=None, idxstats=None, stats=None, insert_cap=None) -> int:
         if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None or barcode_tag is not None or barcode_name or barcode_edits is not None:
             return self._align_bam(lambda o: self.align_file(reads_fa, o, batch_reads=batch_reads, paired=paired, chunk_bases=chunk_bases), out, fmt, level,
                                    sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift, optical_distance, barcode_tag, barcode_name, barcode_edits)
@@ -929,11 +1075,18 @@ class Aligner:
         if cov_req is not None:
             from .lib import coverage_opt
             self._coverage_opt = coverage_opt(cov_req["min_mapq"], cov_req["deletions"], cov_req["bin"], 0, "align_file")
+        stats_req = getattr(self, "_stats_req", None) if sort else None
+        if stats_req is not None:
+            from .lib import stats_opt
+            self._stats_opt = stats_opt(stats_req["insert_cap"], "align_file")
         try:
             n = run(shim)
             if cov_req is not None:                                # (no reads: no run was made -- the coverage of a file without records)
                 from .lib import bam_coverage
                 self.coverage = self._native.coverage() if n else bam_coverage(b"", self.contigs, host=True, min_mapq=cov_req["min_mapq"], deletions=cov_req["deletions"], bin=cov_req["bin"])
+            if stats_req is not None:                              # (no reads: the statistics of a file without records)
+                from .lib import bam_stats
+                self.stats = self._native.stats() if n else bam_stats(b"", len(self.contigs), stats_req["insert_cap"], host=True)
             if markdup:
                 from .lib import MARKDUP_COUNTS
                 self.markdup_counts = self._native.markdup_counts() if n else dict.fromkeys(MARKDUP_COUNTS, 0)
@@ -961,6 +1114,7 @@ class Aligner:
             self._barcode_edits = -1
             self._index_format = ("bai", 14)
             self._coverage_opt = None
+            self._stats_opt = None
             nat = getattr(self, "_native", None)
             if nat is not None:
                 nat.set_output("sam", 1)
@@ -984,6 +1138,8 @@ class Aligner:
                 _write_text(cov_req["hist"], coverage_hist_text(self.coverage))
             if cov_req["bed"] is not None:
                 _write_text(cov_req["bed"], coverage_bed_text(self.coverage, self.contigs, cov_req["bin"]))
+        if stats_req is not None:
+            write_stats_texts(stats_req, self.stats, self.contigs)
         if markdup_metrics is not None:
             text = markdup_metrics_text_libraries(self.markdup_library_counts) if getattr(self, "_groups", None) else markdup_metrics_text(self.markdup_counts, getattr(self, "rg_line", ""))
             if hasattr(markdup_metrics, "write"):
@@ -994,12 +1150,18 @@ class Aligner:
         return n
 
     @_coverage_keywords
+    @_stats_keywords
     def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
                     sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None, keep_rg: bool = False,
                     index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
                     collate: bool = False, collate_mem=None,
-                    coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False) -> int:
-        """coverage=, coverage_hist=, coverage_bed= (paths or text file objects; need sort=True): the coverage depth of the file being written, computed on the
+                    coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False,
+                    flagstat=None, idxstats=None, stats=None, insert_cap=None) -> int:
+        """flagstat=, idxstats=, stats= (paths or text file objects; need sort=True): `samtools flagstat`'s and `samtools idxstats`' texts and a sectioned summary with
+        mapq and insert-size histograms (stats_text) of the file being written, computed on the device from every window of the final merge behind its flag step
+        (DESIGN.md 4.15), so with the 0x400 flags markdup=True sets; insert_cap=N (2 .. 65536): sizes from N up share the last bin.  self.stats holds the arrays
+        afterwards (bam_stats' dict).  The BAM and its index are byte for byte those of the run without them.
+        coverage=, coverage_hist=, coverage_bed= (paths or text file objects; need sort=True): the coverage depth of the file being written, computed on the
         device from every window of the final merge behind its flag step -- duplicates that markdup=True marks are counted out.  They receive
         coverage_table_text, coverage_hist_text and coverage_bed_text (the last with coverage_bin=N positions a row); coverage_min_mapq=Q and coverage_deletions=True
         say what counts.  self.coverage holds the arrays afterwards (bam_coverage's dict).  The BAM and its index are byte for byte those of the run without them.
@@ -1093,11 +1255,13 @@ class Aligner:
         return int(self.last_stats.n_reads)
 
     @_coverage_keywords
+    @_stats_keywords
     def align_groups(self, groups, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
                      sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
                      index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
                      collate: bool = False, collate_mem=None,
-                     coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False) -> int:
+                     coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False,
+                    flagstat=None, idxstats=None, stats=None, insert_cap=None) -> int:
         """several read groups -- a sample's lanes and libraries -- into one output (bmh_aligner_run_groups).  groups: [(rg_line, reads, mates or None), ...]; every
         rg_line is unescaped and checked as -R's value is, reads / mates are what align_files takes (one file or R1 + R2; plain, gzip or BGZF; FASTA or FASTQ; or
         one BAM, whose own @RG lines and RG tags stay ignored: align_files(keep_rg=True) is the run that keeps them, and the two do not combine).  Group g's records are byte for byte those of align_files(reads_g, mates_g) alone under -R rg_g, and
@@ -1106,6 +1270,7 @@ class Aligner:
         self.markdup_library_counts holds the counts per library, markdup_metrics one row per library.  Needs the native pipeline; -R must not be set.
         collate / collate_mem: align_files' -- they apply to every group whose input is one BAM; groups of text files are taken as ever.
         coverage / coverage_hist / coverage_bed / coverage_bin / coverage_min_mapq / coverage_deletions: align_files' -- the coverage is the whole file's, not per library.
+        flagstat / idxstats / stats / insert_cap: align_files' -- the statistics are the whole file's, not per read group or library.
         Returns the number of reads."""
         if out is None:
             raise ValueError("align_groups: out (a text or binary file object) is required")

@@ -8,7 +8,7 @@ the index goes to PATH.bai (PATH.csi with --csi), --index PATH names it otherwis
 its @HD line replaced by `@HD VN:1.6 SO:coordinate`; no @PG line is added.  Records stay verbatim but for the bin (recomputed) and, with --markdup, flag 0x400.
 
 The options are those of bwamem_hip.mem, with the same meaning and the same refusals: --markdup, --markdup-metrics PATH, --optical-distance N, --barcode-tag XX,
---barcode-name, --barcode-edits N; --coverage PATH, --coverage-hist PATH, --coverage-bed PATH, --coverage-bin N, --coverage-min-mapq Q, --coverage-deletions;
+--barcode-name, --barcode-edits N; --coverage PATH, --coverage-hist PATH, --coverage-bed PATH, --coverage-bin N, --coverage-min-mapq Q, --coverage-deletions; --flagstat PATH, --idxstats PATH, --stats PATH;
 --csi, --csi-min-shift N, --index PATH, --bam-level 0|1, --sort-mem BYTES, --sort-tmp DIR, --sort-window RECORDS.  Here --barcode-tag needs no -C: the tag is read
 from the record.  Beside them: --libraries (needs --markdup: the header's @RG lines are the table of libraries, duplicates are called within a library and the
 metrics table has a row per library; the rules and refusals of `bwamem_hip.mem --keep-rg --markdup`; off: one library), --batch-bytes N (the record bytes of a
@@ -30,11 +30,14 @@ import sys
 
 def bam_post_file(src, out, index=None, host: bool = False, level: int = 1, sort_window: int = 0, sort_mem=None, sort_tmp=None, batch_bytes=None, index_format: str = "bai",
                   csi_min_shift: int = 14, markdup: bool = False, markdup_metrics=None, libraries: bool = False, optical_distance=None, barcode_tag=None, barcode_name=None,
-                  barcode_edits=None, coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False, collate: bool = False) -> dict:
+                  barcode_edits=None, coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False, collate: bool = False,
+                  flagstat=None, idxstats=None, stats=None, insert_cap=None) -> dict:
     """the BAM or SAM file `src` (a path; "-": stdin) -> the coordinate-sorted BAM written to `out` (a binary file object), its index to `index` (a path or a binary
     file object; None: not written), the metrics table to `markdup_metrics` and the coverage texts to coverage / coverage_hist / coverage_bed (paths or text file
     objects), as Aligner.align_files(sort=True, ...) writes them.  Returns lib.bam_post's dict.  The keywords are align_files' and are refused as there.
-    collate=True (needs markdup=True): templates by name over the whole file, for an input that is not grouped by name (lib.bam_post)."""
+    collate=True (needs markdup=True): templates by name over the whole file, for an input that is not grouped by name (lib.bam_post).
+    flagstat / idxstats / stats (paths or text file objects) and insert_cap: align_files' -- the statistics of the sorted file, from the windows of its merge."""
+    from .aligner import stats_request, write_stats_texts
     from .aligner import coverage_request, coverage_table_text, coverage_hist_text, coverage_bed_text, markdup_metrics_text, markdup_metrics_text_libraries, _write_text
     from .lib import bam_post
     if not ("b" in getattr(out, "mode", "") or hasattr(out, "getbuffer")):
@@ -42,9 +45,11 @@ def bam_post_file(src, out, index=None, host: bool = False, level: int = 1, sort
     if markdup_metrics is not None and not markdup:
         raise ValueError("bam_post_file: markdup_metrics needs markdup=True")
     req = coverage_request("bam_post_file", True, coverage, coverage_hist, coverage_bed, coverage_bin, coverage_min_mapq, coverage_deletions)
+    sreq = stats_request("bam_post_file", True, flagstat, idxstats, stats, insert_cap)
     r = bam_post("/dev/stdin" if src == "-" else src, out.write, host=host, level=level, window=sort_window, index_format=index_format, csi_min_shift=csi_min_shift, sort_mem=sort_mem,
                  sort_tmp=sort_tmp, batch_bytes=batch_bytes, markdup=markdup, libraries=libraries, optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name,
-                 barcode_edits=barcode_edits, coverage=None if req is None else dict(min_mapq=req["min_mapq"], deletions=req["deletions"], bin=req["bin"]), collate=collate)
+                 barcode_edits=barcode_edits, coverage=None if req is None else dict(min_mapq=req["min_mapq"], deletions=req["deletions"], bin=req["bin"]), collate=collate,
+                 stats=None if sreq is None else dict(insert_cap=sreq["insert_cap"]))
     if index is not None:
         if hasattr(index, "write"):
             index.write(r["index"])
@@ -58,12 +63,14 @@ def bam_post_file(src, out, index=None, host: bool = False, level: int = 1, sort
             _write_text(req["hist"], coverage_hist_text(r["coverage"]))
         if req["bed"] is not None:
             _write_text(req["bed"], coverage_bed_text(r["coverage"], r["contigs"], req["bin"]))
+    if sreq is not None:
+        write_stats_texts(sreq, r["stats"], r["contigs"])
     if markdup_metrics is not None:
         _write_text(markdup_metrics, markdup_metrics_text_libraries(r["markdup"]["libraries"]) if libraries else markdup_metrics_text(r["markdup"]))
     return r
 
 
-_VALUED = ("-o", "--device", "--index", "--sort-mem", "--sort-tmp", "--sort-window", "--markdup-metrics", "--batch-bytes", "--coverage", "--coverage-hist", "--coverage-bed", "--barcode-tag",
+_VALUED = ("-o", "--device", "--index", "--sort-mem", "--sort-tmp", "--sort-window", "--markdup-metrics", "--batch-bytes", "--coverage", "--coverage-hist", "--coverage-bed", "--barcode-tag", "--flagstat", "--idxstats", "--stats",
            "--bam-level", "--csi-min-shift", "--optical-distance", "--barcode-edits", "--coverage-bin", "--coverage-min-mapq")
 _NUMBERS = {"--bam-level": (0, 1, "0 or 1"), "--csi-min-shift": (10, 24, "a number in 10 .. 24"), "--optical-distance": (0, 0x7fffffff, "a whole number of pixels, 0 .. 2^31 - 1"),
             "--barcode-edits": (0, 21, "a whole number of mismatches, 0 .. 21"), "--coverage-bin": (1, 0xffffffff, "a whole number of positions, 1 .. 2^32 - 1"),
@@ -142,7 +149,8 @@ def main(argv=None) -> int:
                       markdup_metrics=v.get("--markdup-metrics"), libraries="--libraries" in flags, optical_distance=v.get("--optical-distance"), barcode_tag=v.get("--barcode-tag"),
                       barcode_name=True if "--barcode-name" in flags else None, barcode_edits=v.get("--barcode-edits"), coverage=cov_paths.get("--coverage"),
                       coverage_hist=cov_paths.get("--coverage-hist"), coverage_bed=cov_paths.get("--coverage-bed"), coverage_bin=v.get("--coverage-bin"),
-                      coverage_min_mapq=v.get("--coverage-min-mapq"), coverage_deletions="--coverage-deletions" in flags, collate="--collate" in flags)
+                      coverage_min_mapq=v.get("--coverage-min-mapq"), coverage_deletions="--coverage-deletions" in flags, collate="--collate" in flags,
+                      flagstat=v.get("--flagstat"), idxstats=v.get("--idxstats"), stats=v.get("--stats"))
         out.flush()
     except (ValueError, OSError) as e:
         print(f"{me} {e}", file=sys.stderr)

@@ -54,6 +54,8 @@ EXPORTED_SYMBOLS = [
     "bmh_reads_last_collate_counts", "bmh_aligner_set_collate", "bmh_reads_load_files_ex", "bmh_bam_reads_ex",
     "bmh_coverage_opt_default", "bmh_bam_coverage_device", "bmh_bam_coverage_host", "bmh_bam_sorted_file_coverage_device", "bmh_bam_sorted_file_coverage_host",
     "bmh_aligner_set_coverage", "bmh_aligner_coverage", "bmh_aligner_coverage_ms",
+    "bmh_bam_stats_opt_default", "bmh_bam_stats_free", "bmh_bam_stats_device", "bmh_bam_stats_host", "bmh_bam_sorted_file_stats_device", "bmh_bam_sorted_file_stats_host",
+    "bmh_aligner_set_stats", "bmh_aligner_stats", "bmh_aligner_stats_ms", "bmh_bam_post_file_stats_device", "bmh_bam_post_file_stats_host",
     "bmh_bam_post_opt_default", "bmh_bam_post_result_free", "bmh_bam_post_file_device", "bmh_bam_post_file_host",
     "bmh_bam_templates_device", "bmh_bam_templates_host", "bmh_bam_templates_free",
 ]
@@ -749,8 +751,10 @@ def index_format_code(index_format, csi_min_shift, what: str) -> tuple:
 
 
 def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False, markdup: bool = False, read_groups=None,
-                    index_format: str = "bai", csi_min_shift: int = 14, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None) -> tuple:
-    """coverage={min_mapq, deletions, bin, tile} (bmh_bam_sorted_file_coverage_*; bam_coverage's keywords, {} for the defaults): the file's coverage, taken from
+                    index_format: str = "bai", csi_min_shift: int = 14, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None, stats=None) -> tuple:
+    """stats={insert_cap} (bmh_bam_sorted_file_stats_*; {} for the default): the file's statistics (bam_stats' dict), taken from the same windows with the flags
+    markdup=True sets, come last in the tuple, behind the coverage where both are asked for.
+    coverage={min_mapq, deletions, bin, tile} (bmh_bam_sorted_file_coverage_*; bam_coverage's keywords, {} for the defaults): the file's coverage, taken from
     the windows of the merge as they are written -- with markdup=True the marked duplicates are counted out -- comes last in the tuple.
     bmh_bam_sorted_file_device (host=True: _host): (the complete sorted BAM file -- header members, the records in coordinate order in windows of `window`
     records (0: about 64 MiB), the end-of-file member --, its .bai index).  contigs: (name, length) pairs; both forms give the same bytes.
@@ -784,21 +788,29 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
     head = [header_text.encode(), len(contigs), names, lens.ctypes.data, records, len(records), C.byref(fo)]
     tail = [C.byref(bam), C.byref(nb), C.byref(bai), C.byref(ni), C.byref(res) if markdup else None]
     cov, co = Coverage(), None
+    st, so = BamStats(), None
     if coverage is not None:
         co = coverage_opt(what="bam_sorted_file", **coverage)
+    if stats is not None:
+        so = stats_opt(what="bam_sorted_file", **stats)
+        types = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(SortedFileOpt), C.POINTER(CoverageOpt), C.POINTER(BamStatsOpt)]
+        outs = [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p, C.POINTER(MarkdupCounts), C.POINTER(Coverage), C.POINTER(BamStats)]
+        L.bmh_bam_sorted_file_stats_host.argtypes, L.bmh_bam_sorted_file_stats_device.argtypes = types + outs, types + [C.c_void_p] + outs
+        head, tail = head + [C.byref(co) if co else None, C.byref(so)], tail + [C.byref(cov) if co else None, C.byref(st)]
+    elif coverage is not None:
         types = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(SortedFileOpt), C.POINTER(CoverageOpt)]
         outs = [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p, C.POINTER(MarkdupCounts), C.POINTER(Coverage)]
         L.bmh_bam_sorted_file_coverage_host.argtypes, L.bmh_bam_sorted_file_coverage_device.argtypes = types + outs, types + [C.c_void_p] + outs
         head, tail = head + [C.byref(co)], tail + [C.byref(cov)]
     if host:
-        rc = (L.bmh_bam_sorted_file_coverage_host if co else L.bmh_bam_sorted_file_host)(*head, *tail)
+        rc = (L.bmh_bam_sorted_file_stats_host if so else L.bmh_bam_sorted_file_coverage_host if co else L.bmh_bam_sorted_file_host)(*head, *tail)
     else:
         import torch
-        rc = (L.bmh_bam_sorted_file_coverage_device if co else L.bmh_bam_sorted_file_device)(*head, torch.cuda.current_stream().cuda_stream, *tail)
+        rc = (L.bmh_bam_sorted_file_stats_device if so else L.bmh_bam_sorted_file_coverage_device if co else L.bmh_bam_sorted_file_device)(*head, torch.cuda.current_stream().cuda_stream, *tail)
     if rc != 0:
         raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_sorted_file: " + _err(L))
     try:
-        extra = (coverage_dict(L, cov),) if co else ()
+        extra = ((coverage_dict(L, cov),) if co else ()) + ((stats_dict(L, st),) if so else ())
         if markdup:
             return (C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value), _markdup_dict(o, res, lib_names, read_groups is not None)) + extra
         return (C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)) + extra
@@ -870,6 +882,76 @@ def bam_coverage(records: bytes, contigs, host: bool = False, min_mapq: int = 0,
     return coverage_dict(L, cov)
 
 
+class BamStatsOpt(C.Structure):
+    """bmh_bam_stats_opt_t"""
+    _fields_ = [("insert_cap", C.c_uint32)]
+
+
+class BamStats(C.Structure):
+    """bmh_bam_stats_t"""
+    _fields_ = [("n_contigs", C.c_int32), ("insert_cap", C.c_uint32), ("flag", _u64p), ("summary", _u64p), ("mapq", _u64p), ("contig_mapped", _u64p), ("contig_unmapped", _u64p),
+                ("insert_hist", _u64p), ("unplaced", C.c_uint64), ("insert_min", C.c_uint64 * 3), ("insert_max", C.c_uint64 * 3)]
+
+
+BAM_STATS_FLAGS = ("total", "primary", "secondary", "supplementary", "duplicates", "primary_duplicates", "mapped", "primary_mapped", "paired", "read1", "read2", "properly_paired",
+                   "both_mapped", "singletons", "mate_on_different_contig", "mate_on_different_contig_mapq5")
+BAM_STATS_SUMMARY = ("reads", "bases", "reads_mapped", "bases_mapped", "reads_mq0", "max_read_length", "bases_aligned", "bases_soft_clipped", "ins_events", "ins_bases", "del_events",
+                     "del_bases", "reads_with_nm", "edit_distance")
+BAM_STATS_ORIENTATIONS = ("FR", "RF", "TANDEM")
+INSERT_CAP_DEFAULT = 65536
+
+
+def stats_opt(insert_cap=INSERT_CAP_DEFAULT, what="bam_stats") -> BamStatsOpt:
+    """the statistics' keyword, checked -> bmh_bam_stats_opt_t; ValueError names the keyword"""
+    if insert_cap is None:
+        insert_cap = INSERT_CAP_DEFAULT
+    if not isinstance(insert_cap, (int, np.integer)) or isinstance(insert_cap, bool) or not 2 <= insert_cap <= 65536:
+        raise ValueError(f"{what}: insert_cap {insert_cap!r}: an integer in 2 .. 65536")
+    return BamStatsOpt(int(insert_cap))
+
+
+def stats_dict(L, st: BamStats) -> dict:
+    """bmh_bam_stats_t -> {name: numpy array of uint64}; the record's arrays are released"""
+    L.bmh_bam_stats_free.argtypes, L.bmh_bam_stats_free.restype = [C.POINTER(BamStats)], None
+    try:
+        n, cap = int(st.n_contigs), int(st.insert_cap)
+        out = dict(flag=np.ctypeslib.as_array(st.flag, shape=(2, 16)).copy(), summary=np.ctypeslib.as_array(st.summary, shape=(14,)).copy(),
+                   mapq=np.ctypeslib.as_array(st.mapq, shape=(256,)).copy(), insert_hist=np.ctypeslib.as_array(st.insert_hist, shape=(3, cap + 1)).copy())
+        for nm in ("contig_mapped", "contig_unmapped"):
+            out[nm] = np.ctypeslib.as_array(getattr(st, nm), shape=(max(n, 1),))[:n].copy()
+        out["unplaced"] = np.array([st.unplaced], dtype=np.uint64)
+        out["insert_min"] = np.array(list(st.insert_min), dtype=np.uint64); out["insert_max"] = np.array(list(st.insert_max), dtype=np.uint64)
+        return out
+    finally:
+        L.bmh_bam_stats_free(C.byref(st))
+
+
+def bam_stats(records: bytes, n_contigs: int, insert_cap: int = INSERT_CAP_DEFAULT, host: bool = False) -> dict:
+    """bmh_bam_stats_device (host=True: _host, no device needed): a stream of BAM records in any order among n_contigs contigs -> the statistics of DESIGN.md 4.15
+    as a dict of uint64 arrays, device and host integer for integer the same: flag [2][16] (`samtools flagstat`'s counts by BAM_STATS_FLAGS' names; row 1: the
+    records with 0x200), contig_mapped / contig_unmapped [n_contigs] and unplaced [1] (`samtools idxstats`), summary [14] (BAM_STATS_SUMMARY's names, over primary
+    records), mapq [256] (mapped primary records), insert_hist [3][insert_cap + 1] (FR, RF, TANDEM; sizes from insert_cap up in the last bin), insert_min /
+    insert_max [3] (exact; 0 without a pair).  flagstat_text, idxstats_text, stats_text and insert_size_metrics (bwamem_hip.aligner) make the texts.  A refID outside
+    the contigs, and of mapped primary records damaged tags, an NM that is no count and the long-CIGAR placeholder raise ValueError naming the record."""
+    L = load_library()
+    records = bytes(records)
+    o = stats_opt(insert_cap)
+    if not isinstance(n_contigs, (int, np.integer)) or isinstance(n_contigs, bool) or not 0 <= n_contigs < 1 << 31:
+        raise ValueError(f"bam_stats: n_contigs {n_contigs!r}: a number of contigs")
+    st = BamStats()
+    head = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(BamStatsOpt)]
+    if host:
+        L.bmh_bam_stats_host.argtypes = head + [C.POINTER(BamStats)]
+        rc = L.bmh_bam_stats_host(records, len(records), int(n_contigs), C.byref(o), C.byref(st))
+    else:
+        import torch
+        L.bmh_bam_stats_device.argtypes = head + [C.c_void_p, C.POINTER(BamStats)]
+        rc = L.bmh_bam_stats_device(records, len(records), int(n_contigs), C.byref(o), torch.cuda.current_stream().cuda_stream, C.byref(st))
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_stats: " + _err(L))
+    return stats_dict(L, st)
+
+
 def reads_last_bam_counts() -> dict:
     """bmh_reads_last_bam_counts: what the process's last load_reads_files / run_files / bam_reads call left out of its BAM input -- records skipped (flag 0x100
     or 0x800), f and B tags left out of the comments"""
@@ -883,7 +965,7 @@ def reads_last_bam_counts() -> dict:
 class BamPostOpt(C.Structure):
     """bmh_bam_post_opt_t"""
     _fields_ = [("level", C.c_int32), ("window", C.c_uint32), ("index_format", C.c_int32), ("min_shift", C.c_int32), ("sort_mem", C.c_uint64), ("tmp_dir", C.c_char_p),
-                ("batch_bytes", C.c_uint64), ("markdup", C.POINTER(MarkdupOpt)), ("libraries", C.c_int32), ("coverage", C.POINTER(CoverageOpt)), ("collate", C.c_int32)]
+                ("batch_bytes", C.c_uint64), ("markdup", C.POINTER(MarkdupOpt)), ("libraries", C.c_int32), ("coverage", C.POINTER(CoverageOpt)), ("collate", C.c_int32), ("stats", C.POINTER(BamStatsOpt))]
 
 
 class BamPostResult(C.Structure):
@@ -906,8 +988,9 @@ def _names_blob(addr, n: int) -> list:
 
 
 def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 0, index_format: str = "bai", csi_min_shift: int = 14, sort_mem=None, sort_tmp=None, batch_bytes=None,
-             markdup: bool = False, libraries: bool = False, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None, collate: bool = False) -> dict:
-    """bmh_bam_post_file_device (host=True: bmh_bam_post_file_host, no device needed; it holds the whole record stream in memory): the BAM or SAM file `src` of any
+             markdup: bool = False, libraries: bool = False, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None, collate: bool = False, stats=None) -> dict:
+    """stats={insert_cap} (bmh_bam_post_file_stats_*; {} for the default): "stats" holds the file's statistics (bam_stats' dict), from the windows of the merge.
+    bmh_bam_post_file_device (host=True: bmh_bam_post_file_host, no device needed; it holds the whole record stream in memory): the BAM or SAM file `src` of any
     aligner (a path; plain, gzip or BGZF; a pipe) -> the coordinate-sorted BAM, handed to write(bytes) piece by piece, and a dict: "index" (the .bai or .csi
     bytes), "header" (the output header's text), "contigs" ((name, length) pairs), "counts" (BAM_POST_COUNTS' names), with markdup=True "markdup" (bam_markdup's
     counts; with libraries=True -- the header's @RG lines are the table of libraries -- "libraries" per library), with coverage={min_mapq, deletions, bin, tile}
@@ -942,8 +1025,9 @@ def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 
     if libraries:
         res.lib_counts, res.lib_optical, res.lib_grouped = (C.cast(a, _u64p) for a in arrays)
     co = coverage_opt(what=what, **coverage) if coverage is not None else None
+    so = stats_opt(what=what, **stats) if stats is not None else None
     o = BamPostOpt(int(level), int(window), ix_code, ix_shift, int(sort_mem or 0), os.fsencode(sort_tmp) if sort_tmp is not None else None, int(batch_bytes or 0),
-                   C.pointer(mo) if markdup else None, 1 if libraries else 0, C.pointer(co) if co is not None else None, 1 if collate else 0)
+                   C.pointer(mo) if markdup else None, 1 if libraries else 0, C.pointer(co) if co is not None else None, 1 if collate else 0, C.pointer(so) if so is not None else None)
     failed = []
 
     def sink(_user, p, n):
@@ -953,18 +1037,22 @@ def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 
         except BaseException as e:                                 # (an exception must not cross the C frames: the run ends, then it is raised)
             failed.append(e)
             return 1
-    cb, out, cov = _SINK(sink), BamPostResult(), Coverage()
+    cb, out, cov, st = _SINK(sink), BamPostResult(), Coverage(), BamStats()
     head = [C.c_char_p, C.POINTER(BamPostOpt)]
     tail = [_SINK, C.c_void_p, C.POINTER(BamPostResult), C.POINTER(MarkdupCounts), C.POINTER(Coverage)]
     args = [cb, None, C.byref(out), C.byref(res) if markdup else None, C.byref(cov) if co is not None else None]
     L.bmh_bam_post_result_free.argtypes, L.bmh_bam_post_result_free.restype = [C.POINTER(BamPostResult)], None
+    if so is not None:
+        tail, args = tail + [C.POINTER(BamStats)], args + [C.byref(st)]
     if host:
-        L.bmh_bam_post_file_host.argtypes = head + tail
-        rc = L.bmh_bam_post_file_host(os.fsencode(src), C.byref(o), *args)
+        call = L.bmh_bam_post_file_stats_host if so is not None else L.bmh_bam_post_file_host
+        call.argtypes = head + tail
+        rc = call(os.fsencode(src), C.byref(o), *args)
     else:
         import torch
-        L.bmh_bam_post_file_device.argtypes = head + [C.c_void_p] + tail
-        rc = L.bmh_bam_post_file_device(os.fsencode(src), C.byref(o), torch.cuda.current_stream().cuda_stream, *args)
+        call = L.bmh_bam_post_file_stats_device if so is not None else L.bmh_bam_post_file_device
+        call.argtypes = head + [C.c_void_p] + tail
+        rc = call(os.fsencode(src), C.byref(o), torch.cuda.current_stream().cuda_stream, *args)
     if failed:
         raise failed[0]
     if rc != 0:
@@ -978,6 +1066,8 @@ def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 
             r["markdup"] = _markdup_dict(mo, res, lib_names, libraries)
         if co is not None:
             r["coverage"] = coverage_dict(L, cov)
+        if so is not None:
+            r["stats"] = stats_dict(L, st)
         return r
     finally:
         L.bmh_bam_post_result_free(C.byref(out))
@@ -1314,6 +1404,31 @@ class NativeAligner:
         t, w = C.c_double(0), C.c_uint64(0)
         if L.bmh_aligner_coverage_ms(self.handle, C.byref(t), C.byref(w)) != 0:
             raise ValueError("bmh_aligner_coverage_ms: " + _err(L))
+        return (float(t.value), int(w.value)) if windows else float(t.value)
+
+    def set_stats(self, opt=None) -> None:
+        """bmh_aligner_set_stats: the sorted runs that follow compute their statistics under `opt` (a BamStatsOpt; None: off; refused unless the output is sorted BAM)"""
+        L = load_library()
+        L.bmh_aligner_set_stats.argtypes = [C.c_void_p, C.POINTER(BamStatsOpt)]
+        if L.bmh_aligner_set_stats(self.handle, C.byref(opt) if opt is not None else None) != 0:
+            raise ValueError("bmh_aligner_set_stats: " + _err(L))
+
+    def stats(self) -> dict:
+        """bmh_aligner_stats: the statistics of the last sorted run that computed them, as bam_stats returns them"""
+        L = load_library()
+        L.bmh_aligner_stats.argtypes = [C.c_void_p, C.POINTER(BamStats)]
+        st = BamStats()
+        if L.bmh_aligner_stats(self.handle, C.byref(st)) != 0:
+            raise ValueError("bmh_aligner_stats: " + _err(L))
+        return stats_dict(L, st)
+
+    def stats_ms(self, windows: bool = False):
+        """bmh_aligner_stats_ms: the device milliseconds the last such run's windows spent in the statistics kernel; windows=True: (milliseconds, windows timed)"""
+        L = load_library()
+        L.bmh_aligner_stats_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        t, w = C.c_double(0), C.c_uint64(0)
+        if L.bmh_aligner_stats_ms(self.handle, C.byref(t), C.byref(w)) != 0:
+            raise ValueError("bmh_aligner_stats_ms: " + _err(L))
         return (float(t.value), int(w.value)) if windows else float(t.value)
 
     def markdup_counts(self) -> dict:

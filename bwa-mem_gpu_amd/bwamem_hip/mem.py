@@ -48,7 +48,11 @@ is written: `samtools coverage`'s table (one row per contig and a row `total`), 
 the mean depth of every --coverage-bin N positions (--coverage-bed and --coverage-bin go together).  A record counts by `samtools depth`'s default filters --
 unmapped, secondary, QC-failed and duplicate records are out, so --markdup's duplicates are counted out; supplementary records count -- and with
 --coverage-min-mapq Q (0 .. 255) only at mapq >= Q; it covers the positions under M, = and X, and under D with --coverage-deletions (`samtools depth -J`).
-There is no base-quality filter and no correction for overlapping mates.  With --rg the coverage is the whole file's, not per library.  An option that is
+There is no base-quality filter and no correction for overlapping mates.  With --rg the coverage is the whole file's, not per library.
+--flagstat PATH, --idxstats PATH and --stats PATH (need --sort) write `samtools flagstat`'s sixteen lines, `samtools idxstats`' table and a sectioned summary (flag
+and contig counts, reads, bases, operations, NM, the mapq histogram, the insert-size histogram per orientation and its median, MAD, mode, mean and SD) of the
+file being written, computed on the device while it is written, from the records in their final order with --markdup's final 0x400 flags.  The statistics are
+the whole file's, not per read group or library.  An option that is
 not on that list is refused by name.  Two input files imply pairs.  One plain, regular file is offered to Aligner.align_file first, which takes it when every
 record has one sequence line (its own counting pass decides, before anything is written); every other input goes through
 Aligner.align_files; the text is the same.  A refused file ends the command with status 1 and the library's message on stderr.
@@ -85,6 +89,7 @@ def main(argv=None) -> int:
     keep_rg = False
     collate, collate_mem = False, None
     cov_paths, cov_bin, cov_mapq, cov_del = {}, None, None, False
+    stats_paths = {}
     groups = []                                                     # --rg LINE: [line, files...]; the positionals behind it are its files
     i = 0
     while i < len(argv):
@@ -148,6 +153,12 @@ def main(argv=None) -> int:
                 print(f"[bwamem_hip.mem] option {a} needs a value", file=sys.stderr)
                 return 2
             cov_paths[a] = argv[i + 1]
+            i += 1
+        elif a in ("--flagstat", "--idxstats", "--stats"):
+            if i + 1 >= len(argv):
+                print(f"[bwamem_hip.mem] option {a} needs a value", file=sys.stderr)
+                return 2
+            stats_paths[a] = argv[i + 1]
             i += 1
         elif a == "--coverage-bin":
             if i + 1 >= len(argv) or not (argv[i + 1].isascii() and argv[i + 1].isdigit()) or not 1 <= int(argv[i + 1]) <= 0xffffffff:
@@ -263,6 +274,9 @@ def main(argv=None) -> int:
     if (cov_paths or cov_bin is not None or cov_mapq is not None or cov_del) and not sort:
         print("[bwamem_hip.mem] --coverage, --coverage-hist, --coverage-bed, --coverage-bin, --coverage-min-mapq and --coverage-deletions need --sort (depth is computed where the sorted file is written)", file=sys.stderr)
         return 2
+    if stats_paths and not sort:
+        print("[bwamem_hip.mem] --flagstat, --idxstats and --stats need --sort (the statistics are computed where the sorted file is written)", file=sys.stderr)
+        return 2
     if ("--coverage-bed" in cov_paths) != (cov_bin is not None):
         print("[bwamem_hip.mem] --coverage-bed and --coverage-bin go together (the bins of the BED file)", file=sys.stderr)
         return 2
@@ -304,6 +318,8 @@ def main(argv=None) -> int:
         if cov_paths:
             fmt_kw.update(coverage=cov_paths.get("--coverage"), coverage_hist=cov_paths.get("--coverage-hist"), coverage_bed=cov_paths.get("--coverage-bed"), coverage_bin=cov_bin,
                           coverage_min_mapq=cov_mapq, coverage_deletions=cov_del)
+        if stats_paths:
+            fmt_kw.update(flagstat=stats_paths.get("--flagstat"), idxstats=stats_paths.get("--idxstats"), stats=stats_paths.get("--stats"))
         done = False
         if groups:
             al.align_groups([(g[0], g[1], g[2] if len(g) == 3 else None) for g in groups], out=out, paired=interleaved, **fmt_kw)

@@ -37,6 +37,7 @@
 #include "bam_sort.h"
 #include "bam_dup.h"
 #include "bam_cov.h"
+#include "bam_stats.h"
 #include "batch_queue.h"
 
 namespace {
@@ -900,6 +901,7 @@ struct bmh_aligner {
 	uint64_t grp_counts[BDP_GRP_N] = {0, 0, 0}; bool grp_valid = false;      // ... with barcode edits: the three grouping counts of the last such run
 	uint64_t no_barcode = 0; bool bc_valid = false;      // ... with barcodes: the templates without one in the last such run
 	double dup_times[3] = {0, 0, 0};                     // ... its decision and its windows' flag steps in ms, the bytes its batches' ordinals and entries took on their way down
+	bool stats_on = false; bst_plan_t stats_plan, stats_plan_last; bst_result_t stats_res; bool stats_valid = false; double stats_ms[2] = {0, 0};      // statistics (bmh_aligner_set_stats): as coverage's
 	bool cov_on = false; bcv_plan_t cov_plan, cov_plan_last; bcv_result_t cov_res; bool cov_valid = false; double cov_ms[2] = {0, 0};      // coverage (bmh_aligner_set_coverage): the plan of the runs that follow, the last such run's results and its steps' device ms and the windows timed
 };
 
@@ -933,7 +935,7 @@ int bmh_aligner_set_output(bmh_aligner_t *h, int format, int level)
 	if (format != BMH_OUT_SAM && format != BMH_OUT_BAM && format != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_output: format %d (BMH_OUT_SAM, BMH_OUT_BAM or BMH_OUT_BAM_SORTED)", format); return BMH_EINVAL; }
 	if (format != BMH_OUT_SAM && level != 0 && level != 1) { bmh_set_error("bmh_aligner_set_output: level %d (0 or 1)", level); return BMH_EINVAL; }
 	if (format == BMH_OUT_BAM_SORTED) { h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), "sorted BAM output", h->ix_format, h->ix_shift)); }
-	if (format != BMH_OUT_BAM_SORTED) h->cov_on = false;
+	if (format != BMH_OUT_BAM_SORTED) h->cov_on = h->stats_on = false;
 	if (format != BMH_OUT_BAM_SORTED) { h->a.markdup = false; h->a.plan.opt.distance = -1; h->a.plan.bc.mode = BDP_BC_OFF; h->a.plan.bc.pack = 0; }      // (duplicates are marked in sorted output only: the options go with the format)
 	h->a.out_fmt = format; h->a.out_level = level;
 	return BMH_OK;
@@ -1007,6 +1009,36 @@ int bmh_aligner_coverage_ms(bmh_aligner_t *h, double *out, uint64_t *windows)
 	if (!h->cov_valid) { bmh_set_error("%s: no run has computed coverage (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
 	*out = h->cov_ms[0];
 	if (windows) *windows = (uint64_t)h->cov_ms[1];
+	return BMH_OK;
+}
+
+int bmh_aligner_set_stats(bmh_aligner_t *h, const bmh_bam_stats_opt_t *opt)
+{
+	const char *fn = "bmh_aligner_set_stats";
+	if (!h) { bmh_set_error("%s: null aligner", fn); return BMH_EINVAL; }
+	if (!opt) { h->stats_on = false; return BMH_OK; }
+	if (h->a.out_fmt != BMH_OUT_BAM_SORTED) { bmh_set_error("%s: the statistics are computed while sorted output is written (bmh_aligner_set_output with BMH_OUT_BAM_SORTED comes first)", fn); return BMH_EINVAL; }
+	bst_plan_t P;
+	RCK(bst_plan_make(P, opt->insert_cap, h->a.n_contigs, fn));
+	h->stats_plan = P; h->stats_on = true;
+	return BMH_OK;
+}
+
+int bmh_aligner_stats(bmh_aligner_t *h, bmh_bam_stats_t *out)
+{
+	const char *fn = "bmh_aligner_stats";
+	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (!h->stats_valid) { bmh_set_error("%s: no run has computed statistics (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
+	return bst_export(h->stats_plan_last, h->stats_res, out, fn);
+}
+
+int bmh_aligner_stats_ms(bmh_aligner_t *h, double *out, uint64_t *windows)
+{
+	const char *fn = "bmh_aligner_stats_ms";
+	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	if (!h->stats_valid) { bmh_set_error("%s: no run has computed statistics (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
+	*out = h->stats_ms[0];
+	if (windows) *windows = (uint64_t)h->stats_ms[1];
 	return BMH_OK;
 }
 
@@ -1155,7 +1187,7 @@ struct out_stage_t {
 	int lib_of(int group) const { return group >= 0 && (size_t)group < h->a.plan.table.lib.size() ? (int)h->a.plan.table.lib[(size_t)group] : -1; }
 	int emit(const void *p, size_t n) { if (n && sink(user, (const char *)p, n) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; } n_bytes += n; return BMH_OK; }
 	// (the index is valid again once the merge has written the whole file)
-	int begin() { if (fmt == BMH_OUT_BAM_SORTED) { h->cov_valid = false; h->cov_ms[0] = h->cov_ms[1] = 0; h->dup_valid = false; h->opt_valid = false; h->bc_valid = false; h->opt_ms = 0; h->dup_times[0] = h->dup_times[1] = h->dup_times[2] = 0; h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), fn, h->ix_format, h->ix_shift)); h->sort_ix.valid = false;
+	int begin() { if (fmt == BMH_OUT_BAM_SORTED) { h->cov_valid = false; h->cov_ms[0] = h->cov_ms[1] = 0; h->stats_valid = false; h->stats_ms[0] = h->stats_ms[1] = 0; h->dup_valid = false; h->opt_valid = false; h->bc_valid = false; h->opt_ms = 0; h->dup_times[0] = h->dup_times[1] = h->dup_times[2] = 0; h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), fn, h->ix_format, h->ix_shift)); h->sort_ix.valid = false;
 		if (h->a.markdup) RCK(bsr_markdup_contigs(h->a.n_contigs, h->a.len.data(), h->a.name_ptr.data(), fn)); } return BMH_OK; }
 	int device_batch(const result_t &R)
 	{
@@ -1241,15 +1273,23 @@ struct out_stage_t {
 			if (!(cov.p = bcv_dev_create())) rc = BMH_ENOMEM;
 			if (rc == BMH_OK) rc = bcv_begin_device(cov.p, h->cov_plan_last, L0.st);
 		}
+		struct stats_own_t { bst_dev_t *p = nullptr; ~stats_own_t() { if (p) bst_dev_free(p); } } stats;      // statistics: the run's accumulator, from the first window to the results
+		if (rc == BMH_OK && h->stats_on) {
+			h->stats_plan_last = h->stats_plan;
+			if (!(stats.p = bst_dev_create())) rc = BMH_ENOMEM;
+			if (rc == BMH_OK) rc = bst_begin_device(stats.p, h->stats_plan_last, L0.st);
+		}
 		if (rc == BMH_OK) rc = bsr_merge_device(L0.bsr, L0.bam, h->store, h->sort_window, h->a.out_level, L0.st, h->sort_ix, forward, this, h->a.markdup ? h->dup_counts : nullptr, P, h->dup_times, &h->opt_ms,
-		                                        cov.p, cov.p ? h->cov_ms : nullptr);
+		                                        cov.p, cov.p ? h->cov_ms : nullptr, stats.p, stats.p ? h->stats_ms : nullptr);
+		if (rc == BMH_OK && stats.p) rc = bst_finish_device(stats.p, L0.st, h->stats_res, fn);
+		if (trace && stats.p) fprintf(stderr, "[aligner] statistics: the kernels of %.0f windows took %.2f ms on the device, %.3f ms per window\n", h->stats_ms[1], h->stats_ms[0], h->stats_ms[0] / (h->stats_ms[1] > 0 ? h->stats_ms[1] : 1));
 		if (rc == BMH_OK && cov.p) rc = bcv_finish_device(cov.p, L0.st, h->cov_res, fn, h->cov_ms);
 		if (trace && cov.p) fprintf(stderr, "[aligner] coverage: the depth steps of %.0f windows took %.2f ms on the device, %.3f ms per window (tile %llu, %llu bins)\n", h->cov_ms[1], h->cov_ms[0], h->cov_ms[0] / (h->cov_ms[1] > 0 ? h->cov_ms[1] : 1), (unsigned long long)h->cov_plan_last.tile, (unsigned long long)h->cov_plan_last.n_bins());
 		for (size_t k = 0; rc == BMH_OK && k < h->store.lib_info.size() && k / 3 < n_lib; ++k) h->lib_counts[BDP_N_COUNTS * (k / 3) + BDP_SECSUP + k % 3] = h->store.lib_info[k];
 		if (trace && h->a.markdup) fprintf(stderr, "[aligner] duplicate marking: %.0f bytes of ordinals and entries came down with the batches\n", h->dup_times[2]);
 		if (trace) fprintf(stderr, "[aligner] sorted output: %zu runs (%llu spilled) merged in %.1f ms\n", h->store.runs.size(), (unsigned long long)h->store.spilled, (now_s() - tm0) * 1e3);
 		h->store.clear();
-		if (rc == BMH_OK) { h->sort_ix.valid = true; h->cov_valid = h->cov_on; h->dup_valid = h->a.markdup; h->opt_valid = optical; h->bc_valid = barcode; h->grp_valid = grouped; }
+		if (rc == BMH_OK) { h->sort_ix.valid = true; h->cov_valid = h->cov_on; h->stats_valid = h->stats_on; h->dup_valid = h->a.markdup; h->opt_valid = optical; h->bc_valid = barcode; h->grp_valid = grouped; }
 		return rc;
 	}
 };

@@ -225,14 +225,18 @@ uint32_t bpo_template_start(const uint8_t *recs, const uint64_t *off, uint32_t i
 	return i;
 }
 
-int bpo_run_t::begin(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res, bmh_coverage_t *cov, const char *f, bpo_convert_t conv)
+int bpo_run_t::begin(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res, bmh_coverage_t *cov, const char *f, bpo_convert_t conv,
+                     bmh_bam_stats_t *st, bool with_stats)
 {
 	fn = f;
 	if (out) memset(out, 0, sizeof *out);
 	if (cov) memset(cov, 0, sizeof *cov);
+	if (st) memset(st, 0, sizeof *st);
 	if (!path || !sink || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	if (opt) o = *opt; else bmh_bam_post_opt_default(&o);
 	markdup = o.markdup != nullptr; coverage = o.coverage != nullptr;
+	if (!with_stats) o.stats = nullptr;                               // (the entry points from before the field do not read it)
+	stats = o.stats != nullptr;
 	mode = (markdup ? (uint32_t)BPO_MARKDUP : 0u) | (coverage ? (uint32_t)BPO_COVERAGE : 0u);
 	if (o.level != 0 && o.level != 1) { bmh_set_error("%s: level %d (0 or 1)", fn, o.level); return BMH_EINVAL; }
 	int rc = bsr_index_format_check(o.index_format, o.min_shift, fn);
@@ -244,6 +248,7 @@ int bpo_run_t::begin(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_si
 	if (o.libraries && !markdup) { bmh_set_error("%s: libraries need marking: the header's @RG lines say which templates may be duplicates of each other", fn); return BMH_EINVAL; }
 	if (markdup && !res) { bmh_set_error("%s: null argument (marking needs its counts record)", fn); return BMH_EINVAL; }
 	if (coverage && !cov) { bmh_set_error("%s: null argument (coverage needs its record)", fn); return BMH_EINVAL; }
+	if (stats && !st) { bmh_set_error("%s: null argument (the statistics need their record)", fn); return BMH_EINVAL; }
 	if (markdup) {
 		mo = *o.markdup;
 		if (o.libraries && (mo.rg_ids || mo.rg_lib || mo.n_groups)) { bmh_set_error("%s: libraries come from the header's @RG lines or from the options' read groups, not both", fn); return BMH_EINVAL; }
@@ -251,6 +256,7 @@ int bpo_run_t::begin(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_si
 	}
 	if ((rc = in.open(path, fn, conv)) != BMH_OK) return rc;
 	const int n_ref = (int)in.names.size();
+	if (stats && (rc = bst_plan_make(SP, o.stats->insert_cap, n_ref, fn)) != BMH_OK) return rc;
 	for (const std::string &nm : in.names) name_ptr.push_back(nm.c_str());
 	if ((rc = ix.init(n_ref, in.len.data(), fn, o.index_format, o.min_shift)) != BMH_OK) return rc;
 	if (markdup && (rc = bsr_markdup_contigs(n_ref, in.len.data(), name_ptr.data(), fn)) != BMH_OK) return rc;
@@ -359,12 +365,12 @@ int host_batch(bpo_run_t &R, host_state_t &S)
 }
 }   // namespace
 
-extern "C" int bmh_bam_post_file_host(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res, bmh_coverage_t *cov)
+static int post_host(const char *fn, const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res, bmh_coverage_t *cov,
+                     bmh_bam_stats_t *stats, bool with_stats)
 {
-	const char *fn = "bmh_bam_post_file_host";
 	try {
 		bpo_run_t R;
-		int rc = R.begin(path, opt, sink, out, res, cov, fn, convert_host);
+		int rc = R.begin(path, opt, sink, out, res, cov, fn, convert_host, stats, with_stats);
 		if (rc != BMH_OK) return rc;
 		host_state_t S;
 		while ((rc = R.in.next(R.o.batch_bytes, fn)) == 1) if ((rc = host_batch(R, S)) != BMH_OK) return rc;
@@ -399,6 +405,8 @@ extern "C" int bmh_bam_post_file_host(const char *path, const bmh_bam_post_opt_t
 		const uint64_t base = members.size();
 		bcv_host_t H;
 		if (R.coverage) H.begin(R.CP);
+		bst_host_t SH;
+		if (R.stats) SH.begin(R.SP);
 		const uint64_t W = R.o.window ? R.o.window : std::max<uint64_t>(1, (64ull << 20) / std::max<uint64_t>(1, n ? S.recs.size() / n : 1));
 		std::vector<uint8_t> buf; std::vector<uint64_t> soff, moff;
 		for (size_t a = 0; a < n; a += W) {
@@ -414,12 +422,27 @@ extern "C" int bmh_bam_post_file_host(const char *path, const bmh_bam_post_opt_t
 			if (sr != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; }
 			R.ix.window_host(buf.data(), soff.data(), (uint32_t)(b - a), moff.data());
 			if (R.coverage && (rc = H.window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;
+			if (R.stats && (rc = SH.window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;
 		}
 		if (R.coverage && (rc = H.finish(fn)) != BMH_OK) return rc;
 		if (sink(user, (const char *)bmh_bgzf_eof, 28) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; }
 		std::string ib;
 		if ((rc = R.ix.bytes(base, ib)) != BMH_OK) return rc;
 		if (R.coverage && (rc = bcv_export(R.CP, H.R, cov, fn)) != BMH_OK) return rc;
-		return R.finish(ib, out);
+		if (R.stats) { SH.finish(); if ((rc = bst_export(R.SP, SH.R, stats, fn)) != BMH_OK) return rc; }
+		if ((rc = R.finish(ib, out)) != BMH_OK && R.stats) bmh_bam_stats_free(stats);
+		return rc;
 	} catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+}
+
+extern "C" int bmh_bam_post_file_host(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res, bmh_coverage_t *cov)
+{
+	return post_host("bmh_bam_post_file_host", path, opt, sink, user, out, res, cov, nullptr, false);
+}
+
+// the same run and, with opt->stats, the statistics of the file from the windows of its merge (csrc/bam_stats_host.cpp)
+extern "C" int bmh_bam_post_file_stats_host(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res,
+                                            bmh_coverage_t *cov, bmh_bam_stats_t *stats)
+{
+	return post_host("bmh_bam_post_file_stats_host", path, opt, sink, user, out, res, cov, stats, true);
 }

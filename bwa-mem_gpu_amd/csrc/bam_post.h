@@ -9,6 +9,7 @@
 #include "bam_sort.h"
 #include "bam_dup.h"
 #include "bam_cov.h"
+#include "bam_stats.h"
 #include "bam_post_core.h"
 
 #define BPO_BATCH_DEFAULT (256ull << 20)
@@ -40,13 +41,14 @@ private:
 
 // one run: the options as checked, the marking plan, the coverage plan, the index, the counts
 struct bpo_run_t {
-	const char *fn = ""; bmh_bam_post_opt_t o; bool markdup = false, coverage = false; uint32_t mode = 0;
+	const char *fn = ""; bmh_bam_post_opt_t o; bool markdup = false, coverage = false, stats = false; uint32_t mode = 0;
 	bmh_markdup_opt_t mo; bmh_rg_table_t rg; std::vector<const char *> rg_ids;
-	bdp_plan_t P; bcv_plan_t CP; bsr_index_t ix; bpo_input_t in; bmh_bam_post_counts_t counts = {0, 0, 0, 0, 0, 0};
+	bdp_plan_t P; bcv_plan_t CP; bst_plan_t SP; bsr_index_t ix; bpo_input_t in; bmh_bam_post_counts_t counts = {0, 0, 0, 0, 0, 0};
 	bool collate = false;                                              // templates by name over the whole file (BDP_TPL_FILE, csrc/bam_tpl_core.h)
 	uint64_t sam_line0() const { return in.bam ? 0 : in.header_lines + 1; }      // the SAM line of record 0 (0: a BAM)
 	std::vector<const char *> name_ptr;
-	int begin(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res, bmh_coverage_t *cov, const char *f, bpo_convert_t conv);
+	int begin(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res, bmh_coverage_t *cov, const char *f, bpo_convert_t conv,
+	          bmh_bam_stats_t *st = nullptr, bool with_stats = false);      // with_stats: the entry point reads o.stats (bmh_bam_post_file_stats_*)
 	int header_members(std::string &members) const;                    // the header as BGZF members of the run's level
 	int finish(const std::string &index_bytes, bmh_bam_post_result_t *out) const;     // the results' arrays (malloc'd)
 };

@@ -97,11 +97,11 @@ namespace {
 struct dev_state_t {
 	hipStream_t st = nullptr;
 	dev_buf<uint8_t> recs, off, word; dev_buf<char> text;
-	bsr_dev_t *bsr = nullptr; bdp_dev_t *bdp = nullptr; bmh_bam_ws_t *ws = nullptr, *sam_ws = nullptr; bcv_dev_t *cov = nullptr; btp_dev_t *btp = nullptr;
+	bsr_dev_t *bsr = nullptr; bdp_dev_t *bdp = nullptr; bmh_bam_ws_t *ws = nullptr, *sam_ws = nullptr; bcv_dev_t *cov = nullptr; btp_dev_t *btp = nullptr; bst_dev_t *stats = nullptr;
 	dev_buf<char> ctg_names; dev_buf<uint32_t> ctg_noff; bool ctg_up = false;
 	bsr_store_t store;
 	std::vector<uint8_t> sorted; std::vector<uint64_t> keys, soff, bcs; std::vector<uint32_t> stpl, lib3; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> locs;
-	~dev_state_t() { if (bsr) bsr_dev_free(bsr); if (bdp) bdp_dev_free(bdp); if (ws) bmh_bam_ws_free(ws); if (sam_ws) bmh_bam_ws_free(sam_ws); if (cov) bcv_dev_free(cov); if (btp) btp_dev_free(btp); }
+	~dev_state_t() { if (bsr) bsr_dev_free(bsr); if (bdp) bdp_dev_free(bdp); if (ws) bmh_bam_ws_free(ws); if (sam_ws) bmh_bam_ws_free(sam_ws); if (cov) bcv_dev_free(cov); if (btp) btp_dev_free(btp); if (stats) bst_dev_free(stats); }
 };
 
 // SAM lines through the device's converter; the records come back to the host, where the chain and the batches are made as for a BAM
@@ -208,12 +208,12 @@ struct sink_t { bmh_sam_sink_t sink; void *user; };
 int forward(void *u, const char *b, size_t n) { sink_t *s = (sink_t *)u; return s->sink(s->user, b, n); }
 
 int post_device(const char *fn, const char *path, const bmh_bam_post_opt_t *opt, void *stream, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res,
-                bmh_coverage_t *cov)
+                bmh_coverage_t *cov, bmh_bam_stats_t *stats, bool with_stats)
 {
 	dev_state_t D; D.st = (hipStream_t)stream;
 	bpo_run_t R;
 	RCK(R.begin(path, opt, sink, out, res, cov, fn, [&D](const char *text, size_t n, int nc, const std::string &blob, const std::vector<uint32_t> &noff, std::vector<uint8_t> &recs, uint32_t *bad,
-	                                                       uint32_t *status) { return convert_device(D, text, n, nc, blob, noff, recs, bad, status); }));
+	                                                       uint32_t *status) { return convert_device(D, text, n, nc, blob, noff, recs, bad, status); }, stats, with_stats));
 	if (!(D.bsr = bsr_dev_create()) || !(D.ws = bmh_bam_ws_create())) return BMH_ENOMEM;
 	if (R.o.sort_mem) D.store.mem_bytes = R.o.sort_mem;
 	if (R.o.tmp_dir) D.store.tmp_dir = R.o.tmp_dir;
@@ -247,10 +247,15 @@ int post_device(const char *fn, const char *path, const bmh_bam_post_opt_t *opt,
 		if (!(D.cov = bcv_dev_create())) return BMH_ENOMEM;
 		RCK(bcv_begin_device(D.cov, R.CP, D.st));
 	}
+	if (R.stats) {
+		if (!(D.stats = bst_dev_create())) return BMH_ENOMEM;
+		RCK(bst_begin_device(D.stats, R.SP, D.st));
+	}
 	sink_t fw = {sink, user};
 	R.counts.spilled_runs = D.store.spilled;
-	RCK(bsr_merge_device(D.bsr, D.ws, D.store, R.o.window, R.o.level, D.st, R.ix, forward, &fw, R.markdup ? res->counts : nullptr, P, nullptr, nullptr, D.cov, nullptr));
-	bcv_result_t CR;
+	RCK(bsr_merge_device(D.bsr, D.ws, D.store, R.o.window, R.o.level, D.st, R.ix, forward, &fw, R.markdup ? res->counts : nullptr, P, nullptr, nullptr, D.cov, nullptr, D.stats, nullptr));
+	bcv_result_t CR; bst_result_t SR;
+	if (R.stats) RCK(bst_finish_device(D.stats, D.st, SR, fn));
 	if (R.coverage) RCK(bcv_finish_device(D.cov, D.st, CR, fn, nullptr));
 	if (R.markdup && P.groups() && P.lib_counts)                       // every library's line counts and templates, as the batches counted them
 		for (size_t k = 0; k < D.store.lib_info.size() && k / 3 < P.n_lib(); ++k) P.lib_counts[BDP_N_COUNTS * (k / 3) + BDP_SECSUP + k % 3] = D.store.lib_info[k];
@@ -258,10 +263,13 @@ int post_device(const char *fn, const char *path, const bmh_bam_post_opt_t *opt,
 	std::string ib;
 	RCK(R.ix.bytes(members.size(), ib));
 	if (R.coverage) RCK(bcv_export(R.CP, CR, cov, fn));
+	if (R.stats) RCK(bst_export(R.SP, SR, stats, fn));
 	if (trace)
 		fprintf(stderr, "[bam post] %llu records in %llu batches: read, checked and sorted in %.1f ms, templates by name over the file in %.1f ms, merged in %.1f ms\n",
 		        (unsigned long long)R.counts.records, (unsigned long long)R.counts.batches, t_batches - t_begin, t_grouped - t_batches, now_ms() - t_grouped);
-	return R.finish(ib, out);
+	const int frc = R.finish(ib, out);
+	if (frc != BMH_OK && R.stats) bmh_bam_stats_free(stats);
+	return frc;
 }
 
 }   // namespace
@@ -270,6 +278,15 @@ extern "C" int bmh_bam_post_file_device(const char *path, const bmh_bam_post_opt
                                         bmh_coverage_t *cov)
 {
 	const char *fn = "bmh_bam_post_file_device";
-	try { return post_device(fn, path, opt, stream, sink, user, out, res, cov); }
+	try { return post_device(fn, path, opt, stream, sink, user, out, res, cov, nullptr, false); }
+	catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+}
+
+// the same run and, with opt->stats, the statistics of the file from the windows of its merge (csrc/bam_stats_kernels.hip)
+extern "C" int bmh_bam_post_file_stats_device(const char *path, const bmh_bam_post_opt_t *opt, void *stream, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res,
+                                              bmh_coverage_t *cov, bmh_bam_stats_t *stats)
+{
+	const char *fn = "bmh_bam_post_file_stats_device";
+	try { return post_device(fn, path, opt, stream, sink, user, out, res, cov, stats, true); }
 	catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
 }

@@ -85,17 +85,20 @@ int bsr_sort_keys_device(bsr_dev_t *d, const uint64_t *keys, uint64_t n, void *s
 // window in src.  The records are gathered into order, compressed (ws), indexed (ix: heads appended; lin and counts stay on the device until bsr_index_finish) and
 // the members handed to the sink
 // cov (or NULL): the run's coverage (csrc/bam_cov_kernels.hip, begun by the caller) takes the window behind the flag step; cov_ms (or NULL) += its device milliseconds
+// stats (or NULL): the run's statistics (csrc/bam_stats_kernels.hip, begun by the caller) take the window beside it; stats_ms (or NULL) [2] += their milliseconds, the windows
 // dup, tord [n] (host), flag_ms (or NULL, all three): the decided duplicates (bdp_decide_device) and every record's global template ordinal -- the flags are set between the gather and the compressor
 int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64_t src_bytes, const uint64_t *src_off, const uint32_t *size, uint32_t n, int level,
                       void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, struct bdp_dev_t *dup, const uint32_t *tord, double *flag_ms,
-                      struct bcv_dev_t *cov = nullptr, double *cov_ms = nullptr);
+                      struct bcv_dev_t *cov = nullptr, double *cov_ms = nullptr, struct bst_dev_t *stats = nullptr, double *stats_ms = nullptr);
 // every run of the store -> the record members of the sorted file (to the sink, in windows of `window` records; 0: about 64 MiB of records) and its index
 // dup_counts (or NULL) [8]: mark the duplicates among the store's templates first, as P says (csrc/bam_dup_kernels.hip: the store keeps the locations and the barcode
 // words P's optical step and barcodes ask for), and flag every window's records; the counts of bam_dup.h
 // cov, cov_ms (or NULL): every window goes through the run's coverage (bcv_begin_device before, bcv_finish_device behind: the caller's)
+// stats, stats_ms (or NULL): every window goes through the run's statistics (bst_begin_device before, bst_finish_device behind: the caller's)
 // dup_ms (or NULL) [2]: += the decision's milliseconds (host clock around bdp_decide_device) and the windows' flag steps' (events around the upload of the ordinals
 // and the flag kernel); opt_ms (or NULL) += the optical step's milliseconds
 int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user,
-                     uint64_t *dup_counts, const bdp_plan_t &P, double *dup_ms = nullptr, double *opt_ms = nullptr, struct bcv_dev_t *cov = nullptr, double *cov_ms = nullptr);
+                     uint64_t *dup_counts, const bdp_plan_t &P, double *dup_ms = nullptr, double *opt_ms = nullptr, struct bcv_dev_t *cov = nullptr, double *cov_ms = nullptr,
+                     struct bst_dev_t *stats = nullptr, double *stats_ms = nullptr);
 int bsr_index_begin(bsr_dev_t *d, const bsr_index_t &ix, void *stream);
 int bsr_index_finish(bsr_dev_t *d, bsr_index_t &ix, void *stream);

@@ -12,6 +12,7 @@
 #include "bam_sort.h"
 #include "bam_dup.h"
 #include "bam_cov.h"
+#include "bam_stats.h"
 
 #ifndef O_TMPFILE
 #define O_TMPFILE 0
@@ -305,7 +306,7 @@ extern "C" int bmh_bam_sort_host(const uint8_t *recs, uint64_t n_bytes, uint8_t 
 // header members, the sorted records in windows of `window` records (0: as many as hold about 64 MiB), the end-of-file member; and the index
 static int sorted_file_host(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
                             const bmh_sorted_file_opt_t &o, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts, const bdp_plan_t &P,
-                            bcv_host_t *cov = nullptr)
+                            bcv_host_t *cov = nullptr, bst_host_t *stats = nullptr)
 {
 	const int level = o.level; const uint32_t window = o.window;
 	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
@@ -351,6 +352,7 @@ static int sorted_file_host(const char *fn, const char *header_text, int n_conti
 		if ((rc = members(buf.data(), buf.size(), &moff)) != BMH_OK) return rc;
 		ix.window_host(buf.data(), soff.data(), (uint32_t)(b - a), moff.data());
 		if (cov && (rc = cov->window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;      // the window in its final order, with its final flags
+		if (stats && (rc = stats->window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;
 	}
 	if (cov && (rc = cov->finish(fn)) != BMH_OK) return rc;
 	file.append((const char *)bmh_bgzf_eof, 28);
@@ -395,6 +397,46 @@ extern "C" int bmh_bam_sorted_file_coverage_host(const char *header_text, int n_
 		rc = sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P, &H);
 		if (rc == BMH_OK && (rc = bcv_export(CP, H.R, cov, fn)) != BMH_OK) {      // the one failure behind the file's bytes: they are the call's to release
 			bmh_free(*bam); bmh_free(*index); *bam = *index = nullptr; *bam_bytes = *index_bytes = 0;
+		}
+	} catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); rc = BMH_ENOMEM; }
+	return rc;
+}
+
+// the sorted file and, from the same windows of the merge, its statistics and, with cov, its coverage (the host form of csrc/bam_stats_kernels.hip)
+extern "C" int bmh_bam_sorted_file_stats_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                              const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, const bmh_bam_stats_opt_t *stats_opt, uint8_t **bam, uint64_t *bam_bytes,
+                                              uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res, bmh_coverage_t *cov, bmh_bam_stats_t *stats)
+{
+	const char *fn = "bmh_bam_sorted_file_stats_host";
+	if (bam) *bam = nullptr;                                         // (before anything can be refused: a caller who frees what a failed call left frees nothing)
+	if (index) *index = nullptr;
+	if (cov) memset(cov, 0, sizeof *cov);
+	if (!stats) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	memset(stats, 0, sizeof *stats);
+	bmh_sorted_file_opt_t o; bdp_plan_t P;
+	int rc = bsr_file_opt_check(opt, res, fn, o, P);
+	if (rc != BMH_OK) return rc;
+	bmh_bam_stats_opt_t so; bmh_bam_stats_opt_default(&so);
+	if (stats_opt) so = *stats_opt;
+	bst_plan_t SP;
+	if ((rc = bst_plan_make(SP, so.insert_cap, n_contigs, fn)) != BMH_OK) return rc;
+	bmh_coverage_opt_t co; bmh_coverage_opt_default(&co);
+	if (cov_opt) co = *cov_opt;
+	bcv_plan_t CP;
+	if (cov && (rc = bcv_plan_make(CP, co.min_mapq, co.deletions, co.bin, co.tile, n_contigs, contig_len, fn)) != BMH_OK) return rc;
+	try {
+		bcv_host_t H; bst_host_t SH;
+		if (cov) H.begin(CP);
+		SH.begin(SP);
+		rc = sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P, cov ? &H : nullptr, &SH);
+		if (rc == BMH_OK) {
+			SH.finish();
+			if (cov) rc = bcv_export(CP, H.R, cov, fn);
+			if (rc == BMH_OK && (rc = bst_export(SP, SH.R, stats, fn)) != BMH_OK && cov) {
+				bmh_free(cov->n_reads); bmh_free(cov->cov_bases); bmh_free(cov->sum_depth); bmh_free(cov->max_depth); bmh_free(cov->sum_mapq); bmh_free(cov->hist); bmh_free(cov->bin_sum);
+				memset(cov, 0, sizeof *cov);
+			}
+			if (rc != BMH_OK) { bmh_free(*bam); bmh_free(*index); *bam = *index = nullptr; *bam_bytes = *index_bytes = 0; }      // the failures behind the file's bytes: they are the call's to release
 		}
 	} catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); rc = BMH_ENOMEM; }
 	return rc;

@@ -25,6 +25,7 @@
 #include "bam_sort.h"
 #include "bam_dup.h"
 #include "bam_cov.h"
+#include "bam_stats.h"
 #include "bam_ws.h"
 
 struct bsr_dev_t {
@@ -255,7 +256,8 @@ int bsr_index_finish(bsr_dev_t *d, bsr_index_t &ix, void *stream)
 }
 
 int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64_t src_bytes, const uint64_t *src_off, const uint32_t *size, uint32_t n, int level,
-                      void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, bdp_dev_t *dup, const uint32_t *tord, double *flag_ms, bcv_dev_t *cov, double *cov_ms)
+                      void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, bdp_dev_t *dup, const uint32_t *tord, double *flag_ms, bcv_dev_t *cov, double *cov_ms,
+                      bst_dev_t *stats, double *stats_ms)
 {
 	hipStream_t st = (hipStream_t)stream;
 	if (n == 0) return BMH_OK;
@@ -276,6 +278,8 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 	}
 	// coverage reads the records in their final order with their final flags; the window's last record (host) sets its frontier
 	if (cov) RCK(bcv_window_device(cov, (const uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, n, src + src_off[n - 1], st, "sorted BAM", cov_ms));
+	// the statistics read the same records: one kernel, nothing waits for it here
+	if (stats) RCK(bst_window_device(stats, (const uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, n, st, stats_ms));
 	const uint8_t *d_members = nullptr; uint64_t mb = 0;
 	RCK(bmh_bgzf_deflate_device(ws, (const uint8_t *)d->sorted.p, total, level, st, &d_members, &mb));
 	// the index pass: the members' offsets are the compressor's scan (ws->moff [n_members + 1])
@@ -297,6 +301,7 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 	HIPCK(hipGetLastError());
 	if (dup && flag_ms) { float ms = 0; HIPCK(hipEventElapsedTime(&ms, d->ev_flag[0], d->ev_flag[1])); *flag_ms += ms; }
 	if (cov && cov_ms) RCK(bcv_window_ms(cov, cov_ms));
+	if (stats) RCK(bst_window_ms(stats, stats_ms, "sorted BAM"));        // (a refused record ends the run before the window's members reach the sink)
 	if (nh == 0 || nh > n) { bmh_set_error("sorted BAM: internal error: %u chunk heads among %u records", nh, n); return BMH_EINVAL; }
 	const size_t h0 = ix.heads.size();
 	ix.heads.resize(h0 + nh);
@@ -308,7 +313,7 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 
 // every run of the store -> the sorted file's record members (to the sink) and its index
 int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, uint64_t *dup_counts,
-                     const bdp_plan_t &P, double *dup_ms, double *opt_ms, bcv_dev_t *cov, double *cov_ms)
+                     const bdp_plan_t &P, double *dup_ms, double *opt_ms, bcv_dev_t *cov, double *cov_ms, bst_dev_t *stats, double *stats_ms)
 {
 	const bdp_optical_t *optical = P.optical(); const bool barcode = P.barcode() != nullptr;
 	uint64_t n = 0, bytes = 0;
@@ -360,7 +365,7 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint3
 				if (dup.p) tord[j] = (uint32_t)(R.tbase + R.tpl[i]);
 			}
 			// (the pinned buffer takes the members once the records are on the device: the compressor waits for the stream in between)
-			RCK(bsr_window_device(d, ws, d->h_buf, sb, src_off.data(), size.data(), m, level, stream, ix, sink, user, dup.p, dup.p ? tord.data() : nullptr, dup.p ? &flag_ms : nullptr, cov, cov_ms));
+			RCK(bsr_window_device(d, ws, d->h_buf, sb, src_off.data(), size.data(), m, level, stream, ix, sink, user, dup.p, dup.p ? tord.data() : nullptr, dup.p ? &flag_ms : nullptr, cov, cov_ms, stats, stats_ms));
 		}
 	}
 	if (dup_counts) {
@@ -440,12 +445,20 @@ extern "C" int bmh_bam_sort_device(const uint8_t *recs, uint64_t n_bytes, void *
 
 static int sorted_file_device(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
                               const bmh_sorted_file_opt_t &o, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts, const bdp_plan_t &P,
-                              const bmh_coverage_opt_t *cov_opt = nullptr, bmh_coverage_t *cov_out = nullptr)
+                              const bmh_coverage_opt_t *cov_opt = nullptr, bmh_coverage_t *cov_out = nullptr, const bmh_bam_stats_opt_t *stats_opt = nullptr, bmh_bam_stats_t *stats_out = nullptr)
 {
 	const int level = o.level; const uint32_t window = o.window;
 	const bdp_table_t *G = P.groups();
 	bcv_plan_t CP; bcv_dev_t *cov = nullptr;
 	struct cov_own_t { bcv_dev_t *p = nullptr; ~cov_own_t() { if (p) bcv_dev_free(p); } } cov_own;
+	bst_plan_t SP; bst_dev_t *stats = nullptr;
+	struct stats_own_t { bst_dev_t *p = nullptr; ~stats_own_t() { if (p) bst_dev_free(p); } } stats_own;
+	if (stats_out) {
+		memset(stats_out, 0, sizeof *stats_out);
+		bmh_bam_stats_opt_t so; bmh_bam_stats_opt_default(&so);
+		if (stats_opt) so = *stats_opt;
+		RCK(bst_plan_make(SP, so.insert_cap, n_contigs, fn));
+	}
 	if (cov_out) {
 		memset(cov_out, 0, sizeof *cov_out);
 		bmh_coverage_opt_t co; bmh_coverage_opt_default(&co);
@@ -485,10 +498,15 @@ static int sorted_file_device(const char *fn, const char *header_text, int n_con
 		if (!(cov = cov_own.p = bcv_dev_create())) return BMH_ENOMEM;
 		RCK(bcv_begin_device(cov, CP, stream));
 	}
+	if (stats_out) {
+		if (!(stats = stats_own.p = bst_dev_create())) return BMH_ENOMEM;
+		RCK(bst_begin_device(stats, SP, stream));
+	}
 	bmh_bam_ws_t *ws = bmh_bam_ws_create();
-	rc = bsr_merge_device(&d, ws, S, window, level, stream, ix, sink_string, &file, dup_counts, P, nullptr, nullptr, cov, nullptr);
+	rc = bsr_merge_device(&d, ws, S, window, level, stream, ix, sink_string, &file, dup_counts, P, nullptr, nullptr, cov, nullptr, stats, nullptr);
 	bmh_bam_ws_free(ws);
 	if (rc != BMH_OK) return rc;
+	if (stats) { bst_result_t SR; RCK(bst_finish_device(stats, stream, SR, fn)); RCK(bst_export(SP, SR, stats_out, fn)); }
 	if (cov) { bcv_result_t CR; RCK(bcv_finish_device(cov, stream, CR, fn, nullptr)); RCK(bcv_export(CP, CR, cov_out, fn)); }
 	if (G && P.lib_counts && off.size() > 1)
 		bdp_lib_tally_host(sorted.data(), soff.data(), (uint32_t)(off.size() - 1), dh.tpl.data(), dh.entries.data(), dh.entries.size(), G->n_lib, P.lib_counts);
@@ -525,4 +543,26 @@ extern "C" int bmh_bam_sorted_file_coverage_device(const char *header_text, int 
 	RCK(bsr_file_opt_check(opt, res, fn, o, P));
 	// (the coverage is exported before the file's bytes are allocated: a failed call holds neither)
 	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, stream, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P, cov_opt, cov);
+}
+
+// the sorted file and, from the same windows, its statistics (csrc/bam_stats_kernels.hip) and, with cov, its coverage: both see the flags opt->markdup sets
+extern "C" int bmh_bam_sorted_file_stats_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                                                const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, const bmh_bam_stats_opt_t *stats_opt, void *stream, uint8_t **bam,
+                                                uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res, bmh_coverage_t *cov, bmh_bam_stats_t *stats)
+{
+	const char *fn = "bmh_bam_sorted_file_stats_device";
+	if (bam) *bam = nullptr;                                         // (before anything can be refused: a caller who frees what a failed call left frees nothing)
+	if (index) *index = nullptr;
+	if (cov) memset(cov, 0, sizeof *cov);
+	if (!stats) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	memset(stats, 0, sizeof *stats);
+	bmh_sorted_file_opt_t o; bdp_plan_t P;
+	RCK(bsr_file_opt_check(opt, res, fn, o, P));
+	const int rc = sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, stream, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P,
+	                                  cov_opt, cov, stats_opt, stats);
+	if (rc != BMH_OK) {                                              // (whatever was exported before the failure goes back)
+		bmh_bam_stats_free(stats);
+		if (cov) { bmh_free(cov->n_reads); bmh_free(cov->cov_bases); bmh_free(cov->sum_depth); bmh_free(cov->max_depth); bmh_free(cov->sum_mapq); bmh_free(cov->hist); bmh_free(cov->bin_sum); memset(cov, 0, sizeof *cov); }
+	}
+	return rc;
 }

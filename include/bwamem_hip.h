@@ -1171,6 +1171,7 @@ typedef struct {
 	const bmh_markdup_opt_t *markdup; int32_t libraries;
 	const bmh_coverage_opt_t *coverage;
 	int32_t collate;
+	const struct bmh_bam_stats_opt *stats;                                /* read by bmh_bam_post_file_stats_* only (below) */
 } bmh_bam_post_opt_t;
 typedef struct { uint64_t records, templates, batches, spilled_runs, bins_changed, dup_flags_cleared; } bmh_bam_post_counts_t;
 typedef struct {
@@ -1200,6 +1201,57 @@ typedef struct {
 int bmh_bam_templates_device(const uint8_t *records, uint64_t n_bytes, const bmh_markdup_opt_t *opt, int32_t hash_bits, void *stream, bmh_bam_templates_t *out);
 int bmh_bam_templates_host(const uint8_t *records, uint64_t n_bytes, const bmh_markdup_opt_t *opt, int32_t hash_bits, bmh_bam_templates_t *out);
 void bmh_bam_templates_free(bmh_bam_templates_t *r);
+
+/* ---- Flag counts, contig counts, an alignment summary and insert sizes of sorted BAM, computed while the file is written (csrc/bam_stats_core.h,
+ * csrc/bam_stats_kernels.hip, csrc/bam_stats_host.cpp): what `samtools flagstat`, `samtools idxstats` and an insert-size summary would read the
+ * file again for.  Every word is an exact uint64 over the whole file and does not depend on the order of the records, on windows or on the form.
+ * flag [2][16]: `samtools flagstat`'s counts, column 0 the records without 0x200 and column 1 those with it, in the order total, primary, secondary,
+ * supplementary, duplicates, primary duplicates, mapped, primary mapped, paired, read1, read2, properly paired, with itself and mate mapped, singletons, mate on a
+ * different contig, that at mapq >= 5.  A record with 0x100 and 0x800 is secondary only; proper and singleton need 0x4 clear.
+ * contig_mapped / contig_unmapped [n_contigs], unplaced: `samtools idxstats`' counts over records of every kind -- refID c without and with 0x4, refID -1.
+ * summary [14], over primary records (neither 0x100 nor 0x800): reads, bases (l_seq), reads mapped, bases mapped (0x4 clear), mapped reads at mapq 0, the longest
+ * l_seq; and of the mapped ones, from the operations: bases aligned (M = X I), bases soft-clipped, insertion events and bases, deletion events and bases; from the
+ * tags: records with NM, and the sum of NM (the first NM of a record, of type c C s S i I).  mapq [256]: the mapped primary records by mapq.
+ * insert_hist [3][insert_cap + 1] (FR, RF, TANDEM), insert_min / insert_max [3]: Picard CollectInsertSizeMetrics' rule at its defaults, once per pair -- a record
+ * with 0x1 and 0x80, none of 0x4 0x8 0x100 0x800 0x400, refID == next_refID and tlen != 0 counts with the size |tlen|; TANDEM when 0x10 and 0x20 are equal, else a
+ * forward record is FR with tlen > 0 and a reverse record is FR with next_pos + 1 < pos + its reference length, RF otherwise.  Sizes from insert_cap (2 .. 65536;
+ * the default 65536) up share the last bin; the smallest and the largest size are exact (0 where an orientation holds no pair).
+ * Refused with BMH_EINVAL by the record's index: a refID outside -1 .. n_contigs - 1; of mapped primary records (no other record's operations or tags are read)
+ * tags that cannot be walked to the record's end, an NM of another type or below 0, the long-CIGAR placeholder.  The first such record is the one named.
+ * bmh_bam_stats_device / _host: a record stream in any order (whole records, else refused).  bmh_bam_stats_free releases the arrays (a failed call leaves them NULL).
+ * bmh_bam_sorted_file_stats_device / _host: bmh_bam_sorted_file_* and, from the same windows, the statistics -- with the 0x400 flags opt->markdup sets -- and, with
+ * cov not NULL, the coverage under cov_opt.  A failed call leaves *bam, *index and every array of cov and stats NULL.
+ * bmh_aligner_set_stats: the sorted runs that follow compute their statistics on the device, every window behind its flag step (opt NULL: off); refused unless the
+ * output format is BMH_OUT_BAM_SORTED, switched off by every bmh_aligner_set_output of another format.  Without it no run launches anything more.
+ * bmh_aligner_stats: the statistics of the last such run; bmh_aligner_stats_ms: the milliseconds its windows' kernels took on the device's stream and the windows.
+ * bmh_bam_post_file_stats_device / _host: bmh_bam_post_file_* and, with opt->stats set, the statistics of the file (stats is then required). */
+typedef struct bmh_bam_stats_opt { uint32_t insert_cap; } bmh_bam_stats_opt_t;
+void bmh_bam_stats_opt_default(bmh_bam_stats_opt_t *o);
+typedef struct bmh_bam_stats {
+	int32_t n_contigs; uint32_t insert_cap;
+	uint64_t *flag;                                                      /* [2][16] */
+	uint64_t *summary;                                                   /* [14] */
+	uint64_t *mapq;                                                      /* [256] */
+	uint64_t *contig_mapped, *contig_unmapped;                           /* [n_contigs] each */
+	uint64_t *insert_hist;                                               /* [3][insert_cap + 1] */
+	uint64_t unplaced, insert_min[3], insert_max[3];
+} bmh_bam_stats_t;
+void bmh_bam_stats_free(bmh_bam_stats_t *s);
+int bmh_bam_stats_device(const uint8_t *records, uint64_t n_bytes, int n_contigs, const bmh_bam_stats_opt_t *opt, void *stream, bmh_bam_stats_t *out);
+int bmh_bam_stats_host(const uint8_t *records, uint64_t n_bytes, int n_contigs, const bmh_bam_stats_opt_t *opt, bmh_bam_stats_t *out);
+int bmh_bam_sorted_file_stats_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
+                                     const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, const bmh_bam_stats_opt_t *stats_opt, void *stream, uint8_t **bam,
+                                     uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res, bmh_coverage_t *cov, bmh_bam_stats_t *stats);
+int bmh_bam_sorted_file_stats_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
+                                   const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, const bmh_bam_stats_opt_t *stats_opt, uint8_t **bam, uint64_t *bam_bytes,
+                                   uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res, bmh_coverage_t *cov, bmh_bam_stats_t *stats);
+int bmh_aligner_set_stats(bmh_aligner_t *a, const bmh_bam_stats_opt_t *opt);
+int bmh_aligner_stats(bmh_aligner_t *a, bmh_bam_stats_t *out);
+int bmh_aligner_stats_ms(bmh_aligner_t *a, double *out, uint64_t *windows);
+int bmh_bam_post_file_stats_device(const char *path, const bmh_bam_post_opt_t *opt, void *stream, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out,
+                                   bmh_markdup_counts_t *res, bmh_coverage_t *cov, bmh_bam_stats_t *stats);
+int bmh_bam_post_file_stats_host(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res,
+                                 bmh_coverage_t *cov, bmh_bam_stats_t *stats);
 
 #ifdef __cplusplus
 }

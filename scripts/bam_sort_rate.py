@@ -7,6 +7,12 @@ sorted file's size (the two copies land next to each other) and the merge's comp
 
     python scripts/bam_sort_rate.py [--runs 3] [--reads 1000000] [--genome-mbp 3100] [--out FILE] [--markdup [--groups | --optical N] [--parent-json FILE]]
                                     [--coverage [--coverage-bin N] [--sort-window W] [--parent-json FILE]]
+                                    [--stats [--sort-window W] [--parent-json FILE]]
+
+--stats: the statistics leg (profiles/bam_stats.json), at the coverage leg's size: the sorted in-memory row, the same row with duplicates marked, the row `sorted +
+marked + statistics` (reads_to_sorted_bam_in_memory_markdup_stats) -- with the statistics kernels alone as the library times them (bmh_aligner_stats_ms: events
+around every window's kernel), per run and per window, and their share of the final merge -- and, on the paired set, that row with coverage beside it.
+final_merge_ms of every sorted row is the merge in milliseconds: with and without the option side by side.  --parent-json FILE: as under --coverage.
 
 --coverage: the coverage leg (profiles/bam_coverage.json): the sorted in-memory row, the same row with duplicates marked, and the row `sorted + marked + coverage`
 (reads_to_sorted_bam_in_memory_markdup_coverage) -- with the depth steps alone as the library times them (bmh_aligner_coverage_ms: events around every window's
@@ -66,11 +72,14 @@ def main():
     ap.add_argument("--coverage", action="store_true")
     ap.add_argument("--coverage-bin", type=int, default=1000)
     ap.add_argument("--sort-window", type=int, default=0)
+    ap.add_argument("--stats", action="store_true")
     a = ap.parse_args()
     if a.optical is not None and (not a.markdup or a.groups or not 0 <= a.optical <= 0x7fffffff):
         ap.error("--optical N (0 .. 2^31 - 1) goes with --markdup, without --groups")
     if a.coverage and (a.markdup or a.coverage_bin < 1 or a.sort_window < 0):
         ap.error("--coverage goes without --markdup; --coverage-bin N >= 1, --sort-window W >= 0")
+    if a.stats and (a.markdup or a.coverage or a.sort_window < 0):
+        ap.error("--stats goes without --markdup and --coverage; --sort-window W >= 0")
     dev = torch.device("cuda:0")
     L = B.load_library()
     n_genome = int(a.genome_mbp * 1e6)
@@ -110,7 +119,7 @@ def main():
     path = os.path.join(tmp, "se.fa")
     write_fasta(path, names, asc)
     ppath = os.path.join(tmp, "pe.fa")
-    if a.markdup or a.coverage:                               # FR pairs, n reads per distinct batch, each batch twice; mates share a name
+    if a.markdup or a.coverage or a.stats:                    # FR pairs, n reads per distinct batch, each batch twice; mates share a name
         p1 = B.synth.make_pairs(g, n // 2, rl, seed=7, holes=holes)[0]; p2 = B.synth.make_pairs(g, n // 2, rl, seed=1007, holes=holes)[0]
         pasc = B.synth.codes_to_ascii(np.concatenate([p1.reshape(-1), p2.reshape(-1), p1.reshape(-1), p2.reshape(-1)]))
         pn = np.frombuffer("".join(np.char.add(">p", np.char.zfill((np.arange(n4) // 2).astype(str), w)).tolist()).encode(), np.uint8).reshape(n4, w + 2)
@@ -118,7 +127,7 @@ def main():
     nat = NativeAligner(dindex, pac_h, n_genome, contigs, None, co, ExtParams.default(), po, pe_o)
     result = {"genome_mbp": a.genome_mbp, "reads_per_run": n4, "setup_s": round(time.time() - t0, 1), "runs": a.runs, "host_threads": nth, "rows": {}}
 
-    def run(fmt, spill=False, keep=None, markdup=False, paired=False, groups=None, files=False, optical=None, coverage=None):
+    def run(fmt, spill=False, keep=None, markdup=False, paired=False, groups=None, files=False, optical=None, coverage=None, qc=None):
         src = ppath if paired else path
         nat.set_output(fmt, 1)
         if fmt == "bam_sorted":
@@ -126,9 +135,11 @@ def main():
             nat.set_markdup(markdup)
             if markdup:
                 nat.set_markdup_optical(optical)
-            if a.coverage:                                        # (the other legs also run against a parent commit's library, which has no such call)
+            if a.coverage or a.stats:                             # (the other legs also run against a parent commit's library, which has no such call)
                 nat.set_coverage(coverage)
-        opt_ms, cov_ms = [], []
+            if a.stats:
+                nat.set_stats(qc)
+        opt_ms, cov_ms, st_ms = [], [], []
         nbytes = [0]
 
         def sink(mv):
@@ -153,6 +164,8 @@ def main():
                     opt_ms.append(nat.markdup_optical_ms())
                 if coverage is not None:
                     cov_ms.append(nat.coverage_ms(windows=True))
+                if qc is not None:
+                    st_ms.append(nat.stats_ms(windows=True))
         row = stats(secs, n4, 1e6)
         row["unit"] = "Mreads/s"; row["bytes_out_per_read"] = round(nbytes[0] / n4, 1)
         if fmt == "bam_sorted":
@@ -169,6 +182,15 @@ def main():
                                                "share_of_final_merge_pct": round(100 * sorted(ms)[len(ms) // 2] / (1e3 * sorted(merge)[len(merge) // 2]), 2)}
                 row["coverage"] = {"tile": int(coverage.tile) or 4096, "bin": int(coverage.bin), "bins": int(len(cov["bin_sum"])), "n_reads": int(cov["n_reads"].sum()),
                                    "cov_bases": int(cov["cov_bases"].sum()), "sum_depth": int(cov["sum_depth"].sum()), "max_depth": int(cov["max_depth"].max())}
+            if qc is not None:
+                ms = [t for t, _w in st_ms]
+                got = nat.stats()
+                row["stats_steps_alone"] = {"unit": "ms on the stream per run (events around every window's statistics kernel)",
+                                            "median": round(sorted(ms)[len(ms) // 2], 3), "runs": [round(t, 3) for t in ms], "windows": [w for _t, w in st_ms],
+                                            "ms_per_window": [round(t / max(w, 1), 3) for t, w in st_ms],
+                                            "share_of_final_merge_pct": round(100 * sorted(ms)[len(ms) // 2] / (1e3 * sorted(merge)[len(merge) // 2]), 2)}
+                row["stats"] = {"insert_cap": int(qc.insert_cap), "total": int(got["flag"][:, 0].sum()), "duplicates": int(got["flag"][:, 4].sum()), "mapped": int(got["flag"][:, 6].sum()),
+                                "pairs_counted": [int(v) for v in got["insert_hist"].sum(axis=1)], "largest_insert_bin": int(got["insert_hist"].max()), "edit_distance": int(got["summary"][13])}
             if markdup:
                 row["counts"] = nat.markdup_counts()
                 tpl = row["counts"]["templates"]
@@ -185,6 +207,34 @@ def main():
                     row["library_counts"] = [nat.markdup_library_counts(k) for k in range(1 + max(g[1] for g in groups))]
         return row
     keep = []
+    if a.stats:
+        from bwamem_hip.lib import coverage_opt, stats_opt
+        result["sort_window"] = a.sort_window
+        for pre, pk in (("", {}), ("paired_", dict(paired=True))):
+            result["rows"][pre + "reads_to_sorted_bam_in_memory"] = run("bam_sorted", **pk)
+            result["rows"][pre + "reads_to_sorted_bam_in_memory_markdup"] = run("bam_sorted", markdup=True, **pk)
+            result["rows"][pre + "reads_to_sorted_bam_in_memory_markdup_stats"] = run("bam_sorted", markdup=True, qc=stats_opt(), **pk)
+        result["rows"]["paired_reads_to_sorted_bam_in_memory_markdup_coverage_stats"] = run("bam_sorted", markdup=True, coverage=coverage_opt(), qc=stats_opt(), paired=True)
+        nat.set_coverage(None); nat.set_stats(None)
+        nat.set_output("sam", 1)
+        if a.parent_json:
+            with open(a.parent_json) as f:
+                parent = json.load(f)
+            result["parent_rows"] = {k: v for k, v in parent["rows"].items() if k in result["rows"]}
+            result["parent_genome_mbp"], result["parent_reads_per_run"] = parent.get("genome_mbp"), parent.get("reads_per_run")
+            result["option_off_vs_parent"] = {}
+            for k, pr in result["parent_rows"].items():
+                tr = result["rows"][k]
+                diff = 100 * abs(tr["median"] - pr["median"]) / pr["median"]
+                result["option_off_vs_parent"][k] = {"difference_pct": round(diff, 1), "larger_spread_pct": max(tr["spread_pct"], pr["spread_pct"]), "within_spread": diff <= max(tr["spread_pct"], pr["spread_pct"])}
+        result["not_measured"] = ("real data with deep duplicate stacks (every read occurs twice here), the histogram's atomics under an amplicon library, where nearly every pair has one "
+                                  "size, spilled runs, an insert_cap other than the default")
+        os.remove(ppath); os.remove(path); os.rmdir(tmp)
+        out = a.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bam_stats.json")
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+        print(json.dumps(result))
+        return
     if a.coverage:
         from bwamem_hip.lib import coverage_opt
         result["sort_window"] = a.sort_window
