@@ -330,7 +330,7 @@ __global__ void __launch_bounds__(64) cigar_kernel(cigar_args_t A)
 		}
 		md_putw(md, u, lane);
 		if (md.p && lane == 0) md.p[md.len < md.cap ? md.len : md.cap - 1] = 0;
-		if (md.len + 1 > md.cap && md.cap) flags |= 8;
+		if (md.len + 1 > md.cap && md.cap && !(flags & 1)) flags |= 8;      // (along operations that did not fit there is no MD string to measure)
 		// mem_reg2aln tail: position, squeeze of a leading / trailing deletion, soft clips
 		const long long xx = rb < A.l_pac ? rb : re - 1;
 		const int is_rev = xx >= A.l_pac;
@@ -693,7 +693,7 @@ __global__ void __launch_bounds__(256) cigar_finish_kernel(cigar_args_t A)
 	for (int o = 8; o; o >>= 1) sc_part += __shfl_xor(sc_part, o);
 	if (!(lead && !rej)) return;
 	if (mdp) mdp[md_len < md_cap ? md_len : md_cap - 1] = 0;
-	if (md_len + 1 > md_cap && md_cap) flags |= 8;
+	if (md_len + 1 > md_cap && md_cap && !(flags & 1)) flags |= 8;      // (along operations that did not fit there is no MD string to measure)
 	const int score = J.kind == CG_TRIVIAL ? sc_part : J.score;
 	const long long xx = g.rb < A.l_pac ? g.rb : g.re - 1;
 	const int is_rev = xx >= A.l_pac;

@@ -736,7 +736,8 @@ int bmh_chain_extend_merge_timing(const bmh_chain_ws_t *ws, float ms[3], uint64_
  * forward strand of the concatenated reference), is_rev, n_cigar, NM, global score, MD length, flags (1 = more than
  * max_cigar-2 ops, 2 = interval rejected by bwa_gen_cigar2, 4 = too large: a side of 2^20 bases or more, or a region beyond 704
  * bases whose band -- max(4 opt_w, |rlen - qlen| + 3) -- needs a direction matrix (min(qlen, 2 band + 1) x rlen bytes) over 1 GiB, never
- * the case for sides up to 32 768 bases; 8 = MD longer than md_cap)}, d_md[md_cap]
+ * the case for sides up to 32 768 bases; 8 = MD longer than md_cap -- reported where the operations fit: with flag 1 NM and MD
+ * follow the operations that were kept and mean nothing, the caller redoes the job with larger slots)}, d_md[md_cap]
  * (NUL-terminated; d_md may be NULL).  The index must carry its pac.  Synchronises the stream once (sizes). */
 int bmh_cigar_batch(const bmh_index_t *idx, const uint8_t *d_reads, const uint32_t *d_offs, const uint32_t *d_lens,
                     const int32_t *d_regs, int reg_stride, const uint32_t *d_sel, uint32_t n, const bmh_ext_params_t *p, int opt_w,

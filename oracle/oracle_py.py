@@ -278,6 +278,21 @@ class RefTail:
         self.lib = L = C.CDLL(self.PATH, mode=os.RTLD_LAZY)
         L.ref_tail_run.restype = C.c_int
         L.ref_tail_run.argtypes = [_i32p, C.POINTER(C.c_float), C.c_int64, _u8p, C.c_int, _u8p, C.c_int64, C.c_float, C.c_int, _i32p, _i32p, _u8p, _i32p]
+        if hasattr(L, "ref_tail_reg2aln"):
+            L.ref_tail_reg2aln.restype = C.c_int
+            L.ref_tail_reg2aln.argtypes = [_i32p, C.c_int64, _u8p, C.c_int, C.c_char_p, _i32p, C.c_int64, C.c_int64, _i32p, _u32p, C.c_int, C.c_char_p, C.c_int]
+
+    def reg2aln(self, scoring, opt_w: int, l_pac: int, pac: np.ndarray, read: bytes, qb: int, qe: int, rb: int, re: int, truesc: int, reg_w: int,
+                cap: int = 4096, md_cap: int = 8192) -> dict:
+        """the reference's mem_reg2aln on one region (one contig of l_pac bases, rid 0, secondary -1).  scoring = (a, b, o_del, e_del, o_ins, e_ins); read: the
+        ASCII letters.  -> dict(pos, is_rev, cigar, NM, MD); the reference does not return the global score.  Only for regions bwa_gen_cigar2 accepts."""
+        assert qe > qb and re > rb and not (rb < l_pac < re)
+        oi = np.array([*scoring, opt_w], np.int32); reg = np.array([qb, qe, truesc, reg_w], np.int32)
+        out = np.zeros(6, np.int32); cg = np.zeros(cap, np.uint32); md = C.create_string_buffer(md_cap)
+        rc = self.lib.ref_tail_reg2aln(_ptr(oi, _i32p), int(l_pac), _ptr(np.ascontiguousarray(pac, dtype=np.uint8), _u8p), len(read), bytes(read), _ptr(reg, _i32p),
+                                       int(rb), int(re), _ptr(out, _i32p), _ptr(cg, _u32p), cap, md, md_cap)
+        assert rc == 0, "ref_tail_reg2aln: CIGAR or MD longer than the buffers"
+        return dict(pos=int(np.uint32(out[0])) | int(out[1]) << 32, is_rev=int(out[2]), cigar=cg[: int(out[3])].copy(), NM=int(out[4]), MD=md.value.decode())
 
     def run(self, opt_i, opt_f, l_pac: int, pac: np.ndarray, query: np.ndarray, read_id: int, frac_rep: float, regs8: np.ndarray, rid: np.ndarray,
             is_alt: "np.ndarray | None" = None) -> np.ndarray:

@@ -7,10 +7,11 @@
  * the way mem_align1_core leaves them when it hands them to the tail (src/bwamem.c:2297-2325: truesc = score, w = opt->w, the
  * sequence and is_alt of every region, frac_rep of the read), runs the three functions and writes the regions back as records
  * of 16 ints.  It pins bmh_finalize_regs (csrc/regs_post.cpp) to the reference on inputs natural data does not produce: ties
- * of every sort key, collisions of the tie-break hash, long tandem windows (tests/test_regs_cases.py).
+ * of every sort key, collisions of the tie-break hash, long tandem windows (tests/test_regs_cases.py).  A second entry point,
+ * ref_tail_reg2aln, runs the reference's mem_reg2aln on one region (tests/cigar_cases.py, tests/golden/make_cigar_golden.py).
  *
  * The reference reads the genome through bns->l_pac and pac only on this path (bwa_gen_cigar2 -> bns_get_seq), so the
- * bntseq_t is one in memory with nothing but l_pac.  bwamem.c names five data globals that fastmap.c defines; they are
+ * bntseq_t is one in memory with nothing but l_pac (ref_tail_reg2aln adds one contig: mem_reg2aln looks the position up).  bwamem.c names five data globals that fastmap.c defines; they are
  * defined here (never read on this path).  The GASAL entry points stay unresolved (the library is loaded lazily) and are
  * never called.
  */
@@ -79,4 +80,44 @@ extern "C" int ref_tail_run(const int *opt_i, const float *opt_f, int64_t l_pac,
 	}
 	free(q); free(a); free(opt);
 	return m;
+}
+
+/*
+ * The reference's unchanged mem_reg2aln (src/bwamem.c:2344-2438: band inference, the retry loop, bwa_gen_cigar2 with the strand
+ * flip, NM and MD, the squeeze of a leading / trailing deletion, the clips) on one region of one read.  It pins oracle_reg2aln and
+ * csrc/cigar_kernels.hip on the hand-made regions of tests/cigar_cases.py.
+ *
+ * opt_i = {a, b, o_del, e_del, o_ins, e_ins, w}; the genome is one contig of l_pac bases; read: the letters as they stand in the
+ * FASTQ record (mem_reg2aln converts them); reg = {qb, qe, truesc, w} and [rb, re) of a mem_alnreg_t with rid 0, secondary -1 and
+ * score = truesc.  The region must be one bwa_gen_cigar2 accepts (not empty, not bridging the strands): for the others the
+ * reference has no CIGAR to return.
+ * out = {pos_lo, pos_hi, is_rev, n_cigar, NM, l_MD}; cigar (capacity cap) and md (capacity md_cap, NUL terminated) receive what
+ * fits.  Returns 0, or -1 where a capacity was too small.
+ */
+extern "C" int ref_tail_reg2aln(const int *opt_i, int64_t l_pac, const uint8_t *pac, int l_query, const char *read, const int32_t *reg,
+                                int64_t rb, int64_t re, int32_t *out, uint32_t *cigar, int cap, char *md, int md_cap)
+{
+	mem_opt_t *opt = mem_opt_init();
+	opt->a = opt_i[0]; opt->b = opt_i[1]; opt->o_del = opt_i[2]; opt->e_del = opt_i[3]; opt->o_ins = opt_i[4]; opt->e_ins = opt_i[5];
+	opt->w = opt_i[6];
+	bwa_fill_scmat(opt->a, opt->b, opt->mat);
+	bntann1_t ann;
+	memset(&ann, 0, sizeof(ann));
+	ann.offset = 0; ann.len = (int32_t)l_pac;
+	bntseq_t bns;
+	memset(&bns, 0, sizeof(bns));
+	bns.l_pac = l_pac; bns.n_seqs = 1; bns.anns = &ann;
+	mem_alnreg_t ar;
+	memset(&ar, 0, sizeof(ar));
+	ar.qb = reg[0]; ar.qe = reg[1]; ar.score = ar.truesc = reg[2]; ar.w = reg[3];
+	ar.rb = rb; ar.re = re; ar.rid = 0; ar.secondary = ar.secondary_all = -1;
+	mem_aln_t a = mem_reg2aln(opt, &bns, pac, l_query, read, &ar);
+	const char *m = (const char *)(a.cigar + a.n_cigar);
+	const int l_md = (int)strlen(m);
+	out[0] = (int32_t)(uint32_t)a.pos; out[1] = (int32_t)(a.pos >> 32); out[2] = a.is_rev; out[3] = a.n_cigar; out[4] = (int32_t)a.NM; out[5] = l_md;
+	for (int i = 0; i < a.n_cigar && i < cap; ++i) cigar[i] = a.cigar[i];
+	if (md_cap > 0) { const int n = l_md < md_cap - 1 ? l_md : md_cap - 1; memcpy(md, m, n); md[n] = 0; }
+	const int rc = (a.n_cigar > cap || l_md + 1 > md_cap) ? -1 : 0;
+	free(a.cigar); free(opt);
+	return rc;
 }
