@@ -22,7 +22,7 @@ def lib_path() -> str:
 # every symbol include/bwamem_hip.h and include/seed_gen.h declare
 EXPORTED_SYMBOLS = [
     "bmh_last_error", "bmh_device_count", "bmh_set_device", "bmh_index_upload", "bmh_index_from_device",
-    "bmh_index_free", "bmh_index_kbits_info", "bmh_index_probe", "bmh_index_replicate", "bmh_rccl_where", "bmh_rccl_unique_id", "bmh_rccl_comm_init_rank", "bmh_rccl_comm_destroy", "bmh_index_broadcast_rccl", "bmh_index_replicate_all", "bmh_shard_range", "bmh_index_densify_sa", "bmh_index_build", "bmh_seed_ws_create", "bmh_seed_ws_free", "bmh_seed_batch", "bmh_seed_last_timing", "bmh_reseed_opt_default", "bmh_seed_batch_reseed", "bmh_aligner_set_reseed",
+    "bmh_index_free", "bmh_index_kbits_info", "bmh_index_probe", "bmh_index_replicate", "bmh_rccl_where", "bmh_rccl_unique_id", "bmh_rccl_comm_init_rank", "bmh_rccl_comm_destroy", "bmh_index_broadcast_rccl", "bmh_index_replicate_all", "bmh_shard_range", "bmh_index_densify_sa", "bmh_index_build", "bmh_seed_ws_create", "bmh_seed_ws_free", "bmh_seed_batch", "bmh_seed_last_timing", "bmh_reseed_opt_default", "bmh_seed_batch_reseed", "bmh_reseed_last_counts", "bmh_aligner_set_reseed",
     "bmh_host_pin", "bmh_host_unpin", "bmh_extend_batch", "bmh_extend_batch_long", "bmh_extend_last_ms", "bmh_extend_last_unsupported", "bmh_extend_last_class_sizes", "bmh_extend_set_packed", "bmh_tune_set", "bmh_wtrace_start", "bmh_wtrace_stop", "bmh_wtrace_kept", "bmh_extend_release", "bmh_finalize_release", "bmh_matesw_release", "bmh_calib_gather", "bmh_calib_valu", "bmh_calib_valu_placed", "bmh_calib_last_clock",
     "bmh_jobs_frac_rep", "bmh_post_opt_default", "bmh_finalize_regs", "bmh_finalize_regs_device", "bmh_finalize_regs_device_last_ms", "bmh_finalize_regs_device_last_classes", "bmh_sam_need_cigar", "bmh_format_sam", "bmh_free",
     "bmh_pe_opt_default", "bmh_finalize_pairs", "bmh_finalize_pairs_dev", "bmh_dedup_regs_device", "bmh_finalize_pairs_deduped", "bmh_rescue_check_counts", "bmh_sam_need_cigar_pe", "bmh_format_sam_pe",
@@ -225,6 +225,16 @@ def reads_last_counts() -> dict:
     L.bmh_reads_last_inflate_counts(inf)
     return dict(device_windows=int(out[0]), host_windows=int(out[1]), text_bytes=int(out[2]), records=int(out[3]),
                 device_inflate_members=int(inf[0]), host_inflate_members=int(inf[1]))
+
+
+def reseed_last_counts() -> dict:
+    """bmh_reseed_last_counts: the path the calling thread's last bmh_seed_batch_reseed took -- round-2 tasks, tasks that overflowed the first launch's
+    column (knob RESEED_CAP), seed groups of rounds 1, 2 and 3, rank steps of round 2 (both launches) and of round 3"""
+    out = (C.c_uint64 * 7)()
+    L = load_library()
+    if L.bmh_reseed_last_counts(out) != 0:
+        raise RuntimeError("bmh_reseed_last_counts: " + _err(L))
+    return dict(tasks=int(out[0]), overflowed=int(out[1]), rounds=(int(out[2]), int(out[3]), int(out[4])), steps=(int(out[5]), int(out[6])))
 
 
 # ---- BGZF members inflated on the device (csrc/inflate_kernels.hip) or by the same decoder on the host
@@ -1753,6 +1763,8 @@ def load_library() -> C.CDLL:
     L.bmh_seed_batch_reseed.restype = C.c_int
     L.bmh_seed_batch_reseed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
                                         C.POINTER(ReseedOpt), C.c_void_p, C.POINTER(SeedsT)]
+    L.bmh_reseed_last_counts.restype = C.c_int
+    L.bmh_reseed_last_counts.argtypes = [C.POINTER(C.c_uint64)]
     L.bmh_aligner_set_reseed.restype = C.c_int
     L.bmh_aligner_set_reseed.argtypes = [C.c_void_p, C.POINTER(ReseedOpt)]
     L.bmh_extend_batch.restype = C.c_int

@@ -9,10 +9,12 @@
 //   select   scan over the first round's results: length >= split_len, occurrences <= split_width -> one task
 //            {read, (begin + end) >> 1, min_intv = occurrences + 1} (compacted by the scan's offsets)
 //   round 2  one lane per task: bwt_smem1a(x, min_intv, max_intv = 0) (src/bwt.c:483-556), one rank pair per loop iteration so the
-//            lanes stay convergent on the gathers.  The forward list lives in a private HBM column of RS2_CAP entries and the
-//            backward rounds compact it in place (curr is prev minus some entries, in the same order); the SMEMs go to a second
-//            column (never more of them than forward entries).  A task whose forward list does not fit is listed and run again in
-//            a second launch whose columns hold max_len + 1 entries (the forward list has at most len - x), so nothing is cut short.
+//            lanes stay convergent on the gathers.  The forward list lives in a private HBM column of RESEED_CAP entries (a knob,
+//            32) and the backward rounds compact it in place (curr is prev minus some entries, in the same order); the SMEMs go to
+//            a second column (never more of them than forward entries).  A task whose forward list does not fit is listed and run
+//            again in a second launch whose columns hold max_len + 1 entries (the forward list has at most len - x), so nothing is
+//            cut short.  A lane walks its task alone, as the reference does: a 65 535-base homopolymer read is one task of some
+//            5e8 sequential rank steps, so the case table (tests/reseed_cases.py) keeps every task below 100 000 of them.
 //   round 3  one lane per read: the sequential bwt_seed_strategy1 scan (src/bwt.c:568-590) with its N handling, one forward extension
 //            per iteration; the seeds are at least min_seed_len + 1 long and disjoint, so a read has at most len / (k + 1) of them:
 //            a per-read column of that size, placed by a scan of the lengths.  Lanes of equal-length reads run equal iteration counts
@@ -28,8 +30,6 @@
 #include "devmem.h"
 #include "fmd_dev.h"
 #include "seed_dev.h"
-
-#define RS2_CAP 32u            // forward entries per round-2 task in the first launch (~17 on a 6 Gbase text; the rest runs again, larger)
 
 struct rs_task_t { uint32_t read, x, m, pad; };
 
@@ -86,7 +86,8 @@ enum { R2_FWD = 0, R2_BWD, R2_DONE };
 __global__ void __launch_bounds__(256) reseed_r2_kernel(fmd_dev_t f, read_view_t rv, const uint32_t *__restrict__ lens, int min_seed_len,
                                                         const rs_task_t *__restrict__ tasks, const uint32_t *__restrict__ ids, uint32_t n, uint32_t cap,
                                                         uint4 *__restrict__ list, uint4 *__restrict__ out, uint32_t *__restrict__ n_out,
-                                                        uint32_t *__restrict__ ovf_ids, unsigned long long *__restrict__ counters)
+                                                        uint32_t *__restrict__ ovf_ids, unsigned long long *__restrict__ counters,
+                                                        unsigned long long *__restrict__ n_steps)
 {
 	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
 	const bool live = t < n;
@@ -100,6 +101,7 @@ __global__ void __launch_bounds__(256) reseed_r2_kernel(fmd_dev_t f, read_view_t
 	int st = R2_DONE;
 	uint64_t k = 0, l = 0, s = 0;
 	int i = 0, end = 0, nl = 0;
+	uint32_t steps = 0;                      // rank pairs of this lane (bmh_reseed_last_counts)
 	bool ovf = false;
 	if (live) {
 		const int b = read_base(rv, r, x);
@@ -119,7 +121,7 @@ __global__ void __launch_bounds__(256) reseed_r2_kernel(fmd_dev_t f, read_view_t
 				if (b > 3) { push = true; stop = true; }                    // an ambiguous base ends the extension
 				else {
 					uint64_t ak[4], al[4], as[4];
-					fmd_forward_ext(f, k, l, s, ak, al, as);
+					fmd_forward_ext(f, k, l, s, ak, al, as); ++steps;
 					const int cb = 3 - b;
 					ns = sel4(cb, as[0], as[1], as[2], as[3]); nk = sel4(cb, ak[0], ak[1], ak[2], ak[3]); nlv = sel4(cb, al[0], al[1], al[2], al[3]);
 					if (ns != s) { push = true; stop = ns < m; }            // change of the interval size; too small to extend further
@@ -152,7 +154,7 @@ __global__ void __launch_bounds__(256) reseed_r2_kernel(fmd_dev_t f, read_view_t
 				uint64_t nk = 0, ns = 0;
 				if (c >= 0) {
 					uint64_t ol, ou;
-					fmd_occ1_pair<false>(f, pk - 1, pk + ps - 1, c, ol, ou);
+					fmd_occ1_pair<false>(f, pk - 1, pk + ps - 1, c, ol, ou); ++steps;
 					nk = fmd_L2(f, c) + ol + 1; ns = ou - ol;
 				}
 				if (c < 0 || ns < m) {                                       // keep the hit unless a longer one of this round is still growing
@@ -173,6 +175,7 @@ __global__ void __launch_bounds__(256) reseed_r2_kernel(fmd_dev_t f, read_view_t
 		n_out[t] = (uint32_t)nout;
 	}
 	rs_wave_add(counters, (uint32_t)nout);
+	rs_wave_add(n_steps, steps);
 }
 
 // ---------------------------------------------------------------- round 3: bwt_seed_strategy1 along the read
@@ -181,7 +184,7 @@ enum { R3_OPEN = 0, R3_EXT, R3_DONE };
 
 __global__ void __launch_bounds__(256) reseed_r3_kernel(fmd_dev_t f, read_view_t rv, const uint32_t *__restrict__ lens, int min_seed_len, uint64_t max_intv,
                                                         const uint64_t *__restrict__ off3, uint4 *__restrict__ out, uint32_t *__restrict__ n_out,
-                                                        unsigned long long *__restrict__ counter)
+                                                        unsigned long long *__restrict__ counter, unsigned long long *__restrict__ n_steps)
 {
 	const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
 	const bool live = r < rv.n_reads;
@@ -189,6 +192,7 @@ __global__ void __launch_bounds__(256) reseed_r3_kernel(fmd_dev_t f, read_view_t
 	const size_t base = live ? (size_t)off3[r] : 0;
 	int st = live && len > 0 ? R3_OPEN : R3_DONE;
 	int x = 0, i = 0, nout = 0;
+	uint32_t steps = 0;
 	uint64_t k = 0, l = 0, s = 0;
 	while (__any(st != R3_DONE)) {
 		if (st == R3_OPEN) {
@@ -208,7 +212,7 @@ __global__ void __launch_bounds__(256) reseed_r3_kernel(fmd_dev_t f, read_view_t
 					else ++i;
 				} else {
 					uint64_t ak[4], al[4], as[4];
-					fmd_forward_ext(f, k, l, s, ak, al, as);
+					fmd_forward_ext(f, k, l, s, ak, al, as); ++steps;
 					const int cb = 3 - b;
 					const uint64_t ns = sel4(cb, as[0], as[1], as[2], as[3]), nk = sel4(cb, ak[0], ak[1], ak[2], ak[3]), nlv = sel4(cb, al[0], al[1], al[2], al[3]);
 					if (ns < max_intv && i - x >= min_seed_len) {
@@ -221,6 +225,7 @@ __global__ void __launch_bounds__(256) reseed_r3_kernel(fmd_dev_t f, read_view_t
 	}
 	if (live) n_out[r] = (uint32_t)nout;
 	rs_wave_add(counter, (uint32_t)nout);
+	rs_wave_add(n_steps, steps);
 }
 
 // ---------------------------------------------------------------- merge
@@ -290,9 +295,21 @@ __global__ void __launch_bounds__(256) reseed_gather_kernel(const uint64_t *__re
 struct reseed_state_t {
 	dev_buf<uint8_t> tsk_off, tasks, list, out2, n2, ovf, list_b, out_b, n2b, off3, out3, n3, keys, keys2, vals, vals2, mk, ms, ra, rk, rocc, roff, tmp;
 	dev_buf<unsigned long long> ctr;        // [0] round-2 groups [1] overflowing tasks [2] round-3 groups [3] groups of the second round-2 launch [4] merge cursor
+	                                        // [5] rank steps of round 2, both launches [6] of round 3
 };
 
 void reseed_state_free(reseed_state_t *R) { delete R; }
+
+// round-2 tasks, tasks that overflowed, groups of rounds 1, 2, 3, rank steps of rounds 2 and 3 of the thread's last bmh_seed_batch_reseed (tests: which
+// path a batch took, and how much work it was)
+static thread_local uint64_t g_rs_last[7] = {0, 0, 0, 0, 0, 0, 0};
+void reseed_counts_reset(void) { memset(g_rs_last, 0, sizeof(g_rs_last)); }
+extern "C" int bmh_reseed_last_counts(uint64_t *out)
+{
+	if (!out) { bmh_set_error("bmh_reseed_last_counts: null argument"); return BMH_EINVAL; }
+	memcpy(out, g_rs_last, sizeof(g_rs_last));
+	return BMH_OK;
+}
 
 static inline unsigned rs_nblk(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -308,6 +325,10 @@ int reseed_merge(reseed_state_t **Rp, const reseed_in_t &in, hipStream_t st, res
 	const int split_len = (int)(in.min_seed_len * in.opt.split_factor + .499);      // as mem_collect_intv: int * float + .499
 	const uint64_t n_cands = in.n_cands, n_reads = in.n_reads;
 	const bool r3 = in.opt.max_mem_intv > 0;
+	// forward entries per round-2 task in the first launch (~17 on a 6 Gbase text; the rest runs again, larger).  No list is longer than max_len, so a
+	// larger column holds nothing more
+	const int cap_knob = bmh_tune("RESEED_CAP", 32);
+	const uint32_t cap_a = cap_knob < 1 ? 1u : ((uint32_t)cap_knob > in.max_len + 1 ? in.max_len + 1 : (uint32_t)cap_knob);
 	HIPCK(hipMemsetAsync(R.ctr.p, 0, 64, st));
 
 	// ---- select the round-2 tasks (scan of the flags) and size the round-3 columns (scan of the bounds): one wait for both totals
@@ -332,19 +353,19 @@ int reseed_merge(reseed_state_t **Rp, const reseed_in_t &in, hipStream_t st, res
 	// ---- round 2 (first launch) and round 3
 	if (n_tasks) {
 		RCK(R.tasks.need(sizeof(rs_task_t) * (size_t)n_tasks));
-		RCK(R.list.need(16 * (size_t)n_tasks * RS2_CAP)); RCK(R.out2.need(16 * (size_t)n_tasks * RS2_CAP));
+		RCK(R.list.need(16 * (size_t)n_tasks * cap_a)); RCK(R.out2.need(16 * (size_t)n_tasks * cap_a));
 		RCK(R.n2.need(4 * (size_t)n_tasks)); RCK(R.ovf.need(4 * (size_t)n_tasks));
 		reseed_task_kernel<<<rs_nblk(n_cands), 256, 0, st>>>(in.res_a, in.occ, n_cands, split_len, in.opt.split_width, R.tsk_off.as<uint32_t>(), R.tasks.as<rs_task_t>());
-		reseed_r2_kernel<<<rs_nblk(n_tasks), 256, 0, st>>>(in.f, in.rv, in.lens, k, R.tasks.as<rs_task_t>(), nullptr, n_tasks, RS2_CAP,
-		                                                   R.list.as<uint4>(), R.out2.as<uint4>(), R.n2.as<uint32_t>(), R.ovf.as<uint32_t>(), R.ctr.p);
+		reseed_r2_kernel<<<rs_nblk(n_tasks), 256, 0, st>>>(in.f, in.rv, in.lens, k, R.tasks.as<rs_task_t>(), nullptr, n_tasks, cap_a,
+		                                                   R.list.as<uint4>(), R.out2.as<uint4>(), R.n2.as<uint32_t>(), R.ovf.as<uint32_t>(), R.ctr.p, R.ctr.p + 5);
 	}
 	if (r3) {
 		RCK(R.out3.need(16 * (n_slots3 + 1))); RCK(R.n3.need(4 * (n_reads + 1)));
 		reseed_r3_kernel<<<rs_nblk(n_reads), 256, 0, st>>>(in.f, in.rv, in.lens, k, (uint64_t)in.opt.max_mem_intv, R.off3.as<uint64_t>(),
-		                                                   R.out3.as<uint4>(), R.n3.as<uint32_t>(), R.ctr.p + 2);
+		                                                   R.out3.as<uint4>(), R.n3.as<uint32_t>(), R.ctr.p + 2, R.ctr.p + 6);
 	}
-	unsigned long long c[5] = {0, 0, 0, 0, 0};
-	HIPCK(hipMemcpyAsync(c, R.ctr.p, 40, hipMemcpyDeviceToHost, st));
+	unsigned long long c[7] = {0, 0, 0, 0, 0, 0, 0};
+	HIPCK(hipMemcpyAsync(c, R.ctr.p, 56, hipMemcpyDeviceToHost, st));
 	HIPCK(hipStreamSynchronize(st));
 	// ---- the tasks whose forward list did not fit: again, with columns of max_len + 1 entries (the list holds at most len - x)
 	const uint32_t n_ovf = (uint32_t)(c[1] & 0xFFFFFFFFull);
@@ -352,13 +373,15 @@ int reseed_merge(reseed_state_t **Rp, const reseed_in_t &in, hipStream_t st, res
 	if (n_ovf) {
 		RCK(R.list_b.need(16 * (size_t)n_ovf * cap_b)); RCK(R.out_b.need(16 * (size_t)n_ovf * cap_b)); RCK(R.n2b.need(4 * (size_t)n_ovf));
 		reseed_r2_kernel<<<rs_nblk(n_ovf), 256, 0, st>>>(in.f, in.rv, in.lens, k, R.tasks.as<rs_task_t>(), R.ovf.as<uint32_t>(), n_ovf, cap_b,
-		                                                 R.list_b.as<uint4>(), R.out_b.as<uint4>(), R.n2b.as<uint32_t>(), R.ovf.as<uint32_t>() /* (cannot overflow) */, R.ctr.p + 3);
-		HIPCK(hipMemcpyAsync(&c[3], R.ctr.p + 3, 8, hipMemcpyDeviceToHost, st));
+		                                                 R.list_b.as<uint4>(), R.out_b.as<uint4>(), R.n2b.as<uint32_t>(), R.ovf.as<uint32_t>() /* (cannot overflow) */, R.ctr.p + 3, R.ctr.p + 5);
+		HIPCK(hipMemcpyAsync(&c[3], R.ctr.p + 3, 24, hipMemcpyDeviceToHost, st));      // (c[4] is not read again)
 		HIPCK(hipStreamSynchronize(st));
 	}
 	const uint64_t n1 = in.n_kept, n2 = c[0] + c[3], n3 = c[2], n = n1 + n2 + n3;
 	if (n >> 32) { bmh_set_error("bmh_seed_batch_reseed: more than 2^32 seed groups in one batch"); return BMH_ECAPACITY; }
 	out->n_round[0] = n1; out->n_round[1] = n2; out->n_round[2] = n3;
+	g_rs_last[0] = n_tasks; g_rs_last[1] = n_ovf; g_rs_last[2] = n1; g_rs_last[3] = n2; g_rs_last[4] = n3;
+	g_rs_last[5] = c[5]; g_rs_last[6] = c[6];
 
 	// ---- merge: keys of every group, radix sort, columns
 	RCK(R.keys.need(8 * (n + 1))); RCK(R.keys2.need(8 * (n + 1))); RCK(R.vals.need(4 * (n + 1))); RCK(R.vals2.need(4 * (n + 1)));
@@ -368,7 +391,7 @@ int reseed_merge(reseed_state_t **Rp, const reseed_in_t &in, hipStream_t st, res
 	if (n_cands) reseed_copy_r1_kernel<<<rs_nblk(n_cands), 256, 0, st>>>(in.res_a, in.res_k, in.occ, in.occ_off, n_cands, keys, vals, mk, ms);
 	reseed_set_kernel<<<1, 1, 0, st>>>(R.ctr.p + 4, (unsigned long long)n1);
 	if (n_tasks)
-		reseed_copy_out_kernel<<<rs_nblk(n_tasks), 256, 0, st>>>(R.out2.as<uint4>(), R.n2.as<uint32_t>(), nullptr, RS2_CAP, n_tasks, R.tasks.as<rs_task_t>(), nullptr,
+		reseed_copy_out_kernel<<<rs_nblk(n_tasks), 256, 0, st>>>(R.out2.as<uint4>(), R.n2.as<uint32_t>(), nullptr, cap_a, n_tasks, R.tasks.as<rs_task_t>(), nullptr,
 		                                                         R.ctr.p + 4, keys, vals, mk, ms);
 	if (n_ovf)
 		reseed_copy_out_kernel<<<rs_nblk(n_ovf), 256, 0, st>>>(R.out_b.as<uint4>(), R.n2b.as<uint32_t>(), nullptr, cap_b, n_ovf, R.tasks.as<rs_task_t>(), R.ovf.as<uint32_t>(),

@@ -41,3 +41,4 @@ struct reseed_out_t {
 struct reseed_state_t;
 int reseed_merge(reseed_state_t **R, const reseed_in_t &in, hipStream_t st, reseed_out_t *out);
 void reseed_state_free(reseed_state_t *R);
+void reseed_counts_reset(void);         // zeroes what bmh_reseed_last_counts returns (the calling thread's)

@@ -927,6 +927,7 @@ extern "C" void bmh_reseed_opt_default(bmh_reseed_opt_t *o)
 extern "C" int bmh_seed_batch_reseed(bmh_seed_ws_t *w, const bmh_index_t *idx, const uint8_t *d_reads, const uint32_t *d_offs,
                                      const uint32_t *d_lens, uint32_t n_reads, int min_seed_len, const bmh_reseed_opt_t *opt, void *stream_, bmh_seeds_t *out)
 {
+	reseed_counts_reset();
 	return seed_batch_impl(w, idx, d_reads, d_offs, d_lens, n_reads, min_seed_len, (opt && opt->enable) ? opt : nullptr, stream_, out);
 }
 static int seed_batch_impl(bmh_seed_ws_t *w, const bmh_index_t *idx, const uint8_t *d_reads, const uint32_t *d_offs,

@@ -207,6 +207,11 @@ void bmh_reseed_opt_default(bmh_reseed_opt_t *o);      /* 0 / 1.5 / 10 / 20, as 
 int bmh_seed_batch_reseed(bmh_seed_ws_t *ws, const bmh_index_t *idx, const uint8_t *d_reads,
                           const uint32_t *d_offs, const uint32_t *d_lens, uint32_t n_reads,
                           int min_seed_len, const bmh_reseed_opt_t *opt, void *stream, bmh_seeds_t *out);
+/* Which path the calling thread's last bmh_seed_batch_reseed took: out[0] = round-2 tasks, out[1] = tasks whose forward list did not fit
+ * the first launch's column (knob RESEED_CAP, 32 entries) and ran again in the second, out[2..4] = seed groups of rounds 1, 2 and 3, out[5] = rank steps
+ * (interval extensions) of round 2's lanes in both launches, out[6] = of round 3's.  All 0 before any call, after a call with re-seeding off, and
+ * after one that failed before the merge.  For tests. */
+int bmh_reseed_last_counts(uint64_t out[7]);
 
 /* per-kernel time of the last bmh_seed_batch, in ms (HIP events on the launch stream):
  * [0]=pack [1]=forward [2]=scatter+backward [3]=filter+scans [4]=expand [5]=locate [6]=total

@@ -182,13 +182,18 @@ def longest_runs(g):
     return [(int(a), int(b)) for a, b in zip(st, ln) if b > 18]
 
 
+MORE_WORLDS = {}
+
+
 @functools.lru_cache(maxsize=None)
 def world(which="main"):
     """genome, index, text, the oracle's handle on the index, and where the planted structures lie (at)"""
     import oracle_py
     from bwamem_hip import fmindex
     at = {}
-    if which == "small":
+    if which in MORE_WORLDS:                                   # (a table beside this one brings a genome of its own: tests/reseed_cases.py)
+        g = MORE_WORLDS[which](at)
+    elif which == "small":
         rng = np.random.default_rng(20262)
         g = rng.integers(0, 4, size=8_000).astype(np.uint8)
         g[3000:5000] = 0; g[2999] = 1; g[5000] = 2
@@ -215,7 +220,7 @@ def world(which="main"):
                 g[p:p + 45] = np.concatenate([[0], m, [0], 1 + rng.integers(0, 3, size=3)]); p += 45
         assert p < PLAIN_AT
         at["mers"] = mers
-    assert longest_runs(g) == [at["run"]], longest_runs(g)
+    assert longest_runs(g) == ([at["run"]] if "run" in at else []), longest_runs(g)
     idx = fmindex.build_fmd_index(g)
     orc = oracle_py.Oracle()
     f = orc.fmd(idx)
