@@ -901,18 +901,16 @@ class Aligner:
             if self.long_reads:
                 nat.set_max_qlen(EXT_LONG_MAX)
         nat.set_reseed(self.reseed if self.reseed.enable else None)
-        nat.set_index_format(*getattr(self, "_index_format", ("bai", 14)))
-        nat.set_output(*getattr(self, "_out_fmt", ("sam", 1)))
-        if getattr(self, "_out_fmt", ("sam", 1))[0] == "bam_sorted":
-            nat.set_sort(*self._sort_knobs)
-            nat.set_markdup(bool(getattr(self, "_markdup", False)))
-            nat.set_coverage(getattr(self, "_coverage_opt", None))
-            nat.set_stats(getattr(self, "_stats_opt", None))
-            if getattr(self, "_markdup", False):
-                nat.set_markdup_optical(getattr(self, "_optical", None))
-                nat.set_markdup_barcode(*getattr(self, "_barcode", (0, None)))
-                nat.set_markdup_barcode_edits(getattr(self, "_barcode_edits", -1))
+        fmt, level, sorted_keywords = self._output
+        if fmt == "bam_sorted":
+            nat.set_sorted(level=level, **sorted_keywords)
+        else:
+            nat.set_output(fmt, level)
         return nat
+
+    # what the runs that follow write: the format, the level and, for "bam_sorted", NativeAligner.set_sorted's keywords (_align_bam sets it for its run)
+    _OUTPUT_DEFAULT = ("sam", 1, {})
+    _output = _OUTPUT_DEFAULT
 
     @_coverage_keywords
     @_stats_keywords
@@ -991,10 +989,10 @@ class Aligner:
             return n
         for b, e in zip(cuts[:-1], cuts[1:]):
             if e > b:
-                if getattr(self, "_out_fmt", ("sam", 1))[0] == "bam_sorted":
+                if self._output[0] == "bam_sorted":
                     raise NotImplementedError("sort=True needs the native pipeline (BMH_ALIGNER_NATIVE=0 and profile runs write batch after batch)")
-                if getattr(self, "_out_fmt", ("sam", 1))[0] == "bam":
-                    out.write(self.align_batch(rs.slice(b, e), id0=b, paired=paired, fmt="bam", level=self._out_fmt[1]))
+                if self._output[0] == "bam":
+                    out.write(self.align_batch(rs.slice(b, e), id0=b, paired=paired, fmt="bam", level=self._output[1]))
                     continue
                 out.write(self.align_batch(rs.slice(b, e), id0=b, paired=paired, as_bytes="view" if binary else False))   # (binary: the library's buffer, uncopied)
         return n
@@ -1064,57 +1062,42 @@ class Aligner:
         if sort:
             if os.environ.get("BMH_ALIGNER_NATIVE", "1") == "0" or self.profile:   # (before anything is switched: a refused call leaves the aligner as it was)
                 raise NotImplementedError("sort=True needs the native pipeline (BMH_ALIGNER_NATIVE=0 and profile runs write batch after batch)")
-            self._sort_knobs = (int(sort_mem or 0), sort_tmp, int(sort_window or 0))
-        self._out_fmt = ("bam_sorted" if sort else "bam", level)
-        self._markdup = bool(markdup)
-        self._optical = optical_distance
-        self._barcode = barcode
-        self._barcode_edits = edits
-        self._index_format = (index_format, int(csi_min_shift))
         cov_req = getattr(self, "_cov_req", None) if sort else None
-        if cov_req is not None:
-            from .lib import coverage_opt
-            self._coverage_opt = coverage_opt(cov_req["min_mapq"], cov_req["deletions"], cov_req["bin"], 0, "align_file")
         stats_req = getattr(self, "_stats_req", None) if sort else None
-        if stats_req is not None:
-            from .lib import stats_opt
-            self._stats_opt = stats_opt(stats_req["insert_cap"], "align_file")
+        sorted_keywords = dict(markdup=bool(markdup), optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name, barcode_edits=barcode_edits,
+                               index_format=index_format, csi_min_shift=int(csi_min_shift), window=int(sort_window or 0), sort_mem=sort_mem or None, sort_tmp=sort_tmp,
+                               coverage=dict(min_mapq=cov_req["min_mapq"], deletions=cov_req["deletions"], bin=cov_req["bin"]) if cov_req is not None else None,
+                               stats=dict(insert_cap=stats_req["insert_cap"]) if stats_req is not None else None) if sort else {}
+        self._output = ("bam_sorted" if sort else "bam", level, sorted_keywords)
         try:
             n = run(shim)
-            if cov_req is not None:                                # (no reads: no run was made -- the coverage of a file without records)
+            got = self._native.sorted_results() if sort and n else {}      # (no reads: no run was made -- every part is that of a file without records)
+            if cov_req is not None:
                 from .lib import bam_coverage
-                self.coverage = self._native.coverage() if n else bam_coverage(b"", self.contigs, host=True, min_mapq=cov_req["min_mapq"], deletions=cov_req["deletions"], bin=cov_req["bin"])
-            if stats_req is not None:                              # (no reads: the statistics of a file without records)
+                self.coverage = got["coverage"] if n else bam_coverage(b"", self.contigs, host=True, min_mapq=cov_req["min_mapq"], deletions=cov_req["deletions"], bin=cov_req["bin"])
+            if stats_req is not None:
                 from .lib import bam_stats
-                self.stats = self._native.stats() if n else bam_stats(b"", len(self.contigs), stats_req["insert_cap"], host=True)
+                self.stats = got["stats"] if n else bam_stats(b"", len(self.contigs), stats_req["insert_cap"], host=True)
             if markdup:
-                from .lib import MARKDUP_COUNTS
-                self.markdup_counts = self._native.markdup_counts() if n else dict.fromkeys(MARKDUP_COUNTS, 0)
-                if getattr(self, "_groups", None):                # per library, in order of first appearance (the library index of the run)
-                    libs = list(dict.fromkeys(rg_library(g[0]) for g in self._groups))
-                    self.markdup_library_counts = {lb: (self._native.markdup_library_counts(k) if n else dict.fromkeys(MARKDUP_COUNTS, 0)) for k, lb in enumerate(libs)}
+                from .lib import MARKDUP_COUNTS, BARCODE_GROUP_COUNTS, OPTICAL_COUNTS
+                self.markdup_counts = got["markdup_counts"] if n else dict.fromkeys(MARKDUP_COUNTS, 0)
+                # per library, in order of first appearance (the library index of the run)
+                libs = list(dict.fromkeys(rg_library(g[0]) for g in self._groups)) if getattr(self, "_groups", None) else []
+                if libs:
+                    self.markdup_library_counts = {lb: (got["markdup_library_counts"][k] if n else dict.fromkeys(MARKDUP_COUNTS, 0)) for k, lb in enumerate(libs)}
                 if barcode[0] != BARCODE_OFF:
-                    self.markdup_counts.update(self._native.markdup_barcode_counts() if n else {"templates_without_barcode": 0})
+                    self.markdup_counts.update(got["markdup_barcode_counts"] if n else {"templates_without_barcode": 0})
                 if edits >= 0:
-                    from .lib import BARCODE_GROUP_COUNTS
-                    self.markdup_counts.update(self._native.markdup_barcode_group_counts() if n else dict.fromkeys(BARCODE_GROUP_COUNTS, 0))
+                    self.markdup_counts.update(got["markdup_barcode_group_counts"] if n else dict.fromkeys(BARCODE_GROUP_COUNTS, 0))
                 if optical_distance is not None:
-                    from .lib import OPTICAL_COUNTS
-                    self.markdup_optical_counts = self._native.markdup_optical_counts() if n else dict.fromkeys(OPTICAL_COUNTS, 0)
+                    self.markdup_optical_counts = got["markdup_optical_counts"] if n else dict.fromkeys(OPTICAL_COUNTS, 0)
                     self.markdup_counts.update(self.markdup_optical_counts)
-                    if getattr(self, "_groups", None):
-                        self.markdup_library_optical_counts = {lb: (self._native.markdup_optical_counts(k) if n else dict.fromkeys(OPTICAL_COUNTS, 0)) for k, lb in enumerate(libs)}
+                    if libs:
+                        self.markdup_library_optical_counts = {lb: (got["markdup_library_optical_counts"][k] if n else dict.fromkeys(OPTICAL_COUNTS, 0)) for k, lb in enumerate(libs)}
                         for lb in libs:
                             self.markdup_library_counts[lb].update(self.markdup_library_optical_counts[lb])
         finally:
-            self._out_fmt = ("sam", 1)
-            self._markdup = False
-            self._optical = None
-            self._barcode = (0, None)
-            self._barcode_edits = -1
-            self._index_format = ("bai", 14)
-            self._coverage_opt = None
-            self._stats_opt = None
+            self._output = self._OUTPUT_DEFAULT
             nat = getattr(self, "_native", None)
             if nat is not None:
                 nat.set_output("sam", 1)
@@ -1124,7 +1107,7 @@ class Aligner:
         if index is not None:
             nat = self._native_aligner() if n == 0 else self._native
             if n == 0:                                            # (no run was made: the index of a file without records)
-                nat.set_index_format(index_format, int(csi_min_shift)); nat.set_output("bam_sorted", level); nat.set_output("sam", 1)
+                nat.set_sorted(level=level, index_format=index_format, csi_min_shift=int(csi_min_shift)); nat.set_output("sam", 1)
             bai = nat.sort_index(self._bam_header_bytes)                 # (the bytes of the format the run was made under: .bai or .csi)
             if hasattr(index, "write"):
                 index.write(bai)

@@ -40,22 +40,15 @@ EXPORTED_SYMBOLS = [
     "bmh_bgzf_scan", "bmh_inflate_members_device", "bmh_inflate_members_host", "bmh_inflate_status_name", "bmh_bgzf_inflate",
     "bmh_bam_ws_create", "bmh_bam_ws_free", "bmh_sam_to_bam_device", "bmh_sam_to_bam_host", "bmh_bam_status_name", "bmh_bgzf_deflate_device", "bmh_bgzf_deflate_host",
     "bmh_deflate_blocks_host", "bmh_bam_header", "bmh_aligner_set_output",
-    "bmh_bam_sort_device", "bmh_bam_sort_host", "bmh_bam_sorted_file_device", "bmh_bam_sorted_file_host", "bmh_aligner_set_sort", "bmh_aligner_sort_index",
+    "bmh_bam_sort_device", "bmh_bam_sort_host", "bmh_sorted_opt_default", "bmh_bam_sorted_file_device", "bmh_bam_sorted_file_host", "bmh_aligner_set_sorted_output", "bmh_aligner_sorted_results", "bmh_aligner_sort_index",
     "bmh_bam_reads_device", "bmh_bam_reads_host", "bmh_reads_last_bam_counts", "bmh_aligner_set_bam_pairs",
-    "bmh_markdup_opt_default", "bmh_bam_markdup_device", "bmh_bam_markdup_host", "bmh_aligner_set_markdup", "bmh_aligner_markdup_counts", "bmh_aligner_markdup_times",
-    "bmh_aligner_markdup_library_counts", "bmh_aligner_run_groups",
+    "bmh_markdup_opt_default", "bmh_bam_markdup_device", "bmh_bam_markdup_host", "bmh_aligner_run_groups",
     "bmh_bam_reads_groups_device", "bmh_bam_reads_groups_host", "bmh_bam_header_read_groups", "bmh_format_sam_groups", "bmh_aligner_set_keep_rg",
-    "bmh_aligner_set_index_format",
     "bmh_bam_dup_locations_device", "bmh_bam_dup_locations_host", "bmh_bam_name_location", "bmh_library_size",
-    "bmh_aligner_set_markdup_optical", "bmh_aligner_markdup_optical_counts", "bmh_aligner_markdup_optical_ms",
-    "bmh_bam_dup_barcodes_device", "bmh_bam_dup_barcodes_host", "bmh_barcode_word", "bmh_aligner_set_markdup_barcode", "bmh_aligner_markdup_barcode_counts",
-    "bmh_barcode_pack", "bmh_aligner_set_markdup_barcode_edits",
-    "bmh_aligner_markdup_barcode_group_counts",
+    "bmh_bam_dup_barcodes_device", "bmh_bam_dup_barcodes_host", "bmh_barcode_word", "bmh_barcode_pack",
     "bmh_reads_last_collate_counts", "bmh_aligner_set_collate", "bmh_reads_load_files_ex", "bmh_bam_reads_ex",
-    "bmh_coverage_opt_default", "bmh_bam_coverage_device", "bmh_bam_coverage_host", "bmh_bam_sorted_file_coverage_device", "bmh_bam_sorted_file_coverage_host",
-    "bmh_aligner_set_coverage", "bmh_aligner_coverage", "bmh_aligner_coverage_ms",
-    "bmh_bam_stats_opt_default", "bmh_bam_stats_free", "bmh_bam_stats_device", "bmh_bam_stats_host", "bmh_bam_sorted_file_stats_device", "bmh_bam_sorted_file_stats_host",
-    "bmh_aligner_set_stats", "bmh_aligner_stats", "bmh_aligner_stats_ms", "bmh_bam_post_file_stats_device", "bmh_bam_post_file_stats_host",
+    "bmh_coverage_opt_default", "bmh_bam_coverage_device", "bmh_bam_coverage_host",
+    "bmh_bam_stats_opt_default", "bmh_bam_stats_free", "bmh_bam_stats_device", "bmh_bam_stats_host",
     "bmh_bam_post_opt_default", "bmh_bam_post_result_free", "bmh_bam_post_file_device", "bmh_bam_post_file_host",
     "bmh_bam_templates_device", "bmh_bam_templates_host", "bmh_bam_templates_free",
 ]
@@ -585,19 +578,12 @@ class MarkdupCounts(C.Structure):
                 ("lib_counts", _u64p), ("lib_optical", _u64p), ("lib_grouped", _u64p)]
 
 
-class SortedFileOpt(C.Structure):
-    """bmh_sorted_file_opt_t"""
-    _fields_ = [("level", C.c_int32), ("window", C.c_uint32), ("index_format", C.c_int32), ("min_shift", C.c_int32), ("markdup", C.POINTER(MarkdupOpt))]
-
-
 def _markdup_api(L):
-    """the library with the argument types of the four calls that take the records above"""
+    """the library with the argument types of the two calls that take the records above"""
     if not getattr(L, "_markdup_api", False):
-        stream, file_head = [C.c_char_p, C.c_uint64, C.POINTER(MarkdupOpt)], [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(SortedFileOpt)]
-        out, file_out = [C.POINTER(C.c_void_p), C.POINTER(MarkdupCounts)], [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p, C.POINTER(MarkdupCounts)]
+        stream, out = [C.c_char_p, C.c_uint64, C.POINTER(MarkdupOpt)], [C.POINTER(C.c_void_p), C.POINTER(MarkdupCounts)]
         L.bmh_markdup_opt_default.argtypes, L.bmh_markdup_opt_default.restype = [C.POINTER(MarkdupOpt)], None
         L.bmh_bam_markdup_host.argtypes, L.bmh_bam_markdup_device.argtypes = stream + out, stream + [C.c_void_p] + out
-        L.bmh_bam_sorted_file_host.argtypes, L.bmh_bam_sorted_file_device.argtypes = file_head + file_out, file_head + [C.c_void_p] + file_out
         L.bmh_free.argtypes = [C.c_void_p]
         L._markdup_api = True
     return L
@@ -761,70 +747,42 @@ def index_format_code(index_format, csi_min_shift, what: str) -> tuple:
 
 
 def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False, markdup: bool = False, read_groups=None,
-                    index_format: str = "bai", csi_min_shift: int = 14, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None, stats=None) -> tuple:
-    """stats={insert_cap} (bmh_bam_sorted_file_stats_*; {} for the default): the file's statistics (bam_stats' dict), taken from the same windows with the flags
+                    index_format: str = "bai", csi_min_shift: int = 14, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None, stats=None,
+                    optical_distance=None) -> tuple:
+    """stats={insert_cap} (bmh_sorted_opt_t's stats; {} for the default): the file's statistics (bam_stats' dict), taken from the same windows with the flags
     markdup=True sets, come last in the tuple, behind the coverage where both are asked for.
-    coverage={min_mapq, deletions, bin, tile} (bmh_bam_sorted_file_coverage_*; bam_coverage's keywords, {} for the defaults): the file's coverage, taken from
+    coverage={min_mapq, deletions, bin, tile} (bmh_sorted_opt_t's coverage; bam_coverage's keywords, {} for the defaults): the file's coverage, taken from
     the windows of the merge as they are written -- with markdup=True the marked duplicates are counted out -- comes last in the tuple.
     bmh_bam_sorted_file_device (host=True: _host): (the complete sorted BAM file -- header members, the records in coordinate order in windows of `window`
     records (0: about 64 MiB), the end-of-file member --, its .bai index).  contigs: (name, length) pairs; both forms give the same bytes.
-    markdup=True (a bmh_markdup_opt_t in bmh_sorted_file_opt_t): `records` come in the writer's order, the duplicates among them are marked (bam_markdup's rules) and the counts come third.
+    markdup=True (a bmh_markdup_opt_t in bmh_sorted_opt_t): `records` come in the writer's order, the duplicates among them are marked (bam_markdup's rules) and the counts come third.
     read_groups (needs markdup=True): as bam_markdup takes them -- duplicates per library, and the counts gain "libraries".
     index_format="csi" (index_format, min_shift): the second element is the .csi index -- BGZF-compressed, bins of 2^csi_min_shift bases (10 .. 24) at the depth the
     longest contig asks for --, contigs may hold up to 2^31 - 1 bases (with markdup=True up to 2^30 - 2^24) and the BAM bytes are those of the "bai" call.
     barcode_tag / barcode_name (need markdup=True): as bam_markdup takes them; the counts gain "templates_without_barcode".
-    barcode_edits (needs a barcode source): as bam_markdup takes it; the counts gain BARCODE_GROUP_COUNTS' names."""
-    bc_mode, bc_tag = barcode_source(barcode_tag, barcode_name, "bam_sorted_file")
-    if barcode_edits is not None and not markdup:
-        raise ValueError("bam_sorted_file: barcode_edits needs markdup=True (barcodes are grouped where duplicates are marked)")
-    edits = barcode_edits_value(barcode_edits, bc_mode, "bam_sorted_file")
-    if bc_mode != BARCODE_OFF and not markdup:
-        raise ValueError("bam_sorted_file: barcode_tag / barcode_name need markdup=True (barcodes are compared where duplicates are marked)")
-    if read_groups is not None and not markdup:
-        raise ValueError("bam_sorted_file: read_groups needs markdup=True (they decide which templates may be duplicates of each other)")
-    ix_code, ix_shift = index_format_code(index_format, csi_min_shift, "bam_sorted_file")
-    L = _markdup_api(load_library())
+    barcode_edits (needs a barcode source): as bam_markdup takes it; the counts gain BARCODE_GROUP_COUNTS' names.
+    optical_distance: the record's field, which the library refuses here -- a stand-alone file has no optical step (bam_markdup counts optical duplicates)."""
+    L = _sorted_file_api(load_library())
+    q = sorted_request("bam_sorted_file", L, markdup=markdup, read_groups=read_groups, optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name, barcode_edits=barcode_edits, coverage=coverage,
+                       stats=stats, index_format=index_format, csi_min_shift=csi_min_shift, level=level, window=window)
     records = bytes(records)
     names = (C.c_char_p * max(len(contigs), 1))(*[c[0].encode() for c in contigs])
     lens = np.ascontiguousarray([c[1] for c in contigs] or [0], dtype=np.int64)
-    if ix_code == INDEX_BAI and ((lens < 0) | (lens >= 1 << 29)).any():
+    if q.opt.index_format == INDEX_BAI and ((lens < 0) | (lens >= 1 << 29)).any():
         raise ValueError("bam_sorted_file: a BAI index holds contigs below 2^29 bases (CSI is not written)")
     if ((lens < 0) | (lens >= 1 << 31)).any():
         raise ValueError("bam_sorted_file: BAM and its CSI index hold contigs of at most 2^31 - 1 bases")
     lens = lens.astype(np.int32)
-    o, res, lib_names, _keep = _markdup_records(L, read_groups, bc_mode=bc_mode, bc_tag=bc_tag, edits=edits)
-    fo = SortedFileOpt(int(level), int(window), ix_code, ix_shift, C.pointer(o) if markdup else None)
     bam, bai, nb, ni = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
-    head = [header_text.encode(), len(contigs), names, lens.ctypes.data, records, len(records), C.byref(fo)]
-    tail = [C.byref(bam), C.byref(nb), C.byref(bai), C.byref(ni), C.byref(res) if markdup else None]
-    cov, co = Coverage(), None
-    st, so = BamStats(), None
-    if coverage is not None:
-        co = coverage_opt(what="bam_sorted_file", **coverage)
-    if stats is not None:
-        so = stats_opt(what="bam_sorted_file", **stats)
-        types = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(SortedFileOpt), C.POINTER(CoverageOpt), C.POINTER(BamStatsOpt)]
-        outs = [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p, C.POINTER(MarkdupCounts), C.POINTER(Coverage), C.POINTER(BamStats)]
-        L.bmh_bam_sorted_file_stats_host.argtypes, L.bmh_bam_sorted_file_stats_device.argtypes = types + outs, types + [C.c_void_p] + outs
-        head, tail = head + [C.byref(co) if co else None, C.byref(so)], tail + [C.byref(cov) if co else None, C.byref(st)]
-    elif coverage is not None:
-        types = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(SortedFileOpt), C.POINTER(CoverageOpt)]
-        outs = [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p, C.POINTER(MarkdupCounts), C.POINTER(Coverage)]
-        L.bmh_bam_sorted_file_coverage_host.argtypes, L.bmh_bam_sorted_file_coverage_device.argtypes = types + outs, types + [C.c_void_p] + outs
-        head, tail = head + [C.byref(co)], tail + [C.byref(cov)]
-    if host:
-        rc = (L.bmh_bam_sorted_file_stats_host if so else L.bmh_bam_sorted_file_coverage_host if co else L.bmh_bam_sorted_file_host)(*head, *tail)
-    else:
-        import torch
-        rc = (L.bmh_bam_sorted_file_stats_device if so else L.bmh_bam_sorted_file_coverage_device if co else L.bmh_bam_sorted_file_device)(*head, torch.cuda.current_stream().cuda_stream, *tail)
+    rc = (L.bmh_bam_sorted_file_host if host else L.bmh_bam_sorted_file_device)(header_text.encode(), len(contigs), names, lens.ctypes.data, records, len(records), C.byref(q.opt), *([] if host else [_current_stream()]),
+              C.byref(bam), C.byref(nb), C.byref(bai), C.byref(ni), C.byref(q.res))
     if rc != 0:
         raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_sorted_file: " + _err(L))
     try:
-        extra = ((coverage_dict(L, cov),) if co else ()) + ((stats_dict(L, st),) if so else ())
-        if markdup:
-            return (C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value), _markdup_dict(o, res, lib_names, read_groups is not None)) + extra
-        return (C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)) + extra
+        got = q.results(L)
+        return (C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)) + tuple(got[k] for k in ("markdup", "coverage", "stats") if k in got)
     finally:
+        L.bmh_free.argtypes = [C.c_void_p]
         L.bmh_free(bam); L.bmh_free(bai)
 
 
@@ -972,10 +930,97 @@ def reads_last_bam_counts() -> dict:
     return dict(records_skipped=int(out[0]), tags_left_out=int(out[1]))
 
 
+class SortedOpt(C.Structure):
+    """bmh_sorted_opt_t"""
+    _fields_ = [("level", C.c_int32), ("window", C.c_uint32), ("index_format", C.c_int32), ("min_shift", C.c_int32), ("sort_mem", C.c_uint64), ("tmp_dir", C.c_char_p),
+                ("markdup", C.POINTER(MarkdupOpt)), ("coverage", C.POINTER(CoverageOpt)), ("stats", C.POINTER(BamStatsOpt))]
+
+
+class SortedResults(C.Structure):
+    """bmh_sorted_results_t"""
+    _fields_ = [("markdup", C.POINTER(MarkdupCounts)), ("coverage", C.POINTER(Coverage)), ("stats", C.POINTER(BamStats)), ("parts", C.c_uint32), ("n_libraries", C.c_int32),
+                ("markdup_ms", C.c_double * 2), ("optical_ms", C.c_double), ("coverage_ms", C.c_double), ("stats_ms", C.c_double),
+                ("markdup_d2h_bytes", C.c_uint64), ("coverage_windows", C.c_uint64), ("stats_windows", C.c_uint64)]
+
+
+SortedFileOpt = SortedOpt      # (the name the record had while it served bmh_bam_sorted_file_* alone: code that imports it gets the one record)
+
+
+SORTED_PARTS = dict(markdup=1, optical=2, barcode=4, grouped=8, coverage=16, stats=32)      # BMH_SORTED_*
+
+
+def _current_stream() -> int:
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+class SortedRequest:
+    """what one sorted output is made under and where its results go, as the library takes them: opt (bmh_sorted_opt_t), res (bmh_sorted_results_t) and every
+    record the two point to, kept alive here"""
+
+    def results(self, L, lib_names=None) -> dict:
+        """after a call that succeeded: {"markdup": bam_markdup's counts, "coverage": bam_coverage's arrays, "stats": bam_stats' arrays}, each where it was asked
+        for (the records' arrays are released)"""
+        out = {}
+        if self.opt.markdup:
+            out["markdup"] = _markdup_dict(self.mo, self.mc, self.lib_names if lib_names is None else lib_names, self.read_groups or lib_names is not None)
+        if self.opt.coverage:
+            out["coverage"] = coverage_dict(L, self.cov)
+        if self.opt.stats:
+            out["stats"] = stats_dict(L, self.st)
+        return out
+
+
+def sorted_request(what: str, L, markdup: bool = False, read_groups=None, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None, stats=None,
+                   index_format: str = "bai", csi_min_shift: int = 14, level: int = 1, window: int = 0, sort_mem=None, sort_tmp=None, libraries: int = 0) -> SortedRequest:
+    """the keywords of every sorted output (bam_sorted_file, bam_post, NativeAligner.set_sorted), checked -> a SortedRequest.  ValueError names the keyword: the
+    barcode keywords, optical_distance and read_groups need markdup=True; barcode_edits needs a barcode source; index_format "bai" or "csi" with csi_min_shift
+    10 .. 24; level 0 or 1; sort_mem a number of bytes.  libraries: room for that many libraries' rows in the counts record where read_groups are not given (the
+    callers whose libraries come from elsewhere)"""
+    bc_mode, bc_tag = barcode_source(barcode_tag, barcode_name, what)
+    if barcode_edits is not None and not markdup:
+        raise ValueError(f"{what}: barcode_edits needs markdup=True (barcodes are grouped where duplicates are marked)")
+    edits = barcode_edits_value(barcode_edits, bc_mode, what)
+    if bc_mode != BARCODE_OFF and not markdup:
+        raise ValueError(f"{what}: barcode_tag / barcode_name need markdup=True (barcodes are compared where duplicates are marked)")
+    if optical_distance is not None and not markdup:
+        raise ValueError(f"{what}: optical_distance needs markdup=True (optical duplicates are counted where duplicates are marked)")
+    if read_groups is not None and not markdup:
+        raise ValueError(f"{what}: read_groups needs markdup=True (they decide which templates may be duplicates of each other)")
+    distance = -1 if optical_distance is None else optical_distance_value(optical_distance, what)
+    ix_code, ix_shift = index_format_code(index_format, csi_min_shift, what)
+    if level not in (0, 1):
+        raise ValueError(f"{what}: level {level}: 0 or 1")
+    if sort_mem is not None and (not isinstance(sort_mem, (int, np.integer)) or isinstance(sort_mem, bool) or sort_mem < 1):
+        raise ValueError(f"{what}: sort_mem {sort_mem!r}: a number of bytes, 1 and more")
+    q = SortedRequest()
+    q.read_groups = read_groups is not None
+    q.mo, q.mc, q.lib_names, q.keep = _markdup_records(_markdup_api(L), read_groups, distance, 0, bc_mode, bc_tag, edits, 0)
+    if libraries and read_groups is None:
+        arrays = [(C.c_uint64 * (k * libraries))() for k in (8, 3, 3)]
+        q.mc.lib_counts, q.mc.lib_optical, q.mc.lib_grouped = (C.cast(a, _u64p) for a in arrays)
+        q.keep = arrays
+    q.co = coverage_opt(what=what, **coverage) if coverage is not None else None
+    q.so = stats_opt(what=what, **stats) if stats is not None else None
+    q.cov, q.st = Coverage(), BamStats()
+    q.opt = SortedOpt(int(level), int(window), ix_code, ix_shift, int(sort_mem or 0), os.fsencode(sort_tmp) if sort_tmp is not None else None,
+                      C.pointer(q.mo) if markdup else None, C.pointer(q.co) if q.co is not None else None, C.pointer(q.so) if q.so is not None else None)
+    q.res = SortedResults(C.pointer(q.mc) if markdup else None, C.pointer(q.cov) if q.co is not None else None, C.pointer(q.st) if q.so is not None else None)
+    return q
+
+
+def _sorted_file_api(L):
+    """the library with the argument types of bmh_bam_sorted_file_host and _device"""
+    head = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(SortedOpt)]
+    out = [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p, C.POINTER(SortedResults)]
+    L.bmh_bam_sorted_file_host.argtypes, L.bmh_bam_sorted_file_device.argtypes = head + out, head + [C.c_void_p] + out
+    L.bmh_sorted_opt_default.argtypes, L.bmh_sorted_opt_default.restype = [C.POINTER(SortedOpt)], None
+    return L
+
+
 class BamPostOpt(C.Structure):
     """bmh_bam_post_opt_t"""
-    _fields_ = [("level", C.c_int32), ("window", C.c_uint32), ("index_format", C.c_int32), ("min_shift", C.c_int32), ("sort_mem", C.c_uint64), ("tmp_dir", C.c_char_p),
-                ("batch_bytes", C.c_uint64), ("markdup", C.POINTER(MarkdupOpt)), ("libraries", C.c_int32), ("coverage", C.POINTER(CoverageOpt)), ("collate", C.c_int32), ("stats", C.POINTER(BamStatsOpt))]
+    _fields_ = [("sorted", SortedOpt), ("batch_bytes", C.c_uint64), ("libraries", C.c_int32), ("collate", C.c_int32)]
 
 
 class BamPostResult(C.Structure):
@@ -999,7 +1044,7 @@ def _names_blob(addr, n: int) -> list:
 
 def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 0, index_format: str = "bai", csi_min_shift: int = 14, sort_mem=None, sort_tmp=None, batch_bytes=None,
              markdup: bool = False, libraries: bool = False, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None, collate: bool = False, stats=None) -> dict:
-    """stats={insert_cap} (bmh_bam_post_file_stats_*; {} for the default): "stats" holds the file's statistics (bam_stats' dict), from the windows of the merge.
+    """stats={insert_cap} (bmh_sorted_opt_t's stats; {} for the default): "stats" holds the file's statistics (bam_stats' dict), from the windows of the merge.
     bmh_bam_post_file_device (host=True: bmh_bam_post_file_host, no device needed; it holds the whole record stream in memory): the BAM or SAM file `src` of any
     aligner (a path; plain, gzip or BGZF; a pipe) -> the coordinate-sorted BAM, handed to write(bytes) piece by piece, and a dict: "index" (the .bai or .csi
     bytes), "header" (the output header's text), "contigs" ((name, length) pairs), "counts" (BAM_POST_COUNTS' names), with markdup=True "markdup" (bam_markdup's
@@ -1010,34 +1055,16 @@ def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 
     be marked -- a template is every record of the file under one read name, adjacent or not; a name whose records are no proper template is refused.  It keeps 32
     bytes per record in host memory (48 / 56 with optical_distance / barcodes) until the last batch is in."""
     what = "bam_post"
-    bc_mode, bc_tag = barcode_source(barcode_tag, barcode_name, what)
-    if barcode_edits is not None and not markdup:
-        raise ValueError(f"{what}: barcode_edits needs markdup=True (barcodes are grouped where duplicates are marked)")
-    edits = barcode_edits_value(barcode_edits, bc_mode, what)
-    if bc_mode != BARCODE_OFF and not markdup:
-        raise ValueError(f"{what}: barcode_tag / barcode_name need markdup=True (barcodes are compared where duplicates are marked)")
-    if optical_distance is not None and not markdup:
-        raise ValueError(f"{what}: optical_distance needs markdup=True (optical duplicates are counted where duplicates are marked)")
     if libraries and not markdup:
         raise ValueError(f"{what}: libraries needs markdup=True (they decide which templates may be duplicates of each other)")
-    distance = -1 if optical_distance is None else optical_distance_value(optical_distance, what)
-    ix_code, ix_shift = index_format_code(index_format, csi_min_shift, what)
-    if level not in (0, 1):
-        raise ValueError(f"{what}: level {level}: 0 or 1")
-    for nm, v in (("sort_mem", sort_mem), ("batch_bytes", batch_bytes)):
-        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 1):
-            raise ValueError(f"{what}: {nm} {v!r}: a number of bytes, 1 and more")
+    if batch_bytes is not None and (not isinstance(batch_bytes, (int, np.integer)) or isinstance(batch_bytes, bool) or batch_bytes < 1):
+        raise ValueError(f"{what}: batch_bytes {batch_bytes!r}: a number of bytes, 1 and more")
     if batch_bytes is not None and batch_bytes > 1 << 30:
         raise ValueError(f"{what}: batch_bytes {batch_bytes}: at most 2^30")
-    L = _markdup_api(load_library())
-    mo, res, _names, _keep = _markdup_records(L, None, distance, 0, bc_mode, bc_tag, edits, 0)
-    arrays = [(C.c_uint64 * (k * 255))() for k in (8, 3, 3)] if libraries else []
-    if libraries:
-        res.lib_counts, res.lib_optical, res.lib_grouped = (C.cast(a, _u64p) for a in arrays)
-    co = coverage_opt(what=what, **coverage) if coverage is not None else None
-    so = stats_opt(what=what, **stats) if stats is not None else None
-    o = BamPostOpt(int(level), int(window), ix_code, ix_shift, int(sort_mem or 0), os.fsencode(sort_tmp) if sort_tmp is not None else None, int(batch_bytes or 0),
-                   C.pointer(mo) if markdup else None, 1 if libraries else 0, C.pointer(co) if co is not None else None, 1 if collate else 0, C.pointer(so) if so is not None else None)
+    L = load_library()
+    q = sorted_request(what, L, markdup=markdup, optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name, barcode_edits=barcode_edits, coverage=coverage,
+                       stats=stats, index_format=index_format, csi_min_shift=csi_min_shift, level=level, window=window, sort_mem=sort_mem, sort_tmp=sort_tmp, libraries=255 if libraries else 0)
+    o = BamPostOpt(q.opt, int(batch_bytes or 0), 1 if libraries else 0, 1 if collate else 0)
     failed = []
 
     def sink(_user, p, n):
@@ -1047,22 +1074,11 @@ def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 
         except BaseException as e:                                 # (an exception must not cross the C frames: the run ends, then it is raised)
             failed.append(e)
             return 1
-    cb, out, cov, st = _SINK(sink), BamPostResult(), Coverage(), BamStats()
-    head = [C.c_char_p, C.POINTER(BamPostOpt)]
-    tail = [_SINK, C.c_void_p, C.POINTER(BamPostResult), C.POINTER(MarkdupCounts), C.POINTER(Coverage)]
-    args = [cb, None, C.byref(out), C.byref(res) if markdup else None, C.byref(cov) if co is not None else None]
+    cb, out = _SINK(sink), BamPostResult()
     L.bmh_bam_post_result_free.argtypes, L.bmh_bam_post_result_free.restype = [C.POINTER(BamPostResult)], None
-    if so is not None:
-        tail, args = tail + [C.POINTER(BamStats)], args + [C.byref(st)]
-    if host:
-        call = L.bmh_bam_post_file_stats_host if so is not None else L.bmh_bam_post_file_host
-        call.argtypes = head + tail
-        rc = call(os.fsencode(src), C.byref(o), *args)
-    else:
-        import torch
-        call = L.bmh_bam_post_file_stats_device if so is not None else L.bmh_bam_post_file_device
-        call.argtypes = head + [C.c_void_p] + tail
-        rc = call(os.fsencode(src), C.byref(o), torch.cuda.current_stream().cuda_stream, *args)
+    call = L.bmh_bam_post_file_host if host else L.bmh_bam_post_file_device
+    call.argtypes = [C.c_char_p, C.POINTER(BamPostOpt)] + ([] if host else [C.c_void_p]) + [_SINK, C.c_void_p, C.POINTER(BamPostResult), C.POINTER(SortedResults)]
+    rc = call(os.fsencode(src), C.byref(o), *([] if host else [_current_stream()]), cb, None, C.byref(out), C.byref(q.res))
     if failed:
         raise failed[0]
     if rc != 0:
@@ -1071,13 +1087,7 @@ def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 
         names = _names_blob(out.contig_names, out.n_contigs)
         r = dict(index=C.string_at(out.index, out.index_bytes), header=C.string_at(out.header_text, out.header_bytes).decode("latin-1"),
                  contigs=[(nm, int(out.contig_len[k])) for k, nm in enumerate(names)], counts=dict(zip(BAM_POST_COUNTS, (int(v) for v in out.counts))))
-        if markdup:
-            lib_names = _names_blob(out.library_names, out.n_libraries) if libraries else []
-            r["markdup"] = _markdup_dict(mo, res, lib_names, libraries)
-        if co is not None:
-            r["coverage"] = coverage_dict(L, cov)
-        if so is not None:
-            r["stats"] = stats_dict(L, st)
+        r.update(q.results(L, _names_blob(out.library_names, out.n_libraries) if libraries else None))
         return r
     finally:
         L.bmh_bam_post_result_free(C.byref(out))
@@ -1304,173 +1314,68 @@ class NativeAligner:
             raise ValueError("bmh_aligner_set_reseed: " + _err(L))
 
     def set_output(self, fmt: str = "sam", level: int = 1) -> None:
-        """bmh_aligner_set_output: what the runs that follow hand to `write` -- "sam": the records' text; "bam": BGZF members of BAM records"""
+        """bmh_aligner_set_output: what the runs that follow hand to `write` -- "sam": the records' text; "bam": BGZF members of BAM records; "bam_sorted":
+        set_sorted(level=level) with every other keyword at its default"""
         L = load_library()
         L.bmh_aligner_set_output.argtypes = [C.c_void_p, C.c_int, C.c_int]
         codes = {"sam": OUT_SAM, "bam": OUT_BAM, "bam_sorted": OUT_BAM_SORTED}      # ("bam_sorted": sorted runs, merged at the end of the input)
         if fmt not in codes or L.bmh_aligner_set_output(self.handle, codes[fmt], int(level)) != 0:
             raise ValueError("bmh_aligner_set_output: " + (_err(L) if fmt in codes else f"format {fmt!r} (sam or bam)"))
 
-    def set_sort(self, mem_bytes: int = 0, tmp_dir: "str | None" = None, window_records: int = 0) -> None:
-        """bmh_aligner_set_sort: the sorted output's run store budget (0: 4 GiB), its directory (None: $TMPDIR, else /tmp) and window (0: about 64 MiB)"""
+    def set_sorted(self, **keywords) -> None:
+        """bmh_aligner_set_sorted_output: the runs that follow hand `write` the members of the coordinate-sorted file, made under sorted_request's keywords -- markdup,
+        optical_distance, barcode_tag, barcode_name, barcode_edits, coverage, stats, index_format, csi_min_shift, level, window, sort_mem, sort_tmp (read_groups come
+        from run_groups or set_keep_rg and are refused here).  Everything is checked before anything changes: a ValueError leaves the aligner as it was.  Any
+        set_output switches all of it off again"""
         L = load_library()
-        L.bmh_aligner_set_sort.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint32]
-        if L.bmh_aligner_set_sort(self.handle, int(mem_bytes), os.fsencode(tmp_dir) if tmp_dir is not None else None, int(window_records)) != 0:
-            raise ValueError("bmh_aligner_set_sort: " + _err(L))
+        q = sorted_request("bmh_aligner_set_sorted_output", L, **keywords)
+        L.bmh_aligner_set_sorted_output.argtypes = [C.c_void_p, C.POINTER(SortedOpt)]
+        if L.bmh_aligner_set_sorted_output(self.handle, C.byref(q.opt)) != 0:
+            raise ValueError("bmh_aligner_set_sorted_output: " + _err(L))
 
-    def set_index_format(self, index_format: str = "bai", csi_min_shift: int = 14) -> None:
-        """bmh_aligner_set_index_format: the index of the sorted runs that follow ("bai", or "csi" with bins of 2^csi_min_shift bases); before set_output("bam_sorted")"""
+    def sorted_results(self, *need) -> dict:
+        """bmh_aligner_sorted_results: what the last sorted run left, each where the run computed it -- "markdup_counts" (MARKDUP_COUNTS' names), "markdup_library_counts"
+        and "markdup_library_optical_counts" (a list, one dict per library of a run over read groups), "markdup_times" (decision_ms, window_flags_ms,
+        entries_d2h_bytes), "markdup_barcode_counts", "markdup_barcode_group_counts", "markdup_optical_counts", "markdup_optical_ms", "coverage" (bam_coverage's
+        arrays), "coverage_ms" ((device milliseconds, windows timed)), "stats" (bam_stats' arrays), "stats_ms".  need: names of SORTED_PARTS the caller insists on; a
+        part the last run did not compute raises ValueError saying so"""
         L = load_library()
-        code, shift = index_format_code(index_format, csi_min_shift, "bmh_aligner_set_index_format")
-        L.bmh_aligner_set_index_format.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        if L.bmh_aligner_set_index_format(self.handle, code, shift) != 0:
-            raise ValueError("bmh_aligner_set_index_format: " + _err(L))
-
-    def set_markdup(self, on: bool = True) -> None:
-        """bmh_aligner_set_markdup: the sorted runs that follow mark duplicates (refused unless the output is "bam_sorted"; any other set_output switches it off)"""
-        L = load_library()
-        L.bmh_aligner_set_markdup.argtypes = [C.c_void_p, C.c_int]
-        if L.bmh_aligner_set_markdup(self.handle, 1 if on else 0) != 0:
-            raise ValueError("bmh_aligner_set_markdup: " + _err(L))
-
-    def set_markdup_optical(self, distance=None) -> None:
-        """bmh_aligner_set_markdup_optical: the marked runs that follow count optical duplicates within `distance` (None: off; refused unless marking is on)"""
-        L = load_library()
-        L.bmh_aligner_set_markdup_optical.argtypes = [C.c_void_p, C.c_int64]
-        if L.bmh_aligner_set_markdup_optical(self.handle, -1 if distance is None else int(distance)) != 0:
-            raise ValueError("bmh_aligner_set_markdup_optical: " + _err(L))
-
-    def set_markdup_barcode(self, mode: int = 0, tag=None) -> None:
-        """bmh_aligner_set_markdup_barcode: the marked runs that follow compare the templates' barcodes -- mode 1: tag `tag`, 2: the read name's last field, 0: off
-        (refused unless marking is on)"""
-        L = load_library()
-        L.bmh_aligner_set_markdup_barcode.argtypes = [C.c_void_p, C.c_int, C.c_char_p]
-        if L.bmh_aligner_set_markdup_barcode(self.handle, int(mode), tag) != 0:
-            raise ValueError("bmh_aligner_set_markdup_barcode: " + _err(L))
-
-    def set_markdup_barcode_edits(self, n: int = -1) -> None:
-        """bmh_aligner_set_markdup_barcode_edits: the marked runs that follow group barcodes within n mismatches (0 .. 21; -1: off); after set_markdup_barcode"""
-        L = load_library()
-        L.bmh_aligner_set_markdup_barcode_edits.argtypes = [C.c_void_p, C.c_int]
-        if L.bmh_aligner_set_markdup_barcode_edits(self.handle, int(n)) != 0:
-            raise ValueError("bmh_aligner_set_markdup_barcode_edits: " + _err(L))
-
-    def markdup_barcode_group_counts(self) -> dict:
-        """bmh_aligner_markdup_barcode_group_counts: the grouping counts of the last run that grouped barcodes by edits, by BARCODE_GROUP_COUNTS' names"""
-        L = load_library()
-        L.bmh_aligner_markdup_barcode_group_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        c = (C.c_uint64 * 3)()
-        if L.bmh_aligner_markdup_barcode_group_counts(self.handle, c) != 0:
-            raise ValueError("bmh_aligner_markdup_barcode_group_counts: " + _err(L))
-        return dict(zip(BARCODE_GROUP_COUNTS, (int(v) for v in c)))
-
-    def markdup_barcode_counts(self) -> dict:
-        """bmh_aligner_markdup_barcode_counts: {"templates_without_barcode": ...} of the last run that compared barcodes"""
-        L = load_library()
-        L.bmh_aligner_markdup_barcode_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        c = (C.c_uint64 * 1)()
-        if L.bmh_aligner_markdup_barcode_counts(self.handle, c) != 0:
-            raise ValueError("bmh_aligner_markdup_barcode_counts: " + _err(L))
-        return {"templates_without_barcode": int(c[0])}
-
-    def markdup_optical_counts(self, lib: int = -1) -> dict:
-        """bmh_aligner_markdup_optical_counts: the optical counts of the last run that counted them, by OPTICAL_COUNTS' names -- of library `lib`, or (-1) in total"""
-        L = load_library()
-        L.bmh_aligner_markdup_optical_counts.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
-        c = (C.c_uint64 * 3)()
-        if L.bmh_aligner_markdup_optical_counts(self.handle, int(lib), c) != 0:
-            raise ValueError("bmh_aligner_markdup_optical_counts: " + _err(L))
-        return dict(zip(OPTICAL_COUNTS, (int(v) for v in c)))
-
-    def markdup_optical_ms(self) -> float:
-        """bmh_aligner_markdup_optical_ms: the share of the last such run's decision that the optical step took, in ms"""
-        L = load_library()
-        L.bmh_aligner_markdup_optical_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-        t = C.c_double(0)
-        if L.bmh_aligner_markdup_optical_ms(self.handle, C.byref(t)) != 0:
-            raise ValueError("bmh_aligner_markdup_optical_ms: " + _err(L))
-        return float(t.value)
-
-    def set_coverage(self, opt=None) -> None:
-        """bmh_aligner_set_coverage: the sorted runs that follow compute their coverage under `opt` (a CoverageOpt; None: off; refused unless the output is sorted BAM)"""
-        L = load_library()
-        L.bmh_aligner_set_coverage.argtypes = [C.c_void_p, C.POINTER(CoverageOpt)]
-        if L.bmh_aligner_set_coverage(self.handle, C.byref(opt) if opt is not None else None) != 0:
-            raise ValueError("bmh_aligner_set_coverage: " + _err(L))
-
-    def coverage(self) -> dict:
-        """bmh_aligner_coverage: the coverage of the last sorted run that computed it, as bam_coverage returns it"""
-        L = load_library()
-        L.bmh_aligner_coverage.argtypes = [C.c_void_p, C.POINTER(Coverage)]
-        cov = Coverage()
-        if L.bmh_aligner_coverage(self.handle, C.byref(cov)) != 0:
-            raise ValueError("bmh_aligner_coverage: " + _err(L))
-        return coverage_dict(L, cov)
-
-    def coverage_ms(self, windows: bool = False):
-        """bmh_aligner_coverage_ms: the device milliseconds the last such run's windows spent in the coverage step; windows=True: (milliseconds, windows timed)"""
-        L = load_library()
-        L.bmh_aligner_coverage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-        t, w = C.c_double(0), C.c_uint64(0)
-        if L.bmh_aligner_coverage_ms(self.handle, C.byref(t), C.byref(w)) != 0:
-            raise ValueError("bmh_aligner_coverage_ms: " + _err(L))
-        return (float(t.value), int(w.value)) if windows else float(t.value)
-
-    def set_stats(self, opt=None) -> None:
-        """bmh_aligner_set_stats: the sorted runs that follow compute their statistics under `opt` (a BamStatsOpt; None: off; refused unless the output is sorted BAM)"""
-        L = load_library()
-        L.bmh_aligner_set_stats.argtypes = [C.c_void_p, C.POINTER(BamStatsOpt)]
-        if L.bmh_aligner_set_stats(self.handle, C.byref(opt) if opt is not None else None) != 0:
-            raise ValueError("bmh_aligner_set_stats: " + _err(L))
-
-    def stats(self) -> dict:
-        """bmh_aligner_stats: the statistics of the last sorted run that computed them, as bam_stats returns them"""
-        L = load_library()
-        L.bmh_aligner_stats.argtypes = [C.c_void_p, C.POINTER(BamStats)]
-        st = BamStats()
-        if L.bmh_aligner_stats(self.handle, C.byref(st)) != 0:
-            raise ValueError("bmh_aligner_stats: " + _err(L))
-        return stats_dict(L, st)
-
-    def stats_ms(self, windows: bool = False):
-        """bmh_aligner_stats_ms: the device milliseconds the last such run's windows spent in the statistics kernel; windows=True: (milliseconds, windows timed)"""
-        L = load_library()
-        L.bmh_aligner_stats_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-        t, w = C.c_double(0), C.c_uint64(0)
-        if L.bmh_aligner_stats_ms(self.handle, C.byref(t), C.byref(w)) != 0:
-            raise ValueError("bmh_aligner_stats_ms: " + _err(L))
-        return (float(t.value), int(w.value)) if windows else float(t.value)
-
-    def markdup_counts(self) -> dict:
-        """bmh_aligner_markdup_counts: the counts of the last run that marked duplicates, by MARKDUP_COUNTS' names"""
-        L = load_library()
-        L.bmh_aligner_markdup_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        c = (C.c_uint64 * 8)()
-        if L.bmh_aligner_markdup_counts(self.handle, c) != 0:
-            raise ValueError("bmh_aligner_markdup_counts: " + _err(L))
-        return dict(zip(MARKDUP_COUNTS, (int(v) for v in c)))
-
-    def markdup_library_counts(self, lib: int) -> dict:
-        """bmh_aligner_markdup_library_counts: library `lib`'s counts of the last marked run over read groups"""
-        L = load_library()
-        L.bmh_aligner_markdup_library_counts.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
-        c = (C.c_uint64 * 8)()
-        if L.bmh_aligner_markdup_library_counts(self.handle, int(lib), c) != 0:
-            raise ValueError("bmh_aligner_markdup_library_counts: " + _err(L))
-        return dict(zip(MARKDUP_COUNTS, (int(v) for v in c)))
-
-    def markdup_times(self) -> dict:
-        """bmh_aligner_markdup_times: where the last marked run's extra time went -- the decision and the windows' flag steps in ms, the bytes of ordinals and entries
-        that came down with the batches"""
-        L = load_library()
-        L.bmh_aligner_markdup_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-        t = (C.c_double * 3)()
-        if L.bmh_aligner_markdup_times(self.handle, t) != 0:
-            raise ValueError("bmh_aligner_markdup_times: " + _err(L))
-        return dict(decision_ms=t[0], window_flags_ms=t[1], entries_d2h_bytes=int(t[2]))
+        L.bmh_aligner_sorted_results.argtypes = [C.c_void_p, C.POINTER(SortedResults), C.c_uint32]
+        mask = 0
+        for nm in need:
+            mask |= SORTED_PARTS[nm]
+        res = SortedResults()
+        if L.bmh_aligner_sorted_results(self.handle, C.byref(res), mask) != 0:
+            raise ValueError("bmh_aligner_sorted_results: " + _err(L))
+        has = {nm for nm, bit in SORTED_PARTS.items() if res.parts & bit}
+        n_lib = int(res.n_libraries)
+        mc, cov, st = MarkdupCounts(), Coverage(), BamStats()
+        rows, opt_rows = ((C.c_uint64 * (k * max(n_lib, 1)))() for k in (8, 3))
+        mc.lib_counts, mc.lib_optical = C.cast(rows, _u64p), C.cast(opt_rows, _u64p)
+        res = SortedResults(C.pointer(mc) if "markdup" in has else None, C.pointer(cov) if "coverage" in has else None, C.pointer(st) if "stats" in has else None)
+        if L.bmh_aligner_sorted_results(self.handle, C.byref(res), mask) != 0:
+            raise ValueError("bmh_aligner_sorted_results: " + _err(L))
+        out = {}
+        if "markdup" in has:
+            out["markdup_counts"] = dict(zip(MARKDUP_COUNTS, (int(v) for v in mc.counts)))
+            out["markdup_library_counts"] = [dict(zip(MARKDUP_COUNTS, (int(v) for v in rows[8 * k:8 * k + 8]))) for k in range(n_lib)]
+            out["markdup_times"] = dict(decision_ms=res.markdup_ms[0], window_flags_ms=res.markdup_ms[1], entries_d2h_bytes=int(res.markdup_d2h_bytes))
+        if "barcode" in has:
+            out["markdup_barcode_counts"] = {"templates_without_barcode": int(mc.no_barcode)}
+        if "grouped" in has:
+            out["markdup_barcode_group_counts"] = dict(zip(BARCODE_GROUP_COUNTS, (int(v) for v in mc.grouped)))
+        if "optical" in has:
+            out["markdup_optical_counts"] = dict(zip(OPTICAL_COUNTS, (int(v) for v in mc.optical)))
+            out["markdup_library_optical_counts"] = [dict(zip(OPTICAL_COUNTS, (int(v) for v in opt_rows[3 * k:3 * k + 3]))) for k in range(n_lib)]
+            out["markdup_optical_ms"] = float(res.optical_ms)
+        if "coverage" in has:
+            out["coverage"], out["coverage_ms"] = coverage_dict(L, cov), (float(res.coverage_ms), int(res.coverage_windows))
+        if "stats" in has:
+            out["stats"], out["stats_ms"] = stats_dict(L, st), (float(res.stats_ms), int(res.stats_windows))
+        return out
 
     def sort_index(self, base_offset: int) -> bytes:
-        """bmh_aligner_sort_index: the .bai (or, for a run under set_index_format("csi"), .csi) bytes of the last sorted run; base_offset: the bytes written before the sink's first (the header members)"""
+        """bmh_aligner_sort_index: the .bai (or, for a run under index_format="csi", .csi) bytes of the last sorted run; base_offset: the bytes written before the sink's first (the header members)"""
         L = load_library()
         L.bmh_aligner_sort_index.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), _u64p]
         L.bmh_free.argtypes = [C.c_void_p]

@@ -52,11 +52,10 @@ struct aligner_t {
 	std::string rg_id;             // the aligner's own copy of popt->rg_id (po.rg_id points into it): the caller's string need not outlive the call that created the aligner
 	uint32_t max_qlen = 768;       // the extension cap of the chain workspaces (bmh_aligner_set_max_qlen)
 	bmh_reseed_opt_t rs = {0, 1.5f, 10, 20};   // the seeding rounds (bmh_aligner_set_reseed; enable 0: the first round only)
-	bool markdup = false;                      // sorted BAM output: flag 0x400 on the records of duplicate templates (bmh_aligner_set_markdup)
-	// ... and what the marking is made under (csrc/bam_dup.h).  Its barcode source, edits and optical distance are set through bmh_aligner_set_markdup_barcode, _barcode_edits
-	// and _optical, which refuse without markdup, and go where markdup goes: plan.barcode(), .grouping() and .optical() are NULL in a run that marks nothing.  Its table
-	// is the run's read groups (below), marked or not
-	bdp_plan_t plan;
+	// what the sorted runs that follow are made under, checked (bmh_aligner_set_sorted_output; csrc/bam_sort.h): the level, the window, the index of a file without
+	// records, and the plans of marking, coverage and statistics -- all off unless out_fmt is BMH_OUT_BAM_SORTED.  next.P's table is the run's read groups (below),
+	// marked or not; where the counts go is decided when a run begins
+	bsr_out_t next;
 	int out_fmt = BMH_OUT_SAM, out_level = 1;  // what the sink receives (bmh_aligner_set_output): the records' text, or BGZF members of BAM records
 	std::vector<char> ctg_blob; std::vector<uint32_t> ctg_noff;      // the contig table as the BAM converter takes it
 	// a run over read groups (bmh_aligner_run_groups), while it lasts: every group's ID (a batch's records carry its group's) and the table duplicate marking reads;
@@ -66,7 +65,7 @@ struct aligner_t {
 	// a run that keeps its input's read groups (bmh_aligner_set_keep_rg), while it lasts: the same table holds the header's @RG lines, but the group is a property of
 	// a read (rs.groups), not of a batch -- a batch's group stays -1 and its records take their IDs from the table by the read's index
 	bool per_read = false;
-	bmh_read_groups_t read_groups(const uint32_t *read_group) const { return {read_group, plan.table.ids.data(), plan.table.id_off.data(), (uint32_t)plan.table.lib.size()}; }
+	bmh_read_groups_t read_groups(const uint32_t *read_group) const { return {read_group, next.P.table.ids.data(), next.P.table.id_off.data(), (uint32_t)next.P.table.lib.size()}; }
 };
 
 }   // namespace
@@ -248,7 +247,7 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 	d.d_h_rec = paired ? Ln.d_hrec.p : nullptr; d.d_unflag = paired ? Ln.d_unflag.p : nullptr;
 	if (Ln.has_quals) d.d_quals = Ln.d_quals.p;
 	if (Ln.has_comments) { d.d_comments = Ln.d_comments.p; d.d_comment_off = Ln.d_comment_off.p; }
-	if (Ln.has_rgrp) { d.d_read_group = Ln.d_rgrp.p; d.d_rg_ids = Ln.d_rg_ids.p; d.d_rg_id_off = Ln.d_rg_off.p; d.n_rg = (uint32_t)A.plan.table.lib.size(); }
+	if (Ln.has_rgrp) { d.d_read_group = Ln.d_rgrp.p; d.d_rg_ids = Ln.d_rg_ids.p; d.d_rg_id_off = Ln.d_rg_off.p; d.n_rg = (uint32_t)A.next.P.table.lib.size(); }
 	const size_t wb = bmh_sam_text_work(n);
 	RCK(Ln.d_work.need(wb)); RCK(Ln.d_text_off.need((size_t)n + 2));
 	const int64_t total = bmh_sam_text_sizes(&po, &d, Ln.d_text_off.p, Ln.d_work.p, Ln.d_work.cap, Ln.st);
@@ -272,18 +271,18 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 			const uint32_t nrec = bo.n_records;
 			// duplicate marking: on the records in the writer's order, before the sort -- heads, their scan, one entry per template; the ordinals follow the records
 			const uint32_t *d_tpl = nullptr, *d_info = nullptr, *d_stpl = nullptr, *d_lib3 = nullptr; const bdp_entry_t *d_e = nullptr; const bdp_loc_t *d_l = nullptr; const uint64_t *d_b = nullptr;
-			const bdp_bc_t *bc = A.plan.barcode(); const bool optical = A.plan.optical() != nullptr, barcode = bc != nullptr;
+			const bdp_bc_t *bc = A.next.P.barcode(); const bool optical = A.next.P.optical() != nullptr, barcode = bc != nullptr;
 			const uint32_t tmax = paired ? n / 2 : n;                   // the batch's templates: every read or pair leaves at least one record, so no more entries than this come down
-			if (A.markdup) {
+			if (A.next.markdup) {
 				if (!Ln.bdp && !(Ln.bdp = bdp_dev_create())) return BMH_ENOMEM;
-				if (Ln.groups_serial != A.groups_serial) { RCK(bdp_dev_set_groups(Ln.bdp, &A.plan.table, Ln.st)); Ln.groups_serial = A.groups_serial; }
+				if (Ln.groups_serial != A.groups_serial) { RCK(bdp_dev_set_groups(Ln.bdp, &A.next.P.table, Ln.st)); Ln.groups_serial = A.groups_serial; }
 				RCK(bdp_batch_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &d_tpl, &d_e, &d_info, optical ? &d_l : nullptr, bc, barcode ? &d_b : nullptr));
 				RCK(R.stpl.need((size_t)nrec + 1)); RCK(R.dup_e.need((size_t)std::min(nrec, tmax) + 1));
 				if (optical) RCK(R.dup_l.need((size_t)std::min(nrec, tmax) + 1));
 				if (barcode) RCK(R.dup_b.need((size_t)std::min(nrec, tmax) + 1));
 				if (A.per_read) {                                     // a batch of several libraries: its counts per library, from the entries' library bytes
-					RCK(bdp_batch_lib_counts_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, A.plan.table.n_lib, Ln.st, &d_lib3));
-					RCK(R.lib3.need(3 * (size_t)A.plan.table.n_lib));
+					RCK(bdp_batch_lib_counts_device(Ln.bdp, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, A.next.P.table.n_lib, Ln.st, &d_lib3));
+					RCK(R.lib3.need(3 * (size_t)A.next.P.table.n_lib));
 				}
 			}
 			RCK(bsr_sort_run_device(Ln.bsr, bo.d_bam, (const uint64_t *)Ln.bam->off.p, nrec, bo.bam_bytes, Ln.st, &ds, &dk, &dso, d_tpl, &d_stpl));
@@ -293,23 +292,23 @@ int text_on_device(const aligner_t &A, lane_t &Ln, const bmh_post_opt_t &po, con
 			if (nrec) HIPCK(hipMemcpyAsync(R.skeys.p, dk, 8 * (size_t)nrec, hipMemcpyDeviceToHost, Ln.st));
 			HIPCK(hipMemcpyAsync(R.soff.p, dso, 8 * ((size_t)nrec + 1), hipMemcpyDeviceToHost, Ln.st));
 			R.dup_d2h = 0;
-			if (A.markdup) {                                          // (the count comes down with them and is checked below)
+			if (A.next.markdup) {                                          // (the count comes down with them and is checked below)
 				const size_t ne = std::min(nrec, tmax);
 				if (nrec) HIPCK(hipMemcpyAsync(R.stpl.p, d_stpl, 4 * (size_t)nrec, hipMemcpyDeviceToHost, Ln.st));
 				if (ne) HIPCK(hipMemcpyAsync(R.dup_e.p, d_e, sizeof(bdp_entry_t) * ne, hipMemcpyDeviceToHost, Ln.st));
 				if (ne && optical) HIPCK(hipMemcpyAsync(R.dup_l.p, d_l, sizeof(bdp_loc_t) * ne, hipMemcpyDeviceToHost, Ln.st));
 				if (ne && barcode) HIPCK(hipMemcpyAsync(R.dup_b.p, d_b, 8 * ne, hipMemcpyDeviceToHost, Ln.st));
-				const size_t ni = A.plan.table.empty() && !barcode ? 16 : 4 * bdp_info_words(bc);      // (with read groups: the words of a template without a known group; with barcodes: of one whose tags are refused)
+				const size_t ni = A.next.P.table.empty() && !barcode ? 16 : 4 * bdp_info_words(bc);      // (with read groups: the words of a template without a known group; with barcodes: of one whose tags are refused)
 				HIPCK(hipMemcpyAsync(R.dup_info, d_info, ni, hipMemcpyDeviceToHost, Ln.st));
-				if (d_lib3) HIPCK(hipMemcpyAsync(R.lib3.p, d_lib3, 12 * (size_t)A.plan.table.n_lib, hipMemcpyDeviceToHost, Ln.st));
-				R.dup_d2h = 4ull * nrec + sizeof(bdp_entry_t) * ne + ni + (d_lib3 ? 12ull * A.plan.table.n_lib : 0) + (optical ? sizeof(bdp_loc_t) * ne : 0) + (barcode ? 8ull * ne : 0);
+				if (d_lib3) HIPCK(hipMemcpyAsync(R.lib3.p, d_lib3, 12 * (size_t)A.next.P.table.n_lib, hipMemcpyDeviceToHost, Ln.st));
+				R.dup_d2h = 4ull * nrec + sizeof(bdp_entry_t) * ne + ni + (d_lib3 ? 12ull * A.next.P.table.n_lib : 0) + (optical ? sizeof(bdp_loc_t) * ne : 0) + (barcode ? 8ull * ne : 0);
 				Ln.copy_bytes[1] += R.dup_d2h;
 			}
 			HIPCK(hipEventRecord(Ln.ev_c[3], Ln.st));
 			Ln.copy_bytes[1] += bo.bam_bytes + 16ull * nrec; Ln.d2h_marked = true;
 			HIPCK(hipStreamSynchronize(Ln.st));
-			if (A.markdup && nrec) {
-				RCK(bdp_batch_check(nrec, R.dup_info, !A.plan.table.empty(), "sorted BAM", barcode, barcode && bc->pack));
+			if (A.next.markdup && nrec) {
+				RCK(bdp_batch_check(nrec, R.dup_info, !A.next.P.table.empty(), "sorted BAM", barcode, barcode && bc->pack));
 				if (R.dup_info[0] == 0 || R.dup_info[0] > std::min(nrec, tmax)) { bmh_set_error("sorted BAM: internal error: %u templates among %u records", R.dup_info[0], nrec); return BMH_EINVAL; }
 			}
 			if (R.soff.p[nrec] != bo.bam_bytes) {                 // (the gather skips a record whose offsets lie outside the buffers: the scan of the sizes shows it)
@@ -614,9 +613,9 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 		if (!rs.groups) { bmh_set_error("bmh_aligner_run: internal error: a run that keeps read groups met a batch without them"); return BMH_EINVAL; }
 		if (text_dev) {
 			if (Ln.rg_serial != A.groups_serial) {
-				RCK(Ln.d_rg_ids.need(A.plan.table.ids.size() + 1)); RCK(Ln.d_rg_off.need(A.plan.table.id_off.size()));
-				HIPCK(hipMemcpyAsync(Ln.d_rg_ids.p, A.plan.table.ids.data(), A.plan.table.ids.size(), hipMemcpyHostToDevice, Ln.st));
-				HIPCK(hipMemcpyAsync(Ln.d_rg_off.p, A.plan.table.id_off.data(), 4 * A.plan.table.id_off.size(), hipMemcpyHostToDevice, Ln.st));
+				RCK(Ln.d_rg_ids.need(A.next.P.table.ids.size() + 1)); RCK(Ln.d_rg_off.need(A.next.P.table.id_off.size()));
+				HIPCK(hipMemcpyAsync(Ln.d_rg_ids.p, A.next.P.table.ids.data(), A.next.P.table.ids.size(), hipMemcpyHostToDevice, Ln.st));
+				HIPCK(hipMemcpyAsync(Ln.d_rg_off.p, A.next.P.table.id_off.data(), 4 * A.next.P.table.id_off.size(), hipMemcpyHostToDevice, Ln.st));
 				Ln.rg_serial = A.groups_serial;                       // (the aligner's table outlives the run's batches: the copy reads it in its own time)
 			}
 			RCK(Ln.d_rgrp.need(n + 1));
@@ -893,16 +892,10 @@ struct bmh_aligner {
 	uint64_t bam_pairs_bases = 0; int bam_pairs_lanes = 0;   // bmh_aligner_set_bam_pairs
 	bool keep_rg = false; bmh_rg_header_fn rg_header = nullptr; void *rg_user = nullptr;      // bmh_aligner_set_keep_rg
 	bool collate = false; uint64_t collate_mem = 0;                                            // bmh_aligner_set_collate
-	bsr_store_t store; bsr_index_t sort_ix; uint32_t sort_window = 0;      // sorted BAM output: the runs of the run in progress, the index of the last one, the window
-	int ix_format = BSR_IX_BAI, ix_shift = BSR_LIN_SHIFT;                  // bmh_aligner_set_index_format: the index of the sorted runs that follow
-	uint64_t dup_counts[BDP_N_COUNTS] = {0, 0, 0, 0, 0, 0, 0, 0}; bool dup_valid = false;      // duplicate marking: the counts of the last marked run
-	std::vector<uint64_t> lib_counts;                    // ... with read groups: the same eight per library (bmh_aligner_markdup_library_counts)
-	uint64_t opt_counts[BDP_OPT_N] = {0, 0, 0}; std::vector<uint64_t> lib_opt; bool opt_valid = false; double opt_ms = 0;      // ... with an optical distance: the three optical counts of the last such run, per library, and the step's ms
-	uint64_t grp_counts[BDP_GRP_N] = {0, 0, 0}; bool grp_valid = false;      // ... with barcode edits: the three grouping counts of the last such run
-	uint64_t no_barcode = 0; bool bc_valid = false;      // ... with barcodes: the templates without one in the last such run
-	double dup_times[3] = {0, 0, 0};                     // ... its decision and its windows' flag steps in ms, the bytes its batches' ordinals and entries took on their way down
-	bool stats_on = false; bst_plan_t stats_plan, stats_plan_last; bst_result_t stats_res; bool stats_valid = false; double stats_ms[2] = {0, 0};      // statistics (bmh_aligner_set_stats): as coverage's
-	bool cov_on = false; bcv_plan_t cov_plan, cov_plan_last; bcv_result_t cov_res; bool cov_valid = false; double cov_ms[2] = {0, 0};      // coverage (bmh_aligner_set_coverage): the plan of the runs that follow, the last such run's results and its steps' device ms and the windows timed
+	bsr_store_t store;                                   // sorted BAM output: the runs of the run in progress
+	// the last sorted run: what it was made under, its index and what it left (a.next as the run began, with its own places for the counts: the marking's record and
+	// its libraries' rows); valid: its file was written whole.  What it holds is read off out's plans (bsr_out_t::parts)
+	struct last_t { bsr_out_t out; bmh_markdup_counts_t counts = {}; std::vector<uint64_t> lib_counts, lib_opt; bool valid = false; } last;
 };
 
 bmh_aligner_t *bmh_aligner_create(const bmh_index_t *idx, const uint8_t *pac, int64_t l_pac, int n_contigs, const char *const *contig_names,
@@ -929,23 +922,35 @@ bmh_aligner_t *bmh_aligner_create(const bmh_index_t *idx, const uint8_t *pac, in
 	return h;
 }
 
+// the one setter of sorted output: everything is checked (bsr_out_make's order) before anything changes
+int bmh_aligner_set_sorted_output(bmh_aligner_t *h, const bmh_sorted_opt_t *opt)
+{
+	const char *fn = "bmh_aligner_set_sorted_output";
+	if (!h) { bmh_set_error("%s: null aligner", fn); return BMH_EINVAL; }
+	if (opt && opt->markdup && (opt->markdup->rg_ids || opt->markdup->rg_lib || opt->markdup->n_groups)) {
+		bmh_set_error("%s: an aligner's read groups come from bmh_aligner_run_groups or bmh_aligner_set_keep_rg, not from the marking options (rg_ids stays NULL)", fn); return BMH_EINVAL;
+	}
+	bmh_markdup_counts_t mc; bmh_coverage_t cv; bmh_bam_stats_t st;      // (the records the check asks for: a run has its own)
+	memset(&mc, 0, sizeof mc);
+	bmh_sorted_results_t res; memset(&res, 0, sizeof res);
+	res.markdup = &mc; res.coverage = &cv; res.stats = &st;
+	bsr_out_t J;
+	RCK(bsr_out_make(J, opt, h->a.n_contigs, h->a.len.data(), h->a.name_ptr.data(), &res, fn));
+	J.timed = true; J.P.table = h->a.next.P.table;
+	h->a.next = J; h->a.out_fmt = BMH_OUT_BAM_SORTED; h->a.out_level = J.level;
+	h->store.clear(); h->store.mem_bytes = opt && opt->sort_mem ? opt->sort_mem : 4ull << 30; h->store.tmp_dir = opt && opt->tmp_dir ? opt->tmp_dir : "";
+	h->last = bmh_aligner::last_t(); h->last.out.ix = J.ix; h->last.valid = true;      // (until a run is made: the index of a file without records, and no results)
+	return BMH_OK;
+}
+
 int bmh_aligner_set_output(bmh_aligner_t *h, int format, int level)
 {
 	if (!h) { bmh_set_error("bmh_aligner_set_output: null aligner"); return BMH_EINVAL; }
 	if (format != BMH_OUT_SAM && format != BMH_OUT_BAM && format != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_output: format %d (BMH_OUT_SAM, BMH_OUT_BAM or BMH_OUT_BAM_SORTED)", format); return BMH_EINVAL; }
 	if (format != BMH_OUT_SAM && level != 0 && level != 1) { bmh_set_error("bmh_aligner_set_output: level %d (0 or 1)", level); return BMH_EINVAL; }
-	if (format == BMH_OUT_BAM_SORTED) { h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), "sorted BAM output", h->ix_format, h->ix_shift)); }
-	if (format != BMH_OUT_BAM_SORTED) h->cov_on = h->stats_on = false;
-	if (format != BMH_OUT_BAM_SORTED) { h->a.markdup = false; h->a.plan.opt.distance = -1; h->a.plan.bc.mode = BDP_BC_OFF; h->a.plan.bc.pack = 0; }      // (duplicates are marked in sorted output only: the options go with the format)
-	h->a.out_fmt = format; h->a.out_level = level;
-	return BMH_OK;
-}
-
-int bmh_aligner_set_index_format(bmh_aligner_t *h, int index_format, int min_shift)
-{
-	if (!h) { bmh_set_error("bmh_aligner_set_index_format: null aligner"); return BMH_EINVAL; }
-	RCK(bsr_index_format_check(index_format, min_shift, "bmh_aligner_set_index_format"));
-	h->ix_format = index_format; h->ix_shift = index_format == BSR_IX_CSI ? min_shift : (int)BSR_LIN_SHIFT;
+	if (format == BMH_OUT_BAM_SORTED) { bmh_sorted_opt_t o; bmh_sorted_opt_default(&o); o.level = level; return bmh_aligner_set_sorted_output(h, &o); }
+	bsr_out_t off; off.P.table = h->a.next.P.table;                      // (the options of sorted output go with the format)
+	h->a.next = off; h->a.out_fmt = format; h->a.out_level = level;
 	return BMH_OK;
 }
 
@@ -965,189 +970,35 @@ int bmh_aligner_set_reseed(bmh_aligner_t *h, const bmh_reseed_opt_t *opt)
 	return BMH_OK;
 }
 
-int bmh_aligner_set_sort(bmh_aligner_t *h, uint64_t mem_bytes, const char *tmp_dir, uint32_t window_records)
+int bmh_aligner_sorted_results(bmh_aligner_t *h, bmh_sorted_results_t *out, uint32_t need)
 {
-	if (!h) { bmh_set_error("bmh_aligner_set_sort: null aligner"); return BMH_EINVAL; }
-	h->store.mem_bytes = mem_bytes ? mem_bytes : 4ull << 30; h->store.tmp_dir = tmp_dir ? tmp_dir : ""; h->sort_window = window_records;
-	return BMH_OK;
-}
-
-int bmh_aligner_set_markdup(bmh_aligner_t *h, int on)
-{
-	if (!h) { bmh_set_error("bmh_aligner_set_markdup: null aligner"); return BMH_EINVAL; }
-	if (on && h->a.out_fmt != BMH_OUT_BAM_SORTED) { bmh_set_error("bmh_aligner_set_markdup: duplicates are marked in sorted output (bmh_aligner_set_output with BMH_OUT_BAM_SORTED comes first)"); return BMH_EINVAL; }
-	if (on) RCK(bsr_markdup_contigs(h->a.n_contigs, h->a.len.data(), h->a.name_ptr.data(), "bmh_aligner_set_markdup"));      // (only a CSI run can hold such a contig)
-	h->a.markdup = on != 0;
-	if (!on) { h->a.plan.opt.distance = -1; h->a.plan.bc.mode = BDP_BC_OFF; h->a.plan.bc.pack = 0; }
-	return BMH_OK;
-}
-
-int bmh_aligner_set_coverage(bmh_aligner_t *h, const bmh_coverage_opt_t *opt)
-{
-	const char *fn = "bmh_aligner_set_coverage";
-	if (!h) { bmh_set_error("%s: null aligner", fn); return BMH_EINVAL; }
-	if (!opt) { h->cov_on = false; return BMH_OK; }
-	if (h->a.out_fmt != BMH_OUT_BAM_SORTED) { bmh_set_error("%s: coverage is computed while sorted output is written (bmh_aligner_set_output with BMH_OUT_BAM_SORTED comes first)", fn); return BMH_EINVAL; }
-	bcv_plan_t P;
-	RCK(bcv_plan_make(P, opt->min_mapq, opt->deletions, opt->bin, opt->tile, h->a.n_contigs, h->a.len.data(), fn));
-	h->cov_plan = P; h->cov_on = true;
-	return BMH_OK;
-}
-
-int bmh_aligner_coverage(bmh_aligner_t *h, bmh_coverage_t *out)
-{
-	const char *fn = "bmh_aligner_coverage";
+	const char *fn = "bmh_aligner_sorted_results";
+	static const struct { uint32_t part; const char *did; } parts[] = {{BMH_SORTED_MARKDUP, "marked duplicates"}, {BMH_SORTED_OPTICAL, "counted optical duplicates"}, {BMH_SORTED_BARCODE, "compared barcodes"},
+	                                                                   {BMH_SORTED_GROUPED, "grouped barcodes by edits"}, {BMH_SORTED_COVERAGE, "computed coverage"}, {BMH_SORTED_STATS, "computed statistics"}};
 	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (!h->cov_valid) { bmh_set_error("%s: no run has computed coverage (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
-	return bcv_export(h->cov_plan_last, h->cov_res, out, fn);
-}
-
-int bmh_aligner_coverage_ms(bmh_aligner_t *h, double *out, uint64_t *windows)
-{
-	const char *fn = "bmh_aligner_coverage_ms";
-	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (!h->cov_valid) { bmh_set_error("%s: no run has computed coverage (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
-	*out = h->cov_ms[0];
-	if (windows) *windows = (uint64_t)h->cov_ms[1];
-	return BMH_OK;
-}
-
-int bmh_aligner_set_stats(bmh_aligner_t *h, const bmh_bam_stats_opt_t *opt)
-{
-	const char *fn = "bmh_aligner_set_stats";
-	if (!h) { bmh_set_error("%s: null aligner", fn); return BMH_EINVAL; }
-	if (!opt) { h->stats_on = false; return BMH_OK; }
-	if (h->a.out_fmt != BMH_OUT_BAM_SORTED) { bmh_set_error("%s: the statistics are computed while sorted output is written (bmh_aligner_set_output with BMH_OUT_BAM_SORTED comes first)", fn); return BMH_EINVAL; }
-	bst_plan_t P;
-	RCK(bst_plan_make(P, opt->insert_cap, h->a.n_contigs, fn));
-	h->stats_plan = P; h->stats_on = true;
-	return BMH_OK;
-}
-
-int bmh_aligner_stats(bmh_aligner_t *h, bmh_bam_stats_t *out)
-{
-	const char *fn = "bmh_aligner_stats";
-	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (!h->stats_valid) { bmh_set_error("%s: no run has computed statistics (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
-	return bst_export(h->stats_plan_last, h->stats_res, out, fn);
-}
-
-int bmh_aligner_stats_ms(bmh_aligner_t *h, double *out, uint64_t *windows)
-{
-	const char *fn = "bmh_aligner_stats_ms";
-	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (!h->stats_valid) { bmh_set_error("%s: no run has computed statistics (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
-	*out = h->stats_ms[0];
-	if (windows) *windows = (uint64_t)h->stats_ms[1];
-	return BMH_OK;
-}
-
-int bmh_aligner_set_markdup_barcode(bmh_aligner_t *h, int mode, const char *tag)
-{
-	const char *fn = "bmh_aligner_set_markdup_barcode";
-	if (!h) { bmh_set_error("%s: null aligner", fn); return BMH_EINVAL; }
-	if (mode == BDP_BC_OFF) { h->a.plan.bc.mode = BDP_BC_OFF; h->a.plan.bc.pack = 0; return BMH_OK; }
-	if (!h->a.markdup) { bmh_set_error("%s: barcodes are compared where duplicates are marked (bmh_aligner_set_markdup comes first)", fn); return BMH_EINVAL; }
-	bdp_bc_t bc;
-	RCK(bdp_barcode_check(mode, tag, fn, &bc));
-	h->a.plan.bc = bc;
-	return BMH_OK;
-}
-
-int bmh_aligner_set_markdup_barcode_edits(bmh_aligner_t *h, int n)
-{
-	const char *fn = "bmh_aligner_set_markdup_barcode_edits";
-	if (!h) { bmh_set_error("%s: null aligner", fn); return BMH_EINVAL; }
-	if (n == -1) { h->a.plan.bc.pack = 0; return BMH_OK; }
-	if (!h->a.markdup) { bmh_set_error("%s: barcodes are grouped where duplicates are marked (bmh_aligner_set_markdup comes first)", fn); return BMH_EINVAL; }
-	bdp_bc_t bc = h->a.plan.bc;
-	RCK(bdp_group_check(n, 0, fn, &bc));                              // (a source comes first: bmh_aligner_set_markdup_barcode)
-	h->a.plan.bc = bc; h->a.plan.grp.edits = (uint32_t)n;
-	return BMH_OK;
-}
-
-int bmh_aligner_markdup_barcode_group_counts(bmh_aligner_t *h, uint64_t out[3])
-{
-	const char *fn = "bmh_aligner_markdup_barcode_group_counts";
-	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (!h->dup_valid || !h->grp_valid) { bmh_set_error("%s: no run has grouped barcodes by edits (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
-	for (int k = 0; k < BDP_GRP_N; ++k) out[k] = h->grp_counts[k];
-	return BMH_OK;
-}
-
-int bmh_aligner_markdup_barcode_counts(bmh_aligner_t *h, uint64_t out[1])
-{
-	const char *fn = "bmh_aligner_markdup_barcode_counts";
-	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (!h->dup_valid || !h->bc_valid) { bmh_set_error("%s: no run has compared barcodes (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
-	out[0] = h->no_barcode;
-	return BMH_OK;
-}
-
-int bmh_aligner_set_markdup_optical(bmh_aligner_t *h, int64_t distance)
-{
-	const char *fn = "bmh_aligner_set_markdup_optical";
-	if (!h) { bmh_set_error("%s: null aligner", fn); return BMH_EINVAL; }
-	if (distance == -1) { h->a.plan.opt.distance = -1; return BMH_OK; }
-	if (!h->a.markdup) { bmh_set_error("%s: optical duplicates are counted where duplicates are marked (bmh_aligner_set_markdup comes first)", fn); return BMH_EINVAL; }
-	RCK(bdp_optical_check(distance, 0, fn));
-	h->a.plan.opt.distance = distance;
-	return BMH_OK;
-}
-
-int bmh_aligner_markdup_optical_counts(bmh_aligner_t *h, int lib, uint64_t out[3])
-{
-	const char *fn = "bmh_aligner_markdup_optical_counts";
-	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (!h->dup_valid || !h->opt_valid) { bmh_set_error("%s: no run has counted optical duplicates (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
-	if (lib < -1 || (lib >= 0 && (size_t)lib >= h->lib_opt.size() / BDP_OPT_N)) { bmh_set_error("%s: library %d: the last such run had %zu (a run without read groups has none; -1: the total)", fn, lib, h->lib_opt.size() / BDP_OPT_N); return BMH_EINVAL; }
-	for (int k = 0; k < BDP_OPT_N; ++k) out[k] = lib < 0 ? h->opt_counts[k] : h->lib_opt[(size_t)BDP_OPT_N * (size_t)lib + k];
-	return BMH_OK;
-}
-
-int bmh_aligner_markdup_optical_ms(bmh_aligner_t *h, double *out)
-{
-	const char *fn = "bmh_aligner_markdup_optical_ms";
-	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (!h->dup_valid || !h->opt_valid) { bmh_set_error("%s: no run has counted optical duplicates (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
-	*out = h->opt_ms;
-	return BMH_OK;
-}
-
-int bmh_aligner_markdup_counts(bmh_aligner_t *h, uint64_t out[8])
-{
-	if (!h || !out) { bmh_set_error("bmh_aligner_markdup_counts: null argument"); return BMH_EINVAL; }
-	if (!h->dup_valid) { bmh_set_error("bmh_aligner_markdup_counts: no run has marked duplicates (or the last one failed before its file was complete)"); return BMH_EINVAL; }
-	for (int k = 0; k < BDP_N_COUNTS; ++k) out[k] = h->dup_counts[k];
-	return BMH_OK;
-}
-
-int bmh_aligner_markdup_library_counts(bmh_aligner_t *h, int lib, uint64_t out[8])
-{
-	const char *fn = "bmh_aligner_markdup_library_counts";
-	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	if (!h->dup_valid) { bmh_set_error("%s: no run has marked duplicates (or the last one failed before its file was complete)", fn); return BMH_EINVAL; }
-	if (lib < 0 || (size_t)lib >= h->lib_counts.size() / BDP_N_COUNTS) { bmh_set_error("%s: library %d: the last marked run had %zu (a run without read groups has none)", fn, lib, h->lib_counts.size() / BDP_N_COUNTS); return BMH_EINVAL; }
-	for (int k = 0; k < BDP_N_COUNTS; ++k) out[k] = h->lib_counts[(size_t)BDP_N_COUNTS * (size_t)lib + k];
-	return BMH_OK;
-}
-
-int bmh_aligner_markdup_times(bmh_aligner_t *h, double out[3])
-{
-	if (!h || !out) { bmh_set_error("bmh_aligner_markdup_times: null argument"); return BMH_EINVAL; }
-	if (!h->dup_valid) { bmh_set_error("bmh_aligner_markdup_times: no run has marked duplicates (or the last one failed before its file was complete)"); return BMH_EINVAL; }
-	for (int k = 0; k < 3; ++k) out[k] = h->dup_times[k];
-	return BMH_OK;
+	const bmh_aligner::last_t &T = h->last;
+	const uint32_t have = T.valid ? T.out.parts() : 0;
+	need |= (out->markdup ? BMH_SORTED_MARKDUP : 0u) | (out->coverage ? BMH_SORTED_COVERAGE : 0u) | (out->stats ? BMH_SORTED_STATS : 0u);
+	for (const auto &p : parts)
+		if (need & ~have & p.part) { bmh_set_error("%s: no run has %s (or the last one failed before its file was complete)", fn, p.did); return BMH_EINVAL; }
+	bsr_out_t none;
+	if (bmh_markdup_counts_t *c = out->markdup) {
+		memcpy(c->counts, T.counts.counts, sizeof c->counts); memcpy(c->optical, T.counts.optical, sizeof c->optical); memcpy(c->grouped, T.counts.grouped, sizeof c->grouped);
+		c->no_barcode = T.counts.no_barcode;
+		if (c->lib_counts && !T.lib_counts.empty()) memcpy(c->lib_counts, T.lib_counts.data(), 8 * T.lib_counts.size());
+		if (c->lib_optical && !T.lib_opt.empty()) memcpy(c->lib_optical, T.lib_opt.data(), 8 * T.lib_opt.size());
+	}
+	return bsr_out_export(T.valid ? T.out : none, out, fn);
 }
 
 int bmh_aligner_sort_index(bmh_aligner_t *h, uint64_t base_offset, uint8_t **bai, uint64_t *bai_bytes)
 {
 	if (!h || !bai || !bai_bytes) { bmh_set_error("bmh_aligner_sort_index: null argument"); return BMH_EINVAL; }
 	*bai = nullptr; *bai_bytes = 0;
-	if (h->sort_ix.lin.empty()) { bmh_set_error("bmh_aligner_sort_index: no sorted run has been made (bmh_aligner_set_output with BMH_OUT_BAM_SORTED comes first)"); return BMH_EINVAL; }
-	if (!h->sort_ix.valid) { bmh_set_error("bmh_aligner_sort_index: the last sorted run failed before its file was complete: there is no index of it"); return BMH_EINVAL; }
+	if (h->last.out.ix.lin.empty()) { bmh_set_error("bmh_aligner_sort_index: no sorted run has been made (bmh_aligner_set_output with BMH_OUT_BAM_SORTED comes first)"); return BMH_EINVAL; }
+	if (!h->last.valid) { bmh_set_error("bmh_aligner_sort_index: the last sorted run failed before its file was complete: there is no index of it"); return BMH_EINVAL; }
 	std::string s;
-	RCK(h->sort_ix.bytes(base_offset, s));                    // (.bai or .csi: the format the run was made under)
+	RCK(h->last.out.ix.bytes(base_offset, s));                    // (.bai or .csi: the format the run was made under)
 	uint8_t *o = (uint8_t *)malloc(s.size() + 1);
 	if (!o) { bmh_set_error("bmh_aligner_sort_index: out of memory"); return BMH_ENOMEM; }
 	memcpy(o, s.data(), s.size());
@@ -1184,21 +1035,32 @@ struct batch_src_t {
 struct out_stage_t {
 	bmh_aligner *h; const int fmt; bmh_sam_sink_t sink; void *user; int n_threads; const char *fn;
 	uint64_t n_bytes = 0;                                           // handed to the sink so far
-	int lib_of(int group) const { return group >= 0 && (size_t)group < h->a.plan.table.lib.size() ? (int)h->a.plan.table.lib[(size_t)group] : -1; }
+	int lib_of(int group) const { return group >= 0 && (size_t)group < h->a.next.P.table.lib.size() ? (int)h->a.next.P.table.lib[(size_t)group] : -1; }
 	int emit(const void *p, size_t n) { if (n && sink(user, (const char *)p, n) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; } n_bytes += n; return BMH_OK; }
-	// (the index is valid again once the merge has written the whole file)
-	int begin() { if (fmt == BMH_OUT_BAM_SORTED) { h->cov_valid = false; h->cov_ms[0] = h->cov_ms[1] = 0; h->stats_valid = false; h->stats_ms[0] = h->stats_ms[1] = 0; h->dup_valid = false; h->opt_valid = false; h->bc_valid = false; h->opt_ms = 0; h->dup_times[0] = h->dup_times[1] = h->dup_times[2] = 0; h->store.clear(); RCK(h->sort_ix.init(h->a.n_contigs, h->a.len.data(), fn, h->ix_format, h->ix_shift)); h->sort_ix.valid = false;
-		if (h->a.markdup) RCK(bsr_markdup_contigs(h->a.n_contigs, h->a.len.data(), h->a.name_ptr.data(), fn)); } return BMH_OK; }
+	// a sorted run begins: `last` becomes this run's -- the aligner's plan as it stands (the run's read groups are in it), an index without records, nothing valid --
+	// and the places of its counts are its own
+	int begin()
+	{
+		if (fmt != BMH_OUT_BAM_SORTED) return BMH_OK;
+		h->store.clear();
+		h->last = {h->a.next};
+		bmh_aligner::last_t &T = h->last; bdp_plan_t &P = T.out.P;
+		const uint32_t n_lib = T.out.markdup ? P.table.n_lib : 0;
+		T.lib_counts.assign((size_t)BDP_N_COUNTS * n_lib, 0); T.lib_opt.assign(P.optical() ? (size_t)BDP_OPT_N * n_lib : 0, 0);
+		T.out.dup_counts = T.counts.counts; P.lib_counts = n_lib ? T.lib_counts.data() : nullptr; P.no_barcode = &T.counts.no_barcode;
+		P.opt.out = T.counts.optical; P.opt.lib_out = n_lib ? T.lib_opt.data() : nullptr; P.grp.out = T.counts.grouped; P.grp.lib_out = nullptr;
+		return BMH_OK;
+	}
 	int device_batch(const result_t &R)
 	{
 		if (fmt != BMH_OUT_BAM_SORTED) return emit(R.text.p, (size_t)R.text_len);
 		if (!R.n_rec) return BMH_OK;
 		bsr_dup_t bd = {R.stpl.p, R.dup_e.p, R.dup_info[0], R.dup_info[2], R.dup_info[3], lib_of(R.group)};
-		if (h->a.markdup && h->a.per_read) { bd.lib3 = R.lib3.p; bd.n_lib3 = h->a.plan.table.n_lib; }
-		if (h->a.plan.optical()) bd.locs = R.dup_l.p;
-		if (h->a.plan.barcode()) bd.bcs = R.dup_b.p;
-		if (h->a.markdup) h->dup_times[2] += (double)R.dup_d2h;
-		return h->store.append((const uint8_t *)R.text.p, R.text_len, R.skeys.p, R.soff.p, R.n_rec, h->a.markdup ? &bd : nullptr);      // a sorted run: kept until the end of the input
+		if (h->a.next.markdup && h->a.per_read) { bd.lib3 = R.lib3.p; bd.n_lib3 = h->a.next.P.table.n_lib; }
+		if (h->a.next.P.optical()) bd.locs = R.dup_l.p;
+		if (h->a.next.P.barcode()) bd.bcs = R.dup_b.p;
+		if (h->a.next.markdup) h->last.out.dup_ms[2] += (double)R.dup_d2h;
+		return h->store.append((const uint8_t *)R.text.p, R.text_len, R.skeys.p, R.soff.p, R.n_rec, h->a.next.markdup ? &bd : nullptr);      // a sorted run: kept until the end of the input
 	}
 	int host_batch(const std::vector<std::string> &parts, int group)
 	{
@@ -1225,22 +1087,22 @@ struct out_stage_t {
 				srt.reserve((size_t)bb + 1);
 				for (uint32_t i : ord) { srt.insert(srt.end(), bam + off[i], bam + off[i + 1]); soff.push_back(srt.size()); }
 				std::vector<uint32_t> tpl, stpl; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> locs; std::vector<uint64_t> bcs; uint64_t info[2] = {0, 0};
-				const bool optical = A.plan.optical() != nullptr, barcode = A.plan.barcode() != nullptr;
-				if (A.markdup) {                                   // the host forms of the device's heads, ordinals and entries
-					rc = bdp_entries_host(bam, off.data(), (uint32_t)ord.size(), tpl, E, info, fn, A.plan, optical ? &locs : nullptr, barcode ? &bcs : nullptr);
+				const bool optical = A.next.P.optical() != nullptr, barcode = A.next.P.barcode() != nullptr;
+				if (A.next.markdup) {                                   // the host forms of the device's heads, ordinals and entries
+					rc = bdp_entries_host(bam, off.data(), (uint32_t)ord.size(), tpl, E, info, fn, A.next.P, optical ? &locs : nullptr, barcode ? &bcs : nullptr);
 					for (uint32_t i : ord) stpl.push_back(tpl[i]);
 				}
 				bsr_dup_t bd = {stpl.data(), E.data(), (uint32_t)E.size(), info[0], info[1], lib_of(group)};
 				if (optical) bd.locs = locs.data();
 				if (barcode) bd.bcs = bcs.data();
 				std::vector<uint32_t> lib3;
-				if (rc == BMH_OK && A.markdup && A.per_read) {        // the host form of bdp_batch_lib_counts_device
-					std::vector<uint64_t> lc((size_t)BDP_N_COUNTS * A.plan.table.n_lib, 0);
-					bdp_lib_tally_host(bam, off.data(), (uint32_t)ord.size(), tpl.data(), E.data(), E.size(), A.plan.table.n_lib, lc.data());
-					for (uint32_t l = 0; l < A.plan.table.n_lib; ++l) for (int k = 0; k < 3; ++k) lib3.push_back((uint32_t)lc[(size_t)BDP_N_COUNTS * l + BDP_SECSUP + k]);
-					bd.lib3 = lib3.data(); bd.n_lib3 = A.plan.table.n_lib;
+				if (rc == BMH_OK && A.next.markdup && A.per_read) {        // the host form of bdp_batch_lib_counts_device
+					std::vector<uint64_t> lc((size_t)BDP_N_COUNTS * A.next.P.table.n_lib, 0);
+					bdp_lib_tally_host(bam, off.data(), (uint32_t)ord.size(), tpl.data(), E.data(), E.size(), A.next.P.table.n_lib, lc.data());
+					for (uint32_t l = 0; l < A.next.P.table.n_lib; ++l) for (int k = 0; k < 3; ++k) lib3.push_back((uint32_t)lc[(size_t)BDP_N_COUNTS * l + BDP_SECSUP + k]);
+					bd.lib3 = lib3.data(); bd.n_lib3 = A.next.P.table.n_lib;
 				}
-				if (rc == BMH_OK && !ord.empty()) rc = h->store.append(srt.data(), bb, keys.data(), soff.data(), ord.size(), A.markdup ? &bd : nullptr);
+				if (rc == BMH_OK && !ord.empty()) rc = h->store.append(srt.data(), bb, keys.data(), soff.data(), ord.size(), A.next.markdup ? &bd : nullptr);
 			}
 		} else if (rc == BMH_OK) {
 			rc = bmh_bgzf_deflate_host(bam, bb, A.out_level, n_threads, &mem, &mb);
@@ -1254,42 +1116,18 @@ struct out_stage_t {
 	int end(bool trace)
 	{
 		if (fmt != BMH_OUT_BAM_SORTED) return BMH_OK;
-		lane_t &L0 = *h->lanes[0];
+		lane_t &L0 = *h->lanes[0]; bsr_out_t &J = h->last.out;
 		int rc = BMH_OK;
 		if (!L0.bam && !(L0.bam = bmh_bam_ws_create())) rc = BMH_ENOMEM;
 		if (rc == BMH_OK && !L0.bsr && !(L0.bsr = bsr_dev_create())) rc = BMH_ENOMEM;
 		const double tm0 = now_s();
-		const uint32_t n_lib = h->a.markdup ? h->a.plan.table.n_lib : 0;
-		h->lib_counts.assign((size_t)BDP_N_COUNTS * n_lib, 0);
-		bdp_plan_t P = h->a.plan;                                     // the aligner's plan with the places of this run's counts
-		const bool optical = P.optical() != nullptr, barcode = P.barcode() != nullptr, grouped = P.grouping() != nullptr;
-		h->lib_opt.assign(optical ? (size_t)BDP_OPT_N * n_lib : 0, 0);
-		P.lib_counts = n_lib ? h->lib_counts.data() : nullptr; P.opt.out = h->opt_counts; P.opt.lib_out = n_lib ? h->lib_opt.data() : nullptr; P.grp.out = h->grp_counts;
-		h->no_barcode = barcode ? bdp_no_barcode(h->store.bcs.data(), h->store.bcs.size()) : 0;
-		for (int k = 0; k < BDP_GRP_N; ++k) h->grp_counts[k] = 0;
-		struct cov_own_t { bcv_dev_t *p = nullptr; ~cov_own_t() { if (p) bcv_dev_free(p); } } cov;      // coverage: the run's device state, from the first window to the results
-		if (rc == BMH_OK && h->cov_on) {
-			h->cov_plan_last = h->cov_plan;
-			if (!(cov.p = bcv_dev_create())) rc = BMH_ENOMEM;
-			if (rc == BMH_OK) rc = bcv_begin_device(cov.p, h->cov_plan_last, L0.st);
-		}
-		struct stats_own_t { bst_dev_t *p = nullptr; ~stats_own_t() { if (p) bst_dev_free(p); } } stats;      // statistics: the run's accumulator, from the first window to the results
-		if (rc == BMH_OK && h->stats_on) {
-			h->stats_plan_last = h->stats_plan;
-			if (!(stats.p = bst_dev_create())) rc = BMH_ENOMEM;
-			if (rc == BMH_OK) rc = bst_begin_device(stats.p, h->stats_plan_last, L0.st);
-		}
-		if (rc == BMH_OK) rc = bsr_merge_device(L0.bsr, L0.bam, h->store, h->sort_window, h->a.out_level, L0.st, h->sort_ix, forward, this, h->a.markdup ? h->dup_counts : nullptr, P, h->dup_times, &h->opt_ms,
-		                                        cov.p, cov.p ? h->cov_ms : nullptr, stats.p, stats.p ? h->stats_ms : nullptr);
-		if (rc == BMH_OK && stats.p) rc = bst_finish_device(stats.p, L0.st, h->stats_res, fn);
-		if (trace && stats.p) fprintf(stderr, "[aligner] statistics: the kernels of %.0f windows took %.2f ms on the device, %.3f ms per window\n", h->stats_ms[1], h->stats_ms[0], h->stats_ms[0] / (h->stats_ms[1] > 0 ? h->stats_ms[1] : 1));
-		if (rc == BMH_OK && cov.p) rc = bcv_finish_device(cov.p, L0.st, h->cov_res, fn, h->cov_ms);
-		if (trace && cov.p) fprintf(stderr, "[aligner] coverage: the depth steps of %.0f windows took %.2f ms on the device, %.3f ms per window (tile %llu, %llu bins)\n", h->cov_ms[1], h->cov_ms[0], h->cov_ms[0] / (h->cov_ms[1] > 0 ? h->cov_ms[1] : 1), (unsigned long long)h->cov_plan_last.tile, (unsigned long long)h->cov_plan_last.n_bins());
-		for (size_t k = 0; rc == BMH_OK && k < h->store.lib_info.size() && k / 3 < n_lib; ++k) h->lib_counts[BDP_N_COUNTS * (k / 3) + BDP_SECSUP + k % 3] = h->store.lib_info[k];
-		if (trace && h->a.markdup) fprintf(stderr, "[aligner] duplicate marking: %.0f bytes of ordinals and entries came down with the batches\n", h->dup_times[2]);
+		if (rc == BMH_OK) rc = bsr_write_device(L0.bsr, L0.bam, h->store, J, L0.st, forward, this, fn);
+		if (trace && J.stats) fprintf(stderr, "[aligner] statistics: the kernels of %.0f windows took %.2f ms on the device, %.3f ms per window\n", J.stats_ms[1], J.stats_ms[0], J.stats_ms[0] / (J.stats_ms[1] > 0 ? J.stats_ms[1] : 1));
+		if (trace && J.coverage) fprintf(stderr, "[aligner] coverage: the depth steps of %.0f windows took %.2f ms on the device, %.3f ms per window (tile %llu, %llu bins)\n", J.cov_ms[1], J.cov_ms[0], J.cov_ms[0] / (J.cov_ms[1] > 0 ? J.cov_ms[1] : 1), (unsigned long long)J.CP.tile, (unsigned long long)J.CP.n_bins());
+		if (trace && J.markdup) fprintf(stderr, "[aligner] duplicate marking: %.0f bytes of ordinals and entries came down with the batches\n", J.dup_ms[2]);
 		if (trace) fprintf(stderr, "[aligner] sorted output: %zu runs (%llu spilled) merged in %.1f ms\n", h->store.runs.size(), (unsigned long long)h->store.spilled, (now_s() - tm0) * 1e3);
 		h->store.clear();
-		if (rc == BMH_OK) { h->sort_ix.valid = true; h->cov_valid = h->cov_on; h->stats_valid = h->stats_on; h->dup_valid = h->a.markdup; h->opt_valid = optical; h->bc_valid = barcode; h->grp_valid = grouped; }
+		h->last.valid = rc == BMH_OK;                                 // (the index and the results are those of a whole file, or of none)
 		return rc;
 	}
 };
@@ -1613,10 +1451,10 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 	if (keep) {                                                        // refused before the file is opened
 		if (path2) { bmh_set_error("%s: the input's read groups are kept (bmh_aligner_set_keep_rg) and a mates file was given: such a run takes one BAM file", fn); return BMH_EINVAL; }
 		if (h->a.po.rg_id && h->a.po.rg_id[0]) { bmh_set_error("%s: the input's read groups are kept (bmh_aligner_set_keep_rg) and the aligner has a read group of its own ('%s', -R): one or the other", fn, h->a.po.rg_id); return BMH_EINVAL; }
-		if (h->a.markdup && h->a.n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d reference sequences: with read groups duplicate marking takes at most 2^24 (the library is the top byte of its key)", fn, h->a.n_contigs); return BMH_EINVAL; }
+		if (h->a.next.markdup && h->a.n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d reference sequences: with read groups duplicate marking takes at most 2^24 (the library is the top byte of its key)", fn, h->a.n_contigs); return BMH_EINVAL; }
 	}
 	// (BMH_READS_HOST=1: the pump's host forms cut every window -- the A/B and cross-check switch of the device parser and the BAM decoder kernels)
-	bmh_reads_pump_t *P = bmh_pump_open(path1, path2, n_threads, cm, bmh_tune("READS_HOST", 0) != 0, (size_t)std::max(0, bmh_tune("READS_CHUNK_BYTES", 0)) /* (the tests' small windows; 0: sized by the batch) */, keep, keep && h->a.markdup, h->collate, h->collate_mem);
+	bmh_reads_pump_t *P = bmh_pump_open(path1, path2, n_threads, cm, bmh_tune("READS_HOST", 0) != 0, (size_t)std::max(0, bmh_tune("READS_CHUNK_BYTES", 0)) /* (the tests' small windows; 0: sized by the batch) */, keep, keep && h->a.next.markdup, h->collate, h->collate_mem);
 	if (!P) return BMH_EINVAL;
 	if (h->collate && bmh_pump_bam_paired(P) < 0) {                    // refused before a batch is read
 		bmh_pump_close(P);
@@ -1625,7 +1463,7 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 	}
 	aligner_t &A = h->a;
 	// the run's table is the aligner's until the run is over, whichever way it ends
-	struct table_guard_t { aligner_t &A; bool on; ~table_guard_t() { if (on) { A.group_ids.clear(); A.plan.table = bdp_table_t(); A.per_read = false; ++A.groups_serial; } } } guard{A, false};
+	struct table_guard_t { aligner_t &A; bool on; ~table_guard_t() { if (on) { A.group_ids.clear(); A.next.P.table = bdp_table_t(); A.per_read = false; ++A.groups_serial; } } } guard{A, false};
 	if (keep) {
 		// the header was read whole when the pump opened the file: its @RG lines are the run's read groups, and the caller hears of them before the first record
 		const bmh_rg_table_t *T = bmh_pump_read_groups(P);
@@ -1633,7 +1471,7 @@ int bmh_aligner_run_files(bmh_aligner_t *h, const char *path1, const char *path2
 		G.id_off.assign(1, 0u);
 		for (size_t g = 0; g < T->ids.size(); ++g) { G.ids += T->ids[g]; G.id_off.push_back((uint32_t)G.ids.size()); G.lib.push_back((uint8_t)T->lib[g]); }      // (beyond 255 libraries the byte is not read: no duplicate marking)
 		G.n_lib = (uint32_t)T->lib_names.size();
-		A.group_ids.assign(T->ids.begin(), T->ids.end()); A.plan.table = G; A.per_read = true; ++A.groups_serial; guard.on = true;
+		A.group_ids.assign(T->ids.begin(), T->ids.end()); A.next.P.table = G; A.per_read = true; ++A.groups_serial; guard.on = true;
 		if (h->rg_header) {
 			std::string lines;
 			for (const std::string &l : T->lines) { lines += l; lines += '\n'; }
@@ -1686,8 +1524,8 @@ int bmh_aligner_run_groups(bmh_aligner_t *h, const bmh_read_group_t *groups, int
 	}
 	bdp_table_t T;
 	RCK(bdp_table_make(T, ids.data(), libs.data(), n_groups, fn));
-	if (h->a.markdup && h->a.n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d reference sequences: with read groups duplicate marking takes at most 2^24 (the library is the top byte of its key)", fn, h->a.n_contigs); return BMH_EINVAL; }
-	if (h->a.plan.optical() && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: with an optical distance a run takes at most %d (a location holds its group's row in 16 bits)", fn, n_groups, (int)BDP_OPT_MAX_GROUPS); return BMH_EINVAL; }
+	if (h->a.next.markdup && h->a.n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d reference sequences: with read groups duplicate marking takes at most 2^24 (the library is the top byte of its key)", fn, h->a.n_contigs); return BMH_EINVAL; }
+	if (h->a.next.P.optical() && n_groups > (int)BDP_OPT_MAX_GROUPS) { bmh_set_error("%s: %d read groups: with an optical distance a run takes at most %d (a location holds its group's row in 16 bits)", fn, n_groups, (int)BDP_OPT_MAX_GROUPS); return BMH_EINVAL; }
 	for (int g = 0; g < n_groups; ++g)
 		for (const char *path : {groups[g].path1, groups[g].path2}) {
 			struct stat sb;
@@ -1749,9 +1587,9 @@ int bmh_aligner_run_groups(bmh_aligner_t *h, const bmh_read_group_t *groups, int
 		}
 	};
 	aligner_t &A = h->a;
-	A.group_ids.assign(ids.begin(), ids.end()); A.plan.table = T; ++A.groups_serial;
+	A.group_ids.assign(ids.begin(), ids.end()); A.next.P.table = T; ++A.groups_serial;
 	rc = run_loaded(h, fn, dev, fill, true, run_pairs, n_lanes, n_threads, sink, user, stats);
-	A.group_ids.clear(); A.plan.table = bdp_table_t(); ++A.groups_serial;
+	A.group_ids.clear(); A.next.P.table = bdp_table_t(); ++A.groups_serial;
 	close_pump();
 	bmh_reads_note_counts(ld.cnt); bmh_reads_note_inflate_counts(ld.icnt); bmh_reads_note_bam_counts(ld.bcnt); bmh_reads_note_collate_counts(ld.ccnt);
 	return rc;

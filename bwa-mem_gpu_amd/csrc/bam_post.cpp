@@ -194,7 +194,7 @@ extern "C" void bmh_bam_post_opt_default(bmh_bam_post_opt_t *o)
 {
 	if (!o) return;
 	memset(o, 0, sizeof *o);
-	o->level = 1; o->index_format = BSR_IX_BAI; o->min_shift = BSR_LIN_SHIFT;
+	bmh_sorted_opt_default(&o->sorted);
 }
 
 extern "C" void bmh_bam_post_result_free(bmh_bam_post_result_t *r)
@@ -225,49 +225,33 @@ uint32_t bpo_template_start(const uint8_t *recs, const uint64_t *off, uint32_t i
 	return i;
 }
 
-int bpo_run_t::begin(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res, bmh_coverage_t *cov, const char *f, bpo_convert_t conv,
-                     bmh_bam_stats_t *st, bool with_stats)
+int bpo_run_t::begin(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, bmh_bam_post_result_t *out, bmh_sorted_results_t *res, const char *f, bpo_convert_t conv)
 {
 	fn = f;
 	if (out) memset(out, 0, sizeof *out);
-	if (cov) memset(cov, 0, sizeof *cov);
-	if (st) memset(st, 0, sizeof *st);
-	if (!path || !sink || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	if (opt) o = *opt; else bmh_bam_post_opt_default(&o);
-	markdup = o.markdup != nullptr; coverage = o.coverage != nullptr;
-	if (!with_stats) o.stats = nullptr;                               // (the entry points from before the field do not read it)
-	stats = o.stats != nullptr;
-	mode = (markdup ? (uint32_t)BPO_MARKDUP : 0u) | (coverage ? (uint32_t)BPO_COVERAGE : 0u);
-	if (o.level != 0 && o.level != 1) { bmh_set_error("%s: level %d (0 or 1)", fn, o.level); return BMH_EINVAL; }
-	int rc = bsr_index_format_check(o.index_format, o.min_shift, fn);
+	int rc = bsr_out_make(J, &o.sorted, 0, nullptr, nullptr, res, fn);
 	if (rc != BMH_OK) return rc;
+	if (!path || !sink || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	if (!o.batch_bytes) o.batch_bytes = BPO_BATCH_DEFAULT;
 	if (o.batch_bytes > BPO_BATCH_MAX) { bmh_set_error("%s: batch_bytes %llu (at most 2^30; 0: 2^28)", fn, (unsigned long long)o.batch_bytes); return BMH_EINVAL; }
 	collate = o.collate != 0; in.plain = collate;
-	if (collate && !markdup) { bmh_set_error("%s: collate needs marking: templates by name over the whole file are formed where duplicates are marked", fn); return BMH_EINVAL; }
-	if (o.libraries && !markdup) { bmh_set_error("%s: libraries need marking: the header's @RG lines say which templates may be duplicates of each other", fn); return BMH_EINVAL; }
-	if (markdup && !res) { bmh_set_error("%s: null argument (marking needs its counts record)", fn); return BMH_EINVAL; }
-	if (coverage && !cov) { bmh_set_error("%s: null argument (coverage needs its record)", fn); return BMH_EINVAL; }
-	if (stats && !st) { bmh_set_error("%s: null argument (the statistics need their record)", fn); return BMH_EINVAL; }
-	if (markdup) {
-		mo = *o.markdup;
-		if (o.libraries && (mo.rg_ids || mo.rg_lib || mo.n_groups)) { bmh_set_error("%s: libraries come from the header's @RG lines or from the options' read groups, not both", fn); return BMH_EINVAL; }
-		if ((rc = bdp_plan_make(P, &mo, res, fn)) != BMH_OK) return rc;        // (every option but the header's groups: refused before the input is touched)
-	}
+	if (collate && !J.markdup) { bmh_set_error("%s: collate needs marking: templates by name over the whole file are formed where duplicates are marked", fn); return BMH_EINVAL; }
+	if (o.libraries && !J.markdup) { bmh_set_error("%s: libraries need marking: the header's @RG lines say which templates may be duplicates of each other", fn); return BMH_EINVAL; }
+	if (J.markdup) mo = *o.sorted.markdup;
+	if (o.libraries && (mo.rg_ids || mo.rg_lib || mo.n_groups)) { bmh_set_error("%s: libraries come from the header's @RG lines or from the options' read groups, not both", fn); return BMH_EINVAL; }
 	if ((rc = in.open(path, fn, conv)) != BMH_OK) return rc;
 	const int n_ref = (int)in.names.size();
-	if (stats && (rc = bst_plan_make(SP, o.stats->insert_cap, n_ref, fn)) != BMH_OK) return rc;
 	for (const std::string &nm : in.names) name_ptr.push_back(nm.c_str());
-	if ((rc = ix.init(n_ref, in.len.data(), fn, o.index_format, o.min_shift)) != BMH_OK) return rc;
-	if (markdup && (rc = bsr_markdup_contigs(n_ref, in.len.data(), name_ptr.data(), fn)) != BMH_OK) return rc;
-	if (coverage && (rc = bcv_plan_make(CP, o.coverage->min_mapq, o.coverage->deletions, o.coverage->bin, o.coverage->tile, n_ref, in.len.data(), fn)) != BMH_OK) return rc;
-	if (markdup && o.libraries) {
+	if (o.libraries) {
 		if ((rc = bmh_bam_header_groups(fn, in.header.data(), in.header.size(), true, rg)) != BMH_OK) return rc;
 		for (const std::string &id : rg.ids) rg_ids.push_back(id.c_str());
 		mo.rg_ids = rg_ids.data(); mo.rg_lib = rg.lib.data(); mo.n_groups = (int32_t)rg_ids.size();
-		if ((rc = bdp_plan_make(P, &mo, res, fn)) != BMH_OK) return rc;
+		o.sorted.markdup = &mo;
 	}
-	if (P.groups() && n_ref > (int)BDP_MAX_REF) { bmh_set_error("%s: %d references: with read groups a run holds at most 2^24 (the library takes the duplicate key's top byte)", fn, n_ref); return BMH_EINVAL; }
+	if ((rc = bsr_out_make(J, &o.sorted, n_ref, in.len.data(), name_ptr.data(), res, fn)) != BMH_OK) return rc;
+	mode = (J.markdup ? (uint32_t)BPO_MARKDUP : 0u) | (J.coverage ? (uint32_t)BPO_COVERAGE : 0u);
+	if (J.P.groups() && n_ref > (int)BDP_MAX_REF) { bmh_set_error("%s: %d references: with read groups a run holds at most 2^24 (the library takes the duplicate key's top byte)", fn, n_ref); return BMH_EINVAL; }
 	return BMH_OK;
 }
 
@@ -276,7 +260,7 @@ int bpo_run_t::header_members(std::string &members) const
 	uint8_t *hdr = nullptr, *hm = nullptr; uint64_t hb = 0, hmb = 0;
 	int rc = bmh_bam_header(in.header.c_str(), (int)in.names.size(), name_ptr.data(), in.len.data(), &hdr, &hb);
 	if (rc != BMH_OK) return rc;
-	rc = bmh_bgzf_deflate_host(hdr, hb, o.level, 0, &hm, &hmb);
+	rc = bmh_bgzf_deflate_host(hdr, hb, J.level, 0, &hm, &hmb);
 	bmh_free(hdr);
 	if (rc != BMH_OK) return rc;
 	members.assign((const char *)hm, hmb); bmh_free(hm);
@@ -308,6 +292,17 @@ int bpo_run_t::finish(const std::string &index_bytes, bmh_bam_post_result_t *out
 	r.counts = counts;
 	*out = r;
 	return BMH_OK;
+}
+
+int bpo_run_t::end(int rc, uint64_t base, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_sorted_results_t *res)
+{
+	std::string ib;
+	if (rc == BMH_OK && sink(user, (const char *)bmh_bgzf_eof, 28) != 0) { bmh_set_error("the sink refused the text"); rc = BMH_EINVAL; }
+	if (rc == BMH_OK) rc = J.ix.bytes(base, ib);
+	if (rc == BMH_OK) rc = bsr_out_export(J, res, fn);
+	if (rc == BMH_OK) rc = finish(ib, out);
+	if (rc != BMH_OK) bsr_results_release(res);
+	return rc;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the host form
@@ -346,11 +341,11 @@ int host_batch(bpo_run_t &R, host_state_t &S)
 	}
 	// a refused record: the templates before the one that holds it are whole, and a refusal among them comes first
 	const uint32_t n_ok = code == BPO_OK ? n : R.collate ? 0 : bpo_template_start(recs, off, bad);
-	if (R.collate && code == BPO_OK) for (uint32_t i = 0; i < n; ++i) btp_append_host(S.parts, recs + off[i], off[i + 1] - off[i], R.P, 128);
-	if (R.markdup && n_ok && !R.collate) {
+	if (R.collate && code == BPO_OK) for (uint32_t i = 0; i < n; ++i) btp_append_host(S.parts, recs + off[i], off[i + 1] - off[i], R.J.P, 128);
+	if (R.J.markdup && n_ok && !R.collate) {
 		std::vector<uint32_t> tpl; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> locs; std::vector<uint64_t> bcs;
-		const bool optical = R.P.optical() != nullptr, barcode = R.P.barcode() != nullptr;
-		const int rc = bdp_entries_host(recs, off, n_ok, tpl, E, S.info, R.fn, R.P, optical ? &locs : nullptr, barcode ? &bcs : nullptr, BDP_TPL_NAME, in.base);
+		const bool optical = R.J.P.optical() != nullptr, barcode = R.J.P.barcode() != nullptr;
+		const int rc = bdp_entries_host(recs, off, n_ok, tpl, E, S.info, R.fn, R.J.P, optical ? &locs : nullptr, barcode ? &bcs : nullptr, BDP_TPL_NAME, in.base);
 		if (rc != BMH_OK) return rc;
 		const uint32_t tbase = (uint32_t)S.E.size();
 		for (uint32_t t : tpl) S.tpl.push_back(tbase + t);
@@ -365,84 +360,53 @@ int host_batch(bpo_run_t &R, host_state_t &S)
 }
 }   // namespace
 
-static int post_host(const char *fn, const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res, bmh_coverage_t *cov,
-                     bmh_bam_stats_t *stats, bool with_stats)
+// every batch checked and kept, the duplicates decided and flagged, the records sorted and written: everything of the host form before bpo_run_t::end
+static int post_host(bpo_run_t &R, bmh_sam_sink_t sink, void *user, uint64_t *base)
 {
+	const char *fn = R.fn;
+	int rc;
+	host_state_t S;
+	while ((rc = R.in.next(R.o.batch_bytes, fn)) == 1) if ((rc = host_batch(R, S)) != BMH_OK) return rc;
+	if (rc < 0) return rc;
+	if (S.off.size() > 0xfffffff0ull) { bmh_set_error("%s: 2^32 records", fn); return BMH_EINVAL; }
+	const uint32_t n = (uint32_t)(S.off.size() - 1);
+	uint8_t *recs = S.recs.data();
+	if (R.J.markdup) {                                               // the decision over every template of the file, the flags set before the sort
+		const bdp_plan_t &P = R.J.P; uint64_t *counts = R.J.dup_counts;
+		const bool barcode = P.barcode() != nullptr;
+		std::vector<uint32_t> bits; std::vector<uint64_t> Bp;
+		if (R.collate) {                                           // the templates of the whole file by name, from the records' parts
+			btp_result_t G;
+			if ((rc = btp_group_host(S.parts, P, G, fn)) != BMH_OK) return rc;
+			if (G.word != BPO_NONE) return btp_refused(S.parts, G.word, P, R.sam_line0(), fn);
+			S.tpl.swap(G.rec_tpl); S.E.swap(G.E); S.locs.swap(G.locs); S.bcs.swap(G.bcs); S.info[0] = G.info[0]; S.info[1] = G.info[1];
+			R.counts.templates = S.E.size();
+		}
+		if (S.E.size() >= 1ull << 31) { bmh_set_error("%s: duplicate marking: 2^31 templates", fn); return BMH_EINVAL; }
+		if (P.no_barcode) *P.no_barcode = barcode ? bdp_no_barcode(S.bcs.data(), S.bcs.size()) : 0;
+		bdp_decide_host(S.E.data(), S.E.size(), bits, counts, P, barcode ? S.bcs.data() : nullptr, &Bp);
+		counts[BDP_SECSUP] = S.info[0]; counts[BDP_UNMAPPED] = S.info[1]; counts[BDP_TEMPLATES] = S.E.size();
+		if (P.optical()) bdp_optical_host(S.E.data(), S.locs.data(), S.E.size(), *P.optical(), P.n_lib(), P.grouping() ? Bp.data() : barcode ? S.bcs.data() : nullptr);
+		if (P.groups() && P.lib_counts) bdp_lib_tally_host(recs, S.off.data(), n, S.tpl.data(), S.E.data(), S.E.size(), P.n_lib(), P.lib_counts);
+		for (uint32_t i = 0; i < n; ++i) if (bits[S.tpl[i] >> 5] >> (S.tpl[i] & 31) & 1u) recs[S.off[i] + 19] |= 0x04;
+	}
+	std::vector<uint64_t> keys; std::vector<uint32_t> ord;
+	bsr_sort_host(recs, S.off, keys, ord);
+	std::string members;
+	if ((rc = R.header_members(members)) != BMH_OK) return rc;
+	if (sink(user, members.data(), members.size()) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; }
+	*base = members.size();
+	return bsr_write_host(recs, S.off.data(), ord.data(), n, R.J, sink, user, fn);
+}
+
+extern "C" int bmh_bam_post_file_host(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_sorted_results_t *res)
+{
+	const char *fn = "bmh_bam_post_file_host";
+	bpo_run_t R; uint64_t base = 0;
+	int rc;
 	try {
-		bpo_run_t R;
-		int rc = R.begin(path, opt, sink, out, res, cov, fn, convert_host, stats, with_stats);
-		if (rc != BMH_OK) return rc;
-		host_state_t S;
-		while ((rc = R.in.next(R.o.batch_bytes, fn)) == 1) if ((rc = host_batch(R, S)) != BMH_OK) return rc;
-		if (rc < 0) return rc;
-		if (S.off.size() > 0xfffffff0ull) { bmh_set_error("%s: 2^32 records", fn); return BMH_EINVAL; }
-		const uint32_t n = (uint32_t)(S.off.size() - 1);
-		uint8_t *recs = S.recs.data();
-		if (R.markdup) {                                               // the decision over every template of the file, the flags set before the sort
-			const bdp_plan_t &P = R.P;
-			const bool barcode = P.barcode() != nullptr;
-			std::vector<uint32_t> bits; std::vector<uint64_t> Bp;
-			if (R.collate) {                                           // the templates of the whole file by name, from the records' parts
-				btp_result_t G;
-				if ((rc = btp_group_host(S.parts, R.P, G, fn)) != BMH_OK) return rc;
-				if (G.word != BPO_NONE) return btp_refused(S.parts, G.word, R.P, R.sam_line0(), fn);
-				S.tpl.swap(G.rec_tpl); S.E.swap(G.E); S.locs.swap(G.locs); S.bcs.swap(G.bcs); S.info[0] = G.info[0]; S.info[1] = G.info[1];
-				R.counts.templates = S.E.size();
-			}
-			if (S.E.size() >= 1ull << 31) { bmh_set_error("%s: duplicate marking: 2^31 templates", fn); return BMH_EINVAL; }
-			if (P.no_barcode) *P.no_barcode = barcode ? bdp_no_barcode(S.bcs.data(), S.bcs.size()) : 0;
-			bdp_decide_host(S.E.data(), S.E.size(), bits, res->counts, P, barcode ? S.bcs.data() : nullptr, &Bp);
-			res->counts[BDP_SECSUP] = S.info[0]; res->counts[BDP_UNMAPPED] = S.info[1]; res->counts[BDP_TEMPLATES] = S.E.size();
-			if (P.optical()) bdp_optical_host(S.E.data(), S.locs.data(), S.E.size(), *P.optical(), P.n_lib(), P.grouping() ? Bp.data() : barcode ? S.bcs.data() : nullptr);
-			if (P.groups() && P.lib_counts) bdp_lib_tally_host(recs, S.off.data(), n, S.tpl.data(), S.E.data(), S.E.size(), P.n_lib(), P.lib_counts);
-			for (uint32_t i = 0; i < n; ++i) if (bits[S.tpl[i] >> 5] >> (S.tpl[i] & 31) & 1u) recs[S.off[i] + 19] |= 0x04;
-		}
-		std::vector<uint64_t> keys; std::vector<uint32_t> ord;
-		bsr_sort_host(recs, S.off, keys, ord);
-		std::string members;
-		if ((rc = R.header_members(members)) != BMH_OK) return rc;
-		if (sink(user, members.data(), members.size()) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; }
-		const uint64_t base = members.size();
-		bcv_host_t H;
-		if (R.coverage) H.begin(R.CP);
-		bst_host_t SH;
-		if (R.stats) SH.begin(R.SP);
-		const uint64_t W = R.o.window ? R.o.window : std::max<uint64_t>(1, (64ull << 20) / std::max<uint64_t>(1, n ? S.recs.size() / n : 1));
-		std::vector<uint8_t> buf; std::vector<uint64_t> soff, moff;
-		for (size_t a = 0; a < n; a += W) {
-			const size_t b = (size_t)std::min<uint64_t>(n, a + W);
-			soff.assign(1, 0); buf.clear();
-			for (size_t j = a; j < b; ++j) { const uint64_t o = S.off[ord[j]], s = S.off[ord[j] + 1] - o; buf.insert(buf.end(), recs + o, recs + o + s); soff.push_back(buf.size()); }
-			uint8_t *m = nullptr; uint64_t mb = 0;
-			if ((rc = bmh_bgzf_deflate_host(buf.data(), buf.size(), R.o.level, 0, &m, &mb)) != BMH_OK) return rc;
-			moff.assign(1, 0);
-			for (uint64_t q = 0; q < mb;) { q += ((uint64_t)m[q + 16] | (uint64_t)m[q + 17] << 8) + 1; moff.push_back(q); }
-			const int sr = sink(user, (const char *)m, (size_t)mb);
-			bmh_free(m);
-			if (sr != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; }
-			R.ix.window_host(buf.data(), soff.data(), (uint32_t)(b - a), moff.data());
-			if (R.coverage && (rc = H.window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;
-			if (R.stats && (rc = SH.window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;
-		}
-		if (R.coverage && (rc = H.finish(fn)) != BMH_OK) return rc;
-		if (sink(user, (const char *)bmh_bgzf_eof, 28) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; }
-		std::string ib;
-		if ((rc = R.ix.bytes(base, ib)) != BMH_OK) return rc;
-		if (R.coverage && (rc = bcv_export(R.CP, H.R, cov, fn)) != BMH_OK) return rc;
-		if (R.stats) { SH.finish(); if ((rc = bst_export(R.SP, SH.R, stats, fn)) != BMH_OK) return rc; }
-		if ((rc = R.finish(ib, out)) != BMH_OK && R.stats) bmh_bam_stats_free(stats);
-		return rc;
-	} catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
-}
-
-extern "C" int bmh_bam_post_file_host(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res, bmh_coverage_t *cov)
-{
-	return post_host("bmh_bam_post_file_host", path, opt, sink, user, out, res, cov, nullptr, false);
-}
-
-// the same run and, with opt->stats, the statistics of the file from the windows of its merge (csrc/bam_stats_host.cpp)
-extern "C" int bmh_bam_post_file_stats_host(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res,
-                                            bmh_coverage_t *cov, bmh_bam_stats_t *stats)
-{
-	return post_host("bmh_bam_post_file_stats_host", path, opt, sink, user, out, res, cov, stats, true);
+		rc = R.begin(path, opt, sink, out, res, fn, convert_host);
+		if (rc == BMH_OK) rc = post_host(R, sink, user, &base);
+	} catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); rc = BMH_ENOMEM; }
+	return R.end(rc, base, sink, user, out, res);
 }

@@ -39,18 +39,22 @@ private:
 	int bam_header(const char *fn);
 };
 
-// one run: the options as checked, the marking plan, the coverage plan, the index, the counts
+// one run: the options, the sorted output as checked (csrc/bam_sort.h: the plans, the index), the input, the counts
 struct bpo_run_t {
-	const char *fn = ""; bmh_bam_post_opt_t o; bool markdup = false, coverage = false, stats = false; uint32_t mode = 0;
+	const char *fn = ""; bmh_bam_post_opt_t o; uint32_t mode = 0;
 	bmh_markdup_opt_t mo; bmh_rg_table_t rg; std::vector<const char *> rg_ids;
-	bdp_plan_t P; bcv_plan_t CP; bst_plan_t SP; bsr_index_t ix; bpo_input_t in; bmh_bam_post_counts_t counts = {0, 0, 0, 0, 0, 0};
+	bsr_out_t J; bpo_input_t in; bmh_bam_post_counts_t counts = {0, 0, 0, 0, 0, 0};
 	bool collate = false;                                              // templates by name over the whole file (BDP_TPL_FILE, csrc/bam_tpl_core.h)
 	uint64_t sam_line0() const { return in.bam ? 0 : in.header_lines + 1; }      // the SAM line of record 0 (0: a BAM)
 	std::vector<const char *> name_ptr;
-	int begin(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res, bmh_coverage_t *cov, const char *f, bpo_convert_t conv,
-	          bmh_bam_stats_t *st = nullptr, bool with_stats = false);      // with_stats: the entry point reads o.stats (bmh_bam_post_file_stats_*)
+	// out and res zeroed; every option that needs no contig checked before the input is touched, then the input opened and the rest checked over its contigs
+	int begin(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, bmh_bam_post_result_t *out, bmh_sorted_results_t *res, const char *f, bpo_convert_t conv);
 	int header_members(std::string &members) const;                    // the header as BGZF members of the run's level
-	int finish(const std::string &index_bytes, bmh_bam_post_result_t *out) const;     // the results' arrays (malloc'd)
+	// behind a form's run (rc; base: the header members' bytes): the end-of-file member to the sink, the index bytes, the arrays of res and of out (malloc'd); a
+	// failed run, or a step that fails here, leaves out's pointers and every array of res NULL
+	int end(int rc, uint64_t base, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_sorted_results_t *res);
+private:
+	int finish(const std::string &index_bytes, bmh_bam_post_result_t *out) const;
 };
 // the message of the record with file index `index` that bpo_check refuses with `code` (rec: its sz bytes)
 int bpo_refused(const char *fn, uint64_t index, int code, const uint8_t *rec, uint64_t sz, int n_ref);

@@ -97,11 +97,11 @@ namespace {
 struct dev_state_t {
 	hipStream_t st = nullptr;
 	dev_buf<uint8_t> recs, off, word; dev_buf<char> text;
-	bsr_dev_t *bsr = nullptr; bdp_dev_t *bdp = nullptr; bmh_bam_ws_t *ws = nullptr, *sam_ws = nullptr; bcv_dev_t *cov = nullptr; btp_dev_t *btp = nullptr; bst_dev_t *stats = nullptr;
+	bsr_dev_t *bsr = nullptr; bdp_dev_t *bdp = nullptr; bmh_bam_ws_t *ws = nullptr, *sam_ws = nullptr; btp_dev_t *btp = nullptr;
 	dev_buf<char> ctg_names; dev_buf<uint32_t> ctg_noff; bool ctg_up = false;
 	bsr_store_t store;
 	std::vector<uint8_t> sorted; std::vector<uint64_t> keys, soff, bcs; std::vector<uint32_t> stpl, lib3; std::vector<bdp_entry_t> E; std::vector<bdp_loc_t> locs;
-	~dev_state_t() { if (bsr) bsr_dev_free(bsr); if (bdp) bdp_dev_free(bdp); if (ws) bmh_bam_ws_free(ws); if (sam_ws) bmh_bam_ws_free(sam_ws); if (cov) bcv_dev_free(cov); if (btp) btp_dev_free(btp); if (stats) bst_dev_free(stats); }
+	~dev_state_t() { if (bsr) bsr_dev_free(bsr); if (bdp) bdp_dev_free(bdp); if (ws) bmh_bam_ws_free(ws); if (sam_ws) bmh_bam_ws_free(sam_ws); if (btp) btp_dev_free(btp); }
 };
 
 // SAM lines through the device's converter; the records come back to the host, where the chain and the batches are made as for a BAM
@@ -130,10 +130,10 @@ int convert_device(dev_state_t &D, const char *text, size_t n, int n_contigs, co
 int entries_device(bpo_run_t &R, dev_state_t &D, uint32_t n, uint64_t total, const uint32_t **d_tpl, const bdp_entry_t **d_e, const bdp_loc_t **d_l, const uint64_t **d_b, uint32_t info[BDP_INFO_WORDS_PACK],
                    const uint32_t **d_lib3)
 {
-	const bdp_bc_t *bc = R.P.barcode(); const bool optical = R.P.optical() != nullptr, barcode = bc != nullptr, groups = R.P.groups() != nullptr;
+	const bdp_bc_t *bc = R.J.P.barcode(); const bool optical = R.J.P.optical() != nullptr, barcode = bc != nullptr, groups = R.J.P.groups() != nullptr;
 	const uint32_t *d_info = nullptr;
 	RCK(bdp_batch_device(D.bdp, D.recs.p, (const uint64_t *)D.off.p, n, total, D.st, d_tpl, d_e, &d_info, optical ? d_l : nullptr, bc, barcode ? d_b : nullptr, BDP_TPL_NAME));
-	if (groups && d_lib3) RCK(bdp_batch_lib_counts_device(D.bdp, D.recs.p, (const uint64_t *)D.off.p, n, total, R.P.table.n_lib, D.st, d_lib3));
+	if (groups && d_lib3) RCK(bdp_batch_lib_counts_device(D.bdp, D.recs.p, (const uint64_t *)D.off.p, n, total, R.J.P.table.n_lib, D.st, d_lib3));
 	HIPCK(hipMemcpyAsync(info, d_info, 4 * bdp_info_words(bc), hipMemcpyDeviceToHost, D.st));
 	HIPCK(hipStreamSynchronize(D.st));
 	uint32_t bad = 0;
@@ -162,61 +162,55 @@ int device_batch(bpo_run_t &R, dev_state_t &D)
 	HIPCK(hipStreamSynchronize(D.st));
 	const uint32_t *d_tpl = nullptr, *d_stpl = nullptr, *d_lib3 = nullptr; const bdp_entry_t *d_e = nullptr; const bdp_loc_t *d_l = nullptr; const uint64_t *d_b = nullptr;
 	uint32_t info[BDP_INFO_WORDS_PACK] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-	if (R.collate && !D.btp) { if (!(D.btp = btp_dev_create())) return BMH_ENOMEM; RCK(btp_dev_set_groups(D.btp, R.P.groups(), D.st)); }
-	if (R.markdup && !R.collate && !D.bdp) { if (!(D.bdp = bdp_dev_create())) return BMH_ENOMEM; RCK(bdp_dev_set_groups(D.bdp, R.P.groups(), D.st)); }
+	if (R.collate && !D.btp) { if (!(D.btp = btp_dev_create())) return BMH_ENOMEM; RCK(btp_dev_set_groups(D.btp, R.J.P.groups(), D.st)); }
+	if (R.J.markdup && !R.collate && !D.bdp) { if (!(D.bdp = bdp_dev_create())) return BMH_ENOMEM; RCK(bdp_dev_set_groups(D.bdp, R.J.P.groups(), D.st)); }
 	if (w[0] != BPO_NONE) {
 		// a refused record: the templates before the one that holds it are whole, and a refusal among them comes first
 		const uint32_t bad = (uint32_t)(w[0] >> 3); const int code = (int)(w[0] & 7u);
 		if (bad >= n) { bmh_set_error("%s: internal error: record %u of %u refused", R.fn, bad, n); return BMH_EINVAL; }
 		const uint32_t n_ok = R.collate ? 0 : bpo_template_start(in.buf.data(), in.off.data(), bad);
-		if (R.markdup && n_ok) RCK(entries_device(R, D, n_ok, in.off[n_ok], &d_tpl, &d_e, &d_l, &d_b, info, nullptr));
+		if (R.J.markdup && n_ok) RCK(entries_device(R, D, n_ok, in.off[n_ok], &d_tpl, &d_e, &d_l, &d_b, info, nullptr));
 		return bpo_refused(R.fn, in.base + bad, code, in.buf.data() + in.off[bad], in.off[bad + 1] - in.off[bad], n_ref);
 	}
 	R.counts.bins_changed += w[1]; R.counts.dup_flags_cleared += w[2]; R.counts.templates += w[3];
-	const bool optical = R.P.optical() != nullptr, barcode = R.P.barcode() != nullptr, groups = R.P.groups() != nullptr;
-	if (R.collate) RCK(btp_parts_device(D.btp, D.recs.p, (const uint64_t *)D.off.p, n, total, R.P, 128, D.st, D.store.tpl_parts, &d_tpl));
-	else if (R.markdup) RCK(entries_device(R, D, n, total, &d_tpl, &d_e, &d_l, &d_b, info, &d_lib3));
+	const bool optical = R.J.P.optical() != nullptr, barcode = R.J.P.barcode() != nullptr, groups = R.J.P.groups() != nullptr;
+	if (R.collate) RCK(btp_parts_device(D.btp, D.recs.p, (const uint64_t *)D.off.p, n, total, R.J.P, 128, D.st, D.store.tpl_parts, &d_tpl));
+	else if (R.J.markdup) RCK(entries_device(R, D, n, total, &d_tpl, &d_e, &d_l, &d_b, info, &d_lib3));
 	const uint8_t *ds = nullptr; const uint64_t *dk = nullptr, *dso = nullptr;
 	RCK(bsr_sort_run_device(D.bsr, D.recs.p, (const uint64_t *)D.off.p, n, total, D.st, &ds, &dk, &dso, d_tpl, &d_stpl));
 	D.sorted.resize((size_t)total + 1); D.keys.resize((size_t)n + 1); D.soff.resize((size_t)n + 2);
 	HIPCK(hipMemcpyAsync(D.sorted.data(), ds, (size_t)total, hipMemcpyDeviceToHost, D.st));
 	HIPCK(hipMemcpyAsync(D.keys.data(), dk, 8 * (size_t)n, hipMemcpyDeviceToHost, D.st));
 	HIPCK(hipMemcpyAsync(D.soff.data(), dso, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, D.st));
-	const uint32_t nt = R.markdup ? info[0] : 0;
+	const uint32_t nt = R.J.markdup ? info[0] : 0;
 	if (R.collate) { D.stpl.resize(n); D.E.clear(); HIPCK(hipMemcpyAsync(D.stpl.data(), d_stpl, 4 * (size_t)n, hipMemcpyDeviceToHost, D.st)); }
-	else if (R.markdup) {
+	else if (R.J.markdup) {
 		D.stpl.resize(n); D.E.resize(nt);
 		HIPCK(hipMemcpyAsync(D.stpl.data(), d_stpl, 4 * (size_t)n, hipMemcpyDeviceToHost, D.st));
 		HIPCK(hipMemcpyAsync(D.E.data(), d_e, sizeof(bdp_entry_t) * (size_t)nt, hipMemcpyDeviceToHost, D.st));
 		if (optical) { D.locs.resize(nt); HIPCK(hipMemcpyAsync(D.locs.data(), d_l, sizeof(bdp_loc_t) * (size_t)nt, hipMemcpyDeviceToHost, D.st)); }
 		if (barcode) { D.bcs.resize(nt); HIPCK(hipMemcpyAsync(D.bcs.data(), d_b, 8 * (size_t)nt, hipMemcpyDeviceToHost, D.st)); }
-		if (groups) { D.lib3.resize(3 * (size_t)R.P.table.n_lib); HIPCK(hipMemcpyAsync(D.lib3.data(), d_lib3, 12 * (size_t)R.P.table.n_lib, hipMemcpyDeviceToHost, D.st)); }
+		if (groups) { D.lib3.resize(3 * (size_t)R.J.P.table.n_lib); HIPCK(hipMemcpyAsync(D.lib3.data(), d_lib3, 12 * (size_t)R.J.P.table.n_lib, hipMemcpyDeviceToHost, D.st)); }
 	}
 	HIPCK(hipStreamSynchronize(D.st));
 	if (D.soff[n] != total) { bmh_set_error("%s: internal error: the sorted run holds %llu bytes, the batch's records %llu", R.fn, (unsigned long long)D.soff[n], (unsigned long long)total); return BMH_EINVAL; }
 	bsr_dup_t bd = {D.stpl.data(), D.E.data(), nt, info[2], info[3]};
-	if (groups && !R.collate) { bd.lib3 = D.lib3.data(); bd.n_lib3 = R.P.table.n_lib; }
+	if (groups && !R.collate) { bd.lib3 = D.lib3.data(); bd.n_lib3 = R.J.P.table.n_lib; }
 	if (optical && !R.collate) bd.locs = D.locs.data();
 	if (barcode && !R.collate) bd.bcs = D.bcs.data();
-	RCK(D.store.append(D.sorted.data(), total, D.keys.data(), D.soff.data(), n, R.markdup ? &bd : nullptr));
+	RCK(D.store.append(D.sorted.data(), total, D.keys.data(), D.soff.data(), n, R.J.markdup ? &bd : nullptr));
 	if (R.collate) D.store.runs.back().tbase = in.base;                // (tpl holds batch indices: the file index of a record is tbase + tpl [i])
 	R.counts.records += n; ++R.counts.batches;
 	return BMH_OK;
 }
 
-struct sink_t { bmh_sam_sink_t sink; void *user; };
-int forward(void *u, const char *b, size_t n) { sink_t *s = (sink_t *)u; return s->sink(s->user, b, n); }
-
-int post_device(const char *fn, const char *path, const bmh_bam_post_opt_t *opt, void *stream, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res,
-                bmh_coverage_t *cov, bmh_bam_stats_t *stats, bool with_stats)
+// every batch checked and kept as a sorted run, the templates grouped, the runs merged: everything of the device form before bpo_run_t::end
+int post_device(bpo_run_t &R, dev_state_t &D, bmh_sam_sink_t sink, void *user, uint64_t *base)
 {
-	dev_state_t D; D.st = (hipStream_t)stream;
-	bpo_run_t R;
-	RCK(R.begin(path, opt, sink, out, res, cov, fn, [&D](const char *text, size_t n, int nc, const std::string &blob, const std::vector<uint32_t> &noff, std::vector<uint8_t> &recs, uint32_t *bad,
-	                                                       uint32_t *status) { return convert_device(D, text, n, nc, blob, noff, recs, bad, status); }, stats, with_stats));
+	const char *fn = R.fn;
 	if (!(D.bsr = bsr_dev_create()) || !(D.ws = bmh_bam_ws_create())) return BMH_ENOMEM;
-	if (R.o.sort_mem) D.store.mem_bytes = R.o.sort_mem;
-	if (R.o.tmp_dir) D.store.tmp_dir = R.o.tmp_dir;
+	if (R.o.sorted.sort_mem) D.store.mem_bytes = R.o.sorted.sort_mem;
+	if (R.o.sorted.tmp_dir) D.store.tmp_dir = R.o.sorted.tmp_dir;
 	int rc;
 	const bool trace = getenv("BMH_ALIGNER_TRACE") != nullptr;
 	auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -227,8 +221,8 @@ int post_device(const char *fn, const char *path, const bmh_bam_post_opt_t *opt,
 	if (R.collate) {                                                   // the templates of the whole file by name: the grouping, then the runs' ordinals rewritten
 		if (!D.btp && !(D.btp = btp_dev_create())) return BMH_ENOMEM;
 		btp_result_t G;
-		RCK(btp_group_device(D.btp, D.store.tpl_parts, R.P, D.st, G, fn));
-		if (G.word != BPO_NONE) return btp_refused(D.store.tpl_parts, G.word, R.P, R.sam_line0(), fn);
+		RCK(btp_group_device(D.btp, D.store.tpl_parts, R.J.P, D.st, G, fn));
+		if (G.word != BPO_NONE) return btp_refused(D.store.tpl_parts, G.word, R.J.P, R.sam_line0(), fn);
 		if (G.rec_tpl.size() != R.counts.records) { bmh_set_error("%s: internal error: %zu ordinals for %llu records", fn, G.rec_tpl.size(), (unsigned long long)R.counts.records); return BMH_EINVAL; }
 		D.store.retemplate(G.rec_tpl);
 		D.store.entries.swap(G.E); D.store.locs.swap(G.locs); D.store.bcs.swap(G.bcs); D.store.lib_info.swap(G.lib3);
@@ -241,52 +235,27 @@ int post_device(const char *fn, const char *path, const bmh_bam_post_opt_t *opt,
 	std::string members;
 	RCK(R.header_members(members));
 	if (sink(user, members.data(), members.size()) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; }
-	bdp_plan_t &P = R.P;
-	if (R.markdup && P.no_barcode) *P.no_barcode = P.barcode() ? bdp_no_barcode(D.store.bcs.data(), D.store.bcs.size()) : 0;
-	if (R.coverage) {
-		if (!(D.cov = bcv_dev_create())) return BMH_ENOMEM;
-		RCK(bcv_begin_device(D.cov, R.CP, D.st));
-	}
-	if (R.stats) {
-		if (!(D.stats = bst_dev_create())) return BMH_ENOMEM;
-		RCK(bst_begin_device(D.stats, R.SP, D.st));
-	}
-	sink_t fw = {sink, user};
+	*base = members.size();
 	R.counts.spilled_runs = D.store.spilled;
-	RCK(bsr_merge_device(D.bsr, D.ws, D.store, R.o.window, R.o.level, D.st, R.ix, forward, &fw, R.markdup ? res->counts : nullptr, P, nullptr, nullptr, D.cov, nullptr, D.stats, nullptr));
-	bcv_result_t CR; bst_result_t SR;
-	if (R.stats) RCK(bst_finish_device(D.stats, D.st, SR, fn));
-	if (R.coverage) RCK(bcv_finish_device(D.cov, D.st, CR, fn, nullptr));
-	if (R.markdup && P.groups() && P.lib_counts)                       // every library's line counts and templates, as the batches counted them
-		for (size_t k = 0; k < D.store.lib_info.size() && k / 3 < P.n_lib(); ++k) P.lib_counts[BDP_N_COUNTS * (k / 3) + BDP_SECSUP + k % 3] = D.store.lib_info[k];
-	if (sink(user, (const char *)bmh_bgzf_eof, 28) != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; }
-	std::string ib;
-	RCK(R.ix.bytes(members.size(), ib));
-	if (R.coverage) RCK(bcv_export(R.CP, CR, cov, fn));
-	if (R.stats) RCK(bst_export(R.SP, SR, stats, fn));
+	RCK(bsr_write_device(D.bsr, D.ws, D.store, R.J, D.st, sink, user, fn));
 	if (trace)
 		fprintf(stderr, "[bam post] %llu records in %llu batches: read, checked and sorted in %.1f ms, templates by name over the file in %.1f ms, merged in %.1f ms\n",
 		        (unsigned long long)R.counts.records, (unsigned long long)R.counts.batches, t_batches - t_begin, t_grouped - t_batches, now_ms() - t_grouped);
-	const int frc = R.finish(ib, out);
-	if (frc != BMH_OK && R.stats) bmh_bam_stats_free(stats);
-	return frc;
+	return BMH_OK;
 }
 
 }   // namespace
 
-extern "C" int bmh_bam_post_file_device(const char *path, const bmh_bam_post_opt_t *opt, void *stream, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res,
-                                        bmh_coverage_t *cov)
+extern "C" int bmh_bam_post_file_device(const char *path, const bmh_bam_post_opt_t *opt, void *stream, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_sorted_results_t *res)
 {
 	const char *fn = "bmh_bam_post_file_device";
-	try { return post_device(fn, path, opt, stream, sink, user, out, res, cov, nullptr, false); }
-	catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
-}
-
-// the same run and, with opt->stats, the statistics of the file from the windows of its merge (csrc/bam_stats_kernels.hip)
-extern "C" int bmh_bam_post_file_stats_device(const char *path, const bmh_bam_post_opt_t *opt, void *stream, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res,
-                                              bmh_coverage_t *cov, bmh_bam_stats_t *stats)
-{
-	const char *fn = "bmh_bam_post_file_stats_device";
-	try { return post_device(fn, path, opt, stream, sink, user, out, res, cov, stats, true); }
-	catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+	dev_state_t D; D.st = (hipStream_t)stream;
+	bpo_run_t R; uint64_t base = 0;
+	int rc;
+	try {
+		rc = R.begin(path, opt, sink, out, res, fn, [&D](const char *text, size_t n, int nc, const std::string &blob, const std::vector<uint32_t> &noff, std::vector<uint8_t> &recs, uint32_t *bad,
+		                                                uint32_t *status) { return convert_device(D, text, n, nc, blob, noff, recs, bad, status); });
+		if (rc == BMH_OK) rc = post_device(R, D, sink, user, &base);
+	} catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); rc = BMH_ENOMEM; }
+	return R.end(rc, base, sink, user, out, res);
 }

@@ -7,6 +7,8 @@
 #include "bam_sort_core.h"
 #include "bam_dup.h"
 #include "bam_tpl.h"
+#include "bam_cov.h"
+#include "bam_stats.h"
 
 typedef int (*bsr_sink_t)(void *user, const char *bytes, size_t n);
 
@@ -21,7 +23,6 @@ struct bsr_index_t {
 	std::vector<uint64_t> counts;                                  // [2 r]: mapped, [2 r + 1]: unmapped records of reference r; [2 n_ref]: records without one
 	std::vector<bsr_head_t> heads;
 	uint64_t file_pos = 0;                                         // bytes handed to the sink so far
-	bool valid = false;                                            // the index of a whole file (init: of one without records); false while a run builds it and after it failed
 	int format = BSR_IX_BAI, min_shift = BSR_LIN_SHIFT, depth = BSR_BAI_DEPTH;      // the binning scheme: BAI's (14, 5), or CSI's min_shift and the depth its longest contig asks for
 	// BAI: contigs below 2^29 bases; CSI: any length an int32 holds, min_shift in 10 .. 24, and a lin array that fits (counted before it is allocated)
 	int init(int n_contigs, const int32_t *contig_len, const char *fn, int format = BSR_IX_BAI, int min_shift = BSR_LIN_SHIFT);
@@ -39,9 +40,30 @@ struct bsr_index_t {
 int bsr_markdup_contigs(int n_contigs, const int32_t *contig_len, const char *const *contig_names, const char *fn);
 // format and min_shift as the entry points take them: BMH_EINVAL with a message, or BMH_OK
 int bsr_index_format_check(int format, int min_shift, const char *fn);
-// opt and res as the sorted-file entry points take them -> o: opt or its defaults, the index format checked; with o.markdup the plan P (bdp_plan_make; an optical
-// distance is refused: a stand-alone file has no optical step), its counts going to *res
-int bsr_file_opt_check(const bmh_sorted_file_opt_t *opt, bmh_markdup_counts_t *res, const char *fn, bmh_sorted_file_opt_t &o, bdp_plan_t &P);
+
+// One sorted output, checked: what bmh_sorted_opt_t asks for as plans (markdup, coverage, stats: which of them are on), the index being built, and what the run
+// leaves behind -- the marking's counts where P points (the caller's bmh_markdup_counts_t), the coverage and the statistics as the device or the host form finished
+// them (bsr_out_export makes the caller's arrays of them), and, for a timed run (the aligner's), the milliseconds: dup_ms [3] the decision, the windows' flag steps
+// and the bytes of ordinals and entries that came down with the batches; opt_ms the optical step; cov_ms / stats_ms [2] the steps and the windows timed
+struct bsr_out_t {
+	int level = 1; uint32_t window = 0;
+	bool markdup = false, coverage = false, stats = false, timed = false;
+	bdp_plan_t P; bcv_plan_t CP; bst_plan_t SP;
+	bsr_index_t ix;
+	uint64_t *dup_counts = nullptr;                                // [BDP_N_COUNTS], with markdup
+	bcv_result_t CR; bst_result_t SR;
+	double dup_ms[3] = {0, 0, 0}, opt_ms = 0, cov_ms[2] = {0, 0}, stats_ms[2] = {0, 0};
+	uint32_t parts() const;                                        // BMH_SORTED_*: what a run under these plans computes
+};
+// opt (NULL: the defaults) and the results record as every sorted output takes them, over these contigs -> J.  *res, the records it names and J are zeroed first;
+// then, in this order: the level; the index format and the contigs it holds (J.ix: the index of a file without records); marking -- its record in res, the
+// options (bdp_plan_make's order), the contigs marking holds; coverage -- its record, bcv_plan_make; the statistics -- their record, bst_plan_make.  BMH_EINVAL
+// with a message, or BMH_OK.  res NULL: as a record of NULLs
+int bsr_out_make(bsr_out_t &J, const bmh_sorted_opt_t *opt, int n_contigs, const int32_t *contig_len, const char *const *contig_names, bmh_sorted_results_t *res, const char *fn);
+// the coverage and the statistics of a finished J -> res's records (malloc'd arrays), J's milliseconds -> res
+int bsr_out_export(const bsr_out_t &J, bmh_sorted_results_t *res, const char *fn);
+// every array of res's coverage and statistics released, the records zeroed (a failed call's cleanup; res or its records may be NULL)
+void bsr_results_release(bmh_sorted_results_t *res);
 
 // Sorted runs kept until the end of the input: the records in host memory up to mem_bytes, beyond that in one unnamed temporary file; keys and offsets
 // (16 bytes per record) always in memory.  With duplicate marking (csrc/bam_dup_core.h) a run also keeps every record's template ordinal within its batch (tpl, 4 bytes
@@ -70,9 +92,25 @@ struct bsr_store_t {
 // csrc/bam_sort_host.cpp: records (walked, checked) -> sorted order on the host
 int bsr_walk(const uint8_t *recs, uint64_t n_bytes, int n_ref, std::vector<uint64_t> &off, const char *fn);
 void bsr_sort_host(const uint8_t *recs, const std::vector<uint64_t> &off, std::vector<uint64_t> &keys, std::vector<uint32_t> &ord);
+// the host form of a sorted output's run: records recs at off (flags as marking left them) in the order ord [n] -> the record members of the sorted file, window
+// after window, to the sink; J.ix, and with J.coverage / J.stats J.CR / J.SR from the same windows
+int bsr_write_host(const uint8_t *recs, const uint64_t *off, const uint32_t *ord, uint64_t n, bsr_out_t &J, bsr_sink_t sink, void *user, const char *fn);
+
+// A stand-alone sorted file in the making: what bmh_bam_sorted_file_device and _host share.  begin: *bam and *index NULL before anything can be refused, the
+// options (bsr_out_make; an optical distance is refused: a stand-alone file has no optical step), the arguments, the stream walked (off), the header members
+// (file).  end: behind a form's records -- the end-of-file member, the index bytes, the results' arrays, the caller's copies; a failed call (rc, or a step of
+// end itself) leaves *bam, *index and every array of the results NULL
+struct bsr_file_t {
+	const char *fn = ""; bsr_out_t J; std::vector<uint64_t> off; std::string file; uint64_t base = 0;
+	uint8_t **bam = nullptr, **index = nullptr; uint64_t *bam_bytes = nullptr, *index_bytes = nullptr;
+	int begin(const char *f, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+	          const bmh_sorted_opt_t *opt, uint8_t **bam_, uint64_t *bam_bytes_, uint8_t **index_, uint64_t *index_bytes_, bmh_sorted_results_t *res);
+	int end(int rc, bmh_sorted_results_t *res);
+};
+inline int bsr_sink_string(void *user, const char *b, size_t n) { ((std::string *)user)->append(b, n); return 0; }
 
 // csrc/bam_sort_kernels.hip
-struct bsr_dev_t;                                                  // device buffers of the sort, the gather and the index pass; kept between calls
+struct bsr_dev_t;                                                 // device buffers of the sort, the gather and the index pass; kept between calls
 bsr_dev_t *bsr_dev_create(void);
 void bsr_dev_free(bsr_dev_t *d);
 // a batch's records d_recs with offsets d_off [n + 1] (device) -> the sorted run: *d_sorted (total bytes), *d_keys [n], *d_soff [n + 1], all in d until its next call
@@ -90,15 +128,15 @@ int bsr_sort_keys_device(bsr_dev_t *d, const uint64_t *keys, uint64_t n, void *s
 int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64_t src_bytes, const uint64_t *src_off, const uint32_t *size, uint32_t n, int level,
                       void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, struct bdp_dev_t *dup, const uint32_t *tord, double *flag_ms,
                       struct bcv_dev_t *cov = nullptr, double *cov_ms = nullptr, struct bst_dev_t *stats = nullptr, double *stats_ms = nullptr);
-// every run of the store -> the record members of the sorted file (to the sink, in windows of `window` records; 0: about 64 MiB of records) and its index
-// dup_counts (or NULL) [8]: mark the duplicates among the store's templates first, as P says (csrc/bam_dup_kernels.hip: the store keeps the locations and the barcode
-// words P's optical step and barcodes ask for), and flag every window's records; the counts of bam_dup.h
-// cov, cov_ms (or NULL): every window goes through the run's coverage (bcv_begin_device before, bcv_finish_device behind: the caller's)
-// stats, stats_ms (or NULL): every window goes through the run's statistics (bst_begin_device before, bst_finish_device behind: the caller's)
-// dup_ms (or NULL) [2]: += the decision's milliseconds (host clock around bdp_decide_device) and the windows' flag steps' (events around the upload of the ordinals
-// and the flag kernel); opt_ms (or NULL) += the optical step's milliseconds
-int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user,
-                     uint64_t *dup_counts, const bdp_plan_t &P, double *dup_ms = nullptr, double *opt_ms = nullptr, struct bcv_dev_t *cov = nullptr, double *cov_ms = nullptr,
-                     struct bst_dev_t *stats = nullptr, double *stats_ms = nullptr);
+// every run of the store -> the record members of the sorted file (to the sink, in windows of J.window records; 0: about 64 MiB of records) and its index J.ix
+// J.markdup: mark the duplicates among the store's templates first, as J.P says (csrc/bam_dup_kernels.hip: the store keeps the locations and the barcode words
+// J.P's optical step and barcodes ask for), and flag every window's records; the counts of bam_dup.h go to J.dup_counts
+// cov, stats (or NULL): every window goes through the run's coverage and statistics (begun before, finished behind: bsr_write_device's)
+// J.timed: J.dup_ms [0 .. 1] += the decision's milliseconds (host clock around bdp_decide_device) and the windows' flag steps' (events around the upload of the
+// ordinals and the flag kernel), J.opt_ms += the optical step's, J.cov_ms and J.stats_ms += the windows'
+int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_out_t &J, void *stream, bsr_sink_t sink, void *user, struct bcv_dev_t *cov, struct bst_dev_t *stats);
+// the device form of a sorted output's run, whole: the coverage and the statistics begun (their device state lives here), the store's runs merged to the sink,
+// both finished into J.CR / J.SR, the marking's counts complete (the templates without a barcode, every library's line counts as the batches counted them)
+int bsr_write_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_out_t &J, void *stream, bsr_sink_t sink, void *user, const char *fn);
 int bsr_index_begin(bsr_dev_t *d, const bsr_index_t &ix, void *stream);
 int bsr_index_finish(bsr_dev_t *d, bsr_index_t &ix, void *stream);

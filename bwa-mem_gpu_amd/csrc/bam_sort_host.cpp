@@ -1,5 +1,6 @@
 // Sorted BAM output on the host: the walk over a record stream, the host form of the sort (std::stable_sort), the index pass over a window and the .bai or .csi
-// bytes (csrc/bam_sort_core.h's rules), the run store of csrc/align_pipeline.hip, and bmh_bam_sort_host / bmh_bam_sorted_file_host / _ex_host.
+// bytes (csrc/bam_sort_core.h's rules), the run store of csrc/align_pipeline.hip, the checked record of a sorted output, and bmh_bam_sort_host /
+// bmh_bam_sorted_file_host.
 #include <errno.h>
 #include <fcntl.h>
 #include <stdlib.h>
@@ -52,13 +53,72 @@ int bsr_index_format_check(int format, int min_shift, const char *fn)
 	return BMH_OK;                                        // (BAI: min_shift is not read, it is 14)
 }
 
-int bsr_file_opt_check(const bmh_sorted_file_opt_t *opt, bmh_markdup_counts_t *res, const char *fn, bmh_sorted_file_opt_t &o, bdp_plan_t &P)
+extern "C" void bmh_sorted_opt_default(bmh_sorted_opt_t *o)
 {
-	o = opt ? *opt : bmh_sorted_file_opt_t{1, 0, BSR_IX_BAI, BSR_LIN_SHIFT, nullptr};
-	int rc = bsr_index_format_check(o.index_format, o.min_shift, fn);
-	if (rc != BMH_OK || !o.markdup) return rc;
-	if (o.markdup->optical_distance != -1) { bmh_set_error("%s: a stand-alone sorted file has no optical step: optical_distance stays -1 (bmh_bam_markdup_* counts optical duplicates)", fn); return BMH_EINVAL; }
-	return bdp_plan_make(P, o.markdup, res, fn);
+	if (!o) return;
+	memset(o, 0, sizeof *o);
+	o->level = 1; o->index_format = BSR_IX_BAI; o->min_shift = BSR_LIN_SHIFT;
+}
+
+uint32_t bsr_out_t::parts() const
+{
+	return (markdup ? BMH_SORTED_MARKDUP | (P.optical() ? BMH_SORTED_OPTICAL : 0u) | (P.barcode() ? BMH_SORTED_BARCODE : 0u) | (P.grouping() ? BMH_SORTED_GROUPED : 0u) : 0u) |
+	       (coverage ? BMH_SORTED_COVERAGE : 0u) | (stats ? BMH_SORTED_STATS : 0u);
+}
+
+int bsr_out_make(bsr_out_t &J, const bmh_sorted_opt_t *opt, int n_contigs, const int32_t *contig_len, const char *const *contig_names, bmh_sorted_results_t *res, const char *fn)
+{
+	bmh_sorted_results_t none; memset(&none, 0, sizeof none);
+	if (!res) res = &none;
+	bmh_markdup_counts_t *const mc = res->markdup; bmh_coverage_t *const cov = res->coverage; bmh_bam_stats_t *const st = res->stats;
+	memset(res, 0, sizeof *res); res->markdup = mc; res->coverage = cov; res->stats = st;
+	if (cov) memset(cov, 0, sizeof *cov);
+	if (st) memset(st, 0, sizeof *st);
+	J = bsr_out_t();
+	bmh_sorted_opt_t o;
+	if (opt) o = *opt; else bmh_sorted_opt_default(&o);
+	if (o.level != 0 && o.level != 1) { bmh_set_error("%s: level %d (0 or 1)", fn, o.level); return BMH_EINVAL; }
+	J.level = o.level; J.window = o.window;
+	int rc = J.ix.init(n_contigs, contig_len, fn, o.index_format, o.min_shift);
+	if (rc != BMH_OK) return rc;
+	if (o.markdup) {
+		if (!mc) { bmh_set_error("%s: null argument (marking needs its counts record)", fn); return BMH_EINVAL; }
+		if ((rc = bdp_plan_make(J.P, o.markdup, mc, fn)) != BMH_OK || (rc = bsr_markdup_contigs(n_contigs, contig_len, contig_names, fn)) != BMH_OK) return rc;
+		J.markdup = true; J.dup_counts = mc->counts;
+	}
+	if (o.coverage) {
+		if (!cov) { bmh_set_error("%s: null argument (coverage needs its record)", fn); return BMH_EINVAL; }
+		if ((rc = bcv_plan_make(J.CP, o.coverage->min_mapq, o.coverage->deletions, o.coverage->bin, o.coverage->tile, n_contigs, contig_len, fn)) != BMH_OK) return rc;
+		J.coverage = true;
+	}
+	if (o.stats) {
+		if (!st) { bmh_set_error("%s: null argument (the statistics need their record)", fn); return BMH_EINVAL; }
+		if ((rc = bst_plan_make(J.SP, o.stats->insert_cap, n_contigs, fn)) != BMH_OK) return rc;
+		J.stats = true;
+	}
+	return BMH_OK;
+}
+
+void bsr_results_release(bmh_sorted_results_t *res)
+{
+	if (res && res->stats) bmh_bam_stats_free(res->stats);
+	if (bmh_coverage_t *c = res ? res->coverage : nullptr) {
+		bmh_free(c->n_reads); bmh_free(c->cov_bases); bmh_free(c->sum_depth); bmh_free(c->max_depth); bmh_free(c->sum_mapq); bmh_free(c->hist); bmh_free(c->bin_sum);
+		memset(c, 0, sizeof *c);
+	}
+}
+
+int bsr_out_export(const bsr_out_t &J, bmh_sorted_results_t *res, const char *fn)
+{
+	if (!res) return BMH_OK;
+	res->parts = J.parts(); res->n_libraries = J.markdup ? (int32_t)J.P.n_lib() : 0;
+	res->markdup_ms[0] = J.dup_ms[0]; res->markdup_ms[1] = J.dup_ms[1]; res->markdup_d2h_bytes = (uint64_t)J.dup_ms[2]; res->optical_ms = J.opt_ms;
+	res->coverage_ms = J.cov_ms[0]; res->coverage_windows = (uint64_t)J.cov_ms[1]; res->stats_ms = J.stats_ms[0]; res->stats_windows = (uint64_t)J.stats_ms[1];
+	int rc = BMH_OK;
+	if (J.coverage && res->coverage) rc = bcv_export(J.CP, J.CR, res->coverage, fn);
+	if (rc == BMH_OK && J.stats && res->stats) rc = bst_export(J.SP, J.SR, res->stats, fn);
+	if (rc != BMH_OK) bsr_results_release(res);
+	return rc;
 }
 
 int bsr_markdup_contigs(int n_contigs, const int32_t *contig_len, const char *const *contig_names, const char *fn)
@@ -74,7 +134,7 @@ int bsr_markdup_contigs(int n_contigs, const int32_t *contig_len, const char *co
 
 int bsr_index_t::init(int n_contigs, const int32_t *contig_len, const char *fn, int fmt, int shift)
 {
-	n_ref = n_contigs; n_win.clear(); lin_off.assign(1, 0); heads.clear(); file_pos = 0; valid = false;
+	n_ref = n_contigs; n_win.clear(); lin_off.assign(1, 0); heads.clear(); file_pos = 0;
 	const int rc = bsr_index_format_check(fmt, shift, fn);
 	if (rc != BMH_OK) return rc;
 	format = fmt; min_shift = fmt == BSR_IX_CSI ? shift : (int)BSR_LIN_SHIFT; depth = BSR_BAI_DEPTH;
@@ -96,7 +156,6 @@ int bsr_index_t::init(int n_contigs, const int32_t *contig_len, const char *fn, 
 	}
 	try { lin.assign(lin_off.back() + 1, ~0ull); counts.assign(2 * (size_t)n_ref + 1, 0); }
 	catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory for %llu index windows", fn, (unsigned long long)lin_off.back()); return BMH_ENOMEM; }
-	valid = true;
 	return BMH_OK;
 }
 
@@ -303,141 +362,90 @@ extern "C" int bmh_bam_sort_host(const uint8_t *recs, uint64_t n_bytes, uint8_t 
 	return BMH_OK;
 }
 
-// header members, the sorted records in windows of `window` records (0: as many as hold about 64 MiB), the end-of-file member; and the index
-static int sorted_file_host(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                            const bmh_sorted_file_opt_t &o, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts, const bdp_plan_t &P,
-                            bcv_host_t *cov = nullptr, bst_host_t *stats = nullptr)
+int bsr_write_host(const uint8_t *recs, const uint64_t *off, const uint32_t *ord, uint64_t n, bsr_out_t &J, bsr_sink_t sink, void *user, const char *fn)
 {
-	const int level = o.level; const uint32_t window = o.window;
-	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
-	if (P.groups() && n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d references: with read groups a run holds at most 2^24 (the library takes the duplicate key's top byte)", fn, n_contigs); return BMH_EINVAL; }
-	bsr_index_t ix;
-	int rc = ix.init(n_contigs, contig_len, fn, o.index_format, o.min_shift);
-	if (rc != BMH_OK) return rc;
-	if (dup_counts && (rc = bsr_markdup_contigs(n_contigs, contig_len, contig_names, fn)) != BMH_OK) return rc;
-	std::vector<uint64_t> off, keys; std::vector<uint32_t> ord;
-	if ((rc = bsr_walk(recs, n_bytes, n_contigs, off, fn)) != BMH_OK) return rc;
-	std::vector<uint8_t> marked;                                   // duplicate marking: the flags are set before the sort (0x400 enters no key, bin or index)
-	if (dup_counts) {
-		marked.assign(recs, recs + n_bytes);
-		if ((rc = bdp_markdup_host(marked.data(), off, dup_counts, fn, P)) != BMH_OK) return rc;
-		recs = marked.data();
-	}
-	bsr_sort_host(recs, off, keys, ord);
-	const size_t n = ord.size();
-	std::string file;
-	auto members = [&](const uint8_t *p, uint64_t nb, std::vector<uint64_t> *moff) {
-		uint8_t *m = nullptr; uint64_t mb = 0;
-		const int r = bmh_bgzf_deflate_host(p, nb, level, 0, &m, &mb);
-		if (r != BMH_OK) return r;
-		if (moff) {                                   // the members' offsets: every member's BSIZE
-			moff->assign(1, 0);
-			for (uint64_t q = 0; q < mb;) { q += ((uint64_t)m[q + 16] | (uint64_t)m[q + 17] << 8) + 1; moff->push_back(q); }
-		}
-		file.append((const char *)m, mb); bmh_free(m);
-		return (int)BMH_OK;
-	};
-	uint8_t *hdr = nullptr; uint64_t hb = 0;
-	if ((rc = bmh_bam_header(header_text, n_contigs, contig_names, contig_len, &hdr, &hb)) != BMH_OK) return rc;
-	rc = members(hdr, hb, nullptr); bmh_free(hdr);
-	if (rc != BMH_OK) return rc;
-	const uint64_t base = file.size();
-	const uint64_t W = window ? window : std::max<uint64_t>(1, (64ull << 20) / std::max<uint64_t>(1, n ? n_bytes / n : 1));
+	bcv_host_t H; bst_host_t SH;
+	if (J.coverage) H.begin(J.CP);
+	if (J.stats) SH.begin(J.SP);
+	const uint64_t W = J.window ? J.window : std::max<uint64_t>(1, (64ull << 20) / std::max<uint64_t>(1, n ? off[n] / n : 1));
 	std::vector<uint8_t> buf; std::vector<uint64_t> soff, moff;
-	for (size_t a = 0; a < n; a += W) {
-		const size_t b = std::min<uint64_t>(n, a + W);
+	int rc;
+	for (uint64_t a = 0; a < n; a += W) {
+		const uint64_t b = std::min<uint64_t>(n, a + W);
 		soff.assign(1, 0); buf.clear();
-		for (size_t j = a; j < b; ++j) { const uint64_t o = off[ord[j]], s = off[ord[j] + 1] - o; buf.insert(buf.end(), recs + o, recs + o + s); soff.push_back(buf.size()); }
-		if ((rc = members(buf.data(), buf.size(), &moff)) != BMH_OK) return rc;
-		ix.window_host(buf.data(), soff.data(), (uint32_t)(b - a), moff.data());
-		if (cov && (rc = cov->window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;      // the window in its final order, with its final flags
-		if (stats && (rc = stats->window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;
+		for (uint64_t j = a; j < b; ++j) { const uint64_t o = off[ord[j]], s = off[ord[j] + 1] - o; buf.insert(buf.end(), recs + o, recs + o + s); soff.push_back(buf.size()); }
+		uint8_t *m = nullptr; uint64_t mb = 0;
+		if ((rc = bmh_bgzf_deflate_host(buf.data(), buf.size(), J.level, 0, &m, &mb)) != BMH_OK) return rc;
+		moff.assign(1, 0);                                // the members' offsets: every member's BSIZE
+		for (uint64_t q = 0; q < mb;) { q += ((uint64_t)m[q + 16] | (uint64_t)m[q + 17] << 8) + 1; moff.push_back(q); }
+		const int sr = sink(user, (const char *)m, (size_t)mb);
+		bmh_free(m);
+		if (sr != 0) { bmh_set_error("the sink refused the text"); return BMH_EINVAL; }
+		J.ix.window_host(buf.data(), soff.data(), (uint32_t)(b - a), moff.data());
+		if (J.coverage && (rc = H.window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;      // the window in its final order, with its final flags
+		if (J.stats && (rc = SH.window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;
 	}
-	if (cov && (rc = cov->finish(fn)) != BMH_OK) return rc;
-	file.append((const char *)bmh_bgzf_eof, 28);
-	std::string ib;
-	if ((rc = ix.bytes(base, ib)) != BMH_OK) return rc;
-	uint8_t *f = (uint8_t *)malloc(file.size() + 1), *i = (uint8_t *)malloc(ib.size() + 1);
-	if (!f || !i) { free(f); free(i); bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
-	memcpy(f, file.data(), file.size()); memcpy(i, ib.data(), ib.size());
-	*bam = f; *bam_bytes = file.size(); *bai = i; *bai_bytes = ib.size();
+	if (J.coverage) { if ((rc = H.finish(fn)) != BMH_OK) return rc; J.CR = std::move(H.R); }
+	if (J.stats) { SH.finish(); J.SR = std::move(SH.R); }
 	return BMH_OK;
 }
 
+int bsr_file_t::begin(const char *f, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
+                      const bmh_sorted_opt_t *opt, uint8_t **bam_, uint64_t *bam_bytes_, uint8_t **index_, uint64_t *index_bytes_, bmh_sorted_results_t *res)
+{
+	fn = f; bam = bam_; bam_bytes = bam_bytes_; index = index_; index_bytes = index_bytes_;
+	if (bam) *bam = nullptr;
+	if (index) *index = nullptr;
+	int rc = bsr_out_make(J, opt, n_contigs, contig_len, contig_names, res, fn);
+	if (rc != BMH_OK) return rc;
+	if (J.P.optical()) { bmh_set_error("%s: a stand-alone sorted file has no optical step: optical_distance stays -1 (bmh_bam_markdup_* counts optical duplicates)", fn); return BMH_EINVAL; }
+	if (!header_text || !bam || !bam_bytes || !index || !index_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	*bam_bytes = *index_bytes = 0;
+	if (J.P.groups() && n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d references: with read groups a run holds at most 2^24 (the library takes the duplicate key's top byte)", fn, n_contigs); return BMH_EINVAL; }
+	if ((rc = bsr_walk(recs, n_bytes, n_contigs, off, fn)) != BMH_OK) return rc;
+	uint8_t *hdr = nullptr, *hm = nullptr; uint64_t hb = 0, hmb = 0;
+	if ((rc = bmh_bam_header(header_text, n_contigs, contig_names, contig_len, &hdr, &hb)) != BMH_OK) return rc;
+	rc = bmh_bgzf_deflate_host(hdr, hb, J.level, 0, &hm, &hmb);
+	bmh_free(hdr);
+	if (rc != BMH_OK) return rc;
+	file.assign((const char *)hm, hmb); bmh_free(hm);
+	base = file.size();
+	return BMH_OK;
+}
+
+int bsr_file_t::end(int rc, bmh_sorted_results_t *res)
+{
+	std::string ib;
+	if (rc == BMH_OK) { file.append((const char *)bmh_bgzf_eof, 28); rc = J.ix.bytes(base, ib); }
+	if (rc == BMH_OK) rc = bsr_out_export(J, res, fn);
+	if (rc == BMH_OK) {
+		uint8_t *f = (uint8_t *)malloc(file.size() + 1), *i = (uint8_t *)malloc(ib.size() + 1);
+		if (!f || !i) { free(f); free(i); bmh_set_error("%s: out of memory", fn); rc = BMH_ENOMEM; }
+		else { memcpy(f, file.data(), file.size()); memcpy(i, ib.data(), ib.size()); *bam = f; *bam_bytes = file.size(); *index = i; *index_bytes = ib.size(); }
+	}
+	if (rc != BMH_OK) bsr_results_release(res);
+	return rc;
+}
+
 extern "C" int bmh_bam_sorted_file_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                        const bmh_sorted_file_opt_t *opt, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res)
+                                        const bmh_sorted_opt_t *opt, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_sorted_results_t *res)
 {
 	const char *fn = "bmh_bam_sorted_file_host";
-	bmh_sorted_file_opt_t o; bdp_plan_t P;
-	const int rc = bsr_file_opt_check(opt, res, fn, o, P);
-	if (rc != BMH_OK) return rc;
-	return sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P);
-}
-
-// the sorted file and, from the same windows of the merge, its coverage (the host form of csrc/bam_cov_kernels.hip)
-extern "C" int bmh_bam_sorted_file_coverage_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                                 const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes,
-                                                 bmh_markdup_counts_t *res, bmh_coverage_t *cov)
-{
-	const char *fn = "bmh_bam_sorted_file_coverage_host";
-	if (bam) *bam = nullptr;                                         // (before anything can be refused: a caller who frees what a failed call left frees nothing)
-	if (index) *index = nullptr;
-	if (!cov) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	memset(cov, 0, sizeof *cov);
-	bmh_sorted_file_opt_t o; bdp_plan_t P;
-	int rc = bsr_file_opt_check(opt, res, fn, o, P);
-	if (rc != BMH_OK) return rc;
-	bmh_coverage_opt_t co; bmh_coverage_opt_default(&co);
-	if (cov_opt) co = *cov_opt;
-	bcv_plan_t CP;
-	if ((rc = bcv_plan_make(CP, co.min_mapq, co.deletions, co.bin, co.tile, n_contigs, contig_len, fn)) != BMH_OK) return rc;
+	bsr_file_t F;
+	int rc;
 	try {
-		bcv_host_t H; H.begin(CP);
-		rc = sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P, &H);
-		if (rc == BMH_OK && (rc = bcv_export(CP, H.R, cov, fn)) != BMH_OK) {      // the one failure behind the file's bytes: they are the call's to release
-			bmh_free(*bam); bmh_free(*index); *bam = *index = nullptr; *bam_bytes = *index_bytes = 0;
+		rc = F.begin(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, opt, bam, bam_bytes, index, index_bytes, res);
+		std::vector<uint8_t> marked;                               // duplicate marking: the flags are set before the sort (0x400 enters no key, bin or index)
+		if (rc == BMH_OK && F.J.markdup) {
+			marked.assign(recs, recs + n_bytes);
+			rc = bdp_markdup_host(marked.data(), F.off, F.J.dup_counts, fn, F.J.P);
+			recs = marked.data();
 		}
-	} catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); rc = BMH_ENOMEM; }
-	return rc;
-}
-
-// the sorted file and, from the same windows of the merge, its statistics and, with cov, its coverage (the host form of csrc/bam_stats_kernels.hip)
-extern "C" int bmh_bam_sorted_file_stats_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                              const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, const bmh_bam_stats_opt_t *stats_opt, uint8_t **bam, uint64_t *bam_bytes,
-                                              uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res, bmh_coverage_t *cov, bmh_bam_stats_t *stats)
-{
-	const char *fn = "bmh_bam_sorted_file_stats_host";
-	if (bam) *bam = nullptr;                                         // (before anything can be refused: a caller who frees what a failed call left frees nothing)
-	if (index) *index = nullptr;
-	if (cov) memset(cov, 0, sizeof *cov);
-	if (!stats) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	memset(stats, 0, sizeof *stats);
-	bmh_sorted_file_opt_t o; bdp_plan_t P;
-	int rc = bsr_file_opt_check(opt, res, fn, o, P);
-	if (rc != BMH_OK) return rc;
-	bmh_bam_stats_opt_t so; bmh_bam_stats_opt_default(&so);
-	if (stats_opt) so = *stats_opt;
-	bst_plan_t SP;
-	if ((rc = bst_plan_make(SP, so.insert_cap, n_contigs, fn)) != BMH_OK) return rc;
-	bmh_coverage_opt_t co; bmh_coverage_opt_default(&co);
-	if (cov_opt) co = *cov_opt;
-	bcv_plan_t CP;
-	if (cov && (rc = bcv_plan_make(CP, co.min_mapq, co.deletions, co.bin, co.tile, n_contigs, contig_len, fn)) != BMH_OK) return rc;
-	try {
-		bcv_host_t H; bst_host_t SH;
-		if (cov) H.begin(CP);
-		SH.begin(SP);
-		rc = sorted_file_host(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P, cov ? &H : nullptr, &SH);
 		if (rc == BMH_OK) {
-			SH.finish();
-			if (cov) rc = bcv_export(CP, H.R, cov, fn);
-			if (rc == BMH_OK && (rc = bst_export(SP, SH.R, stats, fn)) != BMH_OK && cov) {
-				bmh_free(cov->n_reads); bmh_free(cov->cov_bases); bmh_free(cov->sum_depth); bmh_free(cov->max_depth); bmh_free(cov->sum_mapq); bmh_free(cov->hist); bmh_free(cov->bin_sum);
-				memset(cov, 0, sizeof *cov);
-			}
-			if (rc != BMH_OK) { bmh_free(*bam); bmh_free(*index); *bam = *index = nullptr; *bam_bytes = *index_bytes = 0; }      // the failures behind the file's bytes: they are the call's to release
+			std::vector<uint64_t> keys; std::vector<uint32_t> ord;
+			bsr_sort_host(recs, F.off, keys, ord);
+			rc = bsr_write_host(recs, F.off.data(), ord.data(), ord.size(), F.J, bsr_sink_string, &F.file, fn);
 		}
 	} catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); rc = BMH_ENOMEM; }
-	return rc;
+	return F.end(rc, res);
 }

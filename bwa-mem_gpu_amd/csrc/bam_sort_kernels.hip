@@ -312,9 +312,11 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 }
 
 // every run of the store -> the sorted file's record members (to the sink) and its index
-int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint32_t window, int level, void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, uint64_t *dup_counts,
-                     const bdp_plan_t &P, double *dup_ms, double *opt_ms, bcv_dev_t *cov, double *cov_ms, bst_dev_t *stats, double *stats_ms)
+int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_out_t &J, void *stream, bsr_sink_t sink, void *user, bcv_dev_t *cov, bst_dev_t *stats)
 {
+	const bdp_plan_t &P = J.P; bsr_index_t &ix = J.ix; const int level = J.level; const uint32_t window = J.window;
+	uint64_t *const dup_counts = J.markdup ? J.dup_counts : nullptr;
+	double *const cov_ms = J.timed && cov ? J.cov_ms : nullptr, *const stats_ms = J.timed && stats ? J.stats_ms : nullptr;
 	const bdp_optical_t *optical = P.optical(); const bool barcode = P.barcode() != nullptr;
 	uint64_t n = 0, bytes = 0;
 	std::vector<uint64_t> first;
@@ -369,16 +371,37 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, uint3
 		}
 	}
 	if (dup_counts) {
-		if (dup_ms) { dup_ms[0] += decide_ms; dup_ms[1] += flag_ms; }
+		if (J.timed) { J.dup_ms[0] += decide_ms; J.dup_ms[1] += flag_ms; }
 		if (getenv("BMH_ALIGNER_TRACE"))
 			fprintf(stderr, "[aligner] duplicate marking: %zu templates (%zu bytes of entries, %llu of ordinals kept) decided in %.2f ms, the windows' flags set in %.2f ms\n", S.entries.size(),
 			        sizeof(bdp_entry_t) * S.entries.size(), 4ull * (unsigned long long)n, decide_ms, flag_ms);
-		if (opt_ms) *opt_ms += o_ms;
+		if (J.timed) J.opt_ms += o_ms;
 		if (optical && getenv("BMH_ALIGNER_TRACE"))
 			fprintf(stderr, "[aligner] optical duplicates: %zu bytes of locations, %llu optical pairs among %llu located ones (%llu sets skipped) counted in %.1f of the decision's ms\n",
 			        sizeof(bdp_loc_t) * S.locs.size(), (unsigned long long)optical->out[BDP_OPT_DUPS], (unsigned long long)optical->out[BDP_OPT_LOCATED], (unsigned long long)optical->out[BDP_OPT_SKIPPED], o_ms);
 	}
 	return bsr_index_finish(d, ix, stream);
+}
+
+int bsr_write_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_out_t &J, void *stream, bsr_sink_t sink, void *user, const char *fn)
+{
+	struct cov_own_t { bcv_dev_t *p = nullptr; ~cov_own_t() { if (p) bcv_dev_free(p); } } cov;            // the run's device state, from the first window to the results
+	struct stats_own_t { bst_dev_t *p = nullptr; ~stats_own_t() { if (p) bst_dev_free(p); } } stats;
+	if (J.markdup && J.P.no_barcode) *J.P.no_barcode = J.P.barcode() ? bdp_no_barcode(S.bcs.data(), S.bcs.size()) : 0;
+	if (J.coverage) {
+		if (!(cov.p = bcv_dev_create())) return BMH_ENOMEM;
+		RCK(bcv_begin_device(cov.p, J.CP, stream));
+	}
+	if (J.stats) {
+		if (!(stats.p = bst_dev_create())) return BMH_ENOMEM;
+		RCK(bst_begin_device(stats.p, J.SP, stream));
+	}
+	RCK(bsr_merge_device(d, ws, S, J, stream, sink, user, cov.p, stats.p));
+	if (stats.p) RCK(bst_finish_device(stats.p, stream, J.SR, fn));
+	if (cov.p) RCK(bcv_finish_device(cov.p, stream, J.CR, fn, J.timed ? J.cov_ms : nullptr));
+	if (J.markdup && J.P.groups() && J.P.lib_counts)                   // every library's line counts and templates, as the batches counted them
+		for (size_t k = 0; k < S.lib_info.size() && k / 3 < J.P.n_lib(); ++k) J.P.lib_counts[BDP_N_COUNTS * (k / 3) + BDP_SECSUP + k % 3] = S.lib_info[k];
+	return BMH_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the stand-alone entry points
@@ -424,7 +447,6 @@ int to_store(bsr_dev_t *d, const uint8_t *recs, uint64_t n_bytes, const std::vec
 	if (soff[n] != n_bytes) { bmh_set_error("sorted BAM: internal error: the sorted records hold %llu bytes, the input %llu", (unsigned long long)soff[n], (unsigned long long)n_bytes); return BMH_EINVAL; }
 	return BMH_OK;
 }
-int sink_string(void *user, const char *b, size_t n) { ((std::string *)user)->append(b, n); return 0; }
 }   // namespace
 
 extern "C" int bmh_bam_sort_device(const uint8_t *recs, uint64_t n_bytes, void *stream, uint8_t **out)
@@ -443,126 +465,38 @@ extern "C" int bmh_bam_sort_device(const uint8_t *recs, uint64_t n_bytes, void *
 	return BMH_OK;
 }
 
-static int sorted_file_device(const char *fn, const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                              const bmh_sorted_file_opt_t &o, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **bai, uint64_t *bai_bytes, uint64_t *dup_counts, const bdp_plan_t &P,
-                              const bmh_coverage_opt_t *cov_opt = nullptr, bmh_coverage_t *cov_out = nullptr, const bmh_bam_stats_opt_t *stats_opt = nullptr, bmh_bam_stats_t *stats_out = nullptr)
+// the records of a checked stand-alone file (csrc/bam_sort.h: bsr_file_t) -> one sorted run, merged into F.file
+static int sorted_file_device(bsr_file_t &F, const uint8_t *recs, uint64_t n_bytes, void *stream)
 {
-	const int level = o.level; const uint32_t window = o.window;
-	const bdp_table_t *G = P.groups();
-	bcv_plan_t CP; bcv_dev_t *cov = nullptr;
-	struct cov_own_t { bcv_dev_t *p = nullptr; ~cov_own_t() { if (p) bcv_dev_free(p); } } cov_own;
-	bst_plan_t SP; bst_dev_t *stats = nullptr;
-	struct stats_own_t { bst_dev_t *p = nullptr; ~stats_own_t() { if (p) bst_dev_free(p); } } stats_own;
-	if (stats_out) {
-		memset(stats_out, 0, sizeof *stats_out);
-		bmh_bam_stats_opt_t so; bmh_bam_stats_opt_default(&so);
-		if (stats_opt) so = *stats_opt;
-		RCK(bst_plan_make(SP, so.insert_cap, n_contigs, fn));
-	}
-	if (cov_out) {
-		memset(cov_out, 0, sizeof *cov_out);
-		bmh_coverage_opt_t co; bmh_coverage_opt_default(&co);
-		if (cov_opt) co = *cov_opt;
-		RCK(bcv_plan_make(CP, co.min_mapq, co.deletions, co.bin, co.tile, n_contigs, contig_len, fn));
-	}
-	if (!header_text || !bam || !bam_bytes || !bai || !bai_bytes || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	*bam = *bai = nullptr; *bam_bytes = *bai_bytes = 0;
-	if (G && n_contigs > (int)BDP_MAX_REF) { bmh_set_error("%s: %d references: with read groups a run holds at most 2^24 (the library takes the duplicate key's top byte)", fn, n_contigs); return BMH_EINVAL; }
-	if (level != 0 && level != 1) { bmh_set_error("%s: level %d (0 or 1)", fn, level); return BMH_EINVAL; }
-	bsr_index_t ix;
-	RCK(ix.init(n_contigs, contig_len, fn, o.index_format, o.min_shift));
-	if (dup_counts) RCK(bsr_markdup_contigs(n_contigs, contig_len, contig_names, fn));
-	std::vector<uint64_t> off, keys, soff; std::vector<uint8_t> sorted;
-	RCK(bsr_walk(recs, n_bytes, n_contigs, off, fn));
+	const char *fn = F.fn; bsr_out_t &J = F.J; const std::vector<uint64_t> &off = F.off; const bdp_plan_t &P = J.P;
+	std::vector<uint64_t> keys, soff; std::vector<uint8_t> sorted;
 	bsr_dev_t d;
 	bsr_store_t S;
-	if (dup_counts)
+	if (J.markdup)
 		for (size_t i = 0; i + 1 < off.size(); ++i)
 			if (!bdp_record_whole(recs + off[i], off[i + 1] - off[i])) { bmh_set_error("%s: record %zu is cut: its bases and qualities do not lie inside its block_size", fn, i); return BMH_EINVAL; }
 	dup_host_t dh;
 	if (off.size() > 1) {
-		RCK(to_store(&d, recs, n_bytes, off, (hipStream_t)stream, sorted, keys, soff, dup_counts ? &dh : nullptr, fn, P));
+		RCK(to_store(&d, recs, n_bytes, off, (hipStream_t)stream, sorted, keys, soff, J.markdup ? &dh : nullptr, fn, P));
 		bsr_dup_t bd = {dh.tpl.data(), dh.entries.data(), (uint32_t)dh.entries.size(), dh.secsup, dh.unmapped};
-		if (P.barcode()) { bd.bcs = dh.bcs.data(); if (P.no_barcode) *P.no_barcode = bdp_no_barcode(dh.bcs.data(), dh.bcs.size()); }
-		RCK(S.append(sorted.data(), n_bytes, keys.data(), soff.data(), off.size() - 1, dup_counts ? &bd : nullptr));
-	}
-	std::string file;
-	uint8_t *hdr = nullptr, *hm = nullptr; uint64_t hb = 0, hmb = 0;
-	RCK(bmh_bam_header(header_text, n_contigs, contig_names, contig_len, &hdr, &hb));
-	int rc = bmh_bgzf_deflate_host(hdr, hb, level, 0, &hm, &hmb);
-	bmh_free(hdr);
-	if (rc != BMH_OK) return rc;
-	file.append((const char *)hm, hmb); bmh_free(hm);
-	const uint64_t base = file.size();
-	if (cov_out) {
-		if (!(cov = cov_own.p = bcv_dev_create())) return BMH_ENOMEM;
-		RCK(bcv_begin_device(cov, CP, stream));
-	}
-	if (stats_out) {
-		if (!(stats = stats_own.p = bst_dev_create())) return BMH_ENOMEM;
-		RCK(bst_begin_device(stats, SP, stream));
+		if (P.barcode()) bd.bcs = dh.bcs.data();
+		RCK(S.append(sorted.data(), n_bytes, keys.data(), soff.data(), off.size() - 1, J.markdup ? &bd : nullptr));
 	}
 	bmh_bam_ws_t *ws = bmh_bam_ws_create();
-	rc = bsr_merge_device(&d, ws, S, window, level, stream, ix, sink_string, &file, dup_counts, P, nullptr, nullptr, cov, nullptr, stats, nullptr);
+	const int rc = bsr_write_device(&d, ws, S, J, stream, bsr_sink_string, &F.file, fn);
 	bmh_bam_ws_free(ws);
 	if (rc != BMH_OK) return rc;
-	if (stats) { bst_result_t SR; RCK(bst_finish_device(stats, stream, SR, fn)); RCK(bst_export(SP, SR, stats_out, fn)); }
-	if (cov) { bcv_result_t CR; RCK(bcv_finish_device(cov, stream, CR, fn, nullptr)); RCK(bcv_export(CP, CR, cov_out, fn)); }
-	if (G && P.lib_counts && off.size() > 1)
-		bdp_lib_tally_host(sorted.data(), soff.data(), (uint32_t)(off.size() - 1), dh.tpl.data(), dh.entries.data(), dh.entries.size(), G->n_lib, P.lib_counts);
-	file.append((const char *)bmh_bgzf_eof, 28);
-	std::string ib;
-	RCK(ix.bytes(base, ib));
-	uint8_t *f = (uint8_t *)malloc(file.size() + 1), *i = (uint8_t *)malloc(ib.size() + 1);
-	if (!f || !i) { free(f); free(i); bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
-	memcpy(f, file.data(), file.size()); memcpy(i, ib.data(), ib.size());
-	*bam = f; *bam_bytes = file.size(); *bai = i; *bai_bytes = ib.size();
+	if (P.groups() && P.lib_counts && off.size() > 1)
+		bdp_lib_tally_host(sorted.data(), soff.data(), (uint32_t)(off.size() - 1), dh.tpl.data(), dh.entries.data(), dh.entries.size(), P.n_lib(), P.lib_counts);
 	return BMH_OK;
 }
 
 extern "C" int bmh_bam_sorted_file_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                          const bmh_sorted_file_opt_t *opt, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res)
+                                          const bmh_sorted_opt_t *opt, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_sorted_results_t *res)
 {
 	const char *fn = "bmh_bam_sorted_file_device";
-	bmh_sorted_file_opt_t o; bdp_plan_t P;
-	RCK(bsr_file_opt_check(opt, res, fn, o, P));
-	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, stream, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P);
-}
-
-// the sorted file and, from the same windows, its coverage (csrc/bam_cov_kernels.hip): duplicates marked by opt->markdup are counted out
-extern "C" int bmh_bam_sorted_file_coverage_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                                   const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index,
-                                                   uint64_t *index_bytes, bmh_markdup_counts_t *res, bmh_coverage_t *cov)
-{
-	const char *fn = "bmh_bam_sorted_file_coverage_device";
-	if (bam) *bam = nullptr;                                         // (before anything can be refused: a caller who frees what a failed call left frees nothing)
-	if (index) *index = nullptr;
-	if (!cov) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	memset(cov, 0, sizeof *cov);
-	bmh_sorted_file_opt_t o; bdp_plan_t P;
-	RCK(bsr_file_opt_check(opt, res, fn, o, P));
-	// (the coverage is exported before the file's bytes are allocated: a failed call holds neither)
-	return sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, stream, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P, cov_opt, cov);
-}
-
-// the sorted file and, from the same windows, its statistics (csrc/bam_stats_kernels.hip) and, with cov, its coverage: both see the flags opt->markdup sets
-extern "C" int bmh_bam_sorted_file_stats_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *recs, uint64_t n_bytes,
-                                                const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, const bmh_bam_stats_opt_t *stats_opt, void *stream, uint8_t **bam,
-                                                uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res, bmh_coverage_t *cov, bmh_bam_stats_t *stats)
-{
-	const char *fn = "bmh_bam_sorted_file_stats_device";
-	if (bam) *bam = nullptr;                                         // (before anything can be refused: a caller who frees what a failed call left frees nothing)
-	if (index) *index = nullptr;
-	if (cov) memset(cov, 0, sizeof *cov);
-	if (!stats) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	memset(stats, 0, sizeof *stats);
-	bmh_sorted_file_opt_t o; bdp_plan_t P;
-	RCK(bsr_file_opt_check(opt, res, fn, o, P));
-	const int rc = sorted_file_device(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, o, stream, bam, bam_bytes, index, index_bytes, o.markdup ? res->counts : nullptr, P,
-	                                  cov_opt, cov, stats_opt, stats);
-	if (rc != BMH_OK) {                                              // (whatever was exported before the failure goes back)
-		bmh_bam_stats_free(stats);
-		if (cov) { bmh_free(cov->n_reads); bmh_free(cov->cov_bases); bmh_free(cov->sum_depth); bmh_free(cov->max_depth); bmh_free(cov->sum_mapq); bmh_free(cov->hist); bmh_free(cov->bin_sum); memset(cov, 0, sizeof *cov); }
-	}
-	return rc;
+	bsr_file_t F;
+	int rc = F.begin(fn, header_text, n_contigs, contig_names, contig_len, recs, n_bytes, opt, bam, bam_bytes, index, index_bytes, res);
+	if (rc == BMH_OK) rc = sorted_file_device(F, recs, n_bytes, stream);
+	return F.end(rc, res);
 }

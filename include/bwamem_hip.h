@@ -910,29 +910,69 @@ int bmh_aligner_set_output(bmh_aligner_t *a, int format, int level);
  * The order is `samtools sort`'s: key (uint32)refID << 32 | (uint32)(pos + 1) << 1 | reverse strand; records without a reference last; equal keys in the order
  * they came in.  The index is the SAM specification's section 5.2 (bins as the records carry them, the pseudo-bin 37450, the 16 KiB linear index, n_no_coor).
  * bmh_bam_sort_device / _host: a record stream in host memory (whole records, else refused) -> the same records in order (malloc'd; bmh_free).
- * bmh_bam_sorted_file_device / _host: header members, the sorted records in windows of `window` records (0: about 64 MiB of records; a window's last member
- * is short), the end-of-file member; and the .bai bytes.  Both forms give the same bytes.  A contig of 2^29 bases or more is refused (BAI cannot index it;
- * a CSI index, below, takes it).
- * bmh_aligner_set_output(a, BMH_OUT_BAM_SORTED, level): every batch becomes a sorted run kept on the host (in memory up to mem_bytes of records, beyond that in
- * an unnamed temporary file in tmp_dir); at the end of the input all runs' keys are sorted once more on the device -- 24 bytes of device memory per record and
- * the sort's work space, fewer than 2^32 records, else the run is refused with a message naming the count -- and the sink receives the record members of the
- * sorted file, window after window.  The header members and the end-of-file member stay with the caller.
- * bmh_aligner_set_sort: the run store's budget (0: 4 GiB), its directory (NULL: $TMPDIR, else /tmp) and the window (0: about 64 MiB of records).
+ * A contig of 2^29 bases or more is refused (BAI cannot index it; a CSI index, below, takes it).
+ *
+ * One options record and one results record serve every place sorted output is made -- bmh_bam_sorted_file_*, bmh_bam_post_file_* (below) and the aligner's
+ * BMH_OUT_BAM_SORTED runs -- and everything it can do there: sort, index, mark duplicates, compute coverage, compute statistics.
+ * bmh_sorted_opt_t: the BGZF level (0 or 1); window: records per window of the merge (0: about 64 MiB of records; a window's last member is short); the index
+ * (BMH_INDEX_*; min_shift is read for CSI only); sort_mem: record bytes the run store keeps in memory before runs spill to an unnamed file in tmp_dir (0: 4 GiB;
+ * NULL: $TMPDIR, else /tmp); markdup, coverage, stats: the options of duplicate marking, coverage and statistics (the sections below), NULL: off.
+ * bmh_sorted_opt_default: level 1, window 0, a BAI index (min_shift 14), the store's defaults, everything off; an opt of NULL means the same.
+ * bmh_sorted_results_t: markdup, coverage, stats -- the caller's records, each required exactly when the matching option is set (else BMH_EINVAL) and not read
+ * otherwise; the arrays of *coverage and *stats are malloc'd (bmh_free each / bmh_bam_stats_free).  The device milliseconds and the windows timed are filled by
+ * aligner runs only: the stand-alone calls time nothing and leave them 0.  results may be NULL where no option asks for a record.
+ * Every call zeroes the results and the records they name first, and a failed call leaves *bam, *index (bmh_bam_post_file_*: out's pointers) and every array of
+ * *coverage and *stats NULL, whatever they held before: a caller who frees what a failed call left frees nothing.
+ * The options are checked in one order, before anything is written: level; the index format and the contigs it can hold; markdup (barcode source, edits, optical
+ * step, read groups, then the contigs marking can hold); coverage; stats.
+ * bmh_bam_sorted_file_device / _host: a record stream in host memory -> header members, the sorted records in windows, the end-of-file member; and the .bai or
+ * .csi bytes (both malloc'd; bmh_free).  Both forms give the same bytes.  With opt->markdup the stream comes in the writer's order; the optical step is not part
+ * of a stand-alone file: optical_distance stays -1, else BMH_EINVAL.  sort_mem and tmp_dir are not read here: the one run stays in memory.
+ * bmh_aligner_set_sorted_output: the runs that follow write BMH_OUT_BAM_SORTED under opt (NULL: the defaults).  Every batch becomes a sorted run kept on the host;
+ * at the end of the input all runs' keys are sorted once more on the device -- 24 bytes of device memory per record and the sort's work space, fewer than 2^32
+ * records, else the run is refused with a message naming the count -- and the sink receives the record members of the sorted file, window after window.  The
+ * header members and the end-of-file member stay with the caller.  Everything is checked, in the order above, before anything changes: a refused call leaves the
+ * aligner exactly as it was.  Read groups come from bmh_aligner_run_groups or bmh_aligner_set_keep_rg: a markdup record with rg_ids is refused.
+ * bmh_aligner_set_output(a, BMH_OUT_BAM_SORTED, level) is bmh_aligner_set_sorted_output with the default record at that level; any other format switches every
+ * option of the sorted output off.
+ * bmh_aligner_sorted_results: what the last sorted run left.  out->parts: the BMH_SORTED_* parts it computed; n_libraries: the libraries of a marked run over read
+ * groups (else 0); the milliseconds -- markdup_ms: the decision (host clock) and the windows' flag steps, markdup_d2h_bytes: the ordinals and entries that came down
+ * with the batches, optical_ms: the decision's share that the optical step took, coverage_ms / stats_ms: the windows' steps on the device's stream and the windows
+ * timed.  A record of out that is not NULL is filled (lib_counts [8 * n_libraries] and lib_optical [3 * n_libraries], the caller's arrays or NULL; lib_grouped is not
+ * written: an aligner run does not count groups per library); it and every part in `need` must be among the parts, else BMH_EINVAL saying which part no run has computed.
  * bmh_aligner_sort_index: the index of the last sorted run (malloc'd; bmh_free); base_offset: the bytes the caller wrote before the sink's first. */
 #define BMH_OUT_BAM_SORTED 2
 int bmh_bam_sort_device(const uint8_t *records, uint64_t n_bytes, void *stream, uint8_t **out);
 int bmh_bam_sort_host(const uint8_t *records, uint64_t n_bytes, uint8_t **out);
-typedef struct bmh_markdup_opt bmh_markdup_opt_t;                  /* (below, with duplicate marking) */
+typedef struct bmh_markdup_opt bmh_markdup_opt_t;                  /* (below, with duplicate marking, coverage and the statistics) */
 typedef struct bmh_markdup_counts bmh_markdup_counts_t;
-/* what a sorted file is made under: the BGZF level (0 or 1), the window, the index (BMH_INDEX_*; min_shift is read for CSI only) and, to mark the duplicates of a
- * stream given in the writer's order, the marking options (NULL: no marking; their optical step is not part of a stand-alone file: optical_distance stays -1,
- * else BMH_EINVAL).  opt NULL: level 1, window 0, a BAI index, no marking.  res: the marking's counts (NULL without marking). */
-typedef struct { int32_t level; uint32_t window; int32_t index_format, min_shift; const bmh_markdup_opt_t *markdup; } bmh_sorted_file_opt_t;
+typedef struct bmh_coverage_opt bmh_coverage_opt_t;
+typedef struct bmh_coverage bmh_coverage_t;
+typedef struct bmh_bam_stats_opt bmh_bam_stats_opt_t;
+typedef struct bmh_bam_stats bmh_bam_stats_t;
+typedef struct {
+	int32_t level; uint32_t window; int32_t index_format, min_shift;
+	uint64_t sort_mem; const char *tmp_dir;
+	const bmh_markdup_opt_t *markdup; const bmh_coverage_opt_t *coverage; const bmh_bam_stats_opt_t *stats;
+} bmh_sorted_opt_t;
+#define BMH_SORTED_MARKDUP 1u
+#define BMH_SORTED_OPTICAL 2u
+#define BMH_SORTED_BARCODE 4u
+#define BMH_SORTED_GROUPED 8u
+#define BMH_SORTED_COVERAGE 16u
+#define BMH_SORTED_STATS 32u
+typedef struct {
+	bmh_markdup_counts_t *markdup; bmh_coverage_t *coverage; bmh_bam_stats_t *stats;
+	uint32_t parts; int32_t n_libraries;
+	double markdup_ms[2], optical_ms, coverage_ms, stats_ms; uint64_t markdup_d2h_bytes, coverage_windows, stats_windows;
+} bmh_sorted_results_t;
+void bmh_sorted_opt_default(bmh_sorted_opt_t *o);
 int bmh_bam_sorted_file_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                               const bmh_sorted_file_opt_t *opt, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res);
+                               const bmh_sorted_opt_t *opt, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_sorted_results_t *results);
 int bmh_bam_sorted_file_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                             const bmh_sorted_file_opt_t *opt, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res);
-int bmh_aligner_set_sort(bmh_aligner_t *a, uint64_t mem_bytes, const char *tmp_dir, uint32_t window_records);
+                             const bmh_sorted_opt_t *opt, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_sorted_results_t *results);
+int bmh_aligner_set_sorted_output(bmh_aligner_t *a, const bmh_sorted_opt_t *opt);
+int bmh_aligner_sorted_results(bmh_aligner_t *a, bmh_sorted_results_t *out, uint32_t need);
 int bmh_aligner_sort_index(bmh_aligner_t *a, uint64_t base_offset, uint8_t **bai, uint64_t *bai_bytes);
 
 /* ---- A CSI index in place of the BAI, for contigs of 2^29 bases and more (BAM holds positions up to 2^31 - 1; only BAI's bins stop at 2^29).  Opt-in: without
@@ -946,14 +986,12 @@ int bmh_aligner_sort_index(bmh_aligner_t *a, uint64_t base_offset, uint8_t **bai
  *   uint64 n_no_coor
  * loffset: the smallest begin offset over the records that overlap the bin's first window, or, if none does, the next window that has one; 0 for the pseudo-bin,
  * whose two chunks are (first begin, last end) and (mapped, unmapped).  A reference without records has n_bin 0.
- * bmh_aligner_set_index_format: the index of the sorted runs that follow; it comes before bmh_aligner_set_output(.., BMH_OUT_BAM_SORTED, ..), which checks the
- * contig lengths against it as every run's begin does (BAI: below 2^29; CSI: at most 2^31 - 1, and an index of fewer than 2^28 windows).  bmh_aligner_sort_index
- * gives the bytes of the format the last sorted run was made under.  For BMH_INDEX_BAI min_shift is not read.
- * Duplicate marking holds an unclipped end in 31 bits around 2^30: with it on, a contig beyond 2^30 - 2^24 bases is refused by name before anything is written.
- * bmh_bam_sorted_file_device / _host with index_format BMH_INDEX_CSI give the index of that format in *index. */
+ * index_format BMH_INDEX_CSI and min_shift in bmh_sorted_opt_t ask for it; the contig lengths are checked against the format where the options are (BAI: below
+ * 2^29; CSI: at most 2^31 - 1, and an index of fewer than 2^28 windows).  bmh_aligner_sort_index gives the bytes of the format the last sorted run was made under.
+ * For BMH_INDEX_BAI min_shift is not read.
+ * Duplicate marking holds an unclipped end in 31 bits around 2^30: with it on, a contig beyond 2^30 - 2^24 bases is refused by name before anything is written. */
 #define BMH_INDEX_BAI 0
 #define BMH_INDEX_CSI 1
-int bmh_aligner_set_index_format(bmh_aligner_t *a, int index_format, int min_shift);
 
 /* ---- Duplicate marking in sorted BAM (csrc/bam_dup_core.h, csrc/bam_dup_kernels.hip, csrc/bam_dup_host.cpp).
  * Picard MarkDuplicates' rules on templates (a single read or a read pair, its records next to each other in the writer's order): the unclipped 5' ends and
@@ -967,9 +1005,7 @@ int bmh_aligner_set_index_format(bmh_aligner_t *a, int index_format, int min_shi
  * lib_grouped [3 * n_lib] are the caller's arrays (or NULL), filled with read groups only.
  * bmh_bam_markdup_device / _host: a record stream in the writer's order (whole records; the first begins a template; paired templates hold both primary lines --
  * else BMH_EINVAL with a message) -> the same records with the flags set (malloc'd; bmh_free).  opt NULL: plain marking; res is required.
- * bmh_bam_sorted_file_device / _host with opt->markdup: the duplicates of the stream (given in the writer's order) marked.
- * bmh_aligner_set_markdup: the runs that follow mark duplicates; refused (the aligner stays as it was) unless the output format is BMH_OUT_BAM_SORTED, and switched
- * off by every bmh_aligner_set_output of another format.  bmh_aligner_markdup_counts: the counts of the last marked run. */
+ * bmh_sorted_opt_t's markdup: the duplicates of a sorted output marked under the same record, its counts in the results' markdup. */
 struct bmh_markdup_opt {
 	const char *const *rg_ids; const int32_t *rg_lib; int32_t n_groups;   /* all NULL / 0: no read groups */
 	int64_t  optical_distance;      /* -1: no optical step */
@@ -986,7 +1022,6 @@ struct bmh_markdup_counts {
 };
 int bmh_bam_markdup_device(const uint8_t *records, uint64_t n_bytes, const bmh_markdup_opt_t *opt, void *stream, uint8_t **out, bmh_markdup_counts_t *res);
 int bmh_bam_markdup_host(const uint8_t *records, uint64_t n_bytes, const bmh_markdup_opt_t *opt, uint8_t **out, bmh_markdup_counts_t *res);
-int bmh_aligner_set_markdup(bmh_aligner_t *a, int on);
 int bmh_aligner_set_bam_pairs(bmh_aligner_t *a, uint64_t batch_bases, int n_lanes);        /* (described with bmh_bam_reads_device above) */
 int bmh_aligner_set_collate(bmh_aligner_t *a, int on, uint64_t mem_bytes);                  /* (described with bmh_reads_last_collate_counts above) */
 /* Keep the input's read groups (off by default; with it off nothing about a run changes).  bmh_aligner_run_files then takes one BAM -- a regular file or a pipe --
@@ -995,15 +1030,11 @@ int bmh_aligner_set_collate(bmh_aligner_t *a, int on, uint64_t mem_bytes);      
  * any number of groups and is cut as without the option, and a read's index (the tie-break hash) is its index in the file.  `header` is called once, after the
  * input's header has been read whole and before the first call of the sink: rg_lines holds the @RG lines verbatim, each with a '\n' behind it -- what the caller
  * writes into its output header --, lib [n_groups] every group's library (bmh_bam_header_read_groups); a non-zero return ends the run.  A refused header ends the
- * run before either is called.  With BMH_OUT_BAM_SORTED and duplicate marking the duplicates are called within a library and bmh_aligner_markdup_library_counts gives
+ * run before either is called.  With BMH_OUT_BAM_SORTED and duplicate marking the duplicates are called within a library and bmh_aligner_sorted_results gives
  * a row per library.  Refused: text input, a mates file, an aligner with a read group of its own (popt->rg_id), bmh_aligner_run_groups (keep-rg and a run over
  * groups do not combine), more than 255 libraries with duplicate marking. */
 typedef int (*bmh_rg_header_fn)(void *user, const char *rg_lines, size_t len, int n_groups, const int32_t *lib);
 int bmh_aligner_set_keep_rg(bmh_aligner_t *a, int on, bmh_rg_header_fn header, void *user);
-int bmh_aligner_markdup_counts(bmh_aligner_t *a, uint64_t out[8]);
-/* where the last marked run's extra time went: [0] the decision, ms  [1] the windows' flag steps (ordinals up, flag kernel), ms  [2] bytes of ordinals and entries
- * that came down with the batches */
-int bmh_aligner_markdup_times(bmh_aligner_t *a, double out[3]);
 
 /* ---- Read groups and libraries.
  * Duplicates per library: rg_ids [n_groups] and rg_lib [n_groups] are the run's read groups and every group's library index (0 .. 254; groups with one index are
@@ -1011,9 +1042,7 @@ int bmh_aligner_markdup_times(bmh_aligner_t *a, double out[3]);
  * pair's end, and the best fragment stays, within one library only.  The library takes the top byte of the duplicate key, above the refID: more than 255 libraries,
  * a refID of 2^24 or more, an empty table, an empty ID and two rows with one ID are refused (BMH_EINVAL) before anything is allocated; so is a template whose first
  * record has no RG:Z tag or names a group the table does not hold, by the record's index.  counts [8]: the totals, as without groups.  lib_counts (or NULL)
- * [8 * n_lib], n_lib = 1 + the largest index: the same eight per library.  Without groups no tag is read.
- * bmh_aligner_markdup_library_counts: library `lib`'s eight of the last marked run over read groups. */
-int bmh_aligner_markdup_library_counts(bmh_aligner_t *a, int lib, uint64_t out[8]);
+ * [8 * n_lib], n_lib = 1 + the largest index: the same eight per library.  Without groups no tag is read. */
 
 /* ---- Optical duplicates and the library-size estimate (csrc/bam_dup_core.h).  Counts only: the records, the flags, the file and its index are
  * byte for byte those of the call without the option (Picard flags nothing more for an optical duplicate by default).
@@ -1027,18 +1056,12 @@ int bmh_aligner_markdup_library_counts(bmh_aligner_t *a, int lib, uint64_t out[8
  * bmh_bam_dup_locations_device / _host: a record stream -> *locs: one 16-byte location per template {int32 x, y; uint32 tile; uint16 group row; uint16 flags --
  * 1: located, 2: role} (malloc'd; bmh_free), *n_templates of them.
  * bmh_bam_name_location: the parser on the host -> 1 and out = {tile, x, y}, or 0: no location.
- * bmh_library_size: Picard's estimateLibrarySize of n_pairs pairs that are no optical duplicates, n_unique of them distinct -> 1 and *size, or 0: no estimate.
- * bmh_aligner_set_markdup_optical: the marked runs that follow count optical duplicates within `distance` (-1: off, the default); refused unless marking is on,
- * and switched off wherever marking is.  bmh_aligner_markdup_optical_counts: the three counts of the last such run, of library `lib` or (-1) in total.
- * bmh_aligner_markdup_optical_ms: the milliseconds of the decision that the optical step took (the locations' upload included). */
+ * bmh_library_size: Picard's estimateLibrarySize of n_pairs pairs that are no optical duplicates, n_unique of them distinct -> 1 and *size, or 0: no estimate. */
 int bmh_bam_dup_locations_device(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, void *stream, uint8_t **locs,
                                  uint64_t *n_templates);
 int bmh_bam_dup_locations_host(const uint8_t *records, uint64_t n_bytes, const char *const *rg_ids, const int32_t *rg_lib, int n_groups, uint8_t **locs, uint64_t *n_templates);
 int bmh_bam_name_location(const char *name, uint32_t len, uint32_t out[3]);
 int bmh_library_size(uint64_t n_pairs, uint64_t n_unique, int64_t *size);
-int bmh_aligner_set_markdup_optical(bmh_aligner_t *a, int64_t distance);
-int bmh_aligner_markdup_optical_counts(bmh_aligner_t *a, int lib, uint64_t out[3]);
-int bmh_aligner_markdup_optical_ms(bmh_aligner_t *a, double *out);
 
 /* ---- Barcode-aware duplicate keys (UMIs; csrc/bam_dup_core.h).  Opt-in: without it every output byte is that of the calls above.
  * A template's barcode comes from its first record -- the record its library and its location come from.  barcode_mode 1 (a tag): the value of tag `tag` (two
@@ -1052,14 +1075,10 @@ int bmh_aligner_markdup_optical_ms(bmh_aligner_t *a, double *out);
  * bmh_bam_dup_barcodes_device / _host: a record stream -> *words: one uint64 per template (malloc'd; bmh_free), *n_templates of them; barcode_mode 1 or 2; packed
  * != 0: the packed words that grouping by edits compares (below).
  * bmh_barcode_word: the word of a value of n bytes.
- * bmh_aligner_set_markdup_barcode: the marked runs that follow compare barcodes (mode as above; 0: off, the default); refused unless marking is on, and switched
- * off wherever marking is.  A tag reaches the records of an aligner run only as a read's comment (-C).
- * bmh_aligner_markdup_barcode_counts: out [0]: the templates without a barcode in the last such run. */
+ * A tag reaches the records of an aligner run only as a read's comment (-C). */
 int bmh_bam_dup_barcodes_device(const uint8_t *records, uint64_t n_bytes, int barcode_mode, const char tag[2], int packed, void *stream, uint64_t **words, uint64_t *n_templates);
 int bmh_bam_dup_barcodes_host(const uint8_t *records, uint64_t n_bytes, int barcode_mode, const char tag[2], int packed, uint64_t **words, uint64_t *n_templates);
 uint64_t bmh_barcode_word(const uint8_t *value, uint64_t n);
-int bmh_aligner_set_markdup_barcode(bmh_aligner_t *a, int mode, const char *tag);
-int bmh_aligner_markdup_barcode_counts(bmh_aligner_t *a, uint64_t out[1]);
 
 /* ---- Barcodes grouped within an edit distance (csrc/bam_dup_core.h).  Opt-in beside a barcode source: `edits` N (0 .. 21; -1: off, the calls
  * above) makes barcodes within N mismatches one molecule, as Picard's UmiAwareMarkDuplicatesWithMateCigar (MAX_EDIT_DISTANCE_TO_JOIN) does.  The barcode word is then
@@ -1073,12 +1092,8 @@ int bmh_aligner_markdup_barcode_counts(bmh_aligner_t *a, uint64_t out[1]);
  * (library, lo, hi, word) over barcoded pairs, their components, and the keys of either pass over the cap.
  * Refused with BMH_EINVAL before anything is written: edits outside -1 .. 21, edits without a barcode source; and by the record's index: a first record whose
  * value holds more than 21 bytes or a byte other than A C G T N - + (lower case too).
- * bmh_barcode_pack: *word of a value of n bytes; 1, or 0 when it does not pack.
- * bmh_aligner_set_markdup_barcode_edits: the marked runs that follow group barcodes within n mismatches (-1: off); after bmh_aligner_set_markdup_barcode, which
- * switches it off again when called anew.  bmh_aligner_markdup_barcode_group_counts: the three counts of the last such run. */
+ * bmh_barcode_pack: *word of a value of n bytes; 1, or 0 when it does not pack. */
 int bmh_barcode_pack(const uint8_t *value, uint64_t n, uint64_t *word);
-int bmh_aligner_set_markdup_barcode_edits(bmh_aligner_t *a, int n);
-int bmh_aligner_markdup_barcode_group_counts(bmh_aligner_t *a, uint64_t out[3]);
 
 /* A run over several read groups: one sample's lanes and libraries into one output.  A group is a read group ID, its library index (as above) and an input as
  * bmh_aligner_run_files takes it (path2: the mates, or NULL; a BAM's own @RG lines and RG tags stay ignored: keeping the input's read groups, bmh_aligner_set_keep_rg, and a run over groups do not combine).  One loader thread walks the groups in order into the
@@ -1108,40 +1123,27 @@ int bmh_aligner_run_groups(bmh_aligner_t *a, const bmh_read_group_t *groups, int
  * Refused with BMH_EINVAL: min_mapq outside 0 .. 255, a tile beyond 4096, 2^28 bins or more (before anything is written); and by the record's index: a record
  * that lies before its predecessor, a counted record whose pos is negative or not below its contig's length, a counted record that holds the long-CIGAR
  * placeholder (l_seq S, N, and a CG:B,I tag).
- * bmh_bam_sorted_file_coverage_device / _host: bmh_bam_sorted_file_* and, from the same windows, the coverage of the file -- duplicates that opt->markdup marks are
- * counted out.
- * bmh_aligner_set_coverage: the sorted runs that follow compute their coverage on the device, every window behind its flag step (opt NULL: off); refused (the
- * aligner stays as it was) unless the output format is BMH_OUT_BAM_SORTED, and switched off by every bmh_aligner_set_output of another format.  Without it nothing
- * about a run changes.  bmh_aligner_coverage: the coverage of the last such run; bmh_aligner_coverage_ms: the milliseconds its windows' steps and its last sweep took on
- * the device's stream (events around every step, read behind the window's own wait; a step's span holds its two host reads) and, with `windows`, the windows timed.
- * A failed bmh_bam_sorted_file_coverage_* call leaves *bam and *index NULL, whatever they held before. */
-typedef struct { int32_t min_mapq, deletions; uint32_t bin; uint32_t tile; } bmh_coverage_opt_t;
+ * bmh_sorted_opt_t's coverage: the coverage of a sorted output from the windows of its merge, every window behind its flag step -- duplicates that markdup marks
+ * are counted out.  Without it nothing about a run changes.  An aligner run times its windows' steps and its last sweep on the device's stream (events around
+ * every step, read behind the window's own wait; a step's span holds its two host reads): coverage_ms, coverage_windows. */
+struct bmh_coverage_opt { int32_t min_mapq, deletions; uint32_t bin; uint32_t tile; };
 void bmh_coverage_opt_default(bmh_coverage_opt_t *o);
-typedef struct bmh_coverage {
+struct bmh_coverage {
 	int32_t n_contigs; uint64_t n_bins;
 	uint64_t *n_reads, *cov_bases, *sum_depth, *max_depth, *sum_mapq;   /* [n_contigs] each */
 	uint64_t *hist;                                                      /* [1001] */
 	uint64_t *bin_sum;                                                   /* [n_bins] */
-} bmh_coverage_t;
+};
 int bmh_bam_coverage_device(const uint8_t *records, uint64_t n_bytes, int n_contigs, const int32_t *contig_len, const bmh_coverage_opt_t *opt, void *stream, bmh_coverage_t *out);
 int bmh_bam_coverage_host(const uint8_t *records, uint64_t n_bytes, int n_contigs, const int32_t *contig_len, const bmh_coverage_opt_t *opt, bmh_coverage_t *out);
-int bmh_bam_sorted_file_coverage_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                                        const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, void *stream, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index,
-                                        uint64_t *index_bytes, bmh_markdup_counts_t *res, bmh_coverage_t *cov);
-int bmh_bam_sorted_file_coverage_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                                      const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, uint8_t **bam, uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes,
-                                      bmh_markdup_counts_t *res, bmh_coverage_t *cov);
-int bmh_aligner_set_coverage(bmh_aligner_t *a, const bmh_coverage_opt_t *opt);
-int bmh_aligner_coverage(bmh_aligner_t *a, bmh_coverage_t *out);
-int bmh_aligner_coverage_ms(bmh_aligner_t *a, double *out, uint64_t *windows);
 
 /* ---- Sort, mark duplicates and index a BAM or SAM that any aligner wrote (csrc/bam_post_core.h, csrc/bam_post_kernels.hip, csrc/bam_post.cpp).
  * No index and no aligner handle: the input (a regular file or a pipe; BAM -- BGZF whose text begins "BAM\1" -- or SAM text, plain, gzip or BGZF, told apart by
  * their bytes) is read in order, inflated on host threads, cut into batches of about batch_bytes record bytes that end where a read name ends, and every batch
  * becomes a sorted run as a batch of the aligner does; at the end of the input the runs are merged into the coordinate-sorted file (header members, record
- * members in windows, the end-of-file member: all of it goes to the sink) with its index, the duplicates marked and the coverage computed as
- * BMH_OUT_BAM_SORTED, bmh_aligner_set_markdup and bmh_aligner_set_coverage do it -- the same calls underneath, so this aligner's own unsorted BAM or SAM gives
- * byte for byte the file of its sorted run.
+ * members in windows, the end-of-file member: all of it goes to the sink) with its index, the duplicates marked, the coverage and the statistics
+ * computed as a BMH_OUT_BAM_SORTED run does it -- the same calls underneath, so this aligner's own unsorted BAM or SAM gives byte for byte the file of its
+ * sorted run.
  * The header's text is the input's with every @HD line removed and "@HD\tVN:1.6\tSO:coordinate\n" in front, nothing else added; the references are the BAM's
  * binary table, or the SAM's @SQ lines (SN, LN) in order -- a SAM without one is refused.  Records stay verbatim but for the bin (recomputed: reg2bin(pos, end),
  * 4680 for pos -1) and, with marking, flag 0x400 (cleared first, then set by the decision).  Equal keys stay in input order over the whole file.
@@ -1152,13 +1154,12 @@ int bmh_aligner_coverage_ms(bmh_aligner_t *a, double *out, uint64_t *windows);
  * -1, an unclipped 5' end u with u + 2^30 outside [0, 2^31); with marking or coverage: a record that holds the long-CIGAR placeholder.  The contig-length
  * refusals of the sorted output hold (BAI below 2^29, marking at most 2^30 - 2^24, the CSI window count).  The result does not depend on batch_bytes, window,
  * sort_mem or spilling.
- * opt (NULL: the defaults): level 0 or 1; window: records per window of the merge (0: about 64 MiB); index_format, min_shift: BMH_INDEX_*; sort_mem: record
- * bytes kept in memory before runs spill to an unnamed file in tmp_dir (0: 4 GiB; NULL: $TMPDIR, else /tmp); batch_bytes (0: 256 MiB; at most 1 GiB);
- * markdup: the marking options or NULL; libraries != 0 (needs markdup, whose rg_ids stay NULL): the header's @RG lines are the table of libraries, by
- * bmh_bam_header_read_groups' rules with markdup on, and res->lib_* (or NULL) then hold room for 255 libraries; coverage: its options or NULL.
+ * opt (NULL: the defaults): sorted -- the record of every sorted output (above), read whole; batch_bytes (0: 256 MiB; at most 1 GiB); libraries != 0 (needs
+ * sorted.markdup, whose rg_ids stay NULL): the header's @RG lines are the table of libraries, by bmh_bam_header_read_groups' rules with markdup on, and the
+ * results' markdup->lib_* (or NULL) then hold room for 255 libraries.
  * out (zeroed first; bmh_bam_post_result_free releases it; a refused call leaves its pointers NULL): the index bytes, the output header's text, the references
  * (names NUL-terminated back to back), with libraries their names likewise, and the counts: records, templates, batches, runs spilled, records whose bin
- * changed, records whose 0x400 was cleared.  res: required with markdup; cov: required with coverage (bmh_free its arrays).
+ * changed, records whose 0x400 was cleared.  results: as above.
  * The host form does the same with the host forms of every step and no device; it holds the whole record stream in memory.
  * collate != 0 (needs markdup, else BMH_EINVAL before anything is read; off by default, and with it off every byte, count and message is as without the field):
  * templates by name over the whole file (BDP_TPL_FILE), so that a coordinate-sorted file can be marked.  A template is the records of the whole file that carry
@@ -1171,14 +1172,7 @@ int bmh_aligner_coverage_ms(bmh_aligner_t *a, double *out, uint64_t *windows);
  * Batches then end at the first record at or beyond batch_bytes.  Every record's 32-byte part (48 or 56 with optical_distance / barcodes) stays in host memory
  * until the grouping: about 32 GB for 10^9 records, outside sort_mem, never spilled.  On a name-grouped file with distinct names the output is byte for byte
  * that of collate 0. */
-typedef struct {
-	int32_t level; uint32_t window; int32_t index_format, min_shift;
-	uint64_t sort_mem; const char *tmp_dir; uint64_t batch_bytes;
-	const bmh_markdup_opt_t *markdup; int32_t libraries;
-	const bmh_coverage_opt_t *coverage;
-	int32_t collate;
-	const struct bmh_bam_stats_opt *stats;                                /* read by bmh_bam_post_file_stats_* only (below) */
-} bmh_bam_post_opt_t;
+typedef struct { bmh_sorted_opt_t sorted; uint64_t batch_bytes; int32_t libraries, collate; } bmh_bam_post_opt_t;
 typedef struct { uint64_t records, templates, batches, spilled_runs, bins_changed, dup_flags_cleared; } bmh_bam_post_counts_t;
 typedef struct {
 	uint8_t *index; uint64_t index_bytes;
@@ -1190,9 +1184,8 @@ typedef struct {
 void bmh_bam_post_opt_default(bmh_bam_post_opt_t *o);
 void bmh_bam_post_result_free(bmh_bam_post_result_t *r);
 int bmh_bam_post_file_device(const char *path, const bmh_bam_post_opt_t *opt, void *stream, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out,
-                             bmh_markdup_counts_t *res, bmh_coverage_t *cov);
-int bmh_bam_post_file_host(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res,
-                           bmh_coverage_t *cov);
+                             bmh_sorted_results_t *results);
+int bmh_bam_post_file_host(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_sorted_results_t *results);
 /* The grouping of collate on its own (csrc/bam_tpl_core.h, csrc/bam_tpl_kernels.hip, csrc/bam_tpl_host.cpp): a stream of whole BAM records in any order -> every
  * record's template ordinal (tpl [n_records]), the templates' entries (24 bytes each: uint64 lo, hi; uint32 score, kind | records << 2), their locations (16
  * bytes each: int32 x, y; uint32 tile; uint16 rg, flags), with opt's barcode source their barcode words, counts: secondary or supplementary records, unmapped
@@ -1225,15 +1218,11 @@ void bmh_bam_templates_free(bmh_bam_templates_t *r);
  * Refused with BMH_EINVAL by the record's index: a refID outside -1 .. n_contigs - 1; of mapped primary records (no other record's operations or tags are read)
  * tags that cannot be walked to the record's end, an NM of another type or below 0, the long-CIGAR placeholder.  The first such record is the one named.
  * bmh_bam_stats_device / _host: a record stream in any order (whole records, else refused).  bmh_bam_stats_free releases the arrays (a failed call leaves them NULL).
- * bmh_bam_sorted_file_stats_device / _host: bmh_bam_sorted_file_* and, from the same windows, the statistics -- with the 0x400 flags opt->markdup sets -- and, with
- * cov not NULL, the coverage under cov_opt.  A failed call leaves *bam, *index and every array of cov and stats NULL.
- * bmh_aligner_set_stats: the sorted runs that follow compute their statistics on the device, every window behind its flag step (opt NULL: off); refused unless the
- * output format is BMH_OUT_BAM_SORTED, switched off by every bmh_aligner_set_output of another format.  Without it no run launches anything more.
- * bmh_aligner_stats: the statistics of the last such run; bmh_aligner_stats_ms: the milliseconds its windows' kernels took on the device's stream and the windows.
- * bmh_bam_post_file_stats_device / _host: bmh_bam_post_file_* and, with opt->stats set, the statistics of the file (stats is then required). */
-typedef struct bmh_bam_stats_opt { uint32_t insert_cap; } bmh_bam_stats_opt_t;
+ * bmh_sorted_opt_t's stats: the statistics of a sorted output from the windows of its merge, every window behind its flag step, with the 0x400 flags markdup
+ * sets.  Without it no run launches anything more.  An aligner run times its windows' kernels on the device's stream: stats_ms, stats_windows. */
+struct bmh_bam_stats_opt { uint32_t insert_cap; };
 void bmh_bam_stats_opt_default(bmh_bam_stats_opt_t *o);
-typedef struct bmh_bam_stats {
+struct bmh_bam_stats {
 	int32_t n_contigs; uint32_t insert_cap;
 	uint64_t *flag;                                                      /* [2][16] */
 	uint64_t *summary;                                                   /* [14] */
@@ -1241,23 +1230,10 @@ typedef struct bmh_bam_stats {
 	uint64_t *contig_mapped, *contig_unmapped;                           /* [n_contigs] each */
 	uint64_t *insert_hist;                                               /* [3][insert_cap + 1] */
 	uint64_t unplaced, insert_min[3], insert_max[3];
-} bmh_bam_stats_t;
+};
 void bmh_bam_stats_free(bmh_bam_stats_t *s);
 int bmh_bam_stats_device(const uint8_t *records, uint64_t n_bytes, int n_contigs, const bmh_bam_stats_opt_t *opt, void *stream, bmh_bam_stats_t *out);
 int bmh_bam_stats_host(const uint8_t *records, uint64_t n_bytes, int n_contigs, const bmh_bam_stats_opt_t *opt, bmh_bam_stats_t *out);
-int bmh_bam_sorted_file_stats_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                                     const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, const bmh_bam_stats_opt_t *stats_opt, void *stream, uint8_t **bam,
-                                     uint64_t *bam_bytes, uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res, bmh_coverage_t *cov, bmh_bam_stats_t *stats);
-int bmh_bam_sorted_file_stats_host(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
-                                   const bmh_sorted_file_opt_t *opt, const bmh_coverage_opt_t *cov_opt, const bmh_bam_stats_opt_t *stats_opt, uint8_t **bam, uint64_t *bam_bytes,
-                                   uint8_t **index, uint64_t *index_bytes, bmh_markdup_counts_t *res, bmh_coverage_t *cov, bmh_bam_stats_t *stats);
-int bmh_aligner_set_stats(bmh_aligner_t *a, const bmh_bam_stats_opt_t *opt);
-int bmh_aligner_stats(bmh_aligner_t *a, bmh_bam_stats_t *out);
-int bmh_aligner_stats_ms(bmh_aligner_t *a, double *out, uint64_t *windows);
-int bmh_bam_post_file_stats_device(const char *path, const bmh_bam_post_opt_t *opt, void *stream, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out,
-                                   bmh_markdup_counts_t *res, bmh_coverage_t *cov, bmh_bam_stats_t *stats);
-int bmh_bam_post_file_stats_host(const char *path, const bmh_bam_post_opt_t *opt, bmh_sam_sink_t sink, void *user, bmh_bam_post_result_t *out, bmh_markdup_counts_t *res,
-                                 bmh_coverage_t *cov, bmh_bam_stats_t *stats);
 
 #ifdef __cplusplus
 }

@@ -129,16 +129,10 @@ def main():
 
     def run(fmt, spill=False, keep=None, markdup=False, paired=False, groups=None, files=False, optical=None, coverage=None, qc=None):
         src = ppath if paired else path
-        nat.set_output(fmt, 1)
         if fmt == "bam_sorted":
-            nat.set_sort(1 if spill else 64 << 30, tmp, a.sort_window)
-            nat.set_markdup(markdup)
-            if markdup:
-                nat.set_markdup_optical(optical)
-            if a.coverage or a.stats:                             # (the other legs also run against a parent commit's library, which has no such call)
-                nat.set_coverage(coverage)
-            if a.stats:
-                nat.set_stats(qc)
+            nat.set_sorted(level=1, sort_mem=1 if spill else 64 << 30, sort_tmp=tmp, window=a.sort_window, markdup=markdup, optical_distance=optical, coverage=coverage, stats=qc)
+        else:
+            nat.set_output(fmt, 1)
         opt_ms, cov_ms, st_ms = [], [], []
         nbytes = [0]
 
@@ -147,6 +141,7 @@ def main():
             if keep is not None and len(keep) < 1:
                 keep.append(bytes(mv))
         secs, merge, times = [], [], []
+        got = {}
         for it in range(a.runs + 1):
             nbytes[0] = 0
             t1 = time.perf_counter()
@@ -158,14 +153,15 @@ def main():
                 st = nat.run_file(src, paired, sink, batch_reads=n4 // 4, n_lanes=3 if paired else 2, n_threads=nth)
             if it:
                 secs.append(time.perf_counter() - t1); merge.append(st.format_seconds)
+                got = nat.sorted_results() if fmt == "bam_sorted" else {}
                 if markdup:
-                    times.append(nat.markdup_times())
+                    times.append(got["markdup_times"])
                 if optical is not None:
-                    opt_ms.append(nat.markdup_optical_ms())
+                    opt_ms.append(got["markdup_optical_ms"])
                 if coverage is not None:
-                    cov_ms.append(nat.coverage_ms(windows=True))
+                    cov_ms.append(got["coverage_ms"])
                 if qc is not None:
-                    st_ms.append(nat.stats_ms(windows=True))
+                    st_ms.append(got["stats_ms"])
         row = stats(secs, n4, 1e6)
         row["unit"] = "Mreads/s"; row["bytes_out_per_read"] = round(nbytes[0] / n4, 1)
         if fmt == "bam_sorted":
@@ -175,24 +171,24 @@ def main():
             row["final_merge_ms"] = {"median": round(1e3 * sorted(merge)[len(merge) // 2], 2), "runs": [round(1e3 * m, 2) for m in merge]}
             if coverage is not None:
                 ms = [t for t, _w in cov_ms]
-                cov = nat.coverage()
+                cov = got["coverage"]
                 row["coverage_steps_alone"] = {"unit": "ms on the stream per run (events around every window's depth step and the last sweep; a step's span holds its two host reads)",
                                                "median": round(sorted(ms)[len(ms) // 2], 3), "runs": [round(t, 3) for t in ms], "windows": [w for _t, w in cov_ms],
                                                "ms_per_window": [round(t / max(w, 1), 3) for t, w in cov_ms],
                                                "share_of_final_merge_pct": round(100 * sorted(ms)[len(ms) // 2] / (1e3 * sorted(merge)[len(merge) // 2]), 2)}
-                row["coverage"] = {"tile": int(coverage.tile) or 4096, "bin": int(coverage.bin), "bins": int(len(cov["bin_sum"])), "n_reads": int(cov["n_reads"].sum()),
+                row["coverage"] = {"tile": 4096, "bin": int(coverage.get("bin", 0)), "bins": int(len(cov["bin_sum"])), "n_reads": int(cov["n_reads"].sum()),
                                    "cov_bases": int(cov["cov_bases"].sum()), "sum_depth": int(cov["sum_depth"].sum()), "max_depth": int(cov["max_depth"].max())}
             if qc is not None:
                 ms = [t for t, _w in st_ms]
-                got = nat.stats()
                 row["stats_steps_alone"] = {"unit": "ms on the stream per run (events around every window's statistics kernel)",
                                             "median": round(sorted(ms)[len(ms) // 2], 3), "runs": [round(t, 3) for t in ms], "windows": [w for _t, w in st_ms],
                                             "ms_per_window": [round(t / max(w, 1), 3) for t, w in st_ms],
                                             "share_of_final_merge_pct": round(100 * sorted(ms)[len(ms) // 2] / (1e3 * sorted(merge)[len(merge) // 2]), 2)}
-                row["stats"] = {"insert_cap": int(qc.insert_cap), "total": int(got["flag"][:, 0].sum()), "duplicates": int(got["flag"][:, 4].sum()), "mapped": int(got["flag"][:, 6].sum()),
-                                "pairs_counted": [int(v) for v in got["insert_hist"].sum(axis=1)], "largest_insert_bin": int(got["insert_hist"].max()), "edit_distance": int(got["summary"][13])}
+                qs = got["stats"]
+                row["stats"] = {"insert_cap": int(qc.get("insert_cap", 65536)), "total": int(qs["flag"][:, 0].sum()), "duplicates": int(qs["flag"][:, 4].sum()), "mapped": int(qs["flag"][:, 6].sum()),
+                                "pairs_counted": [int(v) for v in qs["insert_hist"].sum(axis=1)], "largest_insert_bin": int(qs["insert_hist"].max()), "edit_distance": int(qs["summary"][13])}
             if markdup:
-                row["counts"] = nat.markdup_counts()
+                row["counts"] = got["markdup_counts"]
                 tpl = row["counts"]["templates"]
                 row["decision_alone"] = stats([t["decision_ms"] / 1e3 for t in times], tpl, 1e6); row["decision_alone"]["unit"] = "Mtemplates/s"
                 row["decision_alone"]["ms"] = [round(t["decision_ms"], 2) for t in times]
@@ -200,22 +196,20 @@ def main():
                 row["window_flags_alone"]["ms"] = [round(t["window_flags_ms"], 2) for t in times]
                 row["entries_d2h_bytes_per_read"] = round(times[0]["entries_d2h_bytes"] / n4, 1)
                 if optical is not None:
-                    row["optical_counts"] = nat.markdup_optical_counts()
+                    row["optical_counts"] = got["markdup_optical_counts"]
                     row["optical_step_alone"] = stats([max(t, 1e-6) / 1e3 for t in opt_ms], tpl, 1e6); row["optical_step_alone"]["unit"] = "Mtemplates/s (inside the decision: locations up, sets, sorts, clustering, counts)"
                     row["optical_step_alone"]["ms"] = [round(t, 2) for t in opt_ms]
                 if groups is not None:
-                    row["library_counts"] = [nat.markdup_library_counts(k) for k in range(1 + max(g[1] for g in groups))]
+                    row["library_counts"] = got["markdup_library_counts"]
         return row
     keep = []
     if a.stats:
-        from bwamem_hip.lib import coverage_opt, stats_opt
         result["sort_window"] = a.sort_window
         for pre, pk in (("", {}), ("paired_", dict(paired=True))):
             result["rows"][pre + "reads_to_sorted_bam_in_memory"] = run("bam_sorted", **pk)
             result["rows"][pre + "reads_to_sorted_bam_in_memory_markdup"] = run("bam_sorted", markdup=True, **pk)
-            result["rows"][pre + "reads_to_sorted_bam_in_memory_markdup_stats"] = run("bam_sorted", markdup=True, qc=stats_opt(), **pk)
-        result["rows"]["paired_reads_to_sorted_bam_in_memory_markdup_coverage_stats"] = run("bam_sorted", markdup=True, coverage=coverage_opt(), qc=stats_opt(), paired=True)
-        nat.set_coverage(None); nat.set_stats(None)
+            result["rows"][pre + "reads_to_sorted_bam_in_memory_markdup_stats"] = run("bam_sorted", markdup=True, qc={}, **pk)
+        result["rows"]["paired_reads_to_sorted_bam_in_memory_markdup_coverage_stats"] = run("bam_sorted", markdup=True, coverage={}, qc={}, paired=True)
         nat.set_output("sam", 1)
         if a.parent_json:
             with open(a.parent_json) as f:
@@ -236,14 +230,12 @@ def main():
         print(json.dumps(result))
         return
     if a.coverage:
-        from bwamem_hip.lib import coverage_opt
         result["sort_window"] = a.sort_window
         for pre, pk in (("", {}), ("paired_", dict(paired=True))):
             result["rows"][pre + "reads_to_sorted_bam_in_memory"] = run("bam_sorted", **pk)
             result["rows"][pre + "reads_to_sorted_bam_in_memory_markdup"] = run("bam_sorted", markdup=True, **pk)
-            result["rows"][pre + "reads_to_sorted_bam_in_memory_markdup_coverage"] = run("bam_sorted", markdup=True, coverage=coverage_opt(), **pk)
-            result["rows"][pre + "reads_to_sorted_bam_in_memory_markdup_coverage_bins"] = run("bam_sorted", markdup=True, coverage=coverage_opt(bin=a.coverage_bin), **pk)
-        nat.set_coverage(None)
+            result["rows"][pre + "reads_to_sorted_bam_in_memory_markdup_coverage"] = run("bam_sorted", markdup=True, coverage={}, **pk)
+            result["rows"][pre + "reads_to_sorted_bam_in_memory_markdup_coverage_bins"] = run("bam_sorted", markdup=True, coverage=dict(bin=a.coverage_bin), **pk)
         nat.set_output("sam", 1)
         if a.parent_json:
             with open(a.parent_json) as f:

@@ -421,19 +421,17 @@ def test_core_under_sanitizers(tmp_path):
 _FAILED_CALL = r"""
 import ctypes as C, sys
 import bwamem_hip
-from bwamem_hip.lib import Coverage, CoverageOpt, MarkdupCounts, SortedFileOpt, _u64p
-L = bwamem_hip.load_library()
-types = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(SortedFileOpt), C.POINTER(CoverageOpt)]
-outs = [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p, C.POINTER(MarkdupCounts), C.POINTER(Coverage)]
-L.bmh_bam_sorted_file_coverage_host.argtypes, L.bmh_bam_sorted_file_coverage_device.argtypes = types + outs, types + [C.c_void_p] + outs
-names, lens, fo = (C.c_char_p * 1)(b"c"), (C.c_int32 * 1)(100), SortedFileOpt(1, 0, 0, 14, None)
+from bwamem_hip.lib import Coverage, CoverageOpt, SortedOpt, SortedResults, _sorted_file_api
+L = _sorted_file_api(bwamem_hip.load_library())
+names, lens = (C.c_char_p * 1)(b"c"), (C.c_int32 * 1)(100)
 for device in (False, True):
     for header, opt in ((b"@CO\tx\n", CoverageOpt(0, 0, 0, 5000)), (b"@CO\tx\n", CoverageOpt(300, 0, 0, 0)), (b"@CO\tx\n", CoverageOpt(0, 0, 1, 0)), (None, CoverageOpt(0, 0, 0, 0))):
         bam, bai, nb, ni, cov = C.c_void_p(0xdeadbee0), C.c_void_p(0xdeadbee0), C.c_uint64(7), C.c_uint64(7), Coverage()
         n = 1 if opt.bin == 0 else (1 << 31) - 1                    # (bin 1 on 2^31 - 1 bases: 2^28 bins and more)
         lens[0] = 100 if n == 1 else n
-        head = [header, 1, names, C.addressof(lens), b"", 0, C.byref(fo), C.byref(opt)] + ([None] if device else [])
-        rc = (L.bmh_bam_sorted_file_coverage_device if device else L.bmh_bam_sorted_file_coverage_host)(*head, C.byref(bam), C.byref(nb), C.byref(bai), C.byref(ni), None, C.byref(cov))
+        fo, res = SortedOpt(1, 0, 0, 14, 0, None, None, C.pointer(opt), None), SortedResults(None, C.pointer(cov), None)
+        head = [header, 1, names, C.addressof(lens), b"", 0, C.byref(fo)] + ([None] if device else [])
+        rc = (L.bmh_bam_sorted_file_device if device else L.bmh_bam_sorted_file_host)(*head, C.byref(bam), C.byref(nb), C.byref(bai), C.byref(ni), C.byref(res))
         assert rc == -2 and bam.value is None and bai.value is None and not cov.hist, (device, rc, bam.value, bai.value)
 print("ok")
 """

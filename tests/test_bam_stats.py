@@ -488,7 +488,7 @@ def test_refusals_and_keywords(capsys):
         with pytest.raises(ValueError, match="insert_cap"):
             bam_sorted_file("@CO\tx\n", [("c", 100)], b"", host=True, stats=dict(insert_cap=cap))
     assert bam_stats(b"", 1, insert_cap=2, host=True)["insert_hist"].shape == (3, 3)
-    with pytest.raises(ValueError, match="bmh_bam_sorted_file_stats_host: record 1 has an NM tag that is no count"):
+    with pytest.raises(ValueError, match="bmh_bam_sorted_file_host: record 1 has an NM tag that is no count"):
         bam_sorted_file("@CO\tx\n", [("c", 1000)], srec(b"b", pos=20, tag=b"NMZ1\0") + ok, host=True, stats={})       # (the index in the sorted file)
     from bwamem_hip import bam, mem
     capsys.readouterr()
@@ -632,12 +632,9 @@ def test_core_under_sanitizers(tmp_path):
 _FAILED_CALL = r"""
 import ctypes as C, sys
 import bwamem_hip
-from bwamem_hip.lib import BamStats, BamStatsOpt, Coverage, CoverageOpt, MarkdupCounts, SortedFileOpt, _u64p
-L = bwamem_hip.load_library()
-types = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(SortedFileOpt), C.POINTER(CoverageOpt), C.POINTER(BamStatsOpt)]
-outs = [C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p), _u64p, C.POINTER(MarkdupCounts), C.POINTER(Coverage), C.POINTER(BamStats)]
-L.bmh_bam_sorted_file_stats_host.argtypes, L.bmh_bam_sorted_file_stats_device.argtypes = types + outs, types + [C.c_void_p] + outs
-names, lens, fo = (C.c_char_p * 1)(b"c"), (C.c_int32 * 1)(100), SortedFileOpt(1, 0, 0, 14, None)
+from bwamem_hip.lib import BamStats, BamStatsOpt, Coverage, CoverageOpt, SortedOpt, SortedResults, _sorted_file_api, _u64p
+L = _sorted_file_api(bwamem_hip.load_library())
+names, lens = (C.c_char_p * 1)(b"c"), (C.c_int32 * 1)(100)
 bad_rec = bytes.fromhex(sys.argv[1])
 for device in (False, True):
     for header, recs, co, so in ((b"@CO\tx\n", b"", CoverageOpt(0, 0, 0, 0), BamStatsOpt(1)), (b"@CO\tx\n", b"", CoverageOpt(0, 0, 0, 0), BamStatsOpt(65537)), (b"@CO\tx\n", b"", CoverageOpt(0, 0, 0, 5000), BamStatsOpt(4)),
@@ -646,8 +643,9 @@ for device in (False, True):
             continue                                                # (a refused record is met on the device: test_bam_stats_gpu.py)
         bam, bai, nb, ni, cov, st = C.c_void_p(0xdeadbee0), C.c_void_p(0xdeadbee0), C.c_uint64(7), C.c_uint64(7), Coverage(), BamStats()
         st.flag = C.cast(0xdeadbee0, _u64p); cov.hist = C.cast(0xdeadbee0, _u64p)
-        head = [header, 1, names, C.addressof(lens), recs, len(recs), C.byref(fo), C.byref(co), C.byref(so)] + ([None] if device else [])
-        rc = (L.bmh_bam_sorted_file_stats_device if device else L.bmh_bam_sorted_file_stats_host)(*head, C.byref(bam), C.byref(nb), C.byref(bai), C.byref(ni), None, C.byref(cov), C.byref(st))
+        fo, res = SortedOpt(1, 0, 0, 14, 0, None, None, C.pointer(co), C.pointer(so)), SortedResults(None, C.pointer(cov), C.pointer(st))
+        head = [header, 1, names, C.addressof(lens), recs, len(recs), C.byref(fo)] + ([None] if device else [])
+        rc = (L.bmh_bam_sorted_file_device if device else L.bmh_bam_sorted_file_host)(*head, C.byref(bam), C.byref(nb), C.byref(bai), C.byref(ni), C.byref(res))
         assert rc == -2 and bam.value is None and bai.value is None and not cov.hist and not st.flag and not st.insert_hist and not st.mapq, (device, rc, bam.value, bai.value)
     st = BamStats(); st.flag = C.cast(0xdeadbee0, _u64p)
     L.bmh_bam_stats_host.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(BamStatsOpt), C.POINTER(BamStats)]

@@ -234,9 +234,10 @@ def test_reads_to_edit_grouped_bam(hip, tmp_path, monkeypatch):
     with pytest.raises(ValueError, match="0 .. 21"):
         al.align_files(path, out=out, paired=True, fmt="bam", sort=True, markdup=True, barcode_tag="RX", barcode_edits=22)
     assert out.getvalue() == b""
-    nat = al._native_aligner()
+    # edits without marking cannot be written down in the options record any more: the keywords refuse them, and the aligner stays as it was
     with pytest.raises(ValueError, match="marked"):
-        nat.set_markdup_barcode_edits(1)
+        al._native_aligner().set_sorted(barcode_edits=1)
+    assert run(batch_reads=256) == plain
     al.close()
 
 

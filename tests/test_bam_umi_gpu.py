@@ -163,6 +163,10 @@ def test_reads_to_barcode_marked_bam(hip, tmp_path, monkeypatch, paired):
     # without the option: strictly more flagged, no new count
     plain = run(barcode=False, batch_reads=256 if paired else 128)
     assert _flagged(BamFile(plain[0]).stream) > _flagged(stream) and "templates_without_barcode" not in al.markdup_counts
+    # a barcode source without marking cannot be written down in the options record any more: the keywords refuse it, and the aligner stays as it was
+    with pytest.raises(ValueError, match="marked"):
+        al._native_aligner().set_sorted(barcode_tag="RX")
+    assert run(barcode=False, batch_reads=256 if paired else 128) == plain
     # refused before anything is written
     al.close()
     al = Aligner(PREFIX, n_threads=4)                                  # (without -C)
@@ -172,9 +176,6 @@ def test_reads_to_barcode_marked_bam(hip, tmp_path, monkeypatch, paired):
     with pytest.raises(ValueError, match="markdup"):
         al.align_files(path, out=out, paired=paired, fmt="bam", sort=True, barcode_name=True)
     assert out.getvalue() == b""
-    nat = al._native_aligner()
-    with pytest.raises(ValueError, match="marked"):
-        nat.set_markdup_barcode(1, b"RX")
     al.close()
 
 

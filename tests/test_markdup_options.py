@@ -8,8 +8,8 @@ import itertools
 
 import pytest
 
-from bwamem_hip.lib import (BARCODE_GROUP_COUNTS, MARKDUP_COUNTS, OPTICAL_COUNTS, MarkdupCounts, MarkdupOpt, SortedFileOpt, _markdup_api, bam_markdup, bam_sorted_file,
-                            load_library)
+from bwamem_hip.lib import (BARCODE_GROUP_COUNTS, MARKDUP_COUNTS, OPTICAL_COUNTS, MarkdupCounts, MarkdupOpt, SortedOpt, SortedResults, _markdup_api, _sorted_file_api, bam_markdup,
+                            bam_sorted_file, load_library)
 from test_bam_dup import CONTIGS
 from test_bam_umi import GROUPS, render
 from test_bam_umi_edits import reads
@@ -167,18 +167,20 @@ def test_invalid_combinations():
 
 def test_a_sorted_file_refuses_an_optical_distance():
     """the stand-alone file has no optical step: the record that asks for one is refused, not read past"""
-    L = _markdup_api(load_library())
+    L = _sorted_file_api(_markdup_api(load_library()))
     s = stream()
     o, res = MarkdupOpt(), MarkdupCounts()
     L.bmh_markdup_opt_default(C.byref(o))
     o.optical_distance = DISTANCE
-    fo = SortedFileOpt(1, 0, 0, 14, C.pointer(o))
+    fo = SortedOpt(1, 0, 0, 14, 0, None, C.pointer(o), None, None)
     names = (C.c_char_p * len(CONTIGS))(*[c[0].encode() for c in CONTIGS])
     lens = (C.c_int32 * len(CONTIGS))(*[c[1] for c in CONTIGS])
     bam, idx, nb, ni = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
     call = lambda r: L.bmh_bam_sorted_file_host(HDR.encode(), len(CONTIGS), names, C.cast(lens, C.c_void_p), s, len(s), C.byref(fo), C.byref(bam), C.byref(nb), C.byref(idx), C.byref(ni), r)
-    assert call(C.byref(res)) == -2 and bam.value is None
+    with_counts = C.byref(SortedResults(C.pointer(res), None, None))
+    assert call(with_counts) == -2 and bam.value is None
     o.optical_distance = -1
     assert call(None) == -2 and bam.value is None                   # (marking without its counts record)
-    assert call(C.byref(res)) == 0 and dict(zip(MARKDUP_COUNTS, res.counts)) == host_markdup({})[1]
+    assert call(C.byref(SortedResults())) == -2 and bam.value is None
+    assert call(with_counts) == 0 and dict(zip(MARKDUP_COUNTS, res.counts)) == host_markdup({})[1]
     L.bmh_free(bam); L.bmh_free(idx)
