@@ -113,20 +113,25 @@ DFL_FN void dfl_or_bits(uint32_t *w, uint32_t at, uint64_t v)
 }
 
 // Code lengths of at most maxbits bits for the nsym counts freq[] (a symbol that does not occur gets 0; fewer than two that do: the first symbols that
-// do not are counted once, so that the code is complete).  Scratch: sh.htab.  All lanes call it.
-DFL_FN void dfl_build(dfl_state_t &sh, uint32_t *freq, uint32_t nsym, uint32_t maxbits, uint8_t *len)
+// do not are built in as place-holders with a count of one, so that the code is complete -- freq[] itself stays what the tokens counted, and what the
+// caller sizes the block from).  Scratch: sh.htab, sh.u0, sh.u1.  All lanes call it.
+DFL_FN void dfl_build(dfl_state_t &sh, const uint32_t *freq, uint32_t nsym, uint32_t maxbits, uint8_t *len)
 {
 	uint32_t *key = sh.htab, *srt = sh.htab + 512, *A = sh.htab + 1024;
 	DFL_LANES(lane) {
 		if (lane != 0) continue;
-		uint32_t used = 0;
+		uint32_t used = 0, ph = 0xffffffffu;                                // the place-holders: two symbols of 16 bits, 0xffff for none
 		for (uint32_t i = 0; i < nsym; ++i) used += freq[i] != 0;
-		for (uint32_t i = 0; i < nsym && used < 2; ++i) if (!freq[i]) { freq[i] = 1; ++used; }
-		sh.u0 = used;
+		for (uint32_t i = 0; i < nsym && used < 2; ++i) if (!freq[i]) { ph = ph << 16 | i; ++used; }
+		sh.u0 = used; sh.u1 = ph;
 	}
 	DFL_SYNC();
 	DFL_LANES(lane) {
-		for (uint32_t i = lane; i < nsym; i += 64) { key[i] = freq[i] ? (freq[i] << 9 | i) : DFL_NONE; len[i] = 0; }
+		const uint32_t ph = sh.u1;
+		for (uint32_t i = lane; i < nsym; i += 64) {
+			const uint32_t f = freq[i] ? freq[i] : (i == (ph & 0xffffu) || i == ph >> 16) ? 1u : 0u;
+			key[i] = f ? (f << 9 | i) : DFL_NONE; len[i] = 0;
+		}
 	}
 	DFL_SYNC();
 	DFL_LANES(lane) {
@@ -320,7 +325,7 @@ DFL_FN uint32_t dfl_member(dfl_state_t &sh, const uint8_t *in, uint32_t n, uint3
 		dfl_pass<false>(sh, in, n, out32, 0);
 		DFL_LANES(lane) { if (lane == 0) sh.lfreq[256] = 1; }
 		DFL_SYNC();
-		// (the counts before the builder adds its place-holders: what the tokens cost)
+		// (the builder leaves the counts as they are: the block is sized below from what the tokens cost, without the builder's place-holders)
 		dfl_build(sh, sh.lfreq, 286, 15, sh.llen);
 		dfl_build(sh, sh.dfreq, 30, 15, sh.dlen);
 		DFL_LANES(lane) {
@@ -345,7 +350,7 @@ DFL_FN uint32_t dfl_member(dfl_state_t &sh, const uint8_t *in, uint32_t n, uint3
 			uint32_t bits = 3 + 14 + 3 * nc + sh.extra;
 			for (uint32_t i = 0; i < nlen; ++i) bits += sh.cllen[sh.llen[i]] + sh.lfreq[i] * sh.llen[i];
 			for (uint32_t i = 0; i < ndist; ++i) bits += sh.cllen[sh.dlen[i]] + sh.dfreq[i] * sh.dlen[i];
-			sh.u0 = nc; sh.u1 = bits;
+			sh.u0 = nc; sh.u1 = bits;                                       // (u1 keeps the bits to the end of the call: the trace of tests/deflate_core_host.cpp reads them)
 		}
 		DFL_SYNC();
 		ncode = sh.u0;

@@ -249,6 +249,22 @@ def test_handmade_refusals(core_exe, tmp_path):
         assert zlib_verdict(d, isize, crc) is None, name
 
 
+def test_limit_members(core_exe, tmp_path):
+    """tests/inflate_limits.py: codes of 1 .. 15 bits on both alphabets, the 7-bit code-length code, runs over the literal / distance boundary, ndist 1, tokens of
+    48 bits at every bit offset: OK exactly where zlib takes the member, with zlib's text; the refusals with the status the core documents"""
+    import inflate_limits
+    cases = inflate_limits.members()
+    assert len(cases) == 20 and sum(st == OK for *_, st in cases) == 15
+    res = run_core(core_exe, tmp_path, [(d, isize, crc) for _, d, isize, crc, _ in cases])
+    for (name, d, isize, crc, want), (st, got, crc_got, out) in zip(cases, res):
+        text = zlib_verdict(d, isize, crc)
+        assert (st == OK) == (text is not None) and st == want, (name, st, want)
+        if text is not None:
+            assert out == text == zlib.decompress(d, -15) and got == isize and crc_got == crc, name
+        else:
+            assert got <= min(isize, 65536), name
+
+
 def test_damaged_members_end_with_a_status(core_exe, tmp_path):
     """4000 single-bit flips and truncations: no sanitizer report; the member is refused unless zlib inflates it to the same size and CRC32, and then the bytes are zlib's"""
     cases = damaged(corpus(), 4000, seed=3)

@@ -97,6 +97,23 @@ def test_damaged_members_on_the_device(hip):
     assert list(st[:3]) == [9, 9, 9] and st[3] == host_st[3]
 
 
+@pytest.mark.gpu
+def test_limit_members_on_the_device(hip):
+    """the members of tests/inflate_limits.py, host and device, at every launch size: OK exactly where zlib takes the member, with zlib's text"""
+    import inflate_limits
+    from bwamem_hip.lib import inflate_members
+    cases = inflate_limits.members()
+    blob, tab, nbytes = _table([(d, isize, crc) for _, d, isize, crc, _ in cases])
+    want = [zlib_verdict(d, isize, crc) for _, d, isize, crc, _ in cases]
+    runs = [("host", inflate_members(blob, tab, nbytes, host=True))] + [(per_launch, inflate_members(blob, tab, nbytes, per_launch=per_launch)) for per_launch in (0, 65, 2, 1)]
+    for how, (out, st) in runs:
+        for i, (name, d, isize, crc, status) in enumerate(cases):
+            assert st[i] == status and (st[i] == OK) == (want[i] is not None), (how, name, int(st[i]), status)
+            if want[i] is not None:
+                o = int(tab["out_off"][i])
+                assert out[o:o + isize].tobytes() == want[i], (how, name)
+
+
 def handmade_status():
     return [(n, want) for n, _, _, _, want in handmade()]
 
