@@ -465,6 +465,64 @@ def _stats_keywords(f):
     return call
 
 
+RECAL_KEYWORDS = ("recal", "known_sites", "recal_min_qual", "recal_max_cycle")
+
+
+def recal_request(what: str, sort: bool, recal=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None, need: str = "sort=True"):
+    """the recalibration keywords of align_file / align_files / align_groups / bam_post_file, checked -> None (none given) or a dict of them; ValueError otherwise"""
+    sites = [known_sites] if isinstance(known_sites, (str, bytes, os.PathLike)) else list(known_sites or [])
+    if recal is None:
+        if sites or recal_min_qual is not None or recal_max_cycle is not None:
+            raise ValueError(f"{what}: known_sites, recal_min_qual and recal_max_cycle need recal (they say what is counted, not where it goes)")
+        return None
+    if not sort:
+        raise ValueError(f"{what}: the recalibration options need {need}: the table is counted where the sorted file is written")
+    for nm, v, lo, hi in (("recal_min_qual", recal_min_qual, 0, 93), ("recal_max_cycle", recal_max_cycle, 1, 65535)):
+        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not lo <= v <= hi):
+            raise ValueError(f"{what}: {nm} {v!r}: an integer in {lo} .. {hi}")
+    return dict(table=recal, known_sites=[os.fspath(p) for p in sites], min_qual=6 if recal_min_qual is None else int(recal_min_qual), max_cycle=500 if recal_max_cycle is None else int(recal_max_cycle))
+
+
+def _recal_keywords(f):
+    """_coverage_keywords for the recalibration keywords: the outermost call's request stays in self._recal_req for as long as the run"""
+    sig = inspect.signature(f)
+
+    @functools.wraps(f)
+    def call(self, *args, **kw):
+        if getattr(self, "_recal_req", None) is not None:
+            return f(self, *args, **kw)
+        given = sig.bind(self, *args, **kw)
+        given.apply_defaults()
+        req = recal_request(f.__name__, given.arguments["sort"], *(given.arguments[k] for k in RECAL_KEYWORDS))
+        if req is None:
+            return f(self, *args, **kw)
+        if given.arguments.get("keep_rg"):                        # the table's read groups are the input's: its header is read here, ahead of the run
+            from .bam import peek_header
+            src = given.arguments["reads"]
+            if not isinstance(src, (str, os.PathLike)) or not os.path.isfile(src):
+                raise ValueError(f"{f.__name__}: recal with keep_rg=True reads the input's header before the run: a BAM file, not a pipe")
+            text, _contigs = peek_header(os.fspath(src))
+            req["groups"] = [g[1] for g in bam_read_groups(text)]
+            if len(req["groups"]) > 255:
+                raise ValueError(f"{f.__name__}: {len(req['groups'])} read groups: the recalibration table holds at most 255")
+        self._recal_req = req
+        try:
+            return f(self, *args, **kw)
+        finally:
+            self._recal_req = None
+    return call
+
+
+def read_amb(prefix: str) -> list:
+    """the reference's holes from <prefix>.amb as (offset, length) pairs in pac; no file: none"""
+    try:
+        with open(prefix + ".amb") as f:
+            f.readline()
+            return [(int(a), int(b)) for a, b, *_ in (ln.split() for ln in f if ln.strip())]
+    except FileNotFoundError:
+        return []
+
+
 def _pct(a: int, b: int) -> str:
     return "%.2f%%" % (100.0 * a / b) if b else "N/A"
 
@@ -586,6 +644,7 @@ class Aligner:
         self.long_reads = bool(long_reads)
         self.L = load_library()
         self.dev = torch.device(device)
+        self.prefix = prefix                                  # (the recalibration table reads the reference's holes from <prefix>.amb)
         if _mem is not None:                                  # (index, contigs, packed reference) already in memory: from_memory()
             idx, self.contigs, self.pac = _mem
             self.l_pac = sum(c[1] for c in self.contigs)
@@ -903,6 +962,10 @@ class Aligner:
         nat.set_reseed(self.reseed if self.reseed.enable else None)
         fmt, level, sorted_keywords = self._output
         if fmt == "bam_sorted":
+            if sorted_keywords.get("recal") is not None:          # the table's read groups are the run's: align_groups', keep_rg's (the input's header), else -R's, else the one group `*`
+                kept = (getattr(self, "_recal_req", None) or {}).get("groups")
+                groups = kept if kept else [g[1] for g in self._groups] if getattr(self, "_groups", None) else [self._rg_id.decode()] if getattr(self, "rg_line", "") else None
+                sorted_keywords = dict(sorted_keywords, recal=dict(sorted_keywords["recal"], read_groups=groups))
             nat.set_sorted(level=level, **sorted_keywords)
         else:
             nat.set_output(fmt, level)
@@ -914,11 +977,12 @@ class Aligner:
 
     @_coverage_keywords
     @_stats_keywords
+    @_recal_keywords
     def align_file(self, reads_fa: str, out, batch_reads: int = 0, paired: bool = False, chunk_bases: int = 0, fmt: str = "sam", level: int = 1,
                    sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
                    index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
                    coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False,
-                    flagstat=None, idxstats=None, stats=None, insert_cap=None) -> int:
+                    flagstat=None, idxstats=None, stats=None, insert_cap=None, recal=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None) -> int:
         if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None or barcode_tag is not None or barcode_name or barcode_edits is not None:
             return self._align_bam(lambda o: self.align_file(reads_fa, o, batch_reads=batch_reads, paired=paired, chunk_bases=chunk_bases), out, fmt, level,
                                    sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift, optical_distance, barcode_tag, barcode_name, barcode_edits)
@@ -1064,10 +1128,16 @@ class Aligner:
                 raise NotImplementedError("sort=True needs the native pipeline (BMH_ALIGNER_NATIVE=0 and profile runs write batch after batch)")
         cov_req = getattr(self, "_cov_req", None) if sort else None
         stats_req = getattr(self, "_stats_req", None) if sort else None
+        recal_req = getattr(self, "_recal_req", None) if sort else None
+        recal_kw = None
+        if recal_req is not None:                                 # (the mask: the known sites and the reference's holes, made once per run; the reference is the index's)
+            from .lib import known_sites_mask
+            mask = known_sites_mask(recal_req["known_sites"], self.contigs, l_pac=self.l_pac, holes=read_amb(self.prefix) if getattr(self, "prefix", None) else None)
+            recal_kw = dict(mask=mask, min_qual=recal_req["min_qual"], max_cycle=recal_req["max_cycle"], known_sites=recal_req["known_sites"])
         sorted_keywords = dict(markdup=bool(markdup), optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name, barcode_edits=barcode_edits,
                                index_format=index_format, csi_min_shift=int(csi_min_shift), window=int(sort_window or 0), sort_mem=sort_mem or None, sort_tmp=sort_tmp,
                                coverage=dict(min_mapq=cov_req["min_mapq"], deletions=cov_req["deletions"], bin=cov_req["bin"]) if cov_req is not None else None,
-                               stats=dict(insert_cap=stats_req["insert_cap"]) if stats_req is not None else None) if sort else {}
+                               stats=dict(insert_cap=stats_req["insert_cap"]) if stats_req is not None else None, recal=recal_kw) if sort else {}
         self._output = ("bam_sorted" if sort else "bam", level, sorted_keywords)
         try:
             n = run(shim)
@@ -1078,6 +1148,10 @@ class Aligner:
             if stats_req is not None:
                 from .lib import bam_stats
                 self.stats = got["stats"] if n else bam_stats(b"", len(self.contigs), stats_req["insert_cap"], host=True)
+            if recal_req is not None:
+                from .lib import bam_recal
+                self.recal = got["recal"] if n else dict(bam_recal(b"", self.contigs, self.pac, self.l_pac, mask=recal_kw["mask"], min_qual=recal_req["min_qual"], max_cycle=recal_req["max_cycle"],
+                                                                 host=True), known_sites=recal_req["known_sites"])
             if markdup:
                 from .lib import MARKDUP_COUNTS, BARCODE_GROUP_COUNTS, OPTICAL_COUNTS
                 self.markdup_counts = got["markdup_counts"] if n else dict.fromkeys(MARKDUP_COUNTS, 0)
@@ -1123,6 +1197,9 @@ class Aligner:
                 _write_text(cov_req["bed"], coverage_bed_text(self.coverage, self.contigs, cov_req["bin"]))
         if stats_req is not None:
             write_stats_texts(stats_req, self.stats, self.contigs)
+        if recal_req is not None:
+            from .recal import write_recal_table
+            write_recal_table(self.recal, recal_req["table"])
         if markdup_metrics is not None:
             text = markdup_metrics_text_libraries(self.markdup_library_counts) if getattr(self, "_groups", None) else markdup_metrics_text(self.markdup_counts, getattr(self, "rg_line", ""))
             if hasattr(markdup_metrics, "write"):
@@ -1134,13 +1211,18 @@ class Aligner:
 
     @_coverage_keywords
     @_stats_keywords
+    @_recal_keywords
     def align_files(self, reads: str, mates: str | None = None, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
                     sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None, keep_rg: bool = False,
                     index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
                     collate: bool = False, collate_mem=None,
                     coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False,
-                    flagstat=None, idxstats=None, stats=None, insert_cap=None) -> int:
-        """flagstat=, idxstats=, stats= (paths or text file objects; need sort=True): `samtools flagstat`'s and `samtools idxstats`' texts and a sectioned summary with
+                    flagstat=None, idxstats=None, stats=None, insert_cap=None, recal=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None) -> int:
+        """recal= (a path or a text file object; needs sort=True): the covariate table of base quality score recalibration of the file being written (DESIGN.md
+        4.16; recal_table_text's rows), counted on the device from every window of the final merge behind its flag step against the index's own reference, under
+        known_sites= (VCF or BED files, plain or gzip; the reference's holes are always masked), recal_min_qual= (6) and recal_max_cycle= (500).  The read groups
+        are the run's (-R, align_groups'; with keep_rg=True the @RG lines of the input's header, which is read ahead of the run: a file, not a pipe).  self.recal holds the arrays afterwards (bam_recal's dict).
+        flagstat=, idxstats=, stats= (paths or text file objects; need sort=True): `samtools flagstat`'s and `samtools idxstats`' texts and a sectioned summary with
         mapq and insert-size histograms (stats_text) of the file being written, computed on the device from every window of the final merge behind its flag step
         (DESIGN.md 4.15), so with the 0x400 flags markdup=True sets; insert_cap=N (2 .. 65536): sizes from N up share the last bin.  self.stats holds the arrays
         afterwards (bam_stats' dict).  The BAM and its index are byte for byte those of the run without them.
@@ -1239,12 +1321,13 @@ class Aligner:
 
     @_coverage_keywords
     @_stats_keywords
+    @_recal_keywords
     def align_groups(self, groups, out=None, paired: bool = False, chunk_bases: int = 0, batch_reads: int = 0, fmt: str = "sam", level: int = 1,
                      sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
                      index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
                      collate: bool = False, collate_mem=None,
                      coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False,
-                    flagstat=None, idxstats=None, stats=None, insert_cap=None) -> int:
+                    flagstat=None, idxstats=None, stats=None, insert_cap=None, recal=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None) -> int:
         """several read groups -- a sample's lanes and libraries -- into one output (bmh_aligner_run_groups).  groups: [(rg_line, reads, mates or None), ...]; every
         rg_line is unescaped and checked as -R's value is, reads / mates are what align_files takes (one file or R1 + R2; plain, gzip or BGZF; FASTA or FASTQ; or
         one BAM, whose own @RG lines and RG tags stay ignored: align_files(keep_rg=True) is the run that keeps them, and the two do not combine).  Group g's records are byte for byte those of align_files(reads_g, mates_g) alone under -R rg_g, and

@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "bmh_bam_stats_opt_default", "bmh_bam_stats_free", "bmh_bam_stats_device", "bmh_bam_stats_host",
     "bmh_bam_post_opt_default", "bmh_bam_post_result_free", "bmh_bam_post_file_device", "bmh_bam_post_file_host",
     "bmh_bam_templates_device", "bmh_bam_templates_host", "bmh_bam_templates_free",
+    "bmh_recal_opt_default", "bmh_recal_free", "bmh_recal_kernel_limits", "bmh_bam_recal_device", "bmh_bam_recal_host", "bmh_known_sites_mask", "bmh_recal_mask_holes",
 ]
 
 
@@ -748,8 +749,10 @@ def index_format_code(index_format, csi_min_shift, what: str) -> tuple:
 
 def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False, markdup: bool = False, read_groups=None,
                     index_format: str = "bai", csi_min_shift: int = 14, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None, stats=None,
-                    optical_distance=None) -> tuple:
-    """stats={insert_cap} (bmh_sorted_opt_t's stats; {} for the default): the file's statistics (bam_stats' dict), taken from the same windows with the flags
+                    optical_distance=None, recal=None) -> tuple:
+    """recal={pac, l_pac, contig_offset, mask, read_groups, min_qual, max_cycle, known_sites} (bmh_sorted_opt_t's recal; recal_opt's keywords): the file's covariate
+    table (bam_recal's dict), from the same windows with the flags markdup=True sets, comes last in the tuple.
+    stats={insert_cap} (bmh_sorted_opt_t's stats; {} for the default): the file's statistics (bam_stats' dict), taken from the same windows with the flags
     markdup=True sets, come last in the tuple, behind the coverage where both are asked for.
     coverage={min_mapq, deletions, bin, tile} (bmh_sorted_opt_t's coverage; bam_coverage's keywords, {} for the defaults): the file's coverage, taken from
     the windows of the merge as they are written -- with markdup=True the marked duplicates are counted out -- comes last in the tuple.
@@ -764,7 +767,7 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
     optical_distance: the record's field, which the library refuses here -- a stand-alone file has no optical step (bam_markdup counts optical duplicates)."""
     L = _sorted_file_api(load_library())
     q = sorted_request("bam_sorted_file", L, markdup=markdup, read_groups=read_groups, optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name, barcode_edits=barcode_edits, coverage=coverage,
-                       stats=stats, index_format=index_format, csi_min_shift=csi_min_shift, level=level, window=window)
+                       stats=stats, index_format=index_format, csi_min_shift=csi_min_shift, level=level, window=window, recal=recal)
     records = bytes(records)
     names = (C.c_char_p * max(len(contigs), 1))(*[c[0].encode() for c in contigs])
     lens = np.ascontiguousarray([c[1] for c in contigs] or [0], dtype=np.int64)
@@ -780,7 +783,7 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
         raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_sorted_file: " + _err(L))
     try:
         got = q.results(L)
-        return (C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)) + tuple(got[k] for k in ("markdup", "coverage", "stats") if k in got)
+        return (C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)) + tuple(got[k] for k in ("markdup", "coverage", "stats", "recal") if k in got)
     finally:
         L.bmh_free.argtypes = [C.c_void_p]
         L.bmh_free(bam); L.bmh_free(bai)
@@ -920,6 +923,130 @@ def bam_stats(records: bytes, n_contigs: int, insert_cap: int = INSERT_CAP_DEFAU
     return stats_dict(L, st)
 
 
+class RecalOpt(C.Structure):
+    """bmh_recal_opt_t"""
+    _fields_ = [("min_qual", C.c_int32), ("max_cycle", C.c_int32), ("pac", C.c_void_p), ("l_pac", C.c_uint64), ("contig_offset", C.c_void_p), ("mask", C.c_void_p),
+                ("mask_words", C.c_uint64), ("n_groups", C.c_int32), ("rg_ids", C.POINTER(C.c_char_p))]
+
+
+class Recal(C.Structure):
+    """bmh_recal_t"""
+    _fields_ = [("n_groups", C.c_int32), ("min_qual", C.c_int32), ("max_cycle", C.c_int32), ("n_qual", C.c_int32), ("summary", C.c_uint64 * 16),
+                ("cycle_m", _u64p), ("cycle_id", _u64p), ("context_m", _u64p), ("context_id", _u64p)]
+
+
+RECAL_SUMMARY = ("records_seen", "records_counted", "left_out_no_contig", "left_out_flags", "left_out_mapq", "left_out_no_qualities", "left_out_no_operations", "bases_kept",
+                 "skipped_not_acgt", "skipped_low_quality", "skipped_masked", "skipped_masked_anchor", "cycles_capped", "masked_positions")
+RECAL_MIN_QUAL, RECAL_MAX_CYCLE, RECAL_INDEL_QUAL, RECAL_MAX_GROUPS = 6, 500, 45, 255
+
+
+def recal_opt(what="bam_recal", pac=None, l_pac=0, contig_offset=None, mask=None, read_groups=None, min_qual=None, max_cycle=None, known_sites=None):
+    """the recalibration table's keywords, checked -> (bmh_recal_opt_t, what it points to, to be kept alive as long as it); ValueError names the keyword.
+    pac: the .pac body (bytes or a uint8 array; None where the caller holds the reference: an aligner's run), l_pac its bases, contig_offset every contig's
+    first base in it (None: back to back), mask a uint64 array of (l_pac + 63) // 64 words (known_sites_mask), read_groups the IDs in table order (None: the
+    one group `*`).  known_sites is not read here: the names go into the text"""
+    min_qual = RECAL_MIN_QUAL if min_qual is None else min_qual
+    max_cycle = RECAL_MAX_CYCLE if max_cycle is None else max_cycle
+    if not isinstance(min_qual, (int, np.integer)) or isinstance(min_qual, bool) or not 0 <= min_qual <= 93:
+        raise ValueError(f"{what}: recal_min_qual {min_qual!r}: an integer in 0 .. 93")
+    if not isinstance(max_cycle, (int, np.integer)) or isinstance(max_cycle, bool) or not 1 <= max_cycle <= 65535:
+        raise ValueError(f"{what}: recal_max_cycle {max_cycle!r}: an integer in 1 .. 65535")
+    keep = []
+    o = RecalOpt(int(min_qual), int(max_cycle))
+    if pac is not None:
+        a = np.frombuffer(bytes(pac), dtype=np.uint8) if isinstance(pac, (bytes, bytearray, memoryview)) else np.ascontiguousarray(pac, dtype=np.uint8)
+        if a.size < (int(l_pac) + 3) // 4:
+            raise ValueError(f"{what}: pac holds {a.size} bytes, {int(l_pac)} bases take {(int(l_pac) + 3) // 4}")
+        a = np.concatenate([a, np.zeros(8, np.uint8)])
+        keep.append(a); o.pac = a.ctypes.data
+    o.l_pac = int(l_pac)
+    if contig_offset is not None:
+        a = np.ascontiguousarray(contig_offset, dtype=np.uint64)
+        keep.append(a); o.contig_offset = a.ctypes.data
+    if mask is not None:
+        a = np.ascontiguousarray(mask, dtype=np.uint64)
+        keep.append(a); o.mask = a.ctypes.data; o.mask_words = a.size
+    if read_groups is not None:
+        ids = [str(g) for g in read_groups]
+        if len(ids) > RECAL_MAX_GROUPS:
+            raise ValueError(f"{what}: {len(ids)} read groups: the recalibration table holds at most {RECAL_MAX_GROUPS}")
+        if ids:
+            arr = (C.c_char_p * len(ids))(*[g.encode() for g in ids])
+            keep.append(arr); o.n_groups = len(ids); o.rg_ids = arr
+    return o, keep
+
+
+def recal_dict(L, rt: Recal, read_groups=None, known_sites=None) -> dict:
+    """bmh_recal_t -> {name: numpy array of uint64} and the run's parameters; the record's arrays are released"""
+    L.bmh_recal_free.argtypes, L.bmh_recal_free.restype = [C.POINTER(Recal)], None
+    try:
+        g, c, nq = int(rt.n_groups), int(rt.max_cycle), int(rt.n_qual)
+        return dict(summary=np.array(list(rt.summary), dtype=np.uint64), cycle_m=np.ctypeslib.as_array(rt.cycle_m, shape=(g, nq, 2 * c, 2)).copy(),
+                    cycle_id=np.ctypeslib.as_array(rt.cycle_id, shape=(g, 2 * c, 3)).copy(), context_m=np.ctypeslib.as_array(rt.context_m, shape=(g, nq, 17, 2)).copy(),
+                    context_id=np.ctypeslib.as_array(rt.context_id, shape=(g, 65, 3)).copy(), min_qual=int(rt.min_qual), max_cycle=c,
+                    read_groups=[str(x) for x in read_groups] if read_groups else ["*"], known_sites=[str(p) for p in (known_sites or [])])
+    finally:
+        L.bmh_recal_free(C.byref(rt))
+
+
+def bam_recal(records: bytes, contigs, pac, l_pac: int, mask=None, read_groups=None, min_qual: int = RECAL_MIN_QUAL, max_cycle: int = RECAL_MAX_CYCLE, host: bool = False,
+              contig_offset=None) -> dict:
+    """bmh_bam_recal_device (host=True: _host, no device needed): a stream of BAM records in any order over `contigs` ((name, length) pairs, or lengths) and the
+    reference's .pac body -> the covariate table of DESIGN.md 4.16 as a dict of uint64 arrays, device and host integer for integer the same: summary [16]
+    (RECAL_SUMMARY's names), cycle_m [groups][94][2 max_cycle][2] (event M: observations, errors; slot max_cycle + c - 1 for cycle c > 0, max_cycle + c for
+    c < 0), cycle_id [groups][2 max_cycle][3] (events I and D at quality 45: their observations, insertion errors, deletion errors), context_m
+    [groups][94][17][2] (context 4 a + b, 16: none), context_id [groups][65][3] (16 a + 4 b + c, 64: none); and min_qual, max_cycle, read_groups, known_sites.
+    recal_table_text (bwamem_hip.recal) makes the text.  A refused record raises ValueError naming its index."""
+    L = load_library()
+    records = bytes(records)
+    lens = np.ascontiguousarray([c[1] if isinstance(c, (tuple, list)) else c for c in contigs] or [0], dtype=np.int32)
+    o, keep = recal_opt("bam_recal", pac, l_pac, contig_offset, mask, read_groups, min_qual, max_cycle)
+    rt = Recal()
+    head = [C.c_char_p, C.c_uint64, C.c_int, C.c_void_p, C.POINTER(RecalOpt)]
+    if host:
+        L.bmh_bam_recal_host.argtypes = head + [C.POINTER(Recal)]
+        rc = L.bmh_bam_recal_host(records, len(records), len(contigs), lens.ctypes.data, C.byref(o), C.byref(rt))
+    else:
+        L.bmh_bam_recal_device.argtypes = head + [C.c_void_p, C.POINTER(Recal)]
+        rc = L.bmh_bam_recal_device(records, len(records), len(contigs), lens.ctypes.data, C.byref(o), _current_stream(), C.byref(rt))
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_recal: " + _err(L))
+    return recal_dict(L, rt, read_groups)
+
+
+def known_sites_mask(paths, contigs, l_pac=None, contig_offset=None, holes=None) -> np.ndarray:
+    """bmh_known_sites_mask and bmh_recal_mask_holes: the known-sites files `paths` (VCF or BED text, plain or gzip) over `contigs` ((name, length) pairs) and the
+    reference's holes ((offset, length) pairs in pac: the .amb's) -> the mask, a uint64 array of (l_pac + 63) // 64 words (l_pac None: the contigs' total).  A line
+    that cannot be taken raises ValueError naming file and line"""
+    L = load_library()
+    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths or [])
+    lens = np.ascontiguousarray([c[1] for c in contigs] or [0], dtype=np.int32)
+    total = int(sum(int(c[1]) for c in contigs)) if l_pac is None else int(l_pac)
+    mask = np.zeros((total + 63) // 64, dtype=np.uint64)
+    names = (C.c_char_p * max(len(contigs), 1))(*[c[0].encode() for c in contigs])
+    off = np.ascontiguousarray(contig_offset, dtype=np.uint64) if contig_offset is not None else None
+    ps = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+    L.bmh_known_sites_mask.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    rc = L.bmh_known_sites_mask(ps, len(paths), len(contigs), names, lens.ctypes.data, off.ctypes.data if off is not None else None, mask.ctypes.data, mask.size)
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_known_sites_mask: " + _err(L))
+    if holes:
+        ho = np.ascontiguousarray([h[0] for h in holes], dtype=np.uint64); hl = np.ascontiguousarray([h[1] for h in holes], dtype=np.uint64)
+        L.bmh_recal_mask_holes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
+        if L.bmh_recal_mask_holes(ho.ctypes.data, hl.ctypes.data, len(holes), mask.ctypes.data, mask.size) != 0:
+            raise ValueError("bmh_recal_mask_holes: " + _err(L))
+    return mask
+
+
+def recal_kernel_limits() -> dict:
+    """bmh_recal_kernel_limits: the capacities of the device form, for the tests that sit on them"""
+    L = load_library()
+    out = (C.c_uint32 * 5)()
+    L.bmh_recal_kernel_limits.argtypes, L.bmh_recal_kernel_limits.restype = [C.POINTER(C.c_uint32)], None
+    L.bmh_recal_kernel_limits(out)
+    return dict(zip(("slots", "lanes", "lds_cycles", "block_records", "lds_bases"), (int(v) for v in out)))
+
+
 def reads_last_bam_counts() -> dict:
     """bmh_reads_last_bam_counts: what the process's last load_reads_files / run_files / bam_reads call left out of its BAM input -- records skipped (flag 0x100
     or 0x800), f and B tags left out of the comments"""
@@ -933,20 +1060,21 @@ def reads_last_bam_counts() -> dict:
 class SortedOpt(C.Structure):
     """bmh_sorted_opt_t"""
     _fields_ = [("level", C.c_int32), ("window", C.c_uint32), ("index_format", C.c_int32), ("min_shift", C.c_int32), ("sort_mem", C.c_uint64), ("tmp_dir", C.c_char_p),
-                ("markdup", C.POINTER(MarkdupOpt)), ("coverage", C.POINTER(CoverageOpt)), ("stats", C.POINTER(BamStatsOpt))]
+                ("markdup", C.POINTER(MarkdupOpt)), ("coverage", C.POINTER(CoverageOpt)), ("stats", C.POINTER(BamStatsOpt)), ("recal", C.POINTER(RecalOpt))]
 
 
 class SortedResults(C.Structure):
     """bmh_sorted_results_t"""
     _fields_ = [("markdup", C.POINTER(MarkdupCounts)), ("coverage", C.POINTER(Coverage)), ("stats", C.POINTER(BamStats)), ("parts", C.c_uint32), ("n_libraries", C.c_int32),
                 ("markdup_ms", C.c_double * 2), ("optical_ms", C.c_double), ("coverage_ms", C.c_double), ("stats_ms", C.c_double),
-                ("markdup_d2h_bytes", C.c_uint64), ("coverage_windows", C.c_uint64), ("stats_windows", C.c_uint64)]
+                ("markdup_d2h_bytes", C.c_uint64), ("coverage_windows", C.c_uint64), ("stats_windows", C.c_uint64),
+                ("recal", C.POINTER(Recal)), ("recal_ms", C.c_double), ("recal_windows", C.c_uint64)]
 
 
 SortedFileOpt = SortedOpt      # (the name the record had while it served bmh_bam_sorted_file_* alone: code that imports it gets the one record)
 
 
-SORTED_PARTS = dict(markdup=1, optical=2, barcode=4, grouped=8, coverage=16, stats=32)      # BMH_SORTED_*
+SORTED_PARTS = dict(markdup=1, optical=2, barcode=4, grouped=8, coverage=16, stats=32, recal=64)      # BMH_SORTED_*
 
 
 def _current_stream() -> int:
@@ -968,11 +1096,13 @@ class SortedRequest:
             out["coverage"] = coverage_dict(L, self.cov)
         if self.opt.stats:
             out["stats"] = stats_dict(L, self.st)
+        if self.opt.recal:
+            out["recal"] = recal_dict(L, self.rt, self.recal_kw.get("read_groups"), self.recal_kw.get("known_sites"))
         return out
 
 
 def sorted_request(what: str, L, markdup: bool = False, read_groups=None, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None, stats=None,
-                   index_format: str = "bai", csi_min_shift: int = 14, level: int = 1, window: int = 0, sort_mem=None, sort_tmp=None, libraries: int = 0) -> SortedRequest:
+                   index_format: str = "bai", csi_min_shift: int = 14, level: int = 1, window: int = 0, sort_mem=None, sort_tmp=None, libraries: int = 0, recal=None) -> SortedRequest:
     """the keywords of every sorted output (bam_sorted_file, bam_post, NativeAligner.set_sorted), checked -> a SortedRequest.  ValueError names the keyword: the
     barcode keywords, optical_distance and read_groups need markdup=True; barcode_edits needs a barcode source; index_format "bai" or "csi" with csi_min_shift
     10 .. 24; level 0 or 1; sort_mem a number of bytes.  libraries: room for that many libraries' rows in the counts record where read_groups are not given (the
@@ -1006,6 +1136,10 @@ def sorted_request(what: str, L, markdup: bool = False, read_groups=None, optica
     q.opt = SortedOpt(int(level), int(window), ix_code, ix_shift, int(sort_mem or 0), os.fsencode(sort_tmp) if sort_tmp is not None else None,
                       C.pointer(q.mo) if markdup else None, C.pointer(q.co) if q.co is not None else None, C.pointer(q.so) if q.so is not None else None)
     q.res = SortedResults(C.pointer(q.mc) if markdup else None, C.pointer(q.cov) if q.co is not None else None, C.pointer(q.st) if q.so is not None else None)
+    q.recal_kw, q.rt = dict(recal or {}), Recal()
+    if recal is not None:                                          # (recal_opt's keywords; the record is the options' and the results' last member)
+        q.ro, q.recal_keep = recal_opt(what, **recal)
+        q.opt.recal = C.pointer(q.ro); q.res.recal = C.pointer(q.rt)
     return q
 
 
@@ -1043,8 +1177,9 @@ def _names_blob(addr, n: int) -> list:
 
 
 def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 0, index_format: str = "bai", csi_min_shift: int = 14, sort_mem=None, sort_tmp=None, batch_bytes=None,
-             markdup: bool = False, libraries: bool = False, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None, collate: bool = False, stats=None) -> dict:
-    """stats={insert_cap} (bmh_sorted_opt_t's stats; {} for the default): "stats" holds the file's statistics (bam_stats' dict), from the windows of the merge.
+             markdup: bool = False, libraries: bool = False, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None, collate: bool = False, stats=None, recal=None) -> dict:
+    """recal={pac, l_pac, ...} (recal_opt's keywords; read_groups: the header's @RG IDs in order, see bam_read_groups): "recal" holds the file's covariate table.
+    stats={insert_cap} (bmh_sorted_opt_t's stats; {} for the default): "stats" holds the file's statistics (bam_stats' dict), from the windows of the merge.
     bmh_bam_post_file_device (host=True: bmh_bam_post_file_host, no device needed; it holds the whole record stream in memory): the BAM or SAM file `src` of any
     aligner (a path; plain, gzip or BGZF; a pipe) -> the coordinate-sorted BAM, handed to write(bytes) piece by piece, and a dict: "index" (the .bai or .csi
     bytes), "header" (the output header's text), "contigs" ((name, length) pairs), "counts" (BAM_POST_COUNTS' names), with markdup=True "markdup" (bam_markdup's
@@ -1063,7 +1198,7 @@ def bam_post(src: str, write, host: bool = False, level: int = 1, window: int = 
         raise ValueError(f"{what}: batch_bytes {batch_bytes}: at most 2^30")
     L = load_library()
     q = sorted_request(what, L, markdup=markdup, optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name, barcode_edits=barcode_edits, coverage=coverage,
-                       stats=stats, index_format=index_format, csi_min_shift=csi_min_shift, level=level, window=window, sort_mem=sort_mem, sort_tmp=sort_tmp, libraries=255 if libraries else 0)
+                       stats=stats, index_format=index_format, csi_min_shift=csi_min_shift, level=level, window=window, sort_mem=sort_mem, sort_tmp=sort_tmp, libraries=255 if libraries else 0, recal=recal)
     o = BamPostOpt(q.opt, int(batch_bytes or 0), 1 if libraries else 0, 1 if collate else 0)
     failed = []
 
@@ -1332,6 +1467,7 @@ class NativeAligner:
         L.bmh_aligner_set_sorted_output.argtypes = [C.c_void_p, C.POINTER(SortedOpt)]
         if L.bmh_aligner_set_sorted_output(self.handle, C.byref(q.opt)) != 0:
             raise ValueError("bmh_aligner_set_sorted_output: " + _err(L))
+        self._sorted_req = q                                       # (a recalibration table's mask stays the caller's until the run is over: kept alive here)
 
     def sorted_results(self, *need) -> dict:
         """bmh_aligner_sorted_results: what the last sorted run left, each where the run computed it -- "markdup_counts" (MARKDUP_COUNTS' names), "markdup_library_counts"
@@ -1349,10 +1485,12 @@ class NativeAligner:
             raise ValueError("bmh_aligner_sorted_results: " + _err(L))
         has = {nm for nm, bit in SORTED_PARTS.items() if res.parts & bit}
         n_lib = int(res.n_libraries)
-        mc, cov, st = MarkdupCounts(), Coverage(), BamStats()
+        mc, cov, st, rt = MarkdupCounts(), Coverage(), BamStats(), Recal()
         rows, opt_rows = ((C.c_uint64 * (k * max(n_lib, 1)))() for k in (8, 3))
         mc.lib_counts, mc.lib_optical = C.cast(rows, _u64p), C.cast(opt_rows, _u64p)
         res = SortedResults(C.pointer(mc) if "markdup" in has else None, C.pointer(cov) if "coverage" in has else None, C.pointer(st) if "stats" in has else None)
+        if "recal" in has:                                         # (the results' last members are read only under `need`)
+            res.recal = C.pointer(rt); mask |= SORTED_PARTS["recal"]
         if L.bmh_aligner_sorted_results(self.handle, C.byref(res), mask) != 0:
             raise ValueError("bmh_aligner_sorted_results: " + _err(L))
         out = {}
@@ -1372,6 +1510,9 @@ class NativeAligner:
             out["coverage"], out["coverage_ms"] = coverage_dict(L, cov), (float(res.coverage_ms), int(res.coverage_windows))
         if "stats" in has:
             out["stats"], out["stats_ms"] = stats_dict(L, st), (float(res.stats_ms), int(res.stats_windows))
+        if "recal" in has:
+            kw = getattr(getattr(self, "_sorted_req", None), "recal_kw", {})
+            out["recal"], out["recal_ms"] = recal_dict(L, rt, kw.get("read_groups"), kw.get("known_sites")), (float(res.recal_ms), int(res.recal_windows))
         return out
 
     def sort_index(self, base_offset: int) -> bytes:

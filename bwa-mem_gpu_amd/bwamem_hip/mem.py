@@ -52,7 +52,12 @@ There is no base-quality filter and no correction for overlapping mates.  With -
 --flagstat PATH, --idxstats PATH and --stats PATH (need --sort) write `samtools flagstat`'s sixteen lines, `samtools idxstats`' table and a sectioned summary (flag
 and contig counts, reads, bases, operations, NM, the mapq histogram, the insert-size histogram per orientation and its median, MAD, mode, mean and SD) of the
 file being written, computed on the device while it is written, from the records in their final order with --markdup's final 0x400 flags.  The statistics are
-the whole file's, not per read group or library.  An option that is
+the whole file's, not per read group or library.
+--recal PATH (needs --sort) writes the covariate table of base quality score recalibration -- observations and errors by read group, quality, cycle and context,
+for mismatches, insertions and deletions (GATK BaseRecalibrator's counting rules at its default covariates, restated; BAQ off, no adaptor clipping)
+-- counted on the device while the file is written, against the index's own reference, with --markdup's duplicates counted out.  --known-sites FILE (repeatable;
+VCF or BED, plain or gzip) masks known variants, the reference's holes (.amb) are always masked; --recal-min-qual Q (0 .. 93; 6) and --recal-max-cycle N
+(1 .. 65535; 500).  The read groups are -R's, --rg's or, with --keep-rg, the @RG lines of the input's header (read ahead of the run: a file, not a pipe).  An option that is
 not on that list is refused by name.  Two input files imply pairs.  One plain, regular file is offered to Aligner.align_file first, which takes it when every
 record has one sequence line (its own counting pass decides, before anything is written); every other input goes through
 Aligner.align_files; the text is the same.  A refused file ends the command with status 1 and the library's message on stderr.
@@ -90,6 +95,7 @@ def main(argv=None) -> int:
     collate, collate_mem = False, None
     cov_paths, cov_bin, cov_mapq, cov_del = {}, None, None, False
     stats_paths = {}
+    recal_kw, recal_sites = {}, []
     groups = []                                                     # --rg LINE: [line, files...]; the positionals behind it are its files
     i = 0
     while i < len(argv):
@@ -153,6 +159,21 @@ def main(argv=None) -> int:
                 print(f"[bwamem_hip.mem] option {a} needs a value", file=sys.stderr)
                 return 2
             cov_paths[a] = argv[i + 1]
+            i += 1
+        elif a in ("--recal", "--known-sites", "--recal-min-qual", "--recal-max-cycle"):
+            if i + 1 >= len(argv):
+                print(f"[bwamem_hip.mem] option {a} needs a value", file=sys.stderr)
+                return 2
+            if a == "--known-sites":
+                recal_sites.append(argv[i + 1])
+            elif a == "--recal":
+                recal_kw["recal"] = argv[i + 1]
+            else:
+                lo, hi = (0, 93) if a == "--recal-min-qual" else (1, 65535)
+                if not (argv[i + 1].isascii() and argv[i + 1].isdigit()) or not lo <= int(argv[i + 1]) <= hi:
+                    print(f"[bwamem_hip.mem] option {a} needs a whole number, {lo} .. {hi}", file=sys.stderr)
+                    return 2
+                recal_kw[a[2:].replace("-", "_")] = int(argv[i + 1])
             i += 1
         elif a in ("--flagstat", "--idxstats", "--stats"):
             if i + 1 >= len(argv):
@@ -274,6 +295,12 @@ def main(argv=None) -> int:
     if (cov_paths or cov_bin is not None or cov_mapq is not None or cov_del) and not sort:
         print("[bwamem_hip.mem] --coverage, --coverage-hist, --coverage-bed, --coverage-bin, --coverage-min-mapq and --coverage-deletions need --sort (depth is computed where the sorted file is written)", file=sys.stderr)
         return 2
+    if (recal_sites or "recal_min_qual" in recal_kw or "recal_max_cycle" in recal_kw) and "recal" not in recal_kw:
+        print("[bwamem_hip.mem] --known-sites, --recal-min-qual and --recal-max-cycle need --recal (they say what is counted, not where it goes)", file=sys.stderr)
+        return 2
+    if recal_kw and not sort:
+        print("[bwamem_hip.mem] --recal, --known-sites, --recal-min-qual and --recal-max-cycle need --sort (the table is counted where the sorted file is written)", file=sys.stderr)
+        return 2
     if stats_paths and not sort:
         print("[bwamem_hip.mem] --flagstat, --idxstats and --stats need --sort (the statistics are computed where the sorted file is written)", file=sys.stderr)
         return 2
@@ -320,6 +347,8 @@ def main(argv=None) -> int:
                           coverage_min_mapq=cov_mapq, coverage_deletions=cov_del)
         if stats_paths:
             fmt_kw.update(flagstat=stats_paths.get("--flagstat"), idxstats=stats_paths.get("--idxstats"), stats=stats_paths.get("--stats"))
+        if recal_kw:
+            fmt_kw.update(recal_kw, known_sites=recal_sites or None)
         done = False
         if groups:
             al.align_groups([(g[0], g[1], g[2] if len(g) == 3 else None) for g in groups], out=out, paired=interleaved, **fmt_kw)

@@ -933,10 +933,21 @@ int bmh_aligner_set_sorted_output(bmh_aligner_t *h, const bmh_sorted_opt_t *opt)
 	bmh_markdup_counts_t mc; bmh_coverage_t cv; bmh_bam_stats_t st;      // (the records the check asks for: a run has its own)
 	memset(&mc, 0, sizeof mc);
 	bmh_sorted_results_t res; memset(&res, 0, sizeof res);
-	res.markdup = &mc; res.coverage = &cv; res.stats = &st;
+	bmh_recal_t rt;
+	res.markdup = &mc; res.coverage = &cv; res.stats = &st; res.recal = &rt;
+	// the recalibration table of a run reads the reference the index holds on the device: its bases and the contigs' places are the aligner's (the mask and the
+	// group IDs stay the caller's until the run is over)
+	bmh_sorted_opt_t with; bmh_recal_opt_t ro; std::vector<uint64_t> coff;
+	if (opt && opt->recal && !opt->recal->pac) {
+		with = *opt; ro = *opt->recal;
+		for (int64_t o : h->a.off) coff.push_back((uint64_t)o);
+		ro.l_pac = (uint64_t)h->a.l_pac; ro.contig_offset = coff.data();
+		with.recal = &ro; opt = &with;
+	}
 	bsr_out_t J;
 	RCK(bsr_out_make(J, opt, h->a.n_contigs, h->a.len.data(), h->a.name_ptr.data(), &res, fn));
 	J.timed = true; J.P.table = h->a.next.P.table;
+	if (J.recal && !J.RU.pac) J.recal_d_pac = h->a.idx->dev.pac;
 	h->a.next = J; h->a.out_fmt = BMH_OUT_BAM_SORTED; h->a.out_level = J.level;
 	h->store.clear(); h->store.mem_bytes = opt && opt->sort_mem ? opt->sort_mem : 4ull << 30; h->store.tmp_dir = opt && opt->tmp_dir ? opt->tmp_dir : "";
 	h->last = bmh_aligner::last_t(); h->last.out.ix = J.ix; h->last.valid = true;      // (until a run is made: the index of a file without records, and no results)
@@ -974,11 +985,13 @@ int bmh_aligner_sorted_results(bmh_aligner_t *h, bmh_sorted_results_t *out, uint
 {
 	const char *fn = "bmh_aligner_sorted_results";
 	static const struct { uint32_t part; const char *did; } parts[] = {{BMH_SORTED_MARKDUP, "marked duplicates"}, {BMH_SORTED_OPTICAL, "counted optical duplicates"}, {BMH_SORTED_BARCODE, "compared barcodes"},
-	                                                                   {BMH_SORTED_GROUPED, "grouped barcodes by edits"}, {BMH_SORTED_COVERAGE, "computed coverage"}, {BMH_SORTED_STATS, "computed statistics"}};
+	                                                                   {BMH_SORTED_GROUPED, "grouped barcodes by edits"}, {BMH_SORTED_COVERAGE, "computed coverage"}, {BMH_SORTED_STATS, "computed statistics"},
+	                                                                   {BMH_SORTED_RECAL, "counted a recalibration table"}};
 	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	const bmh_aligner::last_t &T = h->last;
 	const uint32_t have = T.valid ? T.out.parts() : 0;
-	need |= (out->markdup ? BMH_SORTED_MARKDUP : 0u) | (out->coverage ? BMH_SORTED_COVERAGE : 0u) | (out->stats ? BMH_SORTED_STATS : 0u);
+	if (!(need & BMH_SORTED_RECAL)) out->recal = nullptr;              // (the results' last members are read only when the caller asks for the table by `need`)
+	need |= (out->markdup ? BMH_SORTED_MARKDUP : 0u) | (out->coverage ? BMH_SORTED_COVERAGE : 0u) | (out->stats ? BMH_SORTED_STATS : 0u) | (out->recal ? BMH_SORTED_RECAL : 0u);
 	for (const auto &p : parts)
 		if (need & ~have & p.part) { bmh_set_error("%s: no run has %s (or the last one failed before its file was complete)", fn, p.did); return BMH_EINVAL; }
 	bsr_out_t none;
@@ -1123,6 +1136,7 @@ struct out_stage_t {
 		const double tm0 = now_s();
 		if (rc == BMH_OK) rc = bsr_write_device(L0.bsr, L0.bam, h->store, J, L0.st, forward, this, fn);
 		if (trace && J.stats) fprintf(stderr, "[aligner] statistics: the kernels of %.0f windows took %.2f ms on the device, %.3f ms per window\n", J.stats_ms[1], J.stats_ms[0], J.stats_ms[0] / (J.stats_ms[1] > 0 ? J.stats_ms[1] : 1));
+		if (trace && J.recal) fprintf(stderr, "[aligner] recalibration table: the kernels of %.0f windows took %.2f ms on the device, %.3f ms per window\n", J.recal_ms[1], J.recal_ms[0], J.recal_ms[0] / (J.recal_ms[1] > 0 ? J.recal_ms[1] : 1));
 		if (trace && J.coverage) fprintf(stderr, "[aligner] coverage: the depth steps of %.0f windows took %.2f ms on the device, %.3f ms per window (tile %llu, %llu bins)\n", J.cov_ms[1], J.cov_ms[0], J.cov_ms[0] / (J.cov_ms[1] > 0 ? J.cov_ms[1] : 1), (unsigned long long)J.CP.tile, (unsigned long long)J.CP.n_bins());
 		if (trace && J.markdup) fprintf(stderr, "[aligner] duplicate marking: %.0f bytes of ordinals and entries came down with the batches\n", J.dup_ms[2]);
 		if (trace) fprintf(stderr, "[aligner] sorted output: %zu runs (%llu spilled) merged in %.1f ms\n", h->store.runs.size(), (unsigned long long)h->store.spilled, (now_s() - tm0) * 1e3);

@@ -63,20 +63,22 @@ extern "C" void bmh_sorted_opt_default(bmh_sorted_opt_t *o)
 uint32_t bsr_out_t::parts() const
 {
 	return (markdup ? BMH_SORTED_MARKDUP | (P.optical() ? BMH_SORTED_OPTICAL : 0u) | (P.barcode() ? BMH_SORTED_BARCODE : 0u) | (P.grouping() ? BMH_SORTED_GROUPED : 0u) : 0u) |
-	       (coverage ? BMH_SORTED_COVERAGE : 0u) | (stats ? BMH_SORTED_STATS : 0u);
+	       (coverage ? BMH_SORTED_COVERAGE : 0u) | (stats ? BMH_SORTED_STATS : 0u) | (recal ? BMH_SORTED_RECAL : 0u);
 }
 
 int bsr_out_make(bsr_out_t &J, const bmh_sorted_opt_t *opt, int n_contigs, const int32_t *contig_len, const char *const *contig_names, bmh_sorted_results_t *res, const char *fn)
 {
 	bmh_sorted_results_t none; memset(&none, 0, sizeof none);
 	if (!res) res = &none;
-	bmh_markdup_counts_t *const mc = res->markdup; bmh_coverage_t *const cov = res->coverage; bmh_bam_stats_t *const st = res->stats;
-	memset(res, 0, sizeof *res); res->markdup = mc; res->coverage = cov; res->stats = st;
+	bmh_sorted_opt_t o;
+	if (opt) o = *opt; else bmh_sorted_opt_default(&o);
+	// (the results' last members came with the recalibration table: a caller who does not ask for it may not have set them, so they are read with the option only)
+	bmh_markdup_counts_t *const mc = res->markdup; bmh_coverage_t *const cov = res->coverage; bmh_bam_stats_t *const st = res->stats; bmh_recal_t *const rt = o.recal ? res->recal : nullptr;
+	memset(res, 0, sizeof *res); res->markdup = mc; res->coverage = cov; res->stats = st; res->recal = rt;
+	if (rt) memset(rt, 0, sizeof *rt);
 	if (cov) memset(cov, 0, sizeof *cov);
 	if (st) memset(st, 0, sizeof *st);
 	J = bsr_out_t();
-	bmh_sorted_opt_t o;
-	if (opt) o = *opt; else bmh_sorted_opt_default(&o);
 	if (o.level != 0 && o.level != 1) { bmh_set_error("%s: level %d (0 or 1)", fn, o.level); return BMH_EINVAL; }
 	J.level = o.level; J.window = o.window;
 	int rc = J.ix.init(n_contigs, contig_len, fn, o.index_format, o.min_shift);
@@ -96,12 +98,18 @@ int bsr_out_make(bsr_out_t &J, const bmh_sorted_opt_t *opt, int n_contigs, const
 		if ((rc = bst_plan_make(J.SP, o.stats->insert_cap, n_contigs, fn)) != BMH_OK) return rc;
 		J.stats = true;
 	}
+	if (o.recal) {
+		if (!rt) { bmh_set_error("%s: null argument (the recalibration table needs its record)", fn); return BMH_EINVAL; }
+		if ((rc = brc_run_from_opt(J.RU, o.recal, n_contigs, contig_len, false, fn)) != BMH_OK) return rc;
+		J.recal = true;
+	}
 	return BMH_OK;
 }
 
 void bsr_results_release(bmh_sorted_results_t *res)
 {
 	if (res && res->stats) bmh_bam_stats_free(res->stats);
+	if (res && res->recal) brc_release(res->recal);
 	if (bmh_coverage_t *c = res ? res->coverage : nullptr) {
 		bmh_free(c->n_reads); bmh_free(c->cov_bases); bmh_free(c->sum_depth); bmh_free(c->max_depth); bmh_free(c->sum_mapq); bmh_free(c->hist); bmh_free(c->bin_sum);
 		memset(c, 0, sizeof *c);
@@ -114,9 +122,11 @@ int bsr_out_export(const bsr_out_t &J, bmh_sorted_results_t *res, const char *fn
 	res->parts = J.parts(); res->n_libraries = J.markdup ? (int32_t)J.P.n_lib() : 0;
 	res->markdup_ms[0] = J.dup_ms[0]; res->markdup_ms[1] = J.dup_ms[1]; res->markdup_d2h_bytes = (uint64_t)J.dup_ms[2]; res->optical_ms = J.opt_ms;
 	res->coverage_ms = J.cov_ms[0]; res->coverage_windows = (uint64_t)J.cov_ms[1]; res->stats_ms = J.stats_ms[0]; res->stats_windows = (uint64_t)J.stats_ms[1];
+	res->recal_ms = J.recal_ms[0]; res->recal_windows = (uint64_t)J.recal_ms[1];
 	int rc = BMH_OK;
 	if (J.coverage && res->coverage) rc = bcv_export(J.CP, J.CR, res->coverage, fn);
 	if (rc == BMH_OK && J.stats && res->stats) rc = bst_export(J.SP, J.SR, res->stats, fn);
+	if (rc == BMH_OK && J.recal && res->recal) rc = brc_export(J.RU, J.RR, res->recal, fn);
 	if (rc != BMH_OK) bsr_results_release(res);
 	return rc;
 }
@@ -364,9 +374,13 @@ extern "C" int bmh_bam_sort_host(const uint8_t *recs, uint64_t n_bytes, uint8_t 
 
 int bsr_write_host(const uint8_t *recs, const uint64_t *off, const uint32_t *ord, uint64_t n, bsr_out_t &J, bsr_sink_t sink, void *user, const char *fn)
 {
-	bcv_host_t H; bst_host_t SH;
+	bcv_host_t H; bst_host_t SH; brc_host_t RH;
 	if (J.coverage) H.begin(J.CP);
 	if (J.stats) SH.begin(J.SP);
+	if (J.recal) {
+		if (!J.RU.pac && J.RU.l_pac) { bmh_set_error("%s: the recalibration table needs the reference (pac, l_pac)", fn); return BMH_EINVAL; }
+		RH.begin(J.RU);
+	}
 	const uint64_t W = J.window ? J.window : std::max<uint64_t>(1, (64ull << 20) / std::max<uint64_t>(1, n ? off[n] / n : 1));
 	std::vector<uint8_t> buf; std::vector<uint64_t> soff, moff;
 	int rc;
@@ -384,9 +398,11 @@ int bsr_write_host(const uint8_t *recs, const uint64_t *off, const uint32_t *ord
 		J.ix.window_host(buf.data(), soff.data(), (uint32_t)(b - a), moff.data());
 		if (J.coverage && (rc = H.window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;      // the window in its final order, with its final flags
 		if (J.stats && (rc = SH.window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;
+		if (J.recal && (rc = RH.window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;
 	}
 	if (J.coverage) { if ((rc = H.finish(fn)) != BMH_OK) return rc; J.CR = std::move(H.R); }
 	if (J.stats) { SH.finish(); J.SR = std::move(SH.R); }
+	if (J.recal) { RH.finish(); J.RR = std::move(RH.R); }
 	return BMH_OK;
 }
 

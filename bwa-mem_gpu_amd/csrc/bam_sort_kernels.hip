@@ -257,7 +257,7 @@ int bsr_index_finish(bsr_dev_t *d, bsr_index_t &ix, void *stream)
 
 int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64_t src_bytes, const uint64_t *src_off, const uint32_t *size, uint32_t n, int level,
                       void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, bdp_dev_t *dup, const uint32_t *tord, double *flag_ms, bcv_dev_t *cov, double *cov_ms,
-                      bst_dev_t *stats, double *stats_ms)
+                      bst_dev_t *stats, double *stats_ms, brc_dev_t *recal, double *recal_ms)
 {
 	hipStream_t st = (hipStream_t)stream;
 	if (n == 0) return BMH_OK;
@@ -280,6 +280,8 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 	if (cov) RCK(bcv_window_device(cov, (const uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, n, src + src_off[n - 1], st, "sorted BAM", cov_ms));
 	// the statistics read the same records: one kernel, nothing waits for it here
 	if (stats) RCK(bst_window_device(stats, (const uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, n, st, stats_ms));
+	// the recalibration table reads them too, and the reference: one kernel, nothing waits for it here
+	if (recal) RCK(brc_window_device(recal, (const uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, n, st, recal_ms));
 	const uint8_t *d_members = nullptr; uint64_t mb = 0;
 	RCK(bmh_bgzf_deflate_device(ws, (const uint8_t *)d->sorted.p, total, level, st, &d_members, &mb));
 	// the index pass: the members' offsets are the compressor's scan (ws->moff [n_members + 1])
@@ -302,6 +304,7 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 	if (dup && flag_ms) { float ms = 0; HIPCK(hipEventElapsedTime(&ms, d->ev_flag[0], d->ev_flag[1])); *flag_ms += ms; }
 	if (cov && cov_ms) RCK(bcv_window_ms(cov, cov_ms));
 	if (stats) RCK(bst_window_ms(stats, stats_ms, "sorted BAM"));        // (a refused record ends the run before the window's members reach the sink)
+	if (recal) RCK(brc_window_ms(recal, recal_ms, "sorted BAM"));
 	if (nh == 0 || nh > n) { bmh_set_error("sorted BAM: internal error: %u chunk heads among %u records", nh, n); return BMH_EINVAL; }
 	const size_t h0 = ix.heads.size();
 	ix.heads.resize(h0 + nh);
@@ -312,11 +315,11 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 }
 
 // every run of the store -> the sorted file's record members (to the sink) and its index
-int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_out_t &J, void *stream, bsr_sink_t sink, void *user, bcv_dev_t *cov, bst_dev_t *stats)
+int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_out_t &J, void *stream, bsr_sink_t sink, void *user, bcv_dev_t *cov, bst_dev_t *stats, brc_dev_t *recal)
 {
 	const bdp_plan_t &P = J.P; bsr_index_t &ix = J.ix; const int level = J.level; const uint32_t window = J.window;
 	uint64_t *const dup_counts = J.markdup ? J.dup_counts : nullptr;
-	double *const cov_ms = J.timed && cov ? J.cov_ms : nullptr, *const stats_ms = J.timed && stats ? J.stats_ms : nullptr;
+	double *const cov_ms = J.timed && cov ? J.cov_ms : nullptr, *const stats_ms = J.timed && stats ? J.stats_ms : nullptr, *const recal_ms = J.timed && recal ? J.recal_ms : nullptr;
 	const bdp_optical_t *optical = P.optical(); const bool barcode = P.barcode() != nullptr;
 	uint64_t n = 0, bytes = 0;
 	std::vector<uint64_t> first;
@@ -367,7 +370,7 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_o
 				if (dup.p) tord[j] = (uint32_t)(R.tbase + R.tpl[i]);
 			}
 			// (the pinned buffer takes the members once the records are on the device: the compressor waits for the stream in between)
-			RCK(bsr_window_device(d, ws, d->h_buf, sb, src_off.data(), size.data(), m, level, stream, ix, sink, user, dup.p, dup.p ? tord.data() : nullptr, dup.p ? &flag_ms : nullptr, cov, cov_ms, stats, stats_ms));
+			RCK(bsr_window_device(d, ws, d->h_buf, sb, src_off.data(), size.data(), m, level, stream, ix, sink, user, dup.p, dup.p ? tord.data() : nullptr, dup.p ? &flag_ms : nullptr, cov, cov_ms, stats, stats_ms, recal, recal_ms));
 		}
 	}
 	if (dup_counts) {
@@ -396,7 +399,14 @@ int bsr_write_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_o
 		if (!(stats.p = bst_dev_create())) return BMH_ENOMEM;
 		RCK(bst_begin_device(stats.p, J.SP, stream));
 	}
-	RCK(bsr_merge_device(d, ws, S, J, stream, sink, user, cov.p, stats.p));
+	struct recal_own_t { brc_dev_t *p = nullptr; ~recal_own_t() { if (p) brc_dev_free(p); } } recal;
+	if (J.recal) {
+		if (!J.recal_d_pac && !J.RU.pac && J.RU.l_pac) { bmh_set_error("%s: the recalibration table needs the reference (pac, l_pac)", fn); return BMH_EINVAL; }
+		if (!(recal.p = brc_dev_create())) return BMH_ENOMEM;
+		RCK(brc_begin_device(recal.p, J.RU, J.recal_d_pac, stream));
+	}
+	RCK(bsr_merge_device(d, ws, S, J, stream, sink, user, cov.p, stats.p, recal.p));
+	if (recal.p) RCK(brc_finish_device(recal.p, stream, J.RR, fn));
 	if (stats.p) RCK(bst_finish_device(stats.p, stream, J.SR, fn));
 	if (cov.p) RCK(bcv_finish_device(cov.p, stream, J.CR, fn, J.timed ? J.cov_ms : nullptr));
 	if (J.markdup && J.P.groups() && J.P.lib_counts)                   // every library's line counts and templates, as the batches counted them

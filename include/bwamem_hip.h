@@ -916,7 +916,8 @@ int bmh_aligner_set_output(bmh_aligner_t *a, int format, int level);
  * BMH_OUT_BAM_SORTED runs -- and everything it can do there: sort, index, mark duplicates, compute coverage, compute statistics.
  * bmh_sorted_opt_t: the BGZF level (0 or 1); window: records per window of the merge (0: about 64 MiB of records; a window's last member is short); the index
  * (BMH_INDEX_*; min_shift is read for CSI only); sort_mem: record bytes the run store keeps in memory before runs spill to an unnamed file in tmp_dir (0: 4 GiB;
- * NULL: $TMPDIR, else /tmp); markdup, coverage, stats: the options of duplicate marking, coverage and statistics (the sections below), NULL: off.
+ * NULL: $TMPDIR, else /tmp); markdup, coverage, stats, recal: the options of duplicate marking, coverage, statistics and the recalibration table (the sections
+ * below), NULL: off.  recal and the results' recal, recal_ms, recal_windows are the records' last members: code that fills the members before them is unchanged.
  * bmh_sorted_opt_default: level 1, window 0, a BAI index (min_shift 14), the store's defaults, everything off; an opt of NULL means the same.
  * bmh_sorted_results_t: markdup, coverage, stats -- the caller's records, each required exactly when the matching option is set (else BMH_EINVAL) and not read
  * otherwise; the arrays of *coverage and *stats are malloc'd (bmh_free each / bmh_bam_stats_free).  The device milliseconds and the windows timed are filled by
@@ -924,7 +925,7 @@ int bmh_aligner_set_output(bmh_aligner_t *a, int format, int level);
  * Every call zeroes the results and the records they name first, and a failed call leaves *bam, *index (bmh_bam_post_file_*: out's pointers) and every array of
  * *coverage and *stats NULL, whatever they held before: a caller who frees what a failed call left frees nothing.
  * The options are checked in one order, before anything is written: level; the index format and the contigs it can hold; markdup (barcode source, edits, optical
- * step, read groups, then the contigs marking can hold); coverage; stats.
+ * step, read groups, then the contigs marking can hold); coverage; stats; recal (its record in the results is required, zeroed and released like theirs).
  * bmh_bam_sorted_file_device / _host: a record stream in host memory -> header members, the sorted records in windows, the end-of-file member; and the .bai or
  * .csi bytes (both malloc'd; bmh_free).  Both forms give the same bytes.  With opt->markdup the stream comes in the writer's order; the optical step is not part
  * of a stand-alone file: optical_distance stays -1, else BMH_EINVAL.  sort_mem and tmp_dir are not read here: the one run stays in memory.
@@ -950,10 +951,13 @@ typedef struct bmh_coverage_opt bmh_coverage_opt_t;
 typedef struct bmh_coverage bmh_coverage_t;
 typedef struct bmh_bam_stats_opt bmh_bam_stats_opt_t;
 typedef struct bmh_bam_stats bmh_bam_stats_t;
+typedef struct bmh_recal_opt bmh_recal_opt_t;
+typedef struct bmh_recal bmh_recal_t;
 typedef struct {
 	int32_t level; uint32_t window; int32_t index_format, min_shift;
 	uint64_t sort_mem; const char *tmp_dir;
 	const bmh_markdup_opt_t *markdup; const bmh_coverage_opt_t *coverage; const bmh_bam_stats_opt_t *stats;
+	const bmh_recal_opt_t *recal;
 } bmh_sorted_opt_t;
 #define BMH_SORTED_MARKDUP 1u
 #define BMH_SORTED_OPTICAL 2u
@@ -961,10 +965,12 @@ typedef struct {
 #define BMH_SORTED_GROUPED 8u
 #define BMH_SORTED_COVERAGE 16u
 #define BMH_SORTED_STATS 32u
+#define BMH_SORTED_RECAL 64u
 typedef struct {
 	bmh_markdup_counts_t *markdup; bmh_coverage_t *coverage; bmh_bam_stats_t *stats;
 	uint32_t parts; int32_t n_libraries;
 	double markdup_ms[2], optical_ms, coverage_ms, stats_ms; uint64_t markdup_d2h_bytes, coverage_windows, stats_windows;
+	bmh_recal_t *recal; double recal_ms; uint64_t recal_windows;
 } bmh_sorted_results_t;
 void bmh_sorted_opt_default(bmh_sorted_opt_t *o);
 int bmh_bam_sorted_file_device(const char *header_text, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint8_t *records, uint64_t n_bytes,
@@ -1234,6 +1240,45 @@ struct bmh_bam_stats {
 void bmh_bam_stats_free(bmh_bam_stats_t *s);
 int bmh_bam_stats_device(const uint8_t *records, uint64_t n_bytes, int n_contigs, const bmh_bam_stats_opt_t *opt, void *stream, bmh_bam_stats_t *out);
 int bmh_bam_stats_host(const uint8_t *records, uint64_t n_bytes, int n_contigs, const bmh_bam_stats_opt_t *opt, bmh_bam_stats_t *out);
+
+/* ---- The covariate table of base quality score recalibration, counted while sorted BAM is written (csrc/bam_recal_core.h, csrc/bam_recal_kernels.hip,
+ * csrc/bam_recal_host.cpp): what GATK BaseRecalibrator's counting pass would read the file again for, at its default covariates (read group,
+ * quality, cycle, context) with BAQ off.  DESIGN.md 4.16 holds the definition and the differences from GATK (no adaptor-boundary clipping, no low-quality-tail
+ * masking of contexts, no BAQ, cycles above the cap binned, the output is this project's text); nothing here has been compared with GATK itself.
+ * bmh_recal_opt_t: min_qual (0 .. 93; default 6), max_cycle (1 .. 65535; default 500); the reference -- pac: the .pac body on the host (forward strand, 4 bases a
+ * byte), l_pac its bases, contig_offset [n_contigs] every contig's first base in it (NULL: the contigs back to back); an aligner run reads the index's own copy on
+ * the device when pac is NULL.  mask [mask_words] (or NULL): bit i & 63 of word i >> 6 masks base i (bmh_known_sites_mask, bmh_recal_mask_holes); mask_words is
+ * (l_pac + 63) / 64.  rg_ids [n_groups]: the read groups in table order (at most 255); 0 groups: every record belongs to the one group `*` and RG tags are not read.
+ * bmh_recal_t: summary [16] -- records seen, counted, left out (no contig, flags, mapq, no qualities, no operations), bases kept, bases skipped (no ACGT, quality
+ * below min_qual, masked position, masked insertion anchor), cycles capped, masked positions; cycle_m [groups][94][2 max_cycle][2] (observations, errors of event M;
+ * slot max_cycle + c - 1 for cycle c > 0, max_cycle + c for c < 0), cycle_id [groups][2 max_cycle][3] (observations of I and of D -- one word --, insertion errors,
+ * deletion errors, at quality 45), context_m [groups][94][17][2] (context 4 a + b; 16: none), context_id [groups][65][3] (16 a + 4 b + c; 64: none).
+ * The accumulator holds at most 2^28 words (groups x max_cycle is bounded by that), else BMH_EINVAL.
+ * Refused with BMH_EINVAL by the record's index, the smallest first: see DESIGN.md 4.16.  bmh_recal_free releases the arrays (a failed call leaves them NULL).
+ * bmh_bam_recal_device / _host: a record stream in any order.  bmh_sorted_opt_t's recal: the table of a sorted output from the windows of its merge, every
+ * window behind its flag step.  Without it no run launches anything more.
+ * bmh_known_sites_mask: text files, plain or gzip, VCF (first non-empty line begins ##fileformat=VCF or #CHROM: a data line masks [POS - 1, POS - 1 + len(REF)))
+ * or BED ([start, end); track, browser and # lines ignored) -> bits OR-ed into mask; refused naming file and line: an unknown contig, a position outside its
+ * contig, too few fields, a number that does not parse.  bmh_recal_mask_holes: the reference's holes (.amb: offset, length pairs in pac) OR-ed into the mask. */
+struct bmh_recal_opt {
+	int32_t min_qual, max_cycle;
+	const uint8_t *pac; uint64_t l_pac; const uint64_t *contig_offset;
+	const uint64_t *mask; uint64_t mask_words;
+	int32_t n_groups; const char *const *rg_ids;
+};
+void bmh_recal_opt_default(bmh_recal_opt_t *o);
+struct bmh_recal {
+	int32_t n_groups, min_qual, max_cycle, n_qual;
+	uint64_t summary[16];
+	uint64_t *cycle_m, *cycle_id, *context_m, *context_id;
+};
+void bmh_recal_free(bmh_recal_t *r);
+void bmh_recal_kernel_limits(uint32_t out[5]);   /* the device form's capacities: slots, lanes per record, cycles per LDS row, records per block, bases per LDS record */
+int bmh_bam_recal_device(const uint8_t *records, uint64_t n_bytes, int n_contigs, const int32_t *contig_len, const bmh_recal_opt_t *opt, void *stream, bmh_recal_t *out);
+int bmh_bam_recal_host(const uint8_t *records, uint64_t n_bytes, int n_contigs, const int32_t *contig_len, const bmh_recal_opt_t *opt, bmh_recal_t *out);
+int bmh_known_sites_mask(const char *const *paths, int n_paths, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint64_t *contig_offset,
+                         uint64_t *mask, uint64_t mask_words);
+int bmh_recal_mask_holes(const uint64_t *hole_offset, const uint64_t *hole_len, int n_holes, uint64_t *mask, uint64_t mask_words);
 
 #ifdef __cplusplus
 }

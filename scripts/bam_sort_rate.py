@@ -8,7 +8,11 @@ sorted file's size (the two copies land next to each other) and the merge's comp
     python scripts/bam_sort_rate.py [--runs 3] [--reads 1000000] [--genome-mbp 3100] [--out FILE] [--markdup [--groups | --optical N] [--parent-json FILE]]
                                     [--coverage [--coverage-bin N] [--sort-window W] [--parent-json FILE]]
                                     [--stats [--sort-window W] [--parent-json FILE]]
+                                    [--recal [--off-only] [--sort-window W] [--parent-json FILE]]
 
+--recal: the recalibration-table leg (profiles/bam_recal.json), at the statistics leg's size: the paired rows sorted and sorted + marked from FASTA, and from FASTQ
+under two quality alphabets (about 40 distinct values; 4 binned ones) the row sorted + marked and the row with the table counted beside it -- with the counting
+kernels alone as the library times them (events around every window's kernel) and their share of the final merge.  --off-only: the rows without the option alone.
 --stats: the statistics leg (profiles/bam_stats.json), at the coverage leg's size: the sorted in-memory row, the same row with duplicates marked, the row `sorted +
 marked + statistics` (reads_to_sorted_bam_in_memory_markdup_stats) -- with the statistics kernels alone as the library times them (bmh_aligner_stats_ms: events
 around every window's kernel), per run and per window, and their share of the final merge -- and, on the paired set, that row with coverage beside it.
@@ -73,11 +77,15 @@ def main():
     ap.add_argument("--coverage-bin", type=int, default=1000)
     ap.add_argument("--sort-window", type=int, default=0)
     ap.add_argument("--stats", action="store_true")
+    ap.add_argument("--recal", action="store_true", help="the recalibration-table leg (profiles/bam_recal.json)")
+    ap.add_argument("--off-only", action="store_true", help="with --recal: the rows without the option alone (a parent library under BMH_LIB: the file --parent-json takes)")
     a = ap.parse_args()
     if a.optical is not None and (not a.markdup or a.groups or not 0 <= a.optical <= 0x7fffffff):
         ap.error("--optical N (0 .. 2^31 - 1) goes with --markdup, without --groups")
     if a.coverage and (a.markdup or a.coverage_bin < 1 or a.sort_window < 0):
         ap.error("--coverage goes without --markdup; --coverage-bin N >= 1, --sort-window W >= 0")
+    if a.recal and (a.markdup or a.coverage or a.stats or a.sort_window < 0):
+        ap.error("--recal goes without --markdup, --coverage and --stats; --sort-window W >= 0")
     if a.stats and (a.markdup or a.coverage or a.sort_window < 0):
         ap.error("--stats goes without --markdup and --coverage; --sort-window W >= 0")
     dev = torch.device("cuda:0")
@@ -119,7 +127,7 @@ def main():
     path = os.path.join(tmp, "se.fa")
     write_fasta(path, names, asc)
     ppath = os.path.join(tmp, "pe.fa")
-    if a.markdup or a.coverage or a.stats:                    # FR pairs, n reads per distinct batch, each batch twice; mates share a name
+    if a.markdup or a.coverage or a.stats or a.recal:         # FR pairs, n reads per distinct batch, each batch twice; mates share a name
         p1 = B.synth.make_pairs(g, n // 2, rl, seed=7, holes=holes)[0]; p2 = B.synth.make_pairs(g, n // 2, rl, seed=1007, holes=holes)[0]
         pasc = B.synth.codes_to_ascii(np.concatenate([p1.reshape(-1), p2.reshape(-1), p1.reshape(-1), p2.reshape(-1)]))
         pn = np.frombuffer("".join(np.char.add(">p", np.char.zfill((np.arange(n4) // 2).astype(str), w)).tolist()).encode(), np.uint8).reshape(n4, w + 2)
@@ -127,13 +135,14 @@ def main():
     nat = NativeAligner(dindex, pac_h, n_genome, contigs, None, co, ExtParams.default(), po, pe_o)
     result = {"genome_mbp": a.genome_mbp, "reads_per_run": n4, "setup_s": round(time.time() - t0, 1), "runs": a.runs, "host_threads": nth, "rows": {}}
 
-    def run(fmt, spill=False, keep=None, markdup=False, paired=False, groups=None, files=False, optical=None, coverage=None, qc=None):
-        src = ppath if paired else path
+    def run(fmt, spill=False, keep=None, markdup=False, paired=False, groups=None, files=False, optical=None, coverage=None, qc=None, recal=None, src=None):
+        src = src or (ppath if paired else path)
         if fmt == "bam_sorted":
-            nat.set_sorted(level=1, sort_mem=1 if spill else 64 << 30, sort_tmp=tmp, window=a.sort_window, markdup=markdup, optical_distance=optical, coverage=coverage, stats=qc)
+            nat.set_sorted(level=1, sort_mem=1 if spill else 64 << 30, sort_tmp=tmp, window=a.sort_window, markdup=markdup, optical_distance=optical, coverage=coverage, stats=qc,
+                           **({} if recal is None else dict(recal=recal)))
         else:
             nat.set_output(fmt, 1)
-        opt_ms, cov_ms, st_ms = [], [], []
+        opt_ms, cov_ms, st_ms, rc_ms = [], [], [], []
         nbytes = [0]
 
         def sink(mv):
@@ -162,6 +171,8 @@ def main():
                     cov_ms.append(got["coverage_ms"])
                 if qc is not None:
                     st_ms.append(got["stats_ms"])
+                if recal is not None:
+                    rc_ms.append(got["recal_ms"])
         row = stats(secs, n4, 1e6)
         row["unit"] = "Mreads/s"; row["bytes_out_per_read"] = round(nbytes[0] / n4, 1)
         if fmt == "bam_sorted":
@@ -187,6 +198,15 @@ def main():
                 qs = got["stats"]
                 row["stats"] = {"insert_cap": int(qc.get("insert_cap", 65536)), "total": int(qs["flag"][:, 0].sum()), "duplicates": int(qs["flag"][:, 4].sum()), "mapped": int(qs["flag"][:, 6].sum()),
                                 "pairs_counted": [int(v) for v in qs["insert_hist"].sum(axis=1)], "largest_insert_bin": int(qs["insert_hist"].max()), "edit_distance": int(qs["summary"][13])}
+            if recal is not None:
+                ms = [t for t, _w in rc_ms]
+                row["recal_steps_alone"] = {"unit": "ms on the stream per run (events around every window's counting kernel)",
+                                            "median": round(sorted(ms)[len(ms) // 2], 3), "runs": [round(t, 3) for t in ms], "windows": [w for _t, w in rc_ms],
+                                            "ms_per_window": [round(t / max(w, 1), 3) for t, w in rc_ms],
+                                            "share_of_final_merge_pct": round(100 * sorted(ms)[len(ms) // 2] / (1e3 * sorted(merge)[len(merge) // 2]), 2)}
+                rs = got["recal"]
+                row["recal"] = {"records_counted": int(rs["summary"][1]), "bases_kept": int(rs["summary"][7]), "observations": int(rs["cycle_m"][..., 0].sum()), "mismatches": int(rs["cycle_m"][..., 1].sum()),
+                                "qualities_seen": int(np.count_nonzero(rs["cycle_m"][0, :, :, 0].sum(axis=1))), "masked_positions": int(rs["summary"][13])}
             if markdup:
                 row["counts"] = got["markdup_counts"]
                 tpl = row["counts"]["templates"]
@@ -203,6 +223,46 @@ def main():
                     row["library_counts"] = got["markdup_library_counts"]
         return row
     keep = []
+    if a.recal:
+        # the size of the statistics leg; the reads as FASTQ under two quality alphabets -- about 40 distinct values and 4 binned ones: the kernel's dictionary of
+        # (group, quality) slots in LDS fills differently under each
+        result["sort_window"] = a.sort_window
+        def write_fastq(dst, nm, bases, quals):
+            k = nm.shape[1]
+            recs = np.empty((n4, k + 1 + rl + 3 + rl + 1), np.uint8)
+            recs[:, :k] = nm; recs[:, 0] = ord("@"); recs[:, k] = 10; recs[:, k + 1:k + 1 + rl] = bases.reshape(n4, rl); recs[:, k + 1 + rl] = 10; recs[:, k + 2 + rl] = ord("+"); recs[:, k + 3 + rl] = 10
+            recs[:, k + 4 + rl:k + 4 + 2 * rl] = quals + 33; recs[:, -1] = 10
+            recs.tofile(dst)
+        result["rows"]["paired_reads_to_sorted_bam_in_memory"] = run("bam_sorted", paired=True)
+        result["rows"]["paired_reads_to_sorted_bam_in_memory_markdup"] = run("bam_sorted", markdup=True, paired=True)
+        rng = np.random.default_rng(3)
+        for label, alphabet in (("q40", np.arange(2, 42)), ("q4", np.array([2, 12, 23, 37]))):
+            fq = os.path.join(tmp, label + ".fq")
+            write_fastq(fq, pn, pasc, alphabet[rng.integers(0, len(alphabet), (n4, rl))].astype(np.uint8))
+            result["rows"]["paired_fastq_%s_to_sorted_bam_in_memory_markdup" % label] = run("bam_sorted", markdup=True, paired=True, files=True, src=fq)
+            if not a.off_only:
+                from bwamem_hip.lib import known_sites_mask
+                mask = known_sites_mask([], contigs, l_pac=n_genome, holes=[(int(h[0]), int(h[1]) - int(h[0])) for h in holes])
+                result["rows"]["paired_fastq_%s_to_sorted_bam_in_memory_markdup_recal" % label] = run("bam_sorted", markdup=True, paired=True, files=True, src=fq, recal=dict(mask=mask))
+            os.remove(fq)
+        nat.set_output("sam", 1)
+        if a.parent_json:
+            with open(a.parent_json) as f:
+                parent = json.load(f)
+            result["parent_rows"] = {k: v for k, v in parent["rows"].items() if k in result["rows"]}
+            result["option_off_vs_parent"] = {}
+            for k, pr in result["parent_rows"].items():
+                tr = result["rows"][k]
+                diff = 100 * abs(tr["median"] - pr["median"]) / pr["median"]
+                result["option_off_vs_parent"][k] = {"difference_pct": round(diff, 1), "larger_spread_pct": max(tr["spread_pct"], pr["spread_pct"]), "within_spread": diff <= max(tr["spread_pct"], pr["spread_pct"])}
+        result["not_measured"] = ("real data with deep duplicate stacks (every read occurs twice here), a mask of dbSNP's density (the holes alone here), the time to parse a large VCF, spilled runs, "
+                                  "long reads whose cycles exceed the cap, the step beside the window's deflate kernel (no kernel trace was taken)")
+        os.remove(ppath); os.remove(path); os.rmdir(tmp)
+        out = a.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bam_recal.json")
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+        print(json.dumps(result))
+        return
     if a.stats:
         result["sort_window"] = a.sort_window
         for pre, pk in (("", {}), ("paired_", dict(paired=True))):
