@@ -11,8 +11,8 @@ from . import fmindex, synth  # noqa: F401
 from .index import fasta_pack, index_fasta  # noqa: F401
 from .lib import (ExtParams, HipLibraryMissing, Index, SeedWorkspace, extend_batch, lib_path,  # noqa: F401
                   bam_stats, load_library, seed_file)
-from .lib import bam_recal, known_sites_mask  # noqa: F401
-from .recal import read_recal_table, recal_empirical_quality, recal_table_text  # noqa: F401
+from .lib import bam_apply_recal, bam_recal, known_sites_mask, recal_apply_tables  # noqa: F401
+from .recal import read_recal_table, recal_apply_report_text, recal_empirical_quality, recal_table_text  # noqa: F401
 
 
 def insert_size_metrics(hist, smallest, largest) -> dict:

@@ -465,22 +465,39 @@ def _stats_keywords(f):
     return call
 
 
-RECAL_KEYWORDS = ("recal", "known_sites", "recal_min_qual", "recal_max_cycle")
+RECAL_KEYWORDS = ("recal", "known_sites", "recal_min_qual", "recal_max_cycle", "apply_recal", "apply_recal_report")
 
 
-def recal_request(what: str, sort: bool, recal=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None, need: str = "sort=True"):
-    """the recalibration keywords of align_file / align_files / align_groups / bam_post_file, checked -> None (none given) or a dict of them; ValueError otherwise"""
+def recal_request(what: str, sort: bool, recal=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None, apply_recal=None, apply_recal_report=None, need: str = "sort=True", sorted_out: bool = True):
+    """the recalibration keywords of align_file / align_files / align_groups / bam_post_file, checked -> None (none given) or a dict of them; ValueError otherwise.
+    apply_recal (a path or read_recal_table's dict): the table applied to the qualities as they are written -- read here, so that a file that is
+    no table is refused before anything is written; "table" is None where no table is counted.  sort: what `need` asks for, which counting needs; sorted_out: a
+    sorted file is written, which applying needs"""
     sites = [known_sites] if isinstance(known_sites, (str, bytes, os.PathLike)) else list(known_sites or [])
+    if apply_recal is None and apply_recal_report is not None:
+        raise ValueError(f"{what}: apply_recal_report needs apply_recal (it says what the applied table changed)")
     if recal is None:
         if sites or recal_min_qual is not None or recal_max_cycle is not None:
             raise ValueError(f"{what}: known_sites, recal_min_qual and recal_max_cycle need recal (they say what is counted, not where it goes)")
-        return None
-    if not sort:
+        if apply_recal is None:
+            return None
+    elif not sort:
         raise ValueError(f"{what}: the recalibration options need {need}: the table is counted where the sorted file is written")
+    table = None
+    if apply_recal is not None:
+        if not sorted_out:
+            raise ValueError(f"{what}: apply_recal needs sort=True: the qualities are rewritten where the sorted file is written")
+        if isinstance(recal, (str, os.PathLike)) and isinstance(apply_recal, (str, os.PathLike)) and os.path.abspath(os.fspath(recal)) == os.path.abspath(os.fspath(apply_recal)):
+            raise ValueError(f"{what}: recal and apply_recal name the same file: counting and applying one table in one run would take two passes over the windows")
+        from .recal import read_recal_table
+        table = read_recal_table(os.fspath(apply_recal)) if isinstance(apply_recal, (str, os.PathLike)) else apply_recal
+        if not isinstance(table, dict) or "cycle_m" not in table or "context_m" not in table:
+            raise ValueError(f"{what}: apply_recal takes a path or read_recal_table's dict")
     for nm, v, lo, hi in (("recal_min_qual", recal_min_qual, 0, 93), ("recal_max_cycle", recal_max_cycle, 1, 65535)):
         if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not lo <= v <= hi):
             raise ValueError(f"{what}: {nm} {v!r}: an integer in {lo} .. {hi}")
-    return dict(table=recal, known_sites=[os.fspath(p) for p in sites], min_qual=6 if recal_min_qual is None else int(recal_min_qual), max_cycle=500 if recal_max_cycle is None else int(recal_max_cycle))
+    return dict(table=recal, known_sites=[os.fspath(p) for p in sites], min_qual=6 if recal_min_qual is None else int(recal_min_qual), max_cycle=500 if recal_max_cycle is None else int(recal_max_cycle),
+                apply=table, apply_report=apply_recal_report)
 
 
 def _recal_keywords(f):
@@ -493,10 +510,10 @@ def _recal_keywords(f):
             return f(self, *args, **kw)
         given = sig.bind(self, *args, **kw)
         given.apply_defaults()
-        req = recal_request(f.__name__, given.arguments["sort"], *(given.arguments[k] for k in RECAL_KEYWORDS))
+        req = recal_request(f.__name__, given.arguments["sort"], *(given.arguments[k] for k in RECAL_KEYWORDS), sorted_out=given.arguments["sort"])
         if req is None:
             return f(self, *args, **kw)
-        if given.arguments.get("keep_rg"):                        # the table's read groups are the input's: its header is read here, ahead of the run
+        if given.arguments.get("keep_rg") and req["table"] is not None:                        # the table's read groups are the input's: its header is read here, ahead of the run
             from .bam import peek_header
             src = given.arguments["reads"]
             if not isinstance(src, (str, os.PathLike)) or not os.path.isfile(src):
@@ -982,7 +999,7 @@ class Aligner:
                    sort: bool = False, index=None, sort_mem=None, sort_tmp=None, sort_window=None, markdup: bool = False, markdup_metrics=None,
                    index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
                    coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False,
-                    flagstat=None, idxstats=None, stats=None, insert_cap=None, recal=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None) -> int:
+                    flagstat=None, idxstats=None, stats=None, insert_cap=None, recal=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None, apply_recal=None, apply_recal_report=None) -> int:
         if fmt != "sam" or sort or index is not None or markdup or markdup_metrics is not None or index_format != "bai" or csi_min_shift != 14 or optical_distance is not None or barcode_tag is not None or barcode_name or barcode_edits is not None:
             return self._align_bam(lambda o: self.align_file(reads_fa, o, batch_reads=batch_reads, paired=paired, chunk_bases=chunk_bases), out, fmt, level,
                                    sort, index, sort_mem, sort_tmp, sort_window, markdup, markdup_metrics, index_format, csi_min_shift, optical_distance, barcode_tag, barcode_name, barcode_edits)
@@ -1130,10 +1147,12 @@ class Aligner:
         stats_req = getattr(self, "_stats_req", None) if sort else None
         recal_req = getattr(self, "_recal_req", None) if sort else None
         recal_kw = None
-        if recal_req is not None:                                 # (the mask: the known sites and the reference's holes, made once per run; the reference is the index's)
+        if recal_req is not None and recal_req["table"] is not None:      # (the mask: the known sites and the reference's holes, made once per run; the reference is the index's)
             from .lib import known_sites_mask
             mask = known_sites_mask(recal_req["known_sites"], self.contigs, l_pac=self.l_pac, holes=read_amb(self.prefix) if getattr(self, "prefix", None) else None)
             recal_kw = dict(mask=mask, min_qual=recal_req["min_qual"], max_cycle=recal_req["max_cycle"], known_sites=recal_req["known_sites"])
+        if recal_req is not None and recal_req["apply"] is not None:      # the table applied to the qualities as they are written; alone, no table is counted
+            recal_kw = dict(recal_kw, apply=recal_req["apply"]) if recal_kw is not None else dict(apply=recal_req["apply"], count=False)
         sorted_keywords = dict(markdup=bool(markdup), optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name, barcode_edits=barcode_edits,
                                index_format=index_format, csi_min_shift=int(csi_min_shift), window=int(sort_window or 0), sort_mem=sort_mem or None, sort_tmp=sort_tmp,
                                coverage=dict(min_mapq=cov_req["min_mapq"], deletions=cov_req["deletions"], bin=cov_req["bin"]) if cov_req is not None else None,
@@ -1148,7 +1167,10 @@ class Aligner:
             if stats_req is not None:
                 from .lib import bam_stats
                 self.stats = got["stats"] if n else bam_stats(b"", len(self.contigs), stats_req["insert_cap"], host=True)
-            if recal_req is not None:
+            if recal_req is not None and recal_req["apply"] is not None:
+                from .lib import bam_apply_recal
+                self.recal_apply = got["recal"]["apply"] if n else bam_apply_recal(b"", recal_req["apply"], host=True)[1]
+            if recal_req is not None and recal_req["table"] is not None:
                 from .lib import bam_recal
                 self.recal = got["recal"] if n else dict(bam_recal(b"", self.contigs, self.pac, self.l_pac, mask=recal_kw["mask"], min_qual=recal_req["min_qual"], max_cycle=recal_req["max_cycle"],
                                                                  host=True), known_sites=recal_req["known_sites"])
@@ -1197,9 +1219,12 @@ class Aligner:
                 _write_text(cov_req["bed"], coverage_bed_text(self.coverage, self.contigs, cov_req["bin"]))
         if stats_req is not None:
             write_stats_texts(stats_req, self.stats, self.contigs)
-        if recal_req is not None:
+        if recal_req is not None and recal_req["table"] is not None:
             from .recal import write_recal_table
             write_recal_table(self.recal, recal_req["table"])
+        if recal_req is not None and recal_req["apply_report"] is not None:
+            from .recal import write_recal_apply_report
+            write_recal_apply_report(self.recal_apply, recal_req["apply_report"])
         if markdup_metrics is not None:
             text = markdup_metrics_text_libraries(self.markdup_library_counts) if getattr(self, "_groups", None) else markdup_metrics_text(self.markdup_counts, getattr(self, "rg_line", ""))
             if hasattr(markdup_metrics, "write"):
@@ -1217,8 +1242,12 @@ class Aligner:
                     index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
                     collate: bool = False, collate_mem=None,
                     coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False,
-                    flagstat=None, idxstats=None, stats=None, insert_cap=None, recal=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None) -> int:
-        """recal= (a path or a text file object; needs sort=True): the covariate table of base quality score recalibration of the file being written (DESIGN.md
+                    flagstat=None, idxstats=None, stats=None, insert_cap=None, recal=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None, apply_recal=None, apply_recal_report=None) -> int:
+        """apply_recal= (a path to a table recal= wrote, or read_recal_table's dict; needs sort=True): the base qualities of every record are recalibrated by that
+        table as the sorted file is written, on the device in every window of the final merge behind its flag step; coverage, the statistics and
+        recal= then see the qualities as written (recal= gives the "after" table; it may not name the same file), while markdup's choice rests on the original
+        qualities.  apply_recal_report= (a path or a text file object): recal_apply_report_text's rows.  self.recal_apply holds the counts afterwards.
+        recal= (a path or a text file object; needs sort=True): the covariate table of base quality score recalibration of the file being written (DESIGN.md
         4.16; recal_table_text's rows), counted on the device from every window of the final merge behind its flag step against the index's own reference, under
         known_sites= (VCF or BED files, plain or gzip; the reference's holes are always masked), recal_min_qual= (6) and recal_max_cycle= (500).  The read groups
         are the run's (-R, align_groups'; with keep_rg=True the @RG lines of the input's header, which is read ahead of the run: a file, not a pipe).  self.recal holds the arrays afterwards (bam_recal's dict).
@@ -1327,7 +1356,7 @@ class Aligner:
                      index_format: str = "bai", csi_min_shift: int = 14, optical_distance=None, barcode_tag=None, barcode_name=None, barcode_edits=None,
                      collate: bool = False, collate_mem=None,
                      coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False,
-                    flagstat=None, idxstats=None, stats=None, insert_cap=None, recal=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None) -> int:
+                    flagstat=None, idxstats=None, stats=None, insert_cap=None, recal=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None, apply_recal=None, apply_recal_report=None) -> int:
         """several read groups -- a sample's lanes and libraries -- into one output (bmh_aligner_run_groups).  groups: [(rg_line, reads, mates or None), ...]; every
         rg_line is unescaped and checked as -R's value is, reads / mates are what align_files takes (one file or R1 + R2; plain, gzip or BGZF; FASTA or FASTQ; or
         one BAM, whose own @RG lines and RG tags stay ignored: align_files(keep_rg=True) is the run that keeps them, and the two do not combine).  Group g's records are byte for byte those of align_files(reads_g, mates_g) alone under -R rg_g, and

@@ -9,6 +9,7 @@ its @HD line replaced by `@HD VN:1.6 SO:coordinate`; no @PG line is added.  Reco
 
 The options are those of bwamem_hip.mem, with the same meaning and the same refusals: --markdup, --markdup-metrics PATH, --optical-distance N, --barcode-tag XX,
 --barcode-name, --barcode-edits N; --coverage PATH, --coverage-hist PATH, --coverage-bed PATH, --coverage-bin N, --coverage-min-mapq Q, --coverage-deletions; --flagstat PATH, --idxstats PATH, --stats PATH; --recal PATH with --reference PREFIX, --known-sites FILE (repeatable), --recal-min-qual Q, --recal-max-cycle N;
+--apply-recal TABLE, --apply-recal-report PATH (they need no --reference, and --host works);
 --csi, --csi-min-shift N, --index PATH, --bam-level 0|1, --sort-mem BYTES, --sort-tmp DIR, --sort-window RECORDS.  Here --barcode-tag needs no -C: the tag is read
 from the record.  Beside them: --libraries (needs --markdup: the header's @RG lines are the table of libraries, duplicates are called within a library and the
 metrics table has a row per library; the rules and refusals of `bwamem_hip.mem --keep-rg --markdup`; off: one library), --batch-bytes N (the record bytes of a
@@ -25,18 +26,21 @@ message on stderr.
 """
 from __future__ import annotations
 
+import os
 import sys
 
 
 def bam_post_file(src, out, index=None, host: bool = False, level: int = 1, sort_window: int = 0, sort_mem=None, sort_tmp=None, batch_bytes=None, index_format: str = "bai",
                   csi_min_shift: int = 14, markdup: bool = False, markdup_metrics=None, libraries: bool = False, optical_distance=None, barcode_tag=None, barcode_name=None,
                   barcode_edits=None, coverage=None, coverage_hist=None, coverage_bed=None, coverage_bin=None, coverage_min_mapq=None, coverage_deletions=False, collate: bool = False,
-                  flagstat=None, idxstats=None, stats=None, insert_cap=None, recal=None, reference=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None) -> dict:
+                  flagstat=None, idxstats=None, stats=None, insert_cap=None, recal=None, reference=None, known_sites=None, recal_min_qual=None, recal_max_cycle=None, apply_recal=None, apply_recal_report=None) -> dict:
     """the BAM or SAM file `src` (a path; "-": stdin) -> the coordinate-sorted BAM written to `out` (a binary file object), its index to `index` (a path or a binary
     file object; None: not written), the metrics table to `markdup_metrics` and the coverage texts to coverage / coverage_hist / coverage_bed (paths or text file
     objects), as Aligner.align_files(sort=True, ...) writes them.  Returns lib.bam_post's dict.  The keywords are align_files' and are refused as there.
     collate=True (needs markdup=True): templates by name over the whole file, for an input that is not grouped by name (lib.bam_post).
     flagstat / idxstats / stats (paths or text file objects) and insert_cap: align_files' -- the statistics of the sorted file, from the windows of its merge.
+    apply_recal (a path to a table recal wrote, or read_recal_table's dict; needs no reference): the base qualities are recalibrated by that table as the sorted file
+    is written (align_files' keyword), apply_recal_report (a path or a text file object) takes recal_apply_report_text's rows; "recal_apply" holds the counts.
     recal (a path or a text file object; needs reference=PREFIX): the recalibration table of the sorted file against PREFIX.pac / .ann / .amb, under
     known_sites (VCF or BED files), recal_min_qual and recal_max_cycle; its read groups are the header's @RG lines (none: the one group `*`).  `src` is read twice --
     its header first -- so it is a file, not a pipe; a header whose @SQ lines are not the .ann's names and lengths in order is refused before anything is written."""
@@ -49,10 +53,12 @@ def bam_post_file(src, out, index=None, host: bool = False, level: int = 1, sort
         raise ValueError("bam_post_file: markdup_metrics needs markdup=True")
     req = coverage_request("bam_post_file", True, coverage, coverage_hist, coverage_bed, coverage_bin, coverage_min_mapq, coverage_deletions)
     sreq = stats_request("bam_post_file", True, flagstat, idxstats, stats, insert_cap)
-    rreq = recal_request("bam_post_file", reference is not None, recal, known_sites, recal_min_qual, recal_max_cycle, need="reference=PREFIX")
-    if rreq is None and reference is not None:
+    rreq = recal_request("bam_post_file", reference is not None, recal, known_sites, recal_min_qual, recal_max_cycle, apply_recal, apply_recal_report, need="reference=PREFIX")
+    if (rreq is None or rreq["table"] is None) and reference is not None:
         raise ValueError("bam_post_file: reference needs recal (the reference is read for the recalibration table alone)")
-    recal_kw = None if rreq is None else _recal_keywords(src, reference, rreq)
+    recal_kw = None if rreq is None or rreq["table"] is None else _recal_keywords(src, reference, rreq)
+    if rreq is not None and rreq["apply"] is not None:             # the table applied to the qualities as they are written; alone, no table is counted and no reference read
+        recal_kw = dict(recal_kw, apply=rreq["apply"]) if recal_kw is not None else dict(apply=rreq["apply"], count=False)
     r = bam_post("/dev/stdin" if src == "-" else src, out.write, host=host, level=level, window=sort_window, index_format=index_format, csi_min_shift=csi_min_shift, sort_mem=sort_mem,
                  sort_tmp=sort_tmp, batch_bytes=batch_bytes, markdup=markdup, libraries=libraries, optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name,
                  barcode_edits=barcode_edits, coverage=None if req is None else dict(min_mapq=req["min_mapq"], deletions=req["deletions"], bin=req["bin"]), collate=collate,
@@ -72,7 +78,12 @@ def bam_post_file(src, out, index=None, host: bool = False, level: int = 1, sort
             _write_text(req["bed"], coverage_bed_text(r["coverage"], r["contigs"], req["bin"]))
     if sreq is not None:
         write_stats_texts(sreq, r["stats"], r["contigs"])
-    if rreq is not None:
+    if rreq is not None and rreq["apply"] is not None:
+        r["recal_apply"] = r["recal"].pop("apply")
+        if rreq["apply_report"] is not None:
+            from .recal import write_recal_apply_report
+            write_recal_apply_report(r["recal_apply"], rreq["apply_report"])
+    if rreq is not None and rreq["table"] is not None:
         from .recal import write_recal_table
         write_recal_table(r["recal"], rreq["table"])
     if markdup_metrics is not None:
@@ -130,7 +141,7 @@ def _recal_keywords(src, reference: str, rreq: dict) -> dict:
 
 
 _VALUED = ("-o", "--device", "--index", "--sort-mem", "--sort-tmp", "--sort-window", "--markdup-metrics", "--batch-bytes", "--coverage", "--coverage-hist", "--coverage-bed", "--barcode-tag", "--flagstat", "--idxstats", "--stats",
-           "--bam-level", "--csi-min-shift", "--optical-distance", "--barcode-edits", "--coverage-bin", "--coverage-min-mapq", "--recal", "--reference", "--recal-min-qual", "--recal-max-cycle")
+           "--bam-level", "--csi-min-shift", "--optical-distance", "--barcode-edits", "--coverage-bin", "--coverage-min-mapq", "--recal", "--reference", "--recal-min-qual", "--recal-max-cycle", "--apply-recal", "--apply-recal-report")
 _NUMBERS = {"--bam-level": (0, 1, "0 or 1"), "--csi-min-shift": (10, 24, "a number in 10 .. 24"), "--optical-distance": (0, 0x7fffffff, "a whole number of pixels, 0 .. 2^31 - 1"),
             "--barcode-edits": (0, 21, "a whole number of mismatches, 0 .. 21"), "--coverage-bin": (1, 0xffffffff, "a whole number of positions, 1 .. 2^32 - 1"),
             "--coverage-min-mapq": (0, 255, "a whole number, 0 .. 255"), "--sort-mem": (1, 1 << 62, "a number of bytes"), "--batch-bytes": (1, 1 << 30, "a number of bytes, at most 2^30"),
@@ -189,7 +200,10 @@ def main(argv=None) -> int:
               ((sites or "--recal-min-qual" in v or "--recal-max-cycle" in v) and "--recal" not in v,
                "--known-sites, --recal-min-qual and --recal-max-cycle need --recal (they say what is counted, not where it goes)"),
               ("--recal" in v and "--reference" not in v, "--recal needs --reference PREFIX (the table compares the reads with PREFIX.pac, .ann and .amb)"),
-              ("--reference" in v and "--recal" not in v, "--reference needs --recal (the reference is read for the recalibration table alone)")]
+              ("--reference" in v and "--recal" not in v, "--reference needs --recal (the reference is read for the recalibration table alone)"),
+              ("--apply-recal-report" in v and "--apply-recal" not in v, "--apply-recal-report needs --apply-recal (it says what the applied table changed)"),
+              ("--apply-recal" in v and "--recal" in v and os.path.abspath(v["--apply-recal"]) == os.path.abspath(v["--recal"]),
+               "--recal and --apply-recal name the same file: counting and applying one table in one run would take two passes over the windows")]
     for bad, words in checks:
         if bad:
             print(f"{me} {words}", file=sys.stderr)
@@ -204,6 +218,14 @@ def main(argv=None) -> int:
         if not markdup:
             print(f"{me} --barcode-tag and --barcode-name need --markdup (barcodes are compared where duplicates are marked)", file=sys.stderr)
             return 2
+    apply_table = None
+    if "--apply-recal" in v:                                       # (read before the output is opened: a file that is no table leaves nothing behind)
+        from .recal import read_recal_table
+        try:
+            apply_table = read_recal_table(v["--apply-recal"])
+        except (ValueError, OSError) as e:
+            print(f"{me} --apply-recal: {e}", file=sys.stderr)
+            return 1
     out_path, csi, host = v.get("-o"), "--csi" in flags, "--host" in flags
     index_path = v.get("--index")
     if index_path is None and out_path is not None:
@@ -220,7 +242,8 @@ def main(argv=None) -> int:
                       coverage_hist=cov_paths.get("--coverage-hist"), coverage_bed=cov_paths.get("--coverage-bed"), coverage_bin=v.get("--coverage-bin"),
                       coverage_min_mapq=v.get("--coverage-min-mapq"), coverage_deletions="--coverage-deletions" in flags, collate="--collate" in flags,
                       flagstat=v.get("--flagstat"), idxstats=v.get("--idxstats"), stats=v.get("--stats"),
-                      recal=v.get("--recal"), reference=v.get("--reference"), known_sites=sites or None, recal_min_qual=v.get("--recal-min-qual"), recal_max_cycle=v.get("--recal-max-cycle"))
+                      recal=v.get("--recal"), reference=v.get("--reference"), known_sites=sites or None, recal_min_qual=v.get("--recal-min-qual"), recal_max_cycle=v.get("--recal-max-cycle"),
+                      apply_recal=apply_table, apply_recal_report=v.get("--apply-recal-report"))
         out.flush()
     except (ValueError, OSError) as e:
         print(f"{me} {e}", file=sys.stderr)

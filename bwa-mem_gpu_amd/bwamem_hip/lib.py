@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = [
     "bmh_bam_post_opt_default", "bmh_bam_post_result_free", "bmh_bam_post_file_device", "bmh_bam_post_file_host",
     "bmh_bam_templates_device", "bmh_bam_templates_host", "bmh_bam_templates_free",
     "bmh_recal_opt_default", "bmh_recal_free", "bmh_recal_kernel_limits", "bmh_bam_recal_device", "bmh_bam_recal_host", "bmh_known_sites_mask", "bmh_recal_mask_holes",
+    "bmh_recal_apply_tables", "bmh_bam_requal_device", "bmh_bam_requal_host", "bmh_requal_kernel_limits",
 ]
 
 
@@ -749,8 +750,11 @@ def index_format_code(index_format, csi_min_shift, what: str) -> tuple:
 
 def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, window: int = 0, host: bool = False, markdup: bool = False, read_groups=None,
                     index_format: str = "bai", csi_min_shift: int = 14, barcode_tag=None, barcode_name=None, barcode_edits=None, coverage=None, stats=None,
-                    optical_distance=None, recal=None) -> tuple:
-    """recal={pac, l_pac, contig_offset, mask, read_groups, min_qual, max_cycle, known_sites} (bmh_sorted_opt_t's recal; recal_opt's keywords): the file's covariate
+                    optical_distance=None, recal=None, apply_recal=None, apply_recal_report=None) -> tuple:
+    """apply_recal (a path or read_recal_table's dict): the qualities of every record are recalibrated by that table as the windows are written (DESIGN.md 4.17);
+    the tuple's last element is then the recal dict with the step's counts under "apply" (alone there when recal is None), and apply_recal_report (a path or a
+    text file object) takes recal_apply_report_text's rows.
+    recal={pac, l_pac, contig_offset, mask, read_groups, min_qual, max_cycle, known_sites} (bmh_sorted_opt_t's recal; recal_opt's keywords): the file's covariate
     table (bam_recal's dict), from the same windows with the flags markdup=True sets, comes last in the tuple.
     stats={insert_cap} (bmh_sorted_opt_t's stats; {} for the default): the file's statistics (bam_stats' dict), taken from the same windows with the flags
     markdup=True sets, come last in the tuple, behind the coverage where both are asked for.
@@ -766,6 +770,10 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
     barcode_edits (needs a barcode source): as bam_markdup takes it; the counts gain BARCODE_GROUP_COUNTS' names.
     optical_distance: the record's field, which the library refuses here -- a stand-alone file has no optical step (bam_markdup counts optical duplicates)."""
     L = _sorted_file_api(load_library())
+    if apply_recal_report is not None and apply_recal is None:
+        raise ValueError("bam_sorted_file: apply_recal_report needs apply_recal (it says what the applied table changed)")
+    if apply_recal is not None:
+        recal = dict(recal, apply=apply_recal) if recal is not None else dict(apply=apply_recal, count=False)
     q = sorted_request("bam_sorted_file", L, markdup=markdup, read_groups=read_groups, optical_distance=optical_distance, barcode_tag=barcode_tag, barcode_name=barcode_name, barcode_edits=barcode_edits, coverage=coverage,
                        stats=stats, index_format=index_format, csi_min_shift=csi_min_shift, level=level, window=window, recal=recal)
     records = bytes(records)
@@ -783,6 +791,9 @@ def bam_sorted_file(header_text: str, contigs, records: bytes, level: int = 1, w
         raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_sorted_file: " + _err(L))
     try:
         got = q.results(L)
+        if apply_recal_report is not None:
+            from .recal import write_recal_apply_report
+            write_recal_apply_report(got["recal"]["apply"], apply_recal_report)
         return (C.string_at(bam.value, nb.value), C.string_at(bai.value, ni.value)) + tuple(got[k] for k in ("markdup", "coverage", "stats", "recal") if k in got)
     finally:
         L.bmh_free.argtypes = [C.c_void_p]
@@ -923,28 +934,60 @@ def bam_stats(records: bytes, n_contigs: int, insert_cap: int = INSERT_CAP_DEFAU
     return stats_dict(L, st)
 
 
+class Recal(C.Structure):
+    """bmh_recal_t (the members from apply_summary on belong to the apply step, DESIGN.md 4.17: the library touches them only where RecalOpt's apply is set)"""
+    _fields_ = [("n_groups", C.c_int32), ("min_qual", C.c_int32), ("max_cycle", C.c_int32), ("n_qual", C.c_int32), ("summary", C.c_uint64 * 16),
+                ("cycle_m", _u64p), ("cycle_id", _u64p), ("context_m", _u64p), ("context_id", _u64p),
+                ("apply_summary", C.c_uint64 * 16), ("qual_hist", _u64p), ("apply_ms", C.c_double), ("apply_windows", C.c_uint64)]
+
+
+class RecalApplyOpt(C.Structure):
+    """bmh_recal_apply_opt_t"""
+    _fields_ = [("table", C.POINTER(Recal)), ("rg_ids", C.POINTER(C.c_char_p))]
+
+
 class RecalOpt(C.Structure):
     """bmh_recal_opt_t"""
     _fields_ = [("min_qual", C.c_int32), ("max_cycle", C.c_int32), ("pac", C.c_void_p), ("l_pac", C.c_uint64), ("contig_offset", C.c_void_p), ("mask", C.c_void_p),
-                ("mask_words", C.c_uint64), ("n_groups", C.c_int32), ("rg_ids", C.POINTER(C.c_char_p))]
-
-
-class Recal(C.Structure):
-    """bmh_recal_t"""
-    _fields_ = [("n_groups", C.c_int32), ("min_qual", C.c_int32), ("max_cycle", C.c_int32), ("n_qual", C.c_int32), ("summary", C.c_uint64 * 16),
-                ("cycle_m", _u64p), ("cycle_id", _u64p), ("context_m", _u64p), ("context_id", _u64p)]
+                ("mask_words", C.c_uint64), ("n_groups", C.c_int32), ("rg_ids", C.POINTER(C.c_char_p)), ("apply", C.POINTER(RecalApplyOpt)), ("no_count", C.c_int32)]
 
 
 RECAL_SUMMARY = ("records_seen", "records_counted", "left_out_no_contig", "left_out_flags", "left_out_mapq", "left_out_no_qualities", "left_out_no_operations", "bases_kept",
                  "skipped_not_acgt", "skipped_low_quality", "skipped_masked", "skipped_masked_anchor", "cycles_capped", "masked_positions")
 RECAL_MIN_QUAL, RECAL_MAX_CYCLE, RECAL_INDEL_QUAL, RECAL_MAX_GROUPS = 6, 500, 45, 255
+RECAL_APPLY_SUMMARY = ("records_seen", "records_rewritten", "records_without_qualities", "bases_seen", "bases_below_min_qual", "bases_changed", "bases_unchanged", "cycles_capped",
+                       "bases_without_context")
+RECAL_WIDE = 1      # summary[15] of a bmh_recal_t that holds the apply step's members
 
 
-def recal_opt(what="bam_recal", pac=None, l_pac=0, contig_offset=None, mask=None, read_groups=None, min_qual=None, max_cycle=None, known_sites=None):
+def recal_apply_opt(table, what="bam_apply_recal"):
+    """a table to apply (read_recal_table's / bam_recal's dict, or a path to the text) -> (bmh_recal_apply_opt_t, what it points to, to be kept alive as long as it).
+    ValueError names what the dict lacks; the library checks the rows"""
+    if isinstance(table, (str, bytes, os.PathLike)):
+        from .recal import read_recal_table
+        table = read_recal_table(os.fspath(table))
+    if not isinstance(table, dict) or any(k not in table for k in ("cycle_m", "context_m", "min_qual", "max_cycle")):
+        raise ValueError(f"{what}: apply_recal takes a path or read_recal_table's dict (cycle_m, context_m, min_qual, max_cycle, read_groups)")
+    cy, cx = np.ascontiguousarray(table["cycle_m"], dtype=np.uint64), np.ascontiguousarray(table["context_m"], dtype=np.uint64)
+    c = int(table["max_cycle"])
+    if cy.ndim != 4 or cx.ndim != 4 or cy.shape[1:] != (94, 2 * c, 2) or cx.shape != (cy.shape[0], 94, 17, 2):
+        raise ValueError(f"{what}: apply_recal: cycle_m {cy.shape} and context_m {cx.shape} are not [groups][94][2 max_cycle][2] and [groups][94][17][2] at max_cycle {c}")
+    ids = [str(g) for g in (table.get("read_groups") or ["*"])]
+    if len(ids) != cy.shape[0]:
+        raise ValueError(f"{what}: apply_recal: {len(ids)} read groups for a table of {cy.shape[0]}")
+    rt = Recal(cy.shape[0], int(table["min_qual"]), c, 94)
+    rt.cycle_m, rt.context_m = cy.ctypes.data_as(_u64p), cx.ctypes.data_as(_u64p)
+    arr = (C.c_char_p * len(ids))(*[g.encode() for g in ids])
+    a = RecalApplyOpt(C.pointer(rt), arr)
+    return a, [cy, cx, rt, arr]
+
+
+def recal_opt(what="bam_recal", pac=None, l_pac=0, contig_offset=None, mask=None, read_groups=None, min_qual=None, max_cycle=None, known_sites=None, apply=None, count=True):
     """the recalibration table's keywords, checked -> (bmh_recal_opt_t, what it points to, to be kept alive as long as it); ValueError names the keyword.
     pac: the .pac body (bytes or a uint8 array; None where the caller holds the reference: an aligner's run), l_pac its bases, contig_offset every contig's
     first base in it (None: back to back), mask a uint64 array of (l_pac + 63) // 64 words (known_sites_mask), read_groups the IDs in table order (None: the
-    one group `*`).  known_sites is not read here: the names go into the text"""
+    one group `*`).  known_sites is not read here: the names go into the text.  apply: a table to apply to the qualities as they are written (recal_apply_opt's
+    argument); count=False (needs apply): apply only -- no table is counted and nothing but apply is read"""
     min_qual = RECAL_MIN_QUAL if min_qual is None else min_qual
     max_cycle = RECAL_MAX_CYCLE if max_cycle is None else max_cycle
     if not isinstance(min_qual, (int, np.integer)) or isinstance(min_qual, bool) or not 0 <= min_qual <= 93:
@@ -973,6 +1016,11 @@ def recal_opt(what="bam_recal", pac=None, l_pac=0, contig_offset=None, mask=None
         if ids:
             arr = (C.c_char_p * len(ids))(*[g.encode() for g in ids])
             keep.append(arr); o.n_groups = len(ids); o.rg_ids = arr
+    if not count and apply is None:
+        raise ValueError(f"{what}: count=False needs apply (a run that neither counts nor applies a table has no recalibration step)")
+    if apply is not None:
+        a, held = recal_apply_opt(apply, what)
+        keep += [a] + held; o.apply = C.pointer(a); o.no_count = 0 if count else 1
     return o, keep
 
 
@@ -981,10 +1029,18 @@ def recal_dict(L, rt: Recal, read_groups=None, known_sites=None) -> dict:
     L.bmh_recal_free.argtypes, L.bmh_recal_free.restype = [C.POINTER(Recal)], None
     try:
         g, c, nq = int(rt.n_groups), int(rt.max_cycle), int(rt.n_qual)
-        return dict(summary=np.array(list(rt.summary), dtype=np.uint64), cycle_m=np.ctypeslib.as_array(rt.cycle_m, shape=(g, nq, 2 * c, 2)).copy(),
-                    cycle_id=np.ctypeslib.as_array(rt.cycle_id, shape=(g, 2 * c, 3)).copy(), context_m=np.ctypeslib.as_array(rt.context_m, shape=(g, nq, 17, 2)).copy(),
-                    context_id=np.ctypeslib.as_array(rt.context_id, shape=(g, 65, 3)).copy(), min_qual=int(rt.min_qual), max_cycle=c,
-                    read_groups=[str(x) for x in read_groups] if read_groups else ["*"], known_sites=[str(p) for p in (known_sites or [])])
+        out = {}
+        if rt.cycle_m:                                             # (an apply-only run counts no table)
+            summary = np.array(list(rt.summary), dtype=np.uint64); summary[15] = 0
+            out = dict(summary=summary, cycle_m=np.ctypeslib.as_array(rt.cycle_m, shape=(g, nq, 2 * c, 2)).copy(),
+                       cycle_id=np.ctypeslib.as_array(rt.cycle_id, shape=(g, 2 * c, 3)).copy(), context_m=np.ctypeslib.as_array(rt.context_m, shape=(g, nq, 17, 2)).copy(),
+                       context_id=np.ctypeslib.as_array(rt.context_id, shape=(g, 65, 3)).copy(), min_qual=int(rt.min_qual), max_cycle=c,
+                       read_groups=[str(x) for x in read_groups] if read_groups else ["*"], known_sites=[str(p) for p in (known_sites or [])])
+        if rt.summary[15] == RECAL_WIDE:                           # the apply step's counts
+            s = np.array(list(rt.apply_summary), dtype=np.uint64)
+            out["apply"] = dict(summary=s, qual_hist=np.ctypeslib.as_array(rt.qual_hist, shape=(2, 94)).copy(), ms=(float(rt.apply_ms), int(rt.apply_windows)),
+                                **dict(zip(RECAL_APPLY_SUMMARY, (int(v) for v in s))))
+        return out
     finally:
         L.bmh_recal_free(C.byref(rt))
 
@@ -1012,6 +1068,58 @@ def bam_recal(records: bytes, contigs, pac, l_pac: int, mask=None, read_groups=N
     if rc != 0:
         raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_recal: " + _err(L))
     return recal_dict(L, rt, read_groups)
+
+
+def bam_apply_recal(records: bytes, table, host: bool = False) -> tuple:
+    """bmh_bam_requal_device (host=True: _host, no device needed): a stream of BAM records in any order and a recalibration table (read_recal_table's dict or a
+    path) -> (the same stream with the base qualities rewritten as DESIGN.md 4.17 says, the counts: "summary" [16] with RECAL_APPLY_SUMMARY's names beside it,
+    "qual_hist" [2][94] the qualities before and after).  Device and host give the same bytes.  A refused record raises ValueError naming its index, a refused
+    table one naming the row"""
+    L = load_library()
+    records = bytes(records)
+    a, keep = recal_apply_opt(table)
+    rt, out = Recal(), C.c_void_p()
+    head = [C.c_char_p, C.c_uint64, C.POINTER(RecalApplyOpt)]
+    if host:
+        L.bmh_bam_requal_host.argtypes = head + [C.POINTER(C.c_void_p), C.POINTER(Recal)]
+        rc = L.bmh_bam_requal_host(records, len(records), C.byref(a), C.byref(out), C.byref(rt))
+    else:
+        L.bmh_bam_requal_device.argtypes = head + [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(Recal)]
+        rc = L.bmh_bam_requal_device(records, len(records), C.byref(a), _current_stream(), C.byref(out), C.byref(rt))
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_bam_requal: " + _err(L))
+    try:
+        return C.string_at(out.value, len(records)), recal_dict(L, rt)["apply"]
+    finally:
+        L.bmh_free.argtypes = [C.c_void_p]
+        L.bmh_free(out)
+
+
+def recal_apply_tables(table) -> np.ndarray:
+    """bmh_recal_apply_tables: the int16 deltas both forms of the apply step read, [groups][94][1 + 2 max_cycle + 16] -- b, the cycle deltas, the context deltas,
+    in 1/256 of a quality.  A refused table raises ValueError naming the row"""
+    L = load_library()
+    a, keep = recal_apply_opt(table, "recal_apply_tables")
+    out, n = C.c_void_p(), C.c_uint64()
+    L.bmh_recal_apply_tables.argtypes = [C.POINTER(RecalApplyOpt), C.POINTER(C.c_void_p), _u64p]
+    rc = L.bmh_recal_apply_tables(C.byref(a), C.byref(out), C.byref(n))
+    if rc != 0:
+        raise (ValueError if rc == -2 else RuntimeError)("bmh_recal_apply_tables: " + _err(L))
+    try:
+        g = int(a.table.contents.n_groups)
+        return np.frombuffer(C.string_at(out.value, 2 * n.value), dtype=np.int16).reshape(g, 94, -1).copy()
+    finally:
+        L.bmh_free.argtypes = [C.c_void_p]
+        L.bmh_free(out)
+
+
+def requal_kernel_limits() -> dict:
+    """bmh_requal_kernel_limits: the constants of the apply step's device form, for the tests that sit on them"""
+    L = load_library()
+    out = (C.c_uint32 * 3)()
+    L.bmh_requal_kernel_limits.argtypes, L.bmh_requal_kernel_limits.restype = [C.POINTER(C.c_uint32)], None
+    L.bmh_requal_kernel_limits(out)
+    return dict(zip(("lanes", "block_records", "lds_bases"), (int(v) for v in out)))
 
 
 def known_sites_mask(paths, contigs, l_pac=None, contig_offset=None, holes=None) -> np.ndarray:
@@ -1136,9 +1244,10 @@ def sorted_request(what: str, L, markdup: bool = False, read_groups=None, optica
     q.opt = SortedOpt(int(level), int(window), ix_code, ix_shift, int(sort_mem or 0), os.fsencode(sort_tmp) if sort_tmp is not None else None,
                       C.pointer(q.mo) if markdup else None, C.pointer(q.co) if q.co is not None else None, C.pointer(q.so) if q.so is not None else None)
     q.res = SortedResults(C.pointer(q.mc) if markdup else None, C.pointer(q.cov) if q.co is not None else None, C.pointer(q.st) if q.so is not None else None)
-    q.recal_kw, q.rt = dict(recal or {}), Recal()
+    q.recal_kw, q.rt = {k: v for k, v in (recal or {}).items() if k not in ("apply", "count")}, Recal()
     if recal is not None:                                          # (recal_opt's keywords; the record is the options' and the results' last member)
         q.ro, q.recal_keep = recal_opt(what, **recal)
+        q.recal_kw = {k: v for k, v in recal.items() if k not in ("apply", "count")}
         q.opt.recal = C.pointer(q.ro); q.res.recal = C.pointer(q.rt)
     return q
 

@@ -57,7 +57,10 @@ the whole file's, not per read group or library.
 for mismatches, insertions and deletions (GATK BaseRecalibrator's counting rules at its default covariates, restated; BAQ off, no adaptor clipping)
 -- counted on the device while the file is written, against the index's own reference, with --markdup's duplicates counted out.  --known-sites FILE (repeatable;
 VCF or BED, plain or gzip) masks known variants, the reference's holes (.amb) are always masked; --recal-min-qual Q (0 .. 93; 6) and --recal-max-cycle N
-(1 .. 65535; 500).  The read groups are -R's, --rg's or, with --keep-rg, the @RG lines of the input's header (read ahead of the run: a file, not a pipe).  An option that is
+(1 .. 65535; 500).  --apply-recal TABLE (needs --sort) recalibrates the base qualities of every record by a table --recal wrote, on the device while the file
+is written (GATK ApplyBQSR's hierarchical model over mismatches, restated; no OQ tag, no quantisation); --recal in the same run then counts the
+"after" table of the qualities as written (another file than TABLE), and --markdup's choice rests on the original qualities.  --apply-recal-report PATH writes
+what changed (rows `AS name value`, `AQ quality before after`).  The read groups are -R's, --rg's or, with --keep-rg, the @RG lines of the input's header (read ahead of the run: a file, not a pipe).  An option that is
 not on that list is refused by name.  Two input files imply pairs.  One plain, regular file is offered to Aligner.align_file first, which takes it when every
 record has one sequence line (its own counting pass decides, before anything is written); every other input goes through
 Aligner.align_files; the text is the same.  A refused file ends the command with status 1 and the library's message on stderr.
@@ -95,7 +98,7 @@ def main(argv=None) -> int:
     collate, collate_mem = False, None
     cov_paths, cov_bin, cov_mapq, cov_del = {}, None, None, False
     stats_paths = {}
-    recal_kw, recal_sites = {}, []
+    recal_kw, recal_sites, apply_kw = {}, [], {}
     groups = []                                                     # --rg LINE: [line, files...]; the positionals behind it are its files
     i = 0
     while i < len(argv):
@@ -174,6 +177,12 @@ def main(argv=None) -> int:
                     print(f"[bwamem_hip.mem] option {a} needs a whole number, {lo} .. {hi}", file=sys.stderr)
                     return 2
                 recal_kw[a[2:].replace("-", "_")] = int(argv[i + 1])
+            i += 1
+        elif a in ("--apply-recal", "--apply-recal-report"):
+            if i + 1 >= len(argv):
+                print(f"[bwamem_hip.mem] option {a} needs a value", file=sys.stderr)
+                return 2
+            apply_kw[a[2:].replace("-", "_")] = argv[i + 1]
             i += 1
         elif a in ("--flagstat", "--idxstats", "--stats"):
             if i + 1 >= len(argv):
@@ -301,6 +310,22 @@ def main(argv=None) -> int:
     if recal_kw and not sort:
         print("[bwamem_hip.mem] --recal, --known-sites, --recal-min-qual and --recal-max-cycle need --sort (the table is counted where the sorted file is written)", file=sys.stderr)
         return 2
+    if "apply_recal_report" in apply_kw and "apply_recal" not in apply_kw:
+        print("[bwamem_hip.mem] --apply-recal-report needs --apply-recal (it says what the applied table changed)", file=sys.stderr)
+        return 2
+    if apply_kw and not sort:
+        print("[bwamem_hip.mem] --apply-recal and --apply-recal-report need --sort (the qualities are rewritten where the sorted file is written)", file=sys.stderr)
+        return 2
+    if "apply_recal" in apply_kw:
+        if "recal" in recal_kw and os.path.abspath(recal_kw["recal"]) == os.path.abspath(apply_kw["apply_recal"]):
+            print("[bwamem_hip.mem] --recal and --apply-recal name the same file: counting and applying one table in one run would take two passes over the windows", file=sys.stderr)
+            return 2
+        from .recal import read_recal_table
+        try:                                                      # (read before the output is opened: a file that is no table leaves nothing behind)
+            apply_kw["apply_recal"] = read_recal_table(apply_kw["apply_recal"])
+        except (ValueError, OSError) as e:
+            print(f"[bwamem_hip.mem] --apply-recal: {e}", file=sys.stderr)
+            return 1
     if stats_paths and not sort:
         print("[bwamem_hip.mem] --flagstat, --idxstats and --stats need --sort (the statistics are computed where the sorted file is written)", file=sys.stderr)
         return 2
@@ -349,6 +374,8 @@ def main(argv=None) -> int:
             fmt_kw.update(flagstat=stats_paths.get("--flagstat"), idxstats=stats_paths.get("--idxstats"), stats=stats_paths.get("--stats"))
         if recal_kw:
             fmt_kw.update(recal_kw, known_sites=recal_sites or None)
+        if apply_kw:
+            fmt_kw.update(apply_kw)
         done = False
         if groups:
             al.align_groups([(g[0], g[1], g[2] if len(g) == 3 else None) for g in groups], out=out, paired=interleaved, **fmt_kw)

@@ -100,6 +100,26 @@ def write_recal_table(r: dict, dst) -> None:
             f.write(text)
 
 
+def recal_apply_report_text(a: dict) -> str:
+    """the counts of the apply step (bam_apply_recal's dict) -> the report: rows `AS name value`, then `AQ quality before after` for every quality
+    that bases held before or hold now"""
+    from .lib import RECAL_APPLY_SUMMARY
+    rows = [f"AS\t{nm}\t{int(a['summary'][k])}" for k, nm in enumerate(RECAL_APPLY_SUMMARY)]
+    h = a["qual_hist"]
+    rows += [f"AQ\t{q}\t{int(h[0][q])}\t{int(h[1][q])}" for q in range(len(h[0])) if int(h[0][q]) or int(h[1][q])]
+    return "\n".join(rows) + "\n"
+
+
+def write_recal_apply_report(a: dict, dst) -> None:
+    """recal_apply_report_text to dst: a path or a text file object"""
+    text = recal_apply_report_text(a)
+    if hasattr(dst, "write"):
+        dst.write(text)
+    else:
+        with open(dst, "w") as f:
+            f.write(text)
+
+
 def read_recal_table(path) -> dict:
     """the inverse of recal_table_text: a path (or the text's lines) -> bam_recal's dict.  ValueError names the line that is no row of the text, a row outside
     the run's parameters, or a QS / RG row that is not the sum of the cycle rows"""

@@ -939,7 +939,8 @@ int bmh_aligner_set_sorted_output(bmh_aligner_t *h, const bmh_sorted_opt_t *opt)
 	// group IDs stay the caller's until the run is over)
 	bmh_sorted_opt_t with; bmh_recal_opt_t ro; std::vector<uint64_t> coff;
 	if (opt && opt->recal && !opt->recal->pac) {
-		with = *opt; ro = *opt->recal;
+		with = *opt; memset(&ro, 0, sizeof ro); memcpy(&ro, opt->recal, offsetof(bmh_recal_opt_t, no_count));      // (no_count is read with apply only)
+		if (ro.apply) ro.no_count = opt->recal->no_count;
 		for (int64_t o : h->a.off) coff.push_back((uint64_t)o);
 		ro.l_pac = (uint64_t)h->a.l_pac; ro.contig_offset = coff.data();
 		with.recal = &ro; opt = &with;
@@ -986,7 +987,7 @@ int bmh_aligner_sorted_results(bmh_aligner_t *h, bmh_sorted_results_t *out, uint
 	const char *fn = "bmh_aligner_sorted_results";
 	static const struct { uint32_t part; const char *did; } parts[] = {{BMH_SORTED_MARKDUP, "marked duplicates"}, {BMH_SORTED_OPTICAL, "counted optical duplicates"}, {BMH_SORTED_BARCODE, "compared barcodes"},
 	                                                                   {BMH_SORTED_GROUPED, "grouped barcodes by edits"}, {BMH_SORTED_COVERAGE, "computed coverage"}, {BMH_SORTED_STATS, "computed statistics"},
-	                                                                   {BMH_SORTED_RECAL, "counted a recalibration table"}};
+	                                                                   {BMH_SORTED_RECAL, "counted or applied a recalibration table"}};
 	if (!h || !out) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
 	const bmh_aligner::last_t &T = h->last;
 	const uint32_t have = T.valid ? T.out.parts() : 0;
@@ -1137,6 +1138,7 @@ struct out_stage_t {
 		if (rc == BMH_OK) rc = bsr_write_device(L0.bsr, L0.bam, h->store, J, L0.st, forward, this, fn);
 		if (trace && J.stats) fprintf(stderr, "[aligner] statistics: the kernels of %.0f windows took %.2f ms on the device, %.3f ms per window\n", J.stats_ms[1], J.stats_ms[0], J.stats_ms[0] / (J.stats_ms[1] > 0 ? J.stats_ms[1] : 1));
 		if (trace && J.recal) fprintf(stderr, "[aligner] recalibration table: the kernels of %.0f windows took %.2f ms on the device, %.3f ms per window\n", J.recal_ms[1], J.recal_ms[0], J.recal_ms[0] / (J.recal_ms[1] > 0 ? J.recal_ms[1] : 1));
+		if (trace && J.requal) fprintf(stderr, "[aligner] qualities recalibrated: the kernels of %.0f windows took %.2f ms on the device, %.3f ms per window\n", J.requal_ms[1], J.requal_ms[0], J.requal_ms[0] / (J.requal_ms[1] > 0 ? J.requal_ms[1] : 1));
 		if (trace && J.coverage) fprintf(stderr, "[aligner] coverage: the depth steps of %.0f windows took %.2f ms on the device, %.3f ms per window (tile %llu, %llu bins)\n", J.cov_ms[1], J.cov_ms[0], J.cov_ms[0] / (J.cov_ms[1] > 0 ? J.cov_ms[1] : 1), (unsigned long long)J.CP.tile, (unsigned long long)J.CP.n_bins());
 		if (trace && J.markdup) fprintf(stderr, "[aligner] duplicate marking: %.0f bytes of ordinals and entries came down with the batches\n", J.dup_ms[2]);
 		if (trace) fprintf(stderr, "[aligner] sorted output: %zu runs (%llu spilled) merged in %.1f ms\n", h->store.runs.size(), (unsigned long long)h->store.spilled, (now_s() - tm0) * 1e3);

@@ -3,6 +3,7 @@
 // csrc/bam_sort_kernels.hip.  Both forms take the sorted file's windows of records one after the other; nothing but the
 // accumulator and the number of records seen passes from one window to the next.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -15,6 +16,7 @@ enum { BMH_OK = 0, BMH_EINVAL = -2, BMH_ENOMEM = -4 };
 void bmh_set_error(const char *fmt, ...);
 #endif
 #include "bam_recal_core.h"
+#include "bam_requal.h"                                            // the step that follows: its counts are exported into the same record
 
 // what a run is made under, checked: the layout (P), the host's copies of the contigs' places and of the group IDs, and the caller's reference and mask
 struct brc_run_t {
@@ -133,12 +135,18 @@ struct brc_mask_parser_t {
 };
 
 #ifndef BRC_STANDALONE
+// bmh_recal_t as it was before the apply step's members: a record is read and written beyond these bytes only where the caller has set the options' `apply`, or the
+// record says itself (summary [15] = BRC_WIDE, set by the export) that it holds them
+enum { BRC_WIDE = 1 };
+#define BRC_RECAL_OLD_BYTES offsetof(bmh_recal_t, apply_summary)
 // every array released, the record zeroed (bmh_recal_free, and a failed call's cleanup)
 inline void brc_release(bmh_recal_t *r)
 {
 	if (!r) return;
+	const bool wide = r->summary[BRC_N_SUM - 1] == (uint64_t)BRC_WIDE;
 	free(r->cycle_m); free(r->cycle_id); free(r->context_m); free(r->context_id);
-	memset(r, 0, sizeof *r);
+	if (wide) free(r->qual_hist);
+	memset(r, 0, wide ? sizeof *r : BRC_RECAL_OLD_BYTES);
 }
 inline int brc_run_from_opt(brc_run_t &U, const bmh_recal_opt_t *o, int n_contigs, const int32_t *contig_len, bool need_pac, const char *fn)
 {
@@ -146,21 +154,34 @@ inline int brc_run_from_opt(brc_run_t &U, const bmh_recal_opt_t *o, int n_contig
 	if (!o) { memset(&d, 0, sizeof d); d.min_qual = BRC_MIN_QUAL; d.max_cycle = BRC_MAX_CYCLE; o = &d; }
 	return brc_run_make(U, o->min_qual, o->max_cycle, o->pac, o->l_pac, o->contig_offset, o->mask, o->mask_words, o->n_groups, o->rg_ids, n_contigs, contig_len, need_pac, fn);
 }
-// R as the entry points return it (malloc'd arrays; *out zeroed first)
-inline int brc_export(const brc_run_t &U, const brc_result_t &R, bmh_recal_t *out, const char *fn)
+// R as the entry points return it (malloc'd arrays; *out zeroed first).  U and R NULL: no table was counted.  A (or NULL): the apply step's counts, with its
+// milliseconds and windows timed -- the only case in which the record's bytes beyond BRC_RECAL_OLD_BYTES are written
+inline int brc_export(const brc_run_t *U, const brc_result_t *R, bmh_recal_t *out, const char *fn, const brq_result_t *A = nullptr, const double *apply_ms = nullptr)
 {
-	memset(out, 0, sizeof *out);
-	const brc_plan_t &P = U.P;
-	const uint64_t *w = R.w.data();
-	auto dup = [w](uint64_t at, uint64_t n) { uint64_t *p = (uint64_t *)malloc(8 * (size_t)n + 8); if (p && n) memcpy(p, w + at, 8 * (size_t)n); return p; };
-	out->n_groups = P.n_groups; out->min_qual = P.min_qual; out->max_cycle = P.max_cycle; out->n_qual = BRC_NQ;
-	out->cycle_m = dup(P.w_cy_m(), P.w_cy_id() - P.w_cy_m()); out->cycle_id = dup(P.w_cy_id(), P.w_cx_m() - P.w_cy_id());
-	out->context_m = dup(P.w_cx_m(), P.w_cx_id() - P.w_cx_m()); out->context_id = dup(P.w_cx_id(), P.words() - P.w_cx_id());
-	if (!out->cycle_m || !out->cycle_id || !out->context_m || !out->context_id) {
+	memset(out, 0, A ? sizeof *out : BRC_RECAL_OLD_BYTES);
+	out->n_qual = BRC_NQ;
+	bool ok = true;
+	if (U && R) {
+		const brc_plan_t &P = U->P;
+		const uint64_t *w = R->w.data();
+		auto dup = [w](uint64_t at, uint64_t n) { uint64_t *p = (uint64_t *)malloc(8 * (size_t)n + 8); if (p && n) memcpy(p, w + at, 8 * (size_t)n); return p; };
+		out->n_groups = P.n_groups; out->min_qual = P.min_qual; out->max_cycle = P.max_cycle;
+		out->cycle_m = dup(P.w_cy_m(), P.w_cy_id() - P.w_cy_m()); out->cycle_id = dup(P.w_cy_id(), P.w_cx_m() - P.w_cy_id());
+		out->context_m = dup(P.w_cx_m(), P.w_cx_id() - P.w_cx_m()); out->context_id = dup(P.w_cx_id(), P.words() - P.w_cx_id());
+		ok = out->cycle_m && out->cycle_id && out->context_m && out->context_id;
+		for (int k = 0; k < BRC_N_SUM; ++k) out->summary[k] = w[k];
+	}
+	if (A) {
+		out->summary[BRC_N_SUM - 1] = BRC_WIDE;
+		for (int k = 0; k < BRQ_N_SUM; ++k) out->apply_summary[k] = A->w[(size_t)k];
+		out->qual_hist = (uint64_t *)malloc(8 * (size_t)BRQ_HIST);
+		if (out->qual_hist) memcpy(out->qual_hist, A->w.data() + BRQ_N_SUM, 8 * (size_t)BRQ_HIST); else ok = false;
+		if (apply_ms) { out->apply_ms = apply_ms[0]; out->apply_windows = (uint64_t)apply_ms[1]; }
+	}
+	if (!ok) {
 		brc_release(out);
 		bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM;
 	}
-	for (int k = 0; k < BRC_N_SUM; ++k) out->summary[k] = w[k];
 	return BMH_OK;
 }
 

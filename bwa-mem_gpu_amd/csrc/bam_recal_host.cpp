@@ -150,7 +150,7 @@ extern "C" int bmh_bam_recal_host(const uint8_t *recs, uint64_t n_bytes, int n_c
 {
 	const char *fn = "bmh_bam_recal_host";
 	if (!out || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	memset(out, 0, sizeof *out);
+	memset(out, 0, BRC_RECAL_OLD_BYTES);
 	try {
 		brc_run_t U;
 		int rc = brc_run_from_opt(U, opt, n_contigs, contig_len, true, fn);
@@ -164,7 +164,52 @@ extern "C" int bmh_bam_recal_host(const uint8_t *recs, uint64_t n_bytes, int n_c
 			if ((rc = H.window(recs, off.data() + a, (uint32_t)(b - a), fn)) != BMH_OK) return rc;
 		}
 		H.finish();
-		return brc_export(U, H.R, out, fn);
+		return brc_export(&U, &H.R, out, fn);
+	} catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- applying a table
+
+extern "C" int bmh_recal_apply_tables(const bmh_recal_apply_opt_t *apply, int16_t **tables, uint64_t *n_entries)
+{
+	const char *fn = "bmh_recal_apply_tables";
+	if (tables) *tables = nullptr;
+	if (!tables || !n_entries) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	*n_entries = 0;
+	try {
+		brq_run_t U;
+		const int rc = brq_run_from_opt(U, apply, fn);
+		if (rc != BMH_OK) return rc;
+		int16_t *t = (int16_t *)malloc(2 * U.t.size() + 2);
+		if (!t) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+		memcpy(t, U.t.data(), 2 * U.t.size());
+		*tables = t; *n_entries = U.t.size();
+		return BMH_OK;
+	} catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+}
+
+extern "C" int bmh_bam_requal_host(const uint8_t *recs, uint64_t n_bytes, const bmh_recal_apply_opt_t *apply, uint8_t **out, bmh_recal_t *counts)
+{
+	const char *fn = "bmh_bam_requal_host";
+	if (out) *out = nullptr;
+	if (!out || !counts || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
+	memset(counts, 0, sizeof *counts);
+	try {
+		brq_run_t U;
+		int rc = brq_run_from_opt(U, apply, fn);
+		if (rc != BMH_OK) return rc;
+		std::vector<uint64_t> off;
+		if ((rc = bst_walk(recs, n_bytes, off, fn)) != BMH_OK) return rc;
+		uint8_t *res = (uint8_t *)malloc((size_t)n_bytes + 1);
+		if (!res) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
+		if (n_bytes) memcpy(res, recs, (size_t)n_bytes);
+		brq_host_t H; H.begin(U);
+		const size_t n = off.size() - 1;
+		for (size_t a = 0; a < n && rc == BMH_OK; a += 1u << 20) rc = H.window(res, off.data() + a, (uint32_t)(std::min(n, a + (1u << 20)) - a), fn);
+		if (rc == BMH_OK) rc = brc_export(nullptr, nullptr, counts, fn, &H.R);
+		if (rc != BMH_OK) { free(res); return rc; }
+		*out = res;
+		return BMH_OK;
 	} catch (const std::bad_alloc &) { bmh_set_error("%s: out of memory", fn); return BMH_ENOMEM; }
 }
 #endif

@@ -226,7 +226,7 @@ extern "C" int bmh_bam_recal_device(const uint8_t *recs, uint64_t n_bytes, int n
 	const char *fn = "bmh_bam_recal_device";
 	hipStream_t st = (hipStream_t)stream;
 	if (!out || (n_bytes && !recs)) { bmh_set_error("%s: null argument", fn); return BMH_EINVAL; }
-	memset(out, 0, sizeof *out);
+	memset(out, 0, BRC_RECAL_OLD_BYTES);
 	brc_run_t U;
 	RCK(brc_run_from_opt(U, opt, n_contigs, contig_len, true, fn));
 	std::vector<uint64_t> off;
@@ -250,5 +250,5 @@ extern "C" int bmh_bam_recal_device(const uint8_t *recs, uint64_t n_bytes, int n
 		RCK(brc_window_ms(&d, nullptr, fn));
 	}
 	RCK(brc_finish_device(&d, stream, R, fn));
-	return brc_export(U, R, out, fn);
+	return brc_export(&U, &R, out, fn);
 }

@@ -48,10 +48,11 @@ int bsr_index_format_check(int format, int min_shift, const char *fn);
 // and the bytes of ordinals and entries that came down with the batches; opt_ms the optical step; cov_ms / stats_ms [2] the steps and the windows timed
 struct bsr_out_t {
 	int level = 1; uint32_t window = 0;
-	bool markdup = false, coverage = false, stats = false, timed = false, recal = false;
+	bool markdup = false, coverage = false, stats = false, timed = false, recal = false, requal = false;
 	bdp_plan_t P; bcv_plan_t CP; bst_plan_t SP;
 	brc_run_t RU; brc_result_t RR; double recal_ms[2] = {0, 0};    // the recalibration table: its checked run, its words, its windows' milliseconds
 	const uint8_t *recal_d_pac = nullptr;                          // ... the reference on the device where the caller holds one (the aligner's index), else RU.pac goes up
+	brq_run_t QU; brq_result_t QR; double requal_ms[2] = {0, 0};   // applying a table to the qualities: the checked table, the counts, the windows' milliseconds
 	bsr_index_t ix;
 	uint64_t *dup_counts = nullptr;                                // [BDP_N_COUNTS], with markdup
 	bcv_result_t CR; bst_result_t SR;
@@ -128,18 +129,19 @@ int bsr_sort_keys_device(bsr_dev_t *d, const uint64_t *keys, uint64_t n, void *s
 // cov (or NULL): the run's coverage (csrc/bam_cov_kernels.hip, begun by the caller) takes the window behind the flag step; cov_ms (or NULL) += its device milliseconds
 // stats (or NULL): the run's statistics (csrc/bam_stats_kernels.hip, begun by the caller) take the window beside it; stats_ms (or NULL) [2] += their milliseconds, the windows
 // recal (or NULL): the run's recalibration table (csrc/bam_recal_kernels.hip, begun by the caller) takes it beside them; recal_ms as stats_ms
+// requal (or NULL): the table applied to the window's qualities (csrc/bam_requal_kernels.hip, begun by the caller) behind the flag step and in front of all of them, which read the qualities as written; requal_ms as stats_ms
 // dup, tord [n] (host), flag_ms (or NULL, all three): the decided duplicates (bdp_decide_device) and every record's global template ordinal -- the flags are set between the gather and the compressor
 int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64_t src_bytes, const uint64_t *src_off, const uint32_t *size, uint32_t n, int level,
                       void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, struct bdp_dev_t *dup, const uint32_t *tord, double *flag_ms,
                       struct bcv_dev_t *cov = nullptr, double *cov_ms = nullptr, struct bst_dev_t *stats = nullptr, double *stats_ms = nullptr,
-                      struct brc_dev_t *recal = nullptr, double *recal_ms = nullptr);
+                      struct brc_dev_t *recal = nullptr, double *recal_ms = nullptr, struct brq_dev_t *requal = nullptr, double *requal_ms = nullptr);
 // every run of the store -> the record members of the sorted file (to the sink, in windows of J.window records; 0: about 64 MiB of records) and its index J.ix
 // J.markdup: mark the duplicates among the store's templates first, as J.P says (csrc/bam_dup_kernels.hip: the store keeps the locations and the barcode words
 // J.P's optical step and barcodes ask for), and flag every window's records; the counts of bam_dup.h go to J.dup_counts
 // cov, stats (or NULL): every window goes through the run's coverage and statistics (begun before, finished behind: bsr_write_device's)
 // J.timed: J.dup_ms [0 .. 1] += the decision's milliseconds (host clock around bdp_decide_device) and the windows' flag steps' (events around the upload of the
 // ordinals and the flag kernel), J.opt_ms += the optical step's, J.cov_ms and J.stats_ms += the windows'
-int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_out_t &J, void *stream, bsr_sink_t sink, void *user, struct bcv_dev_t *cov, struct bst_dev_t *stats, struct brc_dev_t *recal = nullptr);
+int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_out_t &J, void *stream, bsr_sink_t sink, void *user, struct bcv_dev_t *cov, struct bst_dev_t *stats, struct brc_dev_t *recal = nullptr, struct brq_dev_t *requal = nullptr);
 // the device form of a sorted output's run, whole: the coverage and the statistics begun (their device state lives here), the store's runs merged to the sink,
 // both finished into J.CR / J.SR, the marking's counts complete (the templates without a barcode, every library's line counts as the batches counted them)
 int bsr_write_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_out_t &J, void *stream, bsr_sink_t sink, void *user, const char *fn);

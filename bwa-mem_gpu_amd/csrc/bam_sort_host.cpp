@@ -63,7 +63,7 @@ extern "C" void bmh_sorted_opt_default(bmh_sorted_opt_t *o)
 uint32_t bsr_out_t::parts() const
 {
 	return (markdup ? BMH_SORTED_MARKDUP | (P.optical() ? BMH_SORTED_OPTICAL : 0u) | (P.barcode() ? BMH_SORTED_BARCODE : 0u) | (P.grouping() ? BMH_SORTED_GROUPED : 0u) : 0u) |
-	       (coverage ? BMH_SORTED_COVERAGE : 0u) | (stats ? BMH_SORTED_STATS : 0u) | (recal ? BMH_SORTED_RECAL : 0u);
+	       (coverage ? BMH_SORTED_COVERAGE : 0u) | (stats ? BMH_SORTED_STATS : 0u) | (recal || requal ? BMH_SORTED_RECAL : 0u);
 }
 
 int bsr_out_make(bsr_out_t &J, const bmh_sorted_opt_t *opt, int n_contigs, const int32_t *contig_len, const char *const *contig_names, bmh_sorted_results_t *res, const char *fn)
@@ -75,7 +75,7 @@ int bsr_out_make(bsr_out_t &J, const bmh_sorted_opt_t *opt, int n_contigs, const
 	// (the results' last members came with the recalibration table: a caller who does not ask for it may not have set them, so they are read with the option only)
 	bmh_markdup_counts_t *const mc = res->markdup; bmh_coverage_t *const cov = res->coverage; bmh_bam_stats_t *const st = res->stats; bmh_recal_t *const rt = o.recal ? res->recal : nullptr;
 	memset(res, 0, sizeof *res); res->markdup = mc; res->coverage = cov; res->stats = st; res->recal = rt;
-	if (rt) memset(rt, 0, sizeof *rt);
+	if (rt) memset(rt, 0, o.recal->apply ? sizeof *rt : BRC_RECAL_OLD_BYTES);      // (the apply step's members exist for the caller who sets `apply`)
 	if (cov) memset(cov, 0, sizeof *cov);
 	if (st) memset(st, 0, sizeof *st);
 	J = bsr_out_t();
@@ -100,8 +100,15 @@ int bsr_out_make(bsr_out_t &J, const bmh_sorted_opt_t *opt, int n_contigs, const
 	}
 	if (o.recal) {
 		if (!rt) { bmh_set_error("%s: null argument (the recalibration table needs its record)", fn); return BMH_EINVAL; }
-		if ((rc = brc_run_from_opt(J.RU, o.recal, n_contigs, contig_len, false, fn)) != BMH_OK) return rc;
-		J.recal = true;
+		const bmh_recal_apply_opt_t *const ap = o.recal->apply;
+		if (!(ap && o.recal->no_count)) {
+			if ((rc = brc_run_from_opt(J.RU, o.recal, n_contigs, contig_len, false, fn)) != BMH_OK) return rc;
+			J.recal = true;
+		}
+		if (ap) {
+			if ((rc = brq_run_from_opt(J.QU, ap, fn)) != BMH_OK) return rc;
+			J.requal = true;
+		}
 	}
 	return BMH_OK;
 }
@@ -126,7 +133,7 @@ int bsr_out_export(const bsr_out_t &J, bmh_sorted_results_t *res, const char *fn
 	int rc = BMH_OK;
 	if (J.coverage && res->coverage) rc = bcv_export(J.CP, J.CR, res->coverage, fn);
 	if (rc == BMH_OK && J.stats && res->stats) rc = bst_export(J.SP, J.SR, res->stats, fn);
-	if (rc == BMH_OK && J.recal && res->recal) rc = brc_export(J.RU, J.RR, res->recal, fn);
+	if (rc == BMH_OK && (J.recal || J.requal) && res->recal) rc = brc_export(J.recal ? &J.RU : nullptr, J.recal ? &J.RR : nullptr, res->recal, fn, J.requal ? &J.QR : nullptr, J.requal_ms);
 	if (rc != BMH_OK) bsr_results_release(res);
 	return rc;
 }
@@ -374,13 +381,14 @@ extern "C" int bmh_bam_sort_host(const uint8_t *recs, uint64_t n_bytes, uint8_t 
 
 int bsr_write_host(const uint8_t *recs, const uint64_t *off, const uint32_t *ord, uint64_t n, bsr_out_t &J, bsr_sink_t sink, void *user, const char *fn)
 {
-	bcv_host_t H; bst_host_t SH; brc_host_t RH;
+	bcv_host_t H; bst_host_t SH; brc_host_t RH; brq_host_t QH;
 	if (J.coverage) H.begin(J.CP);
 	if (J.stats) SH.begin(J.SP);
 	if (J.recal) {
 		if (!J.RU.pac && J.RU.l_pac) { bmh_set_error("%s: the recalibration table needs the reference (pac, l_pac)", fn); return BMH_EINVAL; }
 		RH.begin(J.RU);
 	}
+	if (J.requal) QH.begin(J.QU);
 	const uint64_t W = J.window ? J.window : std::max<uint64_t>(1, (64ull << 20) / std::max<uint64_t>(1, n ? off[n] / n : 1));
 	std::vector<uint8_t> buf; std::vector<uint64_t> soff, moff;
 	int rc;
@@ -388,6 +396,7 @@ int bsr_write_host(const uint8_t *recs, const uint64_t *off, const uint32_t *ord
 		const uint64_t b = std::min<uint64_t>(n, a + W);
 		soff.assign(1, 0); buf.clear();
 		for (uint64_t j = a; j < b; ++j) { const uint64_t o = off[ord[j]], s = off[ord[j] + 1] - o; buf.insert(buf.end(), recs + o, recs + o + s); soff.push_back(buf.size()); }
+		if (J.requal && (rc = QH.window(buf.data(), soff.data(), (uint32_t)(b - a), fn)) != BMH_OK) return rc;      // the qualities as they are written: everything below reads them so
 		uint8_t *m = nullptr; uint64_t mb = 0;
 		if ((rc = bmh_bgzf_deflate_host(buf.data(), buf.size(), J.level, 0, &m, &mb)) != BMH_OK) return rc;
 		moff.assign(1, 0);                                // the members' offsets: every member's BSIZE
@@ -403,6 +412,7 @@ int bsr_write_host(const uint8_t *recs, const uint64_t *off, const uint32_t *ord
 	if (J.coverage) { if ((rc = H.finish(fn)) != BMH_OK) return rc; J.CR = std::move(H.R); }
 	if (J.stats) { SH.finish(); J.SR = std::move(SH.R); }
 	if (J.recal) { RH.finish(); J.RR = std::move(RH.R); }
+	if (J.requal) J.QR = std::move(QH.R);
 	return BMH_OK;
 }
 

@@ -257,7 +257,7 @@ int bsr_index_finish(bsr_dev_t *d, bsr_index_t &ix, void *stream)
 
 int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64_t src_bytes, const uint64_t *src_off, const uint32_t *size, uint32_t n, int level,
                       void *stream, bsr_index_t &ix, bsr_sink_t sink, void *user, bdp_dev_t *dup, const uint32_t *tord, double *flag_ms, bcv_dev_t *cov, double *cov_ms,
-                      bst_dev_t *stats, double *stats_ms, brc_dev_t *recal, double *recal_ms)
+                      bst_dev_t *stats, double *stats_ms, brc_dev_t *recal, double *recal_ms, brq_dev_t *requal, double *requal_ms)
 {
 	hipStream_t st = (hipStream_t)stream;
 	if (n == 0) return BMH_OK;
@@ -276,6 +276,8 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 		RCK(bdp_flag_device(dup, (uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, tord, n, total, st));
 		if (flag_ms) HIPCK(hipEventRecord(d->ev_flag[1], st));
 	}
+	// the table applied to the qualities: one kernel that rewrites the window in place; every step below reads the qualities as written
+	if (requal) RCK(brq_window_device(requal, (uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, n, st, requal_ms));
 	// coverage reads the records in their final order with their final flags; the window's last record (host) sets its frontier
 	if (cov) RCK(bcv_window_device(cov, (const uint8_t *)d->sorted.p, (const uint64_t *)d->soff.p, n, src + src_off[n - 1], st, "sorted BAM", cov_ms));
 	// the statistics read the same records: one kernel, nothing waits for it here
@@ -305,6 +307,7 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 	if (cov && cov_ms) RCK(bcv_window_ms(cov, cov_ms));
 	if (stats) RCK(bst_window_ms(stats, stats_ms, "sorted BAM"));        // (a refused record ends the run before the window's members reach the sink)
 	if (recal) RCK(brc_window_ms(recal, recal_ms, "sorted BAM"));
+	if (requal) RCK(brq_window_ms(requal, requal_ms, "sorted BAM"));
 	if (nh == 0 || nh > n) { bmh_set_error("sorted BAM: internal error: %u chunk heads among %u records", nh, n); return BMH_EINVAL; }
 	const size_t h0 = ix.heads.size();
 	ix.heads.resize(h0 + nh);
@@ -315,11 +318,12 @@ int bsr_window_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const uint8_t *src, uint64
 }
 
 // every run of the store -> the sorted file's record members (to the sink) and its index
-int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_out_t &J, void *stream, bsr_sink_t sink, void *user, bcv_dev_t *cov, bst_dev_t *stats, brc_dev_t *recal)
+int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_out_t &J, void *stream, bsr_sink_t sink, void *user, bcv_dev_t *cov, bst_dev_t *stats, brc_dev_t *recal, brq_dev_t *requal)
 {
 	const bdp_plan_t &P = J.P; bsr_index_t &ix = J.ix; const int level = J.level; const uint32_t window = J.window;
 	uint64_t *const dup_counts = J.markdup ? J.dup_counts : nullptr;
-	double *const cov_ms = J.timed && cov ? J.cov_ms : nullptr, *const stats_ms = J.timed && stats ? J.stats_ms : nullptr, *const recal_ms = J.timed && recal ? J.recal_ms : nullptr;
+	double *const cov_ms = J.timed && cov ? J.cov_ms : nullptr, *const stats_ms = J.timed && stats ? J.stats_ms : nullptr, *const recal_ms = J.timed && recal ? J.recal_ms : nullptr,
+	       *const requal_ms = J.timed && requal ? J.requal_ms : nullptr;
 	const bdp_optical_t *optical = P.optical(); const bool barcode = P.barcode() != nullptr;
 	uint64_t n = 0, bytes = 0;
 	std::vector<uint64_t> first;
@@ -370,7 +374,7 @@ int bsr_merge_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_o
 				if (dup.p) tord[j] = (uint32_t)(R.tbase + R.tpl[i]);
 			}
 			// (the pinned buffer takes the members once the records are on the device: the compressor waits for the stream in between)
-			RCK(bsr_window_device(d, ws, d->h_buf, sb, src_off.data(), size.data(), m, level, stream, ix, sink, user, dup.p, dup.p ? tord.data() : nullptr, dup.p ? &flag_ms : nullptr, cov, cov_ms, stats, stats_ms, recal, recal_ms));
+			RCK(bsr_window_device(d, ws, d->h_buf, sb, src_off.data(), size.data(), m, level, stream, ix, sink, user, dup.p, dup.p ? tord.data() : nullptr, dup.p ? &flag_ms : nullptr, cov, cov_ms, stats, stats_ms, recal, recal_ms, requal, requal_ms));
 		}
 	}
 	if (dup_counts) {
@@ -405,7 +409,13 @@ int bsr_write_device(bsr_dev_t *d, bmh_bam_ws_t *ws, const bsr_store_t &S, bsr_o
 		if (!(recal.p = brc_dev_create())) return BMH_ENOMEM;
 		RCK(brc_begin_device(recal.p, J.RU, J.recal_d_pac, stream));
 	}
-	RCK(bsr_merge_device(d, ws, S, J, stream, sink, user, cov.p, stats.p, recal.p));
+	struct requal_own_t { brq_dev_t *p = nullptr; ~requal_own_t() { if (p) brq_dev_free(p); } } requal;
+	if (J.requal) {
+		if (!(requal.p = brq_dev_create())) return BMH_ENOMEM;
+		RCK(brq_begin_device(requal.p, J.QU, stream));
+	}
+	RCK(bsr_merge_device(d, ws, S, J, stream, sink, user, cov.p, stats.p, recal.p, requal.p));
+	if (requal.p) RCK(brq_finish_device(requal.p, stream, J.QR, fn));
 	if (recal.p) RCK(brc_finish_device(recal.p, stream, J.RR, fn));
 	if (stats.p) RCK(bst_finish_device(stats.p, stream, J.SR, fn));
 	if (cov.p) RCK(bcv_finish_device(cov.p, stream, J.CR, fn, J.timed ? J.cov_ms : nullptr));

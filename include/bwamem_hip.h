@@ -953,6 +953,7 @@ typedef struct bmh_bam_stats_opt bmh_bam_stats_opt_t;
 typedef struct bmh_bam_stats bmh_bam_stats_t;
 typedef struct bmh_recal_opt bmh_recal_opt_t;
 typedef struct bmh_recal bmh_recal_t;
+typedef struct bmh_recal_apply_opt bmh_recal_apply_opt_t;
 typedef struct {
 	int32_t level; uint32_t window; int32_t index_format, min_shift;
 	uint64_t sort_mem; const char *tmp_dir;
@@ -1265,12 +1266,18 @@ struct bmh_recal_opt {
 	const uint8_t *pac; uint64_t l_pac; const uint64_t *contig_offset;
 	const uint64_t *mask; uint64_t mask_words;
 	int32_t n_groups; const char *const *rg_ids;
+	const bmh_recal_apply_opt_t *apply;   /* the table to apply to the qualities as they are written (below); NULL: off */
+	int32_t no_count;                     /* read with apply only.  1: apply only -- no table is counted, pac, mask, the contigs' places and rg_ids are not read */
 };
 void bmh_recal_opt_default(bmh_recal_opt_t *o);
 struct bmh_recal {
 	int32_t n_groups, min_qual, max_cycle, n_qual;
 	uint64_t summary[16];
 	uint64_t *cycle_m, *cycle_id, *context_m, *context_id;
+	/* the apply step's members: read and written only where the options' apply is set (bmh_bam_requal_*: always) */
+	uint64_t apply_summary[16];
+	uint64_t *qual_hist;
+	double apply_ms; uint64_t apply_windows;
 };
 void bmh_recal_free(bmh_recal_t *r);
 void bmh_recal_kernel_limits(uint32_t out[5]);   /* the device form's capacities: slots, lanes per record, cycles per LDS row, records per block, bases per LDS record */
@@ -1279,6 +1286,34 @@ int bmh_bam_recal_host(const uint8_t *records, uint64_t n_bytes, int n_contigs, 
 int bmh_known_sites_mask(const char *const *paths, int n_paths, int n_contigs, const char *const *contig_names, const int32_t *contig_len, const uint64_t *contig_offset,
                          uint64_t *mask, uint64_t mask_words);
 int bmh_recal_mask_holes(const uint64_t *hole_offset, const uint64_t *hole_len, int n_holes, uint64_t *mask, uint64_t mask_words);
+
+/* ---- Applying a recalibration table to the base qualities while sorted BAM is written (csrc/bam_requal_core.h, csrc/bam_requal.h, csrc/bam_requal_kernels.hip;
+ * DESIGN.md 4.17): the step that follows the table -- this project's restatement of GATK ApplyBQSR's hierarchical delta model over event M (group, quality, cycle,
+ * context), with the plain empirical quality -10 log10((errors + 1) / (observations + 2)).  It was not compared with GATK.  Not done: an OQ tag, quantised
+ * output qualities, insertion and deletion qualities, GATKReport files, counting and applying one table in one run, the Bayesian empirical quality.
+ * bmh_recal_apply_opt_t: table -- a bmh_recal_t of counts as the counting pass returns it (n_groups, min_qual, max_cycle, n_qual, cycle_m and context_m are read);
+ * rg_ids [table->n_groups] its read groups' IDs (NULL, or the one ID `*`: the table's one group applies to every record and RG tags are not read).
+ * Refused before anything is written, naming the row: errors above observations, a (group, quality) whose cycle rows and context rows sum differently (the slot
+ * `none` included), min_qual or max_cycle out of range.  Refused by the record's index, the smallest of a window first: a record that is not whole; with groups
+ * tags that cannot be walked, no RG tag, an RG tag of another type than Z, an ID the table does not hold.
+ * Every record with qualities is rewritten, whatever its flags; a quality below the table's min_qual stays; nothing else in a record changes.
+ * bmh_recal_opt_t's apply: the step in every window of a sorted output behind the flag step and in front of coverage, statistics, the counting of a table
+ * (which then counts the qualities as written) and the compressor; the results' bmh_recal_t holds apply_summary -- records seen, rewritten, without qualities;
+ * bases seen, below min_qual, changed, unchanged; cycles capped, bases without context --, qual_hist [2][94] (the qualities before and after; malloc'd, released by
+ * bmh_recal_free), the kernels' milliseconds and the windows timed.  Both members are the options' last, the apply members the record's last: a caller who built
+ * either before they existed, positionally or zeroed, leaves apply NULL, and then no byte of the record beyond cycle .. context_id is read or written.
+ * (summary [15] of a record that holds the apply members is 1: that is how bmh_recal_free knows.)
+ * bmh_recal_apply_tables: the int16 deltas both forms read -- [groups][94][1 + 2 max_cycle + 16]: b, the cycle deltas, the context deltas, in 1/256 of a quality
+ * (malloc'd; bmh_free).  bmh_bam_requal_device / _host: a record stream -> the same stream with the qualities rewritten (malloc'd; bmh_free) and the counts; both
+ * forms give the same bytes.  bmh_requal_kernel_limits: lanes per record, records per block, bases of a record whose counts stay in LDS. */
+struct bmh_recal_apply_opt {
+	const bmh_recal_t *table;
+	const char *const *rg_ids;
+};
+int bmh_recal_apply_tables(const bmh_recal_apply_opt_t *apply, int16_t **tables, uint64_t *n_entries);
+int bmh_bam_requal_device(const uint8_t *records, uint64_t n_bytes, const bmh_recal_apply_opt_t *apply, void *stream, uint8_t **out, bmh_recal_t *counts);
+int bmh_bam_requal_host(const uint8_t *records, uint64_t n_bytes, const bmh_recal_apply_opt_t *apply, uint8_t **out, bmh_recal_t *counts);
+void bmh_requal_kernel_limits(uint32_t out[3]);
 
 #ifdef __cplusplus
 }

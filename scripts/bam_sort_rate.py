@@ -8,11 +8,13 @@ sorted file's size (the two copies land next to each other) and the merge's comp
     python scripts/bam_sort_rate.py [--runs 3] [--reads 1000000] [--genome-mbp 3100] [--out FILE] [--markdup [--groups | --optical N] [--parent-json FILE]]
                                     [--coverage [--coverage-bin N] [--sort-window W] [--parent-json FILE]]
                                     [--stats [--sort-window W] [--parent-json FILE]]
-                                    [--recal [--off-only] [--sort-window W] [--parent-json FILE]]
+                                    [--recal [--apply-recal] [--off-only] [--sort-window W] [--parent-json FILE]]
 
 --recal: the recalibration-table leg (profiles/bam_recal.json), at the statistics leg's size: the paired rows sorted and sorted + marked from FASTA, and from FASTQ
 under two quality alphabets (about 40 distinct values; 4 binned ones) the row sorted + marked and the row with the table counted beside it -- with the counting
 kernels alone as the library times them (events around every window's kernel) and their share of the final merge.  --off-only: the rows without the option alone.
+--recal --apply-recal: the leg of the apply step (profiles/bam_requal.json) on the 40-value FASTQ: sorted + marked without the option, with the table
+counted (the counting kernel's milliseconds per window), with that table applied (the apply kernel's, on the same windows), and with both in one run.
 --stats: the statistics leg (profiles/bam_stats.json), at the coverage leg's size: the sorted in-memory row, the same row with duplicates marked, the row `sorted +
 marked + statistics` (reads_to_sorted_bam_in_memory_markdup_stats) -- with the statistics kernels alone as the library times them (bmh_aligner_stats_ms: events
 around every window's kernel), per run and per window, and their share of the final merge -- and, on the paired set, that row with coverage beside it.
@@ -78,6 +80,7 @@ def main():
     ap.add_argument("--sort-window", type=int, default=0)
     ap.add_argument("--stats", action="store_true")
     ap.add_argument("--recal", action="store_true", help="the recalibration-table leg (profiles/bam_recal.json)")
+    ap.add_argument("--apply-recal", action="store_true", help="with --recal: the leg of the apply step (profiles/bam_requal.json)")
     ap.add_argument("--off-only", action="store_true", help="with --recal: the rows without the option alone (a parent library under BMH_LIB: the file --parent-json takes)")
     a = ap.parse_args()
     if a.optical is not None and (not a.markdup or a.groups or not 0 <= a.optical <= 0x7fffffff):
@@ -135,14 +138,14 @@ def main():
     nat = NativeAligner(dindex, pac_h, n_genome, contigs, None, co, ExtParams.default(), po, pe_o)
     result = {"genome_mbp": a.genome_mbp, "reads_per_run": n4, "setup_s": round(time.time() - t0, 1), "runs": a.runs, "host_threads": nth, "rows": {}}
 
-    def run(fmt, spill=False, keep=None, markdup=False, paired=False, groups=None, files=False, optical=None, coverage=None, qc=None, recal=None, src=None):
+    def run(fmt, spill=False, keep=None, markdup=False, paired=False, groups=None, files=False, optical=None, coverage=None, qc=None, recal=None, src=None, table=None):
         src = src or (ppath if paired else path)
         if fmt == "bam_sorted":
             nat.set_sorted(level=1, sort_mem=1 if spill else 64 << 30, sort_tmp=tmp, window=a.sort_window, markdup=markdup, optical_distance=optical, coverage=coverage, stats=qc,
                            **({} if recal is None else dict(recal=recal)))
         else:
             nat.set_output(fmt, 1)
-        opt_ms, cov_ms, st_ms, rc_ms = [], [], [], []
+        opt_ms, cov_ms, st_ms, rc_ms, ap_ms = [], [], [], [], []
         nbytes = [0]
 
         def sink(mv):
@@ -171,8 +174,10 @@ def main():
                     cov_ms.append(got["coverage_ms"])
                 if qc is not None:
                     st_ms.append(got["stats_ms"])
-                if recal is not None:
+                if recal is not None and recal.get("count", True):
                     rc_ms.append(got["recal_ms"])
+                if recal is not None and recal.get("apply") is not None:
+                    ap_ms.append(got["recal"]["apply"]["ms"])
         row = stats(secs, n4, 1e6)
         row["unit"] = "Mreads/s"; row["bytes_out_per_read"] = round(nbytes[0] / n4, 1)
         if fmt == "bam_sorted":
@@ -198,7 +203,14 @@ def main():
                 qs = got["stats"]
                 row["stats"] = {"insert_cap": int(qc.get("insert_cap", 65536)), "total": int(qs["flag"][:, 0].sum()), "duplicates": int(qs["flag"][:, 4].sum()), "mapped": int(qs["flag"][:, 6].sum()),
                                 "pairs_counted": [int(v) for v in qs["insert_hist"].sum(axis=1)], "largest_insert_bin": int(qs["insert_hist"].max()), "edit_distance": int(qs["summary"][13])}
-            if recal is not None:
+            if recal is not None and recal.get("apply") is not None:
+                ms = [t for t, _w in ap_ms]
+                row["apply_steps_alone"] = {"unit": "ms on the stream per run (events around every window's apply kernel)",
+                                            "median": round(sorted(ms)[len(ms) // 2], 3), "runs": [round(t, 3) for t in ms], "windows": [w for _t, w in ap_ms],
+                                            "ms_per_window": [round(t / max(w, 1), 3) for t, w in ap_ms],
+                                            "share_of_final_merge_pct": round(100 * sorted(ms)[len(ms) // 2] / (1e3 * sorted(merge)[len(merge) // 2]), 2)}
+                row["apply"] = {k: int(v) for k, v in got["recal"]["apply"].items() if isinstance(v, int)}
+            if recal is not None and recal.get("count", True):
                 ms = [t for t, _w in rc_ms]
                 row["recal_steps_alone"] = {"unit": "ms on the stream per run (events around every window's counting kernel)",
                                             "median": round(sorted(ms)[len(ms) // 2], 3), "runs": [round(t, 3) for t in ms], "windows": [w for _t, w in rc_ms],
@@ -207,6 +219,8 @@ def main():
                 rs = got["recal"]
                 row["recal"] = {"records_counted": int(rs["summary"][1]), "bases_kept": int(rs["summary"][7]), "observations": int(rs["cycle_m"][..., 0].sum()), "mismatches": int(rs["cycle_m"][..., 1].sum()),
                                 "qualities_seen": int(np.count_nonzero(rs["cycle_m"][0, :, :, 0].sum(axis=1))), "masked_positions": int(rs["summary"][13])}
+            if table is not None:
+                table["recal"] = got["recal"]
             if markdup:
                 row["counts"] = got["markdup_counts"]
                 tpl = row["counts"]["templates"]
@@ -236,14 +250,18 @@ def main():
         result["rows"]["paired_reads_to_sorted_bam_in_memory"] = run("bam_sorted", paired=True)
         result["rows"]["paired_reads_to_sorted_bam_in_memory_markdup"] = run("bam_sorted", markdup=True, paired=True)
         rng = np.random.default_rng(3)
-        for label, alphabet in (("q40", np.arange(2, 42)), ("q4", np.array([2, 12, 23, 37]))):
+        for label, alphabet in (("q40", np.arange(2, 42)), ("q4", np.array([2, 12, 23, 37])))[:1 if a.apply_recal else 2]:
             fq = os.path.join(tmp, label + ".fq")
             write_fastq(fq, pn, pasc, alphabet[rng.integers(0, len(alphabet), (n4, rl))].astype(np.uint8))
             result["rows"]["paired_fastq_%s_to_sorted_bam_in_memory_markdup" % label] = run("bam_sorted", markdup=True, paired=True, files=True, src=fq)
             if not a.off_only:
                 from bwamem_hip.lib import known_sites_mask
                 mask = known_sites_mask([], contigs, l_pac=n_genome, holes=[(int(h[0]), int(h[1]) - int(h[0])) for h in holes])
-                result["rows"]["paired_fastq_%s_to_sorted_bam_in_memory_markdup_recal" % label] = run("bam_sorted", markdup=True, paired=True, files=True, src=fq, recal=dict(mask=mask))
+                counted = {}
+                result["rows"]["paired_fastq_%s_to_sorted_bam_in_memory_markdup_recal" % label] = run("bam_sorted", markdup=True, paired=True, files=True, src=fq, recal=dict(mask=mask), table=counted)
+                if a.apply_recal:                                 # the table that run counted, applied to the same windows: alone, and with the "after" table counted beside it
+                    result["rows"]["paired_fastq_%s_to_sorted_bam_in_memory_markdup_apply" % label] = run("bam_sorted", markdup=True, paired=True, files=True, src=fq, recal=dict(apply=counted["recal"], count=False))
+                    result["rows"]["paired_fastq_%s_to_sorted_bam_in_memory_markdup_apply_recal" % label] = run("bam_sorted", markdup=True, paired=True, files=True, src=fq, recal=dict(mask=mask, apply=counted["recal"]))
             os.remove(fq)
         nat.set_output("sam", 1)
         if a.parent_json:
@@ -255,10 +273,13 @@ def main():
                 tr = result["rows"][k]
                 diff = 100 * abs(tr["median"] - pr["median"]) / pr["median"]
                 result["option_off_vs_parent"][k] = {"difference_pct": round(diff, 1), "larger_spread_pct": max(tr["spread_pct"], pr["spread_pct"]), "within_spread": diff <= max(tr["spread_pct"], pr["spread_pct"])}
+        if a.apply_recal:
+            result["not_measured_apply"] = ("several read groups (lane 0 then walks every record's tags and compares up to 255 IDs), real quality distributions (uniform draws here: a "
+                                            "lane's histogram runs are short), tables at a large max_cycle (a group's rows are 191 KB at the default 500 and stay in L2)")
         result["not_measured"] = ("real data with deep duplicate stacks (every read occurs twice here), a mask of dbSNP's density (the holes alone here), the time to parse a large VCF, spilled runs, "
                                   "long reads whose cycles exceed the cap, the step beside the window's deflate kernel (no kernel trace was taken)")
         os.remove(ppath); os.remove(path); os.rmdir(tmp)
-        out = a.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bam_recal.json")
+        out = a.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bam_requal.json" if a.apply_recal else "bam_recal.json")
         with open(out, "w") as f:
             json.dump(result, f, indent=1)
         print(json.dumps(result))
