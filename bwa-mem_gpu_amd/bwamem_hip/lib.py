@@ -22,7 +22,7 @@ def lib_path() -> str:
 # every symbol include/bwamem_hip.h and include/seed_gen.h declare
 EXPORTED_SYMBOLS = [
     "bmh_last_error", "bmh_device_count", "bmh_set_device", "bmh_index_upload", "bmh_index_from_device",
-    "bmh_index_free", "bmh_index_kbits_info", "bmh_index_probe", "bmh_index_replicate", "bmh_rccl_where", "bmh_rccl_unique_id", "bmh_rccl_comm_init_rank", "bmh_rccl_comm_destroy", "bmh_index_broadcast_rccl", "bmh_index_replicate_all", "bmh_shard_range", "bmh_index_densify_sa", "bmh_index_build", "bmh_seed_ws_create", "bmh_seed_ws_free", "bmh_seed_batch", "bmh_seed_last_timing", "bmh_reseed_opt_default", "bmh_seed_batch_reseed", "bmh_reseed_last_counts", "bmh_aligner_set_reseed",
+    "bmh_index_free", "bmh_index_kbits_info", "bmh_index_probe", "bmh_index_replicate", "bmh_rccl_where", "bmh_rccl_unique_id", "bmh_rccl_comm_init_rank", "bmh_rccl_comm_destroy", "bmh_index_broadcast_rccl", "bmh_index_replicate_all", "bmh_shard_range", "bmh_index_densify_sa", "bmh_index_build", "bmh_seed_ws_create", "bmh_seed_ws_free", "bmh_seed_batch", "bmh_seed_last_timing", "bmh_seed_ws_set_sample", "bmh_seeds_sample_state", "bmh_seeds_locate_all", "bmh_reseed_opt_default", "bmh_seed_batch_reseed", "bmh_reseed_last_counts", "bmh_aligner_set_reseed",
     "bmh_host_pin", "bmh_host_unpin", "bmh_extend_batch", "bmh_extend_batch_long", "bmh_extend_last_ms", "bmh_extend_last_unsupported", "bmh_extend_last_class_sizes", "bmh_extend_set_packed", "bmh_tune_set", "bmh_wtrace_start", "bmh_wtrace_stop", "bmh_wtrace_kept", "bmh_extend_release", "bmh_finalize_release", "bmh_matesw_release", "bmh_calib_gather", "bmh_calib_valu", "bmh_calib_valu_placed", "bmh_calib_last_clock",
     "bmh_jobs_frac_rep", "bmh_post_opt_default", "bmh_finalize_regs", "bmh_finalize_regs_device", "bmh_finalize_regs_device_last_ms", "bmh_finalize_regs_device_last_classes", "bmh_sam_need_cigar", "bmh_format_sam", "bmh_free",
     "bmh_pe_opt_default", "bmh_finalize_pairs", "bmh_finalize_pairs_dev", "bmh_dedup_regs_device", "bmh_finalize_pairs_deduped", "bmh_rescue_check_counts", "bmh_sam_need_cigar_pe", "bmh_format_sam_pe",
@@ -1914,6 +1914,12 @@ def load_library() -> C.CDLL:
     L.bmh_seed_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
                                  C.c_void_p, C.POINTER(SeedsT)]
     L.bmh_seed_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.bmh_seed_ws_set_sample.restype = C.c_int
+    L.bmh_seed_ws_set_sample.argtypes = [C.c_void_p, C.c_uint32]
+    L.bmh_seeds_sample_state.restype = C.c_uint32
+    L.bmh_seeds_sample_state.argtypes = [C.c_void_p]
+    L.bmh_seeds_locate_all.restype = C.c_int
+    L.bmh_seeds_locate_all.argtypes = [C.c_void_p, C.c_void_p]
     L.bmh_reseed_opt_default.argtypes = [C.POINTER(ReseedOpt)]
     L.bmh_seed_batch_reseed.restype = C.c_int
     L.bmh_seed_batch_reseed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
@@ -2142,11 +2148,15 @@ class Index:
 
 
 class SeedWorkspace:
-    def __init__(self, max_reads: int, max_bases: int, max_cands: int = 0, max_occ: int = 0):
+    def __init__(self, max_reads: int, max_bases: int, max_cands: int = 0, max_occ: int = 0, sample_max_occ: int = 500):
+        """sample_max_occ: bmh_seed_ws_set_sample -- of an SMEM with more occurrences only those are located that chaining with this max_occ reads (500: BWA's
+        default, what bmh_chain_opt_default sets); 0: every occurrence.  The chaining calls and seeds_to_host complete a sampled batch where they need more."""
         L = load_library()
         self.handle = L.bmh_seed_ws_create(max_reads, max_bases, max_cands, max_occ)
         if not self.handle:
             raise RuntimeError("bmh_seed_ws_create: " + _err(L))
+        if L.bmh_seed_ws_set_sample(self.handle, int(sample_max_occ)) != 0:
+            raise RuntimeError("bmh_seed_ws_set_sample: " + _err(L))
 
     def seed_batch(self, index: Index, reads_t, offs_t, lens_t, min_seed_len: int = 19, stream: int = 0, reseed: "ReseedOpt | None" = None) -> SeedsT:
         """reads_t/offs_t/lens_t: torch CUDA tensors (uint8 ASCII, int32/uint32 offsets and lengths).  reseed: a ReseedOpt with enable = 1 adds
@@ -2534,8 +2544,11 @@ def dev_jobs_to_host(j: DevJobsT, n_reads: int) -> dict:
 
 
 def seeds_to_host(s: SeedsT, n_reads: int) -> dict:
-    """Copy a bmh_seeds_t to numpy arrays (test/bench helper; uses torch only to read HBM)."""
+    """Copy a bmh_seeds_t to numpy arrays (test/bench helper; uses torch only to read HBM).  A sampled batch is completed first (bmh_seeds_locate_all)."""
     import torch
+    L = load_library()
+    if L.bmh_seeds_locate_all(C.byref(s), None) != 0:
+        raise RuntimeError("bmh_seeds_locate_all: " + _err(L))
 
     def rd(ptr, n, dt, tdt):
         if n == 0:

@@ -640,6 +640,7 @@ int run_batch(const aligner_t &A, lane_t &Ln, const bmh_read_set_t &rs, uint32_t
 	gate_hold_t gate(gpu_gate);
 	double t1 = now_s(); Ln.t[6] += t1 - tg;                     // (the wait at the gate is its own entry, not part of the upload)
 	bmh_seeds_t seeds;
+	RCK(bmh_seed_ws_set_sample(Ln.sws, A.rs.enable ? 0u : (uint32_t)A.co.max_occ));      // only what the chaining below reads is located (re-seeding: everything)
 	RCK(bmh_seed_batch_reseed(Ln.sws, A.idx, Ln.d_reads.p, Ln.d_offs.p, Ln.d_lens.p, n, A.co.min_seed_len, &A.rs, Ln.st, &seeds));
 	double t2 = now_s(); Ln.t[1] += t2 - t1;
 	// ---- chains, jobs, extension, regions

@@ -871,6 +871,13 @@ static int chain_check_args(const char *fn, bmh_chain_ws *w, const bmh_chain_opt
 	return BMH_OK;
 }
 
+// seeds that were sampled for another max_occ than this call's (bmh_seed_ws_set_sample) hold values in other slots than mem_chain will read: every slot is filled first
+static int chain_complete_seeds(const bmh_chain_opt_t *opt, const bmh_seeds_t *seeds, hipStream_t st)
+{
+	const uint32_t sampled = bmh_seeds_sample_state(seeds);
+	return sampled && sampled != (uint32_t)opt->max_occ ? bmh_seeds_locate_all(seeds, (void *)st) : BMH_OK;
+}
+
 static void chain_print_stats(bmh_chain_ws *w)
 {
 	fprintf(stderr, "[chain] lane kernel %.3f ms; wave kernels %.3f ms beside it:", w->ms[1], w->ms[2]);
@@ -889,6 +896,7 @@ extern "C" int bmh_chain_batch(bmh_chain_ws_t *w, const bmh_chain_opt_t *opt, co
 	memset(out, 0, sizeof(*out));
 	{ const int rc = chain_check_args("bmh_chain_batch", w, opt, idx, n_reads, seeds); if (rc != BMH_OK) return rc; }
 	hipStream_t st = (hipStream_t)stream_;
+	{ const int rc = chain_complete_seeds(opt, seeds, st); if (rc != BMH_OK) return rc; }
 	w->n_regs = w->n_jobs = 0; w->over_qlen = 0;
 	memset(w->class_counts, 0, sizeof(w->class_counts));
 	w->last_reads = d_reads; w->last_pac = idx->dev.pac; w->last_l_pac = idx->dev.l_pac;
@@ -1091,6 +1099,7 @@ extern "C" int bmh_chain_extend_merge(bmh_chain_ws_t *w, const bmh_chain_opt_t *
 	memset(out, 0, sizeof(*out));
 	{ const int rc = chain_check_args("bmh_chain_extend_merge", w, opt, idx, n_reads, seeds); if (rc != BMH_OK) return rc; }
 	hipStream_t st = (hipStream_t)stream_;
+	{ const int rc = chain_complete_seeds(opt, seeds, st); if (rc != BMH_OK) return rc; }
 	w->n_regs = w->n_jobs = 0;
 	memset(w->class_counts, 0, sizeof(w->class_counts));
 	w->last_reads = d_reads; w->last_pac = idx->dev.pac; w->last_l_pac = idx->dev.l_pac;

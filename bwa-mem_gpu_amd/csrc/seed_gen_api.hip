@@ -228,6 +228,7 @@ extern "C" mem_seed_v_gpu *seed_gpu(gpuseed_storage_vector *d)
 		HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
 		// candidate capacity = the hard bound on the candidates (one per base; bmh_seed_ws_create adds the slots its chunked appends lose): hard read
 		// sets need more than the library's default guess
+		// (no sample is set on it: every occurrence is located and copied to the host -- the contract here is the reference's)
 		bmh_seed_ws_t *ws = bmh_seed_ws_create(BATCH_READS, BATCH_BASES, BATCH_BASES, 0);
 		if (!ws) FATAL("seed_gpu: %s", bmh_last_error());
 		uint8_t *d_bases; uint32_t *d_offs, *d_lens;

@@ -173,9 +173,15 @@ void bmh_seed_ws_free(bmh_seed_ws_t *ws);
 /* Seeds of one batch, in HBM, in the reference's mem_seed_v_gpu layout
  * (seed_gen.h:68-75): per read SMEMs by end ascending, occurrences by SA row
  * ascending; score = #occurrences at the first slot of each SMEM group, 0 in
- * the others.  Pointers stay valid until the next call on the same workspace. */
+ * the others.  Pointers stay valid until the next call on the same workspace.
+ *
+ * A workspace with a sample set (bmh_seed_ws_set_sample, below) writes a SAMPLED batch: the layout, the counts and every group
+ * head (d_qbeg, d_score = s) are the complete batch's, but of a group of s > max_occ slots only the slots mem_chain reads with
+ * that max_occ hold values -- u = j * (s / max_occ), j < min(ceil(s / (s / max_occ)), max_occ) (src/bwamem.c:430-436); the
+ * slots between them are not written.  bmh_chain_batch / bmh_chain_extend_merge take such a batch as it is when their max_occ
+ * is the sample's and complete it first when not; whoever reads the arrays another way calls bmh_seeds_locate_all first. */
 typedef struct {
-	uint64_t n_seeds;            /* located occurrences in the batch */
+	uint64_t n_seeds;            /* occurrences laid out in the batch (all located unless the batch is sampled) */
 	uint64_t n_smems;            /* SMEM groups */
 	uint64_t n_cands;            /* forward candidates examined */
 	const uint64_t *d_rbeg;      /* [n_seeds] position in the fwd+revcomp text */
@@ -213,9 +219,23 @@ int bmh_seed_batch_reseed(bmh_seed_ws_t *ws, const bmh_index_t *idx, const uint8
  * after one that failed before the merge.  For tests. */
 int bmh_reseed_last_counts(uint64_t out[7]);
 
+/* Sampled locate.  max_occ > 0: the batches that follow locate, of every SMEM group, only the occurrences that chaining with this
+ * max_occ (bmh_chain_opt_t) reads -- see bmh_seeds_t -- where the index holds the whole suffix array (sa_intv 1); 0 (the default):
+ * every occurrence.  Batches of an index with sa_intv > 1, of bmh_seed_batch_reseed with re-seeding on and of the BMH_SEED_FUSED
+ * form are complete whatever the setting. */
+int bmh_seed_ws_set_sample(bmh_seed_ws_t *ws, uint32_t max_occ);
+/* How the arrays of `seeds` stand: the max_occ they were sampled with, 0 when every slot is filled (a complete batch, a completed
+ * one, or a record whose arrays belong to no live workspace, e.g. one built by hand). */
+uint32_t bmh_seeds_sample_state(const bmh_seeds_t *seeds);
+/* Fills every slot of a sampled batch (the full expand + locate over what its workspace kept of it; valid until the workspace's next
+ * batch; the index must still be alive) and waits for it.  Nothing to do, and BMH_OK, for seeds in the state 0. */
+int bmh_seeds_locate_all(const bmh_seeds_t *seeds, void *stream);
+
 /* per-kernel time of the last bmh_seed_batch, in ms (HIP events on the launch stream):
  * [0]=pack [1]=forward [2]=scatter+backward [3]=filter+scans [4]=expand [5]=locate [6]=total
- * (with BMH_SEED_FUSED=1: [1]=fused forward+backward [2]=sort of the SMEMs [3]=gather+scans) */
+ * (a sampled batch: [4]=the one pass that writes and locates the sampled slots, [5]=no kernel, the microseconds between
+ * two event records, never exactly 0;
+ * with BMH_SEED_FUSED=1: [1]=fused forward+backward [2]=sort of the SMEMs [3]=gather+scans) */
 void bmh_seed_last_timing(const bmh_seed_ws_t *ws, float ms[7]);
 
 /* Calibration: n_lanes lanes each gather `iters` random 32-byte index blocks (dependent != 0:
