@@ -347,6 +347,10 @@ struct dev_parser_t {
 	{
 		if (!st) HIPCK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
 		rp_file_t F[2]; memset(F, 0, sizeof(F));
+		// blank[f]: the file ends in this window and the window holds line ends alone ("\n" and "\r": what is left behind the last FASTQ record of a file that
+		// ends in blank or CR LF lines).  kseq skips to the next header and finds none, so the bytes are consumed and no kernel runs: as FASTA text the lone CR
+		// would raise the flag and the host would walk a window without a record
+		bool blank[2] = {false, false};
 		if (h_small.need(128 * sizeof(uint32_t)) != BMH_OK) return BMH_ENOMEM;
 		uint32_t *hs = h_small.as<uint32_t>();
 		uint64_t text = 0;
@@ -366,6 +370,7 @@ struct dev_parser_t {
 				while (p < n && (S[f].buf[p] == '\n' || S[f].buf[p] == '\r')) ++p;
 				if (p < n && S[f].buf[p] != '>' && S[f].buf[p] != '@') return 2;
 				F[f].fq = p < n && S[f].buf[p] == '@';
+				if (p == n && S[f].eof) { blank[f] = true; continue; }
 				if (P.b.need(n + 16) != BMH_OK || P.lid.need((size_t)n * 4) != BMH_OK || P.ctl.need(sizeof(rp_ctl_t)) != BMH_OK) return BMH_ENOMEM;
 				HIPCK(hipMemcpyAsync(P.b.p, S[f].buf, n, hipMemcpyHostToDevice, st));
 				F[f].b = P.b.as<uint8_t>();
@@ -391,9 +396,10 @@ struct dev_parser_t {
 			while (p < np && (pk[p] == '\n' || pk[p] == '\r')) ++p;
 			if (p == np ? np < F[f].n : (pk[p] != '>' && pk[p] != '@')) return 2;       // (more blank bytes than the peek holds: the host looks)
 			F[f].fq = p < np && pk[p] == '@';
+			if (p == np && F[f].eof) blank[f] = true;               // (np == n here)
 		}
 		for (int f = 0; f < nf; ++f) {
-			if (F[f].n == 0) continue;
+			if (F[f].n == 0 || blank[f]) continue;
 			per_file_t &P = D[f];
 			const uint32_t n = F[f].n, m = hs[f];
 			F[f].m = m;
@@ -420,7 +426,7 @@ struct dev_parser_t {
 		HIPCK(hipStreamSynchronize(st));
 		uint64_t nrec[2] = {0, 0};
 		for (int f = 0; f < nf; ++f) {
-			if (F[f].n == 0) continue;
+			if (F[f].n == 0 || blank[f]) continue;
 			const rp_ctl_t *c = (const rp_ctl_t *)(hs + 8 + 4 * f);
 			if (c->flag) return 2;
 			nrec[f] = F[f].fq ? c->n_flag_lines / 4 : (c->n_flag_lines ? c->n_flag_lines - (F[f].eof ? 0u : 1u) : 0u);

@@ -12,7 +12,13 @@ trailing "/<digit>" cut), and the pair r1.fq + r2.fq additionally as bseq_read i
 Per fixture F the archive holds F__names, F__comments (NUL-terminated, back to back), F__seq, F__qual (back to back; qual
 empty for FASTA) and F__lens.  Only the fixture texts and the archive are committed.
 
-Usage:  scripts/record_reads_golden.py --reference DIR [--out DIR]
+With --cases the same driver runs on the case table of tests/reads_cases.py instead: every text of cases() and both texts of every pair of pairs() (the
+refusals are texts kseq_read gives up on or this project refuses: they have no records to store).  It writes cases_expected.npz beside expected.npz, with
+the same five arrays per case plus <case>__sha1, the SHA-1 of the case's text (of text1 + NUL + text2 for a pair), so that the table and the archive
+cannot drift apart; a pair is stored as bseq_read interleaves it, up to the shorter file's last record.  The texts themselves are not stored: the table
+generates them.  The two long-line cases are stored like the others (their sequences compress to about 20 KB each).
+
+Usage:  scripts/record_reads_golden.py --reference DIR [--out DIR] [--cases]
 """
 import argparse
 import os
@@ -123,23 +129,61 @@ def pack(recs) -> dict:
                 seq=u8(b"".join(r[2] for r in recs)), qual=u8(b"".join(r[3] for r in recs)), lens=np.array([len(r[2]) for r in recs], np.uint32))
 
 
+def build_driver(reference: str, tmp: str) -> str:
+    src = os.path.join(tmp, "kseq_driver.c")
+    with open(src, "w") as f:
+        f.write(DRIVER)
+    exe = os.path.join(tmp, "kseq_driver")
+    subprocess.run(["cc", "-O1", "-I", os.path.join(reference, "src"), src, "-o", exe, "-lz"], check=True)
+    return exe
+
+
+def record_cases(reference: str, out: str) -> int:
+    import hashlib
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import reads_cases
+    arch, n = {}, 0
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = build_driver(reference, tmp)
+
+        def run(text: bytes):
+            p = os.path.join(tmp, "case.txt")
+            with open(p, "wb") as f:
+                f.write(text)
+            return parse_driver_output(subprocess.run([exe, p], check=True, stdout=subprocess.PIPE).stdout)
+
+        def store(name, recs, digest):
+            for k, v in pack(recs).items():
+                arch[f"{name}__{k}"] = v
+            arch[f"{name}__sha1"] = np.frombuffer(digest, np.uint8).copy()
+        for name, (text, _kind, _route) in reads_cases.cases().items():
+            recs = run(text)
+            store(name, recs, hashlib.sha1(text).digest()); n += len(recs)
+        for name, (t1, t2) in reads_cases.pairs().items():
+            inter = [r for pr in zip(run(t1), run(t2)) for r in pr]
+            store(name, inter, hashlib.sha1(t1 + b"\0" + t2).digest()); n += len(inter)
+    path = os.path.join(out, "cases_expected.npz")
+    np.savez_compressed(path, **arch)
+    print(f"wrote {path}: {len(reads_cases.cases())} cases and {len(reads_cases.pairs())} pairs, {n} records, {os.path.getsize(path)} bytes")
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reference", required=True, help="the reference's source tree (its src/kseq.h is compiled into the driver)")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "reads_input"))
+    ap.add_argument("--cases", action="store_true", help="record tests/reads_cases.py into cases_expected.npz instead of the fixtures")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
+    if a.cases:
+        return record_cases(a.reference, a.out)
     fx = fixtures(np.random.default_rng(20240607))
     for name, text in fx.items():
         with open(os.path.join(a.out, name), "wb") as f:
             f.write(text)
     arch = {}
     with tempfile.TemporaryDirectory() as tmp:
-        src = os.path.join(tmp, "kseq_driver.c")
-        with open(src, "w") as f:
-            f.write(DRIVER)
-        exe = os.path.join(tmp, "kseq_driver")
-        subprocess.run(["cc", "-O1", "-I", os.path.join(a.reference, "src"), src, "-o", exe, "-lz"], check=True)
+        exe = build_driver(a.reference, tmp)
         per = {}
         for name in fx:
             raw = subprocess.run([exe, os.path.join(a.out, name)], check=True, stdout=subprocess.PIPE).stdout
